@@ -5,7 +5,7 @@ One "step" = one `agent.train(buffer, 256)` of BASELINE.json config[1]: vlsac on
 (S=17, A=6, hidden=256, feature_dim=256, batch=256): 4 feature (VAE-ELBO) steps + critic step + actor and
 temperature step + Polyak updates = 7 optimizer steps, on synthetic replay resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 N>1 is launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`:
 one process per GPU, replay sharded (each rank owns its own ring and samples its own B=256 minibatch:
 weak scaling, global batch 256*N), gradients of every optimizer step all-reduced over RCCL/xGMI.
@@ -19,10 +19,9 @@ import os
 import sys
 import time
 
-# HIP maps streams onto a few hardware queues (4 by default) and streams that share one are serialised.  The pipelined train() uses two
-# streams (plus, with N > 1 ranks, one RCCL stream per process group): give the runtime enough queues, before it initialises.
-os.environ.setdefault('GPU_MAX_HW_QUEUES', '16')
-
+# HIP maps streams onto a few hardware queues (GPU_MAX_HW_QUEUES, 4 by default) and streams that share one are serialised.  The pipelined
+# train() uses two streams (plus, with N > 1 ranks, one RCCL stream per process group) and finds a pair on different queues by trial
+# (rlrep_amd/agent/sac/sac_agent.py _concurrent_stream_pair): the queue count is left to the runtime and the machine's environment.
 import numpy as np
 import torch
 
@@ -74,6 +73,36 @@ def synth_buffer(S, A, seed):
     buf = ReplayBuffer(S, A, max_size=REPLAY_N)
     buf.load(data['state'], data['action'], data['next_state'], data['reward'], data['done'])
     return buf, data
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def timed_outputs(agent, info):
+    """What the last timed train() gave its caller, as host arrays: the metric dict it returned (float64 scalars, `info.<key>`) and the
+    parameters, targets and log_alpha it left behind (`state.<name>`, in their own dtype: float32, log_alpha float64)."""
+    out = {f'info.{k}': np.asarray(float(v), np.float64) for k, v in info.items()}
+    out.update({f'state.{k}': v.numpy() for k, v in agent.core.state().items()})
+    return out
+
+
+def dump_outputs(outputs, path, limit=DUMP_LIMIT_BYTES, seed=0):
+    """Write every array as <path>/<name>.npy, at most `limit` bytes in all: if they are larger together, each array over its even share of
+    the limit is replaced by that many of its flattened elements at positions drawn by a generator seeded with `seed` (the same positions
+    in every run).  Returns what was written, for the result line."""
+    import re
+    os.makedirs(path, exist_ok=True)
+    share = limit // max(len(outputs), 1)
+    over = sum(a.nbytes for a in outputs.values()) > limit
+    sampled, nbytes = [], 0
+    for name, a in outputs.items():
+        if over and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+            sampled.append(name)
+        np.save(os.path.join(path, re.sub(r'[^\w.-]', '_', name) + '.npy'), a)
+        nbytes += a.nbytes
+    return {'dir': os.path.abspath(path), 'files': len(outputs), 'bytes': nbytes, 'sampled': sampled}
 
 
 def dominant_kernel_roofline(agent, B, F, H, reps=200):
@@ -518,7 +547,12 @@ def main():
     ap.add_argument('--no-extra-warmup', action='store_true', help='only the --warmup calls before the timed window (tests: a short run is a protocol check, not a measurement)')
     ap.add_argument('--quick', action='store_true', help='only the warm-up and the --steps window (no median repeats, no add / metric-fetch / main-loop legs): profiler runs')
     ap.add_argument('--pmc-json', default=None, help='PMC summary to take roofline.traffic from (default: the latest profiles/r*_pmc_<workload>.json)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed train() computed (its metric dict; parameters, targets and log_alpha after it) as DIR/<name>.npy, '
+                         'at most 64 MB in all (a fixed, seeded sample of each array that is over its share); rank 0 only')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     under_profiler = args.no_profile or any(k.startswith(('ROCPROF', 'ROCP_')) for k in os.environ) or 'rocprof' in os.environ.get('LD_PRELOAD', '')
     clock_helper = _spawn_clock_probe(under_profiler) if (args.gpus == 1 and int(os.environ.get('RANK', 0)) == 0) else None
 
@@ -618,7 +652,7 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            agent.train(buf, B)
+            info = agent.train(buf, B)
         agent.flush()           # pipelined graph mode: the last train()'s critic / actor steps belong inside the timed window
         barrier()
         dt = time.perf_counter() - t0
@@ -626,7 +660,8 @@ def main():
             tt = torch.tensor([dt], dtype=torch.float64, device='cuda')
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
-        return agent, dt
+        # (read after the window: the returned dict is fetched lazily, the parameters are those the last timed call left)
+        return agent, dt, (timed_outputs(agent, info) if args.dump_outputs else None)
 
     def form_of(agent):
         """what the agent actually runs (the fused form falls back to torch.distributed when its probe fails on this set of ranks)"""
@@ -648,9 +683,9 @@ def main():
         dp_forms, best = [], None
         for form in forms:
             rec = {'form': form}
-            agent_f, dt_f, ok = None, None, True
+            agent_f, dt_f, outputs_f, ok = None, None, None, True
             try:
-                agent_f, dt_f = build_and_time(form)
+                agent_f, dt_f, outputs_f = build_and_time(form)
                 rec['ran_as'] = form_of(agent_f)
                 rec['replicas_identical'] = replicas_check(agent_f)
             except Exception as e:          # noqa: BLE001  (every rank must drop the form together: agreed below)
@@ -662,17 +697,18 @@ def main():
                 rec.update(value=round((1 if args.scaling == 'strong' else world) * args.steps / dt_f, 2), ms_per_step=round(dt_f / args.steps * 1e3, 4),
                            fused_groups=sorted(agent_f.core.fused_groups) if getattr(agent_f.core, 'fused_groups', None) else None)
                 if rec['replicas_identical'] and (best is None or dt_f < best[1]):
-                    best = (agent_f, dt_f, form)
+                    best = (agent_f, dt_f, form, outputs_f)
             elif 'error' not in rec:
                 rec['error'] = 'failed on another rank'
             dp_forms.append(rec)
         if best is None:
             raise SystemExit('bench: no data-parallel form completed with identical replicas: ' + json.dumps(dp_forms))
-        agent, dt = best[0], best[1]
+        agent, dt, outputs = best[0], best[1], best[3]
         for d in dp_forms:
             d['chosen'] = d['form'] == best[2]
     else:
-        agent, dt = build_and_time(args.dp_form if (dist is not None and args.dp_form) else None)
+        agent, dt, outputs = build_and_time(args.dp_form if (dist is not None and args.dp_form) else None)
+    dumped = dump_outputs(outputs, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
     # median of 5 repeats.  The --steps window above is what `value` reports (the driver's contract: EXACTLY K steps); a short
     # window (the driver's 20 steps = 7 ms) is noisy by construction, so the same loop is also timed as 5 repeats of `rep_len` calls and the
     # median reported beside it.  The shader clock is sampled by rocm-smi WHILE those repeats run.
@@ -806,6 +842,8 @@ def main():
             'repeats': {'n': len(rep_rates), 'calls_each': rep_len, 'values': [round(v, 1) for v in rep_rates]},
             'clocks': clocks,
         }
+        if dumped:
+            out['dump_outputs'] = dumped
         # `roofline` describes the RUN: the kernel family with the largest share of GPU time -- its algorithmic flops (bytes), counted by the
         # library per stage, over the time its launches take inside this run, against the peak that bounds it; `traffic` from the committed
         # PMC summary of this workload.  Every family is listed in `kernel_families`.

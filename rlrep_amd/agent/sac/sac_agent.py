@@ -75,8 +75,8 @@ _STREAM_PAIR = {}
 
 
 def _concurrent_stream_pair(core, index=0):
-    """Two torch streams that really run side by side.  ROCm maps HIP streams onto a handful of hardware queues (4 by default; this package
-    asks for 16) and two streams that share one are serialised -- measured here: the same two launch chains overlapped 1.8x or 1.00x
+    """Two torch streams that really run side by side.  ROCm maps HIP streams onto a handful of hardware queues (GPU_MAX_HW_QUEUES, 4 by
+    default) and two streams that share one are serialised -- measured here: the same two launch chains overlapped 1.8x or 1.00x
     depending only on which streams they were given.  So candidates are TIMED: two short kernel chains back to back on one stream against
     one chain on each stream of a pair; streams that overlap with every stream kept so far are kept for the life of the process.
     index > 0 (several replicas inside one process: the loopback form of rlrep_amd/comm.py): pair `index` of a set whose members are ALL

@@ -36,11 +36,19 @@ SIZES = [1, 3, 64, 1000, 4096 + 3, 262144, 481810]        # ... 481 810: the vls
 OFFSETS = [0, 5, 64, 0, 128, 0, 16]                        # (odd offsets take the element-wise path)
 
 
-def _spawn(fn, world, *args, timeout=400):
+def _spawn(fn, world, *args, timeout=400, own_cus=False):
+    """own_cus: every rank gets a disjoint share of the GPU's compute units (HSA_CU_MASK, applied to the queues its runtime creates), as
+    every rank has a chip of its own between GPUs.  Without it a rank that lags behind -- a host-side metrics read, a select_action -- may find
+    no room for its launches beside the blocks of its peers' optimizer launches, which wait on the device for it and hold their slots until a
+    bounded wait runs out: nothing obliges the hardware to preempt them."""
     port = _free_port()
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    procs = [ctx.Process(target=_entry, args=(r, world, port, q, fn) + args) for r in range(world)]
+    masks = [None] * world
+    if own_cus:
+        n = torch.cuda.get_device_properties(0).multi_processor_count // world
+        masks = [f'0:{r * n}-{(r + 1) * n - 1}' for r in range(world)]
+    procs = [ctx.Process(target=_entry, args=(r, world, port, q, fn, masks[r]) + args) for r in range(world)]
     for p in procs:
         p.daemon = True
         p.start()
@@ -63,9 +71,12 @@ def _spawn(fn, world, *args, timeout=400):
     return res
 
 
-def _entry(rank, world, port, q, body, *args):
-    """Process entry point (top level: the spawn context pickles it by name); `body` names one of the *_body functions below."""
+def _entry(rank, world, port, q, body, cu_mask, *args):
+    """Process entry point (top level: the spawn context pickles it by name); `body` names one of the *_body functions below; `cu_mask`: this
+    rank's compute units (see _spawn), set before the process makes its first HIP call."""
     try:
+        if cu_mask:
+            os.environ['HSA_CU_MASK'] = cu_mask
         os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
         dist.init_process_group('gloo', init_method=f'tcp://127.0.0.1:{port}', rank=rank, world_size=world)
         torch.cuda.set_device(0)
@@ -228,11 +239,15 @@ def test_train_with_exchanges_inside_the_launches_equals_gloo(case, world):
         assert np.array_equal(v, out[False][0][k]), f'in-launch exchanges != rank-ordered gloo at {k}'
 
 
-@pytest.mark.parametrize('case', ['sac_tiny', 'vlsac_tiny'])
-def test_two_shot_in_the_optimizer_launch_is_the_rank_ordered_sum_bit_for_bit(case):
-    """Three ranks: the two-shot form inside the optimizer launches (forced for every slice: RLREP_ENABLE=dp_two_shot_kb=0.001 -- reduce-scatter
-    into the reduced region, RED handshake, all-gather from the shards' owners) == the one-shot pull == gloo summed in rank order."""
-    world, out = 3, {}
+@pytest.mark.parametrize('case,world', [('sac_tiny', 3), ('vlsac_tiny', 3), ('spedersac_tiny', 3), ('ctrlsac_tiny', 3), ('spedersac_tiny', 4),
+                                        ('ctrlsac_tiny', 4)],
+                         ids=['sac_tiny', 'vlsac_tiny', 'spedersac_tiny', 'ctrlsac_tiny', 'spedersac_tiny-4', 'ctrlsac_tiny-4'])
+def test_two_shot_in_the_optimizer_launch_is_the_rank_ordered_sum_bit_for_bit(case, world):
+    """Three / four ranks (four = BASELINE config 4's rank count): the two-shot form inside the optimizer launches (forced for every slice:
+    RLREP_ENABLE=dp_two_shot_kb=0.001 -- reduce-scatter into the reduced region, RED handshake, all-gather from the shards' owners) == the
+    one-shot pull == gloo summed in rank order, bit for bit, and equal (1e-4) to the CPU oracle on the concatenated global batch -- spedersac's
+    Phibar / v and ctrlsac's in-batch negatives over ALL ranks' minibatches included."""
+    out = {}
     for form, (fused, enable) in (('two_shot', (True, 'dp_two_shot_kb=0.001')), ('one_shot', (True, 'dp_two_shot_kb=0')), ('gloo', (False, ''))):
         res = _spawn('_agent_body', world, case, fused, False, 3, False, enable, True)
         for r in range(1, world):
@@ -242,6 +257,15 @@ def test_two_shot_in_the_optimizer_launch_is_the_rank_ordered_sum_bit_for_bit(ca
     for form in ('one_shot', 'gloo'):
         for k, v in out['two_shot'].items():
             assert np.array_equal(v, out[form][k]), f'two-shot != {form} at {k}'
+    from fixture_io import Case, rel_l2
+    from test_dp import _inputs, _oracle_global
+    c = Case(case)
+    rs = np.random.RandomState(11)                              # (the draws _agent_body injects, call by call)
+    per_call = [_inputs(c, rs, world) for _ in range(3)]
+    P = _oracle_global(c, per_call, trains=3).state()
+    for k, v in out['two_shot'].items():
+        if k in P and not k.endswith('noise'):
+            assert rel_l2(v, P[k].numpy()) < 1e-4, k
 
 
 @pytest.mark.parametrize('case,world,pipeline', [('spedersac_ant512', 2, True), ('ctrlsac_hc256', 2, True), ('vlsac_hc', 3, False)])
@@ -251,10 +275,12 @@ def test_default_graph_forms_with_exchanges_inside_equal_rank_ordered_gloo_segme
     state of graph segments around gloo collectives summed in rank order.  vlsac_hc with three ranks: its 1.93 MB feature slice and 1.05 MB
     critic slice take the two-shot form inside the optimizer launch -- as ONE graph per train() (RLREP_PIPELINE=0): three ranks share the test
     box's one GPU, and the waiting blocks of three ranks' two chains (3 x (472 + 265) of 1 280 resident) would leave no room for the launches
-    they wait for; between GPUs every rank has a chip of its own (csrc/dp_pull.h, "Progress with SEVERAL channels in flight")."""
+    they wait for; between GPUs every rank has a chip of its own (csrc/dp_pull.h, "Progress with SEVERAL channels in flight") -- and so it has
+    here: a third of the compute units each (_spawn own_cus), where one launch of a rank that fell behind does not have to fit beside two peers'
+    waiting optimizer launches."""
     out = {}
     for form, fused in (('fused', True), ('segments', False)):
-        res = _spawn('_agent_body', world, case, fused, True, 5, False, '', True, pipeline, timeout=300)
+        res = _spawn('_agent_body', world, case, fused, True, 5, False, '', True, pipeline, timeout=300, own_cus=not pipeline)
         for r in range(1, world):
             for k, v in res[0][0].items():
                 assert np.array_equal(v, res[r][0][k]), f'replicas diverged at {k} ({form}, rank {r})'

@@ -110,20 +110,23 @@ def test_rff_linear_critic_initialisation_quirk():
 
 def test_gaussian_policy_sample_with_pinned_noise():
     import torch.distributions.normal as tdn
+    import importlib
     cls = _resolve('networks.policy.GaussianPolicy')
+    dev = importlib.import_module(cls.__module__).device        # the module-level device its action_scale / action_bias are placed on
     pol = cls(action_space=_Space(), **META['policy_sample']['ctor'])
     pol.load_state_dict(_sd('policy_sample'), strict=True)
-    eps = torch.from_numpy(Z['policy_sample/eps'])
+    pol.to(dev)
+    eps = torch.from_numpy(Z['policy_sample/eps']).to(dev)
     orig_sn, orig_rl = tdn._standard_normal, torch.randn_like
     tdn._standard_normal = lambda shape, dtype, device: eps.clone()
     torch.randn_like = lambda t, **k: eps.clone()
     try:
         with torch.no_grad():
-            out = pol.sample(torch.from_numpy(Z['policy_sample/in/0']))
+            out = pol.sample(torch.from_numpy(Z['policy_sample/in/0']).to(dev))
     finally:
         tdn._standard_normal, torch.randn_like = orig_sn, orig_rl
     for i, r in enumerate(out):
-        assert np.allclose(r.numpy(), Z[f'policy_sample/out/{i}'], rtol=1e-5, atol=1e-5), i
+        assert np.allclose(r.cpu().numpy(), Z[f'policy_sample/out/{i}'], rtol=1e-5, atol=1e-5), i
 
 
 def test_live_actor_distribution_with_pinned_noise():
