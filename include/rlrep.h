@@ -483,6 +483,46 @@ int64_t rlrep_launch_counter(void);
  * reference networks/vae.py:40-57,83-85,112-117 and the MLPs of agent/<alg>/<alg>_agent.py. */
 int32_t rlrep_front_end_counts(int64_t* out4);
 
+/* ---- seed groups: R independent sac agents in the same launches (additive to ABI 4) ----------------------------------------------------
+ * A group is R members of identical dims / hyper whose blocks -- the seven arenas of rlrep_agent_create -- are laid out identically at a
+ * constant byte stride in ONE allocation: member r's copy of any word is member 0's address + r * member_stride_bytes.  The step programs are
+ * built once, against member 0's arenas; every launch of the agent then runs all members (grid y = member) and moves every pointer it
+ * dereferences to the member's block.  Each member computes exactly what a standalone agent with its seed computes: same tiles, same
+ * summation order, nothing shared between members.  The returned handle is used with the ordinary step entry points (rlrep_critic_step,
+ * rlrep_actor_alpha_step, rlrep_update_target, rlrep_prefetch_policy, rlrep_end_train), which then run every member; the train prologue and
+ * select_action take their group forms below.  The entry points that have no group form -- rlrep_set_batch, rlrep_replay_sample (other than
+ * the gather the group prologue already did), rlrep_prefetch_batch*, rlrep_prefetch_policy_early, the deferred-chain and image calls,
+ * rlrep_sync_frozen, rlrep_actor_forward, rlrep_select_action, rlrep_run_stage, rlrep_chain_status -- refuse a group with RLREP_ERR_ARG and a
+ * message; a step whose program reaches a kernel without a group form fails with RLREP_ERR_HIP.  No entry point runs member 0 alone.
+ * Rejected with RLREP_ERR_ARG and a message: alg != sac, members outside [1, rlrep_group_max_members()], a stride that is not a positive
+ * multiple of 256 or is smaller than the member span (lowest arena pointer to the end of the highest arena), world_size > 1.
+ * On success members 1..R-1 start as byte copies of member 0's block (after its creation); the caller then writes each member's parameters.
+ * Reference: main.py:63-68 (one run per seed) -- a group runs several seeds at once. */
+int32_t rlrep_group_create(const rlrep_dims* dims, const rlrep_hyper* hyper, const rlrep_arenas* member0_arenas, int32_t members,
+                           int64_t member_stride_bytes, void* stream, rlrep_agent** out);
+int32_t rlrep_group_max_members(void);
+/* members of a group agent; 0 for an ordinary agent */
+int32_t rlrep_group_members(rlrep_agent* agent);
+/* the Philox seed of every member (n = members): member r's index and noise pools are drawn as rlrep_train_prologue draws them with seeds[r] */
+int32_t rlrep_group_set_seeds(rlrep_agent* agent, const uint64_t* seeds_host, int32_t n, void* stream);
+/* rlrep_train_prologue for every member, in ONE launch: member r draws with its seed, gathers from ring_dev + r * ring_stride_bytes bounded
+ * by size_dev[r], writes its pools at idx_pool_dev / eps_pool_dev + r * member stride (the pools must lie inside member 0's block) and counts its
+ * own steps. */
+int32_t rlrep_group_train_prologue(rlrep_agent* agent, const float* ring_dev, int64_t ring_stride_bytes, const int32_t* size_dev,
+                                   int32_t* idx_pool_dev, int64_t n_idx, float* eps_pool_dev, int64_t n_eps, uint64_t idx_offset,
+                                   uint64_t eps_offset, int32_t batch, void* stream);
+/* size a group's step programs for `batch` (blocking table uploads when it changes: call it outside a graph capture).  Launches nothing. */
+int32_t rlrep_group_prepare(rlrep_agent* agent, int32_t batch);
+/* rlrep_select_action for every member in ONE launch: member r reads observation r of obs_host [members, state_dim] and writes action r of
+ * action_host [members, action_dim] (both pinned host memory, read / written in place) with its own actor; explore: its draw is
+ * rlrep_fill_normal(eps[A], 1, seeds[r], offset), as a standalone agent with seed seeds[r] draws it.  (reference agent/sac/sac_agent.py:89-96) */
+int32_t rlrep_group_select_action(rlrep_agent* agent, const float* obs_host, int32_t explore, uint64_t offset, float lo, float hi,
+                                  float* action_host, void* stream);
+/* rlrep_replay_add_sized for `members` rings ring_dev + r * ring_stride_floats, in ONE launch: member r's nrows staged rows start at
+ * rows_host + r * rows_stride_floats (pinned), its fill level goes to size_dev[r]. */
+int32_t rlrep_group_replay_add_sized(float* ring_dev, int64_t ring_stride_floats, int32_t members, int64_t capacity, int32_t row_floats, int64_t ptr,
+                                     const float* rows_host, int64_t rows_stride_floats, int64_t nrows, int32_t* size_dev, int32_t new_size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

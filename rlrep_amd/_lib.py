@@ -79,6 +79,14 @@ def _load():
         'rlrep_metric_names': (i32, [i32, vp, i32]),
         'rlrep_agent_create': (i32, [P(Dims), P(Hyper), P(Arenas), vp, P(vp)]),
         'rlrep_agent_destroy': (None, [vp]),
+        'rlrep_group_create': (i32, [P(Dims), P(Hyper), P(Arenas), i32, i64, vp, P(vp)]),
+        'rlrep_group_max_members': (i32, []),
+        'rlrep_group_members': (i32, [vp]),
+        'rlrep_group_set_seeds': (i32, [vp, vp, i32, vp]),
+        'rlrep_group_train_prologue': (i32, [vp, vp, i64, vp, vp, i64, vp, i64, u64, u64, i32, vp]),
+        'rlrep_group_prepare': (i32, [vp, i32]),
+        'rlrep_group_select_action': (i32, [vp, vp, i32, u64, f32, f32, vp, vp]),
+        'rlrep_group_replay_add_sized': (i32, [vp, i64, i32, i64, i32, i64, vp, i64, i64, vp, i32, vp]),
         'rlrep_set_batch': (i32, [vp, i32, P(Batch), vp]),
         'rlrep_replay_row_floats': (i32, [P(Dims)]),
         'rlrep_replay_add': (i32, [vp, i64, i32, i64, vp, i64, vp]),

@@ -195,7 +195,7 @@ class SACAgent(object):
                      target_update_period=self.target_update_period,
                      extra_feature_steps=int(self.extra_feature_steps), learn_alpha=int(self.learnable_temperature))
         hyper.update({k: float(v) for k, v in self._hyper.items()})
-        self.core = HipCore(self.ALG, dims, hyper, world_size=self.world_size, loopback=self._loopback)
+        self.core = self._make_core(dims, hyper)
         self.core.alpha_state[0] = float(np.log(self._alpha0))      # quirk Q1: float64 log_alpha
         self._init_parameters()
         if self._loopback is not None:
@@ -267,6 +267,9 @@ class SACAgent(object):
         self._img_on = False               # some captured graph relies on managed images
         self._img_dirty = True
         self._img_seen = None
+
+    def _make_core(self, dims, hyper):
+        return HipCore(self.ALG, dims, hyper, world_size=self.world_size, loopback=self._loopback)
 
     # parameter initialisation (values only; layout is the library's)
     def _orth(self, name, gain=1.0):

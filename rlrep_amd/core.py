@@ -101,8 +101,10 @@ class LazyInfo(dict):
 
 
 class HipCore:
-    def __init__(self, alg, dims, hyper, device=None, world_size=1, loopback=None):
-        """loopback: a (LoopbackGroup, rank) pair -- this core is rank `rank` of `world_size` replicas inside ONE process (rlrep_amd/comm.py)."""
+    def __init__(self, alg, dims, hyper, device=None, world_size=1, loopback=None, members=0, member_extra_bytes=0):
+        """loopback: a (LoopbackGroup, rank) pair -- this core is rank `rank` of `world_size` replicas inside ONE process (rlrep_amd/comm.py).
+        members > 0: a seed group (rlrep_group_create) -- `members` copies of the block at a stride of `member_stride` bytes in one allocation,
+        each with `member_extra_bytes` of caller space behind the arenas (member_extra_offset); the tensors below are member 0's."""
         if not torch.cuda.is_available():
             raise RuntimeError('rlrep_amd needs an MI355X (no CPU fallback): torch.cuda.is_available() is False')
         self.alg = alg
@@ -138,8 +140,12 @@ class HipCore:
         if total >= (1 << 34):
             raise RuntimeError(f'rlrep_amd: the arenas of this agent need {total} bytes in one block; the tile engine addresses operands '
                                'as 32-bit float offsets from one base (16 GiB)')
-        self._block = torch.zeros(total + 256, dtype=torch.uint8, device=dev)
+        self.members = int(members)
+        self.member_extra_offset = total
+        self.member_stride = (total + int(member_extra_bytes) + 255) & ~255
+        self._block = torch.zeros(max(self.members, 1) * self.member_stride + 256 if self.members else total + 256, dtype=torch.uint8, device=dev)
         skew = (-self._block.data_ptr()) & 255
+        self._skew, self._offs, self._sizes = skew, offs, sizes
 
         def carve(i, dtype):
             return self._block[skew + offs[i]:skew + offs[i] + sizes[i]].view(dtype)
@@ -176,7 +182,11 @@ class HipCore:
                          self.alpha_state.data_ptr())
         h = C.c_void_p()
         torch.cuda.synchronize()
-        check(lib.rlrep_agent_create(C.byref(self.dims), C.byref(self.hyper), C.byref(ar), _stream(), C.byref(h)), 'agent_create')
+        if self.members:
+            check(lib.rlrep_group_create(C.byref(self.dims), C.byref(self.hyper), C.byref(ar), self.members, self.member_stride, _stream(), C.byref(h)),
+                  'group_create')
+        else:
+            check(lib.rlrep_agent_create(C.byref(self.dims), C.byref(self.hyper), C.byref(ar), _stream(), C.byref(h)), 'agent_create')
         self.h = h
         if self.exchange is not None:
             # gradient slices up to 4 MB (RLREP_ENABLE=dp_fused_mb=N) are summed inside their optimizer launch; larger ones (diffsrsac's 198 MB nabla-mu

@@ -5,6 +5,7 @@
 #include "kparams.h"
 #include "heads_vae_tile.h"      // (also: RL_CONST_AS)
 #include "x3.h"
+#include "group.h"
 
 // ------------------------------------------------------------------------------------------------
 // minibatch slot fill: replay-ring gather (idx) or five separate arrays (reference Batch fields)
@@ -151,29 +152,27 @@ __global__ __launch_bounds__(256) void shadow_kernel(const ShadowEnt* __restrict
     shadow_tile_body(sh, nsh, base, blockIdx.x, target != 0);
 }
 extern "C" int rl_launch_shadow(const ShadowEnt* sh_dev, int nsh, int ntiles, const float* base, int target, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     if (ntiles <= 0 || nsh <= 0) return 0;
     hipLaunchKernelGGL(shadow_kernel, dim3(ntiles), dim3(256), 0, st, sh_dev, nsh, base, target);
     return (int)hipGetLastError();
 }
 
 __global__ __launch_bounds__(256) void train_prologue_kernel(TrainPrologue p) {
-    __builtin_amdgcn_s_setprio(3);      // small launch on a latency-critical chain (see gemm16_kernel)
-    const int bid = blockIdx.x;
-    if (bid < p.nb_idx) philox_fill_body(p.idx, bid, p.nb_idx);
-    else if (bid < p.nb_idx + p.nb_eps) philox_fill_body(p.eps, bid - p.nb_idx, p.nb_eps);
-    else if (bid >= p.nb_idx + p.nb_eps + p.nb_fill) shadow_tile_body(p.sh, p.nsh, p.sh_base, bid - p.nb_idx - p.nb_eps - p.nb_fill, false);
-    else {
-        IdxGen g; g.on = 1; g.seed = p.idx.seed; g.stream_id = p.idx.stream_id;
-        g.off = p.idx.offset + (unsigned long long)(*p.idx.step_dev + p.idx.step_add);
-        g.hi = p.idx.hi_dev ? *p.idx.hi_dev : p.idx.hi;
-        fill_slot_body(p.fill, g, bid - p.nb_idx - p.nb_eps, p.nb_fill);
-    }
-    // steps += 1.  Every block of this launch reads the counter -- so none of them may write what the others read: the blocks read word 2 of the
-    // counter block ("the counter as the next prologue will read it", p.idx.step_dev), ONE thread writes word 0 = word 2 + 1 (what every later
-    // launch reads), and the first optimizer launch behind this one in the chain brings word 2 up to word 0 (AdamTask::sync_steps).  (It used to
-    // be one word, bumped by the block that drew the last of ~300 tickets from an atomic counter: 3.6 us of same-address atomics at the head of
-    // every train(); timing-only build without it: 3 921 -> 3 958 train()/s.)
-    if (bid == 0 && threadIdx.x == 0) *p.counter = *p.idx.step_dev + 1;
+#include "train_prologue_body.h"
+}
+// group form: member m = blockIdx.y draws from its own seed, gathers from its own ring (bounded by its own size word) and counts its own steps
+__global__ __launch_bounds__(256) void train_prologue_kernel_grp(TrainPrologue p0, long long mstride, long long rstride, const unsigned long long* __restrict__ seeds) {
+    const int m = blockIdx.y;
+    const long long dm = (long long)m * mstride;
+    TrainPrologue p = p0;
+    rl_rb(p.idx.dst_i, dm); rl_rb(p.idx.step_dev, dm); p.idx.seed = seeds[m];
+    if (p.idx.hi_dev) p.idx.hi_dev += m;
+    rl_rb(p.eps.dst_f, dm); rl_rb(p.eps.step_dev, dm); p.eps.seed = seeds[m];
+    if (p.eps.hi_dev) p.eps.hi_dev += m;
+    rl_rebase(p.fill, dm, (long long)m * rstride);
+    rl_rb(p.counter, dm); rl_rb(p.ticket, dm);
+#include "train_prologue_body.h"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -203,68 +202,17 @@ __global__ __launch_bounds__(256) void policy_fwd_kernel(PolicyFwd p) {
 // for its A elements.  obs / act may be pinned HOST buffers (mapped): no copy launch on either side -- main.py's loop pays one launch and one
 // stream synchronisation per environment step instead of nine dependent operations (tools/exp/host_loop.py).
 __global__ __launch_bounds__(1024) void select_action_kernel(SelectAct p) {
-    extern __shared__ float sm[];                        // obs[S] | h1[Ha] | h2[Ha] | o[2A]
-    float* const x0 = sm; float* const h1 = x0 + p.S; float* const h2 = h1 + p.Ha; float* const o = h2 + p.Ha;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;          // 16 waves
-    for (int k = threadIdx.x; k < p.S; k += 1024) x0[k] = p.obs[k];
-    __syncthreads();
-    // a wave takes rows w, w + 16, ...; EIGHT rows at a time with all their loads in flight together (a row after the other is one exposed
-    // round trip per row: 147 us for the three layers on one workgroup, measured)
-    auto layer = [&](const float* __restrict__ W, const float* __restrict__ b, const float* in, int K, int N, float* out, bool elu) {
-        for (int j0 = w; j0 < N; j0 += 16 * 8) {
-            float s[8];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) s[r] = 0.f;
-            for (int k0 = 0; k0 < K; k0 += 256) {
-                float wv[8][4], xv[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { const int k = k0 + lane + 64 * i; xv[i] = k < K ? in[k] : 0.f; }
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const int j = min(j0 + 16 * r, N - 1);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) wv[r][i] = W[(size_t)j * K + min(k0 + lane + 64 * i, K - 1)];
-                }
-#pragma unroll
-                for (int r = 0; r < 8; ++r)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) s[r] = fmaf(wv[r][i], xv[i], s[r]);
-            }
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const int j = j0 + 16 * r;
-                const float t = wave_sum(s[r]);
-                if (lane == 0 && j < N) { const float v = t + b[j]; out[j] = elu ? elu_f(v) : v; }
-            }
-        }
-    };
-    layer(p.W1, p.b1, x0, p.S, p.Ha, h1, true);
-    __syncthreads();
-    layer(p.W2, p.b2, h1, p.Ha, p.Ha, h2, true);
-    __syncthreads();
-    layer(p.W3, p.b3, h2, p.Ha, 2 * p.A, o, false);
-    __syncthreads();
-    const int j = threadIdx.x;
-    if (j < p.A) {
-        float e = 0.f;
-        if (p.explore) {                                  // element j of philox_fill_body's normal stream (kind 0, std 1, stream 0, no device counter)
-            const long long q = j >> 2;
-            uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), (uint32_t)p.offset, (uint32_t)(p.offset >> 32)};
-            philox4x32_10(c, (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-            const int h = (j & 3) >> 1;
-            const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-            const float u2 = ((float)(c[2 * h + 1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-            const float rad = sqrtf(-2.0f * logf(u1));
-            float sn, cs;
-            sincosf(6.283185307179586f * u2, &sn, &cs);
-            e = (j & 1) ? rad * sn : rad * cs;
-        }
-        const float mu = o[j];
-        const float t = tanhf(o[p.A + j]);
-        const float sg = expf(-5.f + 3.5f * (t + 1.f));
-        const float y = tanhf(mu + e * sg);
-        p.act[j] = fminf(fmaxf(y, p.lo), p.hi);
-    }
+#include "select_action_body.h"
+}
+// group form: member m = blockIdx.y acts on observation m with its own actor and its own Philox seed, writes action m
+__global__ __launch_bounds__(1024) void select_action_kernel_grp(SelectAct p0, long long mstride, const unsigned long long* __restrict__ seeds) {
+    const int m = blockIdx.y;
+    const long long dm = (long long)m * mstride;
+    SelectAct p = p0;
+    p.obs += (long long)m * p.S; p.act += (long long)m * p.A;
+    rl_rb(p.W1, dm); rl_rb(p.b1, dm); rl_rb(p.W2, dm); rl_rb(p.b2, dm); rl_rb(p.W3, dm); rl_rb(p.b3, dm);
+    p.seed = seeds[m];
+#include "select_action_body.h"
 }
 
 // gradient of the actor loss w.r.t. the trunk output [mu | rho]; h = dL/d(action) from the critic path
@@ -365,85 +313,21 @@ __device__ __forceinline__ float row_dot(const float* __restrict__ e, const floa
 }
 
 __global__ __launch_bounds__(256) void qhead_critic_kernel(QHeadCritic p) {
-    __shared__ float shp[4][4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const float alpha = (float)exp(p.alpha_state[0]);
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int b = blockIdx.x * 4 + w; b < p.B; b += gridDim.x * 4) {
-        const size_t ro = (size_t)b * (p.ldE ? p.ldE : p.H);
-        // the four dot products of the row in ONE pass: 8 loads per step in flight together (one after the other they were four exposed
-        // L2 round trips per row, each followed by its wave reduction); per-lane summation order and reductions as row_dot
-        // the row's scalars go out with the first operand loads (issued behind the reductions they were a second exposed round trip per row)
-        const float bt0 = p.bt[0][0], bt1 = p.bt[1][0], bc0 = p.bc[0][0], bc1 = p.bc[1][0], lpb = p.logp[b], Rb = p.R[b], Db = p.D[b];
-        __builtin_amdgcn_sched_barrier(0);
-        float dd0 = 0.f, dd1 = 0.f, dd2 = 0.f, dd3 = 0.f;
-#pragma unroll 4
-        for (int k = lane; k < p.H; k += 64) {
-            const float e0 = p.Et[0][ro + k], e1 = p.Et[1][ro + k], e2 = p.Ec[0][ro + k], e3 = p.Ec[1][ro + k];
-            const float w0 = p.wt[0][k], w1 = p.wt[1][k], w2 = p.wc[0][k], w3 = p.wc[1][k];
-            dd0 = fmaf(e0, w0, dd0); dd1 = fmaf(e1, w1, dd1); dd2 = fmaf(e2, w2, dd2); dd3 = fmaf(e3, w3, dd3);
-        }
-        const float tq1 = wave_sum(dd0) + bt0;
-        const float tq2 = wave_sum(dd1) + bt1;
-        const float q1 = wave_sum(dd2) + bc0;
-        const float q2 = wave_sum(dd3) + bc1;
-        const float tv = fminf(tq1, tq2) - alpha * lpb;
-        const float y = Rb + (1.f - Db) * p.gamma * tv;
-        const float d1 = q1 - y, d2 = q2 - y;
-        const float g1 = 2.f * d1 * p.inv_batch, g2 = 2.f * d2 * p.inv_batch;
-        if (p.train) {
-            for (int k = lane; k < p.H; k += 64) {
-                p.GE[0][ro + k] = g1 * p.wc[0][k] * elu_grad_from_out(p.Ec[0][ro + k]);
-                p.GE[1][ro + k] = g2 * p.wc[1][k] * elu_grad_from_out(p.Ec[1][ro + k]);
-            }
-            if (lane == 0) { p.dq[b] = g1; p.dq[p.B + b] = g2; }
-        }
-        acc[0] += d1 * d1; acc[1] += d2 * d2; acc[2] += q1; acc[3] += q2;
-    }
-    if (lane == 0) { for (int i = 0; i < 4; ++i) shp[w][i] = acc[i]; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const int i = threadIdx.x;
-        p.partial[4 * blockIdx.x + i] = ((shp[0][i] + shp[1][i]) + shp[2][i]) + shp[3][i];
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && p.step) bump_group(p.step);
+#include "qhead_critic_body.h"
+}
+__global__ __launch_bounds__(256) void qhead_critic_kernel_grp(QHeadCritic p0, long long mstride) {
+    QHeadCritic p = p0;
+    rl_rebase(p, (long long)blockIdx.y * mstride);
+#include "qhead_critic_body.h"
 }
 
 __global__ __launch_bounds__(256) void qhead_actor_kernel(QHeadActor p) {
-    __shared__ float shp[4][2];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const float alpha = (float)exp(p.alpha_state[0]);
-    float accl = 0.f, accc = 0.f;
-    for (int b = blockIdx.x * 4 + w; b < p.B; b += gridDim.x * 4) {
-        const size_t ro = (size_t)b * (p.ldE ? p.ldE : p.H);
-        const float bc0 = p.bc[0][0], bc1 = p.bc[1][0], lp = p.logp[b];          // (out with the first operand loads: see qhead_critic_kernel)
-        __builtin_amdgcn_sched_barrier(0);
-        float d0 = 0.f, d1 = 0.f;                  // both dot products in one pass (see qhead_critic_kernel)
-#pragma unroll 4
-        for (int k = lane; k < p.H; k += 64) {
-            const float e0 = p.Ec[0][ro + k], e1 = p.Ec[1][ro + k], w0 = p.wc[0][k], w1 = p.wc[1][k];
-            d0 = fmaf(e0, w0, d0); d1 = fmaf(e1, w1, d1);
-        }
-        const float q1 = wave_sum(d0) + bc0;
-        const float q2 = wave_sum(d1) + bc1;
-        // d(-min(q1,q2))/dq_i : -1 to the arg-min head, ties split 1/2 (torch.min backward)
-        float s1, s2;
-        if (q1 < q2) { s1 = 1.f; s2 = 0.f; } else if (q2 < q1) { s1 = 0.f; s2 = 1.f; } else { s1 = s2 = 0.5f; }
-        const float g1 = -s1 * p.inv_batch, g2 = -s2 * p.inv_batch;
-        for (int k = lane; k < p.H; k += 64) {
-            p.GE[0][ro + k] = g1 * p.wc[0][k] * elu_grad_from_out(p.Ec[0][ro + k]);
-            p.GE[1][ro + k] = g2 * p.wc[1][k] * elu_grad_from_out(p.Ec[1][ro + k]);
-        }
-        accl += alpha * lp - fminf(q1, q2);
-        accc += -lp - p.target_entropy;
-    }
-    if (lane == 0) { shp[w][0] = accl; shp[w][1] = accc; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        p.partial_loss[blockIdx.x] = ((shp[0][0] + shp[1][0]) + shp[2][0]) + shp[3][0];
-        p.partial_c[blockIdx.x] = ((shp[0][1] + shp[1][1]) + shp[2][1]) + shp[3][1];
-        if (blockIdx.x == 0 && p.step) bump_group(p.step);
-    }
+#include "qhead_actor_body.h"
+}
+__global__ __launch_bounds__(256) void qhead_actor_kernel_grp(QHeadActor p0, long long mstride) {
+    QHeadActor p = p0;
+    rl_rebase(p, (long long)blockIdx.y * mstride);
+#include "qhead_actor_body.h"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -472,11 +356,11 @@ __device__ __forceinline__ void copy_segs_body(const CopySegs& p, int blk, int n
 template <int DP>
 __device__ __forceinline__ void adam_elems(const int bid, float* __restrict__ ap, const float* __restrict__ agr, float* __restrict__ am, float* __restrict__ av,
                                            const GroupCfg* __restrict__ agrp, float* __restrict__ atarget, int an, int hdr, const AdamTask& t, const AdamSnap& snap, const DpPull& dp);
-template <int DP>
+template <int DP, bool GRP = false>
 __device__ __forceinline__ void adam_block(const int bid, float* __restrict__ ap, const float* __restrict__ agr, float* __restrict__ am, float* __restrict__ av,
                                            const GroupCfg* __restrict__ agrp, float* __restrict__ atarget, int an, int hdr, const AdamTask& t,
                                            const FinTask* __restrict__ fin, int nfin, const SlotFill& sf, int fill_blocks, const SlotFill& sf2, int fill2_blocks,
-                                           const AdamSnap& snap, int snap_blocks, const DpPull& dp) {
+                                           const AdamSnap& snap, int snap_blocks, const DpPull& dp, long long mdelta = 0) {
     const int adam_blocks = hdr & 0x3fffffff;
     // Data parallel (DP != 0, dp_pull.h): the optimizer blocks and the trailing block wait for the peers' gradients, read every rank's arena in
     // rank order where they used to read one gradient (DP == 1), or sum their rank's shard first and read the sums from the shards' owners (DP == 2),
@@ -503,7 +387,7 @@ __device__ __forceinline__ void adam_block(const int bid, float* __restrict__ ap
         unsigned dpe = 0; bool good = true;
         if constexpr (dpon) dpe = dp_begin(dp, false, true, &good);
         if (threadIdx.x == 64 && t.sync_steps) t.sync_steps[2] = t.sync_steps[0];          // (beside the metric tasks, not in their serial chain)
-        if (threadIdx.x < 64 && good) finalize_tasks(fin, nfin, threadIdx.x, dpon ? &dp : nullptr);
+        if (threadIdx.x < 64 && good) finalize_tasks<GRP>(fin, nfin, threadIdx.x, dpon ? &dp : nullptr, mdelta);
         if constexpr (dpon) dp_end(dp, dpe, true);
         return;
     }
@@ -655,6 +539,23 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ ap, const
     const DpPull nodp = DpPull();
     adam_block<0>(blockIdx.x, ap, agr, am, av, agrp, atarget, an, hdr, t, fin, nfin, sf, fill_blocks, sf2, fill2_blocks, snap, snap_blocks, nodp);
 }
+// group form (group.h): member = blockIdx.y; the arenas, the record, the riders and the metric finishers' pointers move to the member's block
+__global__ __launch_bounds__(256) void adam_kernel_grp(float* ap, const float* agr, float* am, float* av, const GroupCfg* agrp, float* atarget, int an, int hdr, AdamTask t,
+                                                       const FinTask* __restrict__ fin, int nfin, SlotFill sf, int fill_blocks, SlotFill sf2, int fill2_blocks, AdamSnap snap, int snap_blocks,
+                                                       long long mstride, long long rstride) {
+    __builtin_amdgcn_s_setprio(3);
+    const long long dm = (long long)blockIdx.y * mstride, dr = (long long)blockIdx.y * rstride;
+    rl_rb(ap, dm); rl_rb(agr, dm); rl_rb(am, dm); rl_rb(av, dm); rl_rb(agrp, dm); rl_rb(atarget, dm);
+    AdamTask tt = t; rl_rebase(tt, dm);
+    SlotFill s1 = sf, s2 = sf2; rl_rebase(s1, dm, dr); rl_rebase(s2, dm, dr);
+    AdamSnap sn = snap;
+    rl_rb(sn.block, dm);
+#pragma unroll
+    for (int q = 0; q < COPY_MAX_SEGS; ++q) { rl_rb(sn.segs.src[q], dm); rl_rb(sn.segs.dst[q], dm); }
+    rl_rb(sn.segs.isrc, dm); rl_rb(sn.segs.idst, dm);
+    const DpPull nodp = DpPull();
+    adam_block<0, true>(blockIdx.x, ap, agr, am, av, agrp, atarget, an, hdr, tt, fin, nfin, s1, fill_blocks, s2, fill2_blocks, sn, snap_blocks, nodp, dm);
+}
 template <int DP>
 __global__ __launch_bounds__(256) void adam_dp_kernel(float* __restrict__ ap, const float* __restrict__ agr, float* __restrict__ am, float* __restrict__ av,
                                                       const GroupCfg* __restrict__ agrp, float* __restrict__ atarget, int an, int hdr, AdamTask t,
@@ -734,11 +635,13 @@ static inline int grid_for(long long n, int per_block, int cap) {
 }
 
 extern "C" int rl_launch_fill_slot(const SlotFill* p, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     const long long total = (long long)p->B * (2 * p->S + p->A + 2);
     hipLaunchKernelGGL(fill_slot_kernel, dim3(grid_for(total, 256, 2048)), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_philox(const PhiloxFill* p, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     hipLaunchKernelGGL(philox_fill_kernel, dim3(grid_for((p->n + 3) / 4, 256, 2048)), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
@@ -747,6 +650,7 @@ extern "C" int rl_launch_philox_raw(const uint32_t* ck, uint32_t* out, long long
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_policy_fwd(const PolicyFwd* p, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     hipLaunchKernelGGL(policy_fwd_kernel, dim3((p->B + 255) / 256), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
@@ -763,6 +667,27 @@ __global__ __launch_bounds__(256) void replay_add_kernel(float* __restrict__ rin
     }
     if (size_dev && blockIdx.x == 0 && threadIdx.x == 0) *size_dev = new_size;
 }
+// group form: member m = blockIdx.y copies its own nrows staged rows (rows + m * rows_stride) into its own ring (ring + m * ring_stride floats)
+// and writes its own fill level (size_dev[m])
+__global__ __launch_bounds__(256) void replay_add_kernel_grp(float* __restrict__ ring, long long ring_stride, long long capacity, int row, long long ptr,
+                                                             const float* __restrict__ rows, long long rows_stride, long long nrows, int* size_dev, int new_size) {
+    const int m = blockIdx.y;
+    ring += (long long)m * ring_stride; rows += (long long)m * rows_stride;
+    const long long n = nrows * row;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+        const long long r = e / row, c = e - r * row;
+        long long dst = ptr + r; if (dst >= capacity) dst -= capacity;
+        ring[dst * row + c] = rows[e];
+    }
+    if (size_dev && blockIdx.x == 0 && threadIdx.x == 0) size_dev[m] = new_size;
+}
+extern "C" int rl_launch_replay_add_grp(float* ring, long long ring_stride, int members, long long capacity, int row, long long ptr, const float* rows,
+                                        long long rows_stride, long long nrows, int* size_dev, int new_size, hipStream_t st) {
+    const long long n = nrows * row;
+    const int blocks = (int)std::min<long long>(256, std::max<long long>(1, (n + 255) / 256));
+    hipLaunchKernelGGL(replay_add_kernel_grp, dim3(blocks, members), dim3(256), 0, st, ring, ring_stride, capacity, row, ptr, rows, rows_stride, nrows, size_dev, new_size);
+    return (int)hipGetLastError();
+}
 extern "C" int rl_launch_replay_add(float* ring, long long capacity, int row, long long ptr, const float* rows, long long nrows, int* size_dev, int new_size, hipStream_t st) {
     const long long n = nrows * row;
     const int blocks = (int)std::min<long long>(256, std::max<long long>(1, (n + 255) / 256));
@@ -772,38 +697,50 @@ extern "C" int rl_launch_replay_add(float* ring, long long capacity, int row, lo
 extern "C" int rl_launch_select_action(const SelectAct* p, hipStream_t st) {
     const size_t lds = sizeof(float) * ((size_t)p->S + 2 * (size_t)p->Ha + 2 * (size_t)p->A);
     if (lds > 60 * 1024) return -7;
-    hipLaunchKernelGGL(select_action_kernel, dim3(1), dim3(1024), lds, st, *p);
+    if (const RlGrp* gr = rl_grp_active()) {
+        if (!gr->seeds) return RL_GRP_UNSUPPORTED;
+        hipLaunchKernelGGL(select_action_kernel_grp, dim3(1, gr->members), dim3(1024), lds, st, *p, gr->stride, gr->seeds);
+    } else
+        hipLaunchKernelGGL(select_action_kernel, dim3(1), dim3(1024), lds, st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_policy_bwd(const PolicyBwd* p, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     hipLaunchKernelGGL(policy_bwd_kernel, dim3((p->B + 255) / 256), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_heads_vae(const HeadsVae* p, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     const int tiles = ((p->B + 15) / 16) * p->tiles_c;
     hipLaunchKernelGGL(heads_vae_kernel, dim3(tiles), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_vae_mid(const VaeMid* p, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     hipLaunchKernelGGL(vae_mid_kernel, dim3(p->nblk), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_vae_mse(const VaeMse* p, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     hipLaunchKernelGGL(vae_mse_kernel, dim3(p->nblk), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_qhead_critic(const QHeadCritic* p, hipStream_t st) {
-    hipLaunchKernelGGL(qhead_critic_kernel, dim3(p->nblk), dim3(256), 0, st, *p);
+    if (const RlGrp* gr = rl_grp_active()) hipLaunchKernelGGL(qhead_critic_kernel_grp, dim3(p->nblk, gr->members), dim3(256), 0, st, *p, gr->stride);
+    else hipLaunchKernelGGL(qhead_critic_kernel, dim3(p->nblk), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_qhead_actor(const QHeadActor* p, hipStream_t st) {
-    hipLaunchKernelGGL(qhead_actor_kernel, dim3(p->nblk), dim3(256), 0, st, *p);
+    if (const RlGrp* gr = rl_grp_active()) hipLaunchKernelGGL(qhead_actor_kernel_grp, dim3(p->nblk, gr->members), dim3(256), 0, st, *p, gr->stride);
+    else hipLaunchKernelGGL(qhead_actor_kernel, dim3(p->nblk), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_adam(const AdamTask* task, int adam_blocks, const FinTask* fin, int nfin, const SlotFill* sf, const SlotFill* sf2, const AdamSnap* snap, const DpPull* dp, hipStream_t st) {
     SlotFill none = SlotFill();
     AdamSnap nosnap = AdamSnap();
     DpPull dpv = DpPull();
+    const RlGrp* gr = rl_grp_active();
+    if (gr && ((dp && dp->world > 1) || (task && task->sh))) return RL_GRP_UNSUPPORTED;
     if (dp && dp->world > 1) {
         if (!task || adam_blocks <= 0 || task->nslab || task->nskip) return -9;     // (split-K folds and epilogue optimizers are single-rank forms: the gradient must be complete in the arena)
         dpv = *dp; dpv.nblocks = adam_blocks + 1;                                  // the optimizer blocks and the trailing block take a ticket
@@ -837,7 +774,10 @@ extern "C" int rl_launch_adam(const AdamTask* task, int adam_blocks, const FinTa
             hipLaunchKernelGGL(adam_dp_kernel<1>, grid, dim3(256), 0, st, t.p, t.g, t.m, t.v, t.grp, t.target, (int)t.n, hdr, t,
                                fin, nfin, sf ? *sf : none, fb, sf2 ? *sf2 : none, fb2, snap ? *snap : nosnap, sb, dpv);
         }
-    } else
+    } else if (gr)
+        hipLaunchKernelGGL(adam_kernel_grp, dim3(grid.x, gr->members), dim3(256), 0, st, t.p, t.g, t.m, t.v, t.grp, t.target, (int)t.n, hdr, t,
+                           fin, nfin, sf ? *sf : none, fb, sf2 ? *sf2 : none, fb2, snap ? *snap : nosnap, sb, gr->stride, gr->ring_stride);
+    else
         hipLaunchKernelGGL(adam_kernel, grid, dim3(256), 0, st, t.p, t.g, t.m, t.v, t.grp, t.target, (int)t.n, hdr, t,
                            fin, nfin, sf ? *sf : none, fb, sf2 ? *sf2 : none, fb2, snap ? *snap : nosnap, sb);
     return (int)hipGetLastError();
@@ -854,6 +794,7 @@ extern "C" int rl_adam_dp_occupancy(int* one_shot, int* two_shot) {
 // optimizer launch of one group + the two first-layer tasks of the NEXT feature step as leading tiles (adam_l1_kernel); sf: the gather of that
 // step's minibatch (must be armed: the tiles read the same ring rows through sf->idx)
 extern "C" int rl_launch_adam_l1(const AdamTask* task, int adam_blocks, const FinTask* fin, int nfin, const SlotFill* sf, const GemmTask* g0, const GemmTask* g1, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     if (!task || adam_blocks <= 0 || !sf || !sf->ring || !sf->idx || !g0 || !g1) return -7;
     AdamTask t = *task;
     if (t.n >= (1ll << 31) || adam_blocks >= (1 << 30)) return -5;
@@ -880,28 +821,37 @@ extern "C" int rl_launch_train_prologue(TrainPrologue* p, hipStream_t st) {
     p->nb_idx = grid_for((p->idx.n + 3) / 4, 256, 2048);
     p->nb_eps = grid_for((p->eps.n + 3) / 4, 256, 2048);
     p->nb_fill = grid_for((long long)p->fill.B * (2 * p->fill.S + p->fill.A + 2), 256, 2048);
-    hipLaunchKernelGGL(train_prologue_kernel, dim3(p->nb_idx + p->nb_eps + p->nb_fill + p->nb_tr), dim3(256), 0, st, *p);
+    if (const RlGrp* gr = rl_grp_active()) {
+        if (p->nsh || p->nb_tr || !gr->seeds) return RL_GRP_UNSUPPORTED;          // (shadow refresh: no sac form carries one)
+        hipLaunchKernelGGL(train_prologue_kernel_grp, dim3(p->nb_idx + p->nb_eps + p->nb_fill, gr->members), dim3(256), 0, st, *p, gr->stride, gr->ring_stride, gr->seeds);
+    } else
+        hipLaunchKernelGGL(train_prologue_kernel, dim3(p->nb_idx + p->nb_eps + p->nb_fill + p->nb_tr), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_polyak(const PolyakTask* t, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     hipLaunchKernelGGL(polyak_kernel, dim3(grid_for(t->n, 1024, 1024)), dim3(256), 0, st, *t);
     return (int)hipGetLastError();
 }
 // mirror > 0: c[mirror] follows c[0] (the train() counter's copy for the next train prologue)
 extern "C" int rl_launch_counter_inc(int* c, int mirror, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     hipLaunchKernelGGL(counter_inc_kernel, dim3(1), dim3(64), 0, st, c, mirror);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_counter_sync(int* c, int mirror, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     hipLaunchKernelGGL(counter_sync_kernel, dim3(1), dim3(64), 0, st, c, mirror);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_copy_segs(const CopySegs* p, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     if (p->n <= 0) return 0;
     hipLaunchKernelGGL(copy_segs_kernel, dim3(grid_for(p->end[p->n - 1], 1024, 1024)), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_copy(const float* src, float* dst, long long n, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     hipLaunchKernelGGL(copy_kernel, dim3(grid_for(n, 1024, 1024)), dim3(256), 0, st, src, dst, n);
     return (int)hipGetLastError();
 }

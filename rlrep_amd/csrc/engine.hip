@@ -18,6 +18,23 @@ void rl_set_error(const char* fmt, ...) {
 // TWO environment variables, comma-separated tokens, parsed when the library is entered through rlrep_layout / rlrep_agent_create / rlrep_gemm*
 // (never on a launch path): RLREP_DISABLE lists default mechanisms to switch off (every one of them has an equivalence test that compares the two
 // forms), RLREP_ENABLE lists opt-in ones, optionally with a value (token=value).  INTEGRATION.md has the table.
+// the group of the library call in progress (group.h): launchers issue their group forms while it is set
+static thread_local RlGrp g_grp;
+static thread_local bool g_grp_on = false;
+extern "C" const RlGrp* rl_grp_active() { return g_grp_on ? &g_grp : nullptr; }
+struct GrpScope {
+    bool set = false, prev_on = false; RlGrp prev{};
+    explicit GrpScope(const rlrep_agent* ag) {
+        if (!ag || ag->members <= 0) return;
+        prev = g_grp; prev_on = g_grp_on;          // (nesting-safe: the enclosing call's group comes back on exit)
+        g_grp.members = ag->members; g_grp.stride = ag->grp_stride; g_grp.ring_stride = ag->grp_ring_stride; g_grp.seeds = ag->grp_seeds;
+        g_grp_on = set = true;
+    }
+    ~GrpScope() { if (set) { g_grp = prev; g_grp_on = prev_on; } }
+};
+// entry points that have no group form refuse a seed group by name (instead of running member 0 alone)
+#define GROUP_REFUSE(what) \
+    if (ag && ag->members > 0) { rl_set_error("%s: not available on a seed group (rlrep_group_create)", what); return RLREP_ERR_ARG; }
 static std::map<std::string, std::string> g_sw_off, g_sw_on;
 static void sw_parse(const char* env, std::map<std::string, std::string>& m) {
     m.clear();
@@ -1244,7 +1261,7 @@ int32_t rlrep_agent_create(const rlrep_dims* dims, const rlrep_hyper* hyper, con
     return 0;
 }
 
-void rlrep_agent_destroy(rlrep_agent* agent) { delete agent; }
+void rlrep_agent_destroy(rlrep_agent* agent) { if (agent && agent->grp_seeds) (void)hipFree(agent->grp_seeds); delete agent; }
 
 static int ensure_batch(rlrep_agent* ag, int B) {
     if (B <= 0 || B > ag->d.max_batch) { rl_set_error("batch %d outside (0, max_batch=%d]", B, ag->d.max_batch); return RLREP_ERR_ARG; }
@@ -1257,6 +1274,7 @@ static int ensure_batch(rlrep_agent* ag, int B) {
 }
 
 int32_t rlrep_set_batch(rlrep_agent* ag, int32_t slot, const rlrep_batch* bt, void* stream) {
+    GROUP_REFUSE("set_batch")
     if (!ag || !bt || slot < 0 || slot > 1 || (slot == 1 && ag->d.alg != RLREP_ALG_SPEDERSAC)) { rl_set_error("set_batch: bad argument"); return RLREP_ERR_ARG; }
     if (slot == 0) { ag->pf_done = false; ag->pf_armed = false; } else { ag->pf2_done = false; ag->pf2_armed = false; }
     ag->pi_ready = nullptr; ag->hoist_req = nullptr;           // a new batch invalidates any prefetched policy forward
@@ -1313,6 +1331,7 @@ static void slot_fill_params(rlrep_agent* ag, int slot, const float* ring_dev, c
 }
 
 int32_t rlrep_prefetch_batch(rlrep_agent* ag, const float* ring_dev, const int32_t* idx_dev, int32_t batch) {
+    GROUP_REFUSE("prefetch_batch")
     if (!ag || !ring_dev || !idx_dev) { rl_set_error("prefetch_batch: bad argument"); return RLREP_ERR_ARG; }
     ag->pf_armed = false;
     if (batch != ag->B || rl_off("prefetch_batch")) return 0;      // would need a rebuild: let replay_sample do it
@@ -1322,6 +1341,7 @@ int32_t rlrep_prefetch_batch(rlrep_agent* ag, const float* ring_dev, const int32
 }
 
 int32_t rlrep_prefetch_batch_slot(rlrep_agent* ag, int32_t slot, const float* ring_dev, const int32_t* idx_dev, int32_t batch) {
+    GROUP_REFUSE("prefetch_batch_slot")
     if (slot == 0) return rlrep_prefetch_batch(ag, ring_dev, idx_dev, batch);
     if (!ag || !ring_dev || !idx_dev || slot != 1 || ag->d.alg != RLREP_ALG_SPEDERSAC) { rl_set_error("prefetch_batch_slot: bad argument"); return RLREP_ERR_ARG; }
     ag->pf2_armed = false;
@@ -1337,6 +1357,7 @@ int32_t rlrep_train_prologue(rlrep_agent* ag, const float* ring_dev, const int32
     if (!ag || !ring_dev || !size_dev || !idx_pool_dev || !eps_pool_dev || n_idx < batch || n_eps <= 0 || batch <= 0) {
         rl_set_error("train_prologue: bad argument"); return RLREP_ERR_ARG;
     }
+    if (ag->members > 0 && !g_grp_on) { rl_set_error("train_prologue: a seed group takes rlrep_group_train_prologue"); return RLREP_ERR_ARG; }
     ag->pi_ready = nullptr; ag->hoist_req = nullptr; ag->pf_armed = false; ag->pf_done = false; ag->pf2_armed = false; ag->pf2_done = false;
     ag->chain_next = ag->chain_bwd_done = ag->l1_done = false;
     ag->early_crit = ag->early_act = ag->early_ready_crit = ag->early_ready_act = nullptr;
@@ -1373,6 +1394,7 @@ int32_t rlrep_replay_sample(rlrep_agent* ag, int32_t slot, const float* ring_dev
         ag->pf2_done = false;                                  // gathered by the previous optimizer launch (rlrep_prefetch_batch_slot)
         return 0;
     }
+    GROUP_REFUSE("replay_sample")                              // (a group's gathers are its train prologue's)
     if (slot == 0) { ag->pf_done = false; ag->l1_done = false; ag->chain_next = false; } else ag->pf2_done = false;
     ag->pi_ready = nullptr; ag->hoist_req = nullptr;           // a new batch invalidates any prefetched policy forward
     ag->early_crit = ag->early_act = ag->early_ready_crit = ag->early_ready_act = nullptr;
@@ -1431,6 +1453,7 @@ static int run(rlrep_agent* ag, const Program& p, void* stream) {
 }
 #define STEP_PROLOGUE(needs_feature) \
     if (!ag) { rl_set_error("null agent"); return RLREP_ERR_ARG; } \
+    GrpScope grp_scope_(ag); \
     if ((needs_feature) && ag->d.alg == RLREP_ALG_SAC) { rl_set_error("sac has no feature step"); return RLREP_ERR_ARG; }
 
 int32_t rlrep_feature_backward(rlrep_agent* ag, const float* eps, const int32_t* idx, void* stream) {
@@ -1484,6 +1507,7 @@ int32_t rlrep_feature_chain_next(rlrep_agent* ag) {
     return 1;
 }
 int32_t rlrep_prefetch_policy_early(rlrep_agent* ag, const float* eps_critic, const float* eps_actor) {
+    GROUP_REFUSE("prefetch_policy_early")
     if (!ag) { rl_set_error("null agent"); return RLREP_ERR_ARG; }
     ag->early_crit = ag->early_act = nullptr;
     if (!eps_critic || !eps_actor || ag->feat_bwd_h.stages.empty() || ag->critic_bwd_h2.stages.empty()) return 0;
@@ -1557,6 +1581,7 @@ int32_t rlrep_actor_alpha_step(rlrep_agent* ag, const float* eps, void* stream) 
 }
 int32_t rlrep_update_target(rlrep_agent* ag, void* stream) {
     if (!ag) return RLREP_ERR_ARG;
+    GrpScope grp_scope_(ag);
     const bool done = ag->target_done;
     ag->in_train = ag->target_done = false;
     if (done) return 0;                                  // already folded into this train()'s critic Adam launch
@@ -1565,6 +1590,7 @@ int32_t rlrep_update_target(rlrep_agent* ag, void* stream) {
 }
 int32_t rlrep_begin_train(rlrep_agent* ag, void* stream) {
     if (!ag) return RLREP_ERR_ARG;
+    GrpScope grp_scope_(ag);
     int rc = (++g_rl_launches, rl_launch_counter_inc(ag->steps, 2, (hipStream_t)stream));
     if (rc) { rl_set_error("begin_train: hip error %d", rc); return RLREP_ERR_HIP; }
     if (ag->has_shadows() && (rc = refresh_shadows(ag, stream)) != 0) return rc;
@@ -1582,6 +1608,7 @@ int32_t rlrep_defer_supported(rlrep_agent* ag) {
 // rlrep_defer_snapshot that follows with the same arguments launches nothing.  To be called before the LAST feature step of a train().
 // Returns 1 if armed, 0 if this agent / configuration has no folded form (the caller proceeds as before).
 int32_t rlrep_defer_arm(rlrep_agent* ag, int32_t set, const float* eps_critic, const float* eps_actor) {
+    GROUP_REFUSE("defer_arm")
     if (!ag || set < 0 || set >= rlrep_agent::NSETS) return 0;
     ag->snap_armed = false; ag->snap_done = -1;
     if (!eps_critic || !eps_actor || !rlrep_defer_supported(ag) || ag->dset[set].block_which < 0 || !ag->dset[set].block) return 0;
@@ -1590,6 +1617,7 @@ int32_t rlrep_defer_arm(rlrep_agent* ag, int32_t set, const float* eps_critic, c
     return 1;
 }
 int32_t rlrep_defer_snapshot(rlrep_agent* ag, int32_t set, const float* eps_critic, const float* eps_actor, void* stream) {
+    GROUP_REFUSE("defer_snapshot")
     if (!ag || !eps_critic || !eps_actor || set < 0 || set >= rlrep_agent::NSETS) { rl_set_error("defer_snapshot: bad argument"); return RLREP_ERR_ARG; }
     if (!rlrep_defer_supported(ag)) { rl_set_error("deferred critic/actor steps are not built for this agent"); return RLREP_ERR_STATE; }
     if (!ag->slot[0].filled) { rl_set_error("defer_snapshot before set_batch / replay_sample"); return RLREP_ERR_STATE; }
@@ -1613,6 +1641,7 @@ int32_t rlrep_defer_snapshot(rlrep_agent* ag, int32_t set, const float* eps_crit
 // part: 0 critic backward, 1 critic apply (+ period-gated critic-target Polyak), 2 actor backward, 3 actor + temperature apply; -1 all.
 // Data parallel callers all-reduce the critic / actor gradient slices between 0 and 1 and between 2 and 3.
 int32_t rlrep_deferred_part(rlrep_agent* ag, int32_t set, int32_t part, void* stream) {
+    GROUP_REFUSE("deferred_part")
     if (!ag || set < 0 || set >= rlrep_agent::NSETS || part < -1 || part > 3 || !rlrep_defer_supported(ag)) { rl_set_error("deferred critic/actor steps are not built for this agent"); return RLREP_ERR_STATE; }
     rlrep_agent::DeferSet& D = ag->dset[set];
     if (!D.valid) { rl_set_error("deferred critic/actor steps before rlrep_defer_snapshot of this set"); return RLREP_ERR_STATE; }
@@ -1648,6 +1677,7 @@ int32_t rlrep_images_managed(rlrep_agent* ag, int32_t on) {
     return 1;
 }
 int32_t rlrep_refresh_images(rlrep_agent* ag, void* stream) {
+    GROUP_REFUSE("refresh_images")
     if (!ag) { rl_set_error("null agent"); return RLREP_ERR_ARG; }
     return refresh_x3(ag, stream);
 }
@@ -1681,12 +1711,14 @@ int32_t rlrep_feature_backward_part(rlrep_agent* ag, int32_t part, const float* 
 }
 
 int32_t rlrep_sync_frozen(rlrep_agent* ag, void* stream) {
+    GROUP_REFUSE("sync_frozen")
     if (!ag) return RLREP_ERR_ARG;
     ag->last_launches += (int)ag->sync_prog.stages.size();
     return ag->sync_prog.run((hipStream_t)stream);
 }
 
 int32_t rlrep_actor_forward(rlrep_agent* ag, const float* obs, int32_t n, const float* eps, float lo, float hi, float* action, void* stream) {
+    GROUP_REFUSE("actor_forward")
     if (!ag || !obs || !action || n <= 0 || n > ag->d.max_batch) { rl_set_error("actor_forward: bad argument"); return RLREP_ERR_ARG; }
     const int S = ag->d.state_dim, A = ag->d.action_dim, Ha = ag->d.actor_hidden_dim;
     hipStream_t st = (hipStream_t)stream;
@@ -1722,6 +1754,7 @@ extern "C" int rl_launch_select_action(const SelectAct* p, hipStream_t st);
 // hipHostGetDevicePointer, so that the kernel reads the observation and writes the action in place and no copy launch stands on either side.
 int32_t rlrep_select_action(rlrep_agent* ag, const float* obs, int32_t obs_on_host, int32_t explore, uint64_t seed, uint64_t offset,
                             float lo, float hi, float* action, int32_t action_on_host, void* stream) {
+    GROUP_REFUSE("select_action")
     if (!ag || !obs || !action) { rl_set_error("select_action: bad argument"); return RLREP_ERR_ARG; }
     SelectAct p; memset(&p, 0, sizeof(p));
     void* d = nullptr;
@@ -1765,6 +1798,7 @@ int32_t rlrep_stage_info(rlrep_agent* ag, int32_t program, int32_t stage, int32_
     return 0;
 }
 int32_t rlrep_run_stage(rlrep_agent* ag, int32_t program, int32_t stage, void* stream) {
+    GROUP_REFUSE("run_stage")
     Program* p = ag ? prog_of(ag, program) : nullptr;
     if (!p || stage < 0 || stage >= (int)p->stages.size()) { rl_set_error("run_stage: bad program/stage"); return RLREP_ERR_ARG; }
     if (!ag->slot[0].filled) { rl_set_error("run_stage before a full step"); return RLREP_ERR_STATE; }
@@ -1868,6 +1902,7 @@ int32_t rlrep_nc_fwd_plan(int32_t heads, int32_t B, int32_t F, int32_t H, int32_
 }
 
 int32_t rlrep_chain_status(rlrep_agent* ag, uint32_t* status, void* stream) {
+    GROUP_REFUSE("chain_status")
     if (!ag || !ag->xc_err) { rl_set_error("chain_status: bad argument"); return RLREP_ERR_ARG; }
     unsigned w = 0;
     hipError_t e = hipMemcpyAsync(&w, ag->xc_err, sizeof(w), hipMemcpyDeviceToHost, (hipStream_t)stream);
@@ -1923,6 +1958,7 @@ int64_t rlrep_launch_counter(void) { return g_rl_launches; }
 // exchange scratch -- the feature step carries its batch-coupled exchanges (the programs are rebuilt)
 extern "C" int rl_adam_dp_occupancy(int* one_shot, int* two_shot);
 extern "C" int rl_agent_attach_dp(rlrep_agent* ag, const DpAttach* at, int* attached_mask) {
+    GROUP_REFUSE("attach_dp")
     if (!ag || !at) return RLREP_ERR_ARG;
     const DpPull* proto = &at->proto;
     if (proto->world != ag->h.world_size) { rl_set_error("comm_attach: the comm spans %d ranks, the agent was created with world_size = %d", proto->world, ag->h.world_size); return RLREP_ERR_ARG; }
@@ -1973,6 +2009,115 @@ extern "C" int rl_agent_attach_dp(rlrep_agent* ag, const DpAttach* at, int* atta
 int32_t rlrep_front_end_counts(int64_t* out4) {
     if (!out4) return RLREP_ERR_ARG;
     for (int q = 0; q < 4; ++q) out4[q] = g_rl_front[q];
+    return 0;
+}
+// ---- seed groups ------------------------------------------------------------------------------------------------------------------------------
+// byte extent of the seven arenas of one member: [lowest arena pointer, end of the highest)
+static long long member_span(const rlrep_layout_info& info, const rlrep_arenas* a) {
+    const char* p[7] = {(const char*)a->param_dev, (const char*)a->target_dev, (const char*)a->grad_dev, (const char*)a->exp_avg_dev,
+                        (const char*)a->exp_avg_sq_dev, (const char*)a->workspace_dev, (const char*)a->alpha_state_dev};
+    const long long n[7] = {4 * info.param_floats, 4 * info.target_floats, 4 * info.grad_floats, 4 * info.param_floats, 4 * info.param_floats,
+                            (long long)info.workspace_bytes, 4 * 8};
+    const char* lo = p[0]; const char* hi = p[0] + n[0];
+    for (int q = 1; q < 7; ++q) { lo = std::min(lo, p[q]); hi = std::max(hi, p[q] + n[q]); }
+    return (long long)(hi - lo);
+}
+int32_t rlrep_group_max_members(void) { return RLREP_GROUP_MAX_MEMBERS; }
+
+int32_t rlrep_group_create(const rlrep_dims* dims, const rlrep_hyper* hyper, const rlrep_arenas* arenas, int32_t members, int64_t member_stride_bytes,
+                           void* stream, rlrep_agent** out) {
+    if (!dims || !hyper || !arenas || !out) { rl_set_error("group_create: null argument"); return RLREP_ERR_ARG; }
+    if (dims->alg != RLREP_ALG_SAC) { rl_set_error("group_create: seed groups are built for sac only (alg %d)", dims->alg); return RLREP_ERR_ARG; }
+    if (members < 1 || members > RLREP_GROUP_MAX_MEMBERS) { rl_set_error("group_create: members %d outside [1, %d]", members, RLREP_GROUP_MAX_MEMBERS); return RLREP_ERR_ARG; }
+    if (dims->world_size > 1 || hyper->world_size > 1) { rl_set_error("group_create: a seed group does not attach to data parallel (world_size %d)", std::max(dims->world_size, hyper->world_size)); return RLREP_ERR_ARG; }
+    if (member_stride_bytes <= 0 || (member_stride_bytes & 255)) { rl_set_error("group_create: member stride %lld is not a positive multiple of 256 bytes", (long long)member_stride_bytes); return RLREP_ERR_ARG; }
+    if (!arenas->param_dev || !arenas->grad_dev || !arenas->exp_avg_dev || !arenas->exp_avg_sq_dev || !arenas->workspace_dev ||
+        !arenas->alpha_state_dev || !arenas->target_dev) { rl_set_error("group_create: null arena pointer"); return RLREP_ERR_ARG; }
+    rlrep_layout_info info;
+    if (!check_dims(dims) || rlrep_layout(dims, &info, nullptr, 0) != 0) return RLREP_ERR_ARG;
+    const long long span = member_span(info, arenas);
+    if (member_stride_bytes < span) { rl_set_error("group_create: member stride %lld is smaller than the member span %lld", (long long)member_stride_bytes, span); return RLREP_ERR_ARG; }
+    rlrep_agent* ag = nullptr;
+    int rc = rlrep_agent_create(dims, hyper, arenas, stream, &ag);
+    if (rc) return rc;
+    ag->members = members; ag->grp_stride = member_stride_bytes;
+    // every member starts as a byte copy of member 0's block (step counters, optimizer records, metric slots; the caller then writes each
+    // member's parameters): the programs' device records are member 0's, and a group launch moves every pointer it finds in them
+    hipError_t e = hipMalloc((void**)&ag->grp_seeds, sizeof(unsigned long long) * members);
+    if (e == hipSuccess) e = hipMemsetAsync(ag->grp_seeds, 0, sizeof(unsigned long long) * members, (hipStream_t)stream);
+    const char* lo = (const char*)arenas->param_dev;
+    for (const void* q : {(const void*)arenas->target_dev, (const void*)arenas->grad_dev, (const void*)arenas->exp_avg_dev, (const void*)arenas->exp_avg_sq_dev,
+                          (const void*)arenas->workspace_dev, (const void*)arenas->alpha_state_dev}) lo = std::min(lo, (const char*)q);
+    ag->grp_lo = lo;
+    for (int m = 1; m < members && e == hipSuccess; ++m)
+        e = hipMemcpyAsync((char*)lo + (long long)m * member_stride_bytes, lo, (size_t)span, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) { rl_set_error("group_create: %s", hipGetErrorString(e)); rlrep_agent_destroy(ag); return RLREP_ERR_HIP; }
+    *out = ag;
+    return 0;
+}
+int32_t rlrep_group_members(rlrep_agent* ag) { return ag ? ag->members : RLREP_ERR_ARG; }
+int32_t rlrep_group_set_seeds(rlrep_agent* ag, const uint64_t* seeds, int32_t n, void* stream) {
+    if (!ag || ag->members <= 0 || !seeds || n != ag->members) { rl_set_error("group_set_seeds: need one seed per member of a group"); return RLREP_ERR_ARG; }
+    const hipError_t e = hipMemcpyAsync(ag->grp_seeds, seeds, sizeof(uint64_t) * n, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) (void)hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) { rl_set_error("group_set_seeds: %s", hipGetErrorString(e)); return RLREP_ERR_HIP; }
+    return 0;
+}
+// [p, p + bytes) inside member 0's block [grp_lo, grp_lo + stride): what a group launch moves by r * stride must stay in member r's block
+static bool in_member0(const rlrep_agent* ag, const void* p, long long bytes) {
+    const char* q = (const char*)p;
+    return q && bytes >= 0 && q >= ag->grp_lo && q + bytes <= ag->grp_lo + ag->grp_stride;
+}
+int32_t rlrep_group_train_prologue(rlrep_agent* ag, const float* ring_dev, int64_t ring_stride_bytes, const int32_t* size_dev, int32_t* idx_pool_dev, int64_t n_idx,
+                                   float* eps_pool_dev, int64_t n_eps, uint64_t idx_offset, uint64_t eps_offset, int32_t batch, void* stream) {
+    if (!ag || ag->members <= 0) { rl_set_error("group_train_prologue: not a seed group"); return RLREP_ERR_ARG; }
+    if (ring_stride_bytes < 0 || (ring_stride_bytes & 3) || (ag->members > 1 && ring_stride_bytes < 4ll * batch)) {
+        rl_set_error("group_train_prologue: bad ring stride %lld", (long long)ring_stride_bytes); return RLREP_ERR_ARG;
+    }
+    if (!in_member0(ag, idx_pool_dev, 4 * n_idx) || !in_member0(ag, eps_pool_dev, 4 * n_eps)) {
+        rl_set_error("group_train_prologue: the index / noise pools must lie inside member 0's block (they are written at every member's stride)");
+        return RLREP_ERR_ARG;
+    }
+    ag->grp_ring_stride = ring_stride_bytes;          // (also what a later optimizer launch's ring gather moves by)
+    GrpScope grp_scope_(ag);
+    return rlrep_train_prologue(ag, ring_dev, size_dev, idx_pool_dev, n_idx, eps_pool_dev, n_eps, 0, idx_offset, eps_offset, batch, stream);
+}
+int32_t rlrep_group_prepare(rlrep_agent* ag, int32_t batch) {
+    if (!ag || ag->members <= 0) { rl_set_error("group_prepare: not a seed group"); return RLREP_ERR_ARG; }
+    return ensure_batch(ag, batch);
+}
+int32_t rlrep_group_select_action(rlrep_agent* ag, const float* obs_host, int32_t explore, uint64_t offset, float lo, float hi, float* action_host, void* stream) {
+    if (!ag || ag->members <= 0 || !obs_host || !action_host) { rl_set_error("group_select_action: bad argument (needs a seed group)"); return RLREP_ERR_ARG; }
+    SelectAct p; memset(&p, 0, sizeof(p));
+    void* d = nullptr;
+    if (hipHostGetDevicePointer(&d, const_cast<float*>(obs_host), 0) != hipSuccess || !d) { rl_set_error("group_select_action: the observations are not mapped (pinned) host memory"); return RLREP_ERR_ARG; }
+    p.obs = (const float*)d;
+    if (hipHostGetDevicePointer(&d, action_host, 0) != hipSuccess || !d) { rl_set_error("group_select_action: the action buffer is not mapped (pinned) host memory"); return RLREP_ERR_ARG; }
+    p.act = (float*)d;
+    p.W1 = ag->P("actor.trunk.0.weight"); p.b1 = ag->P("actor.trunk.0.bias"); p.W2 = ag->P("actor.trunk.2.weight"); p.b2 = ag->P("actor.trunk.2.bias");
+    p.W3 = ag->P("actor.trunk.4.weight"); p.b3 = ag->P("actor.trunk.4.bias");
+    p.S = ag->d.state_dim; p.Ha = ag->d.actor_hidden_dim; p.A = ag->d.action_dim; p.explore = explore ? 1 : 0; p.lo = lo; p.hi = hi; p.seed = 0; p.offset = offset;
+    GrpScope grp_scope_(ag);
+    ++g_rl_launches;
+    const int rc = rl_launch_select_action(&p, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_select_action: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    return 0;
+}
+extern "C" int rl_launch_replay_add_grp(float* ring, long long ring_stride, int members, long long capacity, int row, long long ptr, const float* rows,
+                                        long long rows_stride, long long nrows, int* size_dev, int new_size, hipStream_t st);
+int32_t rlrep_group_replay_add_sized(float* ring_dev, int64_t ring_stride_floats, int32_t members, int64_t capacity, int32_t row_floats, int64_t ptr,
+                                     const float* rows_host, int64_t rows_stride_floats, int64_t nrows, int32_t* size_dev, int32_t new_size, void* stream) {
+    if (!ring_dev || !rows_host || members < 1 || members > RLREP_GROUP_MAX_MEMBERS || capacity <= 0 || row_floats <= 0 || ring_stride_floats < capacity * row_floats ||
+        rows_stride_floats < nrows * row_floats ||
+        ptr < 0 || ptr >= capacity || nrows < 0 || nrows > capacity || new_size < 0 || new_size > capacity) {
+        rl_set_error("group_replay_add_sized: bad argument"); return RLREP_ERR_ARG;
+    }
+    void* d = nullptr;
+    if (hipHostGetDevicePointer(&d, const_cast<float*>(rows_host), 0) != hipSuccess || !d) { rl_set_error("group_replay_add_sized: the staging rows are not mapped (pinned) host memory"); return RLREP_ERR_ARG; }
+    ++g_rl_launches;
+    const int rc = rl_launch_replay_add_grp(ring_dev, ring_stride_floats, members, capacity, row_floats, ptr, (const float*)d, rows_stride_floats, nrows, size_dev, new_size, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_replay_add_sized: hip error %d", rc); return RLREP_ERR_HIP; }
     return 0;
 }
 int32_t rlrep_last_launch_count(rlrep_agent* ag) { return ag ? ag->last_launches : 0; }

@@ -1,6 +1,7 @@
 // Internal definitions shared by engine.hip and agents2.hip (agent state, program builder).
 #pragma once
 #include "engine.h"
+#include "group.h"
 #include <deque>
 
 struct Slot { float *XE, *XF, *XF2, *XFpi, *R, *D; bool filled = false; };
@@ -9,6 +10,10 @@ struct Exchange { int after_stage; int kind; float* ptr; int64_t count; int64_t 
 
 struct rlrep_agent {
     rlrep_dims d; rlrep_hyper h; rlrep_arenas a; Layout L; Workspace ws;
+    // seed group (rlrep_group_create): members > 0 -- every launch of this agent runs `members` blocks laid out `grp_stride` bytes apart (group.h)
+    int members = 0; long long grp_stride = 0; unsigned long long* grp_seeds = nullptr;
+    const char* grp_lo = nullptr;          // member 0's lowest arena byte: its block is [grp_lo, grp_lo + grp_stride)
+    long long grp_ring_stride = 0;         // bytes between two members' replay rings, as the last group train prologue was given
     int B = 0;
     int* steps = nullptr; GroupCfg* adam_step = nullptr; float* metrics = nullptr; float* obs_in = nullptr; float* act_out = nullptr;
     Slot slot[2];

@@ -24,6 +24,7 @@
 #include "common.h"
 #include "kparams.h"
 #include "gemm16_tile.h"
+#include "group.h"
 
 #ifdef RL_TIMING
 // Instrumented build (tools/exp/gemm_timeline.py): thread 0 of every 8th workgroup records the 100 MHz wall clock at
@@ -50,6 +51,11 @@ extern "C" unsigned rl_timing_count() { unsigned n = 0; (void)hipMemcpyFromSymbo
 #else
 #define TIM(k) do {} while (0)
 #define TIM_FIN() do {} while (0)
+#endif
+#ifdef RL_TIMING
+#define RL_TIM_NONE , nullptr
+#else
+#define RL_TIM_NONE
 #endif
 
 // The launch header travels TWICE: inside the batch (gemm_lds shares the struct) and as 14 leading scalar arguments -- flags, tile count,
@@ -205,6 +211,104 @@ __global__ __launch_bounds__(256) void gemm16_fastpre_kernel(int hdr, const floa
     gemm16_tile<LD_ROW, LD_COL, 1, false, false, true, false, GemmTask, EPI_K, ACT_K, false, MSE, 4, NJ_K>(t, tr, tc, red, bsum, nullptr, &fo);
 #endif
 }
+// ---- the group forms (group.h): member = blockIdx.y, every pointer of the record (and the fast front ends' base) rebased by member * stride;
+// the x decomposition, the tile body and its summation order are the single-agent kernel's
+template <int LA, int LB, int NF, bool VA, bool VB, bool PRE = false, int EPI_K = -1, int ACT_K = -1, bool MSE = false, int NJ_K = 0>
+__global__ __launch_bounds__(256) void gemm16_kernel_grp(int hdr, int total, int tb0, int tb1, int tb2, int tb3, int tb4, int tb5, int tb6, int tb7,
+                                                         unsigned tc01, unsigned tc23, unsigned tc45, unsigned tc67, GemmBatch gb, long long mstride) {
+    __shared__ float red[4][NF][4][64];
+    __shared__ float bsum[4][16];
+    const int low_prio = hdr & 1;
+    const int tb[GEMM_MAX_TASKS] = {tb0, tb1, tb2, tb3, tb4, tb5, tb6, tb7};
+    const int tcs[GEMM_MAX_TASKS] = {(int)(tc01 & 0xffffu), (int)(tc01 >> 16), (int)(tc23 & 0xffffu), (int)(tc23 >> 16),
+                                     (int)(tc45 & 0xffffu), (int)(tc45 >> 16), (int)(tc67 & 0xffffu), (int)(tc67 >> 16)};
+    if (!low_prio) __builtin_amdgcn_s_setprio(3);
+    int bid = blockIdx.x;
+    if constexpr (LA == LD_COL && LB == LD_COL) {
+        if (hdr & 2) {
+            const int x = bid & 7, j = bid >> 3, q = total >> 3, r = total & 7;
+            bid = x * q + min(x, r) + j;
+        }
+    }
+    int ti = 0, base = tb[0], tiles_c = tcs[0];
+#pragma unroll
+    for (int q = 1; q < GEMM_MAX_TASKS; ++q) if (bid >= tb[q]) { ti = q; base = tb[q]; tiles_c = tcs[q]; }
+    GemmTask t = gb.t[ti];
+    rl_rebase(t, (long long)blockIdx.y * mstride);
+    const int local = bid - base;
+    const int tr = local / tiles_c, tc = local - tr * tiles_c;
+    gemm16_tile<LA, LB, NF, VA, VB, PRE, false, GemmTask, EPI_K, ACT_K, false, MSE, 0, NJ_K>(t, tr, tc, red, bsum, nullptr RL_TIM_NONE);
+}
+template <int LA, int LB, int NF, bool VA, bool VB, int EPI_K, int ACT_K, int FU = 4>
+__global__ __launch_bounds__(256) void gemm16_fast_kernel_grp(int hdr, int tb1, const float* base, unsigned a0, unsigned b0, unsigned ld0, unsigned kr0, unsigned ct0,
+                                                              unsigned a1, unsigned b1, unsigned ld1, unsigned kr1, unsigned ct1, GemmBatch gb, long long mstride) {
+    __shared__ float red[4][NF][4][64];
+    __shared__ float bsum[4][16];
+    if (!(hdr & 1)) __builtin_amdgcn_s_setprio(3);
+    const long long dm = (long long)blockIdx.y * mstride;
+    base = (const float*)((uintptr_t)base + (uintptr_t)dm);
+    const int bid = blockIdx.x;
+    const bool second = bid >= tb1;
+    const unsigned ao = second ? a1 : a0, bo = second ? b1 : b0, ld = second ? ld1 : ld0, kr = second ? kr1 : kr0, ct = second ? ct1 : ct0;
+    const int local = second ? bid - tb1 : bid, sh = (int)(ct >> 16);
+    const int tr = local >> sh, tc = local & ((1 << sh) - 1);
+    FastOps fo;
+    fo.pA = base + (size_t)ao; fo.pB = base + (size_t)bo; fo.lda = (int)(ld & 0xffffu); fo.ldb = (int)(ld >> 16);
+    fo.K = (int)(kr & 0xffffu); fo.R = (int)(kr >> 16); fo.Cn = (int)(ct & 0xffffu); fo.tiles_c = 1 << sh;
+    int ti = __builtin_amdgcn_readfirstlane(second ? 1 : 0);
+    asm volatile("" : "+s"(ti));
+    GemmTask t = gb.t[ti];
+    rl_rebase(t, dm);
+    gemm16_tile<LA, LB, NF, VA, VB, false, false, GemmTask, EPI_K, ACT_K, false, false, FU>(t, tr, tc, red, bsum, nullptr RL_TIM_NONE, &fo);
+}
+template <int LA, int LB, int NF, bool VA, bool VB, int EPI_K, int ACT_K, int FU = 4>
+__global__ __launch_bounds__(256) void gemm16_fast4_kernel_grp(int hdr, const float* base, unsigned ld, unsigned kr, unsigned ct, unsigned a0, unsigned b0, unsigned a1, unsigned b1,
+                                                               unsigned a2, unsigned b2, unsigned a3, unsigned b3, GemmBatch gb, long long mstride) {
+    __shared__ float red[4][NF][4][64];
+    __shared__ float bsum[4][16];
+    if (!(hdr & 1)) __builtin_amdgcn_s_setprio(3);
+    const long long dm = (long long)blockIdx.y * mstride;
+    base = (const float*)((uintptr_t)base + (uintptr_t)dm);
+    const int bid = blockIdx.x, nt = hdr >> 8;
+    int ti = (bid >= nt ? 1 : 0) + (bid >= 2 * nt ? 1 : 0) + (bid >= 3 * nt ? 1 : 0);
+    const unsigned ao = ti == 0 ? a0 : ti == 1 ? a1 : ti == 2 ? a2 : a3, bo = ti == 0 ? b0 : ti == 1 ? b1 : ti == 2 ? b2 : b3;
+    const int local = bid - ti * nt, sh = (int)(ct >> 16);
+    const int tr = local >> sh, tc = local & ((1 << sh) - 1);
+    FastOps fo;
+    fo.pA = base + (size_t)ao; fo.pB = base + (size_t)bo; fo.lda = (int)(ld & 0xffffu); fo.ldb = (int)(ld >> 16);
+    fo.K = (int)(kr & 0xffffu); fo.R = (int)(kr >> 16); fo.Cn = (int)(ct & 0xffffu); fo.tiles_c = 1 << sh;
+    ti = __builtin_amdgcn_readfirstlane(ti);
+    asm volatile("" : "+s"(ti));
+    GemmTask t = gb.t[ti];
+    rl_rebase(t, dm);
+    gemm16_tile<LA, LB, NF, VA, VB, false, false, GemmTask, EPI_K, ACT_K, false, false, FU>(t, tr, tc, red, bsum, nullptr RL_TIM_NONE, &fo);
+}
+template <int EPI_K, int ACT_K, bool MSE, int NJ_K = 0>
+__global__ __launch_bounds__(256) void gemm16_fastpre_kernel_grp(int hdr, const float* base, unsigned ao, unsigned bo, unsigned ld, unsigned kr, unsigned ck, unsigned xo, unsigned wo, unsigned mo,
+                                                                 unsigned ldxw, unsigned ldm, GemmBatch gb, long long mstride) {
+    __shared__ float red[4][1][4][64];
+    __shared__ float bsum[4][16];
+    if (!(hdr & 1)) __builtin_amdgcn_s_setprio(3);
+    const long long dm = (long long)blockIdx.y * mstride;
+    base = (const float*)((uintptr_t)base + (uintptr_t)dm);
+    const int bid = blockIdx.x, sh = hdr >> 8;
+    const int tr = bid >> sh, tc = bid & ((1 << sh) - 1);
+    FastOps fo;
+    fo.pA = base + (size_t)ao; fo.pB = base + (size_t)bo; fo.lda = (int)(ld & 0xffffu); fo.ldb = (int)(ld >> 16);
+    fo.K = (int)(kr & 0xffffu); fo.R = (int)(kr >> 16); fo.Cn = (int)(ck & 0xffffu); fo.tiles_c = 1 << sh;
+    fo.X = base + (size_t)xo; fo.Wt = base + (size_t)wo; fo.M = base + (size_t)mo; fo.K1 = (int)(ck >> 16);
+    fo.ldx = (int)(ldxw & 0xffffu); fo.ldw = (int)(ldxw >> 16); fo.ldm = (int)ldm;
+    GemmTask t = gb.t[0];
+    rl_rebase(t, dm);
+    gemm16_tile<LD_ROW, LD_COL, 1, false, false, true, false, GemmTask, EPI_K, ACT_K, false, MSE, 4, NJ_K>(t, tr, tc, red, bsum, nullptr RL_TIM_NONE, &fo);
+}
+// a launch of kernel KN<TA...>: its group form when a group is active (rl_grp_active), grid (x, members)
+#define RL_LAUNCH16(KN, TA, g, st, ...) do { \
+        const RlGrp* gr_ = rl_grp_active(); \
+        if (gr_) hipLaunchKernelGGL((KN##_grp<RL_UNPAREN TA>), dim3((g).x, gr_->members), dim3(256), 0, st, __VA_ARGS__, gr_->stride); \
+        else hipLaunchKernelGGL((KN<RL_UNPAREN TA>), g, dim3(256), 0, st, __VA_ARGS__); \
+    } while (0)
+
 // launches per front end since the library was loaded (rlrep_front_end_counts): 0 = gemm16_fast_kernel, 1 = gemm16_fast4_kernel, 2 = gemm16_fastpre_kernel,
 // 3 = the record front end (gemm16_kernel / gemm16_duo_kernel).  Which one a launch gets depends on its shapes and on every operand lying within
 // 16 GiB of the lowest one (rlrep_amd/core.py carves all arenas out of one block for that); tests and bench.py read the counts.
@@ -332,9 +436,9 @@ __global__ __launch_bounds__(256) void gemm16_duo_kernel(int hdr, int total, int
 
 template <int LA, int LB, bool VA, bool VB>
 static void launch_nf(int nf, dim3 g, hipStream_t st, const GemmBatch& gb) {
-    if (nf == 1) hipLaunchKernelGGL((gemm16_kernel<LA, LB, 1, VA, VB>), g, dim3(256), 0, st, G16_ARGS(gb));
-    else if (nf == 2) hipLaunchKernelGGL((gemm16_kernel<LA, LB, 2, VA, VB>), g, dim3(256), 0, st, G16_ARGS(gb));
-    else hipLaunchKernelGGL((gemm16_kernel<LA, LB, 4, VA, VB>), g, dim3(256), 0, st, G16_ARGS(gb));
+    if (nf == 1) RL_LAUNCH16(gemm16_kernel, (LA, LB, 1, VA, VB), g, st, G16_ARGS(gb));
+    else if (nf == 2) RL_LAUNCH16(gemm16_kernel, (LA, LB, 2, VA, VB), g, st, G16_ARGS(gb));
+    else RL_LAUNCH16(gemm16_kernel, (LA, LB, 4, VA, VB), g, st, G16_ARGS(gb));
 }
 
 // NF = 1 launches whose tasks all share ONE plain epilogue (forward or dX; none / ReLU / ELU; no rank-1 term, no second output): the
@@ -343,16 +447,16 @@ static void launch_nf(int nf, dim3 g, hipStream_t st, const GemmBatch& gb) {
 template <int LA, int LB, int NF, bool VA, bool VB, int EPI_K, int ACT_K>
 static bool launch_fast(dim3 g, hipStream_t st, const GemmBatch& gb) {
     FastArgs fa; Fast4Args f4;
-    if (fast_args(gb, fa)) { hipLaunchKernelGGL((gemm16_fast_kernel<LA, LB, NF, VA, VB, EPI_K, ACT_K>), g, dim3(256), 0, st, G16_FAST_ARGS(fa, gb)); s_front = 0; return true; }
-    if (fast4_args(gb, f4)) { hipLaunchKernelGGL((gemm16_fast4_kernel<LA, LB, NF, VA, VB, EPI_K, ACT_K>), g, dim3(256), 0, st, G16_FAST4_ARGS(f4, gb)); s_front = 1; return true; }
+    if (fast_args(gb, fa)) { RL_LAUNCH16(gemm16_fast_kernel, (LA, LB, NF, VA, VB, EPI_K, ACT_K), g, st, G16_FAST_ARGS(fa, gb)); s_front = 0; return true; }
+    if (fast4_args(gb, f4)) { RL_LAUNCH16(gemm16_fast4_kernel, (LA, LB, NF, VA, VB, EPI_K, ACT_K), g, st, G16_FAST4_ARGS(f4, gb)); s_front = 1; return true; }
     return false;
 }
 // ... and the first layers (K <= 64, forward form, rows of 17 / 23 / 40 floats: with or without 16-byte operand loads)
 template <int LA, int LB, int NF, bool VA, bool VB, int ACT_K>
 static bool launch_fast_short(dim3 g, hipStream_t st, const GemmBatch& gb) {
     FastArgs fa; Fast4Args f4;
-    if (fast_args(gb, fa, true)) { hipLaunchKernelGGL((gemm16_fast_kernel<LA, LB, NF, VA, VB, EPI_FWD, ACT_K, 1>), g, dim3(256), 0, st, G16_FAST_ARGS(fa, gb)); s_front = 0; return true; }
-    if (fast4_args(gb, f4, true)) { hipLaunchKernelGGL((gemm16_fast4_kernel<LA, LB, NF, VA, VB, EPI_FWD, ACT_K, 1>), g, dim3(256), 0, st, G16_FAST4_ARGS(f4, gb)); s_front = 1; return true; }
+    if (fast_args(gb, fa, true)) { RL_LAUNCH16(gemm16_fast_kernel, (LA, LB, NF, VA, VB, EPI_FWD, ACT_K, 1), g, st, G16_FAST_ARGS(fa, gb)); s_front = 0; return true; }
+    if (fast4_args(gb, f4, true)) { RL_LAUNCH16(gemm16_fast4_kernel, (LA, LB, NF, VA, VB, EPI_FWD, ACT_K, 1), g, st, G16_FAST4_ARGS(f4, gb)); s_front = 1; return true; }
     return false;
 }
 // NF = 1 launches whose tasks all share ONE plain epilogue (forward or dX; none / ReLU / ELU; no rank-1 term, no second output): the
@@ -394,30 +498,30 @@ static bool launch_spec(dim3 g, hipStream_t st, const GemmBatch& gb) {
     // mixed activations (the policy's ELU layers beside f's ReLU layers in one launch): the epilogue KIND compiled in, the activation read from the
     // record -- the fully generic body spends 5 700 cycles between the reduction barrier and the store of such a tile (tools/exp/gemm_timeline.py)
     if (act < 0) {
-        if (LB == LD_ROW && epi == EPI_FWD) { hipLaunchKernelGGL((gemm16_kernel<LA, LB, NF, VA, VB, false, EPI_FWD, -1>), g, dim3(256), 0, st, G16_ARGS(gb)); return true; }
-        if (LB == LD_COL && epi == EPI_DX) { hipLaunchKernelGGL((gemm16_kernel<LA, LB, NF, VA, VB, false, EPI_DX, -1>), g, dim3(256), 0, st, G16_ARGS(gb)); return true; }
+        if (LB == LD_ROW && epi == EPI_FWD) { RL_LAUNCH16(gemm16_kernel, (LA, LB, NF, VA, VB, false, EPI_FWD, -1), g, st, G16_ARGS(gb)); return true; }
+        if (LB == LD_COL && epi == EPI_DX) { RL_LAUNCH16(gemm16_kernel, (LA, LB, NF, VA, VB, false, EPI_DX, -1), g, st, G16_ARGS(gb)); return true; }
         return false;
     }
     if (LB == LD_ROW && epi == EPI_FWD) {
-        if (act == ACT_NONE) hipLaunchKernelGGL((gemm16_kernel<LA, LB, NF, VA, VB, false, EPI_FWD, ACT_NONE>), g, dim3(256), 0, st, G16_ARGS(gb));
-        else if (act == ACT_RELU) hipLaunchKernelGGL((gemm16_kernel<LA, LB, NF, VA, VB, false, EPI_FWD, ACT_RELU>), g, dim3(256), 0, st, G16_ARGS(gb));
-        else if (act == ACT_ELU) hipLaunchKernelGGL((gemm16_kernel<LA, LB, NF, VA, VB, false, EPI_FWD, ACT_ELU>), g, dim3(256), 0, st, G16_ARGS(gb));
+        if (act == ACT_NONE) RL_LAUNCH16(gemm16_kernel, (LA, LB, NF, VA, VB, false, EPI_FWD, ACT_NONE), g, st, G16_ARGS(gb));
+        else if (act == ACT_RELU) RL_LAUNCH16(gemm16_kernel, (LA, LB, NF, VA, VB, false, EPI_FWD, ACT_RELU), g, st, G16_ARGS(gb));
+        else if (act == ACT_ELU) RL_LAUNCH16(gemm16_kernel, (LA, LB, NF, VA, VB, false, EPI_FWD, ACT_ELU), g, st, G16_ARGS(gb));
         else return false;
         return true;
     }
     if (LB == LD_COL && epi == EPI_DX) {
-        if (act == ACT_NONE) hipLaunchKernelGGL((gemm16_kernel<LA, LB, NF, VA, VB, false, EPI_DX, ACT_NONE>), g, dim3(256), 0, st, G16_ARGS(gb));
-        else if (act == ACT_RELU) hipLaunchKernelGGL((gemm16_kernel<LA, LB, NF, VA, VB, false, EPI_DX, ACT_RELU>), g, dim3(256), 0, st, G16_ARGS(gb));
-        else if (act == ACT_ELU) hipLaunchKernelGGL((gemm16_kernel<LA, LB, NF, VA, VB, false, EPI_DX, ACT_ELU>), g, dim3(256), 0, st, G16_ARGS(gb));
+        if (act == ACT_NONE) RL_LAUNCH16(gemm16_kernel, (LA, LB, NF, VA, VB, false, EPI_DX, ACT_NONE), g, st, G16_ARGS(gb));
+        else if (act == ACT_RELU) RL_LAUNCH16(gemm16_kernel, (LA, LB, NF, VA, VB, false, EPI_DX, ACT_RELU), g, st, G16_ARGS(gb));
+        else if (act == ACT_ELU) RL_LAUNCH16(gemm16_kernel, (LA, LB, NF, VA, VB, false, EPI_DX, ACT_ELU), g, st, G16_ARGS(gb));
         else return false;
         return true;
     }
     if (NF == 1 && LB == LD_COL && epi == EPI_DX_POLICYBWD) {  // the policy's backward (same epilogue instantiation as on the fast front end)
-        hipLaunchKernelGGL((gemm16_kernel<LA, LB, 1, VA, VB, false, EPI_DX_POLICYBWD, ACT_NONE>), g, dim3(256), 0, st, G16_ARGS(gb));
+        RL_LAUNCH16(gemm16_kernel, (LA, LB, 1, VA, VB, false, EPI_DX_POLICYBWD, ACT_NONE), g, st, G16_ARGS(gb));
         return true;
     }
     if (NF == 1 && LB == LD_ROW && epi == EPI_FWD_MSE) {       // vlsac decoder heads + mse
-        hipLaunchKernelGGL((gemm16_kernel<LA, LB, 1, VA, VB, false, EPI_FWD_MSE, ACT_NONE>), g, dim3(256), 0, st, G16_ARGS(gb));
+        RL_LAUNCH16(gemm16_kernel, (LA, LB, 1, VA, VB, false, EPI_FWD_MSE, ACT_NONE), g, st, G16_ARGS(gb));
         return true;
     }
     return false;
@@ -482,8 +586,8 @@ static int launch_gemm16_impl(int la, int lb, int nf, const GemmBatch* gb_in, in
             return -3;                                   // first layers fused into the second: measured slower, experiments build only
 #else
             if (lb != LD_ROW) return -3;
-            if (all_vec(*gb, true)) hipLaunchKernelGGL((gemm16_kernel<LD_ROW, LD_ROW, 1, false, true, true>), g, dim3(256), 0, st, G16_ARGS(*gb));
-            else hipLaunchKernelGGL((gemm16_kernel<LD_ROW, LD_ROW, 1, false, false, true>), g, dim3(256), 0, st, G16_ARGS(*gb));
+            if (all_vec(*gb, true)) RL_LAUNCH16(gemm16_kernel, (LD_ROW, LD_ROW, 1, false, true, true), g, st, G16_ARGS(*gb));
+            else RL_LAUNCH16(gemm16_kernel, (LD_ROW, LD_ROW, 1, false, false, true), g, st, G16_ARGS(*gb));
 #endif
         } else {
             if (lb != LD_COL) return -3;
@@ -502,26 +606,26 @@ static int launch_gemm16_impl(int la, int lb, int nf, const GemmBatch* gb_in, in
                 const GemmTask& m0 = gb->t[0];
                 if (gb->ntasks != 1 || !rep || (m0.ldaux2 & 3) || (m0.ldx1 & 3) || (m0.K & 3) || ((((uintptr_t)m0.x2) | ((uintptr_t)m0.x1)) & 15) || !m0.bias || !m0.tgs || !m0.tgr || !m0.mse_part || !m0.x0)
                     return -3;
-                if (fastpre) hipLaunchKernelGGL((gemm16_fastpre_kernel<EPI_DX_REPARAM, ACT_NONE, true>), g, dim3(256), 0, st, G16_FASTPRE_ARGS(fp, *gb));
-                else hipLaunchKernelGGL((gemm16_kernel<LD_ROW, LD_COL, 1, false, false, true, EPI_DX_REPARAM, ACT_NONE, true>), g, dim3(256), 0, st, G16_ARGS(*gb));
+                if (fastpre) RL_LAUNCH16(gemm16_fastpre_kernel, (EPI_DX_REPARAM, ACT_NONE, true), g, st, G16_FASTPRE_ARGS(fp, *gb));
+                else RL_LAUNCH16(gemm16_kernel, (LD_ROW, LD_COL, 1, false, false, true, EPI_DX_REPARAM, ACT_NONE, true), g, st, G16_ARGS(*gb));
                 return (int)hipGetLastError();
             }
             // short products of at most 16 inner indices (the policy head's 2 A <= 16 columns): instantiations without the second 16-wide chunk
             bool nj1 = !s_generic;
             for (int q = 0; q < gb->ntasks; ++q) nj1 = nj1 && gb->t[q].n0 <= 16;
             if (fastpre) {
-                if (elu && nj1) hipLaunchKernelGGL((gemm16_fastpre_kernel<EPI_DX, ACT_ELU, false, 1>), g, dim3(256), 0, st, G16_FASTPRE_ARGS(fp, *gb));
-                else if (elu) hipLaunchKernelGGL((gemm16_fastpre_kernel<EPI_DX, ACT_ELU, false>), g, dim3(256), 0, st, G16_FASTPRE_ARGS(fp, *gb));
-                else if (rep) hipLaunchKernelGGL((gemm16_fastpre_kernel<EPI_DX_REPARAM, ACT_NONE, false>), g, dim3(256), 0, st, G16_FASTPRE_ARGS(fp, *gb));
-                else if (nj1) hipLaunchKernelGGL((gemm16_fastpre_kernel<EPI_DX, ACT_NONE, false, 1>), g, dim3(256), 0, st, G16_FASTPRE_ARGS(fp, *gb));
-                else hipLaunchKernelGGL((gemm16_fastpre_kernel<EPI_DX, ACT_NONE, false>), g, dim3(256), 0, st, G16_FASTPRE_ARGS(fp, *gb));
+                if (elu && nj1) RL_LAUNCH16(gemm16_fastpre_kernel, (EPI_DX, ACT_ELU, false, 1), g, st, G16_FASTPRE_ARGS(fp, *gb));
+                else if (elu) RL_LAUNCH16(gemm16_fastpre_kernel, (EPI_DX, ACT_ELU, false), g, st, G16_FASTPRE_ARGS(fp, *gb));
+                else if (rep) RL_LAUNCH16(gemm16_fastpre_kernel, (EPI_DX_REPARAM, ACT_NONE, false), g, st, G16_FASTPRE_ARGS(fp, *gb));
+                else if (nj1) RL_LAUNCH16(gemm16_fastpre_kernel, (EPI_DX, ACT_NONE, false, 1), g, st, G16_FASTPRE_ARGS(fp, *gb));
+                else RL_LAUNCH16(gemm16_fastpre_kernel, (EPI_DX, ACT_NONE, false), g, st, G16_FASTPRE_ARGS(fp, *gb));
                 return (int)hipGetLastError();
             }
-            if (elu && nj1) hipLaunchKernelGGL((gemm16_kernel<LD_ROW, LD_COL, 1, false, false, true, EPI_DX, ACT_ELU, false, 1>), g, dim3(256), 0, st, G16_ARGS(*gb));
-            else if (elu) hipLaunchKernelGGL((gemm16_kernel<LD_ROW, LD_COL, 1, false, false, true, EPI_DX, ACT_ELU>), g, dim3(256), 0, st, G16_ARGS(*gb));
-            else if (rep) hipLaunchKernelGGL((gemm16_kernel<LD_ROW, LD_COL, 1, false, false, true, EPI_DX_REPARAM, ACT_NONE>), g, dim3(256), 0, st, G16_ARGS(*gb));
-            else if (plain) hipLaunchKernelGGL((gemm16_kernel<LD_ROW, LD_COL, 1, false, false, true, EPI_DX, ACT_NONE>), g, dim3(256), 0, st, G16_ARGS(*gb));
-            else hipLaunchKernelGGL((gemm16_kernel<LD_ROW, LD_COL, 1, false, false, true>), g, dim3(256), 0, st, G16_ARGS(*gb));
+            if (elu && nj1) RL_LAUNCH16(gemm16_kernel, (LD_ROW, LD_COL, 1, false, false, true, EPI_DX, ACT_ELU, false, 1), g, st, G16_ARGS(*gb));
+            else if (elu) RL_LAUNCH16(gemm16_kernel, (LD_ROW, LD_COL, 1, false, false, true, EPI_DX, ACT_ELU), g, st, G16_ARGS(*gb));
+            else if (rep) RL_LAUNCH16(gemm16_kernel, (LD_ROW, LD_COL, 1, false, false, true, EPI_DX_REPARAM, ACT_NONE), g, st, G16_ARGS(*gb));
+            else if (plain) RL_LAUNCH16(gemm16_kernel, (LD_ROW, LD_COL, 1, false, false, true, EPI_DX, ACT_NONE), g, st, G16_ARGS(*gb));
+            else RL_LAUNCH16(gemm16_kernel, (LD_ROW, LD_COL, 1, false, false, true), g, st, G16_ARGS(*gb));
         }
         return (int)hipGetLastError();
     }
@@ -542,14 +646,14 @@ static int launch_gemm16_impl(int la, int lb, int nf, const GemmBatch* gb_in, in
         }
         if (opt) {
             if (!plain) return -3;
-            if (nf == 4) hipLaunchKernelGGL((gemm16_kernel<LD_COL, LD_COL, 4, false, false, false, EPI_DWA, ACT_NONE>), g, dim3(256), 0, st, G16_ARGS(*gb));
-            else if (nf == 2) hipLaunchKernelGGL((gemm16_kernel<LD_COL, LD_COL, 2, false, false, false, EPI_DWA, ACT_NONE>), g, dim3(256), 0, st, G16_ARGS(*gb));
-            else hipLaunchKernelGGL((gemm16_kernel<LD_COL, LD_COL, 1, false, false, false, EPI_DWA, ACT_NONE>), g, dim3(256), 0, st, G16_ARGS(*gb));
+            if (nf == 4) RL_LAUNCH16(gemm16_kernel, (LD_COL, LD_COL, 4, false, false, false, EPI_DWA, ACT_NONE), g, st, G16_ARGS(*gb));
+            else if (nf == 2) RL_LAUNCH16(gemm16_kernel, (LD_COL, LD_COL, 2, false, false, false, EPI_DWA, ACT_NONE), g, st, G16_ARGS(*gb));
+            else RL_LAUNCH16(gemm16_kernel, (LD_COL, LD_COL, 1, false, false, false, EPI_DWA, ACT_NONE), g, st, G16_ARGS(*gb));
             return (int)hipGetLastError();
         }
-        if (plain && nf == 4) hipLaunchKernelGGL((gemm16_kernel<LD_COL, LD_COL, 4, false, false, false, EPI_DW, ACT_NONE>), g, dim3(256), 0, st, G16_ARGS(*gb));
-        else if (plain && nf == 2) hipLaunchKernelGGL((gemm16_kernel<LD_COL, LD_COL, 2, false, false, false, EPI_DW, ACT_NONE>), g, dim3(256), 0, st, G16_ARGS(*gb));
-        else if (plain && nf == 1) hipLaunchKernelGGL((gemm16_kernel<LD_COL, LD_COL, 1, false, false, false, EPI_DW, ACT_NONE>), g, dim3(256), 0, st, G16_ARGS(*gb));
+        if (plain && nf == 4) RL_LAUNCH16(gemm16_kernel, (LD_COL, LD_COL, 4, false, false, false, EPI_DW, ACT_NONE), g, st, G16_ARGS(*gb));
+        else if (plain && nf == 2) RL_LAUNCH16(gemm16_kernel, (LD_COL, LD_COL, 2, false, false, false, EPI_DW, ACT_NONE), g, st, G16_ARGS(*gb));
+        else if (plain && nf == 1) RL_LAUNCH16(gemm16_kernel, (LD_COL, LD_COL, 1, false, false, false, EPI_DW, ACT_NONE), g, st, G16_ARGS(*gb));
         else launch_nf<LD_COL, LD_COL, false, false>(nf, g, st, *gb);
     }
     else return -1;
@@ -558,6 +662,7 @@ static int launch_gemm16_impl(int la, int lb, int nf, const GemmBatch* gb_in, in
 
 // tasks [0, split): LD_ROW x LD_COL at NF = 1; tasks [split, ntasks): LD_COL x LD_COL at NF = nf2 (1 or 4); tile bases / column-tile counts set by the caller
 extern "C" int rl_launch_gemm16_duo(int split, int nf2, const GemmBatch* gb_in, int total_tiles, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     if (total_tiles <= 0) return 0;
     if (split <= 0 || split >= gb_in->ntasks || (nf2 != 1 && nf2 != 4)) return -4;
     GemmBatch planned = *gb_in;

@@ -28,6 +28,7 @@
 #define GL_DIR_ARGS(D) (D)[0], (D)[1], (D)[2], (D)[3], (D)[4], (D)[5], (D)[6], (D)[7]
 extern long long g_rl_launches;
 #include "kparams.h"
+#include "group.h"
 
 #define GL_BK 32
 #define GL_KCS 36
@@ -1210,6 +1211,7 @@ static int launch_x3q(int la, int lb, dim3 g, hipStream_t st, const GemmBatch& g
 // bt: 64 / 128 = fp32-MFMA tiles; 129 = the 128-wide tile on the bf16 pipe (bf16x3); 65 = the 64-wide tile on the bf16 pipe; 257 = the 256 x 128 tile on the
 // bf16 pipe (persistent workgroups: gemm_x3w.h); 33 = the 32 x 32 tile on the bf16 pipe whose four waves split K (gemm_x3q.h)
 extern "C" int rl_launch_gemm_lds(int bt, int la, int lb, const GemmBatch* gb, int total_tiles, int fin_blocks, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     if (total_tiles <= 0) return 0;
     int dir[GEMM_MAX_TASKS], fdir[GEMM_MAX_TASKS];
     for (int q = 0; q < GEMM_MAX_TASKS; ++q) {

@@ -1,0 +1,68 @@
+// Seed groups (rlrep_group_create): R agents of identical shape whose blocks lie at a constant byte stride in ONE allocation.  The step
+// programs are built once, against member 0; a launch issued while a group is active runs every member at once -- member r is
+// blockIdx.y -- and rebases EVERY pointer it dereferences by r * stride (the replay ring by r * ring_stride, the ring's size word by r).
+// The grid's x dimension, the tile decomposition and every summation order are a standalone agent's: member r computes bit for bit
+// what SACAgent(seed = s_r) computes.  No member reads another member's words.
+//
+// The group forms are SEPARATE kernels (`*_grp_kernel`) around the same device bodies: the kernels the single agents launch are untouched.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "common.h"
+#include "kparams.h"
+
+#define RLREP_GROUP_MAX_MEMBERS 64
+
+// host: the group of the library call in progress (null outside one); set by the group entry points for the duration of the call
+struct RlGrp {
+    int members;
+    long long stride;                   // bytes between two members' blocks (multiple of 256)
+    long long ring_stride;              // bytes between two members' replay rings (train prologue only)
+    const unsigned long long* seeds;    // [members] Philox seeds (device), train prologue only
+};
+extern "C" const RlGrp* rl_grp_active();
+// what a launcher without a group form returns while a group is active (the stage fails with this code: no member is left behind silently)
+#define RL_GRP_UNSUPPORTED 77
+
+#define RL_UNPAREN(...) __VA_ARGS__
+
+#ifdef __HIPCC__
+template <class T> __device__ __forceinline__ void rl_rb(T*& p, long long d) { if (p) p = (T*)((uintptr_t)p + (uintptr_t)d); }
+__device__ __forceinline__ void rl_rebase(GemmTask& t, long long d) {
+    rl_rb(t.A, d); rl_rb(t.B, d); rl_rb(t.C, d); rl_rb(t.bias, d); rl_rb(t.aux, d); rl_rb(t.r1u, d); rl_rb(t.r1v, d);
+    rl_rb(t.gidx, d); rl_rb(t.out2, d);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) rl_rb(t.sp[q], d);
+    rl_rb(t.aux2, d); rl_rb(t.aux3, d);
+    rl_rb(t.ad_p, d); rl_rb(t.ad_m, d); rl_rb(t.ad_v, d); rl_rb(t.ad_t, d);
+    rl_rb(t.ad_pb, d); rl_rb(t.ad_mb, d); rl_rb(t.ad_vb, d); rl_rb(t.ad_tb, d); rl_rb(t.ad_grp, d);
+    rl_rb(t.x0, d); rl_rb(t.x1, d); rl_rb(t.x2, d); rl_rb(t.y0, d); rl_rb(t.y1, d); rl_rb(t.dptr, d);
+    rl_rb(t.tgs, d); rl_rb(t.tgr, d); rl_rb(t.mse_part, d); rl_rb(t.slab, d); rl_rb(t.bslab, d);
+}
+__device__ __forceinline__ void rl_rebase(FinTask& f, long long d) {
+    rl_rb(f.partials, d); rl_rb(f.out, d); rl_rb(f.out2, d); rl_rb(f.in_a, d); rl_rb(f.in_b, d); rl_rb(f.alpha_state, d);
+}
+// ring_d: the replay ring's own stride (a gather from the ring); the slot buffers and the index stream live in the member's block
+__device__ __forceinline__ void rl_rebase(SlotFill& s, long long d, long long ring_d) {
+    rl_rb(s.ring, ring_d); rl_rb(s.idx, d);
+    rl_rb(s.s, d); rl_rb(s.a, d); rl_rb(s.r, d); rl_rb(s.s2, d); rl_rb(s.d, d);
+    rl_rb(s.XE, d); rl_rb(s.XF, d); rl_rb(s.XF2, d); rl_rb(s.XFpi, d); rl_rb(s.R, d); rl_rb(s.D, d);
+}
+__device__ __forceinline__ void rl_rebase(AdamTask& t, long long d) {
+    rl_rb(t.p, d); rl_rb(t.g, d); rl_rb(t.m, d); rl_rb(t.v, d); rl_rb(t.grp, d); rl_rb(t.target, d); rl_rb(t.pol_steps, d);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) rl_rb(t.slabs[q].slab, d);
+    rl_rb(t.sync_steps, d);
+}
+__device__ __forceinline__ void rl_rebase(QHeadCritic& p, long long d) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        rl_rb(p.Et[h], d); rl_rb(p.Ec[h], d); rl_rb(p.wt[h], d); rl_rb(p.bt[h], d); rl_rb(p.wc[h], d); rl_rb(p.bc[h], d); rl_rb(p.GE[h], d);
+    }
+    rl_rb(p.logp, d); rl_rb(p.R, d); rl_rb(p.D, d); rl_rb(p.alpha_state, d); rl_rb(p.dq, d); rl_rb(p.partial, d); rl_rb(p.step, d);
+}
+__device__ __forceinline__ void rl_rebase(QHeadActor& p, long long d) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) { rl_rb(p.Ec[h], d); rl_rb(p.wc[h], d); rl_rb(p.bc[h], d); rl_rb(p.GE[h], d); }
+    rl_rb(p.logp, d); rl_rb(p.alpha_state, d); rl_rb(p.partial_loss, d); rl_rb(p.partial_c, d); rl_rb(p.step, d);
+}
+#endif

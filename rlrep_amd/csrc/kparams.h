@@ -123,9 +123,22 @@ struct FinTask {
 #ifdef __HIPCC__
 // dp (data parallel, dp_pull.h): partial sums that live in the gradient arena (FIN_ALPHA's: the temperature gradient) are read from EVERY rank's
 // arena, in rank order -- the caller has passed the READY wait
-__device__ inline void finalize_tasks(const FinTask* __restrict__ fin, int nfin, int lane, const DpPull* dp = nullptr) {
+// GRP: a seed-group launch (group.h) -- the records are member 0's, every pointer in them is moved by mdelta bytes to the member's block
+template <bool GRP> __device__ __forceinline__ FinTask fin_record(const FinTask& f, long long mdelta) {
+    if constexpr (!GRP) return f;
+    FinTask g = f;
+    if (g.partials) g.partials = (const float*)((uintptr_t)g.partials + (uintptr_t)mdelta);
+    if (g.out) g.out = (float*)((uintptr_t)g.out + (uintptr_t)mdelta);
+    if (g.out2) g.out2 = (float*)((uintptr_t)g.out2 + (uintptr_t)mdelta);
+    if (g.in_a) g.in_a = (const float*)((uintptr_t)g.in_a + (uintptr_t)mdelta);
+    if (g.in_b) g.in_b = (const float*)((uintptr_t)g.in_b + (uintptr_t)mdelta);
+    if (g.alpha_state) g.alpha_state = (double*)((uintptr_t)g.alpha_state + (uintptr_t)mdelta);
+    return g;
+}
+template <bool GRP = false>
+__device__ inline void finalize_tasks(const FinTask* __restrict__ fin, int nfin, int lane, const DpPull* dp = nullptr, long long mdelta = 0) {
     for (int q = 0; q < nfin; ++q) {
-        const FinTask f = fin[q];
+        const FinTask f = fin_record<GRP>(fin[q], mdelta);
         if (f.kind == FIN_SUM) {
             float s = 0.f;
             for (int i = lane; i < f.count; i += 64) s += f.partials[(size_t)i * f.stride];

@@ -6,6 +6,9 @@ Same flags, same per-algorithm constructor overrides (main.py:81-104), same loop
 `start_timesteps`, then epsilon-greedy 0.01 around `select_action(explore=True)`, one `agent.train()` per
 environment step, evaluation every `eval_freq` steps).  Metrics go to `log/<env>/<alg>/<dir>/<seed>/metrics.jsonl`
 as {"step": t, "info/<key>": value} lines (and to tensorboardX with the reference's tags if it is installed).
+
+`--seeds 0,1,2,3` (sac only): one SACSeedBatch trains every seed in the same launches, one environment per seed stepped in lockstep;
+each seed has its own np.random.RandomState(seed) for random and epsilon-greedy actions, its own evaluation and its own log directory.
 """
 import argparse
 import json
@@ -64,7 +67,10 @@ def run(argv=None):
     p.add_argument('--extra_feature_steps', default=3, type=int)
     p.add_argument('--eval_episodes', default=10, type=int)
     p.add_argument('--log_root', default='log')
+    p.add_argument('--seeds', default=None, help='comma-separated seeds trained together (sac only): rlrep_amd/agent/sac/seed_batch.py')
     args = p.parse_args(argv)
+    if args.seeds is not None:
+        return run_seeds(args)
 
     env, eval_env = envs.make(args.env), envs.make(args.env)
     env.seed(args.seed)
@@ -124,6 +130,93 @@ def run(argv=None):
     jsonl.close()
     if tb is not None:
         tb.close()
+    print('Total time cost {:.4g}s.'.format(timer.time_cost()))
+    return agent, evaluations
+
+
+class _MemberPolicy(object):
+    """eval_policy's view of one member of a seed batch (deterministic actions: the other members' rows are ignored)"""
+
+    def __init__(self, group, r):
+        self.group, self.r = group, r
+        self.obs = np.zeros((group.R, group.state_dim), np.float32)
+
+    def select_action(self, state):
+        self.obs[self.r] = np.asarray(state, np.float32).reshape(-1)
+        return self.group.select_action(self.obs)[self.r]
+
+
+def run_seeds(args):
+    """The loop of run() for several seeds at once: R environments in lockstep, one SACSeedBatch, one ReplayBufferGroup."""
+    seeds = [int(s) for s in str(args.seeds).split(',') if s.strip() != '']
+    if args.alg != 'sac':
+        raise SystemExit(f'--seeds: seed batches are built for --alg sac only (got --alg {args.alg}); run one process per seed instead')
+    if not seeds or len(set(seeds)) != len(seeds):
+        raise SystemExit(f'--seeds {args.seeds}: give distinct integer seeds, e.g. --seeds 0,1,2,3')
+    from rlrep_amd.agent.sac.seed_batch import SACSeedBatch
+    from rlrep_amd.utils.buffer_group import ReplayBufferGroup
+    R = len(seeds)
+    envs_, evals_ = [envs.make(args.env) for _ in seeds], [envs.make(args.env) for _ in seeds]
+    for s, e, ev in zip(seeds, envs_, evals_):
+        e.seed(s)
+        ev.seed(s)
+    rngs = [np.random.RandomState(s) for s in seeds]
+    max_length = envs_[0]._max_episode_steps
+    logs = []
+    for s in seeds:
+        path = os.path.join(args.log_root, args.env, args.alg, str(args.dir), str(s))
+        os.makedirs(path, exist_ok=True)
+        logs.append(open(os.path.join(path, 'metrics.jsonl'), 'a'))
+    space = envs_[0].action_space
+    state_dim, action_dim = envs_[0].observation_space.shape[0], space.shape[0]
+    lo, hi = np.asarray(space.low, np.float32), np.asarray(space.high, np.float32)
+    agent = SACSeedBatch(seeds, state_dim, action_dim, space, discount=args.discount, tau=args.tau, hidden_dim=args.hidden_dim,
+                         max_batch=args.batch_size)
+    replay = ReplayBufferGroup(R, state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)))
+    policies = [_MemberPolicy(agent, r) for r in range(R)]
+    evaluations = [[util.eval_policy(policies[r], evals_[r], args.eval_episodes)] for r in range(R)]
+    states = np.stack([np.asarray(e.reset(), np.float32) for e in envs_])
+    ep_steps = np.zeros(R, np.int64)
+    infos = None
+    timer = util.Timer()
+    for t in range(int(args.max_timesteps)):
+        ep_steps += 1
+        greedy = None if t < args.start_timesteps else agent.select_action(states, explore=True)
+        actions = np.zeros((R, action_dim), np.float32)
+        for r in range(R):
+            if t < args.start_timesteps or rngs[r].uniform(0, 1) < EPS_GREEDY:
+                actions[r] = rngs[r].uniform(lo, hi)
+            else:
+                actions[r] = greedy[r]
+        nexts, rewards, dones = np.zeros_like(states), np.zeros(R, np.float32), np.zeros(R, np.float32)
+        resets = []
+        for r, e in enumerate(envs_):
+            ns, rew, done, _ = e.step(actions[r])
+            nexts[r], rewards[r] = ns, rew
+            dones[r] = float(done) if ep_steps[r] < max_length else 0.0
+            if done:
+                resets.append(r)
+        replay.add(states, actions, nexts, rewards, dones)
+        states = nexts.copy()
+        for r in resets:
+            states[r] = envs_[r].reset()
+            ep_steps[r] = 0
+        if t >= args.start_timesteps:
+            infos = agent.train(replay, batch_size=args.batch_size)
+        if (t + 1) % args.eval_freq == 0:
+            sps = timer.steps_per_sec(t + 1)
+            for r in range(R):
+                evaluations[r].append(util.eval_policy(policies[r], evals_[r], args.eval_episodes))
+                if infos is not None:
+                    row = {'step': t + 1, 'info/evaluation': float(evaluations[r][-1]), 'steps_per_sec': sps}
+                    row.update({f'info/{k}': float(v) for k, v in infos[r].items()})
+                    logs[r].write(json.dumps(row) + '\n')
+                    logs[r].flush()
+            print('Step {}. Steps per sec (per seed): {:.4g}.'.format(t + 1, sps))
+            if args.save_model:
+                agent.save(os.path.join(args.log_root, args.env, args.alg, str(args.dir), 'seed_batch.pt'))
+    for f in logs:
+        f.close()
     print('Total time cost {:.4g}s.'.format(timer.time_cost()))
     return agent, evaluations
 

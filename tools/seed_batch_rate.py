@@ -1,0 +1,79 @@
+"""Aggregate train() rate of a SACSeedBatch against R standalone SACAgents replayed back to back on one stream.
+
+    python tools/seed_batch_rate.py --workload sac_pendulum_b64 --members 1,2,4,8,16
+
+Per R: the group's aggregate rate (R x calls/s), its graph's launch count per call, and the standalone agents' aggregate rate.  Protocol:
+--warmup calls (default 300), then the median of --windows windows (default 5) of --calls calls (default 500), timed by host wall clock
+around a device synchronisation."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+
+
+def _rate(step, R, warmup, calls, windows):
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    rates = []
+    for _ in range(windows):
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            step()
+        torch.cuda.synchronize()
+        rates.append(R * calls / (time.perf_counter() - t0))
+    return statistics.median(rates)
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument('--workload', default='sac_halfcheetah_b256', choices=['sac_pendulum_b64', 'sac_halfcheetah_b256'])
+    p.add_argument('--members', default='1,2,4,8,16')
+    p.add_argument('--warmup', type=int, default=300)
+    p.add_argument('--calls', type=int, default=500)
+    p.add_argument('--windows', type=int, default=5)
+    p.add_argument('--group-only', action='store_true', help='skip the standalone agents (a profiler run of the group alone)')
+    a = p.parse_args(argv)
+    from rlrep_amd.agent.sac.sac_agent import SACAgent
+    from rlrep_amd.agent.sac.seed_batch import SACSeedBatch
+    from rlrep_amd.utils.buffer_group import ReplayBufferGroup
+    alg, S, A, B, kw = bench.WORKLOADS[a.workload]
+    print(f'# {a.workload}: S={S} A={A} B={B} {kw}; {torch.cuda.get_device_name(0)}; warmup {a.warmup}, median of {a.windows} x {a.calls} calls')
+    print(f'{"R":>3} {"group train()/s":>16} {"launches/call":>14} {"R standalone train()/s":>23} {"ratio":>6}')
+    for R in [int(x) for x in a.members.split(',')]:
+        seeds = list(range(R))
+        rings = ReplayBufferGroup(R, S, A, max_size=bench.REPLAY_N)
+        alone_bufs = []
+        for r in range(R):
+            buf, data = bench.synth_buffer(S, A, r)
+            rings.load(r, data['state'], data['action'], data['next_state'], data['reward'], data['done'])
+            alone_bufs.append(buf)
+        grp = SACSeedBatch(seeds, S, A, bench.Space(A), max_batch=B, **kw)
+        g_rate = _rate(lambda: grp.train(rings, B), R, a.warmup, a.calls, a.windows)
+        launches = grp._graph_launches
+        if a.group_only:
+            print(f'{R:>3} {g_rate:>16.0f} {launches:>14d}', flush=True)
+            continue
+        agents = []
+        for s in seeds:
+            torch.manual_seed(s)
+            agents.append(SACAgent(S, A, bench.Space(A), max_batch=B, seed=s, **kw))
+
+        def alone_step():
+            for ag, buf in zip(agents, alone_bufs):
+                ag.train(buf, B)
+        s_rate = _rate(alone_step, R, a.warmup, a.calls, a.windows)
+        print(f'{R:>3} {g_rate:>16.0f} {launches:>14d} {s_rate:>23.0f} {g_rate / s_rate:>6.2f}', flush=True)
+        del grp, agents, rings, alone_bufs
+        torch.cuda.empty_cache()
+
+
+if __name__ == '__main__':
+    main()
