@@ -483,19 +483,24 @@ int64_t rlrep_launch_counter(void);
  * reference networks/vae.py:40-57,83-85,112-117 and the MLPs of agent/<alg>/<alg>_agent.py. */
 int32_t rlrep_front_end_counts(int64_t* out4);
 
-/* ---- seed groups: R independent sac agents in the same launches (additive to ABI 4) ----------------------------------------------------
+/* ---- seed groups: R independent sac or ctrlsac agents in the same launches (additive to ABI 4) -----------------------------------------
  * A group is R members of identical dims / hyper whose blocks -- the seven arenas of rlrep_agent_create -- are laid out identically at a
  * constant byte stride in ONE allocation: member r's copy of any word is member 0's address + r * member_stride_bytes.  The step programs are
  * built once, against member 0's arenas; every launch of the agent then runs all members (grid y = member) and moves every pointer it
  * dereferences to the member's block.  Each member computes exactly what a standalone agent with its seed computes: same tiles, same
  * summation order, nothing shared between members.  The returned handle is used with the ordinary step entry points (rlrep_critic_step,
- * rlrep_actor_alpha_step, rlrep_update_target, rlrep_prefetch_policy, rlrep_end_train), which then run every member; the train prologue and
- * select_action take their group forms below.  The entry points that have no group form -- rlrep_set_batch, rlrep_replay_sample (other than
- * the gather the group prologue already did), rlrep_prefetch_batch*, rlrep_prefetch_policy_early, the deferred-chain and image calls,
- * rlrep_sync_frozen, rlrep_actor_forward, rlrep_select_action, rlrep_run_stage, rlrep_chain_status -- refuse a group with RLREP_ERR_ARG and a
- * message; a step whose program reaches a kernel without a group form fails with RLREP_ERR_HIP.  No entry point runs member 0 alone.
- * Rejected with RLREP_ERR_ARG and a message: alg != sac, members outside [1, rlrep_group_max_members()], a stride that is not a positive
- * multiple of 256 or is smaller than the member span (lowest arena pointer to the end of the highest arena), world_size > 1.
+ * rlrep_actor_alpha_step, rlrep_update_target, rlrep_prefetch_policy, rlrep_end_train; ctrlsac: rlrep_feature_step, rlrep_sync_frozen and
+ * rlrep_prefetch_batch(_slot 0) with indices inside member 0's block, with or without RLREP_FLAG_NO_FEATURE_TARGET), which then run every
+ * member; the train prologue and select_action take their group forms below.
+ * The entry points that have no group form -- rlrep_set_batch, rlrep_replay_sample (other than the gathers the group prologue or a group
+ * optimizer launch already did), rlrep_prefetch_batch_slot 1, rlrep_prefetch_policy_early, the deferred-chain and image calls, rlrep_actor_forward, rlrep_select_action,
+ * rlrep_run_stage, rlrep_chain_status -- refuse a group with RLREP_ERR_ARG and a message.  Every kernel launcher without a group form refuses
+ * too while a group call is in progress (the persistent 256 x 128 bf16x3 tile, the opt-in fused score + InfoNCE kernel, the spedersac /
+ * diffsrsac / noise-critic kernels, the data-parallel pulls, the experimental engines): a step whose program reaches one fails with
+ * RLREP_ERR_HIP.  No entry point runs member 0 alone.
+ * Rejected with RLREP_ERR_ARG and a message: alg other than sac and ctrlsac (checked first), members outside [1, rlrep_group_max_members()],
+ * a stride that is not a positive multiple of 256 or is smaller than the member span (lowest arena pointer to the end of the highest arena),
+ * world_size > 1.
  * On success members 1..R-1 start as byte copies of member 0's block (after its creation); the caller then writes each member's parameters.
  * Reference: main.py:63-68 (one run per seed) -- a group runs several seeds at once. */
 int32_t rlrep_group_create(const rlrep_dims* dims, const rlrep_hyper* hyper, const rlrep_arenas* member0_arenas, int32_t members,

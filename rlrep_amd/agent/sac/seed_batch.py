@@ -9,238 +9,13 @@ Initialisation rule: member r is initialised exactly as `torch.manual_seed(seeds
 its sample indices and noise from the Philox stream of seed seeds[r].  Member r therefore computes, bit for bit, what that standalone agent
 computes on the same replay ring (tests/test_seed_batch.py).
 """
-import ctypes as C
-import os
-
-import numpy as np
-import torch
-
-from rlrep_amd._lib import lib, check
-from rlrep_amd.core import HipCore, _stream
-from rlrep_amd.agent.sac.sac_agent import SACAgent, ArenaModule
+from rlrep_amd.agent.sac.sac_agent import SACAgent
+from rlrep_amd.agent.seed_batch import SeedBatchMixin, _Member, _MemberCore  # noqa: F401  (this module's names before they were shared)
 
 
-class _MemberCore(HipCore):
-    """Member r's view of a group core: the arenas, device records and metric history of its block (no handle of its own)."""
-
-    def __init__(self, group, r):                   # (HipCore.__init__ is not run: nothing is allocated or created)
-        self.__dict__.update({k: v for k, v in group.__dict__.items() if not k.startswith('_hist') and k not in ('_mt',)})
-        self._group, self._r, self._delta = group, r, r * group.member_stride
-        base = group._skew + self._delta
-
-        def carve(i, dtype):
-            o = base + self._offs[i]
-            return group._block[o:o + self._sizes[i]].view(dtype)
-        self.params, self.targets, self.grads = carve(0, torch.float32), carve(1, torch.float32), carve(2, torch.float32)
-        self.exp_avg, self.exp_avg_sq = carve(3, torch.float32), carve(4, torch.float32)
-        self.workspace, self.alpha_state = carve(5, torch.uint8), carve(6, torch.float64)
-        self._metrics_ptr = group._metrics_ptr + self._delta
-
-    def __del__(self):
-        pass
-
-    def _ws_off(self, member0_ptr):
-        return member0_ptr - self._group.workspace.data_ptr()
-
-    def sync_step_mirror(self):
-        off = self._ws_off(lib.rlrep_steps_dev(self.h))
-        w = self.workspace[off:off + 32].view(torch.int32)
-        w[2] = w[0]
-
-    def group_cfg(self):
-        off = self._ws_off(lib.rlrep_group_cfg_dev(self.h))
-        return self.workspace[off:off + 4 * 22 * 4].view(torch.float32).view(4, 22)
-
-    def _history_views(self):
-        if not hasattr(self, '_hist'):
-            ring, seq, cap, tag = self._group._history_views()
-            o_r, o_q = self._ws_off(ring.data_ptr()), self._ws_off(seq.data_ptr())
-            r = self.workspace[o_r:o_r + ring.numel() * 4].view(torch.float32).view(*ring.shape)
-            q = self.workspace[o_q:o_q + 4].view(torch.int32)
-            self._hist = (r, q, cap, tag)
-        return self._hist
-
-
-class _Member(object):
-    """What `SACSeedBatch.member(r)` returns: the reference's module attributes of member r, views into its block."""
-
-    def __init__(self, core):
-        self.core = core
-        for m in SACAgent.MODULES:
-            setattr(self, m, ArenaModule(core, m))
-
-    @property
-    def log_alpha(self):
-        return self.core.alpha_state[0]
-
-    @property
-    def alpha(self):
-        return self.core.alpha_state[0].exp()
-
-
-class SACSeedBatch(SACAgent):
+class SACSeedBatch(SeedBatchMixin, SACAgent):
     """SACSeedBatch(seeds, state_dim, action_dim, action_space, **SACAgent kwargs): one SAC agent per seed, trained together.
 
     `train(buffers, batch_size)` takes a ReplayBufferGroup (rlrep_amd/utils/buffer_group.py) -- member r samples ring r -- and returns a list of
-    R info dicts.  The single-GPU whole-train() graph is the only form (no data parallel, no eager steps)."""
-
-    def __init__(self, seeds, state_dim, action_dim, action_space, **kwargs):
-        self.seeds = [int(s) for s in seeds]
-        if not self.seeds:
-            raise ValueError('SACSeedBatch: at least one seed')
-        if len(set(self.seeds)) != len(self.seeds):
-            raise ValueError('SACSeedBatch: seeds must be distinct')
-        self.R = len(self.seeds)
-        kwargs = dict(kwargs)
-        kwargs.pop('seed', None)
-        kwargs['seed'] = self.seeds[0]
-        super().__init__(state_dim, action_dim, action_space, **kwargs)
-        if self.world_size > 1 or self._dp or not self.use_graph:
-            raise RuntimeError('SACSeedBatch: a seed group runs the single-GPU whole-train() graph only')
-        self.world_size = 1
-        seeds_arr = (C.c_uint64 * self.R)(*self.seeds)
-        check(lib.rlrep_group_set_seeds(self.core.h, C.cast(seeds_arr, C.c_void_p), self.R, _stream()), 'group_set_seeds')
-
-    # ---- construction -----------------------------------------------------------------------------------------------------------------
-    def _pool_sizes(self, B):
-        idx_keys, eps_specs = self._plan(B)
-        return len(idx_keys) * B, sum(int(np.prod(sh)) for _, sh in eps_specs)
-
-    def _make_core(self, dims, hyper):
-        ni, ne = self._pool_sizes(self.max_batch)
-        # the index and noise pools of a train() sit behind the arenas of every member: the prologue writes member r's at the member stride
-        return HipCore(self.ALG, dims, hyper, members=len(self.seeds), member_extra_bytes=4 * (ni + ne) + 512)
-
-    def _init_parameters(self):
-        group = self.core
-        self._members = [_MemberCore(group, r) for r in range(self.R)]
-        saved = torch.random.get_rng_state()
-        try:
-            for r, s in enumerate(self.seeds):
-                torch.manual_seed(s)
-                self.core = self._members[r]
-                SACAgent._init_parameters(self)
-                self.core.alpha_state[0] = float(np.log(self._alpha0))
-        finally:
-            self.core = group
-            torch.random.set_rng_state(saved)
-        self._member_views = [_Member(m) for m in self._members]
-
-    # ---- pools inside the member block ------------------------------------------------------------------------------------------------
-    def _buf(self, key, shape, dtype=torch.float32):
-        if key not in ('pool_idx', 'pool_eps'):
-            return super()._buf(key, shape, dtype)
-        n = int(np.prod(shape))
-        ni, _ = self._pool_sizes(self.max_batch)
-        c = self.core
-        off = c._skew + c.member_extra_offset + (0 if key == 'pool_idx' else ((4 * ni + 255) & ~255))
-        return c._block[off:off + 4 * n].view(dtype).view(*shape)
-
-    def _fill_pools(self, buffer, B, g):
-        if not g:
-            raise RuntimeError('SACSeedBatch: eager train() forms are not built for seed groups')
-        idx_keys, eps_specs = self._plan(B)
-        ni = len(idx_keys) * B
-        ne = sum(int(np.prod(sh)) for _, sh in eps_specs)
-        ipool = self._buf('pool_idx', (ni,), torch.int32)
-        epool = self._buf('pool_eps', (ne,))
-        check(lib.rlrep_group_train_prologue(self.core.h, C.c_void_p(buffer.ring.data_ptr()), 4 * buffer.ring_stride, C.c_void_p(buffer.size_dev().data_ptr()),
-                                             C.c_void_p(ipool.data_ptr()), ni, C.c_void_p(epool.data_ptr()), ne, 1 << 40, 2 << 40, B, _stream()),
-              'group_train_prologue')
-        self._pool = {}
-        for q, k in enumerate(idx_keys):
-            self._pool['idx_' + k] = ipool[q * B:(q + 1) * B]
-        self._next_key = self._prefetch_chain(idx_keys)
-        o = 0
-        for k, sh in eps_specs:
-            n = int(np.prod(sh))
-            self._pool['eps_' + k] = epool[o:o + n].view(*sh)
-            o += n
-        self._early_key = None
-
-    def _sample_into(self, buffer, B, key, slot=0, g=False):
-        if key == 'warm':
-            # a standalone agent gathers one eager minibatch before its first capture: it sizes the programs for B outside the capture and
-            # draws one index set from the host counter.  A group has no eager gather: it sizes its programs and keeps the counter in step
-            check(lib.rlrep_group_prepare(self.core.h, int(B)), 'group_prepare')
-            self._ctr += 1
-            return
-        return super()._sample_into(buffer, B, key, slot, g)
-
-    @staticmethod
-    def _graph_cache_key(buffer, B):
-        return (buffer.rings.data_ptr(), buffer.size_dev().data_ptr(), int(buffer.max_size), buffer.members, B)
-
-    # ---- surface ----------------------------------------------------------------------------------------------------------------------
-    def train(self, buffers, batch_size):
-        """One train() of every member: ONE graph replay.  Returns R info dicts (member order), fetched when read."""
-        if getattr(buffers, 'members', None) != self.R:
-            raise ValueError(f'SACSeedBatch.train: needs a ReplayBufferGroup of {self.R} members')
-        self.steps += 1
-        return self._train_graph(buffers, batch_size)
-
-    update = train
-
-    def _history_info(self):
-        n = self._hist_n
-        self._hist_n += 1
-        half = max(1, self.core.history_capacity() // 2)
-        out = []
-        for m in self._members:
-            if n % half == half - 1:
-                m.history_resolve()
-            out.append(m.info(lazy_source=m.history_source(n)))
-        return out
-
-    def member(self, r):
-        return self._member_views[r]
-
-    def select_action(self, states, explore=False):
-        """states [R, S] -> actions [R, A]: ONE launch over pinned buffers; member r acts as SACAgent(seed=seeds[r]).select_action does with
-        the same call counter (every member's exploration draw is keyed by its own seed and the shared counter)."""
-        sel = getattr(self, '_gsel', None)
-        if sel is None:
-            sel = self._gsel = dict(obs=torch.empty(self.R, self.state_dim, dtype=torch.float32).pin_memory(),
-                                    act=torch.empty(self.R, self.action_dim, dtype=torch.float32).pin_memory())
-        sel['obs'].numpy()[:] = np.asarray(states, dtype=np.float32).reshape(self.R, self.state_dim)
-        if explore:
-            self._ctr += 1
-        lo, hi = self.action_range
-        check(lib.rlrep_group_select_action(self.core.h, C.c_void_p(sel['obs'].data_ptr()), 1 if explore else 0, self._ctr << 20, lo, hi,
-                                            C.c_void_p(sel['act'].data_ptr()), _stream()), 'group_select_action')
-        torch.cuda.current_stream().synchronize()
-        return sel['act'].numpy().copy()
-
-    def member_snapshot(self, r):
-        """Member r as a SACAgent checkpoint (SACAgent.load accepts it): continue one seed alone."""
-        torch.cuda.synchronize()
-        c = self._members[r]
-        return {'format': self.CHECKPOINT_FORMAT, 'device_state_bytes': int(c.device_state().numel()), 'alg': self.ALG, 'params': c.params.cpu(),
-                'targets': c.targets.cpu(), 'exp_avg': c.exp_avg.cpu(), 'exp_avg_sq': c.exp_avg_sq.cpu(), 'alpha_state': c.alpha_state.cpu(),
-                'device_state': c.device_state().cpu(), 'steps': self.steps, 'noise_ctr': self._ctr, 'seed': self.seeds[r], 'layout': list(c.order)}
-
-    def state_snapshot(self):
-        return {'format': 'rlrep-seed-batch-1', 'seeds': list(self.seeds), 'members': [self.member_snapshot(r) for r in range(self.R)]}
-
-    def save(self, path):
-        torch.save(self.state_snapshot(), path)
-
-    def load(self, path_or_snapshot):
-        snap = torch.load(path_or_snapshot) if isinstance(path_or_snapshot, (str, bytes, os.PathLike)) else path_or_snapshot
-        if snap.get('format') != 'rlrep-seed-batch-1' or list(snap['seeds']) != self.seeds:
-            raise RuntimeError('checkpoint does not match this seed batch (format / seeds differ)')
-        torch.cuda.synchronize()
-        for r, ms in enumerate(snap['members']):
-            c = self._members[r]
-            if ms['layout'] != list(c.order) or ms['device_state'].numel() != c.device_state().numel():
-                raise RuntimeError('checkpoint does not match this seed batch (dimensions differ)')
-            for k, dst in (('params', c.params), ('targets', c.targets), ('exp_avg', c.exp_avg), ('exp_avg_sq', c.exp_avg_sq),
-                           ('alpha_state', c.alpha_state)):
-                dst.copy_(ms[k])
-            hyper = c.group_cfg()[:, 1:6].clone()
-            c.device_state().copy_(ms['device_state'])
-            c.group_cfg()[:, 1:6].copy_(hyper)
-            c.sync_step_mirror()
-        self.steps, self._ctr = snap['members'][0]['steps'], snap['members'][0]['noise_ctr']
-        self._graph = None
-        torch.cuda.synchronize()
+    R info dicts.  The single-GPU whole-train() graph is the only form (no data parallel, no eager steps).  The group machinery is
+    SeedBatchMixin's (rlrep_amd/agent/seed_batch.py)."""

@@ -16,6 +16,7 @@
 #include <vector>
 #include "../../include/rlrep.h"
 #include "dp_pull.h"
+#include "group.h"
 
 void rl_set_error(const char* fmt, ...);
 extern long long g_rl_launches;
@@ -116,6 +117,7 @@ __global__ __launch_bounds__(256) void comm_slots_sum_kernel(DpSlots d, float* _
 
 // the consumer half of a pushed exchange as a stage of a step program (spedersac: Phibar, v): out[0 .. d.n) = rank-ordered sum of the slots
 extern "C" int rl_launch_slots_sum(const DpSlots* d, float* out, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;          // (no group form: a seed group never runs member 0 alone)
     if (!d || d->world < 2 || !out || d->n <= 0) return -7;
     hipLaunchKernelGGL(comm_slots_sum_kernel, dim3(1), dim3(256), 0, st, *d, out);
     return (int)hipGetLastError();
@@ -124,6 +126,7 @@ extern "C" int rl_launch_slots_sum(const DpSlots* d, float* out, hipStream_t st)
 // no_done (both launchers): see DpPull::no_done -- ctrlsac's step program alternates gather and reduce-scatter on two channels; a peer's READY for one
 // is sent after it has completed the other (stream order), so neither needs its own DONE round trip
 extern "C" int rl_launch_xchg_gather(const DpPull* proto, int channel, long long off, long long n, int no_done, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;          // (no group form: a seed group never runs member 0 alone)
     if (!proto || proto->world < 2 || (off & 3) || (n & 3) || n <= 0) return -7;
     DpPull d = *proto; d.channel = channel; d.mode = 1; d.no_done = no_done;
     const long long want = (n / 4 * d.world + 255) / 256;
@@ -133,6 +136,7 @@ extern "C" int rl_launch_xchg_gather(const DpPull* proto, int channel, long long
 }
 // out (device, may alias this rank's block at `off`) = rank-ordered sum of every rank's block[off .. off + n)
 extern "C" int rl_launch_xchg_reduce(const DpPull* proto, int channel, long long off, long long n, float* out, int two_shot, int no_done, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;          // (no group form: a seed group never runs member 0 alone)
     if (!proto || proto->world < 2 || n <= 0 || !out) return -7;
     DpPull d = *proto; d.channel = channel; d.no_done = no_done && !two_shot;
     const bool two = two_shot && d.world >= 3 && d.red[d.rank] && (off & 3) == 0 && (n & 3) == 0 && (((uintptr_t)out) & 15) == 0 && (n >> 2) <= 256ll * 65535;

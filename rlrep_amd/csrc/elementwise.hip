@@ -353,9 +353,10 @@ __device__ __forceinline__ void copy_segs_body(const CopySegs& p, int blk, int n
 // (the body of an optimizer block; `bid` = block index within the optimizer part of the launch)
 // DP (compile time): the data-parallel instantiation (dp_pull.h).  A run-time switch would put the prefetched loads of p / g / m / v into
 // control-flow diamonds (hipcc drains vmcnt at their merges): the single-GPU launch must not pay for code it never runs (measured: 5.4 -> 11.7 us).
-template <int DP>
+template <int DP, bool GRP = false>
 __device__ __forceinline__ void adam_elems(const int bid, float* __restrict__ ap, const float* __restrict__ agr, float* __restrict__ am, float* __restrict__ av,
-                                           const GroupCfg* __restrict__ agrp, float* __restrict__ atarget, int an, int hdr, const AdamTask& t, const AdamSnap& snap, const DpPull& dp);
+                                           const GroupCfg* __restrict__ agrp, float* __restrict__ atarget, int an, int hdr, const AdamTask& t, const AdamSnap& snap, const DpPull& dp,
+                                           long long mdelta = 0);
 template <int DP, bool GRP = false>
 __device__ __forceinline__ void adam_block(const int bid, float* __restrict__ ap, const float* __restrict__ agr, float* __restrict__ am, float* __restrict__ av,
                                            const GroupCfg* __restrict__ agrp, float* __restrict__ atarget, int an, int hdr, const AdamTask& t,
@@ -386,7 +387,7 @@ __device__ __forceinline__ void adam_block(const int bid, float* __restrict__ ap
         // trailing block: finalises the step's metrics / temperature
         unsigned dpe = 0; bool good = true;
         if constexpr (dpon) dpe = dp_begin(dp, false, true, &good);
-        if (threadIdx.x == 64 && t.sync_steps) t.sync_steps[2] = t.sync_steps[0];          // (beside the metric tasks, not in their serial chain)
+        if (threadIdx.x == 64 && t.sync_steps) rl_mv<GRP>(t.sync_steps, mdelta)[2] = rl_mv<GRP>(t.sync_steps, mdelta)[0];          // (beside the metric tasks, not in their serial chain)
         if (threadIdx.x < 64 && good) finalize_tasks<GRP>(fin, nfin, threadIdx.x, dpon ? &dp : nullptr, mdelta);
         if constexpr (dpon) dp_end(dp, dpe, true);
         return;
@@ -394,14 +395,17 @@ __device__ __forceinline__ void adam_block(const int bid, float* __restrict__ ap
     unsigned dpe = 0; bool good = true;
     if constexpr (dpon) dpe = dp_begin(dp, bid == 0, true, &good);
     if constexpr (DP == 2) good = dp_reduce_scatter(dp, dpe, bid, (long long)(agr - dp.base[dp.rank]), (long long)an >> 2, good) && good;
-    if (good) adam_elems<DP>(bid, ap, agr, am, av, agrp, atarget, an, hdr, t, snap, dp);
+    if (good) adam_elems<DP, GRP>(bid, ap, agr, am, av, agrp, atarget, an, hdr, t, snap, dp, mdelta);
     if constexpr (dpon) dp_end(dp, dpe, true);
 }
 
 // the elements of one optimizer block (thread-level early exits inside: the caller brackets it with the data-parallel handshake)
-template <int DP>
+// GRP (a seed group's launch, group.h): `t` is member 0's record as it lies in the kernel-argument segment; the pointers read from it are moved by
+// mdelta where they are dereferenced (a rebased local copy of the record put slabs[] in scratch memory: its index is known at run time only)
+template <int DP, bool GRP>
 __device__ __forceinline__ void adam_elems(const int bid, float* __restrict__ ap, const float* __restrict__ agr, float* __restrict__ am, float* __restrict__ av,
-                                           const GroupCfg* __restrict__ agrp, float* __restrict__ atarget, int an, int hdr, const AdamTask& t, const AdamSnap& snap, const DpPull& dp) {
+                                           const GroupCfg* __restrict__ agrp, float* __restrict__ atarget, int an, int hdr, const AdamTask& t, const AdamSnap& snap, const DpPull& dp,
+                                           long long mdelta) {
     constexpr bool dpon = DP != 0;
     // (the arena pointers and the group record are preloaded arguments: these loads go out before the record `t` has arrived)
     const long long i = ((long long)bid * 256 + threadIdx.x) * 4;
@@ -424,7 +428,7 @@ __device__ __forceinline__ void adam_elems(const int bid, float* __restrict__ ap
     // ranges whose optimizer ran in the weight-gradient epilogues (FLAG_ADAM): nothing to do here
     if (t.nskip > 0 && i >= t.skip_off[0] && i < t.skip_off[0] + t.skip_n[0]) return;
     if (t.nskip > 1 && i >= t.skip_off[1] && i < t.skip_off[1] + t.skip_n[1]) return;
-    const bool pol_on = atarget && (!t.pol_steps || ((*t.pol_steps) % t.pol_period) == 0);
+    const bool pol_on = atarget && (!t.pol_steps || ((*rl_mv<GRP>(t.pol_steps, mdelta)) % t.pol_period) == 0);
     if (vec && t.nslab) {
         // split-K partial gradients finished here (AdamTask::Slab): all partials in flight together, summed in split order (the order of
         // the finishing launch this replaces: bit-identical), the sum filed in the gradient arena for whoever reads gradients
@@ -438,7 +442,7 @@ __device__ __forceinline__ void adam_elems(const int bid, float* __restrict__ ap
             if (sl.cols == 0 || sl.cols == sl.ldpad) {
                 const long long task = l / sl.per, r = l - task * sl.per;
                 const long long ss = sl.cols ? sl.sstride : sl.per;
-                const float* s0 = sl.slab + (size_t)task * splits * sl.per + r;
+                const float* s0 = rl_mv<GRP>(sl.slab, mdelta) + (size_t)task * splits * sl.per + r;
                 f32x4 part[16];
 #pragma unroll
                 for (int sp = 0; sp < 16; ++sp) part[sp] = *reinterpret_cast<const f32x4*>(s0 + (size_t)min(sp, splits - 1) * ss);
@@ -450,7 +454,7 @@ __device__ __forceinline__ void adam_elems(const int bid, float* __restrict__ ap
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
                     const long long ll = l + s, row = ll / sl.cols, col = ll - row * sl.cols;
-                    const float* s0 = sl.slab + (size_t)row * sl.ldpad + col;
+                    const float* s0 = rl_mv<GRP>(sl.slab, mdelta) + (size_t)row * sl.ldpad + col;
                     float a = s0[0];
                     for (int sp = 1; sp < splits; ++sp) a += s0[(size_t)sp * sl.sstride];
                     g[s] = a;
@@ -539,22 +543,18 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ ap, const
     const DpPull nodp = DpPull();
     adam_block<0>(blockIdx.x, ap, agr, am, av, agrp, atarget, an, hdr, t, fin, nfin, sf, fill_blocks, sf2, fill2_blocks, snap, snap_blocks, nodp);
 }
-// group form (group.h): member = blockIdx.y; the arenas, the record, the riders and the metric finishers' pointers move to the member's block
+// group form (group.h): member = blockIdx.y; the arenas, the riders and the metric finishers' pointers move to the member's block, and so do the
+// pointers adam_block / adam_elems read from the record `t`, where they read them (the record itself stays in the kernel-argument segment).  No
+// folded snapshot (the launcher refuses one: a group has no deferred chain); `snap` only fills the argument list.
 __global__ __launch_bounds__(256) void adam_kernel_grp(float* ap, const float* agr, float* am, float* av, const GroupCfg* agrp, float* atarget, int an, int hdr, AdamTask t,
                                                        const FinTask* __restrict__ fin, int nfin, SlotFill sf, int fill_blocks, SlotFill sf2, int fill2_blocks, AdamSnap snap, int snap_blocks,
                                                        long long mstride, long long rstride) {
     __builtin_amdgcn_s_setprio(3);
     const long long dm = (long long)blockIdx.y * mstride, dr = (long long)blockIdx.y * rstride;
     rl_rb(ap, dm); rl_rb(agr, dm); rl_rb(am, dm); rl_rb(av, dm); rl_rb(agrp, dm); rl_rb(atarget, dm);
-    AdamTask tt = t; rl_rebase(tt, dm);
     SlotFill s1 = sf, s2 = sf2; rl_rebase(s1, dm, dr); rl_rebase(s2, dm, dr);
-    AdamSnap sn = snap;
-    rl_rb(sn.block, dm);
-#pragma unroll
-    for (int q = 0; q < COPY_MAX_SEGS; ++q) { rl_rb(sn.segs.src[q], dm); rl_rb(sn.segs.dst[q], dm); }
-    rl_rb(sn.segs.isrc, dm); rl_rb(sn.segs.idst, dm);
     const DpPull nodp = DpPull();
-    adam_block<0, true>(blockIdx.x, ap, agr, am, av, agrp, atarget, an, hdr, tt, fin, nfin, s1, fill_blocks, s2, fill2_blocks, sn, snap_blocks, nodp, dm);
+    adam_block<0, true>(blockIdx.x, ap, agr, am, av, agrp, atarget, an, hdr, t, fin, nfin, s1, fill_blocks, s2, fill2_blocks, snap, snap_blocks, nodp, dm);
 }
 template <int DP>
 __global__ __launch_bounds__(256) void adam_dp_kernel(float* __restrict__ ap, const float* __restrict__ agr, float* __restrict__ am, float* __restrict__ av,
@@ -740,7 +740,7 @@ extern "C" int rl_launch_adam(const AdamTask* task, int adam_blocks, const FinTa
     AdamSnap nosnap = AdamSnap();
     DpPull dpv = DpPull();
     const RlGrp* gr = rl_grp_active();
-    if (gr && ((dp && dp->world > 1) || (task && task->sh))) return RL_GRP_UNSUPPORTED;
+    if (gr && ((dp && dp->world > 1) || (task && task->sh) || (snap && snap->on))) return RL_GRP_UNSUPPORTED;
     if (dp && dp->world > 1) {
         if (!task || adam_blocks <= 0 || task->nslab || task->nskip) return -9;     // (split-K folds and epilogue optimizers are single-rank forms: the gradient must be complete in the arena)
         dpv = *dp; dpv.nblocks = adam_blocks + 1;                                  // the optimizer blocks and the trailing block take a ticket

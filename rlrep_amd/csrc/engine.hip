@@ -1330,9 +1330,14 @@ static void slot_fill_params(rlrep_agent* ag, int slot, const float* ring_dev, c
     p.XE = s.XE; p.XF = s.XF; p.XF2 = s.XF2; p.XFpi = s.XFpi; p.R = s.R; p.D = s.D;
 }
 
+static bool in_member0(const rlrep_agent* ag, const void* p, long long bytes);
 int32_t rlrep_prefetch_batch(rlrep_agent* ag, const float* ring_dev, const int32_t* idx_dev, int32_t batch) {
-    GROUP_REFUSE("prefetch_batch")
     if (!ag || !ring_dev || !idx_dev) { rl_set_error("prefetch_batch: bad argument"); return RLREP_ERR_ARG; }
+    // a seed group's gather rides in its group optimizer launch: member r reads ring r (the stride its train prologue was given) through ITS
+    // index stream, which must therefore lie in member 0's block (it is read at every member's stride)
+    if (ag->members > 0 && !in_member0(ag, idx_dev, 4ll * batch)) {
+        rl_set_error("prefetch_batch: a seed group's indices must lie inside member 0's block"); return RLREP_ERR_ARG;
+    }
     ag->pf_armed = false;
     if (batch != ag->B || rl_off("prefetch_batch")) return 0;      // would need a rebuild: let replay_sample do it
     slot_fill_params(ag, 0, ring_dev, idx_dev, ag->pf_fill);
@@ -1341,8 +1346,8 @@ int32_t rlrep_prefetch_batch(rlrep_agent* ag, const float* ring_dev, const int32
 }
 
 int32_t rlrep_prefetch_batch_slot(rlrep_agent* ag, int32_t slot, const float* ring_dev, const int32_t* idx_dev, int32_t batch) {
-    GROUP_REFUSE("prefetch_batch_slot")
     if (slot == 0) return rlrep_prefetch_batch(ag, ring_dev, idx_dev, batch);
+    GROUP_REFUSE("prefetch_batch_slot")
     if (!ag || !ring_dev || !idx_dev || slot != 1 || ag->d.alg != RLREP_ALG_SPEDERSAC) { rl_set_error("prefetch_batch_slot: bad argument"); return RLREP_ERR_ARG; }
     ag->pf2_armed = false;
     if (batch != ag->B || rl_off("prefetch_batch")) return 0;
@@ -1711,8 +1716,8 @@ int32_t rlrep_feature_backward_part(rlrep_agent* ag, int32_t part, const float* 
 }
 
 int32_t rlrep_sync_frozen(rlrep_agent* ag, void* stream) {
-    GROUP_REFUSE("sync_frozen")
     if (!ag) return RLREP_ERR_ARG;
+    GrpScope grp_scope_(ag);                   // (a seed group: every member's copy, in one launch)
     ag->last_launches += (int)ag->sync_prog.stages.size();
     return ag->sync_prog.run((hipStream_t)stream);
 }
@@ -2027,7 +2032,9 @@ int32_t rlrep_group_max_members(void) { return RLREP_GROUP_MAX_MEMBERS; }
 int32_t rlrep_group_create(const rlrep_dims* dims, const rlrep_hyper* hyper, const rlrep_arenas* arenas, int32_t members, int64_t member_stride_bytes,
                            void* stream, rlrep_agent** out) {
     if (!dims || !hyper || !arenas || !out) { rl_set_error("group_create: null argument"); return RLREP_ERR_ARG; }
-    if (dims->alg != RLREP_ALG_SAC) { rl_set_error("group_create: seed groups are built for sac only (alg %d)", dims->alg); return RLREP_ERR_ARG; }
+    if (dims->alg != RLREP_ALG_SAC && dims->alg != RLREP_ALG_CTRLSAC) {
+        rl_set_error("group_create: seed groups are built for sac and ctrlsac only (alg %d)", dims->alg); return RLREP_ERR_ARG;
+    }
     if (members < 1 || members > RLREP_GROUP_MAX_MEMBERS) { rl_set_error("group_create: members %d outside [1, %d]", members, RLREP_GROUP_MAX_MEMBERS); return RLREP_ERR_ARG; }
     if (dims->world_size > 1 || hyper->world_size > 1) { rl_set_error("group_create: a seed group does not attach to data parallel (world_size %d)", std::max(dims->world_size, hyper->world_size)); return RLREP_ERR_ARG; }
     if (member_stride_bytes <= 0 || (member_stride_bytes & 255)) { rl_set_error("group_create: member stride %lld is not a positive multiple of 256 bytes", (long long)member_stride_bytes); return RLREP_ERR_ARG; }

@@ -426,6 +426,29 @@ __global__ __launch_bounds__(256) void gemm16_duo_kernel(int hdr, int total, int
     else gemm16_tile<LD_COL, LD_COL, NF2, false, false, false, false, GemmTask, -1, -1>(t, tr, tc, red, bsum, nullptr DUO_TIM);
 #undef DUO_TIM
 }
+// group form (group.h): member = blockIdx.y, the task record rebased by member * stride (as gemm16_kernel_grp); x decomposition and tile bodies as above
+template <bool VA1, int NF2>
+__global__ __launch_bounds__(256) void gemm16_duo_kernel_grp(int hdr, int total, int tb0, int tb1, int tb2, int tb3, int tb4, int tb5, int tb6, int tb7,
+                                                             unsigned tc01, unsigned tc23, unsigned tc45, unsigned tc67, GemmBatch gb, long long mstride) {
+    __shared__ float red[4][NF2][4][64];
+    __shared__ float bsum[4][16];
+    const int low_prio = hdr & 1, split = hdr >> 4;
+    const int tb[GEMM_MAX_TASKS] = {tb0, tb1, tb2, tb3, tb4, tb5, tb6, tb7};
+    const int tcs[GEMM_MAX_TASKS] = {(int)(tc01 & 0xffffu), (int)(tc01 >> 16), (int)(tc23 & 0xffffu), (int)(tc23 >> 16),
+                                     (int)(tc45 & 0xffffu), (int)(tc45 >> 16), (int)(tc67 & 0xffffu), (int)(tc67 >> 16)};
+    if (!low_prio) __builtin_amdgcn_s_setprio(3);
+    const int bid = blockIdx.x;
+    int ti = 0, base = tb[0], tiles_c = tcs[0];
+#pragma unroll
+    for (int q = 1; q < GEMM_MAX_TASKS; ++q) if (bid >= tb[q]) { ti = q; base = tb[q]; tiles_c = tcs[q]; }
+    GemmTask t = gb.t[ti];
+    rl_rebase(t, (long long)blockIdx.y * mstride);
+    const int local = bid - base;
+    const int tr = local / tiles_c, tc = local - tr * tiles_c;
+    (void)total;
+    if (ti < split) gemm16_tile<LD_ROW, LD_COL, 1, VA1, false, false, false, GemmTask, -1, -1>(t, tr, tc, reinterpret_cast<float (&)[4][1][4][64]>(red), bsum, nullptr RL_TIM_NONE);
+    else gemm16_tile<LD_COL, LD_COL, NF2, false, false, false, false, GemmTask, -1, -1>(t, tr, tc, red, bsum, nullptr RL_TIM_NONE);
+}
 
 // ------------------------------------------------------------------------------------------------
 // host launcher
@@ -662,7 +685,6 @@ static int launch_gemm16_impl(int la, int lb, int nf, const GemmBatch* gb_in, in
 
 // tasks [0, split): LD_ROW x LD_COL at NF = 1; tasks [split, ntasks): LD_COL x LD_COL at NF = nf2 (1 or 4); tile bases / column-tile counts set by the caller
 extern "C" int rl_launch_gemm16_duo(int split, int nf2, const GemmBatch* gb_in, int total_tiles, hipStream_t st) {
-    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     if (total_tiles <= 0) return 0;
     if (split <= 0 || split >= gb_in->ntasks || (nf2 != 1 && nf2 != 4)) return -4;
     GemmBatch planned = *gb_in;
@@ -679,10 +701,10 @@ extern "C" int rl_launch_gemm16_duo(int split, int nf2, const GemmBatch* gb_in, 
     dim3 g(total_tiles);
 #define DUO_ARGS hdr, planned.total, planned.tb[0], planned.tb[1], planned.tb[2], planned.tb[3], planned.tb[4], planned.tb[5], planned.tb[6], planned.tb[7], \
     (unsigned)(planned.tcs[0] | (planned.tcs[1] << 16)), (unsigned)(planned.tcs[2] | (planned.tcs[3] << 16)), (unsigned)(planned.tcs[4] | (planned.tcs[5] << 16)), (unsigned)(planned.tcs[6] | (planned.tcs[7] << 16)), planned
-    if (va && nf2 == 1) hipLaunchKernelGGL((gemm16_duo_kernel<true, 1>), g, dim3(256), 0, st, DUO_ARGS);
-    else if (va) hipLaunchKernelGGL((gemm16_duo_kernel<true, 4>), g, dim3(256), 0, st, DUO_ARGS);
-    else if (nf2 == 1) hipLaunchKernelGGL((gemm16_duo_kernel<false, 1>), g, dim3(256), 0, st, DUO_ARGS);
-    else hipLaunchKernelGGL((gemm16_duo_kernel<false, 4>), g, dim3(256), 0, st, DUO_ARGS);
+    if (va && nf2 == 1) RL_LAUNCH16(gemm16_duo_kernel, (true, 1), g, st, DUO_ARGS);
+    else if (va) RL_LAUNCH16(gemm16_duo_kernel, (true, 4), g, st, DUO_ARGS);
+    else if (nf2 == 1) RL_LAUNCH16(gemm16_duo_kernel, (false, 1), g, st, DUO_ARGS);
+    else RL_LAUNCH16(gemm16_duo_kernel, (false, 4), g, st, DUO_ARGS);
 #undef DUO_ARGS
     ++g_rl_front[3];
     return (int)hipGetLastError();

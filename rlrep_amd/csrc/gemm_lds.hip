@@ -26,6 +26,7 @@
 // search costs no load, and the first scalar-load round trip is the task's own record (it used to be the second).
 #define GL_DIR_PARAMS int d0, int d1, int d2, int d3, int d4, int d5, int d6, int d7
 #define GL_DIR_ARGS(D) (D)[0], (D)[1], (D)[2], (D)[3], (D)[4], (D)[5], (D)[6], (D)[7]
+#define GL_DIR_FWD d0, d1, d2, d3, d4, d5, d6, d7
 extern long long g_rl_launches;
 #include "kparams.h"
 #include "group.h"
@@ -121,24 +122,26 @@ __device__ __forceinline__ void gl_frag(const float* __restrict__ S, int wbase, 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 // one output element (outputs whose row stride / width / pointers rule out 16-byte accesses)
-__device__ __forceinline__ void gl_epilogue1(const GemmTask& t, int r, int c, float v) {
+// GRP (seed groups, group.h): every pointer of the record is dereferenced at + dm bytes (the member's block); the null tests read the record's own
+template <bool GRP = false>
+__device__ __forceinline__ void gl_epilogue1(const GemmTask& t, int r, int c, float v, long long dm = 0) {
     v *= t.scale;
-    float* cp = t.C + (size_t)r * t.ldc + c;
+    float* cp = rl_mv<GRP>(t.C, dm) + (size_t)r * t.ldc + c;
     if (t.epi == EPI_FWD) {
-        if (t.bias) v += t.bias[c];
+        if (t.bias) v += rl_mv<GRP>(t.bias, dm)[c];
         float y;
         switch (t.act) {
         case ACT_RELU: y = fmaxf(v, 0.f); break;
         case ACT_ELU: y = elu_f(v); break;
-        case ACT_SIN: y = sinf(v); t.out2[(size_t)r * t.ldout2 + c] = v; break;
+        case ACT_SIN: y = sinf(v); rl_mv<GRP>(t.out2, dm)[(size_t)r * t.ldout2 + c] = v; break;
         case ACT_TANH: y = tanhf(v); break;
         default: y = v;
         }
         *cp = y;
     } else if (t.epi == EPI_DX) {
-        if (t.r1u) v += t.r1u[r] * t.r1v[c];
+        if (t.r1u) v += rl_mv<GRP>(t.r1u, dm)[r] * rl_mv<GRP>(t.r1v, dm)[c];
         if (t.act != ACT_NONE) {
-            const float a = t.aux[(size_t)r * t.ldaux + c];
+            const float a = rl_mv<GRP>(t.aux, dm)[(size_t)r * t.ldaux + c];
             switch (t.act) {
             case ACT_RELU: v = a > 0.f ? v : 0.f; break;
             case ACT_ELU: v *= elu_grad_from_out(a); break;
@@ -156,21 +159,23 @@ __device__ __forceinline__ void gl_epilogue1(const GemmTask& t, int r, int c, fl
 // bias_pre: the four bias values of columns c .. c + 3, loaded by the caller BEFORE its store loop (a tile's store loop keeps its columns and walks the
 // rows: loaded here, the bias was a dependent global round trip in every iteration -- eight per wave and 128-wide tile, ~15 us of a 60 us workgroup
 // in the 788 MB forward of the nabla-mu head); nullptr: load it here
-__device__ __forceinline__ f32x4 gl_bias4(const GemmTask& t, int c) {
+template <bool GRP = false>
+__device__ __forceinline__ f32x4 gl_bias4(const GemmTask& t, int c, long long dm = 0) {
     f32x4 b = {0.f, 0.f, 0.f, 0.f};
-    if (t.epi == EPI_FWD && t.bias && !(t.flags & FLAG_SCALAR_C) && c + 4 <= t.Cn) b = ld4(t.bias + c);
+    if (t.epi == EPI_FWD && t.bias && !(t.flags & FLAG_SCALAR_C) && c + 4 <= t.Cn) b = ld4(rl_mv<GRP>(t.bias, dm) + c);
     return b;
 }
-__device__ __forceinline__ void gl_epilogue4(const GemmTask& t, int r, int c, f32x4 v, const f32x4* bias_pre = nullptr) {
+template <bool GRP = false>
+__device__ __forceinline__ void gl_epilogue4(const GemmTask& t, int r, int c, f32x4 v, const f32x4* bias_pre = nullptr, long long dm = 0) {
     if (t.flags & FLAG_SCALAR_C) {
 #pragma unroll
-        for (int q = 0; q < 4; ++q) if (c + q < t.Cn) gl_epilogue1(t, r, c + q, v[q]);
+        for (int q = 0; q < 4; ++q) if (c + q < t.Cn) gl_epilogue1<GRP>(t, r, c + q, v[q], dm);
         return;
     }
     v *= t.scale;
-    float* cp = t.C + (size_t)r * t.ldc + c;
+    float* cp = rl_mv<GRP>(t.C, dm) + (size_t)r * t.ldc + c;
     if (t.epi == EPI_FWD) {
-        if (t.bias) v += bias_pre ? *bias_pre : ld4(t.bias + c);
+        if (t.bias) v += bias_pre ? *bias_pre : ld4(rl_mv<GRP>(t.bias, dm) + c);
         f32x4 y;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -183,12 +188,12 @@ __device__ __forceinline__ void gl_epilogue4(const GemmTask& t, int r, int c, f3
             default: y[q] = x;
             }
         }
-        if (t.act == ACT_SIN) st4(t.out2 + (size_t)r * t.ldout2 + c, v);
+        if (t.act == ACT_SIN) st4(rl_mv<GRP>(t.out2, dm) + (size_t)r * t.ldout2 + c, v);
         st4(cp, y);
     } else if (t.epi == EPI_DX) {
-        if (t.r1u) v += t.r1u[r] * ld4(t.r1v + c);
+        if (t.r1u) v += rl_mv<GRP>(t.r1u, dm)[r] * ld4(rl_mv<GRP>(t.r1v, dm) + c);
         if (t.act != ACT_NONE) {
-            const f32x4 a = ld4(t.aux + (size_t)r * t.ldaux + c);
+            const f32x4 a = ld4(rl_mv<GRP>(t.aux, dm) + (size_t)r * t.ldaux + c);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 switch (t.act) {
@@ -216,124 +221,19 @@ __device__ __forceinline__ int gl_xcd_remap(int local, int n) {
 
 template <int BT, int LA, int LB>
 __global__ __launch_bounds__(256, (BT == 128 ? 2 : 4)) void gemm_lds_kernel(GL_DIR_PARAMS, GemmBatch gb) {
-    const int gdir[GEMM_MAX_TASKS] = {d0, d1, d2, d3, d4, d5, d6, d7};
-    constexpr int WT = BT / 2, TT = WT / 16;
-    constexpr int SA = GlTile<BT, LA>::FLOATS, SB = GlTile<BT, LB>::FLOATS;
-    constexpr int EPF = 4 * WT * (WT + 4);
-    constexpr int LDSF = (2 * (SA + SB) > EPF) ? 2 * (SA + SB) : EPF;
-    __shared__ __attribute__((aligned(16))) float lds[LDSF];
-
-    const int bid = blockIdx.x;
-    int ti = 0;
-#pragma unroll
-    for (int q = 1; q < GEMM_MAX_TASKS; ++q) if (bid >= gdir[q]) ti = q;          // (preloaded directory: first tiles, INT_MAX beyond the last task)
-    const GemmTask& t = gb.t[ti];
-    const float* const pA = t.A; const float* const pB = t.B;
-    const int lda = t.lda, ldb = t.ldb, R = t.R, Cn = t.Cn, K = t.K;
-    const int tiles_c = t.tiles_c, splits = t.splits, kchunk = t.kchunk;
-    const int tiles_r = (R + BT - 1) / BT;
-
-    const int local = gl_xcd_remap(bid - t.tile_base, t.ntiles);
-    const int per_split = tiles_r * tiles_c;
-    const int split = local / per_split, rem = local - split * per_split;
-    const int tc = rem / tiles_r, tr = rem - tc * tiles_r;
-    const int r0 = tr * BT, c0 = tc * BT;
-    const int kbeg = split * kchunk, kend = min(K, kbeg + kchunk);
-    const int nk = (kend - kbeg + GL_BK - 1) / GL_BK;
-
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int wr = w >> 1, wc = w & 1;
-    const int i = lane & 15, kq = lane >> 4;
-
-    f32x4 acc[TT][TT];
-#pragma unroll
-    for (int a = 0; a < TT; ++a)
-#pragma unroll
-        for (int b = 0; b < TT; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float asum[TT];
-#pragma unroll
-    for (int a = 0; a < TT; ++a) asum[a] = 0.f;
-
-    const bool vecA = !(t.flags & FLAG_SCALAR_A), vecB = !(t.flags & FLAG_SCALAR_B);
-    f32x4 va[BT / 32], vb[BT / 32];
-    gl_stage_load<BT, LA>(pA, lda, r0, R, kbeg, kend, vecA, va);
-    gl_stage_load<BT, LB>(pB, ldb, c0, Cn, kbeg, kend, vecB, vb);
-    gl_stage_write<BT, LA>(lds, va);
-    gl_stage_write<BT, LB>(lds + SA, vb);
-    __syncthreads();
-
-    for (int kt = 0; kt < nk; ++kt) {
-        const int cur = kt & 1;
-        // slice kt+1 (past the end: a clamped, zeroed re-read that nobody consumes) -- issued before the MFMAs of slice kt
-        const int kn = kbeg + GL_BK * (kt + 1);
-        gl_stage_load<BT, LA>(pA, lda, r0, R, kn, kend, vecA, va);
-        gl_stage_load<BT, LB>(pB, ldb, c0, Cn, kn, kend, vecB, vb);
-        const float* As = lds + cur * (SA + SB);
-        const float* Bs = As + SA;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float fa[TT][2], fb[TT][2];
-            gl_frag<BT, LA, TT>(As, wr * WT, i, kq, j, fa);
-            gl_frag<BT, LB, TT>(Bs, wc * WT, i, kq, j, fb);
-#pragma unroll
-            for (int e = 0; e < 2; ++e)
-#pragma unroll
-                for (int a = 0; a < TT; ++a)
-#pragma unroll
-                    for (int b = 0; b < TT; ++b)
-                        acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[a][e], fb[b][e], acc[a][b], 0, 0, 0);
-            if (LA == LD_COL) {
-#pragma unroll
-                for (int a = 0; a < TT; ++a) asum[a] += fa[a][0] + fa[a][1];
-            }
-        }
-        float* Sn = lds + (cur ^ 1) * (SA + SB);
-        gl_stage_write<BT, LA>(Sn, va);
-        gl_stage_write<BT, LB>(Sn + SA, vb);
-        __syncthreads();
-    }
-
-    const size_t C4w = (size_t)((Cn + 3) & ~3);
-    // bias gradient (EPI_DW): row sums of operand A, taken from the fragments the column-0 waves of column-tile 0 consumed
-    const bool has_bias = LA == LD_COL && t.epi == EPI_DW && (t.flags & FLAG_BIASGRAD) && tc == 0;
-    if (has_bias && wc == 0) {
-#pragma unroll
-        for (int a = 0; a < TT; ++a) {
-            float s = asum[a];
-            s += __shfl_xor(s, 16, 64);
-            s += __shfl_xor(s, 32, 64);
-            const int r = r0 + wr * WT + a * 16 + lane;
-            if (lane < 16 && r < R) {
-                if (splits > 1) t.bslab[(size_t)split * R + r] = s;
-                else t.out2[r] = s;
-            }
-        }
-    }
-
-    // accumulators -> this wave's LDS patch -> 16-byte row segments (coalesced stores, vector epilogue operands)
-    float* E = lds + w * (WT * (WT + 4));
-#pragma unroll
-    for (int a = 0; a < TT; ++a)
-#pragma unroll
-        for (int b = 0; b < TT; ++b)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) E[(a * 16 + 4 * kq + q) * (WT + 4) + b * 16 + i] = acc[a][b][q];
-    constexpr int LPR = WT / 4, RPI = 64 / LPR;
-    const f32x4 bpre = splits > 1 ? (f32x4){0.f, 0.f, 0.f, 0.f} : gl_bias4(t, c0 + wc * WT + (lane % LPR) * 4);      // (this lane's columns: the same in every iteration)
-#pragma unroll 4
-    for (int it = 0; it < WT / RPI; ++it) {
-        const int rr = it * RPI + lane / LPR, cc = (lane % LPR) * 4;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(E + rr * (WT + 4) + cc);
-        const int r = r0 + wr * WT + rr, c = c0 + wc * WT + cc;
-        if (r < R && c < Cn) {
-            if (splits > 1) st4(t.slab + ((size_t)split * R + r) * C4w + c, v);       // partial tile: the finishing blocks add the slabs in split order
-            else gl_epilogue4(t, r, c, v, &bpre);
-        }
-    }
+    constexpr bool GRP = false; constexpr long long dm = 0;
+#include "gemm_lds_body.h"
+}
+// group form (group.h): member = blockIdx.y
+template <int BT, int LA, int LB>
+__global__ __launch_bounds__(256, (BT == 128 ? 2 : 4)) void gemm_lds_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride) {
+    constexpr bool GRP = true; const long long dm = (long long)blockIdx.y * mstride;
+#include "gemm_lds_body.h"
 }
 
 // split-K finisher: out = epilogue(sum over splits, in split order); bias gradient likewise
-__global__ __launch_bounds__(256) void gemm_lds_fin_kernel(GL_DIR_PARAMS, GemmBatch gb) {
+template <bool GRP>
+__device__ __forceinline__ void gemm_lds_fin_kernel_body(GL_DIR_PARAMS, const GemmBatch& gb, long long dm) {
     const int gdir[GEMM_MAX_TASKS] = {d0, d1, d2, d3, d4, d5, d6, d7};
     const int bid = blockIdx.x;
     int ti = -1;
@@ -349,18 +249,25 @@ __global__ __launch_bounds__(256) void gemm_lds_fin_kernel(GL_DIR_PARAMS, GemmBa
         const long long e = (long long)lb * 256 + threadIdx.x;
         if (e >= nvec) return;
         const int r = (int)(e / C4), c = (int)(e - (long long)r * C4) * 4;
-        const float* p = t.slab + ((size_t)r * C4) * 4 + c;
+        const float* p = rl_mv<GRP>(t.slab, dm) + ((size_t)r * C4) * 4 + c;
         const size_t stride = (size_t)R * C4 * 4;
         f32x4 v = ld4(p);
         for (int s = 1; s < t.splits; ++s) v += ld4(p + s * stride);
-        gl_epilogue4(t, r, c, v);
+        gl_epilogue4<GRP>(t, r, c, v, nullptr, dm);
     } else if (t.epi == EPI_DW && (t.flags & FLAG_BIASGRAD)) {
         const int r = (lb - nb_main) * 256 + threadIdx.x;
         if (r >= R) return;
-        float s = t.bslab[r];
-        for (int q = 1; q < t.splits; ++q) s += t.bslab[(size_t)q * R + r];
-        t.out2[r] = s;
+        float s = rl_mv<GRP>(t.bslab, dm)[r];
+        for (int q = 1; q < t.splits; ++q) s += rl_mv<GRP>(t.bslab, dm)[(size_t)q * R + r];
+        rl_mv<GRP>(t.out2, dm)[r] = s;
     }
+}
+__global__ __launch_bounds__(256) void gemm_lds_fin_kernel(GL_DIR_PARAMS, GemmBatch gb) {
+    gemm_lds_fin_kernel_body<false>(GL_DIR_FWD, gb, 0);
+}
+// group form (group.h): member = blockIdx.y; the tasks' pointers are moved by member * stride where the body loads them
+__global__ __launch_bounds__(256) void gemm_lds_fin_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride) {
+    gemm_lds_fin_kernel_body<true>(GL_DIR_FWD, gb, (long long)blockIdx.y * mstride);
 }
 
 // ================================================================================================
@@ -453,120 +360,14 @@ __device__ __forceinline__ void x3_stage_write(unsigned char* __restrict__ img, 
 // two workgroups per CU, so split (VALU), fragment reads (LDS) and the matrix pipe overlap across waves
 template <int LA, int LB>
 __global__ __launch_bounds__(512, 4) void gemm_x3_kernel(GL_DIR_PARAMS, GemmBatch gb) {
-    const int gdir[GEMM_MAX_TASKS] = {d0, d1, d2, d3, d4, d5, d6, d7};
-    constexpr int BT = 128;
-    constexpr int EPB = 8 * 32 * 68 * 4;                         // epilogue patches [32][68] per wave, bytes
-    constexpr int STB = 6 * X3_IMGB;                             // six images
-    constexpr int LDSB = EPB > STB ? EPB : STB;
-    __shared__ __attribute__((aligned(16))) float lds[LDSB / 4];
-    unsigned char* const L = reinterpret_cast<unsigned char*>(lds);
-
-    const int bid = blockIdx.x;
-    int ti = 0;
-#pragma unroll
-    for (int q = 1; q < GEMM_MAX_TASKS; ++q) if (bid >= gdir[q]) ti = q;          // (preloaded directory: first tiles, INT_MAX beyond the last task)
-    const GemmTask& t = gb.t[ti];
-    const float* const pA = t.A; const float* const pB = t.B;
-    const int lda = t.lda, ldb = t.ldb, R = t.R, Cn = t.Cn, K = t.K;
-    const int tiles_c = t.tiles_c, splits = t.splits, kchunk = t.kchunk;
-    const int tiles_r = (R + BT - 1) / BT;
-    const int local = gl_xcd_remap(bid - t.tile_base, t.ntiles);
-    const int per_split = tiles_r * tiles_c;
-    const int split = local / per_split, rem = local - split * per_split;
-    const int tc = rem / tiles_r, tr = rem - tc * tiles_r;
-    const int r0 = tr * BT, c0 = tc * BT;
-    const int kbeg = split * kchunk, kend = min(K, kbeg + kchunk);
-    const int nk = (kend - kbeg + GL_BK - 1) / GL_BK;
-
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int wr = w >> 1, wc = w & 1;
-    const int r32 = lane & 31, hh = lane >> 5;
-    const bool want_bias = (LA == LD_COL) && t.epi == EPI_DW && (t.flags & FLAG_BIASGRAD) && tc == 0;
-
-    f32x16 acc[2];
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[b][q] = 0.f;
-    float rs = 0.f;
-
-    float ea[8], eb[8];
-    x3_stage_load<LA>(pA, lda, r0, R, kbeg, kend, ea);
-    x3_stage_load<LB>(pB, ldb, c0, Cn, kbeg, kend, eb);
-
-    // The two workgroups of a CU alternate a VALU phase (split + LDS write) and a matrix phase; started together they
-    // stay in step.  Workgroups are dealt one per CU before any CU gets its second (observed, speed only), so delaying
-    // every second group of 256 by about one VALU phase starts the pair in anti-phase.
-    if (X3_STAGGER && ((blockIdx.x >> 8) & 1)) __builtin_amdgcn_s_sleep(X3_STAGGER);
-
-    // fragment of 16-deep block c: chunk 2 c + hh of this lane's row -- the swizzle term (row >> 2) & 3 is the same for rows r32, 32 + r32, ...
-    const unsigned char* const fa = L + x3r_off(wr * 32 + r32, hh);
-    const unsigned char* const fb = L + 3 * X3_IMGB + x3r_off(wc * 64 + r32, hh);
-    const int fsw = x3r_off(r32, 2 + hh) - x3r_off(r32, hh);            // block 1 relative to block 0: +32 or -32 bytes
-
-    for (int kt = 0; kt < nk; ++kt) {
-        if (want_bias) rs += ((ea[0] + ea[1]) + (ea[2] + ea[3])) + ((ea[4] + ea[5]) + (ea[6] + ea[7]));
-        x3_stage_write<LA>(L, ea);
-        x3_stage_write<LB>(L + 3 * X3_IMGB, eb);
-        __syncthreads();
-        const int kn = kbeg + GL_BK * (kt + 1);
-        x3_stage_load<LA>(pA, lda, r0, R, kn, kend, ea);
-        x3_stage_load<LB>(pB, ldb, c0, Cn, kn, kend, eb);
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            bf16x8 a[3], b[2][3];
-#pragma unroll
-            for (int m = 0; m < 3; ++m) {
-                a[m] = *reinterpret_cast<const bf16x8*>(fa + m * X3_IMGB + fsw * c);
-                b[0][m] = *reinterpret_cast<const bf16x8*>(fb + m * X3_IMGB + fsw * c);
-                b[1][m] = *reinterpret_cast<const bf16x8*>(fb + 32 * X3_RSB + m * X3_IMGB + fsw * c);
-            }
-#pragma unroll
-            for (int y = 0; y < 2; ++y) {
-                f32x16 v = acc[y];
-                v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[y][2], v, 0, 0, 0);
-                v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[y][0], v, 0, 0, 0);
-                v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[y][1], v, 0, 0, 0);
-                v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[y][1], v, 0, 0, 0);
-                v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[y][0], v, 0, 0, 0);
-                v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[y][0], v, 0, 0, 0);
-                acc[y] = v;
-            }
-        }
-        __syncthreads();
-    }
-
-    // bias gradient: this thread's row (k-major A: row tid & 127, one of four k groups) -> LDS -> fixed-order sum
-    if (want_bias) {
-        float* part = lds;                                   // [128][4]
-        part[(threadIdx.x & 127) * 4 + (threadIdx.x >> 7)] = rs;
-        __syncthreads();
-        if (threadIdx.x < 128) {
-            const float* q = part + threadIdx.x * 4;
-            const float s = (q[0] + q[1]) + (q[2] + q[3]);
-            const int r = r0 + threadIdx.x;
-            if (r < R) { if (splits > 1) t.bslab[(size_t)split * R + r] = s; else t.out2[r] = s; }
-        }
-        __syncthreads();
-    }
-
-    // accumulators (32x32 C/D map: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)) -> LDS patch -> row segments
-    float* E = lds + w * (32 * 68);
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) E[((q & 3) + 8 * (q >> 2) + 4 * hh) * 68 + y * 32 + r32] = acc[y][q];
-    const f32x4 bpre = splits > 1 ? (f32x4){0.f, 0.f, 0.f, 0.f} : gl_bias4(t, c0 + wc * 64 + (lane & 15) * 4);      // (this lane's columns: the same in every iteration)
-#pragma unroll 4
-    for (int it = 0; it < 8; ++it) {
-        const int rr = it * 4 + (lane >> 4), cc = (lane & 15) * 4;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(E + rr * 68 + cc);
-        const int r = r0 + wr * 32 + rr, c = c0 + wc * 64 + cc;
-        if (r < R && c < Cn) {
-            if (splits > 1) st4(t.slab + ((size_t)split * R + r) * ((Cn + 3) & ~3) + c, v);
-            else gl_epilogue4(t, r, c, v, &bpre);
-        }
-    }
+    constexpr bool GRP = false; constexpr long long dm = 0;
+#include "gemm_x3_body.h"
+}
+// group form (group.h): member = blockIdx.y
+template <int LA, int LB>
+__global__ __launch_bounds__(512, 4) void gemm_x3_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride) {
+    constexpr bool GRP = true; const long long dm = (long long)blockIdx.y * mstride;
+#include "gemm_x3_body.h"
 }
 
 // ================================================================================================
@@ -634,133 +435,14 @@ __device__ __forceinline__ unsigned x3t_addr(unsigned lds_base, int kq, int chun
 // images, ds_read_b128 fragments) -- and only B k-major through the transposed reads (dX = G W with W stored [K = out features][Cn = in features]).
 template <int LA>
 __global__ __launch_bounds__(512, 4) void gemm_x3t_kernel(GL_DIR_PARAMS, GemmBatch gb) {
-    const int gdir[GEMM_MAX_TASKS] = {d0, d1, d2, d3, d4, d5, d6, d7};
-    constexpr int BT = 128;
-    constexpr int EPB = 8 * 32 * 68 * 4;                         // epilogue patches [32][68] per wave, bytes
-    constexpr int AIMG = LA == LD_ROW ? X3_IMGB : X3T_IMGB;      // bytes per A image
-    constexpr int STB = 3 * AIMG + 3 * X3T_IMGB;                 // six images
-    constexpr int LDSB = EPB > STB ? EPB : STB;
-    __shared__ __attribute__((aligned(16))) float lds[LDSB / 4];
-    unsigned char* const L = reinterpret_cast<unsigned char*>(lds);
-    const unsigned Lb = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)L;
-
-    const int bid = blockIdx.x;
-    int ti = 0;
-#pragma unroll
-    for (int q = 1; q < GEMM_MAX_TASKS; ++q) if (bid >= gdir[q]) ti = q;          // (preloaded directory: first tiles, INT_MAX beyond the last task)
-    const GemmTask& t = gb.t[ti];
-    const float* const pA = t.A; const float* const pB = t.B;
-    const int lda = t.lda, ldb = t.ldb, R = t.R, Cn = t.Cn, K = t.K;
-    const int tiles_c = t.tiles_c, splits = t.splits, kchunk = t.kchunk;
-    const int tiles_r = (R + BT - 1) / BT;
-    const int local = gl_xcd_remap(bid - t.tile_base, t.ntiles);
-    const int per_split = tiles_r * tiles_c;
-    const int split = local / per_split, rem = local - split * per_split;
-    const int tc = rem / tiles_r, tr = rem - tc * tiles_r;
-    const int r0 = tr * BT, c0 = tc * BT;
-    const int kbeg = split * kchunk, kend = min(K, kbeg + kchunk);
-    const int nk = (kend - kbeg + GL_BK - 1) / GL_BK;
-
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int wr = w >> 1, wc = w & 1;
-    const int r32 = lane & 31, hh = lane >> 5, g1 = (lane >> 4) & 1;
-    const bool want_bias = LA == LD_COL && t.epi == EPI_DW && (t.flags & FLAG_BIASGRAD) && tc == 0;
-
-    f32x16 acc[2];
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[b][q] = 0.f;
-    f32x4 rs = {0.f, 0.f, 0.f, 0.f};
-
-    f32x4 ea[2], eb[2];
-    float ear[8];                                               // (row-major A: gemm_x3_kernel's staging registers)
-    if constexpr (LA == LD_ROW) x3_stage_load<LD_ROW>(pA, lda, r0, R, kbeg, kend, ear);
-    else x3t_stage_load(pA, lda, r0, R, kbeg, kend, ea);
-    x3t_stage_load(pB, ldb, c0, Cn, kbeg, kend, eb);
-    if (X3_STAGGER && ((blockIdx.x >> 8) & 1)) __builtin_amdgcn_s_sleep(X3_STAGGER);        // (anti-phase start of a CU's two workgroups: gemm_x3_kernel)
-
-    // transposed-read addresses: k-block h of this lane's k group (k = 8 hh + 4 h within a 16-deep block c; c and the image by immediate offset)
-    const unsigned aA0 = x3t_addr(Lb, 8 * hh, wr * 4 + 2 * g1), aA1 = x3t_addr(Lb, 8 * hh + 4, wr * 4 + 2 * g1);
-    const unsigned aB00 = x3t_addr(Lb + 3 * AIMG, 8 * hh, wc * 8 + 2 * g1), aB01 = x3t_addr(Lb + 3 * AIMG, 8 * hh + 4, wc * 8 + 2 * g1);
-    const unsigned aB10 = x3t_addr(Lb + 3 * AIMG, 8 * hh, wc * 8 + 4 + 2 * g1), aB11 = x3t_addr(Lb + 3 * AIMG, 8 * hh + 4, wc * 8 + 4 + 2 * g1);
-    const unsigned char* const far = L + x3r_off(wr * 32 + r32, hh);                       // row-major A fragments (ds_read_b128; swizzled chunks: x3r_off)
-    const int fsw = x3r_off(r32, 2 + hh) - x3r_off(r32, hh);
-
-    for (int kt = 0; kt < nk; ++kt) {
-        if (want_bias) rs += ea[0] + ea[1];
-        if constexpr (LA == LD_ROW) x3_stage_write<LD_ROW>(L, ear);
-        else x3t_stage_write(L, ea);
-        x3t_stage_write(L + 3 * AIMG, eb);
-        __syncthreads();
-        const int kn = kbeg + GL_BK * (kt + 1);
-        if constexpr (LA == LD_ROW) x3_stage_load<LD_ROW>(pA, lda, r0, R, kn, kend, ear);
-        else x3t_stage_load(pA, lda, r0, R, kn, kend, ea);
-        x3t_stage_load(pB, ldb, c0, Cn, kn, kend, eb);
-#define X3T_BLOCK(C)                                                                                                          \
-        {                                                                                                                     \
-            bf16x8 a[3], b[2][3];                                                                                             \
-            if constexpr (LA == LD_ROW) {                                                                                     \
-                _Pragma("unroll") for (int m = 0; m < 3; ++m) a[m] = *reinterpret_cast<const bf16x8*>(far + m * X3_IMGB + fsw * (C)); \
-            } else {                                                                                                          \
-                a[0] = x3t_frag<(C) * 4096>(aA0, aA1); a[1] = x3t_frag<(C) * 4096 + X3T_IMGB>(aA0, aA1);                       \
-                a[2] = x3t_frag<(C) * 4096 + 2 * X3T_IMGB>(aA0, aA1);                                                         \
-            }                                                                                                                 \
-            b[0][0] = x3t_frag<(C) * 4096>(aB00, aB01); b[0][1] = x3t_frag<(C) * 4096 + X3T_IMGB>(aB00, aB01);                 \
-            b[0][2] = x3t_frag<(C) * 4096 + 2 * X3T_IMGB>(aB00, aB01);                                                        \
-            b[1][0] = x3t_frag<(C) * 4096>(aB10, aB11); b[1][1] = x3t_frag<(C) * 4096 + X3T_IMGB>(aB10, aB11);                 \
-            b[1][2] = x3t_frag<(C) * 4096 + 2 * X3T_IMGB>(aB10, aB11);                                                        \
-            _Pragma("unroll") for (int y = 0; y < 2; ++y) {                                                                   \
-                f32x16 v = acc[y];                                                                                            \
-                v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[y][2], v, 0, 0, 0);                                       \
-                v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[y][0], v, 0, 0, 0);                                       \
-                v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[y][1], v, 0, 0, 0);                                       \
-                v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[y][1], v, 0, 0, 0);                                       \
-                v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[y][0], v, 0, 0, 0);                                       \
-                v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[y][0], v, 0, 0, 0);                                       \
-                acc[y] = v;                                                                                                   \
-            }                                                                                                                 \
-        }
-        X3T_BLOCK(0) X3T_BLOCK(1)
-#undef X3T_BLOCK
-        __syncthreads();
-    }
-
-    // bias gradient = row sums of operand A: this thread holds four rows (4 (tid % 32) ..) over its k slots -> LDS -> fixed-order sum over the 16 slots
-    if (want_bias) {
-        float* part = lds;                                   // [128 rows][16 k slots]
-        const int c4 = (int)(threadIdx.x & 31) * 4, ks = (int)(threadIdx.x >> 5);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) part[(c4 + q) * 16 + ks] = rs[q];
-        __syncthreads();
-        if (threadIdx.x < 128) {
-            const float* q = part + threadIdx.x * 16;
-            float s0 = 0.f;
-#pragma unroll
-            for (int z = 0; z < 16; ++z) s0 += q[z];
-            const int r = r0 + threadIdx.x;
-            if (r < R) { if (splits > 1) t.bslab[(size_t)split * R + r] = s0; else t.out2[r] = s0; }
-        }
-        __syncthreads();
-    }
-
-    // accumulators (32x32 C/D map: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)) -> LDS patch -> row segments
-    float* E = lds + w * (32 * 68);
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) E[((q & 3) + 8 * (q >> 2) + 4 * hh) * 68 + y * 32 + r32] = acc[y][q];
-    const f32x4 bpre = splits > 1 ? (f32x4){0.f, 0.f, 0.f, 0.f} : gl_bias4(t, c0 + wc * 64 + (lane & 15) * 4);      // (this lane's columns: the same in every iteration)
-#pragma unroll 4
-    for (int it = 0; it < 8; ++it) {
-        const int rr = it * 4 + (lane >> 4), cc = (lane & 15) * 4;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(E + rr * 68 + cc);
-        const int r = r0 + wr * 32 + rr, c = c0 + wc * 64 + cc;
-        if (r < R && c < Cn) {
-            if (splits > 1) st4(t.slab + ((size_t)split * R + r) * ((Cn + 3) & ~3) + c, v);
-            else gl_epilogue4(t, r, c, v, &bpre);
-        }
-    }
+    constexpr bool GRP = false; constexpr long long dm = 0;
+#include "gemm_x3t_body.h"
+}
+// group form (group.h): member = blockIdx.y
+template <int LA>
+__global__ __launch_bounds__(512, 4) void gemm_x3t_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride) {
+    constexpr bool GRP = true; const long long dm = (long long)blockIdx.y * mstride;
+#include "gemm_x3t_body.h"
 }
 
 #include "gemm_x3w.h"
@@ -946,191 +628,14 @@ __device__ __forceinline__ unsigned x3s_taddr(unsigned lds_base, int kq, int chu
 
 template <int LA, int LB, int VEC>
 __global__ __launch_bounds__(256, 3) void gemm_x3s_kernel(GL_DIR_PARAMS, GemmBatch gb) {      // (48 KB of LDS: three workgroups per CU)
-    const int gdir[GEMM_MAX_TASKS] = {d0, d1, d2, d3, d4, d5, d6, d7};
-    constexpr int BT = 64;
-    constexpr int AIMG = LA == LD_ROW ? X3S_RIMGB : X3S_TIMGB, BIMG = LB == LD_ROW ? X3S_RIMGB : X3S_TIMGB;
-    constexpr int EPB = 4 * 32 * 36 * 4;                         // epilogue patches [32][36] per wave, bytes
-    constexpr int STB = 3 * AIMG + 3 * BIMG;
-    static_assert(EPB <= STB, "the epilogue patches live in stage 0");
-    // TWO LDS stages (two arrays: the compiler then knows that the fragment reads of one and the staging writes of the other do not alias), ONE
-    // barrier per slice: slice kt is multiplied out of one stage while slice kt + 1 is split into the other.
-    __shared__ __attribute__((aligned(16))) float lds[STB / 4], lds1[STB / 4];
-    unsigned char* const L0 = reinterpret_cast<unsigned char*>(lds);
-    unsigned char* const L1 = reinterpret_cast<unsigned char*>(lds1);
-    const unsigned Lb0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)L0;
-    const unsigned Lb1 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)L1;
-
-    const int bid = blockIdx.x;
-    int ti = 0;
-#pragma unroll
-    for (int q = 1; q < GEMM_MAX_TASKS; ++q) if (bid >= gdir[q]) ti = q;          // (preloaded directory: first tiles, INT_MAX beyond the last task)
-    const GemmTask& t = gb.t[ti];
-    const float* const pA = t.A; const float* const pB = t.B;
-    const int lda = t.lda, ldb = t.ldb, R = t.R, Cn = t.Cn, K = t.K;
-    const int tiles_c = t.tiles_c, splits = t.splits, kchunk = t.kchunk;
-    const int tiles_r = (R + BT - 1) / BT;
-    const int local = gl_xcd_remap(bid - t.tile_base, t.ntiles);
-    const int per_split = tiles_r * tiles_c;
-    const int split = local / per_split, rem = local - split * per_split;
-    const int tc = rem / tiles_r, tr = rem - tc * tiles_r;
-    const int r0 = tr * BT, c0 = tc * BT;
-    const int kbeg = split * kchunk, kend = min(K, kbeg + kchunk);
-    const int nk = (kend - kbeg + GL_BK - 1) / GL_BK;
-
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int wr = w >> 1, wc = w & 1;
-    const int r32 = lane & 31, hh = lane >> 5, g1 = (lane >> 4) & 1;
-    const bool want_bias = LA == LD_COL && t.epi == EPI_DW && (t.flags & FLAG_BIASGRAD) && tc == 0;
-
-    f32x16 acc;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-    f32x4 rs = {0.f, 0.f, 0.f, 0.f};
-
-    // TWO sets of staging registers, loads two slices ahead of their split: set z holds the slices of parity z.  (One set, loaded behind the barrier
-    // and split before the next one, left a load's whole latency in every slice wherever fewer than four workgroups share a CU.)
-    f32x4 ear[2][2], ebr[2][2];
-    f32x4 eac[2][2], ebc[2][2];
-#define X3S_LOAD(Z, KS)                                                                                                       \
-    {                                                                                                                         \
-        const int kz_ = kbeg + GL_BK * (KS);                                                                                  \
-        if constexpr (LA == LD_ROW) x3s_load_row<VEC, 0>(pA, lda, r0, R, kz_, kend, ear[Z]); else x3s_load_col<VEC, 0>(pA, lda, r0, R, kz_, kend, eac[Z]); \
-        if constexpr (LB == LD_ROW) x3s_load_row<VEC, 0>(pB, ldb, c0, Cn, kz_, kend, ebr[Z]); else x3s_load_col<VEC, 0>(pB, ldb, c0, Cn, kz_, kend, ebc[Z]); \
-    }
-    // what depends on the loaded values (K tail / edge zero fill, unaligned shift), then split set Z = slice KS into the stage at LW
-#define X3S_SPLIT(Z, KS, LW)                                                                                                  \
-    {                                                                                                                         \
-        const int kz_ = kbeg + GL_BK * (KS);                                                                                  \
-        if constexpr (LA == LD_ROW) x3s_load_row<VEC, 1>(pA, lda, r0, R, kz_, kend, ear[Z]); else x3s_load_col<VEC, 1>(pA, lda, r0, R, kz_, kend, eac[Z]); \
-        if constexpr (LB == LD_ROW) x3s_load_row<VEC, 1>(pB, ldb, c0, Cn, kz_, kend, ebr[Z]); else x3s_load_col<VEC, 1>(pB, ldb, c0, Cn, kz_, kend, ebc[Z]); \
-        if (want_bias) rs += eac[Z][0] + eac[Z][1];                                                                           \
-        if constexpr (LA == LD_ROW) x3s_write_row(LW, ear[Z]); else x3s_write_col(LW, eac[Z]);                                \
-        if constexpr (LB == LD_ROW) x3s_write_row((LW) + 3 * AIMG, ebr[Z]); else x3s_write_col((LW) + 3 * AIMG, ebc[Z]);      \
-    }
-    X3S_LOAD(0, 0) X3S_LOAD(1, 1)
-    X3S_SPLIT(0, 0, L0)
-    X3S_LOAD(0, 2)
-
-    const int foA = x3r_off(wr * 32 + r32, hh), foB = 3 * AIMG + x3r_off(wc * 32 + r32, hh);
-    const int fsw = x3r_off(r32, 2 + hh) - x3r_off(r32, hh);            // block 1 relative to block 0 (swizzled chunks)
-    const unsigned tA0 = x3s_taddr(0, 8 * hh, wr * 4 + 2 * g1), tA1 = x3s_taddr(0, 8 * hh + 4, wr * 4 + 2 * g1);
-    const unsigned tB0 = x3s_taddr(3 * AIMG, 8 * hh, wc * 4 + 2 * g1), tB1 = x3s_taddr(3 * AIMG, 8 * hh + 4, wc * 4 + 2 * g1);
-
-#define X3S_BLOCK(C, LR, LBR)                                                                                                 \
-        {                                                                                                                     \
-            bf16x8 a[3], b[3];                                                                                                \
-            if constexpr (LA == LD_ROW) {                                                                                     \
-                _Pragma("unroll") for (int m = 0; m < 3; ++m) a[m] = *reinterpret_cast<const bf16x8*>((LR) + foA + m * X3S_RIMGB + fsw * (C)); \
-            } else {                                                                                                          \
-                a[0] = x3t_frag<(C) * 2048>((LBR) + tA0, (LBR) + tA1); a[1] = x3t_frag<(C) * 2048 + X3S_TIMGB>((LBR) + tA0, (LBR) + tA1); \
-                a[2] = x3t_frag<(C) * 2048 + 2 * X3S_TIMGB>((LBR) + tA0, (LBR) + tA1);                                         \
-            }                                                                                                                 \
-            if constexpr (LB == LD_ROW) {                                                                                     \
-                _Pragma("unroll") for (int m = 0; m < 3; ++m) b[m] = *reinterpret_cast<const bf16x8*>((LR) + foB + m * X3S_RIMGB + fsw * (C)); \
-            } else {                                                                                                          \
-                b[0] = x3t_frag<(C) * 2048>((LBR) + tB0, (LBR) + tB1); b[1] = x3t_frag<(C) * 2048 + X3S_TIMGB>((LBR) + tB0, (LBR) + tB1); \
-                b[2] = x3t_frag<(C) * 2048 + 2 * X3S_TIMGB>((LBR) + tB0, (LBR) + tB1);                                         \
-            }                                                                                                                 \
-            f32x16 v = acc;                                                                                                   \
-            v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], v, 0, 0, 0);                                              \
-            v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], v, 0, 0, 0);                                              \
-            v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], v, 0, 0, 0);                                              \
-            v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], v, 0, 0, 0);                                              \
-            v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], v, 0, 0, 0);                                              \
-            v = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], v, 0, 0, 0);                                              \
-            acc = v;                                                                                                          \
-        }
-    // one slice: multiply slice KT out of the stage LR while set Z (slice KT + 1) is split into LW and refilled with slice KT + 3
-#define X3S_ITER(Z, KT, LR, LBR, LW)                                                                                          \
-    {                                                                                                                         \
-        __syncthreads();                                                                                                      \
-        X3S_SPLIT(Z, (KT) + 1, LW)                                                                                            \
-        X3S_LOAD(Z, (KT) + 3)                                                                                                 \
-        X3S_BLOCK(0, LR, LBR) X3S_BLOCK(1, LR, LBR)                                                                           \
-    }
-    // (ONE basic block per pair of slices: with a branch between the two the compiler's wait-count pass waited with vmcnt(0) in the second -- for the
-    // loads the first had just issued.  A slice past the end of an odd chunk multiplies the zeros its own K-tail fill produces.)
-    for (int kt = 0; kt < nk; kt += 2) {
-        X3S_ITER(1, kt, L0, Lb0, L1)
-        X3S_ITER(0, kt + 1, L1, Lb1, L0)
-    }
-#undef X3S_ITER
-#undef X3S_BLOCK
-#undef X3S_SPLIT
-#undef X3S_LOAD
-    __syncthreads();                                             // (the epilogue's patches and the bias sums reuse stage 0)
-
-    // split-K without a finishing launch (FLAG_FIN_INLINE): every split workgroup writes its partial tile THROUGH to memory (the XCDs' L2s are
-    // not coherent with each other inside a launch), takes a ticket on the tile's counter, and the LAST one to arrive sums the slabs IN SPLIT ORDER
-    // (its own included, from memory: the arithmetic of gemm_lds_fin_kernel, bit for bit) and runs the epilogue.  The counters sit behind the
-    // task's slabs, zero between launches (the last arrival resets its own).
-    const bool inl = splits > 1 && (t.flags & FLAG_FIN_INLINE);
-    const int C4p = (Cn + 3) & ~3;
-    if (want_bias) {       // row sums of the k-major A: this thread holds rows 4 (tid % 16) .. over its 16 k slots
-        float* part = lds;                                   // [64 rows][16 k slots]
-        const int c4 = (int)(threadIdx.x & 15) * 4, ks = (int)(threadIdx.x >> 4);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) part[(c4 + q) * 16 + ks] = rs[q];
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            const float* q = part + threadIdx.x * 16;
-            float s0 = 0.f;
-#pragma unroll
-            for (int z = 0; z < 16; ++z) s0 += q[z];
-            const int r = r0 + threadIdx.x;
-            if (r < R) { if (inl) dp_store1(t.bslab + (size_t)split * R + r, s0); else if (splits > 1) t.bslab[(size_t)split * R + r] = s0; else t.out2[r] = s0; }
-        }
-        __syncthreads();
-    }
-
-    // accumulator (32x32 C/D map: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)) -> LDS patch -> row segments
-    float* E = lds + w * (32 * 36);
-#pragma unroll
-    for (int q = 0; q < 16; ++q) E[((q & 3) + 8 * (q >> 2) + 4 * hh) * 36 + r32] = acc[q];
-    const f32x4 bpre = splits > 1 ? (f32x4){0.f, 0.f, 0.f, 0.f} : gl_bias4(t, c0 + wc * 32 + (lane & 7) * 4);       // (this lane's columns: the same in every iteration)
-#pragma unroll 4
-    for (int it = 0; it < 4; ++it) {
-        const int rr = it * 8 + (lane >> 3), cc = (lane & 7) * 4;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(E + rr * 36 + cc);
-        const int r = r0 + wr * 32 + rr, c = c0 + wc * 32 + cc;
-        if (r < R && c < Cn) {
-            if (inl) dp_store4(t.slab + ((size_t)split * R + r) * C4p + c, v);
-            else if (splits > 1) st4(t.slab + ((size_t)split * R + r) * C4p + c, v);
-            else gl_epilogue4(t, r, c, v, &bpre);
-        }
-    }
-    if (!inl) return;
-    __builtin_amdgcn_s_waitcnt(0x0F70);                          // vmcnt(0): this thread's write-through stores have reached memory
-    __syncthreads();
-    int* const tick = reinterpret_cast<int*>(t.slab + (size_t)splits * R * C4p) + rem;
-    if (threadIdx.x == 0) {
-        const int old = atomicAdd(tick, 1);
-        const int last = old == splits - 1;
-        if (last) atomicExch(tick, 0);
-        reinterpret_cast<volatile int*>(lds)[0] = last;          // (stage 0 is free: the patches above were consumed before the barrier)
-    }
-    __syncthreads();
-    if (reinterpret_cast<volatile int*>(lds)[0] == 0) return;
-#pragma unroll 2
-    for (int it = 0; it < 4; ++it) {
-        const int rr = it * 8 + (lane >> 3), cc = (lane & 7) * 4;
-        const int r = r0 + wr * 32 + rr, c = c0 + wc * 32 + cc;
-        if (r < R && c < Cn) {
-            const float* p = t.slab + (size_t)r * C4p + c;
-            const size_t stride = (size_t)R * C4p;
-            f32x4 v = dp_load4(p);
-            for (int s = 1; s < splits; ++s) v += dp_load4(p + s * stride);
-            gl_epilogue4(t, r, c, v);
-        }
-    }
-    if (want_bias && threadIdx.x < 64) {
-        const int r = r0 + threadIdx.x;
-        if (r < R) {
-            float s0 = dp_load1(t.bslab + r);
-            for (int q = 1; q < splits; ++q) s0 += dp_load1(t.bslab + (size_t)q * R + r);
-            t.out2[r] = s0;
-        }
-    }
+    constexpr bool GRP = false; constexpr long long dm = 0;
+#include "gemm_x3s_body.h"
+}
+// group form (group.h): member = blockIdx.y
+template <int LA, int LB, int VEC>
+__global__ __launch_bounds__(256, 3) void gemm_x3s_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride) {
+    constexpr bool GRP = true; const long long dm = (long long)blockIdx.y * mstride;
+#include "gemm_x3s_body.h"
 }
 
 #include "gemm_x3q.h"
@@ -1138,22 +643,30 @@ __global__ __launch_bounds__(256, 3) void gemm_x3s_kernel(GL_DIR_PARAMS, GemmBat
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+// a launch of kernel KN<TA...> with nt threads: its group form when a group is active (rl_grp_active), grid (x, members).  (Member r's blocks
+// follow member r - 1's in dispatch order, so the XCD that gl_xcd_remap deals a tile to is shifted by r * gridDim.x: same tiles, another XCD.)
+#define GL_LAUNCH(KN, TA, g, nt, st, ...) do { \
+        const RlGrp* gr_ = rl_grp_active(); \
+        if (gr_) hipLaunchKernelGGL((KN##_grp<RL_UNPAREN TA>), dim3((g).x, gr_->members), dim3(nt), 0, st, __VA_ARGS__, gr_->stride); \
+        else hipLaunchKernelGGL((KN<RL_UNPAREN TA>), g, dim3(nt), 0, st, __VA_ARGS__); \
+    } while (0)
+
 template <int BT>
 static int launch_bt(int la, int lb, dim3 g, hipStream_t st, const GemmBatch& gb, const int* dir) {
-    if (la == LD_ROW && lb == LD_ROW) hipLaunchKernelGGL((gemm_lds_kernel<BT, LD_ROW, LD_ROW>), g, dim3(256), 0, st, GL_DIR_ARGS(dir), gb);
-    else if (la == LD_ROW && lb == LD_COL) hipLaunchKernelGGL((gemm_lds_kernel<BT, LD_ROW, LD_COL>), g, dim3(256), 0, st, GL_DIR_ARGS(dir), gb);
-    else if (la == LD_COL && lb == LD_COL) hipLaunchKernelGGL((gemm_lds_kernel<BT, LD_COL, LD_COL>), g, dim3(256), 0, st, GL_DIR_ARGS(dir), gb);
+    if (la == LD_ROW && lb == LD_ROW) GL_LAUNCH(gemm_lds_kernel, (BT, LD_ROW, LD_ROW), g, 256, st, GL_DIR_ARGS(dir), gb);
+    else if (la == LD_ROW && lb == LD_COL) GL_LAUNCH(gemm_lds_kernel, (BT, LD_ROW, LD_COL), g, 256, st, GL_DIR_ARGS(dir), gb);
+    else if (la == LD_COL && lb == LD_COL) GL_LAUNCH(gemm_lds_kernel, (BT, LD_COL, LD_COL), g, 256, st, GL_DIR_ARGS(dir), gb);
     else return -1;
     return (int)hipGetLastError();
 }
 
 static int launch_x3(int la, int lb, dim3 g, hipStream_t st, const GemmBatch& gb, const int* dir) {
-    if (la == LD_ROW && lb == LD_ROW) hipLaunchKernelGGL((gemm_x3_kernel<LD_ROW, LD_ROW>), g, dim3(512), 0, st, GL_DIR_ARGS(dir), gb);
+    if (la == LD_ROW && lb == LD_ROW) GL_LAUNCH(gemm_x3_kernel, (LD_ROW, LD_ROW), g, 512, st, GL_DIR_ARGS(dir), gb);
     // dX form: the k-major B operand through the transposed LDS reads; its 16-byte loads along the rows need Cn % 4 == 0 and an aligned B -- which the
     // routing guarantees for every task of the 128-wide bf16x3 tile
-    else if (la == LD_ROW && lb == LD_COL) hipLaunchKernelGGL((gemm_x3t_kernel<LD_ROW>), g, dim3(512), 0, st, GL_DIR_ARGS(dir), gb);
+    else if (la == LD_ROW && lb == LD_COL) GL_LAUNCH(gemm_x3t_kernel, (LD_ROW), g, 512, st, GL_DIR_ARGS(dir), gb);
     // weight-gradient form: both operands staged as they lie in memory
-    else if (la == LD_COL && lb == LD_COL) hipLaunchKernelGGL((gemm_x3t_kernel<LD_COL>), g, dim3(512), 0, st, GL_DIR_ARGS(dir), gb);
+    else if (la == LD_COL && lb == LD_COL) GL_LAUNCH(gemm_x3t_kernel, (LD_COL), g, 512, st, GL_DIR_ARGS(dir), gb);
     else return -1;
     return (int)hipGetLastError();
 }
@@ -1183,15 +696,15 @@ static int launch_x3s(int la, int lb, dim3 g, hipStream_t st, const GemmBatch& g
     bool unal = false;
     for (int q = 0; q < gb.ntasks; ++q) if (gb.t[q].flags & (FLAG_SCALAR_A | FLAG_SCALAR_B)) { unal = true; if (!x3s_unaligned_ok(&gb.t[q])) return -2; }
     if (unal) {
-        if (la == LD_ROW && lb == LD_ROW) hipLaunchKernelGGL((gemm_x3s_kernel<LD_ROW, LD_ROW, 2>), g, dim3(256), 0, st, GL_DIR_ARGS(dir), gb);
-        else if (la == LD_ROW && lb == LD_COL) hipLaunchKernelGGL((gemm_x3s_kernel<LD_ROW, LD_COL, 2>), g, dim3(256), 0, st, GL_DIR_ARGS(dir), gb);
-        else if (la == LD_COL && lb == LD_COL) hipLaunchKernelGGL((gemm_x3s_kernel<LD_COL, LD_COL, 2>), g, dim3(256), 0, st, GL_DIR_ARGS(dir), gb);
+        if (la == LD_ROW && lb == LD_ROW) GL_LAUNCH(gemm_x3s_kernel, (LD_ROW, LD_ROW, 2), g, 256, st, GL_DIR_ARGS(dir), gb);
+        else if (la == LD_ROW && lb == LD_COL) GL_LAUNCH(gemm_x3s_kernel, (LD_ROW, LD_COL, 2), g, 256, st, GL_DIR_ARGS(dir), gb);
+        else if (la == LD_COL && lb == LD_COL) GL_LAUNCH(gemm_x3s_kernel, (LD_COL, LD_COL, 2), g, 256, st, GL_DIR_ARGS(dir), gb);
         else return -1;
         return (int)hipGetLastError();
     }
-    if (la == LD_ROW && lb == LD_ROW) hipLaunchKernelGGL((gemm_x3s_kernel<LD_ROW, LD_ROW, 1>), g, dim3(256), 0, st, GL_DIR_ARGS(dir), gb);
-    else if (la == LD_ROW && lb == LD_COL) hipLaunchKernelGGL((gemm_x3s_kernel<LD_ROW, LD_COL, 1>), g, dim3(256), 0, st, GL_DIR_ARGS(dir), gb);
-    else if (la == LD_COL && lb == LD_COL) hipLaunchKernelGGL((gemm_x3s_kernel<LD_COL, LD_COL, 1>), g, dim3(256), 0, st, GL_DIR_ARGS(dir), gb);
+    if (la == LD_ROW && lb == LD_ROW) GL_LAUNCH(gemm_x3s_kernel, (LD_ROW, LD_ROW, 1), g, 256, st, GL_DIR_ARGS(dir), gb);
+    else if (la == LD_ROW && lb == LD_COL) GL_LAUNCH(gemm_x3s_kernel, (LD_ROW, LD_COL, 1), g, 256, st, GL_DIR_ARGS(dir), gb);
+    else if (la == LD_COL && lb == LD_COL) GL_LAUNCH(gemm_x3s_kernel, (LD_COL, LD_COL, 1), g, 256, st, GL_DIR_ARGS(dir), gb);
     else return -1;
     return (int)hipGetLastError();
 }
@@ -1202,8 +715,8 @@ static int launch_x3q(int la, int lb, dim3 g, hipStream_t st, const GemmBatch& g
         const GemmTask& t = gb.t[q];
         if ((t.flags & (FLAG_SCALAR_A | FLAG_SCALAR_B)) || (t.K & 15) || t.K < 32 || t.splits != 1 || (lb == LD_COL && ((t.Cn & 7) || t.Cn < 8))) return -2;
     }
-    if (lb == LD_ROW) hipLaunchKernelGGL((gemm_x3q_kernel<LD_ROW>), g, dim3(256), 0, st, GL_DIR_ARGS(dir), gb);
-    else if (lb == LD_COL) hipLaunchKernelGGL((gemm_x3q_kernel<LD_COL>), g, dim3(256), 0, st, GL_DIR_ARGS(dir), gb);
+    if (lb == LD_ROW) GL_LAUNCH(gemm_x3q_kernel, (LD_ROW), g, 256, st, GL_DIR_ARGS(dir), gb);
+    else if (lb == LD_COL) GL_LAUNCH(gemm_x3q_kernel, (LD_COL), g, 256, st, GL_DIR_ARGS(dir), gb);
     else return -1;
     return (int)hipGetLastError();
 }
@@ -1211,7 +724,8 @@ static int launch_x3q(int la, int lb, dim3 g, hipStream_t st, const GemmBatch& g
 // bt: 64 / 128 = fp32-MFMA tiles; 129 = the 128-wide tile on the bf16 pipe (bf16x3); 65 = the 64-wide tile on the bf16 pipe; 257 = the 256 x 128 tile on the
 // bf16 pipe (persistent workgroups: gemm_x3w.h); 33 = the 32 x 32 tile on the bf16 pipe whose four waves split K (gemm_x3q.h)
 extern "C" int rl_launch_gemm_lds(int bt, int la, int lb, const GemmBatch* gb, int total_tiles, int fin_blocks, hipStream_t st) {
-    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
+    const RlGrp* gr = rl_grp_active();
+    if (gr && bt == 257) return RL_GRP_UNSUPPORTED;          // (the persistent tile walks its tiles by grid stride: no group form)
     if (total_tiles <= 0) return 0;
     int dir[GEMM_MAX_TASKS], fdir[GEMM_MAX_TASKS];
     for (int q = 0; q < GEMM_MAX_TASKS; ++q) {
@@ -1223,7 +737,8 @@ extern "C" int rl_launch_gemm_lds(int bt, int la, int lb, const GemmBatch* gb, i
            : bt == 128 ? launch_bt<128>(la, lb, dim3(total_tiles), st, *gb, dir) : launch_bt<64>(la, lb, dim3(total_tiles), st, *gb, dir);
     if (rc != 0) return rc;
     if (fin_blocks > 0) {
-        hipLaunchKernelGGL(gemm_lds_fin_kernel, dim3(fin_blocks), dim3(256), 0, st, GL_DIR_ARGS(fdir), *gb);
+        if (gr) hipLaunchKernelGGL(gemm_lds_fin_kernel_grp, dim3(fin_blocks, gr->members), dim3(256), 0, st, GL_DIR_ARGS(fdir), *gb, gr->stride);
+        else hipLaunchKernelGGL(gemm_lds_fin_kernel, dim3(fin_blocks), dim3(256), 0, st, GL_DIR_ARGS(fdir), *gb);
         ++g_rl_launches;              // split-K: the stage is two kernels
         rc = (int)hipGetLastError();
     }

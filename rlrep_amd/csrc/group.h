@@ -5,6 +5,8 @@
 // what SACAgent(seed = s_r) computes.  No member reads another member's words.
 //
 // The group forms are SEPARATE kernels (`*_grp_kernel`) around the same device bodies: the kernels the single agents launch are untouched.
+// The large bodies (`*_body.h`) are #included into both kernels rather than called: moved into a forceinline function, the gemm_lds
+// kernels' instruction schedules changed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "common.h"
@@ -27,6 +29,12 @@ extern "C" const RlGrp* rl_grp_active();
 
 #ifdef __HIPCC__
 template <class T> __device__ __forceinline__ void rl_rb(T*& p, long long d) { if (p) p = (T*)((uintptr_t)p + (uintptr_t)d); }
+// p moved by d bytes in a group form (GRP), p itself in the single-agent kernel: for bodies that read a pointer from a record left in the
+// kernel-argument segment, at the place they load it (no local copy of the record: no scratch)
+template <bool GRP, class T> __device__ __forceinline__ T* rl_mv(T* p, long long d) {
+    if constexpr (GRP) return (T*)((uintptr_t)p + (uintptr_t)d);
+    else { (void)d; return p; }
+}
 __device__ __forceinline__ void rl_rebase(GemmTask& t, long long d) {
     rl_rb(t.A, d); rl_rb(t.B, d); rl_rb(t.C, d); rl_rb(t.bias, d); rl_rb(t.aux, d); rl_rb(t.r1u, d); rl_rb(t.r1v, d);
     rl_rb(t.gidx, d); rl_rb(t.out2, d);
@@ -59,6 +67,10 @@ __device__ __forceinline__ void rl_rebase(QHeadCritic& p, long long d) {
         rl_rb(p.Et[h], d); rl_rb(p.Ec[h], d); rl_rb(p.wt[h], d); rl_rb(p.bt[h], d); rl_rb(p.wc[h], d); rl_rb(p.bc[h], d); rl_rb(p.GE[h], d);
     }
     rl_rb(p.logp, d); rl_rb(p.R, d); rl_rb(p.D, d); rl_rb(p.alpha_state, d); rl_rb(p.dq, d); rl_rb(p.partial, d); rl_rb(p.step, d);
+}
+__device__ __forceinline__ void rl_rebase(InfoNce& p, long long d) {
+    rl_rb(p.S, d); rl_rb(p.rhat, d); rl_rb(p.r, d); rl_rb(p.drhat, d); rl_rb(p.partial, d); rl_rb(p.step, d);
+    rl_rb(p.Z, d); rl_rb(p.theta_w, d); rl_rb(p.theta_b, d); rl_rb(p.ZM, d);
 }
 __device__ __forceinline__ void rl_rebase(QHeadActor& p, long long d) {
 #pragma unroll

@@ -24,6 +24,7 @@
 extern long long g_rl_launches;
 #include "kparams.h"
 #include "x3.h"
+#include "group.h"
 
 #define NC_NF 5          // N / 4 accumulator fragments per batch-row group (N = 20)
 
@@ -1691,6 +1692,7 @@ extern "C" void rl_nc_fwd_plan(const NcFwdTask* tasks, int ntasks, int* engine, 
     *g2 = ((long long)ntasks * ((B + 3) / 4) * ((H + 63) / 64) <= 2048) ? 1 : 2;
 }
 extern "C" int rl_launch_nc_fwd(const NcFwdBatch* nb, int total_tiles, int g2, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;          // (no group form: a seed group never runs member 0 alone)
     if (total_tiles <= 0) return 0;
     for (int q = 0; q < nb->ntasks; ++q) if (nb->t[q].N != 4 * NC_NF) return -2;      // the row mapping is built for N = 20
     const int F = nb->t[0].F, N = nb->t[0].N;
@@ -1732,6 +1734,7 @@ extern "C" int rl_nc_dx_engine(const NcDxTask* t) {
     return 1;
 }
 extern "C" int rl_launch_nc_dx(const NcDxTask* t, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;          // (no group form: a seed group never runs member 0 alone)
     if (t->ntiles <= 0) return 0;
     if (t->N != 4 * NC_NF) return -2;
     // 16-byte loads of U / GH rows need 4-float-aligned rows in every head
@@ -1772,6 +1775,7 @@ extern "C" int rl_nc_dw_splits(int B, int F, int H, int ntasks) {
     return sp > maxsp ? (maxsp < 1 ? 1 : maxsp) : sp;
 }
 extern "C" int rl_launch_nc_dw(const NcDwBatch* nb, int total_tiles, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;          // (no group form: a seed group never runs member 0 alone)
     if (total_tiles <= 0) return 0;
     for (int q = 0; q < nb->ntasks; ++q) if (nb->t[q].N != 4 * NC_NF || nb->t[q].B <= 0) return -2;
     if (nb->engine == 1) {

@@ -3,6 +3,7 @@
 // deterministic per-block partial sums, gradients written in the layout the backward GEMMs consume.
 #include "common.h"
 #include "kparams.h"
+#include "group.h"
 
 // ------------------------------------------------------------------------------------------------
 // ctrlsac InfoNCE (agent/ctrlsac/ctrlsac_agent.py:226-233)
@@ -10,44 +11,13 @@
 //   dS = (softmax_row(S) - I)/B  (in place),  drhat = (rhat - r)/B
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void infonce_kernel(InfoNce p) {
-    __shared__ float shp[4][2];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    float accm = 0.f, accr = 0.f;
-    for (int i = blockIdx.x * 4 + w; i < p.B; i += gridDim.x * 4) {
-        float* row = p.S + (size_t)i * p.ldS;
-        float mx = -INFINITY;
-        const int NC = p.ncols, di = p.diag_off + i;
-        for (int j = lane; j < NC; j += 64) mx = fmaxf(mx, row[j]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-        float se = 0.f;
-        for (int j = lane; j < NC; j += 64) se += expf(row[j] - mx);
-        se = wave_sum(se);
-        const float lse = mx + logf(se);
-        const float sii = row[di];
-        for (int j = lane; j < NC; j += 64) {
-            const float sm = expf(row[j] - lse);
-            row[j] = (sm - (j == di ? 1.f : 0.f)) * p.inv_batch;
-        }
-        float rh;
-        if (p.Z) {
-            const float* z = p.Z + (size_t)i * p.ldZ;
-            float s = 0.f;
-            for (int f = lane; f < p.F; f += 64) s = fmaf(z[f], p.theta_w[f], s);
-            rh = wave_sum(s) + p.theta_b[0];
-        } else rh = p.rhat[i];
-        const float dr = rh - p.r[i];
-        if (lane == 0) p.drhat[i] = dr * p.inv_batch;
-        accm += lse - sii;
-        accr += dr * dr;
-    }
-    if (lane == 0) { shp[w][0] = accm; shp[w][1] = accr; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        p.partial[2 * blockIdx.x] = ((shp[0][0] + shp[1][0]) + shp[2][0]) + shp[3][0];
-        p.partial[2 * blockIdx.x + 1] = ((shp[0][1] + shp[1][1]) + shp[2][1]) + shp[3][1];
-        if (blockIdx.x == 0 && p.step) bump_group(p.step);
-    }
+#include "infonce_body.h"
+}
+// group form (group.h): member = blockIdx.y, every pointer of the record moved by member * stride
+__global__ __launch_bounds__(256) void infonce_kernel_grp(InfoNce p0, long long mstride) {
+    InfoNce p = p0;
+    rl_rebase(p, (long long)blockIdx.y * mstride);
+#include "infonce_body.h"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -594,6 +564,16 @@ __global__ __launch_bounds__(256) void copy2_kernel(const float* __restrict__ sr
         if (d2) d2[i] = v;
     }
 }
+// group form (group.h): member = blockIdx.y; the three arrays moved by member * stride (d2 stays null where it is null)
+__global__ __launch_bounds__(256) void copy2_kernel_grp(const float* src, float* d1, float* d2, long long n, long long mstride) {
+    const long long dm = (long long)blockIdx.y * mstride;
+    rl_rb(src, dm); rl_rb(d1, dm); rl_rb(d2, dm);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const float v = src[i];
+        d1[i] = v;
+        if (d2) d2[i] = v;
+    }
+}
 
 // ------------------------------------------------------------------------------------------------
 // diffsrsac ELU-layer regulariser statistics (RegStats).  Blocks [0, 4 nbc): 1024 elements of one Gram matrix each; blocks
@@ -628,6 +608,7 @@ __global__ __launch_bounds__(256) void reg_stats_kernel(RegStats p) {
     if (threadIdx.x == 0) p.partial[bid] = p.lambda * r;
 }
 extern "C" int rl_launch_reg_stats(const RegStats* p, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     hipLaunchKernelGGL(reg_stats_kernel, dim3(4 * (p->nbc + p->nbr)), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
@@ -636,16 +617,20 @@ extern "C" int rl_launch_reg_stats(const RegStats* p, hipStream_t st) {
 static inline int rows_blocks(int B) { int g = (B + 3) / 4; return g > 128 ? 128 : g; }
 
 extern "C" int rl_launch_infonce(const InfoNce* p, hipStream_t st) {
-    if (p->ZM) {          // score matrix + loss + gradient in one launch (score_infonce_kernel): 16 whole rows per workgroup
+    const RlGrp* gr = rl_grp_active();
+    if (p->ZM) {
+        if (gr) return RL_GRP_UNSUPPORTED;             // (the opt-in score_infonce_kernel has no group form)          // score matrix + loss + gradient in one launch (score_infonce_kernel): 16 whole rows per workgroup
         if (!p->Z || (p->F & 63) || (p->ldZ & 3) || (p->ldZM & 3) || ((((uintptr_t)p->Z) | ((uintptr_t)p->ZM) | ((uintptr_t)p->theta_w)) & 15) || p->ncols > 64 * SI_MAX_TILES ||
             p->nblk != (p->B + 15) / 16) return -7;
         hipLaunchKernelGGL(score_infonce_kernel, dim3(p->nblk), dim3(256), 0, st, *p);
         return (int)hipGetLastError();
     }
-    hipLaunchKernelGGL(infonce_kernel, dim3(p->nblk), dim3(256), 0, st, *p);
+    if (gr) hipLaunchKernelGGL(infonce_kernel_grp, dim3(p->nblk, gr->members), dim3(256), 0, st, *p, gr->stride);
+    else hipLaunchKernelGGL(infonce_kernel, dim3(p->nblk), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_colsum(const ColSum* p, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     ColSum q = *p;
     q.dp.nblocks = (p->F + 15) / 16;                   // the first set's blocks take the ticket (dp_slots_publish)
     if (q.dp.world > 1 && (q.dp.n < p->F || !q.dp.slot[q.dp.rank])) return -7;
@@ -653,16 +638,19 @@ extern "C" int rl_launch_colsum(const ColSum* p, hipStream_t st) {
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_speder_rows(const SpederRows* p, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     hipLaunchKernelGGL(speder_rows_kernel, dim3(p->nblk), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_speder_grads(const SpederGrads* p, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     long long n = (long long)p->B * p->F;
     int g = (int)((n + 1023) / 1024); if (g > 2048) g = 2048; if (g < 1) g = 1;
     hipLaunchKernelGGL(speder_grads_kernel, dim3(g), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_diffsr_perturb(const DiffsrPerturb* p, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     long long n = (long long)p->B * (p->S + 1);
     int g = (int)((n + 255) / 256); if (g > 2048) g = 2048; if (g < 1) g = 1;
     hipLaunchKernelGGL(diffsr_perturb_kernel, dim3(g), dim3(256), 0, st, *p);
@@ -676,6 +664,7 @@ extern "C" int rl_replearn_init() {
     return (int)e;
 }
 extern "C" int rl_launch_diffsr_score(const DiffsrScore* p, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
     // one pass through LDS where it applies; column chunks of 64 floats (64 KB of LDS at F = 256: two workgroups per CU, whose load and store
     // phases overlap) measured best at Humanoid dims: 380 us against 393 (32), 514 (128: one workgroup per CU) and 462 for the two-pass kernel.
     // RLREP_ENABLE=score_ch=32 / 64 / 128 selects the chunk, 0 the two-pass kernels.
@@ -699,6 +688,7 @@ extern "C" int rl_launch_diffsr_score(const DiffsrScore* p, hipStream_t st) {
 }
 extern "C" int rl_launch_copy2(const float* src, float* d1, float* d2, long long n, hipStream_t st) {
     int g = (int)((n + 1023) / 1024); if (g > 2048) g = 2048; if (g < 1) g = 1;
-    hipLaunchKernelGGL(copy2_kernel, dim3(g), dim3(256), 0, st, src, d1, d2, n);
+    if (const RlGrp* gr = rl_grp_active()) hipLaunchKernelGGL(copy2_kernel_grp, dim3(g, gr->members), dim3(256), 0, st, src, d1, d2, n, gr->stride);
+    else hipLaunchKernelGGL(copy2_kernel, dim3(g), dim3(256), 0, st, src, d1, d2, n);
     return (int)hipGetLastError();
 }

@@ -12,6 +12,7 @@
 #include "common.h"
 #include "kparams.h"
 #include "rowprog.h"
+#include "group.h"
 
 #define RP_MAX_OPS 40
 #define RP_OP_WORDS ((int)(sizeof(RpOp) / 4))
@@ -638,6 +639,7 @@ extern "C" int rl_rowprog_init() {
 }
 
 extern "C" int rl_launch_rowprog(const RpLaunch* L, int total_blocks, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;          // (no group form: a seed group never runs member 0 alone)
     if (total_blocks <= 0) return 0;
     if ((size_t)L->lds_floats * 4 > RP_LDS_DYN_MAX) return -2;
     hipLaunchKernelGGL(rowprog_kernel, dim3(total_blocks), dim3(RP_THREADS), (size_t)L->lds_floats * 4, st, *L);

@@ -23,6 +23,7 @@
 #include "kparams.h"
 #include "gemm16_tile.h"
 #include "heads_vae_tile.h"
+#include "group.h"
 
 #define XC_SPIN_LIMIT (1 << 18)
 
@@ -180,6 +181,7 @@ __global__ __launch_bounds__(256) void xchain_kernel(XcLaunch L) {
 }
 
 extern "C" int rl_launch_xchain(const XcLaunch* L, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;          // (no group form: a seed group never runs member 0 alone)
     if (L->nph <= 0) return 0;
     if (L->mpg < 1 || L->mpg > XC_FLAG_STRIDE) return -1;
     hipLaunchKernelGGL(xchain_kernel, dim3(XC_GROUPS * L->mpg), dim3(256), 0, st, *L);

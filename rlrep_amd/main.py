@@ -7,8 +7,9 @@ Same flags, same per-algorithm constructor overrides (main.py:81-104), same loop
 environment step, evaluation every `eval_freq` steps).  Metrics go to `log/<env>/<alg>/<dir>/<seed>/metrics.jsonl`
 as {"step": t, "info/<key>": value} lines (and to tensorboardX with the reference's tags if it is installed).
 
-`--seeds 0,1,2,3` (sac only): one SACSeedBatch trains every seed in the same launches, one environment per seed stepped in lockstep;
-each seed has its own np.random.RandomState(seed) for random and epsilon-greedy actions, its own evaluation and its own log directory.
+`--seeds 0,1,2,3` (sac and ctrlsac): one SACSeedBatch / CTRLSACSeedBatch trains every seed in the same launches, one environment per seed
+stepped in lockstep; each seed has its own np.random.RandomState(seed) for random and epsilon-greedy actions, its own evaluation and its own
+log directory.  ctrlsac takes the dimensions build_agent gives it (main.py:90-91).
 """
 import argparse
 import json
@@ -67,7 +68,7 @@ def run(argv=None):
     p.add_argument('--extra_feature_steps', default=3, type=int)
     p.add_argument('--eval_episodes', default=10, type=int)
     p.add_argument('--log_root', default='log')
-    p.add_argument('--seeds', default=None, help='comma-separated seeds trained together (sac only): rlrep_amd/agent/sac/seed_batch.py')
+    p.add_argument('--seeds', default=None, help='comma-separated seeds trained together (sac and ctrlsac only): rlrep_amd/agent/seed_batch.py')
     args = p.parse_args(argv)
     if args.seeds is not None:
         return run_seeds(args)
@@ -149,11 +150,10 @@ class _MemberPolicy(object):
 def run_seeds(args):
     """The loop of run() for several seeds at once: R environments in lockstep, one SACSeedBatch, one ReplayBufferGroup."""
     seeds = [int(s) for s in str(args.seeds).split(',') if s.strip() != '']
-    if args.alg != 'sac':
-        raise SystemExit(f'--seeds: seed batches are built for --alg sac only (got --alg {args.alg}); run one process per seed instead')
     if not seeds or len(set(seeds)) != len(seeds):
         raise SystemExit(f'--seeds {args.seeds}: give distinct integer seeds, e.g. --seeds 0,1,2,3')
-    from rlrep_amd.agent.sac.seed_batch import SACSeedBatch
+    if args.alg not in ('sac', 'ctrlsac'):
+        raise SystemExit(f'--seeds: seed batches are built for --alg sac and ctrlsac only (got --alg {args.alg}); run one process per seed instead')
     from rlrep_amd.utils.buffer_group import ReplayBufferGroup
     R = len(seeds)
     envs_, evals_ = [envs.make(args.env) for _ in seeds], [envs.make(args.env) for _ in seeds]
@@ -170,8 +170,14 @@ def run_seeds(args):
     space = envs_[0].action_space
     state_dim, action_dim = envs_[0].observation_space.shape[0], space.shape[0]
     lo, hi = np.asarray(space.low, np.float32), np.asarray(space.high, np.float32)
-    agent = SACSeedBatch(seeds, state_dim, action_dim, space, discount=args.discount, tau=args.tau, hidden_dim=args.hidden_dim,
-                         max_batch=args.batch_size)
+    common = dict(discount=args.discount, tau=args.tau, hidden_dim=args.hidden_dim, max_batch=args.batch_size)
+    if args.alg == 'ctrlsac':
+        from rlrep_amd.agent.ctrlsac.seed_batch import CTRLSACSeedBatch
+        common.update(feature_dim=2048, hidden_dim=1024)                       # as build_agent (main.py:90-91)
+        agent = CTRLSACSeedBatch(seeds, state_dim, action_dim, space, extra_feature_steps=args.extra_feature_steps, **common)
+    else:
+        from rlrep_amd.agent.sac.seed_batch import SACSeedBatch
+        agent = SACSeedBatch(seeds, state_dim, action_dim, space, **common)
     replay = ReplayBufferGroup(R, state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)))
     policies = [_MemberPolicy(agent, r) for r in range(R)]
     evaluations = [[util.eval_policy(policies[r], evals_[r], args.eval_episodes)] for r in range(R)]

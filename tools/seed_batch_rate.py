@@ -1,6 +1,10 @@
-"""Aggregate train() rate of a SACSeedBatch against R standalone SACAgents replayed back to back on one stream.
+"""Aggregate train() rate of a seed batch against R standalone agents replayed back to back on one stream.
 
     python tools/seed_batch_rate.py --workload sac_pendulum_b64 --members 1,2,4,8,16
+    python tools/seed_batch_rate.py --workload ctrlsac_halfcheetah_f2048_b256 --members 1,2,4,8
+
+sac workloads: SACSeedBatch against SACAgent; ctrlsac workloads: CTRLSACSeedBatch against CTRLSACAgent(pipeline=False), the one-graph
+train() a ctrlsac group runs (the pipelined two-chain form is not built for groups).
 
 Per R: the group's aggregate rate (R x calls/s), its graph's launch count per call, and the standalone agents' aggregate rate.  Protocol:
 --warmup calls (default 300), then the median of --windows windows (default 5) of --calls calls (default 500), timed by host wall clock
@@ -34,18 +38,26 @@ def _rate(step, R, warmup, calls, windows):
 
 def main(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--workload', default='sac_halfcheetah_b256', choices=['sac_pendulum_b64', 'sac_halfcheetah_b256'])
+    p.add_argument('--workload', default='sac_halfcheetah_b256', choices=['sac_pendulum_b64', 'sac_halfcheetah_b256', 'ctrlsac_halfcheetah_f256_b256',
+                                                                          'ctrlsac_halfcheetah_f2048_b256'])
     p.add_argument('--members', default='1,2,4,8,16')
     p.add_argument('--warmup', type=int, default=300)
     p.add_argument('--calls', type=int, default=500)
     p.add_argument('--windows', type=int, default=5)
     p.add_argument('--group-only', action='store_true', help='skip the standalone agents (a profiler run of the group alone)')
     a = p.parse_args(argv)
-    from rlrep_amd.agent.sac.sac_agent import SACAgent
-    from rlrep_amd.agent.sac.seed_batch import SACSeedBatch
     from rlrep_amd.utils.buffer_group import ReplayBufferGroup
     alg, S, A, B, kw = bench.WORKLOADS[a.workload]
-    print(f'# {a.workload}: S={S} A={A} B={B} {kw}; {torch.cuda.get_device_name(0)}; warmup {a.warmup}, median of {a.windows} x {a.calls} calls')
+    alone_kw = {}
+    if alg == 'ctrlsac':
+        from rlrep_amd.agent.ctrlsac.ctrlsac_agent import CTRLSACAgent as Agent
+        from rlrep_amd.agent.ctrlsac.seed_batch import CTRLSACSeedBatch as Group
+        alone_kw = dict(pipeline=False)
+    else:
+        from rlrep_amd.agent.sac.sac_agent import SACAgent as Agent
+        from rlrep_amd.agent.sac.seed_batch import SACSeedBatch as Group
+    print(f'# {a.workload}: S={S} A={A} B={B} {kw}; {Group.__name__} against {Agent.__name__}({alone_kw}); {torch.cuda.get_device_name(0)}; '
+          f'warmup {a.warmup}, median of {a.windows} x {a.calls} calls')
     print(f'{"R":>3} {"group train()/s":>16} {"launches/call":>14} {"R standalone train()/s":>23} {"ratio":>6}')
     for R in [int(x) for x in a.members.split(',')]:
         seeds = list(range(R))
@@ -55,7 +67,7 @@ def main(argv=None):
             buf, data = bench.synth_buffer(S, A, r)
             rings.load(r, data['state'], data['action'], data['next_state'], data['reward'], data['done'])
             alone_bufs.append(buf)
-        grp = SACSeedBatch(seeds, S, A, bench.Space(A), max_batch=B, **kw)
+        grp = Group(seeds, S, A, bench.Space(A), max_batch=B, **kw)
         g_rate = _rate(lambda: grp.train(rings, B), R, a.warmup, a.calls, a.windows)
         launches = grp._graph_launches
         if a.group_only:
@@ -64,7 +76,7 @@ def main(argv=None):
         agents = []
         for s in seeds:
             torch.manual_seed(s)
-            agents.append(SACAgent(S, A, bench.Space(A), max_batch=B, seed=s, **kw))
+            agents.append(Agent(S, A, bench.Space(A), max_batch=B, seed=s, **alone_kw, **kw))
 
         def alone_step():
             for ag, buf in zip(agents, alone_bufs):
