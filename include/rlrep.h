@@ -484,7 +484,7 @@ int64_t rlrep_launch_counter(void);
 int32_t rlrep_front_end_counts(int64_t* out4);
 
 /* ---- seed groups: R independent sac or ctrlsac agents in the same launches (additive to ABI 4) -----------------------------------------
- * A group is R members of identical dims / hyper whose blocks -- the seven arenas of rlrep_agent_create -- are laid out identically at a
+ * A group is R members of identical dims (and hyper, but for what rlrep_group_set_member_hyper may vary) whose blocks -- the seven arenas of rlrep_agent_create -- are laid out identically at a
  * constant byte stride in ONE allocation: member r's copy of any word is member 0's address + r * member_stride_bytes.  The step programs are
  * built once, against member 0's arenas; every launch of the agent then runs all members (grid y = member) and moves every pointer it
  * dereferences to the member's block.  Each member computes exactly what a standalone agent with its seed computes: same tiles, same
@@ -508,6 +508,18 @@ int32_t rlrep_group_create(const rlrep_dims* dims, const rlrep_hyper* hyper, con
 int32_t rlrep_group_max_members(void);
 /* members of a group agent; 0 for an ordinary agent */
 int32_t rlrep_group_members(rlrep_agent* agent);
+/* Sweeps: members may differ in the hyper-parameters that no launch's shape depends on.  Member `member`'s lr_feature, lr_critic, lr_actor
+ * (its temperature optimizer's too), discount, tau, feature_tau, target_update_period and learn_alpha become `hyper`'s: its four optimizer
+ * records' lr / tau words (rlrep_group_cfg_dev, the member's copy) and its record of the scalars the programs otherwise carry by value
+ * (discount, target_update_period, the temperature lr and learn_alpha), read by the group launches from the member's block.  Stream-ordered on
+ * `stream` and then synchronised; a captured graph reads the new values at its next replay (no re-capture).  The step counters, moments and
+ * the temperature state are untouched: the initial temperature is the caller's alpha_state[0].
+ * Rejected with RLREP_ERR_ARG and a message: an ordinary agent, a member outside [0, members), a structural field that differs from the
+ * group's (target_entropy, sigma_scale, extra_feature_steps, world_size, beta1, beta2, adam_eps, critic_reg_lambda), a learning rate that is
+ * not finite and positive, a non-finite discount, tau or feature_tau outside [0, 1], target_update_period < 1.  Until it is called a member
+ * has rlrep_group_create's hyper.  rlrep_group_get_member_hyper reads a member's values back (world_size as the group normalises it). */
+int32_t rlrep_group_set_member_hyper(rlrep_agent* agent, int32_t member, const rlrep_hyper* hyper, void* stream);
+int32_t rlrep_group_get_member_hyper(rlrep_agent* agent, int32_t member, rlrep_hyper* out);
 /* the Philox seed of every member (n = members): member r's index and noise pools are drawn as rlrep_train_prologue draws them with seeds[r] */
 int32_t rlrep_group_set_seeds(rlrep_agent* agent, const uint64_t* seeds_host, int32_t n, void* stream);
 /* rlrep_train_prologue for every member, in ONE launch: member r draws with its seed, gathers from ring_dev + r * ring_stride_bytes bounded

@@ -29,8 +29,12 @@ class CTRLSACAgent(SACAgent):
                           feature_dim=feature_dim, phi_hidden_dim=hidden_dim, phi_hidden_depth=2,
                           mu_hidden_dim=hidden_dim, mu_hidden_depth=2,
                           flags=0 if self.use_feature_target else _lib.FLAG_NO_FEATURE_TARGET)
-        self._hyper = dict(lr_feature=lr, lr_critic=lr, lr_actor=lr / 3)
+        self._hyper = self._lr_hyper(lr)
         self._finish_init(_hip)
+
+    @staticmethod
+    def _lr_hyper(lr):
+        return dict(lr_feature=lr, lr_critic=lr, lr_actor=lr / 3)
 
     def _init_parameters(self):
         self._init_prefix('actor', True)

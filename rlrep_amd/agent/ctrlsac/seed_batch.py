@@ -19,6 +19,8 @@ class CTRLSACSeedBatch(SeedBatchMixin, CTRLSACAgent):
     `train(buffers, batch_size)` takes a ReplayBufferGroup (rlrep_amd/utils/buffer_group.py) -- member r samples ring r -- and returns a list of
     R info dicts.  Only the single-GPU one-graph train() is built: pipeline=True, graph=False and data parallel are refused."""
 
+    SWEEP_KEYS = SeedBatchMixin.SWEEP_KEYS + ('feature_tau',)
+
     def __init__(self, seeds, state_dim, action_dim, action_space, **kwargs):
         kwargs = dict(kwargs)
         if kwargs.get('pipeline', False):

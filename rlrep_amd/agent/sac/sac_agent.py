@@ -161,8 +161,13 @@ class SACAgent(object):
                           auto_entropy_tuning)
         self._dims = dict(state_dim=state_dim, action_dim=action_dim, hidden_dim=hidden_dim,
                           actor_hidden_dim=hidden_dim)
-        self._hyper = dict(lr_feature=lr, lr_critic=lr, lr_actor=lr)
+        self._hyper = self._lr_hyper(lr)
         self._finish_init(_hip)
+
+    @staticmethod
+    def _lr_hyper(lr):
+        """the constructor's `lr` as the library's three learning rates (the temperature optimizer takes lr_actor)"""
+        return dict(lr_feature=lr, lr_critic=lr, lr_actor=lr)
 
     # ---- construction -------------------------------------------------------------------------
     def _init_common(self, state_dim, action_dim, action_space, discount, target_update_period, tau, alpha,

@@ -9,8 +9,16 @@ SeedBatchMixin goes in front of the standalone agent class (SACSeedBatch(SeedBat
 CTRLSACAgent)): member cores, the train() pools inside the member block, the group train prologue, select_action for every member in one
 launch, member export and checkpoints.  Initialisation rule: member r is initialised exactly as `torch.manual_seed(seeds[r]); Agent(...,
 seed=seeds[r])` initialises, and draws its sample indices and noise from the Philox stream of seed seeds[r].
+
+Sweeps: `member_hyper=[dict, ...]` (one dict per member) lets members differ in the hyper-parameters no launch's shape depends on (SWEEP_KEYS:
+lr, discount, tau, alpha, target_update_period, auto_entropy_tuning; ctrlsac also feature_tau).  The constructor kwargs are the shared
+defaults; member r is then `torch.manual_seed(seeds[r]); Agent(..., seed=seeds[r], **defaults, **member_hyper[r])`.  Seeds may repeat as long
+as the (seed, hyper) pairs are distinct.  Everything else -- dimensions, extra_feature_steps, use_feature_target, max_batch -- is structural:
+shared by every member and refused in a member dict.
 """
 import ctypes as C
+import inspect
+import math
 import os
 
 import numpy as np
@@ -84,18 +92,96 @@ class SeedBatchMixin(object):
     (rlrep_amd/utils/buffer_group.py) -- member r samples ring r -- and returns a list of R info dicts.  The single-GPU whole-train() graph is
     the only form (no data parallel, no eager steps)."""
 
+    # constructor kwargs a member may override (member_hyper): what the group launches read per member (include/rlrep.h
+    # rlrep_group_set_member_hyper) or what only initialisation uses (alpha)
+    SWEEP_KEYS = ('lr', 'discount', 'tau', 'alpha', 'target_update_period', 'auto_entropy_tuning')
 
-    def __init__(self, seeds, state_dim, action_dim, action_space, **kwargs):
+    @classmethod
+    def _agent_class(cls):
+        mro = cls.__mro__
+        return mro[mro.index(SeedBatchMixin) + 1]
+
+    @classmethod
+    def sweep_defaults(cls):
+        """{key: the standalone agent's default} for every SWEEP_KEYS entry"""
+        sig = inspect.signature(cls._agent_class().__init__)
+        return {k: sig.parameters[k].default for k in cls.SWEEP_KEYS}
+
+    @classmethod
+    def normalise_hyper(cls, key, value, who=None):
+        """value of a sweepable key as the agent stores it; ValueError (naming `who` and the key) when it is not one the library accepts"""
+        who = who or cls.__name__
+        try:
+            if key == 'target_update_period':
+                if isinstance(value, float) and not value.is_integer():
+                    raise ValueError
+                v = int(value)
+                ok = v >= 1
+            elif key == 'auto_entropy_tuning':
+                if isinstance(value, str):
+                    if value.lower() not in ('0', '1', 'true', 'false'):
+                        raise ValueError
+                    value = value.lower() in ('1', 'true')
+                v, ok = bool(value), True
+            else:
+                v = float(value)
+                ok = math.isfinite(v) and {'lr': v > 0, 'alpha': v > 0, 'tau': 0 <= v <= 1, 'feature_tau': 0 <= v <= 1}.get(key, True)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            need = {'lr': 'a finite positive number', 'alpha': 'a finite positive number', 'tau': 'a number in [0, 1]',
+                    'feature_tau': 'a number in [0, 1]', 'target_update_period': 'an integer >= 1', 'discount': 'a finite number',
+                    'auto_entropy_tuning': 'a boolean'}[key]
+            raise ValueError(f'{who}: {key}={value!r} is not valid ({key} must be {need})')
+        return v
+
+    @classmethod
+    def member_hypers(cls, seeds, kwargs, member_hyper):
+        """Each member's sweepable hyper-parameters (dicts in SWEEP_KEYS order), checked before anything touches the GPU."""
+        name = cls.__name__
+        defaults = cls.sweep_defaults()
+        base = {k: cls.normalise_hyper(k, kwargs.get(k, defaults[k])) for k in cls.SWEEP_KEYS}
+        if member_hyper is None:
+            return [dict(base) for _ in seeds]
+        member_hyper = list(member_hyper)
+        if len(member_hyper) != len(seeds):
+            raise ValueError(f'{name}: member_hyper has {len(member_hyper)} entries for {len(seeds)} seeds (one dict per member)')
+        structural = set(inspect.signature(cls._agent_class().__init__).parameters) - set(cls.SWEEP_KEYS) - {'self', '_hip'}
+        out = []
+        for r, mh in enumerate(member_hyper):
+            if not isinstance(mh, dict):
+                raise ValueError(f'{name}: member_hyper[{r}] is not a dict')
+            for k in mh:
+                if k in cls.SWEEP_KEYS:
+                    continue
+                if k in structural or k in ('max_batch', 'seed', 'pipeline', 'graph'):
+                    raise ValueError(f'{name}: member_hyper[{r}][{k!r}] is structural (shared by every member of a group): pass it to the constructor')
+                raise ValueError(f'{name}: member_hyper[{r}] has unknown key {k!r} (sweepable: {", ".join(cls.SWEEP_KEYS)})')
+            h = dict(base)
+            h.update({k: cls.normalise_hyper(k, v, f'{name}: member_hyper[{r}]') for k, v in mh.items()})
+            out.append(h)
+        seen = {}
+        for r, (s, h) in enumerate(zip(seeds, out)):
+            key = (s, tuple(h.items()))
+            if key in seen:
+                raise ValueError(f'{name}: members {seen[key]} and {r} have the same seed {s} and the same hyper-parameters (duplicate (seed, hyper) pair)')
+            seen[key] = r
+        return out
+
+    def __init__(self, seeds, state_dim, action_dim, action_space, member_hyper=None, **kwargs):
         name = type(self).__name__
         self.seeds = [int(s) for s in seeds]
         if not self.seeds:
             raise ValueError(f'{name}: at least one seed')
-        if len(set(self.seeds)) != len(self.seeds):
+        if member_hyper is None and len(set(self.seeds)) != len(self.seeds):
             raise ValueError(f'{name}: seeds must be distinct')
+        self._mhyper = self.member_hypers(self.seeds, kwargs, member_hyper)
+        self._swept = member_hyper is not None
         self.R = len(self.seeds)
         kwargs = dict(kwargs)
         kwargs.pop('seed', None)
         kwargs['seed'] = self.seeds[0]
+        kwargs.update(self._mhyper[0])          # the group is created with member 0's values; the others' go in right after (_make_core)
         super().__init__(state_dim, action_dim, action_space, **kwargs)
         if self.world_size > 1 or self._dp or not self.use_graph:
             raise RuntimeError(f'{name}: a seed group runs the single-GPU whole-train() graph only')
@@ -111,7 +197,29 @@ class SeedBatchMixin(object):
     def _make_core(self, dims, hyper):
         ni, ne = self._pool_sizes(self.max_batch)
         # the index and noise pools of a train() sit behind the arenas of every member: the prologue writes member r's at the member stride
-        return HipCore(self.ALG, dims, hyper, members=len(self.seeds), member_extra_bytes=4 * (ni + ne) + 512)
+        core = HipCore(self.ALG, dims, hyper, members=len(self.seeds), member_extra_bytes=4 * (ni + ne) + 512)
+        if self._swept:
+            for r in range(len(self.seeds)):
+                h = self._hyper_struct(core, self._mhyper[r])
+                check(lib.rlrep_group_set_member_hyper(core.h, r, C.byref(h), _stream()), 'group_set_member_hyper')
+        return core
+
+    def _hyper_struct(self, core, hp):
+        """the library's hyper record of a member with sweepable values `hp`, the group's structural fields unchanged (as _finish_init
+        builds a standalone agent's)"""
+        h = type(core.hyper).from_buffer_copy(core.hyper)
+        for k, v in self._lr_hyper(hp['lr']).items():
+            setattr(h, k, float(v))
+        h.discount, h.tau = hp['discount'], hp['tau']
+        if 'feature_tau' in hp:
+            h.feature_tau = hp['feature_tau']
+        h.target_update_period, h.learn_alpha = hp['target_update_period'], int(hp['auto_entropy_tuning'])
+        return h
+
+    def member_hyper(self, r):
+        """member r's sweepable hyper-parameters: `Agent(..., seed=seeds[r], **member_hyper(r))` (with the group's other kwargs) is its
+        standalone twin"""
+        return dict(self._mhyper[r])
 
     def _init_parameters(self):
         group = self.core
@@ -122,7 +230,7 @@ class SeedBatchMixin(object):
                 torch.manual_seed(s)
                 self.core = self._members[r]
                 super()._init_parameters()
-                self.core.alpha_state[0] = float(np.log(self._alpha0))
+                self.core.alpha_state[0] = float(np.log(self._mhyper[r]['alpha']))
         finally:
             self.core = group
             torch.random.set_rng_state(saved)
@@ -219,7 +327,8 @@ class SeedBatchMixin(object):
         c = self._members[r]
         return {'format': self.CHECKPOINT_FORMAT, 'device_state_bytes': int(c.device_state().numel()), 'alg': self.ALG, 'params': c.params.cpu(),
                 'targets': c.targets.cpu(), 'exp_avg': c.exp_avg.cpu(), 'exp_avg_sq': c.exp_avg_sq.cpu(), 'alpha_state': c.alpha_state.cpu(),
-                'device_state': c.device_state().cpu(), 'steps': self.steps, 'noise_ctr': self._ctr, 'seed': self.seeds[r], 'layout': list(c.order)}
+                'device_state': c.device_state().cpu(), 'steps': self.steps, 'noise_ctr': self._ctr, 'seed': self.seeds[r], 'layout': list(c.order),
+                'hyper': self.member_hyper(r)}
 
     def state_snapshot(self):
         return {'format': 'rlrep-seed-batch-1', 'seeds': list(self.seeds), 'members': [self.member_snapshot(r) for r in range(self.R)]}
@@ -236,6 +345,11 @@ class SeedBatchMixin(object):
             c = self._members[r]
             if ms['layout'] != list(c.order) or ms['device_state'].numel() != c.device_state().numel():
                 raise RuntimeError('checkpoint does not match this seed batch (dimensions differ)')
+            if 'hyper' in ms and dict(ms['hyper']) != self.member_hyper(r):
+                raise RuntimeError(f'checkpoint does not match this seed batch (member {r} hyper-parameters differ: {dict(ms["hyper"])} '
+                                   f'against {self.member_hyper(r)})')
+        for r, ms in enumerate(snap['members']):
+            c = self._members[r]
             for k, dst in (('params', c.params), ('targets', c.targets), ('exp_avg', c.exp_avg), ('exp_avg_sq', c.exp_avg_sq),
                            ('alpha_state', c.alpha_state)):
                 dst.copy_(ms[k])

@@ -315,9 +315,11 @@ __device__ __forceinline__ float row_dot(const float* __restrict__ e, const floa
 __global__ __launch_bounds__(256) void qhead_critic_kernel(QHeadCritic p) {
 #include "qhead_critic_body.h"
 }
-__global__ __launch_bounds__(256) void qhead_critic_kernel_grp(QHeadCritic p0, long long mstride) {
+// hyp: member 0's MemberHyper (kparams.h) -- the member's discount comes from its record, not from member 0's p0.gamma
+__global__ __launch_bounds__(256) void qhead_critic_kernel_grp(QHeadCritic p0, long long mstride, const MemberHyper* __restrict__ hyp) {
     QHeadCritic p = p0;
     rl_rebase(p, (long long)blockIdx.y * mstride);
+    p.gamma = rl_mv<true>(hyp, (long long)blockIdx.y * mstride)->gamma;
 #include "qhead_critic_body.h"
 }
 
@@ -353,15 +355,20 @@ __device__ __forceinline__ void copy_segs_body(const CopySegs& p, int blk, int n
 // (the body of an optimizer block; `bid` = block index within the optimizer part of the launch)
 // DP (compile time): the data-parallel instantiation (dp_pull.h).  A run-time switch would put the prefetched loads of p / g / m / v into
 // control-flow diamonds (hipcc drains vmcnt at their merges): the single-GPU launch must not pay for code it never runs (measured: 5.4 -> 11.7 us).
+// the target-update period of the Polyak gate: the record's in the single-agent kernels, the member's MemberHyper in a group form
+template <bool GRP> __device__ __forceinline__ int pol_period_of(const AdamTask& t, const MemberHyper* hyp, long long mdelta) {
+    if constexpr (GRP) return rl_mv<GRP>(hyp, mdelta)->pol_period;
+    else { (void)hyp; (void)mdelta; return t.pol_period; }
+}
 template <int DP, bool GRP = false>
 __device__ __forceinline__ void adam_elems(const int bid, float* __restrict__ ap, const float* __restrict__ agr, float* __restrict__ am, float* __restrict__ av,
                                            const GroupCfg* __restrict__ agrp, float* __restrict__ atarget, int an, int hdr, const AdamTask& t, const AdamSnap& snap, const DpPull& dp,
-                                           long long mdelta = 0);
+                                           long long mdelta = 0, const MemberHyper* hyp = nullptr);
 template <int DP, bool GRP = false>
 __device__ __forceinline__ void adam_block(const int bid, float* __restrict__ ap, const float* __restrict__ agr, float* __restrict__ am, float* __restrict__ av,
                                            const GroupCfg* __restrict__ agrp, float* __restrict__ atarget, int an, int hdr, const AdamTask& t,
                                            const FinTask* __restrict__ fin, int nfin, const SlotFill& sf, int fill_blocks, const SlotFill& sf2, int fill2_blocks,
-                                           const AdamSnap& snap, int snap_blocks, const DpPull& dp, long long mdelta = 0) {
+                                           const AdamSnap& snap, int snap_blocks, const DpPull& dp, long long mdelta = 0, const MemberHyper* hyp = nullptr) {
     const int adam_blocks = hdr & 0x3fffffff;
     // Data parallel (DP != 0, dp_pull.h): the optimizer blocks and the trailing block wait for the peers' gradients, read every rank's arena in
     // rank order where they used to read one gradient (DP == 1), or sum their rank's shard first and read the sums from the shards' owners (DP == 2),
@@ -388,14 +395,14 @@ __device__ __forceinline__ void adam_block(const int bid, float* __restrict__ ap
         unsigned dpe = 0; bool good = true;
         if constexpr (dpon) dpe = dp_begin(dp, false, true, &good);
         if (threadIdx.x == 64 && t.sync_steps) rl_mv<GRP>(t.sync_steps, mdelta)[2] = rl_mv<GRP>(t.sync_steps, mdelta)[0];          // (beside the metric tasks, not in their serial chain)
-        if (threadIdx.x < 64 && good) finalize_tasks<GRP>(fin, nfin, threadIdx.x, dpon ? &dp : nullptr, mdelta);
+        if (threadIdx.x < 64 && good) finalize_tasks<GRP>(fin, nfin, threadIdx.x, dpon ? &dp : nullptr, mdelta, hyp);
         if constexpr (dpon) dp_end(dp, dpe, true);
         return;
     }
     unsigned dpe = 0; bool good = true;
     if constexpr (dpon) dpe = dp_begin(dp, bid == 0, true, &good);
     if constexpr (DP == 2) good = dp_reduce_scatter(dp, dpe, bid, (long long)(agr - dp.base[dp.rank]), (long long)an >> 2, good) && good;
-    if (good) adam_elems<DP, GRP>(bid, ap, agr, am, av, agrp, atarget, an, hdr, t, snap, dp, mdelta);
+    if (good) adam_elems<DP, GRP>(bid, ap, agr, am, av, agrp, atarget, an, hdr, t, snap, dp, mdelta, hyp);
     if constexpr (dpon) dp_end(dp, dpe, true);
 }
 
@@ -405,7 +412,7 @@ __device__ __forceinline__ void adam_block(const int bid, float* __restrict__ ap
 template <int DP, bool GRP>
 __device__ __forceinline__ void adam_elems(const int bid, float* __restrict__ ap, const float* __restrict__ agr, float* __restrict__ am, float* __restrict__ av,
                                            const GroupCfg* __restrict__ agrp, float* __restrict__ atarget, int an, int hdr, const AdamTask& t, const AdamSnap& snap, const DpPull& dp,
-                                           long long mdelta) {
+                                           long long mdelta, const MemberHyper* hyp) {
     constexpr bool dpon = DP != 0;
     // (the arena pointers and the group record are preloaded arguments: these loads go out before the record `t` has arrived)
     const long long i = ((long long)bid * 256 + threadIdx.x) * 4;
@@ -428,7 +435,7 @@ __device__ __forceinline__ void adam_elems(const int bid, float* __restrict__ ap
     // ranges whose optimizer ran in the weight-gradient epilogues (FLAG_ADAM): nothing to do here
     if (t.nskip > 0 && i >= t.skip_off[0] && i < t.skip_off[0] + t.skip_n[0]) return;
     if (t.nskip > 1 && i >= t.skip_off[1] && i < t.skip_off[1] + t.skip_n[1]) return;
-    const bool pol_on = atarget && (!t.pol_steps || ((*rl_mv<GRP>(t.pol_steps, mdelta)) % t.pol_period) == 0);
+    const bool pol_on = atarget && (!t.pol_steps || ((*rl_mv<GRP>(t.pol_steps, mdelta)) % pol_period_of<GRP>(t, hyp, mdelta)) == 0);
     if (vec && t.nslab) {
         // split-K partial gradients finished here (AdamTask::Slab): all partials in flight together, summed in split order (the order of
         // the finishing launch this replaces: bit-identical), the sum filed in the gradient arena for whoever reads gradients
@@ -545,16 +552,17 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ ap, const
 }
 // group form (group.h): member = blockIdx.y; the arenas, the riders and the metric finishers' pointers move to the member's block, and so do the
 // pointers adam_block / adam_elems read from the record `t`, where they read them (the record itself stays in the kernel-argument segment).  No
-// folded snapshot (the launcher refuses one: a group has no deferred chain); `snap` only fills the argument list.
+// folded snapshot (the launcher refuses one: a group has no deferred chain); `snap` only fills the argument list.  hyp: member 0's MemberHyper
+// (kparams.h) -- the Polyak gate's period and the temperature optimizer's lr / learn gate come from the member's record, not from `t` / `fin`.
 __global__ __launch_bounds__(256) void adam_kernel_grp(float* ap, const float* agr, float* am, float* av, const GroupCfg* agrp, float* atarget, int an, int hdr, AdamTask t,
                                                        const FinTask* __restrict__ fin, int nfin, SlotFill sf, int fill_blocks, SlotFill sf2, int fill2_blocks, AdamSnap snap, int snap_blocks,
-                                                       long long mstride, long long rstride) {
+                                                       long long mstride, long long rstride, const MemberHyper* hyp) {
     __builtin_amdgcn_s_setprio(3);
     const long long dm = (long long)blockIdx.y * mstride, dr = (long long)blockIdx.y * rstride;
     rl_rb(ap, dm); rl_rb(agr, dm); rl_rb(am, dm); rl_rb(av, dm); rl_rb(agrp, dm); rl_rb(atarget, dm);
     SlotFill s1 = sf, s2 = sf2; rl_rebase(s1, dm, dr); rl_rebase(s2, dm, dr);
     const DpPull nodp = DpPull();
-    adam_block<0, true>(blockIdx.x, ap, agr, am, av, agrp, atarget, an, hdr, t, fin, nfin, s1, fill_blocks, s2, fill2_blocks, snap, snap_blocks, nodp, dm);
+    adam_block<0, true>(blockIdx.x, ap, agr, am, av, agrp, atarget, an, hdr, t, fin, nfin, s1, fill_blocks, s2, fill2_blocks, snap, snap_blocks, nodp, dm, hyp);
 }
 template <int DP>
 __global__ __launch_bounds__(256) void adam_dp_kernel(float* __restrict__ ap, const float* __restrict__ agr, float* __restrict__ am, float* __restrict__ av,
@@ -726,7 +734,7 @@ extern "C" int rl_launch_vae_mse(const VaeMse* p, hipStream_t st) {
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_qhead_critic(const QHeadCritic* p, hipStream_t st) {
-    if (const RlGrp* gr = rl_grp_active()) hipLaunchKernelGGL(qhead_critic_kernel_grp, dim3(p->nblk, gr->members), dim3(256), 0, st, *p, gr->stride);
+    if (const RlGrp* gr = rl_grp_active()) hipLaunchKernelGGL(qhead_critic_kernel_grp, dim3(p->nblk, gr->members), dim3(256), 0, st, *p, gr->stride, gr->hyp);
     else hipLaunchKernelGGL(qhead_critic_kernel, dim3(p->nblk), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
@@ -776,7 +784,7 @@ extern "C" int rl_launch_adam(const AdamTask* task, int adam_blocks, const FinTa
         }
     } else if (gr)
         hipLaunchKernelGGL(adam_kernel_grp, dim3(grid.x, gr->members), dim3(256), 0, st, t.p, t.g, t.m, t.v, t.grp, t.target, (int)t.n, hdr, t,
-                           fin, nfin, sf ? *sf : none, fb, sf2 ? *sf2 : none, fb2, snap ? *snap : nosnap, sb, gr->stride, gr->ring_stride);
+                           fin, nfin, sf ? *sf : none, fb, sf2 ? *sf2 : none, fb2, snap ? *snap : nosnap, sb, gr->stride, gr->ring_stride, gr->hyp);
     else
         hipLaunchKernelGGL(adam_kernel, grid, dim3(256), 0, st, t.p, t.g, t.m, t.v, t.grp, t.target, (int)t.n, hdr, t,
                            fin, nfin, sf ? *sf : none, fb, sf2 ? *sf2 : none, fb2, snap ? *snap : nosnap, sb);

@@ -6,6 +6,8 @@
 // the batch size changes; the hot path performs no allocation, no host<->device copy and no sync.
 #include "engine_internal.h"
 #include <cstdarg>
+#include <cmath>
+#include <cstddef>
 #include <memory>
 
 static thread_local char g_err[512] = "";
@@ -27,7 +29,7 @@ struct GrpScope {
     explicit GrpScope(const rlrep_agent* ag) {
         if (!ag || ag->members <= 0) return;
         prev = g_grp; prev_on = g_grp_on;          // (nesting-safe: the enclosing call's group comes back on exit)
-        g_grp.members = ag->members; g_grp.stride = ag->grp_stride; g_grp.ring_stride = ag->grp_ring_stride; g_grp.seeds = ag->grp_seeds;
+        g_grp.members = ag->members; g_grp.stride = ag->grp_stride; g_grp.ring_stride = ag->grp_ring_stride; g_grp.seeds = ag->grp_seeds; g_grp.hyp = ag->mhyp;
         g_grp_on = set = true;
     }
     ~GrpScope() { if (set) { g_grp = prev; g_grp_on = prev_on; } }
@@ -1052,6 +1054,9 @@ static void static_state(rlrep_agent* ag) {
     if (!ws.dry && ws.ok()) { (void)hipMemset(ag->hist, 0xff, sizeof(float) * RL_HIST_N * RL_HIST_REC); (void)hipMemset(ag->hist_seq, 0, sizeof(int) * 4); }
     ag->xc_err = (unsigned*)ws.alloc(256);
     if (!ws.dry && ws.ok()) (void)hipMemset(ag->xc_err, 0, 256);
+    // a seed group member's by-value hyper-parameters (group kernel forms only; written by rlrep_group_create / _set_member_hyper).  Behind the
+    // metric slots: not part of the device records a checkpoint carries (HipCore.device_state)
+    ag->mhyp = (MemberHyper*)ws.alloc(sizeof(MemberHyper));
     if (!ws.dry && ws.ok()) { const int one[4] = {1, 0, 0, 0}; (void)hipMemcpy(ag->rp_epoch, one, sizeof(one), hipMemcpyHostToDevice); }
     // transposed weight shadows (see rlrep_agent::sh_dev): vlsac's feature group, read by the feature step's row programs
     ag->shadow_of.clear();
@@ -2028,6 +2033,13 @@ static long long member_span(const rlrep_layout_info& info, const rlrep_arenas* 
     return (long long)(hi - lo);
 }
 int32_t rlrep_group_max_members(void) { return RLREP_GROUP_MAX_MEMBERS; }
+// what the step programs carry by value from rlrep_hyper, as a group member's record holds it (kparams.h MemberHyper; engine.hip actor_fins,
+// critic_apply_folded and the qhead critic stages read the same fields)
+static MemberHyper member_hyper_of(const rlrep_hyper& h) {
+    MemberHyper m;
+    m.gamma = h.discount; m.pol_period = h.target_update_period; m.alpha_lr = h.lr_actor; m.learn = h.learn_alpha;
+    return m;
+}
 
 int32_t rlrep_group_create(const rlrep_dims* dims, const rlrep_hyper* hyper, const rlrep_arenas* arenas, int32_t members, int64_t member_stride_bytes,
                            void* stream, rlrep_agent** out) {
@@ -2056,6 +2068,9 @@ int32_t rlrep_group_create(const rlrep_dims* dims, const rlrep_hyper* hyper, con
     for (const void* q : {(const void*)arenas->target_dev, (const void*)arenas->grad_dev, (const void*)arenas->exp_avg_dev, (const void*)arenas->exp_avg_sq_dev,
                           (const void*)arenas->workspace_dev, (const void*)arenas->alpha_state_dev}) lo = std::min(lo, (const char*)q);
     ag->grp_lo = lo;
+    ag->grp_hyper.assign(members, ag->h);
+    const MemberHyper mh0 = member_hyper_of(ag->h);
+    if (e == hipSuccess) e = hipMemcpyAsync(ag->mhyp, &mh0, sizeof(mh0), hipMemcpyHostToDevice, (hipStream_t)stream);
     for (int m = 1; m < members && e == hipSuccess; ++m)
         e = hipMemcpyAsync((char*)lo + (long long)m * member_stride_bytes, lo, (size_t)span, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
@@ -2069,6 +2084,60 @@ int32_t rlrep_group_set_seeds(rlrep_agent* ag, const uint64_t* seeds, int32_t n,
     const hipError_t e = hipMemcpyAsync(ag->grp_seeds, seeds, sizeof(uint64_t) * n, hipMemcpyHostToDevice, (hipStream_t)stream);
     if (e == hipSuccess) (void)hipStreamSynchronize((hipStream_t)stream);
     if (e != hipSuccess) { rl_set_error("group_set_seeds: %s", hipGetErrorString(e)); return RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_group_set_member_hyper(rlrep_agent* ag, int32_t member, const rlrep_hyper* hyper, void* stream) {
+    if (!ag || ag->members <= 0) { rl_set_error("group_set_member_hyper: not a seed group"); return RLREP_ERR_ARG; }
+    if (member < 0 || member >= ag->members) { rl_set_error("group_set_member_hyper: member %d outside [0, %d)", member, ag->members); return RLREP_ERR_ARG; }
+    if (!hyper) { rl_set_error("group_set_member_hyper: null hyper"); return RLREP_ERR_ARG; }
+    const rlrep_hyper& g = ag->h;
+    // structural: these shape the step programs (or are shared by every member's launches) -- equal to the group's or refused
+    const int ws = hyper->world_size > 0 ? hyper->world_size : 1;
+    const struct { const char* name; double have, want; } st[] = {
+        {"target_entropy", hyper->target_entropy, g.target_entropy}, {"sigma_scale", hyper->sigma_scale, g.sigma_scale},
+        {"extra_feature_steps", (double)hyper->extra_feature_steps, (double)g.extra_feature_steps}, {"world_size", (double)ws, (double)g.world_size},
+        {"beta1", hyper->beta1, g.beta1}, {"beta2", hyper->beta2, g.beta2}, {"adam_eps", hyper->adam_eps, g.adam_eps},
+        {"critic_reg_lambda", hyper->critic_reg_lambda, g.critic_reg_lambda}};
+    for (const auto& f : st)
+        if (!(f.have == f.want)) {
+            rl_set_error("group_set_member_hyper: %s is structural and must equal the group's (%g, the group has %g)", f.name, f.have, f.want);
+            return RLREP_ERR_ARG;
+        }
+    const struct { const char* name; float v; } lrs[] = {{"lr_feature", hyper->lr_feature}, {"lr_critic", hyper->lr_critic}, {"lr_actor", hyper->lr_actor}};
+    for (const auto& f : lrs)
+        if (!std::isfinite(f.v) || !(f.v > 0.f)) { rl_set_error("group_set_member_hyper: %s %g is not a finite positive learning rate", f.name, (double)f.v); return RLREP_ERR_ARG; }
+    if (!std::isfinite(hyper->discount)) { rl_set_error("group_set_member_hyper: discount %g is not finite", (double)hyper->discount); return RLREP_ERR_ARG; }
+    if (!(hyper->tau >= 0.f && hyper->tau <= 1.f)) { rl_set_error("group_set_member_hyper: tau %g outside [0, 1]", (double)hyper->tau); return RLREP_ERR_ARG; }
+    if (!(hyper->feature_tau >= 0.f && hyper->feature_tau <= 1.f)) { rl_set_error("group_set_member_hyper: feature_tau %g outside [0, 1]", (double)hyper->feature_tau); return RLREP_ERR_ARG; }
+    if (hyper->target_update_period < 1) { rl_set_error("group_set_member_hyper: target_update_period %d is below 1", hyper->target_update_period); return RLREP_ERR_ARG; }
+    rlrep_hyper h = *hyper;
+    h.world_size = ws;
+    // the member's optimizer records: lr, beta1, beta2, eps, tau of each of the four groups -- as rlrep_agent_create writes them (the step
+    // counters and the running powers stay); then its by-value record.  Both are read at the next launch: captured graphs need no re-capture.
+    struct Words { float lr, b1, b2, eps, tau; } w[4];
+    static_assert(offsetof(GroupCfg, tau) - offsetof(GroupCfg, lr) == 4 * sizeof(float), "GroupCfg words lr .. tau");
+    for (int q = 0; q < 4; ++q) {
+        w[q].lr = q == 1 ? h.lr_critic : q == 2 ? h.lr_actor : h.lr_feature;
+        w[q].b1 = h.beta1; w[q].b2 = h.beta2; w[q].eps = h.adam_eps;
+        w[q].tau = (q == 0) ? h.feature_tau : (q == 1) ? h.tau : 0.f;
+    }
+    const MemberHyper mh = member_hyper_of(h);
+    const long long d = (long long)member * ag->grp_stride;
+    hipStream_t sm = (hipStream_t)stream;
+    hipError_t e = hipSuccess;
+    for (int q = 0; q < 4 && e == hipSuccess; ++q)
+        e = hipMemcpyAsync((char*)&ag->adam_step[q].lr + d, &w[q], sizeof(Words), hipMemcpyHostToDevice, sm);
+    if (e == hipSuccess) e = hipMemcpyAsync((char*)ag->mhyp + d, &mh, sizeof(mh), hipMemcpyHostToDevice, sm);
+    if (e == hipSuccess) e = hipStreamSynchronize(sm);          // (the host words above live on this stack frame)
+    if (e != hipSuccess) { rl_set_error("group_set_member_hyper: %s", hipGetErrorString(e)); return RLREP_ERR_HIP; }
+    ag->grp_hyper[member] = h;
+    return 0;
+}
+int32_t rlrep_group_get_member_hyper(rlrep_agent* ag, int32_t member, rlrep_hyper* out) {
+    if (!ag || ag->members <= 0) { rl_set_error("group_get_member_hyper: not a seed group"); return RLREP_ERR_ARG; }
+    if (member < 0 || member >= ag->members) { rl_set_error("group_get_member_hyper: member %d outside [0, %d)", member, ag->members); return RLREP_ERR_ARG; }
+    if (!out) { rl_set_error("group_get_member_hyper: null output"); return RLREP_ERR_ARG; }
+    *out = ag->grp_hyper[member];
     return 0;
 }
 // [p, p + bytes) inside member 0's block [grp_lo, grp_lo + stride): what a group launch moves by r * stride must stay in member r's block

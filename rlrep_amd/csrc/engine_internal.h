@@ -14,6 +14,8 @@ struct rlrep_agent {
     int members = 0; long long grp_stride = 0; unsigned long long* grp_seeds = nullptr;
     const char* grp_lo = nullptr;          // member 0's lowest arena byte: its block is [grp_lo, grp_lo + grp_stride)
     long long grp_ring_stride = 0;         // bytes between two members' replay rings, as the last group train prologue was given
+    MemberHyper* mhyp = nullptr;           // by-value hyper record (kparams.h; workspace, static_state): member 0's, read by the group kernel forms only
+    std::vector<rlrep_hyper> grp_hyper;    // [members] each member's hyper-parameters (rlrep_group_set_member_hyper)
     int B = 0;
     int* steps = nullptr; GroupCfg* adam_step = nullptr; float* metrics = nullptr; float* obs_in = nullptr; float* act_out = nullptr;
     Slot slot[2];

@@ -20,6 +20,7 @@ struct RlGrp {
     long long stride;                   // bytes between two members' blocks (multiple of 256)
     long long ring_stride;              // bytes between two members' replay rings (train prologue only)
     const unsigned long long* seeds;    // [members] Philox seeds (device), train prologue only
+    const MemberHyper* hyp;             // member 0's by-value hyper-parameters (kparams.h); member r's lie r * stride further
 };
 extern "C" const RlGrp* rl_grp_active();
 // what a launcher without a group form returns while a group is active (the stage fails with this code: no member is left behind silently)

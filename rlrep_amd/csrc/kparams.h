@@ -117,6 +117,11 @@ struct FinTask {
     double* alpha_state; float lr, beta1, beta2, eps; int learn;
 };
 
+// A seed group member's by-value hyper-parameters (rlrep_group_set_member_hyper): the scalars the step programs otherwise carry BY VALUE in
+// member 0's records -- QHeadCritic::gamma, AdamTask::pol_period, FIN_ALPHA's FinTask::lr / learn.  One record per agent at a fixed
+// workspace offset (engine.hip static_state), so member r's is member 0's address + r * stride.  Only the group kernel forms read it.
+struct MemberHyper { float gamma; int pol_period; float alpha_lr; int learn; };
+
 // Metric finalisation + temperature update, run by ONE wave: the trailing block of the Adam launch, or (optimizer fused
 // into the weight-gradient launch) the extra trailing workgroup of that launch.
 // torch/optim/adam.py::_single_tensor_adam operation order; SURVEY Appendix A.11/A.12
@@ -135,8 +140,10 @@ template <bool GRP> __device__ __forceinline__ FinTask fin_record(const FinTask&
     if (g.alpha_state) g.alpha_state = (double*)((uintptr_t)g.alpha_state + (uintptr_t)mdelta);
     return g;
 }
+// hyp (GRP only): member 0's MemberHyper; FIN_ALPHA takes the temperature optimizer's lr and learn gate from the member's record, not from `f`
 template <bool GRP = false>
-__device__ inline void finalize_tasks(const FinTask* __restrict__ fin, int nfin, int lane, const DpPull* dp = nullptr, long long mdelta = 0) {
+__device__ inline void finalize_tasks(const FinTask* __restrict__ fin, int nfin, int lane, const DpPull* dp = nullptr, long long mdelta = 0,
+                                      const MemberHyper* hyp = nullptr) {
     for (int q = 0; q < nfin; ++q) {
         const FinTask f = fin_record<GRP>(fin[q], mdelta);
         if (f.kind == FIN_SUM) {
@@ -165,7 +172,12 @@ __device__ inline void finalize_tasks(const FinTask* __restrict__ fin, int nfin,
                 const float mean_c = s * f.scale;
                 const double alpha = exp(st[0]);
                 *f.out = (float)alpha * mean_c;       // alpha_loss (fp32 product as in the reference)
-                if (f.learn) {
+                float alr = f.lr; int learn = f.learn;
+                if constexpr (GRP) {
+                    const MemberHyper* mh = (const MemberHyper*)((uintptr_t)hyp + (uintptr_t)mdelta);
+                    alr = mh->alpha_lr; learn = mh->learn;
+                } else (void)hyp;
+                if (learn) {
                     const double g = (double)mean_c * alpha;
                     const double b1 = (double)f.beta1, b2 = (double)f.beta2;
                     st[3] += 1.0;
@@ -173,7 +185,7 @@ __device__ inline void finalize_tasks(const FinTask* __restrict__ fin, int nfin,
                     st[2] = st[2] * b2 + (1.0 - b2) * g * g;
                     const double bc1 = 1.0 - pow(b1, st[3]), bc2 = 1.0 - pow(b2, st[3]);
                     const double denom = sqrt(st[2]) / sqrt(bc2) + (double)f.eps;
-                    st[0] = st[0] - ((double)f.lr / bc1) * (st[1] / denom);
+                    st[0] = st[0] - ((double)alr / bc1) * (st[1] / denom);
                 }
                 *f.out2 = (float)exp(st[0]);          // info['alpha'] is read after the optimizer step
             }

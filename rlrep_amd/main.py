@@ -10,6 +10,10 @@ as {"step": t, "info/<key>": value} lines (and to tensorboardX with the referenc
 `--seeds 0,1,2,3` (sac and ctrlsac): one SACSeedBatch / CTRLSACSeedBatch trains every seed in the same launches, one environment per seed
 stepped in lockstep; each seed has its own np.random.RandomState(seed) for random and epsilon-greedy actions, its own evaluation and its own
 log directory.  ctrlsac takes the dimensions build_agent gives it (main.py:90-91).
+
+`--sweep key=v1,v2` (repeatable; with --seeds, or with --seed alone) adds hyper-parameter configurations: the group's members are
+product(configurations) x seeds, all trained in the same launches (SeedBatchMixin member_hyper).  A member logs to
+`log/<env>/<alg>/<dir>/<tag>/<seed>/metrics.jsonl`, tag = `key=value` joined by `_` (e.g. `lr=0.0001_tau=0.01`).
 """
 import argparse
 import json
@@ -69,8 +73,10 @@ def run(argv=None):
     p.add_argument('--eval_episodes', default=10, type=int)
     p.add_argument('--log_root', default='log')
     p.add_argument('--seeds', default=None, help='comma-separated seeds trained together (sac and ctrlsac only): rlrep_amd/agent/seed_batch.py')
+    p.add_argument('--sweep', action='append', default=None, metavar='KEY=V1,V2',
+                   help='hyper-parameter values trained together with the seeds (repeatable; members = product of the sweeps x seeds)')
     args = p.parse_args(argv)
-    if args.seeds is not None:
+    if args.seeds is not None or args.sweep:
         return run_seeds(args)
 
     env, eval_env = envs.make(args.env), envs.make(args.env)
@@ -147,13 +153,66 @@ class _MemberPolicy(object):
         return self.group.select_action(self.obs)[self.r]
 
 
+def _group_class(alg):
+    if alg == 'ctrlsac':
+        from rlrep_amd.agent.ctrlsac.seed_batch import CTRLSACSeedBatch
+        return CTRLSACSeedBatch
+    from rlrep_amd.agent.sac.seed_batch import SACSeedBatch
+    return SACSeedBatch
+
+
+def parse_sweeps(sweeps, alg, n_seeds):
+    """--sweep arguments -> [(tag, {key: value})] in product order (one ('', {}) without a sweep).  SystemExit on an unknown key, a key --alg
+    does not take, a bad or repeated value, or more members than a group holds."""
+    import itertools
+    if not sweeps:
+        return [('', {})]
+    cls = _group_class(alg)
+    known = ('lr', 'discount', 'tau', 'feature_tau', 'alpha', 'target_update_period', 'auto_entropy_tuning')
+    axes = []
+    for arg in sweeps:
+        key, eq, vals = str(arg).partition('=')
+        key = key.strip()
+        if not eq or not vals.strip():
+            raise SystemExit(f'--sweep {arg}: give KEY=V1,V2,..., e.g. --sweep lr=1e-4,3e-4')
+        if key not in known:
+            raise SystemExit(f'--sweep {arg}: unknown key {key!r} (sweepable: {", ".join(known)})')
+        if key not in cls.SWEEP_KEYS:
+            raise SystemExit(f'--sweep {arg}: {key} is not a hyper-parameter of --alg {alg} (it takes {", ".join(cls.SWEEP_KEYS)})')
+        if key in [k for k, _ in axes]:
+            raise SystemExit(f'--sweep {arg}: {key} is swept twice')
+        values = []
+        for v in vals.split(','):
+            try:
+                values.append(cls.normalise_hyper(key, v.strip(), '--sweep'))
+            except ValueError as e:
+                raise SystemExit(f'--sweep {arg}: {e}')
+        if len(set(values)) != len(values):
+            raise SystemExit(f'--sweep {arg}: repeated value')
+        axes.append((key, values))
+    configs = []
+    for combo in itertools.product(*[v for _, v in axes]):
+        cfg = dict(zip([k for k, _ in axes], combo))
+        configs.append(('_'.join(f'{k}={v}' for k, v in cfg.items()), cfg))
+    from rlrep_amd._lib import lib
+    cap = int(lib.rlrep_group_max_members())
+    if len(configs) * n_seeds > cap:
+        raise SystemExit(f'--sweep: {len(configs)} configurations x {n_seeds} seeds = {len(configs) * n_seeds} members, more than a group holds ({cap})')
+    return configs
+
+
 def run_seeds(args):
     """The loop of run() for several seeds at once: R environments in lockstep, one SACSeedBatch, one ReplayBufferGroup."""
-    seeds = [int(s) for s in str(args.seeds).split(',') if s.strip() != '']
+    seeds = [int(s) for s in str(args.seeds).split(',') if s.strip() != ''] if args.seeds is not None else [int(args.seed)]
     if not seeds or len(set(seeds)) != len(seeds):
         raise SystemExit(f'--seeds {args.seeds}: give distinct integer seeds, e.g. --seeds 0,1,2,3')
     if args.alg not in ('sac', 'ctrlsac'):
         raise SystemExit(f'--seeds: seed batches are built for --alg sac and ctrlsac only (got --alg {args.alg}); run one process per seed instead')
+    configs = parse_sweeps(args.sweep, args.alg, len(seeds))
+    swept = bool(args.sweep)
+    tags = [t for t, _ in configs for _ in seeds]
+    member_hyper = [cfg for _, cfg in configs for _ in seeds] if swept else None
+    seeds = [s for _ in configs for s in seeds]              # member = (configuration, seed), configurations outermost
     from rlrep_amd.utils.buffer_group import ReplayBufferGroup
     R = len(seeds)
     envs_, evals_ = [envs.make(args.env) for _ in seeds], [envs.make(args.env) for _ in seeds]
@@ -163,8 +222,8 @@ def run_seeds(args):
     rngs = [np.random.RandomState(s) for s in seeds]
     max_length = envs_[0]._max_episode_steps
     logs = []
-    for s in seeds:
-        path = os.path.join(args.log_root, args.env, args.alg, str(args.dir), str(s))
+    for tag, s in zip(tags, seeds):
+        path = os.path.join(args.log_root, args.env, args.alg, str(args.dir), *([tag] if swept else []), str(s))
         os.makedirs(path, exist_ok=True)
         logs.append(open(os.path.join(path, 'metrics.jsonl'), 'a'))
     space = envs_[0].action_space
@@ -174,10 +233,10 @@ def run_seeds(args):
     if args.alg == 'ctrlsac':
         from rlrep_amd.agent.ctrlsac.seed_batch import CTRLSACSeedBatch
         common.update(feature_dim=2048, hidden_dim=1024)                       # as build_agent (main.py:90-91)
-        agent = CTRLSACSeedBatch(seeds, state_dim, action_dim, space, extra_feature_steps=args.extra_feature_steps, **common)
+        agent = CTRLSACSeedBatch(seeds, state_dim, action_dim, space, extra_feature_steps=args.extra_feature_steps, member_hyper=member_hyper, **common)
     else:
         from rlrep_amd.agent.sac.seed_batch import SACSeedBatch
-        agent = SACSeedBatch(seeds, state_dim, action_dim, space, **common)
+        agent = SACSeedBatch(seeds, state_dim, action_dim, space, member_hyper=member_hyper, **common)
     replay = ReplayBufferGroup(R, state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)))
     policies = [_MemberPolicy(agent, r) for r in range(R)]
     evaluations = [[util.eval_policy(policies[r], evals_[r], args.eval_episodes)] for r in range(R)]

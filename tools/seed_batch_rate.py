@@ -6,6 +6,10 @@
 sac workloads: SACSeedBatch against SACAgent; ctrlsac workloads: CTRLSACSeedBatch against CTRLSACAgent(pipeline=False), the one-graph
 train() a ctrlsac group runs (the pipelined two-chain form is not built for groups).
 
+--sweep: the group is a hyper-parameter sweep (member r: seed r // 4, lr / tau / discount (ctrlsac: feature_tau) of configuration r % 4,
+SeedBatchMixin member_hyper), measured against a seed-only group of the same R and against R standalone agents built with each member's seed
+and hyper-parameters.
+
 Per R: the group's aggregate rate (R x calls/s), its graph's launch count per call, and the standalone agents' aggregate rate.  Protocol:
 --warmup calls (default 300), then the median of --windows windows (default 5) of --calls calls (default 500), timed by host wall clock
 around a device synchronisation."""
@@ -45,7 +49,10 @@ def main(argv=None):
     p.add_argument('--calls', type=int, default=500)
     p.add_argument('--windows', type=int, default=5)
     p.add_argument('--group-only', action='store_true', help='skip the standalone agents (a profiler run of the group alone)')
+    p.add_argument('--sweep', action='store_true', help='a hyper-parameter sweep group against a seed-only group and R standalone agents')
     a = p.parse_args(argv)
+    if a.sweep:
+        return sweep_main(a)
     from rlrep_amd.utils.buffer_group import ReplayBufferGroup
     alg, S, A, B, kw = bench.WORKLOADS[a.workload]
     alone_kw = {}
@@ -84,6 +91,63 @@ def main(argv=None):
         s_rate = _rate(alone_step, R, a.warmup, a.calls, a.windows)
         print(f'{R:>3} {g_rate:>16.0f} {launches:>14d} {s_rate:>23.0f} {g_rate / s_rate:>6.2f}', flush=True)
         del grp, agents, rings, alone_bufs
+        torch.cuda.empty_cache()
+
+
+def _sweep_members(alg, R):
+    """R (seed, member_hyper) pairs: four configurations x seeds (seed r // 4 ... every configuration once per seed), all distinct"""
+    cfgs = [dict(lr=1e-4, tau=0.005), dict(lr=3e-4, tau=0.01, discount=0.98), dict(lr=2e-4, tau=0.02, target_update_period=1),
+            dict(lr=5e-5, discount=0.95, target_update_period=3)]
+    if alg == 'ctrlsac':
+        for q, c in enumerate(cfgs):
+            c['feature_tau'] = 0.005 * (q + 1)
+    return [(r // len(cfgs), dict(cfgs[r % len(cfgs)])) for r in range(R)]
+
+
+def sweep_main(a):
+    from rlrep_amd.utils.buffer_group import ReplayBufferGroup
+    alg, S, A, B, kw = bench.WORKLOADS[a.workload]
+    alone_kw = {}
+    if alg == 'ctrlsac':
+        from rlrep_amd.agent.ctrlsac.ctrlsac_agent import CTRLSACAgent as Agent
+        from rlrep_amd.agent.ctrlsac.seed_batch import CTRLSACSeedBatch as Group
+        alone_kw = dict(pipeline=False)
+    else:
+        from rlrep_amd.agent.sac.sac_agent import SACAgent as Agent
+        from rlrep_amd.agent.sac.seed_batch import SACSeedBatch as Group
+    print(f'# {a.workload}: S={S} A={A} B={B} {kw}; sweep {Group.__name__} against a seed-only group and {Agent.__name__}({alone_kw}); '
+          f'{torch.cuda.get_device_name(0)}; warmup {a.warmup}, median of {a.windows} x {a.calls} calls')
+    print(f'{"R":>3} {"sweep train()/s":>16} {"seeds train()/s":>16} {"sweep/seeds":>12} {"launches/call":>14} {"R standalone train()/s":>23} {"sweep/alone":>12}')
+    for R in [int(x) for x in a.members.split(',')]:
+        members = _sweep_members(alg, R)
+        rings = ReplayBufferGroup(R, S, A, max_size=bench.REPLAY_N)
+        alone_bufs = []
+        for r in range(R):
+            buf, data = bench.synth_buffer(S, A, r)
+            rings.load(r, data['state'], data['action'], data['next_state'], data['reward'], data['done'])
+            alone_bufs.append(buf)
+        sweep = Group([s for s, _ in members], S, A, bench.Space(A), max_batch=B, member_hyper=[h for _, h in members], **kw)
+        w_rate = _rate(lambda: sweep.train(rings, B), R, a.warmup, a.calls, a.windows)
+        launches = sweep._graph_launches
+        del sweep
+        seeds = Group(list(range(R)), S, A, bench.Space(A), max_batch=B, **kw)
+        s_rate = _rate(lambda: seeds.train(rings, B), R, a.warmup, a.calls, a.windows)
+        assert seeds._graph_launches == launches
+        del seeds
+        if a.group_only:
+            print(f'{R:>3} {w_rate:>16.0f} {s_rate:>16.0f} {w_rate / s_rate:>12.3f} {launches:>14d}', flush=True)
+            continue
+        agents = []
+        for s, h in members:
+            torch.manual_seed(s)
+            agents.append(Agent(S, A, bench.Space(A), max_batch=B, seed=s, **alone_kw, **kw, **h))
+
+        def alone_step():
+            for ag, buf in zip(agents, alone_bufs):
+                ag.train(buf, B)
+        a_rate = _rate(alone_step, R, a.warmup, a.calls, a.windows)
+        print(f'{R:>3} {w_rate:>16.0f} {s_rate:>16.0f} {w_rate / s_rate:>12.3f} {launches:>14d} {a_rate:>23.0f} {w_rate / a_rate:>12.2f}', flush=True)
+        del agents, rings, alone_bufs
         torch.cuda.empty_cache()
 
 
