@@ -149,6 +149,7 @@ def _world():
 class SACAgent(object):
     ALG = 'sac'
     PREFETCH_CHAIN = True     # every pooled index key is a slot-0 minibatch, consumed in _plan() order
+    PREFETCH_POLICY_EARLY = True      # the policy forwards of the critic / actor steps may ride in the last feature step (rlrep_prefetch_policy_early)
     MODULES = ('critic', 'critic_target', 'actor')
     FEATURE_KEYS = ()
     CRITIC_KEYS = ('q_loss', 'q1', 'q2')
@@ -185,6 +186,11 @@ class SACAgent(object):
         self.feature_tau = 0.0
 
     def _finish_init(self, hip_kwargs):
+        # deferred critic / actor chain (vlsac / ctrlsac / spedersac; _train_graph_pipelined): 2 = the two chains on two streams, 0 = the
+        # sequential one-graph train().  Read once, here: the per-call paths do not touch os.environ
+        pipeline = os.environ.get('RLREP_PIPELINE', '2').strip()
+        if pipeline not in ('0', '2'):
+            raise ValueError(f'RLREP_PIPELINE={pipeline!r}: accepted values are 0 (sequential) and 2 (two streams, the default)')
         self.max_batch = int(hip_kwargs.get('max_batch', os.environ.get('RLREP_MAX_BATCH', 256)))
         self.world_size, self.rank = _world()
         # loopback=(LoopbackGroup, rank): this agent is one of several replicas inside ONE process (rlrep_amd/comm.py; tools/exp/dp_loopback.py, tests)
@@ -249,14 +255,12 @@ class SACAgent(object):
         self._next_key = {}
         self._early_key = None
         self.use_graph = bool(int(os.environ.get('RLREP_GRAPH', '1'))) and hip_kwargs.get('graph', True)
-        # critic / actor steps of train(t) as a graph branch beside the feature steps of train(t+1) (vlsac; _train_graph_pipelined)
-        self.use_pipeline = bool(int(os.environ.get('RLREP_PIPELINE', '1'))) and hip_kwargs.get('pipeline', True)
+        self.use_pipeline = pipeline == '2' and hip_kwargs.get('pipeline', True)
         # The two-chain schedule pays when train() calls follow each other; a caller that LOOKS at the critic / actor between two calls -- main.py's
         # loop: select_action before every train() -- ends the overlap each time, and what is left of the schedule is its cost (snapshot, event
         # hand-off between the streams: 466 us per call against 431 us for the one-graph sequential train(); tools/exp/rl_loop.py: 1 600 vs 1 880
         # iterations/s).  Both forms perform identical updates (tests), so train() picks per call: three calls in a row whose pair was waited
         # for before the next call -> the sequential graph; two calls in a row with nothing looked at in between -> back to the two chains.
-        self._pipeline_mode = int(os.environ.get('RLREP_PIPELINE', '2'))          # (read once: the per-call paths do not touch os.environ)
         self._stamp_on = _sw.opt('stamp') is not None
         self._adaptive = not _sw.off('adaptive_pipeline') and hip_kwargs.get('adaptive', 'pipeline' not in hip_kwargs)      # (an explicit pipeline= argument pins the form)
         self._looked, self._n_looked, self._n_b2b = False, 0, 0
@@ -381,34 +385,50 @@ class SACAgent(object):
         self.steps += 1
         if (self.steps & 31) == 0:
             self.core.exchange_check()           # (a word in mapped host memory: no synchronisation; a launch that saw a timeout applied nothing)
-        if self.use_graph and (not self._dp or self._fused_all):
-            if self.use_pipeline and self._feature_iters() > 0 and self.core.defer_supported():
-                if self._prefer_sequential():
-                    self.flush()
-                    out = self._train_graph(buffer, batch_size)
-                else:
-                    out = self._train_graph_pipelined(buffer, batch_size)
-                self._looked = False             # (flush() calls made by the call itself do not count)
-                return out
+        form = self._form()
+        if form == 'two_chains':
+            if self._prefer_sequential():
+                self.flush()
+                out = self._train_graph(buffer, batch_size)
+            else:
+                out = self._train_graph_pipelined(buffer, batch_size)
+            self._looked = False                 # (flush() calls made by the call itself do not count)
+            return out
+        if form == 'graph':
             return self._train_graph(buffer, batch_size)
-        if self.use_graph and self.use_graph_dp:
-            if self.use_pipeline and self.use_pipeline_dp and self._feature_iters() > 0 and self.ALG == 'vlsac' and self.core.defer_supported():
-                return self._train_graph_dp_pipelined(buffer, batch_size)
+        if form == 'dp_two_chains':
+            return self._train_graph_dp_pipelined(buffer, batch_size)
+        if form == 'dp_segments':
             return self._train_graph_dp(buffer, batch_size)
         return self._train_eager(buffer, batch_size)
 
     update = train      # BASELINE.json's north_star calls it agent.update()
+
+    def _form(self):
+        """The form the next train() takes: 'graph' (one hipGraph), 'two_chains' (the feature chain and the deferred critic / actor chain on
+        two streams; train() may still pick 'graph' per call), 'dp_segments' (data parallel: graph segments around the all-reduces, or one
+        graph that captured them), 'dp_two_chains' (both chains cut into segments, one communicator each) or 'eager'."""
+        if self.use_graph and (not self._dp or self._fused_all):
+            if self.use_pipeline and self._feature_iters() > 0 and self.core.defer_supported():
+                return 'two_chains'
+            return 'graph'
+        if self.use_graph and self.use_graph_dp:
+            if self.use_pipeline and self.use_pipeline_dp and self._feature_iters() > 0 and self.ALG == 'vlsac' and self.core.defer_supported():
+                return 'dp_two_chains'
+            return 'dp_segments'
+        return 'eager'
 
     def prepare(self, buffer, batch_size):
         """Capture the hipGraphs the next train(buffer, batch_size) will replay, WITHOUT launching anything of a train().  Several replicas in
         one process (the loopback form: rlrep_amd/comm.py LoopbackGroup) must build their graphs one after the other -- a capture synchronises
         the device, which would wait for a peer's optimizer launch that in turn waits for this replica's -- and replay them side by side
         afterwards.  No-op for the forms that are not whole graphs."""
-        if not (self.use_graph and (not self._dp or self._fused_all)):
+        form = self._form()
+        if form not in ('graph', 'two_chains'):
             return
         self._prepare_only = True
         try:
-            if self.use_pipeline and self._feature_iters() > 0 and self.core.defer_supported():
+            if form == 'two_chains':
                 self._train_graph_pipelined(buffer, batch_size)         # (the two-chain form ...
             self._train_graph(buffer, batch_size)                       #  ... and the one-graph form train() switches to for a caller that looks at the actor between calls)
         finally:
@@ -594,22 +614,17 @@ class SACAgent(object):
         """(index draws, normal draws) of one train(): lists of keys / (key, shape), in consumption order."""
         return ['s0'], [('crit', (B, self.action_dim)), ('act', (B, self.action_dim))]
 
+    def _pool_sizes(self, B):
+        """(index pool, noise pool) lengths of one train() at batch size B"""
+        idx_keys, eps_specs = self._plan(B)
+        return len(idx_keys) * B, sum(int(np.prod(sh)) for _, sh in eps_specs)
+
     def _fill_pools(self, buffer, B, g):
         idx_keys, eps_specs = self._plan(B)
-        ni = len(idx_keys) * B
-        ne = sum(int(np.prod(sh)) for _, sh in eps_specs)
+        ni, ne = self._pool_sizes(B)
         ipool = self._buf('pool_idx', (ni,), torch.int32)
         epool = self._buf('pool_eps', (ne,))
-        if g and _sw.off('prologue'):
-            self.core.fill_indices_dev(ipool, buffer.size_dev(), self._seed, 1 << 40)
-            self.core.fill_normal_dev(epool, 1.0, self._seed, 2 << 40)
-        elif g:
-            # one launch: steps += 1, both pools and the gather of the first minibatch (first B pool indices)
-            self.core.train_prologue(buffer.ring, buffer.size_dev(), ipool, epool, self._seed, 1 << 40, 2 << 40, B)
-        else:
-            self._ctr += 1
-            self.core.fill_indices(ipool, buffer.size, self._seed, (1 << 40) + self._ctr)
-            self.core.fill_normal(epool, 1.0, self._seed, (2 << 40) + self._ctr)
+        self._draw_pools(buffer, B, g, ipool, epool)
         self._pool = {}
         for q, k in enumerate(idx_keys):
             self._pool['idx_' + k] = ipool[q * B:(q + 1) * B]
@@ -622,8 +637,21 @@ class SACAgent(object):
             self._pool['eps_' + k] = epool[o:o + n].view(*sh)
             o += n
         # the critic / actor steps reuse the last feature minibatch: both policy forwards can ride in its feature step
-        self._early_key = idx_keys[-1] if (g and self.PREFETCH_CHAIN and self._feature_iters() > 0
+        self._early_key = idx_keys[-1] if (g and self.PREFETCH_CHAIN and self.PREFETCH_POLICY_EARLY and self._feature_iters() > 0
                                            and 'eps_crit' in self._pool and 'eps_act' in self._pool) else None
+
+    def _draw_pools(self, buffer, B, g, ipool, epool):
+        """The launches that fill the index and noise pools of one train()."""
+        if g and _sw.off('prologue'):
+            self.core.fill_indices_dev(ipool, buffer.size_dev(), self._seed, 1 << 40)
+            self.core.fill_normal_dev(epool, 1.0, self._seed, 2 << 40)
+        elif g:
+            # one launch: steps += 1, both pools and the gather of the first minibatch (first B pool indices)
+            self.core.train_prologue(buffer.ring, buffer.size_dev(), ipool, epool, self._seed, 1 << 40, 2 << 40, B)
+        else:
+            self._ctr += 1
+            self.core.fill_indices(ipool, buffer.size, self._seed, (1 << 40) + self._ctr)
+            self.core.fill_normal(epool, 1.0, self._seed, (2 << 40) + self._ctr)
 
     def _prefetch_chain(self, idx_keys):
         """key -> the key whose gather (same slot) rides in the optimizer launch of the step that consumes `key`."""
@@ -729,6 +757,19 @@ class SACAgent(object):
         finally:
             self.core.images_managed(False)
 
+    @contextlib.contextmanager
+    def _history_capture(self):
+        """Around the capture of a whole train() (one graph, or its segments): the call's metrics are filed in the library's history ring by
+        the last launch of the graph (rlrep_history) and fetched when the returned dict is read -- no snapshot launch per call (sac: 10 120 ->
+        10 600 train()/s).  RLREP_DISABLE=info_history: a clone per call."""
+        self._hist = not _sw.off('info_history')
+        self.core.history(self._hist)
+        try:
+            yield
+        finally:
+            self.core.history(False)
+        self._hist_n = self.core.history_seq() if self._hist else 0           # (synchronises; once per capture)
+
     def _sync_images(self):
         """Before replaying graphs that were captured with managed images: if anything but such a graph may have written critic /
         critic_target since the images were last known to be current -- an eager step method, a checkpoint load, any torch write into the
@@ -791,20 +832,47 @@ class SACAgent(object):
         self._body(buffer, B, False)
         return self.core.info()
 
+    def _capture_prologue(self, buffer, B, cached_key, flush=False, refresh_on=None):
+        """The head of every graph form of train(): bring the buffer's device rows and size scalar up to date (on stream `refresh_on`; the
+        caller's by default), and return the cache key of (buffer, B) when the form's graphs, captured for `cached_key`, cannot serve this
+        call -- None when they can.  Before such a capture: `flush` (the two-chain forms) finishes the pair still in flight; one eager gather
+        sizes the library's tables for B outside any capture (it re-uploads them with blocking copies when the batch size changes); the
+        pools are allocated outside any capture too (no launch: the train prologue would count a step and draw from the generator)."""
+        if refresh_on is None:
+            buffer.flush()
+            buffer.size_dev()
+        else:
+            with _on_stream(refresh_on):
+                buffer.flush()
+                buffer.size_dev()
+        key = self._graph_cache_key(buffer, B)
+        if key == cached_key:
+            return None
+        if flush:
+            self.flush()
+        self._sample_into(buffer, B, 'warm', 0, False)
+        ni, ne = self._pool_sizes(B)
+        self._buf('pool_idx', (ni,), torch.int32)
+        self._buf('pool_eps', (ne,))
+        torch.cuda.synchronize()
+        return key
+
+    @staticmethod
+    def _replay(items):
+        """Replay a segmented train() chain: ('graph', g) items are hipGraph segments, ('coll', fn) items the eager collectives between them."""
+        for kind, x in items:
+            if kind == 'graph':
+                x.replay()
+            else:
+                x()
+
     def _train_graph_dp(self, buffer, B):
         """world_size > 1: the launches between two gradient all-reduces are captured as separate hipGraphs
         (7 for vlsac) and replayed around eager RCCL all-reduces."""
         import torch.distributed as dist
-        buffer.flush()
-        buffer.size_dev()
-        key = self._graph_cache_key(buffer, B)
-        if self._graph is None or self._graph_key != key:
+        key = self._capture_prologue(buffer, B, None if self._graph is None else self._graph_key)
+        if key is not None:
             with _no_gc():          # (a cyclic-GC pass inside a capture may run destructors that touch the device: see _no_gc)
-                self._sample_into(buffer, B, 'warm', 0, False)
-                idx_keys, eps_specs = self._plan(B)            # allocate the pools outside any capture (no launch: the train
-                self._buf('pool_idx', (len(idx_keys) * B,), torch.int32)   # prologue would count a step and draw from the generator)
-                self._buf('pool_eps', (sum(int(np.prod(sh)) for _, sh in eps_specs),))
-                torch.cuda.synchronize()
                 s = torch.cuda.Stream()
                 s.wait_stream(torch.cuda.current_stream())
                 self._seg_capture_colls = self.capture_collectives and dist.is_initialized() and dist.get_backend() == 'nccl'
@@ -814,36 +882,17 @@ class SACAgent(object):
                     # every rank builds its graph at the same train() call, so this is a matched collective
                     dist.all_reduce(torch.zeros(1, device=self.core.device))
                     torch.cuda.synchronize()
-                self._hist = not _sw.off('info_history')      # see _train_graph
-                self.core.history(self._hist)
                 try:
-                    with torch.cuda.stream(s):
-                        first = torch.cuda.CUDAGraph()
-                        # thread-local capture mode: the process group's watchdog thread may query events while we capture
-                        first.capture_begin(capture_error_mode='thread_local')
-                        self._seg = ([], first)
-                        try:
-                            self._body(buffer, B, True)
-                            segs, cur = self._seg
-                            self._seg = None
-                            cur.capture_end()
-                            segs.append(('graph', cur))
-                        finally:
-                            self.core.history(False)
-                            self._abort_open_capture()
+                    with self._history_capture(), torch.cuda.stream(s):
+                        segs = self._capture_segments(lambda: self._body(buffer, B, True))
                     torch.cuda.current_stream().wait_stream(s)
                     torch.cuda.synchronize()
                 except Exception as e:
                     self._raise_capture_hint(e)
                 self._graph, self._graph_key = segs, key
-                self._hist_n = self.core.history_seq() if self._hist else 0
                 self._fresh_dp_graph = True
         try:
-            for kind, x in self._graph:
-                if kind == 'graph':
-                    x.replay()
-                else:
-                    x()
+            self._replay(self._graph)
             if self._fresh_dp_graph:                  # the first replay of a newly built graph is checked to the end (once per capture)
                 self._fresh_dp_graph = False
                 torch.cuda.synchronize()
@@ -857,10 +906,10 @@ class SACAgent(object):
     # train(t) = feature steps(t) -> critic(t) -> actor(t).  Feature steps read and write (encoder, decoder, f, f_target); critic
     # and actor read f_target / the last minibatch / their noise and write (critic, critic_target, actor, log_alpha).  With those
     # reads snapshotted (rlrep_defer_snapshot) the critic and actor steps of train(t) are independent of the feature steps of
-    # train(t+1), and the steady-state graph runs them as TWO CONCURRENT BRANCHES: the dependent-launch chain per train() drops
+    # train(t+1), and the two run as TWO CONCURRENT CHAINS on two streams: the dependent-launch chain per train() drops
     # from 71 launches to max(48 feature, 25 critic+actor).  Every parameter sees exactly the updates, in exactly the order, of
     # the sequential train(); `flush()` (called by everything that looks at the critic / actor: select_action, checkpoints,
-    # reading a returned info dict, the eager step methods) runs the one pending critic+actor pair.
+    # reading a returned info dict, the eager step methods) waits for the one pending critic+actor pair.
     def _feature_part(self, buffer, B, snap_set=None):
         self._pool = None
         self._next_key = {}
@@ -901,103 +950,78 @@ class SACAgent(object):
                 return                      # the write is issued ON the feature stream: ordered behind the chain by the stream itself
             cur.wait_event(P['last_f'])
 
+    def _run_chains(self, P, k, fs, ca, replay):
+        """What both two-chain forms do once their waits for set k (= t % nset) are issued: the feature chain `fs` on the feature stream, then
+        the critic / actor chain `ca` on its own stream behind the snapshot; replay(x) runs one chain."""
+        s_f, s_ca = P['s_f'], P['s_ca']
+        P['t'] += 1
+        with _on_stream(s_f):
+            replay(fs)
+            P['ev_snap'][k].record(s_f)
+        P['last_f'] = P['ev_snap'][k]
+        with _on_stream(s_ca):
+            s_ca.wait_event(P['ev_snap'][k])
+            replay(ca)
+            P['ev_ca'][k].record(s_ca)
+        P['used'][k] = True
+        self._pending = 2
+        return self.core.info(lazy_source=self._flushed_metrics, early=(self.FEATURE_KEYS, self._feature_metrics_of(P['ev_snap'][k])))
+
     def _train_graph_pipelined(self, buffer, B):
         self._hook_buffer(buffer)
-        P0 = self._pipe
-        if P0 is not None and P0.get('mode') == 2 and self._pending == 2:
-            # rows staged by add() since the last call and the size scalar are written ON THE FEATURE STREAM: behind the chain that may
-            # still be sampling from the ring, in front of the one this call launches -- ordered by the stream, no cross-stream wait.  (On the
-            # caller's stream the write had to wait for the chain in flight: a barrier packet parked in the caller's queue for most of every
-            # period, which taxes both chains' launches -- DESIGN.md 5.4; add() + train() in a loop: 2 650 -> 3 360 train()/s, tools/exp/add_train_loop.py.)
-            e0 = getattr(buffer, 'device_epoch', None)
-            with _on_stream(P0['s_f']):
-                buffer.flush()
-                buffer.size_dev()
-            cur_id = _raw_stream()
-            if e0 is not None and P0.get('seen') == (e0, cur_id):
-                P0['seen'] = (buffer.device_epoch, cur_id)        # our own writes need no wait for the caller's stream
-        else:
-            buffer.flush()
-            buffer.size_dev()
-        key = self._graph_cache_key(buffer, B)
-        c = self.core
-        if self._pipe is None or self._pipe['key'] != key:
-            with _no_gc(), self._managed_images():          # (a cyclic-GC pass inside a capture may run destructors that touch the device: see _no_gc)
-                self.flush()
-                self._sample_into(buffer, B, 'warm', 0, False)      # sizes the library's tables for B outside any capture
-                idx_keys, eps_specs = self._plan(B)
-                self._buf('pool_idx', (len(idx_keys) * B,), torch.int32)
-                self._buf('pool_eps', (sum(int(np.prod(sh)) for _, sh in eps_specs),))
-                torch.cuda.synchronize()
-                mode = int(os.environ.get('RLREP_PIPELINE', '2'))
-                s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
-                P = dict(key=key, mode=mode, t=0)
-                if mode == 1:
-                    # one graph per train(): the two branches inside it (snapshot set 0 only).  In-graph branches cost ~2.6 us per launch
-                    # pair on this runtime (tools/exp/twochains.hip); kept as the single-stream form.
-                    first, steady, tail = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(first, stream=s1):
-                        ec, ea = self._feature_part(buffer, B)
-                        c.defer_snapshot(ec, ea, 0)
-                        c.end_train()
-                    with torch.cuda.graph(steady, stream=s1):
-                        fork = torch.cuda.Event()
-                        fork.record()
-                        s2.wait_event(fork)
-                        c.deferred_critic_actor(0)                      # branch 1 (s1): critic + actor of the previous train()
-                        with torch.cuda.stream(s2):                      # branch 2 (s2): this train()'s feature steps
-                            ec, ea = self._feature_part(buffer, B)
-                            join = torch.cuda.Event()
-                            join.record()
-                        torch.cuda.current_stream().wait_event(join)
-                        c.defer_snapshot(ec, ea, 0)
-                        c.end_train()
-                    with torch.cuda.graph(tail, stream=s1):
-                        c.deferred_critic_actor(0)
-                    P.update(first=first, steady=steady, tail=tail)
-                else:
-                    # two streams that were TIMED to be concurrent; train(t) uses snapshot set t % nset:
-                    #   stream F : [feature steps(t) + snapshot(t -> set)]            after the critic/actor pair of t-2 (same set)
-                    #   stream CA: [critic + actor(t) from set]                       after snapshot(t)
-                    from rlrep_amd._lib import lib as _l, front_end_counts as _fe
-                    fs, ca = [], []
-                    n0, f0 = _l.rlrep_launch_counter(), _fe()
-                    nset = min(c.defer_supported(), max(2, int(_sw.opt('defer_sets', '3'))))
-                    for k in range(nset):
-                        g = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(g, stream=s1):
-                            self._stamp(1)
-                            ec, ea = self._feature_part(buffer, B, snap_set=k)
-                            c.defer_snapshot(ec, ea, k)
-                            c.end_train()
-                            self._stamp(2)
-                        fs.append(g)
-                    n1 = _l.rlrep_launch_counter()
-                    for k in range(nset):
-                        g = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(g, stream=s1):
-                            self._stamp(3)
-                            c.deferred_critic_actor(k)
-                            self._stamp(4)
-                        ca.append(g)
-                    P['launches'] = ((n1 - n0) // nset, (_l.rlrep_launch_counter() - n1) // nset)      # kernels in the feature / critic+actor graph
-                    f1 = _fe()
-                    P['front_ends'] = {k: (f1[k] - f0[k]) // nset for k in f1}      # 16-row tile engine launches of one train() per front end
-                    s_ca, s_f = self._stream_pair()
-                    P.update(fs=fs, ca=ca, s_ca=s_ca, s_f=s_f, nset=nset, ev_snap=[torch.cuda.Event() for _ in range(nset)],
-                             ev_ca=[torch.cuda.Event() for _ in range(nset)], used=[False] * nset)
-                self._pipe = P
         P = self._pipe
+        # while a pair is in flight, rows staged by add() since the last call and the size scalar are written ON THE FEATURE STREAM: behind the
+        # chain that may still be sampling from the ring, in front of the one this call launches -- ordered by the stream, no cross-stream wait.
+        # (On the caller's stream the write had to wait for the chain in flight: a barrier packet parked in the caller's queue for most of every
+        # period, which taxes both chains' launches -- DESIGN.md 5.4; add() + train() in a loop: 2 650 -> 3 360 train()/s, tools/exp/add_train_loop.py.)
+        s_rows = P['s_f'] if (P is not None and P['mode'] == 2 and self._pending == 2) else None
+        e0 = getattr(buffer, 'device_epoch', None)
+        key = self._capture_prologue(buffer, B, P and P['key'], flush=True, refresh_on=s_rows)
+        if s_rows is not None:
+            cur_id = _raw_stream()
+            if e0 is not None and P.get('seen') == (e0, cur_id):
+                P['seen'] = (buffer.device_epoch, cur_id)        # our own writes need no wait for the caller's stream
+        c = self.core
+        if key is not None:
+            with _no_gc(), self._managed_images():          # (a cyclic-GC pass inside a capture may run destructors that touch the device: see _no_gc)
+                # two streams that were TIMED to be concurrent; train(t) uses snapshot set t % nset:
+                #   stream F : [feature steps(t) + snapshot(t -> set)]            after the critic/actor pair of t-2 (same set)
+                #   stream CA: [critic + actor(t) from set]                       after snapshot(t)
+                from rlrep_amd._lib import lib as _l, front_end_counts as _fe
+                s1 = torch.cuda.Stream()
+                P = dict(key=key, mode=2, t=0)
+                fs, ca = [], []
+                n0, f0 = _l.rlrep_launch_counter(), _fe()
+                nset = min(c.defer_supported(), max(2, int(_sw.opt('defer_sets', '3'))))
+                for k in range(nset):
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, stream=s1):
+                        self._stamp(1)
+                        ec, ea = self._feature_part(buffer, B, snap_set=k)
+                        c.defer_snapshot(ec, ea, k)
+                        c.end_train()
+                        self._stamp(2)
+                    fs.append(g)
+                n1 = _l.rlrep_launch_counter()
+                for k in range(nset):
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g, stream=s1):
+                        self._stamp(3)
+                        c.deferred_critic_actor(k)
+                        self._stamp(4)
+                    ca.append(g)
+                P['launches'] = ((n1 - n0) // nset, (_l.rlrep_launch_counter() - n1) // nset)      # kernels in the feature / critic+actor graph
+                f1 = _fe()
+                P['front_ends'] = {k: (f1[k] - f0[k]) // nset for k in f1}      # 16-row tile engine launches of one train() per front end
+                s_ca, s_f = self._stream_pair()
+                P.update(fs=fs, ca=ca, s_ca=s_ca, s_f=s_f, nset=nset, ev_snap=[torch.cuda.Event() for _ in range(nset)],
+                         ev_ca=[torch.cuda.Event() for _ in range(nset)], used=[False] * nset)
+                self._pipe = P
         if self._prepare_only:
             return None
         self._sync_images()
-        if P['mode'] == 1:
-            (P['steady'] if self._pending else P['first']).replay()
-            self._pending = True
-            return self.core.info(lazy_source=self._flushed_metrics)
         k = P['t'] % P['nset']
-        P['t'] += 1
-        s_ca, s_f = P['s_ca'], P['s_f']
+        s_f = P['s_f']
         cur = _current_stream()
         # replay rows staged by ReplayBuffer.add() land on the caller's stream: order the feature chain after them -- but only when the
         # buffer has enqueued something since the last call (or the chains were idle): the event record + wait pair is ~5 us of the
@@ -1008,19 +1032,9 @@ class SACAgent(object):
             P['seen'] = seen
         # (the critic / actor stream needs no wait of its own for the caller's stream: its chain starts behind the snapshot event, which the
         #  feature stream records after a chain that has just been ordered behind the caller's stream)
-        with _on_stream(s_f):
-            if P['used'][k]:
-                self._wait_set_free(P, k, s_f)
-            P['fs'][k].replay()
-            P['ev_snap'][k].record(s_f)
-            P['last_f'] = P['ev_snap'][k]
-        with _on_stream(s_ca):
-            s_ca.wait_event(P['ev_snap'][k])
-            P['ca'][k].replay()
-            P['ev_ca'][k].record(s_ca)
-        P['used'][k] = True
-        self._pending = 2
-        return self.core.info(lazy_source=self._flushed_metrics, early=(self.FEATURE_KEYS, self._feature_metrics_of(P['ev_snap'][k])))
+        if P['used'][k]:
+            self._wait_set_free(P, k, s_f)
+        return self._run_chains(P, k, P['fs'][k], P['ca'][k], torch.cuda.CUDAGraph.replay)
 
     # ---- data parallel + deferred critic / actor chain ---------------------------------------------------------------------------
     # The two launch chains of the pipelined mode, each cut into hipGraph segments at its gradient all-reduces (feature chain: 4,
@@ -1031,6 +1045,7 @@ class SACAgent(object):
     # rank that reads its metrics while the others do not cannot desynchronise the ranks.
 
     def _capture_segments(self, fn):
+        # thread-local capture mode: the process group's watchdog thread may query events while we capture
         first = torch.cuda.CUDAGraph()
         first.capture_begin(capture_error_mode='thread_local')
         self._seg = ([], first)
@@ -1060,23 +1075,17 @@ class SACAgent(object):
             import torch.distributed as dist
             self._pg_ca = dist.new_group()             # collective: every rank reaches its first pipelined train() (same program)
         self._hook_buffer(buffer)
-        buffer.flush()
-        buffer.size_dev()
-        key = self._graph_cache_key(buffer, B)
+        P = self._pipe
+        key = self._capture_prologue(buffer, B, P and P['key'], flush=True)
         c = self.core
-        if self._pipe is None or self._pipe['key'] != key:
+        if key is not None:
             with _no_gc():          # (a cyclic-GC pass inside a capture may run destructors that touch the device: see _no_gc)
-                self.flush()
-                self._sample_into(buffer, B, 'warm', 0, False)
-                idx_keys, eps_specs = self._plan(B)
-                self._buf('pool_idx', (len(idx_keys) * B,), torch.int32)
-                self._buf('pool_eps', (sum(int(np.prod(sh)) for _, sh in eps_specs),))
                 import torch.distributed as dist
                 self._seg_capture_colls = self.capture_collectives and dist.is_initialized() and dist.get_backend() == 'nccl'
                 if self._seg_capture_colls:          # both communicators exist before the captures begin (see _train_graph_dp)
                     dist.all_reduce(torch.zeros(1, device=c.device))
                     dist.all_reduce(torch.zeros(1, device=c.device), group=self._pg_ca)
-                torch.cuda.synchronize()
+                    torch.cuda.synchronize()
                 cap = torch.cuda.Stream()
                 cap.wait_stream(torch.cuda.current_stream())
                 fs, cs = [], []
@@ -1099,35 +1108,22 @@ class SACAgent(object):
                 torch.cuda.current_stream().wait_stream(cap)
                 torch.cuda.synchronize()
                 s_ca, s_f = self._stream_pair()
-                self._pipe = dict(key=key, mode=3, t=0, nset=nset, host_wait=nset == 3, fs=fs, cs=cs, s_ca=s_ca, s_f=s_f,
-                                  ev_snap=[torch.cuda.Event() for _ in range(nset)], ev_ca=[torch.cuda.Event() for _ in range(nset)], used=[False] * nset)
-        P = self._pipe
+                self._pipe = P = dict(key=key, mode=3, t=0, nset=nset, host_wait=nset == 3, fs=fs, cs=cs, s_ca=s_ca, s_f=s_f,
+                                      ev_snap=[torch.cuda.Event() for _ in range(nset)], ev_ca=[torch.cuda.Event() for _ in range(nset)],
+                                      used=[False] * nset)
         k = P['t'] % P['nset']
-        P['t'] += 1
         s_ca, s_f = P['s_ca'], P['s_f']
         cur = _current_stream()
         s_f.wait_stream(cur)
         if not self._pending:
             s_ca.wait_stream(cur)
         if P['used'][k]:
-            if P.get('host_wait'):
+            if P['host_wait']:
                 P['ev_ca'][k].synchronize()                # (train t-3: long done)
             else:
                 s_f.wait_event(P['ev_ca'][k])              # the pair that read this snapshot set last (train t-2); a stream wait here: the
                                                            # host, which issues 14 items per call in this form, must keep its run-ahead
-        with _on_stream(s_f):
-            for kind, x in P['fs'][k]:
-                x.replay() if kind == 'graph' else x()
-            P['ev_snap'][k].record(s_f)
-        P['last_f'] = P['ev_snap'][k]
-        with _on_stream(s_ca):
-            s_ca.wait_event(P['ev_snap'][k])
-            for kind, x in P['cs'][k]:
-                x.replay() if kind == 'graph' else x()
-            P['ev_ca'][k].record(s_ca)
-        P['used'][k] = True
-        self._pending = 2
-        return self.core.info(lazy_source=self._flushed_metrics, early=(self.FEATURE_KEYS, self._feature_metrics_of(P['ev_snap'][k])))
+        return self._run_chains(P, k, P['fs'][k], P['cs'][k], self._replay)
 
     @staticmethod
     def _graph_cache_key(buffer, B):
@@ -1156,7 +1152,7 @@ class SACAgent(object):
     def _prefer_sequential(self):
         """Per-call choice between the two-chain and the one-graph form of train() (see __init__): has the caller been waiting for the critic /
         actor pair between the calls?"""
-        if not self._adaptive or self._pipeline_mode == 1:
+        if not self._adaptive:
             return False
         if self._looked:
             self._n_looked, self._n_b2b = min(self._n_looked + 1, 8), 0
@@ -1167,10 +1163,10 @@ class SACAgent(object):
         return self._n_looked >= 3
 
     def flush(self):
-        """Finish the critic + actor steps of the last pipelined train() (no-op otherwise)."""
+        """Finish the critic + actor steps of the last two-chain train() (no-op otherwise)."""
         self._looked = True
         self.core.exchange_check()               # a peer that never arrived (bounded waits of the in-launch gradient exchange): raise, do not train on
-        if self._pending == 2:                         # two-stream forms: the pair is already in flight on its own streams
+        if self._pending == 2:                         # the pair is already in flight on its own streams
             self._pending = False
             P = self._pipe
             # Waited for on the HOST (every caller of flush() is about to read results anyway).  A stream-level wait here -- a barrier
@@ -1180,38 +1176,22 @@ class SACAgent(object):
             # The critic / actor chain of the last call is the last thing in flight: its feature chain ended before it started.
             P['ev_ca'][(P['t'] - 1) % P['nset']].synchronize()
             self.core.exchange_check()           # ... and again behind the wait: a timeout raised by the launches that were still running (advisor r05)
-        elif self._pending:
-            self._pending = False
-            self._pipe['tail'].replay()
 
     def _train_graph(self, buffer, B):
-        buffer.flush()
-        buffer.size_dev()
-        key = self._graph_cache_key(buffer, B)
-        if self._graph is None or self._graph_key != key:
+        key = self._capture_prologue(buffer, B, None if self._graph is None else self._graph_key)
+        if key is not None:
             with _no_gc():          # (a cyclic-GC pass inside a capture may run destructors that touch the device: see _no_gc)
-                # size the library's tables for B outside the capture (it re-uploads them with blocking copies
-                # when the batch size changes), then capture the whole train() into one hipGraph
-                self._sample_into(buffer, B, 'warm', 0, False)
-                torch.cuda.synchronize()
+                # the whole train() as one hipGraph
                 from rlrep_amd._lib import lib as _l, front_end_counts as _fe
                 s = torch.cuda.Stream()
                 g = torch.cuda.CUDAGraph()
                 n0, f0 = _l.rlrep_launch_counter(), _fe()
-                # the call's metrics are filed in the library's history ring by the last launch of the graph (rlrep_history) and fetched when the
-                # returned dict is read: no snapshot launch per call (sac: 10 120 -> 10 600 train()/s).  RLREP_DISABLE=info_history: a clone per call.
-                self._hist = not _sw.off('info_history')
-                self.core.history(self._hist)
-                try:
-                    with self._managed_images(), torch.cuda.graph(g, stream=s):
-                        self._body(buffer, B, True)
-                finally:
-                    self.core.history(False)
+                with self._history_capture(), self._managed_images(), torch.cuda.graph(g, stream=s):
+                    self._body(buffer, B, True)
                 self._graph, self._graph_key = g, key
                 self._graph_launches = _l.rlrep_launch_counter() - n0
                 f1 = _fe()
                 self._graph_front_ends = {k: f1[k] - f0[k] for k in f1}
-                self._hist_n = self.core.history_seq() if self._hist else 0           # (synchronises; once per capture)
         if self._prepare_only:
             return None
         self._sync_images()

@@ -95,6 +95,7 @@ class SeedBatchMixin(object):
     # constructor kwargs a member may override (member_hyper): what the group launches read per member (include/rlrep.h
     # rlrep_group_set_member_hyper) or what only initialisation uses (alpha)
     SWEEP_KEYS = ('lr', 'discount', 'tau', 'alpha', 'target_update_period', 'auto_entropy_tuning')
+    PREFETCH_POLICY_EARLY = False         # no group form of rlrep_prefetch_policy_early (the library refuses it)
 
     @classmethod
     def _agent_class(cls):
@@ -190,10 +191,6 @@ class SeedBatchMixin(object):
         check(lib.rlrep_group_set_seeds(self.core.h, C.cast(seeds_arr, C.c_void_p), self.R, _stream()), 'group_set_seeds')
 
     # ---- construction -----------------------------------------------------------------------------------------------------------------
-    def _pool_sizes(self, B):
-        idx_keys, eps_specs = self._plan(B)
-        return len(idx_keys) * B, sum(int(np.prod(sh)) for _, sh in eps_specs)
-
     def _make_core(self, dims, hyper):
         ni, ne = self._pool_sizes(self.max_batch)
         # the index and noise pools of a train() sit behind the arenas of every member: the prologue writes member r's at the member stride
@@ -246,27 +243,13 @@ class SeedBatchMixin(object):
         off = c._skew + c.member_extra_offset + (0 if key == 'pool_idx' else ((4 * ni + 255) & ~255))
         return c._block[off:off + 4 * n].view(dtype).view(*shape)
 
-    def _fill_pools(self, buffer, B, g):
+    def _draw_pools(self, buffer, B, g, ipool, epool):
         if not g:
             raise RuntimeError(f'{type(self).__name__}: eager train() forms are not built for seed groups')
-        idx_keys, eps_specs = self._plan(B)
-        ni = len(idx_keys) * B
-        ne = sum(int(np.prod(sh)) for _, sh in eps_specs)
-        ipool = self._buf('pool_idx', (ni,), torch.int32)
-        epool = self._buf('pool_eps', (ne,))
         check(lib.rlrep_group_train_prologue(self.core.h, C.c_void_p(buffer.ring.data_ptr()), 4 * buffer.ring_stride, C.c_void_p(buffer.size_dev().data_ptr()),
-                                             C.c_void_p(ipool.data_ptr()), ni, C.c_void_p(epool.data_ptr()), ne, 1 << 40, 2 << 40, B, _stream()),
+                                             C.c_void_p(ipool.data_ptr()), ipool.numel(), C.c_void_p(epool.data_ptr()), epool.numel(),
+                                             1 << 40, 2 << 40, B, _stream()),
               'group_train_prologue')
-        self._pool = {}
-        for q, k in enumerate(idx_keys):
-            self._pool['idx_' + k] = ipool[q * B:(q + 1) * B]
-        self._next_key = self._prefetch_chain(idx_keys)
-        o = 0
-        for k, sh in eps_specs:
-            n = int(np.prod(sh))
-            self._pool['eps_' + k] = epool[o:o + n].view(*sh)
-            o += n
-        self._early_key = None
 
     def _sample_into(self, buffer, B, key, slot=0, g=False):
         if key == 'warm':

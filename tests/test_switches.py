@@ -49,3 +49,14 @@ def test_lds_images_of_the_bf16x3_tiles_are_conflict_free_by_the_guides_rules():
             assert lb.extra_cycles('ds_read_b128', [off(l & 31, 32 * c + 16 * (l >> 5)) for l in range(64)]) == 0
     # the 16x16x32 fragment read of the noise-critic kernels on 80-byte rows: 4 extra cycles (docs/history/r05.md)
     assert lb.extra_cycles('ds_read_b128', [(l & 15) * 80 + (l >> 4) * 16 for l in range(64)]) == 4
+
+
+def test_pipeline_switch_refuses_the_removed_one_graph_branch_form(monkeypatch):
+    """RLREP_PIPELINE is read once, at construction, before anything touches the GPU: 0 (sequential) and 2 (two streams) are its only forms."""
+    import types
+    import numpy as np
+    from rlrep_amd.agent.sac.sac_agent import SACAgent
+    monkeypatch.setenv('RLREP_PIPELINE', '1')
+    space = types.SimpleNamespace(low=np.array([-1.0]), high=np.array([1.0]))
+    with pytest.raises(ValueError, match=r"RLREP_PIPELINE=.*accepted values are 0 \(sequential\) and 2"):
+        SACAgent(3, 1, space)
