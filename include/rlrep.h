@@ -520,6 +520,16 @@ int32_t rlrep_group_members(rlrep_agent* agent);
  * has rlrep_group_create's hyper.  rlrep_group_get_member_hyper reads a member's values back (world_size as the group normalises it). */
 int32_t rlrep_group_set_member_hyper(rlrep_agent* agent, int32_t member, const rlrep_hyper* hyper, void* stream);
 int32_t rlrep_group_get_member_hyper(rlrep_agent* agent, int32_t member, rlrep_hyper* out);
+/* Exploit step of population-based training: for k < n, member dst[k] becomes member src[k] -- parameters, targets, Adam moments and
+ * step counts, temperature state, train() counter -- and keeps its own hyper-parameters (rlrep_group_set_member_hyper), seed, replay
+ * ring and metric history.  ONE launch, stream-ordered on `stream`; captured train() graphs read the new state at their next replay.
+ * Copied, from src's block to dst's: the parameter, target, exp_avg and exp_avg_sq arenas, alpha_state and the batch-independent device
+ * records (the train() counter block, the four optimizer records, the metric slots) except words 1..5 of every optimizer record (lr, beta1,
+ * beta2, eps, tau: rlrep_group_cfg_dev), which stay dst's.  Gradients, activations and the index / noise pools are rewritten by every train().
+ * Rejected with RLREP_ERR_ARG and a message, before anything is launched: an ordinary agent, n outside [1, members], a member outside
+ * [0, members), src == dst in a pair, a destination named twice, a member that is a source of one pair and the destination of another (pairs
+ * are independent: the launch orders nothing between them), a call between rlrep_group_train_prologue and the end of that train(). */
+int32_t rlrep_group_clone_members(rlrep_agent* agent, const int32_t* src_host, const int32_t* dst_host, int32_t n, void* stream);
 /* the Philox seed of every member (n = members): member r's index and noise pools are drawn as rlrep_train_prologue draws them with seeds[r] */
 int32_t rlrep_group_set_seeds(rlrep_agent* agent, const uint64_t* seeds_host, int32_t n, void* stream);
 /* rlrep_train_prologue for every member, in ONE launch: member r draws with its seed, gathers from ring_dev + r * ring_stride_bytes bounded

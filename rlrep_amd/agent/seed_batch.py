@@ -15,6 +15,10 @@ lr, discount, tau, alpha, target_update_period, auto_entropy_tuning; ctrlsac als
 defaults; member r is then `torch.manual_seed(seeds[r]); Agent(..., seed=seeds[r], **defaults, **member_hyper[r])`.  Seeds may repeat as long
 as the (seed, hyper) pairs are distinct.  Everything else -- dimensions, extra_feature_steps, use_feature_target, max_batch -- is structural:
 shared by every member and refused in a member dict.
+
+Population-based training: `clone_members([(src, dst), ...])` makes member dst a copy of member src on the device, in one launch (exploit),
+and `set_member_hyper(r, lr=...)` retunes a live member (explore); both leave the captured train() graph as it is.  A cloned member keeps its
+own hyper-parameters, seed, replay ring and metric history.  rlrep_amd/agent/pbt.py plans who copies whom; `lineage` records what happened.
 """
 import ctypes as C
 import inspect
@@ -178,6 +182,7 @@ class SeedBatchMixin(object):
             raise ValueError(f'{name}: seeds must be distinct')
         self._mhyper = self.member_hypers(self.seeds, kwargs, member_hyper)
         self._swept = member_hyper is not None
+        self.lineage = []                       # one record per clone / retune (clone_members, set_member_hyper); checkpoints carry it
         self.R = len(self.seeds)
         kwargs = dict(kwargs)
         kwargs.pop('seed', None)
@@ -217,6 +222,62 @@ class SeedBatchMixin(object):
         """member r's sweepable hyper-parameters: `Agent(..., seed=seeds[r], **member_hyper(r))` (with the group's other kwargs) is its
         standalone twin"""
         return dict(self._mhyper[r])
+
+    # ---- population-based training: exploit (clone) and explore (retune) between two train() calls ---------------------------------------
+    def clone_members(self, pairs):
+        """pairs = [(src, dst), ...]: member dst becomes member src -- parameters, targets, Adam moments and step counts, temperature state,
+        train() counter -- in ONE launch on the current stream (include/rlrep.h rlrep_group_clone_members).  dst keeps its hyper-parameters,
+        seed, replay ring and metric history (info dicts returned earlier stay valid); the captured train() graph is kept.  No member may be
+        both a source and a destination, no destination may repeat."""
+        name = type(self).__name__
+        try:
+            pairs = [(int(s), int(d)) for s, d in pairs]
+        except (TypeError, ValueError):
+            raise ValueError(f'{name}.clone_members: pairs must be a list of (src, dst) member indices')
+        if not 1 <= len(pairs) <= self.R:
+            raise ValueError(f'{name}.clone_members: {len(pairs)} pairs outside [1, {self.R}]')
+        for s, d in pairs:
+            if not (0 <= s < self.R and 0 <= d < self.R):
+                raise ValueError(f'{name}.clone_members: pair ({s}, {d}) names a member outside [0, {self.R})')
+            if s == d:
+                raise ValueError(f'{name}.clone_members: pair ({s}, {d}) copies member {s} onto itself')
+        dsts = [d for _, d in pairs]
+        for d in dsts:
+            if dsts.count(d) > 1:
+                raise ValueError(f'{name}.clone_members: member {d} is a destination twice')
+        both = sorted(set(dsts) & {s for s, _ in pairs})
+        if both:
+            raise ValueError(f'{name}.clone_members: member {both[0]} is both a source and a destination')
+        n = len(pairs)
+        src, dst = (C.c_int32 * n)(*[s for s, _ in pairs]), (C.c_int32 * n)(*dsts)
+        check(lib.rlrep_group_clone_members(self.core.h, src, dst, n, _stream()), 'group_clone_members')
+        for s, d in pairs:
+            self.lineage.append({'train_calls': int(self.steps), 'kind': 'clone', 'members': [s, d], 'old': None, 'new': None})
+
+    def set_member_hyper(self, r, **kw):
+        """Retune live member r: keys from SWEEP_KEYS but `alpha` (the INITIAL temperature: it has no meaning for a member that is already
+        training).  The member's device words change (rlrep_group_set_member_hyper); the captured graph reads them at its next replay."""
+        name = type(self).__name__
+        r = int(r)
+        if not 0 <= r < self.R:
+            raise ValueError(f'{name}.set_member_hyper: member {r} outside [0, {self.R})')
+        for k in kw:
+            if k == 'alpha':
+                raise ValueError(f'{name}.set_member_hyper: alpha is the initial temperature only (a live member\'s temperature is its '
+                                 'alpha_state, which training owns); it cannot be retuned')
+            if k not in self.SWEEP_KEYS:
+                raise ValueError(f'{name}.set_member_hyper: unknown key {k!r} (retunable: {", ".join(k for k in self.SWEEP_KEYS if k != "alpha")})')
+        new = {k: self.normalise_hyper(k, v, f'{name}.set_member_hyper') for k, v in kw.items()}
+        self._apply_member_hyper(r, new)
+
+    def _apply_member_hyper(self, r, new):
+        old = self.member_hyper(r)
+        hp = dict(old)
+        hp.update(new)
+        check(lib.rlrep_group_set_member_hyper(self.core.h, r, C.byref(self._hyper_struct(self.core, hp)), _stream()), 'group_set_member_hyper')
+        self._mhyper[r] = hp
+        self._swept = True
+        self.lineage.append({'train_calls': int(self.steps), 'kind': 'retune', 'members': [r], 'old': {k: old[k] for k in new}, 'new': dict(new)})
 
     def _init_parameters(self):
         group = self.core
@@ -314,12 +375,15 @@ class SeedBatchMixin(object):
                 'hyper': self.member_hyper(r)}
 
     def state_snapshot(self):
-        return {'format': 'rlrep-seed-batch-1', 'seeds': list(self.seeds), 'members': [self.member_snapshot(r) for r in range(self.R)]}
+        return {'format': 'rlrep-seed-batch-1', 'seeds': list(self.seeds), 'members': [self.member_snapshot(r) for r in range(self.R)],
+                'lineage': [dict(e) for e in self.lineage]}
 
     def save(self, path):
         torch.save(self.state_snapshot(), path)
 
-    def load(self, path_or_snapshot):
+    def load(self, path_or_snapshot, adopt_hyper=False):
+        """adopt_hyper: members whose hyper-parameters differ from the checkpoint's take the checkpoint's (a population-based run is resumed
+        into a group built with the initial values); otherwise such a checkpoint is refused."""
         snap = torch.load(path_or_snapshot) if isinstance(path_or_snapshot, (str, bytes, os.PathLike)) else path_or_snapshot
         if snap.get('format') != 'rlrep-seed-batch-1' or list(snap['seeds']) != self.seeds:
             raise RuntimeError('checkpoint does not match this seed batch (format / seeds differ)')
@@ -328,9 +392,15 @@ class SeedBatchMixin(object):
             c = self._members[r]
             if ms['layout'] != list(c.order) or ms['device_state'].numel() != c.device_state().numel():
                 raise RuntimeError('checkpoint does not match this seed batch (dimensions differ)')
-            if 'hyper' in ms and dict(ms['hyper']) != self.member_hyper(r):
+            if 'hyper' in ms and dict(ms['hyper']) != self.member_hyper(r) and not (adopt_hyper and set(ms['hyper']) == set(self.SWEEP_KEYS)):
                 raise RuntimeError(f'checkpoint does not match this seed batch (member {r} hyper-parameters differ: {dict(ms["hyper"])} '
                                    f'against {self.member_hyper(r)})')
+        for r, ms in enumerate(snap['members']):
+            if 'hyper' in ms and dict(ms['hyper']) != self.member_hyper(r):
+                hp = {k: self.normalise_hyper(k, v) for k, v in ms['hyper'].items()}
+                self._apply_member_hyper(r, {k: v for k, v in hp.items() if k != 'alpha'})
+                self._mhyper[r]['alpha'] = hp['alpha']          # (the initial temperature: a record only, alpha_state comes with the checkpoint)
+        self.lineage = [dict(e) for e in snap.get('lineage', [])]
         for r, ms in enumerate(snap['members']):
             c = self._members[r]
             for k, dst in (('params', c.params), ('targets', c.targets), ('exp_avg', c.exp_avg), ('exp_avg_sq', c.exp_avg_sq),

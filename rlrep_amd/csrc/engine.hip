@@ -2140,6 +2140,58 @@ int32_t rlrep_group_get_member_hyper(rlrep_agent* ag, int32_t member, rlrep_hype
     *out = ag->grp_hyper[member];
     return 0;
 }
+extern "C" int rl_launch_group_clone(const CloneTab* tab, const ClonePairs* pairs, int npairs, hipStream_t st);
+int32_t rlrep_group_clone_members(rlrep_agent* ag, const int32_t* src_host, const int32_t* dst_host, int32_t n, void* stream) {
+    if (!ag || ag->members <= 0) { rl_set_error("group_clone_members: not a seed group"); return RLREP_ERR_ARG; }
+    if (!src_host || !dst_host) { rl_set_error("group_clone_members: null member list"); return RLREP_ERR_ARG; }
+    if (n < 1 || n > ag->members) { rl_set_error("group_clone_members: n %d outside [1, %d]", n, ag->members); return RLREP_ERR_ARG; }
+    // pairs must be independent of each other (one launch serves all of them, in no order): role 1 = a source, 2 = a destination
+    char role[RLREP_GROUP_MAX_MEMBERS] = {0};
+    ClonePairs pairs; memset(&pairs, 0, sizeof(pairs));
+    for (int k = 0; k < n; ++k) {
+        const int s = src_host[k], d = dst_host[k];
+        if (s < 0 || s >= ag->members || d < 0 || d >= ag->members) {
+            rl_set_error("group_clone_members: pair %d (%d -> %d) names a member outside [0, %d)", k, s, d, ag->members); return RLREP_ERR_ARG;
+        }
+        if (s == d) { rl_set_error("group_clone_members: pair %d copies member %d onto itself", k, s); return RLREP_ERR_ARG; }
+        if (role[d] == 2) { rl_set_error("group_clone_members: member %d is a destination twice", d); return RLREP_ERR_ARG; }
+        if (role[d] == 1 || role[s] == 2) {
+            rl_set_error("group_clone_members: member %d is both a source and a destination", role[d] == 1 ? d : s); return RLREP_ERR_ARG;
+        }
+        role[s] = 1; role[d] = 2;
+        pairs.src[k] = s; pairs.dst[k] = d;
+    }
+    if (ag->in_train) { rl_set_error("group_clone_members: inside a train() (between rlrep_group_train_prologue and the end of that train())"); return RLREP_ERR_ARG; }
+    // what a standalone agent's load(snapshot) restores: four arenas, the temperature state, the device records (static_state: the train()
+    // counter block, the optimizer records, the metric slots -- the head of the workspace, up to the end of the metric slots)
+    CloneTab tab; memset(&tab, 0, sizeof(tab));
+    tab.base = const_cast<char*>(ag->grp_lo); tab.stride = ag->grp_stride;
+    const long long pf = 4ll * ag->L.cur[RLREP_ARENA_PARAM], tf = 4ll * ag->L.cur[RLREP_ARENA_TARGET];
+    const char* ws0 = (const char*)ag->a.workspace_dev;
+    const struct { const void* p; long long bytes; } segs[] = {
+        {ag->a.param_dev, pf}, {ag->a.target_dev, tf}, {ag->a.exp_avg_dev, pf}, {ag->a.exp_avg_sq_dev, pf}, {ag->a.alpha_state_dev, 4 * 8},
+        {ws0, (long long)((const char*)(ag->metrics + M_COUNT) - ws0)}};
+    static_assert(sizeof(segs) / sizeof(segs[0]) <= RL_CLONE_MAX_SEGS, "CloneTab segments");
+    for (const auto& g : segs) {
+        if (g.bytes <= 0) continue;
+        const long long off = (const char*)g.p - ag->grp_lo;
+        if (off < 0 || (off & 3) || (g.bytes & 3) || off + g.bytes > ag->grp_stride) {
+            rl_set_error("group_clone_members: a segment [%lld, %lld) leaves the member block of %lld bytes", off, off + g.bytes, ag->grp_stride); return RLREP_ERR_ARG;
+        }
+        if (g.p == ws0) {
+            tab.rec_seg = tab.nseg;
+            tab.rec_w0 = (int)(((const char*)ag->adam_step - ws0) >> 2); tab.rec_nw = 4 * RLREP_GROUP_CFG_WORDS; tab.rec_words = RLREP_GROUP_CFG_WORDS;
+            if ((const char*)ag->steps != ws0 || (const char*)(ag->adam_step + 4) > (const char*)ag->metrics) {
+                rl_set_error("group_clone_members: the device records are not laid out as static_state lays them out"); return RLREP_ERR_ARG;
+            }
+        }
+        tab.seg[tab.nseg].off = off; tab.seg[tab.nseg].bytes = g.bytes; ++tab.nseg;
+    }
+    ++g_rl_launches;
+    const int rc = rl_launch_group_clone(&tab, &pairs, n, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_clone_members: launch failed (%d)", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
 // [p, p + bytes) inside member 0's block [grp_lo, grp_lo + stride): what a group launch moves by r * stride must stay in member r's block
 static bool in_member0(const rlrep_agent* ag, const void* p, long long bytes) {
     const char* q = (const char*)p;

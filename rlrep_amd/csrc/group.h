@@ -28,6 +28,20 @@ extern "C" const RlGrp* rl_grp_active();
 
 #define RL_UNPAREN(...) __VA_ARGS__
 
+// rlrep_group_clone_members (group_clone.hip): what one clone launch copies from member src's block to member dst's, both by value in the
+// kernel arguments.  A segment is [off, off + bytes) from the member block's base, both multiples of 4.  Segment rec_seg holds the device
+// records and moves word by word: of its words [rec_w0, rec_w0 + rec_nw) -- the optimizer records, rec_words words each -- words 1..5 of every
+// record (lr, beta1, beta2, eps, tau) stay the destination's.
+#define RL_CLONE_MAX_SEGS 8
+struct CloneSeg { long long off, bytes; };
+struct CloneTab {
+    char* base;                         // member 0's block (rlrep_agent::grp_lo)
+    long long stride;                   // bytes between two members' blocks
+    int nseg, rec_seg, rec_w0, rec_nw, rec_words, pad_;
+    CloneSeg seg[RL_CLONE_MAX_SEGS];
+};
+struct ClonePairs { int src[RLREP_GROUP_MAX_MEMBERS], dst[RLREP_GROUP_MAX_MEMBERS]; };
+
 #ifdef __HIPCC__
 template <class T> __device__ __forceinline__ void rl_rb(T*& p, long long d) { if (p) p = (T*)((uintptr_t)p + (uintptr_t)d); }
 // p moved by d bytes in a group form (GRP), p itself in the single-agent kernel: for bodies that read a pointer from a record left in the

@@ -14,6 +14,14 @@ log directory.  ctrlsac takes the dimensions build_agent gives it (main.py:90-91
 `--sweep key=v1,v2` (repeatable; with --seeds, or with --seed alone) adds hyper-parameter configurations: the group's members are
 product(configurations) x seeds, all trained in the same launches (SeedBatchMixin member_hyper).  A member logs to
 `log/<env>/<alg>/<dir>/<tag>/<seed>/metrics.jsonl`, tag = `key=value` joined by `_` (e.g. `lr=0.0001_tau=0.01`).
+
+`--pbt-interval N` (with --seeds / --sweep; N environment steps, a multiple of --eval_freq; 0 = off) turns the group into a population
+(population-based training, Jaderberg et al. 2017): at every step t + 1 that is a multiple of N beyond start_timesteps the members are ranked
+by their latest evaluation, the bottom `--pbt-fraction` each become a copy of a member drawn from the top fraction (SeedBatchMixin.clone_members,
+one launch) and take its hyper-parameters with every `--pbt-keys` entry multiplied by a factor drawn from `--pbt-factors`
+(set_member_hyper).  The defaults 0.25 / 0.8,1.2 are the paper's.  Every event is one line of `log/<env>/<alg>/<dir>/pbt.jsonl` (step, src,
+dst, scores, old and new values); the members' metrics.jsonl rows are unchanged, and a sweep tag directory keeps naming the member's INITIAL
+configuration, whatever PBT has made of it since.
 """
 import argparse
 import json
@@ -75,9 +83,16 @@ def run(argv=None):
     p.add_argument('--seeds', default=None, help='comma-separated seeds trained together (sac and ctrlsac only): rlrep_amd/agent/seed_batch.py')
     p.add_argument('--sweep', action='append', default=None, metavar='KEY=V1,V2',
                    help='hyper-parameter values trained together with the seeds (repeatable; members = product of the sweeps x seeds)')
+    p.add_argument('--pbt-interval', default=None, type=int, help='population-based training every N environment steps (a multiple of --eval_freq; 0 = off)')
+    p.add_argument('--pbt-fraction', default=None, type=float, help='share of the members replaced at a PBT step, and of those they copy (default 0.25)')
+    p.add_argument('--pbt-keys', default=None, help='comma-separated hyper-parameters a copied member perturbs (default lr)')
+    p.add_argument('--pbt-factors', default=None, help='comma-separated factors a perturbed value is multiplied by (default 0.8,1.2)')
+    p.add_argument('--pbt-seed', default=None, type=int, help='seed of the PBT draws (default 0)')
     args = p.parse_args(argv)
     if args.seeds is not None or args.sweep:
         return run_seeds(args)
+    if _pbt_requested(args):
+        raise SystemExit('--pbt-*: population-based training needs a seed group (--seeds and / or --sweep)')
 
     env, eval_env = envs.make(args.env), envs.make(args.env)
     env.seed(args.seed)
@@ -201,6 +216,65 @@ def parse_sweeps(sweeps, alg, n_seeds):
     return configs
 
 
+PBT_OPTIONS = ('pbt_interval', 'pbt_fraction', 'pbt_keys', 'pbt_factors', 'pbt_seed')
+
+
+def _pbt_requested(args):
+    # (--pbt-interval 0 alone is "off", spelled out)
+    return bool(args.pbt_interval) or any(getattr(args, k) is not None for k in PBT_OPTIONS if k != 'pbt_interval')
+
+
+def parse_pbt(args, alg, members):
+    """--pbt-* -> None (off) or dict(interval, fraction, keys, factors, seed).  SystemExit on fewer than 2 members, an interval that is not a
+    positive multiple of --eval_freq, a fraction outside (0, 0.5], a key --alg does not sweep or that cannot be perturbed, bad factors."""
+    import math
+    if not _pbt_requested(args):
+        return None
+    if members < 2:
+        raise SystemExit(f'--pbt-interval: population-based training needs at least 2 members (the group has {members})')
+    interval, freq = int(args.pbt_interval or 0), int(args.eval_freq)
+    if interval <= 0 or freq <= 0 or interval % freq:
+        raise SystemExit(f'--pbt-interval {args.pbt_interval}: give a positive multiple of --eval_freq ({freq}): members are ranked by their latest evaluation')
+    fraction = 0.25 if args.pbt_fraction is None else float(args.pbt_fraction)
+    if not (math.isfinite(fraction) and 0.0 < fraction <= 0.5):
+        raise SystemExit(f'--pbt-fraction {args.pbt_fraction}: outside (0, 0.5]')
+    cls = _group_class(alg)
+    keys = [k.strip() for k in str('lr' if args.pbt_keys is None else args.pbt_keys).split(',') if k.strip()]
+    if not keys:
+        raise SystemExit(f'--pbt-keys {args.pbt_keys}: give at least one key, e.g. --pbt-keys lr,tau')
+    for k in keys:
+        if k not in cls.SWEEP_KEYS:
+            raise SystemExit(f'--pbt-keys {args.pbt_keys}: {k} is not a sweepable hyper-parameter of --alg {alg} (it takes {", ".join(cls.SWEEP_KEYS)})')
+        if k in ('alpha', 'auto_entropy_tuning'):
+            raise SystemExit(f'--pbt-keys {args.pbt_keys}: {k} cannot be perturbed (alpha is the initial temperature only, auto_entropy_tuning is a boolean)')
+    if len(set(keys)) != len(keys):
+        raise SystemExit(f'--pbt-keys {args.pbt_keys}: repeated key')
+    try:
+        factors = [float(f) for f in str('0.8,1.2' if args.pbt_factors is None else args.pbt_factors).split(',') if f.strip()]
+    except ValueError:
+        factors = []
+    if not factors or not all(math.isfinite(f) and f > 0 for f in factors):
+        raise SystemExit(f'--pbt-factors {args.pbt_factors}: give finite positive factors, e.g. --pbt-factors 0.8,1.2')
+    return dict(interval=interval, fraction=fraction, keys=keys, factors=factors, seed=int(args.pbt_seed or 0))
+
+
+def pbt_step(agent, scores, cfg, rng, step, log):
+    """One exploit / explore step on a seed group: plan, clone in one launch, retune every destination; one `log` line per destination."""
+    from rlrep_amd.agent import pbt
+    pairs = pbt.plan_exploit(scores, cfg['fraction'], rng)
+    agent.clone_members(pairs)
+    for src, dst in pairs:
+        old = agent.member_hyper(dst)
+        new = pbt.perturb(agent.member_hyper(src), cfg['keys'], cfg['factors'], rng)
+        retune = {k: new[k] for k in new if k != 'alpha'}
+        agent.set_member_hyper(dst, **retune)
+        now = agent.member_hyper(dst)
+        log.write(json.dumps({'step': int(step), 'src': int(src), 'dst': int(dst), 'scores': [float(s) for s in scores],
+                              'old': {k: old[k] for k in retune}, 'new': {k: now[k] for k in retune}}) + '\n')
+    log.flush()
+    return pairs
+
+
 def run_seeds(args):
     """The loop of run() for several seeds at once: R environments in lockstep, one SACSeedBatch, one ReplayBufferGroup."""
     seeds = [int(s) for s in str(args.seeds).split(',') if s.strip() != ''] if args.seeds is not None else [int(args.seed)]
@@ -213,6 +287,7 @@ def run_seeds(args):
     tags = [t for t, _ in configs for _ in seeds]
     member_hyper = [cfg for _, cfg in configs for _ in seeds] if swept else None
     seeds = [s for _ in configs for s in seeds]              # member = (configuration, seed), configurations outermost
+    pbt_cfg = parse_pbt(args, args.alg, len(seeds))
     from rlrep_amd.utils.buffer_group import ReplayBufferGroup
     R = len(seeds)
     envs_, evals_ = [envs.make(args.env) for _ in seeds], [envs.make(args.env) for _ in seeds]
@@ -243,6 +318,10 @@ def run_seeds(args):
     states = np.stack([np.asarray(e.reset(), np.float32) for e in envs_])
     ep_steps = np.zeros(R, np.int64)
     infos = None
+    pbt_rng = pbt_log = None
+    if pbt_cfg is not None:
+        pbt_rng = np.random.RandomState(pbt_cfg['seed'])
+        pbt_log = open(os.path.join(args.log_root, args.env, args.alg, str(args.dir), 'pbt.jsonl'), 'a')
     timer = util.Timer()
     for t in range(int(args.max_timesteps)):
         ep_steps += 1
@@ -278,9 +357,11 @@ def run_seeds(args):
                     logs[r].write(json.dumps(row) + '\n')
                     logs[r].flush()
             print('Step {}. Steps per sec (per seed): {:.4g}.'.format(t + 1, sps))
+            if pbt_cfg is not None and (t + 1) % pbt_cfg['interval'] == 0 and t + 1 > args.start_timesteps:
+                pbt_step(agent, [evaluations[r][-1] for r in range(R)], pbt_cfg, pbt_rng, t + 1, pbt_log)
             if args.save_model:
                 agent.save(os.path.join(args.log_root, args.env, args.alg, str(args.dir), 'seed_batch.pt'))
-    for f in logs:
+    for f in logs + ([pbt_log] if pbt_log is not None else []):
         f.close()
     print('Total time cost {:.4g}s.'.format(timer.time_cost()))
     return agent, evaluations

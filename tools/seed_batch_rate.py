@@ -10,6 +10,12 @@ train() a ctrlsac group runs (the pipelined two-chain form is not built for grou
 SeedBatchMixin member_hyper), measured against a seed-only group of the same R and against R standalone agents built with each member's seed
 and hyper-parameters.
 
+--clone: population-based training's exploit step at R = 8, 2 pairs (--workload is ignored: sac HalfCheetah, ctrlsac F = 256 and F = 2048).
+Time per SeedBatchMixin.clone_members call (one launch), the bytes it moves and GB/s, against the same effect done on the device without it:
+per pair five `copy_` between the members' arena views, then the device records with the destination's hyper words saved and restored
+(what SeedBatchMixin.load() does from the host).  Device events around 100 calls after 10 warm-up calls, the two forms alternated, median of
+--windows windows.  The clone must not be the slower one at any shape (exit status 1 otherwise).
+
 Per R: the group's aggregate rate (R x calls/s), its graph's launch count per call, and the standalone agents' aggregate rate.  Protocol:
 --warmup calls (default 300), then the median of --windows windows (default 5) of --calls calls (default 500), timed by host wall clock
 around a device synchronisation."""
@@ -50,7 +56,10 @@ def main(argv=None):
     p.add_argument('--windows', type=int, default=5)
     p.add_argument('--group-only', action='store_true', help='skip the standalone agents (a profiler run of the group alone)')
     p.add_argument('--sweep', action='store_true', help='a hyper-parameter sweep group against a seed-only group and R standalone agents')
+    p.add_argument('--clone', action='store_true', help='time clone_members against per-arena copy_ calls (R = 8, 2 pairs, three shapes)')
     a = p.parse_args(argv)
+    if a.clone:
+        return clone_main(a)
     if a.sweep:
         return sweep_main(a)
     from rlrep_amd.utils.buffer_group import ReplayBufferGroup
@@ -151,5 +160,69 @@ def sweep_main(a):
         torch.cuda.empty_cache()
 
 
+HBM_MEASURED_TBS = 6.29          # measured HBM rate of a float4 copy on the MI355X
+
+
+def _event_ms(step, warmup, calls):
+    for _ in range(warmup):
+        step()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(calls):
+        step()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / calls
+
+
+def clone_main(a):
+    R, pairs, warmup, calls = 8, [(0, 4), (1, 5)], 10, 100
+    print(f'# clone_members against per-arena copy_ calls; R = {R}, pairs {pairs}; {torch.cuda.get_device_name(0)}; device events around {calls} calls '
+          f'after {warmup} warm-up calls, forms alternated, median of {a.windows} windows')
+    print(f'{"workload":<32} {"MB moved/call":>14} {"clone us":>9} {"clone GB/s":>11} {"copy_ us":>9} {"copy_ GB/s":>11} {"copy_/clone":>12} {"of 6.29 TB/s":>13}')
+    slower = []
+    for wl in ('sac_halfcheetah_b256', 'ctrlsac_halfcheetah_f256_b256', 'ctrlsac_halfcheetah_f2048_b256'):
+        alg, S, A, B, kw = bench.WORKLOADS[wl]
+        if alg == 'ctrlsac':
+            from rlrep_amd.agent.ctrlsac.seed_batch import CTRLSACSeedBatch as Group
+        else:
+            from rlrep_amd.agent.sac.seed_batch import SACSeedBatch as Group
+        members = _sweep_members(alg, R)
+        grp = Group([s for s, _ in members], S, A, bench.Space(A), max_batch=B, member_hyper=[h for _, h in members], **kw)
+        m = grp._members
+        arenas = ('params', 'targets', 'exp_avg', 'exp_avg_sq', 'alpha_state')
+        # read + write bytes of one call: the four arenas, alpha_state and the device records but for 4 x 5 hyper words, per pair
+        one = sum(getattr(m[0], k).numel() * getattr(m[0], k).element_size() for k in arenas) + m[0].device_state().numel() - 4 * 5 * 4
+        moved = 2 * one * len(pairs)
+
+        def by_copies():
+            for s, d in pairs:
+                for k in arenas:
+                    getattr(m[d], k).copy_(getattr(m[s], k))
+                hyper = m[d].group_cfg()[:, 1:6].clone()
+                m[d].device_state().copy_(m[s].device_state())
+                m[d].group_cfg()[:, 1:6].copy_(hyper)
+
+        def by_clone():
+            grp.clone_members(pairs)
+        t_clone, t_copy = [], []
+        for _ in range(a.windows):
+            t_clone.append(_event_ms(by_clone, warmup, calls))
+            t_copy.append(_event_ms(by_copies, warmup, calls))
+        c, p_ = statistics.median(t_clone), statistics.median(t_copy)
+        share = f'{moved / (c * 1e-3) / (HBM_MEASURED_TBS * 1e12):>12.1%}' if wl.endswith('f2048_b256') else f'{"":>12}'
+        print(f'{wl:<32} {moved / 1e6:>14.3f} {c * 1e3:>9.1f} {moved / (c * 1e-3) / 1e9:>11.1f} {p_ * 1e3:>9.1f} {moved / (p_ * 1e-3) / 1e9:>11.1f} '
+              f'{p_ / c:>12.2f} {share}', flush=True)
+        if c > p_:
+            slower.append(wl)
+        del grp, m
+        torch.cuda.empty_cache()
+    if slower:
+        print(f'# FAILED: clone_members is slower than the copy_ calls at {", ".join(slower)}')
+        return 1
+    return 0
+
+
 if __name__ == '__main__':
-    main()
+    sys.exit(main())
