@@ -530,6 +530,17 @@ int32_t rlrep_group_get_member_hyper(rlrep_agent* agent, int32_t member, rlrep_h
  * [0, members), src == dst in a pair, a destination named twice, a member that is a source of one pair and the destination of another (pairs
  * are independent: the launch orders nothing between them), a call between rlrep_group_train_prologue and the end of that train(). */
 int32_t rlrep_group_clone_members(rlrep_agent* agent, const int32_t* src_host, const int32_t* dst_host, int32_t n, void* stream);
+/* Successive halving: take members out of every group launch, keep their state, put them back.  live_host [members], 1 = live, 0 = retired.
+ * The group's live table (device: n_live, then the live members in ascending order) is rebuilt from the mask in ONE launch, stream-ordered on
+ * `stream`; grid y of the group launches stays `members`, and a workgroup whose slot lies at or behind n_live returns at once, so a captured
+ * train() graph obeys the mask from its next replay (no re-capture).  Nothing of a retired member is read or written by rlrep_group_train_prologue,
+ * the step programs or rlrep_group_select_action (its action row is left unwritten): parameters, moments, step counters, tickets, pools, slot
+ * buffers, metric slots and history stand still until it is revived.  rlrep_group_clone_members, rlrep_group_set_member_hyper and
+ * rlrep_group_replay_add_sized do not look at the mask.  After rlrep_group_create every member is live.
+ * Rejected with RLREP_ERR_ARG and a message, before anything is launched: an ordinary agent, a mask with no live member, a value other than
+ * 0 / 1, a call between rlrep_group_train_prologue and the end of that train().  rlrep_group_get_live reads the mask back. */
+int32_t rlrep_group_set_live(rlrep_agent* agent, const int32_t* live_host, void* stream);
+int32_t rlrep_group_get_live(rlrep_agent* agent, int32_t* live_out);
 /* the Philox seed of every member (n = members): member r's index and noise pools are drawn as rlrep_train_prologue draws them with seeds[r] */
 int32_t rlrep_group_set_seeds(rlrep_agent* agent, const uint64_t* seeds_host, int32_t n, void* stream);
 /* rlrep_train_prologue for every member, in ONE launch: member r draws with its seed, gathers from ring_dev + r * ring_stride_bytes bounded

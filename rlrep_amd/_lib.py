@@ -86,6 +86,8 @@ def _load():
         'rlrep_group_set_member_hyper': (i32, [vp, i32, P(Hyper), vp]),
         'rlrep_group_get_member_hyper': (i32, [vp, i32, P(Hyper)]),
         'rlrep_group_clone_members': (i32, [vp, P(i32), P(i32), i32, vp]),
+        'rlrep_group_set_live': (i32, [vp, P(i32), vp]),
+        'rlrep_group_get_live': (i32, [vp, P(i32)]),
         'rlrep_group_train_prologue': (i32, [vp, vp, i64, vp, vp, i64, vp, i64, u64, u64, i32, vp]),
         'rlrep_group_prepare': (i32, [vp, i32]),
         'rlrep_group_select_action': (i32, [vp, vp, i32, u64, f32, f32, vp, vp]),

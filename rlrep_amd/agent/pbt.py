@@ -1,10 +1,38 @@
 """Population-based training (Jaderberg et al. 2017: truncation selection + perturbation) on the host: who copies whom, and how a copied
-member's hyper-parameters move.  Both functions are deterministic in their arguments and a `np.random.RandomState`; neither touches the GPU
-(the device side is SeedBatchMixin.clone_members / set_member_hyper, rlrep_amd/agent/seed_batch.py).
+member's hyper-parameters move -- and successive halving (Jamieson & Talwalkar 2016): who is retired.  Every function is deterministic in its
+arguments (and a `np.random.RandomState` where it draws); none touches the GPU (the device side is SeedBatchMixin.clone_members /
+set_member_hyper / retire_members, rlrep_amd/agent/seed_batch.py).
 """
 import math
 
 import numpy as np
+
+
+def _rank_key(scores):
+    """sort key, best first: higher is better, NaN below everything, ties to the lower member index"""
+    return lambda r: (math.isnan(scores[r]), -scores[r] if not math.isnan(scores[r]) else 0.0, r)
+
+
+def plan_halving(scores, live, keep, min_live=1):
+    """The members to retire, ascending: of the n live members (`live`: one boolean per member) the best max(1, ceil(keep * n)) stay, ranked
+    as plan_exploit ranks (higher is better, NaN below everything, ties to the lower index); 0 < keep < 1.  Retired members' scores are not
+    looked at and they are never returned; [] when one member is live.  min_live: never fewer than this many members stay (the launcher's
+    --halving-min)."""
+    scores = [float(s) for s in scores]
+    live = [bool(v) for v in live]
+    if len(live) != len(scores):
+        raise ValueError(f'plan_halving: {len(scores)} scores for {len(live)} members')
+    keep = float(keep)
+    if not (math.isfinite(keep) and 0.0 < keep < 1.0):
+        raise ValueError(f'plan_halving: keep {keep} outside (0, 1)')
+    alive = [r for r in range(len(live)) if live[r]]
+    if not alive:
+        raise ValueError('plan_halving: no live member')
+    if int(min_live) < 1:
+        raise ValueError(f'plan_halving: min_live {min_live} is below 1')
+    stay = max(1, int(min_live), int(math.ceil(keep * len(alive))))
+    order = sorted(alive, key=_rank_key(scores))      # best first
+    return sorted(order[stay:])
 
 
 def plan_exploit(scores, fraction, rng):
@@ -21,7 +49,7 @@ def plan_exploit(scores, fraction, rng):
     k = max(1, int(math.floor(fraction * R)))
     if 2 * k > R:
         raise ValueError(f'plan_exploit: fraction {fraction} of {R} members makes the top and the bottom {k} overlap')
-    order = sorted(range(R), key=lambda r: (math.isnan(scores[r]), -scores[r] if not math.isnan(scores[r]) else 0.0, r))      # best first
+    order = sorted(range(R), key=_rank_key(scores))      # best first
     top, bottom = order[:k], order[R - k:][::-1]
     return [(top[int(rng.randint(k))], dst) for dst in bottom]
 

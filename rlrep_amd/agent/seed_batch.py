@@ -19,7 +19,13 @@ shared by every member and refused in a member dict.
 Population-based training: `clone_members([(src, dst), ...])` makes member dst a copy of member src on the device, in one launch (exploit),
 and `set_member_hyper(r, lr=...)` retunes a live member (explore); both leave the captured train() graph as it is.  A cloned member keeps its
 own hyper-parameters, seed, replay ring and metric history.  rlrep_amd/agent/pbt.py plans who copies whom; `lineage` records what happened.
+
+Successive halving: `retire_members([r, ...])` takes members out of every launch (include/rlrep.h rlrep_group_set_live: the workgroups of a
+retired member return at once; grid y and the captured graph stay) and `revive_members` puts them back.  A retired member's state is frozen, not
+gone: member(r), member_snapshot(r), set_member_hyper(r) and clone_members work on it, so "clone a winner into a retired slot, perturb, revive"
+respawns it.  train() returns None in its place, select_action a row of zeros.  pbt.plan_halving plans who goes.
 """
+import contextlib
 import ctypes as C
 import inspect
 import math
@@ -31,6 +37,7 @@ import torch
 from rlrep_amd._lib import lib, check
 from rlrep_amd.core import HipCore, _stream
 from rlrep_amd.agent.sac.sac_agent import ArenaModule
+from rlrep_amd.utils import switches as _sw
 
 
 class _MemberCore(HipCore):
@@ -184,6 +191,7 @@ class SeedBatchMixin(object):
         self._swept = member_hyper is not None
         self.lineage = []                       # one record per clone / retune (clone_members, set_member_hyper); checkpoints carry it
         self.R = len(self.seeds)
+        self._live = [True] * self.R            # retire_members / revive_members; checkpoints carry it
         kwargs = dict(kwargs)
         kwargs.pop('seed', None)
         kwargs['seed'] = self.seeds[0]
@@ -270,6 +278,54 @@ class SeedBatchMixin(object):
         new = {k: self.normalise_hyper(k, v, f'{name}.set_member_hyper') for k, v in kw.items()}
         self._apply_member_hyper(r, new)
 
+    # ---- successive halving: members leave and re-enter the launches between two train() calls ------------------------------------------------
+    @property
+    def live(self):
+        """[R] booleans: False for a retired member"""
+        return list(self._live)
+
+    def retire_members(self, members):
+        """Members `members` leave every launch from the next train() / select_action on: nothing of theirs is read or written until they are
+        revived (their step counters stand still, so a revived member draws what it would have drawn next).  At least one member stays live.
+        At most ONE launch on the current stream (the live table); the captured train() graph is kept."""
+        self._set_live(members, False)
+
+    def revive_members(self, members):
+        """Retired members `members` rejoin the launches, with the state they were retired with (or were given since: clone_members,
+        set_member_hyper)."""
+        self._set_live(members, True)
+
+    def _set_live(self, members, on):
+        what = 'revive_members' if on else 'retire_members'
+        name = f'{type(self).__name__}.{what}'
+        try:
+            members = [int(r) for r in members]
+        except (TypeError, ValueError):
+            raise ValueError(f'{name}: members must be a list of member indices')
+        if not members:
+            raise ValueError(f'{name}: no member named')
+        live = list(self._live)
+        for r in members:
+            if not 0 <= r < self.R:
+                raise ValueError(f'{name}: member {r} outside [0, {self.R})')
+            if members.count(r) > 1:
+                raise ValueError(f'{name}: member {r} is named twice')
+            if live[r] == on:
+                raise ValueError(f'{name}: member {r} is ' + ('live already' if on else 'retired already'))
+            live[r] = on
+        if not any(live):
+            raise ValueError(f'{name}: members {members} are the last live members (at least one member of a group stays live)')
+        self._upload_live(live)
+        self.lineage.append({'event': 'revive' if on else 'retire', 'kind': 'revive' if on else 'retire', 'members': list(members),
+                             'step': int(self.steps)})
+
+    def _upload_live(self, live):
+        mask = (C.c_int32 * self.R)(*[1 if v else 0 for v in live])
+        check(lib.rlrep_group_set_live(self.core.h, mask, _stream()), 'group_set_live')          # (refuses a call inside a train())
+        self._live = [bool(v) for v in live]
+        if _sw.opt('grp_compact'):              # (measured, not adopted: grid y = the live members, so the graph is captured again)
+            self._graph = None
+
     def _apply_member_hyper(self, r, new):
         old = self.member_hyper(r)
         hp = dict(old)
@@ -326,8 +382,16 @@ class SeedBatchMixin(object):
         return (buffer.rings.data_ptr(), buffer.size_dev().data_ptr(), int(buffer.max_size), buffer.members, B)
 
     # ---- surface ----------------------------------------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def _history_capture(self):
+        with super()._history_capture():
+            yield
+        # members file their records in rings of their own, and a retired member's ring stands still: one record count per member
+        self._mhist_n = [m.history_seq() for m in self._members] if self._hist else [0] * self.R
+
     def train(self, buffers, batch_size):
-        """One train() of every member: ONE graph replay.  Returns R info dicts (member order), fetched when read."""
+        """One train() of every live member: ONE graph replay.  Returns R entries (member order): an info dict, fetched when read, or None for
+        a retired member."""
         if getattr(buffers, 'members', None) != self.R:
             raise ValueError(f'{type(self).__name__}.train: needs a ReplayBufferGroup of {self.R} members')
         self.steps += 1
@@ -336,11 +400,14 @@ class SeedBatchMixin(object):
     update = train
 
     def _history_info(self):
-        n = self._hist_n
-        self._hist_n += 1
         half = max(1, self.core.history_capacity() // 2)
         out = []
-        for m in self._members:
+        for r, m in enumerate(self._members):
+            if not self._live[r]:
+                out.append(None)
+                continue
+            n = self._mhist_n[r]
+            self._mhist_n[r] += 1
             if n % half == half - 1:
                 m.history_resolve()
             out.append(m.info(lazy_source=m.history_source(n)))
@@ -351,12 +418,16 @@ class SeedBatchMixin(object):
 
     def select_action(self, states, explore=False):
         """states [R, S] -> actions [R, A]: ONE launch over pinned buffers; member r acts as the standalone agent with seed seeds[r] does with
-        the same call counter (every member's exploration draw is keyed by its own seed and the shared counter)."""
+        the same call counter (every member's exploration draw is keyed by its own seed and the shared counter).  A retired member's
+        observation is not read and its action row is zeros."""
         sel = getattr(self, '_gsel', None)
         if sel is None:
             sel = self._gsel = dict(obs=torch.empty(self.R, self.state_dim, dtype=torch.float32).pin_memory(),
                                     act=torch.empty(self.R, self.action_dim, dtype=torch.float32).pin_memory())
         sel['obs'].numpy()[:] = np.asarray(states, dtype=np.float32).reshape(self.R, self.state_dim)
+        for r in range(self.R):
+            if not self._live[r]:
+                sel['act'].numpy()[r] = 0.0     # (the launch leaves a retired member's row unwritten)
         if explore:
             self._ctr += 1
         lo, hi = self.action_range
@@ -376,7 +447,7 @@ class SeedBatchMixin(object):
 
     def state_snapshot(self):
         return {'format': 'rlrep-seed-batch-1', 'seeds': list(self.seeds), 'members': [self.member_snapshot(r) for r in range(self.R)],
-                'lineage': [dict(e) for e in self.lineage]}
+                'lineage': [dict(e) for e in self.lineage], 'live': list(self._live)}
 
     def save(self, path):
         torch.save(self.state_snapshot(), path)
@@ -401,6 +472,11 @@ class SeedBatchMixin(object):
                 self._apply_member_hyper(r, {k: v for k, v in hp.items() if k != 'alpha'})
                 self._mhyper[r]['alpha'] = hp['alpha']          # (the initial temperature: a record only, alpha_state comes with the checkpoint)
         self.lineage = [dict(e) for e in snap.get('lineage', [])]
+        live = [bool(v) for v in snap.get('live', [True] * self.R)]          # (a checkpoint written before members could retire: all live)
+        if len(live) != self.R or not any(live):
+            raise RuntimeError('checkpoint does not match this seed batch (live mask)')
+        if live != self._live:
+            self._upload_live(live)
         for r, ms in enumerate(snap['members']):
             c = self._members[r]
             for k, dst in (('params', c.params), ('targets', c.targets), ('exp_avg', c.exp_avg), ('exp_avg_sq', c.exp_avg_sq),

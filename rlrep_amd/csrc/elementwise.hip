@@ -162,8 +162,9 @@ __global__ __launch_bounds__(256) void train_prologue_kernel(TrainPrologue p) {
 #include "train_prologue_body.h"
 }
 // group form: member m = blockIdx.y draws from its own seed, gathers from its own ring (bounded by its own size word) and counts its own steps
-__global__ __launch_bounds__(256) void train_prologue_kernel_grp(TrainPrologue p0, long long mstride, long long rstride, const unsigned long long* __restrict__ seeds) {
-    const int m = blockIdx.y;
+__global__ __launch_bounds__(256) void train_prologue_kernel_grp(TrainPrologue p0, long long mstride, long long rstride, const unsigned long long* __restrict__ seeds,
+                                                                 const int* __restrict__ live) {
+    RL_GRP_MEMBER(m, live);
     const long long dm = (long long)m * mstride;
     TrainPrologue p = p0;
     rl_rb(p.idx.dst_i, dm); rl_rb(p.idx.step_dev, dm); p.idx.seed = seeds[m];
@@ -205,8 +206,8 @@ __global__ __launch_bounds__(1024) void select_action_kernel(SelectAct p) {
 #include "select_action_body.h"
 }
 // group form: member m = blockIdx.y acts on observation m with its own actor and its own Philox seed, writes action m
-__global__ __launch_bounds__(1024) void select_action_kernel_grp(SelectAct p0, long long mstride, const unsigned long long* __restrict__ seeds) {
-    const int m = blockIdx.y;
+__global__ __launch_bounds__(1024) void select_action_kernel_grp(SelectAct p0, long long mstride, const unsigned long long* __restrict__ seeds, const int* __restrict__ live) {
+    RL_GRP_MEMBER(m, live);
     const long long dm = (long long)m * mstride;
     SelectAct p = p0;
     p.obs += (long long)m * p.S; p.act += (long long)m * p.A;
@@ -316,19 +317,21 @@ __global__ __launch_bounds__(256) void qhead_critic_kernel(QHeadCritic p) {
 #include "qhead_critic_body.h"
 }
 // hyp: member 0's MemberHyper (kparams.h) -- the member's discount comes from its record, not from member 0's p0.gamma
-__global__ __launch_bounds__(256) void qhead_critic_kernel_grp(QHeadCritic p0, long long mstride, const MemberHyper* __restrict__ hyp) {
+__global__ __launch_bounds__(256) void qhead_critic_kernel_grp(QHeadCritic p0, long long mstride, const MemberHyper* __restrict__ hyp, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
     QHeadCritic p = p0;
-    rl_rebase(p, (long long)blockIdx.y * mstride);
-    p.gamma = rl_mv<true>(hyp, (long long)blockIdx.y * mstride)->gamma;
+    rl_rebase(p, (long long)member * mstride);
+    p.gamma = rl_mv<true>(hyp, (long long)member * mstride)->gamma;
 #include "qhead_critic_body.h"
 }
 
 __global__ __launch_bounds__(256) void qhead_actor_kernel(QHeadActor p) {
 #include "qhead_actor_body.h"
 }
-__global__ __launch_bounds__(256) void qhead_actor_kernel_grp(QHeadActor p0, long long mstride) {
+__global__ __launch_bounds__(256) void qhead_actor_kernel_grp(QHeadActor p0, long long mstride, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
     QHeadActor p = p0;
-    rl_rebase(p, (long long)blockIdx.y * mstride);
+    rl_rebase(p, (long long)member * mstride);
 #include "qhead_actor_body.h"
 }
 
@@ -556,9 +559,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ ap, const
 // (kparams.h) -- the Polyak gate's period and the temperature optimizer's lr / learn gate come from the member's record, not from `t` / `fin`.
 __global__ __launch_bounds__(256) void adam_kernel_grp(float* ap, const float* agr, float* am, float* av, const GroupCfg* agrp, float* atarget, int an, int hdr, AdamTask t,
                                                        const FinTask* __restrict__ fin, int nfin, SlotFill sf, int fill_blocks, SlotFill sf2, int fill2_blocks, AdamSnap snap, int snap_blocks,
-                                                       long long mstride, long long rstride, const MemberHyper* hyp) {
+                                                       long long mstride, long long rstride, const MemberHyper* hyp, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
     __builtin_amdgcn_s_setprio(3);
-    const long long dm = (long long)blockIdx.y * mstride, dr = (long long)blockIdx.y * rstride;
+    const long long dm = (long long)member * mstride, dr = (long long)member * rstride;
     rl_rb(ap, dm); rl_rb(agr, dm); rl_rb(am, dm); rl_rb(av, dm); rl_rb(agrp, dm); rl_rb(atarget, dm);
     SlotFill s1 = sf, s2 = sf2; rl_rebase(s1, dm, dr); rl_rebase(s2, dm, dr);
     const DpPull nodp = DpPull();
@@ -707,7 +711,7 @@ extern "C" int rl_launch_select_action(const SelectAct* p, hipStream_t st) {
     if (lds > 60 * 1024) return -7;
     if (const RlGrp* gr = rl_grp_active()) {
         if (!gr->seeds) return RL_GRP_UNSUPPORTED;
-        hipLaunchKernelGGL(select_action_kernel_grp, dim3(1, gr->members), dim3(1024), lds, st, *p, gr->stride, gr->seeds);
+        hipLaunchKernelGGL(select_action_kernel_grp, dim3(1, gr->grid_y), dim3(1024), lds, st, *p, gr->stride, gr->seeds, gr->live);
     } else
         hipLaunchKernelGGL(select_action_kernel, dim3(1), dim3(1024), lds, st, *p);
     return (int)hipGetLastError();
@@ -734,12 +738,12 @@ extern "C" int rl_launch_vae_mse(const VaeMse* p, hipStream_t st) {
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_qhead_critic(const QHeadCritic* p, hipStream_t st) {
-    if (const RlGrp* gr = rl_grp_active()) hipLaunchKernelGGL(qhead_critic_kernel_grp, dim3(p->nblk, gr->members), dim3(256), 0, st, *p, gr->stride, gr->hyp);
+    if (const RlGrp* gr = rl_grp_active()) hipLaunchKernelGGL(qhead_critic_kernel_grp, dim3(p->nblk, gr->grid_y), dim3(256), 0, st, *p, gr->stride, gr->hyp, gr->live);
     else hipLaunchKernelGGL(qhead_critic_kernel, dim3(p->nblk), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_qhead_actor(const QHeadActor* p, hipStream_t st) {
-    if (const RlGrp* gr = rl_grp_active()) hipLaunchKernelGGL(qhead_actor_kernel_grp, dim3(p->nblk, gr->members), dim3(256), 0, st, *p, gr->stride);
+    if (const RlGrp* gr = rl_grp_active()) hipLaunchKernelGGL(qhead_actor_kernel_grp, dim3(p->nblk, gr->grid_y), dim3(256), 0, st, *p, gr->stride, gr->live);
     else hipLaunchKernelGGL(qhead_actor_kernel, dim3(p->nblk), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
@@ -783,8 +787,8 @@ extern "C" int rl_launch_adam(const AdamTask* task, int adam_blocks, const FinTa
                                fin, nfin, sf ? *sf : none, fb, sf2 ? *sf2 : none, fb2, snap ? *snap : nosnap, sb, dpv);
         }
     } else if (gr)
-        hipLaunchKernelGGL(adam_kernel_grp, dim3(grid.x, gr->members), dim3(256), 0, st, t.p, t.g, t.m, t.v, t.grp, t.target, (int)t.n, hdr, t,
-                           fin, nfin, sf ? *sf : none, fb, sf2 ? *sf2 : none, fb2, snap ? *snap : nosnap, sb, gr->stride, gr->ring_stride, gr->hyp);
+        hipLaunchKernelGGL(adam_kernel_grp, dim3(grid.x, gr->grid_y), dim3(256), 0, st, t.p, t.g, t.m, t.v, t.grp, t.target, (int)t.n, hdr, t,
+                           fin, nfin, sf ? *sf : none, fb, sf2 ? *sf2 : none, fb2, snap ? *snap : nosnap, sb, gr->stride, gr->ring_stride, gr->hyp, gr->live);
     else
         hipLaunchKernelGGL(adam_kernel, grid, dim3(256), 0, st, t.p, t.g, t.m, t.v, t.grp, t.target, (int)t.n, hdr, t,
                            fin, nfin, sf ? *sf : none, fb, sf2 ? *sf2 : none, fb2, snap ? *snap : nosnap, sb);
@@ -831,7 +835,7 @@ extern "C" int rl_launch_train_prologue(TrainPrologue* p, hipStream_t st) {
     p->nb_fill = grid_for((long long)p->fill.B * (2 * p->fill.S + p->fill.A + 2), 256, 2048);
     if (const RlGrp* gr = rl_grp_active()) {
         if (p->nsh || p->nb_tr || !gr->seeds) return RL_GRP_UNSUPPORTED;          // (shadow refresh: no sac form carries one)
-        hipLaunchKernelGGL(train_prologue_kernel_grp, dim3(p->nb_idx + p->nb_eps + p->nb_fill, gr->members), dim3(256), 0, st, *p, gr->stride, gr->ring_stride, gr->seeds);
+        hipLaunchKernelGGL(train_prologue_kernel_grp, dim3(p->nb_idx + p->nb_eps + p->nb_fill, gr->grid_y), dim3(256), 0, st, *p, gr->stride, gr->ring_stride, gr->seeds, gr->live);
     } else
         hipLaunchKernelGGL(train_prologue_kernel, dim3(p->nb_idx + p->nb_eps + p->nb_fill + p->nb_tr), dim3(256), 0, st, *p);
     return (int)hipGetLastError();

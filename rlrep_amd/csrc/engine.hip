@@ -29,7 +29,7 @@ struct GrpScope {
     explicit GrpScope(const rlrep_agent* ag) {
         if (!ag || ag->members <= 0) return;
         prev = g_grp; prev_on = g_grp_on;          // (nesting-safe: the enclosing call's group comes back on exit)
-        g_grp.members = ag->members; g_grp.stride = ag->grp_stride; g_grp.ring_stride = ag->grp_ring_stride; g_grp.seeds = ag->grp_seeds; g_grp.hyp = ag->mhyp;
+        g_grp.members = ag->members; g_grp.stride = ag->grp_stride; g_grp.ring_stride = ag->grp_ring_stride; g_grp.seeds = ag->grp_seeds; g_grp.hyp = ag->mhyp; g_grp.live = ag->grp_live; g_grp.grid_y = ag->grp_grid_y;
         g_grp_on = set = true;
     }
     ~GrpScope() { if (set) { g_grp = prev; g_grp_on = prev_on; } }
@@ -1266,7 +1266,11 @@ int32_t rlrep_agent_create(const rlrep_dims* dims, const rlrep_hyper* hyper, con
     return 0;
 }
 
-void rlrep_agent_destroy(rlrep_agent* agent) { if (agent && agent->grp_seeds) (void)hipFree(agent->grp_seeds); delete agent; }
+void rlrep_agent_destroy(rlrep_agent* agent) {
+    if (agent && agent->grp_seeds) (void)hipFree(agent->grp_seeds);
+    if (agent && agent->grp_live) (void)hipFree(agent->grp_live);
+    delete agent;
+}
 
 static int ensure_batch(rlrep_agent* ag, int B) {
     if (B <= 0 || B > ag->d.max_batch) { rl_set_error("batch %d outside (0, max_batch=%d]", B, ag->d.max_batch); return RLREP_ERR_ARG; }
@@ -2064,6 +2068,14 @@ int32_t rlrep_group_create(const rlrep_dims* dims, const rlrep_hyper* hyper, con
     // member's parameters): the programs' device records are member 0's, and a group launch moves every pointer it finds in them
     hipError_t e = hipMalloc((void**)&ag->grp_seeds, sizeof(unsigned long long) * members);
     if (e == hipSuccess) e = hipMemsetAsync(ag->grp_seeds, 0, sizeof(unsigned long long) * members, (hipStream_t)stream);
+    // the live table: everybody live (n_live = members, slot r = member r)
+    LiveTab live0; memset(&live0, 0, sizeof(live0));
+    live0.n_live = members;
+    for (int m = 0; m < members; ++m) live0.slot_member[m] = m;
+    if (e == hipSuccess) e = hipMalloc((void**)&ag->grp_live, sizeof(int) * (1 + members));
+    if (e == hipSuccess) e = hipMemcpyAsync(ag->grp_live, &live0, sizeof(int) * (1 + members), hipMemcpyHostToDevice, (hipStream_t)stream);   // (synchronised below)
+    ag->grp_live_mask.assign(members, 1);
+    ag->grp_compact = rl_opt("grp_compact") != nullptr; ag->grp_grid_y = members;
     const char* lo = (const char*)arenas->param_dev;
     for (const void* q : {(const void*)arenas->target_dev, (const void*)arenas->grad_dev, (const void*)arenas->exp_avg_dev, (const void*)arenas->exp_avg_sq_dev,
                           (const void*)arenas->workspace_dev, (const void*)arenas->alpha_state_dev}) lo = std::min(lo, (const char*)q);
@@ -2190,6 +2202,31 @@ int32_t rlrep_group_clone_members(rlrep_agent* ag, const int32_t* src_host, cons
     ++g_rl_launches;
     const int rc = rl_launch_group_clone(&tab, &pairs, n, (hipStream_t)stream);
     if (rc) { rl_set_error("group_clone_members: launch failed (%d)", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+extern "C" int rl_launch_group_live(int* table_dev, const LiveTab* tab, int members, hipStream_t st);
+int32_t rlrep_group_set_live(rlrep_agent* ag, const int32_t* live_host, void* stream) {
+    if (!ag || ag->members <= 0) { rl_set_error("group_set_live: not a seed group"); return RLREP_ERR_ARG; }
+    if (!live_host) { rl_set_error("group_set_live: null mask"); return RLREP_ERR_ARG; }
+    LiveTab tab; memset(&tab, 0, sizeof(tab));
+    for (int m = 0; m < ag->members; ++m) {
+        if (live_host[m] != 0 && live_host[m] != 1) { rl_set_error("group_set_live: mask[%d] = %d is neither 0 nor 1", m, live_host[m]); return RLREP_ERR_ARG; }
+        if (live_host[m]) tab.slot_member[tab.n_live++] = m;
+    }
+    if (tab.n_live < 1) { rl_set_error("group_set_live: no live member (at least one member of a group stays live)"); return RLREP_ERR_ARG; }
+    if (ag->in_train) { rl_set_error("group_set_live: inside a train() (between rlrep_group_train_prologue and the end of that train())"); return RLREP_ERR_ARG; }
+    // the slots behind n_live name no member (0): a launch never reads them
+    ++g_rl_launches;
+    const int rc = rl_launch_group_live(ag->grp_live, &tab, ag->members, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_set_live: launch failed (%d)", rc); return RLREP_ERR_HIP; }
+    ag->grp_live_mask.assign(live_host, live_host + ag->members);
+    ag->grp_grid_y = ag->grp_compact ? tab.n_live : ag->members;
+    return 0;
+}
+int32_t rlrep_group_get_live(rlrep_agent* ag, int32_t* live_out) {
+    if (!ag || ag->members <= 0) { rl_set_error("group_get_live: not a seed group"); return RLREP_ERR_ARG; }
+    if (!live_out) { rl_set_error("group_get_live: null output"); return RLREP_ERR_ARG; }
+    for (int m = 0; m < ag->members; ++m) live_out[m] = ag->grp_live_mask[m];
     return 0;
 }
 // [p, p + bytes) inside member 0's block [grp_lo, grp_lo + stride): what a group launch moves by r * stride must stay in member r's block

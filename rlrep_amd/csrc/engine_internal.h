@@ -16,6 +16,11 @@ struct rlrep_agent {
     long long grp_ring_stride = 0;         // bytes between two members' replay rings, as the last group train prologue was given
     MemberHyper* mhyp = nullptr;           // by-value hyper record (kparams.h; workspace, static_state): member 0's, read by the group kernel forms only
     std::vector<rlrep_hyper> grp_hyper;    // [members] each member's hyper-parameters (rlrep_group_set_member_hyper)
+    int* grp_live = nullptr;               // the live table (group.h LiveTab; device, an allocation of its own), rlrep_group_set_live
+    std::vector<int32_t> grp_live_mask;    // [members] 1 = live: what the table was last built from
+    // RLREP_ENABLE=grp_compact (measured, not adopted: profiles/seed_batch_halving.txt): grid y of the group launches is the number of live
+    // members instead of `members`; a graph captured before members were revived must then be captured again (the caller's business)
+    bool grp_compact = false; int grp_grid_y = 0;
     int B = 0;
     int* steps = nullptr; GroupCfg* adam_step = nullptr; float* metrics = nullptr; float* obs_in = nullptr; float* act_out = nullptr;
     Slot slot[2];

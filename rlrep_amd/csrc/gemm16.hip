@@ -215,7 +215,8 @@ __global__ __launch_bounds__(256) void gemm16_fastpre_kernel(int hdr, const floa
 // the x decomposition, the tile body and its summation order are the single-agent kernel's
 template <int LA, int LB, int NF, bool VA, bool VB, bool PRE = false, int EPI_K = -1, int ACT_K = -1, bool MSE = false, int NJ_K = 0>
 __global__ __launch_bounds__(256) void gemm16_kernel_grp(int hdr, int total, int tb0, int tb1, int tb2, int tb3, int tb4, int tb5, int tb6, int tb7,
-                                                         unsigned tc01, unsigned tc23, unsigned tc45, unsigned tc67, GemmBatch gb, long long mstride) {
+                                                         unsigned tc01, unsigned tc23, unsigned tc45, unsigned tc67, GemmBatch gb, long long mstride, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
     __shared__ float red[4][NF][4][64];
     __shared__ float bsum[4][16];
     const int low_prio = hdr & 1;
@@ -234,18 +235,19 @@ __global__ __launch_bounds__(256) void gemm16_kernel_grp(int hdr, int total, int
 #pragma unroll
     for (int q = 1; q < GEMM_MAX_TASKS; ++q) if (bid >= tb[q]) { ti = q; base = tb[q]; tiles_c = tcs[q]; }
     GemmTask t = gb.t[ti];
-    rl_rebase(t, (long long)blockIdx.y * mstride);
+    rl_rebase(t, (long long)member * mstride);
     const int local = bid - base;
     const int tr = local / tiles_c, tc = local - tr * tiles_c;
     gemm16_tile<LA, LB, NF, VA, VB, PRE, false, GemmTask, EPI_K, ACT_K, false, MSE, 0, NJ_K>(t, tr, tc, red, bsum, nullptr RL_TIM_NONE);
 }
 template <int LA, int LB, int NF, bool VA, bool VB, int EPI_K, int ACT_K, int FU = 4>
 __global__ __launch_bounds__(256) void gemm16_fast_kernel_grp(int hdr, int tb1, const float* base, unsigned a0, unsigned b0, unsigned ld0, unsigned kr0, unsigned ct0,
-                                                              unsigned a1, unsigned b1, unsigned ld1, unsigned kr1, unsigned ct1, GemmBatch gb, long long mstride) {
+                                                              unsigned a1, unsigned b1, unsigned ld1, unsigned kr1, unsigned ct1, GemmBatch gb, long long mstride, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
     __shared__ float red[4][NF][4][64];
     __shared__ float bsum[4][16];
     if (!(hdr & 1)) __builtin_amdgcn_s_setprio(3);
-    const long long dm = (long long)blockIdx.y * mstride;
+    const long long dm = (long long)member * mstride;
     base = (const float*)((uintptr_t)base + (uintptr_t)dm);
     const int bid = blockIdx.x;
     const bool second = bid >= tb1;
@@ -263,11 +265,12 @@ __global__ __launch_bounds__(256) void gemm16_fast_kernel_grp(int hdr, int tb1, 
 }
 template <int LA, int LB, int NF, bool VA, bool VB, int EPI_K, int ACT_K, int FU = 4>
 __global__ __launch_bounds__(256) void gemm16_fast4_kernel_grp(int hdr, const float* base, unsigned ld, unsigned kr, unsigned ct, unsigned a0, unsigned b0, unsigned a1, unsigned b1,
-                                                               unsigned a2, unsigned b2, unsigned a3, unsigned b3, GemmBatch gb, long long mstride) {
+                                                               unsigned a2, unsigned b2, unsigned a3, unsigned b3, GemmBatch gb, long long mstride, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
     __shared__ float red[4][NF][4][64];
     __shared__ float bsum[4][16];
     if (!(hdr & 1)) __builtin_amdgcn_s_setprio(3);
-    const long long dm = (long long)blockIdx.y * mstride;
+    const long long dm = (long long)member * mstride;
     base = (const float*)((uintptr_t)base + (uintptr_t)dm);
     const int bid = blockIdx.x, nt = hdr >> 8;
     int ti = (bid >= nt ? 1 : 0) + (bid >= 2 * nt ? 1 : 0) + (bid >= 3 * nt ? 1 : 0);
@@ -285,11 +288,12 @@ __global__ __launch_bounds__(256) void gemm16_fast4_kernel_grp(int hdr, const fl
 }
 template <int EPI_K, int ACT_K, bool MSE, int NJ_K = 0>
 __global__ __launch_bounds__(256) void gemm16_fastpre_kernel_grp(int hdr, const float* base, unsigned ao, unsigned bo, unsigned ld, unsigned kr, unsigned ck, unsigned xo, unsigned wo, unsigned mo,
-                                                                 unsigned ldxw, unsigned ldm, GemmBatch gb, long long mstride) {
+                                                                 unsigned ldxw, unsigned ldm, GemmBatch gb, long long mstride, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
     __shared__ float red[4][1][4][64];
     __shared__ float bsum[4][16];
     if (!(hdr & 1)) __builtin_amdgcn_s_setprio(3);
-    const long long dm = (long long)blockIdx.y * mstride;
+    const long long dm = (long long)member * mstride;
     base = (const float*)((uintptr_t)base + (uintptr_t)dm);
     const int bid = blockIdx.x, sh = hdr >> 8;
     const int tr = bid >> sh, tc = bid & ((1 << sh) - 1);
@@ -305,7 +309,7 @@ __global__ __launch_bounds__(256) void gemm16_fastpre_kernel_grp(int hdr, const 
 // a launch of kernel KN<TA...>: its group form when a group is active (rl_grp_active), grid (x, members)
 #define RL_LAUNCH16(KN, TA, g, st, ...) do { \
         const RlGrp* gr_ = rl_grp_active(); \
-        if (gr_) hipLaunchKernelGGL((KN##_grp<RL_UNPAREN TA>), dim3((g).x, gr_->members), dim3(256), 0, st, __VA_ARGS__, gr_->stride); \
+        if (gr_) hipLaunchKernelGGL((KN##_grp<RL_UNPAREN TA>), dim3((g).x, gr_->grid_y), dim3(256), 0, st, __VA_ARGS__, gr_->stride, gr_->live); \
         else hipLaunchKernelGGL((KN<RL_UNPAREN TA>), g, dim3(256), 0, st, __VA_ARGS__); \
     } while (0)
 
@@ -429,7 +433,8 @@ __global__ __launch_bounds__(256) void gemm16_duo_kernel(int hdr, int total, int
 // group form (group.h): member = blockIdx.y, the task record rebased by member * stride (as gemm16_kernel_grp); x decomposition and tile bodies as above
 template <bool VA1, int NF2>
 __global__ __launch_bounds__(256) void gemm16_duo_kernel_grp(int hdr, int total, int tb0, int tb1, int tb2, int tb3, int tb4, int tb5, int tb6, int tb7,
-                                                             unsigned tc01, unsigned tc23, unsigned tc45, unsigned tc67, GemmBatch gb, long long mstride) {
+                                                             unsigned tc01, unsigned tc23, unsigned tc45, unsigned tc67, GemmBatch gb, long long mstride, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
     __shared__ float red[4][NF2][4][64];
     __shared__ float bsum[4][16];
     const int low_prio = hdr & 1, split = hdr >> 4;
@@ -442,7 +447,7 @@ __global__ __launch_bounds__(256) void gemm16_duo_kernel_grp(int hdr, int total,
 #pragma unroll
     for (int q = 1; q < GEMM_MAX_TASKS; ++q) if (bid >= tb[q]) { ti = q; base = tb[q]; tiles_c = tcs[q]; }
     GemmTask t = gb.t[ti];
-    rl_rebase(t, (long long)blockIdx.y * mstride);
+    rl_rebase(t, (long long)member * mstride);
     const int local = bid - base;
     const int tr = local / tiles_c, tc = local - tr * tiles_c;
     (void)total;

@@ -226,8 +226,9 @@ __global__ __launch_bounds__(256, (BT == 128 ? 2 : 4)) void gemm_lds_kernel(GL_D
 }
 // group form (group.h): member = blockIdx.y
 template <int BT, int LA, int LB>
-__global__ __launch_bounds__(256, (BT == 128 ? 2 : 4)) void gemm_lds_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride) {
-    constexpr bool GRP = true; const long long dm = (long long)blockIdx.y * mstride;
+__global__ __launch_bounds__(256, (BT == 128 ? 2 : 4)) void gemm_lds_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
+    constexpr bool GRP = true; const long long dm = (long long)member * mstride;
 #include "gemm_lds_body.h"
 }
 
@@ -266,8 +267,9 @@ __global__ __launch_bounds__(256) void gemm_lds_fin_kernel(GL_DIR_PARAMS, GemmBa
     gemm_lds_fin_kernel_body<false>(GL_DIR_FWD, gb, 0);
 }
 // group form (group.h): member = blockIdx.y; the tasks' pointers are moved by member * stride where the body loads them
-__global__ __launch_bounds__(256) void gemm_lds_fin_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride) {
-    gemm_lds_fin_kernel_body<true>(GL_DIR_FWD, gb, (long long)blockIdx.y * mstride);
+__global__ __launch_bounds__(256) void gemm_lds_fin_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
+    gemm_lds_fin_kernel_body<true>(GL_DIR_FWD, gb, (long long)member * mstride);
 }
 
 // ================================================================================================
@@ -365,8 +367,9 @@ __global__ __launch_bounds__(512, 4) void gemm_x3_kernel(GL_DIR_PARAMS, GemmBatc
 }
 // group form (group.h): member = blockIdx.y
 template <int LA, int LB>
-__global__ __launch_bounds__(512, 4) void gemm_x3_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride) {
-    constexpr bool GRP = true; const long long dm = (long long)blockIdx.y * mstride;
+__global__ __launch_bounds__(512, 4) void gemm_x3_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
+    constexpr bool GRP = true; const long long dm = (long long)member * mstride;
 #include "gemm_x3_body.h"
 }
 
@@ -440,8 +443,9 @@ __global__ __launch_bounds__(512, 4) void gemm_x3t_kernel(GL_DIR_PARAMS, GemmBat
 }
 // group form (group.h): member = blockIdx.y
 template <int LA>
-__global__ __launch_bounds__(512, 4) void gemm_x3t_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride) {
-    constexpr bool GRP = true; const long long dm = (long long)blockIdx.y * mstride;
+__global__ __launch_bounds__(512, 4) void gemm_x3t_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
+    constexpr bool GRP = true; const long long dm = (long long)member * mstride;
 #include "gemm_x3t_body.h"
 }
 
@@ -633,8 +637,9 @@ __global__ __launch_bounds__(256, 3) void gemm_x3s_kernel(GL_DIR_PARAMS, GemmBat
 }
 // group form (group.h): member = blockIdx.y
 template <int LA, int LB, int VEC>
-__global__ __launch_bounds__(256, 3) void gemm_x3s_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride) {
-    constexpr bool GRP = true; const long long dm = (long long)blockIdx.y * mstride;
+__global__ __launch_bounds__(256, 3) void gemm_x3s_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
+    constexpr bool GRP = true; const long long dm = (long long)member * mstride;
 #include "gemm_x3s_body.h"
 }
 
@@ -647,7 +652,7 @@ __global__ __launch_bounds__(256, 3) void gemm_x3s_kernel_grp(GL_DIR_PARAMS, Gem
 // follow member r - 1's in dispatch order, so the XCD that gl_xcd_remap deals a tile to is shifted by r * gridDim.x: same tiles, another XCD.)
 #define GL_LAUNCH(KN, TA, g, nt, st, ...) do { \
         const RlGrp* gr_ = rl_grp_active(); \
-        if (gr_) hipLaunchKernelGGL((KN##_grp<RL_UNPAREN TA>), dim3((g).x, gr_->members), dim3(nt), 0, st, __VA_ARGS__, gr_->stride); \
+        if (gr_) hipLaunchKernelGGL((KN##_grp<RL_UNPAREN TA>), dim3((g).x, gr_->grid_y), dim3(nt), 0, st, __VA_ARGS__, gr_->stride, gr_->live); \
         else hipLaunchKernelGGL((KN<RL_UNPAREN TA>), g, dim3(nt), 0, st, __VA_ARGS__); \
     } while (0)
 
@@ -737,7 +742,7 @@ extern "C" int rl_launch_gemm_lds(int bt, int la, int lb, const GemmBatch* gb, i
            : bt == 128 ? launch_bt<128>(la, lb, dim3(total_tiles), st, *gb, dir) : launch_bt<64>(la, lb, dim3(total_tiles), st, *gb, dir);
     if (rc != 0) return rc;
     if (fin_blocks > 0) {
-        if (gr) hipLaunchKernelGGL(gemm_lds_fin_kernel_grp, dim3(fin_blocks, gr->members), dim3(256), 0, st, GL_DIR_ARGS(fdir), *gb, gr->stride);
+        if (gr) hipLaunchKernelGGL(gemm_lds_fin_kernel_grp, dim3(fin_blocks, gr->grid_y), dim3(256), 0, st, GL_DIR_ARGS(fdir), *gb, gr->stride, gr->live);
         else hipLaunchKernelGGL(gemm_lds_fin_kernel, dim3(fin_blocks), dim3(256), 0, st, GL_DIR_ARGS(fdir), *gb);
         ++g_rl_launches;              // split-K: the stage is two kernels
         rc = (int)hipGetLastError();

@@ -91,7 +91,8 @@ __global__ __launch_bounds__(256, 2) void gemm_x3q_kernel(GL_DIR_PARAMS, GemmBat
 }
 // group form (group.h): member = blockIdx.y
 template <int LB>
-__global__ __launch_bounds__(256, 2) void gemm_x3q_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride) {
-    constexpr bool GRP = true; const long long dm = (long long)blockIdx.y * mstride;
+__global__ __launch_bounds__(256, 2) void gemm_x3q_kernel_grp(GL_DIR_PARAMS, GemmBatch gb, long long mstride, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
+    constexpr bool GRP = true; const long long dm = (long long)member * mstride;
 #include "gemm_x3q_body.h"
 }

@@ -1,6 +1,6 @@
 // Seed groups (rlrep_group_create): R agents of identical shape whose blocks lie at a constant byte stride in ONE allocation.  The step
-// programs are built once, against member 0; a launch issued while a group is active runs every member at once -- member r is
-// blockIdx.y -- and rebases EVERY pointer it dereferences by r * stride (the replay ring by r * ring_stride, the ring's size word by r).
+// programs are built once, against member 0; a launch issued while a group is active runs every live member at once -- grid y is a slot of
+// the live table (RL_GRP_MEMBER below; slot r is member r while nobody is retired) -- and rebases EVERY pointer it dereferences by r * stride (the replay ring by r * ring_stride, the ring's size word by r).
 // The grid's x dimension, the tile decomposition and every summation order are a standalone agent's: member r computes bit for bit
 // what SACAgent(seed = s_r) computes.  No member reads another member's words.
 //
@@ -21,12 +21,24 @@ struct RlGrp {
     long long ring_stride;              // bytes between two members' replay rings (train prologue only)
     const unsigned long long* seeds;    // [members] Philox seeds (device), train prologue only
     const MemberHyper* hyp;             // member 0's by-value hyper-parameters (kparams.h); member r's lie r * stride further
+    const int* live;                    // the live table (device): n_live, then slot_member[members] -- see RL_GRP_MEMBER
+    int grid_y;                         // grid y of the group launches: members (RLREP_ENABLE=grp_compact: the live members at the last rlrep_group_set_live)
 };
 extern "C" const RlGrp* rl_grp_active();
 // what a launcher without a group form returns while a group is active (the stage fails with this code: no member is left behind silently)
 #define RL_GRP_UNSUPPORTED 77
 
 #define RL_UNPAREN(...) __VA_ARGS__
+
+// Retired members (rlrep_group_set_live).  One device table per group, an allocation of its own: int n_live, then int slot_member[members], the
+// live members in ascending order.  Grid y stays `members` (captured graphs are kept); every group kernel form begins with RL_GRP_MEMBER(m, live):
+// slot = blockIdx.y, a slot at or behind n_live returns, otherwise m = slot_member[slot].  Both reads are wave-uniform (scalar loads) and the
+// return comes before any LDS use, barrier, ticket or counter access.  A member's blocks all leave or all stay, so the per-member protocols
+// (split-K tickets, "last block finalises", the prologue's ticket) stay sound, and a retired member's block is neither read nor written.
+struct LiveTab { int n_live; int slot_member[RLREP_GROUP_MAX_MEMBERS]; };
+#define RL_GRP_MEMBER(m, live) \
+    if ((int)blockIdx.y >= (live)[0]) return; \
+    const int m = (live)[1 + blockIdx.y]
 
 // rlrep_group_clone_members (group_clone.hip): what one clone launch copies from member src's block to member dst's, both by value in the
 // kernel arguments.  A segment is [off, off + bytes) from the member block's base, both multiples of 4.  Segment rec_seg holds the device

@@ -52,6 +52,19 @@ __global__ __launch_bounds__(256) void group_clone_kernel(CloneTab tab, ClonePai
     }
 }
 
+// rlrep_group_set_live: the group's live table (group.h LiveTab) rewritten from the kernel arguments, one word per lane -- stream-ordered like
+// any launch, so a captured train() graph obeys it from its next replay and the host keeps no staging buffer alive.
+__global__ __launch_bounds__(128) void group_live_kernel(int* __restrict__ table, LiveTab tab, int members) {
+    const int w = threadIdx.x;
+    if (w == 0) table[0] = tab.n_live;
+    else if (w <= members) table[w] = tab.slot_member[w - 1];
+}
+extern "C" int rl_launch_group_live(int* table_dev, const LiveTab* tab, int members, hipStream_t st) {
+    if (members < 1 || members > RLREP_GROUP_MAX_MEMBERS) return -7;
+    hipLaunchKernelGGL(group_live_kernel, dim3(1), dim3(128), 0, st, table_dev, *tab, members);
+    return (int)hipGetLastError();
+}
+
 extern "C" int rl_launch_group_clone(const CloneTab* tab, const ClonePairs* pairs, int npairs, hipStream_t st) {
     long long longest = 0;
     for (int s = 0; s < tab->nseg; ++s) longest = std::max(longest, tab->seg[s].bytes);

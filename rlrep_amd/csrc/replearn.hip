@@ -14,9 +14,10 @@ __global__ __launch_bounds__(256) void infonce_kernel(InfoNce p) {
 #include "infonce_body.h"
 }
 // group form (group.h): member = blockIdx.y, every pointer of the record moved by member * stride
-__global__ __launch_bounds__(256) void infonce_kernel_grp(InfoNce p0, long long mstride) {
+__global__ __launch_bounds__(256) void infonce_kernel_grp(InfoNce p0, long long mstride, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
     InfoNce p = p0;
-    rl_rebase(p, (long long)blockIdx.y * mstride);
+    rl_rebase(p, (long long)member * mstride);
 #include "infonce_body.h"
 }
 
@@ -565,8 +566,9 @@ __global__ __launch_bounds__(256) void copy2_kernel(const float* __restrict__ sr
     }
 }
 // group form (group.h): member = blockIdx.y; the three arrays moved by member * stride (d2 stays null where it is null)
-__global__ __launch_bounds__(256) void copy2_kernel_grp(const float* src, float* d1, float* d2, long long n, long long mstride) {
-    const long long dm = (long long)blockIdx.y * mstride;
+__global__ __launch_bounds__(256) void copy2_kernel_grp(const float* src, float* d1, float* d2, long long n, long long mstride, const int* __restrict__ live) {
+    RL_GRP_MEMBER(member, live);
+    const long long dm = (long long)member * mstride;
     rl_rb(src, dm); rl_rb(d1, dm); rl_rb(d2, dm);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const float v = src[i];
@@ -625,7 +627,7 @@ extern "C" int rl_launch_infonce(const InfoNce* p, hipStream_t st) {
         hipLaunchKernelGGL(score_infonce_kernel, dim3(p->nblk), dim3(256), 0, st, *p);
         return (int)hipGetLastError();
     }
-    if (gr) hipLaunchKernelGGL(infonce_kernel_grp, dim3(p->nblk, gr->members), dim3(256), 0, st, *p, gr->stride);
+    if (gr) hipLaunchKernelGGL(infonce_kernel_grp, dim3(p->nblk, gr->grid_y), dim3(256), 0, st, *p, gr->stride, gr->live);
     else hipLaunchKernelGGL(infonce_kernel, dim3(p->nblk), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }
@@ -688,7 +690,7 @@ extern "C" int rl_launch_diffsr_score(const DiffsrScore* p, hipStream_t st) {
 }
 extern "C" int rl_launch_copy2(const float* src, float* d1, float* d2, long long n, hipStream_t st) {
     int g = (int)((n + 1023) / 1024); if (g > 2048) g = 2048; if (g < 1) g = 1;
-    if (const RlGrp* gr = rl_grp_active()) hipLaunchKernelGGL(copy2_kernel_grp, dim3(g, gr->members), dim3(256), 0, st, src, d1, d2, n, gr->stride);
+    if (const RlGrp* gr = rl_grp_active()) hipLaunchKernelGGL(copy2_kernel_grp, dim3(g, gr->grid_y), dim3(256), 0, st, src, d1, d2, n, gr->stride, gr->live);
     else hipLaunchKernelGGL(copy2_kernel, dim3(g), dim3(256), 0, st, src, d1, d2, n);
     return (int)hipGetLastError();
 }

@@ -22,6 +22,13 @@ one launch) and take its hyper-parameters with every `--pbt-keys` entry multipli
 (set_member_hyper).  The defaults 0.25 / 0.8,1.2 are the paper's.  Every event is one line of `log/<env>/<alg>/<dir>/pbt.jsonl` (step, src,
 dst, scores, old and new values); the members' metrics.jsonl rows are unchanged, and a sweep tag directory keeps naming the member's INITIAL
 configuration, whatever PBT has made of it since.
+
+`--halving-interval N` (with --seeds / --sweep; N environment steps, a multiple of --eval_freq; 0 = off) runs successive halving (Jamieson &
+Talwalkar 2016) on the group: at every step t + 1 that is a multiple of N beyond start_timesteps the live members are ranked by their latest
+evaluation and all but the best `--halving-keep` (default 0.5, rounded up) are retired (SeedBatchMixin.retire_members: their workgroups leave
+every launch), never below `--halving-min` live members (default 1).  A retired member's environment is no longer stepped or evaluated and its
+metrics.jsonl stops growing; its state stays in the group (and in --save_model checkpoints).  Every halving is one line of
+`log/<env>/<alg>/<dir>/halving.jsonl` (step, retired members with their seeds and scores, live count).  Not together with --pbt-interval.
 """
 import argparse
 import json
@@ -88,11 +95,16 @@ def run(argv=None):
     p.add_argument('--pbt-keys', default=None, help='comma-separated hyper-parameters a copied member perturbs (default lr)')
     p.add_argument('--pbt-factors', default=None, help='comma-separated factors a perturbed value is multiplied by (default 0.8,1.2)')
     p.add_argument('--pbt-seed', default=None, type=int, help='seed of the PBT draws (default 0)')
+    p.add_argument('--halving-interval', default=None, type=int, help='successive halving every N environment steps (a multiple of --eval_freq; 0 = off)')
+    p.add_argument('--halving-keep', default=None, type=float, help='share of the live members that stay at a halving step, rounded up (default 0.5)')
+    p.add_argument('--halving-min', default=None, type=int, help='stop retiring at this many live members (default 1)')
     args = p.parse_args(argv)
     if args.seeds is not None or args.sweep:
         return run_seeds(args)
     if _pbt_requested(args):
         raise SystemExit('--pbt-*: population-based training needs a seed group (--seeds and / or --sweep)')
+    if _halving_requested(args):
+        raise SystemExit('--halving-*: successive halving needs a seed group (--seeds and / or --sweep)')
 
     env, eval_env = envs.make(args.env), envs.make(args.env)
     env.seed(args.seed)
@@ -275,6 +287,49 @@ def pbt_step(agent, scores, cfg, rng, step, log):
     return pairs
 
 
+HALVING_OPTIONS = ('halving_interval', 'halving_keep', 'halving_min')
+
+
+def _halving_requested(args):
+    # (--halving-interval 0 alone is "off", spelled out)
+    return bool(args.halving_interval) or any(getattr(args, k) is not None for k in HALVING_OPTIONS if k != 'halving_interval')
+
+
+def parse_halving(args, members, pbt_cfg):
+    """--halving-* -> None (off) or dict(interval, keep, min).  SystemExit on fewer than 2 members, an interval that is not a positive multiple
+    of --eval_freq, keep outside (0, 1), min below 1, or together with --pbt-interval."""
+    import math
+    if not _halving_requested(args):
+        return None
+    if members < 2:
+        raise SystemExit(f'--halving-interval: successive halving needs at least 2 members (the group has {members})')
+    interval, freq = int(args.halving_interval or 0), int(args.eval_freq)
+    if interval <= 0 or freq <= 0 or interval % freq:
+        raise SystemExit(f'--halving-interval {args.halving_interval}: give a positive multiple of --eval_freq ({freq}): members are ranked by their latest evaluation')
+    keep = 0.5 if args.halving_keep is None else float(args.halving_keep)
+    if not (math.isfinite(keep) and 0.0 < keep < 1.0):
+        raise SystemExit(f'--halving-keep {args.halving_keep}: outside (0, 1)')
+    least = 1 if args.halving_min is None else int(args.halving_min)
+    if least < 1:
+        raise SystemExit(f'--halving-min {args.halving_min}: below 1 (at least one member of a group stays live)')
+    if pbt_cfg is not None:
+        raise SystemExit('--halving-interval together with --pbt-interval: population-based training over a shrinking population is a later change; '
+                         'run one of the two')
+    return dict(interval=interval, keep=keep, min=least)
+
+
+def halving_step(agent, scores, seeds, cfg, step, log):
+    """One halving on a seed group: plan, retire the losers (one launch), one `log` line.  Returns the retired members."""
+    from rlrep_amd.agent import pbt
+    out = pbt.plan_halving(scores, agent.live, cfg['keep'], cfg['min'])
+    if out:
+        agent.retire_members(out)
+        log.write(json.dumps({'step': int(step), 'retired': [int(r) for r in out], 'seeds': [int(seeds[r]) for r in out],
+                              'scores': [float(scores[r]) for r in out], 'live': int(sum(agent.live))}) + '\n')
+        log.flush()
+    return out
+
+
 def run_seeds(args):
     """The loop of run() for several seeds at once: R environments in lockstep, one SACSeedBatch, one ReplayBufferGroup."""
     seeds = [int(s) for s in str(args.seeds).split(',') if s.strip() != ''] if args.seeds is not None else [int(args.seed)]
@@ -288,6 +343,7 @@ def run_seeds(args):
     member_hyper = [cfg for _, cfg in configs for _ in seeds] if swept else None
     seeds = [s for _ in configs for s in seeds]              # member = (configuration, seed), configurations outermost
     pbt_cfg = parse_pbt(args, args.alg, len(seeds))
+    halving_cfg = parse_halving(args, len(seeds), pbt_cfg)
     from rlrep_amd.utils.buffer_group import ReplayBufferGroup
     R = len(seeds)
     envs_, evals_ = [envs.make(args.env) for _ in seeds], [envs.make(args.env) for _ in seeds]
@@ -322,12 +378,19 @@ def run_seeds(args):
     if pbt_cfg is not None:
         pbt_rng = np.random.RandomState(pbt_cfg['seed'])
         pbt_log = open(os.path.join(args.log_root, args.env, args.alg, str(args.dir), 'pbt.jsonl'), 'a')
+    halving_log = None
+    if halving_cfg is not None:
+        halving_log = open(os.path.join(args.log_root, args.env, args.alg, str(args.dir), 'halving.jsonl'), 'a')
+    live = agent.live
+    staged = None                           # the rows of the last replay.add: a retired member's ring takes its last row again (nobody samples it)
     timer = util.Timer()
     for t in range(int(args.max_timesteps)):
         ep_steps += 1
         greedy = None if t < args.start_timesteps else agent.select_action(states, explore=True)
         actions = np.zeros((R, action_dim), np.float32)
         for r in range(R):
+            if not live[r]:
+                continue
             if t < args.start_timesteps or rngs[r].uniform(0, 1) < EPS_GREEDY:
                 actions[r] = rngs[r].uniform(lo, hi)
             else:
@@ -335,12 +398,18 @@ def run_seeds(args):
         nexts, rewards, dones = np.zeros_like(states), np.zeros(R, np.float32), np.zeros(R, np.float32)
         resets = []
         for r, e in enumerate(envs_):
+            if not live[r]:
+                continue
             ns, rew, done, _ = e.step(actions[r])
             nexts[r], rewards[r] = ns, rew
             dones[r] = float(done) if ep_steps[r] < max_length else 0.0
             if done:
                 resets.append(r)
+        for r in range(R):
+            if not live[r]:
+                states[r], actions[r], nexts[r], rewards[r], dones[r] = (a[r] for a in staged)
         replay.add(states, actions, nexts, rewards, dones)
+        staged = (states, actions, nexts, rewards, dones)
         states = nexts.copy()
         for r in resets:
             states[r] = envs_[r].reset()
@@ -350,6 +419,8 @@ def run_seeds(args):
         if (t + 1) % args.eval_freq == 0:
             sps = timer.steps_per_sec(t + 1)
             for r in range(R):
+                if not live[r]:
+                    continue
                 evaluations[r].append(util.eval_policy(policies[r], evals_[r], args.eval_episodes))
                 if infos is not None:
                     row = {'step': t + 1, 'info/evaluation': float(evaluations[r][-1]), 'steps_per_sec': sps}
@@ -359,9 +430,12 @@ def run_seeds(args):
             print('Step {}. Steps per sec (per seed): {:.4g}.'.format(t + 1, sps))
             if pbt_cfg is not None and (t + 1) % pbt_cfg['interval'] == 0 and t + 1 > args.start_timesteps:
                 pbt_step(agent, [evaluations[r][-1] for r in range(R)], pbt_cfg, pbt_rng, t + 1, pbt_log)
+            if halving_cfg is not None and (t + 1) % halving_cfg['interval'] == 0 and t + 1 > args.start_timesteps:
+                halving_step(agent, [evaluations[r][-1] for r in range(R)], seeds, halving_cfg, t + 1, halving_log)
+                live = agent.live
             if args.save_model:
                 agent.save(os.path.join(args.log_root, args.env, args.alg, str(args.dir), 'seed_batch.pt'))
-    for f in logs + ([pbt_log] if pbt_log is not None else []):
+    for f in logs + [f for f in (pbt_log, halving_log) if f is not None]:
         f.close()
     print('Total time cost {:.4g}s.'.format(timer.time_cost()))
     return agent, evaluations

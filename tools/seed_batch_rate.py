@@ -16,6 +16,12 @@ per pair five `copy_` between the members' arena views, then the device records 
 (what SeedBatchMixin.load() does from the host).  Device events around 100 calls after 10 warm-up calls, the two forms alternated, median of
 --windows windows.  The clone must not be the slower one at any shape (exit status 1 otherwise).
 
+--retire 0,4,6,7: successive halving at R = 8.  For every K the group with its last K members retired (SeedBatchMixin.retire_members: grid y
+stays 8, the retired members' workgroups return at once) against a FRESH group built with only the R' = 8 - K live members, in the same process:
+arms alternated, --repeats repeats (at least 3) per arm of --calls calls after --warmup calls, microseconds per train() as median and min .. max.
+Retiring must make a train() faster than with all members live for every K > 0 (exit status 1 otherwise); the ratio to the fresh group is what
+the empty workgroups cost.
+
 Per R: the group's aggregate rate (R x calls/s), its graph's launch count per call, and the standalone agents' aggregate rate.  Protocol:
 --warmup calls (default 300), then the median of --windows windows (default 5) of --calls calls (default 500), timed by host wall clock
 around a device synchronisation."""
@@ -57,7 +63,11 @@ def main(argv=None):
     p.add_argument('--group-only', action='store_true', help='skip the standalone agents (a profiler run of the group alone)')
     p.add_argument('--sweep', action='store_true', help='a hyper-parameter sweep group against a seed-only group and R standalone agents')
     p.add_argument('--clone', action='store_true', help='time clone_members against per-arena copy_ calls (R = 8, 2 pairs, three shapes)')
+    p.add_argument('--retire', default=None, help='comma-separated numbers of retired members (R = 8): the group against fresh groups of the live members only')
+    p.add_argument('--repeats', type=int, default=3, help='--retire: repeats per arm (at least 3)')
     a = p.parse_args(argv)
+    if a.retire is not None:
+        return retire_main(a)
     if a.clone:
         return clone_main(a)
     if a.sweep:
@@ -158,6 +168,73 @@ def sweep_main(a):
         print(f'{R:>3} {w_rate:>16.0f} {s_rate:>16.0f} {w_rate / s_rate:>12.3f} {launches:>14d} {a_rate:>23.0f} {w_rate / a_rate:>12.2f}', flush=True)
         del agents, rings, alone_bufs
         torch.cuda.empty_cache()
+
+
+def _us_per_call(step, warmup, calls):
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(calls):
+        step()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / calls * 1e6
+
+
+def retire_main(a):
+    from rlrep_amd.utils.buffer_group import ReplayBufferGroup
+    R = 8
+    ks = [int(x) for x in a.retire.split(',')]
+    if not ks or any(not 0 <= k < R for k in ks) or a.repeats < 3:
+        print(f'--retire: give numbers in [0, {R}) and --repeats >= 3')
+        return 2
+    alg, S, A, B, kw = bench.WORKLOADS[a.workload]
+    if alg == 'ctrlsac':
+        from rlrep_amd.agent.ctrlsac.seed_batch import CTRLSACSeedBatch as Group
+    else:
+        from rlrep_amd.agent.sac.seed_batch import SACSeedBatch as Group
+
+    def rings_of(n):
+        rings = ReplayBufferGroup(n, S, A, max_size=bench.REPLAY_N)
+        for r in range(n):
+            _, data = bench.synth_buffer(S, A, r)
+            rings.load(r, data['state'], data['action'], data['next_state'], data['reward'], data['done'])
+        return rings
+    print(f'# {a.workload}: S={S} A={A} B={B} {kw}; {Group.__name__} R = {R} with K members retired against a fresh group of the R - K live members; '
+          f'{torch.cuda.get_device_name(0)}; us per train(), median (min .. max) of {a.repeats} repeats x {a.calls} calls after {a.warmup} warm-up calls, '
+          'arms alternated')
+    big, big_rings = Group(list(range(R)), S, A, bench.Space(A), max_batch=B, **kw), rings_of(R)
+    fresh = {k: (Group(list(range(R - k)), S, A, bench.Space(A), max_batch=B, **kw), rings_of(R - k)) for k in sorted(set(ks))}
+    t_big, t_fresh = {k: [] for k in ks}, {k: [] for k in ks}
+    for _ in range(a.repeats):
+        for k in ks:
+            want = [r < R - k for r in range(R)]
+            live = big.live
+            back, out = [r for r in range(R) if want[r] and not live[r]], [r for r in range(R) if live[r] and not want[r]]
+            if back:
+                big.revive_members(back)
+            if out:
+                big.retire_members(out)
+            t_big[k].append(_us_per_call(lambda: big.train(big_rings, B), a.warmup, a.calls))
+            g, rg = fresh[k]
+            t_fresh[k].append(_us_per_call(lambda: g.train(rg, B), a.warmup, a.calls))
+    assert big._graph_launches == fresh[ks[0]][0]._graph_launches
+    print(f'{"K":>2} {"live":>4} {"retired group us":>30} {"fresh R - K group us":>30} {"retired/fresh":>14} {"retired/all live":>17}')
+    med = {k: statistics.median(t_big[k]) for k in ks}
+    all_live = med.get(0)
+    slower = []
+    for k in ks:
+        fm = statistics.median(t_fresh[k])
+        b = f'{med[k]:.1f} ({min(t_big[k]):.1f} .. {max(t_big[k]):.1f})'
+        f = f'{fm:.1f} ({min(t_fresh[k]):.1f} .. {max(t_fresh[k]):.1f})'
+        rel = f'{med[k] / all_live:.3f}' if all_live else ''
+        print(f'{k:>2} {R - k:>4} {b:>30} {f:>30} {med[k] / fm:>14.3f} {rel:>17}', flush=True)
+        if all_live and k > 0 and not med[k] < all_live:
+            slower.append(k)
+    if slower:
+        print(f'# FAILED: with {slower} members retired a train() is not faster than with all {R} live')
+        return 1
+    return 0
 
 
 HBM_MEASURED_TBS = 6.29          # measured HBM rate of a float4 copy on the MI355X
