@@ -561,6 +561,52 @@ int32_t rlrep_group_select_action(rlrep_agent* agent, const float* obs_host, int
 int32_t rlrep_group_replay_add_sized(float* ring_dev, int64_t ring_stride_floats, int32_t members, int64_t capacity, int32_t row_floats, int64_t ptr,
                                      const float* rows_host, int64_t rows_stride_floats, int64_t nrows, int32_t* size_dev, int32_t new_size, void* stream);
 
+/* ---- device environments of a seed group (additive to ABI 4) ------------------------------------------------------------------------------
+ * The launcher's group loop (main.py run_seeds) waits for select_action, steps R NumPy environments, draws the exploration actions and stages
+ * R ring rows on the host every iteration, and every evaluation costs episodes x 200 further round trips per member.  A device environment
+ * keeps one record per member on the device (an allocation of its own: the member stride, rlrep_group_clone_members' segments and the
+ * checkpoint device records do not know it) and does all of that in ONE launch per iteration, capturable in front of the group's train()
+ * graph, and one launch per evaluation.  kind 0 = Pendulum-v1 (the public specification as rlrep_amd/envs/pendulum.py restates it; fp64
+ * dynamics in one lane, rounded to fp32 where the host environment rounds); any other kind is RLREP_ERR_ARG.
+ *
+ * Record (256 bytes per member, csrc/group_env.h EnvRecord): double theta, theta_dot, episode_return; int64 ring_ptr, nsteps; int32 t,
+ * ring_size, episodes_done, force; float force_action, act; float obs[4]; double returns[16] (finished episodes, entry episodes_done % 16
+ * is written next); 48 bytes of padding.  Counters (16 bytes, group-wide): int64 t_global (steps since reset), uint64 calls (the
+ * select_action call counter).
+ * Philox streams (counter word 3, where every other draw of the library has a value below 2^17): 0xE0000000 collection -- counter = the
+ * member's nsteps, word 2 = 0 for a step's exploration draws (word 0: the epsilon-greedy test, word 1: the uniform action), word 2 = 1 for
+ * an episode's start state; 0xE1000000 evaluation start states, counter = eval_index * episodes + episode.  Key = the member's seed
+ * (rlrep_group_set_seeds).  The index, noise and select_action streams of train() are untouched.
+ *
+ * rlrep_group_env_step, per LIVE member (a retired member's record, ring and block are neither read nor written): the actor forward on the
+ * record's observation and the exploring sample exactly as rlrep_group_select_action(explore = 1, offset = (calls + 1) << 20) computes them;
+ * a uniform action in [lo, hi] instead while t_global < start_timesteps or with probability eps_greedy (or the record's force_action when
+ * force is set: one shot); the dynamics; the row [s, a, s', r, done_bool = 0] at ring_ptr of ring_dev + member * ring_stride_floats
+ * (rlrep_group_replay_add_sized's layout, row = 9 floats); ring_ptr and ring_size advance (wrap at `capacity`), size_dev[member] = ring_size;
+ * on the 200th step the episode return is filed and a new episode starts.  The launch's last workgroup adds 1 to t_global and, past warm-up,
+ * to calls.  rlrep_group_env_evaluate: workgroup (episode e, member) rolls out one 200-step episode with the mean action
+ * (select_action(explore = 0), clamped to Pendulum's +-2) from its Philox start state and writes the fp64 sum of the fp32 rewards to
+ * out_dev[member * episodes + e] (a retired member's entries are left unwritten); episodes in [1, 64].
+ * rlrep_group_env_reset: every record starts a fresh episode (start state at counter 0), cursors, counters and returns zeroed.
+ * rlrep_group_env_state: copy block `what` (RLREP_ENV_STATE_*) to (write = 0) or from (write = 1) host memory, `bytes` = the block's exact
+ * size (records: 256 * members; counters: 16; the start states of the last evaluation, read only: 16 * members * episodes, [member, episode,
+ * (theta, theta_dot)]); stream-ordered on `stream`, then synchronised.
+ * All launches are stream-ordered and capturable; nothing is allocated after create.  Rejected with RLREP_ERR_ARG and a message, before any
+ * launch: a null pointer, an ordinary agent, state / action dims other than 3 / 1, an environment of another group, a call between
+ * rlrep_group_train_prologue and the end of that train(), episodes outside [1, 64], a capacity below 1 or a ring stride that does not hold it. */
+typedef struct rlrep_group_env rlrep_group_env;
+#define RLREP_ENV_PENDULUM 0
+#define RLREP_ENV_STATE_RECORDS 0
+#define RLREP_ENV_STATE_COUNTERS 1
+#define RLREP_ENV_STATE_EVAL_STARTS 2
+int32_t rlrep_group_env_create(rlrep_agent* agent, int32_t kind, rlrep_group_env** out);
+void rlrep_group_env_destroy(rlrep_group_env* env);
+int32_t rlrep_group_env_reset(rlrep_group_env* env, void* stream);
+int32_t rlrep_group_env_step(rlrep_agent* agent, rlrep_group_env* env, float* ring_dev, int64_t ring_stride_floats, int64_t capacity, int32_t* size_dev,
+                             float lo, float hi, float eps_greedy, int64_t start_timesteps, void* stream);
+int32_t rlrep_group_env_evaluate(rlrep_agent* agent, rlrep_group_env* env, int32_t episodes, uint64_t eval_index, double* out_dev, void* stream);
+int32_t rlrep_group_env_state(rlrep_group_env* env, int32_t what, void* host, int64_t bytes, int32_t write, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,7 +36,7 @@ import torch
 
 from rlrep_amd._lib import lib, check
 from rlrep_amd.core import HipCore, _stream
-from rlrep_amd.agent.sac.sac_agent import ArenaModule
+from rlrep_amd.agent.sac.sac_agent import ArenaModule, _no_gc
 from rlrep_amd.utils import switches as _sw
 
 
@@ -399,6 +399,72 @@ class SeedBatchMixin(object):
 
     update = train
 
+    # ---- device environments (rlrep_amd/envs/device.py): collect, train and score without a host round trip -------------------------------
+    def iterate(self, env, buffers, batch_size, train=True):
+        """One environment step of every live member on the device -- act, explore, step the dynamics, write the ring row
+        (rlrep_group_env_step) -- and, with `train`, one train() of every live member on the rings as they then stand: ONE graph replay, no host
+        round trip.  `env` is a DevicePendulumGroup of this group, `buffers` a ReplayBufferGroup whose cursor the device owns from here on
+        (ReplayBufferGroup.adopt_device_cursor gives it back).  Returns what train() returns, or None without `train`.  The step's exploring
+        draw is the one `select_action(states, explore=True)` would make now: both count calls in the same counter."""
+        name = type(self).__name__
+        if getattr(buffers, 'members', None) != self.R:
+            raise ValueError(f'{name}.iterate: needs a ReplayBufferGroup of {self.R} members')
+        if getattr(env, 'agent', None) is not self:
+            raise ValueError(f'{name}.iterate: the device environment belongs to another group')
+        B, train = int(batch_size), bool(train)
+        buffers.collect_on_device(env)
+        key = (self._graph_cache_key(buffers, B), id(env), train, float(env.eps_greedy), int(env.start_timesteps))
+        graphs = self.__dict__.setdefault('_iter_graphs', {})
+        g = graphs.get(key)
+        if g is None:
+            if train:               # as _capture_prologue: size the programs and allocate the pools outside the capture
+                self._sample_into(buffers, B, 'warm', 0, False)
+                ni, ne = self._pool_sizes(B)
+                self._buf('pool_idx', (ni,), torch.int32)
+                self._buf('pool_eps', (ne,))
+            torch.cuda.synchronize()
+            with _no_gc():
+                s, g = torch.cuda.Stream(), torch.cuda.CUDAGraph()
+                if train:
+                    with self._history_capture(), self._managed_images(), torch.cuda.graph(g, stream=s):
+                        env.step(buffers, env.eps_greedy, env.start_timesteps)
+                        self._body(buffers, B, True)
+                else:
+                    with torch.cuda.graph(g, stream=s):
+                        env.step(buffers, env.eps_greedy, env.start_timesteps)
+            graphs.clear()          # (one form at a time is kept: a warm-up graph gives way to the training graph)
+            graphs[key] = g
+            self._held_env_buffer = buffers
+        if env.calls != self._ctr:              # select_action, a capture or a checkpoint moved the call counter: the device follows (rare)
+            env.set_counters(env.t_global, self._ctr)
+        if train:
+            self._sync_images()
+        g.replay()
+        warm = env.t_global < env.start_timesteps
+        env.t_global += 1
+        if not warm:
+            self._ctr += 1
+            env.calls = self._ctr
+        if not train:
+            return None
+        self.steps += 1
+        return self._history_info() if self._hist else self.core.info()
+
+    def evaluate(self, env, episodes, eval_index=None):
+        """Mean return of `episodes` mean-action episodes per member, [R] float64 (NaN for a retired member): ONE launch
+        (rlrep_group_env_evaluate) and one copy back.  The start states are a function of (member seed, eval_index, episode); by default
+        eval_index counts the evaluations of `env`, so successive evaluations see fresh starts and every member of a sweep sharing a seed the
+        same ones."""
+        if getattr(env, 'agent', None) is not self:
+            raise ValueError(f'{type(self).__name__}.evaluate: the device environment belongs to another group')
+        episodes = int(episodes)
+        if eval_index is None:
+            eval_index = env.eval_index
+            env.eval_index += 1
+        out = torch.full((self.R, episodes), float('nan'), dtype=torch.float64, device=self.core.device)
+        env.evaluate(episodes, eval_index, out)
+        return out.mean(dim=1).cpu().numpy()
+
     def _history_info(self):
         half = max(1, self.core.history_capacity() // 2)
         out = []
@@ -445,16 +511,20 @@ class SeedBatchMixin(object):
                 'device_state': c.device_state().cpu(), 'steps': self.steps, 'noise_ctr': self._ctr, 'seed': self.seeds[r], 'layout': list(c.order),
                 'hyper': self.member_hyper(r)}
 
-    def state_snapshot(self):
-        return {'format': 'rlrep-seed-batch-1', 'seeds': list(self.seeds), 'members': [self.member_snapshot(r) for r in range(self.R)],
+    def state_snapshot(self, env=None):
+        snap = {'format': 'rlrep-seed-batch-1', 'seeds': list(self.seeds), 'members': [self.member_snapshot(r) for r in range(self.R)],
                 'lineage': [dict(e) for e in self.lineage], 'live': list(self._live)}
+        if env is not None:         # a device environment's records and counters (rlrep_amd/envs/device.py)
+            snap['device_env'] = env.snapshot()
+        return snap
 
-    def save(self, path):
-        torch.save(self.state_snapshot(), path)
+    def save(self, path, env=None):
+        torch.save(self.state_snapshot(env), path)
 
-    def load(self, path_or_snapshot, adopt_hyper=False):
+    def load(self, path_or_snapshot, adopt_hyper=False, env=None):
         """adopt_hyper: members whose hyper-parameters differ from the checkpoint's take the checkpoint's (a population-based run is resumed
-        into a group built with the initial values); otherwise such a checkpoint is refused."""
+        into a group built with the initial values); otherwise such a checkpoint is refused.  env: a device environment takes the
+        checkpoint's records, or a fresh reset when the checkpoint carries none."""
         snap = torch.load(path_or_snapshot) if isinstance(path_or_snapshot, (str, bytes, os.PathLike)) else path_or_snapshot
         if snap.get('format') != 'rlrep-seed-batch-1' or list(snap['seeds']) != self.seeds:
             raise RuntimeError('checkpoint does not match this seed batch (format / seeds differ)')
@@ -489,3 +559,8 @@ class SeedBatchMixin(object):
         self.steps, self._ctr = snap['members'][0]['steps'], snap['members'][0]['noise_ctr']
         self._graph = None
         torch.cuda.synchronize()
+        if env is not None:
+            if 'device_env' in snap:
+                env.load_snapshot(snap['device_env'])
+            else:
+                env.reset()

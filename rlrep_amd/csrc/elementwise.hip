@@ -63,16 +63,7 @@ __global__ __launch_bounds__(256) void fill_slot_kernel(SlotFill p) {
 // ------------------------------------------------------------------------------------------------
 // Philox4x32-10 (Salmon et al. 2011): counter-based, replayable under hipGraph (counter from device)
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
+#include "philox.h"
 
 __device__ __forceinline__ void philox_fill_body(const PhiloxFill& p, int block, int nblocks) {
     const unsigned long long step = p.step_dev ? (unsigned long long)(*p.step_dev + p.step_add) : 0ull;

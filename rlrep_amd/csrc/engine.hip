@@ -5,6 +5,7 @@
 // of the agent's computation graph.  Tables live in the caller-provided workspace and are uploaded when
 // the batch size changes; the hot path performs no allocation, no host<->device copy and no sync.
 #include "engine_internal.h"
+#include "group_env.h"
 #include <cstdarg>
 #include <cmath>
 #include <cstddef>
@@ -2283,6 +2284,112 @@ int32_t rlrep_group_replay_add_sized(float* ring_dev, int64_t ring_stride_floats
     ++g_rl_launches;
     const int rc = rl_launch_replay_add_grp(ring_dev, ring_stride_floats, members, capacity, row_floats, ptr, (const float*)d, rows_stride_floats, nrows, size_dev, new_size, (hipStream_t)stream);
     if (rc) { rl_set_error("group_replay_add_sized: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+// ---- device environments of a seed group (group_env.hip) --------------------------------------------------------------------------------------
+struct rlrep_group_env {
+    rlrep_agent* ag; int kind, members;
+    EnvRecord* recs; EnvCtl* ctl;                     // [members] records and the group's counters: allocations of their own
+    double* starts;                                   // [members, RL_ENV_MAX_EPISODES, 2] start states of the last evaluation
+    int last_episodes;
+};
+extern "C" int rl_launch_group_env_reset(EnvRecord* recs, EnvCtl* ctl, const unsigned long long* seeds, int members, hipStream_t st);
+extern "C" int rl_launch_group_env_step(const SelectAct* p, long long mstride, const unsigned long long* seeds, const int* live, int grid_y, EnvRecord* recs,
+                                        EnvCtl* ctl, float* ring, long long ring_stride, long long capacity, int* size_dev, float eps_greedy,
+                                        long long start_timesteps, hipStream_t st);
+extern "C" int rl_launch_group_env_eval(const SelectAct* p, long long mstride, const unsigned long long* seeds, const int* live, int grid_y,
+                                        unsigned long long counter0, int episodes, double* out, double* starts, hipStream_t st);
+// what every entry point that launches checks first: `what` names the caller in the message
+static int group_env_check(const char* what, rlrep_agent* ag, rlrep_group_env* env) {
+    if (!ag || !env) { rl_set_error("%s: null agent or environment", what); return RLREP_ERR_ARG; }
+    if (ag->members <= 0) { rl_set_error("%s: not a seed group (device environments are built for rlrep_group_create agents)", what); return RLREP_ERR_ARG; }
+    if (env->ag != ag || env->members != ag->members) { rl_set_error("%s: the environment was created for another group", what); return RLREP_ERR_ARG; }
+    if (ag->in_train) { rl_set_error("%s: inside a train() (between rlrep_group_train_prologue and the end of that train())", what); return RLREP_ERR_ARG; }
+    return 0;
+}
+static void group_env_actor(rlrep_agent* ag, SelectAct& p, float lo, float hi) {
+    memset(&p, 0, sizeof(p));
+    p.W1 = ag->P("actor.trunk.0.weight"); p.b1 = ag->P("actor.trunk.0.bias"); p.W2 = ag->P("actor.trunk.2.weight"); p.b2 = ag->P("actor.trunk.2.bias");
+    p.W3 = ag->P("actor.trunk.4.weight"); p.b3 = ag->P("actor.trunk.4.bias");
+    p.S = ag->d.state_dim; p.Ha = ag->d.actor_hidden_dim; p.A = ag->d.action_dim; p.lo = lo; p.hi = hi;
+}
+int32_t rlrep_group_env_create(rlrep_agent* ag, int32_t kind, rlrep_group_env** out) {
+    if (kind != RLREP_ENV_PENDULUM) { rl_set_error("group_env_create: kind %d is not built (0 = Pendulum-v1)", kind); return RLREP_ERR_ARG; }
+    if (!ag || !out) { rl_set_error("group_env_create: null argument"); return RLREP_ERR_ARG; }
+    if (ag->members <= 0) { rl_set_error("group_env_create: not a seed group (device environments are built for rlrep_group_create agents)"); return RLREP_ERR_ARG; }
+    if (ag->d.state_dim != 3 || ag->d.action_dim != 1) {
+        rl_set_error("group_env_create: Pendulum-v1 has 3 observations and 1 action (the group has %d and %d)", ag->d.state_dim, ag->d.action_dim); return RLREP_ERR_ARG;
+    }
+    rlrep_group_env* env = new rlrep_group_env();
+    env->ag = ag; env->kind = kind; env->members = ag->members; env->last_episodes = 0;
+    hipError_t e = hipMalloc((void**)&env->recs, sizeof(EnvRecord) * env->members);
+    if (e == hipSuccess) e = hipMalloc((void**)&env->ctl, sizeof(EnvCtl));
+    if (e == hipSuccess) e = hipMalloc((void**)&env->starts, sizeof(double) * 2 * RL_ENV_MAX_EPISODES * env->members);
+    if (e == hipSuccess) e = hipMemset(env->recs, 0, sizeof(EnvRecord) * env->members);
+    if (e == hipSuccess) e = hipMemset(env->ctl, 0, sizeof(EnvCtl));
+    if (e == hipSuccess) e = hipMemset(env->starts, 0, sizeof(double) * 2 * RL_ENV_MAX_EPISODES * env->members);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { rl_set_error("group_env_create: %s", hipGetErrorString(e)); rlrep_group_env_destroy(env); return RLREP_ERR_HIP; }
+    *out = env;
+    return 0;
+}
+void rlrep_group_env_destroy(rlrep_group_env* env) {
+    if (!env) return;
+    if (env->recs) (void)hipFree(env->recs);
+    if (env->ctl) (void)hipFree(env->ctl);
+    if (env->starts) (void)hipFree(env->starts);
+    delete env;
+}
+int32_t rlrep_group_env_reset(rlrep_group_env* env, void* stream) {
+    if (const int rc = group_env_check("group_env_reset", env ? env->ag : nullptr, env)) return rc;
+    ++g_rl_launches;
+    const int rc = rl_launch_group_env_reset(env->recs, env->ctl, env->ag->grp_seeds, env->members, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_env_reset: launch failed (%d)", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_group_env_step(rlrep_agent* ag, rlrep_group_env* env, float* ring_dev, int64_t ring_stride_floats, int64_t capacity, int32_t* size_dev,
+                             float lo, float hi, float eps_greedy, int64_t start_timesteps, void* stream) {
+    if (const int rc = group_env_check("group_env_step", ag, env)) return rc;
+    if (!ring_dev || !size_dev) { rl_set_error("group_env_step: null ring or size pointer"); return RLREP_ERR_ARG; }
+    const int row = 2 * ag->d.state_dim + ag->d.action_dim + 2;
+    if (capacity < 1 || ring_stride_floats < capacity * row) {
+        rl_set_error("group_env_step: capacity %lld / ring stride %lld floats do not hold %lld rows of %d floats", (long long)capacity, (long long)ring_stride_floats, (long long)capacity, row);
+        return RLREP_ERR_ARG;
+    }
+    if (!(lo <= hi) || !(eps_greedy >= 0.f && eps_greedy <= 1.f)) { rl_set_error("group_env_step: bad action range [%g, %g] or eps_greedy %g", (double)lo, (double)hi, (double)eps_greedy); return RLREP_ERR_ARG; }
+    SelectAct p; group_env_actor(ag, p, lo, hi);
+    ++g_rl_launches;
+    const int rc = rl_launch_group_env_step(&p, ag->grp_stride, ag->grp_seeds, ag->grp_live, ag->grp_grid_y, env->recs, env->ctl, ring_dev, ring_stride_floats, capacity,
+                                            size_dev, eps_greedy, start_timesteps, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_env_step: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_group_env_evaluate(rlrep_agent* ag, rlrep_group_env* env, int32_t episodes, uint64_t eval_index, double* out_dev, void* stream) {
+    if (const int rc = group_env_check("group_env_evaluate", ag, env)) return rc;
+    if (episodes < 1 || episodes > RL_ENV_MAX_EPISODES) { rl_set_error("group_env_evaluate: episodes %d outside [1, %d]", episodes, RL_ENV_MAX_EPISODES); return RLREP_ERR_ARG; }
+    if (!out_dev) { rl_set_error("group_env_evaluate: null output"); return RLREP_ERR_ARG; }
+    SelectAct p; group_env_actor(ag, p, -2.f, 2.f);          // Pendulum-v1's own action range (its max_torque)
+    ++g_rl_launches;
+    const int rc = rl_launch_group_env_eval(&p, ag->grp_stride, ag->grp_seeds, ag->grp_live, ag->grp_grid_y, eval_index * (uint64_t)episodes, episodes, out_dev,
+                                            env->starts, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_env_evaluate: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    env->last_episodes = episodes;
+    return 0;
+}
+int32_t rlrep_group_env_state(rlrep_group_env* env, int32_t what, void* host, int64_t bytes, int32_t write, void* stream) {
+    if (!env || !host) { rl_set_error("group_env_state: null argument"); return RLREP_ERR_ARG; }
+    void* dev = nullptr; int64_t have = 0;
+    if (what == RLREP_ENV_STATE_RECORDS) { dev = env->recs; have = (int64_t)sizeof(EnvRecord) * env->members; }
+    else if (what == RLREP_ENV_STATE_COUNTERS) { dev = env->ctl; have = 16; }
+    else if (what == RLREP_ENV_STATE_EVAL_STARTS && !write) { dev = env->starts; have = (int64_t)sizeof(double) * 2 * env->last_episodes * env->members; }
+    else { rl_set_error("group_env_state: what = %d (write %d) is not a block of the environment", what, write); return RLREP_ERR_ARG; }
+    if (bytes != have) { rl_set_error("group_env_state: block %d holds %lld bytes, the buffer %lld", what, (long long)have, (long long)bytes); return RLREP_ERR_ARG; }
+    if (env->ag->in_train) { rl_set_error("group_env_state: inside a train() (between rlrep_group_train_prologue and the end of that train())"); return RLREP_ERR_ARG; }
+    hipError_t e = hipSuccess;
+    if (bytes > 0) e = write ? hipMemcpyAsync(dev, host, (size_t)bytes, hipMemcpyHostToDevice, (hipStream_t)stream)
+                             : hipMemcpyAsync(host, dev, (size_t)bytes, hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) { rl_set_error("group_env_state: %s", hipGetErrorString(e)); return RLREP_ERR_HIP; }
     return 0;
 }
 int32_t rlrep_last_launch_count(rlrep_agent* ag) { return ag ? ag->last_launches : 0; }

@@ -29,6 +29,11 @@ evaluation and all but the best `--halving-keep` (default 0.5, rounded up) are r
 every launch), never below `--halving-min` live members (default 1).  A retired member's environment is no longer stepped or evaluated and its
 metrics.jsonl stops growing; its state stays in the group (and in --save_model checkpoints).  Every halving is one line of
 `log/<env>/<alg>/<dir>/halving.jsonl` (step, retired members with their seeds and scores, live count).  Not together with --pbt-interval.
+
+`--device-env` (with --seeds / --sweep and --env Pendulum-v1) moves the environments onto the device (rlrep_amd/envs/device.py): acting,
+exploring, stepping, the replay-ring row and train() of every live member are one graph replay per step (SeedBatchMixin.iterate) and an
+evaluation is one launch (SeedBatchMixin.evaluate); --pbt-interval and --halving-interval rank by those scores.  Exploration and reset draws
+come from Philox streams of the members' seeds, so a run differs from the host loop's in its random numbers, not in its algorithm.
 """
 import argparse
 import json
@@ -98,6 +103,8 @@ def run(argv=None):
     p.add_argument('--halving-interval', default=None, type=int, help='successive halving every N environment steps (a multiple of --eval_freq; 0 = off)')
     p.add_argument('--halving-keep', default=None, type=float, help='share of the live members that stay at a halving step, rounded up (default 0.5)')
     p.add_argument('--halving-min', default=None, type=int, help='stop retiring at this many live members (default 1)')
+    p.add_argument('--device-env', action='store_true',
+                   help='step and score the environments on the device (with --seeds / --sweep and --env Pendulum-v1): rlrep_amd/envs/device.py')
     args = p.parse_args(argv)
     if args.seeds is not None or args.sweep:
         return run_seeds(args)
@@ -105,6 +112,8 @@ def run(argv=None):
         raise SystemExit('--pbt-*: population-based training needs a seed group (--seeds and / or --sweep)')
     if _halving_requested(args):
         raise SystemExit('--halving-*: successive halving needs a seed group (--seeds and / or --sweep)')
+    if args.device_env:
+        raise SystemExit('--device-env: device environments are built for seed groups (give --seeds and / or --sweep)')
 
     env, eval_env = envs.make(args.env), envs.make(args.env)
     env.seed(args.seed)
@@ -344,6 +353,8 @@ def run_seeds(args):
     seeds = [s for _ in configs for s in seeds]              # member = (configuration, seed), configurations outermost
     pbt_cfg = parse_pbt(args, args.alg, len(seeds))
     halving_cfg = parse_halving(args, len(seeds), pbt_cfg)
+    if args.device_env and not str(args.env).startswith('Pendulum'):
+        raise SystemExit(f'--device-env: only Pendulum-v1 is built on the device (got --env {args.env}); run without --device-env')
     from rlrep_amd.utils.buffer_group import ReplayBufferGroup
     R = len(seeds)
     envs_, evals_ = [envs.make(args.env) for _ in seeds], [envs.make(args.env) for _ in seeds]
@@ -369,6 +380,8 @@ def run_seeds(args):
         from rlrep_amd.agent.sac.seed_batch import SACSeedBatch
         agent = SACSeedBatch(seeds, state_dim, action_dim, space, member_hyper=member_hyper, **common)
     replay = ReplayBufferGroup(R, state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)))
+    if args.device_env:
+        return _device_loop(args, agent, replay, seeds, logs, pbt_cfg, halving_cfg)
     policies = [_MemberPolicy(agent, r) for r in range(R)]
     evaluations = [[util.eval_policy(policies[r], evals_[r], args.eval_episodes)] for r in range(R)]
     states = np.stack([np.asarray(e.reset(), np.float32) for e in envs_])
@@ -435,6 +448,53 @@ def run_seeds(args):
                 live = agent.live
             if args.save_model:
                 agent.save(os.path.join(args.log_root, args.env, args.alg, str(args.dir), 'seed_batch.pt'))
+    for f in logs + [f for f in (pbt_log, halving_log) if f is not None]:
+        f.close()
+    print('Total time cost {:.4g}s.'.format(timer.time_cost()))
+    return agent, evaluations
+
+
+def _device_loop(args, agent, replay, seeds, logs, pbt_cfg, halving_cfg):
+    """run_seeds' loop with the environments on the device (--device-env): one `agent.iterate` per step -- act, explore, step, ring row and
+    train() of every live member in one graph replay -- and one `agent.evaluate` launch per evaluation.  The exploration and reset draws are
+    Philox streams of the members' seeds instead of NumPy generators, and an evaluation's start states are a function of (seed, evaluation
+    index, episode); the metrics.jsonl / pbt.jsonl / halving.jsonl rows keep their keys."""
+    from rlrep_amd.envs.device import DevicePendulumGroup
+    R = len(seeds)
+    root = os.path.join(args.log_root, args.env, args.alg, str(args.dir))
+    env = DevicePendulumGroup(agent, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps))
+    evaluations = [[float(s)] for s in agent.evaluate(env, args.eval_episodes)]
+    pbt_rng = pbt_log = halving_log = None
+    if pbt_cfg is not None:
+        pbt_rng = np.random.RandomState(pbt_cfg['seed'])
+        pbt_log = open(os.path.join(root, 'pbt.jsonl'), 'a')
+    if halving_cfg is not None:
+        halving_log = open(os.path.join(root, 'halving.jsonl'), 'a')
+    live, infos = agent.live, None
+    timer = util.Timer()
+    for t in range(int(args.max_timesteps)):
+        out = agent.iterate(env, replay, args.batch_size, train=t >= args.start_timesteps)
+        infos = out if out is not None else infos
+        if (t + 1) % args.eval_freq == 0:
+            sps = timer.steps_per_sec(t + 1)
+            scores = agent.evaluate(env, args.eval_episodes)
+            for r in range(R):
+                if not live[r]:
+                    continue
+                evaluations[r].append(float(scores[r]))
+                if infos is not None:
+                    row = {'step': t + 1, 'info/evaluation': float(evaluations[r][-1]), 'steps_per_sec': sps}
+                    row.update({f'info/{k}': float(v) for k, v in infos[r].items()})
+                    logs[r].write(json.dumps(row) + '\n')
+                    logs[r].flush()
+            print('Step {}. Steps per sec (per seed): {:.4g}.'.format(t + 1, sps))
+            if pbt_cfg is not None and (t + 1) % pbt_cfg['interval'] == 0 and t + 1 > args.start_timesteps:
+                pbt_step(agent, [evaluations[r][-1] for r in range(R)], pbt_cfg, pbt_rng, t + 1, pbt_log)
+            if halving_cfg is not None and (t + 1) % halving_cfg['interval'] == 0 and t + 1 > args.start_timesteps:
+                halving_step(agent, [evaluations[r][-1] for r in range(R)], seeds, halving_cfg, t + 1, halving_log)
+                live = agent.live
+            if args.save_model:
+                agent.save(os.path.join(root, 'seed_batch.pt'), env=env)
     for f in logs + [f for f in (pbt_log, halving_log) if f is not None]:
         f.close()
     print('Total time cost {:.4g}s.'.format(timer.time_cost()))

@@ -33,6 +33,7 @@ class ReplayBufferGroup(object):
         self._size_dev = torch.zeros(self.members, dtype=torch.int32, device=self.device)
         self._size_pushed = None
         self.before_device_write_hooks = []
+        self._device_env = None        # the device environment that owns the cursor (collect_on_device); None: the host does
 
     # ---- what the agent reads ----------------------------------------------------------------
     @property
@@ -59,6 +60,9 @@ class ReplayBufferGroup(object):
     # ---- filling ------------------------------------------------------------------------------
     def add(self, state, action, next_state, reward, done):
         """One transition per member: state / next_state [R, S], action [R, A], reward / done [R]."""
+        if self._device_env is not None:
+            raise RuntimeError('ReplayBufferGroup.add: a device environment has been advancing these rings (SeedBatchMixin.iterate), so the host '
+                               'cursor is stale: call adopt_device_cursor() first')
         if self._staged == self._stage.shape[1]:
             self.flush()
         if self._copy_done is not None:
@@ -101,6 +105,36 @@ class ReplayBufferGroup(object):
             if first < n:
                 self.rings[:, :n - first].copy_(self._stage[:, first:n])
         self._staged = 0
+
+    # ---- device collection (rlrep_amd/envs/device.py) -----------------------------------------------------------------------------
+    def collect_on_device(self, env):
+        """Hand the cursor to device environment `env`: staged rows are flushed, the environment's records take (ptr, sizes), and from here on
+        the step launches advance the rings and the fill levels in size_dev().  add() refuses until adopt_device_cursor()."""
+        if self._device_env is env:
+            return
+        if self._device_env is not None:
+            raise RuntimeError('ReplayBufferGroup.collect_on_device: another device environment owns the cursor (adopt_device_cursor() first)')
+        self.flush()
+        self.size_dev()
+        env.set_cursor(self.ptr, self.sizes)
+        self._device_env = env
+
+    def adopt_device_cursor(self):
+        """Take the cursor back from the device environment: ptr and sizes become what its records hold (synchronises), and add() continues
+        behind the last row the device wrote.  The host ring advances in lockstep, so members whose cursors differ (some were retired
+        while the device collected) are refused."""
+        env = self._device_env
+        if env is None:
+            return
+        rec = env.state()
+        ptrs = sorted(set(int(p) for p in rec['ring_ptr']))
+        if len(ptrs) != 1:
+            raise RuntimeError(f'ReplayBufferGroup.adopt_device_cursor: the members\' ring cursors differ ({ptrs}): the host ring takes one row per '
+                               'member in lockstep')
+        self.ptr = ptrs[0] % self.max_size
+        self.sizes = [int(n) for n in rec['ring_size']]
+        self._size_pushed = list(self.sizes)          # (the step launches have published them)
+        self._device_env = None
 
     def load(self, r, state, action, next_state, reward, done):
         """Bulk-fill member r's ring (tests / synthetic benchmarks), as ReplayBuffer.load does for one ring."""

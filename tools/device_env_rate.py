@@ -1,0 +1,170 @@
+"""Iterations/s of a seed group's environment loop on the host against the device loop, and one evaluation by either.
+
+    python tools/device_env_rate.py --alg sac --members 4,8,16
+    python tools/device_env_rate.py --alg ctrlsac --members 4,8,16
+
+Host loop: the body of main.py run_seeds past warm-up -- group select_action (one launch, one synchronisation), R NumPy PendulumEnv steps and
+the epsilon-greedy draws in a Python loop, ReplayBufferGroup.add, train().  Device loop: SeedBatchMixin.iterate (rlrep_amd/envs/device.py):
+one graph replay.  Both on groups of the same seeds and shapes (sac: hidden 256; ctrlsac: F = 256, hidden 256; Pendulum dims, B = 64), in ONE
+process, arms alternated: --warmup iterations per arm, then --windows windows of --calls iterations each, host wall clock around a device
+synchronisation; median and min .. max of the windows.  Also the group's bare train() (the floor of either loop) in the same alternation.
+Evaluation: util.eval_policy per member (as run_seeds scores) against SeedBatchMixin.evaluate, --eval-episodes episodes, median of 3.
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+EPS_GREEDY = 0.01
+
+
+def _group(alg, seeds, B):
+    from rlrep_amd.envs.pendulum import PendulumEnv
+    space = PendulumEnv().action_space
+    if alg == 'sac':
+        from rlrep_amd.agent.sac.seed_batch import SACSeedBatch
+        return SACSeedBatch(seeds, 3, 1, space, max_batch=B, hidden_dim=256)
+    from rlrep_amd.agent.ctrlsac.seed_batch import CTRLSACSeedBatch
+    return CTRLSACSeedBatch(seeds, 3, 1, space, max_batch=B, hidden_dim=256, feature_dim=256, extra_feature_steps=3)
+
+
+class HostLoop(object):
+    """run_seeds' loop body (main.py), all members live, past warm-up"""
+
+    def __init__(self, alg, seeds, B):
+        from rlrep_amd import envs
+        from rlrep_amd.utils.buffer_group import ReplayBufferGroup
+        self.R, self.B = len(seeds), B
+        self.agent = _group(alg, seeds, B)
+        self.replay = ReplayBufferGroup(self.R, 3, 1, max_size=100000)
+        self.envs = [envs.make('Pendulum-v1') for _ in seeds]
+        for s, e in zip(seeds, self.envs):
+            e.seed(s)
+        self.rngs = [np.random.RandomState(s) for s in seeds]
+        self.states = np.stack([np.asarray(e.reset(), np.float32) for e in self.envs])
+        self.ep_steps = np.zeros(self.R, np.int64)
+        self.lo, self.hi = np.float32(-2.0), np.float32(2.0)
+
+    def step(self):
+        R = self.R
+        self.ep_steps += 1
+        greedy = self.agent.select_action(self.states, explore=True)
+        actions = np.zeros((R, 1), np.float32)
+        for r in range(R):
+            actions[r] = self.rngs[r].uniform(self.lo, self.hi) if self.rngs[r].uniform(0, 1) < EPS_GREEDY else greedy[r]
+        nexts, rewards, dones = np.zeros_like(self.states), np.zeros(R, np.float32), np.zeros(R, np.float32)
+        resets = []
+        for r, e in enumerate(self.envs):
+            ns, rew, done, _ = e.step(actions[r])
+            nexts[r], rewards[r] = ns, rew
+            dones[r] = float(done) if self.ep_steps[r] < 200 else 0.0
+            if done:
+                resets.append(r)
+        self.replay.add(self.states, actions, nexts, rewards, dones)
+        self.states = nexts.copy()
+        for r in resets:
+            self.states[r] = self.envs[r].reset()
+            self.ep_steps[r] = 0
+        self.agent.train(self.replay, self.B)
+
+
+class DeviceLoop(object):
+    def __init__(self, alg, seeds, B):
+        from rlrep_amd.envs.device import DevicePendulumGroup
+        from rlrep_amd.utils.buffer_group import ReplayBufferGroup
+        self.R, self.B = len(seeds), B
+        self.agent = _group(alg, seeds, B)
+        self.replay = ReplayBufferGroup(self.R, 3, 1, max_size=100000)
+        self.env = DevicePendulumGroup(self.agent, eps_greedy=EPS_GREEDY, start_timesteps=0)
+
+    def step(self):
+        self.agent.iterate(self.env, self.replay, self.B)
+
+
+class TrainOnly(object):
+    """the group's bare train() on a ring a device loop filled: what either loop cannot go below"""
+
+    def __init__(self, alg, seeds, B):
+        d = DeviceLoop(alg, seeds, B)
+        for _ in range(256):
+            d.agent.iterate(d.env, d.replay, B, train=False)
+        self.agent, self.replay, self.B = d.agent, d.replay, B
+
+    def step(self):
+        self.agent.train(self.replay, self.B)
+
+
+def _windows(arms, warmup, calls, windows):
+    for a in arms.values():
+        for _ in range(warmup):
+            a.step()
+    torch.cuda.synchronize()
+    rates = {k: [] for k in arms}
+    for _ in range(windows):
+        for k, a in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(calls):
+                a.step()
+            torch.cuda.synchronize()
+            rates[k].append(calls / (time.perf_counter() - t0))
+    return rates
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument('--alg', default='sac', choices=['sac', 'ctrlsac'])
+    p.add_argument('--members', default='4,8,16')
+    p.add_argument('--batch', type=int, default=64)
+    p.add_argument('--warmup', type=int, default=300)
+    p.add_argument('--calls', type=int, default=400)
+    p.add_argument('--windows', type=int, default=5)
+    p.add_argument('--eval-episodes', type=int, default=10)
+    args = p.parse_args(argv)
+    from rlrep_amd.utils import util
+    from rlrep_amd.main import _MemberPolicy
+    from rlrep_amd import envs
+    print(f'# {torch.cuda.get_device_name(0)}; {args.alg} Pendulum-v1 B = {args.batch}; {args.warmup} warm-up iterations, median (min .. max) of '
+          f'{args.windows} windows of {args.calls} iterations, arms alternated in one process')
+    for R in [int(v) for v in args.members.split(',')]:
+        seeds = list(range(R))
+        arms = {'host': HostLoop(args.alg, seeds, args.batch), 'device': DeviceLoop(args.alg, seeds, args.batch),
+                'train': TrainOnly(args.alg, seeds, args.batch)}
+        rates = _windows(arms, args.warmup, args.calls, args.windows)
+        med = {k: statistics.median(v) for k, v in rates.items()}
+        for k in ('host', 'device', 'train'):
+            what = {'host': 'host loop  (select_action, NumPy step, add, train)', 'device': 'device loop (iterate: one graph replay)      ',
+                    'train': 'bare train() of the group                    '}[k]
+            print(f'{args.alg} R={R:2d} {what}: {med[k]:9.1f} iterations/s ({min(rates[k]):.1f} .. {max(rates[k]):.1f}) = {1e6 / med[k]:7.1f} us')
+        print(f'{args.alg} R={R:2d} iterate / host loop: {med["device"] / med["host"]:.2f}x; iterate period - train() period: '
+              f'{1e6 / med["device"] - 1e6 / med["train"]:.1f} us')
+        # one evaluation of every member
+        host, dev = arms['host'], arms['device']
+        policies = [_MemberPolicy(host.agent, r) for r in range(R)]
+        evals = [envs.make('Pendulum-v1') for _ in seeds]
+        th, td = [], []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for r in range(R):
+                util.eval_policy(policies[r], evals[r], args.eval_episodes)
+            th.append(time.perf_counter() - t0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            dev.agent.evaluate(dev.env, args.eval_episodes)
+            td.append(time.perf_counter() - t0)
+        mh, md = statistics.median(th), statistics.median(td)
+        print(f'{args.alg} R={R:2d} one evaluation ({args.eval_episodes} episodes x {R} members): util.eval_policy {1e3 * mh:.1f} ms, evaluate {1e3 * md:.2f} ms '
+              f'({mh / md:.0f}x)', flush=True)
+        del arms, host, dev, policies
+
+
+if __name__ == '__main__':
+    main()
