@@ -231,6 +231,11 @@ class SeedBatchMixin(object):
         standalone twin"""
         return dict(self._mhyper[r])
 
+    def _check_member(self, where, r, named=None):
+        """ValueError naming `where` unless 0 <= r < R; `named`: what the message says instead of 'member r'"""
+        if not 0 <= r < self.R:
+            raise ValueError(f'{where}: {named or f"member {r}"} outside [0, {self.R})')
+
     # ---- population-based training: exploit (clone) and explore (retune) between two train() calls ---------------------------------------
     def clone_members(self, pairs):
         """pairs = [(src, dst), ...]: member dst becomes member src -- parameters, targets, Adam moments and step counts, temperature state,
@@ -245,8 +250,8 @@ class SeedBatchMixin(object):
         if not 1 <= len(pairs) <= self.R:
             raise ValueError(f'{name}.clone_members: {len(pairs)} pairs outside [1, {self.R}]')
         for s, d in pairs:
-            if not (0 <= s < self.R and 0 <= d < self.R):
-                raise ValueError(f'{name}.clone_members: pair ({s}, {d}) names a member outside [0, {self.R})')
+            for r in (s, d):
+                self._check_member(f'{name}.clone_members', r, f'pair ({s}, {d}) names a member')
             if s == d:
                 raise ValueError(f'{name}.clone_members: pair ({s}, {d}) copies member {s} onto itself')
         dsts = [d for _, d in pairs]
@@ -267,8 +272,7 @@ class SeedBatchMixin(object):
         training).  The member's device words change (rlrep_group_set_member_hyper); the captured graph reads them at its next replay."""
         name = type(self).__name__
         r = int(r)
-        if not 0 <= r < self.R:
-            raise ValueError(f'{name}.set_member_hyper: member {r} outside [0, {self.R})')
+        self._check_member(f'{name}.set_member_hyper', r)
         for k in kw:
             if k == 'alpha':
                 raise ValueError(f'{name}.set_member_hyper: alpha is the initial temperature only (a live member\'s temperature is its '
@@ -306,8 +310,7 @@ class SeedBatchMixin(object):
             raise ValueError(f'{name}: no member named')
         live = list(self._live)
         for r in members:
-            if not 0 <= r < self.R:
-                raise ValueError(f'{name}: member {r} outside [0, {self.R})')
+            self._check_member(name, r)
             if members.count(r) > 1:
                 raise ValueError(f'{name}: member {r} is named twice')
             if live[r] == on:

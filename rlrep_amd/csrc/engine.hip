@@ -38,6 +38,9 @@ struct GrpScope {
 // entry points that have no group form refuse a seed group by name (instead of running member 0 alone)
 #define GROUP_REFUSE(what) \
     if (ag && ag->members > 0) { rl_set_error("%s: not available on a seed group (rlrep_group_create)", what); return RLREP_ERR_ARG; }
+// ... and the entry points of a seed group refuse everything else
+#define GROUP_ONLY(what) \
+    if (!ag || ag->members <= 0) { rl_set_error("%s: not a seed group", what); return RLREP_ERR_ARG; }
 static std::map<std::string, std::string> g_sw_off, g_sw_on;
 static void sw_parse(const char* env, std::map<std::string, std::string>& m) {
     m.clear();
@@ -2100,7 +2103,7 @@ int32_t rlrep_group_set_seeds(rlrep_agent* ag, const uint64_t* seeds, int32_t n,
     return 0;
 }
 int32_t rlrep_group_set_member_hyper(rlrep_agent* ag, int32_t member, const rlrep_hyper* hyper, void* stream) {
-    if (!ag || ag->members <= 0) { rl_set_error("group_set_member_hyper: not a seed group"); return RLREP_ERR_ARG; }
+    GROUP_ONLY("group_set_member_hyper")
     if (member < 0 || member >= ag->members) { rl_set_error("group_set_member_hyper: member %d outside [0, %d)", member, ag->members); return RLREP_ERR_ARG; }
     if (!hyper) { rl_set_error("group_set_member_hyper: null hyper"); return RLREP_ERR_ARG; }
     const rlrep_hyper& g = ag->h;
@@ -2147,15 +2150,20 @@ int32_t rlrep_group_set_member_hyper(rlrep_agent* ag, int32_t member, const rlre
     return 0;
 }
 int32_t rlrep_group_get_member_hyper(rlrep_agent* ag, int32_t member, rlrep_hyper* out) {
-    if (!ag || ag->members <= 0) { rl_set_error("group_get_member_hyper: not a seed group"); return RLREP_ERR_ARG; }
+    GROUP_ONLY("group_get_member_hyper")
     if (member < 0 || member >= ag->members) { rl_set_error("group_get_member_hyper: member %d outside [0, %d)", member, ag->members); return RLREP_ERR_ARG; }
     if (!out) { rl_set_error("group_get_member_hyper: null output"); return RLREP_ERR_ARG; }
     *out = ag->grp_hyper[member];
     return 0;
 }
+// what changes a group between two train() calls refuses to run inside one: `what` names the caller in the message
+static bool in_train_refused(const char* what, const rlrep_agent* ag) {
+    if (ag->in_train) rl_set_error("%s: inside a train() (between rlrep_group_train_prologue and the end of that train())", what);
+    return ag->in_train;
+}
 extern "C" int rl_launch_group_clone(const CloneTab* tab, const ClonePairs* pairs, int npairs, hipStream_t st);
 int32_t rlrep_group_clone_members(rlrep_agent* ag, const int32_t* src_host, const int32_t* dst_host, int32_t n, void* stream) {
-    if (!ag || ag->members <= 0) { rl_set_error("group_clone_members: not a seed group"); return RLREP_ERR_ARG; }
+    GROUP_ONLY("group_clone_members")
     if (!src_host || !dst_host) { rl_set_error("group_clone_members: null member list"); return RLREP_ERR_ARG; }
     if (n < 1 || n > ag->members) { rl_set_error("group_clone_members: n %d outside [1, %d]", n, ag->members); return RLREP_ERR_ARG; }
     // pairs must be independent of each other (one launch serves all of them, in no order): role 1 = a source, 2 = a destination
@@ -2174,7 +2182,7 @@ int32_t rlrep_group_clone_members(rlrep_agent* ag, const int32_t* src_host, cons
         role[s] = 1; role[d] = 2;
         pairs.src[k] = s; pairs.dst[k] = d;
     }
-    if (ag->in_train) { rl_set_error("group_clone_members: inside a train() (between rlrep_group_train_prologue and the end of that train())"); return RLREP_ERR_ARG; }
+    if (in_train_refused("group_clone_members", ag)) return RLREP_ERR_ARG;
     // what a standalone agent's load(snapshot) restores: four arenas, the temperature state, the device records (static_state: the train()
     // counter block, the optimizer records, the metric slots -- the head of the workspace, up to the end of the metric slots)
     CloneTab tab; memset(&tab, 0, sizeof(tab));
@@ -2207,7 +2215,7 @@ int32_t rlrep_group_clone_members(rlrep_agent* ag, const int32_t* src_host, cons
 }
 extern "C" int rl_launch_group_live(int* table_dev, const LiveTab* tab, int members, hipStream_t st);
 int32_t rlrep_group_set_live(rlrep_agent* ag, const int32_t* live_host, void* stream) {
-    if (!ag || ag->members <= 0) { rl_set_error("group_set_live: not a seed group"); return RLREP_ERR_ARG; }
+    GROUP_ONLY("group_set_live")
     if (!live_host) { rl_set_error("group_set_live: null mask"); return RLREP_ERR_ARG; }
     LiveTab tab; memset(&tab, 0, sizeof(tab));
     for (int m = 0; m < ag->members; ++m) {
@@ -2215,7 +2223,7 @@ int32_t rlrep_group_set_live(rlrep_agent* ag, const int32_t* live_host, void* st
         if (live_host[m]) tab.slot_member[tab.n_live++] = m;
     }
     if (tab.n_live < 1) { rl_set_error("group_set_live: no live member (at least one member of a group stays live)"); return RLREP_ERR_ARG; }
-    if (ag->in_train) { rl_set_error("group_set_live: inside a train() (between rlrep_group_train_prologue and the end of that train())"); return RLREP_ERR_ARG; }
+    if (in_train_refused("group_set_live", ag)) return RLREP_ERR_ARG;
     // the slots behind n_live name no member (0): a launch never reads them
     ++g_rl_launches;
     const int rc = rl_launch_group_live(ag->grp_live, &tab, ag->members, (hipStream_t)stream);
@@ -2225,7 +2233,7 @@ int32_t rlrep_group_set_live(rlrep_agent* ag, const int32_t* live_host, void* st
     return 0;
 }
 int32_t rlrep_group_get_live(rlrep_agent* ag, int32_t* live_out) {
-    if (!ag || ag->members <= 0) { rl_set_error("group_get_live: not a seed group"); return RLREP_ERR_ARG; }
+    GROUP_ONLY("group_get_live")
     if (!live_out) { rl_set_error("group_get_live: null output"); return RLREP_ERR_ARG; }
     for (int m = 0; m < ag->members; ++m) live_out[m] = ag->grp_live_mask[m];
     return 0;
@@ -2237,7 +2245,7 @@ static bool in_member0(const rlrep_agent* ag, const void* p, long long bytes) {
 }
 int32_t rlrep_group_train_prologue(rlrep_agent* ag, const float* ring_dev, int64_t ring_stride_bytes, const int32_t* size_dev, int32_t* idx_pool_dev, int64_t n_idx,
                                    float* eps_pool_dev, int64_t n_eps, uint64_t idx_offset, uint64_t eps_offset, int32_t batch, void* stream) {
-    if (!ag || ag->members <= 0) { rl_set_error("group_train_prologue: not a seed group"); return RLREP_ERR_ARG; }
+    GROUP_ONLY("group_train_prologue")
     if (ring_stride_bytes < 0 || (ring_stride_bytes & 3) || (ag->members > 1 && ring_stride_bytes < 4ll * batch)) {
         rl_set_error("group_train_prologue: bad ring stride %lld", (long long)ring_stride_bytes); return RLREP_ERR_ARG;
     }
@@ -2250,20 +2258,25 @@ int32_t rlrep_group_train_prologue(rlrep_agent* ag, const float* ring_dev, int64
     return rlrep_train_prologue(ag, ring_dev, size_dev, idx_pool_dev, n_idx, eps_pool_dev, n_eps, 0, idx_offset, eps_offset, batch, stream);
 }
 int32_t rlrep_group_prepare(rlrep_agent* ag, int32_t batch) {
-    if (!ag || ag->members <= 0) { rl_set_error("group_prepare: not a seed group"); return RLREP_ERR_ARG; }
+    GROUP_ONLY("group_prepare")
     return ensure_batch(ag, batch);
+}
+// the actor part of a SelectAct (member 0's weights, the dimensions, the action range); everything else zero
+static void group_actor(rlrep_agent* ag, SelectAct& p, float lo, float hi) {
+    memset(&p, 0, sizeof(p));
+    p.W1 = ag->P("actor.trunk.0.weight"); p.b1 = ag->P("actor.trunk.0.bias"); p.W2 = ag->P("actor.trunk.2.weight"); p.b2 = ag->P("actor.trunk.2.bias");
+    p.W3 = ag->P("actor.trunk.4.weight"); p.b3 = ag->P("actor.trunk.4.bias");
+    p.S = ag->d.state_dim; p.Ha = ag->d.actor_hidden_dim; p.A = ag->d.action_dim; p.lo = lo; p.hi = hi;
 }
 int32_t rlrep_group_select_action(rlrep_agent* ag, const float* obs_host, int32_t explore, uint64_t offset, float lo, float hi, float* action_host, void* stream) {
     if (!ag || ag->members <= 0 || !obs_host || !action_host) { rl_set_error("group_select_action: bad argument (needs a seed group)"); return RLREP_ERR_ARG; }
-    SelectAct p; memset(&p, 0, sizeof(p));
+    SelectAct p; group_actor(ag, p, lo, hi);
     void* d = nullptr;
     if (hipHostGetDevicePointer(&d, const_cast<float*>(obs_host), 0) != hipSuccess || !d) { rl_set_error("group_select_action: the observations are not mapped (pinned) host memory"); return RLREP_ERR_ARG; }
     p.obs = (const float*)d;
     if (hipHostGetDevicePointer(&d, action_host, 0) != hipSuccess || !d) { rl_set_error("group_select_action: the action buffer is not mapped (pinned) host memory"); return RLREP_ERR_ARG; }
     p.act = (float*)d;
-    p.W1 = ag->P("actor.trunk.0.weight"); p.b1 = ag->P("actor.trunk.0.bias"); p.W2 = ag->P("actor.trunk.2.weight"); p.b2 = ag->P("actor.trunk.2.bias");
-    p.W3 = ag->P("actor.trunk.4.weight"); p.b3 = ag->P("actor.trunk.4.bias");
-    p.S = ag->d.state_dim; p.Ha = ag->d.actor_hidden_dim; p.A = ag->d.action_dim; p.explore = explore ? 1 : 0; p.lo = lo; p.hi = hi; p.seed = 0; p.offset = offset;
+    p.explore = explore ? 1 : 0; p.seed = 0; p.offset = offset;
     GrpScope grp_scope_(ag);
     ++g_rl_launches;
     const int rc = rl_launch_select_action(&p, (hipStream_t)stream);
@@ -2304,14 +2317,8 @@ static int group_env_check(const char* what, rlrep_agent* ag, rlrep_group_env* e
     if (!ag || !env) { rl_set_error("%s: null agent or environment", what); return RLREP_ERR_ARG; }
     if (ag->members <= 0) { rl_set_error("%s: not a seed group (device environments are built for rlrep_group_create agents)", what); return RLREP_ERR_ARG; }
     if (env->ag != ag || env->members != ag->members) { rl_set_error("%s: the environment was created for another group", what); return RLREP_ERR_ARG; }
-    if (ag->in_train) { rl_set_error("%s: inside a train() (between rlrep_group_train_prologue and the end of that train())", what); return RLREP_ERR_ARG; }
+    if (in_train_refused(what, ag)) return RLREP_ERR_ARG;
     return 0;
-}
-static void group_env_actor(rlrep_agent* ag, SelectAct& p, float lo, float hi) {
-    memset(&p, 0, sizeof(p));
-    p.W1 = ag->P("actor.trunk.0.weight"); p.b1 = ag->P("actor.trunk.0.bias"); p.W2 = ag->P("actor.trunk.2.weight"); p.b2 = ag->P("actor.trunk.2.bias");
-    p.W3 = ag->P("actor.trunk.4.weight"); p.b3 = ag->P("actor.trunk.4.bias");
-    p.S = ag->d.state_dim; p.Ha = ag->d.actor_hidden_dim; p.A = ag->d.action_dim; p.lo = lo; p.hi = hi;
 }
 int32_t rlrep_group_env_create(rlrep_agent* ag, int32_t kind, rlrep_group_env** out) {
     if (kind != RLREP_ENV_PENDULUM) { rl_set_error("group_env_create: kind %d is not built (0 = Pendulum-v1)", kind); return RLREP_ERR_ARG; }
@@ -2357,7 +2364,7 @@ int32_t rlrep_group_env_step(rlrep_agent* ag, rlrep_group_env* env, float* ring_
         return RLREP_ERR_ARG;
     }
     if (!(lo <= hi) || !(eps_greedy >= 0.f && eps_greedy <= 1.f)) { rl_set_error("group_env_step: bad action range [%g, %g] or eps_greedy %g", (double)lo, (double)hi, (double)eps_greedy); return RLREP_ERR_ARG; }
-    SelectAct p; group_env_actor(ag, p, lo, hi);
+    SelectAct p; group_actor(ag, p, lo, hi);
     ++g_rl_launches;
     const int rc = rl_launch_group_env_step(&p, ag->grp_stride, ag->grp_seeds, ag->grp_live, ag->grp_grid_y, env->recs, env->ctl, ring_dev, ring_stride_floats, capacity,
                                             size_dev, eps_greedy, start_timesteps, (hipStream_t)stream);
@@ -2368,7 +2375,7 @@ int32_t rlrep_group_env_evaluate(rlrep_agent* ag, rlrep_group_env* env, int32_t 
     if (const int rc = group_env_check("group_env_evaluate", ag, env)) return rc;
     if (episodes < 1 || episodes > RL_ENV_MAX_EPISODES) { rl_set_error("group_env_evaluate: episodes %d outside [1, %d]", episodes, RL_ENV_MAX_EPISODES); return RLREP_ERR_ARG; }
     if (!out_dev) { rl_set_error("group_env_evaluate: null output"); return RLREP_ERR_ARG; }
-    SelectAct p; group_env_actor(ag, p, -2.f, 2.f);          // Pendulum-v1's own action range (its max_torque)
+    SelectAct p; group_actor(ag, p, -2.f, 2.f);          // Pendulum-v1's own action range (its max_torque)
     ++g_rl_launches;
     const int rc = rl_launch_group_env_eval(&p, ag->grp_stride, ag->grp_seeds, ag->grp_live, ag->grp_grid_y, eval_index * (uint64_t)episodes, episodes, out_dev,
                                             env->starts, (hipStream_t)stream);
@@ -2384,7 +2391,7 @@ int32_t rlrep_group_env_state(rlrep_group_env* env, int32_t what, void* host, in
     else if (what == RLREP_ENV_STATE_EVAL_STARTS && !write) { dev = env->starts; have = (int64_t)sizeof(double) * 2 * env->last_episodes * env->members; }
     else { rl_set_error("group_env_state: what = %d (write %d) is not a block of the environment", what, write); return RLREP_ERR_ARG; }
     if (bytes != have) { rl_set_error("group_env_state: block %d holds %lld bytes, the buffer %lld", what, (long long)have, (long long)bytes); return RLREP_ERR_ARG; }
-    if (env->ag->in_train) { rl_set_error("group_env_state: inside a train() (between rlrep_group_train_prologue and the end of that train())"); return RLREP_ERR_ARG; }
+    if (in_train_refused("group_env_state", env->ag)) return RLREP_ERR_ARG;
     hipError_t e = hipSuccess;
     if (bytes > 0) e = write ? hipMemcpyAsync(dev, host, (size_t)bytes, hipMemcpyHostToDevice, (hipStream_t)stream)
                              : hipMemcpyAsync(host, dev, (size_t)bytes, hipMemcpyDeviceToHost, (hipStream_t)stream);

@@ -119,7 +119,7 @@ def run(argv=None):
     env.seed(args.seed)
     eval_env.seed(args.seed)
     max_length = env._max_episode_steps
-    log_path = os.path.join(args.log_root, args.env, args.alg, str(args.dir), str(args.seed))
+    log_path = os.path.join(_log_root(args), str(args.seed))
     os.makedirs(log_path, exist_ok=True)
     jsonl = open(os.path.join(log_path, 'metrics.jsonl'), 'a')
     try:
@@ -177,6 +177,10 @@ def run(argv=None):
     return agent, evaluations
 
 
+def _log_root(args):
+    return os.path.join(args.log_root, args.env, args.alg, str(args.dir))
+
+
 class _MemberPolicy(object):
     """eval_policy's view of one member of a seed batch (deterministic actions: the other members' rows are ignored)"""
 
@@ -204,7 +208,9 @@ def parse_sweeps(sweeps, alg, n_seeds):
     if not sweeps:
         return [('', {})]
     cls = _group_class(alg)
-    known = ('lr', 'discount', 'tau', 'feature_tau', 'alpha', 'target_update_period', 'auto_entropy_tuning')
+    sac, ctrl = (_group_class(a).SWEEP_KEYS for a in ('sac', 'ctrlsac'))
+    i = sac.index('alpha')                  # (the message names what ctrlsac alone takes, feature_tau, beside tau)
+    known = sac[:i] + tuple(k for k in ctrl if k not in sac) + sac[i:]
     axes = []
     for arg in sweeps:
         key, eq, vals = str(arg).partition('=')
@@ -237,6 +243,17 @@ def parse_sweeps(sweeps, alg, n_seeds):
     return configs
 
 
+def _ranking_interval(flag, what, value, eval_freq, members):
+    """--pbt-interval / --halving-interval -> the interval.  SystemExit on fewer than 2 members or an interval that is not a positive multiple
+    of --eval_freq."""
+    if members < 2:
+        raise SystemExit(f'{flag}: {what} needs at least 2 members (the group has {members})')
+    interval, freq = int(value or 0), int(eval_freq)
+    if interval <= 0 or freq <= 0 or interval % freq:
+        raise SystemExit(f'{flag} {value}: give a positive multiple of --eval_freq ({freq}): members are ranked by their latest evaluation')
+    return interval
+
+
 PBT_OPTIONS = ('pbt_interval', 'pbt_fraction', 'pbt_keys', 'pbt_factors', 'pbt_seed')
 
 
@@ -251,11 +268,7 @@ def parse_pbt(args, alg, members):
     import math
     if not _pbt_requested(args):
         return None
-    if members < 2:
-        raise SystemExit(f'--pbt-interval: population-based training needs at least 2 members (the group has {members})')
-    interval, freq = int(args.pbt_interval or 0), int(args.eval_freq)
-    if interval <= 0 or freq <= 0 or interval % freq:
-        raise SystemExit(f'--pbt-interval {args.pbt_interval}: give a positive multiple of --eval_freq ({freq}): members are ranked by their latest evaluation')
+    interval = _ranking_interval('--pbt-interval', 'population-based training', args.pbt_interval, args.eval_freq, members)
     fraction = 0.25 if args.pbt_fraction is None else float(args.pbt_fraction)
     if not (math.isfinite(fraction) and 0.0 < fraction <= 0.5):
         raise SystemExit(f'--pbt-fraction {args.pbt_fraction}: outside (0, 0.5]')
@@ -310,11 +323,7 @@ def parse_halving(args, members, pbt_cfg):
     import math
     if not _halving_requested(args):
         return None
-    if members < 2:
-        raise SystemExit(f'--halving-interval: successive halving needs at least 2 members (the group has {members})')
-    interval, freq = int(args.halving_interval or 0), int(args.eval_freq)
-    if interval <= 0 or freq <= 0 or interval % freq:
-        raise SystemExit(f'--halving-interval {args.halving_interval}: give a positive multiple of --eval_freq ({freq}): members are ranked by their latest evaluation')
+    interval = _ranking_interval('--halving-interval', 'successive halving', args.halving_interval, args.eval_freq, members)
     keep = 0.5 if args.halving_keep is None else float(args.halving_keep)
     if not (math.isfinite(keep) and 0.0 < keep < 1.0):
         raise SystemExit(f'--halving-keep {args.halving_keep}: outside (0, 1)')
@@ -337,6 +346,52 @@ def halving_step(agent, scores, seeds, cfg, step, log):
                               'scores': [float(scores[r]) for r in out], 'live': int(sum(agent.live))}) + '\n')
         log.flush()
     return out
+
+
+class _GroupEvaluations(object):
+    """What run_seeds' two loops do at an evaluation step, and the files it needs: the members' metrics.jsonl rows, the print, the PBT step,
+    the halving step (and with it `live`), --save_model.  `evaluations[r]` is member r's scores so far; the loop files the initial ones."""
+
+    def __init__(self, args, agent, seeds, logs, pbt_cfg, halving_cfg):
+        self.args, self.agent, self.seeds, self.logs, self.root = args, agent, seeds, logs, _log_root(args)
+        self.pbt_cfg, self.halving_cfg = pbt_cfg, halving_cfg
+        self.pbt_rng = self.pbt_log = self.halving_log = None
+        if pbt_cfg is not None:
+            self.pbt_rng = np.random.RandomState(pbt_cfg['seed'])
+            self.pbt_log = open(os.path.join(self.root, 'pbt.jsonl'), 'a')
+        if halving_cfg is not None:
+            self.halving_log = open(os.path.join(self.root, 'halving.jsonl'), 'a')
+        self.evaluations, self.live = None, agent.live
+
+    def step(self, step, sps, scores, infos, env=None):
+        """Step `step` was an evaluation step: scores[r] is live member r's evaluation (a retired member's entry is not read), infos the
+        latest train()'s, env the device environment a checkpoint carries."""
+        args, agent, evaluations = self.args, self.agent, self.evaluations
+        for r in range(agent.R):
+            if not self.live[r]:
+                continue
+            evaluations[r].append(scores[r])
+            if infos is not None:
+                row = {'step': step, 'info/evaluation': float(evaluations[r][-1]), 'steps_per_sec': sps}
+                row.update({f'info/{k}': float(v) for k, v in infos[r].items()})
+                self.logs[r].write(json.dumps(row) + '\n')
+                self.logs[r].flush()
+        print('Step {}. Steps per sec (per seed): {:.4g}.'.format(step, sps))
+
+        def due(cfg):
+            return cfg is not None and step % cfg['interval'] == 0 and step > args.start_timesteps
+
+        if due(self.pbt_cfg):
+            pbt_step(agent, [e[-1] for e in evaluations], self.pbt_cfg, self.pbt_rng, step, self.pbt_log)
+        if due(self.halving_cfg):
+            halving_step(agent, [e[-1] for e in evaluations], self.seeds, self.halving_cfg, step, self.halving_log)
+            self.live = agent.live
+        if args.save_model:
+            agent.save(os.path.join(self.root, 'seed_batch.pt'), env=env)
+
+    def close(self):
+        for f in self.logs + [f for f in (self.pbt_log, self.halving_log) if f is not None]:
+            f.close()
 
 
 def run_seeds(args):
@@ -365,7 +420,7 @@ def run_seeds(args):
     max_length = envs_[0]._max_episode_steps
     logs = []
     for tag, s in zip(tags, seeds):
-        path = os.path.join(args.log_root, args.env, args.alg, str(args.dir), *([tag] if swept else []), str(s))
+        path = os.path.join(_log_root(args), *([tag] if swept else []), str(s))
         os.makedirs(path, exist_ok=True)
         logs.append(open(os.path.join(path, 'metrics.jsonl'), 'a'))
     space = envs_[0].action_space
@@ -373,32 +428,22 @@ def run_seeds(args):
     lo, hi = np.asarray(space.low, np.float32), np.asarray(space.high, np.float32)
     common = dict(discount=args.discount, tau=args.tau, hidden_dim=args.hidden_dim, max_batch=args.batch_size)
     if args.alg == 'ctrlsac':
-        from rlrep_amd.agent.ctrlsac.seed_batch import CTRLSACSeedBatch
-        common.update(feature_dim=2048, hidden_dim=1024)                       # as build_agent (main.py:90-91)
-        agent = CTRLSACSeedBatch(seeds, state_dim, action_dim, space, extra_feature_steps=args.extra_feature_steps, member_hyper=member_hyper, **common)
-    else:
-        from rlrep_amd.agent.sac.seed_batch import SACSeedBatch
-        agent = SACSeedBatch(seeds, state_dim, action_dim, space, member_hyper=member_hyper, **common)
+        common.update(feature_dim=2048, hidden_dim=1024, extra_feature_steps=args.extra_feature_steps)          # as build_agent (main.py:90-91)
+    agent = _group_class(args.alg)(seeds, state_dim, action_dim, space, member_hyper=member_hyper, **common)
     replay = ReplayBufferGroup(R, state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)))
+    ev = _GroupEvaluations(args, agent, seeds, logs, pbt_cfg, halving_cfg)
     if args.device_env:
-        return _device_loop(args, agent, replay, seeds, logs, pbt_cfg, halving_cfg)
+        return _device_loop(args, agent, replay, ev)
     policies = [_MemberPolicy(agent, r) for r in range(R)]
-    evaluations = [[util.eval_policy(policies[r], evals_[r], args.eval_episodes)] for r in range(R)]
+    ev.evaluations = [[util.eval_policy(policies[r], evals_[r], args.eval_episodes)] for r in range(R)]
     states = np.stack([np.asarray(e.reset(), np.float32) for e in envs_])
     ep_steps = np.zeros(R, np.int64)
     infos = None
-    pbt_rng = pbt_log = None
-    if pbt_cfg is not None:
-        pbt_rng = np.random.RandomState(pbt_cfg['seed'])
-        pbt_log = open(os.path.join(args.log_root, args.env, args.alg, str(args.dir), 'pbt.jsonl'), 'a')
-    halving_log = None
-    if halving_cfg is not None:
-        halving_log = open(os.path.join(args.log_root, args.env, args.alg, str(args.dir), 'halving.jsonl'), 'a')
-    live = agent.live
     staged = None                           # the rows of the last replay.add: a retired member's ring takes its last row again (nobody samples it)
     timer = util.Timer()
     for t in range(int(args.max_timesteps)):
         ep_steps += 1
+        live = ev.live
         greedy = None if t < args.start_timesteps else agent.select_action(states, explore=True)
         actions = np.zeros((R, action_dim), np.float32)
         for r in range(R):
@@ -431,74 +476,32 @@ def run_seeds(args):
             infos = agent.train(replay, batch_size=args.batch_size)
         if (t + 1) % args.eval_freq == 0:
             sps = timer.steps_per_sec(t + 1)
-            for r in range(R):
-                if not live[r]:
-                    continue
-                evaluations[r].append(util.eval_policy(policies[r], evals_[r], args.eval_episodes))
-                if infos is not None:
-                    row = {'step': t + 1, 'info/evaluation': float(evaluations[r][-1]), 'steps_per_sec': sps}
-                    row.update({f'info/{k}': float(v) for k, v in infos[r].items()})
-                    logs[r].write(json.dumps(row) + '\n')
-                    logs[r].flush()
-            print('Step {}. Steps per sec (per seed): {:.4g}.'.format(t + 1, sps))
-            if pbt_cfg is not None and (t + 1) % pbt_cfg['interval'] == 0 and t + 1 > args.start_timesteps:
-                pbt_step(agent, [evaluations[r][-1] for r in range(R)], pbt_cfg, pbt_rng, t + 1, pbt_log)
-            if halving_cfg is not None and (t + 1) % halving_cfg['interval'] == 0 and t + 1 > args.start_timesteps:
-                halving_step(agent, [evaluations[r][-1] for r in range(R)], seeds, halving_cfg, t + 1, halving_log)
-                live = agent.live
-            if args.save_model:
-                agent.save(os.path.join(args.log_root, args.env, args.alg, str(args.dir), 'seed_batch.pt'))
-    for f in logs + [f for f in (pbt_log, halving_log) if f is not None]:
-        f.close()
+            scores = [util.eval_policy(policies[r], evals_[r], args.eval_episodes) if live[r] else None for r in range(R)]
+            ev.step(t + 1, sps, scores, infos)
+    ev.close()
     print('Total time cost {:.4g}s.'.format(timer.time_cost()))
-    return agent, evaluations
+    return agent, ev.evaluations
 
 
-def _device_loop(args, agent, replay, seeds, logs, pbt_cfg, halving_cfg):
+def _device_loop(args, agent, replay, ev):
     """run_seeds' loop with the environments on the device (--device-env): one `agent.iterate` per step -- act, explore, step, ring row and
     train() of every live member in one graph replay -- and one `agent.evaluate` launch per evaluation.  The exploration and reset draws are
     Philox streams of the members' seeds instead of NumPy generators, and an evaluation's start states are a function of (seed, evaluation
     index, episode); the metrics.jsonl / pbt.jsonl / halving.jsonl rows keep their keys."""
     from rlrep_amd.envs.device import DevicePendulumGroup
-    R = len(seeds)
-    root = os.path.join(args.log_root, args.env, args.alg, str(args.dir))
     env = DevicePendulumGroup(agent, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps))
-    evaluations = [[float(s)] for s in agent.evaluate(env, args.eval_episodes)]
-    pbt_rng = pbt_log = halving_log = None
-    if pbt_cfg is not None:
-        pbt_rng = np.random.RandomState(pbt_cfg['seed'])
-        pbt_log = open(os.path.join(root, 'pbt.jsonl'), 'a')
-    if halving_cfg is not None:
-        halving_log = open(os.path.join(root, 'halving.jsonl'), 'a')
-    live, infos = agent.live, None
+    ev.evaluations = [[float(s)] for s in agent.evaluate(env, args.eval_episodes)]
+    infos = None
     timer = util.Timer()
     for t in range(int(args.max_timesteps)):
         out = agent.iterate(env, replay, args.batch_size, train=t >= args.start_timesteps)
         infos = out if out is not None else infos
         if (t + 1) % args.eval_freq == 0:
             sps = timer.steps_per_sec(t + 1)
-            scores = agent.evaluate(env, args.eval_episodes)
-            for r in range(R):
-                if not live[r]:
-                    continue
-                evaluations[r].append(float(scores[r]))
-                if infos is not None:
-                    row = {'step': t + 1, 'info/evaluation': float(evaluations[r][-1]), 'steps_per_sec': sps}
-                    row.update({f'info/{k}': float(v) for k, v in infos[r].items()})
-                    logs[r].write(json.dumps(row) + '\n')
-                    logs[r].flush()
-            print('Step {}. Steps per sec (per seed): {:.4g}.'.format(t + 1, sps))
-            if pbt_cfg is not None and (t + 1) % pbt_cfg['interval'] == 0 and t + 1 > args.start_timesteps:
-                pbt_step(agent, [evaluations[r][-1] for r in range(R)], pbt_cfg, pbt_rng, t + 1, pbt_log)
-            if halving_cfg is not None and (t + 1) % halving_cfg['interval'] == 0 and t + 1 > args.start_timesteps:
-                halving_step(agent, [evaluations[r][-1] for r in range(R)], seeds, halving_cfg, t + 1, halving_log)
-                live = agent.live
-            if args.save_model:
-                agent.save(os.path.join(root, 'seed_batch.pt'), env=env)
-    for f in logs + [f for f in (pbt_log, halving_log) if f is not None]:
-        f.close()
+            ev.step(t + 1, sps, [float(s) for s in agent.evaluate(env, args.eval_episodes)], infos, env=env)
+    ev.close()
     print('Total time cost {:.4g}s.'.format(timer.time_cost()))
-    return agent, evaluations
+    return agent, ev.evaluations
 
 
 if __name__ == '__main__':

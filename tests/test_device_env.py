@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import seed_group_util as sg  # noqa: E402
 
 SEEDS = (3, 11, 42)
 B = 64
@@ -80,40 +81,6 @@ def _env(grp, **kw):
 def _rings(R, n):
     from rlrep_amd.utils.buffer_group import ReplayBufferGroup
     return ReplayBufferGroup(R, 3, 1, max_size=n)
-
-
-def _steps_words(core):
-    from rlrep_amd._lib import lib
-    off = lib.rlrep_steps_dev(core.h) - core._group.workspace.data_ptr()
-    return core.workspace[off:off + 16].view(torch.int32).clone()
-
-
-def _state(core):
-    """Everything a train() writes and a checkpoint restores (as tests/test_seed_batch_ctrlsac.py)"""
-    torch.cuda.synchronize()
-    return {'params': core.params.clone(), 'targets': core.targets.clone(), 'exp_avg': core.exp_avg.clone(),
-            'exp_avg_sq': core.exp_avg_sq.clone(), 'alpha_state': core.alpha_state.clone(),
-            'optimizer_steps': core.group_cfg()[:, 0].view(torch.int32).clone(), 'train_steps': _steps_words(core)}
-
-
-def _assert_equal(sa, sb, what):
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), (what, k)
-
-
-def _assert_info_equal(ia, ib, what):
-    assert set(ia.keys()) == set(ib.keys())
-    for k in ia.keys():
-        a, b = ia[k], ib[k]
-        a = a.item() if torch.is_tensor(a) else a
-        b = b.item() if torch.is_tensor(b) else b
-        assert a == b or (a != a and b != b), (what, k, a, b)
-
-
-def _member_bytes(grp, r):
-    torch.cuda.synchronize()
-    stride, skew = grp.core.member_stride, grp.core._skew
-    return grp.core._block[skew + r * stride:skew + (r + 1) * stride].clone()
 
 
 # ---- 1. dynamics ------------------------------------------------------------------------------------------------------------------------------
@@ -207,10 +174,10 @@ def test_device_loop_equals_host_loop_on_the_same_transitions(alg):
         if t >= warm:
             out2 = twin.train(buf2, B)
             for m in range(3):
-                _assert_info_equal(infos[t - warm][m], out2[m], (alg, t, m))
+                sg.assert_info_equal(infos[t - warm][m], out2[m], (alg, t, m))
     assert twin.steps == grp.steps == calls
     for m in range(3):
-        _assert_equal(_state(grp._members[m]), _state(twin._members[m]), (alg, m))
+        sg.assert_equal(sg.state(grp._members[m]), sg.state(twin._members[m]), (alg, m))
     assert torch.equal(buf2.rings[:, :warm + calls].cpu(), buf.rings[:, :warm + calls].cpu())
     # the transitions are a rollout: s of row t + 1 is s' of row t (no episode ended), warm-up actions are uniform draws in [-2, 2]
     assert np.array_equal(rows[:, 1:warm + calls, :3], rows[:, :warm + calls - 1, 4:7])
@@ -262,19 +229,19 @@ def test_a_retired_member_is_not_touched_and_continues_when_revived(alg):
     for t in range(12):
         grp.iterate(env, buf, B, train=t >= 5)
     grp.retire_members([2])
-    block, ring, rec = _member_bytes(grp, 2), buf.rings[2].clone(), env.state()
-    others = [_state(grp._members[q])['params'] for q in range(4)]
+    block, ring, rec = sg.member_bytes(grp, 2), buf.rings[2].clone(), env.state()
+    others = [sg.state(grp._members[q])['params'] for q in range(4)]
     for _ in range(6):
         out = grp.iterate(env, buf, B)
         assert out[2] is None and all(out[q] is not None for q in (0, 1, 3))
     scores = grp.evaluate(env, 2)
     assert np.isnan(scores[2]) and np.all(np.isfinite(scores[[0, 1, 3]])) and np.all(scores[[0, 1, 3]] < 0)
     now = env.state()
-    assert torch.equal(_member_bytes(grp, 2), block) and torch.equal(buf.rings[2], ring) and now[2].tobytes() == rec[2].tobytes()
+    assert torch.equal(sg.member_bytes(grp, 2), block) and torch.equal(buf.rings[2], ring) and now[2].tobytes() == rec[2].tobytes()
     assert buf.size_dev().cpu().tolist() == [18, 18, 12, 18]
     for q in (0, 1, 3):
         assert now['nsteps'][q] == 18 and now['ring_ptr'][q] == 18
-        assert not torch.equal(_state(grp._members[q])['params'], others[q])
+        assert not torch.equal(sg.state(grp._members[q])['params'], others[q])
         assert not torch.equal(buf.rings[q, 12:18], torch.zeros_like(buf.rings[q, 12:18]))
     assert env.counters()[0] == 18                                                  # the group's step counter does not wait for a retired member
     grp.revive_members([2])

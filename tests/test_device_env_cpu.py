@@ -7,6 +7,8 @@ import re
 import numpy as np
 import pytest
 
+from seed_group_util import run_launcher
+
 ENTRY_POINTS = {
     'rlrep_group_env_create': ('int32_t', ['rlrep_agent*', 'int32_t', 'rlrep_group_env**']),
     'rlrep_group_env_destroy': ('void', ['rlrep_group_env*']),
@@ -119,35 +121,30 @@ def test_host_pendulum_reference_is_usable_for_the_gpu_tests_cases():
 
 
 # ---- launcher ---------------------------------------------------------------------------------------------------------------------------
-def _run(argv):
-    from rlrep_amd import main
-    main.run(argv)
-
-
 def test_device_env_needs_a_seed_group():
     with pytest.raises(SystemExit) as e:
-        _run(['--alg', 'sac', '--env', 'Pendulum-v1', '--device-env'])
+        run_launcher(['--alg', 'sac', '--env', 'Pendulum-v1', '--device-env'])
     assert '--device-env' in str(e.value) and 'seed group' in str(e.value) and '--seeds' in str(e.value)
 
 
 @pytest.mark.parametrize('alg', ['sac', 'ctrlsac'])
 def test_device_env_is_pendulum_only(alg):
     with pytest.raises(SystemExit) as e:
-        _run(['--alg', alg, '--env', 'HalfCheetah-v4', '--seeds', '0,1', '--device-env'])
+        run_launcher(['--alg', alg, '--env', 'HalfCheetah-v4', '--seeds', '0,1', '--device-env'])
     assert '--device-env' in str(e.value) and 'only Pendulum-v1' in str(e.value) and 'HalfCheetah-v4' in str(e.value)
     with pytest.raises(SystemExit, match='only Pendulum-v1'):
-        _run(['--alg', alg, '--env', 'HalfCheetah-v4', '--sweep', 'lr=1e-4,3e-4', '--device-env'])
+        run_launcher(['--alg', alg, '--env', 'HalfCheetah-v4', '--sweep', 'lr=1e-4,3e-4', '--device-env'])
 
 
 def test_existing_launcher_checks_still_come_first():
     with pytest.raises(SystemExit, match='sac and ctrlsac only'):
-        _run(['--alg', 'vlsac', '--env', 'Pendulum-v1', '--seeds', '0,1', '--device-env'])
+        run_launcher(['--alg', 'vlsac', '--env', 'Pendulum-v1', '--seeds', '0,1', '--device-env'])
     with pytest.raises(SystemExit, match='sac and ctrlsac only'):
-        _run(['--alg', 'vlsac', '--env', 'HalfCheetah-v4', '--seeds', '0,1', '--device-env'])
+        run_launcher(['--alg', 'vlsac', '--env', 'HalfCheetah-v4', '--seeds', '0,1', '--device-env'])
     with pytest.raises(SystemExit, match='distinct'):
-        _run(['--alg', 'sac', '--env', 'HalfCheetah-v4', '--seeds', '1,1', '--device-env'])
+        run_launcher(['--alg', 'sac', '--env', 'HalfCheetah-v4', '--seeds', '1,1', '--device-env'])
     with pytest.raises(SystemExit, match='positive multiple of --eval_freq'):
-        _run(['--alg', 'sac', '--env', 'HalfCheetah-v4', '--seeds', '0,1', '--eval_freq', '100', '--halving-interval', '150', '--device-env'])
+        run_launcher(['--alg', 'sac', '--env', 'HalfCheetah-v4', '--seeds', '0,1', '--eval_freq', '100', '--halving-interval', '150', '--device-env'])
 
 
 def test_group_classes_and_the_buffer_have_the_device_surface():

@@ -16,87 +16,11 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+import seed_group_util as sg  # noqa: E402
 
 SEEDS = (3, 11, 42, 7)
 SMALL_SAC, SMALL_CTRL = 'sac_pendulum_b64', 'ctrlsac_halfcheetah_f256_b256'
 WORKLOADS = (SMALL_SAC, 'sac_halfcheetah_b256', SMALL_CTRL, 'ctrlsac_halfcheetah_f2048_b256')
-
-
-def _dims(wl, **extra):
-    alg, S, A, B, kw = bench.WORKLOADS[wl]
-    kw = dict(kw)
-    kw.update(extra)
-    return alg, S, A, B, kw
-
-
-def _standalone(wl, seed, hyper=None, **extra):
-    alg, S, A, B, kw = _dims(wl, **extra)
-    kw.update(hyper or {})
-    torch.manual_seed(seed)
-    if alg == 'sac':
-        from rlrep_amd.agent.sac.sac_agent import SACAgent
-        return SACAgent(S, A, bench.Space(A), max_batch=B, seed=seed, **kw)
-    from rlrep_amd.agent.ctrlsac.ctrlsac_agent import CTRLSACAgent
-    return CTRLSACAgent(S, A, bench.Space(A), max_batch=B, seed=seed, pipeline=False, **kw)
-
-
-def _group(wl, seeds=SEEDS, **extra):
-    alg, S, A, B, kw = _dims(wl, **extra)
-    if alg == 'sac':
-        from rlrep_amd.agent.sac.seed_batch import SACSeedBatch as G
-    else:
-        from rlrep_amd.agent.ctrlsac.seed_batch import CTRLSACSeedBatch as G
-    return G(list(seeds), S, A, bench.Space(A), max_batch=B, **kw)
-
-
-def _rings(wl, n):
-    """The group's rings and the standalone rings: member r's ring holds bench.synth_buffer(S, A, r)."""
-    from rlrep_amd.utils.buffer_group import ReplayBufferGroup
-    _, S, A, _, _ = _dims(wl)
-    g = ReplayBufferGroup(n, S, A, max_size=bench.REPLAY_N)
-    alone = []
-    for r in range(n):
-        buf, data = bench.synth_buffer(S, A, r)
-        g.load(r, data['state'], data['action'], data['next_state'], data['reward'], data['done'])
-        alone.append(buf)
-    return g, alone
-
-
-def _steps_words(core):
-    from rlrep_amd._lib import lib
-    ws0 = core._group.workspace if hasattr(core, '_group') else core.workspace
-    off = lib.rlrep_steps_dev(core.h) - ws0.data_ptr()
-    return core.workspace[off:off + 16].view(torch.int32).clone()
-
-
-def _state(core):
-    """Everything a train() writes and a checkpoint restores: parameters and targets, Adam moments and step counts, the float64 temperature
-    state, the train() counter words."""
-    torch.cuda.synchronize()
-    return {'params': core.params.clone(), 'targets': core.targets.clone(), 'exp_avg': core.exp_avg.clone(),
-            'exp_avg_sq': core.exp_avg_sq.clone(), 'alpha_state': core.alpha_state.clone(),
-            'optimizer_steps': core.group_cfg()[:, 0].view(torch.int32).clone(), 'train_steps': _steps_words(core)}
-
-
-def _assert_equal(sa, sb, what):
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), (what, k)
-
-
-def _assert_info_equal(ia, ib, what):
-    assert set(ia.keys()) == set(ib.keys())
-    for k in ia.keys():
-        a, b = ia[k], ib[k]
-        a = a.item() if torch.is_tensor(a) else a
-        b = b.item() if torch.is_tensor(b) else b
-        assert a == b or (a != a and b != b), (what, k, a, b)
-
-
-def _member_bytes(grp, r):
-    """member r's whole block of the group allocation: arenas, device records, workspace (slot buffers, history ring), pools"""
-    torch.cuda.synchronize()
-    stride, skew = grp.core.member_stride, grp.core._skew
-    return grp.core._block[skew + r * stride:skew + (r + 1) * stride].clone()
 
 
 def _live_abi(grp):
@@ -108,10 +32,10 @@ def _live_abi(grp):
 
 # ---- 1. live members are standalone agents ----------------------------------------------------------------------------------------------
 def _live_members_test(wl, **extra):
-    _, _, _, B, _ = _dims(wl, **extra)
-    grp = _group(wl, **extra)
-    rings, alone_rings = _rings(wl, 4)
-    alone = [_standalone(wl, s, **extra) for s in SEEDS]
+    _, _, _, B, _ = sg.dims(wl, **extra)
+    grp = sg.group(wl, SEEDS, **extra)
+    rings, alone_rings = sg.rings(wl, range(4))
+    alone = [sg.standalone(wl, s, **extra) for s in SEEDS]
     retire_after = {5: 1, 10: 3}
     assert grp.live == [True] * 4 == _live_abi(grp)
     for call in range(1, 26):
@@ -122,15 +46,15 @@ def _live_members_test(wl, **extra):
         if call in (1, 6, 11, 25):
             for r in range(4):
                 if live[r]:
-                    _assert_info_equal(infos[r], ainfos[r], (wl, call, r))
-                    _assert_equal(_state(grp._members[r]), _state(alone[r].core), (wl, call, r))
+                    sg.assert_info_equal(infos[r], ainfos[r], (wl, call, r))
+                    sg.assert_equal(sg.state(grp._members[r]), sg.state(alone[r].core), (wl, call, r))
         if call in retire_after:
             grp.retire_members([retire_after[call]])
             assert grp.lineage[-1] == {'event': 'retire', 'kind': 'retire', 'members': [retire_after[call]], 'step': call}
     assert grp.live == [True, False, True, False] == _live_abi(grp)
     # the retired members stand where they were retired: the standalone agents stopped at the same call
     for r in (1, 3):
-        _assert_equal(_state(grp._members[r]), _state(alone[r].core), (wl, 'retired', r))
+        sg.assert_equal(sg.state(grp._members[r]), sg.state(alone[r].core), (wl, 'retired', r))
 
 
 @pytest.mark.parametrize('wl', WORKLOADS)
@@ -145,59 +69,59 @@ def test_live_members_equal_standalone_agents_without_feature_target():
 # ---- 2. a retired member is untouched -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('wl', [SMALL_SAC, SMALL_CTRL, 'ctrlsac_halfcheetah_f2048_b256'])
 def test_a_retired_members_block_is_not_written(wl):
-    _, S, _, B, _ = _dims(wl)
-    grp = _group(wl)
-    rings, _ = _rings(wl, 4)
+    _, S, _, B, _ = sg.dims(wl)
+    grp = sg.group(wl, SEEDS)
+    rings, _ = sg.rings(wl, range(4))
     for _ in range(3):
         grp.train(rings, B)
     grp.select_action(np.zeros((4, S), np.float32), explore=True)
     for r in (2, 0):                                  # member 0 too: the programs' records are its, but its block is a member's like any other
         grp.retire_members([r])
-        block = _member_bytes(grp, r)
-        others = [_state(grp._members[q]) for q in range(4)]
+        block = sg.member_bytes(grp, r)
+        others = [sg.state(grp._members[q]) for q in range(4)]
         obs = np.random.RandomState(r).randn(4, S).astype(np.float32)
         for _ in range(5):
             grp.train(rings, B)
         for explore in (True, False, True):
             grp.select_action(obs, explore=explore)
-        assert torch.equal(_member_bytes(grp, r), block), (wl, r)
+        assert torch.equal(sg.member_bytes(grp, r), block), (wl, r)
         for q in range(4):
-            assert torch.equal(_state(grp._members[q])['params'], others[q]['params']) == (not grp.live[q]), (wl, r, q)
+            assert torch.equal(sg.state(grp._members[q])['params'], others[q]['params']) == (not grp.live[q]), (wl, r, q)
         del block
 
 
 # ---- 3. revive ------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('wl', [SMALL_SAC, SMALL_CTRL])
 def test_a_revived_member_continues_where_it_stood(wl):
-    _, _, _, B, _ = _dims(wl)
-    grp = _group(wl)
-    rings, alone_rings = _rings(wl, 4)
-    twin = _standalone(wl, SEEDS[2])
+    _, _, _, B, _ = sg.dims(wl)
+    grp = sg.group(wl, SEEDS)
+    rings, alone_rings = sg.rings(wl, range(4))
+    twin = sg.standalone(wl, SEEDS[2])
     for call in range(1, 21):
         live = grp.live[2]
         infos = grp.train(rings, B)
         if live:
-            _assert_info_equal(infos[2], twin.train(alone_rings[2], B), (wl, call))
+            sg.assert_info_equal(infos[2], twin.train(alone_rings[2], B), (wl, call))
         else:
             assert infos[2] is None
         if call == 5:
             grp.retire_members([2])
-            frozen = _state(grp._members[2])
+            frozen = sg.state(grp._members[2])
         if call == 12:
-            _assert_equal(_state(grp._members[2]), frozen, (wl, 'frozen'))
+            sg.assert_equal(sg.state(grp._members[2]), frozen, (wl, 'frozen'))
             grp.revive_members([2])
             assert grp.lineage[-1] == {'event': 'revive', 'kind': 'revive', 'members': [2], 'step': 12} and grp.live == [True] * 4
     # 5 + 8 = 13 calls of its own: its index and noise draws followed its own step counter
-    _assert_equal(_state(grp._members[2]), _state(twin.core), (wl, 'revived'))
-    assert int(_steps_words(grp._members[2])[0]) == 13 and int(_steps_words(grp._members[0])[0]) == 20
+    sg.assert_equal(sg.state(grp._members[2]), sg.state(twin.core), (wl, 'revived'))
+    assert int(sg.steps_words(grp._members[2])[0]) == 13 and int(sg.steps_words(grp._members[0])[0]) == 20
 
 
 # ---- 4. respawn: clone a winner into a retired slot, perturb, revive -----------------------------------------------------------------------------
 @pytest.mark.parametrize('wl', [SMALL_SAC, SMALL_CTRL])
 def test_respawn_a_retired_slot_from_a_clone(wl):
-    _, _, _, B, _ = _dims(wl)
-    grp = _group(wl)
-    rings, alone_rings = _rings(wl, 4)
+    _, _, _, B, _ = sg.dims(wl)
+    grp = sg.group(wl, SEEDS)
+    rings, alone_rings = sg.rings(wl, range(4))
     for _ in range(5):
         grp.train(rings, B)
     grp.retire_members([2])
@@ -210,14 +134,14 @@ def test_respawn_a_retired_slot_from_a_clone(wl):
     assert grp.member_hyper(2)['lr'] == 7e-4 and grp.member_snapshot(2)['hyper']['lr'] == 7e-4      # (works on a retired member)
     grp.revive_members([2])
     snap['seed'] = grp.seeds[2]
-    twin = _standalone(wl, grp.seeds[2], grp.member_hyper(2))
+    twin = sg.standalone(wl, grp.seeds[2], grp.member_hyper(2))
     twin.load(snap)
-    _assert_equal(_state(grp._members[2]), _state(twin.core), (wl, 'respawned'))
+    sg.assert_equal(sg.state(grp._members[2]), sg.state(twin.core), (wl, 'respawned'))
     for call in range(8):
         infos = grp.train(rings, B)
-        _assert_info_equal(infos[2], twin.train(alone_rings[2], B), (wl, call))
+        sg.assert_info_equal(infos[2], twin.train(alone_rings[2], B), (wl, call))
     assert grp._graph is graph
-    _assert_equal(_state(grp._members[2]), _state(twin.core), (wl, 'respawned + 8'))
+    sg.assert_equal(sg.state(grp._members[2]), sg.state(twin.core), (wl, 'respawned + 8'))
     assert not torch.equal(grp._members[2].params, grp._members[0].params)
     assert [e.get('event', e['kind']) for e in grp.lineage] == ['retire', 'clone', 'retune', 'revive']
 
@@ -226,11 +150,11 @@ def test_respawn_a_retired_slot_from_a_clone(wl):
 @pytest.mark.parametrize('wl', ['sac_halfcheetah_b256', SMALL_CTRL])
 def test_retiring_keeps_the_graph_and_is_at_most_one_launch(wl):
     from rlrep_amd._lib import lib
-    _, _, _, B, _ = _dims(wl)
+    _, _, _, B, _ = sg.dims(wl)
     R = 8
-    grp = _group(wl, tuple(range(100, 100 + R)))
-    rings, alone_rings = _rings(wl, R)
-    a = _standalone(wl, 100)
+    grp = sg.group(wl, tuple(range(100, 100 + R)))
+    rings, alone_rings = sg.rings(wl, range(R))
+    a = sg.standalone(wl, 100)
     a.train(alone_rings[0], B)
     for _ in range(3):
         grp.train(rings, B)
@@ -255,10 +179,10 @@ def test_retiring_keeps_the_graph_and_is_at_most_one_launch(wl):
 @pytest.mark.parametrize('wl', [SMALL_SAC, SMALL_CTRL])
 def test_select_action_with_members_retired(wl):
     from rlrep_amd._lib import lib
-    _, S, A, B, _ = _dims(wl)
-    grp = _group(wl)
-    rings, alone_rings = _rings(wl, 4)
-    alone = [_standalone(wl, s) for s in SEEDS]
+    _, S, A, B, _ = sg.dims(wl)
+    grp = sg.group(wl, SEEDS)
+    rings, alone_rings = sg.rings(wl, range(4))
+    alone = [sg.standalone(wl, s) for s in SEEDS]
     for _ in range(3):
         grp.train(rings, B)
         for r, a in enumerate(alone):
@@ -287,29 +211,29 @@ def test_select_action_with_members_retired(wl):
 # ---- 7. independence ----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('wl', [SMALL_SAC, SMALL_CTRL])
 def test_live_members_do_not_depend_on_a_retired_member(wl):
-    _, _, _, B, _ = _dims(wl)
+    _, _, _, B, _ = sg.dims(wl)
     runs = []
     for bump in (0.0, 1e-3):                     # only retired member 1's parameters differ between the two groups
-        g = _group(wl)
-        rings, _ = _rings(wl, 4)
+        g = sg.group(wl, SEEDS)
+        rings, _ = sg.rings(wl, range(4))
         for _ in range(3):
             g.train(rings, B)
         g.retire_members([1])
         g._members[1].params.add_(bump)
         for _ in range(6):
             g.train(rings, B)
-        runs.append([_state(m) for m in g._members])
+        runs.append([sg.state(m) for m in g._members])
     for r in (0, 2, 3):
-        _assert_equal(runs[0][r], runs[1][r], (wl, 'member', r))
+        sg.assert_equal(runs[0][r], runs[1][r], (wl, 'member', r))
     assert not torch.equal(runs[0][1]['params'], runs[1][1]['params'])
 
 
 # ---- 8. checkpoints -----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('wl', [SMALL_SAC, SMALL_CTRL])
 def test_checkpoint_carries_the_live_mask(wl, tmp_path):
-    _, _, _, B, _ = _dims(wl)
-    grp = _group(wl)
-    rings, _ = _rings(wl, 4)
+    _, _, _, B, _ = sg.dims(wl)
+    grp = sg.group(wl, SEEDS)
+    rings, _ = sg.rings(wl, range(4))
     for _ in range(4):
         grp.train(rings, B)
     grp.retire_members([3])
@@ -321,27 +245,27 @@ def test_checkpoint_carries_the_live_mask(wl, tmp_path):
     grp.save(path)
     snap = torch.load(path)
     assert snap['live'] == [False, True, True, False] and snap['lineage'] == grp.lineage and len(grp.lineage) == 2
-    fresh = _group(wl)
+    fresh = sg.group(wl, SEEDS)
     fresh.load(path)
     assert fresh.live == grp.live == _live_abi(fresh) and fresh.lineage == grp.lineage
     for r in range(4):
-        _assert_equal(_state(grp._members[r]), _state(fresh._members[r]), (wl, 'loaded', r))
+        sg.assert_equal(sg.state(grp._members[r]), sg.state(fresh._members[r]), (wl, 'loaded', r))
     for call in range(4):
         gi, fi = grp.train(rings, B), fresh.train(rings, B)
         for r in range(4):
             if grp.live[r]:
-                _assert_info_equal(gi[r], fi[r], (wl, 'resumed', call, r))
+                sg.assert_info_equal(gi[r], fi[r], (wl, 'resumed', call, r))
             else:
                 assert gi[r] is None and fi[r] is None
     for r in range(4):
-        _assert_equal(_state(grp._members[r]), _state(fresh._members[r]), (wl, 'resumed', r))
+        sg.assert_equal(sg.state(grp._members[r]), sg.state(fresh._members[r]), (wl, 'resumed', r))
     # a checkpoint written before members could retire has no mask: everybody is live
     old = {k: v for k, v in snap.items() if k != 'live'}
     fresh.load(old)
     assert fresh.live == [True] * 4 == _live_abi(fresh)
     infos = fresh.train(rings, B)
     assert all(i is not None for i in infos)
-    assert not torch.equal(_state(fresh._members[0])['params'], _state(grp._members[0])['params'])
+    assert not torch.equal(sg.state(fresh._members[0])['params'], sg.state(grp._members[0])['params'])
 
 
 # ---- 9. refusals --------------------------------------------------------------------------------------------------------------------------
@@ -349,13 +273,13 @@ def test_refusals_leave_everything_as_it_was():
     from rlrep_amd._lib import lib
     from rlrep_amd.core import _stream
     wl = SMALL_SAC
-    _, _, _, B, _ = _dims(wl)
-    grp = _group(wl)
-    rings, _ = _rings(wl, 4)
+    _, _, _, B, _ = sg.dims(wl)
+    grp = sg.group(wl, SEEDS)
+    rings, _ = sg.rings(wl, range(4))
     for _ in range(3):
         grp.train(rings, B)
     grp.retire_members([1])
-    before = [_member_bytes(grp, r) for r in range(4)]
+    before = [sg.member_bytes(grp, r) for r in range(4)]
     lineage = [dict(e) for e in grp.lineage]
     launches = lib.rlrep_launch_counter()
     name = type(grp).__name__
@@ -380,7 +304,7 @@ def test_refusals_leave_everything_as_it_was():
     for mask, words in (([0, 0, 0, 0], 'no live member'), ([1, 2, 1, 1], 'neither 0 nor 1'), ([1, -1, 1, 1], 'neither 0 nor 1')):
         rc, msg = raw(mask)
         assert rc == -1 and words in msg and 'group_set_live' in msg, (mask, rc, msg)
-    plain = _standalone(wl, 3)
+    plain = sg.standalone(wl, 3)
     rc, msg = raw([1, 1, 1, 1], handle=plain.core.h)
     assert rc == -1 and 'not a seed group' in msg
     out = (C.c_int32 * 4)()
@@ -401,7 +325,7 @@ def test_refusals_leave_everything_as_it_was():
         grp.revive_members([1])
     assert lib.rlrep_launch_counter() == n0
     assert grp.live == [True, False, True, True] == _live_abi(grp) and grp.lineage == lineage
-    assert torch.equal(_member_bytes(grp, 1), before[1])             # (the prologue itself left the retired member alone)
+    assert torch.equal(sg.member_bytes(grp, 1), before[1])             # (the prologue itself left the retired member alone)
     assert lib.rlrep_end_train(grp.core.h) == 0
     rc, msg = raw([1, 0, 0, 1])
     assert rc == 0, msg

@@ -7,6 +7,8 @@ import math
 import numpy as np
 import pytest
 
+from seed_group_util import run_launcher
+
 
 # ---- plan_halving -----------------------------------------------------------------------------------------------------------------------
 def test_plan_halving_ranks_higher_better_nan_first_out_ties_to_the_lower_index():
@@ -112,11 +114,6 @@ def test_group_classes_have_the_halving_surface():
 
 
 # ---- launcher ---------------------------------------------------------------------------------------------------------------------------
-def _run(argv):
-    from rlrep_amd import main
-    main.run(argv)
-
-
 GROUP = ['--alg', 'sac', '--seeds', '0,1,2,3', '--eval_freq', '100']
 
 
@@ -139,23 +136,23 @@ GROUP = ['--alg', 'sac', '--seeds', '0,1,2,3', '--eval_freq', '100']
 ])
 def test_halving_arguments_are_checked_before_the_gpu(argv, words):
     with pytest.raises(SystemExit) as e:
-        _run(argv + ['--env', 'Pendulum-v1'])
+        run_launcher(argv + ['--env', 'Pendulum-v1'])
     assert words in str(e.value), str(e.value)
 
 
 def test_existing_launcher_checks_still_come_first():
     with pytest.raises(SystemExit, match='distinct'):
-        _run(['--alg', 'sac', '--env', 'Pendulum-v1', '--seeds', '1,1', '--halving-interval', '5'])
+        run_launcher(['--alg', 'sac', '--env', 'Pendulum-v1', '--seeds', '1,1', '--halving-interval', '5'])
     with pytest.raises(SystemExit, match='sac and ctrlsac only'):
-        _run(['--alg', 'vlsac', '--env', 'Pendulum-v1', '--seeds', '0,1', '--halving-interval', '5'])
+        run_launcher(['--alg', 'vlsac', '--env', 'Pendulum-v1', '--seeds', '0,1', '--halving-interval', '5'])
     with pytest.raises(SystemExit, match="unknown key 'beta'"):
-        _run(['--alg', 'sac', '--env', 'Pendulum-v1', '--seeds', '0,1', '--sweep', 'beta=0.9', '--halving-interval', '5'])
+        run_launcher(['--alg', 'sac', '--env', 'Pendulum-v1', '--seeds', '0,1', '--sweep', 'beta=0.9', '--halving-interval', '5'])
     # ... and the --pbt-* checks, which are older than the --halving-* ones
     with pytest.raises(SystemExit, match='needs a seed group') as e:
-        _run(['--alg', 'sac', '--env', 'Pendulum-v1', '--pbt-interval', '100', '--halving-interval', '100', '--eval_freq', '100'])
+        run_launcher(['--alg', 'sac', '--env', 'Pendulum-v1', '--pbt-interval', '100', '--halving-interval', '100', '--eval_freq', '100'])
     assert '--pbt-*' in str(e.value)
     with pytest.raises(SystemExit, match=r'outside \(0, 0.5\]'):
-        _run(GROUP + ['--env', 'Pendulum-v1', '--pbt-interval', '200', '--pbt-fraction', '0.9', '--halving-interval', '150'])
+        run_launcher(GROUP + ['--env', 'Pendulum-v1', '--pbt-interval', '200', '--pbt-fraction', '0.9', '--halving-interval', '150'])
 
 
 def test_parse_halving_defaults_and_off():

@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+import seed_group_util as sg  # noqa: E402
 
 SEEDS = (3, 11, 42, 7, 19, 23, 5, 2)
 # distinct lr, tau, discount, target_update_period per member
@@ -30,63 +31,6 @@ PAIRS = [(0, 2), (1, 3)]
 
 def _members(n):
     return [(SEEDS[r], dict(HYPERS[r % len(HYPERS)])) for r in range(n)]
-
-
-def _dims(wl, **extra):
-    alg, S, A, B, kw = bench.WORKLOADS[wl]
-    kw = dict(kw)
-    kw.update(extra)
-    return alg, S, A, B, kw
-
-
-def _standalone(wl, seed, hyper, **extra):
-    alg, S, A, B, kw = _dims(wl, **extra)
-    kw.update(hyper)
-    torch.manual_seed(seed)
-    if alg == 'sac':
-        from rlrep_amd.agent.sac.sac_agent import SACAgent
-        return SACAgent(S, A, bench.Space(A), max_batch=B, seed=seed, **kw)
-    from rlrep_amd.agent.ctrlsac.ctrlsac_agent import CTRLSACAgent
-    return CTRLSACAgent(S, A, bench.Space(A), max_batch=B, seed=seed, pipeline=False, **kw)
-
-
-def _group(wl, members, **extra):
-    alg, S, A, B, kw = _dims(wl, **extra)
-    if alg == 'sac':
-        from rlrep_amd.agent.sac.seed_batch import SACSeedBatch as G
-    else:
-        from rlrep_amd.agent.ctrlsac.seed_batch import CTRLSACSeedBatch as G
-    mh = None if all(h is None for _, h in members) else [dict(h) for _, h in members]
-    return G([s for s, _ in members], S, A, bench.Space(A), max_batch=B, member_hyper=mh, **kw)
-
-
-def _rings(wl, n):
-    """The group's rings and the standalone rings: member r's ring holds bench.synth_buffer(S, A, r)."""
-    from rlrep_amd.utils.buffer_group import ReplayBufferGroup
-    _, S, A, _, _ = _dims(wl)
-    g = ReplayBufferGroup(n, S, A, max_size=bench.REPLAY_N)
-    alone = []
-    for r in range(n):
-        buf, data = bench.synth_buffer(S, A, r)
-        g.load(r, data['state'], data['action'], data['next_state'], data['reward'], data['done'])
-        alone.append(buf)
-    return g, alone
-
-
-def _steps_words(core):
-    from rlrep_amd._lib import lib
-    ws0 = core._group.workspace if hasattr(core, '_group') else core.workspace
-    off = lib.rlrep_steps_dev(core.h) - ws0.data_ptr()
-    return core.workspace[off:off + 16].view(torch.int32).clone()
-
-
-def _state(core):
-    """Everything a train() writes and a checkpoint restores: parameters and targets (ctrlsac: frozen_phi / frozen_phi_target included), Adam
-    moments and step counts, the float64 temperature state, the train() counter."""
-    torch.cuda.synchronize()
-    return {'params': core.params.clone(), 'targets': core.targets.clone(), 'exp_avg': core.exp_avg.clone(),
-            'exp_avg_sq': core.exp_avg_sq.clone(), 'alpha_state': core.alpha_state.clone(),
-            'optimizer_steps': core.group_cfg()[:, 0].view(torch.int32).clone(), 'train_steps': _steps_words(core)}
 
 
 def _hyper_words(core):
@@ -107,7 +51,7 @@ def _records(core):
 
 
 def _full(core):
-    s = _state(core)
+    s = sg.state(core)
     s['hyper_words'] = _hyper_words(core)
     s['device_state'] = core.device_state().clone()
     return s
@@ -120,35 +64,21 @@ def _member_hyper_abi(grp, r):
     return {f: getattr(out, f) for f, _ in _lib.Hyper._fields_}
 
 
-def _assert_equal(sa, sb, what):
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), (what, k)
-
-
-def _assert_info_equal(ia, ib, what):
-    assert set(ia.keys()) == set(ib.keys())
-    for k in ia.keys():
-        a, b = ia[k], ib[k]
-        a = a.item() if torch.is_tensor(a) else a
-        b = b.item() if torch.is_tensor(b) else b
-        assert a == b or (a != a and b != b), (what, k, a, b)
-
-
 def _twin(wl, grp, r, snapshot, **extra):
     """the standalone agent member r must equal from now on: built with r's seed and hyper-parameters, loaded with `snapshot` under r's seed"""
     snap = dict(snapshot)
     snap['seed'] = grp.seeds[r]
-    a = _standalone(wl, grp.seeds[r], grp.member_hyper(r), **extra)
+    a = sg.standalone(wl, grp.seeds[r], grp.member_hyper(r), **extra)
     a.load(snap)
     return a
 
 
 # ---- 5. the twin test -----------------------------------------------------------------------------------------------------------------------
 def _twin_test(wl, **extra):
-    _, _, _, B, _ = _dims(wl, **extra)
+    _, _, _, B, _ = sg.dims(wl, **extra)
     members = _members(4)
-    grp = _group(wl, members, **extra)
-    rings, alone_rings = _rings(wl, 4)
+    grp = sg.group(wl, *zip(*members), **extra)
+    rings, alone_rings = sg.rings(wl, range(4))
     for _ in range(5):
         grp.train(rings, B)
     snaps = {s: grp.member_snapshot(s) for s, _ in PAIRS}
@@ -159,7 +89,7 @@ def _twin_test(wl, **extra):
     after = [_full(m) for m in grp._members]
     for s, d in PAIRS:
         # immediately: dst's copied fields are src's, bit for bit ...
-        _assert_equal(_state(grp._members[d]), {k: before[s][k] for k in _state(grp._members[d])}, ('clone', wl, s, d))
+        sg.assert_equal(sg.state(grp._members[d]), {k: before[s][k] for k in sg.state(grp._members[d])}, ('clone', wl, s, d))
         assert torch.equal(_records(grp._members[d]), records[s]), ('device records', wl, s, d)
         # ... its optimizer words 1..5, its MemberHyper values and its seed are its own
         assert torch.equal(after[d]['hyper_words'], before[d]['hyper_words']), ('hyper words', wl, d)
@@ -167,17 +97,17 @@ def _twin_test(wl, **extra):
         assert _member_hyper_abi(grp, d) == hyp_abi[d] and grp.member_hyper(d) == dict(grp.sweep_defaults(), **members[d][1])
         assert grp.seeds[d] == members[d][0]               # (the device's copy of the seed shows in what the member draws: the twin's info dicts below)
         # the sources are untouched
-        _assert_equal(after[s], before[s], ('source', wl, s))
+        sg.assert_equal(after[s], before[s], ('source', wl, s))
     twins = {d: _twin(wl, grp, d, snaps[s], **extra) for s, d in PAIRS}
     for d, a in twins.items():
-        _assert_equal(_state(grp._members[d]), _state(a.core), ('twin loaded', wl, d))
+        sg.assert_equal(sg.state(grp._members[d]), sg.state(a.core), ('twin loaded', wl, d))
     for call in range(10):
         infos = grp.train(rings, B)
         for d, a in twins.items():
             ai = a.train(alone_rings[d], B)
-            _assert_info_equal(infos[d], ai, ('twin', wl, call, d))
+            sg.assert_info_equal(infos[d], ai, ('twin', wl, call, d))
             if call in (0, 1, 9):
-                _assert_equal(_state(grp._members[d]), _state(a.core), ('twin', wl, call, d))
+                sg.assert_equal(sg.state(grp._members[d]), sg.state(a.core), ('twin', wl, call, d))
     # the destinations really went on with their own hyper-parameters, rings and seeds: they left their sources
     for s, d in PAIRS:
         assert not torch.equal(grp._members[d].params, grp._members[s].params)
@@ -200,12 +130,12 @@ def test_ctrlsac_f2048_cloned_member_equals_its_standalone_twin_bit_for_bit():
 # ---- 6. a clone writes nothing outside its destinations ---------------------------------------------------------------------------------
 @pytest.mark.parametrize('wl', [SMALL_SAC, SMALL_CTRL])
 def test_clone_writes_nothing_outside_its_destinations(wl):
-    _, _, _, B, _ = _dims(wl)
+    _, _, _, B, _ = sg.dims(wl)
     members = _members(5)
     runs = []
     for clone in (True, False):
-        grp = _group(wl, members)
-        rings, _ = _rings(wl, 5)
+        grp = sg.group(wl, *zip(*members))
+        rings, _ = sg.rings(wl, range(5))
         for _ in range(5):
             grp.train(rings, B)
         if clone:
@@ -232,9 +162,9 @@ def test_clone_writes_nothing_outside_its_destinations(wl):
             del block
         for _ in range(10):
             grp.train(rings, B)
-        runs.append([_state(m) for m in grp._members])
+        runs.append([sg.state(m) for m in grp._members])
     for r in (0, 1, 4):
-        _assert_equal(runs[0][r], runs[1][r], (wl, 'member', r))
+        sg.assert_equal(runs[0][r], runs[1][r], (wl, 'member', r))
     for _, d in PAIRS:
         assert not torch.equal(runs[0][d]['params'], runs[1][d]['params'])
 
@@ -243,10 +173,10 @@ def test_clone_writes_nothing_outside_its_destinations(wl):
 def test_clone_keeps_the_graph_and_is_one_launch():
     from rlrep_amd._lib import lib
     wl = 'sac_halfcheetah_b256'
-    _, _, _, B, _ = _dims(wl)
+    _, _, _, B, _ = sg.dims(wl)
     R = 8
-    grp = _group(wl, _members(R))
-    rings, _ = _rings(wl, R)
+    grp = sg.group(wl, *zip(*_members(R)))
+    rings, _ = sg.rings(wl, range(R))
     for _ in range(3):
         grp.train(rings, B)
     graph, per_train, graph_launches = grp._graph, lib.rlrep_last_launch_count(grp.core.h), grp._graph_launches
@@ -265,13 +195,13 @@ def test_clone_keeps_the_graph_and_is_one_launch():
 # ---- 8. set_member_hyper on a live member ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('wl', [SMALL_SAC, SMALL_CTRL])
 def test_retuned_member_equals_the_standalone_twin_with_the_new_values(wl):
-    _, _, _, B, _ = _dims(wl)
+    _, _, _, B, _ = sg.dims(wl)
     members = _members(3)
     new = dict(lr=7e-4, tau=0.05, target_update_period=3, auto_entropy_tuning=False)
     runs = []
     for retune in (True, False):
-        grp = _group(wl, members)
-        rings, alone_rings = _rings(wl, 3)
+        grp = sg.group(wl, *zip(*members))
+        rings, alone_rings = sg.rings(wl, range(3))
         for _ in range(5):
             grp.train(rings, B)
         if retune:
@@ -291,23 +221,23 @@ def test_retuned_member_equals_the_standalone_twin_with_the_new_values(wl):
             twin = _twin(wl, grp, 1, grp.member_snapshot(1))
             for call in range(10):
                 infos = grp.train(rings, B)
-                _assert_info_equal(infos[1], twin.train(alone_rings[1], B), ('retuned', wl, call))
+                sg.assert_info_equal(infos[1], twin.train(alone_rings[1], B), ('retuned', wl, call))
             assert grp._graph is graph
-            _assert_equal(_state(grp._members[1]), _state(twin.core), ('retuned', wl))
+            sg.assert_equal(sg.state(grp._members[1]), sg.state(twin.core), ('retuned', wl))
         else:
             for _ in range(10):
                 grp.train(rings, B)
-        runs.append([_state(m) for m in grp._members])
+        runs.append([sg.state(m) for m in grp._members])
     for r in (0, 2):
-        _assert_equal(runs[0][r], runs[1][r], (wl, 'untouched member', r))
+        sg.assert_equal(runs[0][r], runs[1][r], (wl, 'untouched member', r))
     assert not torch.equal(runs[0][1]['params'], runs[1][1]['params'])
 
 
 def test_set_member_hyper_makes_a_plain_seed_group_swept():
     wl = SMALL_SAC
-    _, _, _, B, _ = _dims(wl)
-    grp = _group(wl, [(3, None), (11, None)])
-    rings, alone_rings = _rings(wl, 2)
+    _, _, _, B, _ = sg.dims(wl)
+    grp = sg.group(wl, (3, 11))
+    rings, alone_rings = sg.rings(wl, range(2))
     for _ in range(3):
         grp.train(rings, B)
     grp.set_member_hyper(0, lr=1e-3, discount=0.9)
@@ -315,8 +245,8 @@ def test_set_member_hyper_makes_a_plain_seed_group_swept():
     twin = _twin(wl, grp, 0, grp.member_snapshot(0))
     for call in range(4):
         infos = grp.train(rings, B)
-        _assert_info_equal(infos[0], twin.train(alone_rings[0], B), ('swept', call))
-    _assert_equal(_state(grp._members[0]), _state(twin.core), 'swept')
+        sg.assert_info_equal(infos[0], twin.train(alone_rings[0], B), ('swept', call))
+    sg.assert_equal(sg.state(grp._members[0]), sg.state(twin.core), 'swept')
 
 
 # ---- 9. refusals -------------------------------------------------------------------------------------------------------------------------
@@ -324,9 +254,9 @@ def test_clone_refusals_leave_every_member_as_it_was():
     from rlrep_amd._lib import lib
     from rlrep_amd.core import _stream
     wl = SMALL_SAC
-    _, _, _, B, _ = _dims(wl)
-    grp = _group(wl, _members(4))
-    rings, _ = _rings(wl, 4)
+    _, _, _, B, _ = sg.dims(wl)
+    grp = sg.group(wl, *zip(*_members(4)))
+    rings, _ = sg.rings(wl, range(4))
     for _ in range(3):
         grp.train(rings, B)
     before = [_full(m) for m in grp._members]
@@ -354,12 +284,12 @@ def test_clone_refusals_leave_every_member_as_it_was():
         assert py_words in str(e.value) and name in str(e.value), str(e.value)
         rc, msg = raw(pairs)
         assert rc == -1 and abi_words in msg and 'group_clone_members' in msg, (pairs, rc, msg)
-    plain = _standalone(wl, 3, {})
+    plain = sg.standalone(wl, 3, {})
     rc, msg = raw([(0, 1)], handle=plain.core.h)
     assert rc == -1 and 'not a seed group' in msg
     assert lib.rlrep_launch_counter() == launches                    # refused before anything is launched
     for r, m in enumerate(grp._members):
-        _assert_equal(_full(m), before[r], ('refused', r))
+        sg.assert_equal(_full(m), before[r], ('refused', r))
     assert grp.lineage == []
 
     # inside a train(): between the group train prologue and the end of that train()
@@ -372,7 +302,7 @@ def test_clone_refusals_leave_every_member_as_it_was():
     assert rc == -1 and 'inside a train()' in msg, (rc, msg)
     assert lib.rlrep_launch_counter() == n0
     for r, m in enumerate(grp._members):
-        _assert_equal(_full(m), inside[r], ('refused inside a train()', r))
+        sg.assert_equal(_full(m), inside[r], ('refused inside a train()', r))
     assert lib.rlrep_end_train(grp.core.h) == 0
     rc, msg = raw([(0, 1)])
     assert rc == 0, msg
@@ -383,10 +313,10 @@ def test_clone_refusals_leave_every_member_as_it_was():
 # ---- 10. checkpoints ------------------------------------------------------------------------------------------------------------------------
 def test_checkpoint_after_clone_and_retune_resumes_with_adopt_hyper(tmp_path):
     wl = SMALL_SAC
-    _, _, _, B, _ = _dims(wl)
+    _, _, _, B, _ = sg.dims(wl)
     members = _members(4)
-    grp = _group(wl, members)
-    rings, _ = _rings(wl, 4)
+    grp = sg.group(wl, *zip(*members))
+    rings, _ = sg.rings(wl, range(4))
     for _ in range(5):
         grp.train(rings, B)
     grp.clone_members([(0, 3)])
@@ -397,7 +327,7 @@ def test_checkpoint_after_clone_and_retune_resumes_with_adopt_hyper(tmp_path):
     path = os.path.join(tmp_path, 'pbt.pt')
     grp.save(path)
     assert [e['kind'] for e in grp.lineage] == ['clone', 'retune', 'retune'] and grp.lineage[0]['members'] == [0, 3]
-    fresh = _group(wl, members)                                      # the INITIAL values
+    fresh = sg.group(wl, *zip(*members))                                      # the INITIAL values
     with pytest.raises(RuntimeError, match='member 3 hyper-parameters differ'):
         fresh.load(path)
     fresh.load(path, adopt_hyper=True)
@@ -407,11 +337,11 @@ def test_checkpoint_after_clone_and_retune_resumes_with_adopt_hyper(tmp_path):
     for call in range(5):
         gi, fi = grp.train(rings, B), fresh.train(rings, B)
         for r in range(4):
-            _assert_info_equal(gi[r], fi[r], ('resumed', call, r))
+            sg.assert_info_equal(gi[r], fi[r], ('resumed', call, r))
     for r in range(4):
-        _assert_equal(_full(grp._members[r]), _full(fresh._members[r]), ('resumed', r))
+        sg.assert_equal(_full(grp._members[r]), _full(fresh._members[r]), ('resumed', r))
     # the default is what it was: a checkpoint whose values are the group's loads without the flag
-    same = _group(wl, [(s, grp.member_hyper(r)) for r, (s, _) in enumerate(members)])
+    same = sg.group(wl, [s for s, _ in members], [grp.member_hyper(r) for r in range(4)])
     same.load(path)
     assert same.lineage == grp.lineage
 

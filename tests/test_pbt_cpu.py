@@ -7,6 +7,8 @@ import math
 import numpy as np
 import pytest
 
+from seed_group_util import run_launcher
+
 
 # ---- plan_exploit -----------------------------------------------------------------------------------------------------------------------
 FRACTIONS = (0.01, 0.1, 0.125, 0.2, 0.25, 1.0 / 3.0, 0.4, 0.5)
@@ -129,11 +131,6 @@ def test_group_classes_have_the_pbt_surface():
 
 
 # ---- launcher ---------------------------------------------------------------------------------------------------------------------------
-def _run(argv):
-    from rlrep_amd import main
-    main.run(argv)
-
-
 GROUP = ['--alg', 'sac', '--seeds', '0,1,2,3', '--eval_freq', '100']
 
 
@@ -157,17 +154,17 @@ GROUP = ['--alg', 'sac', '--seeds', '0,1,2,3', '--eval_freq', '100']
 ])
 def test_pbt_arguments_are_checked_before_the_gpu(argv, words):
     with pytest.raises(SystemExit) as e:
-        _run(argv + ['--env', 'Pendulum-v1'])
+        run_launcher(argv + ['--env', 'Pendulum-v1'])
     assert words in str(e.value), str(e.value)
 
 
 def test_existing_launcher_checks_still_come_first():
     with pytest.raises(SystemExit, match='distinct'):
-        _run(['--alg', 'sac', '--env', 'Pendulum-v1', '--seeds', '1,1', '--pbt-interval', '5'])
+        run_launcher(['--alg', 'sac', '--env', 'Pendulum-v1', '--seeds', '1,1', '--pbt-interval', '5'])
     with pytest.raises(SystemExit, match='sac only'):
-        _run(['--alg', 'vlsac', '--env', 'Pendulum-v1', '--seeds', '0,1', '--pbt-interval', '5'])
+        run_launcher(['--alg', 'vlsac', '--env', 'Pendulum-v1', '--seeds', '0,1', '--pbt-interval', '5'])
     with pytest.raises(SystemExit, match="unknown key 'beta'"):
-        _run(['--alg', 'sac', '--env', 'Pendulum-v1', '--seeds', '0,1', '--sweep', 'beta=0.9', '--pbt-interval', '5'])
+        run_launcher(['--alg', 'sac', '--env', 'Pendulum-v1', '--seeds', '0,1', '--sweep', 'beta=0.9', '--pbt-interval', '5'])
 
 
 def test_parse_pbt_defaults_and_off():

@@ -12,124 +12,63 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+import seed_group_util as sg  # noqa: E402
 
 SEEDS = (3, 11, 42)
 WORKLOADS = ('sac_pendulum_b64', 'sac_halfcheetah_b256')
 
 
-def _dims(wl):
-    alg, S, A, B, kw = bench.WORKLOADS[wl]
-    assert alg == 'sac'
-    return S, A, B, kw
-
-
-def _standalone(wl, seed):
-    from rlrep_amd.agent.sac.sac_agent import SACAgent
-    S, A, B, kw = _dims(wl)
-    torch.manual_seed(seed)
-    return SACAgent(S, A, bench.Space(A), max_batch=B, seed=seed, **kw)
-
-
-def _group(wl, seeds=SEEDS):
-    from rlrep_amd.agent.sac.seed_batch import SACSeedBatch
-    S, A, B, kw = _dims(wl)
-    return SACSeedBatch(seeds, S, A, bench.Space(A), max_batch=B, **kw)
-
-
-def _rings(wl, data_seeds):
-    """The group's rings and the standalone rings: member r's ring holds bench.synth_buffer(S, A, data_seeds[r])."""
-    from rlrep_amd.utils.buffer_group import ReplayBufferGroup
-    S, A, _, _ = _dims(wl)
-    g = ReplayBufferGroup(len(data_seeds), S, A, max_size=bench.REPLAY_N)
-    alone = []
-    for r, ds in enumerate(data_seeds):
-        buf, data = bench.synth_buffer(S, A, ds)
-        g.load(r, data['state'], data['action'], data['next_state'], data['reward'], data['done'])
-        alone.append(buf)
-    return g, alone
-
-
-def _steps_words(core):
-    """the train() counter block of an agent / a group member (words 0 and 2: include/rlrep.h rlrep_steps_dev)"""
-    from rlrep_amd._lib import lib
-    ws0 = core._group.workspace if hasattr(core, '_group') else core.workspace
-    off = lib.rlrep_steps_dev(core.h) - ws0.data_ptr()
-    return core.workspace[off:off + 16].view(torch.int32).clone()
-
-
-def _state(core):
-    torch.cuda.synchronize()
-    return {'params': core.params.clone(), 'targets': core.targets.clone(), 'exp_avg': core.exp_avg.clone(),
-            'exp_avg_sq': core.exp_avg_sq.clone(), 'alpha_state': core.alpha_state.clone(),
-            'optimizer_steps': core.group_cfg()[:, 0].view(torch.int32).clone(),
-            'train_steps': _steps_words(core)}
-
-
-def _assert_equal(sa, sb, what):
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), (what, k)
-
-
-def _assert_info_equal(ia, ib, what):
-    assert set(ia.keys()) == set(ib.keys())
-    for k in ia.keys():
-        a, b = ia[k], ib[k]
-        a = a.item() if torch.is_tensor(a) else a
-        b = b.item() if torch.is_tensor(b) else b
-        assert a == b or (a != a and b != b), (what, k, a, b)
-
-
 @pytest.mark.parametrize('wl', WORKLOADS)
 def test_members_equal_standalone_agents_bit_for_bit(wl):
-    _, _, B, _ = _dims(wl)
-    grp = _group(wl)
-    rings, alone_rings = _rings(wl, range(len(SEEDS)))
-    alone = [_standalone(wl, s) for s in SEEDS]
+    _, _, _, B, _ = sg.dims(wl)
+    grp = sg.group(wl, SEEDS)
+    rings, alone_rings = sg.rings(wl, range(len(SEEDS)))
+    alone = [sg.standalone(wl, s) for s in SEEDS]
     for r in range(len(SEEDS)):
-        _assert_equal(_state(grp._members[r]), _state(alone[r].core), ('init', r))
+        sg.assert_equal(sg.state(grp._members[r]), sg.state(alone[r].core), ('init', r))
     for call in range(1, 26):
         infos = grp.train(rings, B)
         ainfos = [a.train(alone_rings[r], B) for r, a in enumerate(alone)]
         if call in (1, 2, 25):
             for r in range(len(SEEDS)):
-                _assert_info_equal(infos[r], ainfos[r], (call, r))
-                _assert_equal(_state(grp._members[r]), _state(alone[r].core), (call, r))
+                sg.assert_info_equal(infos[r], ainfos[r], (call, r))
+                sg.assert_equal(sg.state(grp._members[r]), sg.state(alone[r].core), (call, r))
 
 
 def test_group_graph_has_one_agents_launch_count():
     wl = 'sac_pendulum_b64'
-    _, _, B, _ = _dims(wl)
-    a = _standalone(wl, 3)
-    buf, _ = bench.synth_buffer(*_dims(wl)[:2], 0)
+    _, _, _, B, _ = sg.dims(wl)
+    a = sg.standalone(wl, 3)
+    buf, _ = bench.synth_buffer(*sg.dims(wl)[1:3], 0)
     a.train(buf, B)
     for R in (1, 3, 8):
         seeds = tuple(range(100, 100 + R))
-        g = _group(wl, seeds)
-        rings, _ = _rings(wl, range(R))
+        g = sg.group(wl, seeds)
+        rings, _ = sg.rings(wl, range(R))
         g.train(rings, B)
         assert g._graph_launches == a._graph_launches, (R, g._graph_launches, a._graph_launches)
 
 
 def test_members_are_independent():
     wl = 'sac_halfcheetah_b256'
-    _, _, B, _ = _dims(wl)
+    _, _, _, B, _ = sg.dims(wl)
     runs = []
     for data in ((0, 1, 2), (0, 7, 2)):           # only member 1's ring differs
-        g = _group(wl)
-        rings, _ = _rings(wl, data)
+        g = sg.group(wl, SEEDS)
+        rings, _ = sg.rings(wl, data)
         for _ in range(5):
             g.train(rings, B)
-        runs.append([_state(m) for m in g._members])
-    _assert_equal(runs[0][0], runs[1][0], 'member 0')
-    _assert_equal(runs[0][2], runs[1][2], 'member 2')
+        runs.append([sg.state(m) for m in g._members])
+    sg.assert_equal(runs[0][0], runs[1][0], 'member 0')
+    sg.assert_equal(runs[0][2], runs[1][2], 'member 2')
     assert not torch.equal(runs[0][1]['params'], runs[1][1]['params'])
 
 
 def test_init_rule():
     for wl in WORKLOADS:
-        grp = _group(wl)
+        grp = sg.group(wl, SEEDS)
         for r, s in enumerate(SEEDS):
-            a = _standalone(wl, s)
+            a = sg.standalone(wl, s)
             m = grp.member(r)
             for name, mod in (('critic', a.critic), ('critic_target', a.critic_target), ('actor', a.actor)):
                 sd, gd = mod.state_dict(), getattr(m, name).state_dict()
@@ -142,35 +81,35 @@ def test_init_rule():
 def test_member_export_and_group_checkpoint(tmp_path):
     from rlrep_amd.agent.sac.sac_agent import SACAgent
     wl = 'sac_pendulum_b64'
-    S, A, B, kw = _dims(wl)
-    grp = _group(wl)
-    rings, alone_rings = _rings(wl, range(len(SEEDS)))
+    _, S, A, B, kw = sg.dims(wl)
+    grp = sg.group(wl, SEEDS)
+    rings, alone_rings = sg.rings(wl, range(len(SEEDS)))
     for _ in range(10):
         grp.train(rings, B)
     path = os.path.join(tmp_path, 'group.pt')
     grp.save(path)
     a = SACAgent(S, A, bench.Space(A), max_batch=B, seed=12345, **kw)
     a.load(grp.member_snapshot(2))
-    grp2 = _group(wl)
+    grp2 = sg.group(wl, SEEDS)
     grp2.load(path)
     for _ in range(5):
         gi = grp.train(rings, B)
         ai = a.train(alone_rings[2], B)
         g2i = grp2.train(rings, B)
-    _assert_info_equal(gi[2], ai, 'export')
-    _assert_equal(_state(grp._members[2]), _state(a.core), 'export')
+    sg.assert_info_equal(gi[2], ai, 'export')
+    sg.assert_equal(sg.state(grp._members[2]), sg.state(a.core), 'export')
     for r in range(len(SEEDS)):
-        _assert_info_equal(gi[r], g2i[r], ('checkpoint', r))
-        _assert_equal(_state(grp._members[r]), _state(grp2._members[r]), ('checkpoint', r))
+        sg.assert_info_equal(gi[r], g2i[r], ('checkpoint', r))
+        sg.assert_equal(sg.state(grp._members[r]), sg.state(grp2._members[r]), ('checkpoint', r))
 
 
 @pytest.mark.parametrize('wl', WORKLOADS)
 def test_group_select_action_equals_standalone_in_one_launch(wl):
     from rlrep_amd._lib import lib
-    S, A, B, _ = _dims(wl)
-    grp = _group(wl)
-    rings, alone_rings = _rings(wl, range(len(SEEDS)))
-    alone = [_standalone(wl, s) for s in SEEDS]
+    _, S, A, B, _ = sg.dims(wl)
+    grp = sg.group(wl, SEEDS)
+    rings, alone_rings = sg.rings(wl, range(len(SEEDS)))
+    alone = [sg.standalone(wl, s) for s in SEEDS]
     for _ in range(3):                                  # trained actors, not just initial ones
         grp.train(rings, B)
         for r, a in enumerate(alone):
@@ -191,13 +130,13 @@ def test_entry_points_without_a_group_form_refuse_a_group():
     import ctypes as C
     from rlrep_amd._lib import lib
     wl = 'sac_pendulum_b64'
-    S, A, B, _ = _dims(wl)
-    grp = _group(wl)
+    _, S, A, B, _ = sg.dims(wl)
+    grp = sg.group(wl, SEEDS)
     obs = torch.zeros(1, S).pin_memory()
     act = torch.zeros(1, A).pin_memory()
     rc = lib.rlrep_select_action(grp.core.h, C.c_void_p(obs.data_ptr()), 1, 0, 0, 0, -1.0, 1.0, C.c_void_p(act.data_ptr()), 1, None)
     assert rc == -1 and b'seed group' in lib.rlrep_last_error()
-    rings, _ = _rings(wl, range(len(SEEDS)))
+    rings, _ = sg.rings(wl, range(len(SEEDS)))
     idx = torch.zeros(B, dtype=torch.int32, device='cuda')
     rc = lib.rlrep_replay_sample(grp.core.h, 0, C.c_void_p(rings.ring.data_ptr()), C.c_void_p(idx.data_ptr()), B, None)
     assert rc == -1 and b'seed group' in lib.rlrep_last_error()

@@ -13,75 +13,11 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+import seed_group_util as sg  # noqa: E402
 
 SEEDS = (3, 11, 42)
 WORKLOADS = ('ctrlsac_halfcheetah_f256_b256', 'ctrlsac_halfcheetah_f2048_b256')
 SMALL = 'ctrlsac_halfcheetah_f256_b256'
-
-
-def _dims(wl, **extra):
-    alg, S, A, B, kw = bench.WORKLOADS[wl]
-    assert alg == 'ctrlsac'
-    kw = dict(kw)
-    kw.update(extra)
-    return S, A, B, kw
-
-
-def _standalone(wl, seed, **extra):
-    from rlrep_amd.agent.ctrlsac.ctrlsac_agent import CTRLSACAgent
-    S, A, B, kw = _dims(wl, **extra)
-    torch.manual_seed(seed)
-    return CTRLSACAgent(S, A, bench.Space(A), max_batch=B, seed=seed, pipeline=False, **kw)
-
-
-def _group(wl, seeds=SEEDS, **extra):
-    from rlrep_amd.agent.ctrlsac.seed_batch import CTRLSACSeedBatch
-    S, A, B, kw = _dims(wl, **extra)
-    return CTRLSACSeedBatch(seeds, S, A, bench.Space(A), max_batch=B, **kw)
-
-
-def _rings(wl, data_seeds):
-    """The group's rings and the standalone rings: member r's ring holds bench.synth_buffer(S, A, data_seeds[r])."""
-    from rlrep_amd.utils.buffer_group import ReplayBufferGroup
-    S, A, _, _ = _dims(wl)
-    g = ReplayBufferGroup(len(data_seeds), S, A, max_size=bench.REPLAY_N)
-    alone = []
-    for r, ds in enumerate(data_seeds):
-        buf, data = bench.synth_buffer(S, A, ds)
-        g.load(r, data['state'], data['action'], data['next_state'], data['reward'], data['done'])
-        alone.append(buf)
-    return g, alone
-
-
-def _steps_words(core):
-    from rlrep_amd._lib import lib
-    ws0 = core._group.workspace if hasattr(core, '_group') else core.workspace
-    off = lib.rlrep_steps_dev(core.h) - ws0.data_ptr()
-    return core.workspace[off:off + 16].view(torch.int32).clone()
-
-
-def _state(core):
-    """Everything a train() writes: parameters and targets (frozen_phi / frozen_phi_target included), Adam moments and step counts, the
-    float64 temperature state, the train() counter."""
-    torch.cuda.synchronize()
-    return {'params': core.params.clone(), 'targets': core.targets.clone(), 'exp_avg': core.exp_avg.clone(),
-            'exp_avg_sq': core.exp_avg_sq.clone(), 'alpha_state': core.alpha_state.clone(),
-            'optimizer_steps': core.group_cfg()[:, 0].view(torch.int32).clone(),
-            'train_steps': _steps_words(core)}
-
-
-def _assert_equal(sa, sb, what):
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), (what, k)
-
-
-def _assert_info_equal(ia, ib, what):
-    assert set(ia.keys()) == set(ib.keys())
-    for k in ia.keys():
-        a, b = ia[k], ib[k]
-        a = a.item() if torch.is_tensor(a) else a
-        b = b.item() if torch.is_tensor(b) else b
-        assert a == b or (a != a and b != b), (what, k, a, b)
 
 
 def _frozen_equal_phi(agent_or_member):
@@ -91,19 +27,19 @@ def _frozen_equal_phi(agent_or_member):
 
 
 def _bit_exact(wl, calls, **extra):
-    _, _, B, _ = _dims(wl, **extra)
-    grp = _group(wl, **extra)
-    rings, alone_rings = _rings(wl, range(len(SEEDS)))
-    alone = [_standalone(wl, s, **extra) for s in SEEDS]
+    _, _, _, B, _ = sg.dims(wl, **extra)
+    grp = sg.group(wl, SEEDS, **extra)
+    rings, alone_rings = sg.rings(wl, range(len(SEEDS)))
+    alone = [sg.standalone(wl, s, **extra) for s in SEEDS]
     for r in range(len(SEEDS)):
-        _assert_equal(_state(grp._members[r]), _state(alone[r].core), ('init', r))
+        sg.assert_equal(sg.state(grp._members[r]), sg.state(alone[r].core), ('init', r))
     for call in range(1, calls + 1):
         infos = grp.train(rings, B)
         ainfos = [a.train(alone_rings[r], B) for r, a in enumerate(alone)]
         if call in (1, 2, calls):
             for r in range(len(SEEDS)):
-                _assert_info_equal(infos[r], ainfos[r], (wl, call, r))
-                _assert_equal(_state(grp._members[r]), _state(alone[r].core), (wl, call, r))
+                sg.assert_info_equal(infos[r], ainfos[r], (wl, call, r))
+                sg.assert_equal(sg.state(grp._members[r]), sg.state(alone[r].core), (wl, call, r))
     for r in range(len(SEEDS)):
         assert _frozen_equal_phi(grp.member(r))
     return grp
@@ -120,38 +56,38 @@ def test_members_equal_standalone_agents_without_feature_target():
 
 
 def test_group_graph_has_one_agents_launch_count():
-    _, _, B, _ = _dims(SMALL)
-    a = _standalone(SMALL, 3)
-    buf, _ = bench.synth_buffer(*_dims(SMALL)[:2], 0)
+    _, _, _, B, _ = sg.dims(SMALL)
+    a = sg.standalone(SMALL, 3)
+    buf, _ = bench.synth_buffer(*sg.dims(SMALL)[1:3], 0)
     a.train(buf, B)
     for R in (1, 3, 8):
-        g = _group(SMALL, tuple(range(100, 100 + R)))
-        rings, _ = _rings(SMALL, range(R))
+        g = sg.group(SMALL, tuple(range(100, 100 + R)))
+        rings, _ = sg.rings(SMALL, range(R))
         g.train(rings, B)
         assert g._graph_launches == a._graph_launches, (R, g._graph_launches, a._graph_launches)
 
 
 def test_members_are_independent():
-    _, _, B, _ = _dims(SMALL)
+    _, _, _, B, _ = sg.dims(SMALL)
     runs = []
     for bump in (0.0, 1e-3):                     # only member 1's parameters differ between the two groups
-        g = _group(SMALL)
-        rings, _ = _rings(SMALL, range(len(SEEDS)))
+        g = sg.group(SMALL, SEEDS)
+        rings, _ = sg.rings(SMALL, range(len(SEEDS)))
         g._members[1].params.add_(bump)
         for _ in range(5):
             g.train(rings, B)
-        runs.append([_state(m) for m in g._members])
-    _assert_equal(runs[0][0], runs[1][0], 'member 0')
-    _assert_equal(runs[0][2], runs[1][2], 'member 2')
+        runs.append([sg.state(m) for m in g._members])
+    sg.assert_equal(runs[0][0], runs[1][0], 'member 0')
+    sg.assert_equal(runs[0][2], runs[1][2], 'member 2')
     assert not torch.equal(runs[0][1]['params'], runs[1][1]['params'])
 
 
 def test_group_select_action_equals_standalone_in_one_launch():
     from rlrep_amd._lib import lib
-    S, A, B, _ = _dims(SMALL)
-    grp = _group(SMALL)
-    rings, alone_rings = _rings(SMALL, range(len(SEEDS)))
-    alone = [_standalone(SMALL, s) for s in SEEDS]
+    _, S, A, B, _ = sg.dims(SMALL)
+    grp = sg.group(SMALL, SEEDS)
+    rings, alone_rings = sg.rings(SMALL, range(len(SEEDS)))
+    alone = [sg.standalone(SMALL, s) for s in SEEDS]
     for _ in range(3):
         grp.train(rings, B)
         for r, a in enumerate(alone):
@@ -170,26 +106,26 @@ def test_group_select_action_equals_standalone_in_one_launch():
 
 def test_member_export_and_group_checkpoint(tmp_path):
     from rlrep_amd.agent.ctrlsac.ctrlsac_agent import CTRLSACAgent
-    S, A, B, kw = _dims(SMALL)
-    grp = _group(SMALL)
-    rings, alone_rings = _rings(SMALL, range(len(SEEDS)))
+    _, S, A, B, kw = sg.dims(SMALL)
+    grp = sg.group(SMALL, SEEDS)
+    rings, alone_rings = sg.rings(SMALL, range(len(SEEDS)))
     for _ in range(6):
         grp.train(rings, B)
     path = os.path.join(tmp_path, 'group.pt')
     grp.save(path)
     a = CTRLSACAgent(S, A, bench.Space(A), max_batch=B, seed=12345, pipeline=False, **kw)
     a.load(grp.member_snapshot(2))
-    grp2 = _group(SMALL)
+    grp2 = sg.group(SMALL, SEEDS)
     grp2.load(path)
     for _ in range(4):
         gi = grp.train(rings, B)
         ai = a.train(alone_rings[2], B)
         g2i = grp2.train(rings, B)
-    _assert_info_equal(gi[2], ai, 'export')
-    _assert_equal(_state(grp._members[2]), _state(a.core), 'export')
+    sg.assert_info_equal(gi[2], ai, 'export')
+    sg.assert_equal(sg.state(grp._members[2]), sg.state(a.core), 'export')
     for r in range(len(SEEDS)):
-        _assert_info_equal(gi[r], g2i[r], ('checkpoint', r))
-        _assert_equal(_state(grp._members[r]), _state(grp2._members[r]), ('checkpoint', r))
+        sg.assert_info_equal(gi[r], g2i[r], ('checkpoint', r))
+        sg.assert_equal(sg.state(grp._members[r]), sg.state(grp2._members[r]), ('checkpoint', r))
 
 
 def test_launcher_trains_several_ctrlsac_seeds(tmp_path):

@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
+import seed_group_util as sg  # noqa: E402
 
 # (seed, member_hyper): lr x seeds with a repeated seed, and discount, tau, target_update_period 1 / 2 / 3, alpha, no temperature learning
 SAC_MEMBERS = (
@@ -37,91 +38,25 @@ SAC_WORKLOADS = ('sac_pendulum_b64', 'sac_halfcheetah_b256')
 CTRL_SMALL = 'ctrlsac_halfcheetah_f256_b256'
 
 
-def _dims(wl, **extra):
-    alg, S, A, B, kw = bench.WORKLOADS[wl]
-    kw = dict(kw)
-    kw.update(extra)
-    return alg, S, A, B, kw
-
-
-def _standalone(wl, seed, hyper, **extra):
-    alg, S, A, B, kw = _dims(wl, **extra)
-    torch.manual_seed(seed)
-    if alg == 'sac':
-        from rlrep_amd.agent.sac.sac_agent import SACAgent
-        return SACAgent(S, A, bench.Space(A), max_batch=B, seed=seed, **kw, **hyper)
-    from rlrep_amd.agent.ctrlsac.ctrlsac_agent import CTRLSACAgent
-    return CTRLSACAgent(S, A, bench.Space(A), max_batch=B, seed=seed, pipeline=False, **kw, **hyper)
-
-
-def _group(wl, members, **extra):
-    alg, S, A, B, kw = _dims(wl, **extra)
-    if alg == 'sac':
-        from rlrep_amd.agent.sac.seed_batch import SACSeedBatch as G
-    else:
-        from rlrep_amd.agent.ctrlsac.seed_batch import CTRLSACSeedBatch as G
-    return G([s for s, _ in members], S, A, bench.Space(A), max_batch=B, member_hyper=[dict(h) for _, h in members], **kw)
-
-
-def _rings(wl, n):
-    """The group's rings and the standalone rings: member r's ring holds bench.synth_buffer(S, A, r)."""
-    from rlrep_amd.utils.buffer_group import ReplayBufferGroup
-    _, S, A, _, _ = _dims(wl)
-    g = ReplayBufferGroup(n, S, A, max_size=bench.REPLAY_N)
-    alone = []
-    for r in range(n):
-        buf, data = bench.synth_buffer(S, A, r)
-        g.load(r, data['state'], data['action'], data['next_state'], data['reward'], data['done'])
-        alone.append(buf)
-    return g, alone
-
-
-def _steps_words(core):
-    from rlrep_amd._lib import lib
-    ws0 = core._group.workspace if hasattr(core, '_group') else core.workspace
-    off = lib.rlrep_steps_dev(core.h) - ws0.data_ptr()
-    return core.workspace[off:off + 16].view(torch.int32).clone()
-
-
-def _state(core):
-    """Everything a train() writes: parameters and targets, Adam moments and step counts, the float64 temperature state, the train() counter
-    (and the optimizer records' hyper words: the member's lr / tau)."""
-    torch.cuda.synchronize()
-    cfg = core.group_cfg()
-    return {'params': core.params.clone(), 'targets': core.targets.clone(), 'exp_avg': core.exp_avg.clone(),
-            'exp_avg_sq': core.exp_avg_sq.clone(), 'alpha_state': core.alpha_state.clone(),
-            'optimizer_steps': cfg[:, 0].view(torch.int32).clone(), 'optimizer_hyper': cfg[:, 1:6].clone(),
-            'train_steps': _steps_words(core)}
-
-
-def _assert_equal(sa, sb, what):
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), (what, k)
-
-
-def _assert_info_equal(ia, ib, what):
-    assert set(ia.keys()) == set(ib.keys())
-    for k in ia.keys():
-        a, b = ia[k], ib[k]
-        a = a.item() if torch.is_tensor(a) else a
-        b = b.item() if torch.is_tensor(b) else b
-        assert a == b or (a != a and b != b), (what, k, a, b)
+def _swept_state(core):
+    """sg.state and the optimizer records' hyper words: the member's lr / tau"""
+    return sg.state(core, hyper=True)
 
 
 def _bit_exact(wl, members, calls, **extra):
-    _, _, _, B, _ = _dims(wl, **extra)
-    grp = _group(wl, members, **extra)
-    rings, alone_rings = _rings(wl, len(members))
-    alone = [_standalone(wl, s, h, **extra) for s, h in members]
+    _, _, _, B, _ = sg.dims(wl, **extra)
+    grp = sg.group(wl, *zip(*members), **extra)
+    rings, alone_rings = sg.rings(wl, range(len(members)))
+    alone = [sg.standalone(wl, s, h, **extra) for s, h in members]
     for r in range(len(members)):
-        _assert_equal(_state(grp._members[r]), _state(alone[r].core), ('init', r))
+        sg.assert_equal(_swept_state(grp._members[r]), _swept_state(alone[r].core), ('init', r))
     for call in range(1, calls + 1):
         infos = grp.train(rings, B)
         ainfos = [a.train(alone_rings[r], B) for r, a in enumerate(alone)]
         if call in (1, 2, calls):
             for r in range(len(members)):
-                _assert_info_equal(infos[r], ainfos[r], (wl, call, r))
-                _assert_equal(_state(grp._members[r]), _state(alone[r].core), (wl, call, r))
+                sg.assert_info_equal(infos[r], ainfos[r], (wl, call, r))
+                sg.assert_equal(_swept_state(grp._members[r]), _swept_state(alone[r].core), (wl, call, r))
     return grp
 
 
@@ -148,14 +83,14 @@ def test_ctrlsac_sweep_f2048_two_members():
 
 @pytest.mark.parametrize('wl, members', [('sac_halfcheetah_b256', SAC_MEMBERS), (CTRL_SMALL, CTRL_MEMBERS)])
 def test_sweep_group_graph_has_one_agents_launch_count(wl, members):
-    _, S, A, B, _ = _dims(wl)
-    a = _standalone(wl, 3, {})
+    _, S, A, B, _ = sg.dims(wl)
+    a = sg.standalone(wl, 3, {})
     buf, _ = bench.synth_buffer(S, A, 0)
     a.train(buf, B)
     for R in (1, 3, 8):
         mem = [(100 + (r % 2), dict(members[r % len(members)][1], discount=0.9 + 0.01 * r)) for r in range(R)]
-        g = _group(wl, mem)
-        rings, _ = _rings(wl, R)
+        g = sg.group(wl, *zip(*mem))
+        rings, _ = sg.rings(wl, range(R))
         g.train(rings, B)
         assert g._graph_launches == a._graph_launches, (wl, R, g._graph_launches, a._graph_launches)
 
@@ -164,12 +99,12 @@ def test_set_member_hyper_between_replays_changes_that_member_only():
     from rlrep_amd._lib import lib, check
     from rlrep_amd.core import _stream
     wl = 'sac_halfcheetah_b256'
-    _, _, _, B, _ = _dims(wl)
+    _, _, _, B, _ = sg.dims(wl)
     members = SAC_MEMBERS[:3]
     runs = []
     for change in (False, True):
-        g = _group(wl, members)
-        rings, _ = _rings(wl, len(members))
+        g = sg.group(wl, *zip(*members))
+        rings, _ = sg.rings(wl, range(len(members)))
         for _ in range(3):
             g.train(rings, B)
         graph = g._graph
@@ -179,9 +114,9 @@ def test_set_member_hyper_between_replays_changes_that_member_only():
         for _ in range(4):
             g.train(rings, B)
         assert g._graph is graph                 # the same captured graph replays the new values: no re-capture
-        runs.append([_state(m) for m in g._members])
-    _assert_equal(runs[0][0], runs[1][0], 'member 0')
-    _assert_equal(runs[0][2], runs[1][2], 'member 2')
+        runs.append([_swept_state(m) for m in g._members])
+    sg.assert_equal(runs[0][0], runs[1][0], 'member 0')
+    sg.assert_equal(runs[0][2], runs[1][2], 'member 2')
     for k in ('params', 'targets', 'alpha_state', 'optimizer_hyper'):
         assert not torch.equal(runs[0][1][k], runs[1][1][k]), k
 
@@ -191,7 +126,7 @@ def test_member_hyper_abi_refusals_and_read_back():
     from rlrep_amd._lib import lib
     from rlrep_amd.core import _stream
     wl = 'sac_pendulum_b64'
-    g = _group(wl, SAC_MEMBERS[:2])
+    g = sg.group(wl, *zip(*SAC_MEMBERS[:2]))
     good = g._hyper_struct(g.core, g.member_hyper(1))
     out = _lib.Hyper()
     assert lib.rlrep_group_get_member_hyper(g.core.h, 1, C.byref(out)) == 0
@@ -209,7 +144,7 @@ def test_member_hyper_abi_refusals_and_read_back():
         for k, v in kw.items():
             setattr(h, k, v)
         return h
-    plain = _standalone(wl, 3, {})
+    plain = sg.standalone(wl, 3, {})
     refused(good, 'not a seed group', handle=plain.core.h)
     refused(good, 'member 2 outside [0, 2)', member=2)
     refused(good, 'member -1 outside', member=-1)
@@ -231,10 +166,10 @@ def test_member_hyper_abi_refusals_and_read_back():
 def test_member_export_and_sweep_group_checkpoint(tmp_path):
     from rlrep_amd.agent.sac.sac_agent import SACAgent
     wl = 'sac_pendulum_b64'
-    _, S, A, B, kw = _dims(wl)
+    _, S, A, B, kw = sg.dims(wl)
     members = SAC_MEMBERS[:4]
-    grp = _group(wl, members)
-    rings, alone_rings = _rings(wl, len(members))
+    grp = sg.group(wl, *zip(*members))
+    rings, alone_rings = sg.rings(wl, range(len(members)))
     for _ in range(6):
         grp.train(rings, B)
     path = os.path.join(tmp_path, 'group.pt')
@@ -243,20 +178,20 @@ def test_member_export_and_sweep_group_checkpoint(tmp_path):
     r = 3
     a = SACAgent(S, A, bench.Space(A), max_batch=B, seed=12345, **kw, **grp.member_hyper(r))
     a.load(grp.member_snapshot(r))
-    grp2 = _group(wl, members)
+    grp2 = sg.group(wl, *zip(*members))
     grp2.load(path)
     for _ in range(4):
         gi = grp.train(rings, B)
         ai = a.train(alone_rings[r], B)
         g2i = grp2.train(rings, B)
-    _assert_info_equal(gi[r], ai, 'export')
-    _assert_equal(_state(grp._members[r]), _state(a.core), 'export')
+    sg.assert_info_equal(gi[r], ai, 'export')
+    sg.assert_equal(_swept_state(grp._members[r]), _swept_state(a.core), 'export')
     for q in range(len(members)):
-        _assert_info_equal(gi[q], g2i[q], ('checkpoint', q))
-        _assert_equal(_state(grp._members[q]), _state(grp2._members[q]), ('checkpoint', q))
+        sg.assert_info_equal(gi[q], g2i[q], ('checkpoint', q))
+        sg.assert_equal(_swept_state(grp._members[q]), _swept_state(grp2._members[q]), ('checkpoint', q))
     other = [(s, dict(h)) for s, h in members]
     other[2][1]['tau'] = 0.03
-    grp3 = _group(wl, other)
+    grp3 = sg.group(wl, *zip(*other))
     with pytest.raises(RuntimeError, match='member 2 hyper-parameters differ'):
         grp3.load(path)
 

@@ -4,6 +4,8 @@ import ctypes as C
 
 import pytest
 
+from seed_group_util import run_launcher
+
 
 def test_member_hyper_entry_points_refuse_what_is_not_a_group():
     from rlrep_amd import _lib
@@ -71,11 +73,6 @@ def test_member_hypers_resolve_against_the_agents_defaults():
     assert hc[0]['lr'] == 1e-4 and hc[0]['feature_tau'] == 0.01
 
 
-def _run(argv):
-    from rlrep_amd import main
-    main.run(argv)
-
-
 @pytest.mark.parametrize('argv, words', [
     (['--alg', 'sac', '--seeds', '0,1', '--sweep', 'beta=0.9'], "unknown key 'beta'"),
     (['--alg', 'sac', '--seeds', '0,1', '--sweep', 'feature_tau=0.01'], 'feature_tau is not a hyper-parameter of --alg sac'),
@@ -91,18 +88,18 @@ def _run(argv):
 ])
 def test_sweep_arguments_are_checked_before_the_gpu(argv, words):
     with pytest.raises(SystemExit) as e:
-        _run(argv + ['--env', 'Pendulum-v1'])
+        run_launcher(argv + ['--env', 'Pendulum-v1'])
     assert words in str(e.value), str(e.value)
 
 
 def test_existing_launcher_checks_come_first():
     # the distinct-seeds and algorithm checks keep their messages, and run before any --sweep check
     with pytest.raises(SystemExit, match='distinct'):
-        _run(['--alg', 'sac', '--env', 'Pendulum-v1', '--seeds', '1,1', '--sweep', 'nonsense=1'])
+        run_launcher(['--alg', 'sac', '--env', 'Pendulum-v1', '--seeds', '1,1', '--sweep', 'nonsense=1'])
     with pytest.raises(SystemExit, match='sac only'):
-        _run(['--alg', 'vlsac', '--env', 'Pendulum-v1', '--seeds', '0,1', '--sweep', 'lr=1e-4'])
+        run_launcher(['--alg', 'vlsac', '--env', 'Pendulum-v1', '--seeds', '0,1', '--sweep', 'lr=1e-4'])
     with pytest.raises(SystemExit, match='sac only'):
-        _run(['--alg', 'diffsrsac', '--env', 'Pendulum-v1', '--seeds', '0,1', '--sweep', 'feature_tau=0.1'])
+        run_launcher(['--alg', 'diffsrsac', '--env', 'Pendulum-v1', '--seeds', '0,1', '--sweep', 'feature_tau=0.1'])
 
 
 def test_sweep_tags_and_member_order():
