@@ -1,7 +1,7 @@
 """VLSACAgent (reference agent/vlsac/vlsac_agent.py:67-273) on the HIP step programs.
 
 feature_step = VAE ELBO (encoder/decoder/f) + Adam + Polyak f->f_target in one step program
-(csrc/engine.hip build_vlsac); critic = noise-averaged RFF critic (csrc/noisecritic.hip).
+(csrc/agents1.hip build_vlsac); critic = noise-averaged RFF critic (csrc/noisecritic.hip).
 """
 import torch
 

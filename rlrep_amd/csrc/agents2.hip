@@ -1,21 +1,6 @@
 // Step programs of ctrlsac, spedersac and diffsrsac (host side; kernels in gemm16.hip / replearn.hip /
-// elementwise.hip).  Same construction as sac/vlsac in engine.hip: a short list of grouped launches.
+// elementwise.hip).  Same construction as sac/vlsac in agents1.hip: a short list of grouped launches.
 #include "engine_internal.h"
-
-extern "C" {
-int rl_launch_infonce(const InfoNce* p, hipStream_t st);
-int rl_launch_colsum(const ColSum* p, hipStream_t st);
-int rl_launch_reg_stats(const RegStats* p, hipStream_t st);
-int rl_launch_speder_rows(const SpederRows* p, hipStream_t st);
-int rl_launch_speder_grads(const SpederGrads* p, hipStream_t st);
-int rl_launch_diffsr_perturb(const DiffsrPerturb* p, hipStream_t st);
-int rl_launch_diffsr_score(const DiffsrScore* p, hipStream_t st);
-int rl_launch_copy2(const float* src, float* d1, float* d2, long long n, hipStream_t st);
-// comm.hip: ctrlsac's batch-coupled exchanges as launches of the step program (attached agents)
-int rl_launch_xchg_gather(const DpPull* proto, int channel, long long off, long long n, int no_done, hipStream_t st);
-int rl_launch_xchg_reduce(const DpPull* proto, int channel, long long off, long long n, float* out, int two_shot, int no_done, hipStream_t st);
-int rl_launch_slots_sum(const DpSlots* d, float* out, hipStream_t st);
-}
 
 // ================================================================================================
 // generic MLP (utils/util.py:85-96: Linear(+ELU) x depth, Linear) on Sequential names <prefix>.{0,2,..}

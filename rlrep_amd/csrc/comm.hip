@@ -17,9 +17,7 @@
 #include "../../include/rlrep.h"
 #include "dp_pull.h"
 #include "group.h"
-
-void rl_set_error(const char* fmt, ...);
-extern long long g_rl_launches;
+#include "launchers.h"
 
 struct rlrep_comm {
     int rank = 0, world = 1;
@@ -34,9 +32,6 @@ struct rlrep_comm {
     size_t scratch_off = 0, red_off = 0, flags_off = 0, bytes = 0;
     bool fine_grained = false, connected = false;
 };
-
-// rlrep_agent side (engine.hip)
-extern "C" int rl_agent_attach_dp(rlrep_agent* ag, const DpAttach* at, int* attached_mask);
 
 extern "C" void rl_comm_fill_pull(const rlrep_comm* c, DpPull* d) {
     memset(d, 0, sizeof(*d));

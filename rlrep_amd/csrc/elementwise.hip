@@ -6,6 +6,7 @@
 #include "heads_vae_tile.h"      // (also: RL_CONST_AS)
 #include "x3.h"
 #include "group.h"
+#include "launchers.h"
 
 // ------------------------------------------------------------------------------------------------
 // minibatch slot fill: replay-ring gather (idx) or five separate arrays (reference Batch fields)

@@ -11,56 +11,7 @@
 #include "common.h"
 #include "kparams.h"
 #include "rowprog.h"
-
-// kernel launchers (defined next to the kernels)
-extern "C" {
-int rl_launch_gemm16(int la, int lb, int nf, const GemmBatch* gb, int total_tiles, hipStream_t st);
-int rl_launch_gemm_lds(int bt, int la, int lb, const GemmBatch* gb, int total_tiles, int fin_blocks, hipStream_t st);
-int rl_gemm_lds_align_ok(const GemmTask* t, int la, int lb);
-int rl_gemm_lds_dims_ok(const GemmTask* t, int la, int lb);
-int rl_gemm_lds_ptrs_ok(const GemmTask* t);
-int rl_gemm_lds_dim_flags(const GemmTask* t, int la, int lb);
-int rl_gemm_lds_ptr_flags(const GemmTask* t);
-int rl_gemm_lds_route(const GemmTask* t, int la, int lb, int extra_flags, int* splits, int* kchunk, int* flags);
-void rl_gemm_lds_plan(const GemmTask* t, int* bt, int* splits, int* kchunk);
-int rl_launch_nc_fwd(const NcFwdBatch* nb, int total_tiles, int g2, hipStream_t st);
-int rl_launch_nc_dx(const NcDxTask* t, hipStream_t st);
-int rl_launch_nc_dw(const NcDwBatch* nb, int total_tiles, hipStream_t st);
-int rl_nc_init();
-int rl_nc_dw_engine();
-int rl_nc_dw_splits(int B, int F, int H, int ntasks);
-int rl_nc_fwd_cols();
-void rl_nc_fwd_plan(const NcFwdTask* tasks, int ntasks, int* engine, int* g2, int* cols);
-int rl_launch_fill_slot(const SlotFill* p, hipStream_t st);
-int rl_launch_philox(const PhiloxFill* p, hipStream_t st);
-int rl_launch_philox_raw(const uint32_t* ck, uint32_t* out, long long n, hipStream_t st);
-int rl_launch_policy_fwd(const PolicyFwd* p, hipStream_t st);
-int rl_launch_policy_bwd(const PolicyBwd* p, hipStream_t st);
-int rl_launch_vae_mid(const VaeMid* p, hipStream_t st);
-int rl_launch_heads_vae(const HeadsVae* p, hipStream_t st);
-int rl_launch_xchain(const XcLaunch* L, hipStream_t st);
-int rl_launch_vae_mse(const VaeMse* p, hipStream_t st);
-int rl_launch_qhead_critic(const QHeadCritic* p, hipStream_t st);
-int rl_launch_qhead_actor(const QHeadActor* p, hipStream_t st);
-int rl_launch_gemm16_duo(int split, int nf2, const GemmBatch* gb, int total_tiles, hipStream_t st);
-extern "C" int rl_replearn_init();
-int rl_launch_counter_sync(int* c, int mirror, hipStream_t st);
-int rl_launch_adam(const AdamTask* task, int adam_blocks, const FinTask* fin, int nfin, const SlotFill* sf, const SlotFill* sf2, const AdamSnap* snap, const DpPull* dp, hipStream_t st);
-int rl_launch_adam_l1(const AdamTask* task, int adam_blocks, const FinTask* fin, int nfin, const SlotFill* sf, const GemmTask* g0, const GemmTask* g1, hipStream_t st);
-int rl_launch_train_prologue(TrainPrologue* p, hipStream_t st);
-int rl_launch_polyak(const PolyakTask* t, hipStream_t st);
-int rl_launch_counter_inc(int* c, int mirror, hipStream_t st);
-int rl_launch_copy(const float* src, float* dst, long long n, hipStream_t st);
-int rl_launch_copy_segs(const CopySegs* p, hipStream_t st);
-int rl_launch_shadow(const ShadowEnt* sh_dev, int nsh, int ntiles, const float* base, int target, hipStream_t st);
-}
-
-void rl_set_error(const char* fmt, ...);
-// diagnostic switches (engine.hip): token listed in RLREP_DISABLE / value of a token of RLREP_ENABLE ("1" when listed bare; nullptr: not listed),
-// as parsed at the last library entry (rl_switches_read)
-void rl_switches_read();
-bool rl_off(const char* token);
-const char* rl_opt(const char* token);
+#include "launchers.h"
 
 // metric slots (union over the agents; names per agent in rlrep_metric_names)
 enum Metric : int {
@@ -136,10 +87,6 @@ struct Workspace {
 // ------------------------------------------------------------------------------------------------
 // programs
 // ------------------------------------------------------------------------------------------------
-// process-wide count of kernel launches issued by the library (rlrep_launch_counter: bench.py counts the launches a captured train() holds)
-extern long long g_rl_launches;
-extern long long g_rl_front[4];                 // gemm16.hip: launches per front end (fast, fast4, fastpre, record)
-extern "C" void rl_gemm16_read_env();           // gemm16.hip: RLREP_DISABLE=gemm16_fast / gemm16_spec, RLREP_ENABLE=gemm16_trace, read at agent creation
 // engine / flops / bytes: what rlrep_stage_info reports (include/rlrep.h RLREP_ENGINE_*: which kernel family the stage launches, the
 // ALGORITHMIC flops (2 * MAC) of its products and the bytes of their operands and results, each counted once)
 struct Stage { std::function<int(hipStream_t)> run; const char* what; int engine = 0; double flops = 0.0, bytes = 0.0; };

@@ -1,4 +1,4 @@
-// Internal definitions shared by engine.hip and agents2.hip (agent state, program builder).
+// Internal definitions shared by engine.hip, agents1.hip, agents2.hip and group_api.hip (agent state, program builder).
 #pragma once
 #include "engine.h"
 #include "group.h"
@@ -702,6 +702,10 @@ void update_target_program(rlrep_agent* ag, const std::string& first_src, const 
 Slot defer_begin(Builder& b, rlrep_agent* ag, int set, const char* prefix, const char* first, const float* block_src, int64_t block_n);
 void defer_end(Builder& b, rlrep_agent* ag, int set, const Slot& keep, const std::string& critic_target_first, std::vector<FinTask> cfins);
 
+// agents1.hip
+void build_sac(Builder& b, rlrep_agent* ag);
+void build_vlsac(Builder& b, rlrep_agent* ag);
+
 // agents2.hip
 void lay_ctrlsac(const rlrep_dims& d, Layout& L);
 void lay_spedersac(const rlrep_dims& d, Layout& L);
@@ -711,3 +715,23 @@ void lay_six(Layout& L, const std::string& m, int in_f, int H, int arena, int gr
 void build_ctrlsac(Builder& b, rlrep_agent* ag);
 void build_spedersac(Builder& b, rlrep_agent* ag);
 void build_diffsrsac(Builder& b, rlrep_agent* ag);
+
+// engine.hip
+bool check_dims(const rlrep_dims* d);
+int ensure_batch(rlrep_agent* ag, int B);
+// a seed group's launches for the duration of a library call: while one is alive, rl_grp_active() answers with the agent's group
+struct GrpScope {
+    bool set = false, prev_on = false; RlGrp prev{};
+    explicit GrpScope(const rlrep_agent* ag);
+    ~GrpScope();
+};
+// entry points that have no group form refuse a seed group by name (instead of running member 0 alone)
+#define GROUP_REFUSE(what) \
+    if (ag && ag->members > 0) { rl_set_error("%s: not available on a seed group (rlrep_group_create)", what); return RLREP_ERR_ARG; }
+// ... and the entry points of a seed group refuse everything else
+#define GROUP_ONLY(what) \
+    if (!ag || ag->members <= 0) { rl_set_error("%s: not a seed group", what); return RLREP_ERR_ARG; }
+
+// group_api.hip
+// [p, p + bytes) inside member 0's block [grp_lo, grp_lo + stride): what a group launch moves by r * stride must stay in member r's block
+bool in_member0(const rlrep_agent* ag, const void* p, long long bytes);

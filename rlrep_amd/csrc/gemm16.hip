@@ -25,6 +25,7 @@
 #include "kparams.h"
 #include "gemm16_tile.h"
 #include "group.h"
+#include "launchers.h"
 
 #ifdef RL_TIMING
 // Instrumented build (tools/exp/gemm_timeline.py): thread 0 of every 8th workgroup records the 100 MHz wall clock at

@@ -27,9 +27,9 @@
 #define GL_DIR_PARAMS int d0, int d1, int d2, int d3, int d4, int d5, int d6, int d7
 #define GL_DIR_ARGS(D) (D)[0], (D)[1], (D)[2], (D)[3], (D)[4], (D)[5], (D)[6], (D)[7]
 #define GL_DIR_FWD d0, d1, d2, d3, d4, d5, d6, d7
-extern long long g_rl_launches;
 #include "kparams.h"
 #include "group.h"
+#include "launchers.h"
 
 #define GL_BK 32
 #define GL_KCS 36

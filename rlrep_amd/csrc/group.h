@@ -24,7 +24,6 @@ struct RlGrp {
     const int* live;                    // the live table (device): n_live, then slot_member[members] -- see RL_GRP_MEMBER
     int grid_y;                         // grid y of the group launches: members (RLREP_ENABLE=grp_compact: the live members at the last rlrep_group_set_live)
 };
-extern "C" const RlGrp* rl_grp_active();
 // what a launcher without a group form returns while a group is active (the stage fails with this code: no member is left behind silently)
 #define RL_GRP_UNSUPPORTED 77
 

@@ -1,0 +1,371 @@
+// C ABI of seed groups and of their device environments (include/rlrep.h rlrep_group_*, rlrep_group_env_*): host side; the group forms of the
+// kernels live beside the single-agent kernels, group_clone.hip and group_env.hip hold the kernels only groups have.
+#include "engine_internal.h"
+#include <cmath>
+#include <cstddef>
+
+// [p, p + bytes) inside member 0's block [grp_lo, grp_lo + stride): what a group launch moves by r * stride must stay in member r's block
+bool in_member0(const rlrep_agent* ag, const void* p, long long bytes) {
+    const char* q = (const char*)p;
+    return q && bytes >= 0 && q >= ag->grp_lo && q + bytes <= ag->grp_lo + ag->grp_stride;
+}
+
+extern "C" {
+
+// ---- seed groups ------------------------------------------------------------------------------------------------------------------------------
+// byte extent of the seven arenas of one member: [lowest arena pointer, end of the highest)
+static long long member_span(const rlrep_layout_info& info, const rlrep_arenas* a) {
+    const char* p[7] = {(const char*)a->param_dev, (const char*)a->target_dev, (const char*)a->grad_dev, (const char*)a->exp_avg_dev,
+                        (const char*)a->exp_avg_sq_dev, (const char*)a->workspace_dev, (const char*)a->alpha_state_dev};
+    const long long n[7] = {4 * info.param_floats, 4 * info.target_floats, 4 * info.grad_floats, 4 * info.param_floats, 4 * info.param_floats,
+                            (long long)info.workspace_bytes, 4 * 8};
+    const char* lo = p[0]; const char* hi = p[0] + n[0];
+    for (int q = 1; q < 7; ++q) { lo = std::min(lo, p[q]); hi = std::max(hi, p[q] + n[q]); }
+    return (long long)(hi - lo);
+}
+int32_t rlrep_group_max_members(void) { return RLREP_GROUP_MAX_MEMBERS; }
+// what the step programs carry by value from rlrep_hyper, as a group member's record holds it (kparams.h MemberHyper; agents1.hip actor_fins,
+// critic_apply_folded and the qhead critic stages read the same fields)
+static MemberHyper member_hyper_of(const rlrep_hyper& h) {
+    MemberHyper m;
+    m.gamma = h.discount; m.pol_period = h.target_update_period; m.alpha_lr = h.lr_actor; m.learn = h.learn_alpha;
+    return m;
+}
+
+int32_t rlrep_group_create(const rlrep_dims* dims, const rlrep_hyper* hyper, const rlrep_arenas* arenas, int32_t members, int64_t member_stride_bytes,
+                           void* stream, rlrep_agent** out) {
+    if (!dims || !hyper || !arenas || !out) { rl_set_error("group_create: null argument"); return RLREP_ERR_ARG; }
+    if (dims->alg != RLREP_ALG_SAC && dims->alg != RLREP_ALG_CTRLSAC) {
+        rl_set_error("group_create: seed groups are built for sac and ctrlsac only (alg %d)", dims->alg); return RLREP_ERR_ARG;
+    }
+    if (members < 1 || members > RLREP_GROUP_MAX_MEMBERS) { rl_set_error("group_create: members %d outside [1, %d]", members, RLREP_GROUP_MAX_MEMBERS); return RLREP_ERR_ARG; }
+    if (dims->world_size > 1 || hyper->world_size > 1) { rl_set_error("group_create: a seed group does not attach to data parallel (world_size %d)", std::max(dims->world_size, hyper->world_size)); return RLREP_ERR_ARG; }
+    if (member_stride_bytes <= 0 || (member_stride_bytes & 255)) { rl_set_error("group_create: member stride %lld is not a positive multiple of 256 bytes", (long long)member_stride_bytes); return RLREP_ERR_ARG; }
+    if (!arenas->param_dev || !arenas->grad_dev || !arenas->exp_avg_dev || !arenas->exp_avg_sq_dev || !arenas->workspace_dev ||
+        !arenas->alpha_state_dev || !arenas->target_dev) { rl_set_error("group_create: null arena pointer"); return RLREP_ERR_ARG; }
+    rlrep_layout_info info;
+    if (!check_dims(dims) || rlrep_layout(dims, &info, nullptr, 0) != 0) return RLREP_ERR_ARG;
+    const long long span = member_span(info, arenas);
+    if (member_stride_bytes < span) { rl_set_error("group_create: member stride %lld is smaller than the member span %lld", (long long)member_stride_bytes, span); return RLREP_ERR_ARG; }
+    rlrep_agent* ag = nullptr;
+    int rc = rlrep_agent_create(dims, hyper, arenas, stream, &ag);
+    if (rc) return rc;
+    ag->members = members; ag->grp_stride = member_stride_bytes;
+    // every member starts as a byte copy of member 0's block (step counters, optimizer records, metric slots; the caller then writes each
+    // member's parameters): the programs' device records are member 0's, and a group launch moves every pointer it finds in them
+    hipError_t e = hipMalloc((void**)&ag->grp_seeds, sizeof(unsigned long long) * members);
+    if (e == hipSuccess) e = hipMemsetAsync(ag->grp_seeds, 0, sizeof(unsigned long long) * members, (hipStream_t)stream);
+    // the live table: everybody live (n_live = members, slot r = member r)
+    LiveTab live0; memset(&live0, 0, sizeof(live0));
+    live0.n_live = members;
+    for (int m = 0; m < members; ++m) live0.slot_member[m] = m;
+    if (e == hipSuccess) e = hipMalloc((void**)&ag->grp_live, sizeof(int) * (1 + members));
+    if (e == hipSuccess) e = hipMemcpyAsync(ag->grp_live, &live0, sizeof(int) * (1 + members), hipMemcpyHostToDevice, (hipStream_t)stream);   // (synchronised below)
+    ag->grp_live_mask.assign(members, 1);
+    ag->grp_compact = rl_opt("grp_compact") != nullptr; ag->grp_grid_y = members;
+    const char* lo = (const char*)arenas->param_dev;
+    for (const void* q : {(const void*)arenas->target_dev, (const void*)arenas->grad_dev, (const void*)arenas->exp_avg_dev, (const void*)arenas->exp_avg_sq_dev,
+                          (const void*)arenas->workspace_dev, (const void*)arenas->alpha_state_dev}) lo = std::min(lo, (const char*)q);
+    ag->grp_lo = lo;
+    ag->grp_hyper.assign(members, ag->h);
+    const MemberHyper mh0 = member_hyper_of(ag->h);
+    if (e == hipSuccess) e = hipMemcpyAsync(ag->mhyp, &mh0, sizeof(mh0), hipMemcpyHostToDevice, (hipStream_t)stream);
+    for (int m = 1; m < members && e == hipSuccess; ++m)
+        e = hipMemcpyAsync((char*)lo + (long long)m * member_stride_bytes, lo, (size_t)span, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) { rl_set_error("group_create: %s", hipGetErrorString(e)); rlrep_agent_destroy(ag); return RLREP_ERR_HIP; }
+    *out = ag;
+    return 0;
+}
+int32_t rlrep_group_members(rlrep_agent* ag) { return ag ? ag->members : RLREP_ERR_ARG; }
+int32_t rlrep_group_set_seeds(rlrep_agent* ag, const uint64_t* seeds, int32_t n, void* stream) {
+    if (!ag || ag->members <= 0 || !seeds || n != ag->members) { rl_set_error("group_set_seeds: need one seed per member of a group"); return RLREP_ERR_ARG; }
+    const hipError_t e = hipMemcpyAsync(ag->grp_seeds, seeds, sizeof(uint64_t) * n, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) (void)hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) { rl_set_error("group_set_seeds: %s", hipGetErrorString(e)); return RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_group_set_member_hyper(rlrep_agent* ag, int32_t member, const rlrep_hyper* hyper, void* stream) {
+    GROUP_ONLY("group_set_member_hyper")
+    if (member < 0 || member >= ag->members) { rl_set_error("group_set_member_hyper: member %d outside [0, %d)", member, ag->members); return RLREP_ERR_ARG; }
+    if (!hyper) { rl_set_error("group_set_member_hyper: null hyper"); return RLREP_ERR_ARG; }
+    const rlrep_hyper& g = ag->h;
+    // structural: these shape the step programs (or are shared by every member's launches) -- equal to the group's or refused
+    const int ws = hyper->world_size > 0 ? hyper->world_size : 1;
+    const struct { const char* name; double have, want; } st[] = {
+        {"target_entropy", hyper->target_entropy, g.target_entropy}, {"sigma_scale", hyper->sigma_scale, g.sigma_scale},
+        {"extra_feature_steps", (double)hyper->extra_feature_steps, (double)g.extra_feature_steps}, {"world_size", (double)ws, (double)g.world_size},
+        {"beta1", hyper->beta1, g.beta1}, {"beta2", hyper->beta2, g.beta2}, {"adam_eps", hyper->adam_eps, g.adam_eps},
+        {"critic_reg_lambda", hyper->critic_reg_lambda, g.critic_reg_lambda}};
+    for (const auto& f : st)
+        if (!(f.have == f.want)) {
+            rl_set_error("group_set_member_hyper: %s is structural and must equal the group's (%g, the group has %g)", f.name, f.have, f.want);
+            return RLREP_ERR_ARG;
+        }
+    const struct { const char* name; float v; } lrs[] = {{"lr_feature", hyper->lr_feature}, {"lr_critic", hyper->lr_critic}, {"lr_actor", hyper->lr_actor}};
+    for (const auto& f : lrs)
+        if (!std::isfinite(f.v) || !(f.v > 0.f)) { rl_set_error("group_set_member_hyper: %s %g is not a finite positive learning rate", f.name, (double)f.v); return RLREP_ERR_ARG; }
+    if (!std::isfinite(hyper->discount)) { rl_set_error("group_set_member_hyper: discount %g is not finite", (double)hyper->discount); return RLREP_ERR_ARG; }
+    if (!(hyper->tau >= 0.f && hyper->tau <= 1.f)) { rl_set_error("group_set_member_hyper: tau %g outside [0, 1]", (double)hyper->tau); return RLREP_ERR_ARG; }
+    if (!(hyper->feature_tau >= 0.f && hyper->feature_tau <= 1.f)) { rl_set_error("group_set_member_hyper: feature_tau %g outside [0, 1]", (double)hyper->feature_tau); return RLREP_ERR_ARG; }
+    if (hyper->target_update_period < 1) { rl_set_error("group_set_member_hyper: target_update_period %d is below 1", hyper->target_update_period); return RLREP_ERR_ARG; }
+    rlrep_hyper h = *hyper;
+    h.world_size = ws;
+    // the member's optimizer records: lr, beta1, beta2, eps, tau of each of the four groups -- as rlrep_agent_create writes them (the step
+    // counters and the running powers stay); then its by-value record.  Both are read at the next launch: captured graphs need no re-capture.
+    struct Words { float lr, b1, b2, eps, tau; } w[4];
+    static_assert(offsetof(GroupCfg, tau) - offsetof(GroupCfg, lr) == 4 * sizeof(float), "GroupCfg words lr .. tau");
+    for (int q = 0; q < 4; ++q) {
+        w[q].lr = q == 1 ? h.lr_critic : q == 2 ? h.lr_actor : h.lr_feature;
+        w[q].b1 = h.beta1; w[q].b2 = h.beta2; w[q].eps = h.adam_eps;
+        w[q].tau = (q == 0) ? h.feature_tau : (q == 1) ? h.tau : 0.f;
+    }
+    const MemberHyper mh = member_hyper_of(h);
+    const long long d = (long long)member * ag->grp_stride;
+    hipStream_t sm = (hipStream_t)stream;
+    hipError_t e = hipSuccess;
+    for (int q = 0; q < 4 && e == hipSuccess; ++q)
+        e = hipMemcpyAsync((char*)&ag->adam_step[q].lr + d, &w[q], sizeof(Words), hipMemcpyHostToDevice, sm);
+    if (e == hipSuccess) e = hipMemcpyAsync((char*)ag->mhyp + d, &mh, sizeof(mh), hipMemcpyHostToDevice, sm);
+    if (e == hipSuccess) e = hipStreamSynchronize(sm);          // (the host words above live on this stack frame)
+    if (e != hipSuccess) { rl_set_error("group_set_member_hyper: %s", hipGetErrorString(e)); return RLREP_ERR_HIP; }
+    ag->grp_hyper[member] = h;
+    return 0;
+}
+int32_t rlrep_group_get_member_hyper(rlrep_agent* ag, int32_t member, rlrep_hyper* out) {
+    GROUP_ONLY("group_get_member_hyper")
+    if (member < 0 || member >= ag->members) { rl_set_error("group_get_member_hyper: member %d outside [0, %d)", member, ag->members); return RLREP_ERR_ARG; }
+    if (!out) { rl_set_error("group_get_member_hyper: null output"); return RLREP_ERR_ARG; }
+    *out = ag->grp_hyper[member];
+    return 0;
+}
+// what changes a group between two train() calls refuses to run inside one: `what` names the caller in the message
+static bool in_train_refused(const char* what, const rlrep_agent* ag) {
+    if (ag->in_train) rl_set_error("%s: inside a train() (between rlrep_group_train_prologue and the end of that train())", what);
+    return ag->in_train;
+}
+int32_t rlrep_group_clone_members(rlrep_agent* ag, const int32_t* src_host, const int32_t* dst_host, int32_t n, void* stream) {
+    GROUP_ONLY("group_clone_members")
+    if (!src_host || !dst_host) { rl_set_error("group_clone_members: null member list"); return RLREP_ERR_ARG; }
+    if (n < 1 || n > ag->members) { rl_set_error("group_clone_members: n %d outside [1, %d]", n, ag->members); return RLREP_ERR_ARG; }
+    // pairs must be independent of each other (one launch serves all of them, in no order): role 1 = a source, 2 = a destination
+    char role[RLREP_GROUP_MAX_MEMBERS] = {0};
+    ClonePairs pairs; memset(&pairs, 0, sizeof(pairs));
+    for (int k = 0; k < n; ++k) {
+        const int s = src_host[k], d = dst_host[k];
+        if (s < 0 || s >= ag->members || d < 0 || d >= ag->members) {
+            rl_set_error("group_clone_members: pair %d (%d -> %d) names a member outside [0, %d)", k, s, d, ag->members); return RLREP_ERR_ARG;
+        }
+        if (s == d) { rl_set_error("group_clone_members: pair %d copies member %d onto itself", k, s); return RLREP_ERR_ARG; }
+        if (role[d] == 2) { rl_set_error("group_clone_members: member %d is a destination twice", d); return RLREP_ERR_ARG; }
+        if (role[d] == 1 || role[s] == 2) {
+            rl_set_error("group_clone_members: member %d is both a source and a destination", role[d] == 1 ? d : s); return RLREP_ERR_ARG;
+        }
+        role[s] = 1; role[d] = 2;
+        pairs.src[k] = s; pairs.dst[k] = d;
+    }
+    if (in_train_refused("group_clone_members", ag)) return RLREP_ERR_ARG;
+    // what a standalone agent's load(snapshot) restores: four arenas, the temperature state, the device records (static_state: the train()
+    // counter block, the optimizer records, the metric slots -- the head of the workspace, up to the end of the metric slots)
+    CloneTab tab; memset(&tab, 0, sizeof(tab));
+    tab.base = const_cast<char*>(ag->grp_lo); tab.stride = ag->grp_stride;
+    const long long pf = 4ll * ag->L.cur[RLREP_ARENA_PARAM], tf = 4ll * ag->L.cur[RLREP_ARENA_TARGET];
+    const char* ws0 = (const char*)ag->a.workspace_dev;
+    const struct { const void* p; long long bytes; } segs[] = {
+        {ag->a.param_dev, pf}, {ag->a.target_dev, tf}, {ag->a.exp_avg_dev, pf}, {ag->a.exp_avg_sq_dev, pf}, {ag->a.alpha_state_dev, 4 * 8},
+        {ws0, (long long)((const char*)(ag->metrics + M_COUNT) - ws0)}};
+    static_assert(sizeof(segs) / sizeof(segs[0]) <= RL_CLONE_MAX_SEGS, "CloneTab segments");
+    for (const auto& g : segs) {
+        if (g.bytes <= 0) continue;
+        const long long off = (const char*)g.p - ag->grp_lo;
+        if (off < 0 || (off & 3) || (g.bytes & 3) || off + g.bytes > ag->grp_stride) {
+            rl_set_error("group_clone_members: a segment [%lld, %lld) leaves the member block of %lld bytes", off, off + g.bytes, ag->grp_stride); return RLREP_ERR_ARG;
+        }
+        if (g.p == ws0) {
+            tab.rec_seg = tab.nseg;
+            tab.rec_w0 = (int)(((const char*)ag->adam_step - ws0) >> 2); tab.rec_nw = 4 * RLREP_GROUP_CFG_WORDS; tab.rec_words = RLREP_GROUP_CFG_WORDS;
+            if ((const char*)ag->steps != ws0 || (const char*)(ag->adam_step + 4) > (const char*)ag->metrics) {
+                rl_set_error("group_clone_members: the device records are not laid out as static_state lays them out"); return RLREP_ERR_ARG;
+            }
+        }
+        tab.seg[tab.nseg].off = off; tab.seg[tab.nseg].bytes = g.bytes; ++tab.nseg;
+    }
+    ++g_rl_launches;
+    const int rc = rl_launch_group_clone(&tab, &pairs, n, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_clone_members: launch failed (%d)", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_group_set_live(rlrep_agent* ag, const int32_t* live_host, void* stream) {
+    GROUP_ONLY("group_set_live")
+    if (!live_host) { rl_set_error("group_set_live: null mask"); return RLREP_ERR_ARG; }
+    LiveTab tab; memset(&tab, 0, sizeof(tab));
+    for (int m = 0; m < ag->members; ++m) {
+        if (live_host[m] != 0 && live_host[m] != 1) { rl_set_error("group_set_live: mask[%d] = %d is neither 0 nor 1", m, live_host[m]); return RLREP_ERR_ARG; }
+        if (live_host[m]) tab.slot_member[tab.n_live++] = m;
+    }
+    if (tab.n_live < 1) { rl_set_error("group_set_live: no live member (at least one member of a group stays live)"); return RLREP_ERR_ARG; }
+    if (in_train_refused("group_set_live", ag)) return RLREP_ERR_ARG;
+    // the slots behind n_live name no member (0): a launch never reads them
+    ++g_rl_launches;
+    const int rc = rl_launch_group_live(ag->grp_live, &tab, ag->members, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_set_live: launch failed (%d)", rc); return RLREP_ERR_HIP; }
+    ag->grp_live_mask.assign(live_host, live_host + ag->members);
+    ag->grp_grid_y = ag->grp_compact ? tab.n_live : ag->members;
+    return 0;
+}
+int32_t rlrep_group_get_live(rlrep_agent* ag, int32_t* live_out) {
+    GROUP_ONLY("group_get_live")
+    if (!live_out) { rl_set_error("group_get_live: null output"); return RLREP_ERR_ARG; }
+    for (int m = 0; m < ag->members; ++m) live_out[m] = ag->grp_live_mask[m];
+    return 0;
+}
+int32_t rlrep_group_train_prologue(rlrep_agent* ag, const float* ring_dev, int64_t ring_stride_bytes, const int32_t* size_dev, int32_t* idx_pool_dev, int64_t n_idx,
+                                   float* eps_pool_dev, int64_t n_eps, uint64_t idx_offset, uint64_t eps_offset, int32_t batch, void* stream) {
+    GROUP_ONLY("group_train_prologue")
+    if (ring_stride_bytes < 0 || (ring_stride_bytes & 3) || (ag->members > 1 && ring_stride_bytes < 4ll * batch)) {
+        rl_set_error("group_train_prologue: bad ring stride %lld", (long long)ring_stride_bytes); return RLREP_ERR_ARG;
+    }
+    if (!in_member0(ag, idx_pool_dev, 4 * n_idx) || !in_member0(ag, eps_pool_dev, 4 * n_eps)) {
+        rl_set_error("group_train_prologue: the index / noise pools must lie inside member 0's block (they are written at every member's stride)");
+        return RLREP_ERR_ARG;
+    }
+    ag->grp_ring_stride = ring_stride_bytes;          // (also what a later optimizer launch's ring gather moves by)
+    GrpScope grp_scope_(ag);
+    return rlrep_train_prologue(ag, ring_dev, size_dev, idx_pool_dev, n_idx, eps_pool_dev, n_eps, 0, idx_offset, eps_offset, batch, stream);
+}
+int32_t rlrep_group_prepare(rlrep_agent* ag, int32_t batch) {
+    GROUP_ONLY("group_prepare")
+    return ensure_batch(ag, batch);
+}
+// the actor part of a SelectAct (member 0's weights, the dimensions, the action range); everything else zero
+static void group_actor(rlrep_agent* ag, SelectAct& p, float lo, float hi) {
+    memset(&p, 0, sizeof(p));
+    p.W1 = ag->P("actor.trunk.0.weight"); p.b1 = ag->P("actor.trunk.0.bias"); p.W2 = ag->P("actor.trunk.2.weight"); p.b2 = ag->P("actor.trunk.2.bias");
+    p.W3 = ag->P("actor.trunk.4.weight"); p.b3 = ag->P("actor.trunk.4.bias");
+    p.S = ag->d.state_dim; p.Ha = ag->d.actor_hidden_dim; p.A = ag->d.action_dim; p.lo = lo; p.hi = hi;
+}
+int32_t rlrep_group_select_action(rlrep_agent* ag, const float* obs_host, int32_t explore, uint64_t offset, float lo, float hi, float* action_host, void* stream) {
+    if (!ag || ag->members <= 0 || !obs_host || !action_host) { rl_set_error("group_select_action: bad argument (needs a seed group)"); return RLREP_ERR_ARG; }
+    SelectAct p; group_actor(ag, p, lo, hi);
+    void* d = nullptr;
+    if (hipHostGetDevicePointer(&d, const_cast<float*>(obs_host), 0) != hipSuccess || !d) { rl_set_error("group_select_action: the observations are not mapped (pinned) host memory"); return RLREP_ERR_ARG; }
+    p.obs = (const float*)d;
+    if (hipHostGetDevicePointer(&d, action_host, 0) != hipSuccess || !d) { rl_set_error("group_select_action: the action buffer is not mapped (pinned) host memory"); return RLREP_ERR_ARG; }
+    p.act = (float*)d;
+    p.explore = explore ? 1 : 0; p.seed = 0; p.offset = offset;
+    GrpScope grp_scope_(ag);
+    ++g_rl_launches;
+    const int rc = rl_launch_select_action(&p, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_select_action: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_group_replay_add_sized(float* ring_dev, int64_t ring_stride_floats, int32_t members, int64_t capacity, int32_t row_floats, int64_t ptr,
+                                     const float* rows_host, int64_t rows_stride_floats, int64_t nrows, int32_t* size_dev, int32_t new_size, void* stream) {
+    if (!ring_dev || !rows_host || members < 1 || members > RLREP_GROUP_MAX_MEMBERS || capacity <= 0 || row_floats <= 0 || ring_stride_floats < capacity * row_floats ||
+        rows_stride_floats < nrows * row_floats ||
+        ptr < 0 || ptr >= capacity || nrows < 0 || nrows > capacity || new_size < 0 || new_size > capacity) {
+        rl_set_error("group_replay_add_sized: bad argument"); return RLREP_ERR_ARG;
+    }
+    void* d = nullptr;
+    if (hipHostGetDevicePointer(&d, const_cast<float*>(rows_host), 0) != hipSuccess || !d) { rl_set_error("group_replay_add_sized: the staging rows are not mapped (pinned) host memory"); return RLREP_ERR_ARG; }
+    ++g_rl_launches;
+    const int rc = rl_launch_replay_add_grp(ring_dev, ring_stride_floats, members, capacity, row_floats, ptr, (const float*)d, rows_stride_floats, nrows, size_dev, new_size, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_replay_add_sized: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+// ---- device environments of a seed group (group_env.hip) --------------------------------------------------------------------------------------
+struct rlrep_group_env {
+    rlrep_agent* ag; int kind, members;
+    EnvRecord* recs; EnvCtl* ctl;                     // [members] records and the group's counters: allocations of their own
+    double* starts;                                   // [members, RL_ENV_MAX_EPISODES, 2] start states of the last evaluation
+    int last_episodes;
+};
+// what every entry point that launches checks first: `what` names the caller in the message
+static int group_env_check(const char* what, rlrep_agent* ag, rlrep_group_env* env) {
+    if (!ag || !env) { rl_set_error("%s: null agent or environment", what); return RLREP_ERR_ARG; }
+    if (ag->members <= 0) { rl_set_error("%s: not a seed group (device environments are built for rlrep_group_create agents)", what); return RLREP_ERR_ARG; }
+    if (env->ag != ag || env->members != ag->members) { rl_set_error("%s: the environment was created for another group", what); return RLREP_ERR_ARG; }
+    if (in_train_refused(what, ag)) return RLREP_ERR_ARG;
+    return 0;
+}
+int32_t rlrep_group_env_create(rlrep_agent* ag, int32_t kind, rlrep_group_env** out) {
+    if (kind != RLREP_ENV_PENDULUM) { rl_set_error("group_env_create: kind %d is not built (0 = Pendulum-v1)", kind); return RLREP_ERR_ARG; }
+    if (!ag || !out) { rl_set_error("group_env_create: null argument"); return RLREP_ERR_ARG; }
+    if (ag->members <= 0) { rl_set_error("group_env_create: not a seed group (device environments are built for rlrep_group_create agents)"); return RLREP_ERR_ARG; }
+    if (ag->d.state_dim != 3 || ag->d.action_dim != 1) {
+        rl_set_error("group_env_create: Pendulum-v1 has 3 observations and 1 action (the group has %d and %d)", ag->d.state_dim, ag->d.action_dim); return RLREP_ERR_ARG;
+    }
+    rlrep_group_env* env = new rlrep_group_env();
+    env->ag = ag; env->kind = kind; env->members = ag->members; env->last_episodes = 0;
+    hipError_t e = hipMalloc((void**)&env->recs, sizeof(EnvRecord) * env->members);
+    if (e == hipSuccess) e = hipMalloc((void**)&env->ctl, sizeof(EnvCtl));
+    if (e == hipSuccess) e = hipMalloc((void**)&env->starts, sizeof(double) * 2 * RL_ENV_MAX_EPISODES * env->members);
+    if (e == hipSuccess) e = hipMemset(env->recs, 0, sizeof(EnvRecord) * env->members);
+    if (e == hipSuccess) e = hipMemset(env->ctl, 0, sizeof(EnvCtl));
+    if (e == hipSuccess) e = hipMemset(env->starts, 0, sizeof(double) * 2 * RL_ENV_MAX_EPISODES * env->members);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { rl_set_error("group_env_create: %s", hipGetErrorString(e)); rlrep_group_env_destroy(env); return RLREP_ERR_HIP; }
+    *out = env;
+    return 0;
+}
+void rlrep_group_env_destroy(rlrep_group_env* env) {
+    if (!env) return;
+    if (env->recs) (void)hipFree(env->recs);
+    if (env->ctl) (void)hipFree(env->ctl);
+    if (env->starts) (void)hipFree(env->starts);
+    delete env;
+}
+int32_t rlrep_group_env_reset(rlrep_group_env* env, void* stream) {
+    if (const int rc = group_env_check("group_env_reset", env ? env->ag : nullptr, env)) return rc;
+    ++g_rl_launches;
+    const int rc = rl_launch_group_env_reset(env->recs, env->ctl, env->ag->grp_seeds, env->members, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_env_reset: launch failed (%d)", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_group_env_step(rlrep_agent* ag, rlrep_group_env* env, float* ring_dev, int64_t ring_stride_floats, int64_t capacity, int32_t* size_dev,
+                             float lo, float hi, float eps_greedy, int64_t start_timesteps, void* stream) {
+    if (const int rc = group_env_check("group_env_step", ag, env)) return rc;
+    if (!ring_dev || !size_dev) { rl_set_error("group_env_step: null ring or size pointer"); return RLREP_ERR_ARG; }
+    const int row = 2 * ag->d.state_dim + ag->d.action_dim + 2;
+    if (capacity < 1 || ring_stride_floats < capacity * row) {
+        rl_set_error("group_env_step: capacity %lld / ring stride %lld floats do not hold %lld rows of %d floats", (long long)capacity, (long long)ring_stride_floats, (long long)capacity, row);
+        return RLREP_ERR_ARG;
+    }
+    if (!(lo <= hi) || !(eps_greedy >= 0.f && eps_greedy <= 1.f)) { rl_set_error("group_env_step: bad action range [%g, %g] or eps_greedy %g", (double)lo, (double)hi, (double)eps_greedy); return RLREP_ERR_ARG; }
+    SelectAct p; group_actor(ag, p, lo, hi);
+    ++g_rl_launches;
+    const int rc = rl_launch_group_env_step(&p, ag->grp_stride, ag->grp_seeds, ag->grp_live, ag->grp_grid_y, env->recs, env->ctl, ring_dev, ring_stride_floats, capacity,
+                                            size_dev, eps_greedy, start_timesteps, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_env_step: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_group_env_evaluate(rlrep_agent* ag, rlrep_group_env* env, int32_t episodes, uint64_t eval_index, double* out_dev, void* stream) {
+    if (const int rc = group_env_check("group_env_evaluate", ag, env)) return rc;
+    if (episodes < 1 || episodes > RL_ENV_MAX_EPISODES) { rl_set_error("group_env_evaluate: episodes %d outside [1, %d]", episodes, RL_ENV_MAX_EPISODES); return RLREP_ERR_ARG; }
+    if (!out_dev) { rl_set_error("group_env_evaluate: null output"); return RLREP_ERR_ARG; }
+    SelectAct p; group_actor(ag, p, -2.f, 2.f);          // Pendulum-v1's own action range (its max_torque)
+    ++g_rl_launches;
+    const int rc = rl_launch_group_env_eval(&p, ag->grp_stride, ag->grp_seeds, ag->grp_live, ag->grp_grid_y, eval_index * (uint64_t)episodes, episodes, out_dev,
+                                            env->starts, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_env_evaluate: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    env->last_episodes = episodes;
+    return 0;
+}
+int32_t rlrep_group_env_state(rlrep_group_env* env, int32_t what, void* host, int64_t bytes, int32_t write, void* stream) {
+    if (!env || !host) { rl_set_error("group_env_state: null argument"); return RLREP_ERR_ARG; }
+    void* dev = nullptr; int64_t have = 0;
+    if (what == RLREP_ENV_STATE_RECORDS) { dev = env->recs; have = (int64_t)sizeof(EnvRecord) * env->members; }
+    else if (what == RLREP_ENV_STATE_COUNTERS) { dev = env->ctl; have = 16; }
+    else if (what == RLREP_ENV_STATE_EVAL_STARTS && !write) { dev = env->starts; have = (int64_t)sizeof(double) * 2 * env->last_episodes * env->members; }
+    else { rl_set_error("group_env_state: what = %d (write %d) is not a block of the environment", what, write); return RLREP_ERR_ARG; }
+    if (bytes != have) { rl_set_error("group_env_state: block %d holds %lld bytes, the buffer %lld", what, (long long)have, (long long)bytes); return RLREP_ERR_ARG; }
+    if (in_train_refused("group_env_state", env->ag)) return RLREP_ERR_ARG;
+    hipError_t e = hipSuccess;
+    if (bytes > 0) e = write ? hipMemcpyAsync(dev, host, (size_t)bytes, hipMemcpyHostToDevice, (hipStream_t)stream)
+                             : hipMemcpyAsync(host, dev, (size_t)bytes, hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) { rl_set_error("group_env_state: %s", hipGetErrorString(e)); return RLREP_ERR_HIP; }
+    return 0;
+}
+
+}  // extern "C"

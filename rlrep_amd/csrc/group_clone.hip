@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "group.h"
+#include "launchers.h"
 
 __global__ __launch_bounds__(256) void group_clone_kernel(CloneTab tab, ClonePairs pairs) {
     const int pair = blockIdx.y;

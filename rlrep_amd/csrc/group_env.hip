@@ -17,6 +17,7 @@
 #include "group.h"
 #include "philox.h"
 #include "group_env.h"
+#include "launchers.h"
 
 #define RL_PI 3.141592653589793
 

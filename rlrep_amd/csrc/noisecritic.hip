@@ -21,10 +21,10 @@
 // next step's operands into registers before issuing the current step's MFMAs.
 #include <type_traits>
 #include "common.h"
-extern long long g_rl_launches;
 #include "kparams.h"
 #include "x3.h"
 #include "group.h"
+#include "launchers.h"
 
 #define NC_NF 5          // N / 4 accumulator fragments per batch-row group (N = 20)
 

@@ -4,6 +4,7 @@
 #include "common.h"
 #include "kparams.h"
 #include "group.h"
+#include "launchers.h"
 
 // ------------------------------------------------------------------------------------------------
 // ctrlsac InfoNCE (agent/ctrlsac/ctrlsac_agent.py:226-233)

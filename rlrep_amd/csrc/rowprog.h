@@ -77,6 +77,3 @@ struct RpLaunch {
     const int* epoch;                      // device counter that differs between any two launches whose granules / flags could be confused
     unsigned* err;                         // error word (rlrep_chain_status bit 2): a wait of this launch timed out
 };
-
-extern "C" int rl_launch_rowprog(const RpLaunch* L, int total_blocks, hipStream_t st);
-extern "C" int rl_rowprog_init();

@@ -13,6 +13,7 @@
 #include "kparams.h"
 #include "rowprog.h"
 #include "group.h"
+#include "launchers.h"
 
 #define RP_MAX_OPS 40
 #define RP_OP_WORDS ((int)(sizeof(RpOp) / 4))

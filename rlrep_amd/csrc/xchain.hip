@@ -24,6 +24,7 @@
 #include "gemm16_tile.h"
 #include "heads_vae_tile.h"
 #include "group.h"
+#include "launchers.h"
 
 #define XC_SPIN_LIMIT (1 << 18)
 
