@@ -433,6 +433,29 @@ int32_t rlrep_gemm(int32_t engine, int32_t la, int32_t lb, const float* a_dev, i
                    const float* bias_dev, const float* aux_dev, int32_t ldaux, float* out2_dev, int32_t bt, int32_t splits,
                    float* workspace_dev, int64_t workspace_floats, void* stream);
 
+/* Unit-test hook of the 16-row tile engine alone (tests/test_gemm16_engine.py): a TABLE of 1..8 independent products in ONE launch, through
+ * the launchers and the tile numbering the step programs use -- which rlrep_gemm (one task, 16-column tiles) cannot reach: 32- / 64-column
+ * tiles (nf = 2 / 4), multi-task directories, the front ends that load operands from preloaded scalars (one or two tasks with inner % 256 == 0
+ * or inner <= 64; three or four tasks of one shape), the weight-gradient launch's dealing of tiles to the XCDs, and the duo form.
+ * Fields as rlrep_gemm's arguments; out2 of a forward task has c's row stride; r1u[rows] / r1v[cols]: dX adds r1u[r] * r1v[c] to the product
+ * before the activation derivative (both or neither); scale multiplies the product (1.0: none).
+ *   duo_split == 0: every task has layouts la / lb and tiles of 16 * nf columns;
+ *   duo_split  > 0: tasks [0, duo_split) are row-major x k-major products (dX form, 16-column tiles), the rest k-major x k-major ones
+ *                   (weight-gradient form, 16 * nf2 columns, nf2 = 1 or 4) -- one launch of both forms; la / lb are ignored.
+ * Which front end the launch got: the difference of rlrep_front_end_counts around the call.  RLREP_ERR_ARG (before any GPU call) for ntasks
+ * outside 1..8, nf not in {1, 2, 4}, a null a / b / c, non-positive extents or an epilogue outside {0, 1, 3}.  The fused-loss, policy,
+ * reparameterisation, fused-short-product and optimizer epilogues are reachable only through an agent. */
+typedef struct rlrep_gemm16_task {
+    const float* a; const float* b; float* c;
+    int32_t lda, ldb, ldc, rows, cols, inner;
+    int32_t epi, act, flags;              /* as rlrep_gemm: epi 0 / 1 / 3, act 0..4, flags bit 0 accumulate, bit 1 bias gradient */
+    const float* bias; const float* aux; int32_t ldaux; float* out2;
+    const float* r1u; const float* r1v;   /* dX: optional rank-1 term, may be NULL */
+    float scale;                          /* multiplies the product; 1.0 default */
+} rlrep_gemm16_task;
+int32_t rlrep_gemm16_table(int32_t la, int32_t lb, int32_t nf, const rlrep_gemm16_task* tasks, int32_t ntasks,
+                           int32_t duo_split, int32_t nf2, int32_t low_prio, void* stream);
+
 /* Host-only (no GPU call): the GEMM engine the program builder picks for a product of these dimensions and layouts --
  * *engine 0 = 16-row tile engine, 1 = LDS-tiled fp32-MFMA, 2 = LDS-tiled bf16x3 -- with its tile edge (64 / 128; 256 = the persistent
  * 256 x 128 tile of engine 2), split-K plan and which sides fall back to 4-byte accesses (bit 0: A, bit 1: B, bit 2: C). */

@@ -57,6 +57,15 @@ class Batch(C.Structure):
                 ('next_state_dev', C.c_void_p), ('done_dev', C.c_void_p), ('batch', C.c_int32)]
 
 
+class Gemm16Task(C.Structure):
+    """rlrep_gemm16_task (include/rlrep.h): one product of a rlrep_gemm16_table launch."""
+    _fields_ = [('a', C.c_void_p), ('b', C.c_void_p), ('c', C.c_void_p),
+                ('lda', C.c_int32), ('ldb', C.c_int32), ('ldc', C.c_int32), ('rows', C.c_int32), ('cols', C.c_int32), ('inner', C.c_int32),
+                ('epi', C.c_int32), ('act', C.c_int32), ('flags', C.c_int32),
+                ('bias', C.c_void_p), ('aux', C.c_void_p), ('ldaux', C.c_int32), ('out2', C.c_void_p),
+                ('r1u', C.c_void_p), ('r1v', C.c_void_p), ('scale', C.c_float)]
+
+
 def declared_symbols():
     """Every function name include/rlrep.h declares (used by the CPU test that checks the exports)."""
     src = open(HEADER_PATH).read()
@@ -164,6 +173,7 @@ def _load():
         'rlrep_run_stage': (i32, [vp, i32, i32, vp]),
         'rlrep_stage_info': (i32, [vp, i32, i32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         'rlrep_gemm': (i32, [i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, vp, i64, vp]),
+        'rlrep_gemm16_table': (i32, [i32, i32, i32, P(Gemm16Task), i32, i32, i32, i32, vp]),
         'rlrep_gemm_plan': (i32, [i32] * 8 + [P(i32)] * 5),
         'rlrep_nc_fwd_plan': (i32, [i32] * 4 + [P(i32)] * 3),
         'rlrep_chain_status': (i32, [vp, P(C.c_uint32), vp]),

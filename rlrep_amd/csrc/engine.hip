@@ -974,7 +974,7 @@ int32_t rlrep_gemm(int32_t engine, int32_t la, int32_t lb, const float* A, int32
     GemmBatch gb; memset(&gb, 0, sizeof(gb)); gb.ntasks = 1;
     int rc;
     if (engine == 0) {
-        t.tiles_c = (Cn + 15) / 16; t.ntiles = ((R + 15) / 16) * t.tiles_c; t.tile_base = 0;
+        rl_gemm16_number_tiles(&t, 1, 1);
         gb.t[0] = t;
         rc = rl_launch_gemm16(la, lb, 1, &gb, t.ntiles, (hipStream_t)stream);
     } else {
@@ -1021,6 +1021,45 @@ int32_t rlrep_gemm(int32_t engine, int32_t la, int32_t lb, const float* A, int32
         rc = rl_launch_gemm_lds(wide ? 257 : engine == 2 ? (pbt == 64 ? 65 : 129) : pbt, la, lb, &gb, t.ntiles, fin, (hipStream_t)stream);
     }
     if (rc != 0) { rl_set_error("gemm: launch failed (%d)", rc); return rc < 0 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    return 0;
+}
+
+// Unit-test hook of the 16-row tile engine: a whole task TABLE through the launchers the step programs use, numbered by the builder's own helpers
+// (engine_internal.h rl_gemm16_number_tiles*), so that tile widths, multi-task directories, the fast front ends and the duo form can be reached
+// without an agent (tests/test_gemm16_engine.py).
+int32_t rlrep_gemm16_table(int32_t la, int32_t lb, int32_t nf, const rlrep_gemm16_task* tasks, int32_t ntasks, int32_t duo_split, int32_t nf2,
+                           int32_t low_prio, void* stream) {
+    rl_switches_read();
+    if (!tasks || ntasks < 1 || ntasks > GEMM_MAX_TASKS) { rl_set_error("gemm16_table: ntasks %d outside 1..%d", ntasks, GEMM_MAX_TASKS); return RLREP_ERR_ARG; }
+    if (nf != 1 && nf != 2 && nf != 4) { rl_set_error("gemm16_table: nf %d not in {1, 2, 4}", nf); return RLREP_ERR_ARG; }
+    if (duo_split < 0 || (duo_split > 0 && (duo_split >= ntasks || (nf2 != 1 && nf2 != 4)))) { rl_set_error("gemm16_table: bad duo split %d / nf2 %d", duo_split, nf2); return RLREP_ERR_ARG; }
+    GemmBatch gb; memset(&gb, 0, sizeof(gb));
+    gb.ntasks = ntasks; gb.low_prio = low_prio ? 1 : 0;
+    for (int q = 0; q < ntasks; ++q) {
+        const rlrep_gemm16_task& s = tasks[q];
+        if (!s.a || !s.b || !s.c) { rl_set_error("gemm16_table: task %d has a null operand or output", q); return RLREP_ERR_ARG; }
+        if (s.rows <= 0 || s.cols <= 0 || s.inner <= 0 || s.lda <= 0 || s.ldb <= 0 || s.ldc <= 0) { rl_set_error("gemm16_table: task %d has a non-positive extent", q); return RLREP_ERR_ARG; }
+        if (s.epi != EPI_FWD && s.epi != EPI_DX && s.epi != EPI_DW) { rl_set_error("gemm16_table: task %d: epilogue %d not in {0, 1, 3}", q, s.epi); return RLREP_ERR_ARG; }
+        if (s.act < ACT_NONE || s.act > ACT_TANH) { rl_set_error("gemm16_table: task %d: activation %d outside 0..4", q, s.act); return RLREP_ERR_ARG; }
+        if ((s.r1u != nullptr) != (s.r1v != nullptr)) { rl_set_error("gemm16_table: task %d: the rank-1 term needs both vectors", q); return RLREP_ERR_ARG; }
+        if (s.epi == EPI_FWD && s.act == ACT_SIN && !s.out2) { rl_set_error("gemm16_table: task %d: the sin epilogue stores its pre-activation to out2", q); return RLREP_ERR_ARG; }
+        if (s.epi == EPI_DX && s.act != ACT_NONE && !s.aux) { rl_set_error("gemm16_table: task %d: dX with an activation needs aux", q); return RLREP_ERR_ARG; }
+        GemmTask& t = gb.t[q];
+        t.scale = s.scale; t.A = s.a; t.lda = s.lda; t.B = s.b; t.ldb = s.ldb; t.C = s.c; t.ldc = s.ldc; t.R = s.rows; t.Cn = s.cols; t.K = s.inner;
+        t.epi = s.epi; t.act = s.act; t.flags = s.flags & FLAG_ACCUM;
+        if (s.epi == EPI_FWD) { t.bias = s.bias; t.out2 = s.out2; t.ldout2 = s.ldc; }
+        if (s.epi == EPI_DX) { t.aux = s.aux; t.ldaux = s.ldaux; t.r1u = s.r1u; t.r1v = s.r1v; }
+        if (s.epi == EPI_DW && (s.flags & FLAG_BIASGRAD) && s.out2) { t.flags |= FLAG_BIASGRAD; t.out2 = s.out2; }
+    }
+    int rc;
+    if (duo_split > 0) {
+        const int total = rl_gemm16_number_tiles_duo(gb.t, duo_split, gb.t + duo_split, ntasks - duo_split, nf2);
+        rc = rl_launch_gemm16_duo(duo_split, nf2, &gb, total, (hipStream_t)stream);
+    } else {
+        const int total = rl_gemm16_number_tiles(gb.t, ntasks, nf);
+        rc = rl_launch_gemm16(la, lb, nf, &gb, total, (hipStream_t)stream);
+    }
+    if (rc != 0) { rl_set_error("gemm16_table: launch failed (%d)", rc); return rc < 0 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
     return 0;
 }
 

@@ -131,6 +131,24 @@ struct rlrep_agent {
 // ------------------------------------------------------------------------------------------------
 // builder helpers
 // ------------------------------------------------------------------------------------------------
+// Tile numbering of a launch of the 16-row tile engine: every task gets its column-tile count (16 * nf columns a tile), its tile count and
+// its first tile; returns the launch's total.  `first`: the first tile of tasks[0] (a duo launch numbers its second form behind its first).
+// The program builder and the unit-test hook (rlrep_gemm16_table) number through this one function.
+static inline int rl_gemm16_number_tiles(GemmTask* tasks, int ntasks, int nf, int first = 0) {
+    int base_tile = first;
+    for (int q = 0; q < ntasks; ++q) {
+        GemmTask& t = tasks[q];
+        t.tiles_c = (t.Cn + 16 * nf - 1) / (16 * nf);
+        const int tr = (t.R + 15) / 16;
+        t.ntiles = tr * t.tiles_c; t.tile_base = base_tile; base_tile += t.ntiles;
+    }
+    return base_tile;
+}
+// ... of a duo launch (gemm16_duo_kernel): n1 tasks of the dX form at NF = 1, then n2 of the weight-gradient form at NF = nf2
+static inline int rl_gemm16_number_tiles_duo(GemmTask* d1, int n1, GemmTask* d2, int n2, int nf2) {
+    return rl_gemm16_number_tiles(d2, n2, nf2, rl_gemm16_number_tiles(d1, n1, 1));
+}
+
 struct Builder {
     rlrep_agent* ag; Workspace& ws; bool dry;
     Builder(rlrep_agent* a) : ag(a), ws(a->ws), dry(a->ws.dry) {}
@@ -299,12 +317,7 @@ struct Builder {
             if (!force1) { if (count(2) >= 384) nf = 2; if (count(4) >= 384) nf = 4; }
             if (!tasks.empty() && (tasks[0].flags & FLAG_PRE)) nf = 1;
         }
-        int base_tile = 0;
-        for (auto& t : tasks) {
-            t.tiles_c = (t.Cn + 16 * nf - 1) / (16 * nf);
-            const int tr = (t.R + 15) / 16;
-            t.ntiles = tr * t.tiles_c; t.tile_base = base_tile; base_tile += t.ntiles;
-        }
+        const int base_tile = rl_gemm16_number_tiles(tasks.data(), (int)tasks.size(), nf);
         if (tasks.size() > GEMM_MAX_TASKS) { fprintf(stderr, "rlrep: too many tasks in stage %s\n", what); abort(); }
         GemmBatch gb; memset(&gb, 0, sizeof(gb));
         gb.ntasks = (int)tasks.size();
@@ -340,9 +353,7 @@ struct Builder {
         if (!ok) { gemm(p, LD_ROW, LD_COL, d1, w1); gemm(p, LD_COL, LD_COL, d2, w2); return; }
         auto count4 = [&]() { long long n = 0; for (auto& t : d2) n += (long long)((t.R + 15) / 16) * ((t.Cn + 63) / 64); return n; };
         const int nf2 = count4() >= 192 ? 4 : 1;
-        int base_tile = 0;
-        for (auto& t : d1) { t.tiles_c = (t.Cn + 15) / 16; t.ntiles = ((t.R + 15) / 16) * t.tiles_c; t.tile_base = base_tile; base_tile += t.ntiles; }
-        for (auto& t : d2) { t.tiles_c = (t.Cn + 16 * nf2 - 1) / (16 * nf2); t.ntiles = ((t.R + 15) / 16) * t.tiles_c; t.tile_base = base_tile; base_tile += t.ntiles; }
+        const int base_tile = rl_gemm16_number_tiles_duo(d1.data(), (int)d1.size(), d2.data(), (int)d2.size(), nf2);
         GemmBatch gb; memset(&gb, 0, sizeof(gb));
         gb.ntasks = (int)(d1.size() + d2.size()); gb.low_prio = low_prio ? 1 : 0;
         for (size_t q = 0; q < d1.size(); ++q) gb.t[q] = d1[q];

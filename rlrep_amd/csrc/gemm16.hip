@@ -320,7 +320,7 @@ __global__ __launch_bounds__(256) void gemm16_fastpre_kernel_grp(int hdr, const 
 long long g_rl_front[4] = {0, 0, 0, 0};
 static int s_front = 3;
 // diagnostic switches, read when an agent is created (rl_gemm16_read_env; no getenv on the per-launch path): RLREP_DISABLE=gemm16_fast = every launch on
-// the record front end, RLREP_DISABLE=gemm16_spec = no compiled-in epilogues (both: bit-identical results, tests/test_default_mode.py)
+// the record front end, RLREP_DISABLE=gemm16_spec = no compiled-in epilogues (both: bit-identical results, tests/test_default_mode.py and tests/test_gemm16_engine.py)
 static bool s_no_fast = false, s_generic = false, s_trace = false, s_dw_xcd = true;
 extern "C" void rl_gemm16_read_env() {
     s_no_fast = rl_off("gemm16_fast"); s_generic = rl_off("gemm16_spec"); s_trace = rl_opt("gemm16_trace") != nullptr;

@@ -515,6 +515,7 @@ __device__ __forceinline__ void gemm16_tile(const TaskT& t, const int tr, const 
     float e0[NF], cold[NF], cold2[NF], cold3[NF], cold4[NF];
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
+#pragma clang fp contract(off)      // (see the forward / dX epilogues below)
         const int c = c0 + 16 * f + (ol & 15);
         float m[5];
 #pragma unroll
@@ -605,7 +606,11 @@ __device__ __forceinline__ void gemm16_tile(const TaskT& t, const int tr, const 
         const float v = (((red[0][f][oreg][ol] + red[1][f][oreg][ol]) + red[2][f][oreg][ol]) + red[3][f][oreg][ol]) * scale;
         float* cp = pC + (size_t)r * ldc + c;
         switch (epi) {
+        // forward and dX: every operation rounds on its own.  Left to the compiler, an instantiation with the activation compiled in fuses the
+        // last multiply and add (cold + g * act') into one fma while the generic body, whose multiply sits in a switch arm, cannot: the same task
+        // then gives other bits depending on which instantiation its launch got (tests/test_gemm16_engine.py, dX with ELU accumulating).
         case EPI_FWD: {
+#pragma clang fp contract(off)
             const float x = v + e0[f];
             float y;
             switch (act) {
@@ -618,6 +623,7 @@ __device__ __forceinline__ void gemm16_tile(const TaskT& t, const int tr, const 
             *cp = y;
         } break;
         case EPI_DX: {
+#pragma clang fp contract(off)
             float g = v + cold2[f];
             switch (act) {
             case ACT_RELU: g = e0[f] > 0.f ? g : 0.f; break;

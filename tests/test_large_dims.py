@@ -201,3 +201,36 @@ def test_diffsrsac_regulariser_at_config_dimensions():
     [256 x 256] reduce over 1024 rows through the LDS-tiled weight-gradient engine (split-K slabs reserved whatever lambda is)."""
     _run('diffsrsac', ('rlrep_amd.agent.diffsrsac.diffsrsac_agent', 'DIFFSRSACAgent'), 17, 6, 1024,
          dict(hidden_dim=256, extra_feature_steps=0, critic_elu_layer_regularizer_lambda=0.5), trains=2)
+
+
+_HC256 = {
+    'sac': (('rlrep_amd.agent.sac.sac_agent', 'SACAgent'), dict(hidden_dim=256)),
+    'vlsac': (('rlrep_amd.agent.vlsac.vlsac_agent', 'VLSACAgent'), dict(hidden_dim=256, feature_dim=256, extra_feature_steps=1)),
+    'ctrlsac': (('rlrep_amd.agent.ctrlsac.ctrlsac_agent', 'CTRLSACAgent'), dict(hidden_dim=256, feature_dim=256, extra_feature_steps=1)),
+    # (the smallest feature nets that keep the critic and the actor 256 wide)
+    'spedersac': (('rlrep_amd.agent.spedersac.spedersac_agent', 'SPEDERSACAgent'),
+                  dict(phi_and_mu_lr=1e-5, phi_hidden_dim=64, phi_hidden_depth=1, mu_hidden_dim=64, mu_hidden_depth=0, critic_and_actor_lr=3e-4,
+                       critic_and_actor_hidden_dim=256, feature_dim=64, hidden_dim=256, extra_feature_steps=1)),
+    'diffsrsac': (('rlrep_amd.agent.diffsrsac.diffsrsac_agent', 'DIFFSRSACAgent'),
+                  dict(hidden_dim=256, feature_dim=32, phi_hidden_dim=32, nabla_mu_hidden_dim=32, extra_feature_steps=1)),
+}
+
+
+@pytest.mark.parametrize('alg,B', [('sac', 100), ('vlsac', 100), ('ctrlsac', 100), ('spedersac', 100), ('diffsrsac', 100), ('vlsac', 250), ('sac', 250)])
+def test_ragged_batch_at_256_wide_layers(alg, B, monkeypatch):
+    """The reference's default hidden width (256) with a batch that is no multiple of the 16-row tile: every 256-deep layer takes the 16-row
+    engine's fast front ends -- operand loads issued from preloaded scalars before the task record arrives, the row mask from R unpacked out of a
+    16-bit half word -- on a partial last row tile (B = 100: 4 of 16 rows; B = 250: 10 of 16), and the wide launches the 32- / 64-column tiles.
+    The golden cases run these kernels at B = 256 only, the ragged-batch tests at widths that never qualify for them.  HalfCheetah's S = 17,
+    A = 6, two train() calls, against the CPU oracle; the front-end counts around the run say that the kernels in question did run."""
+    from rlrep_amd import _lib
+    monkeypatch.delenv('RLREP_DISABLE', raising=False)
+    cls_path, kw = _HC256[alg]
+    f0 = _lib.front_end_counts()
+    _run(alg, cls_path, 17, 6, B, kw, trains=2, replay_n=1024)
+    f1 = _lib.front_end_counts()
+    fe = {k: f1[k] - f0[k] for k in f1}
+    print(f'{alg} B={B}: 16-row engine launches per front end {fe}')
+    assert fe['fast'] > 0, (alg, B, fe)
+    if alg == 'vlsac':
+        assert fe['fast4'] > 0 and fe['fastpre'] > 0, (alg, B, fe)
