@@ -589,13 +589,17 @@ int32_t rlrep_group_replay_add_sized(float* ring_dev, int64_t ring_stride_floats
  * R ring rows on the host every iteration, and every evaluation costs episodes x 200 further round trips per member.  A device environment
  * keeps one record per member on the device (an allocation of its own: the member stride, rlrep_group_clone_members' segments and the
  * checkpoint device records do not know it) and does all of that in ONE launch per iteration, capturable in front of the group's train()
- * graph, and one launch per evaluation.  kind 0 = Pendulum-v1 (the public specification as rlrep_amd/envs/pendulum.py restates it; fp64
- * dynamics in one lane, rounded to fp32 where the host environment rounds); any other kind is RLREP_ERR_ARG.
+ * graph, and one launch per evaluation.  kind 0 = Pendulum-v1 (S = 3), kind 2 = MountainCarContinuous-v0 (S = 2; the goal p >= 0.45 with
+ * v >= 0 ends an episode, 999-step time limit) -- the public specifications as rlrep_amd/envs/pendulum.py and envs/mountain_car.py restate
+ * them; fp64 dynamics in one lane, rounded to fp32 where the host environment rounds; any other kind is RLREP_ERR_ARG.  The kind lives in the
+ * handle: step, evaluate and reset dispatch on it.  Below, "200" and "9 floats" are Pendulum's time limit and row: a kind has its own
+ * (MountainCarContinuous-v0: 999 and 7).
  *
  * Record (256 bytes per member, csrc/group_env.h EnvRecord): double theta, theta_dot, episode_return; int64 ring_ptr, nsteps; int32 t,
  * ring_size, episodes_done, force; float force_action, act; float obs[4]; double returns[16] (finished episodes, entry episodes_done % 16
  * is written next); 48 bytes of padding.  Counters (16 bytes, group-wide): int64 t_global (steps since reset), uint64 calls (the
- * select_action call counter).
+ * select_action call counter).  MountainCarContinuous-v0: theta / theta_dot hold position and velocity (fp32-representable values: that
+ * environment rounds its state to fp32 at reset and after every step), obs[0..1] = (p, v).
  * Philox streams (counter word 3, where every other draw of the library has a value below 2^17): 0xE0000000 collection -- counter = the
  * member's nsteps, word 2 = 0 for a step's exploration draws (word 0: the epsilon-greedy test, word 1: the uniform action), word 2 = 1 for
  * an episode's start state; 0xE1000000 evaluation start states, counter = eval_index * episodes + episode.  Key = the member's seed
@@ -606,19 +610,23 @@ int32_t rlrep_group_replay_add_sized(float* ring_dev, int64_t ring_stride_floats
  * a uniform action in [lo, hi] instead while t_global < start_timesteps or with probability eps_greedy (or the record's force_action when
  * force is set: one shot); the dynamics; the row [s, a, s', r, done_bool = 0] at ring_ptr of ring_dev + member * ring_stride_floats
  * (rlrep_group_replay_add_sized's layout, row = 9 floats); ring_ptr and ring_size advance (wrap at `capacity`), size_dev[member] = ring_size;
- * on the 200th step the episode return is filed and a new episode starts.  The launch's last workgroup adds 1 to t_global and, past warm-up,
+ * on the 200th step the episode return is filed and a new episode starts.  MountainCarContinuous-v0: done_bool = 1 where the step reaches the
+ * goal before the 999th step of its episode (a goal ON the 999th step is the time limit's and stays 0, the host loop's rule); the episode
+ * ends at the goal or on the 999th step, and the new start is p = fp32(-0.6 + 0.2 u), v = 0 from words 0..1 of the start-state block.  The launch's last workgroup adds 1 to t_global and, past warm-up,
  * to calls.  rlrep_group_env_evaluate: workgroup (episode e, member) rolls out one 200-step episode with the mean action
  * (select_action(explore = 0), clamped to Pendulum's +-2) from its Philox start state and writes the fp64 sum of the fp32 rewards to
- * out_dev[member * episodes + e] (a retired member's entries are left unwritten); episodes in [1, 64].
+ * out_dev[member * episodes + e] (a retired member's entries are left unwritten); episodes in [1, 64].  MountainCarContinuous-v0: up to 999
+ * steps, the action clamped to +-1, and the workgroup leaves the loop (uniformly) once the goal is reached.
  * rlrep_group_env_reset: every record starts a fresh episode (start state at counter 0), cursors, counters and returns zeroed.
  * rlrep_group_env_state: copy block `what` (RLREP_ENV_STATE_*) to (write = 0) or from (write = 1) host memory, `bytes` = the block's exact
  * size (records: 256 * members; counters: 16; the start states of the last evaluation, read only: 16 * members * episodes, [member, episode,
  * (theta, theta_dot)]); stream-ordered on `stream`, then synchronised.
  * All launches are stream-ordered and capturable; nothing is allocated after create.  Rejected with RLREP_ERR_ARG and a message, before any
- * launch: a null pointer, an ordinary agent, state / action dims other than 3 / 1, an environment of another group, a call between
+ * launch: a null pointer, an ordinary agent, state / action dims other than the kind's (3 / 1, 2 / 1), an environment of another group, a call between
  * rlrep_group_train_prologue and the end of that train(), episodes outside [1, 64], a capacity below 1 or a ring stride that does not hold it. */
 typedef struct rlrep_group_env rlrep_group_env;
 #define RLREP_ENV_PENDULUM 0
+#define RLREP_ENV_MOUNTAIN_CAR_CONTINUOUS 2
 #define RLREP_ENV_STATE_RECORDS 0
 #define RLREP_ENV_STATE_COUNTERS 1
 #define RLREP_ENV_STATE_EVAL_STARTS 2

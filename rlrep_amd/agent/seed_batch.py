@@ -406,7 +406,7 @@ class SeedBatchMixin(object):
     def iterate(self, env, buffers, batch_size, train=True):
         """One environment step of every live member on the device -- act, explore, step the dynamics, write the ring row
         (rlrep_group_env_step) -- and, with `train`, one train() of every live member on the rings as they then stand: ONE graph replay, no host
-        round trip.  `env` is a DevicePendulumGroup of this group, `buffers` a ReplayBufferGroup whose cursor the device owns from here on
+        round trip.  `env` is a DeviceEnvGroup (envs/device.py) of this group, `buffers` a ReplayBufferGroup whose cursor the device owns from here on
         (ReplayBufferGroup.adopt_device_cursor gives it back).  Returns what train() returns, or None without `train`.  The step's exploring
         draw is the one `select_action(states, explore=True)` would make now: both count calls in the same counter."""
         name = type(self).__name__

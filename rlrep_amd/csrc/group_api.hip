@@ -274,6 +274,7 @@ int32_t rlrep_group_replay_add_sized(float* ring_dev, int64_t ring_stride_floats
     return 0;
 }
 // ---- device environments of a seed group (group_env.hip) --------------------------------------------------------------------------------------
+static_assert(EnvPendulum::KIND == RLREP_ENV_PENDULUM && EnvMountainCar::KIND == RLREP_ENV_MOUNTAIN_CAR_CONTINUOUS, "group_env.h kinds are include/rlrep.h RLREP_ENV_*");
 struct rlrep_group_env {
     rlrep_agent* ag; int kind, members;
     EnvRecord* recs; EnvCtl* ctl;                     // [members] records and the group's counters: allocations of their own
@@ -289,11 +290,12 @@ static int group_env_check(const char* what, rlrep_agent* ag, rlrep_group_env* e
     return 0;
 }
 int32_t rlrep_group_env_create(rlrep_agent* ag, int32_t kind, rlrep_group_env** out) {
-    if (kind != RLREP_ENV_PENDULUM) { rl_set_error("group_env_create: kind %d is not built (0 = Pendulum-v1)", kind); return RLREP_ERR_ARG; }
+    const EnvKindInfo* k = rl_env_kind(kind);
+    if (!k) { rl_set_error("group_env_create: kind %d is not built (0 = Pendulum-v1, 2 = MountainCarContinuous-v0)", kind); return RLREP_ERR_ARG; }
     if (!ag || !out) { rl_set_error("group_env_create: null argument"); return RLREP_ERR_ARG; }
     if (ag->members <= 0) { rl_set_error("group_env_create: not a seed group (device environments are built for rlrep_group_create agents)"); return RLREP_ERR_ARG; }
-    if (ag->d.state_dim != 3 || ag->d.action_dim != 1) {
-        rl_set_error("group_env_create: Pendulum-v1 has 3 observations and 1 action (the group has %d and %d)", ag->d.state_dim, ag->d.action_dim); return RLREP_ERR_ARG;
+    if (ag->d.state_dim != k->S || ag->d.action_dim != k->A) {
+        rl_set_error("group_env_create: %s has %d observations and %d action (the group has %d and %d)", k->name, k->S, k->A, ag->d.state_dim, ag->d.action_dim); return RLREP_ERR_ARG;
     }
     rlrep_group_env* env = new rlrep_group_env();
     env->ag = ag; env->kind = kind; env->members = ag->members; env->last_episodes = 0;
@@ -318,7 +320,7 @@ void rlrep_group_env_destroy(rlrep_group_env* env) {
 int32_t rlrep_group_env_reset(rlrep_group_env* env, void* stream) {
     if (const int rc = group_env_check("group_env_reset", env ? env->ag : nullptr, env)) return rc;
     ++g_rl_launches;
-    const int rc = rl_launch_group_env_reset(env->recs, env->ctl, env->ag->grp_seeds, env->members, (hipStream_t)stream);
+    const int rc = rl_launch_group_env_reset(env->kind, env->recs, env->ctl, env->ag->grp_seeds, env->members, (hipStream_t)stream);
     if (rc) { rl_set_error("group_env_reset: launch failed (%d)", rc); return RLREP_ERR_HIP; }
     return 0;
 }
@@ -334,7 +336,7 @@ int32_t rlrep_group_env_step(rlrep_agent* ag, rlrep_group_env* env, float* ring_
     if (!(lo <= hi) || !(eps_greedy >= 0.f && eps_greedy <= 1.f)) { rl_set_error("group_env_step: bad action range [%g, %g] or eps_greedy %g", (double)lo, (double)hi, (double)eps_greedy); return RLREP_ERR_ARG; }
     SelectAct p; group_actor(ag, p, lo, hi);
     ++g_rl_launches;
-    const int rc = rl_launch_group_env_step(&p, ag->grp_stride, ag->grp_seeds, ag->grp_live, ag->grp_grid_y, env->recs, env->ctl, ring_dev, ring_stride_floats, capacity,
+    const int rc = rl_launch_group_env_step(env->kind, &p, ag->grp_stride, ag->grp_seeds, ag->grp_live, ag->grp_grid_y, env->recs, env->ctl, ring_dev, ring_stride_floats, capacity,
                                             size_dev, eps_greedy, start_timesteps, (hipStream_t)stream);
     if (rc) { rl_set_error("group_env_step: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
     return 0;
@@ -343,9 +345,10 @@ int32_t rlrep_group_env_evaluate(rlrep_agent* ag, rlrep_group_env* env, int32_t 
     if (const int rc = group_env_check("group_env_evaluate", ag, env)) return rc;
     if (episodes < 1 || episodes > RL_ENV_MAX_EPISODES) { rl_set_error("group_env_evaluate: episodes %d outside [1, %d]", episodes, RL_ENV_MAX_EPISODES); return RLREP_ERR_ARG; }
     if (!out_dev) { rl_set_error("group_env_evaluate: null output"); return RLREP_ERR_ARG; }
-    SelectAct p; group_actor(ag, p, -2.f, 2.f);          // Pendulum-v1's own action range (its max_torque)
+    const EnvKindInfo* k = rl_env_kind(env->kind);
+    SelectAct p; group_actor(ag, p, k->lo, k->hi);       // the environment's own action range (Pendulum-v1: its max_torque)
     ++g_rl_launches;
-    const int rc = rl_launch_group_env_eval(&p, ag->grp_stride, ag->grp_seeds, ag->grp_live, ag->grp_grid_y, eval_index * (uint64_t)episodes, episodes, out_dev,
+    const int rc = rl_launch_group_env_eval(env->kind, &p, ag->grp_stride, ag->grp_seeds, ag->grp_live, ag->grp_grid_y, eval_index * (uint64_t)episodes, episodes, out_dev,
                                             env->starts, (hipStream_t)stream);
     if (rc) { rl_set_error("group_env_evaluate: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
     env->last_episodes = episodes;

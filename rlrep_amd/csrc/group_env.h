@@ -6,14 +6,14 @@
 
 #define RL_ENV_RETURNS 16                 // finished-episode returns a record keeps (a ring: entry episodes_done % 16 is written next)
 #define RL_ENV_MAX_EPISODES 64            // grid x of one evaluation launch at the most
-#define RL_ENV_EPISODE_STEPS 200          // Pendulum-v1's time limit
 // Philox stream ids (XORed into counter word 3, as PhiloxFill::stream_id is).  Every draw of train() and select_action uses stream 0 with
 // offsets below 2^49, so word 3 stays below 2^17 there: these two words are used by nothing else.
 #define RL_STREAM_ENV 0xE0000000u         // collection: word 2 = 0 the exploration draws of a step, 1 an episode's start state; counter = the member's nsteps
 #define RL_STREAM_EVAL 0xE1000000u        // evaluation start states: counter = eval_index * episodes + episode
 
 struct EnvRecord {                        // 256 bytes
-    double theta, theta_dot;              //   0: the state, fp64 as the host environment keeps it
+    double theta, theta_dot;              //   0: the state, fp64 as the host environment keeps it (MountainCarContinuous-v0: position p and velocity v,
+                                          //      fp32-representable values: that environment rounds its state where gym's float32 array does)
     double episode_return;                //  16: fp64 sum of the fp32 rewards of the running episode
     long long ring_ptr;                   //  24: the row of the member's replay ring the next step writes
     long long nsteps;                     //  32: steps since rlrep_group_env_reset (the counter of the member's RL_STREAM_ENV draws)
@@ -23,7 +23,8 @@ struct EnvRecord {                        // 256 bytes
     int force;                            //  52: 1 = the next step takes force_action instead of the policy's / the exploration draw (one shot)
     float force_action;                   //  56
     float act;                            //  60: the last action taken
-    float obs[4];                         //  64: the current observation (cos, sin, theta_dot), fp32 as the host environment returns it
+    float obs[4];                         //  64: the current observation, fp32 as the host environment returns it: obs[0..S-1] of the kind, (cos, sin,
+                                          //      theta_dot) resp. (p, v); the rest is 0
     double returns[RL_ENV_RETURNS];       //  80: returns of finished episodes
     double pad_[6];                       // 208
 };
@@ -36,3 +37,89 @@ struct EnvCtl {
     int ticket, pad_;
 };
 static_assert(sizeof(EnvCtl) == 24, "EnvCtl layout");
+
+// ---- the kinds (include/rlrep.h RLREP_ENV_*) -------------------------------------------------------------------------------------------------
+// Everything a kind is, in ONE place: a row of rl_env_kinds for the host entry points, and a traits struct for the kernels of group_env.hip,
+// which are templates over it -- S, the ring row 2S + A + 2, the time limit, whether a state can END the episode (a kind that cannot pays
+// nothing for the test: `if constexpr`), and three functions:
+//   start(c, x0, x1)             an episode's start state from the four words of one Philox block
+//   observe(x0, x1, obs)         obs[0..S-1], fp32 as the host environment returns it
+//   dynamics(x0, x1, a, goal)    one step in fp64, operation for operation the host file's, contraction off; returns the fp32 reward and sets
+//                                `goal` where the new state is terminal.  (x0, x1) leave as the host environment holds them afterwards.
+// A further kind is one more struct, one more row and one more case in the three launchers' switch.
+struct EnvKindInfo { int kind; const char* name; int S, A, row, limit; float lo, hi; };           // lo, hi: the environment's own action range
+static const EnvKindInfo rl_env_kinds[] = {
+    {0, "Pendulum-v1", 3, 1, 9, 200, -2.f, 2.f},
+    {2, "MountainCarContinuous-v0", 2, 1, 7, 999, -1.f, 1.f},
+};
+static inline const EnvKindInfo* rl_env_kind(int kind) {
+    for (const EnvKindInfo& k : rl_env_kinds) if (k.kind == kind) return &k;
+    return nullptr;
+}
+
+#ifdef __HIPCC__
+#define RL_PI 3.141592653589793
+__device__ __forceinline__ float env_u01f(uint32_t w) { return ((float)(w >> 8) + 0.5f) * (1.0f / 16777216.0f); }          // (0, 1), 24 bits
+__device__ __forceinline__ double env_u01d(uint32_t hi, uint32_t lo) {                                                   // (0, 1), 53 bits
+    return ((double)((((unsigned long long)hi << 32) | lo) >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+}
+
+// Pendulum-v1 (rlrep_amd/envs/pendulum.py): g = 10, m = l = 1, dt = 0.05, torque clipped to +-2, speed to +-8, reward from the wrapped angle,
+// 200-step time limit and no other end, reset theta ~ U(-pi, pi), theta_dot ~ U(-1, 1).  The state stays fp64.
+struct EnvPendulum {
+    static constexpr int KIND = 0, S = 3, A = 1, ROW = 9, LIMIT = 200;
+    static constexpr bool TERMINATES = false;
+    static __device__ __forceinline__ void start(const uint32_t* c, double& th, double& thd) {
+        th = -RL_PI + 2.0 * RL_PI * env_u01d(c[0], c[1]);
+        thd = -1.0 + 2.0 * env_u01d(c[2], c[3]);
+    }
+    static __device__ __forceinline__ void observe(double th, double thd, float* obs) {
+        obs[0] = (float)cos(th); obs[1] = (float)sin(th); obs[2] = (float)thd;
+    }
+    // PendulumEnv.step (envs/pendulum.py:46-56), operation for operation
+    static __device__ __forceinline__ float dynamics(double& th, double& thd, float action, bool& goal) {
+#pragma clang fp contract(off)
+        const double u = fmin(fmax((double)action, -2.0), 2.0);
+        double wrapped = fmod(th + RL_PI, 2.0 * RL_PI);                 // Python's float %: the sign of the divisor
+        if (wrapped < 0.0) wrapped += 2.0 * RL_PI;
+        wrapped -= RL_PI;
+        const double cost = (wrapped * wrapped + 0.1 * (thd * thd)) + 0.001 * (u * u);
+        double v = thd + (15.0 * sin(th) + 3.0 * u) * 0.05;
+        v = fmin(fmax(v, -8.0), 8.0);
+        th = th + v * 0.05;
+        thd = v;
+        goal = false;
+        return (float)(-cost);
+    }
+};
+
+// MountainCarContinuous-v0 (rlrep_amd/envs/mountain_car.py): power 0.0015, speed clipped to +-0.07, position to [-1.2, 0.6], an inelastic left
+// wall, the goal p >= 0.45 with v >= 0 ends the episode with +100, reward -0.1 a^2 of the RAW action, 999-step time limit, reset
+// p ~ U(-0.6, -0.4), v = 0.  (p, v) are rounded to fp32 at reset and at the end of every step, as gym's float32 state array does; the goal is
+// decided on the fp64 values before that rounding.
+struct EnvMountainCar {
+    static constexpr int KIND = 2, S = 2, A = 1, ROW = 7, LIMIT = 999;
+    static constexpr bool TERMINATES = true;
+    static __device__ __forceinline__ void start(const uint32_t* c, double& p, double& v) {
+#pragma clang fp contract(off)
+        p = (double)(float)(-0.6 + 0.2 * env_u01d(c[0], c[1]));
+        v = 0.0;
+    }
+    static __device__ __forceinline__ void observe(double p, double v, float* obs) { obs[0] = (float)p; obs[1] = (float)v; }
+    // MountainCarContinuousEnv.step, operation for operation
+    static __device__ __forceinline__ float dynamics(double& p_, double& v_, float action, bool& goal) {
+#pragma clang fp contract(off)
+        const double a = (double)action;
+        const double force = fmin(fmax(a, -1.0), 1.0);
+        double v = v_ + (force * 0.0015 - 0.0025 * cos(3.0 * p_));
+        v = fmin(fmax(v, -0.07), 0.07);
+        double p = p_ + v;
+        p = fmin(fmax(p, -1.2), 0.6);
+        if (p == -1.2 && v < 0.0) v = 0.0;
+        goal = p >= 0.45 && v >= 0.0;
+        const double r = (goal ? 100.0 : 0.0) - 0.1 * (a * a);
+        p_ = (double)(float)p; v_ = (double)(float)v;
+        return (float)r;
+    }
+};
+#endif

@@ -1,11 +1,12 @@
-// Pendulum-v1 environments of a seed group ON THE DEVICE (include/rlrep.h rlrep_group_env_*): acting, exploring, stepping the dynamics and
-// writing the replay-ring row of every live member are ONE launch (group_env_step_kernel), captured in front of the group's train() graph, and
-// one evaluation of every live member is ONE launch (group_env_eval_kernel) instead of members x episodes x 200 host round trips.
+// Environments of a seed group ON THE DEVICE (include/rlrep.h rlrep_group_env_*): acting, exploring, stepping the dynamics and writing the
+// replay-ring row of every live member are ONE launch (group_env_step_kernel), captured in front of the group's train() graph, and one
+// evaluation of every live member is ONE launch (group_env_eval_kernel) instead of members x episodes x (up to the time limit) host round trips.
 //
-// The dynamics are the public Pendulum-v1 specification as rlrep_amd/envs/pendulum.py restates it (g = 10, m = l = 1, dt = 0.05, torque
-// clipped to +-2, speed to +-8, reward from the wrapped angle, 200-step time limit, reset theta ~ U(-pi, pi), theta_dot ~ U(-1, 1)), computed
-// in fp64 by ONE lane in the operation order of that file, with contraction off (NumPy does not fuse): the observation and the reward are
-// rounded to fp32 once, where the host environment rounds them.  What differs from the host is libm: sin / cos / fmod are the device library's.
+// The kernels are templates over the kind (group_env.h: EnvPendulum, EnvMountainCar -- S, the row width, the time limit, start state,
+// observation and dynamics).  The dynamics are the public gym specifications as rlrep_amd/envs/pendulum.py and envs/mountain_car.py restate
+// them, computed in fp64 by ONE lane in the operation order of those files, with contraction off (NumPy does not fuse): observation, reward and
+// (for the kinds that keep an fp32 state) the state are rounded to fp32 where the host environment rounds them.  What differs from the host is
+// libm: sin / cos / fmod are the device library's.
 //
 // Shape: grid (1, members) resp. (episodes, members), 1024 threads, RL_GRP_MEMBER first (group.h): the workgroups of a retired member return
 // before they read or write anything.  The actor forward is select_action_body.h, the body of select_action_kernel(_grp): same tiles, same
@@ -19,48 +20,27 @@
 #include "group_env.h"
 #include "launchers.h"
 
-#define RL_PI 3.141592653589793
-
-__device__ __forceinline__ float env_u01f(uint32_t w) { return ((float)(w >> 8) + 0.5f) * (1.0f / 16777216.0f); }          // (0, 1), 24 bits
-__device__ __forceinline__ double env_u01d(uint32_t hi, uint32_t lo) {                                                   // (0, 1), 53 bits
-    return ((double)((((unsigned long long)hi << 32) | lo) >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-}
-// an episode's start state from one Philox block: theta ~ U(-pi, pi), theta_dot ~ U(-1, 1)
-__device__ __forceinline__ void env_start(unsigned long long seed, unsigned long long counter, uint32_t word2, uint32_t stream, double& th, double& thd) {
+// an episode's start state of kind Env from one Philox block
+template <class Env>
+__device__ __forceinline__ void env_start(unsigned long long seed, unsigned long long counter, uint32_t word2, uint32_t stream, double& x0, double& x1) {
     uint32_t c[4] = {(uint32_t)counter, (uint32_t)(counter >> 32), word2, stream};
     philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    th = -RL_PI + 2.0 * RL_PI * env_u01d(c[0], c[1]);
-    thd = -1.0 + 2.0 * env_u01d(c[2], c[3]);
-}
-__device__ __forceinline__ void env_observe(double th, double thd, float* obs) {
-    obs[0] = (float)cos(th); obs[1] = (float)sin(th); obs[2] = (float)thd;
-}
-// PendulumEnv.step (envs/pendulum.py:46-56), operation for operation; returns the fp32 reward
-__device__ __forceinline__ float env_dynamics(double& th, double& thd, float action) {
-#pragma clang fp contract(off)
-    const double u = fmin(fmax((double)action, -2.0), 2.0);
-    double wrapped = fmod(th + RL_PI, 2.0 * RL_PI);                 // Python's float %: the sign of the divisor
-    if (wrapped < 0.0) wrapped += 2.0 * RL_PI;
-    wrapped -= RL_PI;
-    const double cost = (wrapped * wrapped + 0.1 * (thd * thd)) + 0.001 * (u * u);
-    double v = thd + (15.0 * sin(th) + 3.0 * u) * 0.05;
-    v = fmin(fmax(v, -8.0), 8.0);
-    th = th + v * 0.05;
-    thd = v;
-    return (float)(-cost);
+    Env::start(c, x0, x1);
 }
 
 // rlrep_group_env_reset: every member's record starts a fresh episode (all members, whatever the live table says: a reset is the caller's
 // explicit act, like rlrep_group_clone_members); ring cursors, counters and the returns ring are zeroed, and so is the group's EnvCtl.
+template <class Env>
 __global__ __launch_bounds__(64) void group_env_reset_kernel(EnvRecord* __restrict__ recs, EnvCtl* __restrict__ ctl, const unsigned long long* __restrict__ seeds) {
     if (threadIdx.x != 0) return;
     const int m = blockIdx.y;
     EnvRecord* rec = recs + m;
     double th, thd;
-    env_start(seeds[m], 0ull, 1u, RL_STREAM_ENV, th, thd);
+    env_start<Env>(seeds[m], 0ull, 1u, RL_STREAM_ENV, th, thd);
     rec->theta = th; rec->theta_dot = thd; rec->episode_return = 0.0; rec->ring_ptr = 0; rec->nsteps = 0;
     rec->t = 0; rec->ring_size = 0; rec->episodes_done = 0; rec->force = 0; rec->force_action = 0.f; rec->act = 0.f;
-    env_observe(th, thd, rec->obs); rec->obs[3] = 0.f;
+    Env::observe(th, thd, rec->obs);
+    for (int q = Env::S; q < 4; ++q) rec->obs[q] = 0.f;
     for (int q = 0; q < RL_ENV_RETURNS; ++q) rec->returns[q] = 0.0;
     for (int q = 0; q < 6; ++q) rec->pad_[q] = 0.0;
     if (m == 0) { ctl->t_global = 0; ctl->calls = 0ull; ctl->ticket = 0; ctl->pad_ = 0; }
@@ -68,6 +48,7 @@ __global__ __launch_bounds__(64) void group_env_reset_kernel(EnvRecord* __restri
 
 // One environment step of every live member.  p0: member 0's actor (obs / act unset); ring: member 0's replay ring, member m's lies
 // ring_stride floats further and holds `capacity` rows [s | a | s' | r | done_bool] (replay_add_kernel_grp's layout).
+template <class Env>
 __global__ __launch_bounds__(1024) void group_env_step_kernel(SelectAct p0, long long mstride, const unsigned long long* __restrict__ seeds,
                                                               const int* __restrict__ live, EnvRecord* __restrict__ recs, EnvCtl* __restrict__ ctl,
                                                               float* __restrict__ ring, long long ring_stride, long long capacity,
@@ -97,15 +78,21 @@ __global__ __launch_bounds__(1024) void group_env_step_kernel(SelectAct p0, long
     }
     if (rec->force) { a = rec->force_action; rec->force = 0; }
     double th = rec->theta, thd = rec->theta_dot;
-    const float s0 = rec->obs[0], s1 = rec->obs[1], s2 = rec->obs[2];
-    const float r32 = env_dynamics(th, thd, a);
-    float nx[3];
-    env_observe(th, thd, nx);
+    float s[Env::S], nx[Env::S];
+#pragma unroll
+    for (int q = 0; q < Env::S; ++q) s[q] = rec->obs[q];
+    bool goal;
+    const float r32 = Env::dynamics(th, thd, a, goal);
+    Env::observe(th, thd, nx);
     long long ptr = rec->ring_ptr;
     if (ptr < 0 || ptr >= capacity) ptr = 0;                        // (a cursor written by the host: never leave the ring)
-    float* row = ring + (long long)m * ring_stride + ptr * 9;
-    row[0] = s0; row[1] = s1; row[2] = s2; row[3] = a; row[4] = nx[0]; row[5] = nx[1]; row[6] = nx[2]; row[7] = r32;
-    row[8] = 0.f;                                                   // done_bool: the time limit is Pendulum's only end, and it does not count
+    float* row = ring + (long long)m * ring_stride + ptr * Env::ROW;
+#pragma unroll
+    for (int q = 0; q < Env::S; ++q) { row[q] = s[q]; row[Env::S + 1 + q] = nx[q]; }
+    row[Env::S] = a; row[2 * Env::S + 1] = r32;
+    const int t = rec->t + 1;
+    // done_bool is the host loop's rule (main.py): an end by the time limit does not count, and neither does a goal reached on the limit's step
+    row[2 * Env::S + 2] = (Env::TERMINATES && goal && t < Env::LIMIT) ? 1.f : 0.f;
     rec->ring_ptr = ptr + 1 >= capacity ? 0 : ptr + 1;
     const int fill = (int)min((long long)rec->ring_size + 1, capacity);
     rec->ring_size = fill;
@@ -113,19 +100,19 @@ __global__ __launch_bounds__(1024) void group_env_step_kernel(SelectAct p0, long
     rec->act = a;
     rec->nsteps = (long long)(n + 1);
     const double ret = rec->episode_return + (double)r32;
-    const int t = rec->t + 1;
-    if (t >= RL_ENV_EPISODE_STEPS) {
+    if ((Env::TERMINATES && goal) || t >= Env::LIMIT) {
         const int done = rec->episodes_done;
         rec->returns[done & (RL_ENV_RETURNS - 1)] = ret;
         rec->episodes_done = done + 1;
         rec->episode_return = 0.0; rec->t = 0;
-        env_start(p.seed, n + 1, 1u, RL_STREAM_ENV, th, thd);
-        env_observe(th, thd, nx);
+        env_start<Env>(p.seed, n + 1, 1u, RL_STREAM_ENV, th, thd);
+        Env::observe(th, thd, nx);
     } else {
         rec->episode_return = ret; rec->t = t;
     }
     rec->theta = th; rec->theta_dot = thd;
-    rec->obs[0] = nx[0]; rec->obs[1] = nx[1]; rec->obs[2] = nx[2];
+#pragma unroll
+    for (int q = 0; q < Env::S; ++q) rec->obs[q] = nx[q];
     // "last workgroup advances the counters": every workgroup read them before its own ticket, so the last ticket follows every read
     __threadfence();
     if (atomicAdd(&ctl->ticket, 1) == n_live - 1) {
@@ -139,12 +126,18 @@ __global__ __launch_bounds__(1024) void group_env_step_kernel(SelectAct p0, long
 // start state Philox(seed, RL_STREAM_EVAL, counter0 + e) gives, and writes the fp64 sum of the fp32 rewards to out[m * episodes + e] and the
 // start state to starts[(m * episodes + e) * 2 ..].  The observation and the action live in LDS behind the body's buffers; the weights are
 // read from L2 every step (the three layers do not fit in LDS).
+// A kind whose episodes can end before the limit leaves the loop WORKGROUP-UNIFORMLY: lane 0 alone decides (it holds the state) and writes a
+// flag word in LDS, and every lane reads that word behind the barrier at the head of the next iteration -- the barrier that follows the
+// dynamics anyway -- so all 1024 lanes see one value and break in the same iteration; no lane waits at a barrier the others have left.  The
+// flag is written again only behind the body's barriers, after every lane has read it.  The trip count is bounded by the constant Env::LIMIT.
+template <class Env>
 __global__ __launch_bounds__(1024) void group_env_eval_kernel(SelectAct p0, long long mstride, const unsigned long long* __restrict__ seeds,
                                                               const int* __restrict__ live, unsigned long long counter0, int episodes,
                                                               double* __restrict__ out, double* __restrict__ starts) {
     RL_GRP_MEMBER(m, live);
     extern __shared__ float sm[];
-    // behind the body's buffers (8-byte aligned): theta | theta_dot | return (fp64: kept out of the registers the body needs), then obs[S] | act[A]
+    // behind the body's buffers (8-byte aligned): x0 | x1 | return (fp64: kept out of the registers the body needs), then obs[S] | act[A]
+    // (| the end flag of a kind that terminates)
     double* const st = (double*)(sm + ((p0.S + 2 * p0.Ha + 2 * p0.A + 1) & ~1));
     float* const slot = (float*)(st + 3);
     const int e = blockIdx.x;
@@ -156,49 +149,78 @@ __global__ __launch_bounds__(1024) void group_env_eval_kernel(SelectAct p0, long
     p.explore = 0; p.offset = 0ull;
     if (threadIdx.x == 0) {
         double th, thd;
-        env_start(p.seed, counter0 + (unsigned long long)e, 0u, RL_STREAM_EVAL, th, thd);
+        env_start<Env>(p.seed, counter0 + (unsigned long long)e, 0u, RL_STREAM_EVAL, th, thd);
         double* first = starts + ((long long)m * episodes + e) * 2;
         first[0] = th; first[1] = thd;
         st[0] = th; st[1] = thd; st[2] = 0.0;
-        env_observe(th, thd, slot);
+        Env::observe(th, thd, slot);
+        if constexpr (Env::TERMINATES) slot[p0.S + p0.A] = 0.f;
     }
-    for (int step = 0; step < RL_ENV_EPISODE_STEPS; ++step) {
+    for (int step = 0; step < Env::LIMIT; ++step) {
         __syncthreads();
+        if constexpr (Env::TERMINATES) {
+            if (slot[p0.S + p0.A] != 0.f) break;                    // uniform: one LDS word, read by all lanes behind the barrier
+        }
         {
 #include "select_action_body.h"
         }
         __syncthreads();
         if (threadIdx.x == 0) {
             double th = st[0], thd = st[1];
-            st[2] += (double)env_dynamics(th, thd, slot[p0.S]);
+            bool goal;
+            st[2] += (double)Env::dynamics(th, thd, slot[p0.S], goal);
             st[0] = th; st[1] = thd;
-            env_observe(th, thd, slot);
+            Env::observe(th, thd, slot);
+            if constexpr (Env::TERMINATES) { if (goal) slot[p0.S + p0.A] = 1.f; }
         }
     }
     if (threadIdx.x == 0) out[(long long)m * episodes + e] = st[2];
 }
 
-static size_t env_lds(const SelectAct* p, bool slot) {
-    return sizeof(float) * ((size_t)p->S + 2 * (size_t)p->Ha + 2 * (size_t)p->A + (slot ? 1 + 6 + (size_t)p->S + (size_t)p->A : 0));          // (eval: alignment slack, three doubles, obs, act)
+static size_t env_lds(const SelectAct* p, bool slot, bool flag) {
+    return sizeof(float) * ((size_t)p->S + 2 * (size_t)p->Ha + 2 * (size_t)p->A + (slot ? 1 + 6 + (size_t)p->S + (size_t)p->A + (flag ? 1 : 0) : 0));      // (eval: alignment slack, three doubles, obs, act, end flag)
 }
-extern "C" int rl_launch_group_env_reset(EnvRecord* recs, EnvCtl* ctl, const unsigned long long* seeds, int members, hipStream_t st) {
-    if (members < 1 || members > RLREP_GROUP_MAX_MEMBERS) return -7;
-    hipLaunchKernelGGL(group_env_reset_kernel, dim3(1, members), dim3(64), 0, st, recs, ctl, seeds);
-    return (int)hipGetLastError();
-}
-extern "C" int rl_launch_group_env_step(const SelectAct* p, long long mstride, const unsigned long long* seeds, const int* live, int grid_y, EnvRecord* recs,
-                                        EnvCtl* ctl, float* ring, long long ring_stride, long long capacity, int* size_dev, float eps_greedy,
-                                        long long start_timesteps, hipStream_t st) {
-    const size_t lds = env_lds(p, false);
-    if (lds > 60 * 1024 || p->S != 3 || p->A != 1 || grid_y < 1 || grid_y > RLREP_GROUP_MAX_MEMBERS) return -7;
-    hipLaunchKernelGGL(group_env_step_kernel, dim3(1, grid_y), dim3(1024), lds, st, *p, mstride, seeds, live, recs, ctl, ring, ring_stride, capacity, size_dev,
+template <class Env>
+static int env_launch_step(const SelectAct* p, long long mstride, const unsigned long long* seeds, const int* live, int grid_y, EnvRecord* recs, EnvCtl* ctl,
+                           float* ring, long long ring_stride, long long capacity, int* size_dev, float eps_greedy, long long start_timesteps, hipStream_t st) {
+    const size_t lds = env_lds(p, false, false);
+    if (lds > 60 * 1024 || p->S != Env::S || p->A != Env::A || grid_y < 1 || grid_y > RLREP_GROUP_MAX_MEMBERS) return -7;
+    hipLaunchKernelGGL(group_env_step_kernel<Env>, dim3(1, grid_y), dim3(1024), lds, st, *p, mstride, seeds, live, recs, ctl, ring, ring_stride, capacity, size_dev,
                        eps_greedy, start_timesteps);
     return (int)hipGetLastError();
 }
-extern "C" int rl_launch_group_env_eval(const SelectAct* p, long long mstride, const unsigned long long* seeds, const int* live, int grid_y,
-                                        unsigned long long counter0, int episodes, double* out, double* starts, hipStream_t st) {
-    const size_t lds = env_lds(p, true);
-    if (lds > 60 * 1024 || p->S != 3 || p->A != 1 || grid_y < 1 || grid_y > RLREP_GROUP_MAX_MEMBERS || episodes < 1 || episodes > RL_ENV_MAX_EPISODES) return -7;
-    hipLaunchKernelGGL(group_env_eval_kernel, dim3(episodes, grid_y), dim3(1024), lds, st, *p, mstride, seeds, live, counter0, episodes, out, starts);
+template <class Env>
+static int env_launch_eval(const SelectAct* p, long long mstride, const unsigned long long* seeds, const int* live, int grid_y, unsigned long long counter0,
+                           int episodes, double* out, double* starts, hipStream_t st) {
+    const size_t lds = env_lds(p, true, Env::TERMINATES);
+    if (lds > 60 * 1024 || p->S != Env::S || p->A != Env::A || grid_y < 1 || grid_y > RLREP_GROUP_MAX_MEMBERS || episodes < 1 || episodes > RL_ENV_MAX_EPISODES) return -7;
+    hipLaunchKernelGGL(group_env_eval_kernel<Env>, dim3(episodes, grid_y), dim3(1024), lds, st, *p, mstride, seeds, live, counter0, episodes, out, starts);
     return (int)hipGetLastError();
+}
+// the launchers dispatch on the kind (an unknown one is -7: rlrep_group_env_create refuses it long before)
+extern "C" int rl_launch_group_env_reset(int kind, EnvRecord* recs, EnvCtl* ctl, const unsigned long long* seeds, int members, hipStream_t st) {
+    if (members < 1 || members > RLREP_GROUP_MAX_MEMBERS) return -7;
+    switch (kind) {
+    case EnvPendulum::KIND: hipLaunchKernelGGL(group_env_reset_kernel<EnvPendulum>, dim3(1, members), dim3(64), 0, st, recs, ctl, seeds); break;
+    case EnvMountainCar::KIND: hipLaunchKernelGGL(group_env_reset_kernel<EnvMountainCar>, dim3(1, members), dim3(64), 0, st, recs, ctl, seeds); break;
+    default: return -7;
+    }
+    return (int)hipGetLastError();
+}
+extern "C" int rl_launch_group_env_step(int kind, const SelectAct* p, long long mstride, const unsigned long long* seeds, const int* live, int grid_y,
+                                        EnvRecord* recs, EnvCtl* ctl, float* ring, long long ring_stride, long long capacity, int* size_dev, float eps_greedy,
+                                        long long start_timesteps, hipStream_t st) {
+    switch (kind) {
+    case EnvPendulum::KIND: return env_launch_step<EnvPendulum>(p, mstride, seeds, live, grid_y, recs, ctl, ring, ring_stride, capacity, size_dev, eps_greedy, start_timesteps, st);
+    case EnvMountainCar::KIND: return env_launch_step<EnvMountainCar>(p, mstride, seeds, live, grid_y, recs, ctl, ring, ring_stride, capacity, size_dev, eps_greedy, start_timesteps, st);
+    default: return -7;
+    }
+}
+extern "C" int rl_launch_group_env_eval(int kind, const SelectAct* p, long long mstride, const unsigned long long* seeds, const int* live, int grid_y,
+                                        unsigned long long counter0, int episodes, double* out, double* starts, hipStream_t st) {
+    switch (kind) {
+    case EnvPendulum::KIND: return env_launch_eval<EnvPendulum>(p, mstride, seeds, live, grid_y, counter0, episodes, out, starts, st);
+    case EnvMountainCar::KIND: return env_launch_eval<EnvMountainCar>(p, mstride, seeds, live, grid_y, counter0, episodes, out, starts, st);
+    default: return -7;
+    }
 }

@@ -1,9 +1,10 @@
-"""Pendulum-v1 environments of a seed group on the device (include/rlrep.h rlrep_group_env_*; rlrep_amd/csrc/group_env.hip).
+"""Environments of a seed group on the device (include/rlrep.h rlrep_group_env_*; rlrep_amd/csrc/group_env.hip): Pendulum-v1
+(DevicePendulumGroup) and MountainCarContinuous-v0 (DeviceMountainCarGroup, whose goal state ends an episode with done = 1).
 
 One record per member lives on the device; `SeedBatchMixin.iterate(env, buffers, batch_size)` acts, explores, steps the dynamics, writes the
 replay-ring row and trains every live member in ONE graph replay, and `SeedBatchMixin.evaluate(env, episodes)` scores every live member in one
-launch.  The dynamics are those of rlrep_amd/envs/pendulum.py (fp64 in one lane, rounded to fp32 where that file rounds); the random draws
-are Philox streams of the member's seed, so two groups with equal seeds collect identical transitions.
+launch.  The dynamics are those of rlrep_amd/envs/pendulum.py resp. envs/mountain_car.py (fp64 in one lane, rounded to fp32 where those
+files round); the random draws are Philox streams of the member's seed, so two groups with equal seeds collect identical transitions.
 """
 import ctypes as C
 
@@ -13,7 +14,9 @@ import torch
 from rlrep_amd._lib import lib, check
 from rlrep_amd.core import _stream
 
-KIND_PENDULUM = 0
+KIND_PENDULUM, KIND_MOUNTAIN_CAR_CONTINUOUS = 0, 2          # include/rlrep.h RLREP_ENV_*
+# kind -> (name, S, A, time limit): csrc/group_env.h rl_env_kinds
+KINDS = {KIND_PENDULUM: ('Pendulum-v1', 3, 1, 200), KIND_MOUNTAIN_CAR_CONTINUOUS: ('MountainCarContinuous-v0', 2, 1, 999)}
 STATE_RECORDS, STATE_COUNTERS, STATE_EVAL_STARTS = 0, 1, 2
 RETURNS = 16
 MAX_EPISODES = 64
@@ -27,21 +30,25 @@ assert RECORD_DTYPE.itemsize == 256
 COUNTERS_DTYPE = np.dtype([('t_global', '<i8'), ('calls', '<u8')])
 
 
-class DevicePendulumGroup(object):
-    """The device environments of seed group `agent` (a SACSeedBatch / CTRLSACSeedBatch with Pendulum's dimensions).  Created reset."""
+class DeviceEnvGroup(object):
+    """The device environments of kind `kind` (a key of KINDS) of seed group `agent` (a SACSeedBatch / CTRLSACSeedBatch with the kind's
+    dimensions).  Created reset."""
 
-    max_episode_steps = EPISODE_STEPS
-
-    def __init__(self, agent, eps_greedy=0.0, start_timesteps=0):
+    def __init__(self, agent, kind, eps_greedy=0.0, start_timesteps=0):
         """eps_greedy: the probability of a uniform action in place of the policy's; start_timesteps: the warm-up, steps (counted since
         reset) that take uniform actions only.  Both ride by value in a captured iterate() graph."""
+        name = type(self).__name__
         if getattr(agent, 'R', None) is None or not hasattr(agent, 'seeds'):
-            raise ValueError('DevicePendulumGroup: needs a seed group (SACSeedBatch / CTRLSACSeedBatch)')
+            raise ValueError(f'{name}: needs a seed group (SACSeedBatch / CTRLSACSeedBatch)')
+        if kind not in KINDS:
+            raise ValueError(f'{name}: kind {kind} is not built ({", ".join(f"{k} = {v[0]}" for k, v in KINDS.items())})')
+        self.kind = int(kind)
+        self.env_name, self.state_dim, self.action_dim, self.max_episode_steps = KINDS[self.kind]
         self.agent, self.R = agent, agent.R
         self.eps_greedy, self.start_timesteps = float(eps_greedy), int(start_timesteps)
         self.t_global, self.calls = 0, 0        # host mirrors of the device counters (SeedBatchMixin.iterate keeps them in step)
         h = C.c_void_p()
-        check(lib.rlrep_group_env_create(agent.core.h, KIND_PENDULUM, C.byref(h)), 'group_env_create')
+        check(lib.rlrep_group_env_create(agent.core.h, self.kind, C.byref(h)), 'group_env_create')
         self.h = h
         self._drained = [0] * self.R            # finished episodes returns() has handed out, per member
         self.eval_index = 0                     # evaluations run so far (SeedBatchMixin.evaluate): the next one's start states
@@ -70,7 +77,7 @@ class DevicePendulumGroup(object):
     def set_state(self, records):
         rec = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
         if rec.shape != (self.R,):
-            raise ValueError(f'DevicePendulumGroup.set_state: needs {self.R} records')
+            raise ValueError(f'{type(self).__name__}.set_state: needs {self.R} records')
         self._block(STATE_RECORDS, rec, True)
         self._drained = [int(n) for n in rec['episodes_done']]
 
@@ -92,7 +99,7 @@ class DevicePendulumGroup(object):
         self._block(STATE_RECORDS, rec, True)
 
     def eval_starts(self, episodes):
-        """[R, episodes, 2] (theta, theta_dot): the start states of the last evaluation (rows of retired members are stale)"""
+        """[R, episodes, 2] (theta, theta_dot) resp. (p, v): the start states of the last evaluation (rows of retired members are stale)"""
         return self._block(STATE_EVAL_STARTS, np.zeros((self.R, int(episodes), 2), np.float64), False)
 
     def returns(self):
@@ -123,12 +130,40 @@ class DevicePendulumGroup(object):
     # ---- checkpoints ----------------------------------------------------------------------------------------------------------------
     def snapshot(self):
         t, calls = self.counters()
-        return {'kind': KIND_PENDULUM, 'records': torch.from_numpy(self.state().view(np.uint8).copy()), 't_global': t, 'calls': calls,
+        return {'kind': self.kind, 'records': torch.from_numpy(self.state().view(np.uint8).copy()), 't_global': t, 'calls': calls,
                 'eval_index': int(self.eval_index)}
 
     def load_snapshot(self, snap):
-        if snap.get('kind') != KIND_PENDULUM or snap['records'].numel() != self.R * RECORD_DTYPE.itemsize:
+        if snap.get('kind') != self.kind or snap['records'].numel() != self.R * RECORD_DTYPE.itemsize:
             raise RuntimeError('checkpoint does not match this device environment (kind / members differ)')
         self.set_state(snap['records'].numpy().view(RECORD_DTYPE))
         self.set_counters(snap['t_global'], snap['calls'])
         self.eval_index = int(snap.get('eval_index', 0))
+
+
+class DevicePendulumGroup(DeviceEnvGroup):
+    """Pendulum-v1: 200-step episodes that never terminate (done_bool is always 0)"""
+
+    max_episode_steps = EPISODE_STEPS
+
+    def __init__(self, agent, eps_greedy=0.0, start_timesteps=0):
+        super().__init__(agent, KIND_PENDULUM, eps_greedy, start_timesteps)
+
+
+class DeviceMountainCarGroup(DeviceEnvGroup):
+    """MountainCarContinuous-v0: the goal ends an episode with done_bool = 1 (unless it falls on the 999th step: the time limit does not
+    count, as in main.py's host loop); the record's theta / theta_dot hold position and velocity, fp32-representable."""
+
+    max_episode_steps = 999
+
+    def __init__(self, agent, eps_greedy=0.0, start_timesteps=0):
+        super().__init__(agent, KIND_MOUNTAIN_CAR_CONTINUOUS, eps_greedy, start_timesteps)
+
+
+def device_class(env_name):
+    """the device environment class of --env `env_name`, or None where none is built"""
+    if str(env_name).startswith('Pendulum'):
+        return DevicePendulumGroup
+    if str(env_name).startswith('MountainCarContinuous'):
+        return DeviceMountainCarGroup
+    return None

@@ -57,11 +57,14 @@ class PendulumEnv:
 
 
 def make(name, seed=None):
-    """`gym.make` stand-in: Pendulum-v1 natively; anything else through gym if it is installed."""
+    """`gym.make` stand-in: Pendulum-v1 and MountainCarContinuous-v0 natively; anything else through gym if it is installed."""
     if name.startswith('Pendulum'):
         return PendulumEnv(seed)
+    if name.startswith('MountainCarContinuous'):
+        from .mountain_car import MountainCarContinuousEnv
+        return MountainCarContinuousEnv(seed)
     try:
         import gym
     except ImportError as e:
-        raise RuntimeError(f'environment {name!r} needs gym (not installed); only Pendulum-v1 is built in') from e
+        raise RuntimeError(f'environment {name!r} needs gym (not installed); only Pendulum-v1 and MountainCarContinuous-v0 are built in') from e
     return gym.make(name)

@@ -30,7 +30,7 @@ every launch), never below `--halving-min` live members (default 1).  A retired 
 metrics.jsonl stops growing; its state stays in the group (and in --save_model checkpoints).  Every halving is one line of
 `log/<env>/<alg>/<dir>/halving.jsonl` (step, retired members with their seeds and scores, live count).  Not together with --pbt-interval.
 
-`--device-env` (with --seeds / --sweep and --env Pendulum-v1) moves the environments onto the device (rlrep_amd/envs/device.py): acting,
+`--device-env` (with --seeds / --sweep and --env Pendulum-v1 or MountainCarContinuous-v0) moves the environments onto the device (rlrep_amd/envs/device.py): acting,
 exploring, stepping, the replay-ring row and train() of every live member are one graph replay per step (SeedBatchMixin.iterate) and an
 evaluation is one launch (SeedBatchMixin.evaluate); --pbt-interval and --halving-interval rank by those scores.  Exploration and reset draws
 come from Philox streams of the members' seeds, so a run differs from the host loop's in its random numbers, not in its algorithm.
@@ -104,7 +104,7 @@ def run(argv=None):
     p.add_argument('--halving-keep', default=None, type=float, help='share of the live members that stay at a halving step, rounded up (default 0.5)')
     p.add_argument('--halving-min', default=None, type=int, help='stop retiring at this many live members (default 1)')
     p.add_argument('--device-env', action='store_true',
-                   help='step and score the environments on the device (with --seeds / --sweep and --env Pendulum-v1): rlrep_amd/envs/device.py')
+                   help='step and score the environments on the device (with --seeds / --sweep and --env Pendulum-v1 or MountainCarContinuous-v0): rlrep_amd/envs/device.py')
     args = p.parse_args(argv)
     if args.seeds is not None or args.sweep:
         return run_seeds(args)
@@ -408,8 +408,8 @@ def run_seeds(args):
     seeds = [s for _ in configs for s in seeds]              # member = (configuration, seed), configurations outermost
     pbt_cfg = parse_pbt(args, args.alg, len(seeds))
     halving_cfg = parse_halving(args, len(seeds), pbt_cfg)
-    if args.device_env and not str(args.env).startswith('Pendulum'):
-        raise SystemExit(f'--device-env: only Pendulum-v1 is built on the device (got --env {args.env}); run without --device-env')
+    if args.device_env and not str(args.env).startswith(('Pendulum', 'MountainCarContinuous')):
+        raise SystemExit(f'--device-env: only Pendulum-v1 and MountainCarContinuous-v0 are built on the device (got --env {args.env}); run without --device-env')
     from rlrep_amd.utils.buffer_group import ReplayBufferGroup
     R = len(seeds)
     envs_, evals_ = [envs.make(args.env) for _ in seeds], [envs.make(args.env) for _ in seeds]
@@ -488,8 +488,8 @@ def _device_loop(args, agent, replay, ev):
     train() of every live member in one graph replay -- and one `agent.evaluate` launch per evaluation.  The exploration and reset draws are
     Philox streams of the members' seeds instead of NumPy generators, and an evaluation's start states are a function of (seed, evaluation
     index, episode); the metrics.jsonl / pbt.jsonl / halving.jsonl rows keep their keys."""
-    from rlrep_amd.envs.device import DevicePendulumGroup
-    env = DevicePendulumGroup(agent, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps))
+    from rlrep_amd.envs.device import device_class
+    env = device_class(args.env)(agent, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps))
     ev.evaluations = [[float(s)] for s in agent.evaluate(env, args.eval_episodes)]
     infos = None
     timer = util.Timer()

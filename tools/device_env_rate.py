@@ -2,13 +2,14 @@
 
     python tools/device_env_rate.py --alg sac --members 4,8,16
     python tools/device_env_rate.py --alg ctrlsac --members 4,8,16
+    python tools/device_env_rate.py --alg sac --env MountainCarContinuous-v0 --calls 300
 
-Host loop: the body of main.py run_seeds past warm-up -- group select_action (one launch, one synchronisation), R NumPy PendulumEnv steps and
+Host loop: the body of main.py run_seeds past warm-up -- group select_action (one launch, one synchronisation), R NumPy environment steps (--env: Pendulum-v1 or MountainCarContinuous-v0) and
 the epsilon-greedy draws in a Python loop, ReplayBufferGroup.add, train().  Device loop: SeedBatchMixin.iterate (rlrep_amd/envs/device.py):
-one graph replay.  Both on groups of the same seeds and shapes (sac: hidden 256; ctrlsac: F = 256, hidden 256; Pendulum dims, B = 64), in ONE
+one graph replay.  Both on groups of the same seeds and shapes (sac: hidden 256; ctrlsac: F = 256, hidden 256; the environment's dims, B = 64), in ONE
 process, arms alternated: --warmup iterations per arm, then --windows windows of --calls iterations each, host wall clock around a device
 synchronisation; median and min .. max of the windows.  Also the group's bare train() (the floor of either loop) in the same alternation.
-Evaluation: util.eval_policy per member (as run_seeds scores) against SeedBatchMixin.evaluate, --eval-episodes episodes, median of 3.
+Evaluation: util.eval_policy per member (as run_seeds scores) against SeedBatchMixin.evaluate, --eval-episodes episodes, median of --eval-repeats.
 """
 import argparse
 import os
@@ -25,14 +26,22 @@ sys.path.insert(0, ROOT)
 EPS_GREEDY = 0.01
 
 
+ENV = 'Pendulum-v1'          # --env
+
+
+def _dims():
+    from rlrep_amd import envs
+    e = envs.make(ENV)
+    return e.observation_space.shape[0], e.action_space.shape[0], e.action_space, e._max_episode_steps
+
+
 def _group(alg, seeds, B):
-    from rlrep_amd.envs.pendulum import PendulumEnv
-    space = PendulumEnv().action_space
+    S, A, space, _ = _dims()
     if alg == 'sac':
         from rlrep_amd.agent.sac.seed_batch import SACSeedBatch
-        return SACSeedBatch(seeds, 3, 1, space, max_batch=B, hidden_dim=256)
+        return SACSeedBatch(seeds, S, A, space, max_batch=B, hidden_dim=256)
     from rlrep_amd.agent.ctrlsac.seed_batch import CTRLSACSeedBatch
-    return CTRLSACSeedBatch(seeds, 3, 1, space, max_batch=B, hidden_dim=256, feature_dim=256, extra_feature_steps=3)
+    return CTRLSACSeedBatch(seeds, S, A, space, max_batch=B, hidden_dim=256, feature_dim=256, extra_feature_steps=3)
 
 
 class HostLoop(object):
@@ -43,14 +52,15 @@ class HostLoop(object):
         from rlrep_amd.utils.buffer_group import ReplayBufferGroup
         self.R, self.B = len(seeds), B
         self.agent = _group(alg, seeds, B)
-        self.replay = ReplayBufferGroup(self.R, 3, 1, max_size=100000)
-        self.envs = [envs.make('Pendulum-v1') for _ in seeds]
+        S, A, space, self.limit = _dims()
+        self.replay = ReplayBufferGroup(self.R, S, A, max_size=100000)
+        self.envs = [envs.make(ENV) for _ in seeds]
         for s, e in zip(seeds, self.envs):
             e.seed(s)
         self.rngs = [np.random.RandomState(s) for s in seeds]
         self.states = np.stack([np.asarray(e.reset(), np.float32) for e in self.envs])
         self.ep_steps = np.zeros(self.R, np.int64)
-        self.lo, self.hi = np.float32(-2.0), np.float32(2.0)
+        self.lo, self.hi = np.float32(space.low[0]), np.float32(space.high[0])
 
     def step(self):
         R = self.R
@@ -64,7 +74,7 @@ class HostLoop(object):
         for r, e in enumerate(self.envs):
             ns, rew, done, _ = e.step(actions[r])
             nexts[r], rewards[r] = ns, rew
-            dones[r] = float(done) if self.ep_steps[r] < 200 else 0.0
+            dones[r] = float(done) if self.ep_steps[r] < self.limit else 0.0
             if done:
                 resets.append(r)
         self.replay.add(self.states, actions, nexts, rewards, dones)
@@ -77,12 +87,13 @@ class HostLoop(object):
 
 class DeviceLoop(object):
     def __init__(self, alg, seeds, B):
-        from rlrep_amd.envs.device import DevicePendulumGroup
+        from rlrep_amd.envs.device import device_class
         from rlrep_amd.utils.buffer_group import ReplayBufferGroup
         self.R, self.B = len(seeds), B
         self.agent = _group(alg, seeds, B)
-        self.replay = ReplayBufferGroup(self.R, 3, 1, max_size=100000)
-        self.env = DevicePendulumGroup(self.agent, eps_greedy=EPS_GREEDY, start_timesteps=0)
+        S, A, _, _ = _dims()
+        self.replay = ReplayBufferGroup(self.R, S, A, max_size=100000)
+        self.env = device_class(ENV)(self.agent, eps_greedy=EPS_GREEDY, start_timesteps=0)
 
     def step(self):
         self.agent.iterate(self.env, self.replay, self.B)
@@ -127,11 +138,15 @@ def main(argv=None):
     p.add_argument('--calls', type=int, default=400)
     p.add_argument('--windows', type=int, default=5)
     p.add_argument('--eval-episodes', type=int, default=10)
+    p.add_argument('--eval-repeats', type=int, default=3)
+    p.add_argument('--env', default='Pendulum-v1', choices=['Pendulum-v1', 'MountainCarContinuous-v0'])
     args = p.parse_args(argv)
+    global ENV
+    ENV = args.env
     from rlrep_amd.utils import util
     from rlrep_amd.main import _MemberPolicy
     from rlrep_amd import envs
-    print(f'# {torch.cuda.get_device_name(0)}; {args.alg} Pendulum-v1 B = {args.batch}; {args.warmup} warm-up iterations, median (min .. max) of '
+    print(f'# {torch.cuda.get_device_name(0)}; {args.alg} {ENV} B = {args.batch}; {args.warmup} warm-up iterations, median (min .. max) of '
           f'{args.windows} windows of {args.calls} iterations, arms alternated in one process')
     for R in [int(v) for v in args.members.split(',')]:
         seeds = list(range(R))
@@ -148,9 +163,9 @@ def main(argv=None):
         # one evaluation of every member
         host, dev = arms['host'], arms['device']
         policies = [_MemberPolicy(host.agent, r) for r in range(R)]
-        evals = [envs.make('Pendulum-v1') for _ in seeds]
+        evals = [envs.make(ENV) for _ in seeds]
         th, td = [], []
-        for _ in range(3):
+        for _ in range(args.eval_repeats):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for r in range(R):
