@@ -980,45 +980,35 @@ int32_t rlrep_gemm(int32_t engine, int32_t la, int32_t lb, const float* A, int32
     } else {
         t.flags |= rl_gemm_lds_dim_flags(&t, la, lb) | rl_gemm_lds_ptr_flags(&t);
         // (the 64-wide bf16x3 tile has any-alignment loaders; the 128-wide one needs 16-byte-regular operands)
-        if (engine == 2 && (t.flags & (FLAG_SCALAR_A | FLAG_SCALAR_B)) && (bt != 64 || R < 4 || Cn < 4 || K < 4)) { rl_set_error("gemm: shape/alignment not eligible for the bf16x3 tile"); return RLREP_ERR_ARG; }
+        if (engine == 2 && (t.flags & (FLAG_SCALAR_A | FLAG_SCALAR_B)) && (bt != 64 || !gl_x3s_unaligned_can_run(&t))) { rl_set_error("gemm: shape/alignment not eligible for the bf16x3 tile"); return RLREP_ERR_ARG; }
         if (engine == 2 && bt != 64 && bt != 32 && (t.flags & FLAG_SCALAR_C)) { rl_set_error("gemm: shape/alignment not eligible for the bf16x3 tile"); return RLREP_ERR_ARG; }
-        if (engine == 2 && bt == 32) {
-            // the 32 x 32 tile whose four waves split K (gemm_x3q.h): row-major A, K % 16 == 0, no slabs
-            if (la != LD_ROW || (t.flags & (FLAG_SCALAR_A | FLAG_SCALAR_B)) || (K & 15) || K < 32 || (lb == LD_COL && ((Cn & 7) || Cn < 8))) { rl_set_error("gemm: shape/alignment not eligible for the 32 x 32 bf16x3 tile"); return RLREP_ERR_ARG; }
-            t.splits = 1; t.kchunk = K;
-            t.tiles_c = (Cn + 31) / 32; t.ntiles = ((R + 31) / 32) * t.tiles_c; t.tile_base = 0;
-            gb.t[0] = t;
-            rc = rl_launch_gemm_lds(33, la, lb, &gb, t.ntiles, 0, (hipStream_t)stream);
-            if (rc != 0) { rl_set_error("gemm: launch failed (%d)", rc); return rc < 0 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
-            return 0;
-        }
         int pbt = 0, psp = 1, pkc = 0;
         rl_gemm_lds_plan(&t, &pbt, &psp, &pkc);
         if (bt == 64 || bt == 128) pbt = bt;
-        if (engine == 2 && bt != 64) pbt = 128;          // bf16x3: the 128-wide tile, or (bt = 64) the 64-wide one
-        if (splits > 0) { psp = splits; pkc = ((K + psp - 1) / psp + 31) / 32 * 32; psp = (K + pkc - 1) / pkc; }
+        // bt names the tile: bf16x3 (engine 2) 32 / 64 / 256, anything else its 128-wide tile; fp32 MFMA 64 / 128, anything else the planner's width
+        const GlKind kind = engine == 2 ? (bt == 32 ? GL_X3Q32 : bt == 64 ? GL_X3S64 : bt == 256 ? GL_X3W256 : GL_X3_128) : pbt == 64 ? GL_T64 : GL_T128;
+        if (!GL_KINDS[kind].split_k) { psp = 1; pkc = K; }
+        else if (splits > 0) { psp = splits; pkc = ((K + psp - 1) / psp + 31) / 32 * 32; psp = (K + pkc - 1) / pkc; }
         t.splits = psp; t.kchunk = pkc;
-        int fin = 0;
+        // the 32 x 32 tile whose four waves split K (gemm_x3q.h): row-major A, K % 16 == 0, no slabs
+        if (kind == GL_X3Q32 && !gl_x3q_can_run(&t, la, lb, t.flags, t.splits)) { rl_set_error("gemm: shape/alignment not eligible for the 32 x 32 bf16x3 tile"); return RLREP_ERR_ARG; }
         if (psp > 1) {
-            const bool bg = (t.flags & FLAG_BIASGRAD) != 0;
             if (!wsp || ws_floats < (int64_t)psp * R * (((Cn + 3) & ~3) + 1)) { rl_set_error("gemm: workspace too small for %d splits", psp); return RLREP_ERR_ARG; }
-            t.slab = wsp; t.bslab = wsp + (size_t)psp * R * ((Cn + 3) & ~3); t.fin_base = 0;
-            fin = (int)(((long long)R * ((Cn + 3) / 4) + 255) / 256) + (bg ? (R + 255) / 256 : 0);
-            if ((flags & 4) && engine == 2 && pbt == 64) {
+            t.slab = wsp; t.bslab = wsp + (size_t)psp * R * ((Cn + 3) & ~3);
+            if ((flags & 4) && GL_KINDS[kind].fin_inline) {
                 // flags & 4: the 64-wide bf16x3 tile finishes its split-K products inside the launch (FLAG_FIN_INLINE: one ticket word per output
                 // tile behind the slabs, zero between launches) -- no finishing launch
                 const size_t ticks = (size_t)((R + 63) / 64) * ((Cn + 63) / 64);
                 if (ws_floats < (int64_t)psp * R * (((Cn + 3) & ~3) + 1) + (int64_t)ticks) { rl_set_error("gemm: workspace too small for %d splits", psp); return RLREP_ERR_ARG; }
                 if (hipMemsetAsync(t.bslab, 0, ticks * sizeof(int), (hipStream_t)stream) != hipSuccess) return RLREP_ERR_HIP;
-                t.bslab += ticks; t.flags |= FLAG_FIN_INLINE; t.fin_base = 0x7fffffff; fin = 0;
+                t.bslab += ticks; t.flags |= FLAG_FIN_INLINE;
             }
         }
-        const bool wide = engine == 2 && bt == 256;          // the 256 x 128 persistent tile (gemm_x3w.h)
-        if (wide && (act == ACT_SIN || act == ACT_TANH)) { rl_set_error("gemm: the 256 x 128 tile has no sin / tanh epilogue"); return RLREP_ERR_ARG; }
-        const int er = wide ? 256 : pbt, ec = wide ? 128 : pbt;
-        t.tiles_c = (Cn + ec - 1) / ec; t.ntiles = ((R + er - 1) / er) * t.tiles_c * psp; t.tile_base = 0;
+        if (kind == GL_X3W256 && (act == ACT_SIN || act == ACT_TANH)) { rl_set_error("gemm: the 256 x 128 tile has no sin / tanh epilogue"); return RLREP_ERR_ARG; }
+        int fin = 0;
+        const int total = gl_number_tiles(&t, 1, kind, &fin);
         gb.t[0] = t;
-        rc = rl_launch_gemm_lds(wide ? 257 : engine == 2 ? (pbt == 64 ? 65 : 129) : pbt, la, lb, &gb, t.ntiles, fin, (hipStream_t)stream);
+        rc = rl_launch_gemm_lds(kind, la, lb, &gb, total, fin, (hipStream_t)stream);
     }
     if (rc != 0) { rl_set_error("gemm: launch failed (%d)", rc); return rc < 0 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
     return 0;
@@ -1070,12 +1060,13 @@ int32_t rlrep_gemm_plan(int32_t la, int32_t lb, int32_t R, int32_t Cn, int32_t K
     GemmTask t; memset(&t, 0, sizeof(t));
     t.R = R; t.Cn = Cn; t.K = K; t.lda = lda; t.ldb = ldb; t.ldc = ldc; t.epi = la == LD_COL ? EPI_DW : EPI_FWD;
     int sp = 1, kc = 0, fl = 0;
-    const int code = rl_gemm_lds_route(&t, la, lb, 0, &sp, &kc, &fl);
-    *engine = code == 0 ? 0 : (code == 257 || code == 129 || code == 65 || code == 33) ? 2 : 1;
-    if (tile) *tile = code == 0 ? 16 : code == 257 ? 256 : code == 129 ? 128 : code == 65 ? 64 : code == 33 ? 32 : code;
-    if (splits) *splits = code ? sp : 1;
-    if (kchunk) *kchunk = code ? kc : K;
-    if (scalar_sides) *scalar_sides = code ? (((fl & FLAG_SCALAR_A) ? 1 : 0) | ((fl & FLAG_SCALAR_B) ? 2 : 0) | ((fl & FLAG_SCALAR_C) ? 4 : 0)) : 0;
+    const GlKind kind = rl_gemm_lds_route(&t, la, lb, 0, &sp, &kc, &fl);
+    const bool lds = kind != GL_GEMM16;
+    *engine = GL_KINDS[kind].plan_engine;
+    if (tile) *tile = GL_KINDS[kind].rows;
+    if (splits) *splits = lds ? sp : 1;
+    if (kchunk) *kchunk = lds ? kc : K;
+    if (scalar_sides) *scalar_sides = lds ? (((fl & FLAG_SCALAR_A) ? 1 : 0) | ((fl & FLAG_SCALAR_B) ? 2 : 0) | ((fl & FLAG_SCALAR_C) ? 4 : 0)) : 0;
     return 0;
 }
 

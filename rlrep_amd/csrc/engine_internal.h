@@ -207,11 +207,11 @@ struct Builder {
     // only, so the dry sizing pass and the real pass allocate identically; a task whose pointers turn out not to be
     // 16-byte aligned simply stays on gemm16 and leaves its slab unused.
     void gemm(Program& p, int la, int lb, std::vector<GemmTask> tasks, const char* what) {
-        std::vector<GemmTask> small, big128, big64, bigx3, bigx3s, bigx3w, bigx3q;
+        std::vector<GemmTask> bucket[GL_NKINDS];          // per tile kind (gemm_lds_tiles.h); bucket[GL_GEMM16]: the small tasks
         for (auto& t : tasks) {
             int sp = 1, kc = 0, fl = 0;
             // dimensions decide the engine and the slab reservation (identical in the dry and the real pass) ...
-            if (rl_gemm_lds_route(&t, la, lb, 0, &sp, &kc, &fl)) {
+            if (rl_gemm_lds_route(&t, la, lb, 0, &sp, &kc, &fl) != GL_GEMM16) {
                 // (a task routed to the slab-free 32 x 32 tile still reserves the slabs of its 64-wide plan: pointer alignment, or a neighbour in its
                 //  stage, may send it back there)
                 { int b0 = 0, k0 = 0; if (sp == 1) rl_gemm_lds_plan(&t, &b0, &sp, &k0); }
@@ -222,33 +222,33 @@ struct Builder {
                 if (slab && !dry && ws.ok()) (void)hipMemset(slab + slab_floats, 0, ticks * sizeof(int));
                 float* bslab = (sp > 1 && t.epi == EPI_DW) ? ws.f((size_t)sp * t.R) : nullptr;
                 // ... pointer alignment can only add scalar-access flags (and take bf16x3 away)
-                const int code = rl_gemm_lds_route(&t, la, lb, dry ? 0 : rl_gemm_lds_ptr_flags(&t), &sp, &kc, &fl);
+                const GlKind kind = rl_gemm_lds_route(&t, la, lb, dry ? 0 : rl_gemm_lds_ptr_flags(&t), &sp, &kc, &fl);
                 t.splits = sp; t.kchunk = kc; t.slab = slab; t.bslab = bslab; t.flags |= fl;
-                (code == 33 ? bigx3q : code == 257 ? bigx3w : code == 129 ? bigx3 : code == 65 ? bigx3s : code == 128 ? big128 : big64).push_back(t);
+                bucket[kind].push_back(t);
                 continue;
             }
-            small.push_back(t);
+            bucket[GL_GEMM16].push_back(t);
         }
+        std::vector<GemmTask> &t64 = bucket[GL_T64], &x3s = bucket[GL_X3S64], &x3q = bucket[GL_X3Q32];
         // one launch per tile width: if some 64-wide tasks of the stage cannot take the bf16x3 tile (scalar staging), all of them stay on fp32
-        if (!big64.empty() && !bigx3s.empty()) { big64.insert(big64.end(), bigx3s.begin(), bigx3s.end()); bigx3s.clear(); }
+        if (!t64.empty() && !x3s.empty()) { t64.insert(t64.end(), x3s.begin(), x3s.end()); x3s.clear(); }
         // (a stage stays ONE launch where it can: 32 x 32 tasks beside 64-wide ones of the same stage all take the 64-wide tile -- with their split plan)
-        if (!bigx3q.empty() && (!bigx3s.empty() || !big64.empty())) {
-            for (auto t : bigx3q) {
+        if (!x3q.empty() && (!x3s.empty() || !t64.empty())) {
+            for (auto t : x3q) {
                 int sp = 1, kc = 0, bt0 = 0;
                 rl_gemm_lds_plan(&t, &bt0, &sp, &kc);
                 t.splits = sp; t.kchunk = kc;
-                (big64.empty() ? bigx3s : big64).push_back(t);
+                (t64.empty() ? x3s : t64).push_back(t);
             }
-            bigx3q.clear();
+            x3q.clear();
         }
-        if (!bigx3q.empty() || !bigx3w.empty() || !bigx3.empty() || !big128.empty() || !big64.empty() || !bigx3s.empty()) chain_flush();
-        if (!bigx3q.empty()) gemm_lds_stage(p, la, lb, 33, bigx3q, what);
-        if (!bigx3w.empty()) gemm_lds_stage(p, la, lb, 257, bigx3w, what);
-        if (!bigx3.empty()) gemm_lds_stage(p, la, lb, 129, bigx3, what);
-        if (!big128.empty()) gemm_lds_stage(p, la, lb, 128, big128, what);
-        if (!bigx3s.empty()) gemm_lds_stage(p, la, lb, 65, bigx3s, what);
-        if (!big64.empty()) gemm_lds_stage(p, la, lb, 64, big64, what);
-        if (!small.empty()) gemm_small(p, la, lb, small, what);
+        // the stages a GEMM stage becomes, in this order; the small tasks follow them
+        static constexpr GlKind order[] = {GL_X3Q32, GL_X3W256, GL_X3_128, GL_T128, GL_X3S64, GL_T64};
+        bool any = false;
+        for (GlKind k : order) any = any || !bucket[k].empty();
+        if (any) chain_flush();
+        for (GlKind k : order) if (!bucket[k].empty()) gemm_lds_stage(p, la, lb, k, bucket[k], what);
+        if (!bucket[GL_GEMM16].empty()) gemm_small(p, la, lb, bucket[GL_GEMM16], what);
     }
     // fold_group >= 0 (set by an agent's builder around its weight-gradient stage): the split-K weight-gradient tasks built now leave the sum of
     // their partial slabs to that group's optimizer launch (AdamTask::Slab) -- no finishing blocks for them, and when no task of the stage
@@ -278,29 +278,20 @@ struct Builder {
         t.flags |= FLAG_FIN_IN_ADAM;
         return true;
     }
-    void gemm_lds_stage(Program& p, int la, int lb, int bt, std::vector<GemmTask> tasks, const char* what) {
-        int base = 0, fin = 0;
-        const int edge = bt == 129 ? 128 : bt == 65 ? 64 : bt == 33 ? 32 : bt;       // 129 / 65 / 33: the 128- / 64- / 32-wide tile on the bf16 pipe
-        const int er = bt == 257 ? 256 : edge, ec = bt == 257 ? 128 : edge;     // 257: 256 rows x 128 columns (gemm_x3w.h)
-        for (auto& t : tasks) {
-            t.tiles_c = (t.Cn + ec - 1) / ec;
-            t.ntiles = ((t.R + er - 1) / er) * t.tiles_c * t.splits; t.tile_base = base; base += t.ntiles;
-            if (t.splits > 1 && fold_fin(t)) t.fin_base = 0x7fffffff;       // (no finishing block ever matches it)
-            // (OPT-IN, RLREP_ENABLE=fin_inline: the last split workgroup of a tile finishes it inside the launch.  Bit-identical and one launch less per
-            //  split stage -- and 1.1x (spedersac) to 3.5x (ctrlsac F = 2048) SLOWER per train(): the slabs have to go through to memory and come back past
-            //  the L2s, docs/history/r06.md)
-            else if (t.splits > 1 && bt == 65 && rl_opt("fin_inline")) { t.flags |= FLAG_FIN_INLINE; t.fin_base = 0x7fffffff; }
-            else if (t.splits > 1) {
-                const bool bias = t.epi == EPI_DW && (t.flags & FLAG_BIASGRAD);
-                t.fin_base = fin;
-                fin += (int)(((long long)t.R * ((t.Cn + 3) / 4) + 255) / 256) + (bias ? (t.R + 255) / 256 : 0);
-            }
-        }
+    void gemm_lds_stage(Program& p, int la, int lb, GlKind kind, std::vector<GemmTask> tasks, const char* what) {
+        // split tasks that need no finishing block: fold_fin flags those whose slabs the optimizer launch sums, and
+        // (OPT-IN, RLREP_ENABLE=fin_inline: the last split workgroup of a tile finishes it inside the launch.  Bit-identical and one launch less per
+        //  split stage -- and 1.1x (spedersac) to 3.5x (ctrlsac F = 2048) SLOWER per train(): the slabs have to go through to memory and come back past
+        //  the L2s, docs/history/r06.md)
+        for (auto& t : tasks)
+            if (t.splits > 1 && !fold_fin(t) && GL_KINDS[kind].fin_inline && rl_opt("fin_inline")) t.flags |= FLAG_FIN_INLINE;
+        int fin = 0;
+        const int base = gl_number_tiles(tasks.data(), (int)tasks.size(), kind, &fin);
         GemmBatch gb; memset(&gb, 0, sizeof(gb));
         gb.ntasks = (int)tasks.size();
         for (size_t q = 0; q < tasks.size(); ++q) gb.t[q] = tasks[q];
-        p.stages.push_back({[=](hipStream_t st) { return rl_launch_gemm_lds(bt, la, lb, &gb, base, fin, st); }, what});
-        tag_gemms(p, (bt == 257 || bt == 129 || bt == 65 || bt == 33) ? RLREP_ENGINE_X3 : bt == 128 ? RLREP_ENGINE_LDS128 : RLREP_ENGINE_LDS64, tasks);
+        p.stages.push_back({[=](hipStream_t st) { return rl_launch_gemm_lds(kind, la, lb, &gb, base, fin, st); }, what});
+        tag_gemms(p, GL_KINDS[kind].engine_tag, tasks);
     }
     void gemm_small(Program& p, int la, int lb, std::vector<GemmTask> tasks, const char* what) {
         if (chain_take(p, la, lb, tasks, what)) return;
@@ -345,7 +336,7 @@ struct Builder {
     // Two INDEPENDENT stages of different tile forms -- d1: row-major x k-major products (the dX form), d2: k-major x k-major ones (the
     // weight-gradient form) -- as ONE launch (gemm16_duo_kernel): a dependent launch less.  Falls back to the two stages (d1 first) when a
     // task is routed to the LDS-tiled engines, carries a fused short product, or the table does not fit.  RLREP_DISABLE=duo: always the two stages.
-    bool routes_small(const GemmTask& t, int la, int lb) { int sp = 1, kc = 0, fl = 0; GemmTask c = t; return !rl_gemm_lds_route(&c, la, lb, 0, &sp, &kc, &fl); }
+    bool routes_small(const GemmTask& t, int la, int lb) { int sp = 1, kc = 0, fl = 0; GemmTask c = t; return rl_gemm_lds_route(&c, la, lb, 0, &sp, &kc, &fl) == GL_GEMM16; }
     void gemm_duo(Program& p, std::vector<GemmTask> d1, std::vector<GemmTask> d2, const char* w1, const char* w2, const char* what) {
         bool ok = !rl_off("duo") && !chain_prog && !d1.empty() && !d2.empty() && d1.size() + d2.size() <= GEMM_MAX_TASKS;
         for (auto& t : d1) ok = ok && routes_small(t, LD_ROW, LD_COL) && !(t.flags & (FLAG_PRE | FLAG_DYN_EPS | FLAG_DYN_EPS2 | FLAG_DYN_EPS3));

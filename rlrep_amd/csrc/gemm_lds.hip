@@ -695,19 +695,14 @@ static int launch_x3w(int la, int lb, int total_tiles, hipStream_t st, const Gem
     return (int)hipGetLastError();
 }
 
-static bool x3s_unaligned_ok(const GemmTask* t) { return t->R >= 4 && t->Cn >= 4 && t->K >= 4; }       // (the pulled-back tail load needs four elements to exist)
 static int launch_x3s(int la, int lb, dim3 g, hipStream_t st, const GemmBatch& gb, const int* dir) {
     // one instantiation per launch: the any-alignment loaders as soon as ONE task of the stage has an operand that is not 16-byte regular
     bool unal = false;
-    for (int q = 0; q < gb.ntasks; ++q) if (gb.t[q].flags & (FLAG_SCALAR_A | FLAG_SCALAR_B)) { unal = true; if (!x3s_unaligned_ok(&gb.t[q])) return -2; }
-    if (unal) {
-        if (la == LD_ROW && lb == LD_ROW) GL_LAUNCH(gemm_x3s_kernel, (LD_ROW, LD_ROW, 2), g, 256, st, GL_DIR_ARGS(dir), gb);
-        else if (la == LD_ROW && lb == LD_COL) GL_LAUNCH(gemm_x3s_kernel, (LD_ROW, LD_COL, 2), g, 256, st, GL_DIR_ARGS(dir), gb);
-        else if (la == LD_COL && lb == LD_COL) GL_LAUNCH(gemm_x3s_kernel, (LD_COL, LD_COL, 2), g, 256, st, GL_DIR_ARGS(dir), gb);
-        else return -1;
-        return (int)hipGetLastError();
-    }
-    if (la == LD_ROW && lb == LD_ROW) GL_LAUNCH(gemm_x3s_kernel, (LD_ROW, LD_ROW, 1), g, 256, st, GL_DIR_ARGS(dir), gb);
+    for (int q = 0; q < gb.ntasks; ++q) if (gb.t[q].flags & (FLAG_SCALAR_A | FLAG_SCALAR_B)) { unal = true; if (!gl_x3s_unaligned_can_run(&gb.t[q])) return -2; }
+    if (unal && la == LD_ROW && lb == LD_ROW) GL_LAUNCH(gemm_x3s_kernel, (LD_ROW, LD_ROW, 2), g, 256, st, GL_DIR_ARGS(dir), gb);
+    else if (unal && la == LD_ROW && lb == LD_COL) GL_LAUNCH(gemm_x3s_kernel, (LD_ROW, LD_COL, 2), g, 256, st, GL_DIR_ARGS(dir), gb);
+    else if (unal && la == LD_COL && lb == LD_COL) GL_LAUNCH(gemm_x3s_kernel, (LD_COL, LD_COL, 2), g, 256, st, GL_DIR_ARGS(dir), gb);
+    else if (la == LD_ROW && lb == LD_ROW) GL_LAUNCH(gemm_x3s_kernel, (LD_ROW, LD_ROW, 1), g, 256, st, GL_DIR_ARGS(dir), gb);
     else if (la == LD_ROW && lb == LD_COL) GL_LAUNCH(gemm_x3s_kernel, (LD_ROW, LD_COL, 1), g, 256, st, GL_DIR_ARGS(dir), gb);
     else if (la == LD_COL && lb == LD_COL) GL_LAUNCH(gemm_x3s_kernel, (LD_COL, LD_COL, 1), g, 256, st, GL_DIR_ARGS(dir), gb);
     else return -1;
@@ -716,30 +711,33 @@ static int launch_x3s(int la, int lb, dim3 g, hipStream_t st, const GemmBatch& g
 
 static int launch_x3q(int la, int lb, dim3 g, hipStream_t st, const GemmBatch& gb, const int* dir) {
     if (la != LD_ROW) return -1;
-    for (int q = 0; q < gb.ntasks; ++q) {
-        const GemmTask& t = gb.t[q];
-        if ((t.flags & (FLAG_SCALAR_A | FLAG_SCALAR_B)) || (t.K & 15) || t.K < 32 || t.splits != 1 || (lb == LD_COL && ((t.Cn & 7) || t.Cn < 8))) return -2;
-    }
+    for (int q = 0; q < gb.ntasks; ++q) if (!gl_x3q_can_run(&gb.t[q], la, lb, gb.t[q].flags, gb.t[q].splits)) return -2;
     if (lb == LD_ROW) GL_LAUNCH(gemm_x3q_kernel, (LD_ROW), g, 256, st, GL_DIR_ARGS(dir), gb);
     else if (lb == LD_COL) GL_LAUNCH(gemm_x3q_kernel, (LD_COL), g, 256, st, GL_DIR_ARGS(dir), gb);
     else return -1;
     return (int)hipGetLastError();
 }
 
-// bt: 64 / 128 = fp32-MFMA tiles; 129 = the 128-wide tile on the bf16 pipe (bf16x3); 65 = the 64-wide tile on the bf16 pipe; 257 = the 256 x 128 tile on the
-// bf16 pipe (persistent workgroups: gemm_x3w.h); 33 = the 32 x 32 tile on the bf16 pipe whose four waves split K (gemm_x3q.h)
-extern "C" int rl_launch_gemm_lds(int bt, int la, int lb, const GemmBatch* gb, int total_tiles, int fin_blocks, hipStream_t st) {
+// one launch of tile kind `kind` (gemm_lds_tiles.h) over a table numbered by gl_number_tiles, and its finishing launch where tasks keep finishing blocks
+extern "C" int rl_launch_gemm_lds(GlKind kind, int la, int lb, const GemmBatch* gb, int total_tiles, int fin_blocks, hipStream_t st) {
     const RlGrp* gr = rl_grp_active();
-    if (gr && bt == 257) return RL_GRP_UNSUPPORTED;          // (the persistent tile walks its tiles by grid stride: no group form)
+    if (gr && !GL_KINDS[kind].group_form) return RL_GRP_UNSUPPORTED;
     if (total_tiles <= 0) return 0;
     int dir[GEMM_MAX_TASKS], fdir[GEMM_MAX_TASKS];
     for (int q = 0; q < GEMM_MAX_TASKS; ++q) {
         dir[q] = q < gb->ntasks ? gb->t[q].tile_base : 0x7fffffff;
         fdir[q] = (q < gb->ntasks && gb->t[q].splits > 1) ? gb->t[q].fin_base : 0x7fffffff;
     }
-    int rc = bt == 33 ? launch_x3q(la, lb, dim3(total_tiles), st, *gb, dir)
-           : bt == 257 ? launch_x3w(la, lb, total_tiles, st, *gb, dir) : bt == 65 ? launch_x3s(la, lb, dim3(total_tiles), st, *gb, dir) : bt == 129 ? launch_x3(la, lb, dim3(total_tiles), st, *gb, dir)
-           : bt == 128 ? launch_bt<128>(la, lb, dim3(total_tiles), st, *gb, dir) : launch_bt<64>(la, lb, dim3(total_tiles), st, *gb, dir);
+    int rc = -1;
+    switch (kind) {
+    case GL_X3Q32: rc = launch_x3q(la, lb, dim3(total_tiles), st, *gb, dir); break;
+    case GL_X3W256: rc = launch_x3w(la, lb, total_tiles, st, *gb, dir); break;
+    case GL_X3S64: rc = launch_x3s(la, lb, dim3(total_tiles), st, *gb, dir); break;
+    case GL_X3_128: rc = launch_x3(la, lb, dim3(total_tiles), st, *gb, dir); break;
+    case GL_T128: rc = launch_bt<128>(la, lb, dim3(total_tiles), st, *gb, dir); break;
+    case GL_T64: rc = launch_bt<64>(la, lb, dim3(total_tiles), st, *gb, dir); break;
+    default: break;          // (GL_GEMM16 is not a tile of this engine)
+    }
     if (rc != 0) return rc;
     if (fin_blocks > 0) {
         if (gr) hipLaunchKernelGGL(gemm_lds_fin_kernel_grp, dim3(fin_blocks, gr->grid_y), dim3(256), 0, st, GL_DIR_ARGS(fdir), *gb, gr->stride, gr->live);
@@ -760,15 +758,10 @@ extern "C" int rl_gemm_lds_dim_flags(const GemmTask* t, int la, int lb) {
     if (t->epi == EPI_FWD && t->act == ACT_SIN && (t->ldout2 & 3)) f |= FLAG_SCALAR_C;
     return f;
 }
-extern "C" int rl_gemm_lds_align_ok(const GemmTask* t, int la, int lb) {
-    if (t->epi != EPI_FWD && t->epi != EPI_DX && t->epi != EPI_DW) return 0;
-    (void)la; (void)lb;
-    return 1;
-}
 // Is the task large enough to be worth leaving the latency-tuned 16-row engine?  Judged by dimensions alone, so that the
 // dry sizing pass and the real pass of the program builder agree.
-extern "C" int rl_gemm_lds_dims_ok(const GemmTask* t, int la, int lb) {
-    if (!rl_gemm_lds_align_ok(t, la, lb) || t->K < 64) return 0;
+extern "C" int rl_gemm_lds_dims_ok(const GemmTask* t) {
+    if ((t->epi != EPI_FWD && t->epi != EPI_DX && t->epi != EPI_DW) || t->K < 64) return 0;
     return 2.0 * t->R * t->Cn * t->K >= 2.0e8;
 }
 static bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
@@ -784,7 +777,6 @@ extern "C" int rl_gemm_lds_ptr_flags(const GemmTask* t) {
     if (t->epi == EPI_DX && t->r1u && !al16(t->r1v)) f |= FLAG_SCALAR_C;
     return f;
 }
-extern "C" int rl_gemm_lds_ptrs_ok(const GemmTask* t) { (void)t; return 1; }
 // tile edge and split count for a task (dimensions only).  128-wide tiles run two workgroups per CU, so a grid that
 // already has >= 256 of them is left alone and a smaller one is split along K towards 512 workgroups (each split keeps
 // at least eight 32-deep slices); outputs too small for that use 64-wide tiles under the same rule.
@@ -807,12 +799,12 @@ extern "C" void rl_gemm_lds_plan(const GemmTask* t, int* bt, int* splits, int* k
 }
 
 // The program builder's routing decision for one task, from dimensions alone (pointer alignment may add scalar flags
-// later, which also rules out bf16x3): returns 0 = stays on the 16-row engine, 64 / 128 = fp32-MFMA tile, 129 = the 128-wide
-// tile on the bf16 pipe, 257 = the 256 x 128 persistent tile on the bf16 pipe, 65 = the 64-wide one.  Products of >= 2 GFLOP with a row-major A (forward, dX: diffsrsac's 202-GFLOP nabla-mu head) take
+// later, which also rules out bf16x3): the tile kind (gemm_lds_tiles.h), GL_GEMM16 = stays on the 16-row engine.
+// Products of >= 2 GFLOP with a row-major A (forward, dX: diffsrsac's 202-GFLOP nabla-mu head) take
 // bf16x3: 159 / 137 TF against 110 on the fp32 pipe; the k-major/k-major weight-gradient form stays on fp32 MFMA (107 vs 116).
-extern "C" int rl_gemm_lds_route(const GemmTask* t, int la, int lb, int extra_flags, int* splits, int* kchunk, int* flags) {
+extern "C" GlKind rl_gemm_lds_route(const GemmTask* t, int la, int lb, int extra_flags, int* splits, int* kchunk, int* flags) {
     const bool combo = (la == LD_ROW && lb == LD_ROW) || (la == LD_ROW && lb == LD_COL) || (la == LD_COL && lb == LD_COL);
-    if (!combo || rl_off("gemm_lds") || !rl_gemm_lds_dims_ok(t, la, lb)) return 0;
+    if (!combo || rl_off("gemm_lds") || !rl_gemm_lds_dims_ok(t)) return GL_GEMM16;
     int bt = 0;
     rl_gemm_lds_plan(t, &bt, splits, kchunk);
     *flags = rl_gemm_lds_dim_flags(t, la, lb) | extra_flags;
@@ -824,8 +816,8 @@ extern "C" int rl_gemm_lds_route(const GemmTask* t, int la, int lb, int extra_fl
         // (RLREP_DISABLE=x3w keeps the 128 x 128 tile)
         const long long wt = (long long)((t->R + 255) / 256) * ((t->Cn + 127) / 128) * *splits;
         const bool fills = wt >= 256 && (double)wt / (double)(((wt + 255) / 256) * 256) >= 0.85;
-        if (fills && x3w_epilogue_ok(t) && !rl_off("x3w")) return 257;
-        return 129;
+        if (fills && x3w_epilogue_ok(t) && !rl_off("x3w")) return GL_X3W256;
+        return GL_X3_128;
     }
     // 64-wide tiles: on the bf16 pipe too when both operands allow 16-byte staging (gemm_x3s_kernel); RLREP_DISABLE=x3s keeps the fp32 tile
     // (the program builder keeps a STAGE on one engine: a stage whose tasks would be split between this tile and the fp32 one becomes two dependent
@@ -836,14 +828,14 @@ extern "C" int rl_gemm_lds_route(const GemmTask* t, int la, int lb, int extra_fl
     // few rows, long inner dimension (ctrlsac's M = 256 layers at main.py's dimensions): where the 64-wide tile would cut K into slabs and a
     // 32 x 32 tiling has enough workgroups without them, the tile whose four waves split K among themselves (gemm_x3q.h): no slab, no finishing
     // launch.  RLREP_DISABLE=x3q keeps the 64-wide tile.
-    if (bt == 64 && *splits > 1 && la == LD_ROW && !rl_off("x3") && !rl_off("x3q") && !(*flags & (FLAG_SCALAR_A | FLAG_SCALAR_B)) &&
-        (t->K & 15) == 0 && t->K >= 512 && (lb == LD_ROW || (t->Cn & 7) == 0) && t->Cn >= 32 && t->R <= 256 &&
+    if (bt == 64 && *splits > 1 && !rl_off("x3") && !rl_off("x3q") && gl_x3q_can_run(t, la, lb, *flags, 1) &&
+        t->K >= 512 && t->Cn >= 32 && t->R <= 256 &&
         (long long)((t->R + 31) / 32) * ((t->Cn + 31) / 32) >= 192) {          // (R <= 256: spedersac's M = 1024 critic layers measured 0.8 % slower on it)
         *splits = 1; *kchunk = t->K;
-        return 33;
+        return GL_X3Q32;
     }
     if (bt == 64 && !rl_off("x3") && !rl_off("x3s") &&
-        (!(*flags & (FLAG_SCALAR_A | FLAG_SCALAR_B)) || (x3s_unaligned_ok(t) && !rl_off("x3s_unaligned")))) return 65;
-    return bt;
+        (!(*flags & (FLAG_SCALAR_A | FLAG_SCALAR_B)) || (gl_x3s_unaligned_can_run(t) && !rl_off("x3s_unaligned")))) return GL_X3S64;
+    return bt == 128 ? GL_T128 : GL_T64;
 }
 

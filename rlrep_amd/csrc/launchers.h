@@ -9,6 +9,7 @@
 #include <stdint.h>
 #include "common.h"
 #include "kparams.h"
+#include "gemm_lds_tiles.h"
 #include "group.h"
 #include "group_env.h"
 #include "rowprog.h"
@@ -27,13 +28,11 @@ void rl_gemm16_read_env();                            // RLREP_DISABLE=gemm16_fa
 int rl_launch_gemm16(int la, int lb, int nf, const GemmBatch* gb, int total_tiles, hipStream_t st);
 int rl_launch_gemm16_duo(int split, int nf2, const GemmBatch* gb, int total_tiles, hipStream_t st);
 // ---- gemm_lds.hip ----
-int rl_launch_gemm_lds(int bt, int la, int lb, const GemmBatch* gb, int total_tiles, int fin_blocks, hipStream_t st);
-int rl_gemm_lds_align_ok(const GemmTask* t, int la, int lb);
-int rl_gemm_lds_dims_ok(const GemmTask* t, int la, int lb);
-int rl_gemm_lds_ptrs_ok(const GemmTask* t);
+int rl_launch_gemm_lds(GlKind kind, int la, int lb, const GemmBatch* gb, int total_tiles, int fin_blocks, hipStream_t st);
+int rl_gemm_lds_dims_ok(const GemmTask* t);
 int rl_gemm_lds_dim_flags(const GemmTask* t, int la, int lb);
 int rl_gemm_lds_ptr_flags(const GemmTask* t);
-int rl_gemm_lds_route(const GemmTask* t, int la, int lb, int extra_flags, int* splits, int* kchunk, int* flags);
+GlKind rl_gemm_lds_route(const GemmTask* t, int la, int lb, int extra_flags, int* splits, int* kchunk, int* flags);
 void rl_gemm_lds_plan(const GemmTask* t, int* bt, int* splits, int* kchunk);
 // ---- noisecritic.hip ----
 int rl_launch_nc_fwd(const NcFwdBatch* nb, int total_tiles, int g2, hipStream_t st);
