@@ -61,7 +61,9 @@ typedef enum {
     RLREP_ALG_DIFFSRSAC = 4
 } rlrep_alg;
 
-/* Network dimensions (mirrors the reference constructors' dimension kwargs). */
+/* Network dimensions (mirrors the reference constructors' dimension kwargs).
+ * vlsac: feature_dim is any positive multiple of 4 (every noise-critic kernel moves 16-byte rows) and num_noise is 20; no upper bound on
+ * feature_dim comes from the kernels -- what rlrep_layout can size is accepted -- and the suite runs widths up to 1024 against the oracle. */
 typedef struct {
     int32_t alg;               /* rlrep_alg */
     int32_t state_dim;         /* S */

@@ -646,7 +646,10 @@ void build_vlsac(Builder& b, rlrep_agent* ag) {
             nb.t[q] = t;
         }
         const int total = base_tile;
-        p.stages.push_back({[=](hipStream_t st) { return rl_launch_nc_fwd(&nb, total, g2, st); }, what});
+        // the form of the fp32 forward is decided here, once (RLREP_ENABLE is not read on a launch path); the K-chunked one runs under a name of its own
+        const int chunked = (engine == 0 && rl_nc_fwd_chunked(F, g2)) ? 1 : 0;
+        if (chunked) { ag->stage_names.push_back(std::string(what) + " [K-chunked]"); what = ag->stage_names.back().c_str(); }
+        p.stages.push_back({[=](hipStream_t st) { return rl_launch_nc_fwd(&nb, total, g2, chunked, st); }, what});
         {   // per head: [B*N, F] x [F, H]; reads mean / log_std / W, writes the noise-row mean (and U where the head keeps it)
             double by = 0.0;
             for (auto& t : tasks) by += 4.0 * (2.0 * (double)B * F + (double)F * H + (double)B * H + (t.U ? (double)B * N * H : 0.0));

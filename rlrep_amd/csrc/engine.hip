@@ -170,7 +170,6 @@ bool check_dims(const rlrep_dims* d) {
     if (d->alg == RLREP_ALG_VLSAC) {
         if (d->num_noise != 4 * NC_NF_HOST) { rl_set_error("vlsac: num_noise must be %d", 4 * NC_NF_HOST); return false; }
         if (d->feature_dim <= 0 || d->vae_hidden_dim <= 0 || (d->feature_dim & 3)) { rl_set_error("vlsac: feature_dim must be a positive multiple of 4"); return false; }
-        if ((size_t)(16 + d->num_noise) * (((d->feature_dim + 15) & ~15) + 16) * 4 > 64 * 1024) { rl_set_error("vlsac: feature_dim too large for the LDS-resident noise tables"); return false; }
     }
     if (d->alg == RLREP_ALG_CTRLSAC || d->alg == RLREP_ALG_SPEDERSAC || d->alg == RLREP_ALG_DIFFSRSAC) {
         if (d->feature_dim <= 0 || d->phi_hidden_dim <= 0 || d->mu_hidden_dim <= 0 || d->phi_hidden_depth < 0 || d->mu_hidden_depth < 0 ||

@@ -35,7 +35,8 @@ int rl_gemm_lds_ptr_flags(const GemmTask* t);
 GlKind rl_gemm_lds_route(const GemmTask* t, int la, int lb, int extra_flags, int* splits, int* kchunk, int* flags);
 void rl_gemm_lds_plan(const GemmTask* t, int* bt, int* splits, int* kchunk);
 // ---- noisecritic.hip ----
-int rl_launch_nc_fwd(const NcFwdBatch* nb, int total_tiles, int g2, hipStream_t st);
+int rl_launch_nc_fwd(const NcFwdBatch* nb, int total_tiles, int g2, int chunked, hipStream_t st);
+int rl_nc_fwd_chunked(int F, int g2);
 int rl_launch_nc_dx(const NcDxTask* t, hipStream_t st);
 int rl_launch_nc_dw(const NcDwBatch* nb, int total_tiles, hipStream_t st);
 int rl_nc_init();

@@ -56,141 +56,26 @@ __device__ __forceinline__ void ld4(const float* p, bool vec, int valid, float (
 // ------------------------------------------------------------------------------------------------
 // NW waves per workgroup = 16 * NW hidden units: the tables depend on the batch rows only, so a wider workgroup stages them
 // once for more columns (NW = 8: half the table traffic and staging time of NW = 4 at the same waves per SIMD)
+//
+// K-chunked form (CHUNK): the whole-table form keeps all Fp columns of the (2 RB + 20)-row mean / sigma / noise table in LDS, which fits the
+// 64 KB a workgroup may take without costing workgroups per CU only up to F = 432 (G2 = 2: 8 batch rows).  With CHUNK the table is staged NC_CW = 256 columns
+// at a time -- stage chunk c, barrier, the K loop over that chunk into the same accumulators, barrier, stage chunk c + 1 -- so any F runs in
+// (2 RB + 20) x (256 + 16) x 4 bytes: 30.5 / 39.2 / 56.6 KB for G2 = 1 / 2 / 4.  256 because that is what one wave-wide 16-byte load moves:
+// a chunk row is ONE load per wave, the staging loop below is unchanged (one trip per chunk) and its row stride 256 + 16 is the stride the
+// whole-table form has at F = 256, whose bank behaviour is the measured one.  The accumulators see k in the same order as in the whole-table
+// form, so the two forms agree bit for bit; the W-fragment prefetch runs on across chunk boundaries (its bound is the row end Fp, not the chunk
+// end).  A separate instantiation (nc_fwd_chunk_kernel) of one body (nc_fwd_body.h, included as the group forms of the GEMM kernels include
+// theirs: a shared inline function changed the whole-table kernels' schedules): those kernels are instruction for instruction what they were.
+#define NC_CW 256
 template <int G2, int NW>
 __global__ __launch_bounds__(64 * NW) void nc_fwd_kernel(NcFwdBatch nb) {
-    const int bid = blockIdx.x;
-    NCT(0); NCT(4);
-    int ti = 0;
-#pragma unroll
-    for (int q = 1; q < NC_MAX_TASKS; ++q) if (q < nb.ntasks && bid >= nb.t[q].tile_base) ti = q;
-    const NcFwdTask& t = nb.t[ti];
-    const int local = bid - t.tile_base;
-    const int tb = local / t.tiles_h, th = local - tb * t.tiles_h;
-    const int RB = 4 * G2;
-    const int b0 = tb * RB, n0 = th * (16 * NW);
-    const int F = t.F, H = t.H, N = t.N;
-    const int Fp = (F + 15) & ~15;
-    const int LDS_LD = Fp + 16;
-    float* mu_s = nc_smem;                     // [RB][LDS_LD]
-    float* sg_s = mu_s + RB * LDS_LD;          // [RB][LDS_LD]
-    float* nz_s = sg_s + RB * LDS_LD;          // [N][LDS_LD]
-
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int m16 = lane & 15, kq = lane >> 4;
-    const int bp = m16 >> 2, nn = m16 & 3;
-    const int col = n0 + 16 * w + m16;
-    const bool colok = col < H;
-    const bool vecW = ((F & 3) == 0) && ((((uintptr_t)t.W) & 15) == 0);
-    const float* wrow = t.W + (size_t)(colok ? col : 0) * F;
-
-    // first W fragment is in flight while the tables are staged
-    float wv[4], wn[4];
-    {
-        const int k0 = 4 * kq;
-        const int valid = colok ? max(0, min(4, F - k0)) : 0;
-        ld4(wrow + k0, vecW, valid, wv);
-    }
-    // Table staging: one wave-wide 16-byte load moves a whole 256-float row; every wave issues ALL of its
-    // row loads back to back (fixed trip count, fully unrolled) so their L2 latencies overlap instead of
-    // serialising (the element-wise loop this replaces cost 7.7 us of a 40 us launch).
-    {
-        constexpr int NROWS = 2 * RB + 4 * NC_NF;          // mean rows, sigma rows, noise rows (N = 20)
-        constexpr int SLOTS = (NROWS + NW - 1) / NW;
-        for (int cb = 0; cb < Fp; cb += 256) {
-            const int k = cb + 4 * lane;
-            f32x4 v[SLOTS];
-#pragma unroll
-            for (int q = 0; q < SLOTS; ++q) {
-                const int row = NW * q + w;
-                v[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (row < NROWS && k < F) {
-                    if (row < 2 * RB) {
-                        const int rr = row < RB ? row : row - RB;
-                        const float* src = (row < RB ? t.mean : t.lstd) + (size_t)(b0 + rr) * t.ld_ml + k;
-                        if (b0 + rr < t.B) v[q] = *reinterpret_cast<const f32x4*>(src);
-                    } else {
-                        v[q] = *reinterpret_cast<const f32x4*>(t.noise + (size_t)(row - 2 * RB) * F + k);
-                    }
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < SLOTS; ++q) {
-                const int row = NW * q + w;
-                if (row >= NROWS || k >= Fp) continue;
-                f32x4 x = v[q];
-                if (row >= RB && row < 2 * RB) {
-                    const int rr = row - RB;
-                    const bool ok = (b0 + rr < t.B) && (k < F);
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) x[s] = ok ? expf(clamp_lstd(x[s])) : 0.f;
-                    if (t.sigma_out && th == 0 && ok) *reinterpret_cast<f32x4*>(t.sigma_out + (size_t)(b0 + rr) * F + k) = x;
-                }
-                float* dst = (row < RB ? mu_s + row * LDS_LD : row < 2 * RB ? sg_s + (row - RB) * LDS_LD : nz_s + (row - 2 * RB) * LDS_LD) + k;
-                *reinterpret_cast<f32x4*>(dst) = x;
-            }
-        }
-    }
-    __syncthreads();
-    NCT(1);
-
-    f32x4 acc[G2][NC_NF];
-#pragma unroll
-    for (int g = 0; g < G2; ++g)
-#pragma unroll
-        for (int f = 0; f < NC_NF; ++f) acc[g][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    // (A variant with two named register sets, which issued the LDS table reads and the W fragment of chunk c+1 before the MFMAs
-    // of chunk c, measured the same 47.8k cycles per workgroup for this loop -- tools/exp/nc_timeline.py: staging 4.9k, loop
-    // 48.2k, epilogue 3.6k cycles at 2.1 GHz.  The loop runs at 85 % of 32 cycles per MFMA, the rate tools/exp/mfma_peak.hip
-    // measures for four waves per SIMD: 126 of 157 TF.)
-    for (int kb = 0; kb < Fp; kb += 16) {
-        const int k0 = kb + 4 * kq;
-        {   // prefetch the next W fragment
-            const int k1 = k0 + 16;
-            const int valid = colok ? max(0, min(4, F - k1)) : 0;
-            if (kb + 16 < Fp) ld4(wrow + k1, vecW, valid, wn);
-        }
-        f32x4 mu4[G2], sg4[G2], nz4[NC_NF];
-#pragma unroll
-        for (int g = 0; g < G2; ++g) {
-            mu4[g] = *reinterpret_cast<const f32x4*>(&mu_s[(4 * g + bp) * LDS_LD + k0]);
-            sg4[g] = *reinterpret_cast<const f32x4*>(&sg_s[(4 * g + bp) * LDS_LD + k0]);
-        }
-#pragma unroll
-        for (int f = 0; f < NC_NF; ++f) nz4[f] = *reinterpret_cast<const f32x4*>(&nz_s[(4 * f + nn) * LDS_LD + k0]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int g = 0; g < G2; ++g)
-#pragma unroll
-                for (int f = 0; f < NC_NF; ++f)
-                    acc[g][f] = __builtin_amdgcn_mfma_f32_16x16x4f32(fmaf(sg4[g][s], nz4[f][s], mu4[g][s]), wv[s], acc[g][f], 0, 0, 0);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) wv[s] = wn[s];
-    }
-
-    NCT(2);
-    if (!colok) return;
-    const float bj = t.bias[col];
-    const float invN = 1.0f / (float)N;
-#pragma unroll
-    for (int g = 0; g < G2; ++g) {
-        const int b = b0 + 4 * g + (lane >> 4);
-        if (b >= t.B) continue;
-        float sum = 0.f;
-#pragma unroll
-        for (int f = 0; f < NC_NF; ++f)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float y = elu_fast(acc[g][f][r] + bj);
-                sum += y;
-#ifndef RL_NC_NOU
-                if (t.U) t.U[((size_t)b * N + 4 * f + r) * H + col] = y;
-#endif
-            }
-        t.Hm[(size_t)b * H + col] = sum * invN;
-    }
-    NCT(3); NCT(5);
+    constexpr bool CHUNK = false;
+#include "nc_fwd_body.h"
+}
+template <int G2, int NW>
+__global__ __launch_bounds__(64 * NW) void nc_fwd_chunk_kernel(NcFwdBatch nb) {
+    constexpr bool CHUNK = true;
+#include "nc_fwd_body.h"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1691,7 +1576,16 @@ extern "C" void rl_nc_fwd_plan(const NcFwdTask* tasks, int ntasks, int* engine, 
     *cols = rl_nc_fwd_cols();
     *g2 = ((long long)ntasks * ((B + 3) / 4) * ((H + 63) / 64) <= 2048) ? 1 : 2;
 }
-extern "C" int rl_launch_nc_fwd(const NcFwdBatch* nb, int total_tiles, int g2, hipStream_t st) {
+// form of the fp32 forward: 1 = K-chunked tables (nc_fwd_chunk_kernel), 0 = the whole table in LDS.  Decided ONCE, where the stage is built (the
+// program builder passes it to the launcher and names the stage by it; rl_opt is not read on a launch path).  The whole table is kept for
+// exactly the widths it has always served: those whose table of 8 batch rows (g2 = 2, the rule rlrep_layout used to refuse wider ones by) fits
+// 64 KB, F <= 432 -- so a width is served by ONE form whatever g2 the planner picks for the batch -- and never past 64 KB for the g2 at hand.
+// RLREP_ENABLE=nc_fwd_chunk forces the chunked form at widths that fit (the bit-identity test: both forms at one width).
+extern "C" int rl_nc_fwd_chunked(int F, int g2) {
+    const int Fp = (F + 15) & ~15;
+    return (size_t)(8 * (g2 > 2 ? g2 : 2) + 4 * NC_NF) * (Fp + 16) * sizeof(float) > 64 * 1024 || rl_opt("nc_fwd_chunk") != nullptr;
+}
+extern "C" int rl_launch_nc_fwd(const NcFwdBatch* nb, int total_tiles, int g2, int chunked, hipStream_t st) {
     if (rl_grp_active()) return RL_GRP_UNSUPPORTED;          // (no group form: a seed group never runs member 0 alone)
     if (total_tiles <= 0) return 0;
     for (int q = 0; q < nb->ntasks; ++q) if (nb->t[q].N != 4 * NC_NF) return -2;      // the row mapping is built for N = 20
@@ -1711,9 +1605,19 @@ extern "C" int rl_launch_nc_fwd(const NcFwdBatch* nb, int total_tiles, int g2, h
         else hipLaunchKernelGGL((nc_fwd_x3_kernel<1>), dim3(total_tiles), dim3(512), 2 * NX_BUFB, st, *nb);
         return (int)hipGetLastError();
     }
+    const int nw = nb->cols / 16;
+    if (chunked) {
+        // (128 hidden units per workgroup only: rl_nc_fwd_cols is what the fp32 engine is built with; a missing form is an error, not a fallback)
+        if (nw != 8) return -3;
+        const size_t lds = (size_t)(8 * g2 + N) * (NC_CW + 16) * sizeof(float);       // at most 56.6 KB (g2 = 4), whatever F
+        if (g2 == 1) hipLaunchKernelGGL((nc_fwd_chunk_kernel<1, 8>), dim3(total_tiles), dim3(512), lds, st, *nb);
+        else if (g2 == 2) hipLaunchKernelGGL((nc_fwd_chunk_kernel<2, 8>), dim3(total_tiles), dim3(512), lds, st, *nb);
+        else hipLaunchKernelGGL((nc_fwd_chunk_kernel<4, 8>), dim3(total_tiles), dim3(512), lds, st, *nb);
+        return (int)hipGetLastError();
+    }
     const int Fp = (F + 15) & ~15;
     const size_t lds = (size_t)(8 * g2 + N) * (Fp + 16) * sizeof(float);
-    const int nw = nb->cols / 16;
+    if (lds > 64 * 1024) return -3;                          // (such a width belongs to the chunked form: rl_nc_fwd_chunked)
     if (nw == 8) {
         if (g2 == 1) hipLaunchKernelGGL((nc_fwd_kernel<1, 8>), dim3(total_tiles), dim3(512), lds, st, *nb);
         else if (g2 == 2) hipLaunchKernelGGL((nc_fwd_kernel<2, 8>), dim3(total_tiles), dim3(512), lds, st, *nb);

@@ -2,7 +2,9 @@
 
 RLREP_DISABLE lists default mechanisms to switch off (each has an equivalence test that compares the two forms), RLREP_ENABLE lists opt-in ones,
 optionally with a value (`token=value`).  The library parses the same two variables when an agent is created (csrc/engine.hip rl_switches_read);
-the Python side reads them where an agent is constructed or a graph is captured -- never per train() call."""
+the Python side reads them where an agent is constructed or a graph is captured -- never per train() call.
+
+Tokens the library alone reads need no code here; INTEGRATION.md lists them all (RLREP_ENABLE=nc_fwd_chunk among them)."""
 import os
 
 
