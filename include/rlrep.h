@@ -640,6 +640,29 @@ int32_t rlrep_group_env_step(rlrep_agent* agent, rlrep_group_env* env, float* ri
 int32_t rlrep_group_env_evaluate(rlrep_agent* agent, rlrep_group_env* env, int32_t episodes, uint64_t eval_index, double* out_dev, void* stream);
 int32_t rlrep_group_env_state(rlrep_group_env* env, int32_t what, void* host, int64_t bytes, int32_t write, void* stream);
 
+/* ---- the device environment of a SINGLE agent (additive to ABI 4) ---------------------------------------------------------------------------
+ * The same thing for an ordinary agent (rlrep_agent_create) of any of the five algorithms -- they carry the same actor trunk: one record, the
+ * same kinds, record and counters layout, Philox streams, dynamics, row layout and done_bool rule as above (one code: csrc/env_step_body.h,
+ * env_eval_body.h), with the member's seed replaced by `seed` of rlrep_env_create -- the seed rlrep_select_action is called with.
+ * rlrep_env_step is ONE launch of one workgroup, capturable in front of the agent's train(): the action is bit for bit
+ * rlrep_select_action(explore = 1, seed, offset = (calls + 1) << 20) on the record's observation; ring_dev holds `capacity` rows,
+ * size_dev[0] receives the fill level.  rlrep_env_evaluate is ONE launch, grid (episodes, 1): out_dev[e] is episode e's return.
+ * rlrep_env_state: as rlrep_group_env_state with one record (256 bytes; counters 16; start states 16 * episodes).
+ * Rejected with RLREP_ERR_ARG and a message that names the entry point, before any launch: a null pointer, a seed group ("takes
+ * rlrep_group_env_create"), a data-parallel agent, an unknown kind, dimensions other than the kind's, an environment of another agent, a call
+ * inside a train(), episodes outside [1, 64], a capacity below 1.  rlrep_env_destroy(NULL) is a no-op.
+ * rlrep_prepare: size an agent's step programs for `batch` (blocking table uploads when it changes: call it outside a graph capture); launches
+ * nothing.  rlrep_group_prepare's twin for an ordinary agent. */
+typedef struct rlrep_env rlrep_env;
+int32_t rlrep_env_create(rlrep_agent* agent, int32_t kind, uint64_t seed, rlrep_env** out);
+void rlrep_env_destroy(rlrep_env* env);
+int32_t rlrep_env_reset(rlrep_env* env, void* stream);
+int32_t rlrep_env_step(rlrep_agent* agent, rlrep_env* env, float* ring_dev, int64_t capacity, int32_t* size_dev, float lo, float hi, float eps_greedy,
+                       int64_t start_timesteps, void* stream);
+int32_t rlrep_env_evaluate(rlrep_agent* agent, rlrep_env* env, int32_t episodes, uint64_t eval_index, double* out_dev, void* stream);
+int32_t rlrep_env_state(rlrep_env* env, int32_t what, void* host, int64_t bytes, int32_t write, void* stream);
+int32_t rlrep_prepare(rlrep_agent* agent, int32_t batch);
+
 #ifdef __cplusplus
 }
 #endif

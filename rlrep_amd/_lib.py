@@ -107,6 +107,13 @@ def _load():
         'rlrep_group_env_step': (i32, [vp, vp, vp, i64, i64, vp, f32, f32, f32, i64, vp]),
         'rlrep_group_env_evaluate': (i32, [vp, vp, i32, u64, vp, vp]),
         'rlrep_group_env_state': (i32, [vp, i32, vp, i64, i32, vp]),
+        'rlrep_env_create': (i32, [vp, i32, u64, P(vp)]),
+        'rlrep_env_destroy': (None, [vp]),
+        'rlrep_env_reset': (i32, [vp, vp]),
+        'rlrep_env_step': (i32, [vp, vp, vp, i64, vp, f32, f32, f32, i64, vp]),
+        'rlrep_env_evaluate': (i32, [vp, vp, i32, u64, vp, vp]),
+        'rlrep_env_state': (i32, [vp, i32, vp, i64, i32, vp]),
+        'rlrep_prepare': (i32, [vp, i32]),
         'rlrep_set_batch': (i32, [vp, i32, P(Batch), vp]),
         'rlrep_replay_row_floats': (i32, [P(Dims)]),
         'rlrep_replay_add': (i32, [vp, i64, i32, i64, vp, i64, vp]),

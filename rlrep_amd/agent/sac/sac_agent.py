@@ -435,21 +435,26 @@ class SACAgent(object):
             self._prepare_only = False
 
     # ---- checkpoint / resume (absent in the reference: `--save_model` is parsed and never read, main.py:37) ------
-    def state_snapshot(self):
+    def state_snapshot(self, env=None):
         c = self.core
         self.flush()
         torch.cuda.synchronize()
         c.exchange_check()                       # behind the device synchronisation: a replica whose last launches timed out is never written out
-        return {'format': self.CHECKPOINT_FORMAT, 'device_state_bytes': int(c.device_state().numel()), 'alg': self.ALG, 'params': c.params.cpu(), 'targets': c.targets.cpu(), 'exp_avg': c.exp_avg.cpu(),
+        snap = {'format': self.CHECKPOINT_FORMAT, 'device_state_bytes': int(c.device_state().numel()), 'alg': self.ALG, 'params': c.params.cpu(), 'targets': c.targets.cpu(), 'exp_avg': c.exp_avg.cpu(),
                 'exp_avg_sq': c.exp_avg_sq.cpu(), 'alpha_state': c.alpha_state.cpu(), 'device_state': c.device_state().cpu(),
                 'steps': self.steps, 'noise_ctr': self._ctr, 'seed': self._seed, 'layout': list(c.order)}
+        if env is not None:         # a device environment's record and counters (rlrep_amd/envs/device.py DeviceEnv)
+            snap['device_env'] = env.snapshot()
+        return snap
 
-    def save(self, path):
-        snap = self.state_snapshot()
+    def save(self, path, env=None):
+        snap = self.state_snapshot(env)
         self.core.exchange_check()               # (the copies above were synchronous; refuse to persist a replica that is out of step)
         torch.save(snap, path)
 
-    def load(self, path_or_snapshot):
+    def load(self, path_or_snapshot, env=None):
+        """env: a device environment (DeviceEnv) takes the checkpoint's record and counters, or a fresh reset when the checkpoint carries
+        none."""
         snap = torch.load(path_or_snapshot) if isinstance(path_or_snapshot, (str, bytes, os.PathLike)) else path_or_snapshot
         self.flush()                                   # nothing of a pipelined train() may still be writing the arenas
         torch.cuda.synchronize()
@@ -477,6 +482,105 @@ class SACAgent(object):
         self._graph = None
         self._pipe, self._pending = None, False
         torch.cuda.synchronize()
+        if env is not None:
+            if 'device_env' in snap:
+                env.load_snapshot(snap['device_env'])
+            else:
+                env.reset()
+
+    # ---- device environments (rlrep_amd/envs/device.py DeviceEnv): collect, train and score without a host round trip -------------------
+    def iterate(self, env, buffer, batch_size, train=True):
+        """One environment step on the device -- act, explore, step the dynamics, write the ring row (rlrep_env_step) -- and, with `train`,
+        one train() on the ring as it then stands: ONE graph replay, no host round trip.  `env` is a DeviceEnv of this agent, `buffer` a
+        ReplayBuffer whose cursor the device owns from here on (ReplayBuffer.adopt_device_cursor gives it back).  Returns what train()
+        returns, or None without `train`.  The step's exploring draw is the one `select_action(state, explore=True)` would make now: both
+        count calls in the same counter.
+        Always the one-graph form: the step needs the actor train(t) left, and the feature steps of train(t + 1) sample the row the step
+        writes, so the two chains of the pipelined train() have nothing to overlap here.  A pipelined train() still in flight is finished
+        first.  The step programs are sized for the batch by rlrep_prepare, not by the eager gather a train() capture uses: while the
+        device owns the cursor the host's `buffer.size` is stale (and 0 for a ring only the device has written)."""
+        name = type(self).__name__
+        if self.world_size > 1 or self._dp:
+            raise RuntimeError(f'{name}.iterate: a data-parallel agent has no device environment')
+        if not self.use_graph:
+            raise RuntimeError(f'{name}.iterate: needs the graph form of train() (this agent was built with graph=False)')
+        if (getattr(buffer, 'members', None) is not None or not hasattr(buffer, 'collect_on_device')
+                or (getattr(buffer, 'state_dim', None), getattr(buffer, 'action_dim', None)) != (self.state_dim, self.action_dim)):
+            raise ValueError(f'{name}.iterate: needs a ReplayBuffer of {self.state_dim} observations and {self.action_dim} actions')
+        if getattr(env, 'agent', None) is not self:
+            raise ValueError(f'{name}.iterate: the device environment belongs to another agent')
+        if env.seed != self._seed:
+            raise ValueError(f'{name}.iterate: the device environment draws with seed {env.seed}, the agent now with {self._seed} (a checkpoint '
+                             'of another seed was loaded): create the environment after load()')
+        B, train = int(batch_size), bool(train)
+        if self._pending:
+            self.flush()
+        buffer.collect_on_device(env)
+        key = (self._graph_cache_key(buffer, B), id(env), train, float(env.eps_greedy), int(env.start_timesteps))
+        graphs = self.__dict__.setdefault('_iter_graphs', {})
+        g = graphs.get(key)
+        if g is None:
+            if train:               # as _capture_prologue: size the programs and allocate the pools outside the capture
+                self._warm(buffer, B)
+                ni, ne = self._pool_sizes(B)
+                self._buf('pool_idx', (ni,), torch.int32)
+                self._buf('pool_eps', (ne,))
+            torch.cuda.synchronize()
+            with _no_gc():
+                from rlrep_amd._lib import lib as _l
+                s, g = torch.cuda.Stream(), torch.cuda.CUDAGraph()
+                n0 = _l.rlrep_launch_counter()
+                if train:
+                    with self._history_capture(), self._managed_images(), torch.cuda.graph(g, stream=s):
+                        env.step(buffer, env.eps_greedy, env.start_timesteps)
+                        self._body(buffer, B, True)
+                else:
+                    with torch.cuda.graph(g, stream=s):
+                        env.step(buffer, env.eps_greedy, env.start_timesteps)
+                self._iter_launches = _l.rlrep_launch_counter() - n0          # kernels in the captured iterate()
+            graphs.clear()          # (one form at a time is kept: a warm-up graph gives way to the training graph)
+            graphs[key] = g
+            self._held_env_buffer = buffer
+        if env.calls != self._ctr:              # select_action, a capture or a checkpoint moved the call counter: the device follows (rare)
+            env.set_counters(env.t_global, self._ctr)
+        if train:
+            self._sync_images()
+        g.replay()
+        warm = env.t_global < env.start_timesteps
+        env.t_global += 1
+        if not warm:
+            self._ctr += 1
+            env.calls = self._ctr
+        if not train:
+            return None
+        self.steps += 1
+        return self._history_info() if self._hist else self.core.info()
+
+    def evaluate(self, env, episodes, eval_index=None):
+        """Mean return of `episodes` mean-action episodes, a float: ONE launch (rlrep_env_evaluate) and one copy back.  The start states are
+        a function of (seed, eval_index, episode); by default eval_index counts the evaluations of `env`, so successive evaluations see
+        fresh starts."""
+        if getattr(env, 'agent', None) is not self:
+            raise ValueError(f'{type(self).__name__}.evaluate: the device environment belongs to another agent')
+        if self._pending:
+            self.flush()
+        episodes = int(episodes)
+        if eval_index is None:
+            eval_index = env.eval_index
+            env.eval_index += 1
+        out = torch.full((1, max(episodes, 1)), float('nan'), dtype=torch.float64, device=self.core.device)
+        env.evaluate(episodes, eval_index, out)
+        return float(out.mean().cpu())
+
+    def _warm(self, buffer, B):
+        """Before a capture: size the library's tables for B (blocking copies when the batch size changes) and count one call of the host
+        counter.  A buffer the host fills gets the one eager gather it always got; a ring whose cursor a device environment owns is not
+        sampled by the stale host fill level -- rlrep_prepare sizes the programs and launches nothing."""
+        if getattr(buffer, '_device_env', None) is None or getattr(buffer, 'members', None) is not None:       # (a seed group sizes in its own _sample_into)
+            return self._sample_into(buffer, B, 'warm', 0, False)
+        from rlrep_amd._lib import lib as _l, check as _check
+        _check(_l.rlrep_prepare(self.core.h, int(B)), 'prepare')
+        self._ctr += 1
 
     # ---- internals ----------------------------------------------------------------------------
     def _set_batch(self, batch, slot=0):
@@ -850,7 +954,7 @@ class SACAgent(object):
             return None
         if flush:
             self.flush()
-        self._sample_into(buffer, B, 'warm', 0, False)
+        self._warm(buffer, B)
         ni, ne = self._pool_sizes(B)
         self._buf('pool_idx', (ni,), torch.int32)
         self._buf('pool_eps', (ne,))

@@ -1,4 +1,4 @@
-// C ABI of seed groups and of their device environments (include/rlrep.h rlrep_group_*, rlrep_group_env_*): host side; the group forms of the
+// C ABI of seed groups and of device environments -- a group's and a single agent's (include/rlrep.h rlrep_group_*, rlrep_group_env_*, rlrep_env_*): host side; the group forms of the
 // kernels live beside the single-agent kernels, group_clone.hip and group_env.hip hold the kernels only groups have.
 #include "engine_internal.h"
 #include <cmath>
@@ -354,21 +354,116 @@ int32_t rlrep_group_env_evaluate(rlrep_agent* ag, rlrep_group_env* env, int32_t 
     env->last_episodes = episodes;
     return 0;
 }
-int32_t rlrep_group_env_state(rlrep_group_env* env, int32_t what, void* host, int64_t bytes, int32_t write, void* stream) {
-    if (!env || !host) { rl_set_error("group_env_state: null argument"); return RLREP_ERR_ARG; }
+// rlrep_group_env_state / rlrep_env_state: copy one block of an environment of `n` records to or from the host; `what_fn` names the caller
+static int32_t env_state_copy(const char* what_fn, rlrep_agent* ag, EnvRecord* recs, int n, EnvCtl* ctl, double* starts, int last_episodes, int32_t what,
+                              void* host, int64_t bytes, int32_t write, void* stream) {
     void* dev = nullptr; int64_t have = 0;
-    if (what == RLREP_ENV_STATE_RECORDS) { dev = env->recs; have = (int64_t)sizeof(EnvRecord) * env->members; }
-    else if (what == RLREP_ENV_STATE_COUNTERS) { dev = env->ctl; have = 16; }
-    else if (what == RLREP_ENV_STATE_EVAL_STARTS && !write) { dev = env->starts; have = (int64_t)sizeof(double) * 2 * env->last_episodes * env->members; }
-    else { rl_set_error("group_env_state: what = %d (write %d) is not a block of the environment", what, write); return RLREP_ERR_ARG; }
-    if (bytes != have) { rl_set_error("group_env_state: block %d holds %lld bytes, the buffer %lld", what, (long long)have, (long long)bytes); return RLREP_ERR_ARG; }
-    if (in_train_refused("group_env_state", env->ag)) return RLREP_ERR_ARG;
+    if (what == RLREP_ENV_STATE_RECORDS) { dev = recs; have = (int64_t)sizeof(EnvRecord) * n; }
+    else if (what == RLREP_ENV_STATE_COUNTERS) { dev = ctl; have = 16; }
+    else if (what == RLREP_ENV_STATE_EVAL_STARTS && !write) { dev = starts; have = (int64_t)sizeof(double) * 2 * last_episodes * n; }
+    else { rl_set_error("%s: what = %d (write %d) is not a block of the environment", what_fn, what, write); return RLREP_ERR_ARG; }
+    if (bytes != have) { rl_set_error("%s: block %d holds %lld bytes, the buffer %lld", what_fn, what, (long long)have, (long long)bytes); return RLREP_ERR_ARG; }
+    if (in_train_refused(what_fn, ag)) return RLREP_ERR_ARG;
     hipError_t e = hipSuccess;
     if (bytes > 0) e = write ? hipMemcpyAsync(dev, host, (size_t)bytes, hipMemcpyHostToDevice, (hipStream_t)stream)
                              : hipMemcpyAsync(host, dev, (size_t)bytes, hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    if (e != hipSuccess) { rl_set_error("group_env_state: %s", hipGetErrorString(e)); return RLREP_ERR_HIP; }
+    if (e != hipSuccess) { rl_set_error("%s: %s", what_fn, hipGetErrorString(e)); return RLREP_ERR_HIP; }
     return 0;
+}
+int32_t rlrep_group_env_state(rlrep_group_env* env, int32_t what, void* host, int64_t bytes, int32_t write, void* stream) {
+    if (!env || !host) { rl_set_error("group_env_state: null argument"); return RLREP_ERR_ARG; }
+    return env_state_copy("group_env_state", env->ag, env->recs, env->members, env->ctl, env->starts, env->last_episodes, what, host, bytes, write, stream);
+}
+
+// ---- the device environment of a SINGLE agent (group_env.hip env_*_kernel): any of the five algorithms, they carry the same actor trunk --------
+struct rlrep_env {
+    rlrep_agent* ag; int kind; uint64_t seed;
+    EnvRecord* rec; EnvCtl* ctl;                      // one record and its counters: allocations of their own
+    double* starts;                                   // [RL_ENV_MAX_EPISODES, 2] start states of the last evaluation
+    int last_episodes;
+};
+static int env_check(const char* what, rlrep_agent* ag, rlrep_env* env) {
+    if (!ag || !env) { rl_set_error("%s: null agent or environment", what); return RLREP_ERR_ARG; }
+    if (ag->members > 0) { rl_set_error("%s: a seed group takes rlrep_group_env_*", what); return RLREP_ERR_ARG; }
+    if (env->ag != ag) { rl_set_error("%s: the environment was created for another agent", what); return RLREP_ERR_ARG; }
+    if (in_train_refused(what, ag)) return RLREP_ERR_ARG;
+    return 0;
+}
+int32_t rlrep_env_create(rlrep_agent* ag, int32_t kind, uint64_t seed, rlrep_env** out) {
+    const EnvKindInfo* k = rl_env_kind(kind);
+    if (!k) { rl_set_error("env_create: kind %d is not built (0 = Pendulum-v1, 2 = MountainCarContinuous-v0)", kind); return RLREP_ERR_ARG; }
+    if (!ag || !out) { rl_set_error("env_create: null argument"); return RLREP_ERR_ARG; }
+    if (ag->members > 0) { rl_set_error("env_create: a seed group of %d members takes rlrep_group_env_create", ag->members); return RLREP_ERR_ARG; }
+    if (ag->h.world_size > 1 || ag->dp_proto.world > 1) {
+        rl_set_error("env_create: a data-parallel agent (world_size %d) has no device environment", std::max(ag->h.world_size, ag->dp_proto.world)); return RLREP_ERR_ARG;
+    }
+    if (ag->d.state_dim != k->S || ag->d.action_dim != k->A) {
+        rl_set_error("env_create: %s has %d observations and %d action (the agent has %d and %d)", k->name, k->S, k->A, ag->d.state_dim, ag->d.action_dim); return RLREP_ERR_ARG;
+    }
+    rlrep_env* env = new rlrep_env();
+    env->ag = ag; env->kind = kind; env->seed = seed; env->last_episodes = 0; env->rec = nullptr; env->ctl = nullptr; env->starts = nullptr;
+    hipError_t e = hipMalloc((void**)&env->rec, sizeof(EnvRecord));
+    if (e == hipSuccess) e = hipMalloc((void**)&env->ctl, sizeof(EnvCtl));
+    if (e == hipSuccess) e = hipMalloc((void**)&env->starts, sizeof(double) * 2 * RL_ENV_MAX_EPISODES);
+    if (e == hipSuccess) e = hipMemset(env->rec, 0, sizeof(EnvRecord));
+    if (e == hipSuccess) e = hipMemset(env->ctl, 0, sizeof(EnvCtl));
+    if (e == hipSuccess) e = hipMemset(env->starts, 0, sizeof(double) * 2 * RL_ENV_MAX_EPISODES);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { rl_set_error("env_create: %s", hipGetErrorString(e)); rlrep_env_destroy(env); return RLREP_ERR_HIP; }
+    *out = env;
+    return 0;
+}
+void rlrep_env_destroy(rlrep_env* env) {
+    if (!env) return;
+    if (env->rec) (void)hipFree(env->rec);
+    if (env->ctl) (void)hipFree(env->ctl);
+    if (env->starts) (void)hipFree(env->starts);
+    delete env;
+}
+int32_t rlrep_env_reset(rlrep_env* env, void* stream) {
+    if (const int rc = env_check("env_reset", env ? env->ag : nullptr, env)) return rc;
+    ++g_rl_launches;
+    const int rc = rl_launch_env_reset(env->kind, env->rec, env->ctl, env->seed, (hipStream_t)stream);
+    if (rc) { rl_set_error("env_reset: launch failed (%d)", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_env_step(rlrep_agent* ag, rlrep_env* env, float* ring_dev, int64_t capacity, int32_t* size_dev, float lo, float hi, float eps_greedy,
+                       int64_t start_timesteps, void* stream) {
+    if (const int rc = env_check("env_step", ag, env)) return rc;
+    if (!ring_dev || !size_dev) { rl_set_error("env_step: null ring or size pointer"); return RLREP_ERR_ARG; }
+    if (capacity < 1) { rl_set_error("env_step: capacity %lld is below one row", (long long)capacity); return RLREP_ERR_ARG; }
+    if (!(lo <= hi) || !(eps_greedy >= 0.f && eps_greedy <= 1.f)) { rl_set_error("env_step: bad action range [%g, %g] or eps_greedy %g", (double)lo, (double)hi, (double)eps_greedy); return RLREP_ERR_ARG; }
+    SelectAct p; group_actor(ag, p, lo, hi);
+    p.seed = env->seed;
+    ++g_rl_launches;
+    const int rc = rl_launch_env_step(env->kind, &p, env->rec, env->ctl, ring_dev, capacity, size_dev, eps_greedy, start_timesteps, (hipStream_t)stream);
+    if (rc) { rl_set_error("env_step: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_env_evaluate(rlrep_agent* ag, rlrep_env* env, int32_t episodes, uint64_t eval_index, double* out_dev, void* stream) {
+    if (const int rc = env_check("env_evaluate", ag, env)) return rc;
+    if (episodes < 1 || episodes > RL_ENV_MAX_EPISODES) { rl_set_error("env_evaluate: episodes %d outside [1, %d]", episodes, RL_ENV_MAX_EPISODES); return RLREP_ERR_ARG; }
+    if (!out_dev) { rl_set_error("env_evaluate: null output"); return RLREP_ERR_ARG; }
+    const EnvKindInfo* k = rl_env_kind(env->kind);
+    SelectAct p; group_actor(ag, p, k->lo, k->hi);       // the environment's own action range
+    p.seed = env->seed;
+    ++g_rl_launches;
+    const int rc = rl_launch_env_eval(env->kind, &p, eval_index * (uint64_t)episodes, episodes, out_dev, env->starts, (hipStream_t)stream);
+    if (rc) { rl_set_error("env_evaluate: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    env->last_episodes = episodes;
+    return 0;
+}
+int32_t rlrep_env_state(rlrep_env* env, int32_t what, void* host, int64_t bytes, int32_t write, void* stream) {
+    if (!env || !host) { rl_set_error("env_state: null argument"); return RLREP_ERR_ARG; }
+    return env_state_copy("env_state", env->ag, env->rec, 1, env->ctl, env->starts, env->last_episodes, what, host, bytes, write, stream);
+}
+// size a single agent's step programs for `batch` outside a capture (rlrep_group_prepare's twin): SACAgent.iterate captures its graph while
+// the DEVICE owns the ring cursor, where the eager gather a train() capture sizes them with would sample by a stale host fill level
+int32_t rlrep_prepare(rlrep_agent* ag, int32_t batch) {
+    GROUP_REFUSE("prepare")
+    if (!ag) { rl_set_error("prepare: null agent"); return RLREP_ERR_ARG; }
+    return ensure_batch(ag, batch);
 }
 
 }  // extern "C"

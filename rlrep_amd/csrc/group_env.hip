@@ -12,6 +12,10 @@
 // before they read or write anything.  The actor forward is select_action_body.h, the body of select_action_kernel(_grp): same tiles, same
 // summation order, same Philox draw -- the action is bit for bit what rlrep_group_select_action returns for the same observation, seed and
 // offset.  All stores are ordinary per-lane stores from lane 0.
+//
+// A SINGLE agent (any of the five algorithms: they share the actor trunk; rlrep_env_*) has forms of its own -- env_reset_kernel,
+// env_step_kernel, env_eval_kernel: grid (1, 1) resp. (episodes, 1), no member stride, no live table, the seed by value in SelectAct::seed.
+// What a record's step and an episode's rollout ARE is written once, in env_step_body.h and env_eval_body.h, and included into both forms.
 #include <hip/hip_runtime.h>
 #include "common.h"
 #include "kparams.h"
@@ -28,22 +32,35 @@ __device__ __forceinline__ void env_start(unsigned long long seed, unsigned long
     Env::start(c, x0, x1);
 }
 
-// rlrep_group_env_reset: every member's record starts a fresh episode (all members, whatever the live table says: a reset is the caller's
-// explicit act, like rlrep_group_clone_members); ring cursors, counters and the returns ring are zeroed, and so is the group's EnvCtl.
+// a record starts a fresh episode (start state at counter 0): ring cursor, counters and the returns ring are zeroed
 template <class Env>
-__global__ __launch_bounds__(64) void group_env_reset_kernel(EnvRecord* __restrict__ recs, EnvCtl* __restrict__ ctl, const unsigned long long* __restrict__ seeds) {
-    if (threadIdx.x != 0) return;
-    const int m = blockIdx.y;
-    EnvRecord* rec = recs + m;
+__device__ __forceinline__ void env_reset_record(EnvRecord* rec, unsigned long long seed) {
     double th, thd;
-    env_start<Env>(seeds[m], 0ull, 1u, RL_STREAM_ENV, th, thd);
+    env_start<Env>(seed, 0ull, 1u, RL_STREAM_ENV, th, thd);
     rec->theta = th; rec->theta_dot = thd; rec->episode_return = 0.0; rec->ring_ptr = 0; rec->nsteps = 0;
     rec->t = 0; rec->ring_size = 0; rec->episodes_done = 0; rec->force = 0; rec->force_action = 0.f; rec->act = 0.f;
     Env::observe(th, thd, rec->obs);
     for (int q = Env::S; q < 4; ++q) rec->obs[q] = 0.f;
     for (int q = 0; q < RL_ENV_RETURNS; ++q) rec->returns[q] = 0.0;
     for (int q = 0; q < 6; ++q) rec->pad_[q] = 0.0;
-    if (m == 0) { ctl->t_global = 0; ctl->calls = 0ull; ctl->ticket = 0; ctl->pad_ = 0; }
+}
+__device__ __forceinline__ void env_reset_ctl(EnvCtl* ctl) { ctl->t_global = 0; ctl->calls = 0ull; ctl->ticket = 0; ctl->pad_ = 0; }
+
+// rlrep_group_env_reset: every member's record starts a fresh episode (all members, whatever the live table says: a reset is the caller's
+// explicit act, like rlrep_group_clone_members); ring cursors, counters and the returns ring are zeroed, and so is the group's EnvCtl.
+template <class Env>
+__global__ __launch_bounds__(64) void group_env_reset_kernel(EnvRecord* __restrict__ recs, EnvCtl* __restrict__ ctl, const unsigned long long* __restrict__ seeds) {
+    if (threadIdx.x != 0) return;
+    const int m = blockIdx.y;
+    env_reset_record<Env>(recs + m, seeds[m]);
+    if (m == 0) env_reset_ctl(ctl);
+}
+// rlrep_env_reset: the single agent's form -- one record, the seed by value
+template <class Env>
+__global__ __launch_bounds__(64) void env_reset_kernel(EnvRecord* __restrict__ rec, EnvCtl* __restrict__ ctl, unsigned long long seed) {
+    if (threadIdx.x != 0) return;
+    env_reset_record<Env>(rec, seed);
+    env_reset_ctl(ctl);
 }
 
 // One environment step of every live member.  p0: member 0's actor (obs / act unset); ring: member 0's replay ring, member m's lies
@@ -62,57 +79,13 @@ __global__ __launch_bounds__(1024) void group_env_step_kernel(SelectAct p0, long
     const bool warm = t_global < start_timesteps;
     const long long dm = (long long)m * mstride;
     SelectAct p = p0;
-    p.obs = rec->obs; p.act = &rec->act;
     rl_rb(p.W1, dm); rl_rb(p.b1, dm); rl_rb(p.W2, dm); rl_rb(p.b2, dm); rl_rb(p.W3, dm); rl_rb(p.b3, dm);
     p.seed = seeds[m];
-    p.explore = 1; p.offset = (calls + 1ull) << 20;                 // SeedBatchMixin.select_action(explore=True): `_ctr += 1`, offset `_ctr << 20`
-#include "select_action_body.h"
-    if (threadIdx.x != 0) return;
-    // ---- one lane from here on (it wrote rec->act itself: A = 1) ----
-    float a = rec->act;
-    const unsigned long long n = (unsigned long long)rec->nsteps;
-    {
-        uint32_t c[4] = {(uint32_t)n, (uint32_t)(n >> 32), 0u, RL_STREAM_ENV};
-        philox4x32_10(c, (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-        if (warm || env_u01f(c[0]) < eps_greedy) a = fminf(fmaxf(p.lo + (p.hi - p.lo) * env_u01f(c[1]), p.lo), p.hi);
-    }
-    if (rec->force) { a = rec->force_action; rec->force = 0; }
-    double th = rec->theta, thd = rec->theta_dot;
-    float s[Env::S], nx[Env::S];
-#pragma unroll
-    for (int q = 0; q < Env::S; ++q) s[q] = rec->obs[q];
-    bool goal;
-    const float r32 = Env::dynamics(th, thd, a, goal);
-    Env::observe(th, thd, nx);
-    long long ptr = rec->ring_ptr;
-    if (ptr < 0 || ptr >= capacity) ptr = 0;                        // (a cursor written by the host: never leave the ring)
-    float* row = ring + (long long)m * ring_stride + ptr * Env::ROW;
-#pragma unroll
-    for (int q = 0; q < Env::S; ++q) { row[q] = s[q]; row[Env::S + 1 + q] = nx[q]; }
-    row[Env::S] = a; row[2 * Env::S + 1] = r32;
-    const int t = rec->t + 1;
-    // done_bool is the host loop's rule (main.py): an end by the time limit does not count, and neither does a goal reached on the limit's step
-    row[2 * Env::S + 2] = (Env::TERMINATES && goal && t < Env::LIMIT) ? 1.f : 0.f;
-    rec->ring_ptr = ptr + 1 >= capacity ? 0 : ptr + 1;
-    const int fill = (int)min((long long)rec->ring_size + 1, capacity);
-    rec->ring_size = fill;
-    size_dev[m] = fill;
-    rec->act = a;
-    rec->nsteps = (long long)(n + 1);
-    const double ret = rec->episode_return + (double)r32;
-    if ((Env::TERMINATES && goal) || t >= Env::LIMIT) {
-        const int done = rec->episodes_done;
-        rec->returns[done & (RL_ENV_RETURNS - 1)] = ret;
-        rec->episodes_done = done + 1;
-        rec->episode_return = 0.0; rec->t = 0;
-        env_start<Env>(p.seed, n + 1, 1u, RL_STREAM_ENV, th, thd);
-        Env::observe(th, thd, nx);
-    } else {
-        rec->episode_return = ret; rec->t = t;
-    }
-    rec->theta = th; rec->theta_dot = thd;
-#pragma unroll
-    for (int q = 0; q < Env::S; ++q) rec->obs[q] = nx[q];
+#define ENV_RING (ring + (long long)m * ring_stride)
+#define ENV_SIZE_WORD size_dev[m]
+#include "env_step_body.h"
+#undef ENV_RING
+#undef ENV_SIZE_WORD
     // "last workgroup advances the counters": every workgroup read them before its own ticket, so the last ticket follows every read
     __threadfence();
     if (atomicAdd(&ctl->ticket, 1) == n_live - 1) {
@@ -120,6 +93,25 @@ __global__ __launch_bounds__(1024) void group_env_step_kernel(SelectAct p0, long
         ctl->t_global = t_global + 1;
         if (!warm) ctl->calls = calls + 1ull;
     }
+}
+
+// rlrep_env_step: the single agent's form of the step -- one workgroup, one record, no member stride, no live table; the seed rides by value
+// in SelectAct::seed, as select_action_kernel takes it.  p0: the agent's actor (obs / act unset).  The body is the group's (env_step_body.h);
+// one workgroup needs no ticket: lane 0 advances the counters it read at the head.
+template <class Env>
+__global__ __launch_bounds__(1024) void env_step_kernel(SelectAct p0, EnvRecord* __restrict__ rec, EnvCtl* __restrict__ ctl, float* __restrict__ ring,
+                                                        long long capacity, int* __restrict__ size_dev, float eps_greedy, long long start_timesteps) {
+    const long long t_global = ctl->t_global;
+    const unsigned long long calls = ctl->calls;
+    const bool warm = t_global < start_timesteps;
+    SelectAct p = p0;
+#define ENV_RING ring
+#define ENV_SIZE_WORD size_dev[0]
+#include "env_step_body.h"
+#undef ENV_RING
+#undef ENV_SIZE_WORD
+    ctl->t_global = t_global + 1;
+    if (!warm) ctl->calls = calls + 1ull;
 }
 
 // One evaluation: workgroup (e, slot) rolls out one whole episode of its member with the MEAN action (select_action(explore=False)) from the
@@ -135,46 +127,29 @@ __global__ __launch_bounds__(1024) void group_env_eval_kernel(SelectAct p0, long
                                                               const int* __restrict__ live, unsigned long long counter0, int episodes,
                                                               double* __restrict__ out, double* __restrict__ starts) {
     RL_GRP_MEMBER(m, live);
-    extern __shared__ float sm[];
-    // behind the body's buffers (8-byte aligned): x0 | x1 | return (fp64: kept out of the registers the body needs), then obs[S] | act[A]
-    // (| the end flag of a kind that terminates)
-    double* const st = (double*)(sm + ((p0.S + 2 * p0.Ha + 2 * p0.A + 1) & ~1));
-    float* const slot = (float*)(st + 3);
-    const int e = blockIdx.x;
-    const long long dm = (long long)m * mstride;
-    SelectAct p = p0;
-    p.obs = slot; p.act = slot + p0.S;
-    rl_rb(p.W1, dm); rl_rb(p.b1, dm); rl_rb(p.W2, dm); rl_rb(p.b2, dm); rl_rb(p.W3, dm); rl_rb(p.b3, dm);
+// (the member's actor and seed: spelled where the body takes its parameter block)
+#define ENV_EVAL_ACTOR \
+    const long long dm = (long long)m * mstride; \
+    rl_rb(p.W1, dm); rl_rb(p.b1, dm); rl_rb(p.W2, dm); rl_rb(p.b2, dm); rl_rb(p.W3, dm); rl_rb(p.b3, dm); \
     p.seed = seeds[m];
-    p.explore = 0; p.offset = 0ull;
-    if (threadIdx.x == 0) {
-        double th, thd;
-        env_start<Env>(p.seed, counter0 + (unsigned long long)e, 0u, RL_STREAM_EVAL, th, thd);
-        double* first = starts + ((long long)m * episodes + e) * 2;
-        first[0] = th; first[1] = thd;
-        st[0] = th; st[1] = thd; st[2] = 0.0;
-        Env::observe(th, thd, slot);
-        if constexpr (Env::TERMINATES) slot[p0.S + p0.A] = 0.f;
-    }
-    for (int step = 0; step < Env::LIMIT; ++step) {
-        __syncthreads();
-        if constexpr (Env::TERMINATES) {
-            if (slot[p0.S + p0.A] != 0.f) break;                    // uniform: one LDS word, read by all lanes behind the barrier
-        }
-        {
-#include "select_action_body.h"
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double th = st[0], thd = st[1];
-            bool goal;
-            st[2] += (double)Env::dynamics(th, thd, slot[p0.S], goal);
-            st[0] = th; st[1] = thd;
-            Env::observe(th, thd, slot);
-            if constexpr (Env::TERMINATES) { if (goal) slot[p0.S + p0.A] = 1.f; }
-        }
-    }
-    if (threadIdx.x == 0) out[(long long)m * episodes + e] = st[2];
+#define ENV_EVAL_FIRST (starts + ((long long)m * episodes + e) * 2)
+#define ENV_EVAL_SCORE out[(long long)m * episodes + e]
+#include "env_eval_body.h"
+#undef ENV_EVAL_FIRST
+#undef ENV_EVAL_SCORE
+#undef ENV_EVAL_ACTOR
+}
+
+// rlrep_env_evaluate: the single agent's form -- workgroup e rolls out episode e (env_eval_body.h), out[e] and starts[2 e ..]
+template <class Env>
+__global__ __launch_bounds__(1024) void env_eval_kernel(SelectAct p0, unsigned long long counter0, double* __restrict__ out, double* __restrict__ starts) {
+#define ENV_EVAL_ACTOR
+#define ENV_EVAL_FIRST (starts + (long long)e * 2)
+#define ENV_EVAL_SCORE out[e]
+#include "env_eval_body.h"
+#undef ENV_EVAL_FIRST
+#undef ENV_EVAL_SCORE
+#undef ENV_EVAL_ACTOR
 }
 
 static size_t env_lds(const SelectAct* p, bool slot, bool flag) {
@@ -221,6 +196,44 @@ extern "C" int rl_launch_group_env_eval(int kind, const SelectAct* p, long long 
     switch (kind) {
     case EnvPendulum::KIND: return env_launch_eval<EnvPendulum>(p, mstride, seeds, live, grid_y, counter0, episodes, out, starts, st);
     case EnvMountainCar::KIND: return env_launch_eval<EnvMountainCar>(p, mstride, seeds, live, grid_y, counter0, episodes, out, starts, st);
+    default: return -7;
+    }
+}
+// ---- the single agent's forms (rlrep_env_*): the seed rides in p->seed ----
+template <class Env>
+static int env_launch_step1(const SelectAct* p, EnvRecord* rec, EnvCtl* ctl, float* ring, long long capacity, int* size_dev, float eps_greedy, long long start_timesteps, hipStream_t st) {
+    const size_t lds = env_lds(p, false, false);
+    if (lds > 60 * 1024 || p->S != Env::S || p->A != Env::A || capacity < 1) return -7;
+    hipLaunchKernelGGL(env_step_kernel<Env>, dim3(1, 1), dim3(1024), lds, st, *p, rec, ctl, ring, capacity, size_dev, eps_greedy, start_timesteps);
+    return (int)hipGetLastError();
+}
+template <class Env>
+static int env_launch_eval1(const SelectAct* p, unsigned long long counter0, int episodes, double* out, double* starts, hipStream_t st) {
+    const size_t lds = env_lds(p, true, Env::TERMINATES);
+    if (lds > 60 * 1024 || p->S != Env::S || p->A != Env::A || episodes < 1 || episodes > RL_ENV_MAX_EPISODES) return -7;
+    hipLaunchKernelGGL(env_eval_kernel<Env>, dim3(episodes, 1), dim3(1024), lds, st, *p, counter0, out, starts);
+    return (int)hipGetLastError();
+}
+extern "C" int rl_launch_env_reset(int kind, EnvRecord* rec, EnvCtl* ctl, unsigned long long seed, hipStream_t st) {
+    switch (kind) {
+    case EnvPendulum::KIND: hipLaunchKernelGGL(env_reset_kernel<EnvPendulum>, dim3(1, 1), dim3(64), 0, st, rec, ctl, seed); break;
+    case EnvMountainCar::KIND: hipLaunchKernelGGL(env_reset_kernel<EnvMountainCar>, dim3(1, 1), dim3(64), 0, st, rec, ctl, seed); break;
+    default: return -7;
+    }
+    return (int)hipGetLastError();
+}
+extern "C" int rl_launch_env_step(int kind, const SelectAct* p, EnvRecord* rec, EnvCtl* ctl, float* ring, long long capacity, int* size_dev, float eps_greedy,
+                                  long long start_timesteps, hipStream_t st) {
+    switch (kind) {
+    case EnvPendulum::KIND: return env_launch_step1<EnvPendulum>(p, rec, ctl, ring, capacity, size_dev, eps_greedy, start_timesteps, st);
+    case EnvMountainCar::KIND: return env_launch_step1<EnvMountainCar>(p, rec, ctl, ring, capacity, size_dev, eps_greedy, start_timesteps, st);
+    default: return -7;
+    }
+}
+extern "C" int rl_launch_env_eval(int kind, const SelectAct* p, unsigned long long counter0, int episodes, double* out, double* starts, hipStream_t st) {
+    switch (kind) {
+    case EnvPendulum::KIND: return env_launch_eval1<EnvPendulum>(p, counter0, episodes, out, starts, st);
+    case EnvMountainCar::KIND: return env_launch_eval1<EnvMountainCar>(p, counter0, episodes, out, starts, st);
     default: return -7;
     }
 }

@@ -94,6 +94,10 @@ int rl_launch_group_env_step(int kind, const SelectAct* p, long long mstride, co
                              long long start_timesteps, hipStream_t st);
 int rl_launch_group_env_eval(int kind, const SelectAct* p, long long mstride, const unsigned long long* seeds, const int* live, int grid_y,
                              unsigned long long counter0, int episodes, double* out, double* starts, hipStream_t st);
+int rl_launch_env_reset(int kind, EnvRecord* rec, EnvCtl* ctl, unsigned long long seed, hipStream_t st);
+int rl_launch_env_step(int kind, const SelectAct* p, EnvRecord* rec, EnvCtl* ctl, float* ring, long long capacity, int* size_dev, float eps_greedy,
+                       long long start_timesteps, hipStream_t st);
+int rl_launch_env_eval(int kind, const SelectAct* p, unsigned long long counter0, int episodes, double* out, double* starts, hipStream_t st);
 // ---- rowprog.hip / xchain.hip (experiments build); experiments_off.hip (product build: stubs) ----
 int rl_launch_rowprog(const RpLaunch* L, int total_blocks, hipStream_t st);
 int rl_rowprog_init();

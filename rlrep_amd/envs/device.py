@@ -1,5 +1,6 @@
-"""Environments of a seed group on the device (include/rlrep.h rlrep_group_env_*; rlrep_amd/csrc/group_env.hip): Pendulum-v1
-(DevicePendulumGroup) and MountainCarContinuous-v0 (DeviceMountainCarGroup, whose goal state ends an episode with done = 1).
+"""Environments on the device (include/rlrep.h rlrep_group_env_*, rlrep_env_*; rlrep_amd/csrc/group_env.hip): Pendulum-v1
+(DevicePendulumGroup) and MountainCarContinuous-v0 (DeviceMountainCarGroup, whose goal state ends an episode with done = 1) for a seed group,
+DevicePendulum and DeviceMountainCar for a single agent of any algorithm (`SACAgent.iterate` / `SACAgent.evaluate`, the same contracts at R = 1).
 
 One record per member lives on the device; `SeedBatchMixin.iterate(env, buffers, batch_size)` acts, explores, steps the dynamics, writes the
 replay-ring row and trains every live member in ONE graph replay, and `SeedBatchMixin.evaluate(env, episodes)` scores every live member in one
@@ -30,44 +31,44 @@ assert RECORD_DTYPE.itemsize == 256
 COUNTERS_DTYPE = np.dtype([('t_global', '<i8'), ('calls', '<u8')])
 
 
-class DeviceEnvGroup(object):
-    """The device environments of kind `kind` (a key of KINDS) of seed group `agent` (a SACSeedBatch / CTRLSACSeedBatch with the kind's
-    dimensions).  Created reset."""
+class _DeviceEnvBase(object):
+    """What the device environments of a seed group (DeviceEnvGroup, R records) and of a single agent (DeviceEnv, one record) share: the
+    records and counters, the returns drain and the checkpoint form.  A subclass sets PREFIX (its entry points in
+    include/rlrep.h), FORM (what its snapshots say they are) and creates the handle `h` for `R` records."""
 
-    def __init__(self, agent, kind, eps_greedy=0.0, start_timesteps=0):
-        """eps_greedy: the probability of a uniform action in place of the policy's; start_timesteps: the warm-up, steps (counted since
-        reset) that take uniform actions only.  Both ride by value in a captured iterate() graph."""
+    PREFIX = None
+    FORM = None
+
+    def _setup(self, agent, kind, eps_greedy, start_timesteps, R):
         name = type(self).__name__
-        if getattr(agent, 'R', None) is None or not hasattr(agent, 'seeds'):
-            raise ValueError(f'{name}: needs a seed group (SACSeedBatch / CTRLSACSeedBatch)')
         if kind not in KINDS:
             raise ValueError(f'{name}: kind {kind} is not built ({", ".join(f"{k} = {v[0]}" for k, v in KINDS.items())})')
         self.kind = int(kind)
         self.env_name, self.state_dim, self.action_dim, self.max_episode_steps = KINDS[self.kind]
-        self.agent, self.R = agent, agent.R
+        self.agent, self.R = agent, int(R)
         self.eps_greedy, self.start_timesteps = float(eps_greedy), int(start_timesteps)
-        self.t_global, self.calls = 0, 0        # host mirrors of the device counters (SeedBatchMixin.iterate keeps them in step)
-        h = C.c_void_p()
-        check(lib.rlrep_group_env_create(agent.core.h, self.kind, C.byref(h)), 'group_env_create')
-        self.h = h
-        self._drained = [0] * self.R            # finished episodes returns() has handed out, per member
-        self.eval_index = 0                     # evaluations run so far (SeedBatchMixin.evaluate): the next one's start states
-        self.reset()
+        self.t_global, self.calls = 0, 0        # host mirrors of the device counters (iterate keeps them in step)
+        self.h = None
+        self._drained = [0] * self.R            # finished episodes returns() has handed out, per record
+        self.eval_index = 0                     # evaluations run so far (evaluate): the next one's start states
+
+    def _call(self, name, *args):
+        check(getattr(lib, self.PREFIX + name)(*args), self.PREFIX[len('rlrep_'):] + name)
 
     def __del__(self):
         h, self.h = getattr(self, 'h', None), None
         if h:
-            lib.rlrep_group_env_destroy(h)
+            getattr(lib, self.PREFIX + 'destroy')(h)
 
     def reset(self):
         """Every member starts a fresh episode; ring cursors, counters and returns are zeroed (one launch)."""
-        check(lib.rlrep_group_env_reset(self.h, _stream()), 'group_env_reset')
+        self._call('reset', self.h, _stream())
         self._drained = [0] * self.R
         self.t_global, self.calls = 0, 0
 
     # ---- records --------------------------------------------------------------------------------------------------------------------
     def _block(self, what, arr, write):
-        check(lib.rlrep_group_env_state(self.h, what, C.c_void_p(arr.ctypes.data), arr.nbytes, 1 if write else 0, _stream()), 'group_env_state')
+        self._call('state', self.h, what, C.c_void_p(arr.ctypes.data), arr.nbytes, 1 if write else 0, _stream())
         return arr
 
     def state(self):
@@ -95,7 +96,7 @@ class DeviceEnvGroup(object):
     def set_cursor(self, ptr, sizes):
         """every member's ring cursor (the rings are filled in lockstep) and fill level, e.g. from a ReplayBufferGroup filled on the host"""
         rec = self.state()
-        rec['ring_ptr'], rec['ring_size'] = int(ptr), np.asarray(sizes, np.int32)
+        rec['ring_ptr'], rec['ring_size'] = int(ptr), np.asarray(sizes, np.int32).reshape(-1)
         self._block(STATE_RECORDS, rec, True)
 
     def eval_starts(self, episodes):
@@ -114,31 +115,81 @@ class DeviceEnvGroup(object):
             self._drained[r] = done
         return out
 
-    # ---- launches -------------------------------------------------------------------------------------------------------------------
-    def step(self, buffers, eps_greedy, start_timesteps):
-        """One step of every live member into `buffers` (a ReplayBufferGroup): ONE launch on the current stream, capturable."""
-        lo, hi = self.agent.action_range
-        check(lib.rlrep_group_env_step(self.agent.core.h, self.h, C.c_void_p(buffers.rings.data_ptr()), buffers.ring_stride, buffers.max_size,
-                                       C.c_void_p(buffers.size_dev().data_ptr()), lo, hi, float(eps_greedy), int(start_timesteps), _stream()),
-              'group_env_step')
-
-    def evaluate(self, episodes, eval_index, out):
-        """`episodes` mean-action episodes of every live member -> out [R, episodes] float64 (device): ONE launch"""
-        check(lib.rlrep_group_env_evaluate(self.agent.core.h, self.h, int(episodes), int(eval_index), C.c_void_p(out.data_ptr()), _stream()),
-              'group_env_evaluate')
-
     # ---- checkpoints ----------------------------------------------------------------------------------------------------------------
     def snapshot(self):
         t, calls = self.counters()
-        return {'kind': self.kind, 'records': torch.from_numpy(self.state().view(np.uint8).copy()), 't_global': t, 'calls': calls,
+        return {'kind': self.kind, 'form': self.FORM, 'records': torch.from_numpy(self.state().view(np.uint8).copy()), 't_global': t, 'calls': calls,
                 'eval_index': int(self.eval_index)}
 
     def load_snapshot(self, snap):
+        if snap.get('form', 'group') != self.FORM:              # (snapshots written before single agents had device environments: a group's)
+            raise RuntimeError(f'checkpoint does not match this device environment (it holds the environment of a {snap.get("form", "group")}, '
+                               f'this one is the environment of a {self.FORM})')
         if snap.get('kind') != self.kind or snap['records'].numel() != self.R * RECORD_DTYPE.itemsize:
             raise RuntimeError('checkpoint does not match this device environment (kind / members differ)')
         self.set_state(snap['records'].numpy().view(RECORD_DTYPE))
         self.set_counters(snap['t_global'], snap['calls'])
         self.eval_index = int(snap.get('eval_index', 0))
+
+
+class DeviceEnvGroup(_DeviceEnvBase):
+    """The device environments of kind `kind` (a key of KINDS) of seed group `agent` (a SACSeedBatch / CTRLSACSeedBatch with the kind's
+    dimensions).  Created reset."""
+
+    PREFIX, FORM = 'rlrep_group_env_', 'group'
+
+    def __init__(self, agent, kind, eps_greedy=0.0, start_timesteps=0):
+        """eps_greedy: the probability of a uniform action in place of the policy's; start_timesteps: the warm-up, steps (counted since
+        reset) that take uniform actions only.  Both ride by value in a captured iterate() graph."""
+        name = type(self).__name__
+        if getattr(agent, 'R', None) is None or not hasattr(agent, 'seeds'):
+            raise ValueError(f'{name}: needs a seed group (SACSeedBatch / CTRLSACSeedBatch)')
+        self._setup(agent, kind, eps_greedy, start_timesteps, agent.R)
+        h = C.c_void_p()
+        self._call('create', agent.core.h, self.kind, C.byref(h))
+        self.h = h
+        self.reset()
+
+    # ---- launches -------------------------------------------------------------------------------------------------------------------
+    def step(self, buffers, eps_greedy, start_timesteps):
+        """One step of every live member into `buffers` (a ReplayBufferGroup): ONE launch on the current stream, capturable."""
+        lo, hi = self.agent.action_range
+        self._call('step', self.agent.core.h, self.h, C.c_void_p(buffers.rings.data_ptr()), buffers.ring_stride, buffers.max_size,
+                   C.c_void_p(buffers.size_dev().data_ptr()), lo, hi, float(eps_greedy), int(start_timesteps), _stream())
+
+    def evaluate(self, episodes, eval_index, out):
+        """`episodes` mean-action episodes of every live member -> out [R, episodes] float64 (device): ONE launch"""
+        self._call('evaluate', self.agent.core.h, self.h, int(episodes), int(eval_index), C.c_void_p(out.data_ptr()), _stream())
+
+
+class DeviceEnv(_DeviceEnvBase):
+    """The device environment of kind `kind` of ONE agent (any of the five algorithms, with the kind's dimensions): the surface of
+    DeviceEnvGroup with R = 1 -- state() is one record, returns() one list, eval_starts() [1, episodes, 2].  `SACAgent.iterate(env, buffer,
+    batch_size)` steps it and trains in one graph replay, `SACAgent.evaluate(env, episodes)` scores in one launch.  Its Philox key is the
+    agent's seed, as select_action's is.  Created reset."""
+
+    PREFIX, FORM = 'rlrep_env_', 'single'
+
+    def __init__(self, agent, kind, eps_greedy=0.0, start_timesteps=0):
+        name = type(self).__name__
+        if getattr(agent, 'R', None) is not None or not hasattr(agent, '_seed'):
+            raise ValueError(f'{name}: needs a single agent (a seed group takes DeviceEnvGroup)')
+        self._setup(agent, kind, eps_greedy, start_timesteps, 1)
+        self.seed = int(agent._seed)            # the Philox key of every draw: what the agent's select_action draws with
+        h = C.c_void_p()
+        self._call('create', agent.core.h, self.kind, self.seed, C.byref(h))
+        self.h = h
+        self.reset()
+
+    def step(self, buffer, eps_greedy, start_timesteps):
+        """One step into `buffer` (a ReplayBuffer): ONE launch on the current stream, capturable."""
+        lo, hi = self.agent.action_range
+        self._call('step', self.agent.core.h, self.h, C.c_void_p(buffer.ring.data_ptr()), buffer.max_size, C.c_void_p(buffer._size_dev.data_ptr()),
+                   lo, hi, float(eps_greedy), int(start_timesteps), _stream())
+
+    def evaluate(self, episodes, eval_index, out):
+        """`episodes` mean-action episodes -> out [1, episodes] float64 (device): ONE launch"""
+        self._call('evaluate', self.agent.core.h, self.h, int(episodes), int(eval_index), C.c_void_p(out.data_ptr()), _stream())
 
 
 class DevicePendulumGroup(DeviceEnvGroup):
@@ -160,6 +211,20 @@ class DeviceMountainCarGroup(DeviceEnvGroup):
         super().__init__(agent, KIND_MOUNTAIN_CAR_CONTINUOUS, eps_greedy, start_timesteps)
 
 
+class DevicePendulum(DeviceEnv):
+    """Pendulum-v1 for a single agent"""
+
+    def __init__(self, agent, eps_greedy=0.0, start_timesteps=0):
+        super().__init__(agent, KIND_PENDULUM, eps_greedy, start_timesteps)
+
+
+class DeviceMountainCar(DeviceEnv):
+    """MountainCarContinuous-v0 for a single agent"""
+
+    def __init__(self, agent, eps_greedy=0.0, start_timesteps=0):
+        super().__init__(agent, KIND_MOUNTAIN_CAR_CONTINUOUS, eps_greedy, start_timesteps)
+
+
 def device_class(env_name):
     """the device environment class of --env `env_name`, or None where none is built"""
     if str(env_name).startswith('Pendulum'):
@@ -167,3 +232,9 @@ def device_class(env_name):
     if str(env_name).startswith('MountainCarContinuous'):
         return DeviceMountainCarGroup
     return None
+
+
+def single_device_class(env_name):
+    """the device environment class of --env `env_name` for a single agent (--device-loop), or None where none is built"""
+    group = device_class(env_name)
+    return {DevicePendulumGroup: DevicePendulum, DeviceMountainCarGroup: DeviceMountainCar}.get(group)

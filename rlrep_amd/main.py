@@ -34,6 +34,10 @@ metrics.jsonl stops growing; its state stays in the group (and in --save_model c
 exploring, stepping, the replay-ring row and train() of every live member are one graph replay per step (SeedBatchMixin.iterate) and an
 evaluation is one launch (SeedBatchMixin.evaluate); --pbt-interval and --halving-interval rank by those scores.  Exploration and reset draws
 come from Philox streams of the members' seeds, so a run differs from the host loop's in its random numbers, not in its algorithm.
+
+`--device-loop` (one agent of any --alg, no --seeds / --sweep, --env Pendulum-v1 or MountainCarContinuous-v0) is the same for a single agent:
+`SACAgent.iterate` is one graph replay per step and `SACAgent.evaluate` one launch per evaluation, for sac, vlsac, ctrlsac, spedersac and
+diffsrsac alike; --save_model writes the environment's record with the checkpoint.
 """
 import argparse
 import json
@@ -105,7 +109,11 @@ def run(argv=None):
     p.add_argument('--halving-min', default=None, type=int, help='stop retiring at this many live members (default 1)')
     p.add_argument('--device-env', action='store_true',
                    help='step and score the environments on the device (with --seeds / --sweep and --env Pendulum-v1 or MountainCarContinuous-v0): rlrep_amd/envs/device.py')
+    p.add_argument('--device-loop', action='store_true',
+                   help='a single agent of any --alg with its environment on the device (--env Pendulum-v1 or MountainCarContinuous-v0): SACAgent.iterate / evaluate')
     args = p.parse_args(argv)
+    if args.device_loop:
+        _check_device_loop(args)
     if args.seeds is not None or args.sweep:
         return run_seeds(args)
     if _pbt_requested(args):
@@ -133,6 +141,8 @@ def run(argv=None):
     state_dim, action_dim = env.observation_space.shape[0], env.action_space.shape[0]
     agent = build_agent(args, state_dim, action_dim, env.action_space)
     replay = buffer.ReplayBuffer(state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)))
+    if args.device_loop:
+        return _single_device_loop(args, agent, replay, log_path, jsonl, tb)
     evaluations = [util.eval_policy(agent, eval_env, args.eval_episodes)]
 
     state, done = env.reset(), False
@@ -170,6 +180,54 @@ def run(argv=None):
             print('Step {}. Steps per sec: {:.4g}.'.format(t + 1, sps))
             if args.save_model:
                 agent.save(os.path.join(log_path, 'agent.pt'))
+    jsonl.close()
+    if tb is not None:
+        tb.close()
+    print('Total time cost {:.4g}s.'.format(timer.time_cost()))
+    return agent, evaluations
+
+
+def _check_device_loop(args):
+    """--device-loop is the single agent's device environment; SystemExit, before anything touches the GPU, on what it does not run with"""
+    for flag, given in (('--seeds', args.seeds is not None), ('--sweep', bool(args.sweep)), ('--pbt-*', _pbt_requested(args)),
+                        ('--halving-*', _halving_requested(args)), ('--device-env', args.device_env)):
+        if given:
+            raise SystemExit(f'--device-loop: runs ONE agent with its environment on the device and does not go with {flag}; a seed group takes '
+                             '--device-env (with --seeds and / or --sweep)')
+    from rlrep_amd.envs.device import single_device_class
+    if single_device_class(args.env) is None:
+        raise SystemExit(f'--device-loop: only Pendulum-v1 and MountainCarContinuous-v0 are built on the device (got --env {args.env}); run without --device-loop')
+
+
+def _single_device_loop(args, agent, replay, log_path, jsonl, tb):
+    """run()'s loop with the environment on the device (--device-loop), _device_loop's shape for one agent: an initial evaluation, one
+    `agent.iterate` per step -- act, explore, step, ring row and train() in one graph replay -- and one `agent.evaluate` launch every
+    --eval_freq.  The exploration and reset draws are Philox streams of the agent's seed instead of NumPy generators; the metrics.jsonl rows
+    keep their keys, and --save_model writes the environment's record with the checkpoint."""
+    from rlrep_amd.envs.device import single_device_class
+    env = single_device_class(args.env)(agent, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps))
+    evaluations = [agent.evaluate(env, args.eval_episodes)]
+    info = None
+    timer = util.Timer()
+    for t in range(int(args.max_timesteps)):
+        out = agent.iterate(env, replay, args.batch_size, train=t >= args.start_timesteps)
+        info = out if out is not None else info
+        if (t + 1) % args.eval_freq == 0:
+            sps = timer.steps_per_sec(t + 1)
+            evaluations.append(agent.evaluate(env, args.eval_episodes))
+            if info is not None:
+                row = {'step': t + 1, 'info/evaluation': float(evaluations[-1]), 'steps_per_sec': sps}
+                row.update({f'info/{k}': float(v) for k, v in info.items()})
+                jsonl.write(json.dumps(row) + '\n')
+                jsonl.flush()
+                if tb is not None:
+                    for k, v in row.items():
+                        if k.startswith('info/'):
+                            tb.add_scalar(k, v, t + 1)
+                    tb.flush()
+            print('Step {}. Steps per sec: {:.4g}.'.format(t + 1, sps))
+            if args.save_model:
+                agent.save(os.path.join(log_path, 'agent.pt'), env=env)
     jsonl.close()
     if tb is not None:
         tb.close()

@@ -43,9 +43,13 @@ class ReplayBuffer(object):
         # hooks called before the ring / size scalar is overwritten on the caller's stream (a pipelined train() may still be sampling from
         # them on its own stream: each agent that trains from this buffer appends one that makes the caller's stream wait)
         self.before_device_write_hooks = []
+        self._device_env = None      # the device environment that owns the cursor (collect_on_device); None: the host does
 
     # ---- reference API ------------------------------------------------------------------------
     def add(self, state, action, next_state, reward, done):
+        if self._device_env is not None:
+            raise RuntimeError('ReplayBuffer.add: a device environment has been advancing this ring (SACAgent.iterate), so the host cursor is stale: '
+                               'call adopt_device_cursor() first')
         if self.shard is not None:
             i = self._offered
             self._offered += 1
@@ -106,6 +110,34 @@ class ReplayBuffer(object):
                 self.ring[:n - first].copy_(self._stage[first:n])
         self._staged = 0
         self.device_epoch += 1
+
+    # ---- device collection (rlrep_amd/envs/device.py DeviceEnv), with ReplayBufferGroup's semantics -------------------------------------
+    def collect_on_device(self, env):
+        """Hand the cursor to device environment `env`: staged rows are flushed, the environment's record takes (ptr, size), and from here on
+        the step launches advance the ring and the fill level in size_dev().  add() refuses until adopt_device_cursor()."""
+        if self._device_env is env:
+            return
+        if self._device_env is not None:
+            raise RuntimeError('ReplayBuffer.collect_on_device: another device environment owns the cursor (adopt_device_cursor() first)')
+        if self.shard is not None:
+            raise ValueError('ReplayBuffer.collect_on_device: a sharded ring (shard=) keeps one transition in `world`; a device environment '
+                             'writes every row it steps')
+        self.flush()
+        self.size_dev()
+        env.set_cursor(self.ptr, [self.size])
+        self._device_env = env
+
+    def adopt_device_cursor(self):
+        """Take the cursor back from the device environment: ptr and size become what its record holds (synchronises), and add() continues
+        behind the last row the device wrote."""
+        env = self._device_env
+        if env is None:
+            return
+        rec = env.state()
+        self.ptr = int(rec['ring_ptr'][0]) % self.max_size
+        self.size = int(rec['ring_size'][0])
+        self._size_pushed = self.size               # (the step launches have published it)
+        self._device_env = None
 
     def load(self, state, action, next_state, reward, done):
         """Bulk-fill the ring (synthetic benchmarks / tests)."""

@@ -10,6 +10,13 @@ one graph replay.  Both on groups of the same seeds and shapes (sac: hidden 256;
 process, arms alternated: --warmup iterations per arm, then --windows windows of --calls iterations each, host wall clock around a device
 synchronisation; median and min .. max of the windows.  Also the group's bare train() (the floor of either loop) in the same alternation.
 Evaluation: util.eval_policy per member (as run_seeds scores) against SeedBatchMixin.evaluate, --eval-episodes episodes, median of --eval-repeats.
+
+    python tools/device_env_rate.py --single --alg vlsac --batch 256 --calls 300
+
+--single: ONE agent of --alg (sac, vlsac, ctrlsac, spedersac, diffsrsac; widths 256) instead of a group.  Host loop: the body of main.py run()
+past warm-up (select_action, NumPy step, ReplayBuffer.add, train() in the form the agent picks).  Device loop: SACAgent.iterate.  Bare train():
+the ONE-GRAPH train() (an agent built with pipeline=False) on a ring a device loop filled.  The same alternation and windows; one evaluation
+by util.eval_policy against SACAgent.evaluate.
 """
 import argparse
 import os
@@ -112,6 +119,119 @@ class TrainOnly(object):
         self.agent.train(self.replay, self.B)
 
 
+def _single(alg, B, **extra):
+    S, A, space, _ = _dims()
+    kw = dict(max_batch=B, seed=0, hidden_dim=256)
+    if alg == 'sac':
+        from rlrep_amd.agent.sac.sac_agent import SACAgent as cls
+    elif alg == 'vlsac':
+        from rlrep_amd.agent.vlsac.vlsac_agent import VLSACAgent as cls
+        kw.update(feature_dim=256, extra_feature_steps=3)
+    elif alg == 'ctrlsac':
+        from rlrep_amd.agent.ctrlsac.ctrlsac_agent import CTRLSACAgent as cls
+        kw.update(feature_dim=256, extra_feature_steps=3)
+    elif alg == 'spedersac':
+        from rlrep_amd.agent.spedersac.spedersac_agent import SPEDERSACAgent as cls
+        kw.update(phi_and_mu_lr=1e-5, phi_hidden_dim=256, phi_hidden_depth=1, mu_hidden_dim=256, mu_hidden_depth=0, critic_and_actor_lr=3e-4,
+                  critic_and_actor_hidden_dim=256, feature_dim=256, extra_feature_steps=5)
+    else:
+        from rlrep_amd.agent.diffsrsac.diffsrsac_agent import DIFFSRSACAgent as cls
+        kw.update(feature_dim=256, extra_feature_steps=3)
+    kw.update(extra)
+    torch.manual_seed(0)
+    return cls(S, A, space, **kw)
+
+
+class SingleHostLoop(object):
+    """run()'s loop body (main.py), past warm-up"""
+
+    def __init__(self, alg, B):
+        from rlrep_amd import envs
+        from rlrep_amd.utils.buffer import ReplayBuffer
+        self.B = B
+        self.agent = _single(alg, B)
+        S, A, space, self.limit = _dims()
+        self.replay = ReplayBuffer(S, A, max_size=100000)
+        self.env = envs.make(ENV)
+        self.env.seed(0)
+        self.rng = np.random.RandomState(0)
+        self.space = space
+        self.state, self.ep_steps = self.env.reset(), 0
+
+    def step(self):
+        self.ep_steps += 1
+        if self.rng.uniform(0, 1) < EPS_GREEDY:
+            action = self.space.sample()
+        else:
+            action = self.agent.select_action(self.state, explore=True)
+        nxt, rew, done, _ = self.env.step(action)
+        self.replay.add(self.state, action, nxt, rew, float(done) if self.ep_steps < self.limit else 0)
+        self.state = nxt
+        self.agent.train(self.replay, self.B)
+        if done:
+            self.state, self.ep_steps = self.env.reset(), 0
+
+
+class SingleDeviceLoop(object):
+    def __init__(self, alg, B, **extra):
+        from rlrep_amd.envs.device import single_device_class
+        from rlrep_amd.utils.buffer import ReplayBuffer
+        self.B = B
+        self.agent = _single(alg, B, **extra)
+        S, A, _, _ = _dims()
+        self.replay = ReplayBuffer(S, A, max_size=100000)
+        self.env = single_device_class(ENV)(self.agent, eps_greedy=EPS_GREEDY, start_timesteps=0)
+
+    def step(self):
+        self.agent.iterate(self.env, self.replay, self.B)
+
+
+class SingleTrainOnly(object):
+    """the agent's bare ONE-GRAPH train() on a ring a device loop filled: what iterate() adds its step launch to"""
+
+    def __init__(self, alg, B):
+        d = SingleDeviceLoop(alg, B, pipeline=False)
+        for _ in range(256):
+            d.agent.iterate(d.env, d.replay, B, train=False)
+        self.agent, self.replay, self.B = d.agent, d.replay, B
+
+    def step(self):
+        self.agent.train(self.replay, self.B)
+
+
+def single_main(args):
+    from rlrep_amd.utils import util
+    from rlrep_amd import envs
+    alg, B = args.alg, args.batch
+    print(f'# {torch.cuda.get_device_name(0)}; single agent, {alg} {ENV} B = {B}; {args.warmup} warm-up iterations, median (min .. max) of '
+          f'{args.windows} windows of {args.calls} iterations, arms alternated in one process')
+    arms = {'host': SingleHostLoop(alg, B), 'device': SingleDeviceLoop(alg, B), 'train': SingleTrainOnly(alg, B)}
+    rates = _windows(arms, args.warmup, args.calls, args.windows)
+    med = {k: statistics.median(v) for k, v in rates.items()}
+    for k in ('host', 'device', 'train'):
+        what = {'host': 'host loop  (select_action, NumPy step, add, train)', 'device': 'device loop (iterate: one graph replay)      ',
+                'train': 'bare one-graph train()                       '}[k]
+        us = sorted(1e6 / r for r in rates[k])
+        print(f'{alg} single {what}: {med[k]:9.1f} iterations/s ({min(rates[k]):.1f} .. {max(rates[k]):.1f}) = {1e6 / med[k]:7.1f} us '
+              f'(windows {", ".join(f"{u:.1f}" for u in us)})')
+    print(f'{alg} single iterate / host loop: {med["device"] / med["host"]:.2f}x; iterate period - train() period: '
+          f'{1e6 / med["device"] - 1e6 / med["train"]:.1f} us; iterate graph: {arms["device"].agent._iter_launches} launches')
+    host, dev = arms['host'], arms['device']
+    ev = envs.make(ENV)
+    th, td = [], []
+    for _ in range(args.eval_repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        util.eval_policy(host.agent, ev, args.eval_episodes)
+        th.append(time.perf_counter() - t0)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        dev.agent.evaluate(dev.env, args.eval_episodes)
+        td.append(time.perf_counter() - t0)
+    mh, md = statistics.median(th), statistics.median(td)
+    print(f'{alg} single one evaluation ({args.eval_episodes} episodes): util.eval_policy {1e3 * mh:.1f} ms, evaluate {1e3 * md:.2f} ms ({mh / md:.0f}x)', flush=True)
+
+
 def _windows(arms, warmup, calls, windows):
     for a in arms.values():
         for _ in range(warmup):
@@ -131,7 +251,8 @@ def _windows(arms, warmup, calls, windows):
 
 def main(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--alg', default='sac', choices=['sac', 'ctrlsac'])
+    p.add_argument('--alg', default='sac', choices=['sac', 'ctrlsac', 'vlsac', 'spedersac', 'diffsrsac'])
+    p.add_argument('--single', action='store_true', help='one agent (any --alg) instead of a seed group')
     p.add_argument('--members', default='4,8,16')
     p.add_argument('--batch', type=int, default=64)
     p.add_argument('--warmup', type=int, default=300)
@@ -143,6 +264,10 @@ def main(argv=None):
     args = p.parse_args(argv)
     global ENV
     ENV = args.env
+    if args.single:
+        return single_main(args)
+    if args.alg not in ('sac', 'ctrlsac'):
+        raise SystemExit(f'--alg {args.alg}: seed groups are built for sac and ctrlsac (give --single)')
     from rlrep_amd.utils import util
     from rlrep_amd.main import _MemberPolicy
     from rlrep_amd import envs
