@@ -663,6 +663,29 @@ int32_t rlrep_env_evaluate(rlrep_agent* agent, rlrep_env* env, int32_t episodes,
 int32_t rlrep_env_state(rlrep_env* env, int32_t what, void* host, int64_t bytes, int32_t write, void* stream);
 int32_t rlrep_prepare(rlrep_agent* agent, int32_t batch);
 
+/* ---- several environments per member / agent (additive to ABI 4) -----------------------------------------------------------------------------
+ * rlrep_group_env_create_n / rlrep_env_create_n: as the create calls above (which are their num_envs = 1 forms), with num_envs = E in [1, 64]
+ * environments per member resp. for the agent: [members][E] records, record (m, e) at index m * E + e.  The other entry points keep their
+ * signatures and take E from the handle:
+ *   reset     every record starts a fresh episode; record (m, e)'s ring cursor is row e.
+ *   step      ONE launch, grid (E, members) resp. (E, 1): workgroup (e, slot) steps environment e of its member and writes ONE ring row, so a
+ *             step writes E rows per live member, at (ptr + e) mod capacity in environment order where ptr is the member's next free row
+ *             (every record carries its own cursor and advances it by E; record (m, 0)'s cursor is the next free row).  ring_size grows by
+ *             E (capped at capacity) and environment 0 publishes it to size_dev.  t_global advances by E per launch and, past warm-up
+ *             (decided once per launch: keep start_timesteps a multiple of E), calls by E.  capacity >= E.
+ *   draws     key = the member's seed, counter = the record's nsteps, word 3 = the collection stream, word 2 = 2 e (exploration) resp.
+ *             2 e + 1 (start state): environment 0 draws what the single environment draws.  The action of environment e is bit for bit
+ *             select_action(explore = 1, offset = (calls + 1 + e) << 20) on its observation.
+ *   evaluate  unchanged, per member: it does not depend on E.
+ *   state     the records block holds 256 * members * E bytes (single: 256 * E), in index order; counters and start states as before.
+ * rlrep_group_env_num_envs / rlrep_env_num_envs: E of a handle (0 for NULL).  With E = 1 every call launches the kernels it launched
+ * before.  Rejected with RLREP_ERR_ARG and a message naming the entry point (group_env_create_n / env_create_n), before any launch: a kind
+ * that is not built, num_envs outside [1, 64], a null pointer, and what the create calls reject. */
+int32_t rlrep_group_env_create_n(rlrep_agent* agent, int32_t kind, int32_t num_envs, rlrep_group_env** out);
+int32_t rlrep_group_env_num_envs(rlrep_group_env* env);
+int32_t rlrep_env_create_n(rlrep_agent* agent, int32_t kind, uint64_t seed, int32_t num_envs, rlrep_env** out);
+int32_t rlrep_env_num_envs(rlrep_env* env);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,10 @@ def _load():
         'rlrep_env_evaluate': (i32, [vp, vp, i32, u64, vp, vp]),
         'rlrep_env_state': (i32, [vp, i32, vp, i64, i32, vp]),
         'rlrep_prepare': (i32, [vp, i32]),
+        'rlrep_group_env_create_n': (i32, [vp, i32, i32, P(vp)]),
+        'rlrep_group_env_num_envs': (i32, [vp]),
+        'rlrep_env_create_n': (i32, [vp, i32, u64, i32, P(vp)]),
+        'rlrep_env_num_envs': (i32, [vp]),
         'rlrep_set_batch': (i32, [vp, i32, P(Batch), vp]),
         'rlrep_replay_row_floats': (i32, [P(Dims)]),
         'rlrep_replay_add': (i32, [vp, i64, i32, i64, vp, i64, vp]),

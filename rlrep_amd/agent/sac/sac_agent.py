@@ -516,7 +516,7 @@ class SACAgent(object):
         if self._pending:
             self.flush()
         buffer.collect_on_device(env)
-        key = (self._graph_cache_key(buffer, B), id(env), train, float(env.eps_greedy), int(env.start_timesteps))
+        key = (self._graph_cache_key(buffer, B), id(env), train, float(env.eps_greedy), int(env.start_timesteps), int(getattr(env, 'num_envs', 1)))
         graphs = self.__dict__.setdefault('_iter_graphs', {})
         g = graphs.get(key)
         if g is None:
@@ -546,10 +546,11 @@ class SACAgent(object):
         if train:
             self._sync_images()
         g.replay()
+        E = int(getattr(env, 'num_envs', 1))    # (the launch steps E environments: E steps per member, E select_action calls)
         warm = env.t_global < env.start_timesteps
-        env.t_global += 1
+        env.t_global += E
         if not warm:
-            self._ctr += 1
+            self._ctr += E
             env.calls = self._ctr
         if not train:
             return None

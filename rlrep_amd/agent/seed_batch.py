@@ -416,7 +416,7 @@ class SeedBatchMixin(object):
             raise ValueError(f'{name}.iterate: the device environment belongs to another group')
         B, train = int(batch_size), bool(train)
         buffers.collect_on_device(env)
-        key = (self._graph_cache_key(buffers, B), id(env), train, float(env.eps_greedy), int(env.start_timesteps))
+        key = (self._graph_cache_key(buffers, B), id(env), train, float(env.eps_greedy), int(env.start_timesteps), int(getattr(env, 'num_envs', 1)))
         graphs = self.__dict__.setdefault('_iter_graphs', {})
         g = graphs.get(key)
         if g is None:
@@ -428,6 +428,7 @@ class SeedBatchMixin(object):
             torch.cuda.synchronize()
             with _no_gc():
                 s, g = torch.cuda.Stream(), torch.cuda.CUDAGraph()
+                n0 = lib.rlrep_launch_counter()
                 if train:
                     with self._history_capture(), self._managed_images(), torch.cuda.graph(g, stream=s):
                         env.step(buffers, env.eps_greedy, env.start_timesteps)
@@ -435,6 +436,7 @@ class SeedBatchMixin(object):
                 else:
                     with torch.cuda.graph(g, stream=s):
                         env.step(buffers, env.eps_greedy, env.start_timesteps)
+                self._iter_launches = lib.rlrep_launch_counter() - n0          # kernels in the captured iterate()
             graphs.clear()          # (one form at a time is kept: a warm-up graph gives way to the training graph)
             graphs[key] = g
             self._held_env_buffer = buffers
@@ -443,10 +445,11 @@ class SeedBatchMixin(object):
         if train:
             self._sync_images()
         g.replay()
+        E = int(getattr(env, 'num_envs', 1))    # (the launch steps E environments: E steps per member, E select_action calls)
         warm = env.t_global < env.start_timesteps
-        env.t_global += 1
+        env.t_global += E
         if not warm:
-            self._ctr += 1
+            self._ctr += E
             env.calls = self._ctr
         if not train:
             return None

@@ -276,8 +276,8 @@ int32_t rlrep_group_replay_add_sized(float* ring_dev, int64_t ring_stride_floats
 // ---- device environments of a seed group (group_env.hip) --------------------------------------------------------------------------------------
 static_assert(EnvPendulum::KIND == RLREP_ENV_PENDULUM && EnvMountainCar::KIND == RLREP_ENV_MOUNTAIN_CAR_CONTINUOUS, "group_env.h kinds are include/rlrep.h RLREP_ENV_*");
 struct rlrep_group_env {
-    rlrep_agent* ag; int kind, members;
-    EnvRecord* recs; EnvCtl* ctl;                     // [members] records and the group's counters: allocations of their own
+    rlrep_agent* ag; int kind, members, num_envs;
+    EnvRecord* recs; EnvCtl* ctl;                     // [members][num_envs] records and the group's counters: allocations of their own
     double* starts;                                   // [members, RL_ENV_MAX_EPISODES, 2] start states of the last evaluation
     int last_episodes;
 };
@@ -289,27 +289,36 @@ static int group_env_check(const char* what, rlrep_agent* ag, rlrep_group_env* e
     if (in_train_refused(what, ag)) return RLREP_ERR_ARG;
     return 0;
 }
-int32_t rlrep_group_env_create(rlrep_agent* ag, int32_t kind, rlrep_group_env** out) {
+// rlrep_group_env_create (`what` = "group_env_create", num_envs = 1) and rlrep_group_env_create_n: one code, the message names the caller
+static int32_t group_env_create(const char* what, rlrep_agent* ag, int32_t kind, int32_t num_envs, rlrep_group_env** out) {
     const EnvKindInfo* k = rl_env_kind(kind);
-    if (!k) { rl_set_error("group_env_create: kind %d is not built (0 = Pendulum-v1, 2 = MountainCarContinuous-v0)", kind); return RLREP_ERR_ARG; }
-    if (!ag || !out) { rl_set_error("group_env_create: null argument"); return RLREP_ERR_ARG; }
-    if (ag->members <= 0) { rl_set_error("group_env_create: not a seed group (device environments are built for rlrep_group_create agents)"); return RLREP_ERR_ARG; }
+    if (!k) { rl_set_error("%s: kind %d is not built (0 = Pendulum-v1, 2 = MountainCarContinuous-v0)", what, kind); return RLREP_ERR_ARG; }
+    if (num_envs < 1 || num_envs > RL_ENV_MAX_ENVS) { rl_set_error("%s: num_envs %d outside [1, %d]", what, num_envs, RL_ENV_MAX_ENVS); return RLREP_ERR_ARG; }
+    if (!ag || !out) { rl_set_error("%s: null argument", what); return RLREP_ERR_ARG; }
+    if (ag->members <= 0) { rl_set_error("%s: not a seed group (device environments are built for rlrep_group_create agents)", what); return RLREP_ERR_ARG; }
     if (ag->d.state_dim != k->S || ag->d.action_dim != k->A) {
-        rl_set_error("group_env_create: %s has %d observations and %d action (the group has %d and %d)", k->name, k->S, k->A, ag->d.state_dim, ag->d.action_dim); return RLREP_ERR_ARG;
+        rl_set_error("%s: %s has %d observations and %d action (the group has %d and %d)", what, k->name, k->S, k->A, ag->d.state_dim, ag->d.action_dim); return RLREP_ERR_ARG;
     }
     rlrep_group_env* env = new rlrep_group_env();
-    env->ag = ag; env->kind = kind; env->members = ag->members; env->last_episodes = 0;
-    hipError_t e = hipMalloc((void**)&env->recs, sizeof(EnvRecord) * env->members);
+    env->ag = ag; env->kind = kind; env->members = ag->members; env->num_envs = num_envs; env->last_episodes = 0;
+    env->recs = nullptr; env->ctl = nullptr; env->starts = nullptr;
+    const size_t rec_bytes = sizeof(EnvRecord) * (size_t)env->members * (size_t)num_envs;
+    hipError_t e = hipMalloc((void**)&env->recs, rec_bytes);
     if (e == hipSuccess) e = hipMalloc((void**)&env->ctl, sizeof(EnvCtl));
     if (e == hipSuccess) e = hipMalloc((void**)&env->starts, sizeof(double) * 2 * RL_ENV_MAX_EPISODES * env->members);
-    if (e == hipSuccess) e = hipMemset(env->recs, 0, sizeof(EnvRecord) * env->members);
+    if (e == hipSuccess) e = hipMemset(env->recs, 0, rec_bytes);
     if (e == hipSuccess) e = hipMemset(env->ctl, 0, sizeof(EnvCtl));
     if (e == hipSuccess) e = hipMemset(env->starts, 0, sizeof(double) * 2 * RL_ENV_MAX_EPISODES * env->members);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { rl_set_error("group_env_create: %s", hipGetErrorString(e)); rlrep_group_env_destroy(env); return RLREP_ERR_HIP; }
+    if (e != hipSuccess) { rl_set_error("%s: %s", what, hipGetErrorString(e)); rlrep_group_env_destroy(env); return RLREP_ERR_HIP; }
     *out = env;
     return 0;
 }
+int32_t rlrep_group_env_create(rlrep_agent* ag, int32_t kind, rlrep_group_env** out) { return group_env_create("group_env_create", ag, kind, 1, out); }
+int32_t rlrep_group_env_create_n(rlrep_agent* ag, int32_t kind, int32_t num_envs, rlrep_group_env** out) {
+    return group_env_create("group_env_create_n", ag, kind, num_envs, out);
+}
+int32_t rlrep_group_env_num_envs(rlrep_group_env* env) { return env ? env->num_envs : 0; }
 void rlrep_group_env_destroy(rlrep_group_env* env) {
     if (!env) return;
     if (env->recs) (void)hipFree(env->recs);
@@ -320,7 +329,7 @@ void rlrep_group_env_destroy(rlrep_group_env* env) {
 int32_t rlrep_group_env_reset(rlrep_group_env* env, void* stream) {
     if (const int rc = group_env_check("group_env_reset", env ? env->ag : nullptr, env)) return rc;
     ++g_rl_launches;
-    const int rc = rl_launch_group_env_reset(env->kind, env->recs, env->ctl, env->ag->grp_seeds, env->members, (hipStream_t)stream);
+    const int rc = rl_launch_group_env_reset(env->kind, env->recs, env->ctl, env->ag->grp_seeds, env->members, env->num_envs, (hipStream_t)stream);
     if (rc) { rl_set_error("group_env_reset: launch failed (%d)", rc); return RLREP_ERR_HIP; }
     return 0;
 }
@@ -329,6 +338,7 @@ int32_t rlrep_group_env_step(rlrep_agent* ag, rlrep_group_env* env, float* ring_
     if (const int rc = group_env_check("group_env_step", ag, env)) return rc;
     if (!ring_dev || !size_dev) { rl_set_error("group_env_step: null ring or size pointer"); return RLREP_ERR_ARG; }
     const int row = 2 * ag->d.state_dim + ag->d.action_dim + 2;
+    if (capacity < env->num_envs) { rl_set_error("group_env_step: capacity %lld is below the %d rows of one step (num_envs)", (long long)capacity, env->num_envs); return RLREP_ERR_ARG; }
     if (capacity < 1 || ring_stride_floats < capacity * row) {
         rl_set_error("group_env_step: capacity %lld / ring stride %lld floats do not hold %lld rows of %d floats", (long long)capacity, (long long)ring_stride_floats, (long long)capacity, row);
         return RLREP_ERR_ARG;
@@ -336,7 +346,7 @@ int32_t rlrep_group_env_step(rlrep_agent* ag, rlrep_group_env* env, float* ring_
     if (!(lo <= hi) || !(eps_greedy >= 0.f && eps_greedy <= 1.f)) { rl_set_error("group_env_step: bad action range [%g, %g] or eps_greedy %g", (double)lo, (double)hi, (double)eps_greedy); return RLREP_ERR_ARG; }
     SelectAct p; group_actor(ag, p, lo, hi);
     ++g_rl_launches;
-    const int rc = rl_launch_group_env_step(env->kind, &p, ag->grp_stride, ag->grp_seeds, ag->grp_live, ag->grp_grid_y, env->recs, env->ctl, ring_dev, ring_stride_floats, capacity,
+    const int rc = rl_launch_group_env_step(env->kind, &p, ag->grp_stride, ag->grp_seeds, ag->grp_live, ag->grp_grid_y, env->num_envs, env->recs, env->ctl, ring_dev, ring_stride_floats, capacity,
                                             size_dev, eps_greedy, start_timesteps, (hipStream_t)stream);
     if (rc) { rl_set_error("group_env_step: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
     return 0;
@@ -354,11 +364,12 @@ int32_t rlrep_group_env_evaluate(rlrep_agent* ag, rlrep_group_env* env, int32_t 
     env->last_episodes = episodes;
     return 0;
 }
-// rlrep_group_env_state / rlrep_env_state: copy one block of an environment of `n` records to or from the host; `what_fn` names the caller
-static int32_t env_state_copy(const char* what_fn, rlrep_agent* ag, EnvRecord* recs, int n, EnvCtl* ctl, double* starts, int last_episodes, int32_t what,
+// rlrep_group_env_state / rlrep_env_state: copy one block of an environment of `n` agents with `num_envs` records each to or from the host;
+// `what_fn` names the caller
+static int32_t env_state_copy(const char* what_fn, rlrep_agent* ag, EnvRecord* recs, int n, int num_envs, EnvCtl* ctl, double* starts, int last_episodes, int32_t what,
                               void* host, int64_t bytes, int32_t write, void* stream) {
     void* dev = nullptr; int64_t have = 0;
-    if (what == RLREP_ENV_STATE_RECORDS) { dev = recs; have = (int64_t)sizeof(EnvRecord) * n; }
+    if (what == RLREP_ENV_STATE_RECORDS) { dev = recs; have = (int64_t)sizeof(EnvRecord) * n * num_envs; }
     else if (what == RLREP_ENV_STATE_COUNTERS) { dev = ctl; have = 16; }
     else if (what == RLREP_ENV_STATE_EVAL_STARTS && !write) { dev = starts; have = (int64_t)sizeof(double) * 2 * last_episodes * n; }
     else { rl_set_error("%s: what = %d (write %d) is not a block of the environment", what_fn, what, write); return RLREP_ERR_ARG; }
@@ -373,13 +384,13 @@ static int32_t env_state_copy(const char* what_fn, rlrep_agent* ag, EnvRecord* r
 }
 int32_t rlrep_group_env_state(rlrep_group_env* env, int32_t what, void* host, int64_t bytes, int32_t write, void* stream) {
     if (!env || !host) { rl_set_error("group_env_state: null argument"); return RLREP_ERR_ARG; }
-    return env_state_copy("group_env_state", env->ag, env->recs, env->members, env->ctl, env->starts, env->last_episodes, what, host, bytes, write, stream);
+    return env_state_copy("group_env_state", env->ag, env->recs, env->members, env->num_envs, env->ctl, env->starts, env->last_episodes, what, host, bytes, write, stream);
 }
 
 // ---- the device environment of a SINGLE agent (group_env.hip env_*_kernel): any of the five algorithms, they carry the same actor trunk --------
 struct rlrep_env {
-    rlrep_agent* ag; int kind; uint64_t seed;
-    EnvRecord* rec; EnvCtl* ctl;                      // one record and its counters: allocations of their own
+    rlrep_agent* ag; int kind, num_envs; uint64_t seed;
+    EnvRecord* rec; EnvCtl* ctl;                      // [num_envs] records and their counters: allocations of their own
     double* starts;                                   // [RL_ENV_MAX_EPISODES, 2] start states of the last evaluation
     int last_episodes;
 };
@@ -390,30 +401,36 @@ static int env_check(const char* what, rlrep_agent* ag, rlrep_env* env) {
     if (in_train_refused(what, ag)) return RLREP_ERR_ARG;
     return 0;
 }
-int32_t rlrep_env_create(rlrep_agent* ag, int32_t kind, uint64_t seed, rlrep_env** out) {
+static int32_t env_create(const char* what, rlrep_agent* ag, int32_t kind, uint64_t seed, int32_t num_envs, rlrep_env** out) {
     const EnvKindInfo* k = rl_env_kind(kind);
-    if (!k) { rl_set_error("env_create: kind %d is not built (0 = Pendulum-v1, 2 = MountainCarContinuous-v0)", kind); return RLREP_ERR_ARG; }
-    if (!ag || !out) { rl_set_error("env_create: null argument"); return RLREP_ERR_ARG; }
-    if (ag->members > 0) { rl_set_error("env_create: a seed group of %d members takes rlrep_group_env_create", ag->members); return RLREP_ERR_ARG; }
+    if (!k) { rl_set_error("%s: kind %d is not built (0 = Pendulum-v1, 2 = MountainCarContinuous-v0)", what, kind); return RLREP_ERR_ARG; }
+    if (num_envs < 1 || num_envs > RL_ENV_MAX_ENVS) { rl_set_error("%s: num_envs %d outside [1, %d]", what, num_envs, RL_ENV_MAX_ENVS); return RLREP_ERR_ARG; }
+    if (!ag || !out) { rl_set_error("%s: null argument", what); return RLREP_ERR_ARG; }
+    if (ag->members > 0) { rl_set_error("%s: a seed group of %d members takes rlrep_group_env_create", what, ag->members); return RLREP_ERR_ARG; }
     if (ag->h.world_size > 1 || ag->dp_proto.world > 1) {
-        rl_set_error("env_create: a data-parallel agent (world_size %d) has no device environment", std::max(ag->h.world_size, ag->dp_proto.world)); return RLREP_ERR_ARG;
+        rl_set_error("%s: a data-parallel agent (world_size %d) has no device environment", what, std::max(ag->h.world_size, ag->dp_proto.world)); return RLREP_ERR_ARG;
     }
     if (ag->d.state_dim != k->S || ag->d.action_dim != k->A) {
-        rl_set_error("env_create: %s has %d observations and %d action (the agent has %d and %d)", k->name, k->S, k->A, ag->d.state_dim, ag->d.action_dim); return RLREP_ERR_ARG;
+        rl_set_error("%s: %s has %d observations and %d action (the agent has %d and %d)", what, k->name, k->S, k->A, ag->d.state_dim, ag->d.action_dim); return RLREP_ERR_ARG;
     }
     rlrep_env* env = new rlrep_env();
-    env->ag = ag; env->kind = kind; env->seed = seed; env->last_episodes = 0; env->rec = nullptr; env->ctl = nullptr; env->starts = nullptr;
-    hipError_t e = hipMalloc((void**)&env->rec, sizeof(EnvRecord));
+    env->ag = ag; env->kind = kind; env->num_envs = num_envs; env->seed = seed; env->last_episodes = 0; env->rec = nullptr; env->ctl = nullptr; env->starts = nullptr;
+    hipError_t e = hipMalloc((void**)&env->rec, sizeof(EnvRecord) * (size_t)num_envs);
     if (e == hipSuccess) e = hipMalloc((void**)&env->ctl, sizeof(EnvCtl));
     if (e == hipSuccess) e = hipMalloc((void**)&env->starts, sizeof(double) * 2 * RL_ENV_MAX_EPISODES);
-    if (e == hipSuccess) e = hipMemset(env->rec, 0, sizeof(EnvRecord));
+    if (e == hipSuccess) e = hipMemset(env->rec, 0, sizeof(EnvRecord) * (size_t)num_envs);
     if (e == hipSuccess) e = hipMemset(env->ctl, 0, sizeof(EnvCtl));
     if (e == hipSuccess) e = hipMemset(env->starts, 0, sizeof(double) * 2 * RL_ENV_MAX_EPISODES);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { rl_set_error("env_create: %s", hipGetErrorString(e)); rlrep_env_destroy(env); return RLREP_ERR_HIP; }
+    if (e != hipSuccess) { rl_set_error("%s: %s", what, hipGetErrorString(e)); rlrep_env_destroy(env); return RLREP_ERR_HIP; }
     *out = env;
     return 0;
 }
+int32_t rlrep_env_create(rlrep_agent* ag, int32_t kind, uint64_t seed, rlrep_env** out) { return env_create("env_create", ag, kind, seed, 1, out); }
+int32_t rlrep_env_create_n(rlrep_agent* ag, int32_t kind, uint64_t seed, int32_t num_envs, rlrep_env** out) {
+    return env_create("env_create_n", ag, kind, seed, num_envs, out);
+}
+int32_t rlrep_env_num_envs(rlrep_env* env) { return env ? env->num_envs : 0; }
 void rlrep_env_destroy(rlrep_env* env) {
     if (!env) return;
     if (env->rec) (void)hipFree(env->rec);
@@ -424,7 +441,7 @@ void rlrep_env_destroy(rlrep_env* env) {
 int32_t rlrep_env_reset(rlrep_env* env, void* stream) {
     if (const int rc = env_check("env_reset", env ? env->ag : nullptr, env)) return rc;
     ++g_rl_launches;
-    const int rc = rl_launch_env_reset(env->kind, env->rec, env->ctl, env->seed, (hipStream_t)stream);
+    const int rc = rl_launch_env_reset(env->kind, env->rec, env->ctl, env->seed, env->num_envs, (hipStream_t)stream);
     if (rc) { rl_set_error("env_reset: launch failed (%d)", rc); return RLREP_ERR_HIP; }
     return 0;
 }
@@ -433,11 +450,12 @@ int32_t rlrep_env_step(rlrep_agent* ag, rlrep_env* env, float* ring_dev, int64_t
     if (const int rc = env_check("env_step", ag, env)) return rc;
     if (!ring_dev || !size_dev) { rl_set_error("env_step: null ring or size pointer"); return RLREP_ERR_ARG; }
     if (capacity < 1) { rl_set_error("env_step: capacity %lld is below one row", (long long)capacity); return RLREP_ERR_ARG; }
+    if (capacity < env->num_envs) { rl_set_error("env_step: capacity %lld is below the %d rows of one step (num_envs)", (long long)capacity, env->num_envs); return RLREP_ERR_ARG; }
     if (!(lo <= hi) || !(eps_greedy >= 0.f && eps_greedy <= 1.f)) { rl_set_error("env_step: bad action range [%g, %g] or eps_greedy %g", (double)lo, (double)hi, (double)eps_greedy); return RLREP_ERR_ARG; }
     SelectAct p; group_actor(ag, p, lo, hi);
     p.seed = env->seed;
     ++g_rl_launches;
-    const int rc = rl_launch_env_step(env->kind, &p, env->rec, env->ctl, ring_dev, capacity, size_dev, eps_greedy, start_timesteps, (hipStream_t)stream);
+    const int rc = rl_launch_env_step(env->kind, &p, env->num_envs, env->rec, env->ctl, ring_dev, capacity, size_dev, eps_greedy, start_timesteps, (hipStream_t)stream);
     if (rc) { rl_set_error("env_step: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
     return 0;
 }
@@ -456,7 +474,7 @@ int32_t rlrep_env_evaluate(rlrep_agent* ag, rlrep_env* env, int32_t episodes, ui
 }
 int32_t rlrep_env_state(rlrep_env* env, int32_t what, void* host, int64_t bytes, int32_t write, void* stream) {
     if (!env || !host) { rl_set_error("env_state: null argument"); return RLREP_ERR_ARG; }
-    return env_state_copy("env_state", env->ag, env->rec, 1, env->ctl, env->starts, env->last_episodes, what, host, bytes, write, stream);
+    return env_state_copy("env_state", env->ag, env->rec, 1, env->num_envs, env->ctl, env->starts, env->last_episodes, what, host, bytes, write, stream);
 }
 // size a single agent's step programs for `batch` outside a capture (rlrep_group_prepare's twin): SACAgent.iterate captures its graph while
 // the DEVICE owns the ring cursor, where the eager gather a train() capture sizes them with would sample by a stale host fill level

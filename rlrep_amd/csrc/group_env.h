@@ -1,15 +1,29 @@
 // Device environments of a seed group (group_env.hip; include/rlrep.h rlrep_group_env_*): what the kernels and the host entry points share.
-// One EnvRecord per member in an allocation of its own (as grp_seeds and the live table are): the member stride, the clone segments and the
+// One EnvRecord per member and environment ([members][num_envs], record (m, e) at index m * num_envs + e) in an allocation of its own (as grp_seeds and the live table are): the member stride, the clone segments and the
 // checkpoint device records of a group do not know it.  rlrep_amd/envs/device.py reads the same layout (RECORD_DTYPE): keep them in step.
 #pragma once
 #include <stdint.h>
 
 #define RL_ENV_RETURNS 16                 // finished-episode returns a record keeps (a ring: entry episodes_done % 16 is written next)
 #define RL_ENV_MAX_EPISODES 64            // grid x of one evaluation launch at the most
+#define RL_ENV_MAX_ENVS 64                // environments per member / agent (num_envs): grid x of one step launch at the most
 // Philox stream ids (XORed into counter word 3, as PhiloxFill::stream_id is).  Every draw of train() and select_action uses stream 0 with
 // offsets below 2^49, so word 3 stays below 2^17 there: these two words are used by nothing else.
 #define RL_STREAM_ENV 0xE0000000u         // collection: word 2 = 0 the exploration draws of a step, 1 an episode's start state; counter = the member's nsteps
 #define RL_STREAM_EVAL 0xE1000000u        // evaluation start states: counter = eval_index * episodes + episode
+// With E = num_envs environments per member (rlrep_group_env_create_n / rlrep_env_create_n), environment e of a member draws
+//   key            the member's / agent's seed                      (as before)
+//   counter        record (m, e)'s own nsteps                       (as before)
+//   word 3         RL_STREAM_ENV                                    (as before)
+//   word 2         2 e       the exploration draws of a step        (e = 0: 0, the single environment's)
+//                  2 e + 1   an episode's start state               (e = 0: 1, the single environment's)
+//   actor noise    stream 0 at offset (calls + 1 + e) << 20: select_action(explore=True) at call counter calls + 1 + e -- E calls, in
+//                  environment order; the launch then counts E calls
+// so environment 0 is the single environment draw for draw, and word 2 stays below 128.  RL_STREAM_EVAL does not know E: evaluation is
+// per member.
+// Ring rows of a step: record (m, e)'s cursor is (ptr + e) mod capacity where the member's next free row is ptr (reset: ptr = 0;
+// set_cursor(ptr)); a step writes there and advances the cursor by E mod capacity and ring_size by E (capped), so the E rows of one step lie
+// in environment order behind ptr, wrapping inside the step where capacity is no multiple of E.  Record (m, 0)'s cursor is the next free row.
 
 struct EnvRecord {                        // 256 bytes
     double theta, theta_dot;              //   0: the state, fp64 as the host environment keeps it (MountainCarContinuous-v0: position p and velocity v,
@@ -30,10 +44,10 @@ struct EnvRecord {                        // 256 bytes
 };
 static_assert(sizeof(EnvRecord) == 256, "EnvRecord layout (rlrep_amd/envs/device.py RECORD_DTYPE)");
 
-// group-wide counters, advanced by the last live member's workgroup of a step launch
+// group-wide counters, advanced by the last workgroup of a step launch (of n_live * num_envs; the single agent's: of num_envs)
 struct EnvCtl {
-    long long t_global;                   // steps taken since reset: a step with t_global < start_timesteps draws a uniform action (warm-up)
-    unsigned long long calls;             // the select_action call counter: a step past warm-up draws at offset (calls + 1) << 20 and counts one call
+    long long t_global;                   // steps per member taken since reset (a launch adds num_envs): a launch with t_global < start_timesteps draws uniform actions (warm-up)
+    unsigned long long calls;             // the select_action call counter: a step past warm-up draws at offset (calls + 1 + e) << 20 and the launch counts num_envs calls
     int ticket, pad_;
 };
 static_assert(sizeof(EnvCtl) == 24, "EnvCtl layout");

@@ -88,14 +88,14 @@ int rl_launch_slots_sum(const DpSlots* d, float* out, hipStream_t st);
 int rl_launch_group_clone(const CloneTab* tab, const ClonePairs* pairs, int npairs, hipStream_t st);
 int rl_launch_group_live(int* table_dev, const LiveTab* tab, int members, hipStream_t st);
 // ---- group_env.hip ----
-int rl_launch_group_env_reset(int kind, EnvRecord* recs, EnvCtl* ctl, const unsigned long long* seeds, int members, hipStream_t st);
+int rl_launch_group_env_reset(int kind, EnvRecord* recs, EnvCtl* ctl, const unsigned long long* seeds, int members, int num_envs, hipStream_t st);
 int rl_launch_group_env_step(int kind, const SelectAct* p, long long mstride, const unsigned long long* seeds, const int* live, int grid_y,
-                             EnvRecord* recs, EnvCtl* ctl, float* ring, long long ring_stride, long long capacity, int* size_dev, float eps_greedy,
+                             int num_envs, EnvRecord* recs, EnvCtl* ctl, float* ring, long long ring_stride, long long capacity, int* size_dev, float eps_greedy,
                              long long start_timesteps, hipStream_t st);
 int rl_launch_group_env_eval(int kind, const SelectAct* p, long long mstride, const unsigned long long* seeds, const int* live, int grid_y,
                              unsigned long long counter0, int episodes, double* out, double* starts, hipStream_t st);
-int rl_launch_env_reset(int kind, EnvRecord* rec, EnvCtl* ctl, unsigned long long seed, hipStream_t st);
-int rl_launch_env_step(int kind, const SelectAct* p, EnvRecord* rec, EnvCtl* ctl, float* ring, long long capacity, int* size_dev, float eps_greedy,
+int rl_launch_env_reset(int kind, EnvRecord* rec, EnvCtl* ctl, unsigned long long seed, int num_envs, hipStream_t st);
+int rl_launch_env_step(int kind, const SelectAct* p, int num_envs, EnvRecord* rec, EnvCtl* ctl, float* ring, long long capacity, int* size_dev, float eps_greedy,
                        long long start_timesteps, hipStream_t st);
 int rl_launch_env_eval(int kind, const SelectAct* p, unsigned long long counter0, int episodes, double* out, double* starts, hipStream_t st);
 // ---- rowprog.hip / xchain.hip (experiments build); experiments_off.hip (product build: stubs) ----

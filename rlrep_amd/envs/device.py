@@ -6,6 +6,10 @@ One record per member lives on the device; `SeedBatchMixin.iterate(env, buffers,
 replay-ring row and trains every live member in ONE graph replay, and `SeedBatchMixin.evaluate(env, episodes)` scores every live member in one
 launch.  The dynamics are those of rlrep_amd/envs/pendulum.py resp. envs/mountain_car.py (fp64 in one lane, rounded to fp32 where those
 files round); the random draws are Philox streams of the member's seed, so two groups with equal seeds collect identical transitions.
+
+`num_envs = E` (1..64, default 1) gives every member / the agent E environments: one `iterate` steps all of them in the same launch, writes E
+ring rows per member in environment order and trains once.  Environment 0 is the single environment draw for draw; the others draw from
+streams of their own (csrc/group_env.h has the table).
 """
 import ctypes as C
 
@@ -21,6 +25,7 @@ KINDS = {KIND_PENDULUM: ('Pendulum-v1', 3, 1, 200), KIND_MOUNTAIN_CAR_CONTINUOUS
 STATE_RECORDS, STATE_COUNTERS, STATE_EVAL_STARTS = 0, 1, 2
 RETURNS = 16
 MAX_EPISODES = 64
+MAX_ENVS = 64
 EPISODE_STEPS = 200
 
 # csrc/group_env.h EnvRecord
@@ -39,18 +44,33 @@ class _DeviceEnvBase(object):
     PREFIX = None
     FORM = None
 
-    def _setup(self, agent, kind, eps_greedy, start_timesteps, R):
+    def _setup(self, agent, kind, eps_greedy, start_timesteps, R, num_envs=1):
         name = type(self).__name__
         if kind not in KINDS:
             raise ValueError(f'{name}: kind {kind} is not built ({", ".join(f"{k} = {v[0]}" for k, v in KINDS.items())})')
+        self.num_envs = int(num_envs)
+        if not 1 <= self.num_envs <= MAX_ENVS:
+            raise ValueError(f'{name}: num_envs {num_envs} outside [1, {MAX_ENVS}]')
+        if int(start_timesteps) % self.num_envs:
+            raise ValueError(f'{name}: start_timesteps {start_timesteps} is not a multiple of num_envs {self.num_envs} (a step launch is '
+                             'all warm-up or none of it)')
         self.kind = int(kind)
         self.env_name, self.state_dim, self.action_dim, self.max_episode_steps = KINDS[self.kind]
         self.agent, self.R = agent, int(R)
         self.eps_greedy, self.start_timesteps = float(eps_greedy), int(start_timesteps)
         self.t_global, self.calls = 0, 0        # host mirrors of the device counters (iterate keeps them in step)
         self.h = None
-        self._drained = [0] * self.R            # finished episodes returns() has handed out, per record
+        self._drained = [0] * (self.R * self.num_envs)       # finished episodes returns() has handed out, per record
         self.eval_index = 0                     # evaluations run so far (evaluate): the next one's start states
+
+    def _create(self, *args):
+        """the handle: the library's create call for one environment, create_n for several"""
+        h = C.c_void_p()
+        if self.num_envs == 1:
+            self._call('create', *args, C.byref(h))
+        else:
+            self._call('create_n', *args, self.num_envs, C.byref(h))
+        self.h = h
 
     def _call(self, name, *args):
         check(getattr(lib, self.PREFIX + name)(*args), self.PREFIX[len('rlrep_'):] + name)
@@ -63,7 +83,7 @@ class _DeviceEnvBase(object):
     def reset(self):
         """Every member starts a fresh episode; ring cursors, counters and returns are zeroed (one launch)."""
         self._call('reset', self.h, _stream())
-        self._drained = [0] * self.R
+        self._drained = [0] * (self.R * self.num_envs)
         self.t_global, self.calls = 0, 0
 
     # ---- records --------------------------------------------------------------------------------------------------------------------
@@ -72,15 +92,18 @@ class _DeviceEnvBase(object):
         return arr
 
     def state(self):
-        """[R] records (RECORD_DTYPE), a host copy: synchronises the stream"""
-        return self._block(STATE_RECORDS, np.zeros(self.R, RECORD_DTYPE), False)
+        """[R] records (RECORD_DTYPE), [R, num_envs] with several environments; a host copy: synchronises the stream"""
+        return self._block(STATE_RECORDS, np.zeros(self._records_shape(), RECORD_DTYPE), False)
+
+    def _records_shape(self):
+        return (self.R,) if self.num_envs == 1 else (self.R, self.num_envs)
 
     def set_state(self, records):
         rec = np.ascontiguousarray(records, dtype=RECORD_DTYPE)
-        if rec.shape != (self.R,):
-            raise ValueError(f'{type(self).__name__}.set_state: needs {self.R} records')
+        if rec.shape != self._records_shape():
+            raise ValueError(f'{type(self).__name__}.set_state: needs {" x ".join(str(n) for n in self._records_shape())} records')
         self._block(STATE_RECORDS, rec, True)
-        self._drained = [int(n) for n in rec['episodes_done']]
+        self._drained = [int(n) for n in rec['episodes_done'].reshape(-1)]
 
     def counters(self):
         """(t_global, calls): steps since reset, and the select_action call counter the next exploring step continues from"""
@@ -93,11 +116,16 @@ class _DeviceEnvBase(object):
         self._block(STATE_COUNTERS, c, True)
         self.t_global, self.calls = int(t_global), int(calls)
 
-    def set_cursor(self, ptr, sizes):
-        """every member's ring cursor (the rings are filled in lockstep) and fill level, e.g. from a ReplayBufferGroup filled on the host"""
-        rec = self.state()
-        rec['ring_ptr'], rec['ring_size'] = int(ptr), np.asarray(sizes, np.int32).reshape(-1)
-        self._block(STATE_RECORDS, rec, True)
+    def set_cursor(self, ptr, sizes, capacity=None):
+        """every member's next free ring row (the rings are filled in lockstep) and fill level, e.g. from a ReplayBufferGroup filled on the
+        host.  Environment e's own cursor is (ptr + e) mod capacity: with several environments the ring's `capacity` is needed."""
+        if self.num_envs > 1 and (capacity is None or int(capacity) < self.num_envs):
+            raise ValueError(f'{type(self).__name__}.set_cursor: {self.num_envs} environments need the ring\'s capacity (at least {self.num_envs} rows)')
+        rec = self.state().reshape(self.R, self.num_envs)
+        cur = int(ptr) + np.arange(self.num_envs, dtype=np.int64)
+        rec['ring_ptr'] = (cur % int(capacity) if capacity else cur)[None, :]
+        rec['ring_size'] = np.asarray(sizes, np.int32).reshape(-1, 1)
+        self._block(STATE_RECORDS, rec.reshape(self._records_shape()), True)
 
     def eval_starts(self, episodes):
         """[R, episodes, 2] (theta, theta_dot) resp. (p, v): the start states of the last evaluation (rows of retired members are stale)"""
@@ -106,28 +134,33 @@ class _DeviceEnvBase(object):
     def returns(self):
         """R lists: the returns of the episodes each member has finished since the last call (at most the last 16 per member are kept on the
         device).  Synchronises the stream: call it where the loop looks at results anyway."""
-        rec = self.state()
+        rec = self.state().reshape(self.R, self.num_envs)
         out = []
         for r in range(self.R):
-            done, seen = int(rec['episodes_done'][r]), self._drained[r]
-            first = max(seen, done - RETURNS)
-            out.append([float(rec['returns'][r][k % RETURNS]) for k in range(first, done)])
-            self._drained[r] = done
+            got = []
+            for e in range(self.num_envs):                  # (environment by environment)
+                i = r * self.num_envs + e
+                done, seen = int(rec['episodes_done'][r, e]), self._drained[i]
+                first = max(seen, done - RETURNS)
+                got += [float(rec['returns'][r, e][k % RETURNS]) for k in range(first, done)]
+                self._drained[i] = done
+            out.append(got)
         return out
 
     # ---- checkpoints ----------------------------------------------------------------------------------------------------------------
     def snapshot(self):
         t, calls = self.counters()
         return {'kind': self.kind, 'form': self.FORM, 'records': torch.from_numpy(self.state().view(np.uint8).copy()), 't_global': t, 'calls': calls,
-                'eval_index': int(self.eval_index)}
+                'eval_index': int(self.eval_index), 'num_envs': self.num_envs}
 
     def load_snapshot(self, snap):
         if snap.get('form', 'group') != self.FORM:              # (snapshots written before single agents had device environments: a group's)
             raise RuntimeError(f'checkpoint does not match this device environment (it holds the environment of a {snap.get("form", "group")}, '
                                f'this one is the environment of a {self.FORM})')
-        if snap.get('kind') != self.kind or snap['records'].numel() != self.R * RECORD_DTYPE.itemsize:
-            raise RuntimeError('checkpoint does not match this device environment (kind / members differ)')
-        self.set_state(snap['records'].numpy().view(RECORD_DTYPE))
+        if (snap.get('kind') != self.kind or int(snap.get('num_envs', 1)) != self.num_envs          # (a snapshot from before num_envs: one environment)
+                or snap['records'].numel() != self.R * self.num_envs * RECORD_DTYPE.itemsize):
+            raise RuntimeError('checkpoint does not match this device environment (kind / members / num_envs differ)')
+        self.set_state(snap['records'].numpy().view(RECORD_DTYPE).reshape(self._records_shape()))
         self.set_counters(snap['t_global'], snap['calls'])
         self.eval_index = int(snap.get('eval_index', 0))
 
@@ -138,21 +171,21 @@ class DeviceEnvGroup(_DeviceEnvBase):
 
     PREFIX, FORM = 'rlrep_group_env_', 'group'
 
-    def __init__(self, agent, kind, eps_greedy=0.0, start_timesteps=0):
-        """eps_greedy: the probability of a uniform action in place of the policy's; start_timesteps: the warm-up, steps (counted since
-        reset) that take uniform actions only.  Both ride by value in a captured iterate() graph."""
+    def __init__(self, agent, kind, eps_greedy=0.0, start_timesteps=0, num_envs=1):
+        """eps_greedy: the probability of a uniform action in place of the policy's; start_timesteps: the warm-up, steps per member (counted
+        since reset) that take uniform actions only, a multiple of num_envs.  Both ride by value in a captured iterate() graph.
+        num_envs: environments per member, all stepped by one launch."""
         name = type(self).__name__
         if getattr(agent, 'R', None) is None or not hasattr(agent, 'seeds'):
             raise ValueError(f'{name}: needs a seed group (SACSeedBatch / CTRLSACSeedBatch)')
-        self._setup(agent, kind, eps_greedy, start_timesteps, agent.R)
-        h = C.c_void_p()
-        self._call('create', agent.core.h, self.kind, C.byref(h))
-        self.h = h
+        self._setup(agent, kind, eps_greedy, start_timesteps, agent.R, num_envs)
+        self._create(agent.core.h, self.kind)
         self.reset()
 
     # ---- launches -------------------------------------------------------------------------------------------------------------------
     def step(self, buffers, eps_greedy, start_timesteps):
-        """One step of every live member into `buffers` (a ReplayBufferGroup): ONE launch on the current stream, capturable."""
+        """One step of every environment of every live member into `buffers` (a ReplayBufferGroup): ONE launch on the current stream,
+        capturable."""
         lo, hi = self.agent.action_range
         self._call('step', self.agent.core.h, self.h, C.c_void_p(buffers.rings.data_ptr()), buffers.ring_stride, buffers.max_size,
                    C.c_void_p(buffers.size_dev().data_ptr()), lo, hi, float(eps_greedy), int(start_timesteps), _stream())
@@ -170,19 +203,17 @@ class DeviceEnv(_DeviceEnvBase):
 
     PREFIX, FORM = 'rlrep_env_', 'single'
 
-    def __init__(self, agent, kind, eps_greedy=0.0, start_timesteps=0):
+    def __init__(self, agent, kind, eps_greedy=0.0, start_timesteps=0, num_envs=1):
         name = type(self).__name__
         if getattr(agent, 'R', None) is not None or not hasattr(agent, '_seed'):
             raise ValueError(f'{name}: needs a single agent (a seed group takes DeviceEnvGroup)')
-        self._setup(agent, kind, eps_greedy, start_timesteps, 1)
+        self._setup(agent, kind, eps_greedy, start_timesteps, 1, num_envs)
         self.seed = int(agent._seed)            # the Philox key of every draw: what the agent's select_action draws with
-        h = C.c_void_p()
-        self._call('create', agent.core.h, self.kind, self.seed, C.byref(h))
-        self.h = h
+        self._create(agent.core.h, self.kind, self.seed)
         self.reset()
 
     def step(self, buffer, eps_greedy, start_timesteps):
-        """One step into `buffer` (a ReplayBuffer): ONE launch on the current stream, capturable."""
+        """One step of every environment into `buffer` (a ReplayBuffer): ONE launch on the current stream, capturable."""
         lo, hi = self.agent.action_range
         self._call('step', self.agent.core.h, self.h, C.c_void_p(buffer.ring.data_ptr()), buffer.max_size, C.c_void_p(buffer._size_dev.data_ptr()),
                    lo, hi, float(eps_greedy), int(start_timesteps), _stream())
@@ -197,8 +228,8 @@ class DevicePendulumGroup(DeviceEnvGroup):
 
     max_episode_steps = EPISODE_STEPS
 
-    def __init__(self, agent, eps_greedy=0.0, start_timesteps=0):
-        super().__init__(agent, KIND_PENDULUM, eps_greedy, start_timesteps)
+    def __init__(self, agent, eps_greedy=0.0, start_timesteps=0, num_envs=1):
+        super().__init__(agent, KIND_PENDULUM, eps_greedy, start_timesteps, num_envs)
 
 
 class DeviceMountainCarGroup(DeviceEnvGroup):
@@ -207,22 +238,22 @@ class DeviceMountainCarGroup(DeviceEnvGroup):
 
     max_episode_steps = 999
 
-    def __init__(self, agent, eps_greedy=0.0, start_timesteps=0):
-        super().__init__(agent, KIND_MOUNTAIN_CAR_CONTINUOUS, eps_greedy, start_timesteps)
+    def __init__(self, agent, eps_greedy=0.0, start_timesteps=0, num_envs=1):
+        super().__init__(agent, KIND_MOUNTAIN_CAR_CONTINUOUS, eps_greedy, start_timesteps, num_envs)
 
 
 class DevicePendulum(DeviceEnv):
     """Pendulum-v1 for a single agent"""
 
-    def __init__(self, agent, eps_greedy=0.0, start_timesteps=0):
-        super().__init__(agent, KIND_PENDULUM, eps_greedy, start_timesteps)
+    def __init__(self, agent, eps_greedy=0.0, start_timesteps=0, num_envs=1):
+        super().__init__(agent, KIND_PENDULUM, eps_greedy, start_timesteps, num_envs)
 
 
 class DeviceMountainCar(DeviceEnv):
     """MountainCarContinuous-v0 for a single agent"""
 
-    def __init__(self, agent, eps_greedy=0.0, start_timesteps=0):
-        super().__init__(agent, KIND_MOUNTAIN_CAR_CONTINUOUS, eps_greedy, start_timesteps)
+    def __init__(self, agent, eps_greedy=0.0, start_timesteps=0, num_envs=1):
+        super().__init__(agent, KIND_MOUNTAIN_CAR_CONTINUOUS, eps_greedy, start_timesteps, num_envs)
 
 
 def device_class(env_name):

@@ -38,6 +38,10 @@ come from Philox streams of the members' seeds, so a run differs from the host l
 `--device-loop` (one agent of any --alg, no --seeds / --sweep, --env Pendulum-v1 or MountainCarContinuous-v0) is the same for a single agent:
 `SACAgent.iterate` is one graph replay per step and `SACAgent.evaluate` one launch per evaluation, for sac, vlsac, ctrlsac, spedersac and
 diffsrsac alike; --save_model writes the environment's record with the checkpoint.
+
+`--num-envs E` (with --device-env or --device-loop; 1..64, default 1; --start_timesteps and --eval_freq multiples of E) gives every member /
+the agent E environments stepped by the same launch: one `iterate` collects E transitions per member and trains once, so the loop counter
+advances by E and --max_timesteps stays environment steps per member.  E environments with one update per step is 1/E updates per transition.
 """
 import argparse
 import json
@@ -111,7 +115,12 @@ def run(argv=None):
                    help='step and score the environments on the device (with --seeds / --sweep and --env Pendulum-v1 or MountainCarContinuous-v0): rlrep_amd/envs/device.py')
     p.add_argument('--device-loop', action='store_true',
                    help='a single agent of any --alg with its environment on the device (--env Pendulum-v1 or MountainCarContinuous-v0): SACAgent.iterate / evaluate')
+    p.add_argument('--num-envs', default=1, type=int,
+                   help='environments per member / agent on the device, stepped by one launch (with --device-env or --device-loop; 1..64; '
+                        '--start_timesteps and --eval_freq multiples of it).  One iterate collects E transitions and trains once: E environments '
+                        'with one update per step is 1/E updates per transition')
     args = p.parse_args(argv)
+    _check_num_envs(args)
     if args.device_loop:
         _check_device_loop(args)
     if args.seeds is not None or args.sweep:
@@ -187,6 +196,18 @@ def run(argv=None):
     return agent, evaluations
 
 
+def _check_num_envs(args):
+    """--num-envs: SystemExit, before anything touches the GPU, on what it does not run with"""
+    E = int(args.num_envs)
+    if E != 1 and not (args.device_env or args.device_loop):
+        raise SystemExit('--num-envs: several environments per agent are stepped on the device; give --device-env (seed groups) or --device-loop (one agent)')
+    if not 1 <= E <= 64:
+        raise SystemExit(f'--num-envs {E}: outside [1, 64]')
+    for flag, value in (('--start_timesteps', args.start_timesteps), ('--eval_freq', args.eval_freq)):
+        if value != int(value) or int(value) % E:
+            raise SystemExit(f'--num-envs {E}: {flag} {value:g} is not a multiple of it (a step launch takes {E} steps per member at once)')
+
+
 def _check_device_loop(args):
     """--device-loop is the single agent's device environment; SystemExit, before anything touches the GPU, on what it does not run with"""
     for flag, given in (('--seeds', args.seeds is not None), ('--sweep', bool(args.sweep)), ('--pbt-*', _pbt_requested(args)),
@@ -205,13 +226,15 @@ def _single_device_loop(args, agent, replay, log_path, jsonl, tb):
     --eval_freq.  The exploration and reset draws are Philox streams of the agent's seed instead of NumPy generators; the metrics.jsonl rows
     keep their keys, and --save_model writes the environment's record with the checkpoint."""
     from rlrep_amd.envs.device import single_device_class
-    env = single_device_class(args.env)(agent, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps))
+    E = int(args.num_envs)
+    env = single_device_class(args.env)(agent, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps), num_envs=E)
     evaluations = [agent.evaluate(env, args.eval_episodes)]
     info = None
     timer = util.Timer()
-    for t in range(int(args.max_timesteps)):
-        out = agent.iterate(env, replay, args.batch_size, train=t >= args.start_timesteps)
+    for t0 in range(0, int(args.max_timesteps), E):            # one iterate is E environment steps
+        out = agent.iterate(env, replay, args.batch_size, train=t0 >= args.start_timesteps)
         info = out if out is not None else info
+        t = t0 + E - 1
         if (t + 1) % args.eval_freq == 0:
             sps = timer.steps_per_sec(t + 1)
             evaluations.append(agent.evaluate(env, args.eval_episodes))
@@ -547,13 +570,15 @@ def _device_loop(args, agent, replay, ev):
     Philox streams of the members' seeds instead of NumPy generators, and an evaluation's start states are a function of (seed, evaluation
     index, episode); the metrics.jsonl / pbt.jsonl / halving.jsonl rows keep their keys."""
     from rlrep_amd.envs.device import device_class
-    env = device_class(args.env)(agent, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps))
+    E = int(args.num_envs)
+    env = device_class(args.env)(agent, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps), num_envs=E)
     ev.evaluations = [[float(s)] for s in agent.evaluate(env, args.eval_episodes)]
     infos = None
     timer = util.Timer()
-    for t in range(int(args.max_timesteps)):
-        out = agent.iterate(env, replay, args.batch_size, train=t >= args.start_timesteps)
+    for t0 in range(0, int(args.max_timesteps), E):            # one iterate is E environment steps of every live member
+        out = agent.iterate(env, replay, args.batch_size, train=t0 >= args.start_timesteps)
         infos = out if out is not None else infos
+        t = t0 + E - 1
         if (t + 1) % args.eval_freq == 0:
             sps = timer.steps_per_sec(t + 1)
             ev.step(t + 1, sps, [float(s) for s in agent.evaluate(env, args.eval_episodes)], infos, env=env)

@@ -124,7 +124,10 @@ class ReplayBuffer(object):
                              'writes every row it steps')
         self.flush()
         self.size_dev()
-        env.set_cursor(self.ptr, [self.size])
+        if getattr(env, 'num_envs', 1) > 1:          # (environment e's cursor is (ptr + e) mod max_size)
+            env.set_cursor(self.ptr, [self.size], self.max_size)
+        else:
+            env.set_cursor(self.ptr, [self.size])
         self._device_env = env
 
     def adopt_device_cursor(self):
@@ -133,7 +136,7 @@ class ReplayBuffer(object):
         env = self._device_env
         if env is None:
             return
-        rec = env.state()
+        rec = env.state().reshape(-1)                # (environment 0's cursor is the next free row)
         self.ptr = int(rec['ring_ptr'][0]) % self.max_size
         self.size = int(rec['ring_size'][0])
         self._size_pushed = self.size               # (the step launches have published it)

@@ -116,7 +116,10 @@ class ReplayBufferGroup(object):
             raise RuntimeError('ReplayBufferGroup.collect_on_device: another device environment owns the cursor (adopt_device_cursor() first)')
         self.flush()
         self.size_dev()
-        env.set_cursor(self.ptr, self.sizes)
+        if getattr(env, 'num_envs', 1) > 1:          # (environment e's cursor is (ptr + e) mod max_size)
+            env.set_cursor(self.ptr, self.sizes, self.max_size)
+        else:
+            env.set_cursor(self.ptr, self.sizes)
         self._device_env = env
 
     def adopt_device_cursor(self):
@@ -126,7 +129,7 @@ class ReplayBufferGroup(object):
         env = self._device_env
         if env is None:
             return
-        rec = env.state()
+        rec = env.state().reshape(self.members, -1)[:, 0]           # (environment 0's cursor is the member's next free row)
         ptrs = sorted(set(int(p) for p in rec['ring_ptr']))
         if len(ptrs) != 1:
             raise RuntimeError(f'ReplayBufferGroup.adopt_device_cursor: the members\' ring cursors differ ({ptrs}): the host ring takes one row per '

@@ -17,6 +17,13 @@ Evaluation: util.eval_policy per member (as run_seeds scores) against SeedBatchM
 past warm-up (select_action, NumPy step, ReplayBuffer.add, train() in the form the agent picks).  Device loop: SACAgent.iterate.  Bare train():
 the ONE-GRAPH train() (an agent built with pipeline=False) on a ring a device loop filled.  The same alternation and windows; one evaluation
 by util.eval_policy against SACAgent.evaluate.
+
+    python tools/device_env_rate.py --alg sac --members 4 --num-envs 1,4,16,64
+    python tools/device_env_rate.py --single --alg vlsac --batch 256 --num-envs 1,4,16,64 --calls 300
+
+--num-envs E1,E2,...: the device loop with E environments per member / agent (DeviceEnvGroup / DeviceEnv num_envs) for every E of the list and
+the bare train(), arms alternated in the same windows: us per iterate, iterate - train(), environment steps per second per member (E per
+iterate) and the spread of the windows.  No host loop and no evaluation in this form.
 """
 import argparse
 import os
@@ -93,14 +100,14 @@ class HostLoop(object):
 
 
 class DeviceLoop(object):
-    def __init__(self, alg, seeds, B):
+    def __init__(self, alg, seeds, B, num_envs=1):
         from rlrep_amd.envs.device import device_class
         from rlrep_amd.utils.buffer_group import ReplayBufferGroup
         self.R, self.B = len(seeds), B
         self.agent = _group(alg, seeds, B)
         S, A, _, _ = _dims()
         self.replay = ReplayBufferGroup(self.R, S, A, max_size=100000)
-        self.env = device_class(ENV)(self.agent, eps_greedy=EPS_GREEDY, start_timesteps=0)
+        self.env = device_class(ENV)(self.agent, eps_greedy=EPS_GREEDY, start_timesteps=0, num_envs=num_envs)
 
     def step(self):
         self.agent.iterate(self.env, self.replay, self.B)
@@ -173,14 +180,14 @@ class SingleHostLoop(object):
 
 
 class SingleDeviceLoop(object):
-    def __init__(self, alg, B, **extra):
+    def __init__(self, alg, B, num_envs=1, **extra):
         from rlrep_amd.envs.device import single_device_class
         from rlrep_amd.utils.buffer import ReplayBuffer
         self.B = B
         self.agent = _single(alg, B, **extra)
         S, A, _, _ = _dims()
         self.replay = ReplayBuffer(S, A, max_size=100000)
-        self.env = single_device_class(ENV)(self.agent, eps_greedy=EPS_GREEDY, start_timesteps=0)
+        self.env = single_device_class(ENV)(self.agent, eps_greedy=EPS_GREEDY, start_timesteps=0, num_envs=num_envs)
 
     def step(self):
         self.agent.iterate(self.env, self.replay, self.B)
@@ -232,6 +239,33 @@ def single_main(args):
     print(f'{alg} single one evaluation ({args.eval_episodes} episodes): util.eval_policy {1e3 * mh:.1f} ms, evaluate {1e3 * md:.2f} ms ({mh / md:.0f}x)', flush=True)
 
 
+def num_envs_main(args):
+    """--num-envs: iterate at every E of the list against the bare train(), one table per group size (or for the single agent)"""
+    Es = [int(v) for v in args.num_envs.split(',')]
+    alg, B = args.alg, args.batch
+    print(f'# {torch.cuda.get_device_name(0)}; {alg} {ENV} B = {B}; {args.warmup} warm-up iterations, median (min .. max) of '
+          f'{args.windows} windows of {args.calls} iterations, arms alternated in one process')
+    for R in ([None] if args.single else [int(v) for v in args.members.split(',')]):
+        if R is None:
+            arms = {'train': SingleTrainOnly(alg, B)}
+            arms.update({E: SingleDeviceLoop(alg, B, num_envs=E) for E in Es})
+            tag = f'{alg} single'
+        else:
+            seeds = list(range(R))
+            arms = {'train': TrainOnly(alg, seeds, B)}
+            arms.update({E: DeviceLoop(alg, seeds, B, num_envs=E) for E in Es})
+            tag = f'{alg} R={R:2d}'
+        rates = _windows(arms, args.warmup, args.calls, args.windows)
+        us = {k: sorted(1e6 / r for r in v) for k, v in rates.items()}
+        med = {k: statistics.median(v) for k, v in us.items()}
+        print(f'{tag} bare {"one-graph " if R is None else ""}train(): {med["train"]:8.1f} us (windows {", ".join(f"{u:.1f}" for u in us["train"])})')
+        for E in Es:
+            print(f'{tag} num_envs {E:2d}: iterate {med[E]:8.1f} us (windows {", ".join(f"{u:.1f}" for u in us[E])}); iterate - train() '
+                  f'{med[E] - med["train"]:6.1f} us; {E * 1e6 / med[E]:9.0f} environment steps/s per member; graph: '
+                  f'{arms[E].agent._iter_launches} launches, step grid {E} x {R or 1} workgroups', flush=True)
+        del arms
+
+
 def _windows(arms, warmup, calls, windows):
     for a in arms.values():
         for _ in range(warmup):
@@ -261,9 +295,14 @@ def main(argv=None):
     p.add_argument('--eval-episodes', type=int, default=10)
     p.add_argument('--eval-repeats', type=int, default=3)
     p.add_argument('--env', default='Pendulum-v1', choices=['Pendulum-v1', 'MountainCarContinuous-v0'])
+    p.add_argument('--num-envs', default=None, help='comma-separated environments per member / agent: the device loop at each against the bare train()')
     args = p.parse_args(argv)
     global ENV
     ENV = args.env
+    if args.num_envs is not None:
+        if not args.single and args.alg not in ('sac', 'ctrlsac'):
+            raise SystemExit(f'--alg {args.alg}: seed groups are built for sac and ctrlsac (give --single)')
+        return num_envs_main(args)
     if args.single:
         return single_main(args)
     if args.alg not in ('sac', 'ctrlsac'):
