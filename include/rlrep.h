@@ -333,6 +333,17 @@ int32_t rlrep_actor_forward(rlrep_agent* agent, const float* obs_dev, int32_t n,
 int32_t rlrep_select_action(rlrep_agent* agent, const float* obs, int32_t obs_on_host, int32_t explore, uint64_t seed, uint64_t offset,
                             float lo, float hi, float* action, int32_t action_on_host, void* stream);
 
+/* rlrep_select_action for `rows` observations in ONE launch (additive to ABI 4; vector host environments, parallel evaluation episodes): one
+ * workgroup per row.  Row e reads obs[e * S ..], writes action[e * A ..] and draws at offset + (e << 20): with offset = c << 20 that is E
+ * successive rlrep_select_action calls at call counters c, c + 1, ... in row order, and every row is bit for bit what rlrep_select_action
+ * computes for that observation at that offset (same kernel body, same summation order; rows == 1 gives its bytes).  obs [rows, S] /
+ * action [rows, A]: device pointers or (the *_on_host flags) pinned host buffers read / written in place.  rows in [1,
+ * RLREP_SELECT_MAX_ROWS] (at most one workgroup per CU).  Refused with RLREP_ERR_ARG before anything is launched, the message starting
+ * with "select_action_n:": a null argument, rows outside the range, a seed group's handle, a *_on_host buffer that is not pinned. */
+#define RLREP_SELECT_MAX_ROWS 256
+int32_t rlrep_select_action_n(rlrep_agent* agent, const float* obs, int32_t obs_on_host, int32_t rows, int32_t explore, uint64_t seed,
+                              uint64_t offset, float lo, float hi, float* action, int32_t action_on_host, void* stream);
+
 /* ---- metrics ------------------------------------------------------------------------------ */
 /* device float array of n_metrics slots, valid after the stream has passed the producing step */
 const float* rlrep_metrics_dev(rlrep_agent* agent);
@@ -581,6 +592,13 @@ int32_t rlrep_group_prepare(rlrep_agent* agent, int32_t batch);
  * rlrep_fill_normal(eps[A], 1, seeds[r], offset), as a standalone agent with seed seeds[r] draws it.  (reference agent/sac/sac_agent.py:89-96) */
 int32_t rlrep_group_select_action(rlrep_agent* agent, const float* obs_host, int32_t explore, uint64_t offset, float lo, float hi,
                                   float* action_host, void* stream);
+/* rlrep_group_select_action for `rows` observations per member in ONE launch (grid (rows, members); additive to ABI 4): member r's row e reads
+ * obs_host[(r * rows + e) * S ..], writes action_host[(r * rows + e) * A ..] (both pinned) and draws rlrep_fill_normal(eps[A], 1, seeds[r],
+ * offset + (e << 20)) -- what standalone agent r's e-th of `rows` successive select_action calls draws.  A retired member's rows are neither
+ * read nor written.  rows in [1, RLREP_SELECT_MAX_ROWS]; refused before any launch, "group_select_action_n:" first: a null argument, rows
+ * outside the range, a handle that is not a seed group, unpinned buffers. */
+int32_t rlrep_group_select_action_n(rlrep_agent* agent, const float* obs_host, int32_t rows, int32_t explore, uint64_t offset, float lo, float hi,
+                                    float* action_host, void* stream);
 /* rlrep_replay_add_sized for `members` rings ring_dev + r * ring_stride_floats, in ONE launch: member r's nrows staged rows start at
  * rows_host + r * rows_stride_floats (pinned), its fill level goes to size_dev[r]. */
 int32_t rlrep_group_replay_add_sized(float* ring_dev, int64_t ring_stride_floats, int32_t members, int64_t capacity, int32_t row_floats, int64_t ptr,

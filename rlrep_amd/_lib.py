@@ -158,6 +158,8 @@ def _load():
         'rlrep_sync_frozen': (i32, [vp, vp]),
         'rlrep_actor_forward': (i32, [vp, vp, i32, vp, f32, f32, vp, vp]),
         'rlrep_select_action': (i32, [vp, vp, i32, i32, u64, u64, f32, f32, vp, i32, vp]),
+        'rlrep_select_action_n': (i32, [vp, vp, i32, i32, i32, u64, u64, f32, f32, vp, i32, vp]),
+        'rlrep_group_select_action_n': (i32, [vp, vp, i32, i32, u64, f32, f32, vp, vp]),
         'rlrep_images_managed': (i32, [vp, i32]),
         'rlrep_refresh_images': (i32, [vp, vp]),
         'rlrep_feature_chain_next': (i32, [vp]),

@@ -19,6 +19,7 @@ from rlrep_amd.utils import util
 from rlrep_amd.utils.streams import raw_stream as _raw_stream, current_stream as _current_stream, on_stream as _on_stream
 
 device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
+SELECT_MAX_ROWS = 256         # include/rlrep.h RLREP_SELECT_MAX_ROWS: observations per select_actions launch
 
 
 @contextlib.contextmanager
@@ -359,6 +360,29 @@ class SACAgent(object):
         sel['act_pin'].copy_(sel['out'], non_blocking=True)
         _current_stream().synchronize()
         return sel['act_pin'].numpy()[0].copy()
+
+    def select_actions(self, states, explore=False):
+        """states [E, S] -> actions [E, A] in ONE launch and one stream synchronisation (rlrep_select_action_n, one workgroup per row): row e is
+        bit for bit what select_action(states[e], explore) returns as the e-th of E successive calls -- with `explore`, row e draws at call
+        counter _ctr + 1 + e and the counter then advances by E (the device environments' convention); without it the counter stands still.
+        Pinned buffers are kept per E."""
+        self.flush()
+        states = np.asarray(states, dtype=np.float32)
+        if states.ndim != 2 or states.shape[1] != self.state_dim or not 1 <= states.shape[0] <= SELECT_MAX_ROWS:
+            raise ValueError(f'{type(self).__name__}.select_actions: states {states.shape} is not [E, {self.state_dim}] with E in [1, {SELECT_MAX_ROWS}]')
+        E = states.shape[0]
+        bufs = self.__dict__.setdefault('_sel_n', {})
+        sel = bufs.get(E)
+        if sel is None:
+            sel = bufs[E] = (torch.empty(E, self.state_dim, dtype=torch.float32).pin_memory(),
+                             torch.empty(E, self.action_dim, dtype=torch.float32).pin_memory())
+        obs, act = sel
+        obs.numpy()[:] = states
+        self.core.select_action_n(obs, E, explore, self._seed, (self._ctr + 1) << 20 if explore else 0, *self.action_range, act)
+        if explore:
+            self._ctr += E
+        _current_stream().synchronize()
+        return act.numpy().copy()
 
     def update_target(self):
         self.flush()

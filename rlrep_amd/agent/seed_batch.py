@@ -7,7 +7,7 @@ cost one train() graph of exactly one agent's launch count, not R of them.
 
 SeedBatchMixin goes in front of the standalone agent class (SACSeedBatch(SeedBatchMixin, SACAgent), CTRLSACSeedBatch(SeedBatchMixin,
 CTRLSACAgent)): member cores, the train() pools inside the member block, the group train prologue, select_action for every member in one
-launch, member export and checkpoints.  Initialisation rule: member r is initialised exactly as `torch.manual_seed(seeds[r]); Agent(...,
+launch (select_actions: for E observations per member), member export and checkpoints.  Initialisation rule: member r is initialised exactly as `torch.manual_seed(seeds[r]); Agent(...,
 seed=seeds[r])` initialises, and draws its sample indices and noise from the Philox stream of seed seeds[r].
 
 Sweeps: `member_hyper=[dict, ...]` (one dict per member) lets members differ in the hyper-parameters no launch's shape depends on (SWEEP_KEYS:
@@ -36,7 +36,7 @@ import torch
 
 from rlrep_amd._lib import lib, check
 from rlrep_amd.core import HipCore, _stream
-from rlrep_amd.agent.sac.sac_agent import ArenaModule, _no_gc
+from rlrep_amd.agent.sac.sac_agent import ArenaModule, SELECT_MAX_ROWS, _no_gc
 from rlrep_amd.utils import switches as _sw
 
 
@@ -507,6 +507,34 @@ class SeedBatchMixin(object):
                                             C.c_void_p(sel['act'].data_ptr()), _stream()), 'group_select_action')
         torch.cuda.current_stream().synchronize()
         return sel['act'].numpy().copy()
+
+    def select_actions(self, states, explore=False):
+        """states [R, E, S] -> actions [R, E, A]: ONE launch over pinned buffers (rlrep_group_select_action_n, grid (E, R)).  [r, e] is what the
+        standalone agent with seed seeds[r] returns as the e-th of E successive select_action calls: with `explore`, row e draws at call
+        counter _ctr + 1 + e and the counter then advances by E; without it the counter stands still.  A retired member's observations are
+        not read and its rows are zeros."""
+        states = np.asarray(states, dtype=np.float32)
+        if states.ndim != 3 or states.shape[0] != self.R or states.shape[2] != self.state_dim or not 1 <= states.shape[1] <= SELECT_MAX_ROWS:
+            raise ValueError(f'{type(self).__name__}.select_actions: states {states.shape} is not [{self.R}, E, {self.state_dim}] with E in '
+                             f'[1, {SELECT_MAX_ROWS}]')
+        E = states.shape[1]
+        bufs = self.__dict__.setdefault('_gsel_n', {})
+        sel = bufs.get(E)
+        if sel is None:
+            sel = bufs[E] = (torch.empty(self.R, E, self.state_dim, dtype=torch.float32).pin_memory(),
+                             torch.empty(self.R, E, self.action_dim, dtype=torch.float32).pin_memory())
+        obs, act = sel
+        obs.numpy()[:] = states
+        for r in range(self.R):
+            if not self._live[r]:
+                act.numpy()[r] = 0.0            # (the launch leaves a retired member's rows unwritten)
+        lo, hi = self.action_range
+        check(lib.rlrep_group_select_action_n(self.core.h, C.c_void_p(obs.data_ptr()), E, 1 if explore else 0, (self._ctr + 1) << 20 if explore else 0,
+                                              lo, hi, C.c_void_p(act.data_ptr()), _stream()), 'group_select_action_n')
+        if explore:
+            self._ctr += E
+        torch.cuda.current_stream().synchronize()
+        return act.numpy().copy()
 
     def member_snapshot(self, r):
         """Member r as a checkpoint of the standalone agent class (its load() accepts it): continue one seed alone."""

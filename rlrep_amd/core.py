@@ -423,6 +423,11 @@ class HipCore:
         """One observation -> one action in one launch; both buffers pinned host tensors the kernel reads / writes in place (rlrep_select_action)."""
         check(lib.rlrep_select_action(self.h, _ptr(obs_pin), 1, 1 if explore else 0, int(seed), int(offset), float(lo), float(hi), _ptr(act_pin), 1, _stream()), 'select_action')
 
+    def select_action_n(self, obs_pin, rows, explore, seed, offset, lo, hi, act_pin):
+        """`rows` observations -> `rows` actions in one launch, row e drawing at offset + (e << 20); pinned [rows, S] / [rows, A] (rlrep_select_action_n)."""
+        check(lib.rlrep_select_action_n(self.h, _ptr(obs_pin), 1, int(rows), 1 if explore else 0, int(seed), int(offset), float(lo), float(hi), _ptr(act_pin), 1,
+                                        _stream()), 'select_action_n')
+
     # ---- noise --------------------------------------------------------------------------------
     def fill_normal(self, t, std, seed, offset):
         check(lib.rlrep_fill_normal(_ptr(t), t.numel(), float(std), int(seed), int(offset), _stream()), 'fill_normal')

@@ -207,6 +207,29 @@ __global__ __launch_bounds__(1024) void select_action_kernel_grp(SelectAct p0, l
     p.seed = seeds[m];
 #include "select_action_body.h"
 }
+// SACAgent.select_actions: E = gridDim.x observations in ONE launch, one observation row per workgroup -- workgroup e acts on obs + e * S, writes
+// act + e * A and draws at offset + (e << 20), i.e. at call counter c + e when the caller passes c << 20: E successive select_action calls in
+// row order (the device environments' convention, group_env.h).  The body is select_action_kernel's: row e is bit for bit that kernel's
+// action for the same observation at that offset, in the same summation order and with the same latency.
+__global__ __launch_bounds__(1024) void select_action_kernel_n(SelectAct p0) {
+    const long long e = blockIdx.x;
+    SelectAct p = p0;
+    p.obs += e * p.S; p.act += e * p.A;
+    p.offset += (unsigned long long)e << 20;
+#include "select_action_body.h"
+}
+// group form: workgroup (e, slot) is row e of member m -- observation and action row m * E + e, the member's actor and seed
+__global__ __launch_bounds__(1024) void select_action_kernel_grp_n(SelectAct p0, long long mstride, const unsigned long long* __restrict__ seeds, const int* __restrict__ live) {
+    RL_GRP_MEMBER(m, live);
+    const long long dm = (long long)m * mstride;
+    const long long row = (long long)m * gridDim.x + blockIdx.x;
+    SelectAct p = p0;
+    p.obs += row * p.S; p.act += row * p.A;
+    p.offset += (unsigned long long)blockIdx.x << 20;
+    rl_rb(p.W1, dm); rl_rb(p.b1, dm); rl_rb(p.W2, dm); rl_rb(p.b2, dm); rl_rb(p.W3, dm); rl_rb(p.b3, dm);
+    p.seed = seeds[m];
+#include "select_action_body.h"
+}
 
 // gradient of the actor loss w.r.t. the trunk output [mu | rho]; h = dL/d(action) from the critic path
 __global__ __launch_bounds__(256) void policy_bwd_kernel(PolicyBwd p) {
@@ -706,6 +729,17 @@ extern "C" int rl_launch_select_action(const SelectAct* p, hipStream_t st) {
         hipLaunchKernelGGL(select_action_kernel_grp, dim3(1, gr->grid_y), dim3(1024), lds, st, *p, gr->stride, gr->seeds, gr->live);
     } else
         hipLaunchKernelGGL(select_action_kernel, dim3(1), dim3(1024), lds, st, *p);
+    return (int)hipGetLastError();
+}
+// `rows` observations (per member while a group is active) in one launch: grid x = rows.  The LDS rule and the -7 refusal are the one-row launcher's.
+extern "C" int rl_launch_select_action_n(const SelectAct* p, int rows, hipStream_t st) {
+    const size_t lds = sizeof(float) * ((size_t)p->S + 2 * (size_t)p->Ha + 2 * (size_t)p->A);
+    if (lds > 60 * 1024) return -7;
+    if (const RlGrp* gr = rl_grp_active()) {
+        if (!gr->seeds) return RL_GRP_UNSUPPORTED;
+        hipLaunchKernelGGL(select_action_kernel_grp_n, dim3(rows, gr->grid_y), dim3(1024), lds, st, *p, gr->stride, gr->seeds, gr->live);
+    } else
+        hipLaunchKernelGGL(select_action_kernel_n, dim3(rows), dim3(1024), lds, st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_policy_bwd(const PolicyBwd* p, hipStream_t st) {

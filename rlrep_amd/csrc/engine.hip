@@ -922,6 +922,28 @@ int32_t rlrep_select_action(rlrep_agent* ag, const float* obs, int32_t obs_on_ho
     return 0;
 }
 
+// `rows` observations -> `rows` actions in ONE launch (select_action_kernel_n: one workgroup per row).  Everything is refused before the launch;
+// rlrep_select_action and its launcher stay as they are.
+int32_t rlrep_select_action_n(rlrep_agent* ag, const float* obs, int32_t obs_on_host, int32_t rows, int32_t explore, uint64_t seed, uint64_t offset,
+                              float lo, float hi, float* action, int32_t action_on_host, void* stream) {
+    if (!ag || !obs || !action) { rl_set_error("select_action_n: bad argument (null agent, observations or actions)"); return RLREP_ERR_ARG; }
+    if (rows < 1 || rows > RLREP_SELECT_MAX_ROWS) { rl_set_error("select_action_n: rows %d outside [1, %d]", rows, RLREP_SELECT_MAX_ROWS); return RLREP_ERR_ARG; }
+    GROUP_REFUSE("select_action_n")
+    SelectAct p; memset(&p, 0, sizeof(p));
+    void* d = nullptr;
+    if (obs_on_host) { if (hipHostGetDevicePointer(&d, const_cast<float*>(obs), 0) != hipSuccess || !d) { (void)hipGetLastError(); rl_set_error("select_action_n: the observation buffer is not mapped (pinned) host memory"); return RLREP_ERR_ARG; } p.obs = (const float*)d; }
+    else p.obs = obs;
+    if (action_on_host) { if (hipHostGetDevicePointer(&d, action, 0) != hipSuccess || !d) { (void)hipGetLastError(); rl_set_error("select_action_n: the action buffer is not mapped (pinned) host memory"); return RLREP_ERR_ARG; } p.act = (float*)d; }
+    else p.act = action;
+    p.W1 = ag->P("actor.trunk.0.weight"); p.b1 = ag->P("actor.trunk.0.bias"); p.W2 = ag->P("actor.trunk.2.weight"); p.b2 = ag->P("actor.trunk.2.bias");
+    p.W3 = ag->P("actor.trunk.4.weight"); p.b3 = ag->P("actor.trunk.4.bias");
+    p.S = ag->d.state_dim; p.Ha = ag->d.actor_hidden_dim; p.A = ag->d.action_dim; p.explore = explore ? 1 : 0; p.lo = lo; p.hi = hi; p.seed = seed; p.offset = offset;
+    ++g_rl_launches;
+    const int rc = rl_launch_select_action_n(&p, rows, (hipStream_t)stream);
+    if (rc) { rl_set_error("select_action_n: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    return 0;
+}
+
 static Program* prog_of(rlrep_agent* ag, int id) {
     switch (id) {
     case 0: return &ag->feat_bwd; case 1: return &ag->feat_apply; case 2: return &ag->critic_bwd; case 3: return &ag->critic_apply;

@@ -259,6 +259,25 @@ int32_t rlrep_group_select_action(rlrep_agent* ag, const float* obs_host, int32_
     if (rc) { rl_set_error("group_select_action: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
     return 0;
 }
+// `rows` observations per member in ONE launch (select_action_kernel_grp_n): obs_host [members, rows, S], action_host [members, rows, A]
+int32_t rlrep_group_select_action_n(rlrep_agent* ag, const float* obs_host, int32_t rows, int32_t explore, uint64_t offset, float lo, float hi, float* action_host,
+                                    void* stream) {
+    if (!ag || !obs_host || !action_host) { rl_set_error("group_select_action_n: bad argument (null agent, observations or actions)"); return RLREP_ERR_ARG; }
+    if (rows < 1 || rows > RLREP_SELECT_MAX_ROWS) { rl_set_error("group_select_action_n: rows %d outside [1, %d]", rows, RLREP_SELECT_MAX_ROWS); return RLREP_ERR_ARG; }
+    GROUP_ONLY("group_select_action_n")
+    SelectAct p; group_actor(ag, p, lo, hi);
+    void* d = nullptr;
+    if (hipHostGetDevicePointer(&d, const_cast<float*>(obs_host), 0) != hipSuccess || !d) { (void)hipGetLastError(); rl_set_error("group_select_action_n: the observations are not mapped (pinned) host memory"); return RLREP_ERR_ARG; }
+    p.obs = (const float*)d;
+    if (hipHostGetDevicePointer(&d, action_host, 0) != hipSuccess || !d) { (void)hipGetLastError(); rl_set_error("group_select_action_n: the action buffer is not mapped (pinned) host memory"); return RLREP_ERR_ARG; }
+    p.act = (float*)d;
+    p.explore = explore ? 1 : 0; p.seed = 0; p.offset = offset;
+    GrpScope grp_scope_(ag);
+    ++g_rl_launches;
+    const int rc = rl_launch_select_action_n(&p, rows, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_select_action_n: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    return 0;
+}
 int32_t rlrep_group_replay_add_sized(float* ring_dev, int64_t ring_stride_floats, int32_t members, int64_t capacity, int32_t row_floats, int64_t ptr,
                                      const float* rows_host, int64_t rows_stride_floats, int64_t nrows, int32_t* size_dev, int32_t new_size, void* stream) {
     if (!ring_dev || !rows_host || members < 1 || members > RLREP_GROUP_MAX_MEMBERS || capacity <= 0 || row_floats <= 0 || ring_stride_floats < capacity * row_floats ||

@@ -66,6 +66,7 @@ int rl_launch_copy(const float* src, float* dst, long long n, hipStream_t st);
 int rl_launch_copy_segs(const CopySegs* p, hipStream_t st);
 int rl_launch_shadow(const ShadowEnt* sh_dev, int nsh, int ntiles, const float* base, int target, hipStream_t st);
 int rl_launch_select_action(const SelectAct* p, hipStream_t st);
+int rl_launch_select_action_n(const SelectAct* p, int rows, hipStream_t st);      // `rows` observations (per member of an active group), one workgroup each
 int rl_launch_replay_add(float* ring, long long capacity, int row, long long ptr, const float* rows, long long nrows, int* size_dev, int new_size, hipStream_t st);
 int rl_launch_replay_add_grp(float* ring, long long ring_stride, int members, long long capacity, int row, long long ptr, const float* rows,
                              long long rows_stride, long long nrows, int* size_dev, int new_size, hipStream_t st);

@@ -42,6 +42,13 @@ diffsrsac alike; --save_model writes the environment's record with the checkpoin
 `--num-envs E` (with --device-env or --device-loop; 1..64, default 1; --start_timesteps and --eval_freq multiples of E) gives every member /
 the agent E environments stepped by the same launch: one `iterate` collects E transitions per member and trains once, so the loop counter
 advances by E and --max_timesteps stays environment steps per member.  E environments with one update per step is 1/E updates per transition.
+
+`--host-envs E` (1..256, default 1: the loops above, unchanged; --start_timesteps and --eval_freq multiples of E; not with --device-env,
+--device-loop, --pbt-interval or --halving-interval) steps E HOST environments per agent / member, seeded seed + i: an iteration is one
+`select_actions` launch for all E observations (all R x E with --seeds / --sweep), E `env.step`, one `add_batch` and ONE `train()` -- E
+transitions and one update; further updates are the caller's.  Episodes end and reset per environment, and an evaluation steps
+min(E, --eval_episodes) environments in lockstep (util.eval_policy_vec).  For environments that live on the host (gym.vector-style
+collection on the MuJoCo tasks); --num-envs is the device environments' flag and keeps its meaning.
 """
 import argparse
 import json
@@ -119,8 +126,13 @@ def run(argv=None):
                    help='environments per member / agent on the device, stepped by one launch (with --device-env or --device-loop; 1..64; '
                         '--start_timesteps and --eval_freq multiples of it).  One iterate collects E transitions and trains once: E environments '
                         'with one update per step is 1/E updates per transition')
+    p.add_argument('--host-envs', default=1, type=int,
+                   help='host environments per agent / member, seeded seed + i (1..256; --start_timesteps and --eval_freq multiples of it; not with '
+                        '--device-env, --device-loop, --pbt-interval, --halving-interval).  An iteration is E transitions -- one select_actions launch, '
+                        'E env.step, one add_batch -- and one train(); further updates are the caller\'s')
     args = p.parse_args(argv)
     _check_num_envs(args)
+    _check_host_envs(args)
     if args.device_loop:
         _check_device_loop(args)
     if args.seeds is not None or args.sweep:
@@ -152,6 +164,8 @@ def run(argv=None):
     replay = buffer.ReplayBuffer(state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)))
     if args.device_loop:
         return _single_device_loop(args, agent, replay, log_path, jsonl, tb)
+    if args.host_envs > 1:
+        return _host_envs_loop(args, agent, replay, log_path, jsonl, tb)
     evaluations = [util.eval_policy(agent, eval_env, args.eval_episodes)]
 
     state, done = env.reset(), False
@@ -206,6 +220,94 @@ def _check_num_envs(args):
     for flag, value in (('--start_timesteps', args.start_timesteps), ('--eval_freq', args.eval_freq)):
         if value != int(value) or int(value) % E:
             raise SystemExit(f'--num-envs {E}: {flag} {value:g} is not a multiple of it (a step launch takes {E} steps per member at once)')
+
+
+def _check_host_envs(args):
+    """--host-envs: SystemExit, before anything touches the GPU, on what it does not run with"""
+    E = int(args.host_envs)
+    if not 1 <= E <= 256:
+        raise SystemExit(f'--host-envs {E}: outside [1, 256]')
+    if E == 1:
+        return
+    for flag, given in (('--device-env', args.device_env), ('--device-loop', args.device_loop), ('--pbt-interval', _pbt_requested(args)),
+                        ('--halving-interval', _halving_requested(args))):
+        if given:
+            raise SystemExit(f'--host-envs {E}: several host environments per agent do not go with {flag} (device environments take --num-envs; '
+                             'ranking a population over vector environments is not built)')
+    for flag, value in (('--start_timesteps', args.start_timesteps), ('--eval_freq', args.eval_freq)):
+        if value != int(value) or int(value) % E:
+            raise SystemExit(f'--host-envs {E}: {flag} {value:g} is not a multiple of it (an iteration takes {E} environment steps at once)')
+
+
+def _host_envs(name, seed, n):
+    """n host environments `name`, environment i seeded seed + i"""
+    out = [envs.make(name) for _ in range(n)]
+    for i, e in enumerate(out):
+        e.seed(seed + i)
+    return out
+
+
+def _host_envs_loop(args, agent, replay, log_path, jsonl, tb):
+    """run()'s loop over E = --host-envs host environments (seeded seed + i): an iteration is ONE `select_actions` launch, E `env.step`, one
+    `add_batch` (done_bool per environment by run()'s rule) and one `train()`.  During warm-up, and with probability epsilon afterwards, an
+    environment's action is its action space's uniform sample, drawn in environment order as run() draws it.  Episodes end and reset per
+    environment; an evaluation is util.eval_policy_vec over min(E, --eval_episodes) environments."""
+    E = int(args.host_envs)
+    envs_ = _host_envs(args.env, args.seed, E)
+    eval_envs = _host_envs(args.env, args.seed, min(E, int(args.eval_episodes)))
+    max_length = envs_[0]._max_episode_steps
+    evaluations = [util.eval_policy_vec(agent, eval_envs, args.eval_episodes)]
+    states = np.stack([np.asarray(e.reset(), np.float32) for e in envs_])
+    action_dim = envs_[0].action_space.shape[0]
+    ep_reward, ep_steps, ep_num, info = np.zeros(E), np.zeros(E, np.int64), 0, None
+    timer = util.Timer()
+    for t0 in range(0, int(args.max_timesteps), E):             # one iteration is E environment steps
+        ep_steps += 1
+        warm = t0 < args.start_timesteps
+        greedy = None if warm else agent.select_actions(states, explore=True)
+        actions = np.zeros((E, action_dim), np.float32)
+        for i, e in enumerate(envs_):
+            actions[i] = e.action_space.sample() if warm or np.random.uniform(0, 1) < EPS_GREEDY else greedy[i]
+        nexts, rewards, dones = np.zeros_like(states), np.zeros(E, np.float32), np.zeros(E, np.float32)
+        resets = []
+        for i, e in enumerate(envs_):
+            nexts[i], reward, done, _ = e.step(actions[i])
+            rewards[i] = reward
+            dones[i] = float(done) if ep_steps[i] < max_length else 0.0
+            ep_reward[i] += reward
+            if done:
+                resets.append(i)
+        replay.add_batch(states, actions, nexts, rewards, dones)
+        states = nexts
+        for i in resets:
+            ep_num += 1
+            print(f'Total T: {t0 + E} Episode Num: {ep_num} Env: {i} Episode T: {ep_steps[i]} Reward: {ep_reward[i]:.3f}')
+            states[i] = envs_[i].reset()
+            ep_reward[i], ep_steps[i] = 0.0, 0
+        if not warm:
+            info = agent.train(replay, batch_size=args.batch_size)
+        t = t0 + E
+        if t % args.eval_freq == 0:
+            sps = timer.steps_per_sec(t)
+            evaluations.append(util.eval_policy_vec(agent, eval_envs, args.eval_episodes))
+            if info is not None:
+                row = {'step': t, 'info/evaluation': float(evaluations[-1]), 'steps_per_sec': sps}
+                row.update({f'info/{k}': float(v) for k, v in info.items()})
+                jsonl.write(json.dumps(row) + '\n')
+                jsonl.flush()
+                if tb is not None:
+                    for k, v in row.items():
+                        if k.startswith('info/'):
+                            tb.add_scalar(k, v, t)
+                    tb.flush()
+            print('Step {}. Steps per sec: {:.4g}.'.format(t, sps))
+            if args.save_model:
+                agent.save(os.path.join(log_path, 'agent.pt'))
+    jsonl.close()
+    if tb is not None:
+        tb.close()
+    print('Total time cost {:.4g}s.'.format(timer.time_cost()))
+    return agent, evaluations
 
 
 def _check_device_loop(args):
@@ -515,6 +617,8 @@ def run_seeds(args):
     ev = _GroupEvaluations(args, agent, seeds, logs, pbt_cfg, halving_cfg)
     if args.device_env:
         return _device_loop(args, agent, replay, ev)
+    if args.host_envs > 1:
+        return _host_envs_group_loop(args, agent, replay, ev, seeds)
     policies = [_MemberPolicy(agent, r) for r in range(R)]
     ev.evaluations = [[util.eval_policy(policies[r], evals_[r], args.eval_episodes)] for r in range(R)]
     states = np.stack([np.asarray(e.reset(), np.float32) for e in envs_])
@@ -559,6 +663,66 @@ def run_seeds(args):
             sps = timer.steps_per_sec(t + 1)
             scores = [util.eval_policy(policies[r], evals_[r], args.eval_episodes) if live[r] else None for r in range(R)]
             ev.step(t + 1, sps, scores, infos)
+    ev.close()
+    print('Total time cost {:.4g}s.'.format(timer.time_cost()))
+    return agent, ev.evaluations
+
+
+def _host_envs_group_loop(args, agent, replay, ev, seeds):
+    """run_seeds' loop over E = --host-envs host environments per member (member r's environment i seeded seeds[r] + i): an iteration is ONE
+    `select_actions` launch for all R x E observations, R x E `env.step`, one `add_batch` and one `train()` of every member.  Member r's
+    generator draws its environments' random and epsilon-greedy actions in environment order; an evaluation steps min(E, --eval_episodes)
+    environments per member, all members in lockstep, with one `select_actions` per step.  (No member retires here: --pbt-interval and
+    --halving-interval are refused with --host-envs.)"""
+    R, E, n_eval = agent.R, int(args.host_envs), min(int(args.host_envs), int(args.eval_episodes))
+    envs_ = [_host_envs(args.env, s, E) for s in seeds]
+    eval_envs = [e for s in seeds for e in _host_envs(args.env, s, n_eval)]
+    rngs = [np.random.RandomState(s) for s in seeds]
+    space = envs_[0][0].action_space
+    max_length = envs_[0][0]._max_episode_steps
+    lo, hi = np.asarray(space.low, np.float32), np.asarray(space.high, np.float32)
+    obs_eval = np.zeros((R, E, agent.state_dim), np.float32)
+    counts = [len(range(i, int(args.eval_episodes), n_eval)) for _ in seeds for i in range(n_eval)]
+
+    def evaluate():
+        def act(obs, active):
+            obs_eval[:, :n_eval] = obs.reshape(R, n_eval, -1)
+            return agent.select_actions(obs_eval)[:, :n_eval].reshape(R * n_eval, -1)
+        per_env = util.lockstep_rollouts(act, eval_envs, counts)
+        return [float(np.mean([x for env_returns in per_env[r * n_eval:(r + 1) * n_eval] for x in env_returns])) for r in range(R)]
+
+    ev.evaluations = [[s] for s in evaluate()]
+    states = np.stack([[np.asarray(e.reset(), np.float32) for e in member] for member in envs_])
+    ep_steps = np.zeros((R, E), np.int64)
+    infos = None
+    timer = util.Timer()
+    for t0 in range(0, int(args.max_timesteps), E):             # one iteration is E environment steps of every member
+        ep_steps += 1
+        warm = t0 < args.start_timesteps
+        greedy = None if warm else agent.select_actions(states, explore=True)
+        actions = np.zeros((R, E, agent.action_dim), np.float32)
+        for r in range(R):
+            for i in range(E):
+                actions[r, i] = rngs[r].uniform(lo, hi) if warm or rngs[r].uniform(0, 1) < EPS_GREEDY else greedy[r, i]
+        nexts, rewards, dones = np.zeros_like(states), np.zeros((R, E), np.float32), np.zeros((R, E), np.float32)
+        resets = []
+        for r in range(R):
+            for i, e in enumerate(envs_[r]):
+                nexts[r, i], rewards[r, i], done, _ = e.step(actions[r, i])
+                dones[r, i] = float(done) if ep_steps[r, i] < max_length else 0.0
+                if done:
+                    resets.append((r, i))
+        replay.add_batch(states, actions, nexts, rewards, dones)
+        states = nexts
+        for r, i in resets:
+            states[r, i] = envs_[r][i].reset()
+            ep_steps[r, i] = 0
+        if not warm:
+            infos = agent.train(replay, batch_size=args.batch_size)
+        t = t0 + E
+        if t % args.eval_freq == 0:
+            sps = timer.steps_per_sec(t)
+            ev.step(t, sps, evaluate(), infos)
     ev.close()
     print('Total time cost {:.4g}s.'.format(timer.time_cost()))
     return agent, ev.evaluations

@@ -73,6 +73,41 @@ class ReplayBuffer(object):
         self.ptr = (self.ptr + 1) % self.max_size
         self.size = min(self.size + 1, self.max_size)
 
+    def add_batch(self, states, actions, next_states, rewards, dones):
+        """E transitions in one call: states / next_states [E, S], actions [E, A], rewards / dones [E].  Equal in every observable to E add()
+        calls in row order -- the ring after flush(), ptr, size, device_epoch, the shard rule -- also where the batch wraps the ring or is
+        larger than the staging buffer (which is then flushed exactly where the E calls would flush it)."""
+        if self._device_env is not None:
+            raise RuntimeError('ReplayBuffer.add_batch: a device environment has been advancing this ring (SACAgent.iterate), so the host cursor is stale: '
+                               'call adopt_device_cursor() first')
+        S, A = self.state_dim, self.action_dim
+        E = int(np.shape(rewards)[0])
+        rows = np.empty((E, self.row), np.float32)
+        rows[:, :S] = np.asarray(states).reshape(E, S)
+        rows[:, S:S + A] = np.asarray(actions).reshape(E, A)
+        rows[:, S + A:2 * S + A] = np.asarray(next_states).reshape(E, S)
+        rows[:, 2 * S + A] = np.asarray(rewards).reshape(E)
+        rows[:, 2 * S + A + 1] = np.asarray(dones).reshape(E)
+        if self.shard is not None:
+            i = self._offered + np.arange(E)
+            self._offered += E
+            rows = rows[i % self.shard[1] == self.shard[0]]
+        cap, k = self._stage.shape[0], 0
+        while k < len(rows):
+            if self._staged == cap:
+                self.flush()
+            if self._copy_done is not None:
+                self._copy_done.synchronize()
+                self._copy_done = None
+            if self._staged == 0:
+                self._stage_start = self.ptr
+            n = min(len(rows) - k, cap - self._staged)
+            self._stage_np[self._staged:self._staged + n] = rows[k:k + n]
+            self._staged += n
+            self.ptr = (self.ptr + n) % self.max_size
+            self.size = min(self.size + n, self.max_size)
+            k += n
+
     def _before_device_write(self):
         for h in self.before_device_write_hooks:
             h()

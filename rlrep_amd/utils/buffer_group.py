@@ -81,6 +81,37 @@ class ReplayBufferGroup(object):
         self.ptr = (self.ptr + 1) % self.max_size
         self.sizes = [min(s + 1, self.max_size) for s in self.sizes]
 
+    def add_batch(self, states, actions, next_states, rewards, dones):
+        """E transitions per member in one call: states / next_states [R, E, S], actions [R, E, A], rewards / dones [R, E].  Equal in every
+        observable to E add() calls in row order (rings after flush(), ptr, sizes), also where the batch wraps the rings or is larger than the
+        staging buffer."""
+        if self._device_env is not None:
+            raise RuntimeError('ReplayBufferGroup.add_batch: a device environment has been advancing these rings (SeedBatchMixin.iterate), so the host '
+                               'cursor is stale: call adopt_device_cursor() first')
+        S, A, R = self.state_dim, self.action_dim, self.members
+        E = int(np.shape(rewards)[1])
+        rows = np.empty((R, E, self.row), np.float32)
+        rows[:, :, :S] = np.asarray(states).reshape(R, E, S)
+        rows[:, :, S:S + A] = np.asarray(actions).reshape(R, E, A)
+        rows[:, :, S + A:2 * S + A] = np.asarray(next_states).reshape(R, E, S)
+        rows[:, :, 2 * S + A] = np.asarray(rewards).reshape(R, E)
+        rows[:, :, 2 * S + A + 1] = np.asarray(dones).reshape(R, E)
+        cap, k = self._stage.shape[1], 0
+        while k < E:
+            if self._staged == cap:
+                self.flush()
+            if self._copy_done is not None:
+                self._copy_done.synchronize()
+                self._copy_done = None
+            if self._staged == 0:
+                self._stage_start = self.ptr
+            n = min(E - k, cap - self._staged)
+            self._stage_np[:, self._staged:self._staged + n] = rows[:, k:k + n]
+            self._staged += n
+            self.ptr = (self.ptr + n) % self.max_size
+            self.sizes = [min(s + n, self.max_size) for s in self.sizes]
+            k += n
+
     def flush(self):
         n = self._staged
         if n == 0:

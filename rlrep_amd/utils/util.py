@@ -1,5 +1,6 @@
 """Host-side helpers under the reference's names (utils/util.py:10-104): `unpack_batch`, `Timer`, `eval_policy`,
-`weight_init`, `MLP`, `mlp`, `to_np`.  No gym import (the reference only needed the module's name)."""
+`weight_init`, `MLP`, `mlp`, `to_np`.  No gym import (the reference only needed the module's name).  Beyond the reference:
+`eval_policy_vec` / `lockstep_rollouts` evaluate over several host environments in lockstep (one `select_actions` per step)."""
 import time
 
 import numpy as np
@@ -48,6 +49,66 @@ def eval_policy(policy, eval_env, eval_episodes=10):
     bar = '-' * 39
     print(f'{bar}\nEvaluation over {eval_episodes} episodes: {avg:.3f}\n{bar}')
     return avg
+
+
+class EvalResult(float):
+    """What eval_policy_vec returns: the mean return (a float), with the per-episode returns, in episode order, in `.returns`."""
+
+    def __new__(cls, returns):
+        self = super().__new__(cls, float(np.mean(returns)))
+        self.returns = [float(r) for r in returns]
+        return self
+
+
+def lockstep_rollouts(act, envs, counts):
+    """Environment j runs counts[j] whole episodes one after the other (reset, then steps until done), all environments in lockstep: every
+    step is ONE `act(obs [N, S], active [N] bool) -> actions [N, A]` call, of which the rows of the environments with an episode in progress
+    are used (the other rows of `obs` are stale).  Returns [N] lists of returns.  Each environment is reset and stepped exactly as a
+    sequential loop over it alone would, so its own random stream is consumed in the same order."""
+    N = len(envs)
+    left = [int(c) for c in counts]
+    out = [[] for _ in envs]
+    obs, ret, active = None, np.zeros(N), np.zeros(N, bool)
+    for j, env in enumerate(envs):
+        if left[j] > 0:
+            o = np.asarray(env.reset(), np.float32).reshape(-1)
+            if obs is None:
+                obs = np.zeros((N, o.shape[0]), np.float32)
+            obs[j], active[j] = o, True
+    while active.any():
+        actions = act(obs, active)
+        for j in np.flatnonzero(active):
+            o, reward, done, _ = envs[j].step(actions[j])
+            ret[j] += reward
+            if done:
+                out[j].append(ret[j])
+                ret[j], left[j] = 0.0, left[j] - 1
+                if left[j] > 0:
+                    o = envs[j].reset()
+                else:
+                    active[j] = False
+            obs[j] = np.asarray(o, np.float32).reshape(-1)
+    return out
+
+
+def eval_policy_vec(policy, envs, eval_episodes=10):
+    """eval_policy over E = len(envs) environments stepped in lockstep: one `policy.select_actions(obs of the running episodes [n, S])` per
+    step instead of one select_action per environment step.  Environment i runs episodes i, i + E, ... in that order, so each environment's
+    random stream is consumed as a sequential evaluation over that environment would consume it.  Returns an EvalResult: the mean return as
+    a float, the per-episode returns (episode order) in `.returns`."""
+    E = len(envs)
+    counts = [len(range(i, int(eval_episodes), E)) for i in range(E)]
+
+    def act(obs, active):
+        actions = np.zeros((E,) + np.shape(envs[0].action_space.low), np.float32)
+        actions[active] = policy.select_actions(obs[active])
+        return actions
+    per_env = lockstep_rollouts(act, envs, counts)
+    returns = [per_env[k % E][k // E] for k in range(int(eval_episodes))]
+    res = EvalResult(returns)
+    bar = '-' * 39
+    print(f'{bar}\nEvaluation over {eval_episodes} episodes: {float(res):.3f}\n{bar}')
+    return res
 
 
 def weight_init(m):
