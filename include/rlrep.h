@@ -344,6 +344,25 @@ int32_t rlrep_select_action(rlrep_agent* agent, const float* obs, int32_t obs_on
 int32_t rlrep_select_action_n(rlrep_agent* agent, const float* obs, int32_t obs_on_host, int32_t rows, int32_t explore, uint64_t seed,
                               uint64_t offset, float lo, float hi, float* action, int32_t action_on_host, void* stream);
 
+/* The actor for `rows` DEVICE-RESIDENT observations in ONE launch (additive to ABI 4; simulators that live on the GPU): a 256-thread workgroup
+ * takes 16 rows through actor.trunk.{0,2,4} with fp32 MFMAs, the activations in LDS, so every weight it fetches serves 16 rows.  Row e reads
+ * obs_dev[e * ld_obs ..], writes action_dev[e * ld_act ..] (ld_obs >= S, ld_act >= A: column views of wider tensors work) and draws at
+ * offset + (e << 20) as rlrep_select_action_n does.  A row's action depends on its observation, the weights and its draw alone -- not on rows,
+ * on its tile or on its place in it (one accumulation order for every row) -- and agrees with rlrep_select_action_n within fp32 summation order.
+ * Stream-ordered: no copy, no allocation, no synchronisation; nothing is rebuilt when `rows` changes.  Refused with RLREP_ERR_ARG before
+ * anything is launched, the message starting with "act_device:": a null argument, rows outside [1, RLREP_ACT_MAX_ROWS], a row stride below the
+ * row width, a seed group's handle, dimensions whose activation tiles exceed the LDS of one workgroup. */
+#define RLREP_ACT_MAX_ROWS 65536
+int32_t rlrep_act_device(rlrep_agent* agent, const float* obs_dev, int64_t ld_obs, int32_t rows, int32_t explore, uint64_t seed, uint64_t offset,
+                         float lo, float hi, float* action_dev, int64_t ld_act, void* stream);
+/* n DEVICE-RESIDENT transitions into the replay ring in ONE launch (additive to ABI 4): ring rows start, start + 1, ... (modulo max_size) become
+ * [s[i], a[i], s2[i], r[i], d[i]] from s [n, S] / a [n, A] / s2 [n, S] with row strides ld_s / ld_a / ld_s2 and r [n] / d [n]; size_dev (may be
+ * NULL) receives new_size as rlrep_replay_add_sized writes it.  Refused by name ("replay_add_cols:") before the launch: a null ring or array,
+ * n outside [1, max_size], row_floats != 2 S + A + 2, start outside the ring, a row stride below its width. */
+int32_t rlrep_replay_add_cols(float* ring_dev, int64_t max_size, int32_t row_floats, int64_t start, int32_t S, int32_t A, const float* s, int64_t ld_s,
+                              const float* a, int64_t ld_a, const float* s2, int64_t ld_s2, const float* r, const float* d, int64_t n, int32_t* size_dev,
+                              int32_t new_size, void* stream);
+
 /* ---- metrics ------------------------------------------------------------------------------ */
 /* device float array of n_metrics slots, valid after the stream has passed the producing step */
 const float* rlrep_metrics_dev(rlrep_agent* agent);
@@ -603,6 +622,19 @@ int32_t rlrep_group_select_action_n(rlrep_agent* agent, const float* obs_host, i
  * rows_host + r * rows_stride_floats (pinned), its fill level goes to size_dev[r]. */
 int32_t rlrep_group_replay_add_sized(float* ring_dev, int64_t ring_stride_floats, int32_t members, int64_t capacity, int32_t row_floats, int64_t ptr,
                                      const float* rows_host, int64_t rows_stride_floats, int64_t nrows, int32_t* size_dev, int32_t new_size, void* stream);
+
+/* rlrep_act_device for a seed group in ONE launch (grid (ceil(rows / 16), members); additive to ABI 4): obs_dev [members, rows, S] and
+ * action_dev [members, rows, A] are device tensors, member r acts with its own actor and draws with seeds[r] at offset + (e << 20): its plane is
+ * bit for bit what rlrep_act_device gives the standalone agent with that seed.  A retired member's planes are neither read nor written.
+ * Refused before any launch, "group_act_device:" first: a null argument, rows outside [1, RLREP_ACT_MAX_ROWS], a handle that is not a seed
+ * group, the LDS limit. */
+int32_t rlrep_group_act_device(rlrep_agent* agent, const float* obs_dev, int32_t rows, int32_t explore, uint64_t offset, float lo, float hi,
+                               float* action_dev, void* stream);
+/* rlrep_replay_add_cols for `members` rings ring_dev + r * ring_stride_floats in ONE launch: member r's n transitions are rows r * n .. of the
+ * five arrays, its fill level goes to size_dev[r].  Like rlrep_group_replay_add_sized it does not look at the live mask. */
+int32_t rlrep_group_replay_add_cols(float* ring_dev, int64_t max_size, int32_t row_floats, int64_t start, int32_t S, int32_t A, const float* s, int64_t ld_s,
+                                    const float* a, int64_t ld_a, const float* s2, int64_t ld_s2, const float* r, const float* d, int64_t n,
+                                    int32_t members, int64_t ring_stride_floats, int32_t* size_dev, int32_t new_size, void* stream);
 
 /* ---- device environments of a seed group (additive to ABI 4) ------------------------------------------------------------------------------
  * The launcher's group loop (main.py run_seeds) waits for select_action, steps R NumPy environments, draws the exploration actions and stages

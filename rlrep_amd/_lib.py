@@ -160,6 +160,10 @@ def _load():
         'rlrep_select_action': (i32, [vp, vp, i32, i32, u64, u64, f32, f32, vp, i32, vp]),
         'rlrep_select_action_n': (i32, [vp, vp, i32, i32, i32, u64, u64, f32, f32, vp, i32, vp]),
         'rlrep_group_select_action_n': (i32, [vp, vp, i32, i32, u64, f32, f32, vp, vp]),
+        'rlrep_act_device': (i32, [vp, vp, i64, i32, i32, u64, u64, f32, f32, vp, i64, vp]),
+        'rlrep_group_act_device': (i32, [vp, vp, i32, i32, u64, f32, f32, vp, vp]),
+        'rlrep_replay_add_cols': (i32, [vp, i64, i32, i64, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i32, vp]),
+        'rlrep_group_replay_add_cols': (i32, [vp, i64, i32, i64, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, i64, i32, i64, vp, i32, vp]),
         'rlrep_images_managed': (i32, [vp, i32]),
         'rlrep_refresh_images': (i32, [vp, vp]),
         'rlrep_feature_chain_next': (i32, [vp]),

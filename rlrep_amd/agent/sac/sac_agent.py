@@ -20,6 +20,7 @@ from rlrep_amd.utils.streams import raw_stream as _raw_stream, current_stream as
 
 device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
 SELECT_MAX_ROWS = 256         # include/rlrep.h RLREP_SELECT_MAX_ROWS: observations per select_actions launch
+ACT_MAX_ROWS = 65536          # include/rlrep.h RLREP_ACT_MAX_ROWS: device-resident observations per act_device launch
 
 
 @contextlib.contextmanager
@@ -383,6 +384,31 @@ class SACAgent(object):
             self._ctr += E
         _current_stream().synchronize()
         return act.numpy().copy()
+
+    def act_device(self, obs, explore=False, out=None):
+        """obs [N, S], a CUDA float32 tensor with unit inner stride (a column view of a wider tensor works) -> actions [N, A] on the device
+        (`out` if given, same rules), N up to 65 536: ONE launch on the current stream (rlrep_act_device, 16 rows per workgroup), no copy, no
+        `.cpu()`, no synchronisation.  A row's action depends on its observation, the weights and its draw alone -- not on N or on the row's
+        place -- and agrees with select_actions within fp32 summation order (1e-4), not bit for bit.  The call counter moves as in
+        select_actions: with `explore`, row e draws at call counter _ctr + 1 + e and the counter then advances by N; without it the counter
+        stands still.  Ordered behind a train() in flight as select_actions is: flush() first, which is a HOST wait for the critic / actor
+        chain of a two-chain (pipelined) train() and nothing otherwise -- with pipeline=False the call involves no host wait."""
+        self.flush()
+        S, A = self.state_dim, self.action_dim
+        if (not torch.is_tensor(obs) or not obs.is_cuda or obs.dtype != torch.float32 or obs.dim() != 2 or obs.shape[1] != S
+                or not 1 <= obs.shape[0] <= ACT_MAX_ROWS or obs.stride(1) != 1 or (obs.shape[0] > 1 and obs.stride(0) < S)):
+            raise ValueError(f'{type(self).__name__}.act_device: obs must be a CUDA float32 tensor [N, {S}] with unit inner stride and N in [1, {ACT_MAX_ROWS}]')
+        N = int(obs.shape[0])
+        if out is None:
+            out = torch.empty(N, A, dtype=torch.float32, device=obs.device)
+        elif (not torch.is_tensor(out) or out.device != obs.device or out.dtype != torch.float32 or tuple(out.shape) != (N, A) or out.stride(1) != 1
+              or (N > 1 and out.stride(0) < A)):
+            raise ValueError(f'{type(self).__name__}.act_device: out must be a float32 tensor [{N}, {A}] on {obs.device} with unit inner stride')
+        self.core.act_device(obs, obs.stride(0) if N > 1 else S, N, explore, self._seed, (self._ctr + 1) << 20 if explore else 0, *self.action_range,
+                             out, out.stride(0) if N > 1 else A)
+        if explore:
+            self._ctr += N
+        return out
 
     def update_target(self):
         self.flush()

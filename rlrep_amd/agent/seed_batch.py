@@ -36,7 +36,7 @@ import torch
 
 from rlrep_amd._lib import lib, check
 from rlrep_amd.core import HipCore, _stream
-from rlrep_amd.agent.sac.sac_agent import ArenaModule, SELECT_MAX_ROWS, _no_gc
+from rlrep_amd.agent.sac.sac_agent import ArenaModule, SELECT_MAX_ROWS, ACT_MAX_ROWS, _no_gc
 from rlrep_amd.utils import switches as _sw
 
 
@@ -535,6 +535,28 @@ class SeedBatchMixin(object):
             self._ctr += E
         torch.cuda.current_stream().synchronize()
         return act.numpy().copy()
+
+    def act_device(self, obs, explore=False, out=None):
+        """obs [R, N, S], a contiguous CUDA float32 tensor -> actions [R, N, A] on the device (`out` if given, contiguous), N up to 65 536:
+        ONE launch on the current stream (rlrep_group_act_device, grid (ceil(N / 16), R)), no copy and no synchronisation.  Plane r is bit for
+        bit what the standalone agent with seed seeds[r] gets from act_device at the same call counter: with `explore`, row e draws at
+        _ctr + 1 + e and the counter then advances by N; without it the counter stands still.  A retired member's observations are not read;
+        its rows of `out` are left as they were, and a fresh result has zeros there."""
+        R, S, A = self.R, self.state_dim, self.action_dim
+        if (not torch.is_tensor(obs) or not obs.is_cuda or obs.dtype != torch.float32 or obs.dim() != 3 or obs.shape[0] != R or obs.shape[2] != S
+                or not 1 <= obs.shape[1] <= ACT_MAX_ROWS or not obs.is_contiguous()):
+            raise ValueError(f'{type(self).__name__}.act_device: obs must be a contiguous CUDA float32 tensor [{R}, N, {S}] with N in [1, {ACT_MAX_ROWS}]')
+        N = int(obs.shape[1])
+        if out is None:
+            out = (torch.empty if all(self._live) else torch.zeros)(R, N, A, dtype=torch.float32, device=obs.device)
+        elif (not torch.is_tensor(out) or out.device != obs.device or out.dtype != torch.float32 or tuple(out.shape) != (R, N, A) or not out.is_contiguous()):
+            raise ValueError(f'{type(self).__name__}.act_device: out must be a contiguous float32 tensor [{R}, {N}, {A}] on {obs.device}')
+        lo, hi = self.action_range
+        check(lib.rlrep_group_act_device(self.core.h, C.c_void_p(obs.data_ptr()), N, 1 if explore else 0, (self._ctr + 1) << 20 if explore else 0,
+                                         lo, hi, C.c_void_p(out.data_ptr()), _stream()), 'group_act_device')
+        if explore:
+            self._ctr += N
+        return out
 
     def member_snapshot(self, r):
         """Member r as a checkpoint of the standalone agent class (its load() accepts it): continue one seed alone."""

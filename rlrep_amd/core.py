@@ -428,6 +428,11 @@ class HipCore:
         check(lib.rlrep_select_action_n(self.h, _ptr(obs_pin), 1, int(rows), 1 if explore else 0, int(seed), int(offset), float(lo), float(hi), _ptr(act_pin), 1,
                                         _stream()), 'select_action_n')
 
+    def act_device(self, obs, ld_obs, rows, explore, seed, offset, lo, hi, out, ld_act):
+        """`rows` device-resident observations -> `rows` actions in one launch, row e drawing at offset + (e << 20) (rlrep_act_device)."""
+        check(lib.rlrep_act_device(self.h, _ptr(obs), int(ld_obs), int(rows), 1 if explore else 0, int(seed), int(offset), float(lo), float(hi), _ptr(out),
+                                   int(ld_act), _stream()), 'act_device')
+
     # ---- noise --------------------------------------------------------------------------------
     def fill_normal(self, t, std, seed, offset):
         check(lib.rlrep_fill_normal(_ptr(t), t.numel(), float(std), int(seed), int(offset), _stream()), 'fill_normal')

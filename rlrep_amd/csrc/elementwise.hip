@@ -708,6 +708,44 @@ __global__ __launch_bounds__(256) void replay_add_kernel_grp(float* __restrict__
     }
     if (size_dev && blockIdx.x == 0 && threadIdx.x == 0) size_dev[m] = new_size;
 }
+// ReplayBuffer.add_device: n transitions that already live on the device as five arrays (states, actions, next states, rewards, dones; each with
+// its row stride) packed into ring rows [s, a, s', r, d] from row `start` on, wrapping at `capacity`, and the new fill level into the size word
+// as replay_add_kernel writes it: ONE launch, ordinary per-lane loads and stores.
+__device__ __forceinline__ void replay_add_cols_body(const ReplayCols& p, float* __restrict__ ring, long long plane) {
+    const long long total = p.n * p.row;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256) {
+        const long long r = e / p.row; const int c = (int)(e - r * p.row);
+        const long long src = plane + r;
+        float v;
+        if (c < p.S) v = p.s[src * p.ld_s + c];
+        else if (c < p.S + p.A) v = p.a[src * p.ld_a + (c - p.S)];
+        else if (c < 2 * p.S + p.A) v = p.s2[src * p.ld_s2 + (c - p.S - p.A)];
+        else if (c == 2 * p.S + p.A) v = p.r[src];
+        else v = p.d[src];
+        long long dst = p.start + r; if (dst >= p.capacity) dst -= p.capacity;
+        ring[dst * p.row + c] = v;
+    }
+}
+__global__ __launch_bounds__(256) void replay_add_cols_kernel(ReplayCols p) {
+    replay_add_cols_body(p, p.ring, 0);
+    if (p.size_dev && blockIdx.x == 0 && threadIdx.x == 0) *p.size_dev = p.new_size;
+}
+// group form: member m = blockIdx.y packs plane m of the five arrays (rows m * n ..) into its own ring and writes its own fill level; like
+// replay_add_kernel_grp it does not look at the live table
+__global__ __launch_bounds__(256) void replay_add_cols_kernel_grp(ReplayCols p) {
+    const int m = blockIdx.y;
+    replay_add_cols_body(p, p.ring + (long long)m * p.ring_stride, (long long)m * p.n);
+    if (p.size_dev && blockIdx.x == 0 && threadIdx.x == 0) p.size_dev[m] = p.new_size;
+}
+extern "C" int rl_launch_replay_add_cols(const ReplayCols* p, int members, hipStream_t st) {
+    const long long total = p->n * p->row;
+    const int blocks = (int)std::min<long long>(1024, std::max<long long>(1, (total + 255) / 256));
+    if (members > 0)
+        hipLaunchKernelGGL(replay_add_cols_kernel_grp, dim3(blocks, members), dim3(256), 0, st, *p);
+    else
+        hipLaunchKernelGGL(replay_add_cols_kernel, dim3(blocks), dim3(256), 0, st, *p);
+    return (int)hipGetLastError();
+}
 extern "C" int rl_launch_replay_add_grp(float* ring, long long ring_stride, int members, long long capacity, int row, long long ptr, const float* rows,
                                         long long rows_stride, long long nrows, int* size_dev, int new_size, hipStream_t st) {
     const long long n = nrows * row;

@@ -471,6 +471,24 @@ int32_t rlrep_replay_add_sized(float* ring_dev, int64_t capacity, int32_t row_fl
     return 0;
 }
 
+// n device-resident transitions (five arrays with row strides) into the ring in ONE launch, the new fill level with them (replay_add_cols_kernel)
+int32_t rlrep_replay_add_cols(float* ring_dev, int64_t max_size, int32_t row_floats, int64_t start, int32_t S, int32_t A, const float* s, int64_t ld_s,
+                              const float* a, int64_t ld_a, const float* s2, int64_t ld_s2, const float* r, const float* d, int64_t n, int32_t* size_dev,
+                              int32_t new_size, void* stream) {
+    if (!ring_dev || !s || !a || !s2 || !r || !d) { rl_set_error("replay_add_cols: bad argument (null ring or array)"); return RLREP_ERR_ARG; }
+    if (max_size <= 0 || n < 1 || n > max_size) { rl_set_error("replay_add_cols: n %lld outside [1, max_size %lld]", (long long)n, (long long)max_size); return RLREP_ERR_ARG; }
+    if (S < 1 || A < 1 || row_floats != 2 * S + A + 2) { rl_set_error("replay_add_cols: row %d is not 2 S + A + 2 (S %d, A %d)", row_floats, S, A); return RLREP_ERR_ARG; }
+    if (start < 0 || start >= max_size) { rl_set_error("replay_add_cols: start %lld outside the ring of %lld rows", (long long)start, (long long)max_size); return RLREP_ERR_ARG; }
+    if (ld_s < S || ld_a < A || ld_s2 < S || new_size < 0 || new_size > max_size) { rl_set_error("replay_add_cols: bad argument (a row stride below its width, or new_size outside the ring)"); return RLREP_ERR_ARG; }
+    ReplayCols p; memset(&p, 0, sizeof(p));
+    p.ring = ring_dev; p.capacity = max_size; p.start = start; p.row = row_floats; p.S = S; p.A = A; p.new_size = new_size;
+    p.s = s; p.a = a; p.s2 = s2; p.r = r; p.d = d; p.ld_s = ld_s; p.ld_a = ld_a; p.ld_s2 = ld_s2; p.n = n; p.size_dev = size_dev;
+    ++g_rl_launches;
+    const int rc = rl_launch_replay_add_cols(&p, 0, (hipStream_t)stream);
+    if (rc) { rl_set_error("replay_add_cols: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+
 static void slot_fill_params(rlrep_agent* ag, int slot, const float* ring_dev, const int32_t* idx_dev, SlotFill& p) {
     Slot& s = ag->slot[slot];
     memset(&p, 0, sizeof(p));
@@ -941,6 +959,33 @@ int32_t rlrep_select_action_n(rlrep_agent* ag, const float* obs, int32_t obs_on_
     ++g_rl_launches;
     const int rc = rl_launch_select_action_n(&p, rows, (hipStream_t)stream);
     if (rc) { rl_set_error("select_action_n: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    return 0;
+}
+
+// `rows` device-resident observations -> `rows` actions in ONE launch (actor_tile_kernel: 16 rows per workgroup share every weight they fetch).
+// Stream-ordered: no copy, no allocation, no synchronisation, and nothing is rebuilt when `rows` changes.  What needs no handle is checked first.
+int32_t rlrep_act_device(rlrep_agent* ag, const float* obs_dev, int64_t ld_obs, int32_t rows, int32_t explore, uint64_t seed, uint64_t offset,
+                         float lo, float hi, float* action_dev, int64_t ld_act, void* stream) {
+    if (!ag || !obs_dev || !action_dev) { rl_set_error("act_device: bad argument (null agent, observations or actions)"); return RLREP_ERR_ARG; }
+    if (rows < 1 || rows > RLREP_ACT_MAX_ROWS) { rl_set_error("act_device: rows %d outside [1, %d]", rows, RLREP_ACT_MAX_ROWS); return RLREP_ERR_ARG; }
+    GROUP_REFUSE("act_device")
+    const int S = ag->d.state_dim, Ha = ag->d.actor_hidden_dim, A = ag->d.action_dim;
+    if (ld_obs < S || ld_act < A || ld_obs > INT32_MAX || ld_act > INT32_MAX) {
+        rl_set_error("act_device: row strides (%lld, %lld) below the row widths (%d, %d)", (long long)ld_obs, (long long)ld_act, S, A); return RLREP_ERR_ARG;
+    }
+    if (rl_actor_tile_lds_bytes(S, Ha, A) > RL_ACT_TILE_LDS_MAX) {
+        rl_set_error("act_device: the activation tiles of S %d, Ha %d, A %d need %lld bytes of LDS, a workgroup has %d", S, Ha, A, rl_actor_tile_lds_bytes(S, Ha, A), RL_ACT_TILE_LDS_MAX);
+        return RLREP_ERR_ARG;
+    }
+    ActTile p; memset(&p, 0, sizeof(p));
+    p.obs = obs_dev; p.act = action_dev;
+    p.W1 = ag->P("actor.trunk.0.weight"); p.b1 = ag->P("actor.trunk.0.bias"); p.W2 = ag->P("actor.trunk.2.weight"); p.b2 = ag->P("actor.trunk.2.bias");
+    p.W3 = ag->P("actor.trunk.4.weight"); p.b3 = ag->P("actor.trunk.4.bias");
+    p.S = S; p.Ha = Ha; p.A = A; p.explore = explore ? 1 : 0; p.lo = lo; p.hi = hi; p.seed = seed; p.offset = offset;
+    p.rows = rows; p.ld_obs = (int)ld_obs; p.ld_act = (int)ld_act;
+    ++g_rl_launches;
+    const int rc = rl_launch_actor_tile(&p, (hipStream_t)stream);
+    if (rc) { rl_set_error("act_device: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
     return 0;
 }
 

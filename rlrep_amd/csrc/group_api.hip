@@ -292,6 +292,48 @@ int32_t rlrep_group_replay_add_sized(float* ring_dev, int64_t ring_stride_floats
     if (rc) { rl_set_error("group_replay_add_sized: hip error %d", rc); return RLREP_ERR_HIP; }
     return 0;
 }
+// `rows` device-resident observations per member in ONE launch (actor_tile_kernel_grp, grid (ceil(rows / 16), members)): obs_dev [members, rows, S],
+// action_dev [members, rows, A]; member r draws with seeds[r].  A retired member's planes are neither read nor written.
+int32_t rlrep_group_act_device(rlrep_agent* ag, const float* obs_dev, int32_t rows, int32_t explore, uint64_t offset, float lo, float hi, float* action_dev,
+                               void* stream) {
+    if (!ag || !obs_dev || !action_dev) { rl_set_error("group_act_device: bad argument (null agent, observations or actions)"); return RLREP_ERR_ARG; }
+    if (rows < 1 || rows > RLREP_ACT_MAX_ROWS) { rl_set_error("group_act_device: rows %d outside [1, %d]", rows, RLREP_ACT_MAX_ROWS); return RLREP_ERR_ARG; }
+    GROUP_ONLY("group_act_device")
+    SelectAct q; group_actor(ag, q, lo, hi);
+    if (rl_actor_tile_lds_bytes(q.S, q.Ha, q.A) > RL_ACT_TILE_LDS_MAX) {
+        rl_set_error("group_act_device: the activation tiles of S %d, Ha %d, A %d need %lld bytes of LDS, a workgroup has %d", q.S, q.Ha, q.A,
+                     rl_actor_tile_lds_bytes(q.S, q.Ha, q.A), RL_ACT_TILE_LDS_MAX);
+        return RLREP_ERR_ARG;
+    }
+    ActTile p; memset(&p, 0, sizeof(p));
+    p.obs = obs_dev; p.act = action_dev; p.W1 = q.W1; p.b1 = q.b1; p.W2 = q.W2; p.b2 = q.b2; p.W3 = q.W3; p.b3 = q.b3;
+    p.S = q.S; p.Ha = q.Ha; p.A = q.A; p.explore = explore ? 1 : 0; p.lo = lo; p.hi = hi; p.seed = 0; p.offset = offset;
+    p.rows = rows; p.ld_obs = q.S; p.ld_act = q.A;
+    GrpScope grp_scope_(ag);
+    ++g_rl_launches;
+    const int rc = rl_launch_actor_tile(&p, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_act_device: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    return 0;
+}
+// rlrep_replay_add_cols for `members` rings in ONE launch: member r's plane of the five arrays lies n rows behind member r - 1's
+int32_t rlrep_group_replay_add_cols(float* ring_dev, int64_t max_size, int32_t row_floats, int64_t start, int32_t S, int32_t A, const float* s, int64_t ld_s,
+                                    const float* a, int64_t ld_a, const float* s2, int64_t ld_s2, const float* r, const float* d, int64_t n,
+                                    int32_t members, int64_t ring_stride_floats, int32_t* size_dev, int32_t new_size, void* stream) {
+    if (!ring_dev || !s || !a || !s2 || !r || !d) { rl_set_error("group_replay_add_cols: bad argument (null ring or array)"); return RLREP_ERR_ARG; }
+    if (max_size <= 0 || n < 1 || n > max_size) { rl_set_error("group_replay_add_cols: n %lld outside [1, max_size %lld]", (long long)n, (long long)max_size); return RLREP_ERR_ARG; }
+    if (S < 1 || A < 1 || row_floats != 2 * S + A + 2) { rl_set_error("group_replay_add_cols: row %d is not 2 S + A + 2 (S %d, A %d)", row_floats, S, A); return RLREP_ERR_ARG; }
+    if (start < 0 || start >= max_size) { rl_set_error("group_replay_add_cols: start %lld outside the ring of %lld rows", (long long)start, (long long)max_size); return RLREP_ERR_ARG; }
+    if (members < 1 || members > RLREP_GROUP_MAX_MEMBERS || ring_stride_floats < max_size * row_floats || ld_s < S || ld_a < A || ld_s2 < S || new_size < 0 || new_size > max_size) {
+        rl_set_error("group_replay_add_cols: bad argument (members, the ring stride, a row stride below its width, or new_size outside the ring)"); return RLREP_ERR_ARG;
+    }
+    ReplayCols p; memset(&p, 0, sizeof(p));
+    p.ring = ring_dev; p.capacity = max_size; p.start = start; p.ring_stride = ring_stride_floats; p.row = row_floats; p.S = S; p.A = A; p.new_size = new_size;
+    p.s = s; p.a = a; p.s2 = s2; p.r = r; p.d = d; p.ld_s = ld_s; p.ld_a = ld_a; p.ld_s2 = ld_s2; p.n = n; p.size_dev = size_dev;
+    ++g_rl_launches;
+    const int rc = rl_launch_replay_add_cols(&p, members, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_replay_add_cols: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
 // ---- device environments of a seed group (group_env.hip) --------------------------------------------------------------------------------------
 static_assert(EnvPendulum::KIND == RLREP_ENV_PENDULUM && EnvMountainCar::KIND == RLREP_ENV_MOUNTAIN_CAR_CONTINUOUS, "group_env.h kinds are include/rlrep.h RLREP_ENV_*");
 struct rlrep_group_env {

@@ -19,6 +19,24 @@ struct SelectAct {
     float lo, hi;
     unsigned long long seed, offset;                    // the draw = rlrep_fill_normal(eps[A], 1, seed, offset)
 };
+// rlrep_act_device: `rows` device-resident observations through the actor in one launch, 16 rows per workgroup (actor_tile.hip)
+#define RL_ACT_TILE_LDS_MAX (160 * 1024)                // bytes of LDS one workgroup may have on gfx950
+struct ActTile {
+    const float* obs; float* act;                       // [rows, S] at row stride ld_obs, [rows, A] at row stride ld_act (a group: one such plane per member)
+    const float *W1, *b1, *W2, *b2, *W3, *b3;           // actor.trunk.{0,2,4}: [Ha,S], [Ha,Ha], [2A,Ha]
+    int S, Ha, A, explore;
+    float lo, hi;
+    unsigned long long seed, offset;                    // row e draws rlrep_fill_normal(eps[A], 1, seed, offset + (e << 20))
+    int rows, ld_obs, ld_act, LD;                       // LD: LDS row pitch of the activation tiles (set by the launcher)
+};
+// rlrep_replay_add_cols: n device-resident transitions, given as five arrays with row strides, packed into ring rows [s, a, s', r, d]
+struct ReplayCols {
+    float* ring; long long capacity, start, ring_stride;   // ring_stride (floats): the group form's distance between two members' rings
+    int row, S, A, new_size;
+    const float *s, *a, *s2, *r, *d;                       // [n, S], [n, A], [n, S], [n], [n] (a group: one such plane per member, n rows apart)
+    long long ld_s, ld_a, ld_s2, n;
+    int* size_dev;                                         // the fill level word (the group form's: one per member)
+};
 struct PhiloxFill {
     float* dst_f; int* dst_i; long long n;
     int kind;                  // 0: normal*std -> dst_f ; 1: uniform int in [0,hi) -> dst_i

@@ -70,6 +70,10 @@ int rl_launch_select_action_n(const SelectAct* p, int rows, hipStream_t st);    
 int rl_launch_replay_add(float* ring, long long capacity, int row, long long ptr, const float* rows, long long nrows, int* size_dev, int new_size, hipStream_t st);
 int rl_launch_replay_add_grp(float* ring, long long ring_stride, int members, long long capacity, int row, long long ptr, const float* rows,
                              long long rows_stride, long long nrows, int* size_dev, int new_size, hipStream_t st);
+int rl_launch_replay_add_cols(const ReplayCols* p, int members, hipStream_t st);  // members == 0: one ring; otherwise grid y = member
+// ---- actor_tile.hip ----
+long long rl_actor_tile_lds_bytes(int S, int Ha, int A);
+int rl_launch_actor_tile(const ActTile* p, hipStream_t st);                        // p->rows observations (per member of an active group), 16 per workgroup
 // ---- replearn.hip ----
 int rl_replearn_init();
 int rl_launch_infonce(const InfoNce* p, hipStream_t st);

@@ -49,6 +49,12 @@ advances by E and --max_timesteps stays environment steps per member.  E environ
 transitions and one update; further updates are the caller's.  Episodes end and reset per environment, and an evaluation steps
 min(E, --eval_episodes) environments in lockstep (util.eval_policy_vec).  For environments that live on the host (gym.vector-style
 collection on the MuJoCo tasks); --num-envs is the device environments' flag and keeps its meaning.
+
+`--torch-envs N` (1..65536, default 0: the loops above, unchanged; one agent, --env Pendulum-v1; --start_timesteps and --eval_freq multiples
+of N) is the loop of a simulator that already lives on the GPU as torch tensors (envs/torch_pendulum.py is the example): an iteration is ONE
+`act_device` launch on the device observations, `TorchPendulum.step`, ONE `add_device` launch and ONE `train()` -- no transition crosses the
+host.  Warm-up and epsilon-greedy actions are drawn on the device; an evaluation steps min(N, --eval_episodes) environments in lockstep with
+`act_device(explore=False)`.
 """
 import argparse
 import json
@@ -130,9 +136,14 @@ def run(argv=None):
                    help='host environments per agent / member, seeded seed + i (1..256; --start_timesteps and --eval_freq multiples of it; not with '
                         '--device-env, --device-loop, --pbt-interval, --halving-interval).  An iteration is E transitions -- one select_actions launch, '
                         'E env.step, one add_batch -- and one train(); further updates are the caller\'s')
+    p.add_argument('--torch-envs', default=0, type=int,
+                   help='environments of a torch simulator on the device (one agent, --env Pendulum-v1; 1..65536, 0 = off; --start_timesteps and '
+                        '--eval_freq multiples of it; not with --seeds, --sweep, --device-env, --device-loop, --host-envs, --num-envs).  An iteration '
+                        'is N transitions -- one act_device launch, one batched step, one add_device launch -- and one train()')
     args = p.parse_args(argv)
     _check_num_envs(args)
     _check_host_envs(args)
+    _check_torch_envs(args)
     if args.device_loop:
         _check_device_loop(args)
     if args.seeds is not None or args.sweep:
@@ -166,6 +177,8 @@ def run(argv=None):
         return _single_device_loop(args, agent, replay, log_path, jsonl, tb)
     if args.host_envs > 1:
         return _host_envs_loop(args, agent, replay, log_path, jsonl, tb)
+    if args.torch_envs:
+        return _torch_envs_loop(args, agent, replay, log_path, jsonl, tb)
     evaluations = [util.eval_policy(agent, eval_env, args.eval_episodes)]
 
     state, done = env.reset(), False
@@ -290,6 +303,94 @@ def _host_envs_loop(args, agent, replay, log_path, jsonl, tb):
         if t % args.eval_freq == 0:
             sps = timer.steps_per_sec(t)
             evaluations.append(util.eval_policy_vec(agent, eval_envs, args.eval_episodes))
+            if info is not None:
+                row = {'step': t, 'info/evaluation': float(evaluations[-1]), 'steps_per_sec': sps}
+                row.update({f'info/{k}': float(v) for k, v in info.items()})
+                jsonl.write(json.dumps(row) + '\n')
+                jsonl.flush()
+                if tb is not None:
+                    for k, v in row.items():
+                        if k.startswith('info/'):
+                            tb.add_scalar(k, v, t)
+                    tb.flush()
+            print('Step {}. Steps per sec: {:.4g}.'.format(t, sps))
+            if args.save_model:
+                agent.save(os.path.join(log_path, 'agent.pt'))
+    jsonl.close()
+    if tb is not None:
+        tb.close()
+    print('Total time cost {:.4g}s.'.format(timer.time_cost()))
+    return agent, evaluations
+
+
+def _check_torch_envs(args):
+    """--torch-envs: SystemExit, before anything touches the GPU, on what it does not run with"""
+    N = int(args.torch_envs)
+    if N == 0:
+        return
+    if not 1 <= N <= 65536:
+        raise SystemExit(f'--torch-envs {N}: outside [1, 65536]')
+    for flag, given in (('--seeds', args.seeds is not None), ('--sweep', bool(args.sweep)), ('--device-env', args.device_env),
+                        ('--device-loop', args.device_loop), ('--host-envs', args.host_envs > 1), ('--num-envs', args.num_envs > 1)):
+        if given:
+            raise SystemExit(f'--torch-envs {N}: the torch simulator loop runs ONE agent and does not go with {flag} (seed groups have '
+                             'act_device / add_device as an API only)')
+    if not args.env.startswith('Pendulum'):
+        raise SystemExit(f'--torch-envs {N}: the example simulator is Pendulum-v1 (got --env {args.env})')
+    for flag, value in (('--start_timesteps', args.start_timesteps), ('--eval_freq', args.eval_freq)):
+        if value != int(value) or int(value) % N:
+            raise SystemExit(f'--torch-envs {N}: {flag} {value:g} is not a multiple of it (an iteration takes {N} environment steps at once)')
+    if N > min(args.max_timesteps, 1e6):
+        raise SystemExit(f'--torch-envs {N}: more environments than the replay ring has rows (min(--max_timesteps, 1e6))')
+
+
+def _torch_eval(agent, env, episodes):
+    """mean return of `episodes` mean-action episodes, env.num_envs at a time in lockstep: one act_device launch per step, one copy at the end"""
+    returns = []
+    while len(returns) < episodes:
+        obs = env.reset()
+        for _ in range(env._max_episode_steps):
+            env.step(agent.act_device(obs, explore=False))
+            obs = env.obs
+        returns.extend(env.last_return.cpu().tolist())
+    return float(np.mean(returns[:episodes]))
+
+
+def _torch_envs_loop(args, agent, replay, log_path, jsonl, tb):
+    """run()'s loop over N = --torch-envs environments of a simulator on the device (envs/torch_pendulum.py): an iteration is ONE `act_device`
+    launch, one batched `step`, ONE `add_device` launch and one `train()`; nothing of a transition crosses the host.  During warm-up, and
+    with probability epsilon afterwards, an environment's action is uniform in the action range, drawn on the device.  Evaluations follow
+    every --eval_freq steps (none before the first step)."""
+    from rlrep_amd.envs.torch_pendulum import TorchPendulum
+    N, dev = int(args.torch_envs), replay.device
+    env = TorchPendulum(N, dev, seed=args.seed)
+    eval_env = TorchPendulum(min(N, int(args.eval_episodes)), dev, seed=args.seed + 100)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(args.seed))
+    lo, hi = agent.action_range
+    A = env.action_dim
+    evaluations, info, episodes = [], None, 0
+    obs = env.reset()
+    timer = util.Timer()
+    for t0 in range(0, int(args.max_timesteps), N):             # one iteration is N environment steps
+        uniform = lo + (hi - lo) * torch.rand(N, A, dtype=torch.float32, device=dev, generator=gen)
+        if t0 < args.start_timesteps:
+            actions = uniform
+        else:
+            pick = torch.rand(N, 1, dtype=torch.float32, device=dev, generator=gen) < EPS_GREEDY
+            actions = torch.where(pick, uniform, agent.act_device(obs, explore=True))
+        nexts, rewards, dones = env.step(actions)
+        replay.add_device(obs, actions, nexts, rewards, dones)
+        obs = env.obs
+        if env.episodes != episodes:
+            episodes = env.episodes
+            print(f'Total T: {t0 + N} Episode Num: {episodes * N} Mean reward: {float(env.last_return.mean()):.3f}')
+        if t0 >= args.start_timesteps:
+            info = agent.train(replay, batch_size=args.batch_size)
+        t = t0 + N
+        if t % args.eval_freq == 0:
+            sps = timer.steps_per_sec(t)
+            evaluations.append(_torch_eval(agent, eval_env, int(args.eval_episodes)))
             if info is not None:
                 row = {'step': t, 'info/evaluation': float(evaluations[-1]), 'steps_per_sec': sps}
                 row.update({f'info/{k}': float(v) for k, v in info.items()})

@@ -108,6 +108,66 @@ class ReplayBuffer(object):
             self.size = min(self.size + n, self.max_size)
             k += n
 
+    def add_device(self, states, actions, next_states, rewards, dones):
+        """N transitions that live on the device: states / next_states [N, S], actions [N, A], rewards / dones [N] (or [N, 1]), float32
+        tensors on the ring's device (dones may be bool).  ONE launch on the current stream (rlrep_replay_add_cols) packs them into ring rows
+        ptr, ptr + 1, ... (wrapping) and writes the new fill level into size_dev(): nothing goes through the host.  Host rows staged by add()
+        are flushed first, so the order of transitions is the call order.  ptr, size, device_epoch and the ring end up as add_batch() +
+        flush() on the same rows leave them.  N is known on the host: ptr and size advance here."""
+        if self._device_env is not None:
+            raise RuntimeError('ReplayBuffer.add_device: a device environment has been advancing this ring (SACAgent.iterate), so the host cursor is stale: '
+                               'call adopt_device_cursor() first')
+        if self.shard is not None:
+            raise ValueError('ReplayBuffer.add_device: a sharded ring (shard=) keeps one transition in `world`; add_device writes every row it is given')
+        S, A = self.state_dim, self.action_dim
+        N = int(rewards.shape[0])
+        if not 1 <= N <= self.max_size:
+            raise ValueError(f'ReplayBuffer.add_device: {N} transitions for a ring of {self.max_size} rows (N must lie in [1, max_size])')
+
+        def prep(t, w, name):
+            if not torch.is_tensor(t) or t.device != self.ring.device:
+                raise ValueError(f'ReplayBuffer.add_device: {name} must be a tensor on {self.ring.device}')
+            if t.dtype != torch.float32:
+                t = t.to(torch.float32)
+            if w is None:
+                t = t.reshape(N)
+                return t if t.stride(0) == 1 or N == 1 else t.contiguous()
+            if tuple(t.shape) != (N, w):
+                raise ValueError(f'ReplayBuffer.add_device: {name} {tuple(t.shape)} is not [{N}, {w}]')
+            return t if t.stride(1) == 1 and (N == 1 or t.stride(0) >= w) else t.contiguous()
+        s, a, s2 = prep(states, S, 'states'), prep(actions, A, 'actions'), prep(next_states, S, 'next_states')
+        r, d = prep(rewards, None, 'rewards'), prep(dones, None, 'dones')
+        epoch = self.device_epoch
+        self.flush()
+        start = self.ptr
+        self.ptr = (self.ptr + N) % self.max_size
+        self.size = min(self.size + N, self.max_size)
+        self._before_device_write()
+        if self.device.type == 'cuda':
+            import ctypes as C
+            from rlrep_amd._lib import lib, check
+
+            def issue():
+                ld = lambda t, w: t.stride(0) if N > 1 else w
+                check(lib.rlrep_replay_add_cols(C.c_void_p(self.ring.data_ptr()), self.max_size, self.row, start, S, A, C.c_void_p(s.data_ptr()), ld(s, S),
+                                                C.c_void_p(a.data_ptr()), ld(a, A), C.c_void_p(s2.data_ptr()), ld(s2, S), C.c_void_p(r.data_ptr()),
+                                                C.c_void_p(d.data_ptr()), N, C.c_void_p(self._size_dev.data_ptr()), self.size, C.c_void_p(_raw_stream())),
+                      'replay_add_cols')
+                self._size_pushed = self.size
+                if self._copy_event is None:
+                    self._copy_event = torch.cuda.Event()
+                self._copy_done = self._copy_event
+                self._copy_done.record(_current_stream())
+            if self.device.index is None or self.device.index == _current_device_index():
+                issue()
+            else:
+                with torch.cuda.device(self.device):
+                    issue()
+        else:
+            idx = (start + torch.arange(N)) % self.max_size
+            self.ring[idx] = torch.cat([s, a, s2, r.reshape(N, 1), d.reshape(N, 1)], dim=1)
+        self.device_epoch = epoch + 1           # (one step for the call, staged host rows included: what add_batch() + flush() on the same rows count)
+
     def _before_device_write(self):
         for h in self.before_device_write_hooks:
             h()

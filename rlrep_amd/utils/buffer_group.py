@@ -112,6 +112,47 @@ class ReplayBufferGroup(object):
             self.sizes = [min(s + n, self.max_size) for s in self.sizes]
             k += n
 
+    def add_device(self, states, actions, next_states, rewards, dones):
+        """N device-resident transitions per member: states / next_states [R, N, S], actions [R, N, A], rewards / dones [R, N], tensors on the
+        rings' device.  ONE launch (rlrep_group_replay_add_cols) packs member r's plane into its ring from row ptr on (wrapping) and writes
+        every member's fill level; staged host rows are flushed first.  Like flush(), it does not look at retired members."""
+        if self._device_env is not None:
+            raise RuntimeError('ReplayBufferGroup.add_device: a device environment has been advancing these rings (SeedBatchMixin.iterate), so the host '
+                               'cursor is stale: call adopt_device_cursor() first')
+        S, A, R = self.state_dim, self.action_dim, self.members
+        if rewards.dim() < 2 or rewards.shape[0] != R:
+            raise ValueError(f'ReplayBufferGroup.add_device: rewards {tuple(rewards.shape)} is not [{R}, N]')
+        N = int(rewards.shape[1])
+        if not 1 <= N <= self.max_size:
+            raise ValueError(f'ReplayBufferGroup.add_device: {N} transitions for rings of {self.max_size} rows (N must lie in [1, max_size])')
+
+        def prep(t, shape, name):
+            if not torch.is_tensor(t) or t.device != self.rings.device:
+                raise ValueError(f'ReplayBufferGroup.add_device: {name} must be a tensor on {self.rings.device}')
+            return t.to(torch.float32).reshape(shape).contiguous()
+        s, a, s2 = prep(states, (R, N, S), 'states'), prep(actions, (R, N, A), 'actions'), prep(next_states, (R, N, S), 'next_states')
+        r, d = prep(rewards, (R, N), 'rewards'), prep(dones, (R, N), 'dones')
+        self.flush()
+        if len(set(self.sizes)) != 1:
+            raise RuntimeError('ReplayBufferGroup.add_device after load() gave the members different fill levels: the lockstep ring takes N rows per member')
+        start = self.ptr
+        self.ptr = (self.ptr + N) % self.max_size
+        self.sizes = [min(v + N, self.max_size) for v in self.sizes]
+        self._before_device_write()
+        if self.device.type == 'cuda':
+            import ctypes as C
+            from rlrep_amd._lib import lib, check
+            check(lib.rlrep_group_replay_add_cols(C.c_void_p(self.rings.data_ptr()), self.max_size, self.row, start, S, A, C.c_void_p(s.data_ptr()), S,
+                                                  C.c_void_p(a.data_ptr()), A, C.c_void_p(s2.data_ptr()), S, C.c_void_p(r.data_ptr()), C.c_void_p(d.data_ptr()), N,
+                                                  R, self.ring_stride, C.c_void_p(self._size_dev.data_ptr()), self.sizes[0], C.c_void_p(_raw_stream())),
+                  'group_replay_add_cols')
+            self._size_pushed = list(self.sizes)
+            self._copy_done = torch.cuda.Event()
+            self._copy_done.record()
+        else:
+            idx = (start + torch.arange(N)) % self.max_size
+            self.rings[:, idx] = torch.cat([s, a, s2, r.reshape(R, N, 1), d.reshape(R, N, 1)], dim=2)
+
     def flush(self):
         n = self._staged
         if n == 0:
