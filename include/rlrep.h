@@ -363,6 +363,29 @@ int32_t rlrep_replay_add_cols(float* ring_dev, int64_t max_size, int32_t row_flo
                               const float* a, int64_t ld_a, const float* s2, int64_t ld_s2, const float* r, const float* d, int64_t n, int32_t* size_dev,
                               int32_t new_size, void* stream);
 
+/* ---- prioritized replay for sac (additive to ABI 4; DESIGN.md 6f, csrc/per.hip) ------------------------------------------------------
+ * The priorities live beside the ring in a caller-owned sum tree: tree_dev float32[2 P], P = the smallest power of two >= the ring's rows,
+ * node n = tree[2n] + tree[2n + 1] (one fp32 add), row i's leaf = tree[P + i], leaves of unwritten rows 0 (the caller zeroes the tree once).
+ * scal_dev float32[4] = {max_p (starts at 1), alpha, beta, eps}.  One launch each, one workgroup each, stream-ordered, no host round trip.
+ *   rlrep_per_add      leaves of rows [start, start + n) mod capacity <- max_p as this launch reads it; their ancestors are recomputed.
+ *   rlrep_per_rebuild  every internal node from the leaves (after the caller restored them).
+ *   rlrep_per_sample   batch stratified draws: total = tree[1], seg = total / batch, draw j descends with m = (j + u_j) seg, u_j from Philox
+ *                      stream element j (seed, offset + *counter_dev if given) as ((word >> 8) + 0.5) 2^-24; left while r == 0 or m < l, else
+ *                      m -= l and right.  given != 0: idx_dev[batch] is an INPUT.  w_dev[j] = (pmin / p_j)^beta with pmin the smallest sampled
+ *                      priority, exactly 1 where p_j == pmin or beta == 0.  The buffer must hold a row (tree[1] > 0): the caller's to check.
+ *   rlrep_critic_step_weighted   rlrep_critic_step with the critic loss mean_b w[b] ((q1 - y)^2 + (q2 - y)^2); leaves
+ *                      td[b] = 0.5 (|q1 - y| + |q2 - y|) in the agent's workspace (rlrep_per_td_dev).  Same launch count as rlrep_critic_step.
+ *   rlrep_per_update   leaf idx[j] <- (td[j] + eps)^alpha (1 when alpha == 0; the MAXIMUM where an index repeats), max_p = max(max_p, those),
+ *                      ancestors recomputed; a new priority that is not positive or not a number becomes FLT_MIN.  td_dev NULL: the last weighted critic step's (batch must be its batch).
+ * The entry points that take an agent refuse, by name: a seed group's handle, an agent that is not sac, world_size > 1. */
+int32_t rlrep_per_add(float* tree_dev, int64_t P, const float* scal_dev, int64_t capacity, int64_t start, int64_t n, void* stream);
+int32_t rlrep_per_rebuild(float* tree_dev, int64_t P, void* stream);
+int32_t rlrep_per_sample(rlrep_agent* agent, const float* tree_dev, int64_t P, const float* scal_dev, int32_t* idx_dev, float* w_dev, int32_t batch, int32_t given,
+                         uint64_t seed, uint64_t offset, const int32_t* counter_dev, void* stream);
+int32_t rlrep_per_update(rlrep_agent* agent, float* tree_dev, int64_t P, float* scal_dev, const int32_t* idx_dev, const float* td_dev, int32_t batch, void* stream);
+int32_t rlrep_critic_step_weighted(rlrep_agent* agent, const float* eps_dev, const float* w_dev, void* stream);
+const float* rlrep_per_td_dev(rlrep_agent* agent);
+
 /* ---- metrics ------------------------------------------------------------------------------ */
 /* device float array of n_metrics slots, valid after the stream has passed the producing step */
 const float* rlrep_metrics_dev(rlrep_agent* agent);

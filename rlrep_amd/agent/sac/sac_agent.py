@@ -432,6 +432,7 @@ class SACAgent(object):
         """One train step (sac_agent.py:169-188).  In pipelined graph mode (vlsac / ctrlsac / spedersac on one GPU) the critic and
         actor steps of this call may still be in flight when it returns; everything that looks at them waits (`flush()`), including
         reading the returned info dict -- which therefore has to be read before the NEXT train() call to describe THIS one."""
+        self._check_per(buffer, 'train')
         self.steps += 1
         if (self.steps & 31) == 0:
             self.core.exchange_check()           # (a word in mapped host memory: no synchronisation; a launch that saw a timeout applied nothing)
@@ -454,6 +455,42 @@ class SACAgent(object):
 
     update = train      # BASELINE.json's north_star calls it agent.update()
 
+    # ---- prioritized replay (utils/buffer.py PrioritizedReplayBuffer) -------------------------------------------------------
+    PER_STREAM = 3 << 40      # Philox offset of the sampler's draws (1 << 40: the index pool, 2 << 40: the noise pool)
+
+    @staticmethod
+    def _per(buffer):
+        return bool(getattr(buffer, 'prioritized', False))
+
+    def _check_per(self, buffer, what):
+        """A prioritized buffer trains ONE sac agent on ONE GPU; everything else refuses it by its class name, before anything is launched."""
+        if not self._per(buffer):
+            return
+        name, cls = type(self).__name__, type(buffer).__name__
+        if self.ALG != 'sac':
+            raise RuntimeError(f'{name}.{what}: {cls} is built for SACAgent only ({self.ALG} reuses its last feature minibatch for the critic step; '
+                               'what prioritisation means there is open): use a plain ReplayBuffer')
+        if self.world_size > 1 or self._dp:
+            raise RuntimeError(f'{name}.{what}: {cls} does not train a data-parallel agent (one agent, one GPU)')
+        if what == 'iterate':
+            raise RuntimeError(f'{name}.iterate: {cls} cannot be written by a device environment (its step launch knows nothing of the priority '
+                               'tree): use a plain ReplayBuffer')
+
+    def _sample_into_per(self, buffer, B, key, g):
+        """The minibatch of a prioritized buffer: the sample launch (indices + importance weights into the buffer's draw buffers), then the
+        gather.  Injected indices take the sampler's given-indices mode: only the weights are computed."""
+        c = self.core
+        if self._inject is not None:
+            idx, _ = buffer.draw(B, 0, 0, core=c, given=np.asarray(self._inject['idx'].pop(0)))
+        elif g:
+            idx, _ = buffer.draw(B, self._seed, self.PER_STREAM, core=c, counter_dev=c.steps_dev())
+        else:
+            if key == 'warm':
+                self._ctr += 1
+            idx, _ = buffer.draw(B, self._seed, self.PER_STREAM + self._ctr, core=c)
+        self._bufs['idx_' + key] = idx
+        c.sample(0, buffer.ring, idx, B)
+
     def _form(self):
         """The form the next train() takes: 'graph' (one hipGraph), 'two_chains' (the feature chain and the deferred critic / actor chain on
         two streams; train() may still pick 'graph' per call), 'dp_segments' (data parallel: graph segments around the all-reduces, or one
@@ -473,6 +510,7 @@ class SACAgent(object):
         one process (the loopback form: rlrep_amd/comm.py LoopbackGroup) must build their graphs one after the other -- a capture synchronises
         the device, which would wait for a peer's optimizer launch that in turn waits for this replica's -- and replay them side by side
         afterwards.  No-op for the forms that are not whole graphs."""
+        self._check_per(buffer, 'prepare')
         form = self._form()
         if form not in ('graph', 'two_chains'):
             return
@@ -550,6 +588,7 @@ class SACAgent(object):
         first.  The step programs are sized for the batch by rlrep_prepare, not by the eager gather a train() capture uses: while the
         device owns the cursor the host's `buffer.size` is stale (and 0 for a ring only the device has written)."""
         name = type(self).__name__
+        self._check_per(buffer, 'iterate')
         if self.world_size > 1 or self._dp:
             raise RuntimeError(f'{name}.iterate: a data-parallel agent has no device environment')
         if not self.use_graph:
@@ -813,6 +852,8 @@ class SACAgent(object):
         return dict(zip(idx_keys, idx_keys[1:])) if self.PREFETCH_CHAIN else {}
 
     def _sample_into(self, buffer, B, key, slot=0, g=False):
+        if self._per(buffer):
+            return self._sample_into_per(buffer, B, key, g)
         if self._inject is None and self._pool is not None and ('idx_' + key) in self._pool:
             self.core.sample(slot, buffer.ring, self._pool['idx_' + key], B)
             nxt = self._next_key.get(key)
@@ -882,7 +923,10 @@ class SACAgent(object):
         e1 = self._eps('crit', (B, self.action_dim), g)
         e2 = self._eps('act', (B, self.action_dim), g)
         c.prefetch_policy(e2)      # the actor step's forward half rides in the critic step's launches (same batch)
-        if W > 1:
+        if self._per(buffer):      # (one sac agent, one GPU: _check_per) the weighted critic step, then the |TD| errors it left become priorities
+            c.critic_step_weighted(e1, buffer.draw_buffers(B)[1])
+            buffer.update(B, core=c)
+        elif W > 1:
             if self._critic_trains():
                 c.critic_backward(e1); self._allreduce(1); c.critic_apply()
             else:
@@ -969,6 +1013,7 @@ class SACAgent(object):
         """train() with caller-supplied sample indices and noise tensors, consumed in the reference's draw
         order.  Used by the parity tests and smoke(): 'fixed seeds' parity is
         injected-noise parity, the torch/NumPy generators cannot be reproduced on the device."""
+        self._check_per(buffer, 'train_injected')
         self.steps += 1
         self.flush()
         buffer.flush()
@@ -1284,7 +1329,9 @@ class SACAgent(object):
     def _graph_cache_key(buffer, B):
         """What a captured train() bakes in: the ring and size-scalar device addresses and the batch size (id(buffer) can be reused by
         a new ReplayBuffer after the old one is collected)."""
-        return (buffer.ring.data_ptr(), buffer.size_dev().data_ptr(), int(buffer.ring.shape[0]), B)
+        key = (buffer.ring.data_ptr(), buffer.size_dev().data_ptr(), int(buffer.ring.shape[0]), B)
+        per = getattr(buffer, 'per_key', None)               # (a prioritized buffer: its tree and scalar block are baked in as well)
+        return key if per is None else key + per()
 
     def _hook_buffer(self, buffer):
         hooks = getattr(buffer, 'before_device_write_hooks', None)
@@ -1344,6 +1391,8 @@ class SACAgent(object):
                 with self._history_capture(), self._managed_images(), torch.cuda.graph(g, stream=s):
                     self._body(buffer, B, True)
                 self._graph, self._graph_key = g, key
+                if self._per(buffer):
+                    self._held_buffer = buffer          # the cached graph reads its tree and draw buffers: keep it alive as long as the graph
                 self._graph_launches = _l.rlrep_launch_counter() - n0
                 f1 = _fe()
                 self._graph_front_ends = {k: f1[k] - f0[k] for k in f1}

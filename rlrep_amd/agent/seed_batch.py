@@ -392,9 +392,15 @@ class SeedBatchMixin(object):
         # members file their records in rings of their own, and a retired member's ring stands still: one record count per member
         self._mhist_n = [m.history_seq() for m in self._members] if self._hist else [0] * self.R
 
+    def _refuse_per(self, buffers, what):
+        if getattr(buffers, 'prioritized', False):
+            raise RuntimeError(f'{type(self).__name__}.{what}: {type(buffers).__name__} is built for one SACAgent on one GPU; a seed group samples '
+                               'its members\' rings uniformly (ReplayBufferGroup)')
+
     def train(self, buffers, batch_size):
         """One train() of every live member: ONE graph replay.  Returns R entries (member order): an info dict, fetched when read, or None for
         a retired member."""
+        self._refuse_per(buffers, 'train')
         if getattr(buffers, 'members', None) != self.R:
             raise ValueError(f'{type(self).__name__}.train: needs a ReplayBufferGroup of {self.R} members')
         self.steps += 1
@@ -409,6 +415,7 @@ class SeedBatchMixin(object):
         round trip.  `env` is a DeviceEnvGroup (envs/device.py) of this group, `buffers` a ReplayBufferGroup whose cursor the device owns from here on
         (ReplayBufferGroup.adopt_device_cursor gives it back).  Returns what train() returns, or None without `train`.  The step's exploring
         draw is the one `select_action(states, explore=True)` would make now: both count calls in the same counter."""
+        self._refuse_per(buffers, 'iterate')
         name = type(self).__name__
         if getattr(buffers, 'members', None) != self.R:
             raise ValueError(f'{name}.iterate: needs a ReplayBufferGroup of {self.R} members')

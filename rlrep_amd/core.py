@@ -352,6 +352,15 @@ class HipCore:
     def critic_step(self, eps):
         check(lib.rlrep_critic_step(self.h, _ptr(eps), _stream()), 'critic_step')
 
+    def critic_step_weighted(self, eps, w):
+        """critic_step with per-sample weights w[B] in the loss (prioritized replay); leaves |TD| for rlrep_per_update"""
+        check(lib.rlrep_critic_step_weighted(self.h, _ptr(eps), _ptr(w), _stream()), 'critic_step_weighted')
+
+    def per_td(self, B):
+        """float32[B] view of the |TD| errors the last weighted critic step left in the workspace"""
+        off = lib.rlrep_per_td_dev(self.h) - self.workspace.data_ptr()
+        return self.workspace[off:off + 4 * int(B)].view(torch.float32)
+
     def critic_backward(self, eps):
         check(lib.rlrep_critic_backward(self.h, _ptr(eps), _stream()), 'critic_backward')
 
@@ -439,6 +448,10 @@ class HipCore:
 
     def fill_indices(self, t, hi, seed, offset):
         check(lib.rlrep_fill_indices(_ptr(t), t.numel(), int(hi), int(seed), int(offset), _stream()), 'fill_indices')
+
+    def steps_dev(self):
+        """address of the train() counter on the device (what a graph-replayed Philox draw adds to its offset)"""
+        return lib.rlrep_steps_dev(self.h)
 
     def fill_normal_dev(self, t, std, seed, offset):
         check(lib.rlrep_fill_normal_dev(_ptr(t), t.numel(), float(std), int(seed), int(offset),

@@ -126,6 +126,7 @@ void build_sac(Builder& b, rlrep_agent* ag) {
     const int nblk = qhead_blocks(B);
     float* part_q = b.ws.f((size_t)4 * nblk);
     float* part_l = b.ws.f(nblk);
+    ag->per_td = b.ws.f(B);                       // |TD| of the weighted critic head (prioritized replay: rlrep_per_update reads it)
     auto Pw = [&](const char* n) { return ag->P(n); };
     auto Tw = [&](const char* n) { return ag->T(n); };
 
@@ -133,7 +134,9 @@ void build_sac(Builder& b, rlrep_agent* ag) {
     // hoist: the variant that also carries the forward half of the FOLLOWING actor step (policy on s): its three layers read nothing the
     // critic update writes, and as extra tasks of launches that exist anyway they take three launches off train() (rlrep_prefetch_policy)
     const bool can_hoist = policy_fusable(ag) && !rl_off("hoist");
-    auto critic_program = [&](Program& p, bool hoist, bool emit_apply) {
+    // weighted (prioritized replay, rlrep_critic_step_weighted): the head stage is the kernel that takes per-sample weights and leaves |TD|
+    // (per.hip); every other stage, the partials and the apply programs are the unweighted ones
+    auto critic_program = [&](Program& p, bool hoist, bool emit_apply, bool weighted = false) {
         if (hoist) {
             b.fwd_stage(p, {actor_l(ag, 0, s0.XF2, SA, ab), actor_l(ag, 0, s0.XFpi, SA, ab_pi)}, "actor.l1(s') actor.l1(s)");
             b.fwd_stage(p, {actor_l(ag, 1, nullptr, 0, ab), actor_l(ag, 1, nullptr, 0, ab_pi)}, "actor.l2 x2");
@@ -159,6 +162,11 @@ void build_sac(Builder& b, rlrep_agent* ag) {
         q.logp = ab.logp; q.R = s0.R; q.D = s0.D; q.alpha_state = ag->a.alpha_state_dev; q.gamma = ag->h.discount;
         q.inv_batch = ag->inv_batch(); q.dq = dq; q.GE[0] = GE; q.GE[1] = GE + (size_t)B * H; q.partial = part_q;
         q.B = B; q.H = H; q.nblk = nblk; q.train = 1; q.step = ag->adam_step + 1;
+        if (weighted) {
+            float* td = ag->per_td;
+            p.stages.push_back({[=](hipStream_t st) { QHeadCriticW qw; qw.q = q; qw.w = ag->cur_w; qw.td = td; return rl_launch_qhead_critic_w(&qw, st); },
+                                "qhead critic (weighted)"});
+        } else
         p.stages.push_back({[=](hipStream_t st) { return rl_launch_qhead_critic(&q, st); }, "qhead critic"});
         b.dx_stage(p, {Builder::dx(GE, H, B, H, Pw("critic.Q1.2.weight"), H, G1, 2 * H, H, ACT_ELU, E1c, 2 * H),
                        Builder::dx(GE + (size_t)B * H, H, B, H, Pw("critic.Q2.2.weight"), H, G1 + H, 2 * H, H, ACT_ELU, E1c + H, 2 * H)}, "Q l2 dx");
@@ -181,6 +189,10 @@ void build_sac(Builder& b, rlrep_agent* ag) {
     };
     critic_program(ag->critic_bwd, false, true);
     if (can_hoist) critic_program(ag->critic_bwd_h, true, false);
+    if (ag->members == 0 && ag->h.world_size <= 1) {
+        critic_program(ag->critic_bwd_w, false, false, true);
+        if (can_hoist) critic_program(ag->critic_bwd_wh, true, false, true);
+    }
     // ---- actor step ----
     {
         Program& p = ag->actor_bwd;

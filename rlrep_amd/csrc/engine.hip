@@ -124,7 +124,7 @@ bool build_layout(const rlrep_dims& d, Layout& L) {
 static int build_programs(rlrep_agent* ag, int B) {
     ag->B = B;
     ag->ws.used = ag->ws_static;
-    for (Program* p : {&ag->feat_bwd, &ag->feat_apply, &ag->critic_bwd, &ag->critic_apply, &ag->actor_bwd, &ag->actor_apply, &ag->upd_target, &ag->infer, &ag->sync_prog, &ag->critic_bwd_h, &ag->critic_apply_f, &ag->feat_bwd_h, &ag->critic_bwd_h2, &ag->feat_bwd_m, &ag->feat_apply_m})
+    for (Program* p : {&ag->feat_bwd, &ag->feat_apply, &ag->critic_bwd, &ag->critic_apply, &ag->actor_bwd, &ag->actor_apply, &ag->upd_target, &ag->infer, &ag->sync_prog, &ag->critic_bwd_h, &ag->critic_bwd_w, &ag->critic_bwd_wh, &ag->critic_apply_f, &ag->feat_bwd_h, &ag->critic_bwd_h2, &ag->feat_bwd_m, &ag->feat_apply_m})
         p->stages.clear();
     for (auto& D : ag->dset) for (Program* p : {&D.critic_bwd, &D.critic_apply, &D.actor_bwd}) p->stages.clear();
     ag->infer_n = 0; ag->actor_resume = 0; ag->pi_ready = ag->hoist_req = nullptr; ag->in_train = ag->target_done = false;
@@ -691,15 +691,17 @@ int32_t rlrep_prefetch_policy(rlrep_agent* ag, const float* eps_actor) {
     ag->hoist_req = eps_actor;
     return 1;
 }
-int32_t rlrep_critic_backward(rlrep_agent* ag, const float* eps, void* stream) {
+// The critic step's backward half, shared by rlrep_critic_backward (w == nullptr) and rlrep_critic_step_weighted (w = per-sample weights, sac
+// only: the program pair whose head stage is the weighted kernel, per.hip): one dispatch, so the two cannot drift apart.
+static int critic_backward_dispatch(rlrep_agent* ag, const float* eps, const float* w, void* stream) {
     STEP_PROLOGUE(false)
     if (!eps) { rl_set_error("critic step needs eps[B,A]"); return RLREP_ERR_ARG; }
-    ag->cur_eps = eps; ag->last_launches = 0;
+    ag->cur_eps = eps; ag->cur_w = w; ag->last_launches = 0;
     ag->pi_ready = nullptr;
     // the images of critic.l1 / l4 and of their targets, from the tensors as they are now: the target copies have no other writer, and a
     // caller may have written any of them since the last step (the launch rides on the chain that has slack in the pipelined train())
     if (!ag->images_managed) { const int rs = refresh_x3(ag, stream); if (rs) return rs; }
-    if (ag->early_ready_crit && ag->early_ready_crit == eps) {      // both policy forwards already ran (last feature step)
+    if (!w && ag->early_ready_crit && ag->early_ready_crit == eps) {      // both policy forwards already ran (last feature step; never for sac)
         const float* act_eps = ag->early_ready_act;
         ag->early_ready_crit = ag->early_ready_act = nullptr; ag->hoist_req = nullptr;
         const int rc = run(ag, ag->critic_bwd_h2, stream);
@@ -707,14 +709,17 @@ int32_t rlrep_critic_backward(rlrep_agent* ag, const float* eps, void* stream) {
         return rc;
     }
     ag->early_ready_crit = ag->early_ready_act = nullptr;
-    if (ag->hoist_req) {
+    const Program& hoisted = w ? ag->critic_bwd_wh : ag->critic_bwd_h;
+    if (ag->hoist_req && !hoisted.stages.empty()) {
         ag->cur_eps2 = ag->hoist_req; ag->hoist_req = nullptr;
-        const int rc = run(ag, ag->critic_bwd_h, stream);
+        const int rc = run(ag, hoisted, stream);
         if (rc == 0) ag->pi_ready = ag->cur_eps2;
         return rc;
     }
-    return run(ag, ag->critic_bwd, stream);
+    ag->hoist_req = nullptr;
+    return run(ag, w ? ag->critic_bwd_w : ag->critic_bwd, stream);
 }
+int32_t rlrep_critic_backward(rlrep_agent* ag, const float* eps, void* stream) { return critic_backward_dispatch(ag, eps, nullptr, stream); }
 int32_t rlrep_critic_apply(rlrep_agent* ag, void* stream) {
     STEP_PROLOGUE(false)
     if (ag->in_train && !ag->target_done && !ag->critic_apply_f.stages.empty()) {
@@ -745,6 +750,70 @@ int32_t rlrep_critic_step(rlrep_agent* ag, const float* eps, void* stream) {
     int rc = rlrep_critic_backward(ag, eps, stream);
     return rc ? rc : rlrep_critic_apply(ag, stream);
 }
+// ---- prioritized replay (per.hip) -------------------------------------------------------------------------------------
+static bool per_tree_ok(const char* what, const float* tree, int64_t P, const float* scal) {
+    if (!tree || !scal || P < 1 || P > (1ll << 30) || (P & (P - 1)) != 0) { rl_set_error("%s: bad argument (null tree / scalars, or P %lld is not a power of two in [1, 2^30])", what, (long long)P); return false; }
+    return true;
+}
+// the entry points that work for ONE sac agent on ONE GPU
+static int per_agent_ok(const char* what, const rlrep_agent* ag) {
+    if (!ag) { rl_set_error("%s: null agent", what); return RLREP_ERR_ARG; }
+    if (ag->members > 0) { rl_set_error("%s: not available on a seed group (rlrep_group_create): prioritized replay is built for one sac agent", what); return RLREP_ERR_ARG; }
+    if (ag->d.alg != RLREP_ALG_SAC) { rl_set_error("%s: prioritized replay is built for sac only (the representation agents reuse their last feature minibatch)", what); return RLREP_ERR_ARG; }
+    if (ag->h.world_size > 1) { rl_set_error("%s: prioritized replay runs on one GPU (world_size = %d)", what, ag->h.world_size); return RLREP_ERR_ARG; }
+    return 0;
+}
+int32_t rlrep_per_add(float* tree_dev, int64_t P, const float* scal_dev, int64_t capacity, int64_t start, int64_t n, void* stream) {
+    if (!per_tree_ok("per_add", tree_dev, P, scal_dev)) return RLREP_ERR_ARG;
+    if (capacity < 1 || capacity > P || start < 0 || start >= capacity || n < 1 || n > capacity) {
+        rl_set_error("per_add: rows [%lld, +%lld) of a ring of %lld rows (tree of %lld leaves)", (long long)start, (long long)n, (long long)capacity, (long long)P); return RLREP_ERR_ARG;
+    }
+    PerAdd p; memset(&p, 0, sizeof(p));
+    p.tree = tree_dev; p.scal = scal_dev; p.P = P; p.capacity = capacity; p.start = start; p.n = n;
+    const int rc = (++g_rl_launches, rl_launch_per_add(&p, (hipStream_t)stream));
+    if (rc) { rl_set_error("per_add: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_per_rebuild(float* tree_dev, int64_t P, void* stream) {
+    if (!per_tree_ok("per_rebuild", tree_dev, P, tree_dev)) return RLREP_ERR_ARG;
+    const int rc = (++g_rl_launches, rl_launch_per_rebuild(tree_dev, P, (hipStream_t)stream));
+    if (rc) { rl_set_error("per_rebuild: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_per_sample(rlrep_agent* ag, const float* tree_dev, int64_t P, const float* scal_dev, int32_t* idx_dev, float* w_dev, int32_t batch, int32_t given,
+                         uint64_t seed, uint64_t offset, const int32_t* counter_dev, void* stream) {
+    if (int rc = per_agent_ok("per_sample", ag)) return rc;
+    if (!per_tree_ok("per_sample", tree_dev, P, scal_dev)) return RLREP_ERR_ARG;
+    if (!idx_dev || !w_dev || batch < 1) { rl_set_error("per_sample: bad argument (null idx / w, or batch %d)", batch); return RLREP_ERR_ARG; }
+    PerSample p; memset(&p, 0, sizeof(p));
+    p.tree = tree_dev; p.scal = scal_dev; p.idx = idx_dev; p.w = w_dev; p.P = P; p.B = batch; p.given = given ? 1 : 0;
+    p.seed = seed; p.offset = offset; p.step_dev = counter_dev;
+    const int rc = (++g_rl_launches, rl_launch_per_sample(&p, (hipStream_t)stream));
+    if (rc) { rl_set_error("per_sample: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+const float* rlrep_per_td_dev(rlrep_agent* ag) { return (ag && ag->members == 0 && ag->d.alg == RLREP_ALG_SAC) ? ag->per_td : nullptr; }
+int32_t rlrep_per_update(rlrep_agent* ag, float* tree_dev, int64_t P, float* scal_dev, const int32_t* idx_dev, const float* td_dev, int32_t batch, void* stream) {
+    if (int rc = per_agent_ok("per_update", ag)) return rc;
+    if (!per_tree_ok("per_update", tree_dev, P, scal_dev)) return RLREP_ERR_ARG;
+    if (!idx_dev || batch < 1 || (!td_dev && batch != ag->B)) { rl_set_error("per_update: bad argument (null idx, or batch %d is not the batch of the last weighted critic step)", batch); return RLREP_ERR_ARG; }
+    PerUpdate p; memset(&p, 0, sizeof(p));
+    p.tree = tree_dev; p.scal = scal_dev; p.idx = idx_dev; p.td = td_dev ? td_dev : ag->per_td; p.P = P; p.B = batch;
+    if (!p.td) { rl_set_error("per_update: no weighted critic step has run"); return RLREP_ERR_STATE; }
+    const int rc = (++g_rl_launches, rl_launch_per_update(&p, (hipStream_t)stream));
+    if (rc) { rl_set_error("per_update: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+// rlrep_critic_step with per-sample weights w[B]: the same launches, the head stage replaced by the weighted kernel, which also leaves
+// td[b] = 0.5 (|q1 - y| + |q2 - y|) in the agent's workspace (rlrep_per_td_dev) for rlrep_per_update
+int32_t rlrep_critic_step_weighted(rlrep_agent* ag, const float* eps, const float* w, void* stream) {
+    if (int rc = per_agent_ok("critic_step_weighted", ag)) return rc;
+    if (!eps || !w) { rl_set_error("critic_step_weighted: needs eps[B,A] and w[B]"); return RLREP_ERR_ARG; }
+    if (ag->critic_bwd_w.stages.empty()) { rl_set_error("critic_step_weighted: no weighted critic program was built for this agent"); return RLREP_ERR_STATE; }
+    const int rc = critic_backward_dispatch(ag, eps, w, stream);
+    return rc ? rc : rlrep_critic_apply(ag, stream);
+}
+
 int32_t rlrep_actor_alpha_step(rlrep_agent* ag, const float* eps, void* stream) {
     int rc = rlrep_actor_backward(ag, eps, stream);
     return rc ? rc : rlrep_actor_apply(ag, stream);

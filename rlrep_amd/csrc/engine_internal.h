@@ -31,6 +31,9 @@ struct rlrep_agent {
     // changes, so its GEMMs can ride along in the critic step's launches (critic_bwd_h) and the actor step then
     // resumes at stage actor_resume.  Armed per train() by rlrep_prefetch_policy; see there for the protocol.
     Program critic_bwd_h; int actor_resume = 0;
+    // prioritized replay (sac; per.hip): the critic programs whose head stage is the weighted kernel (rlrep_critic_step_weighted; the apply
+    // programs are the unweighted ones), the per-sample weights of the call in progress and the |TD| errors the head leaves for rlrep_per_update
+    Program critic_bwd_w, critic_bwd_wh; const float* cur_w = nullptr; float* per_td = nullptr;
     // Inside a rlrep_begin_train .. rlrep_update_target bracket the Polyak critic -> critic_target is folded into the
     // critic's Adam launch (critic_apply_f): nothing between the two reads critic_target, and the update_target launch
     // (~2 us + a launch boundary) disappears.  Outside a bracket every entry point does exactly what its name says.

@@ -110,6 +110,15 @@ struct QHeadCritic {
     int ldE;                   // row stride of Et/Ec/GE (0 -> H)
 };
 
+// prioritized replay (per.hip).  tree: float32[2P] sum tree, row i's leaf at tree[P + i]; scal: float32[4] = {max_p, alpha, beta, eps}
+struct QHeadCriticW { QHeadCritic q; const float* w; float* td; };      // the weighted sac critic head: per-sample weights w[B] in, |TD| td[B] out
+struct PerAdd { float* tree; const float* scal; long long P, capacity, start, n; };
+struct PerSample {
+    const float* tree; const float* scal; int* idx; float* w; long long P; int B, given;       // given: idx[B] is an input, only the weights are computed
+    unsigned long long seed, offset; const int* step_dev;                                       // Philox stream: offset + *step_dev (null: offset)
+};
+struct PerUpdate { float* tree; float* scal; const int* idx; const float* td; long long P; int B; };
+
 struct QHeadActor {
     const float* Ec[2]; const float* wc[2]; const float* bc[2];
     const float* logp; const double* alpha_state; float inv_batch, target_entropy;

@@ -74,6 +74,12 @@ int rl_launch_replay_add_cols(const ReplayCols* p, int members, hipStream_t st);
 // ---- actor_tile.hip ----
 long long rl_actor_tile_lds_bytes(int S, int Ha, int A);
 int rl_launch_actor_tile(const ActTile* p, hipStream_t st);                        // p->rows observations (per member of an active group), 16 per workgroup
+// ---- per.hip (prioritized replay: one workgroup each; the weighted sac critic head) ----
+int rl_launch_per_add(const PerAdd* p, hipStream_t st);
+int rl_launch_per_rebuild(float* tree, long long P, hipStream_t st);
+int rl_launch_per_sample(const PerSample* p, hipStream_t st);
+int rl_launch_per_update(const PerUpdate* p, hipStream_t st);
+int rl_launch_qhead_critic_w(const QHeadCriticW* p, hipStream_t st);
 // ---- replearn.hip ----
 int rl_replearn_init();
 int rl_launch_infonce(const InfoNce* p, hipStream_t st);

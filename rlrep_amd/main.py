@@ -140,7 +140,14 @@ def run(argv=None):
                    help='environments of a torch simulator on the device (one agent, --env Pendulum-v1; 1..65536, 0 = off; --start_timesteps and '
                         '--eval_freq multiples of it; not with --seeds, --sweep, --device-env, --device-loop, --host-envs, --num-envs).  An iteration '
                         'is N transitions -- one act_device launch, one batched step, one add_device launch -- and one train()')
+    p.add_argument('--per', action='store_true',
+                   help='prioritized experience replay (Schaul et al. 2016; --alg sac, one agent): train() samples in proportion to '
+                        '(|TD| + eps)^alpha from a sum tree on the device and weights the critic loss; beta is annealed linearly to 1 at '
+                        '--max_timesteps, written at every evaluation.  Runs with the plain loop, --host-envs and --torch-envs')
+    p.add_argument('--per-alpha', default=0.6, type=float, help='priority exponent alpha (0 = uniform replay; default 0.6)')
+    p.add_argument('--per-beta', default=0.4, type=float, help='initial importance-sampling exponent beta (default 0.4)')
     args = p.parse_args(argv)
+    _check_per(args)
     _check_num_envs(args)
     _check_host_envs(args)
     _check_torch_envs(args)
@@ -172,7 +179,10 @@ def run(argv=None):
 
     state_dim, action_dim = env.observation_space.shape[0], env.action_space.shape[0]
     agent = build_agent(args, state_dim, action_dim, env.action_space)
-    replay = buffer.ReplayBuffer(state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)))
+    if getattr(args, 'per', False):
+        replay = buffer.PrioritizedReplayBuffer(state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)), alpha=args.per_alpha, beta=args.per_beta)
+    else:
+        replay = buffer.ReplayBuffer(state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)))
     if args.device_loop:
         return _single_device_loop(args, agent, replay, log_path, jsonl, tb)
     if args.host_envs > 1:
@@ -201,6 +211,7 @@ def run(argv=None):
             state, done = env.reset(), False
             ep_reward, ep_steps, ep_num = 0.0, 0, ep_num + 1
         if (t + 1) % args.eval_freq == 0:
+            _per_anneal(args, replay, t + 1)
             sps = timer.steps_per_sec(t + 1)
             evaluations.append(util.eval_policy(agent, eval_env, args.eval_episodes))
             if info is not None:
@@ -221,6 +232,30 @@ def run(argv=None):
         tb.close()
     print('Total time cost {:.4g}s.'.format(timer.time_cost()))
     return agent, evaluations
+
+
+def _check_per(args):
+    """--per: SystemExit, before anything touches the GPU, on what prioritized replay does not run with (an argument namespace without the
+    field -- built by hand -- is a run without it)"""
+    if not getattr(args, 'per', False):
+        return
+    if args.alg != 'sac':
+        raise SystemExit(f'--per: prioritized replay is built for --alg sac (got --alg {args.alg}: the representation agents reuse their last '
+                         'feature minibatch for the critic step)')
+    for flag, given in (('--seeds', args.seeds is not None), ('--sweep', bool(args.sweep)), ('--device-env', args.device_env),
+                        ('--device-loop', args.device_loop), ('--pbt-interval', _pbt_requested(args)),
+                        ('--halving-interval', _halving_requested(args))):
+        if given:
+            raise SystemExit(f'--per: prioritized replay trains ONE agent from a ring the host or add_device fills; it does not go with {flag}')
+    if not 0.0 <= float(args.per_alpha) or not 0.0 <= float(args.per_beta) <= 1.0:
+        raise SystemExit(f'--per: --per-alpha {args.per_alpha} must be >= 0 and --per-beta {args.per_beta} in [0, 1]')
+
+
+def _per_anneal(args, replay, t):
+    """--per: beta rises linearly from --per-beta to 1.0 at --max_timesteps; written (one device word) at the evaluation boundaries"""
+    if getattr(args, 'per', False):
+        frac = min(1.0, float(t) / float(args.max_timesteps))
+        replay.beta = 1.0 if frac >= 1.0 else float(args.per_beta) + (1.0 - float(args.per_beta)) * frac
 
 
 def _check_num_envs(args):
@@ -301,6 +336,7 @@ def _host_envs_loop(args, agent, replay, log_path, jsonl, tb):
             info = agent.train(replay, batch_size=args.batch_size)
         t = t0 + E
         if t % args.eval_freq == 0:
+            _per_anneal(args, replay, t)
             sps = timer.steps_per_sec(t)
             evaluations.append(util.eval_policy_vec(agent, eval_envs, args.eval_episodes))
             if info is not None:
@@ -389,6 +425,7 @@ def _torch_envs_loop(args, agent, replay, log_path, jsonl, tb):
             info = agent.train(replay, batch_size=args.batch_size)
         t = t0 + N
         if t % args.eval_freq == 0:
+            _per_anneal(args, replay, t)
             sps = timer.steps_per_sec(t)
             evaluations.append(_torch_eval(agent, eval_env, int(args.eval_episodes)))
             if info is not None:

@@ -253,7 +253,11 @@ class ReplayBuffer(object):
     def save(self, path):
         self.flush()
         torch.cuda.synchronize() if self.device.type == 'cuda' else None
-        np.savez_compressed(path, ring=self.ring[:self.size].cpu().numpy(), ptr=self.ptr, size=self.size, offered=self._offered)
+        np.savez_compressed(path, **self._save_arrays())
+
+    def _save_arrays(self):
+        """what save() writes (a subclass adds its own arrays)"""
+        return dict(ring=self.ring[:self.size].cpu().numpy(), ptr=self.ptr, size=self.size, offered=self._offered)
 
     def restore(self, path):
         z = np.load(path)
@@ -318,3 +322,236 @@ class ReplayBuffer(object):
     @property
     def done(self):
         return self._col(2 * self.state_dim + self.action_dim + 1, 2 * self.state_dim + self.action_dim + 2)
+
+
+# ---- prioritized replay (Schaul et al. 2016) for sac: DESIGN.md 6f, csrc/per.hip ---------------------------------------------------------
+def _f32(x):
+    return np.float32(x)
+
+
+PER_MIN_PRIORITY = np.float32(1.17549435e-38)        # the smallest normal float32: the floor of an updated leaf (csrc/per.hip)
+
+
+def _per_set(tree, P, rows, value):
+    """host form of per_add / restore: leaves of `rows` <- value, every ancestor one fp32 add of its children"""
+    rows = np.asarray(rows, np.int64)
+    if rows.size == 0:
+        return
+    tree[P + rows] = value
+    nodes = np.unique((P + rows) >> 1)
+    while nodes.size and nodes[0] >= 1:
+        tree[nodes] = tree[2 * nodes] + tree[2 * nodes + 1]          # (float32 arrays: one rounded add)
+        nodes = np.unique(nodes >> 1)
+
+
+def _per_draw(tree, P, B, words):
+    """host form of per_sample's descent: B stratified draws from uint32 Philox words"""
+    total = tree[1]
+    seg = _f32(total / _f32(B))
+    u = ((words >> np.uint32(8)).astype(np.float32) + _f32(0.5)) * _f32(1.0 / 16777216.0)
+    m = (np.arange(B, dtype=np.float32) + u) * seg
+    n = np.ones(B, np.int64)
+    while n[0] < P:
+        l, r = tree[2 * n], tree[2 * n + 1]
+        left = (r == 0) | (m < l)
+        m = np.where(left, m, m - l).astype(np.float32)
+        n = np.where(left, 2 * n, 2 * n + 1)
+    return (n - P).astype(np.int32)
+
+
+class PrioritizedReplayBuffer(ReplayBuffer):
+    """ReplayBuffer whose rows carry priorities in a device-resident sum tree (float32[2P], P = the smallest power of two >= max_size, row
+    i's leaf at tree[P + i], an internal node ONE fp32 add of its children).  A row written by add() / add_batch() (at flush()), add_device()
+    or load() gets the running maximum priority; SACAgent.train() samples in proportion to the leaves (stratified, one launch), weights the
+    critic loss by (N P(j))^-beta normalised by the batch maximum, and writes (|TD| + eps)^alpha back -- all inside the captured train(), no
+    host round trip.  `beta` may be assigned at any time (one device word, written on the caller's stream).  For SACAgent on one GPU; every
+    other agent refuses the class by name.  On device='cpu' the same arithmetic runs in NumPy float32 (draw() / update())."""
+    prioritized = True
+
+    def __init__(self, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, shard=None, alpha=0.6, beta=0.4, eps=1e-6):
+        if shard is not None:
+            raise ValueError('PrioritizedReplayBuffer: shard= is not supported (a shard sees one transition in `world`; priorities are per ring)')
+        super().__init__(state_dim, action_dim, max_size=max_size, device=device, stage_rows=stage_rows)
+        self.P = 1 << max(0, self.max_size - 1).bit_length()
+        self.tree = torch.zeros(2 * self.P, dtype=torch.float32, device=self.device)
+        self._scal = torch.tensor([1.0, alpha, beta, eps], dtype=torch.float32, device=self.device)      # max_p, alpha, beta, eps
+        self._hyper = (float(_f32(alpha)), float(_f32(beta)), float(_f32(eps)))
+        self._draw_bufs = {}
+
+    # ---- hyper-parameters and views --------------------------------------------------------------
+    alpha = property(lambda self: self._hyper[0])
+    eps = property(lambda self: self._hyper[2])
+
+    @property
+    def beta(self):
+        return self._hyper[1]
+
+    @beta.setter
+    def beta(self, x):
+        self._hyper = (self._hyper[0], float(_f32(x)), self._hyper[2])
+        self._before_device_write()
+        self._scal[2:3].fill_(float(x))              # (a fill launch on the caller's stream: no synchronisation)
+        self.device_epoch += 1
+
+    @property
+    def max_priority(self):
+        return float(self._scal[0].cpu())
+
+    def priorities(self):
+        """float32[size]: the leaves of the rows the ring holds (flushes staged rows; synchronises)"""
+        self.flush()
+        self._order_reads()
+        return self.tree[self.P:self.P + self.size].cpu().numpy()
+
+    def per_key(self):
+        """what a captured train() bakes in besides the ring: the tree and the scalar block"""
+        return ('per', self.tree.data_ptr(), self._scal.data_ptr())
+
+    # ---- writers: every written row gets the running maximum priority ----------------------------
+    def _per_add(self, start, n):
+        if n <= 0:
+            return
+        if self.device.type == 'cuda':
+            import ctypes as C
+            from rlrep_amd._lib import lib, check
+
+            def issue():
+                check(lib.rlrep_per_add(C.c_void_p(self.tree.data_ptr()), self.P, C.c_void_p(self._scal.data_ptr()), self.max_size, int(start), int(n),
+                                        C.c_void_p(_raw_stream())), 'per_add')
+            if self.device.index is None or self.device.index == _current_device_index():
+                issue()
+            else:
+                with torch.cuda.device(self.device):
+                    issue()
+        else:
+            _per_set(self.tree.numpy(), self.P, (int(start) + np.arange(int(n))) % self.max_size, self._scal.numpy()[0])
+
+    def flush(self):
+        a, n = self._stage_start, self._staged
+        super().flush()
+        self._per_add(a, n)
+
+    def add_device(self, states, actions, next_states, rewards, dones):
+        epoch = self.device_epoch
+        self.flush()                                 # (staged host rows first, with their leaves: the order of transitions is the call order)
+        start = self.ptr
+        super().add_device(states, actions, next_states, rewards, dones)
+        self._per_add(start, int(rewards.shape[0]))
+        self.device_epoch = epoch + 1
+
+    def load(self, state, action, next_state, reward, done):
+        super().load(state, action, next_state, reward, done)
+        self.tree.zero_()                            # load() resets the ring to its first n rows: rows it no longer holds lose their leaves (max_p stays)
+        self._per_add(0, self.size)
+
+    def collect_on_device(self, env):
+        raise RuntimeError('PrioritizedReplayBuffer.collect_on_device: a device environment writes ring rows inside its step launch, which knows '
+                           'nothing of the priority tree (iterate() / --device-loop take a plain ReplayBuffer)')
+
+    def _save_arrays(self):
+        return dict(super()._save_arrays(), per_leaves=self.tree[self.P:self.P + self.size].cpu().numpy(), per_max_p=self._scal[:1].cpu().numpy())
+
+    def restore(self, path):
+        super().restore(path)
+        z = np.load(path)
+        n = self.size
+        self.tree.zero_()
+        if 'per_leaves' not in z.files:              # a plain ReplayBuffer's file: every row is new
+            self._scal[0:1].fill_(1.0)
+            self._per_add(0, n)
+            return
+        self.set_priorities(z['per_leaves'], float(np.asarray(z['per_max_p']).reshape(-1)[0]))
+
+    def set_priorities(self, leaves, max_priority=None):
+        """Overwrite the leaves of rows 0 .. len(leaves) - 1 (every other leaf becomes 0) and rebuild the tree; max_priority, if given,
+        replaces the running maximum.  What restore() does with a saved tree; also for tests and for priorities computed elsewhere."""
+        leaves = np.asarray(leaves, np.float32).reshape(-1)
+        n = len(leaves)
+        if n > self.size:
+            raise ValueError(f'PrioritizedReplayBuffer.set_priorities: {n} leaves for a ring that holds {self.size} rows')
+        self.flush()
+        self._before_device_write()
+        self.tree.zero_()
+        if max_priority is not None:
+            self._scal[0:1].copy_(torch.from_numpy(np.asarray([max_priority], np.float32)))
+        self.tree[self.P:self.P + n].copy_(torch.from_numpy(leaves))
+        self.device_epoch += 1
+        if self.device.type == 'cuda':
+            import ctypes as C
+            from rlrep_amd._lib import lib, check
+            with torch.cuda.device(self.device):
+                check(lib.rlrep_per_rebuild(C.c_void_p(self.tree.data_ptr()), self.P, C.c_void_p(_raw_stream())), 'per_rebuild')
+        else:
+            t = self.tree.numpy()
+            w = self.P >> 1
+            while w >= 1:
+                nd = np.arange(w, 2 * w)
+                t[nd] = t[2 * nd] + t[2 * nd + 1]
+                w >>= 1
+
+    # ---- the sampler and the priority update (SACAgent calls these inside train()) ---------------
+    def draw_buffers(self, B):
+        """(idx int32[B], w float32[B]) on the ring's device, one pair per batch size for the life of the buffer (captured graphs bake them in)"""
+        bufs = self._draw_bufs.get(int(B))
+        if bufs is None:
+            bufs = self._draw_bufs[int(B)] = (torch.zeros(int(B), dtype=torch.int32, device=self.device),
+                                              torch.ones(int(B), dtype=torch.float32, device=self.device))
+        return bufs
+
+    def draw(self, B, seed, offset, core=None, counter_dev=None, given=None):
+        """B stratified draws in proportion to the priorities, and their importance weights -> (idx, w) = draw_buffers(B).  The draws are
+        Philox stream elements 0 .. B-1 of (seed, offset [+ the device counter]); `given` (int32[B]): take these indices, compute only the
+        weights.  On the device ONE launch on the current stream (`core`: the sac agent's HipCore).  An empty buffer is refused here."""
+        B = int(B)
+        if self.size == 0:
+            raise RuntimeError('PrioritizedReplayBuffer.draw: the buffer is empty')
+        idx, w = self.draw_buffers(B)
+        if given is not None:
+            g = np.asarray(given.cpu() if torch.is_tensor(given) else given).reshape(-1)
+            if len(g) != B or g.min() < 0 or g.max() >= self.size:
+                raise ValueError(f'PrioritizedReplayBuffer.draw: given indices must be {B} rows in [0, {self.size})')
+            idx.copy_(torch.from_numpy(g.astype(np.int32)))
+        if self.device.type == 'cuda':
+            import ctypes as C
+            from rlrep_amd._lib import lib, check
+            if core is None:
+                raise ValueError('PrioritizedReplayBuffer.draw: the device sampler runs for a sac agent (core=agent.core)')
+            self._order_reads()
+            check(lib.rlrep_per_sample(core.h, C.c_void_p(self.tree.data_ptr()), self.P, C.c_void_p(self._scal.data_ptr()), C.c_void_p(idx.data_ptr()),
+                                       C.c_void_p(w.data_ptr()), B, 0 if given is None else 1, int(seed), int(offset), C.c_void_p(counter_dev),
+                                       C.c_void_p(_raw_stream())), 'per_sample')
+            return idx, w
+        from rlrep_amd.utils.philox_host import raw_stream as words
+        t = self.tree.numpy()
+        if given is None:
+            idx.copy_(torch.from_numpy(_per_draw(t, self.P, B, words(B, int(seed), int(offset)))))
+        p = t[self.P + idx.numpy().astype(np.int64)]
+        pmin, beta = p.min(), _f32(self._hyper[1])
+        with np.errstate(divide='ignore', invalid='ignore'):
+            wv = np.power((pmin / p).astype(np.float32), beta, dtype=np.float32)
+        w.copy_(torch.from_numpy(np.where((p == pmin) | (beta == 0), _f32(1.0), wv).astype(np.float32)))
+        return idx, w
+
+    def update(self, B, td=None, core=None):
+        """leaf idx[j] <- (td[j] + eps)^alpha for the last draw of B (1 when alpha == 0; the maximum where an index repeats), max_priority
+        follows, the ancestors are recomputed.  On the device ONE launch; td=None: the |TD| errors the agent's last weighted critic step left."""
+        B = int(B)
+        idx, _ = self.draw_buffers(B)
+        if self.device.type == 'cuda':
+            import ctypes as C
+            from rlrep_amd._lib import lib, check
+            if core is None:
+                raise ValueError('PrioritizedReplayBuffer.update: the device update runs for a sac agent (core=agent.core)')
+            check(lib.rlrep_per_update(core.h, C.c_void_p(self.tree.data_ptr()), self.P, C.c_void_p(self._scal.data_ptr()), C.c_void_p(idx.data_ptr()),
+                                       C.c_void_p(None if td is None else td.data_ptr()), B, C.c_void_p(_raw_stream())), 'per_update')
+            return
+        t, s = self.tree.numpy(), self._scal.numpy()
+        td = np.asarray(td, np.float32).reshape(B)
+        alpha = _f32(self._hyper[0])
+        new = np.ones(B, np.float32) if alpha == 0 else np.power(td + _f32(self._hyper[2]), alpha, dtype=np.float32)
+        new = np.where(new > PER_MIN_PRIORITY, new, PER_MIN_PRIORITY).astype(np.float32)     # (not positive, or NaN: the floor, as per_update_kernel)
+        rows = idx.numpy().astype(np.int64)
+        t[self.P + rows] = 0
+        np.maximum.at(t, self.P + rows, new)
+        s[0] = max(s[0], new.max())
+        _per_set(t, self.P, rows, t[self.P + rows])
