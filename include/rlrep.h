@@ -386,6 +386,27 @@ int32_t rlrep_per_update(rlrep_agent* agent, float* tree_dev, int64_t P, float* 
 int32_t rlrep_critic_step_weighted(rlrep_agent* agent, const float* eps_dev, const float* w_dev, void* stream);
 const float* rlrep_per_td_dev(rlrep_agent* agent);
 
+/* ---- prioritized replay for sac SEED GROUPS (additive to ABI 4; DESIGN.md 6g, csrc/per_group.hip) --------------------------------------------
+ * Every member has a tree and a scalar block of its own, owned by the caller: trees_dev float32[members, 2 P] (member m's tree at m * 2 P
+ * floats, laid out as above), scal_dev float32[members, 4], the draw buffers idx_dev int32[members, batch] and w_dev float32[members, batch].
+ * One launch each (the sample with its gather: two), grid (x, members), stream-ordered and capturable; member m computes bit for bit what the rlrep_per_* entry points compute
+ * for a single agent created with seed seeds[m] on m's slices.  Retired members (rlrep_group_set_live) are skipped by all but rlrep_group_per_add.
+ *   rlrep_group_per_add      rlrep_per_add for every member, retired ones included (the ring writers write every member's ring): no agent.
+ *   rlrep_group_per_sample   rlrep_per_sample for every live member: key = the member's seed (rlrep_group_set_seeds), stream offset
+ *                            `offset` + the member's train() counter when use_counter != 0.  ring_dev != NULL (member 0's ring; rings of
+ *                            `capacity` rows ring_stride_bytes apart): a second launch GATHERS the drawn rows into the members' minibatch
+ *                            slot 0 (a group has no rlrep_replay_sample); batch must then be the prepared batch (rlrep_group_prepare).
+ *   rlrep_group_critic_step_weighted   rlrep_critic_step_weighted for every live member, w_dev[members, B]; discount from the member's hyper record.
+ *   rlrep_group_per_update   rlrep_per_update for every live member; td_dev NULL: each member's |TD| of the last weighted critic step
+ *                            (rlrep_group_per_td_dev: member 0's, member m's lies m member strides further), else float32[members, batch].
+ * The entry points that take an agent refuse, by name: a single agent's handle ("not a seed group"), a ctrlsac group, world_size > 1. */
+int32_t rlrep_group_per_add(float* trees_dev, int64_t P, const float* scal_dev, int32_t members, int64_t capacity, int64_t start, int64_t n, void* stream);
+int32_t rlrep_group_per_sample(rlrep_agent* group, const float* trees_dev, int64_t P, const float* scal_dev, int32_t* idx_dev, float* w_dev, int32_t batch, int32_t given,
+                               uint64_t offset, int32_t use_counter, const float* ring_dev, int64_t ring_stride_bytes, int64_t capacity, void* stream);
+int32_t rlrep_group_per_update(rlrep_agent* group, float* trees_dev, int64_t P, float* scal_dev, const int32_t* idx_dev, const float* td_dev, int32_t batch, void* stream);
+int32_t rlrep_group_critic_step_weighted(rlrep_agent* group, const float* eps_dev, const float* w_dev, void* stream);
+const float* rlrep_group_per_td_dev(rlrep_agent* group);
+
 /* ---- metrics ------------------------------------------------------------------------------ */
 /* device float array of n_metrics slots, valid after the stream has passed the producing step */
 const float* rlrep_metrics_dev(rlrep_agent* agent);

@@ -464,9 +464,12 @@ class SACAgent(object):
 
     def _check_per(self, buffer, what):
         """A prioritized buffer trains ONE sac agent on ONE GPU; everything else refuses it by its class name, before anything is launched."""
+        name, cls = type(self).__name__, type(buffer).__name__
+        if getattr(buffer, 'prioritized_group', False):
+            raise RuntimeError(f'{name}.{what}: {cls} is built for SACSeedBatch.train (a sac seed group); a single agent takes a '
+                               'PrioritizedReplayBuffer')
         if not self._per(buffer):
             return
-        name, cls = type(self).__name__, type(buffer).__name__
         if self.ALG != 'sac':
             raise RuntimeError(f'{name}.{what}: {cls} is built for SACAgent only ({self.ALG} reuses its last feature minibatch for the critic step; '
                                'what prioritisation means there is open): use a plain ReplayBuffer')

@@ -148,7 +148,7 @@ class SeedBatchMixin(object):
         return v
 
     @classmethod
-    def member_hypers(cls, seeds, kwargs, member_hyper):
+    def member_hypers(cls, seeds, kwargs, member_hyper, distinct=True):
         """Each member's sweepable hyper-parameters (dicts in SWEEP_KEYS order), checked before anything touches the GPU."""
         name = cls.__name__
         defaults = cls.sweep_defaults()
@@ -173,7 +173,7 @@ class SeedBatchMixin(object):
             h.update({k: cls.normalise_hyper(k, v, f'{name}: member_hyper[{r}]') for k, v in mh.items()})
             out.append(h)
         seen = {}
-        for r, (s, h) in enumerate(zip(seeds, out)):
+        for r, (s, h) in enumerate(zip(seeds, out) if distinct else ()):
             key = (s, tuple(h.items()))
             if key in seen:
                 raise ValueError(f'{name}: members {seen[key]} and {r} have the same seed {s} and the same hyper-parameters (duplicate (seed, hyper) pair)')
@@ -187,7 +187,11 @@ class SeedBatchMixin(object):
             raise ValueError(f'{name}: at least one seed')
         if member_hyper is None and len(set(self.seeds)) != len(self.seeds):
             raise ValueError(f'{name}: seeds must be distinct')
-        self._mhyper = self.member_hypers(self.seeds, kwargs, member_hyper)
+        kwargs = dict(kwargs)
+        # distinct_members=False: members may share (seed, hyper-parameters) -- they differ in something the agent does not see, the priority
+        # exponents of their replay trees (PrioritizedReplayBufferGroup)
+        distinct = bool(kwargs.pop('distinct_members', True))
+        self._mhyper = self.member_hypers(self.seeds, kwargs, member_hyper, distinct=distinct)
         self._swept = member_hyper is not None
         self.lineage = []                       # one record per clone / retune (clone_members, set_member_hyper); checkpoints carry it
         self.R = len(self.seeds)
@@ -382,7 +386,37 @@ class SeedBatchMixin(object):
 
     @staticmethod
     def _graph_cache_key(buffer, B):
-        return (buffer.rings.data_ptr(), buffer.size_dev().data_ptr(), int(buffer.max_size), buffer.members, B)
+        key = (buffer.rings.data_ptr(), buffer.size_dev().data_ptr(), int(buffer.max_size), buffer.members, B)
+        per = getattr(buffer, 'per_key', None)               # (a prioritized buffer group: its trees and scalar block are baked in as well)
+        return key if per is None else key + per()
+
+    # ---- prioritized replay (utils/buffer_group.py PrioritizedReplayBufferGroup) ---------------------------------------------
+    @staticmethod
+    def _per(buffer):
+        return bool(getattr(buffer, 'prioritized_group', False))
+
+    def _check_per(self, buffer, what):
+        """A prioritized buffer GROUP trains a sac seed group through train(); everything else refuses it by its class name, before
+        anything is launched.  (The single ring's class is refused by _refuse_per / SACAgent._check_per, as before.)"""
+        if not self._per(buffer):
+            return super()._check_per(buffer, what)
+        name, cls = type(self).__name__, type(buffer).__name__
+        if self.ALG != 'sac':
+            raise RuntimeError(f'{name}.{what}: {cls} is built for SACSeedBatch only ({self.ALG} reuses its last feature minibatch for the critic '
+                               'step; what prioritisation means there is open): use a plain ReplayBufferGroup')
+        if what == 'iterate':
+            raise RuntimeError(f'{name}.iterate: {cls} cannot be written by a device environment (its step launch knows nothing of the priority '
+                               'trees): use a plain ReplayBufferGroup')
+        if what == 'train_injected':
+            raise RuntimeError(f'{name}.train_injected: a seed group has no eager train() form; given indices go through {cls}.draw(given=...)')
+
+    def _sample_into_per(self, buffer, B, key, g):
+        """The minibatch of every live member from its own tree: one launch draws the indices and the importance weights into the buffer
+        group's draw buffers, a second gathers the drawn rows into the members' slots (rlrep_group_per_sample issues both)."""
+        if not g or self._inject is not None:
+            raise RuntimeError(f'{type(self).__name__}: eager train() forms are not built for seed groups')
+        idx, _ = buffer.draw(B, self.PER_STREAM, core=self.core, use_counter=True, gather=True)
+        self._bufs['idx_' + key] = idx
 
     # ---- surface ----------------------------------------------------------------------------------------------------------------------
     @contextlib.contextmanager
@@ -401,6 +435,7 @@ class SeedBatchMixin(object):
         """One train() of every live member: ONE graph replay.  Returns R entries (member order): an info dict, fetched when read, or None for
         a retired member."""
         self._refuse_per(buffers, 'train')
+        self._check_per(buffers, 'train')
         if getattr(buffers, 'members', None) != self.R:
             raise ValueError(f'{type(self).__name__}.train: needs a ReplayBufferGroup of {self.R} members')
         self.steps += 1
@@ -416,6 +451,7 @@ class SeedBatchMixin(object):
         (ReplayBufferGroup.adopt_device_cursor gives it back).  Returns what train() returns, or None without `train`.  The step's exploring
         draw is the one `select_action(states, explore=True)` would make now: both count calls in the same counter."""
         self._refuse_per(buffers, 'iterate')
+        self._check_per(buffers, 'iterate')
         name = type(self).__name__
         if getattr(buffers, 'members', None) != self.R:
             raise ValueError(f'{name}.iterate: needs a ReplayBufferGroup of {self.R} members')

@@ -354,11 +354,17 @@ class HipCore:
 
     def critic_step_weighted(self, eps, w):
         """critic_step with per-sample weights w[B] in the loss (prioritized replay); leaves |TD| for rlrep_per_update"""
+        if self.members:            # a sac seed group: w[members, B], every live member in the same launches
+            check(lib.rlrep_group_critic_step_weighted(self.h, _ptr(eps), _ptr(w), _stream()), 'group_critic_step_weighted')
+            return
         check(lib.rlrep_critic_step_weighted(self.h, _ptr(eps), _ptr(w), _stream()), 'critic_step_weighted')
 
     def per_td(self, B):
         """float32[B] view of the |TD| errors the last weighted critic step left in the workspace"""
-        off = lib.rlrep_per_td_dev(self.h) - self.workspace.data_ptr()
+        if self.members:            # a seed group (member 0's view) or one of its members: the same offset in the member's workspace
+            off = lib.rlrep_group_per_td_dev(self.h) - getattr(self, '_group', self).workspace.data_ptr()
+        else:
+            off = lib.rlrep_per_td_dev(self.h) - self.workspace.data_ptr()
         return self.workspace[off:off + 4 * int(B)].view(torch.float32)
 
     def critic_backward(self, eps):

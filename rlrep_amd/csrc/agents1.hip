@@ -189,7 +189,7 @@ void build_sac(Builder& b, rlrep_agent* ag) {
     };
     critic_program(ag->critic_bwd, false, true);
     if (can_hoist) critic_program(ag->critic_bwd_h, true, false);
-    if (ag->members == 0 && ag->h.world_size <= 1) {
+    if (ag->h.world_size <= 1) {          // (one GPU; a seed group's head stage launches its group form, per_group.hip)
         critic_program(ag->critic_bwd_w, false, false, true);
         if (can_hoist) critic_program(ag->critic_bwd_wh, true, false, true);
     }

@@ -693,7 +693,7 @@ int32_t rlrep_prefetch_policy(rlrep_agent* ag, const float* eps_actor) {
 }
 // The critic step's backward half, shared by rlrep_critic_backward (w == nullptr) and rlrep_critic_step_weighted (w = per-sample weights, sac
 // only: the program pair whose head stage is the weighted kernel, per.hip): one dispatch, so the two cannot drift apart.
-static int critic_backward_dispatch(rlrep_agent* ag, const float* eps, const float* w, void* stream) {
+int critic_backward_dispatch(rlrep_agent* ag, const float* eps, const float* w, void* stream) {
     STEP_PROLOGUE(false)
     if (!eps) { rl_set_error("critic step needs eps[B,A]"); return RLREP_ERR_ARG; }
     ag->cur_eps = eps; ag->cur_w = w; ag->last_launches = 0;
@@ -751,7 +751,7 @@ int32_t rlrep_critic_step(rlrep_agent* ag, const float* eps, void* stream) {
     return rc ? rc : rlrep_critic_apply(ag, stream);
 }
 // ---- prioritized replay (per.hip) -------------------------------------------------------------------------------------
-static bool per_tree_ok(const char* what, const float* tree, int64_t P, const float* scal) {
+bool per_tree_ok(const char* what, const float* tree, int64_t P, const float* scal) {
     if (!tree || !scal || P < 1 || P > (1ll << 30) || (P & (P - 1)) != 0) { rl_set_error("%s: bad argument (null tree / scalars, or P %lld is not a power of two in [1, 2^30])", what, (long long)P); return false; }
     return true;
 }

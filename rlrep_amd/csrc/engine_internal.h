@@ -724,6 +724,12 @@ void build_diffsrsac(Builder& b, rlrep_agent* ag);
 // engine.hip
 bool check_dims(const rlrep_dims* d);
 int ensure_batch(rlrep_agent* ag, int B);
+// the critic step's backward half (w: per-sample weights of the weighted form, or null) and the tree check of the rlrep_per_* entry points:
+// shared with the group entry points of prioritized replay (group_api.hip)
+extern "C" {
+int critic_backward_dispatch(rlrep_agent* ag, const float* eps, const float* w, void* stream);
+bool per_tree_ok(const char* what, const float* tree, int64_t P, const float* scal);
+}
 // a seed group's launches for the duration of a library call: while one is alive, rl_grp_active() answers with the agent's group
 struct GrpScope {
     bool set = false, prev_on = false; RlGrp prev{};

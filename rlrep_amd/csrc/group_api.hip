@@ -334,6 +334,85 @@ int32_t rlrep_group_replay_add_cols(float* ring_dev, int64_t max_size, int32_t r
     if (rc) { rl_set_error("group_replay_add_cols: hip error %d", rc); return RLREP_ERR_HIP; }
     return 0;
 }
+// ---- prioritized replay of a sac seed group (per_group.hip) ---------------------------------------------------------------------
+// trees_dev float32[members, 2P], scal_dev float32[members, 4], idx_dev int32[members, batch], w_dev float32[members, batch]: the buffer group's
+static bool per_group_tree_ok(const char* what, const float* trees, int64_t P, const float* scal, int members) {
+    if (!per_tree_ok(what, trees, P, scal)) return false;
+    if (members < 1 || members > RLREP_GROUP_MAX_MEMBERS) { rl_set_error("%s: members %d outside [1, %d]", what, members, RLREP_GROUP_MAX_MEMBERS); return false; }
+    return true;
+}
+// the entry points that take an agent work for a sac seed group on one GPU, and refuse everything else by name
+static int per_group_ok(const char* what, const rlrep_agent* ag) {
+    if (!ag) { rl_set_error("%s: null agent", what); return RLREP_ERR_ARG; }
+    if (ag->members <= 0) { rl_set_error("%s: not a seed group (a single sac agent takes rlrep_per_* / rlrep_critic_step_weighted)", what); return RLREP_ERR_ARG; }
+    if (ag->d.alg != RLREP_ALG_SAC) { rl_set_error("%s: prioritized replay is built for sac seed groups only (a ctrlsac group reuses its last feature minibatch)", what); return RLREP_ERR_ARG; }
+    if (ag->h.world_size > 1) { rl_set_error("%s: prioritized replay runs on one GPU (world_size = %d)", what, ag->h.world_size); return RLREP_ERR_ARG; }
+    return 0;
+}
+int32_t rlrep_group_per_add(float* trees_dev, int64_t P, const float* scal_dev, int32_t members, int64_t capacity, int64_t start, int64_t n, void* stream) {
+    if (!per_group_tree_ok("group_per_add", trees_dev, P, scal_dev, members)) return RLREP_ERR_ARG;
+    if (capacity < 1 || capacity > P || start < 0 || start >= capacity || n < 1 || n > capacity) {
+        rl_set_error("group_per_add: rows [%lld, +%lld) of rings of %lld rows (trees of %lld leaves)", (long long)start, (long long)n, (long long)capacity, (long long)P); return RLREP_ERR_ARG;
+    }
+    PerAdd p; memset(&p, 0, sizeof(p));
+    p.tree = trees_dev; p.scal = scal_dev; p.P = P; p.capacity = capacity; p.start = start; p.n = n;
+    const int rc = (++g_rl_launches, rl_launch_per_add_grp(&p, members, (hipStream_t)stream));
+    if (rc) { rl_set_error("group_per_add: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_group_per_sample(rlrep_agent* ag, const float* trees_dev, int64_t P, const float* scal_dev, int32_t* idx_dev, float* w_dev, int32_t batch, int32_t given,
+                               uint64_t offset, int32_t use_counter, const float* ring_dev, int64_t ring_stride_bytes, int64_t capacity, void* stream) {
+    if (int rc = per_group_ok("group_per_sample", ag)) return rc;
+    if (!per_group_tree_ok("group_per_sample", trees_dev, P, scal_dev, ag->members)) return RLREP_ERR_ARG;
+    if (!idx_dev || !w_dev || batch < 1) { rl_set_error("group_per_sample: bad argument (null idx / w, or batch %d)", batch); return RLREP_ERR_ARG; }
+    PerSample p; memset(&p, 0, sizeof(p));
+    p.tree = trees_dev; p.scal = scal_dev; p.idx = idx_dev; p.w = w_dev; p.P = P; p.B = batch; p.given = given ? 1 : 0;
+    p.seed = 0; p.offset = offset; p.step_dev = use_counter ? ag->steps : nullptr;          // (member m: its seed, its counter)
+    SlotFill f; memset(&f, 0, sizeof(f));
+    if (ring_dev) {         // the gather of the drawn rows into every live member's slot 0: a second launch behind the sampler
+        if (capacity < 1 || capacity > P || ring_stride_bytes < 0 || (ring_stride_bytes & 3) ||
+            (ag->members > 1 && ring_stride_bytes < capacity * 4ll * (2 * ag->d.state_dim + ag->d.action_dim + 2))) {
+            rl_set_error("group_per_sample: rings of %lld rows at a stride of %lld bytes (trees of %lld leaves)", (long long)capacity, (long long)ring_stride_bytes, (long long)P);
+            return RLREP_ERR_ARG;
+        }
+        if (batch != ag->B) { rl_set_error("group_per_sample: batch %d is not the batch the step programs are built for (%d): rlrep_group_prepare first", batch, ag->B); return RLREP_ERR_ARG; }
+        Slot& s = ag->slot[0];
+        f.ring = ring_dev; f.B = ag->B; f.S = ag->d.state_dim; f.A = ag->d.action_dim;
+        f.XE = s.XE; f.XF = s.XF; f.XF2 = s.XF2; f.XFpi = s.XFpi; f.R = s.R; f.D = s.D;
+        ag->grp_ring_stride = ring_stride_bytes;
+        // a new batch: what rlrep_replay_sample invalidates
+        ag->pf_done = false; ag->pi_ready = nullptr; ag->hoist_req = nullptr;
+        s.filled = true;
+    }
+    GrpScope grp_scope_(ag);
+    int rc = (++g_rl_launches, rl_launch_per_sample_grp(&p, (hipStream_t)stream));
+    if (rc == 0 && ring_dev) rc = (++g_rl_launches, rl_launch_per_gather_grp(&f, idx_dev, capacity, (hipStream_t)stream));
+    if (rc) { rl_set_error("group_per_sample: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_group_per_update(rlrep_agent* ag, float* trees_dev, int64_t P, float* scal_dev, const int32_t* idx_dev, const float* td_dev, int32_t batch, void* stream) {
+    if (int rc = per_group_ok("group_per_update", ag)) return rc;
+    if (!per_group_tree_ok("group_per_update", trees_dev, P, scal_dev, ag->members)) return RLREP_ERR_ARG;
+    if (!idx_dev || batch < 1 || (!td_dev && batch != ag->B)) { rl_set_error("group_per_update: bad argument (null idx, or batch %d is not the batch of the last weighted critic step)", batch); return RLREP_ERR_ARG; }
+    PerUpdate p; memset(&p, 0, sizeof(p));
+    p.tree = trees_dev; p.scal = scal_dev; p.idx = idx_dev; p.td = td_dev ? td_dev : ag->per_td; p.P = P; p.B = batch;
+    if (!p.td) { rl_set_error("group_per_update: no weighted critic step has run"); return RLREP_ERR_STATE; }
+    GrpScope grp_scope_(ag);
+    // td_dev given: float32[members, batch]; otherwise every member's |TD| buffer in its workspace
+    const int rc = (++g_rl_launches, rl_launch_per_update_grp(&p, td_dev ? (long long)batch : -1ll, (hipStream_t)stream));
+    if (rc) { rl_set_error("group_per_update: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+const float* rlrep_group_per_td_dev(rlrep_agent* ag) { return (ag && ag->members > 0 && ag->d.alg == RLREP_ALG_SAC) ? ag->per_td : nullptr; }
+// rlrep_critic_step of every live member with per-sample weights w_dev[members, B]; leaves every member's |TD| in its workspace
+int32_t rlrep_group_critic_step_weighted(rlrep_agent* ag, const float* eps, const float* w_dev, void* stream) {
+    if (int rc = per_group_ok("group_critic_step_weighted", ag)) return rc;
+    if (!eps || !w_dev) { rl_set_error("group_critic_step_weighted: needs eps[B,A] (member 0's) and w[members,B]"); return RLREP_ERR_ARG; }
+    if (ag->critic_bwd_w.stages.empty()) { rl_set_error("group_critic_step_weighted: no weighted critic program was built for this group"); return RLREP_ERR_STATE; }
+    const int rc = critic_backward_dispatch(ag, eps, w_dev, stream);
+    return rc ? rc : rlrep_critic_apply(ag, stream);
+}
+
 // ---- device environments of a seed group (group_env.hip) --------------------------------------------------------------------------------------
 static_assert(EnvPendulum::KIND == RLREP_ENV_PENDULUM && EnvMountainCar::KIND == RLREP_ENV_MOUNTAIN_CAR_CONTINUOUS, "group_env.h kinds are include/rlrep.h RLREP_ENV_*");
 struct rlrep_group_env {

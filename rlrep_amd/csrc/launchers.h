@@ -79,7 +79,13 @@ int rl_launch_per_add(const PerAdd* p, hipStream_t st);
 int rl_launch_per_rebuild(float* tree, long long P, hipStream_t st);
 int rl_launch_per_sample(const PerSample* p, hipStream_t st);
 int rl_launch_per_update(const PerUpdate* p, hipStream_t st);
-int rl_launch_qhead_critic_w(const QHeadCriticW* p, hipStream_t st);
+int rl_launch_qhead_critic_w(const QHeadCriticW* p, hipStream_t st);                // its group form (per_group.hip) while a group is active
+// ---- per_group.hip (prioritized replay of a sac seed group: one workgroup per member; all but per_add need an active group) ----
+int rl_launch_per_add_grp(const PerAdd* p, int members, hipStream_t st);                                    // member m: tree + m * 2P, scal + 4 m
+int rl_launch_per_sample_grp(const PerSample* p, hipStream_t st);
+int rl_launch_per_gather_grp(const SlotFill* fill, const int* idx, long long ring_rows, hipStream_t st);      // ring row idx[m][b] of member m's ring -> its slot 0, grid (blocks, R)
+int rl_launch_per_update_grp(const PerUpdate* p, long long td_stride, hipStream_t st);                      // td_stride < 0: td moves by the member stride
+int rl_launch_qhead_critic_w_grp(const QHeadCriticW* p, hipStream_t st);
 // ---- replearn.hip ----
 int rl_replearn_init();
 int rl_launch_infonce(const InfoNce* p, hipStream_t st);

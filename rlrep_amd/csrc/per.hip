@@ -218,7 +218,7 @@ extern "C" int rl_launch_per_update(const PerUpdate* p, hipStream_t st) {
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_qhead_critic_w(const QHeadCriticW* p, hipStream_t st) {
-    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
+    if (rl_grp_active()) return rl_launch_qhead_critic_w_grp(p, st);          // (a sac seed group: per_group.hip)
     hipLaunchKernelGGL(qhead_critic_w_kernel, dim3(p->q.nblk), dim3(256), 0, st, *p);
     return (int)hipGetLastError();
 }

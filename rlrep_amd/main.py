@@ -146,7 +146,13 @@ def run(argv=None):
                         '--max_timesteps, written at every evaluation.  Runs with the plain loop, --host-envs and --torch-envs')
     p.add_argument('--per-alpha', default=0.6, type=float, help='priority exponent alpha (0 = uniform replay; default 0.6)')
     p.add_argument('--per-beta', default=0.4, type=float, help='initial importance-sampling exponent beta (default 0.4)')
+    p.add_argument('--group-per', action='store_true',
+                   help='prioritized experience replay for a seed group (--alg sac with --seeds and / or --sweep): every member samples from a sum '
+                        'tree of its own, one launch per step for all members; --per-alpha / --per-beta as for --per, beta annealed for all '
+                        'members; --sweep per_alpha=0.4,0.6 gives the members different exponents.  Goes with --pbt-interval and '
+                        '--halving-interval; not with --device-env or --per')
     args = p.parse_args(argv)
+    _check_group_per(args)
     _check_per(args)
     _check_num_envs(args)
     _check_host_envs(args)
@@ -251,9 +257,30 @@ def _check_per(args):
         raise SystemExit(f'--per: --per-alpha {args.per_alpha} must be >= 0 and --per-beta {args.per_beta} in [0, 1]')
 
 
-def _per_anneal(args, replay, t):
-    """--per: beta rises linearly from --per-beta to 1.0 at --max_timesteps; written (one device word) at the evaluation boundaries"""
+def _check_group_per(args):
+    """--group-per: SystemExit, before anything touches the GPU, on what prioritized replay of a seed group does not run with (a namespace
+    without the field is a run without it)"""
+    if not getattr(args, 'group_per', False):
+        return
     if getattr(args, 'per', False):
+        raise SystemExit('--group-per: it is the seed-group form of prioritized replay and does not go with --per (the single-agent form); give one of them')
+    if args.alg != 'sac':
+        raise SystemExit(f'--group-per: prioritized replay of a seed group is built for --alg sac (got --alg {args.alg}: the representation agents '
+                         'reuse their last feature minibatch for the critic step)')
+    if args.seeds is None and not args.sweep:
+        raise SystemExit('--group-per: prioritized replay of a seed group needs a seed group: give --seeds and / or --sweep (one agent takes --per)')
+    for flag, given in (('--device-env', args.device_env), ('--device-loop', getattr(args, 'device_loop', False))):
+        if given:
+            raise SystemExit(f'--group-per: a device environment writes ring rows inside its step launch, which knows nothing of the priority '
+                             f'trees; it does not go with {flag}')
+    if not 0.0 <= float(args.per_alpha) or not 0.0 <= float(args.per_beta) <= 1.0:
+        raise SystemExit(f'--group-per: --per-alpha {args.per_alpha} must be >= 0 and --per-beta {args.per_beta} in [0, 1]')
+
+
+def _per_anneal(args, replay, t):
+    """--per / --group-per: beta rises linearly from --per-beta to 1.0 at --max_timesteps; written (one device word per member) at the evaluation
+    boundaries"""
+    if getattr(args, 'per', False) or getattr(args, 'group_per', False):
         frac = min(1.0, float(t) / float(args.max_timesteps))
         replay.beta = 1.0 if frac >= 1.0 else float(args.per_beta) + (1.0 - float(args.per_beta)) * frac
 
@@ -522,9 +549,10 @@ def _group_class(alg):
     return SACSeedBatch
 
 
-def parse_sweeps(sweeps, alg, n_seeds):
+def parse_sweeps(sweeps, alg, n_seeds, group_per=False):
     """--sweep arguments -> [(tag, {key: value})] in product order (one ('', {}) without a sweep).  SystemExit on an unknown key, a key --alg
-    does not take, a bad or repeated value, or more members than a group holds."""
+    does not take, a bad or repeated value, or more members than a group holds.  per_alpha (the priority exponent of a member's replay tree)
+    is a key under --group-per only; run_seeds hands it to the buffer group, not to the agent."""
     import itertools
     if not sweeps:
         return [('', {})]
@@ -538,6 +566,21 @@ def parse_sweeps(sweeps, alg, n_seeds):
         key = key.strip()
         if not eq or not vals.strip():
             raise SystemExit(f'--sweep {arg}: give KEY=V1,V2,..., e.g. --sweep lr=1e-4,3e-4')
+        if key == 'per_alpha':
+            if not group_per:
+                raise SystemExit(f'--sweep {arg}: per_alpha is the priority exponent of a seed group\'s replay trees: it needs --group-per')
+            try:
+                values = [float(v) for v in vals.split(',')]
+                if any(not (0.0 <= v < float('inf')) for v in values):
+                    raise ValueError
+            except ValueError:
+                raise SystemExit(f'--sweep {arg}: per_alpha takes finite numbers >= 0')
+            if len(set(values)) != len(values):
+                raise SystemExit(f'--sweep {arg}: repeated value')
+            if key in [k for k, _ in axes]:
+                raise SystemExit(f'--sweep {arg}: {key} is swept twice')
+            axes.append((key, values))
+            continue
         if key not in known:
             raise SystemExit(f'--sweep {arg}: unknown key {key!r} (sweepable: {", ".join(known)})')
         if key not in cls.SWEEP_KEYS:
@@ -722,16 +765,19 @@ def run_seeds(args):
         raise SystemExit(f'--seeds {args.seeds}: give distinct integer seeds, e.g. --seeds 0,1,2,3')
     if args.alg not in ('sac', 'ctrlsac'):
         raise SystemExit(f'--seeds: seed batches are built for --alg sac and ctrlsac only (got --alg {args.alg}); run one process per seed instead')
-    configs = parse_sweeps(args.sweep, args.alg, len(seeds))
+    group_per = bool(getattr(args, 'group_per', False))
+    configs = parse_sweeps(args.sweep, args.alg, len(seeds), group_per=group_per)
     swept = bool(args.sweep)
     tags = [t for t, _ in configs for _ in seeds]
-    member_hyper = [cfg for _, cfg in configs for _ in seeds] if swept else None
+    # per_alpha belongs to the members' replay trees, not to the agent: taken out of the members' hyper-parameters
+    per_alphas = [float(cfg.get('per_alpha', getattr(args, 'per_alpha', 0.6))) for _, cfg in configs for _ in seeds]
+    member_hyper = [{k: v for k, v in cfg.items() if k != 'per_alpha'} for _, cfg in configs for _ in seeds] if swept else None
     seeds = [s for _ in configs for s in seeds]              # member = (configuration, seed), configurations outermost
     pbt_cfg = parse_pbt(args, args.alg, len(seeds))
     halving_cfg = parse_halving(args, len(seeds), pbt_cfg)
     if args.device_env and not str(args.env).startswith(('Pendulum', 'MountainCarContinuous')):
         raise SystemExit(f'--device-env: only Pendulum-v1 and MountainCarContinuous-v0 are built on the device (got --env {args.env}); run without --device-env')
-    from rlrep_amd.utils.buffer_group import ReplayBufferGroup
+    from rlrep_amd.utils.buffer_group import ReplayBufferGroup, PrioritizedReplayBufferGroup
     R = len(seeds)
     envs_, evals_ = [envs.make(args.env) for _ in seeds], [envs.make(args.env) for _ in seeds]
     for s, e, ev in zip(seeds, envs_, evals_):
@@ -750,8 +796,14 @@ def run_seeds(args):
     common = dict(discount=args.discount, tau=args.tau, hidden_dim=args.hidden_dim, max_batch=args.batch_size)
     if args.alg == 'ctrlsac':
         common.update(feature_dim=2048, hidden_dim=1024, extra_feature_steps=args.extra_feature_steps)          # as build_agent (main.py:90-91)
+    if group_per and any('per_alpha' in cfg for _, cfg in configs):
+        common['distinct_members'] = False          # (members that differ in per_alpha alone share a seed and the agent's hyper-parameters)
     agent = _group_class(args.alg)(seeds, state_dim, action_dim, space, member_hyper=member_hyper, **common)
-    replay = ReplayBufferGroup(R, state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)))
+    if group_per:
+        replay = PrioritizedReplayBufferGroup(R, state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)), alpha=per_alphas, beta=args.per_beta)
+    else:
+        replay = ReplayBufferGroup(R, state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)))
+    agent.replay = replay                           # (what the members train from: for callers of run())
     ev = _GroupEvaluations(args, agent, seeds, logs, pbt_cfg, halving_cfg)
     if args.device_env:
         return _device_loop(args, agent, replay, ev)
@@ -798,6 +850,7 @@ def run_seeds(args):
         if t >= args.start_timesteps:
             infos = agent.train(replay, batch_size=args.batch_size)
         if (t + 1) % args.eval_freq == 0:
+            _per_anneal(args, replay, t + 1)
             sps = timer.steps_per_sec(t + 1)
             scores = [util.eval_policy(policies[r], evals_[r], args.eval_episodes) if live[r] else None for r in range(R)]
             ev.step(t + 1, sps, scores, infos)
@@ -859,6 +912,7 @@ def _host_envs_group_loop(args, agent, replay, ev, seeds):
             infos = agent.train(replay, batch_size=args.batch_size)
         t = t0 + E
         if t % args.eval_freq == 0:
+            _per_anneal(args, replay, t)
             sps = timer.steps_per_sec(t)
             ev.step(t, sps, evaluate(), infos)
     ev.close()

@@ -222,3 +222,232 @@ class ReplayBufferGroup(object):
         self.rings[int(r), :n].copy_(torch.from_numpy(rows))
         self.sizes[int(r)] = n
         self.ptr, self._staged = n % self.max_size, 0
+
+
+# ---- prioritized replay for sac seed groups: DESIGN.md 6g, csrc/per_group.hip ----------------------------------------------------------
+def _per_member(x, R, name):
+    """a per-member hyper-parameter: a scalar broadcasts, a sequence must have one entry per member"""
+    a = np.asarray(x, np.float64).reshape(-1)
+    if a.size == 1:
+        a = np.repeat(a, R)
+    if a.size != R:
+        raise ValueError(f'PrioritizedReplayBufferGroup: {name} has {a.size} entries for {R} members (a scalar, or one value per member)')
+    return a.astype(np.float32)
+
+
+class PrioritizedReplayBufferGroup(ReplayBufferGroup):
+    """ReplayBufferGroup whose members each carry priorities in a sum tree of their own: `trees` float32[R, 2P] (P = the smallest power of
+    two >= max_size; member r's tree laid out as PrioritizedReplayBuffer's), the scalars float32[R, 4] = {max_p, alpha, beta, eps} per member.
+    A row written by add() / add_batch() (at flush()), add_device() or load() gets ITS member's running maximum priority; SACSeedBatch.train()
+    samples every live member in proportion to its leaves, weights its critic loss and writes (|TD| + eps)^alpha back -- one launch per step
+    for all members, inside the captured train().  Member r is bit for bit what SACAgent(seed=s_r) does with a PrioritizedReplayBuffer(alpha_r,
+    beta_r, eps_r) fed the same rows.  `alpha`, `beta`, `eps`: a scalar or one value per member (a sweep over the exponents).  For
+    SACSeedBatch.train(); everything else refuses the class by name.  On device='cpu' the same arithmetic runs in NumPy float32."""
+    prioritized_group = True          # (NOT `prioritized`: that is the single ring's class, which seed groups and other agents refuse)
+
+    def __init__(self, members, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, alpha=0.6, beta=0.4, eps=1e-6):
+        super().__init__(members, state_dim, action_dim, max_size=max_size, device=device, stage_rows=stage_rows)
+        R = self.members
+        self.P = 1 << max(0, self.max_size - 1).bit_length()
+        self.trees = torch.zeros(R, 2 * self.P, dtype=torch.float32, device=self.device)
+        self._hyper = np.stack([_per_member(alpha, R, 'alpha'), _per_member(beta, R, 'beta'), _per_member(eps, R, 'eps')], axis=1)     # [R, 3] float32
+        scal = np.concatenate([np.ones((R, 1), np.float32), self._hyper], axis=1)
+        self._scal = torch.from_numpy(scal).to(self.device)           # [R, 4]: max_p, alpha, beta, eps
+        self._draw_bufs = {}
+        self.device_epoch = 0
+
+    # ---- hyper-parameters and views --------------------------------------------------------------
+    @property
+    def alpha(self):
+        return [float(v) for v in self._hyper[:, 0]]
+
+    @property
+    def eps(self):
+        return [float(v) for v in self._hyper[:, 2]]
+
+    @property
+    def beta(self):
+        return [float(v) for v in self._hyper[:, 1]]
+
+    @beta.setter
+    def beta(self, x):
+        b = _per_member(x, self.members, 'beta')
+        self._hyper[:, 1] = b
+        self._before_device_write()
+        if len(set(b.tolist())) == 1:
+            self._scal[:, 2].fill_(float(b[0]))          # (a fill launch on the caller's stream: no synchronisation)
+        else:
+            self._scal[:, 2].copy_(torch.from_numpy(b))
+        self.device_epoch += 1
+
+    def max_priority(self, r):
+        return float(self._scal[int(r), 0].cpu())
+
+    def priorities(self, r):
+        """float32[sizes[r]]: the leaves of the rows member r's ring holds (flushes staged rows; synchronises)"""
+        self.flush()
+        return self.trees[int(r), self.P:self.P + self.sizes[int(r)]].cpu().numpy()
+
+    def tree(self, r):
+        """member r's whole tree, float32[2P] (a view)"""
+        return self.trees[int(r)]
+
+    def per_key(self):
+        """what a captured train() bakes in besides the rings: the trees and the scalar block"""
+        return ('per_group', self.trees.data_ptr(), self._scal.data_ptr())
+
+    # ---- writers: every written row gets its member's running maximum priority ---------------------
+    def _lib(self):
+        import ctypes as C
+        from rlrep_amd._lib import lib, check
+        return C, lib, check
+
+    def _per_add(self, start, n):
+        if n <= 0:
+            return
+        if self.device.type == 'cuda':
+            C, lib, check = self._lib()
+            with torch.cuda.device(self.device):
+                check(lib.rlrep_group_per_add(C.c_void_p(self.trees.data_ptr()), self.P, C.c_void_p(self._scal.data_ptr()), self.members, self.max_size,
+                                              int(start), int(n), C.c_void_p(_raw_stream())), 'group_per_add')
+        else:
+            from rlrep_amd.utils.buffer import _per_set
+            rows = (int(start) + np.arange(int(n))) % self.max_size
+            for r in range(self.members):
+                _per_set(self.trees[r].numpy(), self.P, rows, self._scal.numpy()[r, 0])
+        self.device_epoch += 1
+
+    def _rebuild(self, r):
+        if self.device.type == 'cuda':
+            C, lib, check = self._lib()
+            with torch.cuda.device(self.device):
+                check(lib.rlrep_per_rebuild(C.c_void_p(self.trees[r].data_ptr()), self.P, C.c_void_p(_raw_stream())), 'per_rebuild')
+        else:
+            t = self.trees[r].numpy()
+            w = self.P >> 1
+            while w >= 1:
+                nd = np.arange(w, 2 * w)
+                t[nd] = t[2 * nd] + t[2 * nd + 1]
+                w >>= 1
+
+    def flush(self):
+        a, n = self._stage_start, self._staged
+        super().flush()
+        self._per_add(a, n)
+
+    def add_device(self, states, actions, next_states, rewards, dones):
+        self.flush()                                 # (staged host rows first, with their leaves: the order of transitions is the call order)
+        start = self.ptr
+        super().add_device(states, actions, next_states, rewards, dones)
+        self._per_add(start, int(rewards.shape[1]))
+
+    def load(self, r, state, action, next_state, reward, done):
+        """Member r only: its tree is zeroed first (rows the ring no longer holds lose their leaves; max_p stays), rows 0 .. n-1 get its max_p."""
+        super().load(r, state, action, next_state, reward, done)
+        r, n = int(r), self.sizes[int(r)]
+        self.trees[r].zero_()
+        if n > 0 and self.device.type == 'cuda':           # (the single ring's add on member r's slices: it takes no agent)
+            C, lib, check = self._lib()
+            with torch.cuda.device(self.device):
+                check(lib.rlrep_per_add(C.c_void_p(self.trees[r].data_ptr()), self.P, C.c_void_p(self._scal[r].data_ptr()), self.max_size, 0, n,
+                                        C.c_void_p(_raw_stream())), 'per_add')
+        elif n > 0:
+            from rlrep_amd.utils.buffer import _per_set
+            _per_set(self.trees[r].numpy(), self.P, np.arange(n), self._scal.numpy()[r, 0])
+        self.device_epoch += 1
+
+    def collect_on_device(self, env):
+        raise RuntimeError('PrioritizedReplayBufferGroup.collect_on_device: a device environment writes ring rows inside its step launch, which '
+                           'knows nothing of the priority trees (iterate() takes a plain ReplayBufferGroup)')
+
+    def set_priorities(self, r, leaves, max_priority=None):
+        """Overwrite the leaves of member r's rows 0 .. len(leaves) - 1 (every other leaf of its tree becomes 0) and rebuild the tree;
+        max_priority, if given, replaces the member's running maximum."""
+        r = int(r)
+        leaves = np.asarray(leaves, np.float32).reshape(-1)
+        n = len(leaves)
+        self.flush()
+        if n > self.sizes[r]:
+            raise ValueError(f'PrioritizedReplayBufferGroup.set_priorities: {n} leaves for a ring that holds {self.sizes[r]} rows')
+        self._before_device_write()
+        self.trees[r].zero_()
+        if max_priority is not None:
+            self._scal[r, 0:1].copy_(torch.from_numpy(np.asarray([max_priority], np.float32)))
+        self.trees[r, self.P:self.P + n].copy_(torch.from_numpy(leaves))
+        self._rebuild(r)
+        self.device_epoch += 1
+
+    # ---- the sampler and the priority update (SACSeedBatch calls these inside train()) -------------
+    def draw_buffers(self, B):
+        """(idx int32[R, B], w float32[R, B]) on the rings' device, one pair per batch size for the life of the buffer group"""
+        bufs = self._draw_bufs.get(int(B))
+        if bufs is None:
+            bufs = self._draw_bufs[int(B)] = (torch.zeros(self.members, int(B), dtype=torch.int32, device=self.device),
+                                              torch.ones(self.members, int(B), dtype=torch.float32, device=self.device))
+        return bufs
+
+    def draw(self, B, offset, core=None, use_counter=False, given=None, gather=False, seeds=None, live=None):
+        """B stratified draws per live member in proportion to its priorities, and their importance weights -> (idx, w) = draw_buffers(B).
+        Member r's draws are Philox stream elements 0 .. B-1 of (its seed, offset [+ its device train() counter]); `given` (int32[R, B]): take
+        these indices, compute only the weights.  On the device ONE launch for all members (`core`: the sac seed group's HipCore; its seeds);
+        `gather`: a second launch copies the drawn rows into every live member's minibatch slot.  On the CPU `seeds` are the members' seeds and
+        `live` the members to draw for (default: all)."""
+        B = int(B)
+        idx, w = self.draw_buffers(B)
+        if min(self.sizes) == 0:
+            raise RuntimeError('PrioritizedReplayBufferGroup.draw: a member\'s buffer is empty')
+        if given is not None:
+            g = np.asarray(given.cpu() if torch.is_tensor(given) else given).reshape(self.members, -1)
+            if g.shape[1] != B or g.min() < 0 or any(g[r].max() >= self.sizes[r] for r in range(self.members)):
+                raise ValueError(f'PrioritizedReplayBufferGroup.draw: given indices must be [{self.members}, {B}] rows inside each member\'s ring')
+            idx.copy_(torch.from_numpy(g.astype(np.int32)))
+        if self.device.type == 'cuda':
+            C, lib, check = self._lib()
+            if core is None:
+                raise ValueError('PrioritizedReplayBufferGroup.draw: the device sampler runs for a sac seed group (core=group.core)')
+            check(lib.rlrep_group_per_sample(core.h, C.c_void_p(self.trees.data_ptr()), self.P, C.c_void_p(self._scal.data_ptr()), C.c_void_p(idx.data_ptr()),
+                                             C.c_void_p(w.data_ptr()), B, 0 if given is None else 1, int(offset), 1 if use_counter else 0,
+                                             C.c_void_p(self.rings.data_ptr() if gather else None), 4 * self.ring_stride, self.max_size,
+                                             C.c_void_p(_raw_stream())), 'group_per_sample')
+            return idx, w
+        from rlrep_amd.utils.buffer import _per_draw
+        from rlrep_amd.utils.philox_host import raw_stream as words
+        for r in (range(self.members) if live is None else live):
+            t = self.trees[r].numpy()
+            if given is None:
+                idx[r].copy_(torch.from_numpy(_per_draw(t, self.P, B, words(B, int(seeds[r]), int(offset)))))
+            p = t[self.P + idx[r].numpy().astype(np.int64)]
+            pmin, beta = p.min(), np.float32(self._hyper[r, 1])
+            with np.errstate(divide='ignore', invalid='ignore'):
+                wv = np.power((pmin / p).astype(np.float32), beta, dtype=np.float32)
+            w[r].copy_(torch.from_numpy(np.where((p == pmin) | (beta == 0), np.float32(1.0), wv).astype(np.float32)))
+        return idx, w
+
+    def update(self, B, td=None, core=None, live=None):
+        """Every live member: leaf idx[r, j] <- (td[r, j] + eps_r)^alpha_r for the last draw of B (1 when alpha_r == 0; the maximum where an
+        index repeats), its max_priority follows, the ancestors are recomputed.  On the device ONE launch; td=None: the |TD| errors the
+        group's last weighted critic step left, else float32[R, B]."""
+        B = int(B)
+        idx, _ = self.draw_buffers(B)
+        if self.device.type == 'cuda':
+            C, lib, check = self._lib()
+            if core is None:
+                raise ValueError('PrioritizedReplayBufferGroup.update: the device update runs for a sac seed group (core=group.core)')
+            if td is not None and (tuple(td.shape) != (self.members, B) or td.dtype != torch.float32 or not td.is_contiguous() or td.device != self.trees.device):
+                raise ValueError(f'PrioritizedReplayBufferGroup.update: td must be a contiguous float32 tensor [{self.members}, {B}] on {self.trees.device}')
+            check(lib.rlrep_group_per_update(core.h, C.c_void_p(self.trees.data_ptr()), self.P, C.c_void_p(self._scal.data_ptr()), C.c_void_p(idx.data_ptr()),
+                                             C.c_void_p(None if td is None else td.data_ptr()), B, C.c_void_p(_raw_stream())), 'group_per_update')
+            return
+        from rlrep_amd.utils.buffer import _per_set, PER_MIN_PRIORITY
+        td = np.asarray(td, np.float32).reshape(self.members, B)
+        s = self._scal.numpy()
+        for r in (range(self.members) if live is None else live):
+            t = self.trees[r].numpy()
+            alpha = np.float32(self._hyper[r, 0])
+            new = np.ones(B, np.float32) if alpha == 0 else np.power(td[r] + np.float32(self._hyper[r, 2]), alpha, dtype=np.float32)
+            new = np.where(new > PER_MIN_PRIORITY, new, PER_MIN_PRIORITY).astype(np.float32)
+            rows = idx[r].numpy().astype(np.int64)
+            t[self.P + rows] = 0
+            np.maximum.at(t, self.P + rows, new)
+            s[r, 0] = max(s[r, 0], new.max())
+            _per_set(t, self.P, rows, t[self.P + rows])
