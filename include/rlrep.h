@@ -407,6 +407,37 @@ int32_t rlrep_group_per_update(rlrep_agent* group, float* trees_dev, int64_t P, 
 int32_t rlrep_group_critic_step_weighted(rlrep_agent* group, const float* eps_dev, const float* w_dev, void* stream);
 const float* rlrep_group_per_td_dev(rlrep_agent* group);
 
+/* ---- n-step returns for sac (additive to ABI 4; DESIGN.md 6h, csrc/nstep.hip) ---------------------------------------------------------------
+ * A replay gather that follows each sampled row's trajectory forward through the ring, ONE launch, stream-ordered and capturable.  For base row
+ * i0 = idx_dev[b] of a ring of max_size rows [s | a | s' | r | d] with fill level *size_dev and successor distance `stride` (the number of
+ * interleaved environments that wrote the ring):  g = 1, R = r[i0], last = i0;  for k = 1 .. n - 1 with j = (last + stride) mod max_size the
+ * chain continues iff d[last] == 0, j < *size_dev and the S words of s[j] equal those of s'[last] bit for bit; then g = g * gamma,
+ * R = R + g * r[j], last = j.  The output row is (s, a) of i0, s' of `last`, reward R and done 1 - g (1 - d[last]), every operation one
+ * correctly rounded fp32 operation: the critic heads' y = R + (1 - D) gamma tv then is the n-step target, and n = 1 is rlrep_replay_sample.
+ *   rlrep_replay_sample_nstep   the gather into minibatch slot 0 of ONE sac agent, gamma = its discount.  Never skipped: it overwrites the
+ *                               gather a preceding rlrep_train_prologue ran.  Refuses, by name: a seed group's handle, an agent that is not
+ *                               sac, world_size > 1, n outside [1, RLREP_NSTEP_MAX], stride < 1.
+ *   rlrep_replay_gather_nstep   the same rows into caller-owned arrays, no agent: xe [batch, 2 S + A] = [s, a, s'], xf [batch, S + A] = [s, a],
+ *                               xf2 [batch, S + A] (columns [0, S) = s'; the rest untouched), xfpi [batch, S + A] (columns [0, S) = s), r, d [batch].
+ *   rlrep_group_replay_gather_nstep   the gather into slot 0 of every live member of a sac SEED GROUP, one launch on grid (x, members): member m's
+ *                               ring (rings_dev + m * ring_stride_bytes), fill level size_dev[m] and discount -- read from its hyper record on the
+ *                               device, so rlrep_group_set_member_hyper holds at the next replay.  idx_per_member == 0: idx_dev lies in member 0's
+ *                               block (the index pool rlrep_group_train_prologue wrote) and moves by the member stride; otherwise idx_dev is
+ *                               int32[members, batch] (the draw buffers of rlrep_group_per_sample, called with a NULL ring).  batch must be the
+ *                               prepared batch.  Refuses, by name: a single agent's handle ("not a seed group"), a ctrlsac group, world_size > 1. */
+#define RLREP_NSTEP_MAX 16
+int32_t rlrep_replay_sample_nstep(rlrep_agent* agent, int32_t slot, const float* ring_dev, const int32_t* idx_dev, int32_t batch, int64_t max_size,
+                                  const int32_t* size_dev, int32_t n, int32_t stride, void* stream);
+int32_t rlrep_replay_gather_nstep(const float* ring_dev, const int32_t* idx_dev, int32_t batch, int32_t S, int32_t A, int64_t max_size, const int32_t* size_dev,
+                                  int32_t n, int32_t stride, float gamma, float* xe_dev, float* xf_dev, float* xf2_dev, float* xfpi_dev, float* r_dev, float* d_dev,
+                                  void* stream);
+/* Read-back of a minibatch slot (tests and tools): which = 0 .. 5 -> XE [batch, 2 S + A], XF [batch, S + A], XF2 [batch, S + A], XFpi [batch, S + A],
+ * R [batch], D [batch], dense, inside the agent's workspace; valid once the stream has passed the gather.  A group: member 0's (member m's lies
+ * m member strides further).  NULL for a bad argument. */
+const float* rlrep_slot_dev(rlrep_agent* agent, int32_t slot, int32_t which);
+int32_t rlrep_group_replay_gather_nstep(rlrep_agent* group, const float* rings_dev, int64_t ring_stride_bytes, const int32_t* idx_dev, int32_t idx_per_member,
+                                        int32_t batch, int64_t max_size, const int32_t* size_dev, int32_t n, int32_t stride, void* stream);
+
 /* ---- metrics ------------------------------------------------------------------------------ */
 /* device float array of n_metrics slots, valid after the stream has passed the producing step */
 const float* rlrep_metrics_dev(rlrep_agent* agent);

@@ -465,6 +465,7 @@ class SACAgent(object):
     def _check_per(self, buffer, what):
         """A prioritized buffer trains ONE sac agent on ONE GPU; everything else refuses it by its class name, before anything is launched."""
         name, cls = type(self).__name__, type(buffer).__name__
+        self._check_nstep(buffer, what)
         if getattr(buffer, 'prioritized_group', False):
             raise RuntimeError(f'{name}.{what}: {cls} is built for SACSeedBatch.train (a sac seed group); a single agent takes a '
                                'PrioritizedReplayBuffer')
@@ -479,6 +480,33 @@ class SACAgent(object):
             raise RuntimeError(f'{name}.iterate: {cls} cannot be written by a device environment (its step launch knows nothing of the priority '
                                'tree): use a plain ReplayBuffer')
 
+    # ---- n-step returns (utils/buffer.py ReplayBuffer(n_step=, n_stride=); DESIGN.md 6h, csrc/nstep.hip) ------------------------------------
+    @staticmethod
+    def _nstep(buffer):
+        return int(getattr(buffer, 'n_step', 1))
+
+    def _check_nstep(self, buffer, what):
+        """An n-step buffer trains a sac agent (or a sac seed group) on ONE GPU; everything else refuses it by its class name and n_step, before
+        anything is launched."""
+        n = self._nstep(buffer)
+        if n <= 1:
+            return
+        name, cls = type(self).__name__, type(buffer).__name__
+        if self.ALG != 'sac':
+            raise RuntimeError(f'{name}.{what}: {cls}(n_step={n}) is built for SACAgent and SACSeedBatch only (the feature step of the representation agents models '
+                               'one-step dynamics and their critic reuses its minibatch): use n_step=1')
+        if self.world_size > 1 or self._dp:
+            raise RuntimeError(f'{name}.{what}: {cls}(n_step={n}) does not train a data-parallel agent (one agent, one GPU)')
+
+    def _gather(self, buffer, slot, idx, B):
+        """The gather of rows idx[0:B] into minibatch slot `slot`: the plain copy, or for an n-step buffer the chain-following gather (one
+        launch that is never skipped: it overwrites the rows the train prologue gathered; this agent's discount)."""
+        n = self._nstep(buffer)
+        if n > 1:
+            self.core.sample_nstep(buffer.ring, idx, B, buffer.max_size, buffer.size_dev(), n, buffer.n_stride)
+        else:
+            self.core.sample(slot, buffer.ring, idx, B)
+
     def _sample_into_per(self, buffer, B, key, g):
         """The minibatch of a prioritized buffer: the sample launch (indices + importance weights into the buffer's draw buffers), then the
         gather.  Injected indices take the sampler's given-indices mode: only the weights are computed."""
@@ -492,7 +520,7 @@ class SACAgent(object):
                 self._ctr += 1
             idx, _ = buffer.draw(B, self._seed, self.PER_STREAM + self._ctr, core=c)
         self._bufs['idx_' + key] = idx
-        c.sample(0, buffer.ring, idx, B)
+        self._gather(buffer, 0, idx, B)
 
     def _form(self):
         """The form the next train() takes: 'graph' (one hipGraph), 'two_chains' (the feature chain and the deferred critic / actor chain on
@@ -858,7 +886,7 @@ class SACAgent(object):
         if self._per(buffer):
             return self._sample_into_per(buffer, B, key, g)
         if self._inject is None and self._pool is not None and ('idx_' + key) in self._pool:
-            self.core.sample(slot, buffer.ring, self._pool['idx_' + key], B)
+            self._gather(buffer, slot, self._pool['idx_' + key], B)
             nxt = self._next_key.get(key)
             if nxt is not None:
                 armed = self.core.prefetch_batch(buffer.ring, self._pool['idx_' + nxt], B, slot)
@@ -878,7 +906,7 @@ class SACAgent(object):
             self.core.fill_indices_dev(idx, buffer.size_dev(), self._seed, self._graph_off(key))
         else:
             idx = self._indices(key, B, buffer.size)
-        self.core.sample(slot, buffer.ring, idx, B)
+        self._gather(buffer, slot, idx, B)
 
     def _early_key_for(self, key):
         """The key of the minibatch whose feature step will carry both policy forwards (rlrep_prefetch_policy_early), as far as it is
@@ -1334,7 +1362,10 @@ class SACAgent(object):
         a new ReplayBuffer after the old one is collected)."""
         key = (buffer.ring.data_ptr(), buffer.size_dev().data_ptr(), int(buffer.ring.shape[0]), B)
         per = getattr(buffer, 'per_key', None)               # (a prioritized buffer: its tree and scalar block are baked in as well)
-        return key if per is None else key + per()
+        key = key if per is None else key + per()
+        if int(getattr(buffer, 'n_step', 1)) > 1:           # (an n-step buffer: the chain length and the successor distance are kernel arguments)
+            key = key + buffer.nstep_key()
+        return key
 
     def _hook_buffer(self, buffer):
         hooks = getattr(buffer, 'before_device_write_hooks', None)

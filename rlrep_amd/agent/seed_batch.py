@@ -384,11 +384,27 @@ class SeedBatchMixin(object):
             return
         return super()._sample_into(buffer, B, key, slot, g)
 
+    def _gather(self, buffer, slot, idx, B):
+        """An n-step buffer group: the chain-following gather of every live member, behind the prologue's own (which it overwrites), on the
+        members' index pools; member r's discount is its hyper record's.  A plain group: the prologue's gather (the call is recognised)."""
+        n = self._nstep(buffer)
+        if n <= 1:
+            return super()._gather(buffer, slot, idx, B)
+        self._gather_nstep(buffer, idx, B, per_member=False)
+
+    def _gather_nstep(self, buffer, idx, B, per_member):
+        check(lib.rlrep_group_replay_gather_nstep(self.core.h, C.c_void_p(buffer.rings.data_ptr()), 4 * buffer.ring_stride, C.c_void_p(idx.data_ptr()),
+                                                  1 if per_member else 0, int(B), buffer.max_size, C.c_void_p(buffer.size_dev().data_ptr()),
+                                                  self._nstep(buffer), buffer.n_stride, _stream()), 'group_replay_gather_nstep')
+
     @staticmethod
     def _graph_cache_key(buffer, B):
         key = (buffer.rings.data_ptr(), buffer.size_dev().data_ptr(), int(buffer.max_size), buffer.members, B)
         per = getattr(buffer, 'per_key', None)               # (a prioritized buffer group: its trees and scalar block are baked in as well)
-        return key if per is None else key + per()
+        key = key if per is None else key + per()
+        if int(getattr(buffer, 'n_step', 1)) > 1:
+            key = key + buffer.nstep_key()
+        return key
 
     # ---- prioritized replay (utils/buffer_group.py PrioritizedReplayBufferGroup; DESIGN.md 6g) ---------------------------------------------
     @staticmethod
@@ -401,6 +417,7 @@ class SeedBatchMixin(object):
         if not self._per(buffer):
             return super()._check_per(buffer, what)
         name, cls = type(self).__name__, type(buffer).__name__
+        self._check_nstep(buffer, what)
         if self.ALG != 'sac':
             raise RuntimeError(f'{name}.{what}: {cls} is built for SACSeedBatch only ({self.ALG} reuses its last feature minibatch for the critic '
                                'step; what prioritisation means there is open): use a plain ReplayBufferGroup')
@@ -415,8 +432,11 @@ class SeedBatchMixin(object):
         group's draw buffers, a second gathers the drawn rows into the members' slots (rlrep_group_per_sample issues both)."""
         if not g or self._inject is not None:
             raise RuntimeError(f'{type(self).__name__}: eager train() forms are not built for seed groups')
-        idx, _ = buffer.draw(B, self.PER_STREAM, core=self.core, use_counter=True, gather=True)
+        nstep = self._nstep(buffer) > 1          # (the n-step gather replaces the sampler's plain one: the launch count stays)
+        idx, _ = buffer.draw(B, self.PER_STREAM, core=self.core, use_counter=True, gather=not nstep)
         self._bufs['idx_' + key] = idx
+        if nstep:
+            self._gather_nstep(buffer, idx, B, per_member=True)
 
     # ---- surface ----------------------------------------------------------------------------------------------------------------------
     @contextlib.contextmanager

@@ -284,6 +284,11 @@ class HipCore:
     def sample(self, slot, ring, idx, batch):
         check(lib.rlrep_replay_sample(self.h, slot, _ptr(ring), _ptr(idx), int(batch), _stream()), 'replay_sample')
 
+    def sample_nstep(self, ring, idx, batch, max_size, size_dev, n, stride):
+        """The n-step gather into slot 0 (csrc/nstep.hip): never skipped, discount = this agent's."""
+        check(lib.rlrep_replay_sample_nstep(self.h, 0, _ptr(ring), _ptr(idx), int(batch), int(max_size), _ptr(size_dev), int(n), int(stride), _stream()),
+              'replay_sample_nstep')
+
     def prefetch_batch(self, ring, idx, batch, slot=0):
         """Arm the gather of the next minibatch of `slot` to ride in the next optimizer launch."""
         rc = lib.rlrep_prefetch_batch_slot(self.h, int(slot), _ptr(ring), _ptr(idx), int(batch))

@@ -580,6 +580,60 @@ int32_t rlrep_replay_sample(rlrep_agent* ag, int32_t slot, const float* ring_dev
     return 0;
 }
 
+// ---- n-step returns (nstep.hip) ------------------------------------------------------------------------------------------------
+static int nstep_args_ok(const char* what, const float* ring, const int32_t* idx, int32_t batch, int64_t max_size, const int32_t* size_dev, int32_t n, int32_t stride) {
+    if (!ring || !idx || !size_dev || batch < 1) { rl_set_error("%s: bad argument (null ring / idx / size_dev, or batch %d)", what, batch); return RLREP_ERR_ARG; }
+    if (max_size < 1 || max_size > 0x7fffffffll) { rl_set_error("%s: a ring of %lld rows (int32 indices address [1, 2^31) rows)", what, (long long)max_size); return RLREP_ERR_ARG; }
+    if (n < 1 || n > RLREP_NSTEP_MAX) { rl_set_error("%s: n %d outside [1, %d]", what, n, RLREP_NSTEP_MAX); return RLREP_ERR_ARG; }
+    if (stride < 1) { rl_set_error("%s: stride %d (the number of interleaved environments) must be >= 1", what, stride); return RLREP_ERR_ARG; }
+    return 0;
+}
+// rlrep_replay_sample(slot 0) with n-step rows: never skipped (the gather the train prologue ran is overwritten), discount = the agent's
+int32_t rlrep_replay_sample_nstep(rlrep_agent* ag, int32_t slot, const float* ring_dev, const int32_t* idx_dev, int32_t batch, int64_t max_size,
+                                  const int32_t* size_dev, int32_t n, int32_t stride, void* stream) {
+    if (!ag) { rl_set_error("replay_sample_nstep: null agent"); return RLREP_ERR_ARG; }
+    if (ag->members > 0) { rl_set_error("replay_sample_nstep: not available on a seed group (rlrep_group_create): n-step replay is built for one sac agent"); return RLREP_ERR_ARG; }
+    if (ag->d.alg != RLREP_ALG_SAC) { rl_set_error("replay_sample_nstep: n-step replay is built for sac only (the representation agents' feature step models one-step dynamics)"); return RLREP_ERR_ARG; }
+    if (ag->h.world_size > 1) { rl_set_error("replay_sample_nstep: n-step replay runs on one GPU (world_size = %d)", ag->h.world_size); return RLREP_ERR_ARG; }
+    if (slot != 0) { rl_set_error("replay_sample_nstep: slot %d (sac has slot 0 only)", slot); return RLREP_ERR_ARG; }
+    if (int rc = nstep_args_ok("replay_sample_nstep", ring_dev, idx_dev, batch, max_size, size_dev, n, stride)) return rc;
+    // a new batch: what rlrep_replay_sample invalidates
+    ag->pf_done = false; ag->l1_done = false; ag->chain_next = false;
+    ag->pi_ready = nullptr; ag->hoist_req = nullptr;
+    ag->early_crit = ag->early_act = ag->early_ready_crit = ag->early_ready_act = nullptr;
+    int rc = ensure_batch(ag, batch);
+    if (rc) return rc;
+    NStepGather p; memset(&p, 0, sizeof(p));
+    slot_fill_params(ag, 0, ring_dev, idx_dev, p.fill);
+    p.size_dev = size_dev; p.capacity = max_size; p.n = n; p.stride = stride; p.gamma = ag->h.discount;
+    ag->slot[0].filled = true;
+    rc = (++g_rl_launches, rl_launch_nstep_gather(&p, (hipStream_t)stream));
+    if (rc) { rl_set_error("replay_sample_nstep: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+// the same gather into caller-owned arrays, no agent: xe [batch, 2 S + A] = [s, a, s'], r [batch], d [batch] (ReplayBuffer.gather_nstep)
+int32_t rlrep_replay_gather_nstep(const float* ring_dev, const int32_t* idx_dev, int32_t batch, int32_t S, int32_t A, int64_t max_size, const int32_t* size_dev,
+                                  int32_t n, int32_t stride, float gamma, float* xe_dev, float* xf_dev, float* xf2_dev, float* xfpi_dev, float* r_dev, float* d_dev,
+                                  void* stream) {
+    if (int rc = nstep_args_ok("replay_gather_nstep", ring_dev, idx_dev, batch, max_size, size_dev, n, stride)) return rc;
+    if (S < 1 || A < 1 || !xe_dev || !xf_dev || !xf2_dev || !xfpi_dev || !r_dev || !d_dev) { rl_set_error("replay_gather_nstep: bad argument (S %d, A %d, or a null output)", S, A); return RLREP_ERR_ARG; }
+    NStepGather p; memset(&p, 0, sizeof(p));
+    p.fill.ring = ring_dev; p.fill.idx = idx_dev; p.fill.B = batch; p.fill.S = S; p.fill.A = A;
+    p.fill.XE = xe_dev; p.fill.XF = xf_dev; p.fill.XF2 = xf2_dev; p.fill.XFpi = xfpi_dev; p.fill.R = r_dev; p.fill.D = d_dev;
+    p.size_dev = size_dev; p.capacity = max_size; p.n = n; p.stride = stride; p.gamma = gamma;
+    const int rc = (++g_rl_launches, rl_launch_nstep_gather(&p, (hipStream_t)stream));
+    if (rc) { rl_set_error("replay_gather_nstep: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+
+// the six arrays of minibatch slot `slot` (which = 0 .. 5: XE, XF, XF2, XFpi, R, D), for read-back by tests and tools; a group: member 0's
+const float* rlrep_slot_dev(rlrep_agent* ag, int32_t slot, int32_t which) {
+    if (!ag || slot < 0 || slot > 1 || which < 0 || which > 5) return nullptr;
+    const Slot& s = ag->slot[slot];
+    const float* const arr[6] = {s.XE, s.XF, s.XF2, s.XFpi, s.R, s.D};
+    return arr[which];
+}
+
 static int philox(float* df, int32_t* di, int64_t n, int kind, float std, int hi, const int* hi_dev, uint64_t seed, uint64_t off,
                   const int* step_dev, void* stream) {
     if (n <= 0) return 0;

@@ -413,6 +413,42 @@ int32_t rlrep_group_critic_step_weighted(rlrep_agent* ag, const float* eps, cons
     return rc ? rc : rlrep_critic_apply(ag, stream);
 }
 
+// ---- n-step returns of a sac seed group (nstep.hip) ------------------------------------------------------------------------------
+// The chain-following gather of every live member into its slot 0, one launch on grid (x, members): member m's ring, fill level size_dev[m]
+// and discount (its hyper record, read on the device).  idx_per_member == 0: idx_dev lies in member 0's block (the index pool the group train
+// prologue wrote) and moves by the member stride; otherwise idx_dev is int32[members, batch] (a prioritized buffer group's draw buffers).
+int32_t rlrep_group_replay_gather_nstep(rlrep_agent* ag, const float* rings_dev, int64_t ring_stride_bytes, const int32_t* idx_dev, int32_t idx_per_member,
+                                        int32_t batch, int64_t max_size, const int32_t* size_dev, int32_t n, int32_t stride, void* stream) {
+    const char* what = "group_replay_gather_nstep";
+    if (!ag) { rl_set_error("%s: null agent", what); return RLREP_ERR_ARG; }
+    if (ag->members <= 0) { rl_set_error("%s: not a seed group (a single sac agent takes rlrep_replay_sample_nstep)", what); return RLREP_ERR_ARG; }
+    if (ag->d.alg != RLREP_ALG_SAC) { rl_set_error("%s: n-step replay is built for sac seed groups only (a ctrlsac group's feature step models one-step dynamics)", what); return RLREP_ERR_ARG; }
+    if (ag->h.world_size > 1) { rl_set_error("%s: n-step replay runs on one GPU (world_size = %d)", what, ag->h.world_size); return RLREP_ERR_ARG; }
+    if (!rings_dev || !idx_dev || !size_dev || batch < 1) { rl_set_error("%s: bad argument (null rings / idx / size_dev, or batch %d)", what, batch); return RLREP_ERR_ARG; }
+    if (max_size < 1 || max_size > 0x7fffffffll || ring_stride_bytes < 0 || (ring_stride_bytes & 3) ||
+        (ag->members > 1 && ring_stride_bytes < max_size * 4ll * (2 * ag->d.state_dim + ag->d.action_dim + 2))) {
+        rl_set_error("%s: rings of %lld rows at a stride of %lld bytes", what, (long long)max_size, (long long)ring_stride_bytes); return RLREP_ERR_ARG;
+    }
+    if (n < 1 || n > RLREP_NSTEP_MAX) { rl_set_error("%s: n %d outside [1, %d]", what, n, RLREP_NSTEP_MAX); return RLREP_ERR_ARG; }
+    if (stride < 1) { rl_set_error("%s: stride %d (the number of interleaved environments) must be >= 1", what, stride); return RLREP_ERR_ARG; }
+    if (!idx_per_member && !in_member0(ag, idx_dev, 4ll * batch)) { rl_set_error("%s: indices that move by the member stride must lie inside member 0's block", what); return RLREP_ERR_ARG; }
+    if (batch != ag->B) { rl_set_error("%s: batch %d is not the batch the step programs are built for (%d): rlrep_group_prepare first", what, batch, ag->B); return RLREP_ERR_ARG; }
+    Slot& s = ag->slot[0];
+    NStepGather p; memset(&p, 0, sizeof(p));
+    p.fill.ring = rings_dev; p.fill.idx = idx_dev; p.fill.B = ag->B; p.fill.S = ag->d.state_dim; p.fill.A = ag->d.action_dim;
+    p.fill.XE = s.XE; p.fill.XF = s.XF; p.fill.XF2 = s.XF2; p.fill.XFpi = s.XFpi; p.fill.R = s.R; p.fill.D = s.D;
+    p.size_dev = size_dev; p.capacity = max_size; p.n = n; p.stride = stride; p.gamma = ag->h.discount;      // (the kernel takes every member's own)
+    ag->grp_ring_stride = ring_stride_bytes;
+    // a new batch: what rlrep_replay_sample invalidates
+    ag->pf_done = false; ag->l1_done = false; ag->chain_next = false; ag->pi_ready = nullptr; ag->hoist_req = nullptr;
+    ag->early_crit = ag->early_act = ag->early_ready_crit = ag->early_ready_act = nullptr;
+    s.filled = true;
+    GrpScope grp_scope_(ag);
+    const int rc = (++g_rl_launches, rl_launch_nstep_gather_grp(&p, idx_per_member ? batch : 0, (hipStream_t)stream));
+    if (rc) { rl_set_error("%s: hip error %d", what, rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+
 // ---- device environments of a seed group (group_env.hip) --------------------------------------------------------------------------------------
 static_assert(EnvPendulum::KIND == RLREP_ENV_PENDULUM && EnvMountainCar::KIND == RLREP_ENV_MOUNTAIN_CAR_CONTINUOUS, "group_env.h kinds are include/rlrep.h RLREP_ENV_*");
 struct rlrep_group_env {

@@ -118,6 +118,9 @@ struct PerSample {
     unsigned long long seed, offset; const int* step_dev;                                       // Philox stream: offset + *step_dev (null: offset)
 };
 struct PerUpdate { float* tree; float* scal; const int* idx; const float* td; long long P; int B; };
+// n-step returns (nstep.hip): the gather that follows each sampled row's trajectory forward through the ring.  fill: the ring,
+// idx[B] and the slot buffers as fill_slot_kernel takes them; row i's successor candidate is row (i + stride) mod capacity
+struct NStepGather { SlotFill fill; const int* size_dev; long long capacity; int n, stride; float gamma; };
 
 struct QHeadActor {
     const float* Ec[2]; const float* wc[2]; const float* bc[2];

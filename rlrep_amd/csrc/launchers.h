@@ -86,6 +86,9 @@ int rl_launch_per_sample_grp(const PerSample* p, hipStream_t st);
 int rl_launch_per_gather_grp(const SlotFill* fill, const int* idx, long long ring_rows, hipStream_t st);      // ring row idx[m][b] of member m's ring -> its slot 0, grid (blocks, R)
 int rl_launch_per_update_grp(const PerUpdate* p, long long td_stride, hipStream_t st);                      // td_stride < 0: td moves by the member stride
 int rl_launch_qhead_critic_w_grp(const QHeadCriticW* p, hipStream_t st);
+// ---- nstep.hip (n-step returns: the chain-following replay gather, one wave per sample) ----
+int rl_launch_nstep_gather(const NStepGather* p, hipStream_t st);
+int rl_launch_nstep_gather_grp(const NStepGather* p, int idx_rows, hipStream_t st);       // grid (x, R); idx_rows == 0: the indices move by the member stride, else int32[R, idx_rows]
 // ---- replearn.hip ----
 int rl_replearn_init();
 int rl_launch_infonce(const InfoNce* p, hipStream_t st);

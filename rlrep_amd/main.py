@@ -151,7 +151,16 @@ def run(argv=None):
                         'tree of its own, one launch per step for all members; --per-alpha / --per-beta as for --per, beta annealed for all '
                         'members; --sweep per_alpha=0.4,0.6 gives the members different exponents.  Goes with --pbt-interval and '
                         '--halving-interval; not with --device-env or --per')
+    p.add_argument('--n-step', default=1, type=int,
+                   help='n-step returns (--alg sac; 1..16, default 1 = one-step targets): train() gathers, on the device, rows that follow each sampled '
+                        'transition up to N steps forward through the replay ring and bootstraps with discount^m.  Goes with --per, --seeds / '
+                        '--sweep (discount= included), --group-per, --pbt-interval / --halving-interval, --host-envs, --torch-envs, --device-loop and '
+                        '--device-env --num-envs')
+    p.add_argument('--n-stride', default=None, type=int,
+                   help='the distance between a ring row and its successor (with --n-step): the number of environments whose transitions interleave '
+                        'in the ring.  Default: what the chosen loop writes (--host-envs E: E, --torch-envs N: N, --num-envs E: E, else 1)')
     args = p.parse_args(argv)
+    _check_nstep(args)
     _check_group_per(args)
     _check_per(args)
     _check_num_envs(args)
@@ -186,9 +195,10 @@ def run(argv=None):
     state_dim, action_dim = env.observation_space.shape[0], env.action_space.shape[0]
     agent = build_agent(args, state_dim, action_dim, env.action_space)
     if getattr(args, 'per', False):
-        replay = buffer.PrioritizedReplayBuffer(state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)), alpha=args.per_alpha, beta=args.per_beta)
+        replay = buffer.PrioritizedReplayBuffer(state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)), alpha=args.per_alpha, beta=args.per_beta,
+                                                **_nstep_kw(args))
     else:
-        replay = buffer.ReplayBuffer(state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)))
+        replay = buffer.ReplayBuffer(state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)), **_nstep_kw(args))
     if args.device_loop:
         return _single_device_loop(args, agent, replay, log_path, jsonl, tb)
     if args.host_envs > 1:
@@ -238,6 +248,42 @@ def run(argv=None):
         tb.close()
     print('Total time cost {:.4g}s.'.format(timer.time_cost()))
     return agent, evaluations
+
+
+def _nstep_stride(args):
+    """the successor distance of the ring the chosen loop writes: --n-stride, or the number of environments the loop interleaves"""
+    if getattr(args, 'n_stride', None) is not None:
+        return int(args.n_stride)
+    for v in (getattr(args, 'host_envs', 1), getattr(args, 'torch_envs', 0), getattr(args, 'num_envs', 1)):
+        if int(v or 0) > 1:
+            return int(v)
+    return 1
+
+
+def _nstep_kw(args):
+    """the n-step keywords of the replay buffer classes (nothing without --n-step: the buffers are built as before)"""
+    n = int(getattr(args, 'n_step', 1))
+    return dict(n_step=n, n_stride=_nstep_stride(args)) if n > 1 else {}
+
+
+def _check_nstep(args):
+    """--n-step / --n-stride: SystemExit, before anything touches the GPU, on what n-step returns do not run with (an argument namespace without
+    the attributes -- the tests build those by hand -- has none)."""
+    n, stride = int(getattr(args, 'n_step', 1)), getattr(args, 'n_stride', None)
+    if not 1 <= n <= 16:
+        raise SystemExit(f'--n-step {n}: n-step returns take 1..16 steps')
+    if stride is not None and int(stride) < 1:
+        raise SystemExit(f'--n-stride {stride}: the distance between a ring row and its successor must be >= 1')
+    if n == 1:
+        if stride is not None:
+            raise SystemExit('--n-stride: it is the successor distance of n-step returns: give --n-step N (N > 1) with it')
+        return
+    if args.alg != 'sac':
+        raise SystemExit(f'--n-step {n}: n-step returns are built for --alg sac (got --alg {args.alg}: the feature step of the representation agents '
+                         'models one-step dynamics and their critic reuses its minibatch)')
+    E = int(getattr(args, 'num_envs', 1))
+    if (getattr(args, 'device_loop', False) or getattr(args, 'device_env', False)) and _nstep_stride(args) != E:
+        raise SystemExit(f'--n-stride {_nstep_stride(args)}: a device environment interleaves --num-envs {E} trajectories in the ring; the stride must be {E}')
 
 
 def _check_per(args):
@@ -800,9 +846,10 @@ def run_seeds(args):
         common['distinct_members'] = False          # (members that differ in per_alpha alone share a seed and the agent's hyper-parameters)
     agent = _group_class(args.alg)(seeds, state_dim, action_dim, space, member_hyper=member_hyper, **common)
     if group_per:
-        replay = PrioritizedReplayBufferGroup(R, state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)), alpha=per_alphas, beta=args.per_beta)
+        replay = PrioritizedReplayBufferGroup(R, state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)), alpha=per_alphas, beta=args.per_beta,
+                                              **_nstep_kw(args))
     else:
-        replay = ReplayBufferGroup(R, state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)))
+        replay = ReplayBufferGroup(R, state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)), **_nstep_kw(args))
     agent.replay = replay                           # (what the members train from: for callers of run())
     ev = _GroupEvaluations(args, agent, seeds, logs, pbt_cfg, halving_cfg)
     if args.device_env:

@@ -15,11 +15,82 @@ from rlrep_amd.utils.streams import raw_stream as _raw_stream, current_stream as
 Batch = collections.namedtuple('Batch', ['state', 'action', 'reward', 'next_state', 'done'])
 
 
+NSTEP_MAX = 16       # include/rlrep.h RLREP_NSTEP_MAX
+
+
+def _check_nstep(cls, n_step, n_stride, shard):
+    if isinstance(n_step, bool) or isinstance(n_stride, bool) or int(n_step) != n_step or int(n_stride) != n_stride:
+        raise ValueError(f'{cls}: n_step {n_step!r} and n_stride {n_stride!r} must be integers')
+    n_step, n_stride = int(n_step), int(n_stride)
+    if not 1 <= n_step <= NSTEP_MAX:
+        raise ValueError(f'{cls}: n_step {n_step} outside [1, {NSTEP_MAX}]')
+    if n_stride < 1:
+        raise ValueError(f'{cls}: n_stride {n_stride} must be >= 1 (the number of interleaved environments that write the ring)')
+    if n_step > 1 and shard is not None:
+        raise ValueError(f'{cls}: shard= is not supported with n_step {n_step} > 1 (a shard keeps one transition in `world`: its rows are no trajectory)')
+    return n_step, n_stride
+
+
+def nstep_rows(ring, ind, size, n_step, n_stride, gamma, S, A):
+    """The n-step rows of base rows `ind` in NumPy float32, operation for operation what csrc/nstep.hip computes: ring float32
+    [max_size, 2S + A + 2], size = the fill level -> (rows float32 [B, 2S + A] = [s, a, s' of the chain's last row], R [B], D [B])."""
+    ring = np.ascontiguousarray(ring, np.float32)
+    bits = ring.view(np.uint32)
+    cap, SA, gamma = ring.shape[0], S + A, np.float32(gamma)
+    ind = np.asarray(ind, np.int64).reshape(-1)
+    rows = np.empty((len(ind), SA + S), np.float32)
+    Rs, Ds = np.empty(len(ind), np.float32), np.empty(len(ind), np.float32)
+    one = np.float32(1.0)
+    for b, i0 in enumerate(ind):
+        last, g, R = int(i0), one, ring[i0, SA + S]
+        for _ in range(1, int(n_step)):
+            j = (last + int(n_stride)) % cap
+            if not (ring[last, SA + S + 1] == 0 and j < size and np.array_equal(bits[j, :S], bits[last, SA:SA + S])):
+                break
+            g = np.float32(g * gamma)
+            R = np.float32(R + np.float32(g * ring[j, SA + S]))
+            last = j
+        rows[b, :SA] = ring[i0, :SA]
+        rows[b, SA:] = ring[last, SA:SA + S]
+        Rs[b] = R
+        Ds[b] = np.float32(one - np.float32(g * np.float32(one - ring[last, SA + S + 1])))
+    return rows, Rs, Ds
+
+
+def nstep_batch(buf, ring, size_dev, size, ind, gamma):
+    """The n-step Batch of base rows `ind` of `ring` ([max_size, row], buf's or one member's of a buffer group) for discount `gamma`: on the
+    device ONE launch (rlrep_replay_gather_nstep) against the fill level word `size_dev`; on the CPU nstep_rows() against `size`.  The six
+    arrays the launch wrote stay in buf._nstep_last (XE, XF, XF2, XFpi, R, D: what a minibatch slot holds)."""
+    S, A = buf.state_dim, buf.action_dim
+    if buf.device.type == 'cuda':
+        import ctypes as C
+        from rlrep_amd._lib import lib, check
+        idx = torch.as_tensor(ind).to(buf.device, torch.int32).reshape(-1).contiguous()
+        B = int(idx.numel())
+        xe = torch.empty(B, 2 * S + A, dtype=torch.float32, device=buf.device)
+        xf, xf2, xfpi = (torch.zeros(B, S + A, dtype=torch.float32, device=buf.device) for _ in range(3))
+        r, d = (torch.empty(B, 1, dtype=torch.float32, device=buf.device) for _ in range(2))
+        with torch.cuda.device(buf.device):
+            check(lib.rlrep_replay_gather_nstep(C.c_void_p(ring.data_ptr()), C.c_void_p(idx.data_ptr()), B, S, A, buf.max_size,
+                                                C.c_void_p(size_dev.data_ptr()), buf.n_step, buf.n_stride, float(gamma), C.c_void_p(xe.data_ptr()),
+                                                C.c_void_p(xf.data_ptr()), C.c_void_p(xf2.data_ptr()), C.c_void_p(xfpi.data_ptr()),
+                                                C.c_void_p(r.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(_raw_stream())), 'replay_gather_nstep')
+        buf._nstep_last = dict(XE=xe, XF=xf, XF2=xf2, XFpi=xfpi, R=r, D=d)
+    else:
+        rows, R, D = nstep_rows(ring.numpy(), np.asarray(torch.as_tensor(ind)), size, buf.n_step, buf.n_stride, gamma, S, A)
+        xe, r, d = torch.from_numpy(rows), torch.from_numpy(R).reshape(-1, 1), torch.from_numpy(D).reshape(-1, 1)
+    return Batch(state=xe[:, :S].contiguous(), action=xe[:, S:S + A].contiguous(), reward=r, next_state=xe[:, S + A:].contiguous(), done=d)
+
+
 class ReplayBuffer(object):
-    def __init__(self, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, shard=None):
+    def __init__(self, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, shard=None, n_step=1, n_stride=1):
         """shard=(rank, world): this ring is one shard of a replay partitioned by transition index: every rank is
         offered the same stream of transitions and keeps transition i iff i % world == rank, at slot i // world of its own ring (the
-        default, shard=None, keeps everything: each data-parallel rank then owns the transitions of its own environment)."""
+        default, shard=None, keeps everything: each data-parallel rank then owns the transitions of its own environment).
+        n_step > 1: SACAgent.train() learns from n-step rows (gather_nstep).  n_stride is the number of interleaved
+        environments that write the ring -- row i's successor candidate is row (i + n_stride) mod max_size: 1 for add(), E for add_batch()
+        of E rows, N for add_device() of N rows, num_envs for a device environment."""
+        self.n_step, self.n_stride = _check_nstep(type(self).__name__, n_step, n_stride, shard)
         self.max_size = int(max_size)
         self.shard = None if shard is None else (int(shard[0]), int(shard[1]))
         self._offered = 0
@@ -217,6 +288,9 @@ class ReplayBuffer(object):
         if self.shard is not None:
             raise ValueError('ReplayBuffer.collect_on_device: a sharded ring (shard=) keeps one transition in `world`; a device environment '
                              'writes every row it steps')
+        if self.n_step > 1 and int(getattr(env, 'num_envs', 1)) != self.n_stride:
+            raise ValueError(f'{type(self).__name__}.collect_on_device: n_step {self.n_step} with n_stride {self.n_stride}, but the device environment '
+                             f'interleaves num_envs = {int(getattr(env, "num_envs", 1))} trajectories in the ring: build the buffer with n_stride = num_envs')
         self.flush()
         self.size_dev()
         if getattr(env, 'num_envs', 1) > 1:          # (environment e's cursor is (ptr + e) mod max_size)
@@ -297,6 +371,20 @@ class ReplayBuffer(object):
                      next_state=rows[:, S + A:2 * S + A].contiguous(),
                      done=rows[:, 2 * S + A + 1:2 * S + A + 2].contiguous())
 
+    def nstep_key(self):
+        """what a captured train() bakes in besides the ring when it gathers n-step rows"""
+        return ('nstep', self.n_step, self.n_stride)
+
+    def gather_nstep(self, ind, gamma):
+        """The n-step batch of base rows `ind` for discount `gamma`: state / action of row ind[b], next_state of the last row of
+        its chain, reward R = sum_k gamma^k r_k over the chain and done D = 1 - gamma^(m-1) (1 - d_last), so that r + (1 - done) gamma V(s') is
+        the m-step target.  On the device ONE launch (csrc/nstep.hip) against the device fill level; on device='cpu' the same arithmetic in
+        NumPy float32.  n_step == 1 returns gather(ind)'s rows."""
+        self.flush()
+        self._order_reads()
+        size_dev = self.size_dev() if self.device.type == 'cuda' else None
+        return nstep_batch(self, self.ring, size_dev, self.size, ind, gamma)
+
     # public array attributes of the reference, materialised on demand (read-only copies)
     def _col(self, a, b):
         self.flush()
@@ -368,10 +456,11 @@ class PrioritizedReplayBuffer(ReplayBuffer):
     other agent refuses the class by name.  On device='cpu' the same arithmetic runs in NumPy float32 (draw() / update())."""
     prioritized = True
 
-    def __init__(self, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, shard=None, alpha=0.6, beta=0.4, eps=1e-6):
+    def __init__(self, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, shard=None, alpha=0.6, beta=0.4, eps=1e-6,
+                 n_step=1, n_stride=1):
         if shard is not None:
             raise ValueError('PrioritizedReplayBuffer: shard= is not supported (a shard sees one transition in `world`; priorities are per ring)')
-        super().__init__(state_dim, action_dim, max_size=max_size, device=device, stage_rows=stage_rows)
+        super().__init__(state_dim, action_dim, max_size=max_size, device=device, stage_rows=stage_rows, n_step=n_step, n_stride=n_stride)
         self.P = 1 << max(0, self.max_size - 1).bit_length()
         self.tree = torch.zeros(2 * self.P, dtype=torch.float32, device=self.device)
         self._scal = torch.tensor([1.0, alpha, beta, eps], dtype=torch.float32, device=self.device)      # max_p, alpha, beta, eps

@@ -12,10 +12,14 @@ from rlrep_amd.utils.streams import raw_stream as _raw_stream
 
 
 class ReplayBufferGroup(object):
-    def __init__(self, members, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096):
+    def __init__(self, members, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, n_step=1, n_stride=1):
+        """n_step > 1: SACSeedBatch.train() learns from n-step rows, every member with its own discount (gather_nstep); n_stride is
+        the number of interleaved environments per member that write the rings (ReplayBuffer)."""
+        from rlrep_amd.utils.buffer import _check_nstep
         self.members = int(members)
         if self.members < 1:
             raise ValueError('ReplayBufferGroup: members must be >= 1')
+        self.n_step, self.n_stride = _check_nstep(type(self).__name__, n_step, n_stride, None)
         self.max_size = int(max_size)
         self.state_dim, self.action_dim = int(state_dim), int(action_dim)
         self.row = 2 * self.state_dim + self.action_dim + 2
@@ -56,6 +60,18 @@ class ReplayBufferGroup(object):
     def _before_device_write(self):
         for h in self.before_device_write_hooks:
             h()
+
+    def nstep_key(self):
+        """what a captured train() bakes in besides the rings when it gathers n-step rows"""
+        return ('nstep', self.n_step, self.n_stride)
+
+    def gather_nstep(self, r, ind, gamma):
+        """Member r's n-step batch of base rows `ind` for discount `gamma`: ReplayBuffer.gather_nstep on its ring and fill level."""
+        from rlrep_amd.utils.buffer import nstep_batch
+        r = int(r)
+        self.flush()
+        size_dev = self.size_dev()[r:r + 1] if self.device.type == 'cuda' else None
+        return nstep_batch(self, self.rings[r], size_dev, self.sizes[r], ind, gamma)
 
     # ---- filling ------------------------------------------------------------------------------
     def add(self, state, action, next_state, reward, done):
@@ -186,6 +202,9 @@ class ReplayBufferGroup(object):
             return
         if self._device_env is not None:
             raise RuntimeError('ReplayBufferGroup.collect_on_device: another device environment owns the cursor (adopt_device_cursor() first)')
+        if self.n_step > 1 and int(getattr(env, 'num_envs', 1)) != self.n_stride:
+            raise ValueError(f'{type(self).__name__}.collect_on_device: n_step {self.n_step} with n_stride {self.n_stride}, but the device environment '
+                             f'interleaves num_envs = {int(getattr(env, "num_envs", 1))} trajectories per ring: build the buffers with n_stride = num_envs')
         self.flush()
         self.size_dev()
         if getattr(env, 'num_envs', 1) > 1:          # (environment e's cursor is (ptr + e) mod max_size)
@@ -245,8 +264,9 @@ class PrioritizedReplayBufferGroup(ReplayBufferGroup):
     SACSeedBatch.train(); everything else refuses the class by name.  On device='cpu' the same arithmetic runs in NumPy float32."""
     prioritized_group = True          # (NOT `prioritized`: that is the single ring's class, which seed groups and other agents refuse)
 
-    def __init__(self, members, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, alpha=0.6, beta=0.4, eps=1e-6):
-        super().__init__(members, state_dim, action_dim, max_size=max_size, device=device, stage_rows=stage_rows)
+    def __init__(self, members, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, alpha=0.6, beta=0.4, eps=1e-6,
+                 n_step=1, n_stride=1):
+        super().__init__(members, state_dim, action_dim, max_size=max_size, device=device, stage_rows=stage_rows, n_step=n_step, n_stride=n_stride)
         R = self.members
         self.P = 1 << max(0, self.max_size - 1).bit_length()
         self.trees = torch.zeros(R, 2 * self.P, dtype=torch.float32, device=self.device)
