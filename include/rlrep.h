@@ -363,6 +363,33 @@ int32_t rlrep_replay_add_cols(float* ring_dev, int64_t max_size, int32_t row_flo
                               const float* a, int64_t ld_a, const float* s2, int64_t ld_s2, const float* r, const float* d, int64_t n, int32_t* size_dev,
                               int32_t new_size, void* stream);
 
+/* ---- the simulator loop as one graph replay (additive to ABI 4) --------------------------------------------------------------
+ * rlrep_act_device and rlrep_replay_add_cols take the call counter, `start` and `new_size` by value, so a captured graph would repeat one
+ * iteration.  The two forms below read them from a loop record instead: ctl_dev, int64[RLREP_LOOP_CTL_WORDS] in caller-owned device memory
+ * (word 0 calls: the select_action call counter; 1 t_global: environment steps; 2 iter: loop iterations; 3 next_ptr, 4 start, 5 size: the ring
+ * cursor; 6 warm: the iteration in flight is a warm-up one; 7 unused).  The caller writes words 0-3 and 5 before the first iteration; one
+ * iteration is the act form, the simulator's step, the append form, in that order on one stream.  In either launch no thread writes a word that
+ * a workgroup of the same launch reads: the act form reads calls / t_global / iter and one of its threads sets start = next_ptr, next_ptr =
+ * (next_ptr + rows) mod max_size, size = min(size + rows, max_size), warm = (t_global < start_timesteps); the append form reads start / size /
+ * warm and one of its threads publishes size to size_dev and sets iter += 1, t_global += n, and calls += n unless warm.  Each is ONE launch,
+ * stream-ordered and capturable: no copy, no allocation, no synchronisation.
+ *
+ * rlrep_act_device_ctl: row e's network output is bit for bit rlrep_act_device(explore = 1, offset = (calls + 1) << 20).  Behind it the
+ * exploration mix: row e takes min(max(lo + (hi - lo) * u_j, lo), hi) in every component j (each operation rounded to fp32 on its own) if
+ * t_global < start_timesteps, or if its pick is below eps_greedy.  The draws are Philox4x32-10 blocks keyed by `seed` with counter
+ * {iter lo, iter hi, e, 0xE2000000 + q}: the pick is word 0 of block q = 0, u_j word (1 + j) mod 4 of block (1 + j) / 4, each word w taken
+ * as ((w >> 8) + 0.5) / 2^24.  Refused with RLREP_ERR_ARG before the launch ("act_device_ctl:"): a null argument, rows outside
+ * [1, RLREP_ACT_MAX_ROWS] or above max_size, a row stride below the row width, a seed group's handle, eps_greedy outside [0, 1], dimensions
+ * whose activation tiles exceed the LDS of one workgroup.
+ * rlrep_replay_add_cols_ctl: rlrep_replay_add_cols with start and the fill level from the record.  Refused by name ("replay_add_cols_ctl:")
+ * before the launch: a null ring, array or record, n outside [1, max_size], row_floats != 2 S + A + 2, a row stride below its width. */
+#define RLREP_LOOP_CTL_WORDS 8
+int32_t rlrep_act_device_ctl(rlrep_agent* agent, const float* obs_dev, int64_t ld_obs, int32_t rows, uint64_t seed, float lo, float hi, float* action_dev,
+                             int64_t ld_act, int64_t* ctl_dev, int64_t max_size, float eps_greedy, int64_t start_timesteps, void* stream);
+int32_t rlrep_replay_add_cols_ctl(float* ring_dev, int64_t max_size, int32_t row_floats, int32_t S, int32_t A, const float* s, int64_t ld_s, const float* a,
+                                  int64_t ld_a, const float* s2, int64_t ld_s2, const float* r, const float* d, int64_t n, int32_t* size_dev, int64_t* ctl_dev,
+                                  void* stream);
+
 /* ---- prioritized replay for sac (additive to ABI 4; DESIGN.md 6f, csrc/per.hip) ------------------------------------------------------
  * The priorities live beside the ring in a caller-owned sum tree: tree_dev float32[2 P], P = the smallest power of two >= the ring's rows,
  * node n = tree[2n] + tree[2n + 1] (one fp32 add), row i's leaf = tree[P + i], leaves of unwritten rows 0 (the caller zeroes the tree once).

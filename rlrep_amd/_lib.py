@@ -164,6 +164,8 @@ def _load():
         'rlrep_group_act_device': (i32, [vp, vp, i32, i32, u64, f32, f32, vp, vp]),
         'rlrep_replay_add_cols': (i32, [vp, i64, i32, i64, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i32, vp]),
         'rlrep_group_replay_add_cols': (i32, [vp, i64, i32, i64, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, i64, i32, i64, vp, i32, vp]),
+        'rlrep_act_device_ctl': (i32, [vp, vp, i64, i32, u64, f32, f32, vp, i64, vp, i64, f32, i64, vp]),
+        'rlrep_replay_add_cols_ctl': (i32, [vp, i64, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp]),
         'rlrep_per_add': (i32, [vp, i64, vp, i64, i64, i64, vp]),
         'rlrep_per_rebuild': (i32, [vp, i64, vp]),
         'rlrep_per_sample': (i32, [vp, vp, i64, vp, vp, vp, i32, i32, u64, u64, vp, vp]),

@@ -677,6 +677,82 @@ class SACAgent(object):
         self.steps += 1
         return self._history_info() if self._hist else self.core.info()
 
+    # ---- torch simulators on the device (rlrep_amd/envs/sim_loop.py SimLoop): the whole iteration as one graph replay ----------------------
+    def iterate_sim(self, loop, buffer, batch_size, train=True):
+        """One iteration of the loop around a torch simulator on the device -- act on its N observations and mix in the exploring uniform
+        actions (rlrep_act_device_ctl), `sim.step_(actions)`, append the N transitions (rlrep_replay_add_cols_ctl) -- and, with `train`, one
+        train() on the ring as it then stands: ONE graph replay, no host round trip.  `loop` is a SimLoop of this agent (its module docstring
+        states what the simulator must keep to), `buffer` a ReplayBuffer whose cursor the device owns from here on
+        (ReplayBuffer.adopt_device_cursor gives it back).  Returns what train() returns, or None without `train`.  Row e's exploring draw is
+        the one `act_device(obs, explore=True)` would make now: both count calls in the same counter, and warm-up iterations leave it alone.
+        Captured on ONE stream as a single chain; always the one-graph form of train(), as in iterate(): a pipelined train() still in flight
+        is finished first.  An n-step buffer (sac) needs n_stride = N.  Not for a data-parallel agent, graph=False, seed groups or
+        prioritized buffers (the captured append does not write the priority tree)."""
+        name, cls = type(self).__name__, type(buffer).__name__
+        if self._per(buffer) or getattr(buffer, 'prioritized_group', False):
+            raise RuntimeError(f'{name}.iterate_sim: {cls} cannot be written by the captured simulator loop (its append launch does not write the '
+                               'priority tree): use a plain ReplayBuffer, or the eager act_device / add_device / train() loop')
+        self._check_nstep(buffer, 'iterate_sim')
+        if self.world_size > 1 or self._dp:
+            raise RuntimeError(f'{name}.iterate_sim: a data-parallel agent has no captured simulator loop')
+        if not self.use_graph:
+            raise RuntimeError(f'{name}.iterate_sim: needs the graph form of train() (this agent was built with graph=False)')
+        if (getattr(buffer, 'members', None) is not None or not hasattr(buffer, 'collect_on_device')
+                or (getattr(buffer, 'state_dim', None), getattr(buffer, 'action_dim', None)) != (self.state_dim, self.action_dim)):
+            raise ValueError(f'{name}.iterate_sim: needs a ReplayBuffer of {self.state_dim} observations and {self.action_dim} actions')
+        if getattr(loop, 'agent', None) is not self:
+            raise ValueError(f'{name}.iterate_sim: the simulator loop belongs to another agent')
+        if loop.seed != self._seed:
+            raise ValueError(f'{name}.iterate_sim: the simulator loop draws with seed {loop.seed}, the agent now with {self._seed} (a checkpoint '
+                             'of another seed was loaded): create the SimLoop after load()')
+        N = int(loop.num_envs)
+        if N > buffer.max_size:
+            raise ValueError(f'{name}.iterate_sim: {N} environments for a ring of {buffer.max_size} rows')
+        B, train = int(batch_size), bool(train)
+        if self._pending:
+            self.flush()
+        buffer.collect_on_device(loop)
+        key = (self._graph_cache_key(buffer, B), id(loop), train, float(loop.eps_greedy), int(loop.start_timesteps), N)
+        graphs = self.__dict__.setdefault('_sim_graphs', {})
+        g = graphs.get(key)
+        if g is None:
+            if train:               # as _capture_prologue: size the programs and allocate the pools outside the capture
+                self._warm(buffer, B)
+                ni, ne = self._pool_sizes(B)
+                self._buf('pool_idx', (ni,), torch.int32)
+                self._buf('pool_eps', (ne,))
+            torch.cuda.synchronize()
+            with _no_gc():
+                from rlrep_amd._lib import lib as _l
+                s, g = torch.cuda.Stream(), torch.cuda.CUDAGraph()
+                for gen in getattr(loop.sim, 'graph_generators', ()):           # (the simulator's draws advance with every replay)
+                    g.register_generator_state(gen)
+                n0 = _l.rlrep_launch_counter()
+                if train:
+                    with self._history_capture(), self._managed_images(), torch.cuda.graph(g, stream=s):
+                        loop.step(buffer)
+                        self._body(buffer, B, True)
+                else:
+                    with torch.cuda.graph(g, stream=s):
+                        loop.step(buffer)
+                self._sim_launches = _l.rlrep_launch_counter() - n0           # the library's kernels in the captured iteration
+                self._sim_captures = getattr(self, '_sim_captures', 0) + 1
+            graphs.clear()          # (one form at a time is kept: a warm-up graph gives way to the training graph)
+            graphs[key] = g
+            self._held_env_buffer = buffer
+        if loop.calls != self._ctr:             # select_action, a capture or a checkpoint moved the call counter: the device follows (rare)
+            loop.set_counters(loop.t_global, self._ctr)
+        if train:
+            self._sync_images()
+        g.replay()
+        if not loop.advance():
+            self._ctr += N
+            loop.calls = self._ctr
+        if not train:
+            return None
+        self.steps += 1
+        return self._history_info() if self._hist else self.core.info()
+
     def evaluate(self, env, episodes, eval_index=None):
         """Mean return of `episodes` mean-action episodes, a float: ONE launch (rlrep_env_evaluate) and one copy back.  The start states are
         a function of (seed, eval_index, episode); by default eval_index counts the evaluations of `env`, so successive evaluations see

@@ -24,6 +24,7 @@
 #include "kparams.h"
 #include "philox.h"
 #include "group.h"
+#include "group_env.h"
 #include "launchers.h"
 
 // one layer for the 16 rows in `in` (LDS, pitch LD, zero-filled to a multiple of 16 columns): out[i][c] = act(sum_k in[i][k] W[c][k] + bias[c]).
@@ -122,6 +123,67 @@ __global__ __launch_bounds__(256) void actor_tile_kernel_grp(ActTile p0, long lo
 #include "actor_tile_body.h"
 }
 
+// lo + (hi - lo) * u of the exploration mix, one rounding per operation (tests/sim_loop_reference.py restates it in NumPy): hipcc contracts
+// a * b + c, and __fmul_rn / __fadd_rn do not stop it (docs/history/nstep.md), so each helper switches contraction off for its own operation
+__device__ __forceinline__ float mix_mul(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float mix_add(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__device__ __forceinline__ float mix_sub(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+// counter-reading form (rlrep_act_device_ctl, capturable: nothing that changes between two replays rides by value): the call counter, the step
+// counter and the iteration come from the loop record (kparams.h RL_CTL_*).  The tile and the head are actor_tile_body.h as actor_tile_kernel
+// compiles it, at explore = 1 and offset (calls + 1) << 20 -- the bytes of rlrep_act_device(explore = 1) at that counter.  Behind it the
+// exploration mix of env_step_body.h for A components: row e takes clamp(lo + (hi - lo) u_j) in every component j during warm-up
+// (T < start_timesteps) or if its pick word is below eps_greedy; the thread that stored element (row, j) in the body is the one that
+// overwrites it.  Philox blocks (key = the agent's seed): counter {iter lo, iter hi, e, RL_STREAM_SIM + q}.  Every workgroup reads CALLS, T
+// and ITER; ONE thread moves the cursor words, which this launch never reads.
+__global__ __launch_bounds__(256) void actor_tile_kernel_ctl(ActTile p0, ActCtl k) {
+    const unsigned long long calls = (unsigned long long)k.ctl[RL_CTL_CALLS];
+    const long long tg = k.ctl[RL_CTL_T];
+    const unsigned long long it = (unsigned long long)k.ctl[RL_CTL_ITER];
+    ActTile p = p0;
+    p.explore = 1; p.offset = (calls + 1ull) << 20;
+    const int r0 = blockIdx.x * 16;
+    {
+#include "actor_tile_body.h"
+    }
+    const bool warm = tg < k.start_timesteps;
+    if (warm || k.eps_greedy > 0.f) {
+        for (int e = threadIdx.x; e < 16 * p.A; e += 256) {
+            const int i = e / p.A, j = e - i * p.A;
+            const long long row = (long long)r0 + i;
+            if (row >= p.rows) continue;
+            uint32_t c[4] = {(uint32_t)it, (uint32_t)(it >> 32), (uint32_t)row, RL_STREAM_SIM};
+            philox4x32_10(c, (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
+            if (!(warm || env_u01f(c[0]) < k.eps_greedy)) continue;
+            const int wq = (1 + j) >> 2, ww = (1 + j) & 3;
+            if (wq) {
+                c[0] = (uint32_t)it; c[1] = (uint32_t)(it >> 32); c[2] = (uint32_t)row; c[3] = RL_STREAM_SIM + (uint32_t)wq;
+                philox4x32_10(c, (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
+            }
+            const uint32_t word = ww == 0 ? c[0] : ww == 1 ? c[1] : ww == 2 ? c[2] : c[3];
+            const float u = mix_add(p.lo, mix_mul(mix_sub(p.hi, p.lo), env_u01f(word)));
+            p.act[row * p.ld_act + j] = fminf(fmaxf(u, p.lo), p.hi);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        long long ptr = k.ctl[RL_CTL_NEXT];
+        if (ptr < 0 || ptr >= k.capacity) ptr = 0;                      // (a cursor written by the host: never leave the ring)
+        const long long nxt = ptr + p.rows;                             // (the launcher holds rows <= capacity)
+        k.ctl[RL_CTL_START] = ptr;
+        k.ctl[RL_CTL_NEXT] = nxt < k.capacity ? nxt : nxt - k.capacity;
+        k.ctl[RL_CTL_SIZE] = min(max(k.ctl[RL_CTL_SIZE], 0ll) + p.rows, k.capacity);
+        k.ctl[RL_CTL_WARM] = warm ? 1 : 0;
+    }
+}
+
 // LDS row pitch of the activation tiles (see the head of this file)
 static int at_pitch(int S, int Ha) {
     const int d16 = (std::max(S, Ha) + 15) & ~15;
@@ -148,5 +210,19 @@ extern "C" int rl_launch_actor_tile(const ActTile* p0, hipStream_t st) {
         hipLaunchKernelGGL(actor_tile_kernel_grp, dim3(gx, gr->grid_y), dim3(256), (size_t)lds, st, p, gr->stride, gr->seeds, gr->live);
     else
         hipLaunchKernelGGL(actor_tile_kernel, dim3(gx), dim3(256), (size_t)lds, st, p);
+    return (int)hipGetLastError();
+}
+// the counter-reading form: one agent (the callers refuse a group's handle), same grid, same LDS
+extern "C" int rl_launch_actor_tile_ctl(const ActTile* p0, const ActCtl* k, hipStream_t st) {
+    const long long lds = rl_actor_tile_lds_bytes(p0->S, p0->Ha, p0->A);
+    if (lds > RL_ACT_TILE_LDS_MAX) return -7;
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
+    ActTile p = *p0;
+    p.LD = at_pitch(p.S, p.Ha);
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(actor_tile_kernel_ctl), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(actor_tile_kernel_ctl, dim3((unsigned)((p.rows + 15) / 16)), dim3(256), (size_t)lds, st, p, *k);
     return (int)hipGetLastError();
 }

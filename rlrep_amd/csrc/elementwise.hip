@@ -737,6 +737,27 @@ __global__ __launch_bounds__(256) void replay_add_cols_kernel_grp(ReplayCols p) 
     replay_add_cols_body(p, p.ring + (long long)m * p.ring_stride, (long long)m * p.n);
     if (p.size_dev && blockIdx.x == 0 && threadIdx.x == 0) p.size_dev[m] = p.new_size;
 }
+// counter-reading form (rlrep_replay_add_cols_ctl, capturable): the first row and the fill level come from the loop record (kparams.h
+// RL_CTL_*) as the act launch of the same iteration left them; the row packing is replay_add_cols_body.  Every workgroup reads START; ONE
+// thread publishes SIZE to the size word and advances the words this launch never reads: ITER, T, and CALLS unless the iteration was a warm-up one.
+__global__ __launch_bounds__(256) void replay_add_cols_kernel_ctl(ReplayCols p0, long long* __restrict__ ctl) {
+    ReplayCols p = p0;
+    const long long st = ctl[RL_CTL_START];
+    p.start = (st < 0 || st >= p.capacity) ? 0 : st;                       // (a cursor written by the host: never leave the ring)
+    replay_add_cols_body(p, p.ring, 0);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (p.size_dev) *p.size_dev = (int)min(max(ctl[RL_CTL_SIZE], 0ll), p.capacity);
+        ctl[RL_CTL_ITER] += 1;
+        ctl[RL_CTL_T] += p.n;
+        if (!ctl[RL_CTL_WARM]) ctl[RL_CTL_CALLS] += p.n;
+    }
+}
+extern "C" int rl_launch_replay_add_cols_ctl(const ReplayCols* p, long long* ctl, hipStream_t st) {
+    const long long total = p->n * p->row;
+    const int blocks = (int)std::min<long long>(1024, std::max<long long>(1, (total + 255) / 256));
+    hipLaunchKernelGGL(replay_add_cols_kernel_ctl, dim3(blocks), dim3(256), 0, st, *p, ctl);
+    return (int)hipGetLastError();
+}
 extern "C" int rl_launch_replay_add_cols(const ReplayCols* p, int members, hipStream_t st) {
     const long long total = p->n * p->row;
     const int blocks = (int)std::min<long long>(1024, std::max<long long>(1, (total + 255) / 256));

@@ -489,6 +489,24 @@ int32_t rlrep_replay_add_cols(float* ring_dev, int64_t max_size, int32_t row_flo
     return 0;
 }
 
+static_assert(RL_LOOP_CTL_WORDS == RLREP_LOOP_CTL_WORDS && RL_CTL_WARM < RL_LOOP_CTL_WORDS, "include/rlrep.h documents the loop record (kparams.h RL_CTL_*)");
+// rlrep_replay_add_cols with `start` and the fill level read from the loop record on the device (replay_add_cols_kernel_ctl): capturable
+int32_t rlrep_replay_add_cols_ctl(float* ring_dev, int64_t max_size, int32_t row_floats, int32_t S, int32_t A, const float* s, int64_t ld_s, const float* a,
+                                  int64_t ld_a, const float* s2, int64_t ld_s2, const float* r, const float* d, int64_t n, int32_t* size_dev, int64_t* ctl_dev,
+                                  void* stream) {
+    if (!ring_dev || !s || !a || !s2 || !r || !d || !ctl_dev) { rl_set_error("replay_add_cols_ctl: bad argument (null ring, array or loop record)"); return RLREP_ERR_ARG; }
+    if (max_size <= 0 || max_size > INT32_MAX || n < 1 || n > max_size) { rl_set_error("replay_add_cols_ctl: n %lld outside [1, max_size %lld]", (long long)n, (long long)max_size); return RLREP_ERR_ARG; }
+    if (S < 1 || A < 1 || row_floats != 2 * S + A + 2) { rl_set_error("replay_add_cols_ctl: row %d is not 2 S + A + 2 (S %d, A %d)", row_floats, S, A); return RLREP_ERR_ARG; }
+    if (ld_s < S || ld_a < A || ld_s2 < S) { rl_set_error("replay_add_cols_ctl: bad argument (a row stride below its width)"); return RLREP_ERR_ARG; }
+    ReplayCols p; memset(&p, 0, sizeof(p));
+    p.ring = ring_dev; p.capacity = max_size; p.row = row_floats; p.S = S; p.A = A;
+    p.s = s; p.a = a; p.s2 = s2; p.r = r; p.d = d; p.ld_s = ld_s; p.ld_a = ld_a; p.ld_s2 = ld_s2; p.n = n; p.size_dev = size_dev;
+    ++g_rl_launches;
+    const int rc = rl_launch_replay_add_cols_ctl(&p, (long long*)ctl_dev, (hipStream_t)stream);
+    if (rc) { rl_set_error("replay_add_cols_ctl: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+
 static void slot_fill_params(rlrep_agent* ag, int slot, const float* ring_dev, const int32_t* idx_dev, SlotFill& p) {
     Slot& s = ag->slot[slot];
     memset(&p, 0, sizeof(p));
@@ -1109,6 +1127,39 @@ int32_t rlrep_act_device(rlrep_agent* ag, const float* obs_dev, int64_t ld_obs, 
     ++g_rl_launches;
     const int rc = rl_launch_actor_tile(&p, (hipStream_t)stream);
     if (rc) { rl_set_error("act_device: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    return 0;
+}
+
+// rlrep_act_device(explore = 1) with the call counter read from the loop record on the device, the exploration mix behind the head and the
+// ring cursor moved by `rows` (actor_tile_kernel_ctl): ONE launch, capturable -- nothing that changes between two replays rides by value
+int32_t rlrep_act_device_ctl(rlrep_agent* ag, const float* obs_dev, int64_t ld_obs, int32_t rows, uint64_t seed, float lo, float hi, float* action_dev,
+                             int64_t ld_act, int64_t* ctl_dev, int64_t max_size, float eps_greedy, int64_t start_timesteps, void* stream) {
+    if (!ag || !obs_dev || !action_dev || !ctl_dev) { rl_set_error("act_device_ctl: bad argument (null agent, observations, actions or loop record)"); return RLREP_ERR_ARG; }
+    if (rows < 1 || rows > RLREP_ACT_MAX_ROWS) { rl_set_error("act_device_ctl: rows %d outside [1, %d]", rows, RLREP_ACT_MAX_ROWS); return RLREP_ERR_ARG; }
+    GROUP_REFUSE("act_device_ctl")
+    const int S = ag->d.state_dim, Ha = ag->d.actor_hidden_dim, A = ag->d.action_dim;
+    if (ld_obs < S || ld_act < A || ld_obs > INT32_MAX || ld_act > INT32_MAX) {
+        rl_set_error("act_device_ctl: row strides (%lld, %lld) below the row widths (%d, %d)", (long long)ld_obs, (long long)ld_act, S, A); return RLREP_ERR_ARG;
+    }
+    if (max_size < rows) { rl_set_error("act_device_ctl: rows %d outside [1, max_size %lld] (the ring the cursor moves in)", rows, (long long)max_size); return RLREP_ERR_ARG; }
+    if (!(eps_greedy >= 0.f && eps_greedy <= 1.f) || start_timesteps < 0) {
+        rl_set_error("act_device_ctl: bad argument (eps_greedy outside [0, 1] or a negative start_timesteps)"); return RLREP_ERR_ARG;
+    }
+    if (rl_actor_tile_lds_bytes(S, Ha, A) > RL_ACT_TILE_LDS_MAX) {
+        rl_set_error("act_device_ctl: the activation tiles of S %d, Ha %d, A %d need %lld bytes of LDS, a workgroup has %d", S, Ha, A, rl_actor_tile_lds_bytes(S, Ha, A), RL_ACT_TILE_LDS_MAX);
+        return RLREP_ERR_ARG;
+    }
+    ActTile p; memset(&p, 0, sizeof(p));
+    p.obs = obs_dev; p.act = action_dev;
+    p.W1 = ag->P("actor.trunk.0.weight"); p.b1 = ag->P("actor.trunk.0.bias"); p.W2 = ag->P("actor.trunk.2.weight"); p.b2 = ag->P("actor.trunk.2.bias");
+    p.W3 = ag->P("actor.trunk.4.weight"); p.b3 = ag->P("actor.trunk.4.bias");
+    p.S = S; p.Ha = Ha; p.A = A; p.explore = 1; p.lo = lo; p.hi = hi; p.seed = seed;
+    p.rows = rows; p.ld_obs = (int)ld_obs; p.ld_act = (int)ld_act;
+    ActCtl k; memset(&k, 0, sizeof(k));
+    k.ctl = (long long*)ctl_dev; k.capacity = max_size; k.start_timesteps = start_timesteps; k.eps_greedy = eps_greedy;
+    ++g_rl_launches;
+    const int rc = rl_launch_actor_tile_ctl(&p, &k, (hipStream_t)stream);
+    if (rc) { rl_set_error("act_device_ctl: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
     return 0;
 }
 

@@ -29,6 +29,23 @@ struct ActTile {
     unsigned long long seed, offset;                    // row e draws rlrep_fill_normal(eps[A], 1, seed, offset + (e << 20))
     int rows, ld_obs, ld_act, LD;                       // LD: LDS row pitch of the activation tiles (set by the launcher)
 };
+// The loop record of a simulator loop replayed as one graph (rlrep_act_device_ctl / rlrep_replay_add_cols_ctl): int64 words in
+// caller-owned device memory.  Both launches have many workgroups and all of them read the record, so in either launch no thread writes a word
+// that any workgroup of the SAME launch reads (train_prologue_body.h's counter comment):
+//   the act launch     reads CALLS, T, ITER          one thread writes START, NEXT, SIZE, WARM
+//   the append launch  reads START, SIZE, WARM       one thread writes CALLS, T, ITER
+#define RL_LOOP_CTL_WORDS 8
+enum { RL_CTL_CALLS = 0,       // the agent's select_action call counter (_ctr)
+       RL_CTL_T = 1,           // environment steps taken
+       RL_CTL_ITER = 2,        // loop iterations: the counter of the exploration mix's Philox blocks
+       RL_CTL_NEXT = 3,        // the ring's next free row
+       RL_CTL_START = 4,       // first ring row of the iteration in flight (what NEXT was when its act launch ran)
+       RL_CTL_SIZE = 5,        // the ring's fill level, the iteration in flight included
+       RL_CTL_WARM = 6 };      // 1: the iteration in flight is a warm-up one (T < start_timesteps when its act launch ran)
+struct ActCtl {
+    long long* ctl; long long capacity, start_timesteps;   // capacity: the ring's rows (>= the launch's rows)
+    float eps_greedy;
+};
 // rlrep_replay_add_cols: n device-resident transitions, given as five arrays with row strides, packed into ring rows [s, a, s', r, d]
 struct ReplayCols {
     float* ring; long long capacity, start, ring_stride;   // ring_stride (floats): the group form's distance between two members' rings

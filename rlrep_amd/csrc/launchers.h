@@ -71,9 +71,11 @@ int rl_launch_replay_add(float* ring, long long capacity, int row, long long ptr
 int rl_launch_replay_add_grp(float* ring, long long ring_stride, int members, long long capacity, int row, long long ptr, const float* rows,
                              long long rows_stride, long long nrows, int* size_dev, int new_size, hipStream_t st);
 int rl_launch_replay_add_cols(const ReplayCols* p, int members, hipStream_t st);  // members == 0: one ring; otherwise grid y = member
+int rl_launch_replay_add_cols_ctl(const ReplayCols* p, long long* ctl, hipStream_t st);     // start and fill level from the loop record (RL_CTL_*)
 // ---- actor_tile.hip ----
 long long rl_actor_tile_lds_bytes(int S, int Ha, int A);
 int rl_launch_actor_tile(const ActTile* p, hipStream_t st);                        // p->rows observations (per member of an active group), 16 per workgroup
+int rl_launch_actor_tile_ctl(const ActTile* p, const ActCtl* k, hipStream_t st);   // one agent; counters from the loop record, exploration mix behind the head
 // ---- per.hip (prioritized replay: one workgroup each; the weighted sac critic head) ----
 int rl_launch_per_add(const PerAdd* p, hipStream_t st);
 int rl_launch_per_rebuild(float* tree, long long P, hipStream_t st);

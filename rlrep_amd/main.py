@@ -55,6 +55,11 @@ of N) is the loop of a simulator that already lives on the GPU as torch tensors 
 `act_device` launch on the device observations, `TorchPendulum.step`, ONE `add_device` launch and ONE `train()` -- no transition crosses the
 host.  Warm-up and epsilon-greedy actions are drawn on the device; an evaluation steps min(N, --eval_episodes) environments in lockstep with
 `act_device(explore=False)`.
+
+`--sim-graph` (only with --torch-envs N; not with --per) runs that loop as ONE graph replay per iteration (`SACAgent.iterate_sim`,
+envs/sim_loop.py): the act launch reads its call counter from a loop record on the device and mixes the exploring uniform actions in itself
+(Philox draws of the agent's seed instead of the torch generator's), `TorchPendulum(capturable=True).step_`, the append launch and train()
+are captured together.  Evaluations are the eager ones of --torch-envs.
 """
 import argparse
 import json
@@ -140,6 +145,9 @@ def run(argv=None):
                    help='environments of a torch simulator on the device (one agent, --env Pendulum-v1; 1..65536, 0 = off; --start_timesteps and '
                         '--eval_freq multiples of it; not with --seeds, --sweep, --device-env, --device-loop, --host-envs, --num-envs).  An iteration '
                         'is N transitions -- one act_device launch, one batched step, one add_device launch -- and one train()')
+    p.add_argument('--sim-graph', action='store_true',
+                   help='with --torch-envs N: act, explore, simulator step, append and train() of an iteration as ONE graph replay '
+                        '(SACAgent.iterate_sim; the counters live on the device).  Not with --per')
     p.add_argument('--per', action='store_true',
                    help='prioritized experience replay (Schaul et al. 2016; --alg sac, one agent): train() samples in proportion to '
                         '(|TD| + eps)^alpha from a sum tree on the device and weights the critic loss; beta is annealed linearly to 1 at '
@@ -166,6 +174,7 @@ def run(argv=None):
     _check_num_envs(args)
     _check_host_envs(args)
     _check_torch_envs(args)
+    _check_sim_graph(args)
     if args.device_loop:
         _check_device_loop(args)
     if args.seeds is not None or args.sweep:
@@ -203,6 +212,8 @@ def run(argv=None):
         return _single_device_loop(args, agent, replay, log_path, jsonl, tb)
     if args.host_envs > 1:
         return _host_envs_loop(args, agent, replay, log_path, jsonl, tb)
+    if args.torch_envs and args.sim_graph:
+        return _sim_graph_loop(args, agent, replay, log_path, jsonl, tb)
     if args.torch_envs:
         return _torch_envs_loop(args, agent, replay, log_path, jsonl, tb)
     evaluations = [util.eval_policy(agent, eval_env, args.eval_episodes)]
@@ -510,6 +521,58 @@ def _torch_envs_loop(args, agent, replay, log_path, jsonl, tb):
                     for k, v in row.items():
                         if k.startswith('info/'):
                             tb.add_scalar(k, v, t)
+                    tb.flush()
+            print('Step {}. Steps per sec: {:.4g}.'.format(t, sps))
+            if args.save_model:
+                agent.save(os.path.join(log_path, 'agent.pt'))
+    jsonl.close()
+    if tb is not None:
+        tb.close()
+    print('Total time cost {:.4g}s.'.format(timer.time_cost()))
+    return agent, evaluations
+
+
+def _check_sim_graph(args):
+    """--sim-graph: SystemExit, before anything touches the GPU, on what it does not run with"""
+    if not getattr(args, 'sim_graph', False):
+        return
+    if not int(args.torch_envs):
+        raise SystemExit('--sim-graph: the one-graph simulator loop is a form of the torch simulator loop; give --torch-envs N with it')
+    if getattr(args, 'per', False):
+        raise SystemExit('--sim-graph: the captured append of --torch-envs does not write the priority tree and does not go with --per')
+
+
+def _sim_graph_loop(args, agent, replay, log_path, jsonl, tb):
+    """_torch_envs_loop with --sim-graph: an iteration is ONE `iterate_sim` graph replay -- the act launch with the exploration mix, the
+    capturable simulator's `step_`, the append launch and train().  The environments run in lockstep, so every 200th iteration ends an
+    episode in all of them.  Evaluations are _torch_eval's, on a simulator of their own."""
+    from rlrep_amd.envs.sim_loop import SimLoop
+    from rlrep_amd.envs.torch_pendulum import TorchPendulum
+    N, dev = int(args.torch_envs), replay.device
+    env = TorchPendulum(N, dev, seed=args.seed, capturable=True)
+    eval_env = TorchPendulum(min(N, int(args.eval_episodes)), dev, seed=args.seed + 100)
+    env.reset()
+    loop = SimLoop(agent, env, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps))
+    evaluations, info = [], None
+    timer = util.Timer()
+    for k, t0 in enumerate(range(0, int(args.max_timesteps), N)):           # one iteration is N environment steps
+        out = agent.iterate_sim(loop, replay, args.batch_size, train=t0 >= args.start_timesteps)
+        info = out if out is not None else info
+        if (k + 1) % env._max_episode_steps == 0:
+            print(f'Total T: {t0 + N} Episode Num: {(k + 1) // env._max_episode_steps * N} Mean reward: {float(env.last_return.mean()):.3f}')
+        t = t0 + N
+        if t % args.eval_freq == 0:
+            sps = timer.steps_per_sec(t)
+            evaluations.append(_torch_eval(agent, eval_env, int(args.eval_episodes)))
+            if info is not None:
+                row = {'step': t, 'info/evaluation': float(evaluations[-1]), 'steps_per_sec': sps}
+                row.update({f'info/{k_}': float(v) for k_, v in info.items()})
+                jsonl.write(json.dumps(row) + '\n')
+                jsonl.flush()
+                if tb is not None:
+                    for k_, v in row.items():
+                        if k_.startswith('info/'):
+                            tb.add_scalar(k_, v, t)
                     tb.flush()
             print('Step {}. Steps per sec: {:.4g}.'.format(t, sps))
             if args.save_model:
