@@ -758,6 +758,7 @@ void build_vlsac(Builder& b, rlrep_agent* ag) {
             nb.splits = ncdw_splits; nb.slab = ncdw_slab; nb.bslab = ncdw_bslab;
             nb.engine = rl_nc_dw_engine();
             nb.fin_in_adam = ncdw_in_adam ? 1 : 0;
+            nb.rows = rl_off("nc_dw_rows") ? 0 : 1;       // (read here, where the program is built: never on a launch path)
             if (nb.engine == 1) {
                 base_tile = 0;
                 for (int q = 0; q < 2; ++q) {

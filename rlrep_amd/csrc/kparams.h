@@ -280,7 +280,8 @@ struct NcDwTask {
 // lean: the 128-VGPR build of the fp32 kernel (launch beside the feature chain).  engine 1 = bf16x3 split-K form: `splits` row ranges
 // per 64 x 64 output tile, partial tiles in slab [task][split][H][F], bias partials in bslab [task][split][H], summed by a finishing launch
 // fin_in_adam: the partials are summed by the critic group's optimizer launch (AdamTask::Slab) instead of nc_dw_fin_kernel
-struct NcDwBatch { int ntasks; int lean; int engine; int splits; float* slab; float* bslab; int fin_in_adam; int pad_; NcDwTask t[2]; };
+// rows: the bf16x3 form steps by noise row (nc_dw_x3r_kernel: sigma / mean split once per chunk of 32 batch rows; RLREP_DISABLE=nc_dw_rows: 0)
+struct NcDwBatch { int ntasks; int lean; int engine; int splits; float* slab; float* bslab; int fin_in_adam; int rows; NcDwTask t[2]; };
 
 struct NcDxTask {
     const float* GH[2]; int ldgh;    // dL/dHm per head [B, H]

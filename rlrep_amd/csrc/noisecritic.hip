@@ -1532,6 +1532,213 @@ __global__ __launch_bounds__(512) void nc_dw_x3_kernel(NcDwBatch nb) {
         }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The same launch stepping BY NOISE ROW (NcDwBatch::rows; RLREP_DISABLE=nc_dw_rows keeps the kernel above).  With A1[b,j] = sum_n dPre[b,n,j]
+//   dW[j,k] = sum_b mean[b,k] A1[b,j]  +  sum_n noise[n,k] * ( sum_b sigma[b,k] dPre[b,n,j] ):
+// the inner rows of a split are taken n-major in chunks of 32 batch rows, a step = one noise row n x the chunk's 32 batch rows.  The B operand
+// of every step is then the same sigma block: the producers split it (and the mean block) ONCE per chunk into images that stay in LDS, hold
+// their 8 values of GH/N in registers, and per step build and split dPre only (no x = mean + sigma * noise, no noise loads: half the elements
+// per step).  The consumers start every step from a zero accumulator and fold it with the step's noise value of their column -- one FMA per
+// accumulator register -- and a 21st step per chunk multiplies A1 (summed by the producers as they go) by the mean images, weight 1.
+// Same tiles, splits, slabs, XCD order, bias partials and barrier scheme as above; LDS: two A buffers + sigma + mean images = 61 440 B.
+// The rounding points move (a chunk's products are summed before the noise weight is applied), so results are fp32-accurate, not bit-equal.
+// ------------------------------------------------------------------------------------------------
+#define NDW_RSTEPS (4 * NC_NF + 1)             /* steps per chunk of 32 batch rows: the noise rows + the mean step */
+
+__global__ __launch_bounds__(512) void nc_dw_x3r_kernel(NcDwBatch nb) {
+    __shared__ __attribute__((aligned(16))) unsigned char L[4 * NDW_OPB];      // 61 440 B: A of even / odd steps, sigma images, mean images
+    const int bid = blockIdx.x;
+    const int q = (nb.ntasks > 1 && bid >= nb.t[1].tile_base) ? 1 : 0;
+    const NcDwTask& t = nb.t[q];
+    const int F = t.F, H = t.H, B = t.B;
+    constexpr int N = 4 * NC_NF;
+    const int TK = (F + 63) >> 6, TJ = (H + 63) >> 6;
+    int local = bid - t.tile_base;
+    {   // XCD-aware order, as nc_dw_x3_kernel
+        const int ngrp = TJ * nb.splits;
+        if ((ngrp & 7) == 0 && (t.tile_base & 7) == 0) {
+            const int x = local & 7, y = local >> 3;
+            local = ((y / TK) * 8 + x) * TK + (y % TK);
+        }
+    }
+    const int sp = local / (TJ * TK); local -= sp * (TJ * TK);
+    const int tj = local / TK, tk = local - tj * TK;
+    const int j0 = tj * 64, k0 = tk * 64;
+    const int bs = (B + nb.splits - 1) / nb.splits;                 // batch rows per split
+    const int bbeg = min(sp * bs, B), nbr = min(bs, B - bbeg);
+    const int T = ((nbr + 31) >> 5) * NDW_RSTEPS;                    // chunks of 32 batch rows x 21 steps
+    const int w8 = threadIdx.x >> 6;
+    float* const slab = nb.slab + ((size_t)(q * nb.splits + sp) * H) * F;
+    if (nbr <= 0) {                                                   // a split without rows (tiny batches): its partials are zero
+        for (int e = threadIdx.x; e < 64 * 64; e += 512) {
+            const int jj = j0 + (e >> 6), kk = k0 + (e & 63);
+            if (jj < H && kk < F) slab[(size_t)jj * F + kk] = 0.f;
+        }
+        if (tk == 0 && threadIdx.x < 64 && j0 + (int)threadIdx.x < H) nb.bslab[(size_t)(q * nb.splits + sp) * H + j0 + threadIdx.x] = 0.f;
+        return;
+    }
+
+    if (w8 >= 4) {
+        // ================= producer: thread = (column c of the 64-wide operands, octet rq of the chunk's batch rows) =================
+        const int tid = threadIdx.x - 256;
+        const int c = tid & 63, rq = tid >> 6;
+        const int j = min(j0 + c, H - 1), k = min(k0 + c, F - 1);
+        const float invN = 1.0f / (float)N;
+        const float* const Uc = t.U + j;
+        const float* const Gc = t.GH + j;
+        const float* const Mc = t.mean + k;
+        const float* const Sc = t.sigma + k;
+        const int wofs = c * NX_RSB + rq * 16;
+        // batch row e of this thread in chunk ch: rows past the split's end re-read its last row (never out of bounds) and count as zero
+        auto brow = [&](int ch, int e) { return bbeg + min(32 * ch + 8 * rq + e, nbr - 1); };
+        struct PReg { float u[8]; };
+        auto gload = [&](int s, PReg& r) {
+            s = min(s, T - 1);
+            const int ch = s / NDW_RSTEPS, n = min(s - ch * NDW_RSTEPS, N - 1);       // (the mean step loads nothing it uses)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) r.u[e] = Uc[((size_t)brow(ch, e) * N + n) * H];
+        };
+        auto write3 = [&](unsigned char* p, const float (&v)[8]) {
+            u32x4 vh, vm, vl;
+#pragma unroll
+            for (int p2 = 0; p2 < 4; ++p2) {
+                unsigned h, m, l;
+                x3_split2(v[2 * p2], v[2 * p2 + 1], h, m, l); vh[p2] = h; vm[p2] = m; vl[p2] = l;
+            }
+            *reinterpret_cast<u32x4*>(p) = vh;
+            *reinterpret_cast<u32x4*>(p + NDW_IMGB) = vm;
+            *reinterpret_cast<u32x4*>(p + 2 * NDW_IMGB) = vl;
+        };
+        float g[8], a1[8], mu[8], bsum = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) g[e] = a1[e] = mu[e] = 0.f;
+        auto produce = [&](int s, const PReg& r, unsigned char* buf) {
+            const int ch = s / NDW_RSTEPS, i = s - ch * NDW_RSTEPS;
+            if (i == 0) {
+                // a new chunk: GH/N of this thread's 8 rows, and the chunk's sigma images.  (The consumers are at the previous chunk's mean step
+                // or before their first: nobody reads the sigma images now.  The mean images are still being read: they follow at i == 1.)
+                float sg[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const bool ok = 32 * ch + 8 * rq + e < nbr;
+                    const size_t b = (size_t)brow(ch, e);
+                    const float gv = Gc[b * t.ldgh], sv = Sc[b * F], mv = Mc[b * t.ld_ml];
+                    g[e] = ok ? gv * invN : 0.f; sg[e] = ok ? sv : 0.f; mu[e] = ok ? mv : 0.f;
+                    a1[e] = 0.f;
+                }
+                write3(L + 2 * NDW_OPB + wofs, sg);
+            }
+            if (i == 1) write3(L + 3 * NDW_OPB + wofs, mu);
+            float a[8];
+            if (i < N) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    a[e] = g[e] * fminf(r.u[e] + 1.f, 1.f);                       // elu'(out) = min(out + 1, 1)
+                    a1[e] += a[e];
+                    bsum += a[e];
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) a[e] = a1[e];
+            }
+            write3(buf + wofs, a);
+        };
+        PReg ra, rb;
+        gload(0, ra); gload(1, rb);
+        produce(0, ra, L);
+        gload(2, ra);
+        __syncthreads();
+        for (int s = 0; s < T; s += 2) {
+            if (s + 1 < T) produce(s + 1, rb, L + NDW_OPB);
+            gload(s + 3, rb);
+            __syncthreads();
+            if (s + 1 < T) {
+                if (s + 2 < T) produce(s + 2, ra, L);
+                gload(s + 4, ra);
+                __syncthreads();
+            }
+        }
+        // bias partial of this split: sum over the four row octets of a column (fixed order), column tile 0 only
+        float* const red = reinterpret_cast<float*>(L);              // the image buffers are free: every consumer is past its last barrier
+        __syncthreads();
+        red[rq * 64 + c] = bsum;
+        __syncthreads();
+        if (tk == 0 && rq == 0 && j0 + c < H)
+            nb.bslab[(size_t)(q * nb.splits + sp) * H + j0 + c] = ((red[c] + red[64 + c]) + red[128 + c]) + red[192 + c];
+        return;
+    }
+
+    // ================= consumer: wave (wj, wk) owns rows j0 + 32 wj .. + 31, columns k0 + 32 wk .. + 31 of the tile =================
+    const int lane = threadIdx.x & 63, w = w8;
+    const int m16 = lane & 15, kq = lane >> 4;
+    const int wj = w >> 1, wk = w & 1;
+    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)L + (unsigned)(m16 * NX_RSB + kq * 16);
+    const unsigned aofs = (unsigned)(32 * wj * NX_RSB), bofs = (unsigned)(2 * NDW_OPB + 32 * wk * NX_RSB);
+    // this lane's two output columns (C/D map: col = lane & 15): the noise values that weight a step's products
+    const float* const nzp0 = t.noise + min(k0 + 32 * wk + m16, F - 1);
+    const float* const nzp1 = t.noise + min(k0 + 32 * wk + 16 + m16, F - 1);
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b2 = 0; b2 < 2; ++b2) acc[a][b2] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    __syncthreads();
+    for (int s = 0, i = 0; s < T; ++s) {
+        const bool ms = i == N;                                        // the chunk's mean step: A1 x mean images, weight 1
+        const int n = ms ? 0 : i;
+        float nz[2] = {nzp0[(size_t)n * F], nzp1[(size_t)n * F]};
+        const unsigned abase = lds0 + (unsigned)((s & 1) * NDW_OPB) + aofs;
+        const unsigned bbase = lds0 + bofs + (ms ? (unsigned)NDW_OPB : 0u);
+        u32x4 fa[2][3], fb[2][3];
+        ndw_fload_at<0>(fa[0], abase);
+        ndw_fload_at<0>(fb[0], bbase);
+        ndw_fload_at<16 * NX_RSB>(fa[1], abase);
+        ndw_fload_at<16 * NX_RSB>(fb[1], bbase);
+        asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[0][2]), "+v"(fb[0][0]), "+v"(fb[0][1]), "+v"(fb[0][2]));
+        f32x4 d[2][2];
+#define NDW_MM(A, Bq)                                                                                                   \
+        {                                                                                                               \
+            const bf16x8 Ah = __builtin_bit_cast(bf16x8, fa[A][0]), Am = __builtin_bit_cast(bf16x8, fa[A][1]), Al = __builtin_bit_cast(bf16x8, fa[A][2]); \
+            const bf16x8 Bh = __builtin_bit_cast(bf16x8, fb[Bq][0]), Bm = __builtin_bit_cast(bf16x8, fb[Bq][1]), Bl = __builtin_bit_cast(bf16x8, fb[Bq][2]); \
+            f32x4 c = (f32x4){0.f, 0.f, 0.f, 0.f};                                                                      \
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Al, Bh, c, 0, 0, 0);                                            \
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, Bl, c, 0, 0, 0);                                            \
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Am, Bm, c, 0, 0, 0);                                            \
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Am, Bh, c, 0, 0, 0);                                            \
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, Bm, c, 0, 0, 0);                                            \
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ah, Bh, c, 0, 0, 0);                                            \
+            d[A][Bq] = c;                                                                                               \
+        }
+        NDW_MM(0, 0)
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[1][0]), "+v"(fa[1][1]), "+v"(fa[1][2]), "+v"(fb[1][0]), "+v"(fb[1][1]), "+v"(fb[1][2]));
+        NDW_MM(0, 1) NDW_MM(1, 0) NDW_MM(1, 1)
+#undef NDW_MM
+        if (ms) nz[0] = nz[1] = 1.f;
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b2 = 0; b2 < 2; ++b2)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc[a][b2][r] = fmaf(nz[b2], d[a][b2][r], acc[a][b2][r]);
+        __syncthreads();
+        i = ms ? 0 : i + 1;
+    }
+    __syncthreads();                                                 // (the producers' bias reduction: two more barriers for every wave)
+    __syncthreads();
+    // partial tile -> slab: C/D map col = lane & 15 (k), row = 4 (lane >> 4) + reg (j)
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b2 = 0; b2 < 2; ++b2) {
+            const int kk = k0 + 32 * wk + 16 * b2 + m16;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int jj = j0 + 32 * wj + 16 * a + 4 * kq + r;
+                if (jj < H && kk < F) slab[(size_t)jj * F + kk] = acc[a][b2][r];
+            }
+        }
+}
+
 // sums the split partials in split order: gW = sum_sp slab[sp], gb = sum_sp bslab[sp]
 __global__ __launch_bounds__(256) void nc_dw_fin_kernel(NcDwBatch nb) {
     const int q = blockIdx.y;
@@ -1686,7 +1893,8 @@ extern "C" int rl_launch_nc_dw(const NcDwBatch* nb, int total_tiles, hipStream_t
         if (!nb->slab || !nb->bslab || nb->splits < 1) return -3;
         const NcDwTask& t0 = nb->t[0];
         for (int q = 1; q < nb->ntasks; ++q) if (nb->t[q].H != t0.H || nb->t[q].F != t0.F || nb->t[q].B != t0.B) return -3;
-        hipLaunchKernelGGL(nc_dw_x3_kernel, dim3(total_tiles), dim3(512), 0, st, *nb);
+        if (nb->rows) hipLaunchKernelGGL(nc_dw_x3r_kernel, dim3(total_tiles), dim3(512), 0, st, *nb);
+        else hipLaunchKernelGGL(nc_dw_x3_kernel, dim3(total_tiles), dim3(512), 0, st, *nb);
         if (nb->fin_in_adam) return (int)hipGetLastError();      // the critic group's optimizer launch adds the slabs (AdamTask::Slab)
         const size_t HF = (size_t)t0.H * t0.F;
         hipLaunchKernelGGL(nc_dw_fin_kernel, dim3((unsigned)((HF + 255) / 256), nb->ntasks), dim3(256), 0, st, *nb);
