@@ -618,64 +618,9 @@ class SACAgent(object):
         writes, so the two chains of the pipelined train() have nothing to overlap here.  A pipelined train() still in flight is finished
         first.  The step programs are sized for the batch by rlrep_prepare, not by the eager gather a train() capture uses: while the
         device owns the cursor the host's `buffer.size` is stale (and 0 for a ring only the device has written)."""
-        name = type(self).__name__
         self._check_per(buffer, 'iterate')
-        if self.world_size > 1 or self._dp:
-            raise RuntimeError(f'{name}.iterate: a data-parallel agent has no device environment')
-        if not self.use_graph:
-            raise RuntimeError(f'{name}.iterate: needs the graph form of train() (this agent was built with graph=False)')
-        if (getattr(buffer, 'members', None) is not None or not hasattr(buffer, 'collect_on_device')
-                or (getattr(buffer, 'state_dim', None), getattr(buffer, 'action_dim', None)) != (self.state_dim, self.action_dim)):
-            raise ValueError(f'{name}.iterate: needs a ReplayBuffer of {self.state_dim} observations and {self.action_dim} actions')
-        if getattr(env, 'agent', None) is not self:
-            raise ValueError(f'{name}.iterate: the device environment belongs to another agent')
-        if env.seed != self._seed:
-            raise ValueError(f'{name}.iterate: the device environment draws with seed {env.seed}, the agent now with {self._seed} (a checkpoint '
-                             'of another seed was loaded): create the environment after load()')
-        B, train = int(batch_size), bool(train)
-        if self._pending:
-            self.flush()
-        buffer.collect_on_device(env)
-        key = (self._graph_cache_key(buffer, B), id(env), train, float(env.eps_greedy), int(env.start_timesteps), int(getattr(env, 'num_envs', 1)))
-        graphs = self.__dict__.setdefault('_iter_graphs', {})
-        g = graphs.get(key)
-        if g is None:
-            if train:               # as _capture_prologue: size the programs and allocate the pools outside the capture
-                self._warm(buffer, B)
-                ni, ne = self._pool_sizes(B)
-                self._buf('pool_idx', (ni,), torch.int32)
-                self._buf('pool_eps', (ne,))
-            torch.cuda.synchronize()
-            with _no_gc():
-                from rlrep_amd._lib import lib as _l
-                s, g = torch.cuda.Stream(), torch.cuda.CUDAGraph()
-                n0 = _l.rlrep_launch_counter()
-                if train:
-                    with self._history_capture(), self._managed_images(), torch.cuda.graph(g, stream=s):
-                        env.step(buffer, env.eps_greedy, env.start_timesteps)
-                        self._body(buffer, B, True)
-                else:
-                    with torch.cuda.graph(g, stream=s):
-                        env.step(buffer, env.eps_greedy, env.start_timesteps)
-                self._iter_launches = _l.rlrep_launch_counter() - n0          # kernels in the captured iterate()
-            graphs.clear()          # (one form at a time is kept: a warm-up graph gives way to the training graph)
-            graphs[key] = g
-            self._held_env_buffer = buffer
-        if env.calls != self._ctr:              # select_action, a capture or a checkpoint moved the call counter: the device follows (rare)
-            env.set_counters(env.t_global, self._ctr)
-        if train:
-            self._sync_images()
-        g.replay()
-        E = int(getattr(env, 'num_envs', 1))    # (the launch steps E environments: E steps per member, E select_action calls)
-        warm = env.t_global < env.start_timesteps
-        env.t_global += E
-        if not warm:
-            self._ctr += E
-            env.calls = self._ctr
-        if not train:
-            return None
-        self.steps += 1
-        return self._history_info() if self._hist else self.core.info()
+        self._check_front('iterate', env, buffer, 'device environment', 'create the environment after load()')
+        return self._iterate(env, buffer, batch_size, train, lambda: env.step(buffer, env.eps_greedy, env.start_timesteps), '_iter')
 
     # ---- torch simulators on the device (rlrep_amd/envs/sim_loop.py SimLoop): the whole iteration as one graph replay ----------------------
     def iterate_sim(self, loop, buffer, batch_size, train=True):
@@ -693,61 +638,58 @@ class SACAgent(object):
             raise RuntimeError(f'{name}.iterate_sim: {cls} cannot be written by the captured simulator loop (its append launch does not write the '
                                'priority tree): use a plain ReplayBuffer, or the eager act_device / add_device / train() loop')
         self._check_nstep(buffer, 'iterate_sim')
-        if self.world_size > 1 or self._dp:
-            raise RuntimeError(f'{name}.iterate_sim: a data-parallel agent has no captured simulator loop')
-        if not self.use_graph:
-            raise RuntimeError(f'{name}.iterate_sim: needs the graph form of train() (this agent was built with graph=False)')
-        if (getattr(buffer, 'members', None) is not None or not hasattr(buffer, 'collect_on_device')
-                or (getattr(buffer, 'state_dim', None), getattr(buffer, 'action_dim', None)) != (self.state_dim, self.action_dim)):
-            raise ValueError(f'{name}.iterate_sim: needs a ReplayBuffer of {self.state_dim} observations and {self.action_dim} actions')
-        if getattr(loop, 'agent', None) is not self:
-            raise ValueError(f'{name}.iterate_sim: the simulator loop belongs to another agent')
-        if loop.seed != self._seed:
-            raise ValueError(f'{name}.iterate_sim: the simulator loop draws with seed {loop.seed}, the agent now with {self._seed} (a checkpoint '
-                             'of another seed was loaded): create the SimLoop after load()')
+        self._check_front('iterate_sim', loop, buffer, 'simulator loop', 'create the SimLoop after load()', lacks='captured simulator loop')
         N = int(loop.num_envs)
         if N > buffer.max_size:
             raise ValueError(f'{name}.iterate_sim: {N} environments for a ring of {buffer.max_size} rows')
+        # (the simulator's draws advance with every replay: its generators are registered with the graph)
+        return self._iterate(loop, buffer, batch_size, train, lambda: loop.step(buffer), '_sim', getattr(loop.sim, 'graph_generators', ()))
+
+    def _check_front(self, what, front, buffer, noun, remedy, lacks=None):
+        """What iterate (`front` a DeviceEnv) and iterate_sim (a SimLoop) refuse alike, by the method's name `what`: `noun` is what the
+        front is called, `remedy` what to do about a seed that moved, `lacks` what a data-parallel agent does not have (the noun by default)."""
+        name = type(self).__name__
+        if self.world_size > 1 or self._dp:
+            raise RuntimeError(f'{name}.{what}: a data-parallel agent has no {lacks or noun}')
+        if not self.use_graph:
+            raise RuntimeError(f'{name}.{what}: needs the graph form of train() (this agent was built with graph=False)')
+        if (getattr(buffer, 'members', None) is not None or not hasattr(buffer, 'collect_on_device')
+                or (getattr(buffer, 'state_dim', None), getattr(buffer, 'action_dim', None)) != (self.state_dim, self.action_dim)):
+            raise ValueError(f'{name}.{what}: needs a ReplayBuffer of {self.state_dim} observations and {self.action_dim} actions')
+        if getattr(front, 'agent', None) is not self:
+            raise ValueError(f'{name}.{what}: the {noun} belongs to another agent')
+        if front.seed != self._seed:
+            raise ValueError(f'{name}.{what}: the {noun} draws with seed {front.seed}, the agent now with {self._seed} (a checkpoint '
+                             f'of another seed was loaded): {remedy}')
+
+    def _iterate(self, front, buffer, batch_size, train, step, cache, generators=()):
+        """What iterate, iterate_sim and a seed group's iterate do once their arguments are checked: one replay of the cached graph of
+        `step()` (the launches of `front`: a DeviceEnv, DeviceEnvGroup or SimLoop) in front of train(), captured on the first call.  `cache`
+        names the attributes the form keeps: <cache>_graphs, <cache>_launches (the library's kernels in the captured iteration) and
+        <cache>_captures; `generators` are registered with the graph."""
         B, train = int(batch_size), bool(train)
         if self._pending:
             self.flush()
-        buffer.collect_on_device(loop)
-        key = (self._graph_cache_key(buffer, B), id(loop), train, float(loop.eps_greedy), int(loop.start_timesteps), N)
-        graphs = self.__dict__.setdefault('_sim_graphs', {})
+        buffer.collect_on_device(front)
+        key = (self._graph_cache_key(buffer, B), id(front), train, float(front.eps_greedy), int(front.start_timesteps), int(front.num_envs))
+        graphs = self.__dict__.setdefault(cache + '_graphs', {})
         g = graphs.get(key)
         if g is None:
-            if train:               # as _capture_prologue: size the programs and allocate the pools outside the capture
-                self._warm(buffer, B)
-                ni, ne = self._pool_sizes(B)
-                self._buf('pool_idx', (ni,), torch.int32)
-                self._buf('pool_eps', (ne,))
-            torch.cuda.synchronize()
-            with _no_gc():
-                from rlrep_amd._lib import lib as _l
-                s, g = torch.cuda.Stream(), torch.cuda.CUDAGraph()
-                for gen in getattr(loop.sim, 'graph_generators', ()):           # (the simulator's draws advance with every replay)
-                    g.register_generator_state(gen)
-                n0 = _l.rlrep_launch_counter()
-                if train:
-                    with self._history_capture(), self._managed_images(), torch.cuda.graph(g, stream=s):
-                        loop.step(buffer)
-                        self._body(buffer, B, True)
-                else:
-                    with torch.cuda.graph(g, stream=s):
-                        loop.step(buffer)
-                self._sim_launches = _l.rlrep_launch_counter() - n0           # the library's kernels in the captured iteration
-                self._sim_captures = getattr(self, '_sim_captures', 0) + 1
+            self._before_capture(buffer, B, train)
+            g, launches, _ = self._capture(buffer, B, step, train, generators)
+            setattr(self, cache + '_launches', launches)
+            setattr(self, cache + '_captures', getattr(self, cache + '_captures', 0) + 1)
             graphs.clear()          # (one form at a time is kept: a warm-up graph gives way to the training graph)
             graphs[key] = g
             self._held_env_buffer = buffer
-        if loop.calls != self._ctr:             # select_action, a capture or a checkpoint moved the call counter: the device follows (rare)
-            loop.set_counters(loop.t_global, self._ctr)
+        if front.calls != self._ctr:            # select_action, a capture or a checkpoint moved the call counter: the device follows (rare)
+            front.set_counters(front.t_global, self._ctr)
         if train:
             self._sync_images()
         g.replay()
-        if not loop.advance():
-            self._ctr += N
-            loop.calls = self._ctr
+        if not front.advance():                 # (the launch steps num_envs environments: as many steps per member and select_action calls)
+            self._ctr += int(front.num_envs)
+            front.calls = self._ctr
         if not train:
             return None
         self.steps += 1
@@ -1157,12 +1099,40 @@ class SACAgent(object):
             return None
         if flush:
             self.flush()
-        self._warm(buffer, B)
-        ni, ne = self._pool_sizes(B)
-        self._buf('pool_idx', (ni,), torch.int32)
-        self._buf('pool_eps', (ne,))
-        torch.cuda.synchronize()
+        self._before_capture(buffer, B)
         return key
+
+    def _before_capture(self, buffer, B, train=True):
+        """Before a capture that holds a train(): size the library's tables for B and allocate the two pools outside it (_capture_prologue
+        says why); before any capture: let the device finish."""
+        if train:
+            self._warm(buffer, B)
+            ni, ne = self._pool_sizes(B)
+            self._buf('pool_idx', (ni,), torch.int32)
+            self._buf('pool_eps', (ne,))
+        torch.cuda.synchronize()
+
+    def _capture(self, buffer, B, step=None, train=True, generators=()):
+        """One hipGraph of `step()` (when given) and, with `train`, the whole train() behind it, captured on a stream of its own.  Returns
+        (graph, launches of the library captured, front-end counts captured).  `generators` (torch.Generator) are registered with the graph
+        before the capture begins, so that their draws advance with every replay."""
+        from rlrep_amd._lib import lib as _l, front_end_counts as _fe
+        with _no_gc():              # (a cyclic-GC pass inside a capture may run destructors that touch the device: see _no_gc)
+            s, g = torch.cuda.Stream(), torch.cuda.CUDAGraph()
+            for gen in generators:
+                g.register_generator_state(gen)
+            n0, f0 = _l.rlrep_launch_counter(), _fe()
+            with contextlib.ExitStack() as around:
+                if train:
+                    around.enter_context(self._history_capture())
+                    around.enter_context(self._managed_images())
+                around.enter_context(torch.cuda.graph(g, stream=s))
+                if step is not None:
+                    step()
+                if train:
+                    self._body(buffer, B, True)
+            launches, f1 = _l.rlrep_launch_counter() - n0, _fe()
+        return g, launches, {k: f1[k] - f0[k] for k in f1}
 
     @staticmethod
     def _replay(items):
@@ -1492,20 +1462,11 @@ class SACAgent(object):
     def _train_graph(self, buffer, B):
         key = self._capture_prologue(buffer, B, None if self._graph is None else self._graph_key)
         if key is not None:
-            with _no_gc():          # (a cyclic-GC pass inside a capture may run destructors that touch the device: see _no_gc)
-                # the whole train() as one hipGraph
-                from rlrep_amd._lib import lib as _l, front_end_counts as _fe
-                s = torch.cuda.Stream()
-                g = torch.cuda.CUDAGraph()
-                n0, f0 = _l.rlrep_launch_counter(), _fe()
-                with self._history_capture(), self._managed_images(), torch.cuda.graph(g, stream=s):
-                    self._body(buffer, B, True)
-                self._graph, self._graph_key = g, key
-                if self._per(buffer):
-                    self._held_buffer = buffer          # the cached graph reads its tree and draw buffers: keep it alive as long as the graph
-                self._graph_launches = _l.rlrep_launch_counter() - n0
-                f1 = _fe()
-                self._graph_front_ends = {k: f1[k] - f0[k] for k in f1}
+            # the whole train() as one hipGraph
+            self._graph, self._graph_launches, self._graph_front_ends = self._capture(buffer, B)
+            self._graph_key = key
+            if self._per(buffer):
+                self._held_buffer = buffer          # the cached graph reads its tree and draw buffers: keep it alive as long as the graph
         if self._prepare_only:
             return None
         self._sync_images()

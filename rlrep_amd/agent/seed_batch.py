@@ -36,7 +36,7 @@ import torch
 
 from rlrep_amd._lib import lib, check
 from rlrep_amd.core import HipCore, _stream
-from rlrep_amd.agent.sac.sac_agent import ArenaModule, SELECT_MAX_ROWS, ACT_MAX_ROWS, _no_gc
+from rlrep_amd.agent.sac.sac_agent import ArenaModule, SELECT_MAX_ROWS, ACT_MAX_ROWS
 from rlrep_amd.utils import switches as _sw
 
 
@@ -477,47 +477,7 @@ class SeedBatchMixin(object):
             raise ValueError(f'{name}.iterate: needs a ReplayBufferGroup of {self.R} members')
         if getattr(env, 'agent', None) is not self:
             raise ValueError(f'{name}.iterate: the device environment belongs to another group')
-        B, train = int(batch_size), bool(train)
-        buffers.collect_on_device(env)
-        key = (self._graph_cache_key(buffers, B), id(env), train, float(env.eps_greedy), int(env.start_timesteps), int(getattr(env, 'num_envs', 1)))
-        graphs = self.__dict__.setdefault('_iter_graphs', {})
-        g = graphs.get(key)
-        if g is None:
-            if train:               # as _capture_prologue: size the programs and allocate the pools outside the capture
-                self._sample_into(buffers, B, 'warm', 0, False)
-                ni, ne = self._pool_sizes(B)
-                self._buf('pool_idx', (ni,), torch.int32)
-                self._buf('pool_eps', (ne,))
-            torch.cuda.synchronize()
-            with _no_gc():
-                s, g = torch.cuda.Stream(), torch.cuda.CUDAGraph()
-                n0 = lib.rlrep_launch_counter()
-                if train:
-                    with self._history_capture(), self._managed_images(), torch.cuda.graph(g, stream=s):
-                        env.step(buffers, env.eps_greedy, env.start_timesteps)
-                        self._body(buffers, B, True)
-                else:
-                    with torch.cuda.graph(g, stream=s):
-                        env.step(buffers, env.eps_greedy, env.start_timesteps)
-                self._iter_launches = lib.rlrep_launch_counter() - n0          # kernels in the captured iterate()
-            graphs.clear()          # (one form at a time is kept: a warm-up graph gives way to the training graph)
-            graphs[key] = g
-            self._held_env_buffer = buffers
-        if env.calls != self._ctr:              # select_action, a capture or a checkpoint moved the call counter: the device follows (rare)
-            env.set_counters(env.t_global, self._ctr)
-        if train:
-            self._sync_images()
-        g.replay()
-        E = int(getattr(env, 'num_envs', 1))    # (the launch steps E environments: E steps per member, E select_action calls)
-        warm = env.t_global < env.start_timesteps
-        env.t_global += E
-        if not warm:
-            self._ctr += E
-            env.calls = self._ctr
-        if not train:
-            return None
-        self.steps += 1
-        return self._history_info() if self._hist else self.core.info()
+        return self._iterate(env, buffers, batch_size, train, lambda: env.step(buffers, env.eps_greedy, env.start_timesteps), '_iter')
 
     def evaluate(self, env, episodes, eval_index=None):
         """Mean return of `episodes` mean-action episodes per member, [R] float64 (NaN for a retired member): ONE launch

@@ -116,6 +116,12 @@ class _DeviceEnvBase(object):
         self._block(STATE_COUNTERS, c, True)
         self.t_global, self.calls = int(t_global), int(calls)
 
+    def advance(self):
+        """the host mirrors after one replay of the step launch (num_envs steps per member); True if it was a warm-up one"""
+        warm = self.t_global < self.start_timesteps
+        self.t_global += self.num_envs
+        return warm
+
     def set_cursor(self, ptr, sizes, capacity=None):
         """every member's next free ring row (the rings are filled in lockstep) and fill level, e.g. from a ReplayBufferGroup filled on the
         host.  Environment e's own cursor is (ptr + e) mod capacity: with several environments the ring's `capacity` is needed."""

@@ -60,8 +60,13 @@ host.  Warm-up and epsilon-greedy actions are drawn on the device; an evaluation
 envs/sim_loop.py): the act launch reads its call counter from a loop record on the device and mixes the exploring uniform actions in itself
 (Philox draws of the agent's seed instead of the torch generator's), `TorchPendulum(capturable=True).step_`, the append launch and train()
 are captured together.  Evaluations are the eager ones of --torch-envs.
+
+The loops differ in what an iteration is, who draws the exploring action and whether there is an initial evaluation; what they do at an
+evaluation step -- anneal beta, take the rate, evaluate, write the row, print, --save_model -- is one copy per side: _Evaluations for one
+agent, _GroupEvaluations for a seed group.
 """
 import argparse
+import functools
 import json
 import os
 
@@ -190,14 +195,6 @@ def run(argv=None):
     env.seed(args.seed)
     eval_env.seed(args.seed)
     max_length = env._max_episode_steps
-    log_path = os.path.join(_log_root(args), str(args.seed))
-    os.makedirs(log_path, exist_ok=True)
-    jsonl = open(os.path.join(log_path, 'metrics.jsonl'), 'a')
-    try:
-        from tensorboardX import SummaryWriter
-        tb = SummaryWriter(log_path)
-    except ImportError:
-        tb = None
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
 
@@ -208,19 +205,21 @@ def run(argv=None):
                                                 **_nstep_kw(args))
     else:
         replay = buffer.ReplayBuffer(state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)), **_nstep_kw(args))
+    ev = _Evaluations(args, agent, replay, os.path.join(_log_root(args), str(args.seed)))
     if args.device_loop:
-        return _single_device_loop(args, agent, replay, log_path, jsonl, tb)
+        return _single_device_loop(args, agent, replay, ev)
     if args.host_envs > 1:
-        return _host_envs_loop(args, agent, replay, log_path, jsonl, tb)
+        return _host_envs_loop(args, agent, replay, ev)
     if args.torch_envs and args.sim_graph:
-        return _sim_graph_loop(args, agent, replay, log_path, jsonl, tb)
+        return _sim_graph_loop(args, agent, replay, ev)
     if args.torch_envs:
-        return _torch_envs_loop(args, agent, replay, log_path, jsonl, tb)
-    evaluations = [util.eval_policy(agent, eval_env, args.eval_episodes)]
+        return _torch_envs_loop(args, agent, replay, ev)
+    evaluate = functools.partial(util.eval_policy, agent, eval_env, args.eval_episodes)
+    ev.evaluations.append(evaluate())
 
     state, done = env.reset(), False
     ep_reward, ep_steps, ep_num, info = 0.0, 0, 0, None
-    timer = util.Timer()
+    ev.timer = util.Timer()
     for t in range(int(args.max_timesteps)):
         ep_steps += 1
         if t < args.start_timesteps or np.random.uniform(0, 1) < EPS_GREEDY:
@@ -238,27 +237,9 @@ def run(argv=None):
             state, done = env.reset(), False
             ep_reward, ep_steps, ep_num = 0.0, 0, ep_num + 1
         if (t + 1) % args.eval_freq == 0:
-            _per_anneal(args, replay, t + 1)
-            sps = timer.steps_per_sec(t + 1)
-            evaluations.append(util.eval_policy(agent, eval_env, args.eval_episodes))
-            if info is not None:
-                row = {'step': t + 1, 'info/evaluation': float(evaluations[-1]), 'steps_per_sec': sps}
-                row.update({f'info/{k}': float(v) for k, v in info.items()})
-                jsonl.write(json.dumps(row) + '\n')
-                jsonl.flush()
-                if tb is not None:
-                    for k, v in row.items():
-                        if k.startswith('info/'):
-                            tb.add_scalar(k, v, t + 1)
-                    tb.flush()
-            print('Step {}. Steps per sec: {:.4g}.'.format(t + 1, sps))
-            if args.save_model:
-                agent.save(os.path.join(log_path, 'agent.pt'))
-    jsonl.close()
-    if tb is not None:
-        tb.close()
-    print('Total time cost {:.4g}s.'.format(timer.time_cost()))
-    return agent, evaluations
+            ev.step(t + 1, evaluate, info)
+    ev.close()
+    return agent, ev.evaluations
 
 
 def _nstep_stride(args):
@@ -310,8 +291,7 @@ def _check_per(args):
                         ('--halving-interval', _halving_requested(args))):
         if given:
             raise SystemExit(f'--per: prioritized replay trains ONE agent from a ring the host or add_device fills; it does not go with {flag}')
-    if not 0.0 <= float(args.per_alpha) or not 0.0 <= float(args.per_beta) <= 1.0:
-        raise SystemExit(f'--per: --per-alpha {args.per_alpha} must be >= 0 and --per-beta {args.per_beta} in [0, 1]')
+    _check_per_exponents('--per', args)
 
 
 def _check_group_per(args):
@@ -330,8 +310,13 @@ def _check_group_per(args):
         if given:
             raise SystemExit(f'--group-per: a device environment writes ring rows inside its step launch, which knows nothing of the priority '
                              f'trees; it does not go with {flag}')
+    _check_per_exponents('--group-per', args)
+
+
+def _check_per_exponents(flag, args):
+    """the ranges of --per-alpha and --per-beta, for `flag` (--per or --group-per)"""
     if not 0.0 <= float(args.per_alpha) or not 0.0 <= float(args.per_beta) <= 1.0:
-        raise SystemExit(f'--group-per: --per-alpha {args.per_alpha} must be >= 0 and --per-beta {args.per_beta} in [0, 1]')
+        raise SystemExit(f'{flag}: --per-alpha {args.per_alpha} must be >= 0 and --per-beta {args.per_beta} in [0, 1]')
 
 
 def _per_anneal(args, replay, t):
@@ -349,9 +334,15 @@ def _check_num_envs(args):
         raise SystemExit('--num-envs: several environments per agent are stepped on the device; give --device-env (seed groups) or --device-loop (one agent)')
     if not 1 <= E <= 64:
         raise SystemExit(f'--num-envs {E}: outside [1, 64]')
-    for flag, value in (('--start_timesteps', args.start_timesteps), ('--eval_freq', args.eval_freq)):
-        if value != int(value) or int(value) % E:
-            raise SystemExit(f'--num-envs {E}: {flag} {value:g} is not a multiple of it (a step launch takes {E} steps per member at once)')
+    _check_multiple('--num-envs', E, args, f'a step launch takes {E} steps per member at once')
+
+
+def _check_multiple(flag, n, args, why):
+    """--start_timesteps and --eval_freq are multiples of `flag`'s value n, or SystemExit: an iteration of its loop is n steps, all warm-up or
+    none of it, and evaluations fall between iterations"""
+    for name, value in (('--start_timesteps', args.start_timesteps), ('--eval_freq', args.eval_freq)):
+        if value != int(value) or int(value) % n:
+            raise SystemExit(f'{flag} {n}: {name} {value:g} is not a multiple of it ({why})')
 
 
 def _check_host_envs(args):
@@ -366,9 +357,7 @@ def _check_host_envs(args):
         if given:
             raise SystemExit(f'--host-envs {E}: several host environments per agent do not go with {flag} (device environments take --num-envs; '
                              'ranking a population over vector environments is not built)')
-    for flag, value in (('--start_timesteps', args.start_timesteps), ('--eval_freq', args.eval_freq)):
-        if value != int(value) or int(value) % E:
-            raise SystemExit(f'--host-envs {E}: {flag} {value:g} is not a multiple of it (an iteration takes {E} environment steps at once)')
+    _check_multiple('--host-envs', E, args, f'an iteration takes {E} environment steps at once')
 
 
 def _host_envs(name, seed, n):
@@ -379,7 +368,7 @@ def _host_envs(name, seed, n):
     return out
 
 
-def _host_envs_loop(args, agent, replay, log_path, jsonl, tb):
+def _host_envs_loop(args, agent, replay, ev):
     """run()'s loop over E = --host-envs host environments (seeded seed + i): an iteration is ONE `select_actions` launch, E `env.step`, one
     `add_batch` (done_bool per environment by run()'s rule) and one `train()`.  During warm-up, and with probability epsilon afterwards, an
     environment's action is its action space's uniform sample, drawn in environment order as run() draws it.  Episodes end and reset per
@@ -388,11 +377,12 @@ def _host_envs_loop(args, agent, replay, log_path, jsonl, tb):
     envs_ = _host_envs(args.env, args.seed, E)
     eval_envs = _host_envs(args.env, args.seed, min(E, int(args.eval_episodes)))
     max_length = envs_[0]._max_episode_steps
-    evaluations = [util.eval_policy_vec(agent, eval_envs, args.eval_episodes)]
+    evaluate = functools.partial(util.eval_policy_vec, agent, eval_envs, args.eval_episodes)
+    ev.evaluations.append(evaluate())
     states = np.stack([np.asarray(e.reset(), np.float32) for e in envs_])
     action_dim = envs_[0].action_space.shape[0]
     ep_reward, ep_steps, ep_num, info = np.zeros(E), np.zeros(E, np.int64), 0, None
-    timer = util.Timer()
+    ev.timer = util.Timer()
     for t0 in range(0, int(args.max_timesteps), E):             # one iteration is E environment steps
         ep_steps += 1
         warm = t0 < args.start_timesteps
@@ -420,27 +410,9 @@ def _host_envs_loop(args, agent, replay, log_path, jsonl, tb):
             info = agent.train(replay, batch_size=args.batch_size)
         t = t0 + E
         if t % args.eval_freq == 0:
-            _per_anneal(args, replay, t)
-            sps = timer.steps_per_sec(t)
-            evaluations.append(util.eval_policy_vec(agent, eval_envs, args.eval_episodes))
-            if info is not None:
-                row = {'step': t, 'info/evaluation': float(evaluations[-1]), 'steps_per_sec': sps}
-                row.update({f'info/{k}': float(v) for k, v in info.items()})
-                jsonl.write(json.dumps(row) + '\n')
-                jsonl.flush()
-                if tb is not None:
-                    for k, v in row.items():
-                        if k.startswith('info/'):
-                            tb.add_scalar(k, v, t)
-                    tb.flush()
-            print('Step {}. Steps per sec: {:.4g}.'.format(t, sps))
-            if args.save_model:
-                agent.save(os.path.join(log_path, 'agent.pt'))
-    jsonl.close()
-    if tb is not None:
-        tb.close()
-    print('Total time cost {:.4g}s.'.format(timer.time_cost()))
-    return agent, evaluations
+            ev.step(t, evaluate, info)
+    ev.close()
+    return agent, ev.evaluations
 
 
 def _check_torch_envs(args):
@@ -457,9 +429,7 @@ def _check_torch_envs(args):
                              'act_device / add_device as an API only)')
     if not args.env.startswith('Pendulum'):
         raise SystemExit(f'--torch-envs {N}: the example simulator is Pendulum-v1 (got --env {args.env})')
-    for flag, value in (('--start_timesteps', args.start_timesteps), ('--eval_freq', args.eval_freq)):
-        if value != int(value) or int(value) % N:
-            raise SystemExit(f'--torch-envs {N}: {flag} {value:g} is not a multiple of it (an iteration takes {N} environment steps at once)')
+    _check_multiple('--torch-envs', N, args, f'an iteration takes {N} environment steps at once')
     if N > min(args.max_timesteps, 1e6):
         raise SystemExit(f'--torch-envs {N}: more environments than the replay ring has rows (min(--max_timesteps, 1e6))')
 
@@ -476,7 +446,7 @@ def _torch_eval(agent, env, episodes):
     return float(np.mean(returns[:episodes]))
 
 
-def _torch_envs_loop(args, agent, replay, log_path, jsonl, tb):
+def _torch_envs_loop(args, agent, replay, ev):
     """run()'s loop over N = --torch-envs environments of a simulator on the device (envs/torch_pendulum.py): an iteration is ONE `act_device`
     launch, one batched `step`, ONE `add_device` launch and one `train()`; nothing of a transition crosses the host.  During warm-up, and
     with probability epsilon afterwards, an environment's action is uniform in the action range, drawn on the device.  Evaluations follow
@@ -489,9 +459,10 @@ def _torch_envs_loop(args, agent, replay, log_path, jsonl, tb):
     gen.manual_seed(int(args.seed))
     lo, hi = agent.action_range
     A = env.action_dim
-    evaluations, info, episodes = [], None, 0
+    evaluate = functools.partial(_torch_eval, agent, eval_env, int(args.eval_episodes))
+    info, episodes = None, 0
     obs = env.reset()
-    timer = util.Timer()
+    ev.timer = util.Timer()
     for t0 in range(0, int(args.max_timesteps), N):             # one iteration is N environment steps
         uniform = lo + (hi - lo) * torch.rand(N, A, dtype=torch.float32, device=dev, generator=gen)
         if t0 < args.start_timesteps:
@@ -509,27 +480,9 @@ def _torch_envs_loop(args, agent, replay, log_path, jsonl, tb):
             info = agent.train(replay, batch_size=args.batch_size)
         t = t0 + N
         if t % args.eval_freq == 0:
-            _per_anneal(args, replay, t)
-            sps = timer.steps_per_sec(t)
-            evaluations.append(_torch_eval(agent, eval_env, int(args.eval_episodes)))
-            if info is not None:
-                row = {'step': t, 'info/evaluation': float(evaluations[-1]), 'steps_per_sec': sps}
-                row.update({f'info/{k}': float(v) for k, v in info.items()})
-                jsonl.write(json.dumps(row) + '\n')
-                jsonl.flush()
-                if tb is not None:
-                    for k, v in row.items():
-                        if k.startswith('info/'):
-                            tb.add_scalar(k, v, t)
-                    tb.flush()
-            print('Step {}. Steps per sec: {:.4g}.'.format(t, sps))
-            if args.save_model:
-                agent.save(os.path.join(log_path, 'agent.pt'))
-    jsonl.close()
-    if tb is not None:
-        tb.close()
-    print('Total time cost {:.4g}s.'.format(timer.time_cost()))
-    return agent, evaluations
+            ev.step(t, evaluate, info)
+    ev.close()
+    return agent, ev.evaluations
 
 
 def _check_sim_graph(args):
@@ -542,7 +495,7 @@ def _check_sim_graph(args):
         raise SystemExit('--sim-graph: the captured append of --torch-envs does not write the priority tree and does not go with --per')
 
 
-def _sim_graph_loop(args, agent, replay, log_path, jsonl, tb):
+def _sim_graph_loop(args, agent, replay, ev):
     """_torch_envs_loop with --sim-graph: an iteration is ONE `iterate_sim` graph replay -- the act launch with the exploration mix, the
     capturable simulator's `step_`, the append launch and train().  The environments run in lockstep, so every 200th iteration ends an
     episode in all of them.  Evaluations are _torch_eval's, on a simulator of their own."""
@@ -553,8 +506,9 @@ def _sim_graph_loop(args, agent, replay, log_path, jsonl, tb):
     eval_env = TorchPendulum(min(N, int(args.eval_episodes)), dev, seed=args.seed + 100)
     env.reset()
     loop = SimLoop(agent, env, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps))
-    evaluations, info = [], None
-    timer = util.Timer()
+    evaluate = functools.partial(_torch_eval, agent, eval_env, int(args.eval_episodes))
+    info = None
+    ev.timer = util.Timer()
     for k, t0 in enumerate(range(0, int(args.max_timesteps), N)):           # one iteration is N environment steps
         out = agent.iterate_sim(loop, replay, args.batch_size, train=t0 >= args.start_timesteps)
         info = out if out is not None else info
@@ -562,26 +516,9 @@ def _sim_graph_loop(args, agent, replay, log_path, jsonl, tb):
             print(f'Total T: {t0 + N} Episode Num: {(k + 1) // env._max_episode_steps * N} Mean reward: {float(env.last_return.mean()):.3f}')
         t = t0 + N
         if t % args.eval_freq == 0:
-            sps = timer.steps_per_sec(t)
-            evaluations.append(_torch_eval(agent, eval_env, int(args.eval_episodes)))
-            if info is not None:
-                row = {'step': t, 'info/evaluation': float(evaluations[-1]), 'steps_per_sec': sps}
-                row.update({f'info/{k_}': float(v) for k_, v in info.items()})
-                jsonl.write(json.dumps(row) + '\n')
-                jsonl.flush()
-                if tb is not None:
-                    for k_, v in row.items():
-                        if k_.startswith('info/'):
-                            tb.add_scalar(k_, v, t)
-                    tb.flush()
-            print('Step {}. Steps per sec: {:.4g}.'.format(t, sps))
-            if args.save_model:
-                agent.save(os.path.join(log_path, 'agent.pt'))
-    jsonl.close()
-    if tb is not None:
-        tb.close()
-    print('Total time cost {:.4g}s.'.format(timer.time_cost()))
-    return agent, evaluations
+            ev.step(t, evaluate, info)
+    ev.close()
+    return agent, ev.evaluations
 
 
 def _check_device_loop(args):
@@ -596,7 +533,7 @@ def _check_device_loop(args):
         raise SystemExit(f'--device-loop: only Pendulum-v1 and MountainCarContinuous-v0 are built on the device (got --env {args.env}); run without --device-loop')
 
 
-def _single_device_loop(args, agent, replay, log_path, jsonl, tb):
+def _single_device_loop(args, agent, replay, ev):
     """run()'s loop with the environment on the device (--device-loop), _device_loop's shape for one agent: an initial evaluation, one
     `agent.iterate` per step -- act, explore, step, ring row and train() in one graph replay -- and one `agent.evaluate` launch every
     --eval_freq.  The exploration and reset draws are Philox streams of the agent's seed instead of NumPy generators; the metrics.jsonl rows
@@ -604,34 +541,18 @@ def _single_device_loop(args, agent, replay, log_path, jsonl, tb):
     from rlrep_amd.envs.device import single_device_class
     E = int(args.num_envs)
     env = single_device_class(args.env)(agent, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps), num_envs=E)
-    evaluations = [agent.evaluate(env, args.eval_episodes)]
+    evaluate = functools.partial(agent.evaluate, env, args.eval_episodes)
+    ev.evaluations.append(evaluate())
     info = None
-    timer = util.Timer()
+    ev.timer = util.Timer()
     for t0 in range(0, int(args.max_timesteps), E):            # one iterate is E environment steps
         out = agent.iterate(env, replay, args.batch_size, train=t0 >= args.start_timesteps)
         info = out if out is not None else info
         t = t0 + E - 1
         if (t + 1) % args.eval_freq == 0:
-            sps = timer.steps_per_sec(t + 1)
-            evaluations.append(agent.evaluate(env, args.eval_episodes))
-            if info is not None:
-                row = {'step': t + 1, 'info/evaluation': float(evaluations[-1]), 'steps_per_sec': sps}
-                row.update({f'info/{k}': float(v) for k, v in info.items()})
-                jsonl.write(json.dumps(row) + '\n')
-                jsonl.flush()
-                if tb is not None:
-                    for k, v in row.items():
-                        if k.startswith('info/'):
-                            tb.add_scalar(k, v, t + 1)
-                    tb.flush()
-            print('Step {}. Steps per sec: {:.4g}.'.format(t + 1, sps))
-            if args.save_model:
-                agent.save(os.path.join(log_path, 'agent.pt'), env=env)
-    jsonl.close()
-    if tb is not None:
-        tb.close()
-    print('Total time cost {:.4g}s.'.format(timer.time_cost()))
-    return agent, evaluations
+            ev.step(t + 1, evaluate, info, env=env)
+    ev.close()
+    return agent, ev.evaluations
 
 
 def _log_root(args):
@@ -821,9 +742,53 @@ def halving_step(agent, scores, seeds, cfg, step, log):
     return out
 
 
+class _Evaluations(object):
+    """What run()'s five loops do at an evaluation step, and the files it needs: the metrics.jsonl row (mirrored to tensorboardX if it is
+    installed), the print, --save_model.  `evaluations` is the scores so far; a loop with an initial evaluation files it, and every loop
+    starts `timer` (util.Timer) where its first iteration begins."""
+
+    def __init__(self, args, agent, replay, log_path):
+        self.args, self.agent, self.replay, self.log_path = args, agent, replay, log_path
+        os.makedirs(log_path, exist_ok=True)
+        self.jsonl = open(os.path.join(log_path, 'metrics.jsonl'), 'a')
+        try:
+            from tensorboardX import SummaryWriter
+            self.tb = SummaryWriter(log_path)
+        except ImportError:
+            self.tb = None
+        self.evaluations, self.timer = [], None
+
+    def step(self, t, score, info, env=None):
+        """Step `t` was an evaluation step: score() runs the evaluation (behind the rate, so that steps_per_sec excludes it), info is the
+        latest train()'s (None before the first: no row), env the device environment a checkpoint carries."""
+        _per_anneal(self.args, self.replay, t)          # (a no-op where the loop cannot run with --per: --sim-graph and --device-loop refuse it)
+        sps = self.timer.steps_per_sec(t)
+        self.evaluations.append(score())
+        if info is not None:
+            row = {'step': t, 'info/evaluation': float(self.evaluations[-1]), 'steps_per_sec': sps}
+            row.update({f'info/{k}': float(v) for k, v in info.items()})
+            self.jsonl.write(json.dumps(row) + '\n')
+            self.jsonl.flush()
+            if self.tb is not None:
+                for k, v in row.items():
+                    if k.startswith('info/'):
+                        self.tb.add_scalar(k, v, t)
+                self.tb.flush()
+        print('Step {}. Steps per sec: {:.4g}.'.format(t, sps))
+        if self.args.save_model:
+            self.agent.save(os.path.join(self.log_path, 'agent.pt'), env=env)
+
+    def close(self):
+        self.jsonl.close()
+        if self.tb is not None:
+            self.tb.close()
+        print('Total time cost {:.4g}s.'.format(self.timer.time_cost()))
+
+
 class _GroupEvaluations(object):
-    """What run_seeds' two loops do at an evaluation step, and the files it needs: the members' metrics.jsonl rows, the print, the PBT step,
-    the halving step (and with it `live`), --save_model.  `evaluations[r]` is member r's scores so far; the loop files the initial ones."""
+    """What run_seeds' three loops do at an evaluation step, and the files it needs: the members' metrics.jsonl rows, the print, the PBT step,
+    the halving step (and with it `live`), --save_model.  `evaluations[r]` is member r's scores so far; the loop files the initial ones and
+    starts `timer` (util.Timer) where its first iteration begins."""
 
     def __init__(self, args, agent, seeds, logs, pbt_cfg, halving_cfg):
         self.args, self.agent, self.seeds, self.logs, self.root = args, agent, seeds, logs, _log_root(args)
@@ -834,12 +799,16 @@ class _GroupEvaluations(object):
             self.pbt_log = open(os.path.join(self.root, 'pbt.jsonl'), 'a')
         if halving_cfg is not None:
             self.halving_log = open(os.path.join(self.root, 'halving.jsonl'), 'a')
-        self.evaluations, self.live = None, agent.live
+        self.evaluations, self.live, self.timer = None, agent.live, None
 
-    def step(self, step, sps, scores, infos, env=None):
-        """Step `step` was an evaluation step: scores[r] is live member r's evaluation (a retired member's entry is not read), infos the
-        latest train()'s, env the device environment a checkpoint carries."""
+    def step(self, step, scores, infos, env=None):
+        """Step `step` was an evaluation step: scores() runs the evaluation (behind the rate, so that steps_per_sec excludes it) and
+        scores()[r] is live member r's (a retired member's entry is not read), infos the latest train()'s, env the device environment a
+        checkpoint carries."""
         args, agent, evaluations = self.args, self.agent, self.evaluations
+        _per_anneal(args, agent.replay, step)           # (a no-op where the loop cannot run with --group-per: --device-env refuses it)
+        sps = self.timer.steps_per_sec(step)
+        scores = scores()
         for r in range(agent.R):
             if not self.live[r]:
                 continue
@@ -865,6 +834,7 @@ class _GroupEvaluations(object):
     def close(self):
         for f in self.logs + [f for f in (self.pbt_log, self.halving_log) if f is not None]:
             f.close()
+        print('Total time cost {:.4g}s.'.format(self.timer.time_cost()))
 
 
 def run_seeds(args):
@@ -920,12 +890,16 @@ def run_seeds(args):
     if args.host_envs > 1:
         return _host_envs_group_loop(args, agent, replay, ev, seeds)
     policies = [_MemberPolicy(agent, r) for r in range(R)]
-    ev.evaluations = [[util.eval_policy(policies[r], evals_[r], args.eval_episodes)] for r in range(R)]
+
+    def evaluate():
+        return [util.eval_policy(policies[r], evals_[r], args.eval_episodes) if ev.live[r] else None for r in range(R)]
+
+    ev.evaluations = [[s] for s in evaluate()]
     states = np.stack([np.asarray(e.reset(), np.float32) for e in envs_])
     ep_steps = np.zeros(R, np.int64)
     infos = None
     staged = None                           # the rows of the last replay.add: a retired member's ring takes its last row again (nobody samples it)
-    timer = util.Timer()
+    ev.timer = util.Timer()
     for t in range(int(args.max_timesteps)):
         ep_steps += 1
         live = ev.live
@@ -960,12 +934,8 @@ def run_seeds(args):
         if t >= args.start_timesteps:
             infos = agent.train(replay, batch_size=args.batch_size)
         if (t + 1) % args.eval_freq == 0:
-            _per_anneal(args, replay, t + 1)
-            sps = timer.steps_per_sec(t + 1)
-            scores = [util.eval_policy(policies[r], evals_[r], args.eval_episodes) if live[r] else None for r in range(R)]
-            ev.step(t + 1, sps, scores, infos)
+            ev.step(t + 1, evaluate, infos)
     ev.close()
-    print('Total time cost {:.4g}s.'.format(timer.time_cost()))
     return agent, ev.evaluations
 
 
@@ -996,7 +966,7 @@ def _host_envs_group_loop(args, agent, replay, ev, seeds):
     states = np.stack([[np.asarray(e.reset(), np.float32) for e in member] for member in envs_])
     ep_steps = np.zeros((R, E), np.int64)
     infos = None
-    timer = util.Timer()
+    ev.timer = util.Timer()
     for t0 in range(0, int(args.max_timesteps), E):             # one iteration is E environment steps of every member
         ep_steps += 1
         warm = t0 < args.start_timesteps
@@ -1022,11 +992,8 @@ def _host_envs_group_loop(args, agent, replay, ev, seeds):
             infos = agent.train(replay, batch_size=args.batch_size)
         t = t0 + E
         if t % args.eval_freq == 0:
-            _per_anneal(args, replay, t)
-            sps = timer.steps_per_sec(t)
-            ev.step(t, sps, evaluate(), infos)
+            ev.step(t, evaluate, infos)
     ev.close()
-    print('Total time cost {:.4g}s.'.format(timer.time_cost()))
     return agent, ev.evaluations
 
 
@@ -1038,18 +1005,20 @@ def _device_loop(args, agent, replay, ev):
     from rlrep_amd.envs.device import device_class
     E = int(args.num_envs)
     env = device_class(args.env)(agent, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps), num_envs=E)
-    ev.evaluations = [[float(s)] for s in agent.evaluate(env, args.eval_episodes)]
+
+    def evaluate():
+        return [float(s) for s in agent.evaluate(env, args.eval_episodes)]
+
+    ev.evaluations = [[s] for s in evaluate()]
     infos = None
-    timer = util.Timer()
+    ev.timer = util.Timer()
     for t0 in range(0, int(args.max_timesteps), E):            # one iterate is E environment steps of every live member
         out = agent.iterate(env, replay, args.batch_size, train=t0 >= args.start_timesteps)
         infos = out if out is not None else infos
         t = t0 + E - 1
         if (t + 1) % args.eval_freq == 0:
-            sps = timer.steps_per_sec(t + 1)
-            ev.step(t + 1, sps, [float(s) for s in agent.evaluate(env, args.eval_episodes)], infos, env=env)
+            ev.step(t + 1, evaluate, infos, env=env)
     ev.close()
-    print('Total time cost {:.4g}s.'.format(timer.time_cost()))
     return agent, ev.evaluations
 
 
