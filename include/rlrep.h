@@ -460,10 +460,35 @@ int32_t rlrep_replay_gather_nstep(const float* ring_dev, const int32_t* idx_dev,
                                   void* stream);
 /* Read-back of a minibatch slot (tests and tools): which = 0 .. 5 -> XE [batch, 2 S + A], XF [batch, S + A], XF2 [batch, S + A], XFpi [batch, S + A],
  * R [batch], D [batch], dense, inside the agent's workspace; valid once the stream has passed the gather.  A group: member 0's (member m's lies
- * m member strides further).  NULL for a bad argument. */
+ * m member strides further).  which = 6 -> Rn [batch], the reward array the critic heads of the representation agents read: R itself (the
+ * same pointer) unless rlrep_set_critic_nstep gave it storage of its own, which lies OUTSIDE the workspace.  NULL for a bad argument. */
 const float* rlrep_slot_dev(rlrep_agent* agent, int32_t slot, int32_t which);
 int32_t rlrep_group_replay_gather_nstep(rlrep_agent* group, const float* rings_dev, int64_t ring_stride_bytes, const int32_t* idx_dev, int32_t idx_per_member,
                                         int32_t batch, int64_t max_size, const int32_t* size_dev, int32_t n, int32_t stride, void* stream);
+
+/* ---- n-step CRITIC targets for vlsac / ctrlsac / spedersac / diffsrsac (additive to ABI 4; DESIGN.md 6h, csrc/nstep_targets.hip) -------------
+ * The feature step of these agents models one-step dynamics from the same minibatch the critic and actor steps reuse, so the minibatch stays
+ * one-step where the feature step reads it (XE, XF, R) and only what the critic and actor steps read of the NEXT state and the return is
+ * replaced: XF2[:, 0:S] = s' of the chain's last row, D = 1 - gamma^(m-1) (1 - d_last), and a reward array of the heads' own, Rn = sum_k
+ * gamma^k r_k.  The walk, its stopping rules and its arithmetic are those of rlrep_replay_sample_nstep above, bit for bit.
+ *   rlrep_set_critic_nstep             on != 0: slot 0 (and every deferred set's snapshot) gets an Rn of its own -- one device allocation of the
+ *                                      agent's, the workspace layout stays what rlrep_layout reported -- and the step programs are rebuilt with
+ *                                      the critic heads reading it; on == 0: Rn is R again.  NOT stream-ordered: it synchronises the device,
+ *                                      call it outside any capture.  Until it is called every program, launch count and array is what it was.
+ *                                      Refuses, by name: a seed group's handle, sac (it has rlrep_replay_sample_nstep), world_size > 1.
+ *   rlrep_replay_sample_nstep_targets  ONE launch behind the rlrep_replay_sample (or the train prologue, or the optimizer launch that carried
+ *                                      the gather) of the slot-0 minibatch the critic reuses, in front of the feature step on it: overwrites
+ *                                      XF2[:, 0:S], Rn and D of slot 0, gamma = the agent's discount; leaves XE, XF, XFpi, R and columns
+ *                                      [S, S + A) of XF2.  Never skipped.  Refuses what rlrep_set_critic_nstep refuses, slot != 0, n outside
+ *                                      [1, RLREP_NSTEP_MAX], stride < 1, and an agent rlrep_set_critic_nstep(agent, 1) was not called on.
+ *   rlrep_replay_gather_nstep_targets  the same three arrays into caller-owned memory, no agent: xf2 [batch, S + A] (columns [0, S) written),
+ *                                      rn [batch], d [batch].
+ * An index outside [0, max_size) writes zeros.  Not built: prioritized replay for these agents, seed groups, data parallel. */
+int32_t rlrep_set_critic_nstep(rlrep_agent* agent, int32_t on);
+int32_t rlrep_replay_sample_nstep_targets(rlrep_agent* agent, int32_t slot, const float* ring_dev, const int32_t* idx_dev, int32_t batch, int64_t max_size,
+                                          const int32_t* size_dev, int32_t n, int32_t stride, void* stream);
+int32_t rlrep_replay_gather_nstep_targets(const float* ring_dev, const int32_t* idx_dev, int32_t batch, int32_t S, int32_t A, int64_t max_size,
+                                          const int32_t* size_dev, int32_t n, int32_t stride, float gamma, float* xf2_dev, float* rn_dev, float* d_dev, void* stream);
 
 /* ---- metrics ------------------------------------------------------------------------------ */
 /* device float array of n_metrics slots, valid after the stream has passed the producing step */

@@ -181,6 +181,9 @@ def _load():
         'rlrep_replay_gather_nstep': (i32, [vp, vp, i32, i32, i32, i64, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]),
         'rlrep_group_replay_gather_nstep': (i32, [vp, vp, i64, vp, i32, i32, i64, vp, i32, i32, vp]),
         'rlrep_slot_dev': (vp, [vp, i32, i32]),
+        'rlrep_set_critic_nstep': (i32, [vp, i32]),
+        'rlrep_replay_sample_nstep_targets': (i32, [vp, i32, vp, vp, i32, i64, vp, i32, i32, vp]),
+        'rlrep_replay_gather_nstep_targets': (i32, [vp, vp, i32, i32, i32, i64, vp, i32, i32, f32, vp, vp, vp, vp]),
         'rlrep_images_managed': (i32, [vp, i32]),
         'rlrep_refresh_images': (i32, [vp, vp]),
         'rlrep_feature_chain_next': (i32, [vp]),

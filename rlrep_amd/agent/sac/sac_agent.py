@@ -466,6 +466,7 @@ class SACAgent(object):
         """A prioritized buffer trains ONE sac agent on ONE GPU; everything else refuses it by its class name, before anything is launched."""
         name, cls = type(self).__name__, type(buffer).__name__
         self._check_nstep(buffer, what)
+        self._check_critic_nstep(buffer, what)
         if getattr(buffer, 'prioritized_group', False):
             raise RuntimeError(f'{name}.{what}: {cls} is built for SACSeedBatch.train (a sac seed group); a single agent takes a '
                                'PrioritizedReplayBuffer')
@@ -497,6 +498,54 @@ class SACAgent(object):
                                'one-step dynamics and their critic reuses its minibatch): use n_step=1')
         if self.world_size > 1 or self._dp:
             raise RuntimeError(f'{name}.{what}: {cls}(n_step={n}) does not train a data-parallel agent (one agent, one GPU)')
+
+    # ---- n-step critic targets of the representation agents (ReplayBuffer(critic_n_step=, n_stride=); DESIGN.md 6h, csrc/nstep_targets.hip) ----
+    SEED_GROUP = False        # (agent/seed_batch.py SeedBatchMixin: True)
+
+    @staticmethod
+    def _critic_nstep(buffer):
+        return int(getattr(buffer, 'critic_n_step', 1))
+
+    def _check_critic_nstep(self, buffer, what):
+        """A critic_n_step buffer trains ONE vlsac / ctrlsac / spedersac / diffsrsac agent on ONE GPU; everything else refuses it by its class
+        name and critic_n_step, before anything is launched."""
+        n = self._critic_nstep(buffer)
+        if n <= 1:
+            return
+        name, cls = type(self).__name__, type(buffer).__name__
+        if self.SEED_GROUP:
+            raise RuntimeError(f'{name}.{what}: {cls}(critic_n_step={n}) does not train a seed group (n-step critic targets are built for one agent)')
+        if self.ALG == 'sac':
+            raise RuntimeError(f'{name}.{what}: {cls}(critic_n_step={n}) is built for the representation agents (vlsac, ctrlsac, spedersac, diffsrsac), '
+                               'whose feature step keeps the one-step rows; a sac agent owns its whole minibatch: use n_step')
+        if self.world_size > 1 or self._dp:
+            raise RuntimeError(f'{name}.{what}: {cls}(critic_n_step={n}) does not train a data-parallel agent (one agent, one GPU)')
+
+    def _ensure_critic_nstep(self, buffer):
+        """Outside any capture, before the programs run for `buffer`: the critic heads read a reward array of their own exactly when the buffer
+        carries critic_n_step > 1 (rlrep_set_critic_nstep rebuilds the step programs, so every cached graph goes when the setting changes)."""
+        on = self._critic_nstep(buffer) > 1
+        if on == getattr(self, '_cn_on', False):
+            return
+        self.flush()
+        self.core.set_critic_nstep(on)
+        self._cn_on = on
+        self._graph, self._pipe, self._pending = None, None, False
+        for cache in ('_iter_graphs', '_sim_graphs'):
+            self.__dict__.get(cache, {}).clear()
+        self._img_dirty = True
+
+    def _critic_key(self, B):
+        """The index key of the slot-0 minibatch the critic and actor steps reuse: the last one of _plan()."""
+        return self._plan(B)[0][-1]
+
+    def _gather_critic_targets(self, buffer, slot, key, idx, B):
+        """Directly behind the gather of minibatch `key`: if it is the one the critic reuses and the buffer asks for n-step critic targets,
+        the one launch that overwrites XF2[:, :S], Rn and D of slot 0 -- in front of the feature step on it, of the policy forwards
+        rlrep_prefetch_policy_early arms and of the optimizer launch that takes the deferred chain's snapshot."""
+        n = self._critic_nstep(buffer)
+        if n > 1 and slot == 0 and self._feature_iters() > 0 and key == self._critic_key(B):
+            self.core.sample_nstep_targets(buffer.ring, idx, B, buffer.max_size, buffer.size_dev(), n, buffer.n_stride)
 
     def _gather(self, buffer, slot, idx, B):
         """The gather of rows idx[0:B] into minibatch slot `slot`: the plain copy, or for an n-step buffer the chain-following gather (one
@@ -638,6 +687,7 @@ class SACAgent(object):
             raise RuntimeError(f'{name}.iterate_sim: {cls} cannot be written by the captured simulator loop (its append launch does not write the '
                                'priority tree): use a plain ReplayBuffer, or the eager act_device / add_device / train() loop')
         self._check_nstep(buffer, 'iterate_sim')
+        self._check_critic_nstep(buffer, 'iterate_sim')
         self._check_front('iterate_sim', loop, buffer, 'simulator loop', 'create the SimLoop after load()', lacks='captured simulator loop')
         N = int(loop.num_envs)
         if N > buffer.max_size:
@@ -905,6 +955,7 @@ class SACAgent(object):
             return self._sample_into_per(buffer, B, key, g)
         if self._inject is None and self._pool is not None and ('idx_' + key) in self._pool:
             self._gather(buffer, slot, self._pool['idx_' + key], B)
+            self._gather_critic_targets(buffer, slot, key, self._pool['idx_' + key], B)
             nxt = self._next_key.get(key)
             if nxt is not None:
                 armed = self.core.prefetch_batch(buffer.ring, self._pool['idx_' + nxt], B, slot)
@@ -925,6 +976,7 @@ class SACAgent(object):
         else:
             idx = self._indices(key, B, buffer.size)
         self._gather(buffer, slot, idx, B)
+        self._gather_critic_targets(buffer, slot, key, idx, B)
 
     def _early_key_for(self, key):
         """The key of the minibatch whose feature step will carry both policy forwards (rlrep_prefetch_policy_early), as far as it is
@@ -1067,6 +1119,7 @@ class SACAgent(object):
         self.flush()
         buffer.flush()
         self._img_dirty = True
+        self._ensure_critic_nstep(buffer)
         self._inject = dict(idx=list(idx), eps=list(eps))
         try:
             self._body(buffer, batch_size, False)
@@ -1078,6 +1131,7 @@ class SACAgent(object):
         self.flush()
         buffer.flush()
         self._img_dirty = True
+        self._ensure_critic_nstep(buffer)
         self._body(buffer, B, False)
         return self.core.info()
 
@@ -1106,6 +1160,7 @@ class SACAgent(object):
         """Before a capture that holds a train(): size the library's tables for B and allocate the two pools outside it (_capture_prologue
         says why); before any capture: let the device finish."""
         if train:
+            self._ensure_critic_nstep(buffer)
             self._warm(buffer, B)
             ni, ne = self._pool_sizes(B)
             self._buf('pool_idx', (ni,), torch.int32)
@@ -1411,6 +1466,8 @@ class SACAgent(object):
         key = key if per is None else key + per()
         if int(getattr(buffer, 'n_step', 1)) > 1:           # (an n-step buffer: the chain length and the successor distance are kernel arguments)
             key = key + buffer.nstep_key()
+        if int(getattr(buffer, 'critic_n_step', 1)) > 1:    # (n-step critic targets: the same two kernel arguments, and other step programs)
+            key = key + buffer.cnstep_key()
         return key
 
     def _hook_buffer(self, buffer):

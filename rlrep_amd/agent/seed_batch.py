@@ -107,6 +107,7 @@ class SeedBatchMixin(object):
     # rlrep_group_set_member_hyper) or what only initialisation uses (alpha)
     SWEEP_KEYS = ('lr', 'discount', 'tau', 'alpha', 'target_update_period', 'auto_entropy_tuning')
     PREFETCH_POLICY_EARLY = False         # no group form of rlrep_prefetch_policy_early (the library refuses it)
+    SEED_GROUP = True                     # (SACAgent._check_critic_nstep: n-step critic targets are built for one agent)
 
     @classmethod
     def _agent_class(cls):

@@ -63,6 +63,10 @@ class SPEDERSACAgent(SACAgent):
             keys += [f'f{i}a', f'f{i}b']
         return keys, [('crit', (B, self.action_dim)), ('act', (B, self.action_dim))]
 
+    def _critic_key(self, B):
+        # the critic and actor steps reuse slot 0 of the last pair
+        return self._plan(B)[0][-2]
+
     def _prefetch_chain(self, idx_keys):
         # two chains, one per slot: f{i}a -> f{i+1}a (slot 0), f{i}b -> f{i+1}b (slot 1): both gathers of the next feature step ride in this
         # step's optimizer launch (rlrep_prefetch_batch_slot); the critic / actor steps reuse the last pair

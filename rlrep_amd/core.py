@@ -289,6 +289,27 @@ class HipCore:
         check(lib.rlrep_replay_sample_nstep(self.h, 0, _ptr(ring), _ptr(idx), int(batch), int(max_size), _ptr(size_dev), int(n), int(stride), _stream()),
               'replay_sample_nstep')
 
+    def set_critic_nstep(self, on):
+        """The critic heads read a reward array of their own (rlrep_set_critic_nstep): synchronises and rebuilds the step programs when the
+        setting changes -- outside any capture."""
+        check(lib.rlrep_set_critic_nstep(self.h, 1 if on else 0), 'set_critic_nstep')
+
+    def sample_nstep_targets(self, ring, idx, batch, max_size, size_dev, n, stride):
+        """The n-step target gather behind sample(0, ...) of the minibatch the critic reuses (csrc/nstep_targets.hip): XF2[:, :S], Rn, D."""
+        check(lib.rlrep_replay_sample_nstep_targets(self.h, 0, _ptr(ring), _ptr(idx), int(batch), int(max_size), _ptr(size_dev), int(n), int(stride),
+                                                    _stream()), 'replay_sample_nstep_targets')
+
+    def slot_array(self, slot, which, n):
+        """float32[n] view of array `which` of minibatch slot `slot` (rlrep_slot_dev: 0 .. 6 = XE, XF, XF2, XFpi, R, D, Rn), for read-back by
+        tests and tools: library memory, valid until the step programs are rebuilt."""
+        ptr = lib.rlrep_slot_dev(self.h, int(slot), int(which))
+        if not ptr:
+            raise ValueError(f'slot_array: no array {which} of slot {slot}')
+
+        class _Dev:
+            __cuda_array_interface__ = dict(shape=(int(n),), typestr='<f4', data=(int(ptr), False), version=2)
+        return torch.as_tensor(_Dev(), device=self.device)
+
     def prefetch_batch(self, ring, idx, batch, slot=0):
         """Arm the gather of the next minibatch of `slot` to ride in the next optimizer launch."""
         rc = lib.rlrep_prefetch_batch_slot(self.h, int(slot), _ptr(ring), _ptr(idx), int(batch))

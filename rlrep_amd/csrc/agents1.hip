@@ -732,7 +732,7 @@ void build_vlsac(Builder& b, rlrep_agent* ag) {
         // quirk Q2: BOTH heads end in l3 (l6 is dead)
         q.wt[0] = q.wt[1] = Tw("critic_target.l3.weight"); q.bt[0] = q.bt[1] = Tw("critic_target.l3.bias");
         q.wc[0] = q.wc[1] = Pw("critic.l3.weight"); q.bc[0] = q.bc[1] = Pw("critic.l3.bias");
-        q.logp = ab.logp; q.R = s0.R; q.D = s0.D; q.alpha_state = ag->a.alpha_state_dev; q.gamma = ag->h.discount;
+        q.logp = ab.logp; q.R = s0.Rn; q.D = s0.D; q.alpha_state = ag->a.alpha_state_dev; q.gamma = ag->h.discount;      // (Rn: s0.R unless rlrep_set_critic_nstep)
         q.inv_batch = ag->inv_batch(); q.dq = dq; q.GE[0] = GE; q.GE[1] = GE + BH; q.partial = part_q;
         q.B = B; q.H = H; q.nblk = nblk; q.train = 1; q.step = ag->adam_step + 1;
         p.stages.push_back({[=](hipStream_t st) { return rl_launch_qhead_critic(&q, st); }, "qhead critic"});
@@ -846,6 +846,8 @@ Slot defer_begin(Builder& b, rlrep_agent* ag, int set, const char* prefix, const
     Slot& s0 = ag->slot[0];
     rlrep_agent::DeferSet& D = ag->dset[set];
     Slot d; d.XE = nullptr; d.XF = ws.f((size_t)B * SA); d.XF2 = ws.f((size_t)B * SA); d.XFpi = ws.f((size_t)B * SA); d.R = ws.f(B); d.D = ws.f(B);
+    const bool own_rn = s0.Rn != s0.R && ag->cn_block;                  // n-step critic targets: the heads' reward array is snapshotted too
+    d.Rn = own_rn ? ag->cn_block + (1 + set) * ag->cn_stride : d.R;
     D.slot = d;
     D.block = block_n > 0 ? ws.f((size_t)block_n) : nullptr;
     D.eps = ws.f((size_t)2 * B * A); D.steps = (int*)ws.alloc(sizeof(int) * 4);
@@ -854,12 +856,13 @@ Slot defer_begin(Builder& b, rlrep_agent* ag, int set, const char* prefix, const
     auto seg = [&](const float* src, float* dst, long long cnt) { cs.src[n] = src; cs.dst[n] = dst; end += cnt; cs.end[n] = end; ++n; };
     seg(s0.XF, d.XF, (long long)B * SA); seg(s0.XF2, d.XF2, (long long)B * SA); seg(s0.XFpi, d.XFpi, (long long)B * SA);
     seg(s0.R, d.R, B); seg(s0.D, d.D, B);
+    if (own_rn) seg(s0.Rn, d.Rn, B);                                    // (9 of COPY_MAX_SEGS = 10 segments at the most)
     if (block_n > 0) seg(block_src, D.block, block_n);
     seg(nullptr, D.eps, (long long)B * A);                             // critic-step policy noise (patched per call)
     seg(nullptr, D.eps ? D.eps + (size_t)B * A : nullptr, (long long)B * A);   // actor-step policy noise
     cs.n = n; cs.isrc = ag->steps; cs.idst = D.steps;
     const Slot keep = s0;
-    s0.XF = d.XF; s0.XF2 = d.XF2; s0.XFpi = d.XFpi; s0.R = d.R; s0.D = d.D;
+    s0.XF = d.XF; s0.XF2 = d.XF2; s0.XFpi = d.XFpi; s0.R = d.R; s0.D = d.D; s0.Rn = d.Rn;
     ag->ov_base = b.dry ? nullptr : D.block; ag->ov_prefix = prefix; ag->ov_first = first;      // the dry pass only sizes the workspace
     ag->dcur = set;
     b.low_prio = true;

@@ -151,7 +151,7 @@ static void qhead_critic_stage(Program& p, rlrep_agent* ag, const float* Et0, co
     QHeadCritic q; memset(&q, 0, sizeof(q));
     q.Et[0] = Et0; q.Et[1] = Et1; q.Ec[0] = Ec0; q.Ec[1] = Ec1; q.ldE = ldE;
     q.wt[0] = wt0; q.wt[1] = wt1; q.bt[0] = bt0; q.bt[1] = bt1; q.wc[0] = wc0; q.wc[1] = wc1; q.bc[0] = bc0; q.bc[1] = bc1;
-    q.logp = logp; q.R = ag->slot[0].R; q.D = ag->slot[0].D; q.alpha_state = ag->a.alpha_state_dev; q.gamma = ag->h.discount;
+    q.logp = logp; q.R = ag->slot[0].Rn; q.D = ag->slot[0].D; q.alpha_state = ag->a.alpha_state_dev; q.gamma = ag->h.discount;      // (Rn: slot[0].R unless rlrep_set_critic_nstep)
     q.inv_batch = ag->inv_batch(); q.dq = dq; q.GE[0] = GE0; q.GE[1] = GE1; q.partial = part_q;
     q.B = ag->B; q.H = H; q.nblk = nblk; q.train = train; q.step = train ? ag->adam_step + 1 : nullptr;
     p.stages.push_back({[=](hipStream_t st) { return rl_launch_qhead_critic(&q, st); }, "qhead critic"});

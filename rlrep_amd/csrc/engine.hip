@@ -145,6 +145,7 @@ static int build_programs(rlrep_agent* ag, int B) {
             s.XE = XE ? XE + (size_t)i * B * (2 * S + A) : nullptr;
             s.XF = XF ? XF + (size_t)i * B * (S + A) : nullptr;
             s.XF2 = b.ws.f((size_t)B * (S + A)); s.XFpi = b.ws.f((size_t)B * (S + A)); s.R = b.ws.f(B); s.D = b.ws.f(B); s.filled = false;
+            s.Rn = (i == 0 && ag->critic_nstep && ag->cn_block) ? ag->cn_block : s.R;          // (the critic heads read slot 0 only)
         }
     }
     switch (ag->d.alg) {
@@ -419,6 +420,7 @@ int32_t rlrep_agent_create(const rlrep_dims* dims, const rlrep_hyper* hyper, con
 void rlrep_agent_destroy(rlrep_agent* agent) {
     if (agent && agent->grp_seeds) (void)hipFree(agent->grp_seeds);
     if (agent && agent->grp_live) (void)hipFree(agent->grp_live);
+    if (agent && agent->cn_block) (void)hipFree(agent->cn_block);
     delete agent;
 }
 
@@ -438,6 +440,10 @@ int32_t rlrep_set_batch(rlrep_agent* ag, int32_t slot, const rlrep_batch* bt, vo
     s.filled = true;
     rc = (++g_rl_launches, rl_launch_fill_slot(&p, (hipStream_t)stream));
     if (rc) { rl_set_error("fill_slot: hip error %d", rc); return RLREP_ERR_HIP; }
+    if (s.Rn != s.R && s.Rn && bt->reward_dev) {           // (rlrep_set_critic_nstep: a caller's batch is what it is -- the critic heads read its rewards)
+        const hipError_t e = hipMemcpyAsync(s.Rn, bt->reward_dev, sizeof(float) * (size_t)ag->B, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+        if (e != hipSuccess) { rl_set_error("set_batch: %s", hipGetErrorString(e)); return RLREP_ERR_HIP; }
+    }
     return 0;
 }
 
@@ -644,11 +650,71 @@ int32_t rlrep_replay_gather_nstep(const float* ring_dev, const int32_t* idx_dev,
     return 0;
 }
 
-// the six arrays of minibatch slot `slot` (which = 0 .. 5: XE, XF, XF2, XFpi, R, D), for read-back by tests and tools; a group: member 0's
+// ---- n-step critic targets of the representation agents (nstep_targets.hip) ----------------------------------------------------
+// on: the critic heads of vlsac / ctrlsac / spedersac / diffsrsac read a reward array of their own (Slot::Rn), which
+// rlrep_replay_sample_nstep_targets fills; the feature programs keep reading R.  Outside any capture: allocates (once) and rebuilds the programs.
+int32_t rlrep_set_critic_nstep(rlrep_agent* ag, int32_t on) {
+    if (!ag) { rl_set_error("set_critic_nstep: null agent"); return RLREP_ERR_ARG; }
+    if (ag->members > 0) { rl_set_error("set_critic_nstep: not available on a seed group (rlrep_group_create): n-step critic targets are built for one agent"); return RLREP_ERR_ARG; }
+    if (ag->d.alg == RLREP_ALG_SAC) { rl_set_error("set_critic_nstep: sac has n_step (rlrep_replay_sample_nstep): its critic owns the whole minibatch"); return RLREP_ERR_ARG; }
+    if (ag->h.world_size > 1) { rl_set_error("set_critic_nstep: n-step critic targets run on one GPU (world_size = %d)", ag->h.world_size); return RLREP_ERR_ARG; }
+    const bool want = on != 0;
+    if (want == ag->critic_nstep) return 0;
+    hipError_t e = hipDeviceSynchronize();                 // (the programs are rebuilt with blocking table uploads, as when the batch size changes)
+    if (e != hipSuccess) { rl_set_error("set_critic_nstep: %s", hipGetErrorString(e)); return RLREP_ERR_HIP; }
+    if (want && !ag->cn_block) {
+        const size_t bytes = sizeof(float) * (size_t)(((long long)ag->d.max_batch + 63) & ~63ll) * (1 + rlrep_agent::NSETS);
+        float* block = nullptr;
+        e = hipMalloc((void**)&block, bytes);
+        if (e != hipSuccess) { rl_set_error("set_critic_nstep: %s", hipGetErrorString(e)); return RLREP_ERR_NOMEM; }
+        e = hipMemset(block, 0, bytes);
+        if (e != hipSuccess) { (void)hipFree(block); rl_set_error("set_critic_nstep: %s", hipGetErrorString(e)); return RLREP_ERR_HIP; }
+        ag->cn_block = block; ag->cn_stride = ((long long)ag->d.max_batch + 63) & ~63ll;
+    }
+    ag->critic_nstep = want;
+    return ag->B > 0 ? build_programs(ag, ag->B) : 0;
+}
+// The target gather behind rlrep_replay_sample(slot 0) of the minibatch the critic and actor steps reuse: XF2[:, 0:S], Rn and D of slot 0 become
+// the n-step ones (discount = the agent's); XE, XF, XFpi and R -- what the feature step reads -- stay.  Never skipped.
+int32_t rlrep_replay_sample_nstep_targets(rlrep_agent* ag, int32_t slot, const float* ring_dev, const int32_t* idx_dev, int32_t batch, int64_t max_size,
+                                          const int32_t* size_dev, int32_t n, int32_t stride, void* stream) {
+    const char* what = "replay_sample_nstep_targets";
+    if (!ag) { rl_set_error("%s: null agent", what); return RLREP_ERR_ARG; }
+    if (ag->members > 0) { rl_set_error("%s: not available on a seed group (rlrep_group_create): n-step critic targets are built for one agent", what); return RLREP_ERR_ARG; }
+    if (ag->d.alg == RLREP_ALG_SAC) { rl_set_error("%s: sac takes rlrep_replay_sample_nstep (its critic owns the whole minibatch)", what); return RLREP_ERR_ARG; }
+    if (ag->h.world_size > 1) { rl_set_error("%s: n-step critic targets run on one GPU (world_size = %d)", what, ag->h.world_size); return RLREP_ERR_ARG; }
+    if (slot != 0) { rl_set_error("%s: slot %d (the critic and actor steps read slot 0)", what, slot); return RLREP_ERR_ARG; }
+    if (int rc = nstep_args_ok(what, ring_dev, idx_dev, batch, max_size, size_dev, n, stride)) return rc;
+    if (!ag->critic_nstep || ag->slot[0].Rn == ag->slot[0].R) { rl_set_error("%s: rlrep_set_critic_nstep(agent, 1) has not been called (the critic heads still read R)", what); return RLREP_ERR_STATE; }
+    if (batch != ag->B || !ag->slot[0].filled) { rl_set_error("%s: batch %d behind no rlrep_replay_sample of that size (slot 0 holds %d rows)", what, batch, ag->slot[0].filled ? ag->B : 0); return RLREP_ERR_STATE; }
+    ag->early_ready_crit = nullptr;                        // (a policy forward on the one-step s' that already ran is stale; one that is armed runs behind this launch)
+    const Slot& s = ag->slot[0];
+    NStepTargets p; memset(&p, 0, sizeof(p));
+    p.ring = ring_dev; p.idx = idx_dev; p.XF2 = s.XF2; p.Rn = s.Rn; p.D = s.D; p.size_dev = size_dev; p.capacity = max_size;
+    p.B = ag->B; p.S = ag->d.state_dim; p.A = ag->d.action_dim; p.n = n; p.stride = stride; p.gamma = ag->h.discount;
+    const int rc = (++g_rl_launches, rl_launch_nstep_targets(&p, (hipStream_t)stream));
+    if (rc) { rl_set_error("%s: hip error %d", what, rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+// the same gather into caller-owned arrays, no agent: xf2 [batch, S + A] (columns [0, S) written), rn [batch], d [batch]
+int32_t rlrep_replay_gather_nstep_targets(const float* ring_dev, const int32_t* idx_dev, int32_t batch, int32_t S, int32_t A, int64_t max_size,
+                                          const int32_t* size_dev, int32_t n, int32_t stride, float gamma, float* xf2_dev, float* rn_dev, float* d_dev, void* stream) {
+    const char* what = "replay_gather_nstep_targets";
+    if (int rc = nstep_args_ok(what, ring_dev, idx_dev, batch, max_size, size_dev, n, stride)) return rc;
+    if (S < 1 || A < 1 || !xf2_dev || !rn_dev || !d_dev) { rl_set_error("%s: bad argument (S %d, A %d, or a null output)", what, S, A); return RLREP_ERR_ARG; }
+    NStepTargets p; memset(&p, 0, sizeof(p));
+    p.ring = ring_dev; p.idx = idx_dev; p.XF2 = xf2_dev; p.Rn = rn_dev; p.D = d_dev; p.size_dev = size_dev; p.capacity = max_size;
+    p.B = batch; p.S = S; p.A = A; p.n = n; p.stride = stride; p.gamma = gamma;
+    const int rc = (++g_rl_launches, rl_launch_nstep_targets(&p, (hipStream_t)stream));
+    if (rc) { rl_set_error("%s: hip error %d", what, rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+
+// the arrays of minibatch slot `slot` (which = 0 .. 6: XE, XF, XF2, XFpi, R, D, Rn), for read-back by tests and tools; a group: member 0's
 const float* rlrep_slot_dev(rlrep_agent* ag, int32_t slot, int32_t which) {
-    if (!ag || slot < 0 || slot > 1 || which < 0 || which > 5) return nullptr;
+    if (!ag || slot < 0 || slot > 1 || which < 0 || which > 6) return nullptr;
     const Slot& s = ag->slot[slot];
-    const float* const arr[6] = {s.XE, s.XF, s.XF2, s.XFpi, s.R, s.D};
+    const float* const arr[7] = {s.XE, s.XF, s.XF2, s.XFpi, s.R, s.D, s.Rn};
     return arr[which];
 }
 

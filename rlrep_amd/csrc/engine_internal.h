@@ -4,7 +4,9 @@
 #include "group.h"
 #include <deque>
 
-struct Slot { float *XE, *XF, *XF2, *XFpi, *R, *D; bool filled = false; };
+// Rn: the reward array the critic heads of the representation agents read.  Rn == R (the same pointer, nothing allocated) unless
+// rlrep_set_critic_nstep gave it storage of its own, which the n-step target gather (nstep_targets.hip) then fills; feature programs read R
+struct Slot { float *XE, *XF, *XF2, *XFpi, *R, *D, *Rn = nullptr; bool filled = false; };
 
 struct Exchange { int after_stage; int kind; float* ptr; int64_t count; int64_t local_off; };
 
@@ -24,6 +26,10 @@ struct rlrep_agent {
     int B = 0;
     int* steps = nullptr; GroupCfg* adam_step = nullptr; float* metrics = nullptr; float* obs_in = nullptr; float* act_out = nullptr;
     Slot slot[2];
+    // n-step critic targets (rlrep_set_critic_nstep): critic_nstep = slot 0 and every deferred set's snapshot carry an Rn of
+    // their own, cut from cn_block (a device allocation of this agent, [1 + NSETS] arrays of cn_stride floats; the workspace layout is what
+    // rlrep_layout reported, with or without it)
+    bool critic_nstep = false; float* cn_block = nullptr; long long cn_stride = 0;
     // per-call dynamic inputs, read by the by-value parameter blocks at launch time
     const float* cur_eps = nullptr; const int* cur_idx = nullptr;
     Program feat_bwd, feat_apply, critic_bwd, critic_apply, actor_bwd, actor_apply, upd_target, infer, sync_prog;

@@ -138,6 +138,9 @@ struct PerUpdate { float* tree; float* scal; const int* idx; const float* td; lo
 // n-step returns (nstep.hip): the gather that follows each sampled row's trajectory forward through the ring.  fill: the ring,
 // idx[B] and the slot buffers as fill_slot_kernel takes them; row i's successor candidate is row (i + stride) mod capacity
 struct NStepGather { SlotFill fill; const int* size_dev; long long capacity; int n, stride; float gamma; };
+// n-step CRITIC targets of the representation agents (nstep_targets.hip): the same walk, writing only what the critic and actor
+// steps read of the chain -- XF2[b, 0:S] = s' of its last row (ld = S + A; columns [S, S + A) stay), Rn[b] = R, D[b] = 1 - g (1 - d)
+struct NStepTargets { const float* ring; const int* idx; float* XF2; float* Rn; float* D; const int* size_dev; long long capacity; int B, S, A, n, stride; float gamma; };
 
 struct QHeadActor {
     const float* Ec[2]; const float* wc[2]; const float* bc[2];

@@ -91,6 +91,8 @@ int rl_launch_qhead_critic_w_grp(const QHeadCriticW* p, hipStream_t st);
 // ---- nstep.hip (n-step returns: the chain-following replay gather, one wave per sample) ----
 int rl_launch_nstep_gather(const NStepGather* p, hipStream_t st);
 int rl_launch_nstep_gather_grp(const NStepGather* p, int idx_rows, hipStream_t st);       // grid (x, R); idx_rows == 0: the indices move by the member stride, else int32[R, idx_rows]
+// ---- nstep_targets.hip (n-step critic targets of the representation agents: the same walk, writing XF2[:, 0:S], Rn and D only) ----
+int rl_launch_nstep_targets(const NStepTargets* p, hipStream_t st);
 // ---- replearn.hip ----
 int rl_replearn_init();
 int rl_launch_infonce(const InfoNce* p, hipStream_t st);

@@ -172,8 +172,14 @@ def run(argv=None):
     p.add_argument('--n-stride', default=None, type=int,
                    help='the distance between a ring row and its successor (with --n-step): the number of environments whose transitions interleave '
                         'in the ring.  Default: what the chosen loop writes (--host-envs E: E, --torch-envs N: N, --num-envs E: E, else 1)')
+    p.add_argument('--critic-n-step', default=1, type=int,
+                   help='n-step critic targets (--alg vlsac, ctrlsac, spedersac or diffsrsac; 1..16, default 1 = one-step targets): the critic and '
+                        'actor steps of train() bootstrap from rows gathered up to N steps forward through the replay ring, while the feature step '
+                        'keeps training on the one-step rows of the same minibatch.  --n-stride as for --n-step.  One agent, one GPU; goes with '
+                        '--host-envs, --torch-envs (--sim-graph) and --device-loop --num-envs; not with --seeds / --sweep, --per or --n-step')
     args = p.parse_args(argv)
     _check_nstep(args)
+    _check_critic_nstep(args)
     _check_group_per(args)
     _check_per(args)
     _check_num_envs(args)
@@ -252,10 +258,42 @@ def _nstep_stride(args):
     return 1
 
 
+def _check_device_stride(args):
+    """the stride rule of the device loops, for --n-step and --critic-n-step alike: a device environment writes --num-envs rows per step"""
+    E = int(getattr(args, 'num_envs', 1))
+    if (getattr(args, 'device_loop', False) or getattr(args, 'device_env', False)) and _nstep_stride(args) != E:
+        raise SystemExit(f'--n-stride {_nstep_stride(args)}: a device environment interleaves --num-envs {E} trajectories in the ring; the stride must be {E}')
+
+
 def _nstep_kw(args):
     """the n-step keywords of the replay buffer classes (nothing without --n-step: the buffers are built as before)"""
-    n = int(getattr(args, 'n_step', 1))
+    n, cn = int(getattr(args, 'n_step', 1)), int(getattr(args, 'critic_n_step', 1))
+    if cn > 1:
+        return dict(critic_n_step=cn, n_stride=_nstep_stride(args))
     return dict(n_step=n, n_stride=_nstep_stride(args)) if n > 1 else {}
+
+
+def _check_critic_nstep(args):
+    """--critic-n-step: SystemExit, before anything touches the GPU, on what n-step critic targets do not run with (an argument namespace
+    without the attribute -- built by hand -- is a run without it)"""
+    cn = int(getattr(args, 'critic_n_step', 1))
+    if not 1 <= cn <= 16:
+        raise SystemExit(f'--critic-n-step {cn}: n-step critic targets take 1..16 steps')
+    if cn == 1:
+        return
+    if args.alg == 'sac':
+        raise SystemExit(f'--critic-n-step {cn}: a sac agent owns its whole minibatch: give --n-step {cn} (--critic-n-step is for --alg vlsac, '
+                         'ctrlsac, spedersac and diffsrsac, whose feature step keeps the one-step rows)')
+    if args.alg not in ('vlsac', 'ctrlsac', 'spedersac', 'diffsrsac'):
+        raise SystemExit(f'--critic-n-step {cn}: built for --alg vlsac, ctrlsac, spedersac and diffsrsac (got --alg {args.alg})')
+    if int(getattr(args, 'n_step', 1)) > 1:
+        raise SystemExit('--critic-n-step: not together with --n-step (a replay buffer trains one kind of agent)')
+    for flag, given in (('--seeds', getattr(args, 'seeds', None) is not None), ('--sweep', bool(getattr(args, 'sweep', None))),
+                        ('--per', getattr(args, 'per', False)), ('--group-per', getattr(args, 'group_per', False)),
+                        ('--device-env', getattr(args, 'device_env', False))):
+        if given:
+            raise SystemExit(f'--critic-n-step {cn}: not with {flag} (n-step critic targets are built for one agent and a plain replay buffer)')
+    _check_device_stride(args)
 
 
 def _check_nstep(args):
@@ -267,15 +305,13 @@ def _check_nstep(args):
     if stride is not None and int(stride) < 1:
         raise SystemExit(f'--n-stride {stride}: the distance between a ring row and its successor must be >= 1')
     if n == 1:
-        if stride is not None:
+        if stride is not None and int(getattr(args, 'critic_n_step', 1)) <= 1:      # (--critic-n-step N shares --n-stride)
             raise SystemExit('--n-stride: it is the successor distance of n-step returns: give --n-step N (N > 1) with it')
         return
     if args.alg != 'sac':
         raise SystemExit(f'--n-step {n}: n-step returns are built for --alg sac (got --alg {args.alg}: the feature step of the representation agents '
                          'models one-step dynamics and their critic reuses its minibatch)')
-    E = int(getattr(args, 'num_envs', 1))
-    if (getattr(args, 'device_loop', False) or getattr(args, 'device_env', False)) and _nstep_stride(args) != E:
-        raise SystemExit(f'--n-stride {_nstep_stride(args)}: a device environment interleaves --num-envs {E} trajectories in the ring; the stride must be {E}')
+    _check_device_stride(args)
 
 
 def _check_per(args):

@@ -31,6 +31,28 @@ def _check_nstep(cls, n_step, n_stride, shard):
     return n_step, n_stride
 
 
+def _check_critic_nstep(cls, critic_n_step, n_step, shard, refuse=None):
+    """critic_n_step: the chain length of the critic targets of the representation agents.  `refuse`: why this class takes
+    none (prioritized and group buffers)."""
+    if isinstance(critic_n_step, bool) or int(critic_n_step) != critic_n_step:
+        raise ValueError(f'{cls}: critic_n_step {critic_n_step!r} must be an integer')
+    critic_n_step = int(critic_n_step)
+    if not 1 <= critic_n_step <= NSTEP_MAX:
+        raise ValueError(f'{cls}: critic_n_step {critic_n_step} outside [1, {NSTEP_MAX}]')
+    if critic_n_step > 1 and n_step > 1:
+        raise ValueError(f'{cls}: n_step {n_step} and critic_n_step {critic_n_step} together (n_step is the whole minibatch of a sac agent, '
+                         'critic_n_step the critic targets of vlsac / ctrlsac / spedersac / diffsrsac: a buffer trains one kind of agent)')
+    if critic_n_step > 1 and refuse is not None:
+        raise ValueError(f'{cls}: critic_n_step {critic_n_step} > 1 is not supported ({refuse}): use a plain ReplayBuffer')
+    if critic_n_step > 1 and shard is not None:
+        raise ValueError(f'{cls}: shard= is not supported with critic_n_step {critic_n_step} > 1 (a shard keeps one transition in `world`: its '
+                         'rows are no trajectory)')
+    return critic_n_step
+
+
+NStepTargets = collections.namedtuple('NStepTargets', ['next_state', 'reward', 'done'])
+
+
 def nstep_rows(ring, ind, size, n_step, n_stride, gamma, S, A):
     """The n-step rows of base rows `ind` in NumPy float32, operation for operation what csrc/nstep.hip computes: ring float32
     [max_size, 2S + A + 2], size = the fill level -> (rows float32 [B, 2S + A] = [s, a, s' of the chain's last row], R [B], D [B])."""
@@ -82,15 +104,44 @@ def nstep_batch(buf, ring, size_dev, size, ind, gamma):
     return Batch(state=xe[:, :S].contiguous(), action=xe[:, S:S + A].contiguous(), reward=r, next_state=xe[:, S + A:].contiguous(), done=d)
 
 
+def nstep_targets(buf, ind, gamma):
+    """The n-step critic targets of base rows `ind` of buf's ring for discount `gamma` (critic_n_step, n_stride): NStepTargets(next_state [B, S]
+    = s' of the chain's last row, reward [B, 1] = sum_k gamma^k r_k, done [B, 1] = 1 - gamma^(m-1) (1 - d_last)).  On the device ONE launch
+    (rlrep_replay_gather_nstep_targets, csrc/nstep_targets.hip) against the device fill level; on the CPU nstep_rows().  The three arrays the
+    launch wrote stay in buf._nstep_targets_last (XF2 [B, S + A] with columns [0, S) written, Rn, D: what it overwrites of a minibatch slot)."""
+    S, A = buf.state_dim, buf.action_dim
+    if buf.device.type == 'cuda':
+        import ctypes as C
+        from rlrep_amd._lib import lib, check
+        idx = torch.as_tensor(ind).to(buf.device, torch.int32).reshape(-1).contiguous()
+        B = int(idx.numel())
+        xf2 = torch.zeros(B, S + A, dtype=torch.float32, device=buf.device)
+        r, d = (torch.empty(B, 1, dtype=torch.float32, device=buf.device) for _ in range(2))
+        with torch.cuda.device(buf.device):
+            check(lib.rlrep_replay_gather_nstep_targets(C.c_void_p(buf.ring.data_ptr()), C.c_void_p(idx.data_ptr()), B, S, A, buf.max_size,
+                                                        C.c_void_p(buf.size_dev().data_ptr()), buf.critic_n_step, buf.n_stride, float(gamma),
+                                                        C.c_void_p(xf2.data_ptr()), C.c_void_p(r.data_ptr()), C.c_void_p(d.data_ptr()),
+                                                        C.c_void_p(_raw_stream())), 'replay_gather_nstep_targets')
+        buf._nstep_targets_last = dict(XF2=xf2, Rn=r, D=d)
+        return NStepTargets(next_state=xf2[:, :S].contiguous(), reward=r, done=d)
+    rows, R, D = nstep_rows(buf.ring.numpy(), np.asarray(torch.as_tensor(ind)), buf.size, buf.critic_n_step, buf.n_stride, gamma, S, A)
+    return NStepTargets(next_state=torch.from_numpy(rows[:, S + A:].copy()), reward=torch.from_numpy(R).reshape(-1, 1),
+                        done=torch.from_numpy(D).reshape(-1, 1))
+
+
 class ReplayBuffer(object):
-    def __init__(self, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, shard=None, n_step=1, n_stride=1):
+    def __init__(self, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, shard=None, n_step=1, n_stride=1, critic_n_step=1):
         """shard=(rank, world): this ring is one shard of a replay partitioned by transition index: every rank is
         offered the same stream of transitions and keeps transition i iff i % world == rank, at slot i // world of its own ring (the
         default, shard=None, keeps everything: each data-parallel rank then owns the transitions of its own environment).
         n_step > 1: SACAgent.train() learns from n-step rows (gather_nstep).  n_stride is the number of interleaved
         environments that write the ring -- row i's successor candidate is row (i + n_stride) mod max_size: 1 for add(), E for add_batch()
-        of E rows, N for add_device() of N rows, num_envs for a device environment."""
+        of E rows, N for add_device() of N rows, num_envs for a device environment.
+        critic_n_step > 1 (1..16; shares n_stride; not together with n_step > 1): VLSACAgent / CTRLSACAgent / SPEDERSACAgent /
+        DIFFSRSACAgent.train() computes the critic targets from n-step returns (gather_nstep_targets) while the feature step keeps
+        training on the one-step rows of the same minibatch."""
         self.n_step, self.n_stride = _check_nstep(type(self).__name__, n_step, n_stride, shard)
+        self.critic_n_step = _check_critic_nstep(type(self).__name__, critic_n_step, self.n_step, shard, getattr(self, '_CRITIC_NSTEP_REFUSAL', None))
         self.max_size = int(max_size)
         self.shard = None if shard is None else (int(shard[0]), int(shard[1]))
         self._offered = 0
@@ -291,6 +342,10 @@ class ReplayBuffer(object):
         if self.n_step > 1 and int(getattr(env, 'num_envs', 1)) != self.n_stride:
             raise ValueError(f'{type(self).__name__}.collect_on_device: n_step {self.n_step} with n_stride {self.n_stride}, but the device environment '
                              f'interleaves num_envs = {int(getattr(env, "num_envs", 1))} trajectories in the ring: build the buffer with n_stride = num_envs')
+        if self.critic_n_step > 1 and int(getattr(env, 'num_envs', 1)) != self.n_stride:
+            raise ValueError(f'{type(self).__name__}.collect_on_device: critic_n_step {self.critic_n_step} with n_stride {self.n_stride}, but the device '
+                             f'environment interleaves num_envs = {int(getattr(env, "num_envs", 1))} trajectories in the ring: build the buffer with '
+                             'n_stride = num_envs')
         self.flush()
         self.size_dev()
         if getattr(env, 'num_envs', 1) > 1:          # (environment e's cursor is (ptr + e) mod max_size)
@@ -385,6 +440,19 @@ class ReplayBuffer(object):
         size_dev = self.size_dev() if self.device.type == 'cuda' else None
         return nstep_batch(self, self.ring, size_dev, self.size, ind, gamma)
 
+    def cnstep_key(self):
+        """what a captured train() bakes in besides the ring when it gathers n-step critic targets"""
+        return ('cnstep', self.critic_n_step, self.n_stride)
+
+    def gather_nstep_targets(self, ind, gamma):
+        """The n-step critic targets of base rows `ind` for discount `gamma` (critic_n_step): NStepTargets(next_state, reward,
+        done) -- what replaces the next_state / reward / done of gather(ind) in the critic and actor steps of a representation agent, whose
+        feature step keeps gather(ind).  On the device ONE launch (csrc/nstep_targets.hip); on device='cpu' the same arithmetic in NumPy
+        float32.  critic_n_step == 1 returns gather(ind)'s three arrays."""
+        self.flush()
+        self._order_reads()
+        return nstep_targets(self, ind, gamma)
+
     # public array attributes of the reference, materialised on demand (read-only copies)
     def _col(self, a, b):
         self.flush()
@@ -455,12 +523,14 @@ class PrioritizedReplayBuffer(ReplayBuffer):
     host round trip.  `beta` may be assigned at any time (one device word, written on the caller's stream).  For SACAgent on one GPU; every
     other agent refuses the class by name.  On device='cpu' the same arithmetic runs in NumPy float32 (draw() / update())."""
     prioritized = True
+    _CRITIC_NSTEP_REFUSAL = 'prioritized replay is built for sac, which has n_step'
 
     def __init__(self, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, shard=None, alpha=0.6, beta=0.4, eps=1e-6,
-                 n_step=1, n_stride=1):
+                 n_step=1, n_stride=1, critic_n_step=1):
         if shard is not None:
             raise ValueError('PrioritizedReplayBuffer: shard= is not supported (a shard sees one transition in `world`; priorities are per ring)')
-        super().__init__(state_dim, action_dim, max_size=max_size, device=device, stage_rows=stage_rows, n_step=n_step, n_stride=n_stride)
+        super().__init__(state_dim, action_dim, max_size=max_size, device=device, stage_rows=stage_rows, n_step=n_step, n_stride=n_stride,
+                         critic_n_step=critic_n_step)
         self.P = 1 << max(0, self.max_size - 1).bit_length()
         self.tree = torch.zeros(2 * self.P, dtype=torch.float32, device=self.device)
         self._scal = torch.tensor([1.0, alpha, beta, eps], dtype=torch.float32, device=self.device)      # max_p, alpha, beta, eps

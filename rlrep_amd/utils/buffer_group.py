@@ -12,14 +12,17 @@ from rlrep_amd.utils.streams import raw_stream as _raw_stream
 
 
 class ReplayBufferGroup(object):
-    def __init__(self, members, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, n_step=1, n_stride=1):
+    def __init__(self, members, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, n_step=1, n_stride=1, critic_n_step=1):
         """n_step > 1: SACSeedBatch.train() learns from n-step rows, every member with its own discount (gather_nstep); n_stride is
-        the number of interleaved environments per member that write the rings (ReplayBuffer)."""
-        from rlrep_amd.utils.buffer import _check_nstep
+        the number of interleaved environments per member that write the rings (ReplayBuffer).  critic_n_step (ReplayBuffer's keyword for the
+        representation agents) is refused above 1: seed groups have no n-step critic targets."""
+        from rlrep_amd.utils.buffer import _check_nstep, _check_critic_nstep
         self.members = int(members)
         if self.members < 1:
             raise ValueError('ReplayBufferGroup: members must be >= 1')
         self.n_step, self.n_stride = _check_nstep(type(self).__name__, n_step, n_stride, None)
+        self.critic_n_step = _check_critic_nstep(type(self).__name__, critic_n_step, self.n_step, None,
+                                                 'n-step critic targets are built for one agent, not for a seed group')
         self.max_size = int(max_size)
         self.state_dim, self.action_dim = int(state_dim), int(action_dim)
         self.row = 2 * self.state_dim + self.action_dim + 2
@@ -265,8 +268,9 @@ class PrioritizedReplayBufferGroup(ReplayBufferGroup):
     prioritized_group = True          # (NOT `prioritized`: that is the single ring's class, which seed groups and other agents refuse)
 
     def __init__(self, members, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, alpha=0.6, beta=0.4, eps=1e-6,
-                 n_step=1, n_stride=1):
-        super().__init__(members, state_dim, action_dim, max_size=max_size, device=device, stage_rows=stage_rows, n_step=n_step, n_stride=n_stride)
+                 n_step=1, n_stride=1, critic_n_step=1):
+        super().__init__(members, state_dim, action_dim, max_size=max_size, device=device, stage_rows=stage_rows, n_step=n_step, n_stride=n_stride,
+                         critic_n_step=critic_n_step)
         R = self.members
         self.P = 1 << max(0, self.max_size - 1).bit_length()
         self.trees = torch.zeros(R, 2 * self.P, dtype=torch.float32, device=self.device)
