@@ -10,7 +10,8 @@ one asynchronous copy per `sample`/`flush`.
 import collections
 import numpy as np
 import torch
-from rlrep_amd.utils.streams import raw_stream as _raw_stream, current_stream as _current_stream, current_device_index as _current_device_index
+from rlrep_amd.utils._ring import Ring, lib_call
+from rlrep_amd.utils.streams import current_stream as _current_stream
 
 Batch = collections.namedtuple('Batch', ['state', 'action', 'reward', 'next_state', 'done'])
 
@@ -79,28 +80,38 @@ def nstep_rows(ring, ind, size, n_step, n_stride, gamma, S, A):
     return rows, Rs, Ds
 
 
+def _nstep_index(buf, ind):
+    """base rows `ind` as the int32 device array the n-step launches read, and its length"""
+    idx = torch.as_tensor(ind).to(buf.device, torch.int32).reshape(-1).contiguous()
+    return idx, int(idx.numel())
+
+
+def _nstep_launch(buf, entry, n, ring, idx, size_dev, gamma, *outs):
+    """ONE launch of a chain-following gather (`entry`: replay_gather_nstep or replay_gather_nstep_targets) for chain length n into `outs`"""
+    lib_call(buf.device, entry, ring.data_ptr(), idx.data_ptr(), int(idx.numel()), buf.state_dim, buf.action_dim, buf.max_size, size_dev.data_ptr(),
+             n, buf.n_stride, float(gamma), *(t.data_ptr() for t in outs))
+
+
+def _nstep_host(buf, ring, size, ind, gamma, n):
+    """device='cpu': nstep_rows() for chain length n as tensors (rows [B, 2S + A], R [B, 1], D [B, 1])"""
+    rows, R, D = nstep_rows(ring.numpy(), np.asarray(torch.as_tensor(ind)), size, n, buf.n_stride, gamma, buf.state_dim, buf.action_dim)
+    return torch.from_numpy(rows), torch.from_numpy(R).reshape(-1, 1), torch.from_numpy(D).reshape(-1, 1)
+
+
 def nstep_batch(buf, ring, size_dev, size, ind, gamma):
     """The n-step Batch of base rows `ind` of `ring` ([max_size, row], buf's or one member's of a buffer group) for discount `gamma`: on the
     device ONE launch (rlrep_replay_gather_nstep) against the fill level word `size_dev`; on the CPU nstep_rows() against `size`.  The six
     arrays the launch wrote stay in buf._nstep_last (XE, XF, XF2, XFpi, R, D: what a minibatch slot holds)."""
     S, A = buf.state_dim, buf.action_dim
     if buf.device.type == 'cuda':
-        import ctypes as C
-        from rlrep_amd._lib import lib, check
-        idx = torch.as_tensor(ind).to(buf.device, torch.int32).reshape(-1).contiguous()
-        B = int(idx.numel())
+        idx, B = _nstep_index(buf, ind)
         xe = torch.empty(B, 2 * S + A, dtype=torch.float32, device=buf.device)
         xf, xf2, xfpi = (torch.zeros(B, S + A, dtype=torch.float32, device=buf.device) for _ in range(3))
         r, d = (torch.empty(B, 1, dtype=torch.float32, device=buf.device) for _ in range(2))
-        with torch.cuda.device(buf.device):
-            check(lib.rlrep_replay_gather_nstep(C.c_void_p(ring.data_ptr()), C.c_void_p(idx.data_ptr()), B, S, A, buf.max_size,
-                                                C.c_void_p(size_dev.data_ptr()), buf.n_step, buf.n_stride, float(gamma), C.c_void_p(xe.data_ptr()),
-                                                C.c_void_p(xf.data_ptr()), C.c_void_p(xf2.data_ptr()), C.c_void_p(xfpi.data_ptr()),
-                                                C.c_void_p(r.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(_raw_stream())), 'replay_gather_nstep')
+        _nstep_launch(buf, 'replay_gather_nstep', buf.n_step, ring, idx, size_dev, gamma, xe, xf, xf2, xfpi, r, d)
         buf._nstep_last = dict(XE=xe, XF=xf, XF2=xf2, XFpi=xfpi, R=r, D=d)
     else:
-        rows, R, D = nstep_rows(ring.numpy(), np.asarray(torch.as_tensor(ind)), size, buf.n_step, buf.n_stride, gamma, S, A)
-        xe, r, d = torch.from_numpy(rows), torch.from_numpy(R).reshape(-1, 1), torch.from_numpy(D).reshape(-1, 1)
+        xe, r, d = _nstep_host(buf, ring, size, ind, gamma, buf.n_step)
     return Batch(state=xe[:, :S].contiguous(), action=xe[:, S:S + A].contiguous(), reward=r, next_state=xe[:, S + A:].contiguous(), done=d)
 
 
@@ -111,25 +122,19 @@ def nstep_targets(buf, ind, gamma):
     launch wrote stay in buf._nstep_targets_last (XF2 [B, S + A] with columns [0, S) written, Rn, D: what it overwrites of a minibatch slot)."""
     S, A = buf.state_dim, buf.action_dim
     if buf.device.type == 'cuda':
-        import ctypes as C
-        from rlrep_amd._lib import lib, check
-        idx = torch.as_tensor(ind).to(buf.device, torch.int32).reshape(-1).contiguous()
-        B = int(idx.numel())
+        idx, B = _nstep_index(buf, ind)
         xf2 = torch.zeros(B, S + A, dtype=torch.float32, device=buf.device)
         r, d = (torch.empty(B, 1, dtype=torch.float32, device=buf.device) for _ in range(2))
-        with torch.cuda.device(buf.device):
-            check(lib.rlrep_replay_gather_nstep_targets(C.c_void_p(buf.ring.data_ptr()), C.c_void_p(idx.data_ptr()), B, S, A, buf.max_size,
-                                                        C.c_void_p(buf.size_dev().data_ptr()), buf.critic_n_step, buf.n_stride, float(gamma),
-                                                        C.c_void_p(xf2.data_ptr()), C.c_void_p(r.data_ptr()), C.c_void_p(d.data_ptr()),
-                                                        C.c_void_p(_raw_stream())), 'replay_gather_nstep_targets')
+        _nstep_launch(buf, 'replay_gather_nstep_targets', buf.critic_n_step, buf.ring, idx, buf.size_dev(), gamma, xf2, r, d)
         buf._nstep_targets_last = dict(XF2=xf2, Rn=r, D=d)
         return NStepTargets(next_state=xf2[:, :S].contiguous(), reward=r, done=d)
-    rows, R, D = nstep_rows(buf.ring.numpy(), np.asarray(torch.as_tensor(ind)), buf.size, buf.critic_n_step, buf.n_stride, gamma, S, A)
-    return NStepTargets(next_state=torch.from_numpy(rows[:, S + A:].copy()), reward=torch.from_numpy(R).reshape(-1, 1),
-                        done=torch.from_numpy(D).reshape(-1, 1))
+    rows, r, d = _nstep_host(buf, buf.ring, buf.size, ind, gamma, buf.critic_n_step)
+    return NStepTargets(next_state=rows[:, S + A:].contiguous(), reward=r, done=d)
 
 
-class ReplayBuffer(object):
+class ReplayBuffer(Ring):
+    _NAME, _ADVANCING, _INTERLEAVES = 'ReplayBuffer', 'this ring (SACAgent.iterate)', ('in the ring', 'the buffer')
+
     def __init__(self, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, shard=None, n_step=1, n_stride=1, critic_n_step=1):
         """shard=(rank, world): this ring is one shard of a replay partitioned by transition index: every rank is
         offered the same stream of transitions and keeps transition i iff i % world == rank, at slot i // world of its own ring (the
@@ -140,52 +145,36 @@ class ReplayBuffer(object):
         critic_n_step > 1 (1..16; shares n_stride; not together with n_step > 1): VLSACAgent / CTRLSACAgent / SPEDERSACAgent /
         DIFFSRSACAgent.train() computes the critic targets from n-step returns (gather_nstep_targets) while the feature step keeps
         training on the one-step rows of the same minibatch."""
-        self.n_step, self.n_stride = _check_nstep(type(self).__name__, n_step, n_stride, shard)
-        self.critic_n_step = _check_critic_nstep(type(self).__name__, critic_n_step, self.n_step, shard, getattr(self, '_CRITIC_NSTEP_REFUSAL', None))
-        self.max_size = int(max_size)
+        n_step, n_stride = _check_nstep(type(self).__name__, n_step, n_stride, shard)
+        critic_n_step = _check_critic_nstep(type(self).__name__, critic_n_step, n_step, shard, getattr(self, '_CRITIC_NSTEP_REFUSAL', None))
+        super().__init__((), state_dim, action_dim, max_size, device, stage_rows, n_step, n_stride, critic_n_step)
         self.shard = None if shard is None else (int(shard[0]), int(shard[1]))
         self._offered = 0
-        self.ptr = 0
         self.size = 0
-        self.state_dim, self.action_dim = int(state_dim), int(action_dim)
-        self.row = 2 * self.state_dim + self.action_dim + 2
-        self.device = torch.device(device if device is not None else
-                                   ('cuda' if torch.cuda.is_available() else 'cpu'))
-        self.ring = torch.zeros(self.max_size, self.row, dtype=torch.float32, device=self.device)
-        pin = self.device.type == 'cuda'
-        self._stage = torch.zeros(min(stage_rows, self.max_size), self.row, dtype=torch.float32, pin_memory=pin)
-        self._stage_np = self._stage.numpy()
-        self._staged = 0            # rows waiting in the staging buffer
-        self._stage_start = 0       # ring position of the first staged row
-        self._copy_done = None
+        self.ring = self._new_ring(())
         self._copy_event = None
         self._size_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._size_pushed = -1
         self.device_epoch = 0        # bumped whenever this buffer enqueues device work on the caller's stream (a pipelined train() then orders itself after it)
-        # hooks called before the ring / size scalar is overwritten on the caller's stream (a pipelined train() may still be sampling from
-        # them on its own stream: each agent that trains from this buffer appends one that makes the caller's stream wait)
-        self.before_device_write_hooks = []
-        self._device_env = None      # the device environment that owns the cursor (collect_on_device); None: the host does
+
+    def _advance(self, n):
+        self.size = min(self.size + n, self.max_size)
+
+    def _fill_levels(self):
+        return [self.size]
 
     # ---- reference API ------------------------------------------------------------------------
     def add(self, state, action, next_state, reward, done):
         if self._device_env is not None:
-            raise RuntimeError('ReplayBuffer.add: a device environment has been advancing this ring (SACAgent.iterate), so the host cursor is stale: '
-                               'call adopt_device_cursor() first')
+            raise self._stale('add')
         if self.shard is not None:
             i = self._offered
             self._offered += 1
             if i % self.shard[1] != self.shard[0]:
                 return
-        if self._staged == self._stage.shape[0]:
-            self.flush()
-        if self._copy_done is not None:
-            self._copy_done.synchronize()
-            self._copy_done = None
-        if self._staged == 0:
-            self._stage_start = self.ptr
+        self._stage_ready()
         S, A = self.state_dim, self.action_dim
-        r = self._stage_np[self._staged]
+        r = self._stage_np[self._staged]             # (in place in the pinned stage, no temporary row: this is main.py's loop)
         r[:S] = state
         r[S:S + A] = action
         r[S + A:2 * S + A] = next_state
@@ -193,42 +182,21 @@ class ReplayBuffer(object):
         r[2 * S + A + 1] = done
         self._staged += 1
         self.ptr = (self.ptr + 1) % self.max_size
-        self.size = min(self.size + 1, self.max_size)
+        self._advance(1)
 
     def add_batch(self, states, actions, next_states, rewards, dones):
         """E transitions in one call: states / next_states [E, S], actions [E, A], rewards / dones [E].  Equal in every observable to E add()
         calls in row order -- the ring after flush(), ptr, size, device_epoch, the shard rule -- also where the batch wraps the ring or is
         larger than the staging buffer (which is then flushed exactly where the E calls would flush it)."""
         if self._device_env is not None:
-            raise RuntimeError('ReplayBuffer.add_batch: a device environment has been advancing this ring (SACAgent.iterate), so the host cursor is stale: '
-                               'call adopt_device_cursor() first')
-        S, A = self.state_dim, self.action_dim
+            raise self._stale('add_batch')
         E = int(np.shape(rewards)[0])
-        rows = np.empty((E, self.row), np.float32)
-        rows[:, :S] = np.asarray(states).reshape(E, S)
-        rows[:, S:S + A] = np.asarray(actions).reshape(E, A)
-        rows[:, S + A:2 * S + A] = np.asarray(next_states).reshape(E, S)
-        rows[:, 2 * S + A] = np.asarray(rewards).reshape(E)
-        rows[:, 2 * S + A + 1] = np.asarray(dones).reshape(E)
+        rows = self._pack_rows((E,), states, actions, next_states, rewards, dones)
         if self.shard is not None:
             i = self._offered + np.arange(E)
             self._offered += E
             rows = rows[i % self.shard[1] == self.shard[0]]
-        cap, k = self._stage.shape[0], 0
-        while k < len(rows):
-            if self._staged == cap:
-                self.flush()
-            if self._copy_done is not None:
-                self._copy_done.synchronize()
-                self._copy_done = None
-            if self._staged == 0:
-                self._stage_start = self.ptr
-            n = min(len(rows) - k, cap - self._staged)
-            self._stage_np[self._staged:self._staged + n] = rows[k:k + n]
-            self._staged += n
-            self.ptr = (self.ptr + n) % self.max_size
-            self.size = min(self.size + n, self.max_size)
-            k += n
+        self._stage_rows(rows)
 
     def add_device(self, states, actions, next_states, rewards, dones):
         """N transitions that live on the device: states / next_states [N, S], actions [N, A], rewards / dones [N] (or [N, 1]), float32
@@ -237,8 +205,7 @@ class ReplayBuffer(object):
         are flushed first, so the order of transitions is the call order.  ptr, size, device_epoch and the ring end up as add_batch() +
         flush() on the same rows leave them.  N is known on the host: ptr and size advance here."""
         if self._device_env is not None:
-            raise RuntimeError('ReplayBuffer.add_device: a device environment has been advancing this ring (SACAgent.iterate), so the host cursor is stale: '
-                               'call adopt_device_cursor() first')
+            raise self._stale('add_device')
         if self.shard is not None:
             raise ValueError('ReplayBuffer.add_device: a sharded ring (shard=) keeps one transition in `world`; add_device writes every row it is given')
         S, A = self.state_dim, self.action_dim
@@ -263,96 +230,40 @@ class ReplayBuffer(object):
         self.flush()
         start = self.ptr
         self.ptr = (self.ptr + N) % self.max_size
-        self.size = min(self.size + N, self.max_size)
+        self._advance(N)
         self._before_device_write()
         if self.device.type == 'cuda':
-            import ctypes as C
-            from rlrep_amd._lib import lib, check
-
-            def issue():
-                ld = lambda t, w: t.stride(0) if N > 1 else w
-                check(lib.rlrep_replay_add_cols(C.c_void_p(self.ring.data_ptr()), self.max_size, self.row, start, S, A, C.c_void_p(s.data_ptr()), ld(s, S),
-                                                C.c_void_p(a.data_ptr()), ld(a, A), C.c_void_p(s2.data_ptr()), ld(s2, S), C.c_void_p(r.data_ptr()),
-                                                C.c_void_p(d.data_ptr()), N, C.c_void_p(self._size_dev.data_ptr()), self.size, C.c_void_p(_raw_stream())),
-                      'replay_add_cols')
-                self._size_pushed = self.size
-                if self._copy_event is None:
-                    self._copy_event = torch.cuda.Event()
-                self._copy_done = self._copy_event
-                self._copy_done.record(_current_stream())
-            if self.device.index is None or self.device.index == _current_device_index():
-                issue()
-            else:
-                with torch.cuda.device(self.device):
-                    issue()
+            ld = lambda t, w: t.stride(0) if N > 1 else w
+            lib_call(self.device, 'replay_add_cols', self.ring.data_ptr(), self.max_size, self.row, start, S, A, s.data_ptr(), ld(s, S), a.data_ptr(),
+                     ld(a, A), s2.data_ptr(), ld(s2, S), r.data_ptr(), d.data_ptr(), N, self._size_dev.data_ptr(), self.size, then=self._wrote)
         else:
-            idx = (start + torch.arange(N)) % self.max_size
-            self.ring[idx] = torch.cat([s, a, s2, r.reshape(N, 1), d.reshape(N, 1)], dim=1)
+            self._write_wrapped(self.ring, start, torch.from_numpy(self._pack_rows((N,), s, a, s2, r, d)))
         self.device_epoch = epoch + 1           # (one step for the call, staged host rows included: what add_batch() + flush() on the same rows count)
 
-    def _before_device_write(self):
-        for h in self.before_device_write_hooks:
-            h()
+    def _wrote(self):
+        """after a launch that wrote ring rows and the fill level: the level is published, and the event add() waits for before it reuses the
+        stage is recorded (ONE event for the life of the ring: a fresh one per flush was host time in front of every train() of main.py's loop)"""
+        self._size_pushed = self.size
+        if self._copy_event is None:
+            self._copy_event = torch.cuda.Event()
+        self._copy_done = self._copy_event
+        self._copy_done.record(_current_stream())
 
     def flush(self):
         n = self._staged
         self._order_reads()          # (whoever samples after this call, on this stream, sees a flush another stream may still be performing)
         if n == 0:
             return
-        a = self._stage_start
-        first = min(n, self.max_size - a)
         self._before_device_write()
         if self.device.type == 'cuda':
-            # the C ABI's entry for this row of the path (include/rlrep.h rlrep_replay_add): the staged rows, wrap-around included
-            import ctypes as C
-            from rlrep_amd._lib import lib, check
-            # (one launch: the staged rows, read in place from the pinned staging buffer, and the new fill level for the device-side sampler;
-            # the device context manager and a fresh Event per call were 15 us of host time in front of every train() of main.py's loop)
-            def issue():
-                check(lib.rlrep_replay_add_sized(C.c_void_p(self.ring.data_ptr()), self.max_size, self.row, a, C.c_void_p(self._stage.data_ptr()), n,
-                                                 C.c_void_p(self._size_dev.data_ptr()), self.size, C.c_void_p(_raw_stream())), 'replay_add_sized')
-                self._size_pushed = self.size
-                if self._copy_event is None:
-                    self._copy_event = torch.cuda.Event()
-                self._copy_done = self._copy_event
-                self._copy_done.record(_current_stream())
-            if self.device.index is None or self.device.index == _current_device_index():
-                issue()
-            else:
-                with torch.cuda.device(self.device):
-                    issue()
+            # the C ABI's entry for this row of the path (include/rlrep.h rlrep_replay_add): ONE launch moves the staged rows, wrap-around
+            # included and read in place from the pinned staging buffer, and writes the new fill level for the device-side sampler
+            lib_call(self.device, 'replay_add_sized', self.ring.data_ptr(), self.max_size, self.row, self._stage_start, self._stage.data_ptr(), n,
+                     self._size_dev.data_ptr(), self.size, then=self._wrote)
         else:
-            self.ring[a:a + first].copy_(self._stage[:first])
-            if first < n:
-                self.ring[:n - first].copy_(self._stage[first:n])
+            self._write_wrapped(self.ring, self._stage_start, self._stage[:n])
         self._staged = 0
         self.device_epoch += 1
-
-    # ---- device collection (rlrep_amd/envs/device.py DeviceEnv), with ReplayBufferGroup's semantics -------------------------------------
-    def collect_on_device(self, env):
-        """Hand the cursor to device environment `env`: staged rows are flushed, the environment's record takes (ptr, size), and from here on
-        the step launches advance the ring and the fill level in size_dev().  add() refuses until adopt_device_cursor()."""
-        if self._device_env is env:
-            return
-        if self._device_env is not None:
-            raise RuntimeError('ReplayBuffer.collect_on_device: another device environment owns the cursor (adopt_device_cursor() first)')
-        if self.shard is not None:
-            raise ValueError('ReplayBuffer.collect_on_device: a sharded ring (shard=) keeps one transition in `world`; a device environment '
-                             'writes every row it steps')
-        if self.n_step > 1 and int(getattr(env, 'num_envs', 1)) != self.n_stride:
-            raise ValueError(f'{type(self).__name__}.collect_on_device: n_step {self.n_step} with n_stride {self.n_stride}, but the device environment '
-                             f'interleaves num_envs = {int(getattr(env, "num_envs", 1))} trajectories in the ring: build the buffer with n_stride = num_envs')
-        if self.critic_n_step > 1 and int(getattr(env, 'num_envs', 1)) != self.n_stride:
-            raise ValueError(f'{type(self).__name__}.collect_on_device: critic_n_step {self.critic_n_step} with n_stride {self.n_stride}, but the device '
-                             f'environment interleaves num_envs = {int(getattr(env, "num_envs", 1))} trajectories in the ring: build the buffer with '
-                             'n_stride = num_envs')
-        self.flush()
-        self.size_dev()
-        if getattr(env, 'num_envs', 1) > 1:          # (environment e's cursor is (ptr + e) mod max_size)
-            env.set_cursor(self.ptr, [self.size], self.max_size)
-        else:
-            env.set_cursor(self.ptr, [self.size])
-        self._device_env = env
 
     def adopt_device_cursor(self):
         """Take the cursor back from the device environment: ptr and size become what its record holds (synchronises), and add() continues
@@ -371,9 +282,7 @@ class ReplayBuffer(object):
         if self.shard is not None:
             raise ValueError('load() fills the whole ring and knows nothing of the shard rule: add() the transitions instead')
         n = int(len(state))
-        rows = np.concatenate([np.asarray(state, np.float32).reshape(n, -1), np.asarray(action, np.float32).reshape(n, -1),
-                               np.asarray(next_state, np.float32).reshape(n, -1), np.asarray(reward, np.float32).reshape(n, 1),
-                               np.asarray(done, np.float32).reshape(n, 1)], axis=1)
+        rows = self._pack_rows((n,), state, action, next_state, reward, done)
         self._before_device_write()
         self.ring[:n].copy_(torch.from_numpy(rows))
         self.size, self.ptr, self._staged = n, n % self.max_size, 0
@@ -515,6 +424,37 @@ def _per_draw(tree, P, B, words):
     return (n - P).astype(np.int32)
 
 
+def _per_weights(tree, P, idx, beta):
+    """host form of per_sample's weights: (pmin / p)^beta over the leaves of rows `idx`, 1 at the minimum and wherever beta == 0"""
+    p = tree[P + idx.astype(np.int64)]
+    pmin, beta = p.min(), _f32(beta)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        wv = np.power((pmin / p).astype(np.float32), beta, dtype=np.float32)
+    return np.where((p == pmin) | (beta == 0), _f32(1.0), wv).astype(np.float32)
+
+
+def _per_update_host(tree, P, scal_row, idx, td, alpha, eps):
+    """host form of per_update: leaf idx[j] <- (td[j] + eps)^alpha (1 when alpha == 0; the maximum where an index repeats), scal_row[0] = max_p
+    follows, the ancestors are recomputed"""
+    alpha = _f32(alpha)
+    new = np.ones(len(idx), np.float32) if alpha == 0 else np.power(td + _f32(eps), alpha, dtype=np.float32)
+    new = np.where(new > PER_MIN_PRIORITY, new, PER_MIN_PRIORITY).astype(np.float32)     # (not positive, or NaN: the floor, as per_update_kernel)
+    rows = idx.astype(np.int64)
+    tree[P + rows] = 0
+    np.maximum.at(tree, P + rows, new)
+    scal_row[0] = max(scal_row[0], new.max())
+    _per_set(tree, P, rows, tree[P + rows])
+
+
+def _per_rebuild_host(tree, P):
+    """host form of per_rebuild: every internal node from its children, level by level from the leaves up"""
+    w = P >> 1
+    while w >= 1:
+        nd = np.arange(w, 2 * w)
+        tree[nd] = tree[2 * nd] + tree[2 * nd + 1]
+        w >>= 1
+
+
 class PrioritizedReplayBuffer(ReplayBuffer):
     """ReplayBuffer whose rows carry priorities in a device-resident sum tree (float32[2P], P = the smallest power of two >= max_size, row
     i's leaf at tree[P + i], an internal node ONE fp32 add of its children).  A row written by add() / add_batch() (at flush()), add_device()
@@ -571,17 +511,7 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         if n <= 0:
             return
         if self.device.type == 'cuda':
-            import ctypes as C
-            from rlrep_amd._lib import lib, check
-
-            def issue():
-                check(lib.rlrep_per_add(C.c_void_p(self.tree.data_ptr()), self.P, C.c_void_p(self._scal.data_ptr()), self.max_size, int(start), int(n),
-                                        C.c_void_p(_raw_stream())), 'per_add')
-            if self.device.index is None or self.device.index == _current_device_index():
-                issue()
-            else:
-                with torch.cuda.device(self.device):
-                    issue()
+            lib_call(self.device, 'per_add', self.tree.data_ptr(), self.P, self._scal.data_ptr(), self.max_size, int(start), int(n))
         else:
             _per_set(self.tree.numpy(), self.P, (int(start) + np.arange(int(n))) % self.max_size, self._scal.numpy()[0])
 
@@ -636,17 +566,9 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         self.tree[self.P:self.P + n].copy_(torch.from_numpy(leaves))
         self.device_epoch += 1
         if self.device.type == 'cuda':
-            import ctypes as C
-            from rlrep_amd._lib import lib, check
-            with torch.cuda.device(self.device):
-                check(lib.rlrep_per_rebuild(C.c_void_p(self.tree.data_ptr()), self.P, C.c_void_p(_raw_stream())), 'per_rebuild')
+            lib_call(self.device, 'per_rebuild', self.tree.data_ptr(), self.P)
         else:
-            t = self.tree.numpy()
-            w = self.P >> 1
-            while w >= 1:
-                nd = np.arange(w, 2 * w)
-                t[nd] = t[2 * nd] + t[2 * nd + 1]
-                w >>= 1
+            _per_rebuild_host(self.tree.numpy(), self.P)
 
     # ---- the sampler and the priority update (SACAgent calls these inside train()) ---------------
     def draw_buffers(self, B):
@@ -671,24 +593,17 @@ class PrioritizedReplayBuffer(ReplayBuffer):
                 raise ValueError(f'PrioritizedReplayBuffer.draw: given indices must be {B} rows in [0, {self.size})')
             idx.copy_(torch.from_numpy(g.astype(np.int32)))
         if self.device.type == 'cuda':
-            import ctypes as C
-            from rlrep_amd._lib import lib, check
             if core is None:
                 raise ValueError('PrioritizedReplayBuffer.draw: the device sampler runs for a sac agent (core=agent.core)')
             self._order_reads()
-            check(lib.rlrep_per_sample(core.h, C.c_void_p(self.tree.data_ptr()), self.P, C.c_void_p(self._scal.data_ptr()), C.c_void_p(idx.data_ptr()),
-                                       C.c_void_p(w.data_ptr()), B, 0 if given is None else 1, int(seed), int(offset), C.c_void_p(counter_dev),
-                                       C.c_void_p(_raw_stream())), 'per_sample')
+            lib_call(self.device, 'per_sample', core.h, self.tree.data_ptr(), self.P, self._scal.data_ptr(), idx.data_ptr(), w.data_ptr(), B,
+                     0 if given is None else 1, int(seed), int(offset), counter_dev)
             return idx, w
         from rlrep_amd.utils.philox_host import raw_stream as words
         t = self.tree.numpy()
         if given is None:
             idx.copy_(torch.from_numpy(_per_draw(t, self.P, B, words(B, int(seed), int(offset)))))
-        p = t[self.P + idx.numpy().astype(np.int64)]
-        pmin, beta = p.min(), _f32(self._hyper[1])
-        with np.errstate(divide='ignore', invalid='ignore'):
-            wv = np.power((pmin / p).astype(np.float32), beta, dtype=np.float32)
-        w.copy_(torch.from_numpy(np.where((p == pmin) | (beta == 0), _f32(1.0), wv).astype(np.float32)))
+        w.copy_(torch.from_numpy(_per_weights(t, self.P, idx.numpy(), self._hyper[1])))
         return idx, w
 
     def update(self, B, td=None, core=None):
@@ -697,20 +612,10 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         B = int(B)
         idx, _ = self.draw_buffers(B)
         if self.device.type == 'cuda':
-            import ctypes as C
-            from rlrep_amd._lib import lib, check
             if core is None:
                 raise ValueError('PrioritizedReplayBuffer.update: the device update runs for a sac agent (core=agent.core)')
-            check(lib.rlrep_per_update(core.h, C.c_void_p(self.tree.data_ptr()), self.P, C.c_void_p(self._scal.data_ptr()), C.c_void_p(idx.data_ptr()),
-                                       C.c_void_p(None if td is None else td.data_ptr()), B, C.c_void_p(_raw_stream())), 'per_update')
+            lib_call(self.device, 'per_update', core.h, self.tree.data_ptr(), self.P, self._scal.data_ptr(), idx.data_ptr(),
+                     None if td is None else td.data_ptr(), B)
             return
-        t, s = self.tree.numpy(), self._scal.numpy()
-        td = np.asarray(td, np.float32).reshape(B)
-        alpha = _f32(self._hyper[0])
-        new = np.ones(B, np.float32) if alpha == 0 else np.power(td + _f32(self._hyper[2]), alpha, dtype=np.float32)
-        new = np.where(new > PER_MIN_PRIORITY, new, PER_MIN_PRIORITY).astype(np.float32)     # (not positive, or NaN: the floor, as per_update_kernel)
-        rows = idx.numpy().astype(np.int64)
-        t[self.P + rows] = 0
-        np.maximum.at(t, self.P + rows, new)
-        s[0] = max(s[0], new.max())
-        _per_set(t, self.P, rows, t[self.P + rows])
+        _per_update_host(self.tree.numpy(), self.P, self._scal.numpy(), idx.numpy(), np.asarray(td, np.float32).reshape(B), self._hyper[0],
+                         self._hyper[2])

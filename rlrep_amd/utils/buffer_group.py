@@ -8,39 +8,29 @@ member's fill level into `size_dev()[r]` -- the word member r's train prologue b
 import numpy as np
 import torch
 
-from rlrep_amd.utils.streams import raw_stream as _raw_stream
+from rlrep_amd.utils._ring import Ring, lib_call
+from rlrep_amd.utils.buffer import _check_critic_nstep, _check_nstep, _per_draw, _per_rebuild_host, _per_set, _per_update_host, _per_weights, nstep_batch
 
 
-class ReplayBufferGroup(object):
+class ReplayBufferGroup(Ring):
+    _NAME, _ADVANCING, _INTERLEAVES = 'ReplayBufferGroup', 'these rings (SeedBatchMixin.iterate)', ('per ring', 'the buffers')
+
     def __init__(self, members, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, n_step=1, n_stride=1, critic_n_step=1):
         """n_step > 1: SACSeedBatch.train() learns from n-step rows, every member with its own discount (gather_nstep); n_stride is
         the number of interleaved environments per member that write the rings (ReplayBuffer).  critic_n_step (ReplayBuffer's keyword for the
         representation agents) is refused above 1: seed groups have no n-step critic targets."""
-        from rlrep_amd.utils.buffer import _check_nstep, _check_critic_nstep
         self.members = int(members)
         if self.members < 1:
             raise ValueError('ReplayBufferGroup: members must be >= 1')
-        self.n_step, self.n_stride = _check_nstep(type(self).__name__, n_step, n_stride, None)
-        self.critic_n_step = _check_critic_nstep(type(self).__name__, critic_n_step, self.n_step, None,
-                                                 'n-step critic targets are built for one agent, not for a seed group')
-        self.max_size = int(max_size)
-        self.state_dim, self.action_dim = int(state_dim), int(action_dim)
-        self.row = 2 * self.state_dim + self.action_dim + 2
-        self.device = torch.device(device if device is not None else ('cuda' if torch.cuda.is_available() else 'cpu'))
-        self.rings = torch.zeros(self.members, self.max_size, self.row, dtype=torch.float32, device=self.device)
+        n_step, n_stride = _check_nstep(type(self).__name__, n_step, n_stride, None)
+        critic_n_step = _check_critic_nstep(type(self).__name__, critic_n_step, n_step, None,
+                                            'n-step critic targets are built for one agent, not for a seed group')
+        super().__init__((self.members,), state_dim, action_dim, max_size, device, stage_rows, n_step, n_stride, critic_n_step)
+        self.rings = self._new_ring((self.members,))
         self.ring_stride = self.max_size * self.row                 # floats between two members' rings
-        pin = self.device.type == 'cuda'
-        self._stage = torch.zeros(self.members, min(int(stage_rows), self.max_size), self.row, dtype=torch.float32, pin_memory=pin)
-        self._stage_np = self._stage.numpy()
-        self._staged = 0               # rows per member waiting in the staging buffer
-        self._stage_start = 0          # ring position of the first staged row (the same for every member: lockstep)
-        self._copy_done = None
-        self.ptr = 0
         self.sizes = [0] * self.members
         self._size_dev = torch.zeros(self.members, dtype=torch.int32, device=self.device)
         self._size_pushed = None
-        self.before_device_write_hooks = []
-        self._device_env = None        # the device environment that owns the cursor (collect_on_device); None: the host does
 
     # ---- what the agent reads ----------------------------------------------------------------
     @property
@@ -60,17 +50,14 @@ class ReplayBufferGroup(object):
             self._size_pushed = list(self.sizes)
         return self._size_dev
 
-    def _before_device_write(self):
-        for h in self.before_device_write_hooks:
-            h()
+    def _advance(self, n):
+        self.sizes = [min(s + n, self.max_size) for s in self.sizes]
 
-    def nstep_key(self):
-        """what a captured train() bakes in besides the rings when it gathers n-step rows"""
-        return ('nstep', self.n_step, self.n_stride)
+    def _fill_levels(self):
+        return self.sizes
 
     def gather_nstep(self, r, ind, gamma):
         """Member r's n-step batch of base rows `ind` for discount `gamma`: ReplayBuffer.gather_nstep on its ring and fill level."""
-        from rlrep_amd.utils.buffer import nstep_batch
         r = int(r)
         self.flush()
         size_dev = self.size_dev()[r:r + 1] if self.device.type == 'cuda' else None
@@ -80,64 +67,28 @@ class ReplayBufferGroup(object):
     def add(self, state, action, next_state, reward, done):
         """One transition per member: state / next_state [R, S], action [R, A], reward / done [R]."""
         if self._device_env is not None:
-            raise RuntimeError('ReplayBufferGroup.add: a device environment has been advancing these rings (SeedBatchMixin.iterate), so the host '
-                               'cursor is stale: call adopt_device_cursor() first')
-        if self._staged == self._stage.shape[1]:
-            self.flush()
-        if self._copy_done is not None:
-            self._copy_done.synchronize()
-            self._copy_done = None
-        if self._staged == 0:
-            self._stage_start = self.ptr
-        S, A, R = self.state_dim, self.action_dim, self.members
-        r = self._stage_np[:, self._staged]
-        r[:, :S] = np.asarray(state, np.float32).reshape(R, S)
-        r[:, S:S + A] = np.asarray(action, np.float32).reshape(R, A)
-        r[:, S + A:2 * S + A] = np.asarray(next_state, np.float32).reshape(R, S)
-        r[:, 2 * S + A] = np.asarray(reward, np.float32).reshape(R)
-        r[:, 2 * S + A + 1] = np.asarray(done, np.float32).reshape(R)
+            raise self._stale('add')
+        self._stage_ready()
+        self._pack_rows((self.members,), state, action, next_state, reward, done, out=self._stage_np[:, self._staged])
         self._staged += 1
         self.ptr = (self.ptr + 1) % self.max_size
-        self.sizes = [min(s + 1, self.max_size) for s in self.sizes]
+        self._advance(1)
 
     def add_batch(self, states, actions, next_states, rewards, dones):
         """E transitions per member in one call: states / next_states [R, E, S], actions [R, E, A], rewards / dones [R, E].  Equal in every
         observable to E add() calls in row order (rings after flush(), ptr, sizes), also where the batch wraps the rings or is larger than the
         staging buffer."""
         if self._device_env is not None:
-            raise RuntimeError('ReplayBufferGroup.add_batch: a device environment has been advancing these rings (SeedBatchMixin.iterate), so the host '
-                               'cursor is stale: call adopt_device_cursor() first')
-        S, A, R = self.state_dim, self.action_dim, self.members
+            raise self._stale('add_batch')
         E = int(np.shape(rewards)[1])
-        rows = np.empty((R, E, self.row), np.float32)
-        rows[:, :, :S] = np.asarray(states).reshape(R, E, S)
-        rows[:, :, S:S + A] = np.asarray(actions).reshape(R, E, A)
-        rows[:, :, S + A:2 * S + A] = np.asarray(next_states).reshape(R, E, S)
-        rows[:, :, 2 * S + A] = np.asarray(rewards).reshape(R, E)
-        rows[:, :, 2 * S + A + 1] = np.asarray(dones).reshape(R, E)
-        cap, k = self._stage.shape[1], 0
-        while k < E:
-            if self._staged == cap:
-                self.flush()
-            if self._copy_done is not None:
-                self._copy_done.synchronize()
-                self._copy_done = None
-            if self._staged == 0:
-                self._stage_start = self.ptr
-            n = min(E - k, cap - self._staged)
-            self._stage_np[:, self._staged:self._staged + n] = rows[:, k:k + n]
-            self._staged += n
-            self.ptr = (self.ptr + n) % self.max_size
-            self.sizes = [min(s + n, self.max_size) for s in self.sizes]
-            k += n
+        self._stage_rows(self._pack_rows((self.members, E), states, actions, next_states, rewards, dones))
 
     def add_device(self, states, actions, next_states, rewards, dones):
         """N device-resident transitions per member: states / next_states [R, N, S], actions [R, N, A], rewards / dones [R, N], tensors on the
         rings' device.  ONE launch (rlrep_group_replay_add_cols) packs member r's plane into its ring from row ptr on (wrapping) and writes
         every member's fill level; staged host rows are flushed first.  Like flush(), it does not look at retired members."""
         if self._device_env is not None:
-            raise RuntimeError('ReplayBufferGroup.add_device: a device environment has been advancing these rings (SeedBatchMixin.iterate), so the host '
-                               'cursor is stale: call adopt_device_cursor() first')
+            raise self._stale('add_device')
         S, A, R = self.state_dim, self.action_dim, self.members
         if rewards.dim() < 2 or rewards.shape[0] != R:
             raise ValueError(f'ReplayBufferGroup.add_device: rewards {tuple(rewards.shape)} is not [{R}, N]')
@@ -156,65 +107,35 @@ class ReplayBufferGroup(object):
             raise RuntimeError('ReplayBufferGroup.add_device after load() gave the members different fill levels: the lockstep ring takes N rows per member')
         start = self.ptr
         self.ptr = (self.ptr + N) % self.max_size
-        self.sizes = [min(v + N, self.max_size) for v in self.sizes]
+        self._advance(N)
         self._before_device_write()
         if self.device.type == 'cuda':
-            import ctypes as C
-            from rlrep_amd._lib import lib, check
-            check(lib.rlrep_group_replay_add_cols(C.c_void_p(self.rings.data_ptr()), self.max_size, self.row, start, S, A, C.c_void_p(s.data_ptr()), S,
-                                                  C.c_void_p(a.data_ptr()), A, C.c_void_p(s2.data_ptr()), S, C.c_void_p(r.data_ptr()), C.c_void_p(d.data_ptr()), N,
-                                                  R, self.ring_stride, C.c_void_p(self._size_dev.data_ptr()), self.sizes[0], C.c_void_p(_raw_stream())),
-                  'group_replay_add_cols')
-            self._size_pushed = list(self.sizes)
-            self._copy_done = torch.cuda.Event()
-            self._copy_done.record()
+            lib_call(self.device, 'group_replay_add_cols', self.rings.data_ptr(), self.max_size, self.row, start, S, A, s.data_ptr(), S, a.data_ptr(), A,
+                     s2.data_ptr(), S, r.data_ptr(), d.data_ptr(), N, R, self.ring_stride, self._size_dev.data_ptr(), self.sizes[0], then=self._wrote)
         else:
-            idx = (start + torch.arange(N)) % self.max_size
-            self.rings[:, idx] = torch.cat([s, a, s2, r.reshape(R, N, 1), d.reshape(R, N, 1)], dim=2)
+            self._write_wrapped(self.rings, start, torch.from_numpy(self._pack_rows((R, N), s, a, s2, r, d)))
+
+    def _wrote(self):
+        """after a launch that wrote ring rows and the fill levels: the levels are published, and add() waits for this event before it
+        reuses the stage (a fresh event per launch; ReplayBuffer reuses one)"""
+        self._size_pushed = list(self.sizes)
+        self._copy_done = torch.cuda.Event()
+        self._copy_done.record()
 
     def flush(self):
         n = self._staged
         if n == 0:
             return
-        a = self._stage_start
         self._before_device_write()
         if self.device.type == 'cuda':
-            import ctypes as C
-            from rlrep_amd._lib import lib, check
             if len(set(self.sizes)) != 1:
                 raise RuntimeError('ReplayBufferGroup.add after load() gave the members different fill levels: the lockstep ring takes one row per member')
             # member r's staged rows are block r of the pinned staging buffer [R, stage_rows, row]
-            check(lib.rlrep_group_replay_add_sized(C.c_void_p(self.rings.data_ptr()), self.ring_stride, self.members, self.max_size, self.row, a,
-                                                   C.c_void_p(self._stage.data_ptr()), self._stage.shape[1] * self.row, n, C.c_void_p(self._size_dev.data_ptr()), self.sizes[0],
-                                                   C.c_void_p(_raw_stream())), 'group_replay_add_sized')
-            self._size_pushed = list(self.sizes)
-            self._copy_done = torch.cuda.Event()
-            self._copy_done.record()
+            lib_call(self.device, 'group_replay_add_sized', self.rings.data_ptr(), self.ring_stride, self.members, self.max_size, self.row,
+                     self._stage_start, self._stage.data_ptr(), self._stage_cap * self.row, n, self._size_dev.data_ptr(), self.sizes[0], then=self._wrote)
         else:
-            first = min(n, self.max_size - a)
-            self.rings[:, a:a + first].copy_(self._stage[:, :first])
-            if first < n:
-                self.rings[:, :n - first].copy_(self._stage[:, first:n])
+            self._write_wrapped(self.rings, self._stage_start, self._stage[:, :n])
         self._staged = 0
-
-    # ---- device collection (rlrep_amd/envs/device.py) -----------------------------------------------------------------------------
-    def collect_on_device(self, env):
-        """Hand the cursor to device environment `env`: staged rows are flushed, the environment's records take (ptr, sizes), and from here on
-        the step launches advance the rings and the fill levels in size_dev().  add() refuses until adopt_device_cursor()."""
-        if self._device_env is env:
-            return
-        if self._device_env is not None:
-            raise RuntimeError('ReplayBufferGroup.collect_on_device: another device environment owns the cursor (adopt_device_cursor() first)')
-        if self.n_step > 1 and int(getattr(env, 'num_envs', 1)) != self.n_stride:
-            raise ValueError(f'{type(self).__name__}.collect_on_device: n_step {self.n_step} with n_stride {self.n_stride}, but the device environment '
-                             f'interleaves num_envs = {int(getattr(env, "num_envs", 1))} trajectories per ring: build the buffers with n_stride = num_envs')
-        self.flush()
-        self.size_dev()
-        if getattr(env, 'num_envs', 1) > 1:          # (environment e's cursor is (ptr + e) mod max_size)
-            env.set_cursor(self.ptr, self.sizes, self.max_size)
-        else:
-            env.set_cursor(self.ptr, self.sizes)
-        self._device_env = env
 
     def adopt_device_cursor(self):
         """Take the cursor back from the device environment: ptr and sizes become what its records hold (synchronises), and add() continues
@@ -236,9 +157,7 @@ class ReplayBufferGroup(object):
     def load(self, r, state, action, next_state, reward, done):
         """Bulk-fill member r's ring (tests / synthetic benchmarks), as ReplayBuffer.load does for one ring."""
         n = int(len(state))
-        rows = np.concatenate([np.asarray(state, np.float32).reshape(n, -1), np.asarray(action, np.float32).reshape(n, -1),
-                               np.asarray(next_state, np.float32).reshape(n, -1), np.asarray(reward, np.float32).reshape(n, 1),
-                               np.asarray(done, np.float32).reshape(n, 1)], axis=1)
+        rows = self._pack_rows((n,), state, action, next_state, reward, done)
         self.flush()
         self._before_device_write()
         self.rings[int(r), :n].copy_(torch.from_numpy(rows))
@@ -321,21 +240,12 @@ class PrioritizedReplayBufferGroup(ReplayBufferGroup):
         return ('per_group', self.trees.data_ptr(), self._scal.data_ptr())
 
     # ---- writers: every written row gets its member's running maximum priority ---------------------
-    def _lib(self):
-        import ctypes as C
-        from rlrep_amd._lib import lib, check
-        return C, lib, check
-
     def _per_add(self, start, n):
         if n <= 0:
             return
         if self.device.type == 'cuda':
-            C, lib, check = self._lib()
-            with torch.cuda.device(self.device):
-                check(lib.rlrep_group_per_add(C.c_void_p(self.trees.data_ptr()), self.P, C.c_void_p(self._scal.data_ptr()), self.members, self.max_size,
-                                              int(start), int(n), C.c_void_p(_raw_stream())), 'group_per_add')
+            lib_call(self.device, 'group_per_add', self.trees.data_ptr(), self.P, self._scal.data_ptr(), self.members, self.max_size, int(start), int(n))
         else:
-            from rlrep_amd.utils.buffer import _per_set
             rows = (int(start) + np.arange(int(n))) % self.max_size
             for r in range(self.members):
                 _per_set(self.trees[r].numpy(), self.P, rows, self._scal.numpy()[r, 0])
@@ -343,16 +253,9 @@ class PrioritizedReplayBufferGroup(ReplayBufferGroup):
 
     def _rebuild(self, r):
         if self.device.type == 'cuda':
-            C, lib, check = self._lib()
-            with torch.cuda.device(self.device):
-                check(lib.rlrep_per_rebuild(C.c_void_p(self.trees[r].data_ptr()), self.P, C.c_void_p(_raw_stream())), 'per_rebuild')
+            lib_call(self.device, 'per_rebuild', self.trees[r].data_ptr(), self.P)
         else:
-            t = self.trees[r].numpy()
-            w = self.P >> 1
-            while w >= 1:
-                nd = np.arange(w, 2 * w)
-                t[nd] = t[2 * nd] + t[2 * nd + 1]
-                w >>= 1
+            _per_rebuild_host(self.trees[r].numpy(), self.P)
 
     def flush(self):
         a, n = self._stage_start, self._staged
@@ -371,12 +274,8 @@ class PrioritizedReplayBufferGroup(ReplayBufferGroup):
         r, n = int(r), self.sizes[int(r)]
         self.trees[r].zero_()
         if n > 0 and self.device.type == 'cuda':           # (the single ring's add on member r's slices: it takes no agent)
-            C, lib, check = self._lib()
-            with torch.cuda.device(self.device):
-                check(lib.rlrep_per_add(C.c_void_p(self.trees[r].data_ptr()), self.P, C.c_void_p(self._scal[r].data_ptr()), self.max_size, 0, n,
-                                        C.c_void_p(_raw_stream())), 'per_add')
+            lib_call(self.device, 'per_add', self.trees[r].data_ptr(), self.P, self._scal[r].data_ptr(), self.max_size, 0, n)
         elif n > 0:
-            from rlrep_amd.utils.buffer import _per_set
             _per_set(self.trees[r].numpy(), self.P, np.arange(n), self._scal.numpy()[r, 0])
         self.device_epoch += 1
 
@@ -426,25 +325,18 @@ class PrioritizedReplayBufferGroup(ReplayBufferGroup):
                 raise ValueError(f'PrioritizedReplayBufferGroup.draw: given indices must be [{self.members}, {B}] rows inside each member\'s ring')
             idx.copy_(torch.from_numpy(g.astype(np.int32)))
         if self.device.type == 'cuda':
-            C, lib, check = self._lib()
             if core is None:
                 raise ValueError('PrioritizedReplayBufferGroup.draw: the device sampler runs for a sac seed group (core=group.core)')
-            check(lib.rlrep_group_per_sample(core.h, C.c_void_p(self.trees.data_ptr()), self.P, C.c_void_p(self._scal.data_ptr()), C.c_void_p(idx.data_ptr()),
-                                             C.c_void_p(w.data_ptr()), B, 0 if given is None else 1, int(offset), 1 if use_counter else 0,
-                                             C.c_void_p(self.rings.data_ptr() if gather else None), 4 * self.ring_stride, self.max_size,
-                                             C.c_void_p(_raw_stream())), 'group_per_sample')
+            lib_call(self.device, 'group_per_sample', core.h, self.trees.data_ptr(), self.P, self._scal.data_ptr(), idx.data_ptr(), w.data_ptr(), B,
+                     0 if given is None else 1, int(offset), 1 if use_counter else 0, self.rings.data_ptr() if gather else None, 4 * self.ring_stride,
+                     self.max_size)
             return idx, w
-        from rlrep_amd.utils.buffer import _per_draw
         from rlrep_amd.utils.philox_host import raw_stream as words
         for r in (range(self.members) if live is None else live):
             t = self.trees[r].numpy()
             if given is None:
                 idx[r].copy_(torch.from_numpy(_per_draw(t, self.P, B, words(B, int(seeds[r]), int(offset)))))
-            p = t[self.P + idx[r].numpy().astype(np.int64)]
-            pmin, beta = p.min(), np.float32(self._hyper[r, 1])
-            with np.errstate(divide='ignore', invalid='ignore'):
-                wv = np.power((pmin / p).astype(np.float32), beta, dtype=np.float32)
-            w[r].copy_(torch.from_numpy(np.where((p == pmin) | (beta == 0), np.float32(1.0), wv).astype(np.float32)))
+            w[r].copy_(torch.from_numpy(_per_weights(t, self.P, idx[r].numpy(), self._hyper[r, 1])))
         return idx, w
 
     def update(self, B, td=None, core=None, live=None):
@@ -454,24 +346,13 @@ class PrioritizedReplayBufferGroup(ReplayBufferGroup):
         B = int(B)
         idx, _ = self.draw_buffers(B)
         if self.device.type == 'cuda':
-            C, lib, check = self._lib()
             if core is None:
                 raise ValueError('PrioritizedReplayBufferGroup.update: the device update runs for a sac seed group (core=group.core)')
             if td is not None and (tuple(td.shape) != (self.members, B) or td.dtype != torch.float32 or not td.is_contiguous() or td.device != self.trees.device):
                 raise ValueError(f'PrioritizedReplayBufferGroup.update: td must be a contiguous float32 tensor [{self.members}, {B}] on {self.trees.device}')
-            check(lib.rlrep_group_per_update(core.h, C.c_void_p(self.trees.data_ptr()), self.P, C.c_void_p(self._scal.data_ptr()), C.c_void_p(idx.data_ptr()),
-                                             C.c_void_p(None if td is None else td.data_ptr()), B, C.c_void_p(_raw_stream())), 'group_per_update')
+            lib_call(self.device, 'group_per_update', core.h, self.trees.data_ptr(), self.P, self._scal.data_ptr(), idx.data_ptr(),
+                     None if td is None else td.data_ptr(), B)
             return
-        from rlrep_amd.utils.buffer import _per_set, PER_MIN_PRIORITY
         td = np.asarray(td, np.float32).reshape(self.members, B)
-        s = self._scal.numpy()
         for r in (range(self.members) if live is None else live):
-            t = self.trees[r].numpy()
-            alpha = np.float32(self._hyper[r, 0])
-            new = np.ones(B, np.float32) if alpha == 0 else np.power(td[r] + np.float32(self._hyper[r, 2]), alpha, dtype=np.float32)
-            new = np.where(new > PER_MIN_PRIORITY, new, PER_MIN_PRIORITY).astype(np.float32)
-            rows = idx[r].numpy().astype(np.int64)
-            t[self.P + rows] = 0
-            np.maximum.at(t, self.P + rows, new)
-            s[r, 0] = max(s[r, 0], new.max())
-            _per_set(t, self.P, rows, t[self.P + rows])
+            _per_update_host(self.trees[r].numpy(), self.P, self._scal.numpy()[r], idx[r].numpy(), td[r], self._hyper[r, 0], self._hyper[r, 2])
