@@ -413,6 +413,26 @@ int32_t rlrep_per_update(rlrep_agent* agent, float* tree_dev, int64_t P, float* 
 int32_t rlrep_critic_step_weighted(rlrep_agent* agent, const float* eps_dev, const float* w_dev, void* stream);
 const float* rlrep_per_td_dev(rlrep_agent* agent);
 
+/* ---- prioritized replay of the CRITIC's minibatch for vlsac / ctrlsac / spedersac / diffsrsac (additive to ABI 4; DESIGN.md 6f.1, csrc/per_fill.hip)
+ * These agents reuse the slot-0 minibatch of their last feature step for the critic and actor steps; that minibatch alone is drawn from the
+ * tree (tree, scalars and sampler exactly as above), every other minibatch of a train() stays the uniform draw.
+ *   rlrep_per_sample_fill     rlrep_per_sample and rlrep_replay_sample(slot 0) of the drawn rows in ONE launch: idx_dev[batch] and w_dev[batch] as
+ *                             rlrep_per_sample writes them, ring rows idx into minibatch slot 0.  Never skipped (it overwrites a gather the
+ *                             train prologue or an optimizer launch ran) and a new batch to every prefetch, as rlrep_replay_sample is.
+ *                             capacity: the ring's rows (<= P); no row outside it is read whatever a given index says.
+ *   rlrep_critic_weights_arm  the NEXT rlrep_critic_step / rlrep_critic_backward runs with the critic loss mean_b w[b] ((q1 - y)^2 + (q2 - y)^2)
+ *                             -- whichever program it takes, the one behind rlrep_prefetch_policy_early included; only the head launch differs
+ *                             -- and writes td[b] = 0.5 (|q1 - y| + |q2 - y|) into the CALLER's td_dev.  That step disarms; so do two nulls.
+ *                             Same launch count as the unweighted step.  Returns 1 armed, 0 disarmed.
+ *   rlrep_per_update_td       rlrep_per_update with the caller's td_dev, no agent (as rlrep_per_add has none).
+ * The two entry points that take an agent refuse, by name: a seed group's handle, a sac agent ("use rlrep_per_sample /
+ * rlrep_critic_step_weighted"), world_size > 1. */
+int32_t rlrep_per_sample_fill(rlrep_agent* agent, const float* ring_dev, int64_t capacity, const float* tree_dev, int64_t P, const float* scal_dev,
+                              int32_t* idx_dev, float* w_dev, int32_t batch, int32_t given, uint64_t seed, uint64_t offset, const int32_t* counter_dev,
+                              void* stream);
+int32_t rlrep_critic_weights_arm(rlrep_agent* agent, const float* w_dev, float* td_dev);
+int32_t rlrep_per_update_td(float* tree_dev, int64_t P, float* scal_dev, const int32_t* idx_dev, const float* td_dev, int32_t batch, void* stream);
+
 /* ---- prioritized replay for sac SEED GROUPS (additive to ABI 4; DESIGN.md 6g, csrc/per_group.hip) --------------------------------------------
  * Every member has a tree and a scalar block of its own, owned by the caller: trees_dev float32[members, 2 P] (member m's tree at m * 2 P
  * floats, laid out as above), scal_dev float32[members, 4], the draw buffers idx_dev int32[members, batch] and w_dev float32[members, batch].

@@ -172,6 +172,9 @@ def _load():
         'rlrep_per_update': (i32, [vp, vp, i64, vp, vp, vp, i32, vp]),
         'rlrep_critic_step_weighted': (i32, [vp, vp, vp, vp]),
         'rlrep_per_td_dev': (vp, [vp]),
+        'rlrep_per_sample_fill': (i32, [vp, vp, i64, vp, i64, vp, vp, vp, i32, i32, u64, u64, vp, vp]),
+        'rlrep_critic_weights_arm': (i32, [vp, vp, vp]),
+        'rlrep_per_update_td': (i32, [vp, i64, vp, vp, vp, i32, vp]),
         'rlrep_group_per_add': (i32, [vp, i64, vp, i32, i64, i64, i64, vp]),
         'rlrep_group_per_sample': (i32, [vp, vp, i64, vp, vp, vp, i32, i32, u64, i32, vp, i64, i64, vp]),
         'rlrep_group_per_update': (i32, [vp, vp, i64, vp, vp, vp, i32, vp]),

@@ -437,6 +437,10 @@ class SACAgent(object):
         if (self.steps & 31) == 0:
             self.core.exchange_check()           # (a word in mapped host memory: no synchronisation; a launch that saw a timeout applied nothing)
         form = self._form()
+        if self._cper(buffer) and form == 'two_chains':
+            # the deferred critic / actor chain knows no weights: the one-graph form, whatever `pipeline` says
+            self.flush()
+            return self._train_graph(buffer, batch_size)
         if form == 'two_chains':
             if self._prefer_sequential():
                 self.flush()
@@ -470,6 +474,7 @@ class SACAgent(object):
         if getattr(buffer, 'prioritized_group', False):
             raise RuntimeError(f'{name}.{what}: {cls} is built for SACSeedBatch.train (a sac seed group); a single agent takes a '
                                'PrioritizedReplayBuffer')
+        self._check_critic_per(buffer, what)
         if not self._per(buffer):
             return
         if self.ALG != 'sac':
@@ -480,6 +485,43 @@ class SACAgent(object):
         if what == 'iterate':
             raise RuntimeError(f'{name}.iterate: {cls} cannot be written by a device environment (its step launch knows nothing of the priority '
                                'tree): use a plain ReplayBuffer')
+
+    # ---- prioritized replay of the critic's minibatch (utils/buffer.py CriticPrioritizedReplayBuffer; DESIGN.md 6f.1, csrc/per_fill.hip) -------
+    @staticmethod
+    def _cper(buffer):
+        return bool(getattr(buffer, 'critic_prioritized', False))
+
+    def _check_critic_per(self, buffer, what):
+        """A CriticPrioritizedReplayBuffer trains ONE vlsac / ctrlsac / spedersac / diffsrsac agent on ONE GPU through train(), prepare() and
+        train_injected(); everything else refuses it by its class name, before anything is launched."""
+        if not self._cper(buffer):
+            return
+        name, cls = type(self).__name__, type(buffer).__name__
+        if self.SEED_GROUP:
+            raise RuntimeError(f'{name}.{what}: {cls} does not train a seed group (prioritized critic replay is built for one agent)')
+        if self.ALG == 'sac':
+            raise RuntimeError(f'{name}.{what}: {cls} is built for the representation agents (vlsac, ctrlsac, spedersac, diffsrsac), which prioritize '
+                               'the minibatch their critic reuses; a sac agent owns its whole minibatch: use PrioritizedReplayBuffer')
+        if self.world_size > 1 or self._dp:
+            raise RuntimeError(f'{name}.{what}: {cls} does not train a data-parallel agent (one agent, one GPU)')
+        if what in ('iterate', 'iterate_sim'):
+            raise RuntimeError(f'{name}.{what}: {cls} cannot be written by a device environment or a captured simulator loop (their launches know '
+                               'nothing of the priority tree): use a plain ReplayBuffer')
+
+    def _sample_into_critic_per(self, buffer, B, key, g):
+        """The minibatch the critic reuses, from a CriticPrioritizedReplayBuffer: ONE launch draws the indices and the importance weights into the
+        buffer's draw buffers and gathers the drawn rows into slot 0, where a plain buffer's gather stands -- in front of the last feature
+        step, so rlrep_prefetch_policy_early follows as it does there.  Injected indices take the given-indices mode."""
+        c = self.core
+        if self._inject is not None:
+            idx, _ = buffer.draw_fill(c, B, 0, 0, given=np.asarray(self._inject['idx'].pop(0)))
+        elif g:
+            idx, _ = buffer.draw_fill(c, B, self._seed, self.PER_STREAM, counter_dev=c.steps_dev())
+        else:
+            idx, _ = buffer.draw_fill(c, B, self._seed, self.PER_STREAM + self._ctr)
+        self._bufs['idx_' + key] = idx
+        if self._inject is None and self._pool is not None and key == self._early_key:
+            c.prefetch_policy_early(self._pool['eps_crit'], self._pool['eps_act'])
 
     # ---- n-step returns (utils/buffer.py ReplayBuffer(n_step=, n_stride=); DESIGN.md 6h, csrc/nstep.hip) ------------------------------------
     @staticmethod
@@ -596,7 +638,7 @@ class SACAgent(object):
             return
         self._prepare_only = True
         try:
-            if form == 'two_chains':
+            if form == 'two_chains' and not self._cper(buffer):
                 self._train_graph_pipelined(buffer, batch_size)         # (the two-chain form ...
             self._train_graph(buffer, batch_size)                       #  ... and the one-graph form train() switches to for a caller that looks at the actor between calls)
         finally:
@@ -686,6 +728,7 @@ class SACAgent(object):
         if self._per(buffer) or getattr(buffer, 'prioritized_group', False):
             raise RuntimeError(f'{name}.iterate_sim: {cls} cannot be written by the captured simulator loop (its append launch does not write the '
                                'priority tree): use a plain ReplayBuffer, or the eager act_device / add_device / train() loop')
+        self._check_critic_per(buffer, 'iterate_sim')
         self._check_nstep(buffer, 'iterate_sim')
         self._check_critic_nstep(buffer, 'iterate_sim')
         self._check_front('iterate_sim', loop, buffer, 'simulator loop', 'create the SimLoop after load()', lacks='captured simulator loop')
@@ -924,6 +967,9 @@ class SACAgent(object):
         # slot-0 batches in the order they are consumed: after gathering one, the next is armed to ride in the
         # step's optimizer launch (rlrep_prefetch_batch)
         self._next_key = self._prefetch_chain(idx_keys) if g else {}
+        if self._cper(buffer):      # (the critic's minibatch is drawn by a launch of its own: no optimizer launch gathers it ahead)
+            ck = self._critic_key(B)
+            self._next_key = {k: v for k, v in self._next_key.items() if v != ck}
         o = 0
         for k, sh in eps_specs:
             n = int(np.prod(sh))
@@ -953,6 +999,8 @@ class SACAgent(object):
     def _sample_into(self, buffer, B, key, slot=0, g=False):
         if self._per(buffer):
             return self._sample_into_per(buffer, B, key, g)
+        if self._cper(buffer) and slot == 0 and key == self._critic_key(B):
+            return self._sample_into_critic_per(buffer, B, key, g)
         if self._inject is None and self._pool is not None and ('idx_' + key) in self._pool:
             self._gather(buffer, slot, self._pool['idx_' + key], B)
             self._gather_critic_targets(buffer, slot, key, self._pool['idx_' + key], B)
@@ -1027,6 +1075,11 @@ class SACAgent(object):
         if self._per(buffer):      # (one sac agent, one GPU: _check_per) the weighted critic step, then the |TD| errors it left become priorities
             c.critic_step_weighted(e1, buffer.draw_buffers(B)[1])
             buffer.update(B, core=c)
+        elif self._cper(buffer):   # (one representation agent, one GPU: _check_critic_per) the same step with the weights armed, then the priorities
+            w, td = buffer.draw_buffers(B)[1:]
+            c.critic_weights_arm(w, td)
+            c.critic_step(e1)
+            buffer.update(B)
         elif W > 1:
             if self._critic_trains():
                 c.critic_backward(e1); self._allreduce(1); c.critic_apply()
@@ -1522,7 +1575,7 @@ class SACAgent(object):
             # the whole train() as one hipGraph
             self._graph, self._graph_launches, self._graph_front_ends = self._capture(buffer, B)
             self._graph_key = key
-            if self._per(buffer):
+            if self._per(buffer) or self._cper(buffer):
                 self._held_buffer = buffer          # the cached graph reads its tree and draw buffers: keep it alive as long as the graph
         if self._prepare_only:
             return None

@@ -385,6 +385,14 @@ class HipCore:
             return
         check(lib.rlrep_critic_step_weighted(self.h, _ptr(eps), _ptr(w), _stream()), 'critic_step_weighted')
 
+    def critic_weights_arm(self, w, td):
+        """The next critic_step / critic_backward of a representation agent is the weighted one (rlrep_critic_weights_arm): w[B] in the loss,
+        |TD| into the caller's td[B]; that step disarms."""
+        rc = lib.rlrep_critic_weights_arm(self.h, _ptr(w), _ptr(td))
+        if rc < 0:
+            check(rc, 'critic_weights_arm')
+        return rc == 1
+
     def per_td(self, B):
         """float32[B] view of the |TD| errors the last weighted critic step left in the workspace"""
         if self.members:            # a seed group (member 0's view) or one of its members: the same offset in the member's workspace

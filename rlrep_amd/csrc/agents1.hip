@@ -735,7 +735,7 @@ void build_vlsac(Builder& b, rlrep_agent* ag) {
         q.logp = ab.logp; q.R = s0.Rn; q.D = s0.D; q.alpha_state = ag->a.alpha_state_dev; q.gamma = ag->h.discount;      // (Rn: s0.R unless rlrep_set_critic_nstep)
         q.inv_batch = ag->inv_batch(); q.dq = dq; q.GE[0] = GE; q.GE[1] = GE + BH; q.partial = part_q;
         q.B = B; q.H = H; q.nblk = nblk; q.train = 1; q.step = ag->adam_step + 1;
-        p.stages.push_back({[=](hipStream_t st) { return rl_launch_qhead_critic(&q, st); }, "qhead critic"});
+        p.stages.push_back({[=](hipStream_t st) { return critic_head_launch(ag, q, st); }, "qhead critic"});
         b.dx_stage(p, {Builder::dx(GE, H, B, H, Pw("critic.l2.weight"), H, GHm, H, H, ACT_NONE, nullptr, 0),
                        Builder::dx(GE + BH, H, B, H, Pw("critic.l5.weight"), H, GHm + BH, H, H, ACT_NONE, nullptr, 0)}, "critic l2/l5 dx");
         b.dw_stage(p, {Builder::dw(dq, 1, 1, Ec, H, H, 2 * B, Gw("critic.l3.weight"), H, Gw("critic.l3.bias")),     // shared l3: heads stacked

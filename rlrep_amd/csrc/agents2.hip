@@ -154,7 +154,7 @@ static void qhead_critic_stage(Program& p, rlrep_agent* ag, const float* Et0, co
     q.logp = logp; q.R = ag->slot[0].Rn; q.D = ag->slot[0].D; q.alpha_state = ag->a.alpha_state_dev; q.gamma = ag->h.discount;      // (Rn: slot[0].R unless rlrep_set_critic_nstep)
     q.inv_batch = ag->inv_batch(); q.dq = dq; q.GE[0] = GE0; q.GE[1] = GE1; q.partial = part_q;
     q.B = ag->B; q.H = H; q.nblk = nblk; q.train = train; q.step = train ? ag->adam_step + 1 : nullptr;
-    p.stages.push_back({[=](hipStream_t st) { return rl_launch_qhead_critic(&q, st); }, "qhead critic"});
+    p.stages.push_back({[=](hipStream_t st) { return critic_head_launch(ag, q, st); }, "qhead critic"});
 }
 static void qhead_actor_stage(Program& p, rlrep_agent* ag, const float* Ec0, const float* Ec1, int ldE, const float* wc0, const float* bc0,
                               const float* wc1, const float* bc1, const float* logp, float* GE0, float* GE1, float* part_l, int H, int nblk) {

@@ -834,12 +834,18 @@ int32_t rlrep_prefetch_policy(rlrep_agent* ag, const float* eps_actor) {
 int critic_backward_dispatch(rlrep_agent* ag, const float* eps, const float* w, void* stream) {
     STEP_PROLOGUE(false)
     if (!eps) { rl_set_error("critic step needs eps[B,A]"); return RLREP_ERR_ARG; }
+    // rlrep_critic_weights_arm (never sac): this backward is the weighted one, whichever of the agent's programs it takes -- their head stage
+    // looks at cur_w when it launches (critic_head_launch) -- and it disarms
+    const bool armed = !w && ag->arm_w;
+    if (armed) { w = ag->arm_w; ag->cur_td = ag->arm_td; }
+    ag->arm_w = nullptr; ag->arm_td = nullptr;
+    struct Disarm { rlrep_agent* a; ~Disarm() { a->cur_w = nullptr; a->cur_td = nullptr; } } disarm_{ag};      // (a deferred chain's head must find none)
     ag->cur_eps = eps; ag->cur_w = w; ag->last_launches = 0;
     ag->pi_ready = nullptr;
     // the images of critic.l1 / l4 and of their targets, from the tensors as they are now: the target copies have no other writer, and a
     // caller may have written any of them since the last step (the launch rides on the chain that has slack in the pipelined train())
     if (!ag->images_managed) { const int rs = refresh_x3(ag, stream); if (rs) return rs; }
-    if (!w && ag->early_ready_crit && ag->early_ready_crit == eps) {      // both policy forwards already ran (last feature step; never for sac)
+    if ((!w || armed) && ag->early_ready_crit && ag->early_ready_crit == eps) {      // both policy forwards already ran (last feature step; never for sac)
         const float* act_eps = ag->early_ready_act;
         ag->early_ready_crit = ag->early_ready_act = nullptr; ag->hoist_req = nullptr;
         const int rc = run(ag, ag->critic_bwd_h2, stream);
@@ -847,7 +853,8 @@ int critic_backward_dispatch(rlrep_agent* ag, const float* eps, const float* w, 
         return rc;
     }
     ag->early_ready_crit = ag->early_ready_act = nullptr;
-    const Program& hoisted = w ? ag->critic_bwd_wh : ag->critic_bwd_h;
+    const bool own = w && !armed;             // sac's weighted programs (rlrep_critic_step_weighted); an armed step runs the agent's own
+    const Program& hoisted = own ? ag->critic_bwd_wh : ag->critic_bwd_h;
     if (ag->hoist_req && !hoisted.stages.empty()) {
         ag->cur_eps2 = ag->hoist_req; ag->hoist_req = nullptr;
         const int rc = run(ag, hoisted, stream);
@@ -855,7 +862,7 @@ int critic_backward_dispatch(rlrep_agent* ag, const float* eps, const float* w, 
         return rc;
     }
     ag->hoist_req = nullptr;
-    return run(ag, w ? ag->critic_bwd_w : ag->critic_bwd, stream);
+    return run(ag, own ? ag->critic_bwd_w : ag->critic_bwd, stream);
 }
 int32_t rlrep_critic_backward(rlrep_agent* ag, const float* eps, void* stream) { return critic_backward_dispatch(ag, eps, nullptr, stream); }
 int32_t rlrep_critic_apply(rlrep_agent* ag, void* stream) {
@@ -950,6 +957,58 @@ int32_t rlrep_critic_step_weighted(rlrep_agent* ag, const float* eps, const floa
     if (ag->critic_bwd_w.stages.empty()) { rl_set_error("critic_step_weighted: no weighted critic program was built for this agent"); return RLREP_ERR_STATE; }
     const int rc = critic_backward_dispatch(ag, eps, w, stream);
     return rc ? rc : rlrep_critic_apply(ag, stream);
+}
+
+// ---- prioritized replay of the critic's minibatch for vlsac / ctrlsac / spedersac / diffsrsac (per_fill.hip) ------------
+// the entry points that work for ONE representation agent on ONE GPU
+static int cper_agent_ok(const char* what, const rlrep_agent* ag) {
+    if (!ag) { rl_set_error("%s: null agent", what); return RLREP_ERR_ARG; }
+    if (ag->members > 0) { rl_set_error("%s: not available on a seed group (rlrep_group_create): prioritized critic replay is built for one agent", what); return RLREP_ERR_ARG; }
+    if (ag->d.alg == RLREP_ALG_SAC) { rl_set_error("%s: a sac agent owns its whole minibatch: use rlrep_per_sample / rlrep_critic_step_weighted", what); return RLREP_ERR_ARG; }
+    if (ag->h.world_size > 1) { rl_set_error("%s: prioritized critic replay runs on one GPU (world_size = %d)", what, ag->h.world_size); return RLREP_ERR_ARG; }
+    return 0;
+}
+// rlrep_per_sample and rlrep_replay_sample(slot 0) of the drawn rows in ONE launch.  Never skipped: it overwrites whatever gather the train
+// prologue or an optimizer launch ran.
+int32_t rlrep_per_sample_fill(rlrep_agent* ag, const float* ring_dev, int64_t capacity, const float* tree_dev, int64_t P, const float* scal_dev, int32_t* idx_dev,
+                              float* w_dev, int32_t batch, int32_t given, uint64_t seed, uint64_t offset, const int32_t* counter_dev, void* stream) {
+    if (int rc = cper_agent_ok("per_sample_fill", ag)) return rc;
+    if (!per_tree_ok("per_sample_fill", tree_dev, P, scal_dev)) return RLREP_ERR_ARG;
+    if (!ring_dev || !idx_dev || !w_dev || batch < 1) { rl_set_error("per_sample_fill: bad argument (null ring / idx / w, or batch %d)", batch); return RLREP_ERR_ARG; }
+    if (capacity < 1 || capacity > P) { rl_set_error("per_sample_fill: a ring of %lld rows under a tree of %lld leaves", (long long)capacity, (long long)P); return RLREP_ERR_ARG; }
+    // a new batch: what rlrep_replay_sample invalidates
+    ag->pf_done = false; ag->l1_done = false; ag->chain_next = false;
+    ag->pi_ready = nullptr; ag->hoist_req = nullptr;
+    ag->early_crit = ag->early_act = ag->early_ready_crit = ag->early_ready_act = nullptr;
+    int rc = ensure_batch(ag, batch);
+    if (rc) return rc;
+    PerSampleFill p; memset(&p, 0, sizeof(p));
+    p.s.tree = tree_dev; p.s.scal = scal_dev; p.s.idx = idx_dev; p.s.w = w_dev; p.s.P = P; p.s.B = batch; p.s.given = given ? 1 : 0;
+    p.s.seed = seed; p.s.offset = offset; p.s.step_dev = counter_dev;
+    slot_fill_params(ag, 0, ring_dev, nullptr, p.f);
+    p.capacity = capacity;
+    ag->slot[0].filled = true;
+    rc = (++g_rl_launches, rl_launch_per_sample_fill(&p, (hipStream_t)stream));
+    if (rc) { rl_set_error("per_sample_fill: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+// The next rlrep_critic_step / rlrep_critic_backward is the weighted one: w[B] in the loss, td[b] = 0.5 (|q1 - y| + |q2 - y|) into the
+// caller's td_dev.  That step disarms; so does passing null.
+int32_t rlrep_critic_weights_arm(rlrep_agent* ag, const float* w_dev, float* td_dev) {
+    if (int rc = cper_agent_ok("critic_weights_arm", ag)) return rc;
+    if ((w_dev == nullptr) != (td_dev == nullptr)) { rl_set_error("critic_weights_arm: needs w[B] and td[B] (or neither, to disarm)"); return RLREP_ERR_ARG; }
+    ag->arm_w = w_dev; ag->arm_td = td_dev;
+    return w_dev ? 1 : 0;
+}
+// rlrep_per_update with the caller's |TD| array and no agent (as rlrep_per_add has none)
+int32_t rlrep_per_update_td(float* tree_dev, int64_t P, float* scal_dev, const int32_t* idx_dev, const float* td_dev, int32_t batch, void* stream) {
+    if (!per_tree_ok("per_update_td", tree_dev, P, scal_dev)) return RLREP_ERR_ARG;
+    if (!idx_dev || !td_dev || batch < 1) { rl_set_error("per_update_td: bad argument (null idx / td, or batch %d)", batch); return RLREP_ERR_ARG; }
+    PerUpdate p; memset(&p, 0, sizeof(p));
+    p.tree = tree_dev; p.scal = scal_dev; p.idx = idx_dev; p.td = td_dev; p.P = P; p.B = batch;
+    const int rc = (++g_rl_launches, rl_launch_per_update(&p, (hipStream_t)stream));
+    if (rc) { rl_set_error("per_update_td: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
 }
 
 int32_t rlrep_actor_alpha_step(rlrep_agent* ag, const float* eps, void* stream) {

@@ -40,6 +40,10 @@ struct rlrep_agent {
     // prioritized replay (sac; per.hip): the critic programs whose head stage is the weighted kernel (rlrep_critic_step_weighted; the apply
     // programs are the unweighted ones), the per-sample weights of the call in progress and the |TD| errors the head leaves for rlrep_per_update
     Program critic_bwd_w, critic_bwd_wh; const float* cur_w = nullptr; float* per_td = nullptr;
+    // the same for vlsac / ctrlsac / spedersac / diffsrsac: the head stage of EVERY critic program of theirs launches the
+    // weighted kernel while cur_w is set (critic_head_launch), so no program is built twice.  rlrep_critic_weights_arm leaves the weights and
+    // the caller's |TD| array here; the next critic backward takes them (cur_w, cur_td) and disarms
+    const float* arm_w = nullptr; float* arm_td = nullptr; float* cur_td = nullptr;
     // Inside a rlrep_begin_train .. rlrep_update_target bracket the Polyak critic -> critic_target is folded into the
     // critic's Adam launch (critic_apply_f): nothing between the two reads critic_target, and the update_target launch
     // (~2 us + a launch boundary) disappears.  Outside a bracket every entry point does exactly what its name says.
@@ -735,6 +739,14 @@ int ensure_batch(rlrep_agent* ag, int B);
 extern "C" {
 int critic_backward_dispatch(rlrep_agent* ag, const float* eps, const float* w, void* stream);
 bool per_tree_ok(const char* what, const float* tree, int64_t P, const float* scal);
+}
+// The head stage of every critic program of vlsac / ctrlsac / spedersac / diffsrsac: qhead_critic_kernel, or -- while a weighted critic
+// backward is in progress (rlrep_critic_weights_arm) -- the weighted head of per.hip with the call's weights and |TD| array.  One stage,
+// one launch either way: the weighted form of a program is the program.
+inline int critic_head_launch(const rlrep_agent* ag, const QHeadCritic& q, hipStream_t st) {
+    if (!ag->cur_w) return rl_launch_qhead_critic(&q, st);
+    QHeadCriticW qw; qw.q = q; qw.w = ag->cur_w; qw.td = ag->cur_td;
+    return rl_launch_qhead_critic_w(&qw, st);
 }
 // a seed group's launches for the duration of a library call: while one is alive, rl_grp_active() answers with the agent's group
 struct GrpScope {

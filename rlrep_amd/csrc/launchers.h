@@ -82,6 +82,8 @@ int rl_launch_per_rebuild(float* tree, long long P, hipStream_t st);
 int rl_launch_per_sample(const PerSample* p, hipStream_t st);
 int rl_launch_per_update(const PerUpdate* p, hipStream_t st);
 int rl_launch_qhead_critic_w(const QHeadCriticW* p, hipStream_t st);                // its group form (per_group.hip) while a group is active
+// ---- per_fill.hip (prioritized replay of the representation agents' critic minibatch: sample + slot gather, workgroup 0 samples, the rest gather) ----
+int rl_launch_per_sample_fill(PerSampleFill* p, hipStream_t st);                    // sets p->rows
 // ---- per_group.hip (prioritized replay of a sac seed group: one workgroup per member; all but per_add need an active group) ----
 int rl_launch_per_add_grp(const PerAdd* p, int members, hipStream_t st);                                    // member m: tree + m * 2P, scal + 4 m
 int rl_launch_per_sample_grp(const PerSample* p, hipStream_t st);

@@ -61,6 +61,10 @@ envs/sim_loop.py): the act launch reads its call counter from a loop record on t
 (Philox draws of the agent's seed instead of the torch generator's), `TorchPendulum(capturable=True).step_`, the append launch and train()
 are captured together.  Evaluations are the eager ones of --torch-envs.
 
+`--critic-per` (vlsac, ctrlsac, spedersac, diffsrsac; one agent) trains from a CriticPrioritizedReplayBuffer: the minibatch the critic and actor
+steps reuse is drawn from a sum tree on the device, the critic loss is weighted and the |TD| errors come back as priorities (DESIGN.md
+6f.1); --per-alpha / --per-beta and the annealing of beta as for --per.  With the plain loop, --host-envs and --torch-envs.
+
 The loops differ in what an iteration is, who draws the exploring action and whether there is an initial evaluation; what they do at an
 evaluation step -- anneal beta, take the rate, evaluate, write the row, print, --save_model -- is one copy per side: _Evaluations for one
 agent, _GroupEvaluations for a seed group.
@@ -157,6 +161,12 @@ def run(argv=None):
                    help='prioritized experience replay (Schaul et al. 2016; --alg sac, one agent): train() samples in proportion to '
                         '(|TD| + eps)^alpha from a sum tree on the device and weights the critic loss; beta is annealed linearly to 1 at '
                         '--max_timesteps, written at every evaluation.  Runs with the plain loop, --host-envs and --torch-envs')
+    p.add_argument('--critic-per', action='store_true',
+                   help='prioritized replay of the critic minibatch (--alg vlsac, ctrlsac, spedersac or diffsrsac; one agent): the minibatch the critic '
+                        'and actor steps reuse is drawn in proportion to (|TD| + eps)^alpha and the critic loss is weighted, while every other '
+                        'feature minibatch stays uniform; --per-alpha / --per-beta as for --per, beta annealed to 1 at --max_timesteps.  Runs with '
+                        'the plain loop, --host-envs and --torch-envs; not with --seeds / --sweep, --device-loop, --sim-graph or --critic-n-step '
+                        '(--alg sac takes --per)')
     p.add_argument('--per-alpha', default=0.6, type=float, help='priority exponent alpha (0 = uniform replay; default 0.6)')
     p.add_argument('--per-beta', default=0.4, type=float, help='initial importance-sampling exponent beta (default 0.4)')
     p.add_argument('--group-per', action='store_true',
@@ -182,6 +192,7 @@ def run(argv=None):
     _check_critic_nstep(args)
     _check_group_per(args)
     _check_per(args)
+    _check_critic_per(args)
     _check_num_envs(args)
     _check_host_envs(args)
     _check_torch_envs(args)
@@ -209,6 +220,9 @@ def run(argv=None):
     if getattr(args, 'per', False):
         replay = buffer.PrioritizedReplayBuffer(state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)), alpha=args.per_alpha, beta=args.per_beta,
                                                 **_nstep_kw(args))
+    elif getattr(args, 'critic_per', False):
+        replay = buffer.CriticPrioritizedReplayBuffer(state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)), alpha=args.per_alpha,
+                                                      beta=args.per_beta, **_nstep_kw(args))
     else:
         replay = buffer.ReplayBuffer(state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)), **_nstep_kw(args))
     ev = _Evaluations(args, agent, replay, os.path.join(_log_root(args), str(args.seed)))
@@ -330,6 +344,27 @@ def _check_per(args):
     _check_per_exponents('--per', args)
 
 
+def _check_critic_per(args):
+    """--critic-per: SystemExit, before anything touches the GPU, on what prioritized replay of the critic minibatch does not run with (a
+    namespace without the field is a run without it)"""
+    if not getattr(args, 'critic_per', False):
+        return
+    if args.alg == 'sac':
+        raise SystemExit('--critic-per: a sac agent owns its whole minibatch: give --per (--critic-per is for --alg vlsac, ctrlsac, spedersac and '
+                         'diffsrsac, whose critic reuses the last feature minibatch)')
+    if args.alg not in ('vlsac', 'ctrlsac', 'spedersac', 'diffsrsac'):
+        raise SystemExit(f'--critic-per: built for --alg vlsac, ctrlsac, spedersac and diffsrsac (got --alg {args.alg})')
+    for flag, given in (('--per', getattr(args, 'per', False)), ('--group-per', getattr(args, 'group_per', False)),
+                        ('--seeds', getattr(args, 'seeds', None) is not None), ('--sweep', bool(getattr(args, 'sweep', None))),
+                        ('--device-env', getattr(args, 'device_env', False)), ('--device-loop', getattr(args, 'device_loop', False)),
+                        ('--sim-graph', getattr(args, 'sim_graph', False)), ('--critic-n-step', int(getattr(args, 'critic_n_step', 1)) > 1),
+                        ('--n-step', int(getattr(args, 'n_step', 1)) > 1)):
+        if given:
+            raise SystemExit(f'--critic-per: prioritized critic replay trains ONE agent from a ring the host or add_device fills, with one-step '
+                             f'targets; it does not go with {flag}')
+    _check_per_exponents('--critic-per', args)
+
+
 def _check_group_per(args):
     """--group-per: SystemExit, before anything touches the GPU, on what prioritized replay of a seed group does not run with (a namespace
     without the field is a run without it)"""
@@ -358,7 +393,7 @@ def _check_per_exponents(flag, args):
 def _per_anneal(args, replay, t):
     """--per / --group-per: beta rises linearly from --per-beta to 1.0 at --max_timesteps; written (one device word per member) at the evaluation
     boundaries"""
-    if getattr(args, 'per', False) or getattr(args, 'group_per', False):
+    if getattr(args, 'per', False) or getattr(args, 'group_per', False) or getattr(args, 'critic_per', False):
         frac = min(1.0, float(t) / float(args.max_timesteps))
         replay.beta = 1.0 if frac >= 1.0 else float(args.per_beta) + (1.0 - float(args.per_beta)) * frac
 

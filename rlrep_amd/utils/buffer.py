@@ -586,7 +586,7 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         B = int(B)
         if self.size == 0:
             raise RuntimeError('PrioritizedReplayBuffer.draw: the buffer is empty')
-        idx, w = self.draw_buffers(B)
+        idx, w = self.draw_buffers(B)[:2]
         if given is not None:
             g = np.asarray(given.cpu() if torch.is_tensor(given) else given).reshape(-1)
             if len(g) != B or g.min() < 0 or g.max() >= self.size:
@@ -610,7 +610,7 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         """leaf idx[j] <- (td[j] + eps)^alpha for the last draw of B (1 when alpha == 0; the maximum where an index repeats), max_priority
         follows, the ancestors are recomputed.  On the device ONE launch; td=None: the |TD| errors the agent's last weighted critic step left."""
         B = int(B)
-        idx, _ = self.draw_buffers(B)
+        idx = self.draw_buffers(B)[0]
         if self.device.type == 'cuda':
             if core is None:
                 raise ValueError('PrioritizedReplayBuffer.update: the device update runs for a sac agent (core=agent.core)')
@@ -619,3 +619,71 @@ class PrioritizedReplayBuffer(ReplayBuffer):
             return
         _per_update_host(self.tree.numpy(), self.P, self._scal.numpy(), idx.numpy(), np.asarray(td, np.float32).reshape(B), self._hyper[0],
                          self._hyper[2])
+
+
+# ---- prioritized replay of the critic's minibatch for vlsac / ctrlsac / spedersac / diffsrsac: DESIGN.md 6f.1, csrc/per_fill.hip ----------
+class CriticPrioritizedReplayBuffer(PrioritizedReplayBuffer):
+    """PrioritizedReplayBuffer for the representation agents (VLSACAgent, CTRLSACAgent, SPEDERSACAgent, DIFFSRSACAgent), with another sampling
+    contract -- hence another name, as critic_n_step stands to n_step.  These agents run their critic and actor steps on the slot-0 minibatch
+    of their LAST feature step; that minibatch alone is drawn from the tree (the parent's sampler, unchanged), the critic loss takes its
+    importance weights and the |TD| errors come back as priorities in the same train().  Every other minibatch of the call -- the earlier
+    feature steps, spedersac's second slot -- stays the uniform draw a plain ReplayBuffer gives at the same seed and step, and the feature
+    losses take no weights: the last feature step sees the prioritized rows unweighted (DESIGN.md 6f.1 says what that costs).  The tree, the
+    scalars, the writers, save / restore and the CPU fallback are the parent's; the draw buffers gain td float32[B], which the weighted
+    critic head writes and update() reads.  One agent, one GPU, the one-graph or eager train(); SACAgent takes the parent class."""
+    prioritized = False               # (NOT the parent's contract: what refuses a PrioritizedReplayBuffer must not mistake this class for one)
+    critic_prioritized = True
+    _CRITIC_NSTEP_REFUSAL = 'n-step critic targets together with prioritized critic replay are not built'
+
+    def __init__(self, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, shard=None, alpha=0.6, beta=0.4, eps=1e-6,
+                 n_step=1, n_stride=1, critic_n_step=1):
+        if shard is not None:
+            raise ValueError('CriticPrioritizedReplayBuffer: shard= is not supported (a shard sees one transition in `world`; priorities are per ring)')
+        if not isinstance(n_step, bool) and int(n_step) == n_step and int(n_step) > 1:
+            raise ValueError(f'CriticPrioritizedReplayBuffer: n_step {int(n_step)} > 1 is not supported (n_step is the whole minibatch of a sac agent, '
+                             'which takes a PrioritizedReplayBuffer)')
+        super().__init__(state_dim, action_dim, max_size=max_size, device=device, stage_rows=stage_rows, alpha=alpha, beta=beta, eps=eps,
+                         n_step=n_step, n_stride=n_stride, critic_n_step=critic_n_step)
+
+    def per_key(self):
+        """what a captured train() bakes in besides the ring: the tree and the scalar block, under this class's own tag"""
+        return ('critic_per', self.tree.data_ptr(), self._scal.data_ptr())
+
+    def collect_on_device(self, env):
+        raise RuntimeError('CriticPrioritizedReplayBuffer.collect_on_device: a device environment writes ring rows inside its step launch, which '
+                           'knows nothing of the priority tree (iterate() / --device-loop take a plain ReplayBuffer)')
+
+    def draw_buffers(self, B):
+        """(idx int32[B], w float32[B], td float32[B]) on the ring's device, one triple per batch size for the life of the buffer"""
+        bufs = self._draw_bufs.get(int(B))
+        if bufs is None:
+            bufs = self._draw_bufs[int(B)] = super().draw_buffers(B) + (torch.zeros(int(B), dtype=torch.float32, device=self.device),)
+        return bufs
+
+    def draw_fill(self, core, B, seed, offset, counter_dev=None, given=None):
+        """The critic's minibatch of a representation agent (`core`: its HipCore): B stratified draws and their importance weights as draw()
+        computes them, and the drawn ring rows gathered into the agent's minibatch slot 0 -- ONE launch on the current stream
+        (rlrep_per_sample_fill).  `given` (int32[B]): take these indices, compute only the weights, gather.  -> (idx, w)."""
+        B = int(B)
+        if self.size == 0:
+            raise RuntimeError('CriticPrioritizedReplayBuffer.draw_fill: the buffer is empty')
+        idx, w, _ = self.draw_buffers(B)
+        if given is not None:
+            g = np.asarray(given.cpu() if torch.is_tensor(given) else given).reshape(-1)
+            if len(g) != B or g.min() < 0 or g.max() >= self.size:
+                raise ValueError(f'CriticPrioritizedReplayBuffer.draw_fill: given indices must be {B} rows in [0, {self.size})')
+            idx.copy_(torch.from_numpy(g.astype(np.int32)))
+        self._order_reads()
+        lib_call(self.device, 'per_sample_fill', core.h, self.ring.data_ptr(), self.max_size, self.tree.data_ptr(), self.P, self._scal.data_ptr(),
+                 idx.data_ptr(), w.data_ptr(), B, 0 if given is None else 1, int(seed), int(offset), counter_dev)
+        return idx, w
+
+    def update(self, B, td=None, core=None):
+        """The parent's update() from this buffer's own td array (td=None: what the last weighted critic step wrote there).  On the device ONE
+        launch that needs no agent (rlrep_per_update_td)."""
+        B = int(B)
+        idx, _, own = self.draw_buffers(B)
+        if self.device.type == 'cuda':
+            lib_call(self.device, 'per_update_td', self.tree.data_ptr(), self.P, self._scal.data_ptr(), idx.data_ptr(), (own if td is None else td).data_ptr(), B)
+            return
+        super().update(B, own if td is None else td)
