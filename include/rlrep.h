@@ -641,6 +641,51 @@ int32_t rlrep_gemm16_table(int32_t la, int32_t lb, int32_t nf, const rlrep_gemm1
 int32_t rlrep_gemm_plan(int32_t la, int32_t lb, int32_t rows, int32_t cols, int32_t inner, int32_t lda, int32_t ldb, int32_t ldc,
                         int32_t* engine, int32_t* tile, int32_t* splits, int32_t* kchunk, int32_t* scalar_sides);
 
+/* Unit-test hook of the representation-loss kernels (csrc/replearn.hip; tests/test_replearn_kernels.py): ONE launch of one kernel on caller
+ * buffers, with no agent, through the launcher the step programs use and with the block counts the program builder computes.  The records
+ * carry the fields of the launch records (csrc/kparams.h) except the group counter (always null: nothing is bumped), the data-parallel slot
+ * descriptor (always world 1) and the block counts.  No group form is reachable this way.
+ *   RLREP_RL_INFONCE        ctrlsac InfoNCE on given scores S [B, ncols] (in place: dS out); rhat given, or Z / theta_w / theta_b given (ZM null)
+ *   RLREP_RL_SCORE_INFONCE  the score matrix S = Z ZM^T and its InfoNCE in one launch (S out only); needs F % 64 == 0, ncols <= 256,
+ *                           ldZ % 4 == 0, ldZM % 4 == 0 and Z, ZM, theta_w on 16-byte boundaries
+ *   RLREP_RL_COLSUM         out[f] = sum_k w[k] X[k, f] (w null: plain); X2 given: a second set in the same launch (+ outb2 = sum of w2, optional)
+ *   RLREP_RL_SPEDER_ROWS / RLREP_RL_SPEDER_GRADS   spedersac's spectral loss rows / its gradients ([2B, F] blocks)
+ *   RLREP_RL_PERTURB / RLREP_RL_SCORE              diffsrsac's perturbation / denoising score matching (U [B, F, S] in, dU out in place)
+ *   RLREP_RL_REG_STATS      diffsrsac's ELU-layer regulariser statistics of four (x [B, H], Gram matrix [H, H]) pairs; partial has
+ *                           4 * (ceil(H*H / 1024) + ceil(B / 4)) floats
+ *   RLREP_RL_COPY2          d1[i] = d2[i] = src[i] (d2 may be null)
+ * partial of the InfoNCE / spectral rows kernels: 2 / 3 floats per block, min(ceil(B / 4), 128) blocks (row i in block (i / 4) % blocks);
+ * of the fused form 2 per block of 16 rows; of score matching one per sample.
+ * Refused with RLREP_ERR_ARG and a message starting "replearn:", before any GPU call: an unknown kernel, a null required pointer, a
+ * non-positive extent, a row stride below the row's width, diag_off < 0 or diag_off + B > ncols, a regulariser batch below 2, the fused
+ * form's preconditions above, and a score-matching S whose row kernel would need more than 64 KB of dynamic LDS (5 * S floats). */
+enum { RLREP_RL_INFONCE = 0, RLREP_RL_SCORE_INFONCE = 1, RLREP_RL_COLSUM = 2, RLREP_RL_SPEDER_ROWS = 3, RLREP_RL_SPEDER_GRADS = 4,
+       RLREP_RL_PERTURB = 5, RLREP_RL_SCORE = 6, RLREP_RL_REG_STATS = 7, RLREP_RL_COPY2 = 8 };
+typedef union rlrep_replearn_args {
+    struct { float* S; int32_t ldS, ncols, diag_off; const float* rhat; const float* r; float* drhat; float* partial; int32_t B; float inv_batch;
+             const float* Z; int32_t ldZ, F; const float* theta_w; const float* theta_b; const float* ZM; int32_t ldZM; } infonce;
+    struct { const float* X; int32_t ldX; const float* w; float* out; int32_t rows, F;
+             const float* X2; int32_t ldX2; const float* w2; float* out2; float* outb2; int32_t rows2; } colsum;
+    struct { const float* phi; const float* mu; const float* mu_r; const float* phibar; const float* theta_w; const float* theta_b; const float* r;
+             float* c; float* drhat; float* partial; int32_t B, F; float inv_batch; } speder_rows;
+    struct { const float* phi; const float* mu; const float* c; const float* drhat; const float* phibar; const float* v; const float* theta_w;
+             float* Gphi; float* Gmu; int32_t B, F; float inv_batch; } speder_grads;
+    struct { const float* alphabars; const int32_t* idx; const float* s2; int32_t ld_s2; const float* eps; float* XN; float* TGT; int32_t B, S; } perturb;
+    struct { float* U; const float* PHI; const float* TGT; const float* alphabars; const int32_t* idx; float* GPHI; float* partial;
+             int32_t B, F, S; float sigma, inv_batch; } score;
+    struct { const float* X[4]; const float* C[4]; int32_t B, H; float lambda; float* partial; } reg_stats;
+    struct { const float* src; float* d1; float* d2; int64_t n; } copy2;
+} rlrep_replearn_args;
+int32_t rlrep_replearn(int32_t kernel, const rlrep_replearn_args* args, void* stream);
+
+/* Host-only (no GPU call): the kernel the score-matching launcher picks for a [F, S] block per sample whose U is (u_aligned16 != 0) or is not
+ * on a 16-byte boundary, under the RLREP_ENABLE=score_ch / RLREP_DISABLE=score_small settings in force at the call.  *form:
+ * one pass through LDS in column chunks of 32 / 64 / 128 floats, a thread per row with 1 / 2 / 4 rows per thread, the 16-byte two-pass
+ * kernel, the lanes-over-columns two-pass kernel. */
+enum { RLREP_SCORE_LDS32 = 0, RLREP_SCORE_LDS64 = 1, RLREP_SCORE_LDS128 = 2, RLREP_SCORE_SMALL1 = 3, RLREP_SCORE_SMALL2 = 4, RLREP_SCORE_SMALL4 = 5,
+       RLREP_SCORE_VEC = 6, RLREP_SCORE_ROWS = 7 };
+int32_t rlrep_diffsr_score_plan(int32_t S, int32_t F, int32_t u_aligned16, int32_t* form);
+
 /* Host-only: the engine the builder picks for the vlsac noise critic's first layer (vlsac_agent.py:44-63) with `heads` heads in one
  * launch -- *engine 0 = fp32 MFMA, 1 = bf16x3 (needs F % 32 == 0 and 16-byte rows; RLREP_NC_X3=0 turns it off) -- and its
  * workgroup tile: *rows batch rows x *cols hidden units. */

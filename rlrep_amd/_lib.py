@@ -66,6 +66,54 @@ class Gemm16Task(C.Structure):
                 ('r1u', C.c_void_p), ('r1v', C.c_void_p), ('scale', C.c_float)]
 
 
+RL_KERNEL = {'infonce': 0, 'score_infonce': 1, 'colsum': 2, 'speder_rows': 3, 'speder_grads': 4, 'perturb': 5, 'score': 6, 'reg_stats': 7, 'copy2': 8}
+SCORE_FORM = ('LDS32', 'LDS64', 'LDS128', 'SMALL1', 'SMALL2', 'SMALL4', 'VEC', 'ROWS')          # RLREP_SCORE_* of include/rlrep.h, by value
+
+
+def _rec(spec):
+    """ctypes fields from 'p:a,b i:c f:d' (p pointer, i int32, f float, l int64), in declaration order"""
+    kinds = {'p': C.c_void_p, 'i': C.c_int32, 'f': C.c_float, 'l': C.c_int64}
+    return [(n, kinds[part[0]]) for part in spec.split() for n in part[2:].split(',')]
+
+
+class _RlInfoNce(C.Structure):
+    _fields_ = _rec('p:S i:ldS,ncols,diag_off p:rhat,r,drhat,partial i:B f:inv_batch p:Z i:ldZ,F p:theta_w,theta_b,ZM i:ldZM')
+
+
+class _RlColSum(C.Structure):
+    _fields_ = _rec('p:X i:ldX p:w,out i:rows,F p:X2 i:ldX2 p:w2,out2,outb2 i:rows2')
+
+
+class _RlSpederRows(C.Structure):
+    _fields_ = _rec('p:phi,mu,mu_r,phibar,theta_w,theta_b,r,c,drhat,partial i:B,F f:inv_batch')
+
+
+class _RlSpederGrads(C.Structure):
+    _fields_ = _rec('p:phi,mu,c,drhat,phibar,v,theta_w,Gphi,Gmu i:B,F f:inv_batch')
+
+
+class _RlPerturb(C.Structure):
+    _fields_ = _rec('p:alphabars,idx,s2 i:ld_s2 p:eps,XN,TGT i:B,S')
+
+
+class _RlScore(C.Structure):
+    _fields_ = _rec('p:U,PHI,TGT,alphabars,idx,GPHI,partial i:B,F,S f:sigma,inv_batch')
+
+
+class _RlRegStats(C.Structure):
+    _fields_ = [('X', C.c_void_p * 4), ('C', C.c_void_p * 4)] + _rec('i:B,H f:lam p:partial')
+
+
+class _RlCopy2(C.Structure):
+    _fields_ = _rec('p:src,d1,d2 l:n')
+
+
+class ReplearnArgs(C.Union):
+    """rlrep_replearn_args (include/rlrep.h): the record of one rlrep_replearn launch (reg_stats.lam is the header's `lambda`)."""
+    _fields_ = [('infonce', _RlInfoNce), ('colsum', _RlColSum), ('speder_rows', _RlSpederRows), ('speder_grads', _RlSpederGrads),
+                ('perturb', _RlPerturb), ('score', _RlScore), ('reg_stats', _RlRegStats), ('copy2', _RlCopy2)]
+
+
 def declared_symbols():
     """Every function name include/rlrep.h declares (used by the CPU test that checks the exports)."""
     src = open(HEADER_PATH).read()
@@ -215,6 +263,8 @@ def _load():
         'rlrep_gemm': (i32, [i32, i32, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, i32, vp, i64, vp]),
         'rlrep_gemm16_table': (i32, [i32, i32, i32, P(Gemm16Task), i32, i32, i32, i32, vp]),
         'rlrep_gemm_plan': (i32, [i32] * 8 + [P(i32)] * 5),
+        'rlrep_replearn': (i32, [i32, P(ReplearnArgs), vp]),
+        'rlrep_diffsr_score_plan': (i32, [i32, i32, i32, P(i32)]),
         'rlrep_nc_fwd_plan': (i32, [i32] * 4 + [P(i32)] * 3),
         'rlrep_chain_status': (i32, [vp, P(C.c_uint32), vp]),
         'rlrep_build_flags': (i32, []),

@@ -240,7 +240,7 @@ void build_ctrlsac(Builder& b, rlrep_agent* ag) {
         // OPT-IN (RLREP_ENABLE=fuse_infonce): measured SLOWER -- 3 546 against 4 150 train()/s at config 3: the 64 waves of 16 workgroups run the 256 MFMAs
         // per wave that 1 024 waves of the GEMM launch share, ~21 us against 11 for the pair (docs/history/r06.md).  The arithmetic K12 was declined with, confirmed.
         const bool fuse_score = theta_in_loss && (F & 63) == 0 && F <= 512 && WB <= 256 && rl_opt("fuse_infonce") != nullptr;
-        const int nblk_loss = fuse_score ? (B + 15) / 16 : nblk_f;
+        const int nblk_loss = fuse_score ? infonce_fused_blocks(B) : nblk_f;
         if (fuse_score) { /* no score-matrix stage */ }
         else if (theta_in_loss) b.fwd_stage(p, {Builder::fwd(pf.Z, F, B, F, ZMall, F, nullptr, WB, Sx, WB, ACT_NONE)}, "score matrix");
         else
@@ -423,7 +423,7 @@ static void build_rff_critic_actor(Builder& b, rlrep_agent* ag, const Mlp& phi, 
             float* XR = ws.f((size_t)4 * BH); float* CR = ws.f((size_t)4 * H * H);
             RegStats rs; memset(&rs, 0, sizeof(rs));
             rs.B = B; rs.H = H; rs.lambda = ag->h.critic_reg_lambda;
-            rs.nbc = (int)(((long long)H * H + 1023) / 1024); rs.nbr = (B + 3) / 4;
+            rs.nbc = reg_gram_blocks(H); rs.nbr = reg_row_blocks(B);
             float* part_r = ws.f((size_t)4 * (rs.nbc + rs.nbr));
             rs.partial = part_r;
             {

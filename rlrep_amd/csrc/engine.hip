@@ -1435,6 +1435,142 @@ int32_t rlrep_gemm_plan(int32_t la, int32_t lb, int32_t R, int32_t Cn, int32_t K
     return 0;
 }
 
+// Unit-test hook of the representation-loss kernels (replearn.hip): one launch on caller buffers through the launcher the step programs use, with the
+// block counts of the builder's own helpers (qhead_blocks, infonce_fused_blocks, reg_gram_blocks / reg_row_blocks).  Every shape is checked
+// HERE, before any GPU call: nothing a test hands in can make a kernel index outside the extents its record states.
+static_assert(RLREP_SCORE_LDS32 == DS_LDS32 && RLREP_SCORE_LDS64 == DS_LDS64 && RLREP_SCORE_LDS128 == DS_LDS128 && RLREP_SCORE_SMALL1 == DS_SMALL1 &&
+              RLREP_SCORE_SMALL2 == DS_SMALL2 && RLREP_SCORE_SMALL4 == DS_SMALL4 && RLREP_SCORE_VEC == DS_VEC && RLREP_SCORE_ROWS == DS_ROWS, "rlrep.h names the forms of kparams.h");
+#define RLR_REFUSE(...) { rl_set_error("replearn: " __VA_ARGS__); return RLREP_ERR_ARG; }
+int32_t rlrep_replearn(int32_t kernel, const rlrep_replearn_args* a, void* stream) {
+    rl_switches_read();
+    if (!a) RLR_REFUSE("null argument record")
+    if (kernel < RLREP_RL_INFONCE || kernel > RLREP_RL_COPY2) RLR_REFUSE("unknown kernel %d", kernel)
+    const hipStream_t st = (hipStream_t)stream;
+    const char* what = "";
+    auto al16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
+    // (the record of the launch is built first, the GPU is touched after every check has passed)
+    InfoNce nc; ColSum cs; SpederRows sr; SpederGrads sg; DiffsrPerturb dp; DiffsrScore ds; RegStats rs;
+    switch (kernel) {
+    case RLREP_RL_INFONCE: case RLREP_RL_SCORE_INFONCE: {
+        const auto& s = a->infonce;
+        const bool fused = kernel == RLREP_RL_SCORE_INFONCE;
+        what = fused ? "score matrix + infonce" : "infonce";
+        if (!s.S || !s.r || !s.drhat || !s.partial) RLR_REFUSE("%s: null S, r, drhat or partial", what)
+        if (s.B <= 0 || s.ncols <= 0 || s.ldS < s.ncols) RLR_REFUSE("%s: B %d, ncols %d, ldS %d: non-positive extent or row stride below the width", what, s.B, s.ncols, s.ldS)
+        if (s.diag_off < 0 || (long long)s.diag_off + s.B > s.ncols) RLR_REFUSE("%s: diagonal columns [%d, %d + %d) outside the %d columns", what, s.diag_off, s.diag_off, s.B, s.ncols)
+        if (fused) {
+            if (!s.Z || !s.ZM || !s.theta_w || !s.theta_b) RLR_REFUSE("%s: null Z, ZM or theta", what)
+            if (s.F <= 0 || s.ldZ < s.F || s.ldZM < s.F) RLR_REFUSE("%s: F %d, ldZ %d, ldZM %d: non-positive extent or row stride below the width", what, s.F, s.ldZ, s.ldZM)
+            if (s.F & 63) RLR_REFUSE("%s: F %d is no multiple of 64", what, s.F)
+            if (s.ncols > 256) RLR_REFUSE("%s: %d columns, at most 256", what, s.ncols)
+            if ((s.ldZ & 3) || (s.ldZM & 3)) RLR_REFUSE("%s: ldZ %d / ldZM %d is no multiple of 4", what, s.ldZ, s.ldZM)
+            if (!al16(s.Z) || !al16(s.ZM) || !al16(s.theta_w)) RLR_REFUSE("%s: Z, ZM or theta_w not on a 16-byte boundary", what)
+        } else {
+            if (s.ZM) RLR_REFUSE("%s: ZM given (the one-launch form is RLREP_RL_SCORE_INFONCE)", what)
+            if (s.Z) {
+                if (!s.theta_w || !s.theta_b) RLR_REFUSE("%s: Z given without theta", what)
+                if (s.F <= 0 || s.ldZ < s.F) RLR_REFUSE("%s: F %d, ldZ %d: non-positive extent or row stride below the width", what, s.F, s.ldZ)
+            } else if (!s.rhat) RLR_REFUSE("%s: neither rhat nor Z given", what)
+        }
+        memset(&nc, 0, sizeof(nc));
+        nc.S = s.S; nc.ldS = s.ldS; nc.ncols = s.ncols; nc.diag_off = s.diag_off; nc.rhat = s.rhat; nc.r = s.r; nc.drhat = s.drhat; nc.partial = s.partial;
+        nc.B = s.B; nc.nblk = fused ? infonce_fused_blocks(s.B) : qhead_blocks(s.B); nc.inv_batch = s.inv_batch;
+        if (s.Z) { nc.Z = s.Z; nc.ldZ = s.ldZ; nc.F = s.F; nc.theta_w = s.theta_w; nc.theta_b = s.theta_b; }
+        if (fused) { nc.ZM = s.ZM; nc.ldZM = s.ldZM; }
+    } break;
+    case RLREP_RL_COLSUM: {
+        const auto& s = a->colsum;
+        what = "column sum";
+        if (!s.X || !s.out) RLR_REFUSE("%s: null X or out", what)
+        if (s.rows <= 0 || s.F <= 0 || s.ldX < s.F) RLR_REFUSE("%s: rows %d, F %d, ldX %d: non-positive extent or row stride below the width", what, s.rows, s.F, s.ldX)
+        if (s.X2 && !s.out2) RLR_REFUSE("%s: second set without out2", what)
+        if (s.X2 && (s.rows2 <= 0 || s.ldX2 < s.F)) RLR_REFUSE("%s: rows2 %d, ldX2 %d: non-positive extent or row stride below the width", what, s.rows2, s.ldX2)
+        memset(&cs, 0, sizeof(cs));
+        cs.X = s.X; cs.ldX = s.ldX; cs.w = s.w; cs.out = s.out; cs.rows = s.rows; cs.F = s.F;
+        if (s.X2) { cs.X2 = s.X2; cs.ldX2 = s.ldX2; cs.w2 = s.w2; cs.out2 = s.out2; cs.outb2 = s.outb2; cs.rows2 = s.rows2; }
+    } break;
+    case RLREP_RL_SPEDER_ROWS: {
+        const auto& s = a->speder_rows;
+        what = "spectral rows";
+        if (!s.phi || !s.mu || !s.mu_r || !s.phibar || !s.theta_w || !s.theta_b || !s.r || !s.c || !s.drhat || !s.partial) RLR_REFUSE("%s: null pointer", what)
+        if (s.B <= 0 || s.F <= 0) RLR_REFUSE("%s: B %d, F %d: non-positive extent", what, s.B, s.F)
+        memset(&sr, 0, sizeof(sr));
+        sr.phi = s.phi; sr.mu = s.mu; sr.mu_r = s.mu_r; sr.phibar = s.phibar; sr.theta_w = s.theta_w; sr.theta_b = s.theta_b; sr.r = s.r;
+        sr.c = s.c; sr.drhat = s.drhat; sr.partial = s.partial; sr.B = s.B; sr.F = s.F; sr.nblk = qhead_blocks(s.B); sr.inv_batch = s.inv_batch;
+    } break;
+    case RLREP_RL_SPEDER_GRADS: {
+        const auto& s = a->speder_grads;
+        what = "spectral gradients";
+        if (!s.phi || !s.mu || !s.c || !s.drhat || !s.phibar || !s.v || !s.theta_w || !s.Gphi || !s.Gmu) RLR_REFUSE("%s: null pointer", what)
+        if (s.B <= 0 || s.F <= 0) RLR_REFUSE("%s: B %d, F %d: non-positive extent", what, s.B, s.F)
+        memset(&sg, 0, sizeof(sg));
+        sg.phi = s.phi; sg.mu = s.mu; sg.c = s.c; sg.drhat = s.drhat; sg.phibar = s.phibar; sg.v = s.v; sg.theta_w = s.theta_w;
+        sg.Gphi = s.Gphi; sg.Gmu = s.Gmu; sg.B = s.B; sg.F = s.F; sg.inv_batch = s.inv_batch;
+    } break;
+    case RLREP_RL_PERTURB: {
+        const auto& s = a->perturb;
+        what = "perturb";
+        if (!s.alphabars || !s.idx || !s.s2 || !s.eps || !s.XN || !s.TGT) RLR_REFUSE("%s: null pointer", what)
+        if (s.B <= 0 || s.S <= 0 || s.ld_s2 < s.S) RLR_REFUSE("%s: B %d, S %d, ld_s2 %d: non-positive extent or row stride below the width", what, s.B, s.S, s.ld_s2)
+        memset(&dp, 0, sizeof(dp));
+        dp.alphabars = s.alphabars; dp.idx = s.idx; dp.s2 = s.s2; dp.ld_s2 = s.ld_s2; dp.eps = s.eps; dp.XN = s.XN; dp.TGT = s.TGT; dp.B = s.B; dp.S = s.S;
+    } break;
+    case RLREP_RL_SCORE: {
+        const auto& s = a->score;
+        what = "score matching";
+        if (!s.U || !s.PHI || !s.TGT || !s.alphabars || !s.idx || !s.GPHI || !s.partial) RLR_REFUSE("%s: null pointer", what)
+        if (s.B <= 0 || s.F <= 0 || s.S <= 0) RLR_REFUSE("%s: B %d, F %d, S %d: non-positive extent", what, s.B, s.F, s.S)
+        memset(&ds, 0, sizeof(ds));
+        ds.U = s.U; ds.PHI = s.PHI; ds.TGT = s.TGT; ds.alphabars = s.alphabars; ds.idx = s.idx; ds.GPHI = s.GPHI; ds.partial = s.partial;
+        ds.B = s.B; ds.F = s.F; ds.S = s.S; ds.sigma = s.sigma; ds.inv_batch = s.inv_batch;
+        const DsForm f = rl_diffsr_score_form(&ds);
+        if ((f == DS_ROWS || f == DS_VEC) && (long long)5 * s.S * (long long)sizeof(float) > 65536)
+            RLR_REFUSE("%s: S %d: the two-pass kernel's %lld bytes of dynamic LDS exceed the 65536 a launch may have", what, s.S, (long long)5 * s.S * (long long)sizeof(float))
+    } break;
+    case RLREP_RL_REG_STATS: {
+        const auto& s = a->reg_stats;
+        what = "regulariser statistics";
+        for (int k = 0; k < 4; ++k) if (!s.X[k] || !s.C[k]) RLR_REFUSE("%s: null X[%d] or C[%d]", what, k, k)
+        if (!s.partial) RLR_REFUSE("%s: null partial", what)
+        if (s.H <= 0) RLR_REFUSE("%s: H %d: non-positive extent", what, s.H)
+        if (s.B < 2) RLR_REFUSE("%s: batch %d below 2 (the statistic divides by (B - 1) B)", what, s.B)
+        memset(&rs, 0, sizeof(rs));
+        for (int k = 0; k < 4; ++k) { rs.X[k] = s.X[k]; rs.C[k] = s.C[k]; }
+        rs.B = s.B; rs.H = s.H; rs.nbc = reg_gram_blocks(s.H); rs.nbr = reg_row_blocks(s.B); rs.lambda = s.lambda; rs.partial = s.partial;
+    } break;
+    case RLREP_RL_COPY2: {
+        const auto& s = a->copy2;
+        what = "copy2";
+        if (!s.src || !s.d1) RLR_REFUSE("%s: null src or d1", what)
+        if (s.n <= 0) RLR_REFUSE("%s: n %lld: non-positive extent", what, (long long)s.n)
+    } break;
+    }
+    int rc = rl_replearn_init();                  // (the LDS reservations of the one-pass score-matching kernels: 69 888 bytes at F = 256)
+    if (rc != 0) { rl_set_error("replearn: %s: rl_replearn_init failed (%d)", what, rc); return RLREP_ERR_HIP; }
+    switch (kernel) {
+    case RLREP_RL_INFONCE: case RLREP_RL_SCORE_INFONCE: rc = rl_launch_infonce(&nc, st); break;
+    case RLREP_RL_COLSUM: rc = rl_launch_colsum(&cs, st); break;
+    case RLREP_RL_SPEDER_ROWS: rc = rl_launch_speder_rows(&sr, st); break;
+    case RLREP_RL_SPEDER_GRADS: rc = rl_launch_speder_grads(&sg, st); break;
+    case RLREP_RL_PERTURB: rc = rl_launch_diffsr_perturb(&dp, st); break;
+    case RLREP_RL_SCORE: rc = rl_launch_diffsr_score(&ds, st); break;
+    case RLREP_RL_REG_STATS: rc = rl_launch_reg_stats(&rs, st); break;
+    case RLREP_RL_COPY2: rc = rl_launch_copy2(a->copy2.src, a->copy2.d1, a->copy2.d2, (long long)a->copy2.n, st); break;
+    }
+    if (rc != 0) { rl_set_error("replearn: %s: launch failed (%d)", what, rc); return rc < 0 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    return 0;
+}
+#undef RLR_REFUSE
+
+int32_t rlrep_diffsr_score_plan(int32_t S, int32_t F, int32_t u_aligned16, int32_t* form) {
+    rl_switches_read();
+    if (S <= 0 || F <= 0 || !form) { rl_set_error("diffsr_score_plan: bad argument"); return RLREP_ERR_ARG; }
+    DiffsrScore p; memset(&p, 0, sizeof(p));
+    p.S = S; p.F = F; p.U = (float*)(uintptr_t)(u_aligned16 ? 64 : 68);        // (only its alignment is read)
+    *form = (int32_t)rl_diffsr_score_form(&p);
+    return 0;
+}
+
 int32_t rlrep_nc_fwd_plan(int32_t heads, int32_t B, int32_t F, int32_t H, int32_t* engine, int32_t* rows, int32_t* cols) {
     rl_switches_read();
     if (heads <= 0 || heads > NC_MAX_TASKS || B <= 0 || F <= 0 || H <= 0 || !engine) { rl_set_error("nc_fwd_plan: bad argument"); return RLREP_ERR_ARG; }

@@ -696,6 +696,10 @@ struct RpAsm {
 struct ActorBufs { float *A1, *A2, *AO, *logp, *dA, *Ghead, *GA2, *GA1; };
 
 int qhead_blocks(int B);
+// block counts of the representation-loss launches (replearn.hip), shared by the program builder (agents2.hip) and the unit-test hook (rlrep_replearn)
+inline int infonce_fused_blocks(int B) { return (B + 15) / 16; }                              // score_infonce_kernel: 16 whole rows per workgroup
+inline int reg_gram_blocks(int H) { return (int)(((long long)H * H + 1023) / 1024); }         // reg_stats_kernel: 1024 Gram-matrix elements per block ...
+inline int reg_row_blocks(int B) { return (B + 3) / 4; }                                      // ... and four rows of x per block
 ActorBufs alloc_actor(Builder& b, int B, int A, int Ha);
 GemmTask actor_l(rlrep_agent* ag, int layer, const float* X, int ldx, const ActorBufs& ab);
 void policy_fwd_stage(Program& p, rlrep_agent* ag, const ActorBufs& ab, float* act, int ld_act, const char* what);

@@ -347,6 +347,8 @@ struct DiffsrScore {
     float* U; const float* PHI; const float* TGT; const float* alphabars; const int* idx;
     float* GPHI; float* partial; int B, F, S; float sigma, inv_batch;
 };
+// which kernel a score-matching launch gets (replearn.hip rl_diffsr_score_form; rlrep.h RLREP_SCORE_*)
+enum DsForm : int { DS_LDS32 = 0, DS_LDS64 = 1, DS_LDS128 = 2, DS_SMALL1 = 3, DS_SMALL2 = 4, DS_SMALL4 = 5, DS_VEC = 6, DS_ROWS = 7 };
 
 // ------------------------------------------------------------------------------------------------
 // xchain.hip: several DEPENDENT row-local stages of a step program in ONE persistent launch, synchronised per XCD

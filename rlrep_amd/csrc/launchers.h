@@ -103,6 +103,7 @@ int rl_launch_reg_stats(const RegStats* p, hipStream_t st);
 int rl_launch_speder_rows(const SpederRows* p, hipStream_t st);
 int rl_launch_speder_grads(const SpederGrads* p, hipStream_t st);
 int rl_launch_diffsr_perturb(const DiffsrPerturb* p, hipStream_t st);
+DsForm rl_diffsr_score_form(const DiffsrScore* p);   // host only: the kernel rl_launch_diffsr_score picks (reads the switches in force)
 int rl_launch_diffsr_score(const DiffsrScore* p, hipStream_t st);
 int rl_launch_copy2(const float* src, float* d1, float* d2, long long n, hipStream_t st);
 // ---- comm.hip: the comm's pull descriptor; ctrlsac's batch-coupled exchanges as launches of the step program (attached agents) ----

@@ -666,27 +666,31 @@ extern "C" int rl_replearn_init() {
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*)diffsr_score_lds_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ds_lds<32>(256));
     return (int)e;
 }
-extern "C" int rl_launch_diffsr_score(const DiffsrScore* p, hipStream_t st) {
-    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
-    // one pass through LDS where it applies; column chunks of 64 floats (64 KB of LDS at F = 256: two workgroups per CU, whose load and store
-    // phases overlap) measured best at Humanoid dims: 380 us against 393 (32), 514 (128: one workgroup per CU) and 462 for the two-pass kernel.
-    // RLREP_ENABLE=score_ch=32 / 64 / 128 selects the chunk, 0 the two-pass kernels.
+// Which kernel a score-matching launch gets.  One pass through LDS where it applies; column chunks of 64 floats (64 KB of LDS at F = 256: two
+// workgroups per CU, whose load and store phases overlap) measured best at Humanoid dims: 380 us against 393 (32), 514 (128: one workgroup per CU)
+// and 462 for the two-pass kernel.  RLREP_ENABLE=score_ch=32 / 64 / 128 selects the chunk, 0 the two-pass kernels.
+extern "C" DsForm rl_diffsr_score_form(const DiffsrScore* p) {
     const char* e = rl_opt("score_ch");
     const int ch = e ? atoi(e) : 64;
-    if (ch && (p->S & 3) == 0 && p->F <= 256 && ((((uintptr_t)p->U) & 15) == 0)) {
-        if (ch == 128) hipLaunchKernelGGL(diffsr_score_lds_kernel<128>, dim3(p->B), dim3(256), ds_lds<128>(p->F), st, *p);
-        else if (ch == 64) hipLaunchKernelGGL(diffsr_score_lds_kernel<64>, dim3(p->B), dim3(256), ds_lds<64>(p->F), st, *p);
-        else hipLaunchKernelGGL(diffsr_score_lds_kernel<32>, dim3(p->B), dim3(256), ds_lds<32>(p->F), st, *p);
+    const bool al = ((((uintptr_t)p->U) & 15) == 0);
+    if (ch && (p->S & 3) == 0 && p->F <= 256 && al) return ch == 128 ? DS_LDS128 : ch == 64 ? DS_LDS64 : DS_LDS32;
+    if (p->S <= 32 && p->F <= 1024 && !rl_off("score_small")) return p->F <= 256 ? DS_SMALL1 : p->F <= 512 ? DS_SMALL2 : DS_SMALL4;
+    if ((p->S & 3) == 0 && p->S <= 512 && al) return DS_VEC;
+    return DS_ROWS;
+}
+extern "C" int rl_launch_diffsr_score(const DiffsrScore* p, hipStream_t st) {
+    if (rl_grp_active()) return RL_GRP_UNSUPPORTED;
+    const dim3 g(p->B), b(256);
+    switch (rl_diffsr_score_form(p)) {
+    case DS_LDS128: hipLaunchKernelGGL(diffsr_score_lds_kernel<128>, g, b, ds_lds<128>(p->F), st, *p); break;
+    case DS_LDS64: hipLaunchKernelGGL(diffsr_score_lds_kernel<64>, g, b, ds_lds<64>(p->F), st, *p); break;
+    case DS_LDS32: hipLaunchKernelGGL(diffsr_score_lds_kernel<32>, g, b, ds_lds<32>(p->F), st, *p); break;
+    case DS_SMALL1: hipLaunchKernelGGL(diffsr_score_small_kernel<1>, g, b, 0, st, *p); break;
+    case DS_SMALL2: hipLaunchKernelGGL(diffsr_score_small_kernel<2>, g, b, 0, st, *p); break;
+    case DS_SMALL4: hipLaunchKernelGGL(diffsr_score_small_kernel<4>, g, b, 0, st, *p); break;
+    case DS_VEC: hipLaunchKernelGGL(diffsr_score_vec_kernel, g, b, (size_t)5 * p->S * sizeof(float), st, *p); break;
+    case DS_ROWS: hipLaunchKernelGGL(diffsr_score_kernel, g, b, (size_t)5 * p->S * sizeof(float), st, *p); break;
     }
-    else if (p->S <= 32 && p->F <= 1024 && !rl_off("score_small")) {
-        if (p->F <= 256) hipLaunchKernelGGL(diffsr_score_small_kernel<1>, dim3(p->B), dim3(256), 0, st, *p);
-        else if (p->F <= 512) hipLaunchKernelGGL(diffsr_score_small_kernel<2>, dim3(p->B), dim3(256), 0, st, *p);
-        else hipLaunchKernelGGL(diffsr_score_small_kernel<4>, dim3(p->B), dim3(256), 0, st, *p);
-    }
-    else if ((p->S & 3) == 0 && p->S <= 512 && ((((uintptr_t)p->U) & 15) == 0))
-        hipLaunchKernelGGL(diffsr_score_vec_kernel, dim3(p->B), dim3(256), (size_t)5 * p->S * sizeof(float), st, *p);
-    else
-        hipLaunchKernelGGL(diffsr_score_kernel, dim3(p->B), dim3(256), (size_t)5 * p->S * sizeof(float), st, *p);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_copy2(const float* src, float* d1, float* d2, long long n, hipStream_t st) {
