@@ -454,6 +454,30 @@ int32_t rlrep_group_per_update(rlrep_agent* group, float* trees_dev, int64_t P, 
 int32_t rlrep_group_critic_step_weighted(rlrep_agent* group, const float* eps_dev, const float* w_dev, void* stream);
 const float* rlrep_group_per_td_dev(rlrep_agent* group);
 
+/* ---- prioritized replay of the CRITIC's minibatch for ctrlsac SEED GROUPS (additive to ABI 4; DESIGN.md 6g.1, csrc/per_fill_group.hip) ----------
+ * The group forms of rlrep_per_sample_fill / rlrep_critic_weights_arm / rlrep_per_update_td.  Trees, scalars and draw buffers as for sac seed
+ * groups above (trees_dev float32[members, 2 P], scal_dev float32[members, 4], idx_dev int32[members, batch], w_dev float32[members, batch]);
+ * td_dev float32[members, batch] is the caller's too.  Member m computes bit for bit what the single-agent entry points compute for a ctrlsac
+ * agent created with seed seeds[m] on m's slices; retired members (rlrep_group_set_live) are skipped: nothing of theirs is read or written.
+ *   rlrep_group_per_sample_fill     rlrep_per_sample_fill for every live member in ONE launch, grid (1 + G, members): key = the member's seed,
+ *                                   stream offset `offset` + the member's train() counter when use_counter != 0; rings_dev is member 0's ring,
+ *                                   rings of `capacity` rows (<= P) ring_stride_bytes apart; the drawn rows go into every live member's minibatch
+ *                                   slot 0.  No row outside a member's ring is read whatever a given index says.  A new batch to every
+ *                                   prefetch, as rlrep_replay_sample is.  batch must be the prepared batch (rlrep_group_prepare).
+ *   rlrep_group_critic_weights_arm  the NEXT rlrep_critic_step / rlrep_critic_backward of the group runs with member m's critic loss weighted by
+ *                                   w_dev[m] and writes td_dev[m][b] = 0.5 (|q1 - y| + |q2 - y|).  Same launch count as the unweighted step: only
+ *                                   the head launch differs.  That step disarms; so do two nulls.  Returns 1 armed, 0 disarmed.
+ *   rlrep_group_per_update_td       rlrep_per_update_td for every live member, td_dev[members, batch].
+ * All three accept a ctrlsac seed group on one GPU and refuse, by name: a single agent's handle ("not a seed group"), a sac group (which takes
+ * rlrep_group_per_sample / rlrep_group_critic_step_weighted / rlrep_group_per_update), world_size > 1, a batch that is not the prepared batch,
+ * null arguments, capacity outside [1, P]. */
+int32_t rlrep_group_per_sample_fill(rlrep_agent* group, const float* rings_dev, int64_t ring_stride_bytes, int64_t capacity, const float* trees_dev, int64_t P,
+                                    const float* scal_dev, int32_t* idx_dev, float* w_dev, int32_t batch, int32_t given, uint64_t offset, int32_t use_counter,
+                                    void* stream);
+int32_t rlrep_group_critic_weights_arm(rlrep_agent* group, const float* w_dev, float* td_dev);
+int32_t rlrep_group_per_update_td(rlrep_agent* group, float* trees_dev, int64_t P, float* scal_dev, const int32_t* idx_dev, const float* td_dev, int32_t batch,
+                                  void* stream);
+
 /* ---- n-step returns for sac (additive to ABI 4; DESIGN.md 6h, csrc/nstep.hip) ---------------------------------------------------------------
  * A replay gather that follows each sampled row's trajectory forward through the ring, ONE launch, stream-ordered and capturable.  For base row
  * i0 = idx_dev[b] of a ring of max_size rows [s | a | s' | r | d] with fill level *size_dev and successor distance `stride` (the number of

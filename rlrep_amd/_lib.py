@@ -228,6 +228,9 @@ def _load():
         'rlrep_group_per_update': (i32, [vp, vp, i64, vp, vp, vp, i32, vp]),
         'rlrep_group_critic_step_weighted': (i32, [vp, vp, vp, vp]),
         'rlrep_group_per_td_dev': (vp, [vp]),
+        'rlrep_group_per_sample_fill': (i32, [vp, vp, i64, i64, vp, i64, vp, vp, vp, i32, i32, u64, i32, vp]),
+        'rlrep_group_critic_weights_arm': (i32, [vp, vp, vp]),
+        'rlrep_group_per_update_td': (i32, [vp, vp, i64, vp, vp, vp, i32, vp]),
         'rlrep_replay_sample_nstep': (i32, [vp, i32, vp, vp, i32, i64, vp, i32, i32, vp]),
         'rlrep_replay_gather_nstep': (i32, [vp, vp, i32, i32, i32, i64, vp, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]),
         'rlrep_group_replay_gather_nstep': (i32, [vp, vp, i64, vp, i32, i32, i64, vp, i32, i32, vp]),

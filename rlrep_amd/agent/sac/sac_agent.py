@@ -494,6 +494,9 @@ class SACAgent(object):
     def _check_critic_per(self, buffer, what):
         """A CriticPrioritizedReplayBuffer trains ONE vlsac / ctrlsac / spedersac / diffsrsac agent on ONE GPU through train(), prepare() and
         train_injected(); everything else refuses it by its class name, before anything is launched."""
+        if getattr(buffer, 'critic_prioritized_group', False):       # (a ctrlsac seed group's class: SeedBatchMixin takes it before it gets here)
+            raise RuntimeError(f'{type(self).__name__}.{what}: {type(buffer).__name__} is built for CTRLSACSeedBatch.train (a ctrlsac seed group); '
+                               'a single agent takes a CriticPrioritizedReplayBuffer')
         if not self._cper(buffer):
             return
         name, cls = type(self).__name__, type(buffer).__name__
@@ -1075,11 +1078,11 @@ class SACAgent(object):
         if self._per(buffer):      # (one sac agent, one GPU: _check_per) the weighted critic step, then the |TD| errors it left become priorities
             c.critic_step_weighted(e1, buffer.draw_buffers(B)[1])
             buffer.update(B, core=c)
-        elif self._cper(buffer):   # (one representation agent, one GPU: _check_critic_per) the same step with the weights armed, then the priorities
+        elif self._cper(buffer):   # (one representation agent, or a ctrlsac seed group with its buffer group, one GPU: _check_critic_per) the same step with the weights armed, then the priorities
             w, td = buffer.draw_buffers(B)[1:]
             c.critic_weights_arm(w, td)
             c.critic_step(e1)
-            buffer.update(B)
+            buffer.update(B, core=c)
         elif W > 1:
             if self._critic_trains():
                 c.critic_backward(e1); self._allreduce(1); c.critic_apply()

@@ -421,12 +421,54 @@ class SeedBatchMixin(object):
         self._check_nstep(buffer, what)
         if self.ALG != 'sac':
             raise RuntimeError(f'{name}.{what}: {cls} is built for SACSeedBatch only ({self.ALG} reuses its last feature minibatch for the critic '
-                               'step; what prioritisation means there is open): use a plain ReplayBufferGroup')
+                               'step; what prioritisation means there is open): use a plain ReplayBufferGroup -- or, to prioritise that '
+                               'minibatch alone, a CriticPrioritizedReplayBufferGroup')
         if what == 'iterate':
             raise RuntimeError(f'{name}.iterate: {cls} cannot be written by a device environment (its step launch knows nothing of the priority '
                                'trees): use a plain ReplayBufferGroup')
         if what == 'train_injected':
             raise RuntimeError(f'{name}.train_injected: a seed group has no eager train() form; given indices go through {cls}.draw(given=...)')
+
+    # ---- prioritized replay of the critic's minibatch (utils/buffer_group.py CriticPrioritizedReplayBufferGroup) ---------------
+    @staticmethod
+    def _cper(buffer):
+        """the single ring's class (which _check_critic_per goes on refusing for a seed group) or the buffer group's"""
+        return bool(getattr(buffer, 'critic_prioritized', False) or getattr(buffer, 'critic_prioritized_group', False))
+
+    def _check_critic_per(self, buffer, what):
+        """A CriticPrioritizedReplayBufferGroup trains a ctrlsac seed group through train() and prepare(); everything else refuses it by its
+        class name, before anything is launched.  (The single ring's class is refused as before.)"""
+        if not getattr(buffer, 'critic_prioritized_group', False):
+            return super()._check_critic_per(buffer, what)
+        name, cls = type(self).__name__, type(buffer).__name__
+        if self.ALG != 'ctrlsac':
+            raise RuntimeError(f'{name}.{what}: {cls} is built for CTRLSACSeedBatch only (a {self.ALG} seed group owns its whole minibatch): use '
+                               'PrioritizedReplayBufferGroup')
+        if what in ('iterate', 'iterate_sim'):
+            raise RuntimeError(f'{name}.{what}: {cls} cannot be written by a device environment or a captured simulator loop (their launches know '
+                               'nothing of the priority trees): use a plain ReplayBufferGroup')
+        if what == 'train_injected':
+            raise RuntimeError(f'{name}.train_injected: a seed group has no eager train() form; given indices go through {cls}.draw_fill(given=...)')
+        if what not in ('train', 'prepare'):
+            raise RuntimeError(f'{name}.{what}: {cls} trains a ctrlsac seed group through train() and prepare() only')
+
+    def _before_capture(self, buffer, B, train=True):
+        """The draw buffers of a CriticPrioritizedReplayBufferGroup are allocated OUTSIDE the capture: allocated inside it, their zero / one
+        fills would be nodes of the graph and every replay would reset the rows of a retired member, which must stand still."""
+        if train and getattr(buffer, 'critic_prioritized_group', False):
+            buffer.draw_buffers(B)
+        super()._before_capture(buffer, B, train)
+
+    def _sample_into_critic_per(self, buffer, B, key, g):
+        """The minibatch the critic reuses, of every live member from its own tree: ONE launch draws the indices and the importance weights
+        into the buffer group's draw buffers and gathers the drawn rows into the members' slot 0 (rlrep_group_per_sample_fill) -- in front of
+        the last feature step, where the single agent makes it, followed by the early policy prefetch where a group has one."""
+        if not g or self._inject is not None:
+            raise RuntimeError(f'{type(self).__name__}: eager train() forms are not built for seed groups')
+        idx, _ = buffer.draw_fill(self.core, B, self.PER_STREAM, use_counter=True)
+        self._bufs['idx_' + key] = idx
+        if self._pool is not None and key == self._early_key:
+            self.core.prefetch_policy_early(self._pool['eps_crit'], self._pool['eps_act'])
 
     def _sample_into_per(self, buffer, B, key, g):
         """The minibatch of every live member from its own tree: one launch draws the indices and the importance weights into the buffer

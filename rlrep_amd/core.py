@@ -388,6 +388,11 @@ class HipCore:
     def critic_weights_arm(self, w, td):
         """The next critic_step / critic_backward of a representation agent is the weighted one (rlrep_critic_weights_arm): w[B] in the loss,
         |TD| into the caller's td[B]; that step disarms."""
+        if self.members:            # a ctrlsac seed group: w[members, B] and td[members, B], every live member in the same launches
+            rc = lib.rlrep_group_critic_weights_arm(self.h, _ptr(w), _ptr(td))
+            if rc < 0:
+                check(rc, 'group_critic_weights_arm')
+            return rc == 1
         rc = lib.rlrep_critic_weights_arm(self.h, _ptr(w), _ptr(td))
         if rc < 0:
             check(rc, 'critic_weights_arm')

@@ -345,7 +345,7 @@ static bool per_group_tree_ok(const char* what, const float* trees, int64_t P, c
 static int per_group_ok(const char* what, const rlrep_agent* ag) {
     if (!ag) { rl_set_error("%s: null agent", what); return RLREP_ERR_ARG; }
     if (ag->members <= 0) { rl_set_error("%s: not a seed group (a single sac agent takes rlrep_per_* / rlrep_critic_step_weighted)", what); return RLREP_ERR_ARG; }
-    if (ag->d.alg != RLREP_ALG_SAC) { rl_set_error("%s: prioritized replay is built for sac seed groups only (a ctrlsac group reuses its last feature minibatch)", what); return RLREP_ERR_ARG; }
+    if (ag->d.alg != RLREP_ALG_SAC) { rl_set_error("%s: prioritized replay is built for sac seed groups only (a ctrlsac group reuses its last feature minibatch: it takes rlrep_group_per_sample_fill / rlrep_group_critic_weights_arm / rlrep_group_per_update_td)", what); return RLREP_ERR_ARG; }
     if (ag->h.world_size > 1) { rl_set_error("%s: prioritized replay runs on one GPU (world_size = %d)", what, ag->h.world_size); return RLREP_ERR_ARG; }
     return 0;
 }
@@ -411,6 +411,79 @@ int32_t rlrep_group_critic_step_weighted(rlrep_agent* ag, const float* eps, cons
     if (ag->critic_bwd_w.stages.empty()) { rl_set_error("group_critic_step_weighted: no weighted critic program was built for this group"); return RLREP_ERR_STATE; }
     const int rc = critic_backward_dispatch(ag, eps, w_dev, stream);
     return rc ? rc : rlrep_critic_apply(ag, stream);
+}
+
+// ---- prioritized replay of the critic's minibatch for a ctrlsac seed group (per_fill_group.hip) --------------------------------
+// the three entry points work for a ctrlsac seed group on one GPU, and refuse everything else by name
+static int cper_group_ok(const char* what, const rlrep_agent* ag) {
+    if (!ag) { rl_set_error("%s: null agent", what); return RLREP_ERR_ARG; }
+    if (ag->members <= 0) { rl_set_error("%s: not a seed group (a single agent takes rlrep_per_sample_fill / rlrep_critic_weights_arm / rlrep_per_update_td)", what); return RLREP_ERR_ARG; }
+    if (ag->d.alg == RLREP_ALG_SAC) {
+        rl_set_error("%s: a sac seed group owns its whole minibatch: use rlrep_group_per_sample / rlrep_group_critic_step_weighted / rlrep_group_per_update", what);
+        return RLREP_ERR_ARG;
+    }
+    if (ag->h.world_size > 1) { rl_set_error("%s: prioritized critic replay runs on one GPU (world_size = %d)", what, ag->h.world_size); return RLREP_ERR_ARG; }
+    return 0;
+}
+static bool cper_group_batch_ok(const char* what, const rlrep_agent* ag, int32_t batch) {
+    if (batch < 1 || batch != ag->B) {
+        rl_set_error("%s: batch %d is not the batch the step programs are built for (%d): rlrep_group_prepare first", what, batch, ag->B); return false;
+    }
+    return true;
+}
+// rlrep_per_sample_fill of every live member in ONE launch.  Never skipped: it overwrites whatever gather the train prologue ran.
+int32_t rlrep_group_per_sample_fill(rlrep_agent* ag, const float* rings_dev, int64_t ring_stride_bytes, int64_t capacity, const float* trees_dev, int64_t P,
+                                    const float* scal_dev, int32_t* idx_dev, float* w_dev, int32_t batch, int32_t given, uint64_t offset, int32_t use_counter,
+                                    void* stream) {
+    const char* what = "group_per_sample_fill";
+    if (int rc = cper_group_ok(what, ag)) return rc;
+    if (!per_group_tree_ok(what, trees_dev, P, scal_dev, ag->members)) return RLREP_ERR_ARG;
+    if (!rings_dev || !idx_dev || !w_dev) { rl_set_error("%s: bad argument (null rings / idx / w)", what); return RLREP_ERR_ARG; }
+    if (capacity < 1 || capacity > P) { rl_set_error("%s: rings of %lld rows under trees of %lld leaves", what, (long long)capacity, (long long)P); return RLREP_ERR_ARG; }
+    if (ring_stride_bytes < 0 || (ring_stride_bytes & 3) ||
+        (ag->members > 1 && ring_stride_bytes < capacity * 4ll * (2 * ag->d.state_dim + ag->d.action_dim + 2))) {
+        rl_set_error("%s: rings of %lld rows at a stride of %lld bytes", what, (long long)capacity, (long long)ring_stride_bytes); return RLREP_ERR_ARG;
+    }
+    if (!cper_group_batch_ok(what, ag, batch)) return RLREP_ERR_ARG;
+    Slot& s = ag->slot[0];
+    PerSampleFill p; memset(&p, 0, sizeof(p));
+    p.s.tree = trees_dev; p.s.scal = scal_dev; p.s.idx = idx_dev; p.s.w = w_dev; p.s.P = P; p.s.B = batch; p.s.given = given ? 1 : 0;
+    p.s.seed = 0; p.s.offset = offset; p.s.step_dev = use_counter ? ag->steps : nullptr;          // (member m: its seed, its counter)
+    p.f.ring = rings_dev; p.f.B = ag->B; p.f.S = ag->d.state_dim; p.f.A = ag->d.action_dim;
+    p.f.XE = s.XE; p.f.XF = s.XF; p.f.XF2 = s.XF2; p.f.XFpi = s.XFpi; p.f.R = s.R; p.f.D = s.D;
+    p.capacity = capacity;
+    ag->grp_ring_stride = ring_stride_bytes;
+    // a new batch: what rlrep_replay_sample invalidates
+    ag->pf_done = false; ag->pi_ready = nullptr; ag->hoist_req = nullptr;
+    s.filled = true;
+    GrpScope grp_scope_(ag);
+    const int rc = (++g_rl_launches, rl_launch_per_sample_fill_grp(&p, (hipStream_t)stream));
+    if (rc) { rl_set_error("%s: hip error %d", what, rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+// The next rlrep_critic_step / rlrep_critic_backward of the group is the weighted one: w[members, B] in the members' losses, their |TD| into the
+// caller's td[members, B] (critic_head_launch picks the group head of per_fill_group.hip).  That step disarms (critic_backward_dispatch); so
+// does passing null.
+int32_t rlrep_group_critic_weights_arm(rlrep_agent* ag, const float* w_dev, float* td_dev) {
+    if (int rc = cper_group_ok("group_critic_weights_arm", ag)) return rc;
+    if ((w_dev == nullptr) != (td_dev == nullptr)) { rl_set_error("group_critic_weights_arm: needs w[members,B] and td[members,B] (or neither, to disarm)"); return RLREP_ERR_ARG; }
+    ag->arm_w = w_dev; ag->arm_td = td_dev;
+    return w_dev ? 1 : 0;
+}
+// rlrep_per_update_td of every live member: per_update_grp_kernel with the caller's |TD| array, `batch` floats per member
+int32_t rlrep_group_per_update_td(rlrep_agent* ag, float* trees_dev, int64_t P, float* scal_dev, const int32_t* idx_dev, const float* td_dev, int32_t batch,
+                                  void* stream) {
+    const char* what = "group_per_update_td";
+    if (int rc = cper_group_ok(what, ag)) return rc;
+    if (!per_group_tree_ok(what, trees_dev, P, scal_dev, ag->members)) return RLREP_ERR_ARG;
+    if (!idx_dev || !td_dev) { rl_set_error("%s: bad argument (null idx / td)", what); return RLREP_ERR_ARG; }
+    if (!cper_group_batch_ok(what, ag, batch)) return RLREP_ERR_ARG;
+    PerUpdate p; memset(&p, 0, sizeof(p));
+    p.tree = trees_dev; p.scal = scal_dev; p.idx = idx_dev; p.td = td_dev; p.P = P; p.B = batch;
+    GrpScope grp_scope_(ag);
+    const int rc = (++g_rl_launches, rl_launch_per_update_grp(&p, (long long)batch, (hipStream_t)stream));
+    if (rc) { rl_set_error("%s: hip error %d", what, rc); return RLREP_ERR_HIP; }
+    return 0;
 }
 
 // ---- n-step returns of a sac seed group (nstep.hip) ------------------------------------------------------------------------------

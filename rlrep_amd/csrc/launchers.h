@@ -90,6 +90,9 @@ int rl_launch_per_sample_grp(const PerSample* p, hipStream_t st);
 int rl_launch_per_gather_grp(const SlotFill* fill, const int* idx, long long ring_rows, hipStream_t st);      // ring row idx[m][b] of member m's ring -> its slot 0, grid (blocks, R)
 int rl_launch_per_update_grp(const PerUpdate* p, long long td_stride, hipStream_t st);                      // td_stride < 0: td moves by the member stride
 int rl_launch_qhead_critic_w_grp(const QHeadCriticW* p, hipStream_t st);
+// ---- per_fill_group.hip (prioritized critic replay of a ctrlsac seed group: the group form of per_fill.hip's launch, grid (1 + G, R); the weighted head with a [R, B] td) ----
+int rl_launch_per_sample_fill_grp(PerSampleFill* p, hipStream_t st);                 // sets p->rows; needs an active group
+int rl_launch_qhead_critic_wtd_grp(const QHeadCriticW* p, hipStream_t st);          // w and td: the buffer group's [R, B] arrays
 // ---- nstep.hip (n-step returns: the chain-following replay gather, one wave per sample) ----
 int rl_launch_nstep_gather(const NStepGather* p, hipStream_t st);
 int rl_launch_nstep_gather_grp(const NStepGather* p, int idx_rows, hipStream_t st);       // grid (x, R); idx_rows == 0: the indices move by the member stride, else int32[R, idx_rows]

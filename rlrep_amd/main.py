@@ -174,6 +174,12 @@ def run(argv=None):
                         'tree of its own, one launch per step for all members; --per-alpha / --per-beta as for --per, beta annealed for all '
                         'members; --sweep per_alpha=0.4,0.6 gives the members different exponents.  Goes with --pbt-interval and '
                         '--halving-interval; not with --device-env or --per')
+    p.add_argument('--group-critic-per', action='store_true',
+                   help='prioritized replay of the critic minibatch for a seed group (--alg ctrlsac with --seeds and / or --sweep): every member draws '
+                        'the minibatch its critic and actor steps reuse from a sum tree of its own and weights its critic loss, one launch per step '
+                        'for all members, while every other feature minibatch stays uniform; --per-alpha / --per-beta as for --per, beta annealed '
+                        'for all members; --sweep per_alpha=0.4,0.6 gives the members different exponents.  Goes with --pbt-interval, '
+                        '--halving-interval and --host-envs; not with --per, --group-per, --critic-per, --device-env or --critic-n-step')
     p.add_argument('--n-step', default=1, type=int,
                    help='n-step returns (--alg sac; 1..16, default 1 = one-step targets): train() gathers, on the device, rows that follow each sampled '
                         'transition up to N steps forward through the replay ring and bootstraps with discount^m.  Goes with --per, --seeds / '
@@ -190,6 +196,7 @@ def run(argv=None):
     args = p.parse_args(argv)
     _check_nstep(args)
     _check_critic_nstep(args)
+    _check_group_critic_per(args)
     _check_group_per(args)
     _check_per(args)
     _check_critic_per(args)
@@ -384,6 +391,31 @@ def _check_group_per(args):
     _check_per_exponents('--group-per', args)
 
 
+def _check_group_critic_per(args):
+    """--group-critic-per: SystemExit, before anything touches the GPU, on what prioritized critic replay of a seed group does not run with (a
+    namespace without the field is a run without it)"""
+    if not getattr(args, 'group_critic_per', False):
+        return
+    for flag, given in (('--per', getattr(args, 'per', False)), ('--group-per', getattr(args, 'group_per', False)),
+                        ('--critic-per', getattr(args, 'critic_per', False))):
+        if given:
+            raise SystemExit(f'--group-critic-per: it is the ctrlsac seed-group form of prioritized replay and does not go with {flag}; give one of them')
+    if args.alg != 'ctrlsac':
+        raise SystemExit(f'--group-critic-per: prioritized critic replay of a seed group is built for --alg ctrlsac (got --alg {args.alg}: a sac seed '
+                         'group takes --group-per, the other representation agents have no seed groups)')
+    if getattr(args, 'seeds', None) is None and not getattr(args, 'sweep', None):
+        raise SystemExit('--group-critic-per: prioritized critic replay of a seed group needs a seed group: give --seeds and / or --sweep (one agent '
+                         'takes --critic-per)')
+    for flag, given in (('--device-env', getattr(args, 'device_env', False)), ('--device-loop', getattr(args, 'device_loop', False))):
+        if given:
+            raise SystemExit(f'--group-critic-per: a device environment writes ring rows inside its step launch, which knows nothing of the priority '
+                             f'trees; it does not go with {flag}')
+    for flag, given in (('--critic-n-step', int(getattr(args, 'critic_n_step', 1)) > 1), ('--n-step', int(getattr(args, 'n_step', 1)) > 1)):
+        if given:
+            raise SystemExit(f'--group-critic-per: prioritized critic replay of a seed group has one-step targets; it does not go with {flag}')
+    _check_per_exponents('--group-critic-per', args)
+
+
 def _check_per_exponents(flag, args):
     """the ranges of --per-alpha and --per-beta, for `flag` (--per or --group-per)"""
     if not 0.0 <= float(args.per_alpha) or not 0.0 <= float(args.per_beta) <= 1.0:
@@ -393,7 +425,7 @@ def _check_per_exponents(flag, args):
 def _per_anneal(args, replay, t):
     """--per / --group-per: beta rises linearly from --per-beta to 1.0 at --max_timesteps; written (one device word per member) at the evaluation
     boundaries"""
-    if getattr(args, 'per', False) or getattr(args, 'group_per', False) or getattr(args, 'critic_per', False):
+    if getattr(args, 'per', False) or getattr(args, 'group_per', False) or getattr(args, 'critic_per', False) or getattr(args, 'group_critic_per', False):
         frac = min(1.0, float(t) / float(args.max_timesteps))
         replay.beta = 1.0 if frac >= 1.0 else float(args.per_beta) + (1.0 - float(args.per_beta)) * frac
 
@@ -669,7 +701,7 @@ def parse_sweeps(sweeps, alg, n_seeds, group_per=False):
             raise SystemExit(f'--sweep {arg}: give KEY=V1,V2,..., e.g. --sweep lr=1e-4,3e-4')
         if key == 'per_alpha':
             if not group_per:
-                raise SystemExit(f'--sweep {arg}: per_alpha is the priority exponent of a seed group\'s replay trees: it needs --group-per')
+                raise SystemExit(f'--sweep {arg}: per_alpha is the priority exponent of a seed group\'s replay trees: it needs --group-per (--alg ctrlsac: --group-critic-per)')
             try:
                 values = [float(v) for v in vals.split(',')]
                 if any(not (0.0 <= v < float('inf')) for v in values):
@@ -916,7 +948,8 @@ def run_seeds(args):
     if args.alg not in ('sac', 'ctrlsac'):
         raise SystemExit(f'--seeds: seed batches are built for --alg sac and ctrlsac only (got --alg {args.alg}); run one process per seed instead')
     group_per = bool(getattr(args, 'group_per', False))
-    configs = parse_sweeps(args.sweep, args.alg, len(seeds), group_per=group_per)
+    group_cper = bool(getattr(args, 'group_critic_per', False))
+    configs = parse_sweeps(args.sweep, args.alg, len(seeds), group_per=group_per or group_cper)
     swept = bool(args.sweep)
     tags = [t for t, _ in configs for _ in seeds]
     # per_alpha belongs to the members' replay trees, not to the agent: taken out of the members' hyper-parameters
@@ -927,7 +960,7 @@ def run_seeds(args):
     halving_cfg = parse_halving(args, len(seeds), pbt_cfg)
     if args.device_env and not str(args.env).startswith(('Pendulum', 'MountainCarContinuous')):
         raise SystemExit(f'--device-env: only Pendulum-v1 and MountainCarContinuous-v0 are built on the device (got --env {args.env}); run without --device-env')
-    from rlrep_amd.utils.buffer_group import ReplayBufferGroup, PrioritizedReplayBufferGroup
+    from rlrep_amd.utils.buffer_group import ReplayBufferGroup, PrioritizedReplayBufferGroup, CriticPrioritizedReplayBufferGroup
     R = len(seeds)
     envs_, evals_ = [envs.make(args.env) for _ in seeds], [envs.make(args.env) for _ in seeds]
     for s, e, ev in zip(seeds, envs_, evals_):
@@ -946,12 +979,15 @@ def run_seeds(args):
     common = dict(discount=args.discount, tau=args.tau, hidden_dim=args.hidden_dim, max_batch=args.batch_size)
     if args.alg == 'ctrlsac':
         common.update(feature_dim=2048, hidden_dim=1024, extra_feature_steps=args.extra_feature_steps)          # as build_agent (main.py:90-91)
-    if group_per and any('per_alpha' in cfg for _, cfg in configs):
+    if (group_per or group_cper) and any('per_alpha' in cfg for _, cfg in configs):
         common['distinct_members'] = False          # (members that differ in per_alpha alone share a seed and the agent's hyper-parameters)
     agent = _group_class(args.alg)(seeds, state_dim, action_dim, space, member_hyper=member_hyper, **common)
     if group_per:
         replay = PrioritizedReplayBufferGroup(R, state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)), alpha=per_alphas, beta=args.per_beta,
                                               **_nstep_kw(args))
+    elif group_cper:
+        replay = CriticPrioritizedReplayBufferGroup(R, state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)), alpha=per_alphas,
+                                                    beta=args.per_beta)
     else:
         replay = ReplayBufferGroup(R, state_dim, action_dim, max_size=int(min(args.max_timesteps, 1e6)), **_nstep_kw(args))
     agent.replay = replay                           # (what the members train from: for callers of run())

@@ -316,7 +316,7 @@ class PrioritizedReplayBufferGroup(ReplayBufferGroup):
         `gather`: a second launch copies the drawn rows into every live member's minibatch slot.  On the CPU `seeds` are the members' seeds and
         `live` the members to draw for (default: all)."""
         B = int(B)
-        idx, w = self.draw_buffers(B)
+        idx, w = self.draw_buffers(B)[:2]          # (a subclass may keep more arrays beside them)
         if min(self.sizes) == 0:
             raise RuntimeError('PrioritizedReplayBufferGroup.draw: a member\'s buffer is empty')
         if given is not None:
@@ -344,7 +344,7 @@ class PrioritizedReplayBufferGroup(ReplayBufferGroup):
         index repeats), its max_priority follows, the ancestors are recomputed.  On the device ONE launch; td=None: the |TD| errors the
         group's last weighted critic step left, else float32[R, B]."""
         B = int(B)
-        idx, _ = self.draw_buffers(B)
+        idx = self.draw_buffers(B)[0]
         if self.device.type == 'cuda':
             if core is None:
                 raise ValueError('PrioritizedReplayBufferGroup.update: the device update runs for a sac seed group (core=group.core)')
@@ -356,3 +356,86 @@ class PrioritizedReplayBufferGroup(ReplayBufferGroup):
         td = np.asarray(td, np.float32).reshape(self.members, B)
         for r in (range(self.members) if live is None else live):
             _per_update_host(self.trees[r].numpy(), self.P, self._scal.numpy()[r], idx[r].numpy(), td[r], self._hyper[r, 0], self._hyper[r, 2])
+
+
+# ---- prioritized replay of the critic's minibatch for ctrlsac seed groups: DESIGN.md 6g.1, csrc/per_fill_group.hip ----------------------
+class CriticPrioritizedReplayBufferGroup(PrioritizedReplayBufferGroup):
+    """PrioritizedReplayBufferGroup for CTRLSACSeedBatch, with CriticPrioritizedReplayBuffer's sampling contract -- hence another name.  A
+    ctrlsac member runs its critic and actor steps on the slot-0 minibatch of its LAST feature step; that minibatch alone is drawn from the
+    member's tree, the member's critic loss takes its importance weights and the |TD| errors come back as priorities in the same captured
+    train().  Every other feature minibatch and all the noise stay the draws a plain ReplayBufferGroup gives at the same seeds and step.
+    Member r is bit for bit what CTRLSACAgent(seed=s_r, pipeline=False) does with a CriticPrioritizedReplayBuffer(alpha_r, beta_r, eps_r) fed
+    the same rows.  The trees, the scalars and the writers are the parent's; the draw buffers gain td float32[R, B], which the weighted
+    critic head writes and update() reads.  For CTRLSACSeedBatch.train() / prepare(); everything else refuses the class by name."""
+    prioritized_group = False         # (NOT the parent's contract: what takes a PrioritizedReplayBufferGroup must not mistake this class for one)
+    critic_prioritized_group = True
+
+    def __init__(self, members, state_dim, action_dim, max_size=int(1e6), device=None, stage_rows=4096, alpha=0.6, beta=0.4, eps=1e-6,
+                 n_step=1, n_stride=1, critic_n_step=1):
+        if not isinstance(n_step, bool) and int(n_step) == n_step and int(n_step) > 1:
+            raise ValueError(f'CriticPrioritizedReplayBufferGroup: n_step {int(n_step)} > 1 is not supported (n_step is the whole minibatch of a sac '
+                             'seed group, which takes a PrioritizedReplayBufferGroup)')
+        super().__init__(members, state_dim, action_dim, max_size=max_size, device=device, stage_rows=stage_rows, alpha=alpha, beta=beta, eps=eps,
+                         n_step=n_step, n_stride=n_stride, critic_n_step=critic_n_step)
+
+    def per_key(self):
+        """what a captured train() bakes in besides the rings: the trees and the scalar block, under this class's own tag"""
+        return ('critic_per_group', self.trees.data_ptr(), self._scal.data_ptr())
+
+    def collect_on_device(self, env):
+        raise RuntimeError('CriticPrioritizedReplayBufferGroup.collect_on_device: a device environment writes ring rows inside its step launch, '
+                           'which knows nothing of the priority trees (iterate() takes a plain ReplayBufferGroup)')
+
+    def draw_buffers(self, B):
+        """(idx int32[R, B], w float32[R, B], td float32[R, B]) on the rings' device, one triple per batch size for the life of the buffer group"""
+        bufs = self._draw_bufs.get(int(B))
+        if bufs is None:
+            bufs = self._draw_bufs[int(B)] = super().draw_buffers(B) + (torch.zeros(self.members, int(B), dtype=torch.float32, device=self.device),)
+        return bufs
+
+    def draw(self, B, offset, core=None, use_counter=False, given=None, gather=False, seeds=None, live=None):
+        """The parent's host draw (device='cpu'); on the device the sampler of this class is draw_fill (the parent's two launches are a sac
+        seed group's)."""
+        if self.device.type == 'cuda':
+            raise RuntimeError('CriticPrioritizedReplayBufferGroup.draw: the device sampler of this class is draw_fill (one launch with the gather)')
+        idx, w, _ = self.draw_buffers(B)
+        super().draw(B, offset, given=given, seeds=seeds, live=live)
+        return idx, w
+
+    def draw_fill(self, core, B, offset, use_counter=False, given=None):
+        """The critic's minibatch of every live member of a ctrlsac seed group (`core`: the group's HipCore): B stratified draws per member and
+        their importance weights as draw() computes them, and the drawn ring rows gathered into the member's minibatch slot 0 -- ONE launch
+        on the current stream (rlrep_group_per_sample_fill).  `given` (int32[R, B]): take these indices, compute only the weights, gather.
+        -> (idx, w)."""
+        B = int(B)
+        if min(self.sizes) == 0:
+            raise RuntimeError('CriticPrioritizedReplayBufferGroup.draw_fill: a member\'s buffer is empty')
+        if self.device.type != 'cuda' or core is None:
+            raise ValueError('CriticPrioritizedReplayBufferGroup.draw_fill: the fused launch runs for a ctrlsac seed group on the device '
+                             '(core=group.core); on device=\'cpu\' use draw()')
+        idx, w, _ = self.draw_buffers(B)
+        if given is not None:
+            g = np.asarray(given.cpu() if torch.is_tensor(given) else given).reshape(self.members, -1)
+            if g.shape[1] != B or g.min() < 0 or any(g[r].max() >= self.sizes[r] for r in range(self.members)):
+                raise ValueError(f'CriticPrioritizedReplayBufferGroup.draw_fill: given indices must be [{self.members}, {B}] rows inside each '
+                                 'member\'s ring')
+            idx.copy_(torch.from_numpy(g.astype(np.int32)))
+        lib_call(self.device, 'group_per_sample_fill', core.h, self.rings.data_ptr(), 4 * self.ring_stride, self.max_size, self.trees.data_ptr(), self.P,
+                 self._scal.data_ptr(), idx.data_ptr(), w.data_ptr(), B, 0 if given is None else 1, int(offset), 1 if use_counter else 0)
+        return idx, w
+
+    def update(self, B, td=None, core=None, live=None):
+        """The parent's update() from this buffer group's own td array (td=None: what the last weighted critic step wrote there).  On the
+        device ONE launch for all live members (rlrep_group_per_update_td; `core`: the ctrlsac seed group's HipCore)."""
+        B = int(B)
+        idx, _, own = self.draw_buffers(B)
+        td = own if td is None else td
+        if self.device.type == 'cuda':
+            if core is None:
+                raise ValueError('CriticPrioritizedReplayBufferGroup.update: the device update runs for a ctrlsac seed group (core=group.core)')
+            if tuple(td.shape) != (self.members, B) or td.dtype != torch.float32 or not td.is_contiguous() or td.device != self.trees.device:
+                raise ValueError(f'CriticPrioritizedReplayBufferGroup.update: td must be a contiguous float32 tensor [{self.members}, {B}] on '
+                                 f'{self.trees.device}')
+            lib_call(self.device, 'group_per_update_td', core.h, self.trees.data_ptr(), self.P, self._scal.data_ptr(), idx.data_ptr(), td.data_ptr(), B)
+            return
+        super().update(B, td.numpy() if torch.is_tensor(td) else td, live=live)
