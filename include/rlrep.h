@@ -390,6 +390,43 @@ int32_t rlrep_replay_add_cols_ctl(float* ring_dev, int64_t max_size, int32_t row
                                   int64_t ld_a, const float* s2, int64_t ld_s2, const float* r, const float* d, int64_t n, int32_t* size_dev, int64_t* ctl_dev,
                                   void* stream);
 
+/* ---- fused simulators for the simulator loop (additive to ABI 4; DESIGN.md 6i "Fused simulators", csrc/sim_step.hip) -------------------------
+ * n environments (1..RLREP_SIM_MAX_ENVS) of one kind (RLREP_ENV_PENDULUM, RLREP_ENV_MOUNTAIN_CAR_CONTINUOUS: the device environments' dynamics,
+ * observation, reward and done_bool rule) stepped by ONE launch, one thread per environment.  The state is caller-owned device memory,
+ * structure of arrays (rlrep_sim_state): x0, x1 the two fp64 state words; ep_return the fp64 sum of the fp32 rewards of the running episode;
+ * last_return the return of the last finished one; t the step in the episode, -1 = ended and frozen; episodes the finished episodes; starts
+ * the start states drawn so far; obs [n, S] float32, the current observation, updated in place.  Start state k of environment e is the kind's
+ * start of the Philox4x32-10 block with key `seed` and counter {k lo, k hi, e, 0xE3000000}.
+ *   rlrep_sim_start            every environment begins a new episode from start state starts[e]: starts[e] += 1, t = 0, ep_return = 0, obs =
+ *                              the start's observation; episodes and last_return stay.
+ *   rlrep_sim_step             act[e * ld_act] is the RAW action (the kinds clip it themselves).  Writes next_obs[e], reward[e] and done[e]
+ *                              (float32 0 / 1: the goal reached before the limit's step), ep_return += reward; where the episode has ended (the
+ *                              goal, or the time limit) last_return = ep_return, episodes += 1 and the environment restarts as rlrep_sim_start
+ *                              does; otherwise t += 1 and obs = next_obs.  With auto_restart = 0 an environment that ended is frozen instead
+ *                              (t = -1, its state, obs and ep_return as the last step left them): its step writes next_obs = obs, reward = 0,
+ *                              done = 0 and changes nothing.
+ *   rlrep_sim_step_append_ctl  the step, and transition e packed into ring row (start + e) mod max_size as [obs before the step, the action as
+ *                              given, next_obs, reward, done], start from the loop record as rlrep_act_device_ctl left it; one thread does
+ *                              what rlrep_replay_add_cols_ctl's does (size to size_dev, which may be NULL; iter += 1, t_global += n, calls += n
+ *                              unless warm), under the same rule.  With it an iteration in front of train() is two launches.
+ * Each is ONE launch, stream-ordered and capturable: no copy, no allocation, no synchronisation, nothing read on the host.  Refused with
+ * RLREP_ERR_ARG before any launch, the message starting with the entry point's name ("sim_start:", "sim_step:", "sim_step_append_ctl:"): a
+ * null pointer, an unknown kind, n outside [1, RLREP_SIM_MAX_ENVS] or above max_size, ld_act below the kind's A, row_floats != 2 S + A + 2.
+ * rlrep_sim_state_bytes: sizeof(rlrep_sim_state), for bindings to check their mirror against. */
+#define RLREP_SIM_MAX_ENVS 65536
+typedef struct rlrep_sim_state {
+    double* x0; double* x1; double* ep_return; double* last_return;
+    int32_t* t; int64_t* episodes; int64_t* starts; float* obs;
+    int32_t kind, n;
+    uint64_t seed;
+    int32_t auto_restart, reserved;
+} rlrep_sim_state;
+int32_t rlrep_sim_state_bytes(void);
+int32_t rlrep_sim_start(const rlrep_sim_state* sim, void* stream);
+int32_t rlrep_sim_step(const rlrep_sim_state* sim, const float* act, int64_t ld_act, float* next_obs, float* reward, float* done, void* stream);
+int32_t rlrep_sim_step_append_ctl(const rlrep_sim_state* sim, const float* act, int64_t ld_act, float* ring_dev, int64_t max_size, int32_t row_floats,
+                                  int32_t* size_dev, int64_t* ctl_dev, void* stream);
+
 /* ---- prioritized replay for sac (additive to ABI 4; DESIGN.md 6f, csrc/per.hip) ------------------------------------------------------
  * The priorities live beside the ring in a caller-owned sum tree: tree_dev float32[2 P], P = the smallest power of two >= the ring's rows,
  * node n = tree[2n] + tree[2n + 1] (one fp32 add), row i's leaf = tree[P + i], leaves of unwritten rows 0 (the caller zeroes the tree once).

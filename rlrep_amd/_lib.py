@@ -66,6 +66,12 @@ class Gemm16Task(C.Structure):
                 ('r1u', C.c_void_p), ('r1v', C.c_void_p), ('scale', C.c_float)]
 
 
+class SimState(C.Structure):
+    """rlrep_sim_state (include/rlrep.h): the arrays of a fused simulator (envs/fused_sim.py); rlrep_sim_state_bytes() is its size."""
+    _fields_ = [(n, C.c_void_p) for n in ('x0', 'x1', 'ep_return', 'last_return', 't', 'episodes', 'starts', 'obs')] + [
+        ('kind', C.c_int32), ('n', C.c_int32), ('seed', C.c_uint64), ('auto_restart', C.c_int32), ('reserved', C.c_int32)]
+
+
 RL_KERNEL = {'infonce': 0, 'score_infonce': 1, 'colsum': 2, 'speder_rows': 3, 'speder_grads': 4, 'perturb': 5, 'score': 6, 'reg_stats': 7, 'copy2': 8}
 SCORE_FORM = ('LDS32', 'LDS64', 'LDS128', 'SMALL1', 'SMALL2', 'SMALL4', 'VEC', 'ROWS')          # RLREP_SCORE_* of include/rlrep.h, by value
 
@@ -214,6 +220,10 @@ def _load():
         'rlrep_group_replay_add_cols': (i32, [vp, i64, i32, i64, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, i64, i32, i64, vp, i32, vp]),
         'rlrep_act_device_ctl': (i32, [vp, vp, i64, i32, u64, f32, f32, vp, i64, vp, i64, f32, i64, vp]),
         'rlrep_replay_add_cols_ctl': (i32, [vp, i64, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp]),
+        'rlrep_sim_state_bytes': (i32, []),
+        'rlrep_sim_start': (i32, [P(SimState), vp]),
+        'rlrep_sim_step': (i32, [P(SimState), vp, i64, vp, vp, vp, vp]),
+        'rlrep_sim_step_append_ctl': (i32, [P(SimState), vp, i64, vp, i64, i32, vp, vp, vp]),
         'rlrep_per_add': (i32, [vp, i64, vp, i64, i64, i64, vp]),
         'rlrep_per_rebuild': (i32, [vp, i64, vp]),
         'rlrep_per_sample': (i32, [vp, vp, i64, vp, vp, vp, i32, i32, u64, u64, vp, vp]),

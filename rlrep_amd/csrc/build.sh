@@ -16,7 +16,7 @@ LIBNAME="${OUTNAME:-librlrep_hip.so}"
 mkdir -p "$OUT" "$OBJ"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -Wno-unused-function $EXTRA_FLAGS"
-SRCS="gemm16 gemm_lds noisecritic elementwise per per_group per_fill per_fill_group nstep nstep_targets actor_tile group_clone group_env replearn comm $EXP_SRCS engine agents1 agents2 group_api $EXTRA_SRCS"
+SRCS="gemm16 gemm_lds noisecritic elementwise per per_group per_fill per_fill_group nstep nstep_targets actor_tile group_clone group_env sim_step replearn comm $EXP_SRCS engine agents1 agents2 group_api $EXTRA_SRCS"
 pids=()
 for f in $SRCS; do
   if [ ! -f "$OBJ/$f.o" ] || [ "$HERE/$f.hip" -nt "$OBJ/$f.o" ] || [ -n "$(find "$HERE" -maxdepth 1 -name '*.h' -newer "$OBJ/$f.o")" ] || [ "$HERE/../../include/rlrep.h" -nt "$OBJ/$f.o" ]; then

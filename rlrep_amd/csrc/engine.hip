@@ -513,6 +513,55 @@ int32_t rlrep_replay_add_cols_ctl(float* ring_dev, int64_t max_size, int32_t row
     return 0;
 }
 
+// ---- fused simulators (sim_step.hip): rlrep_sim_state is kparams.h SimState, field for field ----
+static_assert(sizeof(SimState) == sizeof(rlrep_sim_state) && offsetof(SimState, t) == offsetof(rlrep_sim_state, t) && offsetof(SimState, obs) == offsetof(rlrep_sim_state, obs) &&
+              offsetof(SimState, kind) == offsetof(rlrep_sim_state, kind) && offsetof(SimState, n) == offsetof(rlrep_sim_state, n) &&
+              offsetof(SimState, seed) == offsetof(rlrep_sim_state, seed) && offsetof(SimState, auto_restart) == offsetof(rlrep_sim_state, auto_restart) &&
+              RL_SIM_MAX_ENVS == RLREP_SIM_MAX_ENVS, "include/rlrep.h rlrep_sim_state (kparams.h SimState)");
+int32_t rlrep_sim_state_bytes(void) { return (int32_t)sizeof(rlrep_sim_state); }
+// what the three entry points refuse alike, by the entry point's name `who`; the kind's row of rl_env_kinds, or null with the error set
+static const EnvKindInfo* sim_check(const char* who, const rlrep_sim_state* s) {
+    if (!s || !s->x0 || !s->x1 || !s->ep_return || !s->last_return || !s->t || !s->episodes || !s->starts || !s->obs) {
+        rl_set_error("%s: bad argument (null simulator state or array)", who); return nullptr;
+    }
+    const EnvKindInfo* k = rl_env_kind(s->kind);
+    if (!k) { rl_set_error("%s: kind %d is not built (0 = Pendulum-v1, 2 = MountainCarContinuous-v0)", who, s->kind); return nullptr; }
+    if (s->n < 1 || s->n > RLREP_SIM_MAX_ENVS) { rl_set_error("%s: n %d outside [1, %d]", who, s->n, RLREP_SIM_MAX_ENVS); return nullptr; }
+    return k;
+}
+int32_t rlrep_sim_start(const rlrep_sim_state* sim, void* stream) {
+    if (!sim_check("sim_start", sim)) return RLREP_ERR_ARG;
+    ++g_rl_launches;
+    const int rc = rl_launch_sim_start((const SimState*)sim, (hipStream_t)stream);
+    if (rc) { rl_set_error("sim_start: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_sim_step(const rlrep_sim_state* sim, const float* act, int64_t ld_act, float* next_obs, float* reward, float* done, void* stream) {
+    const EnvKindInfo* k = sim_check("sim_step", sim);
+    if (!k) return RLREP_ERR_ARG;
+    if (!act || !next_obs || !reward || !done) { rl_set_error("sim_step: bad argument (null actions or output array)"); return RLREP_ERR_ARG; }
+    if (ld_act < k->A) { rl_set_error("sim_step: ld_act %lld below the kind's A %d", (long long)ld_act, k->A); return RLREP_ERR_ARG; }
+    ++g_rl_launches;
+    const int rc = rl_launch_sim_step((const SimState*)sim, act, ld_act, next_obs, reward, done, (hipStream_t)stream);
+    if (rc) { rl_set_error("sim_step: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_sim_step_append_ctl(const rlrep_sim_state* sim, const float* act, int64_t ld_act, float* ring_dev, int64_t max_size, int32_t row_floats,
+                                  int32_t* size_dev, int64_t* ctl_dev, void* stream) {
+    const EnvKindInfo* k = sim_check("sim_step_append_ctl", sim);
+    if (!k) return RLREP_ERR_ARG;
+    if (!act || !ring_dev || !ctl_dev) { rl_set_error("sim_step_append_ctl: bad argument (null actions, ring or loop record)"); return RLREP_ERR_ARG; }
+    if (max_size <= 0 || max_size > INT32_MAX || sim->n > max_size) {
+        rl_set_error("sim_step_append_ctl: n %d outside [1, max_size %lld]", sim->n, (long long)max_size); return RLREP_ERR_ARG;
+    }
+    if (ld_act < k->A) { rl_set_error("sim_step_append_ctl: ld_act %lld below the kind's A %d", (long long)ld_act, k->A); return RLREP_ERR_ARG; }
+    if (row_floats != k->row) { rl_set_error("sim_step_append_ctl: row %d is not 2 S + A + 2 (S %d, A %d)", row_floats, k->S, k->A); return RLREP_ERR_ARG; }
+    ++g_rl_launches;
+    const int rc = rl_launch_sim_step_ctl((const SimState*)sim, act, ld_act, ring_dev, max_size, size_dev, (long long*)ctl_dev, (hipStream_t)stream);
+    if (rc) { rl_set_error("sim_step_append_ctl: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+
 static void slot_fill_params(rlrep_agent* ag, int slot, const float* ring_dev, const int32_t* idx_dev, SlotFill& p) {
     Slot& s = ag->slot[slot];
     memset(&p, 0, sizeof(p));

@@ -13,6 +13,7 @@
 #define RL_STREAM_EVAL 0xE1000000u        // evaluation start states: counter = eval_index * episodes + episode
 #define RL_STREAM_SIM 0xE2000000u         // the exploration mix of a simulator loop (actor_tile_kernel_ctl): counter = the loop's iteration, word 2 = row e,
                                           // word 3 = RL_STREAM_SIM + block q; the pick is word 0 of block 0, u_j word (1 + j) & 3 of block (1 + j) >> 2
+#define RL_STREAM_SIM_START 0xE3000000u   // start states of a fused simulator (sim_step.hip): counter = the environment's count of start states drawn, word 2 = environment e
 // With E = num_envs environments per member (rlrep_group_env_create_n / rlrep_env_create_n), environment e of a member draws
 //   key            the member's / agent's seed                      (as before)
 //   counter        record (m, e)'s own nsteps                       (as before)

@@ -54,6 +54,19 @@ struct ReplayCols {
     long long ld_s, ld_a, ld_s2, n;
     int* size_dev;                                         // the fill level word (the group form's: one per member)
 };
+// Fused simulators (sim_step.hip; include/rlrep.h rlrep_sim_state, field for field): the state of n environments of one kind, structure of
+// arrays in caller-owned device memory.  The step-and-append form of the launch keeps to the append launch's row of the table above.
+#define RL_SIM_MAX_ENVS 65536
+struct SimState {
+    double *x0, *x1;                       // [n] the two state words (theta, theta_dot; p, v)
+    double *ep_return, *last_return;       // [n] fp64 sum of the fp32 rewards of the running episode; return of the last finished one
+    int* t;                                // [n] step in the episode; -1: ended and frozen (auto_restart = 0)
+    long long *episodes, *starts;          // [n] finished episodes; start states drawn so far (the index of the next one)
+    float* obs;                            // [n, S] the current observation, updated in place
+    int kind, n;
+    unsigned long long seed;               // the Philox key of the start states
+    int auto_restart, pad_;
+};
 struct PhiloxFill {
     float* dst_f; int* dst_i; long long n;
     int kind;                  // 0: normal*std -> dst_f ; 1: uniform int in [0,hi) -> dst_i

@@ -128,6 +128,11 @@ int rl_launch_env_reset(int kind, EnvRecord* rec, EnvCtl* ctl, unsigned long lon
 int rl_launch_env_step(int kind, const SelectAct* p, int num_envs, EnvRecord* rec, EnvCtl* ctl, float* ring, long long capacity, int* size_dev, float eps_greedy,
                        long long start_timesteps, hipStream_t st);
 int rl_launch_env_eval(int kind, const SelectAct* p, unsigned long long counter0, int episodes, double* out, double* starts, hipStream_t st);
+// ---- sim_step.hip (fused simulators: one thread per environment, grid ceil(n / 256); an unknown kind or n outside [1, RL_SIM_MAX_ENVS]: -7) ----
+int rl_launch_sim_start(const SimState* s, hipStream_t st);
+int rl_launch_sim_step(const SimState* s, const float* act, long long ld_act, float* next_obs, float* reward, float* done, hipStream_t st);
+int rl_launch_sim_step_ctl(const SimState* s, const float* act, long long ld_act, float* ring, long long capacity, int* size_dev, long long* ctl,
+                           hipStream_t st);                                        // + the ring rows and the append launch's one thread (RL_CTL_*)
 // ---- rowprog.hip / xchain.hip (experiments build); experiments_off.hip (product build: stubs) ----
 int rl_launch_rowprog(const RpLaunch* L, int total_blocks, hipStream_t st);
 int rl_rowprog_init();

@@ -21,6 +21,13 @@ attribute would be read from its capture-time address on every replay.  Generato
 sequence of `torch.Generator`; optional), so that the graph registers them.  envs/torch_pendulum.py `TorchPendulum(capturable=True)` is
 the example.
 
+The optional hook.  A simulator may also have `step_append_(actions, buffer, ctl)`: ONE capture-safe launch that steps the simulator AND does
+the append launch's work -- the N transitions [sim.obs as it stood before the step, actions, next_obs, reward, done] into `buffer.ring` rows
+ctl[START], ctl[START] + 1, ... (wrapping at buffer.max_size), ctl[SIZE] published to `buffer._size_dev`, ITER += 1, T += N, CALLS += N unless
+ctl[WARM] (csrc/kparams.h RL_CTL_*: no thread writes a word that a workgroup of the same launch reads).  A loop around such a simulator acts
+DIRECTLY on `sim.obs` -- no copy -- and an iteration in front of train() is two launches; `SimLoop(..., fused_append=False)` keeps the
+separate route.  envs/fused_sim.py `FusedSim` is the example (rlrep_sim_step_append_ctl).
+
 To the replay buffer a SimLoop shows the face of a device environment (`num_envs`, `set_cursor`, `state()` with `ring_ptr` / `ring_size`):
 `ReplayBuffer.collect_on_device` hands it the cursor, `add_device` refuses while it owns it, `adopt_device_cursor` takes it back.
 """
@@ -45,9 +52,10 @@ def _ptr(t):
 class SimLoop(object):
     """The device-resident loop record of `agent` and torch simulator `sim`, and the two launches that read it.  eps_greedy: the probability
     of a uniform action in place of the policy's; start_timesteps: the warm-up, environment steps (a multiple of N) that take uniform actions
-    only.  Both ride by value in the captured graph."""
+    only.  Both ride by value in the captured graph.  fused_append: take the simulator's `step_append_` hook where it has one (the module
+    docstring); False keeps the separate copy / act / step_ / append route."""
 
-    def __init__(self, agent, sim, eps_greedy=0.0, start_timesteps=0):
+    def __init__(self, agent, sim, eps_greedy=0.0, start_timesteps=0, fused_append=True):
         name = type(self).__name__
         if getattr(agent, 'R', None) is not None or not hasattr(agent, '_seed'):
             raise ValueError(f'{name}: needs a single agent (seed groups have act_device / add_device as an API only)')
@@ -59,6 +67,7 @@ class SimLoop(object):
         if not callable(getattr(sim, 'step_', None)):
             raise ValueError(f'{name}: the simulator needs step_(actions) -> (next_obs, reward, done), capture-safe (see the module docstring)')
         self.agent, self.sim = agent, sim
+        self.fused_append = bool(fused_append) and callable(getattr(sim, 'step_append_', None))
         self.num_envs = N = int(obs.shape[0])
         self.eps_greedy, self.start_timesteps = float(eps_greedy), int(start_timesteps)
         if not 0.0 <= self.eps_greedy <= 1.0:
@@ -132,8 +141,13 @@ class SimLoop(object):
 
     def step(self, buffer):
         """One iteration without the train(): copy of the observations, act launch, `sim.step_`, append launch -- stream-ordered on the
-        current stream, nothing read on the host (what iterate_sim captures)."""
+        current stream, nothing read on the host (what iterate_sim captures).  With the simulator's `step_append_` hook: the act launch
+        directly on `sim.obs`, then the hook -- two launches."""
         N, S = self.num_envs, buffer.state_dim
+        if self.fused_append:
+            self.act(self.sim.obs, self.actions, buffer.max_size)
+            self.sim.step_append_(self.actions, buffer, self.ctl)
+            return
         self.obs0.copy_(self.sim.obs)
         self.act(self.obs0, self.actions, buffer.max_size)
         nxt, rew, done = self.sim.step_(self.actions)

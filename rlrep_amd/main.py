@@ -61,6 +61,11 @@ envs/sim_loop.py): the act launch reads its call counter from a loop record on t
 (Philox draws of the agent's seed instead of the torch generator's), `TorchPendulum(capturable=True).step_`, the append launch and train()
 are captured together.  Evaluations are the eager ones of --torch-envs.
 
+`--fused-sim` (only with --torch-envs N --sim-graph; --env Pendulum-v1 or MountainCarContinuous-v0) makes the simulator of that loop a fused
+one (envs/fused_sim.py `FusedSim`, csrc/sim_step.hip): the act launch reads the simulator's observations in place and ONE launch steps the N
+environments and appends their transitions, so the graph holds two launches in front of train().  Episodes end and restart per environment
+on the device; evaluations step a FusedSim(auto_restart=False) of their own, one act_device and one step launch per step.
+
 `--critic-per` (vlsac, ctrlsac, spedersac, diffsrsac; one agent) trains from a CriticPrioritizedReplayBuffer: the minibatch the critic and actor
 steps reuse is drawn from a sum tree on the device, the critic loss is weighted and the |TD| errors come back as priorities (DESIGN.md
 6f.1); --per-alpha / --per-beta and the annealing of beta as for --per.  With the plain loop, --host-envs and --torch-envs.
@@ -157,6 +162,9 @@ def run(argv=None):
     p.add_argument('--sim-graph', action='store_true',
                    help='with --torch-envs N: act, explore, simulator step, append and train() of an iteration as ONE graph replay '
                         '(SACAgent.iterate_sim; the counters live on the device).  Not with --per')
+    p.add_argument('--fused-sim', action='store_true',
+                   help='with --torch-envs N --sim-graph: the simulator is a fused one (envs/fused_sim.py FusedSim; --env Pendulum-v1 or '
+                        'MountainCarContinuous-v0) whose step and ring append are ONE launch, so an iteration in front of train() is two launches')
     p.add_argument('--per', action='store_true',
                    help='prioritized experience replay (Schaul et al. 2016; --alg sac, one agent): train() samples in proportion to '
                         '(|TD| + eps)^alpha from a sum tree on the device and weights the critic loss; beta is annealed linearly to 1 at '
@@ -202,6 +210,7 @@ def run(argv=None):
     _check_critic_per(args)
     _check_num_envs(args)
     _check_host_envs(args)
+    _check_fused_sim(args)
     _check_torch_envs(args)
     _check_sim_graph(args)
     if args.device_loop:
@@ -237,6 +246,8 @@ def run(argv=None):
         return _single_device_loop(args, agent, replay, ev)
     if args.host_envs > 1:
         return _host_envs_loop(args, agent, replay, ev)
+    if args.torch_envs and args.sim_graph and args.fused_sim:
+        return _fused_sim_loop(args, agent, replay, ev)
     if args.torch_envs and args.sim_graph:
         return _sim_graph_loop(args, agent, replay, ev)
     if args.torch_envs:
@@ -530,7 +541,7 @@ def _check_torch_envs(args):
         if given:
             raise SystemExit(f'--torch-envs {N}: the torch simulator loop runs ONE agent and does not go with {flag} (seed groups have '
                              'act_device / add_device as an API only)')
-    if not args.env.startswith('Pendulum'):
+    if not args.env.startswith('Pendulum') and not getattr(args, 'fused_sim', False):         # (--fused-sim has checked --env against its own kinds)
         raise SystemExit(f'--torch-envs {N}: the example simulator is Pendulum-v1 (got --env {args.env})')
     _check_multiple('--torch-envs', N, args, f'an iteration takes {N} environment steps at once')
     if N > min(args.max_timesteps, 1e6):
@@ -617,6 +628,63 @@ def _sim_graph_loop(args, agent, replay, ev):
         info = out if out is not None else info
         if (k + 1) % env._max_episode_steps == 0:
             print(f'Total T: {t0 + N} Episode Num: {(k + 1) // env._max_episode_steps * N} Mean reward: {float(env.last_return.mean()):.3f}')
+        t = t0 + N
+        if t % args.eval_freq == 0:
+            ev.step(t, evaluate, info)
+    ev.close()
+    return agent, ev.evaluations
+
+
+FUSED_SIM_ENVS = ('Pendulum-v1', 'MountainCarContinuous-v0')               # envs/fused_sim.py KINDS
+
+
+def _check_fused_sim(args):
+    """--fused-sim: SystemExit, before anything touches the GPU, on what it does not run with"""
+    if not getattr(args, 'fused_sim', False):
+        return
+    if not int(args.torch_envs) or not getattr(args, 'sim_graph', False):
+        raise SystemExit('--fused-sim: the fused simulators are simulators of the one-graph simulator loop; give --torch-envs N --sim-graph with it')
+    if not args.env.startswith(tuple(n.split('-')[0] for n in FUSED_SIM_ENVS)):
+        raise SystemExit(f'--fused-sim: only {" and ".join(FUSED_SIM_ENVS)} are built as fused simulators (got --env {args.env})')
+
+
+def _fused_eval(agent, env, episodes):
+    """_torch_eval for a FusedSim(auto_restart=False): env.num_envs mean-action episodes at a time, one act_device launch and one step launch
+    per step -- an environment whose episode ended is frozen with its return in last_return -- and one copy at the end.  Every round resets
+    first, so it draws fresh start states."""
+    returns = []
+    act = torch.empty(env.num_envs, env.action_dim, dtype=torch.float32, device=env.obs.device)
+    while len(returns) < episodes:
+        env.reset()
+        for _ in range(env._max_episode_steps):
+            env.step_(agent.act_device(env.obs, explore=False, out=act))
+        returns.extend(env.last_return.cpu().tolist())
+    return float(np.mean(returns[:episodes]))
+
+
+def _fused_sim_loop(args, agent, replay, ev):
+    """_sim_graph_loop with --fused-sim: the simulator is a FusedSim of --env, so an `iterate_sim` graph replay holds the act launch, the
+    step-and-append launch and train().  Episodes end per environment (MountainCar's at different steps) and are counted on the device:
+    their number and the mean of the last returns are printed where an evaluation synchronises anyway, and no iteration reads the host."""
+    from rlrep_amd.envs.fused_sim import FusedSim
+    from rlrep_amd.envs.sim_loop import SimLoop
+    N, dev = int(args.torch_envs), replay.device
+    env = FusedSim(args.env, N, dev, seed=args.seed)
+    eval_env = FusedSim(args.env, min(N, int(args.eval_episodes)), dev, seed=args.seed + 100, auto_restart=False)
+    env.reset()
+    loop = SimLoop(agent, env, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps))
+
+    def evaluate():
+        score = _fused_eval(agent, eval_env, int(args.eval_episodes))
+        episodes = int(env.episodes.sum())
+        if episodes:
+            print(f'Total T: {loop.t_global} Episode Num: {episodes} Mean reward: {float(torch.nanmean(env.last_return)):.3f}')
+        return score
+    info = None
+    ev.timer = util.Timer()
+    for t0 in range(0, int(args.max_timesteps), N):                         # one iteration is N environment steps
+        out = agent.iterate_sim(loop, replay, args.batch_size, train=t0 >= args.start_timesteps)
+        info = out if out is not None else info
         t = t0 + N
         if t % args.eval_freq == 0:
             ev.step(t, evaluate, info)
