@@ -753,6 +753,55 @@ int32_t rlrep_diffsr_score_plan(int32_t S, int32_t F, int32_t u_aligned16, int32
 int32_t rlrep_nc_fwd_plan(int32_t heads, int32_t batch, int32_t feature_dim, int32_t hidden_dim,
                           int32_t* engine, int32_t* rows, int32_t* cols);
 
+/* Unit-test hook of the vlsac noise-critic kernels (csrc/noisecritic.hip; tests/test_noisecritic_kernels.py): ONE launch of one kernel of the
+ * family on caller buffers, with no agent, through the launchers the step programs use (rl_launch_nc_fwd / _dx / _dw) and the tile numbering
+ * the program builder uses.  The records carry the fields of the launch records (csrc/kparams.h NcFwdTask, NcDxTask, NcDwBatch) except the
+ * tile fields; the number of noise rows is 20.  form (may be null) receives the form that was launched.
+ *   RLREP_NC_FWD  Hm[b, j] = (1/20) sum_n elu(W[j, :] . (mean[b] + exp(clamp(lstd[b])) noise[n]) + bias[j]) for 1..4 tasks; U (the elu outputs
+ *                 [B * 20, H]) and sigma_out ([B, F]) may be null per task.  w3 (may be null per task): device scratch of
+ *                 rlrep_nc_w3_bytes(H, F) bytes that the hook fills with the bf16x3 images of W before the forward launch (the production
+ *                 producer: the shadow launch, kind 1) and hands to the kernel; needs F % 32 == 0 and W on a 16-byte boundary.
+ *                 g2 (0 = planner; 1, 2, 4 row groups of 4 batch rows a workgroup) and cols (0 = planner; 64, 128 hidden units a workgroup)
+ *                 override the plan.  Engine and the K-chunked form follow RLREP_DISABLE=x3 / RLREP_ENABLE=nc_fwd_chunk as in production.
+ *                 form[4]: engine (0 fp32 MFMA, 1 bf16x3), g2, cols, K-chunked.
+ *   RLREP_NC_DX   G[b, k] = dmean, G[b, F + k] = dlog_std of one or two heads.  form[2]: engine, 16-byte loads of U / GH (fp32 engine).
+ *   RLREP_NC_DW   gW [H, F], gb [H] of one or two tasks; sigma [B, F] dense is an input.  lean: the 128-register build of the fp32 kernel;
+ *                 splits: 0 = the planner's count, else 1..16; slab (ntasks * splits * H * F floats) and bslab (ntasks * splits * H floats)
+ *                 hold the split partials of the bf16x3 form, which nc_dw_fin_kernel adds in split order (never folded into an optimizer
+ *                 launch here); the bf16x3 form steps by noise row unless RLREP_DISABLE=nc_dw_rows.  form[4]: engine, lean, splits, by noise row.
+ * Refused with RLREP_ERR_ARG and a message starting "noisecritic:", before any GPU call: an unknown kernel, a null required pointer, a count of
+ * tasks / heads outside its range, a non-positive extent, F % 4 != 0, a row stride below the row's width or no multiple of 4, mean / lstd /
+ * noise / sigma / sigma_out off a 16-byte boundary (the kernels stage them with unconditional 16-byte accesses; rlrep_layout guarantees the
+ * alignment to the step programs), tasks of one forward launch that differ in F (its LDS table is sized once) or, where the bf16x3 engine
+ * would take them, in B or H; dW tasks that differ in B, F or H; an override the launcher cannot run (K-chunked with cols 64, a whole table
+ * past 64 KB, g2 != 2 on bf16x3); w3 with F % 32 != 0 or a W / w3 off a 16-byte boundary; slabs that are missing or too small; a seed
+ * group's call in progress. */
+enum { RLREP_NC_FWD = 0, RLREP_NC_DX = 1, RLREP_NC_DW = 2 };
+typedef struct rlrep_nc_fwd_task {
+    const float* mean; const float* lstd; int32_t ld_ml; const float* noise; const float* W; const float* bias; void* w3;
+    float* Hm; float* U; float* sigma_out; int32_t B, F, H;
+} rlrep_nc_fwd_task;
+typedef struct rlrep_nc_dw_task {
+    const float* U; const float* GH; int32_t ldgh; const float* mean; const float* sigma; int32_t ld_ml; const float* noise;
+    float* gW; float* gb; int32_t B, F, H;
+} rlrep_nc_dw_task;
+typedef union rlrep_noisecritic_args {
+    struct { int32_t ntasks, g2, cols; int32_t* form; rlrep_nc_fwd_task t[4]; } fwd;
+    struct { const float* GH[2]; int32_t ldgh; const float* U[2]; const float* W[2]; const float* noise; const float* lstd; int32_t ld_l;
+             float* G; int32_t ldg; int32_t B, F, H, nheads; int32_t* form; } dx;
+    struct { int32_t ntasks, lean, splits; float* slab; int64_t slab_floats; float* bslab; int64_t bslab_floats; int32_t* form;
+             rlrep_nc_dw_task t[2]; } dw;
+} rlrep_noisecritic_args;
+int32_t rlrep_noisecritic(int32_t kernel, const rlrep_noisecritic_args* args, void* stream);
+
+/* Host-only: bytes of the per-task w3 scratch of RLREP_NC_FWD (the three bf16 images of W [H, F] and the producer's table entry behind them);
+ * 0 for a non-positive extent. */
+int64_t rlrep_nc_w3_bytes(int32_t hidden_dim, int32_t feature_dim);
+
+/* Host-only: whether the fp32 forward of width feature_dim runs K-chunked with g2 row groups a workgroup (*chunked; RLREP_ENABLE=nc_fwd_chunk
+ * forces it), and the split count of the bf16x3 weight gradient (*splits) for `tasks` tasks of these dimensions.  Either out pointer may be null. */
+int32_t rlrep_nc_forms(int32_t tasks, int32_t batch, int32_t feature_dim, int32_t hidden_dim, int32_t g2, int32_t* chunked, int32_t* splits);
+
 /* Chains (csrc/xchain.hip): consecutive row-local stages of a step program -- the forward and dX launches of the reference's
  * feature_step / critic_step / update_actor_and_alpha (agent/vlsac/vlsac_agent.py:126-237 and siblings) -- run as ONE persistent launch
  * whose workgroups synchronise per XCD.  The launch checks its own assumptions on the device: *status receives the error word

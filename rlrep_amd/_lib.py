@@ -120,6 +120,37 @@ class ReplearnArgs(C.Union):
                 ('perturb', _RlPerturb), ('score', _RlScore), ('reg_stats', _RlRegStats), ('copy2', _RlCopy2)]
 
 
+NC_KERNEL = {'fwd': 0, 'dx': 1, 'dw': 2}                                          # RLREP_NC_* of include/rlrep.h
+
+
+class NcFwdTask(C.Structure):
+    """rlrep_nc_fwd_task (include/rlrep.h)"""
+    _fields_ = _rec('p:mean,lstd i:ld_ml p:noise,W,bias,w3,Hm,U,sigma_out i:B,F,H')
+
+
+class NcDwTask(C.Structure):
+    """rlrep_nc_dw_task (include/rlrep.h)"""
+    _fields_ = _rec('p:U,GH i:ldgh p:mean,sigma i:ld_ml p:noise,gW,gb i:B,F,H')
+
+
+class _NcFwd(C.Structure):
+    _fields_ = _rec('i:ntasks,g2,cols') + [('form', C.POINTER(C.c_int32)), ('t', NcFwdTask * 4)]
+
+
+class _NcDx(C.Structure):
+    _fields_ = ([('GH', C.c_void_p * 2)] + _rec('i:ldgh') + [('U', C.c_void_p * 2), ('W', C.c_void_p * 2)] + _rec('p:noise,lstd i:ld_l p:G i:ldg,B,F,H,nheads')
+                + [('form', C.POINTER(C.c_int32))])
+
+
+class _NcDw(C.Structure):
+    _fields_ = _rec('i:ntasks,lean,splits p:slab l:slab_floats p:bslab l:bslab_floats') + [('form', C.POINTER(C.c_int32)), ('t', NcDwTask * 2)]
+
+
+class NoisecriticArgs(C.Union):
+    """rlrep_noisecritic_args (include/rlrep.h): the record of one rlrep_noisecritic launch"""
+    _fields_ = [('fwd', _NcFwd), ('dx', _NcDx), ('dw', _NcDw)]
+
+
 def declared_symbols():
     """Every function name include/rlrep.h declares (used by the CPU test that checks the exports)."""
     src = open(HEADER_PATH).read()
@@ -279,6 +310,9 @@ def _load():
         'rlrep_replearn': (i32, [i32, P(ReplearnArgs), vp]),
         'rlrep_diffsr_score_plan': (i32, [i32, i32, i32, P(i32)]),
         'rlrep_nc_fwd_plan': (i32, [i32] * 4 + [P(i32)] * 3),
+        'rlrep_noisecritic': (i32, [i32, P(NoisecriticArgs), vp]),
+        'rlrep_nc_w3_bytes': (i64, [i32, i32]),
+        'rlrep_nc_forms': (i32, [i32] * 5 + [P(i32)] * 2),
         'rlrep_chain_status': (i32, [vp, P(C.c_uint32), vp]),
         'rlrep_build_flags': (i32, []),
         'rlrep_debug_stamp': (i32, [vp, i32, i32, vp]),

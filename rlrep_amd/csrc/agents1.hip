@@ -650,14 +650,9 @@ void build_vlsac(Builder& b, rlrep_agent* ag) {
         int g2 = 1, engine = 0, cols = 128;
         rl_nc_fwd_plan(tasks.data(), (int)tasks.size(), &engine, &g2, &cols);
         NcFwdBatch nb; memset(&nb, 0, sizeof(nb));
-        int base_tile = 0;
         nb.ntasks = (int)tasks.size(); nb.engine = engine; nb.cols = cols; nb.nt_u = rl_opt("nc_u_nt") ? 1 : 0;
-        for (size_t q = 0; q < tasks.size(); ++q) {
-            NcFwdTask& t = tasks[q];
-            t.tiles_h = (H + cols - 1) / cols; t.ntiles = ((B + 4 * g2 - 1) / (4 * g2)) * t.tiles_h; t.tile_base = base_tile; base_tile += t.ntiles;
-            nb.t[q] = t;
-        }
-        const int total = base_tile;
+        const int total = rl_nc_fwd_number_tiles(tasks.data(), (int)tasks.size(), g2, cols);
+        for (size_t q = 0; q < tasks.size(); ++q) nb.t[q] = tasks[q];
         // the form of the fp32 forward is decided here, once (RLREP_ENABLE is not read on a launch path); the K-chunked one runs under a name of its own
         const int chunked = (engine == 0 && rl_nc_fwd_chunked(F, g2)) ? 1 : 0;
         if (chunked) { ag->stage_names.push_back(std::string(what) + " [K-chunked]"); what = ag->stage_names.back().c_str(); }
@@ -745,12 +740,10 @@ void build_vlsac(Builder& b, rlrep_agent* ag) {
             NcDwBatch nb; memset(&nb, 0, sizeof(nb));
             nb.ntasks = 2;
             nb.lean = b.low_prio ? 1 : 0;     // deferred chain (fp32 kernel only): leave registers for the feature chain's launches
-            int base_tile = 0;
             auto ncdw = [&](int q, float* Ubuf, float* GH, float* gW, float* gb) {
                 NcDwTask& t = nb.t[q];
                 t.U = Ubuf; t.GH = GH; t.ldgh = H; t.mean = gt.HH; t.sigma = SIG; t.ld_ml = 2 * F;
                 t.noise = noise; t.gW = gW; t.gb = gb; t.B = B; t.F = F; t.H = H; t.N = N;
-                t.tiles_k = (F + 31) / 32; t.ntiles = ((H + 15) / 16) * t.tiles_k; t.tile_base = base_tile; base_tile += t.ntiles;
             };
             ncdw(0, U, GHm, Gw("critic.l1.weight"), Gw("critic.l1.bias"));
             ncdw(1, U + BNH, GHm + BH, Gw("critic.l4.weight"), Gw("critic.l4.bias"));
@@ -759,13 +752,7 @@ void build_vlsac(Builder& b, rlrep_agent* ag) {
             nb.engine = rl_nc_dw_engine();
             nb.fin_in_adam = ncdw_in_adam ? 1 : 0;
             nb.rows = rl_off("nc_dw_rows") ? 0 : 1;       // (read here, where the program is built: never on a launch path)
-            if (nb.engine == 1) {
-                base_tile = 0;
-                for (int q = 0; q < 2; ++q) {
-                    nb.t[q].ntiles = ((H + 63) / 64) * ((F + 63) / 64) * nb.splits; nb.t[q].tile_base = base_tile; base_tile += nb.t[q].ntiles;
-                }
-            }
-            const int total = base_tile;
+            const int total = rl_nc_dw_number_tiles(&nb);
             p.stages.push_back({[=](hipStream_t st) { return rl_launch_nc_dw(&nb, total, st); }, "noise critic dW l1/l4"});
             Builder::tag(p, RLREP_ENGINE_NOISE_CRITIC, 2.0 * 2.0 * (double)B * N * F * H, 2.0 * 4.0 * ((double)B * N * H + (double)B * H + 2.0 * (double)B * F + (double)F * H));
         }
@@ -805,7 +792,7 @@ void build_vlsac(Builder& b, rlrep_agent* ag) {
             t.W[0] = Pw("critic.l1.weight"); t.W[1] = Pw("critic.l4.weight"); t.noise = noise;
             t.lstd = gp.HH ? gp.HH + F : nullptr; t.ld_l = 2 * F; t.G = GTH; t.ldg = 2 * F;
             t.B = B; t.F = F; t.H = H; t.N = N; t.nheads = 2;
-            t.tiles_k = (F + 63) / 64; t.ntiles = ((B + 3) / 4) * t.tiles_k; t.tile_base = 0;
+            rl_nc_dx_number_tiles(&t);
             p.stages.push_back({[=](hipStream_t st) { return rl_launch_nc_dx(&t, st); }, "noise critic dX -> (dmean, dlog_std)"});
             Builder::tag(p, RLREP_ENGINE_NOISE_CRITIC, 2.0 * 2.0 * (double)B * N * F * H, 4.0 * (2.0 * ((double)B * N * H + (double)B * H + (double)F * H) + 3.0 * (double)B * F));
         }

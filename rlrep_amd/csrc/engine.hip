@@ -1633,6 +1633,155 @@ int32_t rlrep_nc_fwd_plan(int32_t heads, int32_t B, int32_t F, int32_t H, int32_
     return 0;
 }
 
+// Unit-test hook of the noise-critic kernels (noisecritic.hip): one launch on caller buffers through the launchers the step programs use, numbered
+// by the builder's own helpers (engine_internal.h rl_nc_*_number_tiles).  Every shape, stride and alignment the kernels take for granted is
+// checked HERE, before any GPU call -- rl_nc_init() included (the raised dynamic-LDS attribute of the fp32 dW kernel and the bf16x3 forwards,
+// which an agent's creation sets in production).
+static int64_t nc_w3_image_bytes(int H, int F) { return (((int64_t)6 * H * F) + 15) & ~(int64_t)15; }
+int64_t rlrep_nc_w3_bytes(int32_t H, int32_t F) {
+    if (H <= 0 || F <= 0) return 0;
+    return nc_w3_image_bytes(H, F) + (int64_t)((sizeof(ShadowEnt) + 15) & ~(size_t)15);
+}
+int32_t rlrep_nc_forms(int32_t tasks, int32_t B, int32_t F, int32_t H, int32_t g2, int32_t* chunked, int32_t* splits) {
+    rl_switches_read();
+    if (tasks <= 0 || B <= 0 || F <= 0 || H <= 0 || (g2 != 1 && g2 != 2 && g2 != 4)) { rl_set_error("nc_forms: bad argument"); return RLREP_ERR_ARG; }
+    if (chunked) *chunked = rl_nc_fwd_chunked(F, g2);
+    if (splits) *splits = rl_nc_dw_splits(B, F, H, tasks);
+    return 0;
+}
+#define NCR_REFUSE(...) { rl_set_error("noisecritic: " __VA_ARGS__); return RLREP_ERR_ARG; }
+int32_t rlrep_noisecritic(int32_t kernel, const rlrep_noisecritic_args* a, void* stream) {
+    rl_switches_read();
+    if (!a) NCR_REFUSE("null argument record")
+    if (kernel < RLREP_NC_FWD || kernel > RLREP_NC_DW) NCR_REFUSE("unknown kernel %d", kernel)
+    if (rl_grp_active()) NCR_REFUSE("a seed group's call is in progress (the family has no group form)")
+    const hipStream_t st = (hipStream_t)stream;
+    constexpr int N = 4 * NC_NF_HOST;
+    auto al16 = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
+    auto ld_ok = [](int ld, int width) { return ld >= width && (ld & 3) == 0; };
+    const char* what = "";
+    NcFwdBatch fb; NcDxTask dx; NcDwBatch wb;
+    int total = 0, g2 = 1, chunked = 0;
+    switch (kernel) {
+    case RLREP_NC_FWD: {
+        const auto& s = a->fwd;
+        what = "forward";
+        if (s.ntasks < 1 || s.ntasks > NC_MAX_TASKS) NCR_REFUSE("%s: ntasks %d outside 1..%d", what, s.ntasks, NC_MAX_TASKS)
+        if (s.g2 != 0 && s.g2 != 1 && s.g2 != 2 && s.g2 != 4) NCR_REFUSE("%s: g2 %d not in {0, 1, 2, 4}", what, s.g2)
+        if (s.cols != 0 && s.cols != 64 && s.cols != 128) NCR_REFUSE("%s: cols %d not in {0, 64, 128}", what, s.cols)
+        memset(&fb, 0, sizeof(fb));
+        bool same = true;
+        for (int q = 0; q < s.ntasks; ++q) {
+            const rlrep_nc_fwd_task& u = s.t[q];
+            if (!u.mean || !u.lstd || !u.noise || !u.W || !u.bias || !u.Hm) NCR_REFUSE("%s: task %d: null mean, lstd, noise, W, bias or Hm", what, q)
+            if (u.B <= 0 || u.F <= 0 || u.H <= 0) NCR_REFUSE("%s: task %d: B %d, F %d, H %d: non-positive extent", what, q, u.B, u.F, u.H)
+            if (u.F & 3) NCR_REFUSE("%s: task %d: F %d is no multiple of 4", what, q, u.F)
+            if (!ld_ok(u.ld_ml, u.F)) NCR_REFUSE("%s: task %d: ld_ml %d below F %d or no multiple of 4", what, q, u.ld_ml, u.F)
+            if (!al16(u.mean) || !al16(u.lstd) || !al16(u.noise) || !al16(u.sigma_out)) NCR_REFUSE("%s: task %d: mean, lstd, noise or sigma_out not on a 16-byte boundary", what, q)
+            if (u.w3 && ((u.F & 31) || !al16(u.W) || !al16(u.w3))) NCR_REFUSE("%s: task %d: w3 needs F %% 32 == 0 and W, w3 on 16-byte boundaries", what, q)
+            if (u.F != s.t[0].F) NCR_REFUSE("%s: task %d: F %d differs from task 0's %d (one LDS table size per launch)", what, q, u.F, s.t[0].F)
+            same = same && u.B == s.t[0].B && u.H == s.t[0].H;
+            NcFwdTask& t = fb.t[q];
+            t.mean = u.mean; t.lstd = u.lstd; t.ld_ml = u.ld_ml; t.noise = u.noise; t.W = u.W; t.bias = u.bias; t.W3 = (const unsigned char*)u.w3;
+            t.Hm = u.Hm; t.U = u.U; t.sigma_out = u.sigma_out; t.B = u.B; t.F = u.F; t.H = u.H; t.N = N;
+        }
+        const int F = s.t[0].F;
+        if (!same && !rl_off("x3") && (F % 32) == 0 && F >= 64) NCR_REFUSE("%s: tasks of a bf16x3 launch differ in B or H", what)
+        int engine = 0, cols = 128;
+        rl_nc_fwd_plan(fb.t, s.ntasks, &engine, &g2, &cols);
+        if (s.g2) g2 = s.g2;
+        if (s.cols) cols = s.cols;
+        if (engine == 1 && g2 != 2) NCR_REFUSE("%s: g2 %d on the bf16x3 engine (8 batch rows a workgroup: g2 = 2)", what, g2)
+        chunked = (engine == 0 && rl_nc_fwd_chunked(F, g2)) ? 1 : 0;
+        if (chunked && cols != 128) NCR_REFUSE("%s: the K-chunked form has 128 hidden units a workgroup, not %d", what, cols)
+        if (engine == 0 && !chunked && (size_t)(8 * g2 + N) * (size_t)(((F + 15) & ~15) + 16) * sizeof(float) > 64 * 1024)
+            NCR_REFUSE("%s: the whole table of F %d at g2 %d is past 64 KB of LDS", what, F, g2)
+        fb.ntasks = s.ntasks; fb.engine = engine; fb.cols = cols; fb.nt_u = rl_opt("nc_u_nt") ? 1 : 0;
+        total = rl_nc_fwd_number_tiles(fb.t, s.ntasks, g2, cols);
+        if (s.form) { s.form[0] = engine; s.form[1] = g2; s.form[2] = cols; s.form[3] = chunked; }
+    } break;
+    case RLREP_NC_DX: {
+        const auto& s = a->dx;
+        what = "dX";
+        if (s.nheads < 1 || s.nheads > 2) NCR_REFUSE("%s: nheads %d outside 1..2", what, s.nheads)
+        for (int h = 0; h < s.nheads; ++h) if (!s.GH[h] || !s.U[h] || !s.W[h]) NCR_REFUSE("%s: head %d: null GH, U or W", what, h)
+        if (!s.noise || !s.lstd || !s.G) NCR_REFUSE("%s: null noise, lstd or G", what)
+        if (s.B <= 0 || s.F <= 0 || s.H <= 0) NCR_REFUSE("%s: B %d, F %d, H %d: non-positive extent", what, s.B, s.F, s.H)
+        if (s.F & 3) NCR_REFUSE("%s: F %d is no multiple of 4", what, s.F)
+        if (!ld_ok(s.ldgh, s.H) || !ld_ok(s.ld_l, s.F) || !ld_ok(s.ldg, 2 * s.F))
+            NCR_REFUSE("%s: ldgh %d / ld_l %d / ldg %d below the row's width (H %d, F %d, 2 F) or no multiple of 4", what, s.ldgh, s.ld_l, s.ldg, s.H, s.F)
+        if (!al16(s.lstd) || !al16(s.noise)) NCR_REFUSE("%s: lstd or noise not on a 16-byte boundary", what)
+        memset(&dx, 0, sizeof(dx));
+        for (int h = 0; h < s.nheads; ++h) { dx.GH[h] = s.GH[h]; dx.U[h] = s.U[h]; dx.W[h] = s.W[h]; }
+        dx.ldgh = s.ldgh; dx.noise = s.noise; dx.lstd = s.lstd; dx.ld_l = s.ld_l; dx.G = s.G; dx.ldg = s.ldg;
+        dx.B = s.B; dx.F = s.F; dx.H = s.H; dx.N = N; dx.nheads = s.nheads;
+        total = rl_nc_dx_number_tiles(&dx);
+        if (s.form) {
+            bool vec = ((s.H & 3) == 0) && ((s.ldgh & 3) == 0);                  // (rl_launch_nc_dx's own rule)
+            for (int h = 0; h < s.nheads; ++h) vec = vec && al16(s.U[h]) && al16(s.GH[h]);
+            s.form[0] = rl_nc_dx_engine(&dx); s.form[1] = vec ? 1 : 0;
+        }
+    } break;
+    case RLREP_NC_DW: {
+        const auto& s = a->dw;
+        what = "dW";
+        if (s.ntasks < 1 || s.ntasks > 2) NCR_REFUSE("%s: ntasks %d outside 1..2", what, s.ntasks)
+        if (s.lean != 0 && s.lean != 1) NCR_REFUSE("%s: lean %d not 0 or 1", what, s.lean)
+        if (s.splits < 0 || s.splits > 16) NCR_REFUSE("%s: splits %d outside 0..16", what, s.splits)
+        memset(&wb, 0, sizeof(wb));
+        for (int q = 0; q < s.ntasks; ++q) {
+            const rlrep_nc_dw_task& u = s.t[q];
+            if (!u.U || !u.GH || !u.mean || !u.sigma || !u.noise || !u.gW || !u.gb) NCR_REFUSE("%s: task %d: null pointer", what, q)
+            if (u.B <= 0 || u.F <= 0 || u.H <= 0) NCR_REFUSE("%s: task %d: B %d, F %d, H %d: non-positive extent", what, q, u.B, u.F, u.H)
+            if (u.F & 3) NCR_REFUSE("%s: task %d: F %d is no multiple of 4", what, q, u.F)
+            if (!ld_ok(u.ldgh, u.H) || !ld_ok(u.ld_ml, u.F)) NCR_REFUSE("%s: task %d: ldgh %d / ld_ml %d below the row's width (H %d, F %d) or no multiple of 4", what, q, u.ldgh, u.ld_ml, u.H, u.F)
+            if (!al16(u.mean) || !al16(u.sigma) || !al16(u.noise)) NCR_REFUSE("%s: task %d: mean, sigma or noise not on a 16-byte boundary", what, q)
+            if (u.B != s.t[0].B || u.F != s.t[0].F || u.H != s.t[0].H) NCR_REFUSE("%s: task %d differs from task 0 in B, F or H", what, q)
+            NcDwTask& t = wb.t[q];
+            t.U = u.U; t.GH = u.GH; t.ldgh = u.ldgh; t.mean = u.mean; t.sigma = u.sigma; t.ld_ml = u.ld_ml; t.noise = u.noise; t.gW = u.gW; t.gb = u.gb;
+            t.B = u.B; t.F = u.F; t.H = u.H; t.N = N;
+        }
+        const rlrep_nc_dw_task& u0 = s.t[0];
+        wb.ntasks = s.ntasks; wb.lean = s.lean; wb.engine = rl_nc_dw_engine();
+        wb.splits = s.splits ? s.splits : rl_nc_dw_splits(u0.B, u0.F, u0.H, s.ntasks);
+        wb.fin_in_adam = 0; wb.rows = rl_off("nc_dw_rows") ? 0 : 1;
+        if (wb.engine == 1) {
+            const long long need = (long long)s.ntasks * wb.splits * u0.H;
+            if (!s.slab || !s.bslab || s.slab_floats < need * u0.F || s.bslab_floats < need)
+                NCR_REFUSE("%s: the bf16x3 form with %d splits needs a slab of %lld and a bias slab of %lld floats", what, wb.splits, need * u0.F, need)
+            wb.slab = s.slab; wb.bslab = s.bslab;
+        }
+        total = rl_nc_dw_number_tiles(&wb);
+        if (s.form) { s.form[0] = wb.engine; s.form[1] = wb.lean; s.form[2] = wb.splits; s.form[3] = wb.engine == 1 ? wb.rows : 0; }
+    } break;
+    }
+    int rc = rl_nc_init();
+    if (rc != 0) { rl_set_error("noisecritic: %s: rl_nc_init failed (%d)", what, rc); return RLREP_ERR_HIP; }
+    switch (kernel) {
+    case RLREP_NC_FWD:
+        for (int q = 0; q < fb.ntasks && rc == 0; ++q) {
+            NcFwdTask& t = fb.t[q];
+            if (!t.W3) continue;
+            // the production producer of the images (shadow launch, ShadowEnt kind 1); its one-entry table sits behind the images in the scratch
+            unsigned char* img = const_cast<unsigned char*>(t.W3);
+            ShadowEnt se; memset(&se, 0, sizeof(se));
+            se.n = (long long)t.H * t.F; se.rows = t.H; se.cols = t.F; se.kind = 1; se.sp = reinterpret_cast<float*>(img); se.src = t.W;
+            ShadowEnt* dev = reinterpret_cast<ShadowEnt*>(img + nc_w3_image_bytes(t.H, t.F));
+            hipError_t e = hipStreamSynchronize(st);
+            if (e == hipSuccess) e = hipMemcpy(dev, &se, sizeof(se), hipMemcpyHostToDevice);
+            if (e != hipSuccess) { rl_set_error("noisecritic: %s: table upload failed: %s", what, hipGetErrorString(e)); return RLREP_ERR_HIP; }
+            rc = rl_launch_shadow(dev, 1, ((t.H + 31) / 32) * (t.F / 32), nullptr, 0, st);
+        }
+        if (rc == 0) rc = rl_launch_nc_fwd(&fb, total, g2, chunked, st);
+        break;
+    case RLREP_NC_DX: rc = rl_launch_nc_dx(&dx, st); break;
+    case RLREP_NC_DW: rc = rl_launch_nc_dw(&wb, total, st); break;
+    }
+    if (rc != 0) { rl_set_error("noisecritic: %s: launch failed (%d)", what, rc); return rc < 0 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    return 0;
+}
+#undef NCR_REFUSE
+
 int32_t rlrep_chain_status(rlrep_agent* ag, uint32_t* status, void* stream) {
     GROUP_REFUSE("chain_status")
     if (!ag || !ag->xc_err) { rl_set_error("chain_status: bad argument"); return RLREP_ERR_ARG; }

@@ -162,6 +162,39 @@ static inline int rl_gemm16_number_tiles_duo(GemmTask* d1, int n1, GemmTask* d2,
     return rl_gemm16_number_tiles(d2, n2, nf2, rl_gemm16_number_tiles(d1, n1, 1));
 }
 
+// Tile numbering of the three noise-critic launches (noisecritic.hip): tile counts and first tiles of every task; each returns the launch's
+// total.  The program builder (agents1.hip build_vlsac) and the unit-test hook (rlrep_noisecritic) number through these.
+// forward: 4 * g2 batch rows x `cols` hidden units a workgroup
+static inline int rl_nc_fwd_number_tiles(NcFwdTask* tasks, int ntasks, int g2, int cols) {
+    int base_tile = 0;
+    for (int q = 0; q < ntasks; ++q) {
+        NcFwdTask& t = tasks[q];
+        t.tiles_h = (t.H + cols - 1) / cols; t.ntiles = ((t.B + 4 * g2 - 1) / (4 * g2)) * t.tiles_h; t.tile_base = base_tile; base_tile += t.ntiles;
+    }
+    return base_tile;
+}
+// dX: 4 batch rows x 64 feature columns a workgroup (both engines)
+static inline int rl_nc_dx_number_tiles(NcDxTask* t) {
+    t->tiles_k = (t->F + 63) / 64; t->ntiles = ((t->B + 3) / 4) * t->tiles_k; t->tile_base = 0;
+    return t->ntiles;
+}
+// dW: 16 (j) x 32 (k) output tiles on the fp32 engine; nb->engine == 1 (bf16x3 split-K): 64 x 64 tiles x nb->splits ranges of batch rows
+static inline int rl_nc_dw_number_tiles(NcDwBatch* nb) {
+    int base_tile = 0;
+    for (int q = 0; q < nb->ntasks; ++q) {
+        NcDwTask& t = nb->t[q];
+        t.tiles_k = (t.F + 31) / 32; t.ntiles = ((t.H + 15) / 16) * t.tiles_k; t.tile_base = base_tile; base_tile += t.ntiles;
+    }
+    if (nb->engine == 1) {
+        base_tile = 0;
+        for (int q = 0; q < nb->ntasks; ++q) {
+            NcDwTask& t = nb->t[q];
+            t.ntiles = ((t.H + 63) / 64) * ((t.F + 63) / 64) * nb->splits; t.tile_base = base_tile; base_tile += t.ntiles;
+        }
+    }
+    return base_tile;
+}
+
 struct Builder {
     rlrep_agent* ag; Workspace& ws; bool dry;
     Builder(rlrep_agent* a) : ag(a), ws(a->ws), dry(a->ws.dry) {}

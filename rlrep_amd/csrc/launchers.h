@@ -38,6 +38,7 @@ void rl_gemm_lds_plan(const GemmTask* t, int* bt, int* splits, int* kchunk);
 int rl_launch_nc_fwd(const NcFwdBatch* nb, int total_tiles, int g2, int chunked, hipStream_t st);
 int rl_nc_fwd_chunked(int F, int g2);
 int rl_launch_nc_dx(const NcDxTask* t, hipStream_t st);
+int rl_nc_dx_engine(const NcDxTask* t);
 int rl_launch_nc_dw(const NcDwBatch* nb, int total_tiles, hipStream_t st);
 int rl_nc_init();
 int rl_nc_dw_engine();
