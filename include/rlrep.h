@@ -427,6 +427,58 @@ int32_t rlrep_sim_step(const rlrep_sim_state* sim, const float* act, int64_t ld_
 int32_t rlrep_sim_step_append_ctl(const rlrep_sim_state* sim, const float* act, int64_t ld_act, float* ring_dev, int64_t max_size, int32_t row_floats,
                                   int32_t* size_dev, int64_t* ctl_dev, void* stream);
 
+/* ---- fused simulators of a kind compiled at run time (additive to ABI 4; DESIGN.md 6i.2, csrc/sim_jit.h, csrc/sim_jit.hip) -------------------
+ * The caller hands over the C++ text of ONE struct, `name` (csrc/sim_jit.h documents it; rlrep_amd/envs/kinds/ holds two examples): NX state
+ * doubles (1..RLREP_SIMX_MAX_NX), S observations (1..RLREP_SIMX_MAX_S), A actions (1..RLREP_SIMX_MAX_A), LIMIT >= 1, TERMINATES, and the
+ * functions start, observe and dynamics.  rlrep_sim_kind_compile compiles sim_jit.h + that text + static_asserts that hold the struct's
+ * constants to the description + the three kernels for the current device with hiprtc (-O3 -ffp-contract=off: fp64 arithmetic as written) and
+ * loads the module; the kernels are launched with hipModuleLaunchKernel.  A compile failure is RLREP_ERR_HIP with the compiler's log, from
+ * its first error on and truncated, in rlrep_last_error().  rlrep_sim_kind_source writes the text that would be compiled (NUL-terminated,
+ * truncated to cap) and returns its full length, or a negative RLREP_ERR_*; rlrep_sim_kind_code compiles that text for `arch` (e.g. "gfx950")
+ * WITHOUT a device into code_out (cap bytes) and sets *size_out -- for checking a kind where no GPU is.  rlrep_sim_kind_info: the
+ * description's constants and, per kernel (0 start, 1 step, 2 step_append_ctl), registers, scratch (spill) bytes and static LDS bytes as
+ * hipFuncGetAttribute reported them after the load.  Kinds are independent objects: any number live at once, destroyed in any order.  A
+ * kind's record BEGINS with its rlrep_sim_kind_info_t, and the refusals of rlrep_simx_* read nothing else of it.
+ *
+ * rlrep_simx_state is rlrep_sim_state with `x` float64 [NX, n] (word i of environment e at x[i * n + e]) in place of x0 / x1.  Block q of
+ * start state k of environment e is the Philox4x32-10 block with key `seed` and counter {k lo, k hi, e, 0xE3000000 + q}; start() receives
+ * 4 * ceil(NX / 2) words.  rlrep_simx_start / _step / _step_append_ctl are rlrep_sim_start / _step / _step_append_ctl rule for rule, with
+ * act[e * ld_act + j], j < A, and ring row [s | a_0..a_{A-1} | s' | r | done].  Each is ONE launch, stream-ordered and capturable: no copy,
+ * no allocation, no synchronisation, nothing read on the host.
+ * Refused with RLREP_ERR_ARG before any GPU call, the message starting with the entry point's name ("sim_kind_compile:", "simx_start:",
+ * "simx_step:", "simx_step_append_ctl:"): a null description, name or kind; a null or empty source; S, A, NX or limit outside the caps; a
+ * null array; n outside [1, RLREP_SIM_MAX_ENVS] or above max_size; ld_act below A; row_floats != 2 S + A + 2. */
+#define RLREP_SIMX_MAX_NX 8
+#define RLREP_SIMX_MAX_S 16
+#define RLREP_SIMX_MAX_A 8
+typedef struct rlrep_sim_kind rlrep_sim_kind;
+typedef struct rlrep_sim_kind_desc {
+    const char* name;                  /* the struct's name in `source` (a C identifier) */
+    const char* source;                /* the C++ text of the struct (and whatever helpers it needs) */
+    int32_t S, A, NX, limit, terminates, reserved;
+} rlrep_sim_kind_desc;
+typedef struct rlrep_sim_kind_info_t {
+    int32_t S, A, NX, limit, terminates, reserved;
+    int32_t regs[3], scratch_bytes[3], lds_bytes[3];
+} rlrep_sim_kind_info_t;
+typedef struct rlrep_simx_state {
+    double* x; double* ep_return; double* last_return;
+    int32_t* t; int64_t* episodes; int64_t* starts; float* obs;
+    int32_t n, auto_restart;
+    uint64_t seed;
+} rlrep_simx_state;
+int32_t rlrep_simx_state_bytes(void);
+int32_t rlrep_sim_kind_compile(const rlrep_sim_kind_desc* desc, rlrep_sim_kind** kind_out);
+void rlrep_sim_kind_destroy(rlrep_sim_kind* kind);
+int32_t rlrep_sim_kind_info(const rlrep_sim_kind* kind, rlrep_sim_kind_info_t* info_out);
+int64_t rlrep_sim_kind_source(const rlrep_sim_kind_desc* desc, char* text_out, int64_t cap);
+int32_t rlrep_sim_kind_code(const rlrep_sim_kind_desc* desc, const char* arch, void* code_out, int64_t cap, int64_t* size_out);
+int32_t rlrep_simx_start(const rlrep_sim_kind* kind, const rlrep_simx_state* sim, void* stream);
+int32_t rlrep_simx_step(const rlrep_sim_kind* kind, const rlrep_simx_state* sim, const float* act, int64_t ld_act, float* next_obs, float* reward,
+                        float* done, void* stream);
+int32_t rlrep_simx_step_append_ctl(const rlrep_sim_kind* kind, const rlrep_simx_state* sim, const float* act, int64_t ld_act, float* ring_dev,
+                                   int64_t max_size, int32_t row_floats, int32_t* size_dev, int64_t* ctl_dev, void* stream);
+
 /* ---- prioritized replay for sac (additive to ABI 4; DESIGN.md 6f, csrc/per.hip) ------------------------------------------------------
  * The priorities live beside the ring in a caller-owned sum tree: tree_dev float32[2 P], P = the smallest power of two >= the ring's rows,
  * node n = tree[2n] + tree[2n + 1] (one fp32 add), row i's leaf = tree[P + i], leaves of unwritten rows 0 (the caller zeroes the tree once).

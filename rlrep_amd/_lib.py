@@ -72,6 +72,24 @@ class SimState(C.Structure):
         ('kind', C.c_int32), ('n', C.c_int32), ('seed', C.c_uint64), ('auto_restart', C.c_int32), ('reserved', C.c_int32)]
 
 
+class SimKindDesc(C.Structure):
+    """rlrep_sim_kind_desc (include/rlrep.h): a simulator kind given as text (envs/fused_sim.py SimKind)."""
+    _fields_ = [('name', C.c_char_p), ('source', C.c_char_p), ('S', C.c_int32), ('A', C.c_int32), ('NX', C.c_int32), ('limit', C.c_int32),
+                ('terminates', C.c_int32), ('reserved', C.c_int32)]
+
+
+class SimKindInfo(C.Structure):
+    """rlrep_sim_kind_info_t (include/rlrep.h): a compiled kind's constants and, per kernel, registers / scratch bytes / static LDS bytes."""
+    _fields_ = [('S', C.c_int32), ('A', C.c_int32), ('NX', C.c_int32), ('limit', C.c_int32), ('terminates', C.c_int32), ('reserved', C.c_int32),
+                ('regs', C.c_int32 * 3), ('scratch_bytes', C.c_int32 * 3), ('lds_bytes', C.c_int32 * 3)]
+
+
+class SimxState(C.Structure):
+    """rlrep_simx_state (include/rlrep.h): the arrays of a fused simulator of a compiled kind; rlrep_simx_state_bytes() is its size."""
+    _fields_ = [(n, C.c_void_p) for n in ('x', 'ep_return', 'last_return', 't', 'episodes', 'starts', 'obs')] + [
+        ('n', C.c_int32), ('auto_restart', C.c_int32), ('seed', C.c_uint64)]
+
+
 RL_KERNEL = {'infonce': 0, 'score_infonce': 1, 'colsum': 2, 'speder_rows': 3, 'speder_grads': 4, 'perturb': 5, 'score': 6, 'reg_stats': 7, 'copy2': 8}
 SCORE_FORM = ('LDS32', 'LDS64', 'LDS128', 'SMALL1', 'SMALL2', 'SMALL4', 'VEC', 'ROWS')          # RLREP_SCORE_* of include/rlrep.h, by value
 
@@ -255,6 +273,15 @@ def _load():
         'rlrep_sim_start': (i32, [P(SimState), vp]),
         'rlrep_sim_step': (i32, [P(SimState), vp, i64, vp, vp, vp, vp]),
         'rlrep_sim_step_append_ctl': (i32, [P(SimState), vp, i64, vp, i64, i32, vp, vp, vp]),
+        'rlrep_simx_state_bytes': (i32, []),
+        'rlrep_sim_kind_compile': (i32, [P(SimKindDesc), P(vp)]),
+        'rlrep_sim_kind_destroy': (None, [vp]),
+        'rlrep_sim_kind_info': (i32, [vp, P(SimKindInfo)]),
+        'rlrep_sim_kind_source': (i64, [P(SimKindDesc), vp, i64]),
+        'rlrep_sim_kind_code': (i32, [P(SimKindDesc), C.c_char_p, vp, i64, P(i64)]),
+        'rlrep_simx_start': (i32, [vp, P(SimxState), vp]),
+        'rlrep_simx_step': (i32, [vp, P(SimxState), vp, i64, vp, vp, vp, vp]),
+        'rlrep_simx_step_append_ctl': (i32, [vp, P(SimxState), vp, i64, vp, i64, i32, vp, vp, vp]),
         'rlrep_per_add': (i32, [vp, i64, vp, i64, i64, i64, vp]),
         'rlrep_per_rebuild': (i32, [vp, i64, vp]),
         'rlrep_per_sample': (i32, [vp, vp, i64, vp, vp, vp, i32, i32, u64, u64, vp, vp]),

@@ -16,16 +16,21 @@ LIBNAME="${OUTNAME:-librlrep_hip.so}"
 mkdir -p "$OUT" "$OBJ"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -Wno-unused-function $EXTRA_FLAGS"
-SRCS="gemm16 gemm_lds noisecritic elementwise per per_group per_fill per_fill_group nstep nstep_targets actor_tile group_clone group_env sim_step replearn comm $EXP_SRCS engine agents1 agents2 group_api $EXTRA_SRCS"
+SRCS="gemm16 gemm_lds noisecritic elementwise per per_group per_fill per_fill_group nstep nstep_targets actor_tile group_clone group_env sim_step sim_jit sim_jit_check replearn comm $EXP_SRCS engine agents1 agents2 group_api $EXTRA_SRCS"
+# sim_jit.h is also carried in the library as text, for the run-time compile of a user's simulator kind (sim_jit.hip includes this file)
+{ printf 'R"SIMJIT('; cat "$HERE/sim_jit.h"; printf ')SIMJIT"\n'; } > "$OBJ/sim_jit_text.inc.new"
+if cmp -s "$OBJ/sim_jit_text.inc.new" "$OBJ/sim_jit_text.inc"; then rm -f "$OBJ/sim_jit_text.inc.new"; else mv "$OBJ/sim_jit_text.inc.new" "$OBJ/sim_jit_text.inc"; fi
 pids=()
 for f in $SRCS; do
-  if [ ! -f "$OBJ/$f.o" ] || [ "$HERE/$f.hip" -nt "$OBJ/$f.o" ] || [ -n "$(find "$HERE" -maxdepth 1 -name '*.h' -newer "$OBJ/$f.o")" ] || [ "$HERE/../../include/rlrep.h" -nt "$OBJ/$f.o" ]; then
+  if [ ! -f "$OBJ/$f.o" ] || [ "$HERE/$f.hip" -nt "$OBJ/$f.o" ] || [ -n "$(find "$HERE" -maxdepth 1 -name '*.h' -newer "$OBJ/$f.o")" ] || [ "$HERE/../../include/rlrep.h" -nt "$OBJ/$f.o" ] || { [ "$f" = sim_jit_check ] && [ -n "$(find "$HERE/../envs/kinds" -name '*.h' -newer "$OBJ/$f.o")" ]; }; then
     PF=""; { [ "$f" = gemm16 ] || [ "$f" = elementwise ] || [ "$f" = gemm_lds ]; } && PF="-mllvm -amdgpu-kernarg-preload-count=14"     # gemm16_kernel / adam_kernel / the gemm_lds kernels: leading scalars preloaded into SGPRs
+    [ "$f" = sim_jit ] && PF="-I$OBJ"                        # sim_jit_text.inc
+    [ "$f" = sim_jit_check ] && PF="-ffp-contract=off -I$HERE/../envs/kinds"   # the example kinds, compiled as the run-time compile compiles them
     $HIPCC $FLAGS $PF -c "$HERE/$f.hip" -o "$OBJ/$f.o" &
     pids+=($!)
   fi
 done
 for p in "${pids[@]}"; do wait $p; done
 LINK=""; for f in $SRCS; do LINK="$LINK $OBJ/$f.o"; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/$LIBNAME" $LINK
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT/$LIBNAME" $LINK -L"${ROCM_PATH:-/opt/rocm}/lib" -lhiprtc
 echo "built $OUT/$LIBNAME"

@@ -19,15 +19,23 @@ stands: it keeps to SimLoop's simulator contract with no `graph_generators`.
 written in place on every call.  `step_append_(actions, buffer, ctl)` is the step that also packs the N transitions into the replay ring from
 the loop record's cursor and advances the record: with it SimLoop's iteration in front of train() is two launches.
 
+A kind of the user's own (csrc/sim_jit.h): `CustomFusedSim(source, num_envs, ...)` takes the C++ text of ONE struct -- NX state
+doubles, S observations, A actions, LIMIT, TERMINATES, start / observe / dynamics -- and the library compiles it at run time into the same three
+launches; `rlrep_amd/envs/kinds/` holds two examples (`example_kind('pendulum')`, `example_kind('point_mass')`).  It is a drop-in for FusedSim
+in SimLoop / iterate_sim; its state words are one array `x` float64 [NX, N].  `SimKind(source)` is the compiled kind alone, so that several
+simulators (training and evaluation) share one compile.
+
 `auto_restart=False` is the form an evaluation takes: an environment whose episode ended is frozen (t = -1) with its return in
 `last_return`, while its neighbours go on -- MountainCar's episodes end at different steps.
 """
 import ctypes as C
+import os
+import re
 
 import numpy as np
 import torch
 
-from rlrep_amd._lib import lib, check, SimState
+from rlrep_amd._lib import lib, check, SimState, SimKindDesc, SimKindInfo, SimxState
 from rlrep_amd.core import _stream
 
 MAX_ENVS = 65536                                            # include/rlrep.h RLREP_SIM_MAX_ENVS
@@ -151,3 +159,183 @@ class FusedMountainCar(FusedSim):
 
     def __init__(self, num_envs, device=None, seed=0, auto_restart=True):
         super().__init__(KIND_MOUNTAIN_CAR_CONTINUOUS, num_envs, device, seed, auto_restart)
+
+
+# ---- kinds compiled at run time (include/rlrep.h rlrep_sim_kind_*, rlrep_simx_*; csrc/sim_jit.h) ------------------------------------------------
+MAX_NX, MAX_S, MAX_A = 8, 16, 8                             # include/rlrep.h RLREP_SIMX_MAX_*
+KINDS_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'kinds')
+XSTATE_NAMES = ('x', 'ep_return', 'last_return', 't', 'episodes', 'starts', 'obs')
+KERNELS = ('start', 'step', 'step_append_ctl')
+# host observations of the example kinds, for set_state (a kind of the user's own passes `observe=` or `obs=`)
+_EXAMPLE_OBSERVE = {'KindPendulum': lambda x: np.stack([np.cos(x[0]), np.sin(x[0]), x[1]], axis=1).astype(np.float32),
+                    'KindPointMass': lambda x: np.ascontiguousarray(x.T).astype(np.float32)}
+
+
+def example_kind(which):
+    """the text of an example kind: 'pendulum' (Pendulum-v1, the built-in kind's operations) or 'point_mass' (NX = 4, S = 4, A = 2)"""
+    path = os.path.join(KINDS_DIR, f'{which}.h')
+    if not os.path.exists(path):
+        raise ValueError(f'example_kind: no example {which!r} under {KINDS_DIR}')
+    with open(path) as f:
+        return f.read()
+
+
+def kind_constants(source):
+    """dict(name, S, A, NX, limit, terminates, action_range) read from a kind's text: the first `struct NAME`, the integer constants NX, S, A,
+    LIMIT, the bool TERMINATES and, where given, the floats ACT_LO / ACT_HI (default -1, 1).  A constant the text does not spell as a literal
+    is None: give it to SimKind by keyword.  The compile holds every one of them to the struct (static_assert)."""
+    text = re.sub(r'//[^\n]*|/\*.*?\*/', '', str(source), flags=re.S)
+    m = re.search(r'\bstruct\s+([A-Za-z_]\w*)', text)
+
+    def num(name, pat=r'(\d+)', conv=int):
+        m = re.search(r'\b' + name + r'\s*=\s*' + pat, text)
+        return conv(m.group(1)) if m else None
+    flt = r'([-+]?(?:\d+\.?\d*|\.\d+)(?:[eE][-+]?\d+)?)f?'
+    lo, hi = num('ACT_LO', flt, float), num('ACT_HI', flt, float)
+    return dict(name=m.group(1) if m else None, S=num('S'), A=num('A'), NX=num('NX'), limit=num('LIMIT'),
+                terminates=num('TERMINATES', r'(true|false)', lambda v: v == 'true'),
+                action_range=(-1.0 if lo is None else lo, 1.0 if hi is None else hi))
+
+
+class SimKind(object):
+    """One simulator kind compiled from `source` (the C++ text of one struct: csrc/sim_jit.h) for the current device: rlrep_sim_kind_compile.
+    name, S, A, NX, limit, terminates default to what the text spells (kind_constants); the compile refuses a struct that differs from them.
+    A compile failure raises RuntimeError with the compiler's log.  Kinds are independent: any number live at once, destroyed in any order."""
+
+    def __init__(self, source, name=None, S=None, A=None, NX=None, limit=None, terminates=None, action_range=None):
+        self._h = None
+        self.source = str(source) if source is not None else ''
+        self.desc(self.source, name=name, S=S, A=A, NX=NX, limit=limit, terminates=terminates)   # (raises on what the text leaves open)
+        d, k = self._desc, kind_constants(self.source)
+        self.name, self.state_dim, self.action_dim, self.nx, self.limit, self.terminates = d.name.decode(), d.S, d.A, d.NX, d.limit, bool(d.terminates)
+        self.action_range = tuple(float(v) for v in (action_range if action_range is not None else k['action_range']))
+        h = C.c_void_p()
+        check(lib.rlrep_sim_kind_compile(C.byref(d), C.byref(h)), 'sim_kind_compile')
+        self._h = h
+
+    def desc(self, source, **given):
+        """the rlrep_sim_kind_desc of `source` (kept alive on self)"""
+        k = kind_constants(source)
+        val = {key: (given.get(key) if given.get(key) is not None else k[key]) for key in ('name', 'S', 'A', 'NX', 'limit', 'terminates')}
+        missing = [key for key, v in val.items() if v is None]
+        if missing:
+            raise ValueError(f'SimKind: the text does not spell {", ".join(missing)} as a literal; give it by keyword')
+        self._keep = (str(val['name']).encode(), str(source).encode())
+        self._desc = SimKindDesc(name=self._keep[0], source=self._keep[1], S=int(val['S']), A=int(val['A']), NX=int(val['NX']), limit=int(val['limit']),
+                                 terminates=int(bool(val['terminates'])))
+        return self._desc
+
+    def compile_text(self):
+        """the whole text the library compiled: sim_jit.h, the struct, the static_asserts, the kernels"""
+        return assembled_text(self._desc)
+
+    def info(self):
+        """dict kernel -> dict(regs, scratch_bytes, lds_bytes), as hipFuncGetAttribute reported them after the load"""
+        out = SimKindInfo()
+        check(lib.rlrep_sim_kind_info(self._h, C.byref(out)), 'sim_kind_info')
+        return {k: dict(regs=int(out.regs[i]), scratch_bytes=int(out.scratch_bytes[i]), lds_bytes=int(out.lds_bytes[i])) for i, k in enumerate(KERNELS)}
+
+    def destroy(self):
+        if self._h is not None:
+            lib.rlrep_sim_kind_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def assembled_text(desc):
+    """rlrep_sim_kind_source: the text the library would compile for a SimKindDesc (no GPU)"""
+    n = lib.rlrep_sim_kind_source(C.byref(desc), None, 0)
+    if n < 0:
+        check(int(n), 'sim_kind_source')
+    buf = C.create_string_buffer(int(n) + 1)
+    lib.rlrep_sim_kind_source(C.byref(desc), buf, int(n) + 1)
+    return buf.value.decode()
+
+
+class CustomFusedSim(FusedSim):
+    """N environments of a kind given as text (or as a compiled SimKind) on `device`: FusedSim's interface -- obs, num_envs, seed, reset(),
+    step_ / step, step_append_(actions, buffer, ctl), set_state, state() -- and kernel_info().  The state words are `x` float64 [NX, N].
+    name: the struct's name, where the text holds several structs.  observe: a host function x [NX, N] float64 -> obs [N, S] float32 that
+    set_state uses (the two example kinds bring theirs)."""
+
+    def __init__(self, source, num_envs, device=None, seed=0, auto_restart=True, name=None, observe=None, **constants):
+        who = type(self).__name__
+        N = int(num_envs)
+        if not 1 <= N <= MAX_ENVS:
+            raise ValueError(f'{who}: num_envs {num_envs} outside [1, {MAX_ENVS}]')
+        self.device = dev = torch.device(device if device is not None else 'cuda')
+        if dev.type != 'cuda':
+            raise ValueError(f'{who}: the fused simulators live on the GPU (got device {dev})')
+        with torch.cuda.device(dev):
+            self.kind = source if isinstance(source, SimKind) else SimKind(source, name=name, **constants)
+        k = self.kind
+        self.num_envs, self.seed, self.auto_restart = N, int(seed), bool(auto_restart)
+        self.env_name, self.state_dim, self.action_dim, self.nx, self._max_episode_steps, self.action_range = (k.name, k.state_dim, k.action_dim, k.nx, k.limit,
+                                                                                                               k.action_range)
+        self._observe = observe if observe is not None else _EXAMPLE_OBSERVE.get(k.name)
+        f64 = lambda fill=0.0: torch.full((N,), fill, dtype=torch.float64, device=dev)  # noqa: E731
+        self.x = torch.zeros(k.nx, N, dtype=torch.float64, device=dev)
+        self.ep_return, self.last_return = f64(), f64(float('nan'))
+        self.t = torch.zeros(N, dtype=torch.int32, device=dev)
+        self.episodes = torch.zeros(N, dtype=torch.int64, device=dev)
+        self.starts = torch.zeros(N, dtype=torch.int64, device=dev)
+        self.obs = torch.zeros(N, self.state_dim, dtype=torch.float32, device=dev)
+        self.next_obs = torch.zeros(N, self.state_dim, dtype=torch.float32, device=dev)
+        self.reward = torch.zeros(N, dtype=torch.float32, device=dev)
+        self.done = torch.zeros(N, dtype=torch.float32, device=dev)
+        self._st = SimxState(n=N, seed=self.seed & 0xFFFFFFFFFFFFFFFF, auto_restart=int(self.auto_restart),
+                             **{name: getattr(self, name).data_ptr() for name in XSTATE_NAMES})
+        assert C.sizeof(SimxState) == lib.rlrep_simx_state_bytes()
+
+    def reset(self):
+        """ONE launch (rlrep_simx_start): every environment begins a new episode from its next start state; returns `obs`"""
+        check(lib.rlrep_simx_start(self.kind._h, C.byref(self._st), _stream()), 'simx_start')
+        return self.obs
+
+    def step_(self, actions):
+        """ONE launch (rlrep_simx_step): actions [N, A] float32, raw -> (next_obs [N, S], reward [N], done [N] float32), the simulator's own
+        tensors, written in place; `obs` then holds what the next step acts on"""
+        ld = self._actions(actions, 'step_')
+        check(lib.rlrep_simx_step(self.kind._h, C.byref(self._st), _ptr(actions), ld, _ptr(self.next_obs), _ptr(self.reward), _ptr(self.done), _stream()),
+              'simx_step')
+        return self.next_obs, self.reward, self.done
+
+    step = step_
+
+    def step_append_(self, actions, buffer, ctl):
+        """ONE launch (rlrep_simx_step_append_ctl): the step, the N transitions [obs before the step, actions, s', r, done] into `buffer`'s ring
+        from the cursor in the loop record `ctl`, the fill level into the buffer's size word, the record advanced as SimLoop.append advances
+        it.  next_obs / reward / done are NOT written."""
+        ld = self._actions(actions, 'step_append_')
+        if (buffer.state_dim, buffer.action_dim) != (self.state_dim, self.action_dim):
+            raise ValueError(f'{type(self).__name__}.step_append_: needs a ReplayBuffer of {self.state_dim} observations and {self.action_dim} actions')
+        check(lib.rlrep_simx_step_append_ctl(self.kind._h, C.byref(self._st), _ptr(actions), ld, _ptr(buffer.ring), buffer.max_size, buffer.row,
+                                             _ptr(buffer._size_dev), _ptr(ctl), _stream()), 'simx_step_append_ctl')
+
+    def set_state(self, x, t=0, obs=None):
+        """tests: continue from the state words x [NX, N] (or [NX], the same for every environment) at step t (a number or [N]) of the episode;
+        in place.  The observation is `obs` [N, S] where given, else the host `observe` of the kind."""
+        N, NX = self.num_envs, self.nx
+        x = np.asarray(x, np.float64)
+        x = np.array(np.broadcast_to(x.reshape(NX, -1), (NX, N)))
+        if obs is None:
+            if self._observe is None:
+                raise ValueError(f'{type(self).__name__}.set_state: give obs=, or observe= at construction (the kind is known to the device only)')
+            obs = self._observe(x)
+        obs = np.ascontiguousarray(np.asarray(obs, np.float32).reshape(N, self.state_dim))
+        self.x.copy_(torch.from_numpy(x))
+        self.t.copy_(torch.from_numpy(np.array(np.broadcast_to(np.asarray(t, np.int32), (N,)))))
+        self.obs.copy_(torch.from_numpy(obs))
+
+    def state(self):
+        """dict of host copies of every array (synchronises)"""
+        return {k: getattr(self, k).cpu().numpy() for k in XSTATE_NAMES}
+
+    def kernel_info(self):
+        """dict kernel -> dict(regs, scratch_bytes, lds_bytes) of the compiled kind: scratch_bytes > 0 means the kind spills"""
+        return self.kind.info()

@@ -65,6 +65,9 @@ are captured together.  Evaluations are the eager ones of --torch-envs.
 one (envs/fused_sim.py `FusedSim`, csrc/sim_step.hip): the act launch reads the simulator's observations in place and ONE launch steps the N
 environments and appends their transitions, so the graph holds two launches in front of train().  Episodes end and restart per environment
 on the device; evaluations step a FusedSim(auto_restart=False) of their own, one act_device and one step launch per step.
+`--fused-sim-source PATH` (only with all three of --torch-envs N --sim-graph --fused-sim) makes that simulator a kind of your own: PATH holds
+the C++ text of one struct (csrc/sim_jit.h; rlrep_amd/envs/kinds/ has two examples), compiled at run time (`CustomFusedSim`, DESIGN.md
+6i.2); the agent is built from the kind's S and A, and --env only names the log directory.
 
 `--critic-per` (vlsac, ctrlsac, spedersac, diffsrsac; one agent) trains from a CriticPrioritizedReplayBuffer: the minibatch the critic and actor
 steps reuse is drawn from a sum tree on the device, the critic loss is weighted and the |TD| errors come back as priorities (DESIGN.md
@@ -201,7 +204,12 @@ def run(argv=None):
                         'actor steps of train() bootstrap from rows gathered up to N steps forward through the replay ring, while the feature step '
                         'keeps training on the one-step rows of the same minibatch.  --n-stride as for --n-step.  One agent, one GPU; goes with '
                         '--host-envs, --torch-envs (--sim-graph) and --device-loop --num-envs; not with --seeds / --sweep, --per or --n-step')
+    p.add_argument('--fused-sim-source', default=None, metavar='PATH',
+                   help='with --torch-envs N --sim-graph --fused-sim: the simulator is a kind of your own, the C++ text of one struct in PATH '
+                        '(csrc/sim_jit.h; examples under rlrep_amd/envs/kinds/), compiled at run time (envs/fused_sim.py CustomFusedSim); the '
+                        'agent is built from the kind\'s S and A and --env only names the log directory')
     args = p.parse_args(argv)
+    _check_fused_sim_source(args)
     _check_nstep(args)
     _check_critic_nstep(args)
     _check_group_critic_per(args)
@@ -224,7 +232,10 @@ def run(argv=None):
     if args.device_env:
         raise SystemExit('--device-env: device environments are built for seed groups (give --seeds and / or --sweep)')
 
-    env, eval_env = envs.make(args.env), envs.make(args.env)
+    if getattr(args, 'fused_sim_source', None):
+        env = eval_env = _KindSpaces(args.fused_kind)
+    else:
+        env, eval_env = envs.make(args.env), envs.make(args.env)
     env.seed(args.seed)
     eval_env.seed(args.seed)
     max_length = env._max_episode_steps
@@ -644,8 +655,44 @@ def _check_fused_sim(args):
         return
     if not int(args.torch_envs) or not getattr(args, 'sim_graph', False):
         raise SystemExit('--fused-sim: the fused simulators are simulators of the one-graph simulator loop; give --torch-envs N --sim-graph with it')
-    if not args.env.startswith(tuple(n.split('-')[0] for n in FUSED_SIM_ENVS)):
+    if not getattr(args, 'fused_sim_source', None) and not args.env.startswith(tuple(n.split('-')[0] for n in FUSED_SIM_ENVS)):
         raise SystemExit(f'--fused-sim: only {" and ".join(FUSED_SIM_ENVS)} are built as fused simulators (got --env {args.env})')
+
+
+def _check_fused_sim_source(args):
+    """--fused-sim-source PATH: SystemExit, before anything touches the GPU, unless it comes with --torch-envs N --sim-graph --fused-sim, PATH
+    is readable and its text spells the kind's constants; leaves the text and the constants on args (fused_kind_text, fused_kind)"""
+    path = getattr(args, 'fused_sim_source', None)
+    if not path:
+        return
+    for flag, given in (('--torch-envs N', int(args.torch_envs) > 0), ('--sim-graph', getattr(args, 'sim_graph', False)),
+                        ('--fused-sim', getattr(args, 'fused_sim', False))):
+        if not given:
+            raise SystemExit(f'--fused-sim-source: a kind of your own is a simulator of the fused one-graph loop; give {flag} with it '
+                             '(--torch-envs N --sim-graph --fused-sim)')
+    from rlrep_amd.envs.fused_sim import kind_constants
+    try:
+        with open(path) as f:
+            args.fused_kind_text = f.read()
+    except OSError as exc:
+        raise SystemExit(f'--fused-sim-source: cannot read {path}: {exc}')
+    args.fused_kind = k = kind_constants(args.fused_kind_text)
+    missing = [key for key in ('name', 'S', 'A', 'NX', 'limit', 'terminates') if k[key] is None]
+    if missing:
+        raise SystemExit(f'--fused-sim-source: {path} does not spell {", ".join(missing)} as a literal (csrc/sim_jit.h describes a kind\'s struct)')
+
+
+class _KindSpaces(object):
+    """what run() reads of a host environment, for a kind that exists on the device only: the spaces' shapes and the action range"""
+
+    def __init__(self, k):
+        lo, hi = k['action_range']
+        self.observation_space = type('Space', (), dict(shape=(int(k['S']),)))()
+        self.action_space = type('Space', (), dict(shape=(int(k['A']),), low=np.full(int(k['A']), lo, np.float32), high=np.full(int(k['A']), hi, np.float32)))()
+        self._max_episode_steps = int(k['limit'])
+
+    def seed(self, seed):
+        pass
 
 
 def _fused_eval(agent, env, episodes):
@@ -666,11 +713,16 @@ def _fused_sim_loop(args, agent, replay, ev):
     """_sim_graph_loop with --fused-sim: the simulator is a FusedSim of --env, so an `iterate_sim` graph replay holds the act launch, the
     step-and-append launch and train().  Episodes end per environment (MountainCar's at different steps) and are counted on the device:
     their number and the mean of the last returns are printed where an evaluation synchronises anyway, and no iteration reads the host."""
-    from rlrep_amd.envs.fused_sim import FusedSim
+    from rlrep_amd.envs.fused_sim import CustomFusedSim, FusedSim, SimKind
     from rlrep_amd.envs.sim_loop import SimLoop
     N, dev = int(args.torch_envs), replay.device
-    env = FusedSim(args.env, N, dev, seed=args.seed)
-    eval_env = FusedSim(args.env, min(N, int(args.eval_episodes)), dev, seed=args.seed + 100, auto_restart=False)
+    if getattr(args, 'fused_sim_source', None):             # a kind of the user's own: ONE run-time compile, shared by the two simulators
+        kind = SimKind(args.fused_kind_text)
+        env = CustomFusedSim(kind, N, dev, seed=args.seed)
+        eval_env = CustomFusedSim(kind, min(N, int(args.eval_episodes)), dev, seed=args.seed + 100, auto_restart=False)
+    else:
+        env = FusedSim(args.env, N, dev, seed=args.seed)
+        eval_env = FusedSim(args.env, min(N, int(args.eval_episodes)), dev, seed=args.seed + 100, auto_restart=False)
     env.reset()
     loop = SimLoop(agent, env, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps))
 
