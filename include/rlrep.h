@@ -735,8 +735,9 @@ int32_t rlrep_gemm(int32_t engine, int32_t la, int32_t lb, const float* a_dev, i
  *   duo_split  > 0: tasks [0, duo_split) are row-major x k-major products (dX form, 16-column tiles), the rest k-major x k-major ones
  *                   (weight-gradient form, 16 * nf2 columns, nf2 = 1 or 4) -- one launch of both forms; la / lb are ignored.
  * Which front end the launch got: the difference of rlrep_front_end_counts around the call.  RLREP_ERR_ARG (before any GPU call) for ntasks
- * outside 1..8, nf not in {1, 2, 4}, a null a / b / c, non-positive extents or an epilogue outside {0, 1, 3}.  The fused-loss, policy,
- * reparameterisation, fused-short-product and optimizer epilogues are reachable only through an agent. */
+ * outside 1..8, nf not in {1, 2, 4}, a null a / b / c, non-positive extents or an epilogue outside {0, 1, 3}.  The fused-loss, policy and
+ * reparameterisation epilogues (the last with its fused short product and mse phase) have a hook of their own, rlrep_heads; the ELU form of the
+ * fused short product, its forward form and the optimizer epilogues are reachable only through an agent. */
 typedef struct rlrep_gemm16_task {
     const float* a; const float* b; float* c;
     int32_t lda, ldb, ldc, rows, cols, inner;
@@ -853,6 +854,64 @@ int64_t rlrep_nc_w3_bytes(int32_t hidden_dim, int32_t feature_dim);
 /* Host-only: whether the fp32 forward of width feature_dim runs K-chunked with g2 row groups a workgroup (*chunked; RLREP_ENABLE=nc_fwd_chunk
  * forces it), and the split count of the bf16x3 weight gradient (*splits) for `tasks` tasks of these dimensions.  Either out pointer may be null. */
 int32_t rlrep_nc_forms(int32_t tasks, int32_t batch, int32_t feature_dim, int32_t hidden_dim, int32_t g2, int32_t* chunked, int32_t* splits);
+
+/* Unit-test hook of the loss heads every agent shares (csrc/elementwise.hip policy_fwd / policy_bwd / vae_mid / heads_vae / vae_mse /
+ * qhead_critic / qhead_actor kernels, csrc/per.hip qhead_critic_w_kernel, and the 16-row engine's epilogues that replace four of them:
+ * csrc/gemm16_tile.h EPI_FWD_POLICY, EPI_DX_POLICYBWD, EPI_FWD_MSE, EPI_DX_REPARAM; tests/test_heads_kernels.py): ONE launch of one head on
+ * caller buffers, with no agent, through the launchers the step programs use (rl_launch_policy_fwd ... rl_launch_qhead_actor,
+ * rl_launch_qhead_critic_w; rl_launch_gemm16 with rl_gemm16_number_tiles for the fused forms, whose task records are filled by the functions
+ * the program builder fills them with: engine_internal.h rl_task_*).  The records carry the fields of the launch records (csrc/kparams.h
+ * PolicyFwd, PolicyBwd, VaeMid, HeadsVae, VaeMse, QHeadCritic(W), QHeadActor) except block / tile counts (the builder's helpers: qhead_blocks,
+ * rl_vae_blocks, rl_heads_vae_tiles_c) and the group counter (always null: nothing is bumped).  alpha_state: the double the kernels read
+ * log(alpha) from.  form (may be null) receives what was launched: form[0] = 0 the stand-alone kernel / 1 a gemm16 epilogue; form[1] =
+ * HEADS_VAE: 1 the 16-byte loader copy, 0 the 4-byte one; QHEAD_CRITIC: 1 the weighted kernel; REPARAM_DX: pre.  Which gemm16 front end
+ * a fused launch took: the difference of rlrep_front_end_counts around the call.
+ *   fused = 1 (POLICY_FWD, POLICY_BWD, VAE_MSE; REPARAM_DX always): the head runs as the epilogue of its layer's product, and the record
+ *   carries the layer's operands in rlrep_hd_layer: forward X [B, K] (row stride ldx) . W [N, K]^T (ldw) + bias [N]; backward
+ *   G [B, K] (ldx) . W [K, N] (ldw), bias unused.  O / DH / dA, inputs of the stand-alone kernels, then are what the product leaves
+ *   (POLICY_FWD: O [B, 2A] dense is an output; VAE_MSE: GDH is the product's output; POLICY_BWD: dA is not stored and may be null).
+ *   POLICY_FWD fused: 1 or 2 policy tasks (t[0], t[1]: the hoisted "actor.head x2 + policy" stage) and one optional plain forward task
+ *   (extra.l.X non-null: Y [rows, N] = act(X W^T + bias), act as rlrep_gemm) in the same launch.
+ *   REPARAM_DX: G[b, c] += v[b, c], G[b, F + c] += v[b, c] EZ[b, c], v = A . W ([K, F], ldw).  pre = 0: A [B, K] (lda) is read; pre = 1: A =
+ *   (X [B, K1] Wh [K1, K]) relu'(M [B, K]) is recomputed by every tile (the fused short product) and stored to A; pre = 2: X = dmse(M Wh^T + bh;
+ *   s2, r) as well (the heads + mse launch riding along, K1 = S + 1 <= 32): X [B, K1] (ldx) and partial [2 ceil(B / 16)] are outputs.
+ * Refused with RLREP_ERR_ARG and a message starting "heads:", before any GPU call: an unknown kind, a null required pointer, a non-positive
+ * extent, a row stride below the row's width, fused outside {0, 1}, fused = 1 with 2A > 16 (forward) or A > 16 (backward) -- the kinds
+ * that have no fused form, and REPARAM_DX, which has no other, carry no such switch --, a clamp or a null eps on the fused forward, a task
+ * count outside 1..2, pre outside 0..2, K1 outside 1..32, an alpha_state off an 8-byte boundary, a
+ * float pointer off a 4-byte boundary, the 16-byte rows the mse phase of pre = 2 loads (K % 4, ldm % 4, ldwh % 4, M or Wh off a 16-byte
+ * boundary), a seed group's call in progress. */
+enum { RLREP_HD_POLICY_FWD = 0, RLREP_HD_POLICY_BWD = 1, RLREP_HD_VAE_MID = 2, RLREP_HD_HEADS_VAE = 3, RLREP_HD_VAE_MSE = 4,
+       RLREP_HD_REPARAM_DX = 5, RLREP_HD_QHEAD_CRITIC = 6, RLREP_HD_QHEAD_ACTOR = 7 };
+typedef struct rlrep_hd_layer { const float* X; int32_t ldx; const float* W; int32_t ldw; const float* bias; int32_t K; } rlrep_hd_layer;
+typedef struct rlrep_hd_policy_task { float* O; const float* eps; float* act; int32_t ld_act; float* logp; rlrep_hd_layer l; } rlrep_hd_policy_task;
+typedef union rlrep_heads_args {
+    struct { int32_t fused, ntasks, B, A, clamp; float lo, hi; int32_t* form; rlrep_hd_policy_task t[2];
+             struct { rlrep_hd_layer l; float* Y; int32_t ldy, rows, N, act; } extra; } policy_fwd;
+    struct { int32_t fused; const float* O; const float* eps; const float* act; int32_t ld_act; float* dA; int32_t ld_dA;
+             const double* alpha_state; float inv_batch; float* G; int32_t B, A; int32_t* form; rlrep_hd_layer l; } policy_bwd;
+    struct { const float* EH; const float* FH; const float* eps; float* Z; float* EZ; float* GEH; float* GFH; float* partial;
+             int32_t B, F; float scale; int32_t* form; } vae_mid;
+    struct { const float* Ae; const float* Af; int32_t lda; const float* We; const float* be; const float* Wf; const float* bf; const float* eps;
+             float* Z; float* EZ; float* GEH; float* GFH; float* partial; float* EH; float* FH; int32_t B, F, K; float scale; int32_t* form; } heads_vae;
+    struct { int32_t fused; const float* DH; const float* s2; int32_t ld_s2; const float* r; float* GDH; float* partial; int32_t B, S;
+             float scale_s, scale_r; int32_t* form; rlrep_hd_layer l; } vae_mse;
+    struct { int32_t pre; float* A; int32_t lda; const float* W; int32_t ldw; float* G; int32_t ldg; const float* EZ; int32_t ldez; int32_t B, F, K;
+             float* X; int32_t ldx; const float* Wh; int32_t ldwh; int32_t K1; const float* M; int32_t ldm;
+             const float* bh; const float* s2; int32_t ld_s2; const float* r; float scale_s, scale_r; float* partial; int32_t* form; } reparam_dx;
+    struct { const float* Et[2]; const float* Ec[2]; const float* wt[2]; const float* bt[2]; const float* wc[2]; const float* bc[2];
+             const float* logp; const float* R; const float* D; const double* alpha_state; float gamma, inv_batch;
+             float* dq; float* GE[2]; float* partial; int32_t B, H, train, ldE; int32_t weighted; const float* w; float* td; int32_t* form; } qhead_critic;
+    struct { const float* Ec[2]; const float* wc[2]; const float* bc[2]; const float* logp; const double* alpha_state; float inv_batch, target_entropy;
+             float* GE[2]; float* partial_loss; float* partial_c; int32_t B, H, ldE; int32_t* form; } qhead_actor;
+} rlrep_heads_args;
+int32_t rlrep_heads(int32_t kind, const rlrep_heads_args* args, void* stream);
+/* Host-only: every check of rlrep_heads on the record and the form it would launch (args' form), without any GPU call. */
+int32_t rlrep_heads_plan(int32_t kind, const rlrep_heads_args* args);
+/* Host-only: blocks (or tiles) of a head's launch and so the floats of its partial buffers: VAE_MID ceil(B F / 256); HEADS_VAE ceil(B / 16)
+ * ceil(F / 16); VAE_MSE (n = S): fused = 0: 2 ceil(B (S + 1) / 256), fused = 1: 2 ceil(B / 16) ceil((S + 1) / 16); REPARAM_DX (n = unused):
+ * 2 ceil(B / 16); QHEAD_CRITIC 4 qhead_blocks(B); QHEAD_ACTOR qhead_blocks(B) (each of its two); 0 for another kind or a non-positive extent. */
+int32_t rlrep_heads_partials(int32_t kind, int32_t fused, int32_t B, int32_t n);
 
 /* Chains (csrc/xchain.hip): consecutive row-local stages of a step program -- the forward and dX launches of the reference's
  * feature_step / critic_step / update_actor_and_alpha (agent/vlsac/vlsac_agent.py:126-237 and siblings) -- run as ONE persistent launch

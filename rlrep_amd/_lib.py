@@ -169,6 +169,64 @@ class NoisecriticArgs(C.Union):
     _fields_ = [('fwd', _NcFwd), ('dx', _NcDx), ('dw', _NcDw)]
 
 
+HD_KIND = {'policy_fwd': 0, 'policy_bwd': 1, 'vae_mid': 2, 'heads_vae': 3, 'vae_mse': 4, 'reparam_dx': 5, 'qhead_critic': 6, 'qhead_actor': 7}   # RLREP_HD_* of include/rlrep.h
+_FORM = [('form', C.POINTER(C.c_int32))]
+
+
+class HdLayer(C.Structure):
+    """rlrep_hd_layer (include/rlrep.h): the layer whose epilogue a fused head is"""
+    _fields_ = _rec('p:X i:ldx p:W i:ldw p:bias i:K')
+
+
+class HdPolicyTask(C.Structure):
+    """rlrep_hd_policy_task (include/rlrep.h)"""
+    _fields_ = _rec('p:O,eps,act i:ld_act p:logp') + [('l', HdLayer)]
+
+
+class _HdExtra(C.Structure):
+    _fields_ = [('l', HdLayer)] + _rec('p:Y i:ldy,rows,N,act')
+
+
+class _HdPolicyFwd(C.Structure):
+    _fields_ = _rec('i:fused,ntasks,B,A,clamp f:lo,hi') + _FORM + [('t', HdPolicyTask * 2), ('extra', _HdExtra)]
+
+
+class _HdPolicyBwd(C.Structure):
+    _fields_ = _rec('i:fused p:O,eps,act i:ld_act p:dA i:ld_dA p:alpha_state f:inv_batch p:G i:B,A') + _FORM + [('l', HdLayer)]
+
+
+class _HdVaeMid(C.Structure):
+    _fields_ = _rec('p:EH,FH,eps,Z,EZ,GEH,GFH,partial i:B,F f:scale') + _FORM
+
+
+class _HdHeadsVae(C.Structure):
+    _fields_ = _rec('p:Ae,Af i:lda p:We,be,Wf,bf,eps,Z,EZ,GEH,GFH,partial,EH,FH i:B,F,K f:scale') + _FORM
+
+
+class _HdVaeMse(C.Structure):
+    _fields_ = _rec('i:fused p:DH,s2 i:ld_s2 p:r,GDH,partial i:B,S f:scale_s,scale_r') + _FORM + [('l', HdLayer)]
+
+
+class _HdReparamDx(C.Structure):
+    _fields_ = _rec('i:pre p:A i:lda p:W i:ldw p:G i:ldg p:EZ i:ldez,B,F,K p:X i:ldx p:Wh i:ldwh,K1 p:M i:ldm p:bh,s2 i:ld_s2 p:r f:scale_s,scale_r p:partial') + _FORM
+
+
+class _HdQheadCritic(C.Structure):
+    _fields_ = ([(n, C.c_void_p * 2) for n in ('Et', 'Ec', 'wt', 'bt', 'wc', 'bc')] + _rec('p:logp,R,D,alpha_state f:gamma,inv_batch p:dq')
+                + [('GE', C.c_void_p * 2)] + _rec('p:partial i:B,H,train,ldE,weighted p:w,td') + _FORM)
+
+
+class _HdQheadActor(C.Structure):
+    _fields_ = ([(n, C.c_void_p * 2) for n in ('Ec', 'wc', 'bc')] + _rec('p:logp,alpha_state f:inv_batch,target_entropy')
+                + [('GE', C.c_void_p * 2)] + _rec('p:partial_loss,partial_c i:B,H,ldE') + _FORM)
+
+
+class HeadsArgs(C.Union):
+    """rlrep_heads_args (include/rlrep.h): the record of one rlrep_heads launch"""
+    _fields_ = [('policy_fwd', _HdPolicyFwd), ('policy_bwd', _HdPolicyBwd), ('vae_mid', _HdVaeMid), ('heads_vae', _HdHeadsVae), ('vae_mse', _HdVaeMse),
+                ('reparam_dx', _HdReparamDx), ('qhead_critic', _HdQheadCritic), ('qhead_actor', _HdQheadActor)]
+
+
 def declared_symbols():
     """Every function name include/rlrep.h declares (used by the CPU test that checks the exports)."""
     src = open(HEADER_PATH).read()
@@ -340,6 +398,9 @@ def _load():
         'rlrep_noisecritic': (i32, [i32, P(NoisecriticArgs), vp]),
         'rlrep_nc_w3_bytes': (i64, [i32, i32]),
         'rlrep_nc_forms': (i32, [i32] * 5 + [P(i32)] * 2),
+        'rlrep_heads': (i32, [i32, P(HeadsArgs), vp]),
+        'rlrep_heads_partials': (i32, [i32] * 4),
+        'rlrep_heads_plan': (i32, [i32, P(HeadsArgs)]),
         'rlrep_chain_status': (i32, [vp, P(C.c_uint32), vp]),
         'rlrep_build_flags': (i32, []),
         'rlrep_debug_stamp': (i32, [vp, i32, i32, vp]),

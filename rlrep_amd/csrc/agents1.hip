@@ -38,7 +38,7 @@ void policy_fwd_stage(Program& p, rlrep_agent* ag, const ActorBufs& ab, float* a
 bool policy_fusable(const rlrep_agent* ag) { return 2 * ag->d.action_dim <= 16 && !rl_off("fuse_policy"); }
 GemmTask policy_head_task(rlrep_agent* ag, const ActorBufs& ab, float* act, int ld_act, int dyn_flag) {
     GemmTask head = actor_l(ag, 2, nullptr, 0, ab);
-    head.epi = EPI_FWD_POLICY; head.n0 = ag->d.action_dim; head.y0 = act; head.ldx0 = ld_act; head.y1 = ab.logp; head.flags |= dyn_flag;
+    rl_task_policy_head(head, ag->d.action_dim, act, ld_act, ab.logp, dyn_flag);
     return head;
 }
 
@@ -59,8 +59,7 @@ void actor_backward(Builder& b, Program& p, rlrep_agent* ag, const ActorBufs& ab
                            const float* act, int ld_act, GemmTask action_dx) {
     const int S = ag->d.state_dim, A = ag->d.action_dim, Ha = ag->d.actor_hidden_dim, B = ag->B;
     if (A <= 16 && !rl_off("fuse_policy")) {
-        action_dx.epi = EPI_DX_POLICYBWD; action_dx.n0 = A; action_dx.x0 = ab.AO; action_dx.x1 = act; action_dx.ldx1 = ld_act;
-        action_dx.y0 = ab.Ghead; action_dx.dptr = ag->a.alpha_state_dev; action_dx.s0 = ag->inv_batch(); action_dx.flags |= FLAG_DYN_EPS;
+        rl_task_policy_bwd(action_dx, A, ab.AO, act, ld_act, ab.Ghead, ag->a.alpha_state_dev, ag->inv_batch(), FLAG_DYN_EPS);
         b.dx_stage(p, {action_dx}, "dx(action) -> dL/d[mu|rho]");
     } else {
         b.dx_stage(p, {action_dx}, "dx(action)");
@@ -537,7 +536,7 @@ void build_vlsac(Builder& b, rlrep_agent* ag) {
             hv.Ae = ge.H2; hv.Af = gf.H2; hv.lda = Hv; hv.We = Pw("encoder.mean_linear.weight"); hv.be = Pw("encoder.mean_linear.bias");
             hv.Wf = Pw("f.mean_linear.weight"); hv.bf = Pw("f.mean_linear.bias");
             hv.Z = Z; hv.EZ = EZ; hv.GEH = GEH; hv.GFH = GFH; hv.partial = part_kl; hv.EH = nullptr; hv.FH = nullptr;       // (nothing downstream of vae_mid reads the heads themselves)
-            hv.B = B; hv.F = F; hv.K = Hv; hv.tiles_c = (F + 15) / 16; hv.scale = ag->inv_batch() / (float)F; hv.step = ag->adam_step + 0;
+            hv.B = B; hv.F = F; hv.K = Hv; hv.tiles_c = rl_heads_vae_tiles_c(F); hv.scale = ag->inv_batch() / (float)F; hv.step = ag->adam_step + 0;
             b.heads_vae_stage(p, hv, "enc.heads f.heads + vae_mid");
         }
         if (early)                  // the two policy heads of the early variant ride with the next forward launch instead of the heads launch
@@ -550,20 +549,17 @@ void build_vlsac(Builder& b, rlrep_agent* ag) {
             // decoder heads with the 0.5*mse loss fused into the epilogue: the launch writes d loss / d[s_hat | r_hat]
             // (GDH) directly and per-tile partial sums of the squared errors (vlsac_agent.py:137-140)
             GemmTask t = Builder::fwd(D1, Hv, B, Hv, Pw("decoder.state_linear.weight"), Hv, Pw("decoder.state_linear.bias"), S + 1, GDH, S + 1, ACT_NONE);
-            t.epi = EPI_FWD_MSE; t.n0 = S; t.x0 = s0.XE ? s0.XE + SA : nullptr; t.ldx0 = KE; t.x1 = s0.R;
-            t.s0 = ag->inv_batch() / (float)S; t.s1 = ag->inv_batch(); t.y0 = part_mse;
+            rl_task_mse(t, S, s0.XE ? s0.XE + SA : nullptr, KE, s0.R, ag->inv_batch() / (float)S, ag->inv_batch(), part_mse);
             b.fwd_stage(p, {t}, "dec.heads + mse");
         }
         {
             GemmTask t = Builder::dx(GD1, Hv, B, Hv, Pw("decoder.l1.weight"), F, GEH, 2 * F, F, ACT_NONE, nullptr, 0);
-            t.epi = EPI_DX_REPARAM; t.aux3 = EZ; t.ldaux3 = F; t.F = F;
+            rl_task_reparam(t, EZ, F, F);
             // the K = 18 product dL/d(dec.l1 output) = d[s_hat|r_hat] W_heads rides in the dec.l1 dX launch (one launch less per feature step)
             if (fold_mse) {
                 // ... and so does the heads' forward + mse (FLAG_PRE_MSE): every tile of the launch computes d[s_hat|r_hat] of its 16 rows itself
-                t.flags |= FLAG_PRE | FLAG_PRE_MSE;
-                t.x0 = GDH; t.ldx0 = S + 1; t.x1 = Pw("decoder.state_linear.weight"); t.ldx1 = Hv; t.n0 = S + 1; t.x2 = D1; t.ldaux2 = Hv; t.y0 = GD1; t.ldout2 = Hv;
-                t.bias = Pw("decoder.state_linear.bias"); t.tgs = s0.XE ? s0.XE + SA : nullptr; t.ldtgs = KE; t.tgr = s0.R; t.pad_mse = S;
-                t.s0 = ag->inv_batch() / (float)S; t.s1 = ag->inv_batch(); t.mse_part = part_mse;
+                rl_task_pre_mse(t, GDH, S + 1, Pw("decoder.state_linear.weight"), Hv, Pw("decoder.state_linear.bias"), S, D1, Hv, GD1, Hv,
+                                s0.XE ? s0.XE + SA : nullptr, KE, s0.R, ag->inv_batch() / (float)S, ag->inv_batch(), part_mse);
                 b.gemm_small(p, LD_ROW, LD_COL, {t}, "dec.heads + mse | dec.heads dx | dec.l1 dx -> (dmean, dlog_std)");
             } else
             b.dx_stage12(p, Builder::dx(GDH, S + 1, B, S + 1, Pw("decoder.state_linear.weight"), Hv, GD1, Hv, Hv, ACT_RELU, D1, Hv), t,

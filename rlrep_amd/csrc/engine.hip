@@ -1782,6 +1782,250 @@ int32_t rlrep_noisecritic(int32_t kernel, const rlrep_noisecritic_args* a, void*
 }
 #undef NCR_REFUSE
 
+// Unit-test hook of the loss heads (elementwise.hip / per.hip kernels and the gemm16 epilogues that replace four of them): one launch on caller
+// buffers through the launchers the step programs use.  Block and tile counts come from the builder's helpers (qhead_blocks, rl_vae_blocks,
+// rl_heads_vae_tiles_c, rl_gemm16_pick_nf / rl_gemm16_number_tiles), the fused task records from the functions the builder fills them with
+// (engine_internal.h rl_task_*).  Every shape is checked HERE, before any GPU call: nothing a test hands in can make a kernel index outside
+// the extents its record states.
+int32_t rlrep_heads_partials(int32_t kind, int32_t fused, int32_t B, int32_t n) {
+    if (B <= 0) return 0;
+    switch (kind) {
+    case RLREP_HD_VAE_MID: return n > 0 ? rl_vae_blocks(B, n) : 0;
+    case RLREP_HD_HEADS_VAE: return n > 0 ? ((B + 15) / 16) * rl_heads_vae_tiles_c(n) : 0;
+    case RLREP_HD_VAE_MSE: return n > 0 ? 2 * (fused ? ((B + 15) / 16) * ((n + 1 + 15) / 16) : rl_vae_blocks(B, n + 1)) : 0;
+    case RLREP_HD_REPARAM_DX: return 2 * ((B + 15) / 16);
+    case RLREP_HD_QHEAD_CRITIC: return 4 * qhead_blocks(B);
+    case RLREP_HD_QHEAD_ACTOR: return qhead_blocks(B);
+    default: return 0;
+    }
+}
+#define HD_REFUSE(...) { rl_set_error("heads: " __VA_ARGS__); return RLREP_ERR_ARG; }
+static int32_t heads_impl(int32_t kind, const rlrep_heads_args* a, void* stream, bool launch);
+int32_t rlrep_heads(int32_t kind, const rlrep_heads_args* a, void* stream) { return heads_impl(kind, a, stream, true); }
+int32_t rlrep_heads_plan(int32_t kind, const rlrep_heads_args* a) { return heads_impl(kind, a, nullptr, false); }
+static int32_t heads_impl(int32_t kind, const rlrep_heads_args* a, void* stream, bool launch) {
+    rl_switches_read();
+    if (!a) HD_REFUSE("null argument record")
+    if (kind < RLREP_HD_POLICY_FWD || kind > RLREP_HD_QHEAD_ACTOR) HD_REFUSE("unknown kind %d", kind)
+    if (rl_grp_active()) HD_REFUSE("a seed group's call is in progress (the group forms are not reachable here)")
+    const hipStream_t st = (hipStream_t)stream;
+    auto al = [](const void* p, uintptr_t n) { return (((uintptr_t)p) & (n - 1)) == 0; };
+    auto al4 = [&](std::initializer_list<const void*> ps) { for (const void* p : ps) if (!al(p, 4)) return false; return true; };
+    // the layer of a fused form: forward X [rows, K] . W [N, K]^T + bias [N]; backward G [rows, K] . W [K, N]
+    auto layer_bad = [&](const rlrep_hd_layer& l, bool fwd, int N) -> const char* {
+        if (!l.X || !l.W || (fwd && !l.bias)) return "null X, W or bias of the layer";
+        if (l.K <= 0) return "non-positive inner length of the layer";
+        if (l.ldx < l.K || l.ldw < (fwd ? l.K : N)) return "row stride of the layer's X or W below the row's width";
+        if (!al4({l.X, l.W, l.bias})) return "a pointer of the layer off a 4-byte boundary";
+        return nullptr;
+    };
+    const char* what = "";
+    PolicyFwd pf; PolicyBwd pb; VaeMid vm; HeadsVae hv; VaeMse ms; QHeadCriticW qw; QHeadActor qa;
+    GemmBatch gb; memset(&gb, 0, sizeof(gb));
+    int la = LD_ROW, lb = LD_ROW;
+    bool gemm = false;
+    int32_t* form = nullptr; int form1 = 0;
+    switch (kind) {
+    case RLREP_HD_POLICY_FWD: {
+        const auto& s = a->policy_fwd;
+        what = "policy forward"; form = s.form;
+        if (s.fused != 0 && s.fused != 1) HD_REFUSE("%s: fused %d not 0 or 1", what, s.fused)
+        if (s.B <= 0 || s.A <= 0) HD_REFUSE("%s: B %d, A %d: non-positive extent", what, s.B, s.A)
+        const int nt = s.fused ? s.ntasks : 1;
+        if (nt < 1 || nt > 2) HD_REFUSE("%s: ntasks %d outside 1..2", what, s.ntasks)
+        if (s.fused && 2 * s.A > 16) HD_REFUSE("%s: fused with 2 A = %d > 16 (the [mu | rho] row must fit one 16-column tile)", what, 2 * s.A)
+        if (s.fused && s.clamp) HD_REFUSE("%s: the fused form has no clamp", what)
+        for (int q = 0; q < nt; ++q) {
+            const rlrep_hd_policy_task& u = s.t[q];
+            if (!u.O || !u.act) HD_REFUSE("%s: task %d: null O or act", what, q)
+            if (u.ld_act < s.A) HD_REFUSE("%s: task %d: ld_act %d below A %d", what, q, u.ld_act, s.A)
+            if (!al4({u.O, u.eps, u.act, u.logp})) HD_REFUSE("%s: task %d: a pointer off a 4-byte boundary", what, q)
+            if (s.fused) {
+                if (!u.eps) HD_REFUSE("%s: task %d: the fused form needs eps", what, q)
+                if (const char* bad = layer_bad(u.l, true, 2 * s.A)) HD_REFUSE("%s: task %d: %s", what, q, bad)
+            }
+        }
+        if (!s.fused) {
+            memset(&pf, 0, sizeof(pf));
+            pf.O = s.t[0].O; pf.eps = s.t[0].eps; pf.B = s.B; pf.A = s.A; pf.act = s.t[0].act; pf.ld_act = s.t[0].ld_act; pf.logp = s.t[0].logp;
+            pf.clamp = s.clamp ? 1 : 0; pf.lo = s.lo; pf.hi = s.hi;
+            break;
+        }
+        gemm = true;
+        for (int q = 0; q < nt; ++q) {
+            const rlrep_hd_policy_task& u = s.t[q];
+            GemmTask head = Builder::fwd(u.l.X, u.l.ldx, s.B, u.l.K, u.l.W, u.l.ldw, u.l.bias, 2 * s.A, u.O, 2 * s.A, ACT_NONE);
+            rl_task_policy_head(head, s.A, u.act, u.ld_act, u.logp, 0);
+            head.x2 = u.eps;
+            gb.t[gb.ntasks++] = head;
+        }
+        if (s.extra.l.X) {
+            const auto& e = s.extra;
+            if (e.rows <= 0 || e.N <= 0 || !e.Y || e.ldy < e.N) HD_REFUSE("%s: extra task: rows %d, N %d, ldy %d: non-positive extent, null Y or row stride below the width", what, e.rows, e.N, e.ldy)
+            if (e.act < ACT_NONE || e.act > ACT_TANH || e.act == ACT_SIN) HD_REFUSE("%s: extra task: activation %d not in {0, 1, 2, 4}", what, e.act)
+            if (const char* bad = layer_bad(e.l, true, e.N)) HD_REFUSE("%s: extra task: %s", what, bad)
+            if (!al4({e.Y})) HD_REFUSE("%s: extra task: Y off a 4-byte boundary", what)
+            gb.t[gb.ntasks++] = Builder::fwd(e.l.X, e.l.ldx, e.rows, e.l.K, e.l.W, e.l.ldw, e.l.bias, e.N, e.Y, e.ldy, e.act);
+        }
+    } break;
+    case RLREP_HD_POLICY_BWD: {
+        const auto& s = a->policy_bwd;
+        what = "policy backward"; form = s.form;
+        if (s.fused != 0 && s.fused != 1) HD_REFUSE("%s: fused %d not 0 or 1", what, s.fused)
+        if (s.B <= 0 || s.A <= 0) HD_REFUSE("%s: B %d, A %d: non-positive extent", what, s.B, s.A)
+        if (!s.O || !s.eps || !s.act || !s.alpha_state || !s.G) HD_REFUSE("%s: null O, eps, act, alpha_state or G", what)
+        if (s.ld_act < s.A) HD_REFUSE("%s: ld_act %d below A %d", what, s.ld_act, s.A)
+        if (!al(s.alpha_state, 8)) HD_REFUSE("%s: alpha_state off an 8-byte boundary", what)
+        if (!al4({s.O, s.eps, s.act, s.dA, s.G})) HD_REFUSE("%s: a pointer off a 4-byte boundary", what)
+        if (!s.fused) {
+            if (!s.dA || s.ld_dA < s.A) HD_REFUSE("%s: null dA or ld_dA %d below A %d", what, s.ld_dA, s.A)
+            memset(&pb, 0, sizeof(pb));
+            pb.O = s.O; pb.eps = s.eps; pb.act = s.act; pb.ld_act = s.ld_act; pb.dA = s.dA; pb.ld_dA = s.ld_dA;
+            pb.alpha_state = s.alpha_state; pb.inv_batch = s.inv_batch; pb.G = s.G; pb.B = s.B; pb.A = s.A;
+            break;
+        }
+        if (s.A > 16) HD_REFUSE("%s: fused with A = %d > 16", what, s.A)
+        if (const char* bad = layer_bad(s.l, false, s.A)) HD_REFUSE("%s: %s", what, bad)
+        gemm = true; lb = LD_COL;
+        GemmTask dxa = Builder::dx(s.l.X, s.l.ldx, s.B, s.l.K, s.l.W, s.l.ldw, s.dA, s.A, s.A, ACT_NONE, nullptr, 0);
+        rl_task_policy_bwd(dxa, s.A, s.O, s.act, s.ld_act, s.G, s.alpha_state, s.inv_batch, 0);
+        dxa.x2 = s.eps;
+        gb.t[gb.ntasks++] = dxa;
+    } break;
+    case RLREP_HD_VAE_MID: {
+        const auto& s = a->vae_mid;
+        what = "vae_mid"; form = s.form;
+        if (s.B <= 0 || s.F <= 0) HD_REFUSE("%s: B %d, F %d: non-positive extent", what, s.B, s.F)
+        if (!s.EH || !s.FH || !s.eps || !s.Z || !s.EZ || !s.GEH || !s.GFH || !s.partial) HD_REFUSE("%s: null pointer", what)
+        if (!al4({s.EH, s.FH, s.eps, s.Z, s.EZ, s.GEH, s.GFH, s.partial})) HD_REFUSE("%s: a pointer off a 4-byte boundary", what)
+        memset(&vm, 0, sizeof(vm));
+        vm.EH = s.EH; vm.FH = s.FH; vm.eps = s.eps; vm.Z = s.Z; vm.EZ = s.EZ; vm.GEH = s.GEH; vm.GFH = s.GFH; vm.partial = s.partial;
+        vm.B = s.B; vm.F = s.F; vm.nblk = rl_vae_blocks(s.B, s.F); vm.scale = s.scale;
+    } break;
+    case RLREP_HD_HEADS_VAE: {
+        const auto& s = a->heads_vae;
+        what = "heads_vae"; form = s.form;
+        if (s.B <= 0 || s.F <= 0 || s.K <= 0) HD_REFUSE("%s: B %d, F %d, K %d: non-positive extent", what, s.B, s.F, s.K)
+        if (!s.Ae || !s.Af || !s.We || !s.be || !s.Wf || !s.bf || !s.eps || !s.Z || !s.EZ || !s.GEH || !s.GFH || !s.partial) HD_REFUSE("%s: null pointer", what)
+        if (s.lda < s.K) HD_REFUSE("%s: lda %d below K %d", what, s.lda, s.K)
+        if (!al4({s.Ae, s.Af, s.We, s.be, s.Wf, s.bf, s.eps, s.Z, s.EZ, s.GEH, s.GFH, s.partial, s.EH, s.FH})) HD_REFUSE("%s: a pointer off a 4-byte boundary", what)
+        memset(&hv, 0, sizeof(hv));
+        hv.Ae = s.Ae; hv.Af = s.Af; hv.lda = s.lda; hv.We = s.We; hv.be = s.be; hv.Wf = s.Wf; hv.bf = s.bf; hv.eps = s.eps;
+        hv.Z = s.Z; hv.EZ = s.EZ; hv.GEH = s.GEH; hv.GFH = s.GFH; hv.partial = s.partial; hv.EH = s.EH; hv.FH = s.FH;
+        hv.B = s.B; hv.F = s.F; hv.K = s.K; hv.tiles_c = rl_heads_vae_tiles_c(s.F); hv.scale = s.scale;
+        // (heads_vae_tile's own rule for its 16-byte loader copy)
+        form1 = (!(s.K & 3) && !(s.lda & 3) && al(s.Ae, 16) && al(s.Af, 16) && al(s.We, 16) && al(s.Wf, 16)) ? 1 : 0;
+    } break;
+    case RLREP_HD_VAE_MSE: {
+        const auto& s = a->vae_mse;
+        what = "vae_mse"; form = s.form;
+        if (s.fused != 0 && s.fused != 1) HD_REFUSE("%s: fused %d not 0 or 1", what, s.fused)
+        if (s.B <= 0 || s.S <= 0) HD_REFUSE("%s: B %d, S %d: non-positive extent", what, s.B, s.S)
+        if (!s.s2 || !s.r || !s.GDH || !s.partial) HD_REFUSE("%s: null s2, r, GDH or partial", what)
+        if (s.ld_s2 < s.S) HD_REFUSE("%s: ld_s2 %d below S %d", what, s.ld_s2, s.S)
+        if (!al4({s.DH, s.s2, s.r, s.GDH, s.partial})) HD_REFUSE("%s: a pointer off a 4-byte boundary", what)
+        if (!s.fused) {
+            if (!s.DH) HD_REFUSE("%s: null DH", what)
+            memset(&ms, 0, sizeof(ms));
+            ms.DH = s.DH; ms.s2 = s.s2; ms.ld_s2 = s.ld_s2; ms.r = s.r; ms.GDH = s.GDH; ms.partial = s.partial; ms.B = s.B; ms.S = s.S;
+            ms.nblk = rl_vae_blocks(s.B, s.S + 1); ms.scale_s = s.scale_s; ms.scale_r = s.scale_r;
+            break;
+        }
+        if (const char* bad = layer_bad(s.l, true, s.S + 1)) HD_REFUSE("%s: %s", what, bad)
+        gemm = true;
+        GemmTask t = Builder::fwd(s.l.X, s.l.ldx, s.B, s.l.K, s.l.W, s.l.ldw, s.l.bias, s.S + 1, s.GDH, s.S + 1, ACT_NONE);
+        rl_task_mse(t, s.S, s.s2, s.ld_s2, s.r, s.scale_s, s.scale_r, s.partial);
+        gb.t[gb.ntasks++] = t;
+    } break;
+    case RLREP_HD_REPARAM_DX: {
+        const auto& s = a->reparam_dx;
+        what = "reparameterisation dX"; form = s.form; form1 = s.pre;
+        if (s.pre < 0 || s.pre > 2) HD_REFUSE("%s: pre %d outside 0..2", what, s.pre)
+        if (s.B <= 0 || s.F <= 0 || s.K <= 0) HD_REFUSE("%s: B %d, F %d, K %d: non-positive extent", what, s.B, s.F, s.K)
+        if (!s.A || !s.W || !s.G || !s.EZ) HD_REFUSE("%s: null A, W, G or EZ", what)
+        if (s.lda < s.K || s.ldw < s.F || s.ldg < 2 * s.F || s.ldez < s.F) HD_REFUSE("%s: lda %d / ldw %d / ldg %d / ldez %d below the row's width (K %d, F %d, 2 F, F)", what, s.lda, s.ldw, s.ldg, s.ldez, s.K, s.F)
+        if (!al4({s.A, s.W, s.G, s.EZ, s.X, s.Wh, s.M, s.bh, s.s2, s.r, s.partial})) HD_REFUSE("%s: a pointer off a 4-byte boundary", what)
+        gemm = true; lb = LD_COL;
+        GemmTask t = Builder::dx(s.A, s.lda, s.B, s.K, s.W, s.ldw, s.G, s.ldg, s.F, ACT_NONE, nullptr, 0);
+        rl_task_reparam(t, s.EZ, s.ldez, s.F);
+        if (s.pre) {
+            if (!s.X || !s.Wh || !s.M) HD_REFUSE("%s: null X, Wh or M of the fused short product", what)
+            if (s.K1 <= 0 || s.K1 > 32) HD_REFUSE("%s: K1 %d outside 1..32", what, s.K1)
+            if (s.ldx < s.K1 || s.ldwh < s.K || s.ldm < s.K) HD_REFUSE("%s: ldx %d / ldwh %d / ldm %d below the row's width (K1 %d, K %d, K)", what, s.ldx, s.ldwh, s.ldm, s.K1, s.K)
+        }
+        if (s.pre == 1) {
+            // (the dec.heads dX task whose output the tiles recompute: agents1.hip build_vlsac, Builder::dx_stage12)
+            const GemmTask d1 = Builder::dx(s.X, s.ldx, s.B, s.K1, s.Wh, s.ldwh, s.A, s.lda, s.K, ACT_RELU, s.M, s.ldm);
+            rl_task_pre_dx(t, d1);
+        } else if (s.pre == 2) {
+            if (!s.bh || !s.s2 || !s.r || !s.partial) HD_REFUSE("%s: null bh, s2, r or partial of the mse phase", what)
+            if (s.K1 < 2 || s.ld_s2 < s.K1 - 1) HD_REFUSE("%s: K1 %d below 2 (S + 1) or ld_s2 %d below S", what, s.K1, s.ld_s2)
+            if ((s.K & 3) || (s.ldm & 3) || (s.ldwh & 3) || !al(s.M, 16) || !al(s.Wh, 16))
+                HD_REFUSE("%s: the mse phase loads 16 bytes at a time: K %d, ldm %d, ldwh %d must be multiples of 4, M and Wh on 16-byte boundaries", what, s.K, s.ldm, s.ldwh)
+            rl_task_pre_mse(t, s.X, s.ldx, s.Wh, s.ldwh, s.bh, s.K1 - 1, s.M, s.ldm, s.A, s.lda, s.s2, s.ld_s2, s.r, s.scale_s, s.scale_r, s.partial);
+        }
+        gb.t[gb.ntasks++] = t;
+    } break;
+    case RLREP_HD_QHEAD_CRITIC: {
+        const auto& s = a->qhead_critic;
+        what = "qhead critic"; form = s.form; form1 = s.weighted ? 1 : 0;
+        if (s.B <= 0 || s.H <= 0) HD_REFUSE("%s: B %d, H %d: non-positive extent", what, s.B, s.H)
+        for (int h = 0; h < 2; ++h) {
+            if (!s.Et[h] || !s.Ec[h] || !s.wt[h] || !s.bt[h] || !s.wc[h] || !s.bc[h]) HD_REFUSE("%s: head %d: null Et, Ec, wt, bt, wc or bc", what, h)
+            if (s.train && !s.GE[h]) HD_REFUSE("%s: head %d: null GE", what, h)
+            if (!al4({s.Et[h], s.Ec[h], s.wt[h], s.bt[h], s.wc[h], s.bc[h], s.GE[h]})) HD_REFUSE("%s: head %d: a pointer off a 4-byte boundary", what, h)
+        }
+        if (!s.logp || !s.R || !s.D || !s.alpha_state || !s.partial || (s.train && !s.dq)) HD_REFUSE("%s: null logp, R, D, alpha_state, partial or dq", what)
+        if (s.ldE != 0 && s.ldE < s.H) HD_REFUSE("%s: ldE %d below H %d (0: dense)", what, s.ldE, s.H)
+        if (s.weighted && (!s.w || !s.td)) HD_REFUSE("%s: the weighted form needs w and td", what)
+        if (!al(s.alpha_state, 8)) HD_REFUSE("%s: alpha_state off an 8-byte boundary", what)
+        if (!al4({s.logp, s.R, s.D, s.partial, s.dq, s.w, s.td})) HD_REFUSE("%s: a pointer off a 4-byte boundary", what)
+        memset(&qw, 0, sizeof(qw));
+        QHeadCritic& q = qw.q;
+        for (int h = 0; h < 2; ++h) { q.Et[h] = s.Et[h]; q.Ec[h] = s.Ec[h]; q.wt[h] = s.wt[h]; q.bt[h] = s.bt[h]; q.wc[h] = s.wc[h]; q.bc[h] = s.bc[h]; q.GE[h] = s.GE[h]; }
+        q.logp = s.logp; q.R = s.R; q.D = s.D; q.alpha_state = s.alpha_state; q.gamma = s.gamma; q.inv_batch = s.inv_batch; q.dq = s.dq; q.partial = s.partial;
+        q.B = s.B; q.H = s.H; q.nblk = qhead_blocks(s.B); q.train = s.train ? 1 : 0; q.ldE = s.ldE;
+        qw.w = s.w; qw.td = s.td;
+    } break;
+    case RLREP_HD_QHEAD_ACTOR: {
+        const auto& s = a->qhead_actor;
+        what = "qhead actor"; form = s.form;
+        if (s.B <= 0 || s.H <= 0) HD_REFUSE("%s: B %d, H %d: non-positive extent", what, s.B, s.H)
+        for (int h = 0; h < 2; ++h) {
+            if (!s.Ec[h] || !s.wc[h] || !s.bc[h] || !s.GE[h]) HD_REFUSE("%s: head %d: null Ec, wc, bc or GE", what, h)
+            if (!al4({s.Ec[h], s.wc[h], s.bc[h], s.GE[h]})) HD_REFUSE("%s: head %d: a pointer off a 4-byte boundary", what, h)
+        }
+        if (!s.logp || !s.alpha_state || !s.partial_loss || !s.partial_c) HD_REFUSE("%s: null logp, alpha_state, partial_loss or partial_c", what)
+        if (s.ldE != 0 && s.ldE < s.H) HD_REFUSE("%s: ldE %d below H %d (0: dense)", what, s.ldE, s.H)
+        if (!al(s.alpha_state, 8)) HD_REFUSE("%s: alpha_state off an 8-byte boundary", what)
+        if (!al4({s.logp, s.partial_loss, s.partial_c})) HD_REFUSE("%s: a pointer off a 4-byte boundary", what)
+        memset(&qa, 0, sizeof(qa));
+        for (int h = 0; h < 2; ++h) { qa.Ec[h] = s.Ec[h]; qa.wc[h] = s.wc[h]; qa.bc[h] = s.bc[h]; qa.GE[h] = s.GE[h]; }
+        qa.logp = s.logp; qa.alpha_state = s.alpha_state; qa.inv_batch = s.inv_batch; qa.target_entropy = s.target_entropy;
+        qa.partial_loss = s.partial_loss; qa.partial_c = s.partial_c; qa.B = s.B; qa.H = s.H; qa.nblk = qhead_blocks(s.B); qa.ldE = s.ldE;
+    } break;
+    }
+    if (form) { form[0] = gemm ? 1 : 0; form[1] = form1; }
+    if (!launch) return 0;
+    int rc = 0;
+    if (gemm) {
+        const int nf = rl_gemm16_pick_nf(gb.t, gb.ntasks);
+        const int total = rl_gemm16_number_tiles(gb.t, gb.ntasks, nf);
+        rc = rl_launch_gemm16(la, lb, nf, &gb, total, st);
+    } else switch (kind) {
+        case RLREP_HD_POLICY_FWD: rc = rl_launch_policy_fwd(&pf, st); break;
+        case RLREP_HD_POLICY_BWD: rc = rl_launch_policy_bwd(&pb, st); break;
+        case RLREP_HD_VAE_MID: rc = rl_launch_vae_mid(&vm, st); break;
+        case RLREP_HD_HEADS_VAE: rc = rl_launch_heads_vae(&hv, st); break;
+        case RLREP_HD_VAE_MSE: rc = rl_launch_vae_mse(&ms, st); break;
+        case RLREP_HD_QHEAD_CRITIC: rc = a->qhead_critic.weighted ? rl_launch_qhead_critic_w(&qw, st) : rl_launch_qhead_critic(&qw.q, st); break;
+        case RLREP_HD_QHEAD_ACTOR: rc = rl_launch_qhead_actor(&qa, st); break;
+    }
+    if (rc != 0) { rl_set_error("heads: %s: launch failed (%d)", what, rc); return rc < 0 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    return 0;
+}
+#undef HD_REFUSE
+
 int32_t rlrep_chain_status(rlrep_agent* ag, uint32_t* status, void* stream) {
     GROUP_REFUSE("chain_status")
     if (!ag || !ag->xc_err) { rl_set_error("chain_status: bad argument"); return RLREP_ERR_ARG; }

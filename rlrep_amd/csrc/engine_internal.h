@@ -195,6 +195,60 @@ static inline int rl_nc_dw_number_tiles(NcDwBatch* nb) {
     return base_tile;
 }
 
+// Column fragments per workgroup of a launch of the 16-row tile engine: the widest tile that still leaves >= ~1.5 workgroups per CU; the
+// epilogues that need a whole row / per-tile partials in one fragment, and the fused short product, force NF = 1.
+static inline int rl_gemm16_pick_nf(const GemmTask* tasks, int ntasks) {
+    int nf = 1;
+    bool force1 = false;
+    for (int q = 0; q < ntasks; ++q) force1 = force1 || tasks[q].epi == EPI_FWD_POLICY || tasks[q].epi == EPI_FWD_MSE || tasks[q].epi == EPI_DX_REPARAM;
+    auto count = [&](int f) { long long n = 0; for (int q = 0; q < ntasks; ++q) n += (long long)((tasks[q].R + 15) / 16) * ((tasks[q].Cn + 16 * f - 1) / (16 * f)); return n; };
+    if (!force1) { if (count(2) >= 384) nf = 2; if (count(4) >= 384) nf = 4; }
+    if (ntasks > 0 && (tasks[0].flags & FLAG_PRE)) nf = 1;
+    return nf;
+}
+
+// The loss heads that run as epilogues of their layer's product (gemm16_tile.h EPI_FWD_POLICY / EPI_DX_POLICYBWD / EPI_FWD_MSE /
+// EPI_DX_REPARAM): what turns the layer's plain task (Builder::fwd / Builder::dx) into the fused one, as functions of explicit pointers.
+// The program builders (agents1.hip) and the unit-test hook (rlrep_heads) fill their records through these.
+// ... the actor head [B, 2A] = [mu | rho], 2A <= 16: act [B, A] (row stride ld_act) and logp [B] leave the epilogue; the noise is x2 (dyn_flag:
+// which per-call pointer the launch patches in; 0: the caller sets x2 itself)
+static inline void rl_task_policy_head(GemmTask& head, int A, float* act, int ld_act, float* logp, int dyn_flag) {
+    head.epi = EPI_FWD_POLICY; head.n0 = A; head.y0 = act; head.ldx0 = ld_act; head.y1 = logp; head.flags |= dyn_flag;
+}
+// ... dL/da [B, A] (A <= 16) -> dL/d[mu | rho] = Ghead [B, 2A]; AO = the head's output, act = tanh(x)
+static inline void rl_task_policy_bwd(GemmTask& action_dx, int A, const float* AO, const float* act, int ld_act, float* Ghead,
+                                      const double* alpha_state, float inv_batch, int dyn_flag) {
+    action_dx.epi = EPI_DX_POLICYBWD; action_dx.n0 = A; action_dx.x0 = AO; action_dx.x1 = act; action_dx.ldx1 = ld_act;
+    action_dx.y0 = Ghead; action_dx.dptr = alpha_state; action_dx.s0 = inv_batch; action_dx.flags |= dyn_flag;
+}
+// ... the vlsac decoder heads [B, S + 1] with the 0.5 mse losses: the task's output becomes d loss / d[s_hat | r_hat], part gets a pair of
+// squared-error sums per tile
+static inline void rl_task_mse(GemmTask& t, int S, const float* s2, int ld_s2, const float* r, float scale_s, float scale_r, float* part) {
+    t.epi = EPI_FWD_MSE; t.n0 = S; t.x0 = s2; t.ldx0 = ld_s2; t.x1 = r; t.s0 = scale_s; t.s1 = scale_r; t.y0 = part;
+}
+// ... dL/dz accumulated into (dmean | dlog_std) [B, 2F]: EZ = eps exp(log_std) clamp-mask
+static inline void rl_task_reparam(GemmTask& t, const float* EZ, int ldez, int F) {
+    t.epi = EPI_DX_REPARAM; t.aux3 = EZ; t.ldaux3 = ldez; t.F = F;
+}
+// The fused short product of the dX form (FLAG_PRE): d2's operand A is d1's output, recomputed by every tile of d2 and stored where d1 stored it
+static inline void rl_task_pre_dx(GemmTask& t, const GemmTask& d1) {
+    t.flags |= FLAG_PRE | (d1.act == ACT_ELU ? FLAG_PRE_ELU : 0);
+    t.x0 = d1.A; t.ldx0 = d1.lda; t.x1 = d1.B; t.ldx1 = d1.ldb; t.n0 = d1.K; t.x2 = d1.aux; t.ldaux2 = d1.ldaux; t.y0 = d1.C; t.ldout2 = d1.ldc;
+}
+// ... whose row operand GDH [B, S + 1] is itself computed by the tile (FLAG_PRE_MSE): the decoder heads Wh [S + 1, K] / bh on D1 [B, K] with
+// their mse losses; GD1 [B, K] is where the recomputed layer is stored
+static inline void rl_task_pre_mse(GemmTask& t, float* GDH, int ldgdh, const float* Wh, int ldwh, const float* bh, int S, const float* D1, int ldd1,
+                                   float* GD1, int ldgd1, const float* s2, int ld_s2, const float* r, float scale_s, float scale_r, float* part) {
+    t.flags |= FLAG_PRE | FLAG_PRE_MSE;
+    t.x0 = GDH; t.ldx0 = ldgdh; t.x1 = Wh; t.ldx1 = ldwh; t.n0 = S + 1; t.x2 = D1; t.ldaux2 = ldd1; t.y0 = GD1; t.ldout2 = ldgd1;
+    t.bias = bh; t.tgs = s2; t.ldtgs = ld_s2; t.tgr = r; t.pad_mse = S;
+    t.s0 = scale_s; t.s1 = scale_r; t.mse_part = part;
+}
+// Blocks of the elementwise ELBO kernels (vae_mid_kernel: rows x width = B x F; vae_mse_kernel: B x (S + 1)): 256 elements a block, one
+// partial (pair) each; column tiles of heads_vae_kernel (16 x 16 tiles, one KL partial each)
+static inline int rl_vae_blocks(int rows, int width) { return (int)(((long long)rows * width + 255) / 256); }
+static inline int rl_heads_vae_tiles_c(int F) { return (F + 15) / 16; }
+
 struct Builder {
     rlrep_agent* ag; Workspace& ws; bool dry;
     Builder(rlrep_agent* a) : ag(a), ws(a->ws), dry(a->ws.dry) {}
@@ -344,16 +398,7 @@ struct Builder {
         gemm_small_launch(p, la, lb, tasks, what);
     }
     void gemm_small_launch(Program& p, int la, int lb, std::vector<GemmTask> tasks, const char* what) {
-        // column fragments per workgroup: the widest tile that still leaves >= ~1.5 workgroups per CU; the
-        // epilogues that need a whole row / per-tile partials in one fragment force NF = 1
-        int nf = 1;
-        {
-            bool force1 = false;
-            for (auto& t : tasks) force1 = force1 || t.epi == EPI_FWD_POLICY || t.epi == EPI_FWD_MSE || t.epi == EPI_DX_REPARAM;
-            auto count = [&](int f) { long long n = 0; for (auto& t : tasks) n += (long long)((t.R + 15) / 16) * ((t.Cn + 16 * f - 1) / (16 * f)); return n; };
-            if (!force1) { if (count(2) >= 384) nf = 2; if (count(4) >= 384) nf = 4; }
-            if (!tasks.empty() && (tasks[0].flags & FLAG_PRE)) nf = 1;
-        }
+        const int nf = rl_gemm16_pick_nf(tasks.data(), (int)tasks.size());
         const int base_tile = rl_gemm16_number_tiles(tasks.data(), (int)tasks.size(), nf);
         if (tasks.size() > GEMM_MAX_TASKS) { fprintf(stderr, "rlrep: too many tasks in stage %s\n", what); abort(); }
         GemmBatch gb; memset(&gb, 0, sizeof(gb));
@@ -523,8 +568,7 @@ struct Builder {
                         (d2.epi == EPI_DX || d2.epi == EPI_DX_REPARAM) && ((d2.R + 15) / 16) * ((d2.Cn + 15) / 16) < 384 * 2;
         if (!ok) { dx_stage(p, {d1}, w1); dx_stage(p, {d2}, w2); return; }
         GemmTask t = d2;
-        t.flags |= FLAG_PRE | (d1.act == ACT_ELU ? FLAG_PRE_ELU : 0);
-        t.x0 = d1.A; t.ldx0 = d1.lda; t.x1 = d1.B; t.ldx1 = d1.ldb; t.n0 = d1.K; t.x2 = d1.aux; t.ldaux2 = d1.ldaux; t.y0 = d1.C; t.ldout2 = d1.ldc;
+        rl_task_pre_dx(t, d1);
         gemm_small(p, LD_ROW, LD_COL, {t}, w2);
     }
     // Forward twin: layer pairs (first, second) where the FIRST has a short inner length (<= 48), ReLU and a transposed weight shadow `wt`
