@@ -502,7 +502,7 @@ int32_t rlrep_per_update(rlrep_agent* agent, float* tree_dev, int64_t P, float* 
 int32_t rlrep_critic_step_weighted(rlrep_agent* agent, const float* eps_dev, const float* w_dev, void* stream);
 const float* rlrep_per_td_dev(rlrep_agent* agent);
 
-/* ---- prioritized replay of the CRITIC's minibatch for vlsac / ctrlsac / spedersac / diffsrsac (additive to ABI 4; DESIGN.md 6f.1, csrc/per_fill.hip)
+/* ---- prioritized replay of the CRITIC's minibatch for vlsac / ctrlsac / spedersac / diffsrsac (additive to ABI 4; DESIGN.md 6f.1, csrc/per.hip)
  * These agents reuse the slot-0 minibatch of their last feature step for the critic and actor steps; that minibatch alone is drawn from the
  * tree (tree, scalars and sampler exactly as above), every other minibatch of a train() stays the uniform draw.
  *   rlrep_per_sample_fill     rlrep_per_sample and rlrep_replay_sample(slot 0) of the drawn rows in ONE launch: idx_dev[batch] and w_dev[batch] as
@@ -543,7 +543,7 @@ int32_t rlrep_group_per_update(rlrep_agent* group, float* trees_dev, int64_t P, 
 int32_t rlrep_group_critic_step_weighted(rlrep_agent* group, const float* eps_dev, const float* w_dev, void* stream);
 const float* rlrep_group_per_td_dev(rlrep_agent* group);
 
-/* ---- prioritized replay of the CRITIC's minibatch for ctrlsac SEED GROUPS (additive to ABI 4; DESIGN.md 6g.1, csrc/per_fill_group.hip) ----------
+/* ---- prioritized replay of the CRITIC's minibatch for ctrlsac SEED GROUPS (additive to ABI 4; DESIGN.md 6g.1, csrc/per_group.hip) ----------
  * The group forms of rlrep_per_sample_fill / rlrep_critic_weights_arm / rlrep_per_update_td.  Trees, scalars and draw buffers as for sac seed
  * groups above (trees_dev float32[members, 2 P], scal_dev float32[members, 4], idx_dev int32[members, batch], w_dev float32[members, batch]);
  * td_dev float32[members, batch] is the caller's too.  Member m computes bit for bit what the single-agent entry points compute for a ctrlsac

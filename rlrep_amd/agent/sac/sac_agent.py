@@ -486,7 +486,7 @@ class SACAgent(object):
             raise RuntimeError(f'{name}.iterate: {cls} cannot be written by a device environment (its step launch knows nothing of the priority '
                                'tree): use a plain ReplayBuffer')
 
-    # ---- prioritized replay of the critic's minibatch (utils/buffer.py CriticPrioritizedReplayBuffer; DESIGN.md 6f.1, csrc/per_fill.hip) -------
+    # ---- prioritized replay of the critic's minibatch (utils/buffer.py CriticPrioritizedReplayBuffer; DESIGN.md 6f.1, csrc/per.hip) -------
     @staticmethod
     def _cper(buffer):
         return bool(getattr(buffer, 'critic_prioritized', False))

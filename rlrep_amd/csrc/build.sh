@@ -16,7 +16,7 @@ LIBNAME="${OUTNAME:-librlrep_hip.so}"
 mkdir -p "$OUT" "$OBJ"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -Wno-unused-function $EXTRA_FLAGS"
-SRCS="gemm16 gemm_lds noisecritic elementwise per per_group per_fill per_fill_group nstep nstep_targets actor_tile group_clone group_env sim_step sim_jit sim_jit_check replearn comm $EXP_SRCS engine agents1 agents2 group_api $EXTRA_SRCS"
+SRCS="gemm16 gemm_lds noisecritic elementwise per per_group nstep nstep_targets actor_tile group_clone group_env sim_step sim_jit sim_jit_check replearn comm $EXP_SRCS engine agents1 agents2 group_api $EXTRA_SRCS"
 # sim_jit.h is also carried in the library as text, for the run-time compile of a user's simulator kind (sim_jit.hip includes this file)
 { printf 'R"SIMJIT('; cat "$HERE/sim_jit.h"; printf ')SIMJIT"\n'; } > "$OBJ/sim_jit_text.inc.new"
 if cmp -s "$OBJ/sim_jit_text.inc.new" "$OBJ/sim_jit_text.inc"; then rm -f "$OBJ/sim_jit_text.inc.new"; else mv "$OBJ/sim_jit_text.inc.new" "$OBJ/sim_jit_text.inc"; fi

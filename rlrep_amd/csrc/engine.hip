@@ -1008,7 +1008,7 @@ int32_t rlrep_critic_step_weighted(rlrep_agent* ag, const float* eps, const floa
     return rc ? rc : rlrep_critic_apply(ag, stream);
 }
 
-// ---- prioritized replay of the critic's minibatch for vlsac / ctrlsac / spedersac / diffsrsac (per_fill.hip) ------------
+// ---- prioritized replay of the critic's minibatch for vlsac / ctrlsac / spedersac / diffsrsac (per.hip) ------------
 // the entry points that work for ONE representation agent on ONE GPU
 static int cper_agent_ok(const char* what, const rlrep_agent* ag) {
     if (!ag) { rl_set_error("%s: null agent", what); return RLREP_ERR_ARG; }

@@ -824,7 +824,7 @@ bool per_tree_ok(const char* what, const float* tree, int64_t P, const float* sc
 // The head stage of every critic program of vlsac / ctrlsac / spedersac / diffsrsac: qhead_critic_kernel, or -- while a weighted critic
 // backward is in progress (rlrep_critic_weights_arm) -- the weighted head of per.hip with the call's weights and |TD| array.  One stage,
 // one launch either way: the weighted form of a program is the program.  A seed group (rlrep_group_critic_weights_arm: ctrlsac) takes the
-// group form whose w and td are both the buffer group's [R, B] arrays (per_fill_group.hip); sac groups never come here.
+// group form whose w and td are both the buffer group's [R, B] arrays (per_group.hip); sac groups never come here.
 inline int critic_head_launch(const rlrep_agent* ag, const QHeadCritic& q, hipStream_t st) {
     if (!ag->cur_w) return rl_launch_qhead_critic(&q, st);
     QHeadCriticW qw; qw.q = q; qw.w = ag->cur_w; qw.td = ag->cur_td;

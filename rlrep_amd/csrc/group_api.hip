@@ -413,7 +413,7 @@ int32_t rlrep_group_critic_step_weighted(rlrep_agent* ag, const float* eps, cons
     return rc ? rc : rlrep_critic_apply(ag, stream);
 }
 
-// ---- prioritized replay of the critic's minibatch for a ctrlsac seed group (per_fill_group.hip) --------------------------------
+// ---- prioritized replay of the critic's minibatch for a ctrlsac seed group (per_group.hip) --------------------------------
 // the three entry points work for a ctrlsac seed group on one GPU, and refuse everything else by name
 static int cper_group_ok(const char* what, const rlrep_agent* ag) {
     if (!ag) { rl_set_error("%s: null agent", what); return RLREP_ERR_ARG; }
@@ -462,7 +462,7 @@ int32_t rlrep_group_per_sample_fill(rlrep_agent* ag, const float* rings_dev, int
     return 0;
 }
 // The next rlrep_critic_step / rlrep_critic_backward of the group is the weighted one: w[members, B] in the members' losses, their |TD| into the
-// caller's td[members, B] (critic_head_launch picks the group head of per_fill_group.hip).  That step disarms (critic_backward_dispatch); so
+// caller's td[members, B] (critic_head_launch picks the group head of per_group.hip).  That step disarms (critic_backward_dispatch); so
 // does passing null.
 int32_t rlrep_group_critic_weights_arm(rlrep_agent* ag, const float* w_dev, float* td_dev) {
     if (int rc = cper_group_ok("group_critic_weights_arm", ag)) return rc;

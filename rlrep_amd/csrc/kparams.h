@@ -148,7 +148,7 @@ struct PerSample {
     unsigned long long seed, offset; const int* step_dev;                                       // Philox stream: offset + *step_dev (null: offset)
 };
 struct PerUpdate { float* tree; float* scal; const int* idx; const float* td; long long P; int B; };
-// per_fill.hip: the sampler and the gather of the drawn rows into a minibatch slot in one launch.  f: the ring and the slot buffers as
+// per_sample_fill (per.hip): the sampler and the gather of the drawn rows into a minibatch slot in one launch.  f: the ring and the slot buffers as
 // fill_slot_kernel takes them (f.idx unused: the rows are s.idx's); capacity: the ring's rows; rows: samples per gathering workgroup (the launcher's)
 struct PerSampleFill { PerSample s; SlotFill f; long long capacity; int rows; };
 // n-step returns (nstep.hip): the gather that follows each sampled row's trajectory forward through the ring.  fill: the ring,

@@ -77,13 +77,13 @@ int rl_launch_replay_add_cols_ctl(const ReplayCols* p, long long* ctl, hipStream
 long long rl_actor_tile_lds_bytes(int S, int Ha, int A);
 int rl_launch_actor_tile(const ActTile* p, hipStream_t st);                        // p->rows observations (per member of an active group), 16 per workgroup
 int rl_launch_actor_tile_ctl(const ActTile* p, const ActCtl* k, hipStream_t st);   // one agent; counters from the loop record, exploration mix behind the head
-// ---- per.hip (prioritized replay: one workgroup each; the weighted sac critic head) ----
+// ---- per.hip (prioritized replay of a single agent: one workgroup each; the weighted sac critic head; sample + slot gather in one launch) ----
 int rl_launch_per_add(const PerAdd* p, hipStream_t st);
 int rl_launch_per_rebuild(float* tree, long long P, hipStream_t st);
 int rl_launch_per_sample(const PerSample* p, hipStream_t st);
 int rl_launch_per_update(const PerUpdate* p, hipStream_t st);
 int rl_launch_qhead_critic_w(const QHeadCriticW* p, hipStream_t st);                // its group form (per_group.hip) while a group is active
-// ---- per_fill.hip (prioritized replay of the representation agents' critic minibatch: sample + slot gather, workgroup 0 samples, the rest gather) ----
+// (prioritized replay of the representation agents' critic minibatch: sample + slot gather, workgroup 0 samples, the rest gather)
 int rl_launch_per_sample_fill(PerSampleFill* p, hipStream_t st);                    // sets p->rows
 // ---- per_group.hip (prioritized replay of a sac seed group: one workgroup per member; all but per_add need an active group) ----
 int rl_launch_per_add_grp(const PerAdd* p, int members, hipStream_t st);                                    // member m: tree + m * 2P, scal + 4 m
@@ -91,7 +91,7 @@ int rl_launch_per_sample_grp(const PerSample* p, hipStream_t st);
 int rl_launch_per_gather_grp(const SlotFill* fill, const int* idx, long long ring_rows, hipStream_t st);      // ring row idx[m][b] of member m's ring -> its slot 0, grid (blocks, R)
 int rl_launch_per_update_grp(const PerUpdate* p, long long td_stride, hipStream_t st);                      // td_stride < 0: td moves by the member stride
 int rl_launch_qhead_critic_w_grp(const QHeadCriticW* p, hipStream_t st);
-// ---- per_fill_group.hip (prioritized critic replay of a ctrlsac seed group: the group form of per_fill.hip's launch, grid (1 + G, R); the weighted head with a [R, B] td) ----
+// (prioritized critic replay of a ctrlsac seed group: the group form of rl_launch_per_sample_fill, grid (1 + G, R); the weighted head with a [R, B] td)
 int rl_launch_per_sample_fill_grp(PerSampleFill* p, hipStream_t st);                 // sets p->rows; needs an active group
 int rl_launch_qhead_critic_wtd_grp(const QHeadCriticW* p, hipStream_t st);          // w and td: the buffer group's [R, B] arrays
 // ---- nstep.hip (n-step returns: the chain-following replay gather, one wave per sample) ----

@@ -394,7 +394,7 @@ def _f32(x):
     return np.float32(x)
 
 
-PER_MIN_PRIORITY = np.float32(1.17549435e-38)        # the smallest normal float32: the floor of an updated leaf (csrc/per.hip)
+PER_MIN_PRIORITY = np.float32(1.17549435e-38)        # the smallest normal float32: the floor of an updated leaf (csrc/per_tree.h)
 
 
 def _per_set(tree, P, rows, value):
@@ -621,7 +621,7 @@ class PrioritizedReplayBuffer(ReplayBuffer):
                          self._hyper[2])
 
 
-# ---- prioritized replay of the critic's minibatch for vlsac / ctrlsac / spedersac / diffsrsac: DESIGN.md 6f.1, csrc/per_fill.hip ----------
+# ---- prioritized replay of the critic's minibatch for vlsac / ctrlsac / spedersac / diffsrsac: DESIGN.md 6f.1, csrc/per.hip ----------
 class CriticPrioritizedReplayBuffer(PrioritizedReplayBuffer):
     """PrioritizedReplayBuffer for the representation agents (VLSACAgent, CTRLSACAgent, SPEDERSACAgent, DIFFSRSACAgent), with another sampling
     contract -- hence another name, as critic_n_step stands to n_step.  These agents run their critic and actor steps on the slot-0 minibatch

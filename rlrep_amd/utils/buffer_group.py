@@ -358,7 +358,7 @@ class PrioritizedReplayBufferGroup(ReplayBufferGroup):
             _per_update_host(self.trees[r].numpy(), self.P, self._scal.numpy()[r], idx[r].numpy(), td[r], self._hyper[r, 0], self._hyper[r, 2])
 
 
-# ---- prioritized replay of the critic's minibatch for ctrlsac seed groups: DESIGN.md 6g.1, csrc/per_fill_group.hip ----------------------
+# ---- prioritized replay of the critic's minibatch for ctrlsac seed groups: DESIGN.md 6g.1, csrc/per_group.hip ----------------------
 class CriticPrioritizedReplayBufferGroup(PrioritizedReplayBufferGroup):
     """PrioritizedReplayBufferGroup for CTRLSACSeedBatch, with CriticPrioritizedReplayBuffer's sampling contract -- hence another name.  A
     ctrlsac member runs its critic and actor steps on the slot-0 minibatch of its LAST feature step; that minibatch alone is drawn from the

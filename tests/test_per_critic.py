@@ -1,4 +1,4 @@
-"""GPU: prioritized replay of the critic's minibatch for vlsac / ctrlsac / spedersac / diffsrsac (csrc/per_fill.hip).  The fused
+"""GPU: prioritized replay of the critic's minibatch for vlsac / ctrlsac / spedersac / diffsrsac (csrc/per.hip).  The fused
 sample-and-gather launch against tests/per_reference.py and against rlrep_per_sample, which minibatches of a train() are prioritized,
 alpha = 0 as uniform replay, the weighted critic step against weighted CPU oracles, the launch counts, a long graph run with save /
 restore, the refusals and the launcher."""

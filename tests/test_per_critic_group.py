@@ -1,4 +1,4 @@
-"""GPU: prioritized critic replay for ctrlsac seed groups (csrc/per_fill_group.hip).  The fused group launch against
+"""GPU: prioritized critic replay for ctrlsac seed groups (csrc/per_group.hip).  The fused group launch against
 tests/per_reference.py, against rlrep_per_sample_fill on a standalone ctrlsac agent and against the members' ring rows; member r of a
 CTRLSACSeedBatch training from a CriticPrioritizedReplayBufferGroup against its standalone twin -- CTRLSACAgent(seed=s_r, pipeline=False) on a
 CriticPrioritizedReplayBuffer(alpha_r, beta_r) fed the same rows -- bit for bit; which minibatches are prioritized; alpha = 0 as uniform replay;
