@@ -1049,6 +1049,49 @@ int32_t rlrep_group_replay_add_cols(float* ring_dev, int64_t max_size, int32_t r
                                     const float* a, int64_t ld_a, const float* s2, int64_t ld_s2, const float* r, const float* d, int64_t n,
                                     int32_t members, int64_t ring_stride_floats, int32_t* size_dev, int32_t new_size, void* stream);
 
+/* ---- the one-graph simulator loop of a seed group (additive to ABI 4) ---------------------------------------------------------
+ * The counter-reading forms above, for every live member of a group in ONE launch each (grid y = a slot of the live table), stream-ordered and
+ * capturable: no copy, no allocation, no synchronisation.  The loop record of a group is ctl_dev, int64[members][RLREP_LOOP_CTL_WORDS] in
+ * caller-owned device memory, member r's row r * RLREP_LOOP_CTL_WORDS words behind member 0's:
+ *   shared by the group, in row 0:  word 0 calls, 1 t_global (steps PER MEMBER: an iteration adds n), 2 iter, 6 warm -- one value for all
+ *                                   members; they advance whenever at least one member is live
+ *   per member, in row r:           word 3 next, 4 start, 5 size -- member r's cursor into its own ring (words 0, 1, 2, 6 of rows 1.. are unused)
+ * In either launch no thread writes a word that a workgroup of the same launch reads: thread 0 of workgroup (0, slot) moves the cursor of member
+ * slot_member[slot]; the one of slot 0 -- the first live member -- also writes the shared words.  A retired member's row, ring, size word and
+ * planes are neither read nor written.
+ *
+ * rlrep_group_act_device_ctl: obs_dev [members, rows, S], action_dev [members, rows, A] (contiguous); plane r is bit for bit what
+ * rlrep_act_device_ctl gives the standalone agent with seed seeds[r] (rlrep_group_set_seeds) at the same calls / t_global / iter -- seeds[r] is
+ * the key of the head's draw and of the exploration mix.  Refused with RLREP_ERR_ARG before the launch ("group_act_device_ctl:"): a null
+ * argument, rows outside [1, RLREP_ACT_MAX_ROWS] or above max_size, a handle that is not a seed group, eps_greedy outside [0, 1], a negative
+ * start_timesteps, the LDS limit.
+ *
+ * rlrep_group_replay_add_cols_ctl: member r's n transitions are rows r * n .. of the five arrays; they go into ring ring_dev + r *
+ * ring_stride_floats from ITS start, wrapping; ITS size goes to size_dev[r] (which may be NULL); iter += 1, t_global += n and calls += n unless
+ * warm happen once.  Unlike rlrep_group_replay_add_cols it honours the live table.  Refused by name ("group_replay_add_cols_ctl:"): a null
+ * argument, a handle that is not a seed group, n outside [1, RLREP_ACT_MAX_ROWS] or above max_size, row_floats != 2 S + A + 2, a row stride
+ * below its width, a ring stride below a ring.
+ *
+ * rlrep_group_sim_start / _step / _step_append_ctl: rlrep_sim_start / _step / _step_append_ctl for members x n environments.  `sim` is a
+ * rlrep_sim_state whose arrays are [members, n] planes (obs [members, n, S]); its `seed` field is ignored: member r's start states are keyed by
+ * sim_seeds_dev[r] (uint64[members], device) with the environment's index WITHIN the member as counter word 2, so plane r is the single
+ * simulator with that seed, word for word.  act is [members, n] rows at stride ld_act; next_obs [members, n, S], reward and done [members, n].
+ * rlrep_group_sim_start resets every member and does not consult the live table; the two steps skip retired members.  The _ctl form does for
+ * the group what rlrep_group_replay_add_cols_ctl's bookkeeping threads do.  Refused by name before the launch ("group_sim_start:",
+ * "group_sim_step:", "group_sim_step_append_ctl:"): a null argument, a handle that is not a seed group, an unknown kind, n outside [1,
+ * RLREP_SIM_MAX_ENVS] or above max_size, ld_act below the kind's A, row_floats != 2 S + A + 2, a ring stride below a ring. */
+int32_t rlrep_group_act_device_ctl(rlrep_agent* agent, const float* obs_dev, int32_t rows, float lo, float hi, float* action_dev, int64_t* ctl_dev,
+                                   int64_t max_size, float eps_greedy, int64_t start_timesteps, void* stream);
+int32_t rlrep_group_replay_add_cols_ctl(rlrep_agent* agent, float* ring_dev, int64_t max_size, int32_t row_floats, int32_t S, int32_t A, const float* s,
+                                        int64_t ld_s, const float* a, int64_t ld_a, const float* s2, int64_t ld_s2, const float* r, const float* d, int64_t n,
+                                        int64_t ring_stride_floats, int32_t* size_dev, int64_t* ctl_dev, void* stream);
+int32_t rlrep_group_sim_start(rlrep_agent* agent, const rlrep_sim_state* sim, const uint64_t* sim_seeds_dev, void* stream);
+int32_t rlrep_group_sim_step(rlrep_agent* agent, const rlrep_sim_state* sim, const uint64_t* sim_seeds_dev, const float* act, int64_t ld_act, float* next_obs,
+                             float* reward, float* done, void* stream);
+int32_t rlrep_group_sim_step_append_ctl(rlrep_agent* agent, const rlrep_sim_state* sim, const uint64_t* sim_seeds_dev, const float* act, int64_t ld_act,
+                                        float* ring_dev, int64_t max_size, int32_t row_floats, int64_t ring_stride_floats, int32_t* size_dev,
+                                        int64_t* ctl_dev, void* stream);
+
 /* ---- device environments of a seed group (additive to ABI 4) ------------------------------------------------------------------------------
  * The launcher's group loop (main.py run_seeds) waits for select_action, steps R NumPy environments, draws the exploration actions and stages
  * R ring rows on the host every iteration, and every evaluation costs episodes x 200 further round trips per member.  A device environment

@@ -331,6 +331,11 @@ def _load():
         'rlrep_sim_start': (i32, [P(SimState), vp]),
         'rlrep_sim_step': (i32, [P(SimState), vp, i64, vp, vp, vp, vp]),
         'rlrep_sim_step_append_ctl': (i32, [P(SimState), vp, i64, vp, i64, i32, vp, vp, vp]),
+        'rlrep_group_act_device_ctl': (i32, [vp, vp, i32, f32, f32, vp, vp, i64, f32, i64, vp]),
+        'rlrep_group_replay_add_cols_ctl': (i32, [vp, vp, i64, i32, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, i64, i64, vp, vp, vp]),
+        'rlrep_group_sim_start': (i32, [vp, P(SimState), vp, vp]),
+        'rlrep_group_sim_step': (i32, [vp, P(SimState), vp, vp, i64, vp, vp, vp, vp]),
+        'rlrep_group_sim_step_append_ctl': (i32, [vp, P(SimState), vp, vp, i64, vp, i64, i32, i64, vp, vp, vp]),
         'rlrep_simx_state_bytes': (i32, []),
         'rlrep_sim_kind_compile': (i32, [P(SimKindDesc), P(vp)]),
         'rlrep_sim_kind_destroy': (None, [vp]),

@@ -522,6 +522,32 @@ class SeedBatchMixin(object):
             raise ValueError(f'{name}.iterate: the device environment belongs to another group')
         return self._iterate(env, buffers, batch_size, train, lambda: env.step(buffers, env.eps_greedy, env.start_timesteps), '_iter')
 
+    # ---- simulators on the device (rlrep_amd/envs/sim_loop.py SimLoopGroup): the whole iteration of every live member as one graph replay ---
+    def iterate_sim(self, loop, buffers, batch_size, train=True):
+        """One iteration of the loop around a simulator of R x N environments on the device -- act on every live member's N observations and
+        mix in its exploring uniform actions (rlrep_group_act_device_ctl), step the simulator, append every live member's N transitions to its
+        own ring (rlrep_group_replay_add_cols_ctl; with envs/fused_sim.py FusedSimGroup the step does the append: two launches in all) --
+        and, with `train`, one train() of every live member on the rings as they then stand: ONE graph replay, no host round trip.  `loop` is
+        a SimLoopGroup of this group, `buffers` a ReplayBufferGroup whose cursor the device owns from here on.  Returns what train() returns,
+        or None without `train`.  Member r is bit for bit SACAgent(seed=seeds[r]).iterate_sim on a SimLoop of its own; retire_members /
+        revive_members keep the captured graph, and a retired member's ring, cursor and simulator planes stand still.  An n-step buffer
+        group (sac) needs n_stride = N.  Not for the prioritized buffer groups (the captured append does not write the priority trees)."""
+        name, cls = type(self).__name__, type(buffers).__name__
+        self._refuse_per(buffers, 'iterate_sim')
+        if self._per(buffers) or getattr(buffers, 'critic_prioritized_group', False):
+            raise RuntimeError(f'{name}.iterate_sim: {cls} cannot be written by the captured simulator loop (its append launch does not write the '
+                               'priority trees): use a plain ReplayBufferGroup, or the eager act_device / add_device / train() loop')
+        self._check_per(buffers, 'iterate_sim')         # (n-step rows: refused for a ctrlsac group, as iterate refuses them)
+        if (getattr(buffers, 'members', None) != self.R
+                or (getattr(buffers, 'state_dim', None), getattr(buffers, 'action_dim', None)) != (self.state_dim, self.action_dim)):
+            raise ValueError(f'{name}.iterate_sim: needs a ReplayBufferGroup of {self.R} members, {self.state_dim} observations and {self.action_dim} actions')
+        if getattr(loop, 'agent', None) is not self or getattr(loop, 'R', None) != self.R:
+            raise ValueError(f'{name}.iterate_sim: the simulator loop belongs to another group')
+        N = int(loop.num_envs)
+        if N > buffers.max_size:
+            raise ValueError(f'{name}.iterate_sim: {N} environments for rings of {buffers.max_size} rows')
+        return self._iterate(loop, buffers, batch_size, train, lambda: loop.step(buffers), '_sim', getattr(loop.sim, 'graph_generators', ()))
+
     def evaluate(self, env, episodes, eval_index=None):
         """Mean return of `episodes` mean-action episodes per member, [R] float64 (NaN for a retired member): ONE launch
         (rlrep_group_env_evaluate) and one copy back.  The start states are a function of (member seed, eval_index, episode); by default

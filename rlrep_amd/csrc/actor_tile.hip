@@ -154,25 +154,7 @@ __global__ __launch_bounds__(256) void actor_tile_kernel_ctl(ActTile p0, ActCtl 
     {
 #include "actor_tile_body.h"
     }
-    const bool warm = tg < k.start_timesteps;
-    if (warm || k.eps_greedy > 0.f) {
-        for (int e = threadIdx.x; e < 16 * p.A; e += 256) {
-            const int i = e / p.A, j = e - i * p.A;
-            const long long row = (long long)r0 + i;
-            if (row >= p.rows) continue;
-            uint32_t c[4] = {(uint32_t)it, (uint32_t)(it >> 32), (uint32_t)row, RL_STREAM_SIM};
-            philox4x32_10(c, (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-            if (!(warm || env_u01f(c[0]) < k.eps_greedy)) continue;
-            const int wq = (1 + j) >> 2, ww = (1 + j) & 3;
-            if (wq) {
-                c[0] = (uint32_t)it; c[1] = (uint32_t)(it >> 32); c[2] = (uint32_t)row; c[3] = RL_STREAM_SIM + (uint32_t)wq;
-                philox4x32_10(c, (uint32_t)p.seed, (uint32_t)(p.seed >> 32));
-            }
-            const uint32_t word = ww == 0 ? c[0] : ww == 1 ? c[1] : ww == 2 ? c[2] : c[3];
-            const float u = mix_add(p.lo, mix_mul(mix_sub(p.hi, p.lo), env_u01f(word)));
-            p.act[row * p.ld_act + j] = fminf(fmaxf(u, p.lo), p.hi);
-        }
-    }
+#include "actor_tile_mix.h"
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         long long ptr = k.ctl[RL_CTL_NEXT];
         if (ptr < 0 || ptr >= k.capacity) ptr = 0;                      // (a cursor written by the host: never leave the ring)
@@ -181,6 +163,39 @@ __global__ __launch_bounds__(256) void actor_tile_kernel_ctl(ActTile p0, ActCtl 
         k.ctl[RL_CTL_NEXT] = nxt < k.capacity ? nxt : nxt - k.capacity;
         k.ctl[RL_CTL_SIZE] = min(max(k.ctl[RL_CTL_SIZE], 0ll) + p.rows, k.capacity);
         k.ctl[RL_CTL_WARM] = warm ? 1 : 0;
+    }
+}
+// group form of the counter-reading kernel (rlrep_group_act_device_ctl; kparams.h "the loop record of a GROUP"): actor_tile_kernel_grp's
+// rebasing -- the member's actor, its plane of `rows` observation / action rows, its seed as the key of the head's draw and of the mix --
+// around actor_tile_kernel_ctl's body.  CALLS, T and ITER are the group's (row 0 of the record); thread 0 of workgroup (0, slot) moves member
+// m's own cursor words (row m), with the single form's clamps, and the one of slot 0 -- the first live member, there whenever anything runs --
+// writes the group's WARM.  No workgroup of this launch reads any of the words written.
+__global__ __launch_bounds__(256) void actor_tile_kernel_ctl_grp(ActTile p0, ActCtl k, long long mstride, const unsigned long long* __restrict__ seeds,
+                                                                 const int* __restrict__ live) {
+    RL_GRP_MEMBER(m, live);
+    const unsigned long long calls = (unsigned long long)k.ctl[RL_CTL_CALLS];
+    const long long tg = k.ctl[RL_CTL_T];
+    const unsigned long long it = (unsigned long long)k.ctl[RL_CTL_ITER];
+    const long long dm = (long long)m * mstride;
+    ActTile p = p0;
+    p.obs += (long long)m * p.rows * p.ld_obs; p.act += (long long)m * p.rows * p.ld_act;
+    rl_rb(p.W1, dm); rl_rb(p.b1, dm); rl_rb(p.W2, dm); rl_rb(p.b2, dm); rl_rb(p.W3, dm); rl_rb(p.b3, dm);
+    p.seed = seeds[m];
+    p.explore = 1; p.offset = (calls + 1ull) << 20;
+    const int r0 = blockIdx.x * 16;
+    {
+#include "actor_tile_body.h"
+    }
+#include "actor_tile_mix.h"
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        long long* cm = k.ctl + (long long)m * RL_LOOP_CTL_WORDS;
+        long long ptr = cm[RL_CTL_NEXT];
+        if (ptr < 0 || ptr >= k.capacity) ptr = 0;                      // (a cursor written by the host: never leave the ring)
+        const long long nxt = ptr + p.rows;                             // (the launcher holds rows <= capacity)
+        cm[RL_CTL_START] = ptr;
+        cm[RL_CTL_NEXT] = nxt < k.capacity ? nxt : nxt - k.capacity;
+        cm[RL_CTL_SIZE] = min(max(cm[RL_CTL_SIZE], 0ll) + p.rows, k.capacity);
+        if (blockIdx.y == 0) k.ctl[RL_CTL_WARM] = warm ? 1 : 0;
     }
 }
 
@@ -224,5 +239,20 @@ extern "C" int rl_launch_actor_tile_ctl(const ActTile* p0, const ActCtl* k, hipS
         if (e != hipSuccess) return (int)e;
     }
     hipLaunchKernelGGL(actor_tile_kernel_ctl, dim3((unsigned)((p.rows + 15) / 16)), dim3(256), (size_t)lds, st, p, *k);
+    return (int)hipGetLastError();
+}
+// the counter-reading form of a group (the callers refuse everything but a group's handle): grid (ceil(rows / 16), grid_y), same LDS
+extern "C" int rl_launch_actor_tile_ctl_grp(const ActTile* p0, const ActCtl* k, hipStream_t st) {
+    const long long lds = rl_actor_tile_lds_bytes(p0->S, p0->Ha, p0->A);
+    if (lds > RL_ACT_TILE_LDS_MAX) return -7;
+    const RlGrp* gr = rl_grp_active();
+    if (!gr || !gr->seeds || !gr->live) return RL_GRP_UNSUPPORTED;
+    ActTile p = *p0;
+    p.LD = at_pitch(p.S, p.Ha);
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(actor_tile_kernel_ctl_grp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(actor_tile_kernel_ctl_grp, dim3((unsigned)((p.rows + 15) / 16), gr->grid_y), dim3(256), (size_t)lds, st, p, *k, gr->stride, gr->seeds, gr->live);
     return (int)hipGetLastError();
 }

@@ -752,10 +752,39 @@ __global__ __launch_bounds__(256) void replay_add_cols_kernel_ctl(ReplayCols p0,
         if (!ctl[RL_CTL_WARM]) ctl[RL_CTL_CALLS] += p.n;
     }
 }
+// group form of the counter-reading kernel (rlrep_group_replay_add_cols_ctl; kparams.h "the loop record of a GROUP"): workgroup (x, slot)
+// packs plane m of the five arrays (rows m * n ..) into member m's ring from ITS start row (row m of the record) and thread 0 of workgroup
+// (0, slot) publishes ITS fill level; the one of slot 0 advances the group's ITER, T and CALLS once.  Unlike replay_add_cols_kernel_grp it
+// honours the live table: the ring, the fill level and the cursor of a retired member stand still.
+__global__ __launch_bounds__(256) void replay_add_cols_kernel_ctl_grp(ReplayCols p0, long long* __restrict__ ctl, const int* __restrict__ live) {
+    RL_GRP_MEMBER(m, live);
+    ReplayCols p = p0;
+    const long long* cm = ctl + (long long)m * RL_LOOP_CTL_WORDS;
+    const long long st = cm[RL_CTL_START];
+    p.start = (st < 0 || st >= p.capacity) ? 0 : st;                       // (a cursor written by the host: never leave the ring)
+    replay_add_cols_body(p, p.ring + (long long)m * p.ring_stride, (long long)m * p.n);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (p.size_dev) p.size_dev[m] = (int)min(max(cm[RL_CTL_SIZE], 0ll), p.capacity);
+        if (blockIdx.y == 0) {
+            ctl[RL_CTL_ITER] += 1;
+            ctl[RL_CTL_T] += p.n;
+            if (!ctl[RL_CTL_WARM]) ctl[RL_CTL_CALLS] += p.n;
+        }
+    }
+}
 extern "C" int rl_launch_replay_add_cols_ctl(const ReplayCols* p, long long* ctl, hipStream_t st) {
     const long long total = p->n * p->row;
     const int blocks = (int)std::min<long long>(1024, std::max<long long>(1, (total + 255) / 256));
     hipLaunchKernelGGL(replay_add_cols_kernel_ctl, dim3(blocks), dim3(256), 0, st, *p, ctl);
+    return (int)hipGetLastError();
+}
+// the group's (the caller holds the group active: grid y and the live table are its)
+extern "C" int rl_launch_replay_add_cols_ctl_grp(const ReplayCols* p, long long* ctl, hipStream_t st) {
+    const RlGrp* gr = rl_grp_active();
+    if (!gr || !gr->live) return RL_GRP_UNSUPPORTED;
+    const long long total = p->n * p->row;
+    const int blocks = (int)std::min<long long>(1024, std::max<long long>(1, (total + 255) / 256));
+    hipLaunchKernelGGL(replay_add_cols_kernel_ctl_grp, dim3(blocks, gr->grid_y), dim3(256), 0, st, *p, ctl, gr->live);
     return (int)hipGetLastError();
 }
 extern "C" int rl_launch_replay_add_cols(const ReplayCols* p, int members, hipStream_t st) {

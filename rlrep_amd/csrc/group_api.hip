@@ -334,6 +334,116 @@ int32_t rlrep_group_replay_add_cols(float* ring_dev, int64_t max_size, int32_t r
     if (rc) { rl_set_error("group_replay_add_cols: hip error %d", rc); return RLREP_ERR_HIP; }
     return 0;
 }
+// ---- the one-graph simulator loop of a seed group (kparams.h "the loop record of a GROUP": int64[members][8]) ----------------
+// rlrep_act_device_ctl for every live member in ONE launch (actor_tile_kernel_ctl_grp): the group's CALLS / T / ITER, member r's key seeds[r],
+// its cursor moved by `rows` in its own row of the record
+int32_t rlrep_group_act_device_ctl(rlrep_agent* ag, const float* obs_dev, int32_t rows, float lo, float hi, float* action_dev, int64_t* ctl_dev,
+                                   int64_t max_size, float eps_greedy, int64_t start_timesteps, void* stream) {
+    if (!ag || !obs_dev || !action_dev || !ctl_dev) { rl_set_error("group_act_device_ctl: bad argument (null agent, observations, actions or loop record)"); return RLREP_ERR_ARG; }
+    if (rows < 1 || rows > RLREP_ACT_MAX_ROWS) { rl_set_error("group_act_device_ctl: rows %d outside [1, %d]", rows, RLREP_ACT_MAX_ROWS); return RLREP_ERR_ARG; }
+    if (max_size < rows) { rl_set_error("group_act_device_ctl: rows %d outside [1, max_size %lld] (the rings the cursors move in)", rows, (long long)max_size); return RLREP_ERR_ARG; }
+    if (!(eps_greedy >= 0.f && eps_greedy <= 1.f) || start_timesteps < 0) {
+        rl_set_error("group_act_device_ctl: bad argument (eps_greedy outside [0, 1] or a negative start_timesteps)"); return RLREP_ERR_ARG;
+    }
+    GROUP_ONLY("group_act_device_ctl")                  // (what needs no handle is checked first)
+    SelectAct q; group_actor(ag, q, lo, hi);
+    if (rl_actor_tile_lds_bytes(q.S, q.Ha, q.A) > RL_ACT_TILE_LDS_MAX) {
+        rl_set_error("group_act_device_ctl: the activation tiles of S %d, Ha %d, A %d need %lld bytes of LDS, a workgroup has %d", q.S, q.Ha, q.A,
+                     rl_actor_tile_lds_bytes(q.S, q.Ha, q.A), RL_ACT_TILE_LDS_MAX);
+        return RLREP_ERR_ARG;
+    }
+    ActTile p; memset(&p, 0, sizeof(p));
+    p.obs = obs_dev; p.act = action_dev; p.W1 = q.W1; p.b1 = q.b1; p.W2 = q.W2; p.b2 = q.b2; p.W3 = q.W3; p.b3 = q.b3;
+    p.S = q.S; p.Ha = q.Ha; p.A = q.A; p.explore = 1; p.lo = lo; p.hi = hi; p.seed = 0;
+    p.rows = rows; p.ld_obs = q.S; p.ld_act = q.A;
+    ActCtl k; memset(&k, 0, sizeof(k));
+    k.ctl = (long long*)ctl_dev; k.capacity = max_size; k.start_timesteps = start_timesteps; k.eps_greedy = eps_greedy;
+    GrpScope grp_scope_(ag);
+    ++g_rl_launches;
+    const int rc = rl_launch_actor_tile_ctl_grp(&p, &k, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_act_device_ctl: launch failed (%d)", rc); return rc == -7 ? RLREP_ERR_ARG : RLREP_ERR_HIP; }
+    return 0;
+}
+// rlrep_replay_add_cols_ctl for every live member in ONE launch (replay_add_cols_kernel_ctl_grp): member r's plane of the five arrays into its
+// ring from its own start row, its fill level into size_dev[r], the group's counters advanced once
+int32_t rlrep_group_replay_add_cols_ctl(rlrep_agent* ag, float* ring_dev, int64_t max_size, int32_t row_floats, int32_t S, int32_t A, const float* s, int64_t ld_s,
+                                        const float* a, int64_t ld_a, const float* s2, int64_t ld_s2, const float* r, const float* d, int64_t n,
+                                        int64_t ring_stride_floats, int32_t* size_dev, int64_t* ctl_dev, void* stream) {
+    if (!ag || !ring_dev || !s || !a || !s2 || !r || !d || !ctl_dev) { rl_set_error("group_replay_add_cols_ctl: bad argument (null agent, ring, array or loop record)"); return RLREP_ERR_ARG; }
+    if (max_size <= 0 || max_size > INT32_MAX || n < 1 || n > max_size || n > RLREP_ACT_MAX_ROWS) {
+        rl_set_error("group_replay_add_cols_ctl: n %lld outside [1, min(max_size %lld, %d)]", (long long)n, (long long)max_size, RLREP_ACT_MAX_ROWS); return RLREP_ERR_ARG;
+    }
+    if (S < 1 || A < 1 || row_floats != 2 * S + A + 2) { rl_set_error("group_replay_add_cols_ctl: row %d is not 2 S + A + 2 (S %d, A %d)", row_floats, S, A); return RLREP_ERR_ARG; }
+    if (ld_s < S || ld_a < A || ld_s2 < S) { rl_set_error("group_replay_add_cols_ctl: bad argument (a row stride below its width)"); return RLREP_ERR_ARG; }
+    if (ring_stride_floats < max_size * row_floats) {
+        rl_set_error("group_replay_add_cols_ctl: ring stride %lld below a ring's %lld floats", (long long)ring_stride_floats, (long long)(max_size * row_floats)); return RLREP_ERR_ARG;
+    }
+    GROUP_ONLY("group_replay_add_cols_ctl")             // (what needs no handle is checked first)
+    ReplayCols p; memset(&p, 0, sizeof(p));
+    p.ring = ring_dev; p.capacity = max_size; p.ring_stride = ring_stride_floats; p.row = row_floats; p.S = S; p.A = A;
+    p.s = s; p.a = a; p.s2 = s2; p.r = r; p.d = d; p.ld_s = ld_s; p.ld_a = ld_a; p.ld_s2 = ld_s2; p.n = n; p.size_dev = size_dev;
+    GrpScope grp_scope_(ag);
+    ++g_rl_launches;
+    const int rc = rl_launch_replay_add_cols_ctl_grp(&p, (long long*)ctl_dev, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_replay_add_cols_ctl: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+// ---- fused simulators of a seed group (sim_step.hip, the group forms): the state's arrays are [members, n] planes, member r keyed by sim_seeds_dev[r] ----
+// what the three entry points refuse alike without looking into the handle, by the entry point's name `who`; the kind's row of rl_env_kinds,
+// or null with the error set.  The handle is looked at last (GROUP_ONLY), as in the entry points above.
+static const EnvKindInfo* group_sim_check(const char* who, const rlrep_agent* ag, const rlrep_sim_state* s, const uint64_t* seeds) {
+    if (!ag || !s || !seeds || !s->x0 || !s->x1 || !s->ep_return || !s->last_return || !s->t || !s->episodes || !s->starts || !s->obs) {
+        rl_set_error("%s: bad argument (null agent, simulator state, array or seeds)", who); return nullptr;
+    }
+    const EnvKindInfo* k = rl_env_kind(s->kind);
+    if (!k) { rl_set_error("%s: kind %d is not built (0 = Pendulum-v1, 2 = MountainCarContinuous-v0)", who, s->kind); return nullptr; }
+    if (s->n < 1 || s->n > RLREP_SIM_MAX_ENVS) { rl_set_error("%s: n %d outside [1, %d]", who, s->n, RLREP_SIM_MAX_ENVS); return nullptr; }
+    return k;
+}
+int32_t rlrep_group_sim_start(rlrep_agent* ag, const rlrep_sim_state* sim, const uint64_t* sim_seeds_dev, void* stream) {
+    if (!group_sim_check("group_sim_start", ag, sim, sim_seeds_dev)) return RLREP_ERR_ARG;
+    GROUP_ONLY("group_sim_start")
+    GrpScope grp_scope_(ag);
+    ++g_rl_launches;
+    const int rc = rl_launch_sim_start_grp((const SimState*)sim, (const unsigned long long*)sim_seeds_dev, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_sim_start: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_group_sim_step(rlrep_agent* ag, const rlrep_sim_state* sim, const uint64_t* sim_seeds_dev, const float* act, int64_t ld_act, float* next_obs,
+                             float* reward, float* done, void* stream) {
+    const EnvKindInfo* k = group_sim_check("group_sim_step", ag, sim, sim_seeds_dev);
+    if (!k) return RLREP_ERR_ARG;
+    if (!act || !next_obs || !reward || !done) { rl_set_error("group_sim_step: bad argument (null actions or output array)"); return RLREP_ERR_ARG; }
+    if (ld_act < k->A) { rl_set_error("group_sim_step: ld_act %lld below the kind's A %d", (long long)ld_act, k->A); return RLREP_ERR_ARG; }
+    GROUP_ONLY("group_sim_step")
+    GrpScope grp_scope_(ag);
+    ++g_rl_launches;
+    const int rc = rl_launch_sim_step_grp((const SimState*)sim, (const unsigned long long*)sim_seeds_dev, act, ld_act, next_obs, reward, done, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_sim_step: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
+int32_t rlrep_group_sim_step_append_ctl(rlrep_agent* ag, const rlrep_sim_state* sim, const uint64_t* sim_seeds_dev, const float* act, int64_t ld_act,
+                                        float* ring_dev, int64_t max_size, int32_t row_floats, int64_t ring_stride_floats, int32_t* size_dev, int64_t* ctl_dev,
+                                        void* stream) {
+    const EnvKindInfo* k = group_sim_check("group_sim_step_append_ctl", ag, sim, sim_seeds_dev);
+    if (!k) return RLREP_ERR_ARG;
+    if (!act || !ring_dev || !ctl_dev) { rl_set_error("group_sim_step_append_ctl: bad argument (null actions, ring or loop record)"); return RLREP_ERR_ARG; }
+    if (max_size <= 0 || max_size > INT32_MAX || sim->n > max_size) {
+        rl_set_error("group_sim_step_append_ctl: n %d outside [1, max_size %lld]", sim->n, (long long)max_size); return RLREP_ERR_ARG;
+    }
+    if (ld_act < k->A) { rl_set_error("group_sim_step_append_ctl: ld_act %lld below the kind's A %d", (long long)ld_act, k->A); return RLREP_ERR_ARG; }
+    if (row_floats != k->row) { rl_set_error("group_sim_step_append_ctl: row %d is not 2 S + A + 2 (S %d, A %d)", row_floats, k->S, k->A); return RLREP_ERR_ARG; }
+    if (ring_stride_floats < max_size * row_floats) {
+        rl_set_error("group_sim_step_append_ctl: ring stride %lld below a ring's %lld floats", (long long)ring_stride_floats, (long long)(max_size * row_floats)); return RLREP_ERR_ARG;
+    }
+    GROUP_ONLY("group_sim_step_append_ctl")
+    GrpScope grp_scope_(ag);
+    ++g_rl_launches;
+    const int rc = rl_launch_sim_step_ctl_grp((const SimState*)sim, (const unsigned long long*)sim_seeds_dev, act, ld_act, ring_dev, ring_stride_floats, max_size,
+                                              size_dev, (long long*)ctl_dev, (hipStream_t)stream);
+    if (rc) { rl_set_error("group_sim_step_append_ctl: hip error %d", rc); return RLREP_ERR_HIP; }
+    return 0;
+}
 // ---- prioritized replay of a sac seed group (per_group.hip) ---------------------------------------------------------------------
 // trees_dev float32[members, 2P], scal_dev float32[members, 4], idx_dev int32[members, batch], w_dev float32[members, batch]: the buffer group's
 static bool per_group_tree_ok(const char* what, const float* trees, int64_t P, const float* scal, int members) {

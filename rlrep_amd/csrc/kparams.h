@@ -42,6 +42,19 @@ enum { RL_CTL_CALLS = 0,       // the agent's select_action call counter (_ctr)
        RL_CTL_START = 4,       // first ring row of the iteration in flight (what NEXT was when its act launch ran)
        RL_CTL_SIZE = 5,        // the ring's fill level, the iteration in flight included
        RL_CTL_WARM = 6 };      // 1: the iteration in flight is a warm-up one (T < start_timesteps when its act launch ran)
+// The loop record of a GROUP (rlrep_group_act_device_ctl / rlrep_group_replay_add_cols_ctl / rlrep_group_sim_step_append_ctl):
+// int64[members][RL_LOOP_CTL_WORDS], member r's row r * RL_LOOP_CTL_WORDS words behind member 0's.
+//   shared by the group, in ROW 0:   CALLS, T (steps per member: an iteration adds N), ITER, WARM -- one value for all members, as the group's
+//                                    select_action counter is one; they advance whenever at least one member is live
+//   per member, in row r:            NEXT, START, SIZE -- member r's cursor into its own ring (words CALLS, T, ITER, WARM of rows 1.. are unused)
+// Grid y is a slot of the live table (group.h RL_GRP_MEMBER); slot 0 is the first live member and runs whenever anything runs.  The rule of the
+// single record holds per launch:
+//   the act launch     every workgroup reads row 0's CALLS, T, ITER     thread 0 of workgroup (0, slot) writes START, NEXT, SIZE of row
+//                                                                       slot_member[slot]; that of (0, slot 0) also row 0's WARM
+//   the append launch  the workgroups of member m read row m's START    thread 0 of workgroup (0, slot) reads row m's SIZE (published to
+//                                                                       size_dev[m]); that of (0, slot 0) reads row 0's WARM and writes row 0's
+//                                                                       CALLS, T, ITER
+// A retired member's row is neither read nor written: its cursor stands still.
 struct ActCtl {
     long long* ctl; long long capacity, start_timesteps;   // capacity: the ring's rows (>= the launch's rows)
     float eps_greedy;

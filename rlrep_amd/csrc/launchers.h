@@ -73,10 +73,12 @@ int rl_launch_replay_add_grp(float* ring, long long ring_stride, int members, lo
                              long long rows_stride, long long nrows, int* size_dev, int new_size, hipStream_t st);
 int rl_launch_replay_add_cols(const ReplayCols* p, int members, hipStream_t st);  // members == 0: one ring; otherwise grid y = member
 int rl_launch_replay_add_cols_ctl(const ReplayCols* p, long long* ctl, hipStream_t st);     // start and fill level from the loop record (RL_CTL_*)
+int rl_launch_replay_add_cols_ctl_grp(const ReplayCols* p, long long* ctl, hipStream_t st); // an active group: its live members, each from its own row of the record
 // ---- actor_tile.hip ----
 long long rl_actor_tile_lds_bytes(int S, int Ha, int A);
 int rl_launch_actor_tile(const ActTile* p, hipStream_t st);                        // p->rows observations (per member of an active group), 16 per workgroup
 int rl_launch_actor_tile_ctl(const ActTile* p, const ActCtl* k, hipStream_t st);   // one agent; counters from the loop record, exploration mix behind the head
+int rl_launch_actor_tile_ctl_grp(const ActTile* p, const ActCtl* k, hipStream_t st);        // an active group; k->ctl: the group's record, int64[members][8]
 // ---- per.hip (prioritized replay of a single agent: one workgroup each; the weighted sac critic head; sample + slot gather in one launch) ----
 int rl_launch_per_add(const PerAdd* p, hipStream_t st);
 int rl_launch_per_rebuild(float* tree, long long P, hipStream_t st);
@@ -134,6 +136,12 @@ int rl_launch_sim_start(const SimState* s, hipStream_t st);
 int rl_launch_sim_step(const SimState* s, const float* act, long long ld_act, float* next_obs, float* reward, float* done, hipStream_t st);
 int rl_launch_sim_step_ctl(const SimState* s, const float* act, long long ld_act, float* ring, long long capacity, int* size_dev, long long* ctl,
                            hipStream_t st);                                        // + the ring rows and the append launch's one thread (RL_CTL_*)
+// (their group forms: [members, n] planes, member m keyed by seeds[m], grid (ceil(n / 256), y); all need an active group, the steps its live table)
+int rl_launch_sim_start_grp(const SimState* s, const unsigned long long* seeds, hipStream_t st);
+int rl_launch_sim_step_grp(const SimState* s, const unsigned long long* seeds, const float* act, long long ld_act, float* next_obs, float* reward, float* done,
+                           hipStream_t st);
+int rl_launch_sim_step_ctl_grp(const SimState* s, const unsigned long long* seeds, const float* act, long long ld_act, float* ring, long long ring_stride,
+                               long long capacity, int* size_dev, long long* ctl, hipStream_t st);       // the group's loop record: int64[members][8]
 // ---- rowprog.hip / xchain.hip (experiments build); experiments_off.hip (product build: stubs) ----
 int rl_launch_rowprog(const RpLaunch* L, int total_blocks, hipStream_t st);
 int rl_rowprog_init();

@@ -22,6 +22,7 @@
 #include "common.h"
 #include "kparams.h"
 #include "philox.h"
+#include "group.h"
 #include "group_env.h"
 #include "launchers.h"
 
@@ -136,6 +137,81 @@ __global__ __launch_bounds__(256) void sim_step_kernel_ctl(SimState s, const flo
     }
 }
 
+// ---- group forms (include/rlrep.h rlrep_group_sim_*): R x n environments, grid (ceil(n / 256), slot) ----
+// Every array of the state is [members, n] planes (obs [members, n, S]) and member m's start states are keyed by sim_seeds[m]: its plane is the
+// single simulator with that seed, word for word -- sim_step_one and sim_restart run unchanged on a SimState rebased to the plane, so `e` is
+// the environment's index within the member.  s0.seed is ignored.
+template <class Env>
+__device__ __forceinline__ SimState sim_member(const SimState& s0, int m, const unsigned long long* __restrict__ seeds) {
+    SimState s = s0;
+    const long long d = (long long)m * s0.n;
+    s.x0 += d; s.x1 += d; s.ep_return += d; s.last_return += d; s.t += d; s.episodes += d; s.starts += d; s.obs += d * Env::S;
+    s.seed = seeds[m];
+    return s;
+}
+// a reset of the whole group: grid y is the member, the live table is not consulted
+template <class Env>
+__global__ __launch_bounds__(256) void sim_start_kernel_grp(SimState s0, const unsigned long long* __restrict__ seeds) {
+    const SimState s = sim_member<Env>(s0, (int)blockIdx.y, seeds);
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= s.n) return;
+    double x0, x1;
+    sim_restart<Env>(s, e, x0, x1);
+    s.x0[e] = x0; s.x1[e] = x1;
+    float o[Env::S];
+    Env::observe(x0, x1, o);
+#pragma unroll
+    for (int q = 0; q < Env::S; ++q) s.obs[(long long)e * Env::S + q] = o[q];
+}
+// act, next_obs, reward, done: member m's plane lies n rows behind member m - 1's.  A retired member's planes are neither read nor written.
+template <class Env>
+__global__ __launch_bounds__(256) void sim_step_kernel_grp(SimState s0, const unsigned long long* __restrict__ seeds, const int* __restrict__ live,
+                                                           const float* __restrict__ act, long long ld_act, float* __restrict__ next_obs,
+                                                           float* __restrict__ reward, float* __restrict__ done) {
+    RL_GRP_MEMBER(m, live);
+    const SimState s = sim_member<Env>(s0, m, seeds);
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= s.n) return;
+    const long long g = (long long)m * s.n + e;
+    float cur[Env::S], nx[Env::S], r32, d;
+    sim_step_one<Env>(s, e, act[g * ld_act], cur, nx, r32, d);
+#pragma unroll
+    for (int q = 0; q < Env::S; ++q) next_obs[g * Env::S + q] = nx[q];
+    reward[g] = r32; done[g] = d;
+}
+// step-and-append of a group (kparams.h "the loop record of a GROUP"): member m's rows go into its ring (ring + m * ring_stride) from ITS
+// start row; thread 0 of workgroup (0, slot) publishes its fill level, the one of slot 0 advances the group's ITER, T and CALLS once
+template <class Env>
+__global__ __launch_bounds__(256) void sim_step_kernel_ctl_grp(SimState s0, const unsigned long long* __restrict__ seeds, const int* __restrict__ live,
+                                                               const float* __restrict__ act, long long ld_act, float* __restrict__ ring,
+                                                               long long ring_stride, long long capacity, int* __restrict__ size_dev,
+                                                               long long* __restrict__ ctl) {
+    RL_GRP_MEMBER(m, live);
+    const SimState s = sim_member<Env>(s0, m, seeds);
+    const long long* cm = ctl + (long long)m * RL_LOOP_CTL_WORDS;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    long long st = cm[RL_CTL_START];
+    if (st < 0 || st >= capacity) st = 0;                                  // (a cursor written by the host: never leave the ring)
+    if (e < s.n) {
+        const float a = act[((long long)m * s.n + e) * ld_act];
+        float cur[Env::S], nx[Env::S], r32, d;
+        sim_step_one<Env>(s, e, a, cur, nx, r32, d);
+        long long dst = st + e; if (dst >= capacity) dst -= capacity;      // (the launcher holds n <= capacity)
+        float* row = ring + (long long)m * ring_stride + dst * Env::ROW;
+#pragma unroll
+        for (int q = 0; q < Env::S; ++q) { row[q] = cur[q]; row[Env::S + Env::A + q] = nx[q]; }
+        row[Env::S] = a; row[2 * Env::S + Env::A] = r32; row[2 * Env::S + Env::A + 1] = d;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (size_dev) size_dev[m] = (int)min(max(cm[RL_CTL_SIZE], 0ll), capacity);
+        if (blockIdx.y == 0) {
+            ctl[RL_CTL_ITER] += 1;
+            ctl[RL_CTL_T] += s.n;
+            if (!ctl[RL_CTL_WARM]) ctl[RL_CTL_CALLS] += s.n;
+        }
+    }
+}
+
 // ---- launchers: grid ceil(n / 256); the caller (engine.hip rlrep_sim_*) has checked the arguments; an unknown kind is -7 ----
 static inline dim3 sim_grid(const SimState* s) { return dim3((unsigned)((s->n + 255) / 256)); }
 extern "C" int rl_launch_sim_start(const SimState* s, hipStream_t st) {
@@ -162,6 +238,47 @@ extern "C" int rl_launch_sim_step_ctl(const SimState* s, const float* act, long 
     switch (s->kind) {
     case EnvPendulum::KIND: hipLaunchKernelGGL(sim_step_kernel_ctl<EnvPendulum>, sim_grid(s), dim3(256), 0, st, *s, act, ld_act, ring, capacity, size_dev, ctl); break;
     case EnvMountainCar::KIND: hipLaunchKernelGGL(sim_step_kernel_ctl<EnvMountainCar>, sim_grid(s), dim3(256), 0, st, *s, act, ld_act, ring, capacity, size_dev, ctl); break;
+    default: return -7;
+    }
+    return (int)hipGetLastError();
+}
+// the group's: grid (ceil(n / 256), y); the caller (group_api.hip rlrep_group_sim_*) holds the group active and has checked the arguments
+extern "C" int rl_launch_sim_start_grp(const SimState* s, const unsigned long long* seeds, hipStream_t st) {
+    const RlGrp* gr = rl_grp_active();
+    if (!gr) return RL_GRP_UNSUPPORTED;
+    if (s->n < 1 || s->n > RL_SIM_MAX_ENVS) return -7;
+    const dim3 grid(sim_grid(s).x, (unsigned)gr->members);                  // (a reset of every member: not the live table's grid)
+    switch (s->kind) {
+    case EnvPendulum::KIND: hipLaunchKernelGGL(sim_start_kernel_grp<EnvPendulum>, grid, dim3(256), 0, st, *s, seeds); break;
+    case EnvMountainCar::KIND: hipLaunchKernelGGL(sim_start_kernel_grp<EnvMountainCar>, grid, dim3(256), 0, st, *s, seeds); break;
+    default: return -7;
+    }
+    return (int)hipGetLastError();
+}
+extern "C" int rl_launch_sim_step_grp(const SimState* s, const unsigned long long* seeds, const float* act, long long ld_act, float* next_obs, float* reward,
+                                      float* done, hipStream_t st) {
+    const RlGrp* gr = rl_grp_active();
+    if (!gr || !gr->live) return RL_GRP_UNSUPPORTED;
+    if (s->n < 1 || s->n > RL_SIM_MAX_ENVS) return -7;
+    const dim3 grid(sim_grid(s).x, (unsigned)gr->grid_y);
+    switch (s->kind) {
+    case EnvPendulum::KIND: hipLaunchKernelGGL(sim_step_kernel_grp<EnvPendulum>, grid, dim3(256), 0, st, *s, seeds, gr->live, act, ld_act, next_obs, reward, done); break;
+    case EnvMountainCar::KIND: hipLaunchKernelGGL(sim_step_kernel_grp<EnvMountainCar>, grid, dim3(256), 0, st, *s, seeds, gr->live, act, ld_act, next_obs, reward, done); break;
+    default: return -7;
+    }
+    return (int)hipGetLastError();
+}
+extern "C" int rl_launch_sim_step_ctl_grp(const SimState* s, const unsigned long long* seeds, const float* act, long long ld_act, float* ring,
+                                          long long ring_stride, long long capacity, int* size_dev, long long* ctl, hipStream_t st) {
+    const RlGrp* gr = rl_grp_active();
+    if (!gr || !gr->live) return RL_GRP_UNSUPPORTED;
+    if (s->n < 1 || s->n > RL_SIM_MAX_ENVS || capacity < s->n) return -7;
+    const dim3 grid(sim_grid(s).x, (unsigned)gr->grid_y);
+    switch (s->kind) {
+    case EnvPendulum::KIND:
+        hipLaunchKernelGGL(sim_step_kernel_ctl_grp<EnvPendulum>, grid, dim3(256), 0, st, *s, seeds, gr->live, act, ld_act, ring, ring_stride, capacity, size_dev, ctl); break;
+    case EnvMountainCar::KIND:
+        hipLaunchKernelGGL(sim_step_kernel_ctl_grp<EnvMountainCar>, grid, dim3(256), 0, st, *s, seeds, gr->live, act, ld_act, ring, ring_stride, capacity, size_dev, ctl); break;
     default: return -7;
     }
     return (int)hipGetLastError();

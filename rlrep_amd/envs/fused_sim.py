@@ -161,6 +161,123 @@ class FusedMountainCar(FusedSim):
         super().__init__(KIND_MOUNTAIN_CAR_CONTINUOUS, num_envs, device, seed, auto_restart)
 
 
+class FusedSimGroup(object):
+    """R x N environments of `kind_or_env_name` for seed group `group` (include/rlrep.h rlrep_group_sim_*): FusedSim's surface
+    over [R, N] tensors -- `obs` [R, N, S], reset(), step_ / step (actions [R, N, A] -> next_obs [R, N, S], reward [R, N], done [R, N]),
+    step_append_(actions, buffers, ctl), set_state, state().  seeds: R Philox keys of the start states, kept in a device tensor; member r's
+    plane is FusedSim(kind, N, seed=seeds[r]) word for word.  Every launch is ONE launch over grid (ceil(N / 256), R).  reset() restarts the
+    whole group; the steps skip the members the group's live table has retired, whose planes stand still.  The group comes with the
+    constructor or with bind_group() before the first launch (SimLoopGroup binds its own).  A kind compiled at run time (SimKind /
+    CustomFusedSim) has no group form."""
+
+    def __init__(self, kind_or_env_name, members, num_envs, device=None, seeds=None, auto_restart=True, group=None):
+        name = type(self).__name__
+        if isinstance(kind_or_env_name, (SimKind, CustomFusedSim)):
+            raise ValueError(f'{name}: a kind compiled at run time (SimKind / CustomFusedSim) is built for single agents only; a seed group takes '
+                             f'the built-in kinds ({", ".join(v[0] for v in KINDS.values())})')
+        kind = sim_kind(kind_or_env_name)
+        if kind is None:            # (the text of a kind of the user's own ends here too: only CustomFusedSim takes source text)
+            raise ValueError(f'{name}: {str(kind_or_env_name)[:40]!r} is not built for seed groups ({", ".join(f"{k} = {v[0]}" for k, v in KINDS.items())}; '
+                             'kinds compiled at run time are built for single agents only)')
+        R, N = int(members), int(num_envs)
+        if R < 1:
+            raise ValueError(f'{name}: members {members} is below 1')
+        if not 1 <= N <= MAX_ENVS:
+            raise ValueError(f'{name}: num_envs {num_envs} outside [1, {MAX_ENVS}]')
+        seeds = list(range(R)) if seeds is None else [int(s) for s in seeds]
+        if len(seeds) != R:
+            raise ValueError(f'{name}: {len(seeds)} seeds for {R} members (one Philox key per member)')
+        self.kind, self.members, self.num_envs, self.seeds, self.auto_restart = kind, R, N, seeds, bool(auto_restart)
+        self.env_name, self.state_dim, self.action_dim, self._max_episode_steps, self.action_range = KINDS[kind]
+        self.device = dev = torch.device(device if device is not None else 'cuda')
+        if dev.type != 'cuda':
+            raise ValueError(f'{name}: the fused simulators live on the GPU (got device {dev})')
+        f64 = lambda fill=0.0: torch.full((R, N), fill, dtype=torch.float64, device=dev)  # noqa: E731
+        self.x0, self.x1, self.ep_return, self.last_return = f64(), f64(), f64(), f64(float('nan'))
+        self.t = torch.zeros(R, N, dtype=torch.int32, device=dev)
+        self.episodes = torch.zeros(R, N, dtype=torch.int64, device=dev)
+        self.starts = torch.zeros(R, N, dtype=torch.int64, device=dev)
+        self.obs = torch.zeros(R, N, self.state_dim, dtype=torch.float32, device=dev)
+        self.next_obs = torch.zeros(R, N, self.state_dim, dtype=torch.float32, device=dev)
+        self.reward = torch.zeros(R, N, dtype=torch.float32, device=dev)
+        self.done = torch.zeros(R, N, dtype=torch.float32, device=dev)
+        # uint64 keys in an int64 tensor, bit for bit
+        self.seeds_dev = torch.from_numpy(np.array([s & 0xFFFFFFFFFFFFFFFF for s in seeds], np.uint64).view(np.int64).copy()).to(dev)
+        self._st = SimState(kind=kind, n=N, seed=0, auto_restart=int(self.auto_restart), **{k: getattr(self, k).data_ptr() for k in STATE_NAMES})
+        assert C.sizeof(SimState) == lib.rlrep_sim_state_bytes()
+        self.group = None
+        if group is not None:
+            self.bind_group(group)
+
+    def bind_group(self, group):
+        """the seed group whose live table the launches read (R members)"""
+        name = type(self).__name__
+        if getattr(group, 'R', None) is None or not hasattr(group, 'seeds'):
+            raise ValueError(f'{name}: needs a seed group (SACSeedBatch / CTRLSACSeedBatch)')
+        if int(group.R) != self.members:
+            raise ValueError(f'{name}: {self.members} members for a seed group of {group.R}')
+        if self.group is not None and self.group is not group:
+            raise ValueError(f'{name}: the simulator belongs to another group')
+        self.group = group
+
+    def _h(self, what):
+        if self.group is None:
+            raise RuntimeError(f'{type(self).__name__}.{what}: no seed group yet (the launches read its live table): pass group= or call bind_group()')
+        return self.group.core.h
+
+    # ---- launches (stream-ordered, capturable) ----------------------------------------------------------------------------------------------
+    def reset(self):
+        """ONE launch (rlrep_group_sim_start): every environment of EVERY member, retired ones included, begins a new episode from its next
+        start state; returns `obs`"""
+        check(lib.rlrep_group_sim_start(self._h('reset'), C.byref(self._st), _ptr(self.seeds_dev), _stream()), 'group_sim_start')
+        return self.obs
+
+    def _actions(self, actions, what):
+        R, N, A = self.members, self.num_envs, self.action_dim
+        if (not torch.is_tensor(actions) or actions.device != self.obs.device or actions.dtype != torch.float32
+                or tuple(actions.shape) not in ((R, N, A), (R, N)) or not actions.is_contiguous()):
+            raise ValueError(f'{type(self).__name__}.{what}: actions must be a contiguous float32 tensor [{R}, {N}, {A}] on {self.obs.device}')
+        return A
+
+    def step_(self, actions):
+        """ONE launch (rlrep_group_sim_step): actions [R, N, A] float32, raw -> (next_obs [R, N, S], reward [R, N], done [R, N] float32), the
+        simulator's own tensors, written in place; a retired member's planes are neither read nor written"""
+        ld = self._actions(actions, 'step_')
+        check(lib.rlrep_group_sim_step(self._h('step_'), C.byref(self._st), _ptr(self.seeds_dev), _ptr(actions), ld, _ptr(self.next_obs), _ptr(self.reward),
+                                       _ptr(self.done), _stream()), 'group_sim_step')
+        return self.next_obs, self.reward, self.done
+
+    step = step_
+
+    def step_append_(self, actions, buffers, ctl):
+        """ONE launch (rlrep_group_sim_step_append_ctl): the step of every live member, its N transitions into its ring of `buffers` (a
+        ReplayBufferGroup) from its own cursor in the group's loop record `ctl` (int64[R, 8], envs/sim_loop.py SimLoopGroup), its fill level
+        into its size word, the group's counters advanced once.  next_obs / reward / done are NOT written."""
+        ld = self._actions(actions, 'step_append_')
+        if (getattr(buffers, 'members', None) != self.members or (buffers.state_dim, buffers.action_dim) != (self.state_dim, self.action_dim)):
+            raise ValueError(f'{type(self).__name__}.step_append_: needs a ReplayBufferGroup of {self.members} members, {self.state_dim} observations '
+                             f'and {self.action_dim} actions')
+        check(lib.rlrep_group_sim_step_append_ctl(self._h('step_append_'), C.byref(self._st), _ptr(self.seeds_dev), _ptr(actions), ld, _ptr(buffers.rings),
+                                                  buffers.max_size, buffers.row, buffers.ring_stride, _ptr(buffers._size_dev), _ptr(ctl), _stream()),
+              'group_sim_step_append_ctl')
+
+    # ---- tests ----------------------------------------------------------------------------------------------------------------------------
+    def set_state(self, x0, x1, t=0):
+        """tests: continue from the given state words (anything that broadcasts to [R, N]) at step t of the episode; in place.  The
+        observation is the host environment's (NumPy cos / sin, rounded to float32)."""
+        shape = (self.members, self.num_envs)
+        x0, x1 = (np.array(np.broadcast_to(np.asarray(v, np.float64), shape)) for v in (x0, x1))
+        obs = np.stack([np.cos(x0), np.sin(x0), x1] if self.kind == KIND_PENDULUM else [x0, x1], axis=2).astype(np.float32)
+        self.x0.copy_(torch.from_numpy(x0))
+        self.x1.copy_(torch.from_numpy(x1))
+        self.t.copy_(torch.from_numpy(np.array(np.broadcast_to(np.asarray(t, np.int32), shape))))
+        self.obs.copy_(torch.from_numpy(obs))
+
+    def state(self):
+        """dict of host copies of every array (synchronises)"""
+        return {k: getattr(self, k).cpu().numpy() for k in STATE_NAMES}
+
+
 # ---- kinds compiled at run time (include/rlrep.h rlrep_sim_kind_*, rlrep_simx_*; csrc/sim_jit.h) ------------------------------------------------
 MAX_NX, MAX_S, MAX_A = 8, 16, 8                             # include/rlrep.h RLREP_SIMX_MAX_*
 KINDS_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'kinds')

@@ -30,6 +30,8 @@ separate route.  envs/fused_sim.py `FusedSim` is the example (rlrep_sim_step_app
 
 To the replay buffer a SimLoop shows the face of a device environment (`num_envs`, `set_cursor`, `state()` with `ring_ptr` / `ring_size`):
 `ReplayBuffer.collect_on_device` hands it the cursor, `add_device` refuses while it owns it, `adopt_device_cursor` takes it back.
+
+A seed group takes `SimLoopGroup` (below): the same contract with `[R, N, ...]` tensors, one record row per member.
 """
 import ctypes as C
 
@@ -57,32 +59,44 @@ class SimLoop(object):
 
     def __init__(self, agent, sim, eps_greedy=0.0, start_timesteps=0, fused_append=True):
         name = type(self).__name__
-        if getattr(agent, 'R', None) is not None or not hasattr(agent, '_seed'):
-            raise ValueError(f'{name}: needs a single agent (seed groups have act_device / add_device as an API only)')
+        self._lead = lead = self._check_agent(agent)    # the axes in front of [N, S]: () for one agent, (R,) for a seed group
         obs = getattr(sim, 'obs', None)
         S, A = agent.state_dim, agent.action_dim
-        if (not torch.is_tensor(obs) or not obs.is_cuda or obs.dtype != torch.float32 or obs.dim() != 2 or obs.shape[1] != S
-                or not 1 <= obs.shape[0] <= ACT_MAX_ROWS or not obs.is_contiguous()):
-            raise ValueError(f'{name}: sim.obs must be a contiguous CUDA float32 tensor [N, {S}] with N in [1, {ACT_MAX_ROWS}]')
+        if (not torch.is_tensor(obs) or not obs.is_cuda or obs.dtype != torch.float32 or obs.dim() != len(lead) + 2 or obs.shape[-1] != S
+                or tuple(obs.shape[:-2]) != lead or not 1 <= obs.shape[-2] <= ACT_MAX_ROWS or not obs.is_contiguous()):
+            shape = ', '.join([str(n) for n in lead] + ['N', str(S)])
+            raise ValueError(f'{name}: sim.obs must be a contiguous CUDA float32 tensor [{shape}] with N in [1, {ACT_MAX_ROWS}]')
         if not callable(getattr(sim, 'step_', None)):
             raise ValueError(f'{name}: the simulator needs step_(actions) -> (next_obs, reward, done), capture-safe (see the module docstring)')
         self.agent, self.sim = agent, sim
+        if not lead:
+            self.seed = int(agent._seed)                # the Philox key of the mix: what the agent's select_action draws with
         self.fused_append = bool(fused_append) and callable(getattr(sim, 'step_append_', None))
-        self.num_envs = N = int(obs.shape[0])
+        self.num_envs = N = int(obs.shape[-2])
         self.eps_greedy, self.start_timesteps = float(eps_greedy), int(start_timesteps)
         if not 0.0 <= self.eps_greedy <= 1.0:
             raise ValueError(f'{name}: eps_greedy {eps_greedy} outside [0, 1]')
         if self.start_timesteps < 0 or self.start_timesteps % N:
             raise ValueError(f'{name}: start_timesteps {start_timesteps} is not a multiple of the {N} environments (an iteration is all warm-up or none of it)')
-        self.seed = int(agent._seed)                    # the Philox key of the mix: what the agent's select_action draws with
         dev = obs.device
-        self.ctl = torch.zeros(LOOP_CTL_WORDS, dtype=torch.int64, device=dev)
-        self.obs0 = torch.empty(N, S, dtype=torch.float32, device=dev)           # the observations the iteration acted on (the ring's s column)
-        self.actions = torch.empty(N, A, dtype=torch.float32, device=dev)
+        self.ctl = torch.zeros(*lead, LOOP_CTL_WORDS, dtype=torch.int64, device=dev)
+        self.obs0 = torch.empty(*lead, N, S, dtype=torch.float32, device=dev)    # the observations the iteration acted on (the ring's s column)
+        self.actions = torch.empty(*lead, N, A, dtype=torch.float32, device=dev)
         self.t_global, self.calls, self.iter = 0, 0, 0          # host mirrors of the record (iterate_sim keeps them in step)
         self._held = None                               # what the last captured step returned (the graph's pool owns the memory)
 
+    def _check_agent(self, agent):
+        """the axes in front of [N, S] for `agent`, or ValueError"""
+        if getattr(agent, 'R', None) is not None or not hasattr(agent, '_seed'):
+            raise ValueError(f'{type(self).__name__}: needs a single agent (a seed group takes SimLoopGroup; its act_device / add_device are the eager API)')
+        return ()
+
     # ---- the record -----------------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _shared(w):
+        """the words CALLS, T, ITER and WARM of a host copy of the record (a view)"""
+        return w
+
     def _read(self):
         return self.ctl.cpu().numpy()                   # (synchronises)
 
@@ -107,16 +121,17 @@ class SimLoop(object):
 
     def counters(self):
         """(t_global, calls, iter) as the device holds them (synchronises)"""
-        w = self._read()
+        w = self._shared(self._read())
         return int(w[T_GLOBAL]), int(w[CALLS]), int(w[ITER])
 
     def set_counters(self, t_global, calls, iteration=None):
         """environment steps taken and the select_action call counter the next iteration continues from (and the iteration, the counter of
         the mix's draws, when given)"""
         w = self._read()
-        w[T_GLOBAL], w[CALLS] = int(t_global), int(calls)
+        sh = self._shared(w)
+        sh[T_GLOBAL], sh[CALLS] = int(t_global), int(calls)
         if iteration is not None:
-            w[ITER] = int(iteration)
+            sh[ITER] = int(iteration)
             self.iter = int(iteration)
         self._write(w)
         self.t_global, self.calls = int(t_global), int(calls)
@@ -143,7 +158,7 @@ class SimLoop(object):
         """One iteration without the train(): copy of the observations, act launch, `sim.step_`, append launch -- stream-ordered on the
         current stream, nothing read on the host (what iterate_sim captures).  With the simulator's `step_append_` hook: the act launch
         directly on `sim.obs`, then the hook -- two launches."""
-        N, S = self.num_envs, buffer.state_dim
+        N, S, lead = self.num_envs, buffer.state_dim, self._lead
         if self.fused_append:
             self.act(self.sim.obs, self.actions, buffer.max_size)
             self.sim.step_append_(self.actions, buffer, self.ctl)
@@ -154,10 +169,10 @@ class SimLoop(object):
 
         def prep(t, shape, name):
             if not torch.is_tensor(t) or t.device != self.obs0.device or tuple(t.shape) not in (shape, shape + (1,)):
-                raise ValueError(f'SimLoop: step_ returned {name} that is not a tensor {list(shape)} on {self.obs0.device}')
+                raise ValueError(f'{type(self).__name__}: step_ returned {name} that is not a tensor {list(shape)} on {self.obs0.device}')
             t = t if t.dtype == torch.float32 else t.to(torch.float32)
             return t.reshape(shape).contiguous()
-        nxt, rew, done = prep(nxt, (N, S), 'next_obs'), prep(rew, (N,), 'reward'), prep(done, (N,), 'done')
+        nxt, rew, done = prep(nxt, lead + (N, S), 'next_obs'), prep(rew, lead + (N,), 'reward'), prep(done, lead + (N,), 'done')
         self.append(buffer, self.obs0, self.actions, nxt, rew, done)
         self._held = (nxt, rew, done)
 
@@ -167,3 +182,67 @@ class SimLoop(object):
         self.t_global += self.num_envs
         self.iter += 1
         return warm
+
+
+class SimLoopGroup(SimLoop):
+    """SimLoop for a seed group (SACSeedBatch / CTRLSACSeedBatch): `sim.obs` is [R, N, S], `sim.step_(actions [R, N, A])`
+    returns next_obs [R, N, S], reward [R, N], done [R, N], and `SeedBatchMixin.iterate_sim(loop, buffers, batch_size)` replays the whole
+    iteration of every live member as one graph.  envs/fused_sim.py `FusedSimGroup` is the simulator it was built for.
+
+    The record is int64[R, LOOP_CTL_WORDS] (csrc/kparams.h, "the loop record of a group").  CALLS, T, ITER and WARM are the GROUP's, kept in
+    row 0 -- one call counter, one step count per member (an iteration adds N), one iteration count, as the group's `_ctr` is one -- and
+    advance while at least one member is live.  NEXT, START and SIZE are member r's cursor into its own ring, in row r.  The two launches
+    honour the live table: a retired member's cursor, ring, fill level and simulator planes stand still, so a revived member writes on where
+    it stopped.  Member r's exploration mix is keyed by seeds[r]."""
+
+    def _check_agent(self, agent):
+        if getattr(agent, 'R', None) is None or not hasattr(agent, 'seeds'):
+            raise ValueError(f'{type(self).__name__}: needs a seed group (SACSeedBatch / CTRLSACSeedBatch); a single agent takes SimLoop')
+        return (int(agent.R),)
+
+    def __init__(self, group, sim, eps_greedy=0.0, start_timesteps=0, fused_append=True):
+        super().__init__(group, sim, eps_greedy, start_timesteps, fused_append)
+        self.R = int(group.R)
+        self.seeds = [int(s) for s in group.seeds]      # the Philox keys of the members' mixes (the library holds them: rlrep_group_set_seeds)
+        self.actions.zero_()                            # (a retired member's plane is never written)
+        if callable(getattr(sim, 'bind_group', None)):
+            sim.bind_group(group)               # (the simulator's launches read the group's live table)
+
+    @staticmethod
+    def _shared(w):
+        return w[0]
+
+    def state(self):
+        """[R] records (STATE_DTYPE): member r's next free ring row and fill level, and the group's counters in every record; a host copy:
+        synchronises"""
+        w = self._read()
+        rec = np.zeros(self.R, STATE_DTYPE)
+        rec['ring_ptr'], rec['ring_size'], rec['start'] = w[:, NEXT_PTR], w[:, SIZE], w[:, START]
+        rec['t_global'], rec['calls'], rec['iter'] = w[0, T_GLOBAL], w[0, CALLS], w[0, ITER]
+        return rec
+
+    def set_cursor(self, ptr, sizes, capacity=None):
+        """every member's next free row (the host rings advance in lockstep) and its own fill level (ReplayBufferGroup.collect_on_device)"""
+        sizes = np.asarray(sizes, np.int64).reshape(-1)
+        if sizes.size != self.R:
+            raise ValueError(f'{type(self).__name__}.set_cursor: {sizes.size} fill levels for {self.R} members')
+        w = self._read()
+        w[:, NEXT_PTR] = int(ptr) % int(capacity) if capacity else int(ptr)
+        w[:, START] = w[:, NEXT_PTR]
+        w[:, SIZE] = sizes
+        self._write(w)
+
+    def act(self, obs, out, capacity):
+        """ONE launch (rlrep_group_act_device_ctl): plane r of `out` [R, N, A] is what SimLoop.act gives the standalone agent with seed
+        seeds[r] at the group's counters; every live member's cursor moves by N rows in its ring of `capacity` rows"""
+        lo, hi = self.agent.action_range
+        check(lib.rlrep_group_act_device_ctl(self.agent.core.h, _ptr(obs), self.num_envs, float(lo), float(hi), _ptr(out), _ptr(self.ctl), int(capacity),
+                                             self.eps_greedy, self.start_timesteps, _stream()), 'group_act_device_ctl')
+
+    def append(self, buffers, s, a, s2, r, d):
+        """ONE launch (rlrep_group_replay_add_cols_ctl): every live member's N transitions (plane r of the five contiguous arrays) into its
+        ring from its own start row, its fill level into its size word, the group's counters advanced once"""
+        N, S, A = self.num_envs, buffers.state_dim, buffers.action_dim
+        check(lib.rlrep_group_replay_add_cols_ctl(self.agent.core.h, _ptr(buffers.rings), buffers.max_size, buffers.row, S, A, _ptr(s), S, _ptr(a), A, _ptr(s2), S,
+                                                  _ptr(r), _ptr(d), N, buffers.ring_stride, _ptr(buffers._size_dev), _ptr(self.ctl), _stream()),
+              'group_replay_add_cols_ctl')

@@ -65,6 +65,10 @@ are captured together.  Evaluations are the eager ones of --torch-envs.
 one (envs/fused_sim.py `FusedSim`, csrc/sim_step.hip): the act launch reads the simulator's observations in place and ONE launch steps the N
 environments and appends their transitions, so the graph holds two launches in front of train().  Episodes end and restart per environment
 on the device; evaluations step a FusedSim(auto_restart=False) of their own, one act_device and one step launch per step.
+With --seeds / --sweep (sac, ctrlsac) all three flags together run the loop for the whole seed group (`SeedBatchMixin.iterate_sim`,
+`SimLoopGroup`, `FusedSimGroup`): N environments per member, --start_timesteps counted per member, one graph replay per
+iteration for all members, one mean return per member at an evaluation.  Not with --pbt-interval / --halving-interval, --group-per /
+--group-critic-per, --device-env, --host-envs, --num-envs or --fused-sim-source.
 `--fused-sim-source PATH` (only with all three of --torch-envs N --sim-graph --fused-sim) makes that simulator a kind of your own: PATH holds
 the C++ text of one struct (csrc/sim_jit.h; rlrep_amd/envs/kinds/ has two examples), compiled at run time (`CustomFusedSim`, DESIGN.md
 6i.2); the agent is built from the kind's S and A, and --env only names the log directory.
@@ -540,6 +544,12 @@ def _host_envs_loop(args, agent, replay, ev):
     return agent, ev.evaluations
 
 
+def _torch_envs_group(args):
+    """--seeds / --sweep with --torch-envs N --sim-graph --fused-sim: the one-graph simulator loop of a seed group (_fused_sim_group_loop)"""
+    return bool((getattr(args, 'seeds', None) is not None or getattr(args, 'sweep', None)) and int(getattr(args, 'torch_envs', 0) or 0)
+                and getattr(args, 'sim_graph', False) and getattr(args, 'fused_sim', False))
+
+
 def _check_torch_envs(args):
     """--torch-envs: SystemExit, before anything touches the GPU, on what it does not run with"""
     N = int(args.torch_envs)
@@ -547,11 +557,22 @@ def _check_torch_envs(args):
         return
     if not 1 <= N <= 65536:
         raise SystemExit(f'--torch-envs {N}: outside [1, 65536]')
-    for flag, given in (('--seeds', args.seeds is not None), ('--sweep', bool(args.sweep)), ('--device-env', args.device_env),
+    # a seed group runs the fused one-graph loop only (--sim-graph --fused-sim: SeedBatchMixin.iterate_sim); the newer attributes are read
+    # with getattr, for callers that build the Namespace themselves
+    group = _torch_envs_group(args)
+    for flag, given in (('--seeds', args.seeds is not None and not group), ('--sweep', bool(args.sweep) and not group), ('--device-env', args.device_env),
                         ('--device-loop', args.device_loop), ('--host-envs', args.host_envs > 1), ('--num-envs', args.num_envs > 1)):
         if given:
-            raise SystemExit(f'--torch-envs {N}: the torch simulator loop runs ONE agent and does not go with {flag} (seed groups have '
-                             'act_device / add_device as an API only)')
+            raise SystemExit(f'--torch-envs {N}: the torch simulator loop runs ONE agent and does not go with {flag} (a seed group takes '
+                             '--torch-envs N --sim-graph --fused-sim, the fused one-graph loop, and none of the other collection flags)')
+    if group:
+        for flag, given in (('--pbt-interval', hasattr(args, 'pbt_interval') and _pbt_requested(args)),
+                            ('--halving-interval', hasattr(args, 'halving_interval') and _halving_requested(args)),
+                            ('--group-per', bool(getattr(args, 'group_per', False))), ('--group-critic-per', bool(getattr(args, 'group_critic_per', False))),
+                            ('--fused-sim-source', bool(getattr(args, 'fused_sim_source', None)))):
+            if given:
+                raise SystemExit(f'--torch-envs {N}: the one-graph simulator loop of a seed group (--seeds / --sweep with --sim-graph --fused-sim) does '
+                                 f'not go with {flag}')
     if not args.env.startswith('Pendulum') and not getattr(args, 'fused_sim', False):         # (--fused-sim has checked --env against its own kinds)
         raise SystemExit(f'--torch-envs {N}: the example simulator is Pendulum-v1 (got --env {args.env})')
     _check_multiple('--torch-envs', N, args, f'an iteration takes {N} environment steps at once')
@@ -1116,6 +1137,8 @@ def run_seeds(args):
         return _device_loop(args, agent, replay, ev)
     if args.host_envs > 1:
         return _host_envs_group_loop(args, agent, replay, ev, seeds)
+    if _torch_envs_group(args):
+        return _fused_sim_group_loop(args, agent, replay, ev, seeds)
     policies = [_MemberPolicy(agent, r) for r in range(R)]
 
     def evaluate():
@@ -1218,6 +1241,49 @@ def _host_envs_group_loop(args, agent, replay, ev, seeds):
         if not warm:
             infos = agent.train(replay, batch_size=args.batch_size)
         t = t0 + E
+        if t % args.eval_freq == 0:
+            ev.step(t, evaluate, infos)
+    ev.close()
+    return agent, ev.evaluations
+
+
+def _fused_sim_group_loop(args, agent, replay, ev, seeds):
+    """run_seeds' loop with --torch-envs N --sim-graph --fused-sim: N fused environments per member (envs/fused_sim.py FusedSimGroup, member
+    r's start states keyed by its seed), an iteration is ONE `iterate_sim` graph replay of every member -- the act launch with the exploration
+    mix, the step-and-append launch, train().  --start_timesteps counts steps per member.  An evaluation steps min(N, --eval_episodes)
+    environments per member on a FusedSimGroup(auto_restart=False) with the group's act_device(explore=False) and reports one mean return per
+    member from last_return; none is made before the first step, as in the single agent's loop.  (No member retires here: --pbt-interval and
+    --halving-interval are refused with --torch-envs.)"""
+    from rlrep_amd.envs.fused_sim import FusedSimGroup
+    from rlrep_amd.envs.sim_loop import SimLoopGroup
+    R, N, dev, episodes = agent.R, int(args.torch_envs), replay.device, int(args.eval_episodes)
+    n_eval = min(N, episodes)
+    env = FusedSimGroup(args.env, R, N, dev, seeds=seeds, group=agent)
+    eval_env = FusedSimGroup(args.env, R, n_eval, dev, seeds=[s + 100 for s in seeds], auto_restart=False, group=agent)
+    env.reset()
+    loop = SimLoopGroup(agent, env, eps_greedy=EPS_GREEDY, start_timesteps=int(args.start_timesteps))
+    act = torch.zeros(R, n_eval, env.action_dim, dtype=torch.float32, device=dev)
+
+    def evaluate():
+        returns = [[] for _ in range(R)]
+        while len(returns[0]) < episodes:               # every round resets first, so it draws fresh start states
+            eval_env.reset()
+            for _ in range(eval_env._max_episode_steps):
+                eval_env.step_(agent.act_device(eval_env.obs, explore=False, out=act))
+            for r, row in enumerate(eval_env.last_return.cpu().tolist()):
+                returns[r].extend(row)
+        finished = int(env.episodes.sum())
+        if finished:
+            print(f'Total T: {loop.t_global} Episode Num: {finished} Mean reward: {float(torch.nanmean(env.last_return)):.3f}')
+        return [float(np.mean(returns[r][:episodes])) for r in range(R)]
+
+    ev.evaluations = [[] for _ in range(R)]
+    infos = None
+    ev.timer = util.Timer()
+    for t0 in range(0, int(args.max_timesteps), N):             # one iteration is N environment steps of every member
+        out = agent.iterate_sim(loop, replay, args.batch_size, train=t0 >= args.start_timesteps)
+        infos = out if out is not None else infos
+        t = t0 + N
         if t % args.eval_freq == 0:
             ev.step(t, evaluate, infos)
     ev.close()
